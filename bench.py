@@ -30,9 +30,9 @@ A cfg2 run also carries a "cfg3" block: rows strong scaling of configs[2] (16-fr
 4096x4096) with its N = 1 time measured in the same run (by rank 0 alone when N > 1), so
 that the N = 1 / 2 / 4 / 8 curve contains a configuration large enough to scale.
 
-Timing: W untimed warm-up steps, then K timed steps between barriers, max over
-ranks.  A timed region shorter than --min-timed-ms (50 ms) is extended to whole
-multiples of K steps (config.timed_steps); before the warm-up the GPU is driven
+Timing: W untimed warm-up steps, then exactly K timed steps between barriers, max
+over ranks.  --min-timed-ms T (opt-in, default off) extends a timed region shorter
+than T to whole multiples of K steps (config.timed_steps); before the warm-up the GPU is driven
 for --clock-ramp-ms of untimed evaluations (an MI355X reaches its sustained
 clocks only after ~50 ms of load).
 
@@ -42,6 +42,11 @@ Prints ONE JSON line on rank 0 (see the task contract), including
   "cpu_baseline": the CPU oracle (a port of the reference, oracle/) timed on this
                   host on a bounded sample of the same workload: 1 core (the
                   reference is single-threaded) and all cores.
+
+--dump-outputs DIR: after the timed steps, the HR gradient the timed path returned in
+its last step is written as DIR/grad.npy (the evaluation's dtype; a fixed, seeded
+sample of DUMP_MAX_ELEMENTS values when the full gradient is larger).  The inputs
+are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -57,6 +62,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "super-resolution_amd", "python"))
 
+DUMP_MAX_ELEMENTS = 1 << 22  # --dump-outputs: at most 32 MB of f64
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 CONFIGS = {
@@ -205,14 +211,39 @@ def free_port():
     return p
 
 
+def dump_outputs(out_dir, res, shard, dist, rank):
+    """--dump-outputs: rank 0 writes the full HR gradient (C, H, W) of the last timed step as out_dir/grad.npy.  Rows:
+    every rank contributes the rows it owns; channels: its channel; frames: the gradient is all-reduced, rank 0's is it.
+    Larger than DUMP_MAX_ELEMENTS: a fixed sample (seed 0, sorted flat indices of the full array)."""
+    g = res["grad"].cpu().numpy()
+    if shard == "rows":
+        o0, o1 = res["own_rows"]
+        g = g[:, o0:o1, :]
+    if dist is not None and shard in ("rows", "channels"):
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, g)  # gloo, host memory
+        g = np.concatenate(parts, axis=1 if shard == "rows" else 0)
+    if rank != 0:
+        return
+    g = np.ascontiguousarray(g)
+    if g.size > DUMP_MAX_ELEMENTS:
+        idx = np.sort(np.random.default_rng(0).choice(g.size, DUMP_MAX_ELEMENTS, replace=False))
+        g = g.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "grad.npy"), g)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="a timed region shorter than this is extended to whole multiples of --steps")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="opt-in: a timed region shorter than this is extended to whole multiples of --steps "
+                         "(default 0: exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the gradient of the last timed step of the main workload to DIR/grad.npy")
     ap.add_argument("--clock-ramp-ms", type=float, default=100.0,
                     help="untimed evaluations for this many milliseconds BEFORE the W warm-up steps: the GPU reaches its "
                          "sustained clocks only after ~50 ms of load; 0 disables")
@@ -412,10 +443,12 @@ def main():
         xs = [torch.from_numpy(x0).to(dev, r_tdtype).contiguous() for _ in range(n_problems)]
         gs = [torch.empty_like(x) for x in xs]
         turn = [0]
+        last = [0]  # problem of the most recent step: its gradient is what that step returned
 
         def step():
             i = turn[0]
             turn[0] = (i + 1) % n_problems
+            last[0] = i
             if sd is not None:
                 prob.eval_sharded_device(comm, sd, xs[0].data_ptr(), gs[0].data_ptr(), terms, want_cost=False, stream=sh)
             else:
@@ -478,7 +511,7 @@ def main():
         if only_rank0:  # the waiting ranks sit in four barriers
             barrier(); barrier(); barrier(); barrier()
         return dict(wall_per_step=wall / n_timed, dev_ms_per_step=dev_ms / n_timed, timed_steps=n_timed,
-                    ramp_steps=ramp_steps, lr=lr, x0=x0, wts=wts)
+                    ramp_steps=ramp_steps, lr=lr, x0=x0, wts=wts, grad=gs[last[0]], own_rows=(r0 - e0, r1 - e0))
 
     def b_alg_of(cfg, c_unit):
         N, n = cfg["hr"] * cfg["hr"], (cfg["hr"] // cfg["s"]) ** 2
@@ -495,6 +528,10 @@ def main():
     else:
         main_shard, res = "rows", run(cfg, "rows", args.steps, args.warmup)
         second = run(cfg, "frames", args.steps, args.warmup)
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, main_shard, dist, rank)
+        res["grad"] = None
 
     # ---- HBM-fed leg (N = 1): the same evaluation over three independent problems in rotation ----
     hbm_fed = None

@@ -1,7 +1,7 @@
 """The oracle's nonlinear-CG restatement (sro_mincg) against trajectories of the
 reference's vendored ALGLIB 3.10.0 (tests/golden/cg_trajectories.json, made by
-tests/golden/make_cg_trajectories.py) and, when oracle/_ref is present, against
-ALGLIB live."""
+tests/golden/make_cg_trajectories.py): recorded, and live as well when oracle/_ref
+is present."""
 import json
 import os
 
@@ -55,45 +55,65 @@ def test_tv_toy_trajectory(traj):
     assert np.allclose(x, T["x"], rtol=1e-9, atol=1e-12)
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref/libalglib_ref.so not built")
+def _rosen_like(A, b):
+    """Non-quadratic, exercises the bracketing cases.  Elementwise numpy only (no BLAS): the same bits on every host,
+    as in tests/golden/make_cg_trajectories.py, which recorded ALGLIB on it."""
+    def fun(v):
+        Av = (A * v).sum(axis=1)
+        return 0.5 * (v * Av).sum() - (b * v).sum() + 0.1 * (v * v * v * v).sum(), Av - b + 0.4 * (v * v * v)
+    return fun
+
+
+def _alglib_results(recorded, run):
+    """ALGLIB's answers: the recorded ones (tests/golden, made by the reference's vendored ALGLIB) and, when
+    oracle/_ref is built, the live ones of this process."""
+    out = [("recorded", recorded)]
+    if orc.have_ref():
+        out.append(("live", run()))
+    return out
+
+
 def test_live_alglib_bit_exact(traj):
-    """Restatement vs the real ALGLIB on the same objective, same process:
-    identical iterates (bit for bit)."""
-    rng = np.random.default_rng(3)
-    B = rng.standard_normal((24, 24))
-    A = B @ B.T + np.eye(24)
-    b = rng.standard_normal(24)
-
-    def rosen_like(v):  # non-quadratic, exercises the bracketing cases
-        f = 0.5 * v @ A @ v - b @ v + 0.1 * np.sum(v ** 4)
-        return f, A @ v - b + 0.4 * v ** 3
-
-    for fun, x0 in ((rosen_like, rng.standard_normal(24) * 3),
-                    (lambda v: _toy(traj["tv_toy_8x8"]).objective(v), rng.random(64))):
-        ta, tb = [], []
+    """Restatement vs the real ALGLIB on the same objective: identical iterates (bit for bit)."""
+    L = traj["alglib_live"]
+    R = L["rosen_like"]
+    cases = ((_rosen_like(np.array(R["A"]), np.array(R["b"])), np.array(R["x0"]), R),
+             (lambda v: _toy(traj["tv_toy_8x8"]).objective(v), np.array(L["tv_toy_8x8"]["x0"]), L["tv_toy_8x8"]))
+    for fun, x0, rec in cases:
+        ta = []
         xa, ra = orc.mincg(fun, x0, trace=ta, maxits=40)
-        xb, rb = orc.mincg(fun, x0, trace=tb, maxits=40, use_alglib=True)
-        assert (ra.iterations, ra.nfev, ra.termination_type) == (rb.iterations, rb.nfev, rb.termination_type)
-        assert np.array_equal(xa, xb)
-        assert [t[1] for t in ta] == [t[1] for t in tb]
-        assert ra.f == rb.f
+
+        def run():
+            tb = []
+            xb, rb = orc.mincg(fun, x0, trace=tb, maxits=40, use_alglib=True)
+            return {"x": xb.tolist(), "trace_f": [t[1] for t in tb], "iterations": rb.iterations, "nfev": rb.nfev,
+                    "termination_type": rb.termination_type, "f": rb.f}
+
+        for how, b in _alglib_results(rec, run):
+            assert (ra.iterations, ra.nfev, ra.termination_type) == (b["iterations"], b["nfev"], b["termination_type"]), how
+            assert np.array_equal(xa, np.array(b["x"])), how
+            assert [t[1] for t in ta] == b["trace_f"], how
+            assert ra.f == b["f"], how
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref/libalglib_ref.so not built")
-def test_irls_solve_with_alglib_matches(literals):
+def test_irls_solve_with_alglib_matches(traj):
     """IRLS loop driven by the real ALGLIB == driven by the restatement."""
     rng = np.random.default_rng(5)
     gt = rng.random((2, 12, 12))
     shifts = [[0, 0], [1, 0], [0, 1], [1, 1], [2, 1]]
     model = orc.ImageModel(scale=3, shifts=shifts, blur_ksize=3, blur_sigma=1.0)
     lr = np.stack([model.apply(gt, k) for k in range(5)])
-    outs = []
-    for use in (False, True):
+
+    def solve(use):
         prob = orc.Problem(model, lr)
         prob.add_regularizer(orc.REG_BTV, 0.01, btv_range=3, btv_decay=0.5)
         opts = orc.default_irls_options()
         opts.max_num_irls_iterations = 3
         x, rep = prob.solve(np.full((2, 12, 12), 0.5), opts, use_alglib=use)
-        outs.append((x, rep.cg_iterations, rep.nfev, rep.final_cost))
-    assert outs[0][1:] == outs[1][1:]
-    assert np.array_equal(outs[0][0], outs[1][0])
+        return {"x": x.ravel().tolist(), "cg_iterations": rep.cg_iterations, "nfev": rep.nfev,
+                "final_cost": rep.final_cost}
+
+    a = solve(False)
+    for how, b in _alglib_results(traj["alglib_live"]["irls_btv_12x12"], lambda: solve(True)):
+        assert (a["cg_iterations"], a["nfev"], a["final_cost"]) == (b["cg_iterations"], b["nfev"], b["final_cost"]), how
+        assert np.array_equal(np.array(a["x"]), np.array(b["x"])), how
