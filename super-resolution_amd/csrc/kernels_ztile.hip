@@ -51,89 +51,24 @@
 // (deterministic).
 
 
-#include "ztile_dev.hpp"
-#ifndef SRMAP_EXP_XT
-#define SRMAP_EXP_XT 1
-#endif
+#include <type_traits>
 
-// Build-time switch of the measurement builds (tools/exp_build.sh); the product build does not define it.
-//   SRMAP_ZT_ONLY_CFG2  instantiate only k_eval_z<double, 4, 3, BTV, 3> (seconds instead of minutes per variant)
-//   SRMAP_EXP_NOLOAD    TIMING ONLY (results wrong by construction): every global load of a tile workgroup replaced by a
-//                       value formed in registers -- the time no prefetch scheme can beat (profiles/r05_ceiling.txt)
-//   SRMAP_EXP_NOHALO    TIMING ONLY: no halo-row / halo-column passes (what a marching band saves at best)
-//   SRMAP_ZT_ONLY_T     with SRMAP_ZT_ONLY_CFG2: the arithmetic type of that one instance (default double)
-//   SRMAP_EXP_F32_WPE   f32 instances: waves per SIMD the register budget is set for (product: 6 = 80 VGPRs)
-#ifndef SRMAP_ZT_ONLY_T
-#define SRMAP_ZT_ONLY_T double
-#endif
-//   SRMAP_ZT_ONLY_B     with SRMAP_ZT_ONLY_CFG2: the blur size of that one instance (default 3; 1 = the cfg3 / cfg5 instance)
-#ifndef SRMAP_ZT_ONLY_B
-#define SRMAP_ZT_ONLY_B 3
-#endif
-#ifndef SRMAP_EXP_F32_WPE
-#define SRMAP_EXP_F32_WPE 6
-#endif
-//   SRMAP_EXP_SPOLD     sub-pixel instances: the entry-major tap table of rounds 2-4 (one request per pixel and tap)
-//                       instead of the source-major one (z_row_sp2)
-#ifndef SRMAP_EXP_SPOLD
-#define SRMAP_EXP_SPOLD 0
-#endif
-//   SRMAP_EXP_F64_WPE   f64 S > 2 instances: waves per SIMD of __launch_bounds__ (product: 4)
-//   SRMAP_EXP_ALIAS_ZC  TIMING ONLY: zh and 2*lambda*w*r share one LDS array (what a three-phase tile would allocate)
-#ifndef SRMAP_EXP_F64_WPE
-#define SRMAP_EXP_F64_WPE 4
-#endif
-#ifndef SRMAP_EXP_ALIAS_ZC
-#define SRMAP_EXP_ALIAS_ZC 0
-#endif
-//   SRMAP_EXP_LDS_PAD   TIMING ONLY: extra bytes of (dynamic) LDS per workgroup (fewer resident workgroups, same instruction stream)
-#ifndef SRMAP_EXP_LDS_PAD
-#define SRMAP_EXP_LDS_PAD 0
-#endif
-//   SRMAP_EXP_REGFIRST  phase 1: regulariser pass before the data term (the observations get a pass longer to arrive)
-//   SRMAP_EXP_NTLOAD    observations and IRLS weights requested with non-temporal loads (streamed once)
-//   SRMAP_EXP_HEADPRIO  s_setprio 3 from the start of a tile workgroup until its requests are issued
-#ifndef SRMAP_EXP_REGFIRST
-#define SRMAP_EXP_REGFIRST 0
-#endif
-#ifndef SRMAP_EXP_NTLOAD
-#define SRMAP_EXP_NTLOAD 0
-#endif
-#ifndef SRMAP_EXP_HEADPRIO
-#define SRMAP_EXP_HEADPRIO 0
-#endif
-#ifndef SRMAP_EXP_NOLOAD
-#define SRMAP_EXP_NOLOAD 0
-#endif
-#ifndef SRMAP_EXP_NOHALO
-#define SRMAP_EXP_NOHALO 0
-#endif
-// The TIMING-ONLY switches produce wrong results by construction: a build that sets one has to say that it is a
-// measurement build (tools/exp_build.sh, tools/full_build.sh and tools/phase_clock/build.sh define it; the product build does not).
-#if (SRMAP_EXP_NOLOAD || SRMAP_EXP_NOHALO || SRMAP_EXP_ALIAS_ZC || SRMAP_EXP_LDS_PAD || defined(SRMAP_EXP_SPNOLOAD)) && !defined(SRMAP_MEASUREMENT_BUILD)
-#error "SRMAP_EXP_NOLOAD / NOHALO / ALIAS_ZC / LDS_PAD / SPNOLOAD are timing-only switches: define SRMAP_MEASUREMENT_BUILD (tools/exp_build.sh)"
-#endif
+#include "ztile_dev.hpp"
 
 namespace srmap {
 
 namespace {
 
 template <typename T, int S, int B, int REGK, int R, bool WD, bool SP>
-__global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRMAP_EXP_F32_WPE : (S == 2 ? 6 : SRMAP_EXP_F64_WPE))) void k_eval_z(
+__global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 || S == 2 ? 6 : 4)) void k_eval_z(
     ZArgs<T, B, ZCfg<T, S, B, REGK, R>::NP> A) {
   using C = ZCfg<T, S, B, REGK, R>;
   constexpr int HB = C::HB, NV = C::NV, RU = C::RU;
   // border blocks borrow the x tile's LDS for the frame table
   constexpr int kBorderLds = (int)((16 * sizeof(int2) + kBorderTabEntries * sizeof(ZEntry) + 16 * sizeof(double) + sizeof(T) - 1) / sizeof(T));
   __shared__ T xs[C::XS_ELEMS > kBorderLds ? C::XS_ELEMS : kBorderLds];
-#if SRMAP_EXP_ALIAS_ZC
-  __shared__ T zcs[C::ZS_ELEMS > C::CS_ELEMS ? C::ZS_ELEMS : (C::CS_ELEMS > 0 ? C::CS_ELEMS : 1)];
-  T* const zs = zcs;
-  T* const cs = zcs;
-#else
   __shared__ T zs[C::ZS_ELEMS > 0 ? C::ZS_ELEMS : 1];
   __shared__ T cs[C::CS_ELEMS > 0 ? C::CS_ELEMS : 1];
-#endif
   __shared__ double red[2][C::NW];
   __shared__ T wcs[32];  // IRLS weights of the left-halo-column pixels (two columns x up to 16 rows)
   __shared__ T whs[(C::RU > 0 ? C::RU : 1) * S * C::CW];  // IRLS weights of the halo rows of 2*lambda*w*r
@@ -191,7 +126,6 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
     tbx = (by == 0) ? 0 : (by == 1 ? nby_t - 1 : by - 1);
   }
   if (A.sel_mode != 0 && ((A.sel_mode == 1) != (tby >= A.sel0 && tby < A.sel1))) return;  // uniform; before any barrier
-  if (SRMAP_EXP_HEADPRIO) __builtin_amdgcn_s_setprio(3);
   const int R0 = tby * C::TH, CJ0 = tbx * C::CW, C0 = CJ0 * S;
   const int ch = blockIdx.z;
   const size_t N = (size_t)A.W * A.H;
@@ -211,7 +145,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
   // XT: the EXTRA halo cells of ALL rows are requested by the last wave in its (otherwise idle) last round -- one lane per
   // (row, cell) -- instead of by the first EXTRA lanes of every wave in every round (half of a wave's x requests
   // served two lanes each)
-  constexpr bool XT = SRMAP_EXP_XT != 0 && ARI >= 2 && (C::NW - 1) + (ARI - 1) * C::NW >= C::XR && C::XR * EXTRA <= 64;
+  constexpr bool XT = ARI >= 2 && (C::NW - 1) + (ARI - 1) * C::NW >= C::XR && C::XR * EXTRA <= 64;
   T va[ARI][S], vb[ARI][S], ma[ARI], mb[ARI];
   T vda[WD ? ARI : 1][S], vdb[WD ? ARI : 1][S];   // WD: the direction at the window's elements (fold)
   bool owna[ARI] = {}, ownb[ARI] = {};
@@ -228,7 +162,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
     const T* sa = xplane + (ina ? (size_t)grr * A.W + (size_t)gca * S : (size_t)0);
     const T* sb = xplane + (inb ? (size_t)grr * A.W + (size_t)gcb * S : (size_t)0);
 #pragma unroll
-    for (int pc = 0; pc < S; ++pc) va[it][pc] = SRMAP_EXP_NOLOAD ? (T)(lane + pc + it) * A.lambda : sa[pc];
+    for (int pc = 0; pc < S; ++pc) va[it][pc] = sa[pc];
     if (!XT) {
 #pragma unroll
       for (int pc = 0; pc < S; ++pc) vb[it][pc] = sb[pc];
@@ -269,36 +203,28 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
   const bool edge = (R0 - rm < 0) || (R0 + C::TH + rm > A.H) || (CJ0 - cm < 0) || (CJ0 + C::CW + cm > A.wl) ||
                     A.cr0 > 0 || A.cr1 < A.H;  // partial tiles (bottom / right) are edge tiles by the first two tests
   const int hrowz = wv == 0 ? -HB : C::TH - 1 + HB;  // halo rows of zh: tile rows -1 (wave 0) and TH (wave 1)
-  const bool has_z_halo = !SRMAP_EXP_NOHALO && want_data && B > 1 && A.g != nullptr && wv < 2;
+  const bool has_z_halo = want_data && B > 1 && A.g != nullptr && wv < 2;
   T ypre2[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) ypre2[v] = T(0);
-  if (SRMAP_EXP_NOLOAD) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) { ypre[v] = (T)(lane + v) * A.lambda; ypre2[v] = (T)(lane - v) * A.lambda; }
-  } else {
-    if (!SP && want_data) z_row_prefetch<T, S, B, C>(A, wv, R0, CJ0, lane, edge, ybase, ypre);
-    if (!SP && has_z_halo) z_row_prefetch<T, S, B, C>(A, hrowz, R0, CJ0, lane, edge, ybase, ypre2);
-  }
+  if (!SP && want_data) z_row_prefetch<T, S, B, C>(A, wv, R0, CJ0, lane, edge, ybase, ypre);
+  if (!SP && has_z_halo) z_row_prefetch<T, S, B, C>(A, hrowz, R0, CJ0, lane, edge, ybase, ypre2);
   const T* wplane = (want_reg && A.w) ? A.w + (size_t)ch * N : nullptr;
   T wreg[S];
 #pragma unroll
   for (int pc = 0; pc < S; ++pc) wreg[pc] = T(1);
-  if (SRMAP_EXP_NOLOAD) {
+  if (wplane != nullptr && gr < A.H && gc0 < A.W) {
 #pragma unroll
-    for (int pc = 0; pc < S; ++pc) wreg[pc] = (T)(lane + 2 * pc + 1) * A.lambda;
-  } else if (wplane != nullptr && gr < A.H && gc0 < A.W) {
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) wreg[pc] = SRMAP_EXP_NTLOAD ? __builtin_nontemporal_load(&wplane[(size_t)gr * A.W + gc0 + pc]) : wplane[(size_t)gr * A.W + gc0 + pc];
+    for (int pc = 0; pc < S; ++pc) wreg[pc] = wplane[(size_t)gr * A.W + gc0 + pc];
   }
   // halo row of 2*lambda*w*r this wave evaluates (waves 2 .. 2+RU-1: tile rows -1 .. -RU) and its weights
-  const bool reg_halo_on = !SRMAP_EXP_NOHALO && want_reg && A.g != nullptr && RU > 0;
+  const bool reg_halo_on = want_reg && A.g != nullptr && RU > 0;
   const int hrow = -(wv - 1);  // wave 2 -> -1, wave 3 -> -2
   const bool has_reg_halo = reg_halo_on && wv >= 2 && wv < 2 + RU;
   T whalo[S];
 #pragma unroll
   for (int pc = 0; pc < S; ++pc) whalo[pc] = T(1);
-  if (!SRMAP_EXP_NOLOAD && has_reg_halo && wplane != nullptr && R0 + hrow >= 0 && gc0 < A.W) {
+  if (has_reg_halo && wplane != nullptr && R0 + hrow >= 0 && gc0 < A.W) {
 #pragma unroll
     for (int pc = 0; pc < S; ++pc) whalo[pc] = wplane[(size_t)(R0 + hrow) * A.W + gc0 + pc];
   }
@@ -308,7 +234,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
   // and with them the workgroup's second barrier, for a memory round trip
   T wcolv = T(1);
   const bool col_task = reg_halo_on && (wv == 4 || wv == 5) && lane < C::TH + RU;
-  if (!SRMAP_EXP_NOLOAD && col_task && wplane != nullptr) {
+  if (col_task && wplane != nullptr) {
     const int hgr = R0 + lane - RU, hgc = C0 - (wv == 4 ? 1 : 2);
     if (hgr >= 0 && hgr < A.H && hgc >= 0) wcolv = wplane[(size_t)hgr * A.W + hgc];
   }
@@ -335,7 +261,6 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
       }
     }
   }
-  if (SRMAP_EXP_HEADPRIO) __builtin_amdgcn_s_setprio(0);
   // ---------------- x tile -> LDS, polyphase ----------------
 #pragma unroll
   for (int it = 0; it < ARI; ++it) {
@@ -376,6 +301,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
   double cost_data = 0.0, cost_reg = 0.0;
 
   // ---------------- phase 1: data term ----------------
+  // kept as an always-inline lambda called once: written as a plain block the compiler schedules every instance differently
   auto phase1_data = [&]() __attribute__((always_inline)) {
   if (SP && want_data) {
     T dummy[S];
@@ -384,22 +310,16 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
     // table columns reach Dr / S + 1 LR cells around a pixel's own (+ 1 for the neighbour pixels of the cell)
     const int mj = A.Dr / S + 3;
     const bool col_inner = (CJ0 - mj >= 0) && (CJ0 + C::CW + mj <= A.wl);
-#if SRMAP_EXP_SPOLD
-#define SRMAP_ZROW_SP z_row_sp
-#else
-#define SRMAP_ZROW_SP z_row_sp2
-#endif
     if (row_edge) {
-      SRMAP_ZROW_SP<T, S, B, C, true, true>(A, zs, wv, R0, CJ0, lane, ch, zown);
-      if (has_z_halo) SRMAP_ZROW_SP<T, S, B, C, true, true>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
+      z_row_sp2<T, S, B, C, true, true>(A, zs, wv, R0, CJ0, lane, ch, zown);
+      if (has_z_halo) z_row_sp2<T, S, B, C, true, true>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
     } else if (!col_inner) {
-      SRMAP_ZROW_SP<T, S, B, C, false, true>(A, zs, wv, R0, CJ0, lane, ch, zown);
-      if (has_z_halo) SRMAP_ZROW_SP<T, S, B, C, false, true>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
+      z_row_sp2<T, S, B, C, false, true>(A, zs, wv, R0, CJ0, lane, ch, zown);
+      if (has_z_halo) z_row_sp2<T, S, B, C, false, true>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
     } else {
-      SRMAP_ZROW_SP<T, S, B, C, false, false>(A, zs, wv, R0, CJ0, lane, ch, zown);
-      if (has_z_halo) SRMAP_ZROW_SP<T, S, B, C, false, false>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
+      z_row_sp2<T, S, B, C, false, false>(A, zs, wv, R0, CJ0, lane, ch, zown);
+      if (has_z_halo) z_row_sp2<T, S, B, C, false, false>(A, zs, hrowz, R0, CJ0, lane, ch, dummy);
     }
-#undef SRMAP_ZROW_SP
   }
   if (!SP && want_data) {
     T dummy[S];
@@ -413,7 +333,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
     }
   }
   };
-  if (!SRMAP_EXP_REGFIRST) phase1_data();
+  phase1_data();
   // ---------------- phase 1: regulariser ----------------
   if (want_reg) {
     const bool reg_border = (R0 + C::TH + C::WIN > A.H) || (C0 + C::TW + C::WIN > A.W);
@@ -450,7 +370,6 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 ? SRM
       }
     }
   }
-  if (SRMAP_EXP_REGFIRST) phase1_data();
   __syncthreads();
 
   // ---------------- phase 2 ----------------
@@ -614,7 +533,6 @@ void ztile_release(srmap_problem* p) {
   if (z->d_cnt) (void)hipFree(z->d_cnt);
   if (z->d_off) (void)hipFree(z->d_off);
   if (z->d_aux) (void)hipFree(z->d_aux);
-  if (z->d_spw) (void)hipFree(z->d_spw);
   if (z->d_spsrc) (void)hipFree(z->d_spsrc);
   if (z->d_ringbuf) (void)hipFree(z->d_ringbuf);
   spfwd_release(&z->spf);
@@ -677,21 +595,7 @@ bool ztile_plan(srmap_problem* p) {
       else if (rs.kind == SRMAP_REG_BTV && rs.range >= 1 && rs.range <= 3) { z->regk = 2; z->regr = rs.range; z->reg_index = r; }
       break;
     }
-    struct SpE { ZEntry e; double w; };
-    std::vector<std::vector<SpE>> lists((size_t)S * S);
-    for (int pr = 0; pr < S; ++pr)
-      for (int pc = 0; pc < S; ++pc)
-        for (int k = 0; k < K; ++k) {
-          const WarpTaps<double>& b = p->bwd_warps[k];
-          for (int t = 0; t < b.ntaps; ++t) {  // t & 1 = dx tap, t >> 1 = dy tap (motion_module.cpp:40-51, gather form)
-            if (b.w[t] == 0.0) continue;
-            const int rr = pr + b.oy + (t >> 1), cc = pc + b.ox + (t & 1);
-            if (pmod(rr, S) != 0 || pmod(cc, S) != 0) continue;
-            SpE q; q.e.k = k; q.e.io = fdiv(rr, S); q.e.jo = fdiv(cc, S); q.e.oyx = 0; q.w = b.w[t];
-            lists[(size_t)pr * S + pc].push_back(q);
-          }
-        }
-    // the same taps source-major (z_row_sp2): per row phase one record per (frame, vertical tap) on the LR grid
+    // the taps source-major (z_row_sp2): per row phase one record per (frame, vertical tap) on the LR grid
     std::vector<std::vector<ZSrc>> srcs((size_t)S);
     for (int pr = 0; pr < S; ++pr)
       for (int k = 0; k < K; ++k) {
@@ -720,36 +624,10 @@ bool ztile_plan(srmap_problem* p) {
       z->spn[pr] = (int)((srcs[(size_t)pr].size() + kSpChunk - 1) / kSpChunk) * kSpChunk;
       for (size_t n = 0; n < srcs[(size_t)pr].size(); ++n) srctab[(size_t)pr * spmax + n] = srcs[(size_t)pr][n];
     }
-    int MS = 1;
-    for (const auto& l : lists) MS = std::max(MS, (int)l.size());
-    z->MS = MS;
-    std::vector<int> cnt((size_t)S * 8, 0);
-    std::vector<ZEntry> aux((size_t)S * MS * S, ZEntry{0, 0, 0, 0});
-    std::vector<double> spw((size_t)S * MS * S, 0.0);
-    for (int pr = 0; pr < S; ++pr) {
-      int mx = 0;
-      for (int pc = 0; pc < S; ++pc) {
-        const auto& l = lists[(size_t)pr * S + pc];
-        cnt[(size_t)pr * 8 + pc] = (int)l.size();
-        mx = std::max(mx, (int)l.size());
-        for (size_t t = 0; t < l.size(); ++t) {
-          const size_t slot = ((size_t)t * S + pr) * S + pc;
-          aux[slot] = l[t].e;
-          spw[slot] = l[t].w;
-        }
-      }
-      cnt[(size_t)pr * 8 + S] = mx;
-    }
-    for (size_t i = 0; i < cnt.size(); ++i) z->h_cnt[i] = cnt[i];
-    bool ok = hipMalloc((void**)&z->d_cnt, sizeof(int) * cnt.size()) == hipSuccess &&
-              hipMemcpy(z->d_cnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMalloc((void**)&z->d_aux, sizeof(ZEntry) * aux.size()) == hipSuccess &&
-              hipMemcpy(z->d_aux, aux.data(), sizeof(ZEntry) * aux.size(), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMalloc((void**)&z->d_spw, sizeof(double) * spw.size()) == hipSuccess &&
-              hipMemcpy(z->d_spw, spw.data(), sizeof(double) * spw.size(), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMalloc((void**)&z->d_spsrc, sizeof(ZSrc) * srctab.size()) == hipSuccess &&
-              hipMemcpy(z->d_spsrc, srctab.data(), sizeof(ZSrc) * srctab.size(), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMalloc((void**)&z->d_off, 64) == hipSuccess;
+    // the only table an SP instance reads (z_row_sp2: spsrc, spn, spmax); the integer-shift frame table (cnt, off, aux) and
+    // the border blocks' tables stay unset -- no border blocks with E = 0
+    bool ok = hipMalloc((void**)&z->d_spsrc, sizeof(ZSrc) * srctab.size()) == hipSuccess &&
+              hipMemcpy(z->d_spsrc, srctab.data(), sizeof(ZSrc) * srctab.size(), hipMemcpyHostToDevice) == hipSuccess;
     p->zplan = z;
     if (ok && gather_ring_kernel_ok(p, g, K, z->Dr)) {
       // the ring pass runs ahead of the tile kernel into this buffer (g.d and the cost then finish inside the tile launch)
@@ -956,7 +834,7 @@ static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned 
     nbb = A.nby * (int)grid.x;
     grid.y += A.nby;
   }
-  A.rbuf = nullptr; A.spw = z.d_spw; A.Dr = z.Dr; A.ringbuf = nullptr;
+  A.rbuf = nullptr; A.Dr = z.Dr; A.ringbuf = nullptr;
 
   A.mfinish = mfin.on ? 1 : 0;
   A.n_partials = n_tile_partials + nbb * (int)grid.z;
@@ -974,12 +852,12 @@ static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned 
     A.rbuf = (const T*)p->d_resid;
     A.obs_C = geo.C;  // layout of the residual buffer written by launch_forward_direct for this evaluation
     A.ringbuf = ring_ahead ? (const T*)z.d_ringbuf : nullptr;
-    if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, true>), grid, dim3(C::NT), SRMAP_EXP_LDS_PAD, st, A);
-    else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, true>), grid, dim3(C::NT), SRMAP_EXP_LDS_PAD, st, A);
+    if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, true>), grid, dim3(C::NT), 0, st, A);
+    else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, true>), grid, dim3(C::NT), 0, st, A);
   } else {
     auto launch = [&]() {
-      if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, false>), grid, dim3(C::NT), SRMAP_EXP_LDS_PAD, st, A);
-      else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, false>), grid, dim3(C::NT), SRMAP_EXP_LDS_PAD, st, A);
+      if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, false>), grid, dim3(C::NT), 0, st, A);
+      else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, false>), grid, dim3(C::NT), 0, st, A);
     };
     if (p->ov_hook != nullptr) {
       // Row shard: a tile row [8 t, 8 t + 8) reads x rows within the halo width of itself, so the tile rows t with
@@ -1002,56 +880,72 @@ static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned 
   return SRMAP_OK;
 }
 
-// HIP loads a kernel's code object lazily at its first launch (milliseconds): touch the instance when the plan is
-// made, not inside the first evaluation of a solve.
-template <typename T, int S, int B, int REGK, int R>
-static void preload_z() {
-  hipFuncAttributes attr;
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, S, B, REGK, R, false, false>));
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, S, B, REGK, R, true, false>));
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, S, B, REGK, R, false, true>));
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, S, B, REGK, R, true, true>));
+// The tile kernel's instances: runtime (S, B, regulariser) -> f(ZInst<S, B, REGK, R>()).  Preloading and launching both
+// go through here, so this is the one list of what is instantiated (REGK 0 = no fused regulariser, 1 = TV, 2 = BTV of
+// range R).  Returns false when no instance covers the arguments.
+template <int S_, int B_, int REGK_, int R_>
+struct ZInst { static constexpr int S = S_, B = B_, REGK = REGK_, R = R_; };
+
+template <int S, int B, class F>
+static bool with_reg_instance(int regk, int regr, F& f) {
+  if (regk == 0) f(ZInst<S, B, 0, 0>());
+  else if (regk == 1) f(ZInst<S, B, 1, 0>());
+  else if (regk == 2 && regr == 1) f(ZInst<S, B, 2, 1>());
+  else if (regk == 2 && regr == 2) f(ZInst<S, B, 2, 2>());
+  else if (regk == 2 && regr == 3) f(ZInst<S, B, 2, 3>());
+  else return false;
+  return true;
 }
-template <typename T, int S, int B>
-static void preload_reg(int regk, int regr) {
-  preload_z<T, S, B, 0, 0>();
-  if (regk == 1) preload_z<T, S, B, 1, 0>();
-  if (regk == 2 && regr == 1) preload_z<T, S, B, 2, 1>();
-  if (regk == 2 && regr == 2) preload_z<T, S, B, 2, 2>();
-  if (regk == 2 && regr == 3) preload_z<T, S, B, 2, 3>();
-}
-template <typename T>
-static void preload_sb(int S, int B, int regk, int regr) {
+
+template <typename T, class F>
+static bool with_instance(int S, int B, int regk, int regr, F&& f) {
 #ifdef SRMAP_ZT_ONLY_CFG2
-  if (sizeof(T) == sizeof(SRMAP_ZT_ONLY_T) && S == 4 && B == SRMAP_ZT_ONLY_B && regk == 2 && regr == 3) preload_z<SRMAP_ZT_ONLY_T, 4, SRMAP_ZT_ONLY_B, 2, 3>();
-  return;
+  // measurement builds (tools/exp_build.sh): the one instance k_eval_z<SRMAP_ZT_ONLY_T, 4, SRMAP_ZT_ONLY_B, BTV, 3>
+  // (seconds instead of minutes per variant); SRMAP_ZT_ONLY_T defaults to double, SRMAP_ZT_ONLY_B to 3 (1: cfg3 / cfg5)
+#ifndef SRMAP_ZT_ONLY_T
+#define SRMAP_ZT_ONLY_T double
+#endif
+#ifndef SRMAP_ZT_ONLY_B
+#define SRMAP_ZT_ONLY_B 3
+#endif
+  if constexpr (std::is_same<T, SRMAP_ZT_ONLY_T>::value) {
+    if (S == 4 && B == SRMAP_ZT_ONLY_B && regk == 2 && regr == 3) { f(ZInst<4, SRMAP_ZT_ONLY_B, 2, 3>()); return true; }
+  }
+  return false;
 #else
-  if (S == 2 && B == 1) preload_reg<T, 2, 1>(regk, regr);
-  else if (S == 2 && B == 3) preload_reg<T, 2, 3>(regk, regr);
-  else if (S == 3 && B == 1) preload_reg<T, 3, 1>(regk, regr);
-  else if (S == 3 && B == 3) preload_reg<T, 3, 3>(regk, regr);
-  else if (S == 4 && B == 1) preload_reg<T, 4, 1>(regk, regr);
-  else if (S == 4 && B == 3) preload_reg<T, 4, 3>(regk, regr);
+  if (S == 2 && B == 1) return with_reg_instance<2, 1>(regk, regr, f);
+  if (S == 2 && B == 3) return with_reg_instance<2, 3>(regk, regr, f);
+  if (S == 3 && B == 1) return with_reg_instance<3, 1>(regk, regr, f);
+  if (S == 3 && B == 3) return with_reg_instance<3, 3>(regk, regr, f);
+  if (S == 4 && B == 1) return with_reg_instance<4, 1>(regk, regr, f);
+  if (S == 4 && B == 3) return with_reg_instance<4, 3>(regk, regr, f);
+  return false;
+#endif
+}
+
+// HIP loads a kernel's code object lazily at its first launch (milliseconds): touch the instances when the plan is
+// made, not inside the first evaluation of a solve -- the plan's regulariser instance and the one without (evaluations
+// that leave the regulariser out).
+template <typename T>
+static void preload_instances(int S, int B, int regk, int regr) {
+  auto touch = [](auto inst) {
+    using I = decltype(inst);
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, false>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, false>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, true>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, true>));
+  };
+  (void)with_instance<T>(S, B, 0, 0, touch);
+  (void)with_instance<T>(S, B, regk, regr, touch);
   hipFuncAttributes attr;
   (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_finish_eval<T>));
-#endif
 }
 void ztile_preload(const srmap_problem* p) {
   const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
   if (!z) return;
-  if (p->dtype == SRMAP_F32) preload_sb<float>(z->S, z->B, z->regk, z->regr);
-  else preload_sb<double>(z->S, z->B, z->regk, z->regr);
-}
-
-template <typename T, int S, int B>
-static int dispatch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned terms, const T* x, T* g,
-                      const T* wts, const ZPlan& z, int regk, int regr, double* partials, int* nb, hipStream_t st,
-                      const T* dv, double* pgd, MFin mfin, bool ring_ahead) {
-  if (regk == 1) return launch_z<T, S, B, 1, 0>(p, geo, obs_c0, terms, x, g, wts, z, partials, nb, st, dv, pgd, mfin, ring_ahead);
-  if (regk == 2 && regr == 1) return launch_z<T, S, B, 2, 1>(p, geo, obs_c0, terms, x, g, wts, z, partials, nb, st, dv, pgd, mfin, ring_ahead);
-  if (regk == 2 && regr == 2) return launch_z<T, S, B, 2, 2>(p, geo, obs_c0, terms, x, g, wts, z, partials, nb, st, dv, pgd, mfin, ring_ahead);
-  if (regk == 2 && regr == 3) return launch_z<T, S, B, 2, 3>(p, geo, obs_c0, terms, x, g, wts, z, partials, nb, st, dv, pgd, mfin, ring_ahead);
-  return launch_z<T, S, B, 0, 0>(p, geo, obs_c0, terms, x, g, wts, z, partials, nb, st, dv, pgd, mfin, ring_ahead);
+  if (p->dtype == SRMAP_F32) preload_instances<float>(z->S, z->B, z->regk, z->regr);
+  else preload_instances<double>(z->S, z->B, z->regk, z->regr);
 }
 
 template <typename T>
@@ -1126,24 +1020,11 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
   mfin.publish = mfin.on && with_d && p->eval_pub != nullptr;
   mfin.xpart = (mfin.on && sp_data) ? partials - nfwd : nullptr;
   mfin.n_xpart = (mfin.on && sp_data) ? nfwd : 0;
-  auto tiles = [&]() {
-#ifdef SRMAP_ZT_ONLY_CFG2
-    if (sizeof(T) == sizeof(SRMAP_ZT_ONLY_T) && S == 4 && B == SRMAP_ZT_ONLY_B && regk == 2 && regr == 3)
-      return launch_z<SRMAP_ZT_ONLY_T, 4, SRMAP_ZT_ONLY_B, 2, 3>(p, geo, obs_c0, zterms, (const SRMAP_ZT_ONLY_T*)x, (SRMAP_ZT_ONLY_T*)g,
-                                                   (const SRMAP_ZT_ONLY_T*)wts, z, partials, &nb, st, (const SRMAP_ZT_ONLY_T*)dv, pgd,
-                                                   mfin, ring_ahead);
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "measurement build: cfg2 instance only");
-#else
-    if (S == 2 && B == 1) return dispatch_z<T, 2, 1>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    if (S == 2 && B == 3) return dispatch_z<T, 2, 3>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    if (S == 3 && B == 1) return dispatch_z<T, 3, 1>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    if (S == 3 && B == 3) return dispatch_z<T, 3, 3>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    if (S == 4 && B == 1) return dispatch_z<T, 4, 1>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    if (S == 4 && B == 3) return dispatch_z<T, 4, 3>(p, geo, obs_c0, zterms, x, g, wts, z, regk, regr, partials, &nb, st, dv, pgd, mfin, ring_ahead);
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile kernel for scale %d blur %d", S, B);
-#endif
-  };
-  rc = tiles();
+  const bool have = with_instance<T>(S, B, regk, regr, [&](auto inst) {
+    using I = decltype(inst);
+    rc = launch_z<T, I::S, I::B, I::REGK, I::R>(p, geo, obs_c0, zterms, x, g, wts, z, partials, &nb, st, dv, pgd, mfin, ring_ahead);
+  });
+  if (!have) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile kernel for scale %d blur %d regulariser %d/%d", S, B, regk, regr);
   if (rc) return rc;
   if (sp_data) {
     partials -= nfwd;

@@ -54,29 +54,20 @@ __device__ __forceinline__ double absv<double>(double d) { return __builtin_fabs
 // and the register allocation follows the window data in flight, not the arithmetic: with the two regulariser passes pinned
 // per row (round 6) the blur-free f64 instances drop from 116 to 72 VGPRs -- 6 waves per SIMD = three workgroups per CU at
 // their 53 KB of LDS -- and cfg3 runs 0.394 -> 0.358 ms, cfg5 77.5 -> 72.6 us per channel, f32 26.3 -> 25.6 us; the cfg2
-// instance (124 -> 126 VGPRs, 73.5 KB) is unchanged.  Same instructions, same results bit for bit.
-// SRMAP_EXP_PIN = bit mask for A/B builds: 1 = regulariser pass 1 (per window row), 2 = regulariser pass 2 (per neighbour
-// row), 4 = data term (per blur row: costs the cfg2 instance spills -- off).  0 = the schedule of rounds 3 - 5.
-#ifndef SRMAP_EXP_PIN
-#define SRMAP_EXP_PIN 3
-#endif
-template <int WHICH, typename T, int N>
+// instance (124 -> 126 VGPRs, 73.5 KB) is unchanged.  Same instructions, same results bit for bit.  (Pinning the data term
+// per blur row as well costs the cfg2 instance spills.)
+template <typename T, int N>
 __device__ __forceinline__ void pin(T (&a)[N]) {
-  if ((SRMAP_EXP_PIN & WHICH) != 0) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(a[i]) : : "memory");
-  }
+  for (int i = 0; i < N; ++i) asm volatile("" : "+v"(a[i]) : : "memory");
 }
 
 constexpr int zmax(int a, int b) { return a > b ? a : b; }
 constexpr int zceil(int a, int b) { return (a + b - 1) / b; }
 
-#ifndef SRMAP_ZT_NW
-#define SRMAP_ZT_NW 8   // measurement builds: waves (= HR rows) per tile workgroup
-#endif
-template <typename T, int S, int B, int REGK, int R, int NW_ = SRMAP_ZT_NW>
+template <typename T, int S, int B, int REGK, int R>
 struct ZCfg {
-  static constexpr int NW = NW_;               // waves = HR rows per tile
+  static constexpr int NW = 8;                 // waves = HR rows per tile
   static constexpr int NT = 64 * NW;
   static constexpr int TH = NW;
   static constexpr int CW = 64;                // LR cells per tile row = lanes
@@ -305,8 +296,7 @@ struct ZArgs {
   const long long* off;  // [MS][S][S] element offset of the observation relative to (channel plane + LR cell row * w + cell)
   const ZEntry* aux;     // [MS][S][S] the same residuals as (frame, LR row offset, LR column offset) for edge tiles
   const T* rbuf;         // SP instances (sub-pixel shifts): residuals r_k = A_k x - y_k, [K][C][h][w], from k_forward_direct
-  const double* spw;     //   bilinear tap weight of every table entry, [MS][S][S]
-  const ZSrc* spsrc;     //   the same taps source-major: [S][spmax] records, spn[pr] of them in use (z_row_sp2)
+  const ZSrc* spsrc;     //   bilinear taps source-major: [S][spmax] records, spn[pr] of them in use (z_row_sp2)
   int spn[4];
   int spmax;
   int Dr;                //   data gradient of the pixels within Dr of the image edge comes from the exact ring pass
@@ -373,7 +363,7 @@ __device__ __forceinline__ constexpr int ci(int row, int col) {
   return row * C::CROW + posmod(col, C::TW / C::CW) * C::CC + C::CCL + floordiv(col, C::TW / C::CW);
 }
 
-// Read-only tables (frame table rounds > 0, edge-tile entries, sub-pixel tap weights) are read through the CONSTANT
+// Read-only tables (frame table rounds > 0, edge-tile entries) are read through the CONSTANT
 // address space: a uniform load from it is a scalar load wherever it stands -- from a plain global pointer the
 // compiler demotes uniform loads to vector loads + v_readfirstlane once the kernel has stored anything.
 template <typename U>
@@ -443,11 +433,7 @@ __device__ __forceinline__ void load_obs_row(const ArgsT& A, int pr, int rc, int
     for (int v = 0; v < NV; ++v) {
       const int pcv = v - HB, pc = posmod(pcv, S), dc = floordiv(pcv, S);
       const T* yp = yrow + (offs[pc] + dc);  // uniform pointer; the lane adds its (non-negative) cell index
-#if defined(SRMAP_EXP_NTLOAD) && SRMAP_EXP_NTLOAD
-      yv[v] = __builtin_nontemporal_load(&yp[(unsigned)lane]);
-#else
       yv[v] = yp[(unsigned)lane];
-#endif
     }
     return;
   }
@@ -500,7 +486,6 @@ __device__ __forceinline__ void z_row(const ArgsT& A, const T* __restrict__ xs, 
         }
       }
     }
-    pin<4>(bx);
   }
   const T unscale = Pre<T>::down(T(1));
   int cn[S];
@@ -581,88 +566,22 @@ __device__ __forceinline__ void z_row(const ArgsT& A, const T* __restrict__ xs, 
 // negated shift); in the interior it commutes with B^T like the integer shift does, so
 //     z(p) = sum_k sum_b w'_{k,b} [ (p + o'_k + tap_b) on the LR grid ] r_k((p + o'_k + tap_b) / S),   g_data = 2 S^2 B^T z.
 // The residuals come from k_forward_direct (exact 4-tap forward warp, every clip); which (frame, tap) pairs hit a
-// pixel depends only on its phase: host-built table (frame, LR row / column offset, weight).  No cost here (the
-// forward kernel counts it); the pixels within Dr of the edge are evaluated by the exact ring pass instead.
-// EDGE = false: tiles whose table rows all stay inside the LR image -- no uniform branches, one table row per round
-// (padding entries carry weight 0 and a harmless in-range offset).  Columns: the address is clamped and the WEIGHT
-// masked per lane (nothing is done to the loaded value before the multiply-add, so a round's loads stay in flight
-// together).
-// COLCLAMP = false (with EDGE = false): tile columns whose table columns all stay inside the LR image -- the address
-// is a uniform base + the lane, the weight a scalar operand of the multiply-add (no per-lane index arithmetic at all).
-template <typename T, int S, typename C, bool EDGE, bool COLCLAMP, typename ArgsT>
-__device__ __forceinline__ void sp_load_round(const ArgsT& A, int pr, int rc, int t, int cell0, int lane, int ch,
-                                              const int (&cn)[S], T (&rv)[C::NV], T (&wm)[C::NV]) {
-  constexpr int HB = C::HB, NV = C::NV;
-  const size_t nl = (size_t)A.wl * A.hl;
-  const int slot = (t * S + pr) * S;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int pcv = v - HB, pc = posmod(pcv, S), dc = floordiv(pcv, S);
-    rv[v] = T(0);
-    wm[v] = T(0);
-    if (!EDGE || t < cn[pc]) {  // uniform
-      const ZEntry e = ctab(A.aux, (size_t)(slot + pc));
-      const int i = rc + e.io, j = cell0 + lane + dc + e.jo;
-      if (!EDGE || (unsigned)i < (unsigned)A.hl) {  // uniform
-        const T* plane = A.rbuf + (size_t)(e.k * A.obs_C + ch) * nl;
-        if (!EDGE && !COLCLAMP) {
-          const T* rowp = plane + ((long long)i * A.wl + (cell0 + dc + e.jo));  // uniform
-          rv[v] = rowp[(unsigned)lane];
-          wm[v] = (T)ctab(A.spw, (size_t)(slot + pc));
-        } else {
-          const int jc = j < 0 ? 0 : (j >= A.wl ? A.wl - 1 : j);
-          rv[v] = plane[i * A.wl + jc];
-          wm[v] = ((unsigned)j < (unsigned)A.wl) ? (T)ctab(A.spw, (size_t)(slot + pc)) : T(0);
-        }
-      }
-    }
-  }
-}
-
-template <typename T, int S, int B, typename C, bool EDGE, bool COLCLAMP, typename ArgsT>
-__device__ __forceinline__ void z_row_sp(const ArgsT& A, T* __restrict__ zs, int rowrel, int R0, int cell0, int lane, int ch,
-                                         T (&zout)[S]) {
-  constexpr int HB = C::HB, NV = C::NV;
-  int rc, pr;
-  row_phase<S>(R0 + rowrel, rc, pr);
-  int cn[S];
-#pragma unroll
-  for (int pc = 0; pc < S; ++pc) cn[pc] = A.cntk[pr][pc];
-  const int mmax = A.cntk[pr][S];
-  T z[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) z[v] = T(0);
-  for (int t = 0; t < mmax; ++t) {
-    T rv[NV], wm[NV];
-    sp_load_round<T, S, C, EDGE, COLCLAMP>(A, pr, rc, t, cell0, lane, ch, cn, rv, wm);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) z[v] += wm[v] * rv[v];
-  }
-  if (B == 1) {
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) zout[pc] = z[pc];
-  } else {
-#pragma unroll
-    for (int pc = 0; pc < S; ++pc) {
-      T zh = T(0);
-#pragma unroll
-      for (int e = 0; e < B; ++e) zh += k1_tap<B>(A, e) * z[pc + e];
-      zs[(rowrel + HB) * C::ZROW + pc * C::CW + lane] = zh;
-    }
-  }
-}
-
-// The same sum with the taps grouped by SOURCE (frame, vertical tap): the residual r_k(i, m) a horizontal tap pair lands
-// on serves two neighbouring pixels -- (m S - ox) with the dx = 0 weight and the pixel left of it with the dx = 1 weight --
-// so a cell's S + 2 HB pixels need 1 - 2 residuals per source instead of one request per (pixel, tap): 14 requests per
-// row instead of 24 - 30 at cfg2's 16 frames (entry-major rounds are padded to the longest phase).  With
-// a = (-ox) mod S the pixels are pcv = a + S e (dx = 0) and a - 1 + S e (dx = 1), the residual column (ox + a) / S + e,
-// e in {-1, 0, 1}: compile-time pixel indices per value of a (uniform switch).
+// pixel depends only on its phase: host-built table (ZSrc).  No cost here (the forward kernel counts it); the pixels
+// within Dr of the edge are evaluated by the exact ring pass instead.
+// The taps are grouped by SOURCE (frame, vertical tap): the residual r_k(i, m) a horizontal tap pair lands on serves two
+// neighbouring pixels -- (m S - ox) with the dx = 0 weight and the pixel left of it with the dx = 1 weight -- so a cell's
+// S + 2 HB pixels need 1 - 2 residuals per source instead of one request per (pixel, tap): 14 requests per row instead of
+// 24 - 30 at cfg2's 16 frames.  With a = (-ox) mod S the pixels are pcv = a + S e (dx = 0) and a - 1 + S e (dx = 1), the
+// residual column (ox + a) / S + e, e in {-1, 0, 1}: compile-time pixel indices per value of a (uniform switch).
 // Requests and arithmetic are separated per chunk of kSpChunk sources: the chunk's table records are loaded back to back,
 // then all its residual requests are issued (uniform frame base + a 32-bit row / column / lane offset), then the
 // multiply-adds run per source with compile-time pixel indices (uniform switch on a).  The scalar unit of a CU is shared
 // by its sixteen waves: the phase clock showed this gather at 8 - 12 K cycles per row while it held one table round trip,
 // a 64-bit address chain and three column tests per source there (profiles/r05_subpixel.txt).
+// EDGE = false: tiles whose table rows all stay inside the LR image (no row test).  COLCLAMP = true: the column address
+// is clamped and the WEIGHT masked per lane (nothing is done to the loaded value before the multiply-add, so a chunk's
+// loads stay in flight together); false: tile columns whose table columns all stay inside the LR image -- the address is
+// a uniform base + the lane, the weight a scalar operand of the multiply-add.
 constexpr int kSpChunk = 4;
 template <typename T, int S, typename C, int A, bool COLCLAMP, typename ArgsT>
 __device__ __forceinline__ void sp_apply(const ArgsT& A_, const T (&rv)[kSpSlots(S, C::HB)], int elo, int jbase, int lane,
@@ -727,16 +646,12 @@ __device__ __forceinline__ void z_row_sp2(const ArgsT& A, T* __restrict__ zs, in
       const unsigned rowoff = live ? (unsigned)i * (unsigned)A.wl : 0u;
 #pragma unroll
       for (int sl = 0; sl < NSL; ++sl) {
-#ifdef SRMAP_EXP_SPNOLOAD
-        rv[c][sl] = (T)(lane + sl) * (T)rw0[c];                 // TIMING ONLY: no residual request
-#else
         if (!COLCLAMP) {
           rv[c][sl] = base[rowoff + (unsigned)(live ? jb[c] + elo + sl + lane : 0)];
         } else {
           const int j = jb[c] + lane + elo + sl;
           rv[c][sl] = base[rowoff + (unsigned)(live ? (j < 0 ? 0 : (j >= A.wl ? A.wl - 1 : j)) : 0)];
         }
-#endif
       }
     }
     // ---- multiply-adds, per source with compile-time pixel indices ----
@@ -846,8 +761,8 @@ __device__ __forceinline__ void reg_row(T (&acc)[S], double& cost, const T* __re
         if (FULL) dv[pc] = -sgn_pre<T>(dxv, T(1));
       }
     }
-    pin<1>(rv);
-    if (FULL) pin<1>(dv);
+    pin(rv);
+    if (FULL) pin(dv);
   }
 #pragma unroll
   for (int pc = 0; pc < S; ++pc) {
@@ -941,7 +856,7 @@ __device__ __forceinline__ void reg_pass2z(T (&acc)[S], const T* __restrict__ xs
         else sum[pc] += cw[pc + RU] * sgn_pre<T>(x0v[pc] - xw[pc + RU], T(1));
       }
     }
-    pin<2>(sum);
+    pin(sum);
   }
 #pragma unroll
   for (int pc = 0; pc < S; ++pc) acc[pc] += sum[pc];
@@ -1127,7 +1042,6 @@ struct ZPlan {
   bool subpix = false;  // sub-pixel shifts: residuals from k_forward_direct, z by 4-tap tables, exact ring by k_gather_direct
   int Dr = 0;           //   ring width
   void* d_ringbuf = nullptr;   //   [C][ring pixels] data gradient of the ring pixels (the ring pass ahead of the tile kernel)
-  double* d_spw = nullptr;
   ZSrc* d_spsrc = nullptr;     //   source-major tap table [S][spmax] (z_row_sp2)
   int spn[4] = {0, 0, 0, 0};
   int spmax = 0;

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Measurement build of the WHOLE library (for variants that change a shared header: every object is recompiled):
-#   tools/exp_build_all.sh <name> [-DSRMAP_EXP_...=v ...]   -> gpurun_ab/<name>/libsrmap.so
+#   tools/exp_build_all.sh <name> [compiler flags ...]   -> the variant's libsrmap.so ($out below)
 # kernels_ztile.hip is compiled with SRMAP_ZT_ONLY_CFG2 (the cfg2 instance only) unless SRMAP_EXP_FULL=1.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 out=$ROOT/gpurun_ab/$name; mkdir -p $out
 CS=$ROOT/super-resolution_amd/csrc
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -mllvm -simplifycfg-sink-common=false -Wno-invalid-offsetof -I$ROOT/include -I$CS -DSRMAP_MEASUREMENT_BUILD"
+FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on -mllvm -simplifycfg-sink-common=false -Wno-invalid-offsetof -I$ROOT/include -I$CS"
 pids=""
 for src in $CS/*.hip; do
   b=$(basename $src)
