@@ -793,13 +793,12 @@ static bool ztile_gd_instance_ok(const srmap_problem* p, const ZPlan& z, int w, 
   return ztile_est_partials(&z, w, H, C) <= kMaxFusedPartials;
 }
 
-bool ztile_can_fold(const srmap_problem* p) {
+bool ztile_can_fold(const srmap_problem* p, int C) {
   const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
-  if (!z || p->impl == SRMAP_IMPL_DIRECT || p->ov_hook != nullptr) return false;
-  const Geometry& g = p->geo;
+  if (!z || p->impl == SRMAP_IMPL_DIRECT) return false;
   // sub-pixel plans: the trial point is formed by the forward tile kernel, whose window has to hold a workgroup's own pixels
   if (z->subpix && !(z->spf.ok && z->spf.can_fold)) return false;
-  return ztile_gd_instance_ok(p, *z, g.w, g.H, p->view_C > 0 ? p->view_C : g.C, SRMAP_TERM_ALL);
+  return ztile_gd_instance_ok(p, *z, p->geo.w, p->geo.H, C, SRMAP_TERM_ALL);
 }
 
 size_t ztile_partials_needed(const srmap_problem* p) {
@@ -808,16 +807,16 @@ size_t ztile_partials_needed(const srmap_problem* p) {
 }
 
 template <typename T, int S, int B, int REGK, int R>
-static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned terms, const T* x, T* g,
+static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, int obs_c0, unsigned terms, const T* x, T* g,
                     const T* wts, const ZPlan& z, double* partials, int* nblocks, hipStream_t st, const T* dvec,
                     double* partials_gd, MFin mfin, bool ring_ahead) {
   using C = ZCfg<T, S, B, REGK, R>;
   ZArgs<T, B, C::NP> A;
   fill_zargs<T, S, B, REGK, R>(A, p, geo, obs_c0, terms, x, g, wts, z, partials, dvec, partials_gd);
-  if (dvec != nullptr && p->eval_fold_xk != nullptr) {  // line search: the point is xk + stp * d; its own pixels go to x
-    A.fold_norms = p->eval_fold_norms;
+  if (dvec != nullptr && req.fold.xk != nullptr) {  // line search: the point is xk + stp * d; its own pixels go to x
+    A.fold_norms = req.fold.norms;
     if (!(z.subpix && (terms & SRMAP_TERM_DATA))) {
-      A.fold_xk = (const T*)p->eval_fold_xk; A.fold_x = const_cast<T*>(x); A.fold_stp = (T)p->eval_fold_stp;
+      A.fold_xk = (const T*)req.fold.xk; A.fold_x = const_cast<T*>(x); A.fold_stp = (T)req.fold.stp;
     }  // sub-pixel plans: the forward kernel ahead of this launch formed the point and wrote x (launch_eval_ztile); dvec is
        // still the unnormalised direction here (fold_norms)
   }
@@ -841,10 +840,10 @@ static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned 
   A.mpart = z.d_mpart;
   A.mpart_gd = z.d_mpart ? z.d_mpart + z.mpart_cap : nullptr;
   A.cost_out = p->d_cost;
-  A.pub = mfin.publish ? p->eval_pub : nullptr;
-  A.tag_slot = p->eval_pub_tag_slot;
-  A.tag = p->eval_pub_tag;
-  A.to_host = p->eval_timeout_host;
+  A.pub = mfin.publish ? req.pub.out : nullptr;
+  A.tag_slot = req.pub.tag_slot;
+  A.tag = req.pub.tag;
+  A.to_host = req.pub.timeout_host;
   A.xpart = mfin.xpart; A.n_xpart = mfin.n_xpart;
   if (mfin.on && (size_t)A.n_partials > z.mpart_cap) return set_error(p->ctx, SRMAP_EHIP, "granule capacity");
   A.sel_mode = 0; A.sel0 = 0; A.sel1 = 0;
@@ -859,17 +858,17 @@ static int launch_z(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned 
       if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, false>), grid, dim3(C::NT), 0, st, A);
       else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, false>), grid, dim3(C::NT), 0, st, A);
     };
-    if (p->ov_hook != nullptr) {
+    if (req.overlap.fn != nullptr) {
       // Row shard: a tile row [8 t, 8 t + 8) reads x rows within the halo width of itself, so the tile rows t with
-      // 8 t >= 2 * ov_top and 8 t + 8 <= H - 2 * ov_bot touch no halo row.  They run first, the halo exchange is
+      // 8 t >= 2 * top and 8 t + 8 <= H - 2 * bot touch no halo row.  They run first, the halo exchange is
       // posted on its own stream under them, and the boundary tile rows (and the border blocks) follow the event.
       const int th = C::TH;
-      A.sel0 = (2 * p->ov_top + th - 1) / th;
-      A.sel1 = (geo.H - 2 * p->ov_bot) / th;
+      A.sel0 = (2 * req.overlap.top + th - 1) / th;
+      A.sel1 = (geo.H - 2 * req.overlap.bot) / th;
       if (A.sel1 > A.sel0) { A.sel_mode = 1; launch(); }
-      const int rch = p->ov_hook(p->ov_arg);
+      const int rch = req.overlap.fn(req.overlap.arg);
       if (rch) return rch;
-      SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, p->ov_event, 0));
+      SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, req.overlap.event, 0));
       if (A.sel1 > A.sel0) { A.sel_mode = 2; launch(); } else { A.sel_mode = 0; launch(); }
     } else {
       launch();
@@ -949,8 +948,8 @@ void ztile_preload(const srmap_problem* p) {
 }
 
 template <typename T>
-int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned terms, const T* x, T* g,
-                      double* partials, int* nblocks, hipStream_t st) {
+int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const Geometry& geo, int obs_c0,
+                      unsigned terms, const T* x, T* g, double* partials, int* nblocks, hipStream_t st) {
   const ZPlan* zp = static_cast<const ZPlan*>(p->zplan);
   if (!zp) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile plan");
   const ZPlan& z = *zp;
@@ -975,7 +974,7 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
       if (!(regk && r == z.reg_index) && p->reg[r].lambda > 0.0) more_regs = true;
   const size_t est_parts = ztile_est_partials(&z, geo.w, geo.H, geo.C);
   const bool sp_data = z.subpix && (terms & SRMAP_TERM_DATA);
-  const bool with_d = p->eval_dvec != nullptr && g != nullptr && ztile_gd_instance_ok(p, z, geo.w, geo.H, geo.C, terms);
+  const bool with_d = req.dvec != nullptr && g != nullptr && ztile_gd_instance_ok(p, z, geo.w, geo.H, geo.C, terms);
   int nfwd = 0;
   // the exact ring pass AHEAD of the tile kernel (k_gather_ring into the plan's buffer; the edge tiles add the values as
   // they store g, so g.d and the cost finish inside the tile launch) wherever the ring kernel applies; else behind it,
@@ -987,14 +986,10 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
     // sub-pixel shifts: exact residuals (and the data cost) from the direct forward kernel, then the tile kernel
     // gathers them with the 4-tap tables; the pixels within Dr of the edge are evaluated exactly by the ring pass
     if (!p->d_resid) SRMAP_HIP(p->ctx, hipMalloc(&p->d_resid, p->lr_count() * sizeof(T)));
-    SpFold sf;
-    if (p->eval_fold_xk != nullptr) {
-      if (!(with_d && z.spf.ok && z.spf.can_fold))
-        return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
-      sf.xk = p->eval_fold_xk; sf.dvec = p->eval_dvec; sf.stp = p->eval_fold_stp; sf.norms = p->eval_fold_norms;
-    }
+    if (req.fold.xk != nullptr && !(with_d && z.spf.ok && z.spf.can_fold))
+      return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
     if (z.spf.ok)
-      rc = launch_forward_sp<T>(p, geo, z.spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st, sf);
+      rc = launch_forward_sp<T>(p, geo, z.spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st, req.fold);
     else
       rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st);
     if (rc) return rc;
@@ -1004,25 +999,23 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
       if (rc) return rc;
     }
   }
-  if (p->eval_fold_xk != nullptr && !(with_d && p->ov_hook == nullptr))
+  if (req.fold.xk != nullptr && !(with_d && req.overlap.fn == nullptr))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the tile kernel's g.d instance (ztile_can_fold)");
-  const T* dv = with_d ? (const T*)p->eval_dvec : nullptr;
+  const T* dv = with_d ? (const T*)req.dvec : nullptr;
   double* pgd = with_d ? p->d_partials + p->partials_cap / 2 : nullptr;
-  p->gd_valid = false;
-  p->eval_published = false;
   // tiles: the cost reduction inside the kernel (no finish launch) when no in-image pixel of the border frame needs a
   // correction, no further regulariser kernel follows and the granules suffice
   // Sub-pixel plan: the forward kernel's data-cost partials (plain doubles, complete before the tile kernel starts) are
   // added by the same in-kernel finish; the ring pass touches g only.
   MFin mfin;
-  mfin.on = !more_regs && p->ov_hook == nullptr && z.d_mpart != nullptr && est_parts <= z.mpart_cap &&
+  mfin.on = !more_regs && req.overlap.fn == nullptr && z.d_mpart != nullptr && est_parts <= z.mpart_cap &&
             (z.n_ring == 0 || (z.ring.rg[0] == 0 && z.ring.rg[1] == 0)) && (size_t)nfwd <= kMaxFusedPartials;
-  mfin.publish = mfin.on && with_d && p->eval_pub != nullptr;
+  mfin.publish = mfin.on && with_d && req.pub.out != nullptr;
   mfin.xpart = (mfin.on && sp_data) ? partials - nfwd : nullptr;
   mfin.n_xpart = (mfin.on && sp_data) ? nfwd : 0;
   const bool have = with_instance<T>(S, B, regk, regr, [&](auto inst) {
     using I = decltype(inst);
-    rc = launch_z<T, I::S, I::B, I::REGK, I::R>(p, geo, obs_c0, zterms, x, g, wts, z, partials, &nb, st, dv, pgd, mfin, ring_ahead);
+    rc = launch_z<T, I::S, I::B, I::REGK, I::R>(p, req, geo, obs_c0, zterms, x, g, wts, z, partials, &nb, st, dv, pgd, mfin, ring_ahead);
   });
   if (!have) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile kernel for scale %d blur %d regulariser %d/%d", S, B, regk, regr);
   if (rc) return rc;
@@ -1056,8 +1049,8 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
     }
   }
   if (mfin.on) {  // reduced by the last workgroup of the tile kernel
-    p->gd_valid = with_d;  // d_cost[1] = g.d
-    p->eval_published = mfin.publish;
+    out->gd_valid = with_d;  // d_cost[1] = g.d
+    out->published = mfin.publish;
     *nblocks = 0;
     return SRMAP_OK;
   }
@@ -1068,10 +1061,10 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
     const unsigned nb_f = 1u + (unsigned)((nring + 255) / 256);
     hipLaunchKernelGGL(k_finish_eval<T>, dim3(nb_f), dim3(256), 0, st, corr_on ? g : (T*)nullptr, (const T*)z.d_corr,
                        z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, total, p->d_cost, (const double*)pgd,
-                       with_d ? p->eval_pub : (double*)nullptr, p->eval_pub_tag_slot, p->eval_pub_tag);
+                       with_d ? req.pub.out : (double*)nullptr, req.pub.tag_slot, req.pub.tag);
     SRMAP_HIP(p->ctx, hipGetLastError());
-    p->gd_valid = with_d;  // d_cost[1] = g.d
-    p->eval_published = with_d && p->eval_pub != nullptr;
+    out->gd_valid = with_d;  // d_cost[1] = g.d
+    out->published = with_d && req.pub.out != nullptr;
     *nblocks = 0;  // total already in d_cost[0]
     return SRMAP_OK;
   }
@@ -1086,9 +1079,9 @@ int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigne
   return SRMAP_OK;
 }
 
-template int launch_eval_ztile<float>(srmap_problem*, const Geometry&, int, unsigned, const float*, float*,
-                                      double*, int*, hipStream_t);
-template int launch_eval_ztile<double>(srmap_problem*, const Geometry&, int, unsigned, const double*,
-                                       double*, double*, int*, hipStream_t);
+template int launch_eval_ztile<float>(srmap_problem*, const EvalReq&, EvalOut*, const Geometry&, int, unsigned,
+                                      const float*, float*, double*, int*, hipStream_t);
+template int launch_eval_ztile<double>(srmap_problem*, const EvalReq&, EvalOut*, const Geometry&, int, unsigned,
+                                       const double*, double*, double*, int*, hipStream_t);
 
 }  // namespace srmap

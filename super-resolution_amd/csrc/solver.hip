@@ -461,10 +461,10 @@ int shard_exchange_x(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd
   return SRMAP_OK;
 }
 
-int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsigned terms, void* x_dev, void* g_dev,
-               hipStream_t st) {
+int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, EvalReq req, EvalOut* out, unsigned terms,
+               void* x_dev, void* g_dev, hipStream_t st) {
   const int mode = (c && sd && comm_world(c) > 1) ? sd->mode : SRMAP_SHARD_NONE;
-  if (mode == SRMAP_SHARD_NONE) return srmap_eval_device(p, terms, x_dev, g_dev, nullptr, st);
+  if (mode == SRMAP_SHARD_NONE) return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);
   const size_t N = (size_t)p->geo.W * p->geo.H, es = p->elem();
   if (mode == SRMAP_SHARD_ROWS) {
     // The halo rows of x travel on the communicator's side stream while the evaluation's stream runs the tile rows
@@ -480,7 +480,7 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
     if (!overlap) {
       int rc = shard_exchange_x(p, c, sd, x_dev, st);
       if (rc) return rc;
-      return srmap_eval_device(p, terms, x_dev, g_dev, nullptr, st);
+      return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);
     }
     struct Hook { srmap_problem* p; srmap_comm* c; const srmap_shard_desc* sd; void* x; hipStream_t side; hipEvent_t ev; bool called; };
     hipStream_t side; hipEvent_t ev_x, ev_halo;
@@ -489,7 +489,7 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
     SRMAP_HIP(p->ctx, hipEventRecord(ev_x, st));
     SRMAP_HIP(p->ctx, hipStreamWaitEvent(side, ev_x, 0));
     Hook h{p, c, sd, x_dev, side, ev_halo, false};
-    p->ov_hook = [](void* a) -> int {
+    req.overlap.fn = [](void* a) -> int {
       Hook* k = static_cast<Hook*>(a);
       k->called = true;
       int r = shard_exchange_x(k->p, k->c, k->sd, k->x, k->side);
@@ -497,12 +497,11 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
       SRMAP_HIP(k->p->ctx, hipEventRecord(k->ev, k->side));
       return SRMAP_OK;
     };
-    p->ov_arg = &h;
-    p->ov_event = ev_halo;
-    p->ov_top = hu;
-    p->ov_bot = hd;
-    rc = srmap_eval_device(p, terms, x_dev, g_dev, nullptr, st);  // cost rows were set on the problem
-    p->ov_hook = nullptr; p->ov_arg = nullptr; p->ov_event = nullptr;
+    req.overlap.arg = &h;
+    req.overlap.event = ev_halo;
+    req.overlap.top = hu;
+    req.overlap.bot = hd;
+    rc = eval_dispatch(p, req, out, terms, x_dev, g_dev, st);  // cost rows were set on the problem
     // An evaluation that failed before it reached the hook has not posted this rank's half of the exchange: post it
     // now, so that the neighbours' receives complete and they see an error code instead of a hang.
     if (!h.called) {
@@ -540,8 +539,8 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
     const bool band = mine && p->band_all;
     if (band) {
       const int tiles = (p->geo.H + 7) / 8, per = (tiles + world - 1) / world;
-      p->geo.rr0 = std::min(p->geo.H, rank * per * 8);
-      p->geo.rr1 = std::min(p->geo.H, (rank + 1) * per * 8);
+      req.rr0 = rank * per * 8;
+      req.rr1 = (rank + 1) * per * 8;
     } else if (rank != sd->reg_rank) {
       t = terms & SRMAP_TERM_DATA;
     }
@@ -549,9 +548,8 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
       SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
       if (g_dev) SRMAP_HIP(p->ctx, hipMemsetAsync(g_dev, 0, p->hr_count() * es, st));
     } else {
-      rc = srmap_eval_device(p, t, x_dev, g_dev, nullptr, st);
+      rc = eval_dispatch(p, req, out, t, x_dev, g_dev, st);
     }
-    p->geo.rr0 = 0; p->geo.rr1 = p->geo.H;
     if (rc) return rc;
     // the north-star's gradient all-reduce, with the cost in the same group (one launch)
     return comm_allreduce_grad_cost(c, g_dev, g_dev ? p->hr_count() : 0, p->dtype, p->d_cost, st);
@@ -561,19 +559,16 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
     const int fg = comm_rank(c) % fgs;
     // GRID: the regulariser terms of a channel block are evaluated once, by its frame group 0
     const unsigned t = (fg == 0) ? terms : (terms & SRMAP_TERM_DATA);
-    const int saved_c0 = p->view_c0, saved_C = p->view_C;
-    const bool saved_cp = p->view_coupled;
-    p->view_c0 = sd->own_ch0; p->view_C = sd->own_ch1 - sd->own_ch0; p->view_coupled = true;
+    req.view.c0 = sd->own_ch0; req.view.C = sd->own_ch1 - sd->own_ch0; req.view.coupled = true;
+    const size_t cnt = (size_t)req.view.C * N;
     char* gown = g_dev ? (char*)g_dev + (size_t)sd->own_ch0 * N * es : nullptr;
     if (t == 0) {
       rc = SRMAP_OK;
       SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
-      if (gown) SRMAP_HIP(p->ctx, hipMemsetAsync(gown, 0, (size_t)p->view_C * N * es, st));
+      if (gown) SRMAP_HIP(p->ctx, hipMemsetAsync(gown, 0, cnt * es, st));
     } else {
-      rc = srmap_eval_device(p, t, (char*)x_dev + (size_t)sd->own_ch0 * N * es, gown, nullptr, st);
+      rc = eval_dispatch(p, req, out, t, (char*)x_dev + (size_t)sd->own_ch0 * N * es, gown, st);
     }
-    const size_t cnt = (size_t)p->view_C * N;
-    p->view_c0 = saved_c0; p->view_C = saved_C; p->view_coupled = saved_cp;
     if (rc) return rc;
     if (fgs > 1 && gown) {  // sum of the frame groups' data-term gradients of this channel block
       if (!sd->frame_comm) return set_error(p->ctx, SRMAP_EINVAL, "grid shard: frame_comm missing");
@@ -581,7 +576,7 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, unsi
     }
     return rc;
   }
-  return srmap_eval_device(p, terms, x_dev, g_dev, nullptr, st);  // rows: cost rows were set on the problem
+  return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);  // rows: cost rows were set on the problem
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -594,6 +589,8 @@ struct DeviceCG {
   const srmap_shard_desc* shard = nullptr;
   Owned ow{};
   bool reduce_scalars = false;  // row / channel shards: the owned-element sums are all-reduced
+  EvalReq::View view;           // channel view of every evaluation (split_channels)
+  bool gd_valid = false;        // the last evaluation left g.d in d_cost[1]
   bool published = false;       // the last evaluation's finish kernel published {f, g.d} + tag (fetch_f_gd just waits)
   // chained passes (run_cg): launches whose inputs are already on the device are queued without waiting for the host.
   // srmap_irls_options::host_paced_passes turns this off (every pass then waits for the host's answer, as up to
@@ -719,7 +716,7 @@ struct DeviceCG {
     return SRMAP_OK;
   }
   // objective at x: g <- gradient; the cost stays on the device (finish(with_cost) fetches it).  With a direction
-  // the tile kernel may produce g.d in the same pass (p->gd_valid; not under frame sharding, where the local
+  // the tile kernel may produce g.d in the same pass (gd_valid; not under frame sharding, where the local
   // gradient is only a partial sum).
   // the line search may hand its trial point to the evaluation as (xk, stp): un-sharded solves on the tile kernel's
   // g.d instance (ztile_can_fold); decided once per CG run
@@ -728,26 +725,18 @@ struct DeviceCG {
   int evaluate(const T* dir = nullptr, T* at = nullptr, const T* fold_xk = nullptr, double fold_stp = 0.0) {  // at: the point (default x)
     evaluations++;
     const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;
-    p->eval_dvec = (mode == SRMAP_SHARD_FRAMES || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) ? nullptr : dir;
-    p->gd_valid = false;
-    p->eval_published = false;
+    EvalReq req;
+    req.view = view;
+    req.dvec = (mode == SRMAP_SHARD_FRAMES || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) ? nullptr : dir;
     // without a scalar all-reduce the evaluation's finish kernel can publish {f, g.d} and the arrival tag itself
-    p->eval_pub = (!reduce_scalars && p->eval_dvec != nullptr) ? hs : nullptr;
-    p->eval_pub_tag_slot = hs + 15;
-    p->eval_pub_tag = tag + 1.0;
-    p->eval_timeout_host = hs + 13;
+    req.pub = {(!reduce_scalars && req.dvec != nullptr) ? hs : nullptr, hs + 15, tag + 1.0, hs + 13};
     // fold: `dir` is the UNNORMALISED direction dk; the kernel scales it by the factors it derives from the norms the
     // direction pass left at dscal[4..5] (norm_factors / norm_elem: the bits of the stored d)
-    p->eval_fold_xk = (fold_xk != nullptr && p->eval_dvec != nullptr) ? fold_xk : nullptr;
-    p->eval_fold_stp = fold_stp;
-    p->eval_fold_norms = p->eval_fold_xk != nullptr ? (const double*)(dscal + 4) : nullptr;
-    const int rc = shard_eval(p, comm, shard, SRMAP_TERM_ALL, at ? at : x, g, st);
-    p->eval_fold_xk = nullptr;
-    p->eval_fold_norms = nullptr;
-    p->eval_dvec = nullptr;
-    p->eval_pub = nullptr;
-    p->eval_timeout_host = nullptr;
-    published = p->eval_published;
+    if (fold_xk != nullptr && req.dvec != nullptr) req.fold = {fold_xk, req.dvec, fold_stp, (const double*)(dscal + 4)};
+    EvalOut out;
+    const int rc = shard_eval(p, comm, shard, req, &out, SRMAP_TERM_ALL, at ? at : x, g, st);
+    gd_valid = out.gd_valid;
+    published = out.published;
     if (published) tag += 1.0;
     return rc;
   }
@@ -758,9 +747,20 @@ struct DeviceCG {
     evaluations--;
     published = false;
   }
+  // End of a solve or trace: a reduction that gave up waiting for a workgroup (the tile kernel's in-kernel finish:
+  // sticky word d_cost[6]; a CG pass: dscal[15]) left NaN sums behind -- the stopping rules ended the run -- and its
+  // granules un-re-armed.  The evaluations of a run never look at the word (wait_tag ends the run on the host-mapped
+  // word hs[13], which both kinds of finisher raise): look now, re-initialise, report.  No device copy on success.
+  int recover_timeout(int rc) {
+    (void)hipStreamSynchronize(st);
+    if (hs == nullptr || hs[13] == 0.0) return rc;
+    const int rr = recover_reduction_timeout(p, hs + 13);
+    if (rc != SRMAP_OK) return rc;
+    return rr ? rr : set_error(p->ctx, SRMAP_EHIP, "a device-side reduction timed out waiting for a workgroup during the solve (device fault or a wedged queue)");
+  }
   // f and g.d of the evaluation just made, with one wait: out[0] = g.d, out[1] = f
   int fetch_f_gd(double* out) {
-    if (!p->gd_valid) {
+    if (!gd_valid) {
       if (vec()) hipLaunchKernelGGL((k_dot<T, kVec>), dim3(nb()), dim3(256), 0, st, (const T*)g, (const T*)d, n, ow, part, fin_host(true));
       else hipLaunchKernelGGL((k_dot<T, 1>), dim3(nb()), dim3(256), 0, st, (const T*)g, (const T*)d, n, ow, part, fin_host(true));
       return finish(1, false, true, out);
@@ -1049,7 +1049,7 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
   std::swap(cg.xk, cg.x);
   {
     const int mode = (cg.comm && cg.shard && comm_world(cg.comm) > 1) ? cg.shard->mode : SRMAP_SHARD_NONE;
-    cg.foldable = mode == SRMAP_SHARD_NONE && cg.fold_enabled && ztile_can_fold(cg.p);
+    cg.foldable = mode == SRMAP_SHARD_NONE && cg.fold_enabled && ztile_can_fold(cg.p, cg.view.C > 0 ? cg.view.C : cg.p->geo.C);
   }
   int rc = cg.evaluate(nullptr, cg.xk);
   if (rc) return rc;
@@ -1277,10 +1277,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       if (e != hipSuccess) rc = set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed");
     }
   }
-  const int saved_c0 = p->view_c0, saved_C = p->view_C;
   for (int round = 0; round < rounds && rc == SRMAP_OK; ++round) {
     const int c0 = round * per_split;
-    if (opt->split_channels) { p->view_c0 = c0; p->view_C = per_split; }
+    if (opt->split_channels) { cg.view.c0 = c0; cg.view.C = per_split; }
     Geometry vg = geo;
     vg.C = per_split;
     rc = convert_upload(p, x0 + (size_t)c0 * N, cg.x, npts, st);
@@ -1327,23 +1326,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   rep.evaluations = cg.evaluations;
   rep.wait_seconds = cg.wait_seconds;
   rep.waits = cg.waits;
-  p->view_c0 = saved_c0;
-  p->view_C = saved_C;
-  {
-    // A reduction that gave up waiting for a workgroup (the tile kernel's in-kernel finish: sticky word d_cost[6]; a CG
-    // pass: dscal[15]) left NaN sums behind -- the stopping rules ended the run -- and its granules un-re-armed.  The
-    // evaluations inside a solve never look at the word (they pass no cost pointer): look now, re-initialise, report.
-    // Both kinds of finisher also raise the host-mapped word hs[13] (wait_tag ends the solve on it at once): no device
-    // copy on the successful path.
-    (void)hipStreamSynchronize(st);
-    if (cg.hs != nullptr && cg.hs[13] != 0.0) {
-      cg.hs[13] = 0.0;
-      (void)hipDeviceSynchronize();
-      ztile_rearm(p);
-      if (p->d_cost) (void)hipMemset(p->d_cost + 6, 0, sizeof(double));
-      if (rc == SRMAP_OK) rc = set_error(p->ctx, SRMAP_EHIP, "a device-side reduction timed out waiting for a workgroup during the solve (device fault or a wedged queue)");
-    }
-  }
+  rc = cg.recover_timeout(rc);
   cg.release();
   if (report) *report = rep;
   return rc;
@@ -1371,6 +1354,7 @@ static int cg_trace_typed(srmap_problem* p, double epsg, double epsf, double eps
   std::vector<double> tr;
   if (rc == SRMAP_OK) rc = run_cg(cg, epsg, epsf, epsx, maxits, &cr, &tr);
   if (rc == SRMAP_OK) rc = convert_download(p, cg.x, x_out, npts, cg.st);
+  rc = cg.recover_timeout(rc);
   cg.release();
   if (rc) return rc;
   if (iterations) *iterations = cr.its;
@@ -1393,7 +1377,8 @@ int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_sh
   if (!p || !x_dev) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
-  int rc = shard_eval(p, comm, shard, terms, x_dev, g_dev, st);
+  EvalOut out;
+  int rc = shard_eval(p, comm, shard, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;
   if (cost) {
     const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;

@@ -214,7 +214,7 @@ static int ensure(srmap_problem* p, void** buf, size_t bytes) {
 }
 
 static int ensure_partials(srmap_problem* p, size_t n) {
-  n *= 2;  // second half: partials of g.d (eval_dvec)
+  n *= 2;  // second half: partials of g.d (EvalReq::dvec)
   if (p->partials_cap >= n) return SRMAP_OK;
   if (p->d_partials) (void)hipFree(p->d_partials);
   p->d_partials = nullptr;
@@ -235,31 +235,32 @@ static size_t partials_needed(const srmap_problem* p) {
 
 // One ObjectiveFunction::ComputeAllTerms on device buffers.
 template <typename T>
-static int eval_typed(srmap_problem* p, unsigned terms, const T* x, T* g, hipStream_t st) {
+static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned terms, const T* x, T* g, hipStream_t st) {
   Geometry geo = p->geo;
-  const int c0 = p->view_C > 0 ? p->view_c0 : 0;
-  if (p->view_C > 0) geo.C = p->view_C;
-  geo.zlo = (p->view_coupled && c0 > 0) ? 1 : 0;
-  geo.zhi = (p->view_coupled && c0 + geo.C < p->geo.C) ? 1 : 0;
+  const int c0 = req.view.C > 0 ? req.view.c0 : 0;
+  if (req.view.C > 0) geo.C = req.view.C;
+  geo.zlo = (req.view.coupled && c0 > 0) ? 1 : 0;
+  geo.zhi = (req.view.coupled && c0 + geo.C < p->geo.C) ? 1 : 0;
+  geo.rr0 = std::min(req.rr0, geo.H);
+  geo.rr1 = std::min(req.rr1, geo.H);
   const size_t N = (size_t)geo.W * geo.H;
   int rc = ensure_partials(p, partials_needed(p));
   if (rc) return rc;
   if ((terms & SRMAP_TERM_DATA) && !p->have_obs)
     return set_error(p->ctx, SRMAP_EINVAL, "data term requested but no observations set");
   const bool ztile = p->impl != SRMAP_IMPL_DIRECT && p->zplan != nullptr;
-  if (p->ov_hook != nullptr && !(ztile && ztile_overlaps_halo(p))) {
+  if (req.overlap.fn != nullptr && !(ztile && ztile_overlaps_halo(p))) {
     // row shard on a path that cannot run under the halo exchange: exchange first
-    int (*hook)(void*) = p->ov_hook;
-    p->ov_hook = nullptr;
-    rc = hook(p->ov_arg);
+    rc = req.overlap.fn(req.overlap.arg);
     if (rc) return rc;
-    SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, p->ov_event, 0));
+    SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, req.overlap.event, 0));
+    req.overlap.fn = nullptr;
   }
   if (p->impl == SRMAP_IMPL_TILED && !ztile)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover this geometry");
   int nparts = 0;
   if (ztile) {
-    rc = launch_eval_ztile<T>(p, geo, c0, terms, x, g, p->d_partials, &nparts, st);
+    rc = launch_eval_ztile<T>(p, req, out, geo, c0, terms, x, g, p->d_partials, &nparts, st);
     if (rc) return rc;
   } else {
     bool g_written = false;
@@ -331,11 +332,21 @@ static inline int state_read(srmap_problem* p, hipStream_t st) {
   return SRMAP_OK;
 }
 
-static int eval_dispatch(srmap_problem* p, unsigned terms, const void* x, void* g,
-                         hipStream_t st) {
+int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned terms, const void* x, void* g,
+                  hipStream_t st) {
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   if (int rc = state_read(p, st)) return rc;
-  if (p->dtype == SRMAP_F32) return eval_typed<float>(p, terms, (const float*)x, (float*)g, st);
-  return eval_typed<double>(p, terms, (const double*)x, (double*)g, st);
+  if (p->dtype == SRMAP_F32) return eval_typed<float>(p, req, out, terms, (const float*)x, (float*)g, st);
+  return eval_typed<double>(p, req, out, terms, (const double*)x, (double*)g, st);
+}
+
+int recover_reduction_timeout(srmap_problem* p, double* host_word) {
+  // a late workgroup may still publish into the granules: re-initialise them only behind everything in flight
+  SRMAP_HIP(p->ctx, hipDeviceSynchronize());
+  ztile_rearm(p);
+  if (p->d_cost) SRMAP_HIP(p->ctx, hipMemset(p->d_cost + 6, 0, sizeof(double)));
+  if (host_word) *host_word = 0.0;
+  return SRMAP_OK;
 }
 
 }  // namespace srmap
@@ -754,10 +765,9 @@ int srmap_reg_values_and_gradient(srmap_problem* p, int reg, const double* x, co
 int srmap_eval_device(srmap_problem* p, unsigned terms, const void* x_dev, void* g_dev, double* cost,
                       void* hip_stream) {
   if (!p || !x_dev) return SRMAP_EINVAL;
-  if (p->have_obs || !(terms & SRMAP_TERM_DATA)) { /* ok */ }
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
-  int rc = eval_dispatch(p, terms, x_dev, g_dev, st);
+  EvalOut out;
+  int rc = eval_dispatch(p, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;
   if (cost) {
     SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -765,12 +775,9 @@ int srmap_eval_device(srmap_problem* p, unsigned terms, const void* x_dev, void*
     if (*cost != *cost) {  // NaN: the input's, or the in-kernel reduction gave up waiting for a workgroup (sticky word)
       double flag = 0.0;
       SRMAP_HIP(p->ctx, hipMemcpy(&flag, p->d_cost + 6, sizeof(double), hipMemcpyDeviceToHost));
-      if (flag != 0.0) {
-        // the granules were left as they were (a late workgroup may still publish into them): re-initialise them
-        // behind everything in flight, clear the word, and report -- the evaluation's gradient is not trustworthy
-        SRMAP_HIP(p->ctx, hipDeviceSynchronize());
-        ztile_rearm(p);
-        SRMAP_HIP(p->ctx, hipMemset(p->d_cost + 6, 0, sizeof(double)));
+      if (flag != 0.0) {  // re-arm and report: the evaluation's gradient is not trustworthy
+        rc = recover_reduction_timeout(p, nullptr);
+        if (rc) return rc;
         return set_error(p->ctx, SRMAP_EHIP, "in-kernel cost reduction timed out waiting for a workgroup (device fault or a wedged queue)");
       }
     }

@@ -36,9 +36,8 @@ struct Geometry {
   int w, h;        // LR size
   int s;           // scale
   int b, hb;       // blur kernel size (1 = none) and (b-1)/2
-  int rr0, rr1;    // HR rows [rr0, rr1) whose regulariser terms (gradient AND cost) this evaluation produces: frame
-                   // sharding splits the regulariser over the ranks by row band (multiples of 8, the tile height;
-                   // tile kernels only; default 0, H)
+  int rr0, rr1;    // HR rows [rr0, rr1) whose regulariser terms (gradient AND cost) this evaluation produces
+                   // (EvalReq::rr0/rr1, multiples of 8, the tile height; default 0, H)
   int cr0, cr1;    // HR rows [cr0, cr1) whose cost terms are counted (row-band sharding; default 0, H):
                    // regulariser pixels of those rows, data residuals of LR rows [cr0/s, cr1/s)
   int zlo, zhi;    // channel sharding: a halo plane exists before channel 0 / after channel C-1 of this view
@@ -52,6 +51,37 @@ struct RegSpec {
   double lambda;
   void* weights;  // device [C][H][W] dtype; nullptr = all ones
   double pow_table[2 * kMaxBtvRange + 1];  // std::pow(decay, k), host libm
+};
+
+// solver line search: the evaluation's point is xk + stp * d (d = dvec, scaled by the factors of `norms` when given:
+// cg_norm.hpp); the forward kernel forms it as it loads its window and writes it to the evaluation's x.  xk == nullptr: none
+struct SpFold { const void* xk = nullptr; const void* dvec = nullptr; double stp = 0.0; const double* norms = nullptr; };
+
+// What one evaluation is asked for beyond (terms, x, g), set by its caller for that call alone.  A default request
+// evaluates the whole problem and returns nothing but the cost in d_cost[0] (srmap_eval_device).
+struct EvalReq {
+  // channels [c0, c0 + C) (split_channels solves one channel at a time, irls_map_solver.cpp:200-262; C = 0: all);
+  // coupled: the view's neighbour planes are halo channels of a channel shard (3-D TV reads them)
+  struct View { int c0 = 0, C = 0; bool coupled = false; } view;
+  // HR rows [rr0, rr1) (clamped to H) whose regulariser terms this evaluation produces: frame sharding splits the
+  // regulariser over the ranks by row band (tile kernels only)
+  int rr0 = 0, rr1 = 1 << 30;
+  // row sharding: fn(arg) posts the halo exchange of x (on another stream) and records `event` when the halo rows
+  // [0, top) and [H - bot, H) are in place.  The tile kernels run the tiles that read no halo row first, then the hook,
+  // then -- behind the event -- the remaining tile rows; every other path calls the hook and waits before it starts.
+  struct Overlap { int (*fn)(void*) = nullptr; void* arg = nullptr; hipEvent_t event = nullptr; int top = 0, bot = 0; } overlap;
+  // solver: direction d (device, dtype); the tile kernel then produces g.d with the gradient (one pass and two launches
+  // fewer).  fold.xk != nullptr (fold.dvec == dvec): the tile kernel forms the point to evaluate and writes it to the x
+  // the evaluation was given (no separate n-vector pass per trial point); only where ztile_can_fold() says so
+  const void* dvec = nullptr;
+  SpFold fold;
+  // solver: host-mapped words the evaluation's finish kernel publishes {cost, g.d} to, followed by the arrival tag
+  // (saves the separate publish launch); timeout_host: raised when the in-kernel finish gives up waiting
+  struct Publish { double* out = nullptr; double* tag_slot = nullptr; double tag = 0.0; double* timeout_host = nullptr; } pub;
+};
+struct EvalOut {
+  bool gd_valid = false;   // the evaluation left g.d in d_cost[1]
+  bool published = false;  // its finish kernel published {cost, g.d} and the tag (EvalReq::pub)
 };
 
 }  // namespace srmap
@@ -100,37 +130,13 @@ struct srmap_problem {
   void* d_tmp = nullptr;          // [C][H][W] staging (gradient constants, values)
   double* d_partials = nullptr;   // per-block cost partials
   size_t partials_cap = 0;
-  double* d_cost = nullptr;       // [8] reduced scalars: [0] cost, [1] g.d when gd_valid
-  const void* eval_dvec = nullptr;  // set by the solver around an evaluation: direction d (device, dtype); the tile
-                                    // kernel then produces g.d with the gradient (one pass and two launches fewer)
-  bool gd_valid = false;            // the last evaluation left g.d in d_cost[1]
-  // set by the solver's line search around an evaluation (with eval_dvec): the point to evaluate is
-  // eval_fold_xk + eval_fold_stp * eval_dvec, formed by the tile kernel as it loads its window and written to the x the
-  // evaluation was given (no separate n-vector pass per trial point); only where ztile_can_fold() says so
-  const void* eval_fold_xk = nullptr;
-  double eval_fold_stp = 0.0;
-  const double* eval_fold_norms = nullptr;  // device {max|dk|, dk.dk}: eval_dvec is the unnormalised direction (solver.hip norm_elem)
-  // set by the solver around an evaluation: host-mapped words the evaluation's finish kernel publishes
-  // {cost, g.d} to, followed by the arrival tag (saves the separate publish launch); eval_published reports it did
-  double* eval_pub = nullptr;
-  double* eval_pub_tag_slot = nullptr;
+  double* d_cost = nullptr;       // [8] reduced scalars: [0] cost, [1] g.d (EvalOut::gd_valid), [6] time-out word
   double selfcheck_beta_den = 0.0;   // largest relative deviation of the derived beta denominator from the directly summed one
-  double* eval_timeout_host = nullptr;   // host-mapped word the in-kernel finish raises when it gives up waiting (solver)
-  double eval_pub_tag = 0.0;
-  bool eval_published = false;
   // stream ordering of the device STATE an evaluation reads (observations, IRLS weights): state_ev is recorded on the
   // stream that last wrote it asynchronously (state_stream); an evaluation on another stream waits for it once
   // (state_seen); a writer on another stream than the last evaluation's (use_stream) drains that stream first
   hipEvent_t state_ev = nullptr;
   hipStream_t state_stream = nullptr, state_seen = nullptr, use_stream = nullptr;
-  // set by the row-sharded evaluation around one evaluation: ov_hook(ov_arg) posts the halo exchange of x (on another
-  // stream) and records ov_event when the halo rows [0, ov_top) and [H - ov_bot, H) are in place.  The tile kernels
-  // run the tiles that read no halo row first, then the hook, then -- behind the event -- the remaining tile rows;
-  // every other path calls the hook and waits before it starts.
-  int (*ov_hook)(void*) = nullptr;
-  void* ov_arg = nullptr;
-  hipEvent_t ov_event = nullptr;
-  int ov_top = 0, ov_bot = 0;
   // frame sharding: whether EVERY rank of the communicator can evaluate the regulariser of a row band (agreed once by an
   // all-reduce, solver.hip shard_eval); the key it was agreed for
   const void* band_comm = nullptr;
@@ -142,10 +148,6 @@ struct srmap_problem {
   int nreg = 0;
   srmap::RegSpec reg[srmap::kMaxRegularizers];
   void* zplan = nullptr;          // srmap::ZPlan of the z-tile kernels (kernels_ztile.hip), owned; nullptr = not covered
-  // channel view of the current evaluation (split_channels solves one channel
-  // at a time, irls_map_solver.cpp:200-262); default = all channels
-  int view_c0 = 0, view_C = 0;
-  bool view_coupled = false;      // the view's neighbour planes are halo channels of a channel shard (3-D TV reads them)
   size_t elem() const { return dtype == SRMAP_F32 ? 4 : 8; }
   size_t hr_count() const { return (size_t)geo.C * geo.H * geo.W; }
   size_t lr_count() const { return (size_t)geo.K * geo.C * geo.h * geo.w; }
@@ -206,12 +208,13 @@ void ztile_release(srmap_problem* p);
 void ztile_preload(const srmap_problem* p);
 void ztile_rearm(srmap_problem* p);  // re-initialise the granules of the in-kernel cost reduction (after its time-out)
 bool ztile_overlaps_halo(const srmap_problem* p);  // the next tile evaluation can run interior tiles under the halo exchange
-bool ztile_reg_band_ok(const srmap_problem* p, unsigned terms);
-bool ztile_can_fold(const srmap_problem* p);  // a TERM_ALL evaluation with eval_dvec can form its point from xk + stp * d itself  // the tile kernel alone produces the regulariser part
+bool ztile_reg_band_ok(const srmap_problem* p, unsigned terms);  // the tile kernel alone produces the regulariser part
+// a TERM_ALL evaluation over C channels with a direction can form its point from xk + stp * d itself (EvalReq::fold)
+bool ztile_can_fold(const srmap_problem* p, int C);
 size_t ztile_partials_needed(const srmap_problem* p);
 template <typename T>
-int launch_eval_ztile(srmap_problem* p, const Geometry& geo, int obs_c0, unsigned terms,
-                      const T* x, T* g, double* partials, int* nblocks, hipStream_t st);
+int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const Geometry& geo, int obs_c0,
+                      unsigned terms, const T* x, T* g, double* partials, int* nblocks, hipStream_t st);
 
 // ---- forward tile kernel for sub-pixel shifts (kernels_spfwd.hip) ----
 struct SpForwardPlan {
@@ -221,9 +224,6 @@ struct SpForwardPlan {
   int RF0 = 0, NRF = 0, CF0 = 0, NCF = 0;  // union of the window and the workgroup's own HR block (rows / cells FOLD instances walk)
   bool can_fold = false;     // that union fits the kernel's load loop: the trial point can be formed (folded) here
 };
-// solver line search: the evaluation's point is xk + stp * d (d = dvec, scaled by the factors of `norms` when given:
-// cg_norm.hpp); the forward kernel forms it as it loads its window and writes it to the evaluation's x.  xk == nullptr: none
-struct SpFold { const void* xk = nullptr; const void* dvec = nullptr; double stp = 0.0; const double* norms = nullptr; };
 bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp);
 void spfwd_release(SpForwardPlan* sp);
 // out[k][c][h][w] = A_k x - y_k for all frames + cost partials (one per workgroup)
@@ -231,6 +231,14 @@ template <typename T>
 int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y,
                       int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st,
                       const SpFold& fold = SpFold());
+
+// ---- evaluation (srmap_api.hip) ----
+// One ObjectiveFunction::ComputeAllTerms on device buffers, on the stream st (srmap_eval_device with a request).
+int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned terms, const void* x, void* g,
+                  hipStream_t st);
+// After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[6]; the host-mapped word
+// host_word when given): re-initialise the granules behind everything in flight and clear both words.
+int recover_reduction_timeout(srmap_problem* p, double* host_word);
 
 // ---- vector kernels for the solver (solver.hip) ----
 int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
