@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void k_reg_values(const T* __restrict__ x,
   if (hp >= W * H) return;
   const int r = hp / W, col = hp - r * W;
   T v = reg_value_at(x, W, H, C, c, r, col, kind, range, pw, zhi);
-  if (as_weights) {  // w = 1 / max(1e-5, r) in the same pass (k_irls_weights' arithmetic)
+  if (as_weights) {  // w = 1 / max(1e-5, r) in the same pass (irls_map_solver.cpp:128-143, kMinResidualValue :35)
     const T m = v > (T)0.00001 ? v : (T)0.00001;
     v = T(1) / m;
   }
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256) void k_btv_values4(const T* __restrict__ x, T*
 #pragma unroll
   for (int pc = 0; pc < 4; ++pc) {
     T v = tv[pc];
-    if (as_weights) {  // w = 1 / max(1e-5, r) (k_irls_weights' arithmetic)
+    if (as_weights) {  // w = 1 / max(1e-5, r) (irls_map_solver.cpp:128-143, kMinResidualValue :35)
       const T m = v > (T)0.00001 ? v : (T)0.00001;
       v = T(1) / m;
     }
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void k_btv_values4(const T* __restrict__ x, T*
 // The same with a thread walking DOWN a strip of RS rows: the window's R + 1 rows stay in registers and every output
 // row requests ONE new row (two 4-element vectors) instead of R + 1 -- (RS + R) / RS rows read per row written instead
 // of R + 1, a quarter of the memory instructions at R = 3.  Per pixel the same taps in the same order with the same
-// zeros for the skipped ones as k_btv_values4: bit-identical (tests/test_gpu_parity.py, reg values against the CPU path).
+// zeros for the skipped ones as k_btv_values4: bit-identical (tests/test_gpu_reg_kernels.py asserts it).
 #ifndef SRMAP_BTV_STRIP
 #define SRMAP_BTV_STRIP 4
 #endif
@@ -529,7 +529,7 @@ __device__ __forceinline__ void btv_strip_rows(const T* __restrict__ plane, T* _
 #pragma unroll
     for (int pc = 0; pc < 4; ++pc) {
       T v = tv[pc];
-      if (as_weights) {  // w = 1 / max(1e-5, r) (k_irls_weights' arithmetic)
+      if (as_weights) {  // w = 1 / max(1e-5, r) (irls_map_solver.cpp:128-143, kMinResidualValue :35)
         const T m = v > (T)0.00001 ? v : (T)0.00001;
         v = T(1) / m;
       }
@@ -1006,26 +1006,6 @@ int launch_reg_gradient_direct(srmap_problem* p, const Geometry& geo, const RegS
   return SRMAP_OK;
 }
 
-// w = 1 / max(1e-5, r)  (irls_map_solver.cpp:128-143, kMinResidualValue :35)
-template <typename T>
-__global__ __launch_bounds__(256) void k_irls_weights(const T* __restrict__ values,
-                                                     T* __restrict__ weights, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const T r = values[i];
-  const T m = r > (T)0.00001 ? r : (T)0.00001;
-  weights[i] = T(1) / m;
-}
-
-template <typename T>
-int launch_irls_weights(srmap_problem* p, const T* values, T* weights, size_t n,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(k_irls_weights<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     values, weights, n);
-  SRMAP_HIP(p->ctx, hipGetLastError());
-  return SRMAP_OK;
-}
-
 // Deterministic final reduction of per-block partials, fixed order.  out[0] = sum.
 // Up to kReduceChunk partials: one 256-thread block.  More (multi-channel images: one partial per tile and
 // channel -- cfg5 has half a million): first one block per chunk of kReduceChunk partials into a scratch tail
@@ -1072,7 +1052,6 @@ int launch_reduce_partials(srmap_problem* p, const double* partials, int n, doub
                                              const RegSpec&, const T*, const T*, double,   \
                                              const T*, T*, bool, double*, int*,            \
                                              hipStream_t);                                  \
-  template int launch_irls_weights<T>(srmap_problem*, const T*, T*, size_t, hipStream_t);       \
   template int launch_reg_weights<T>(srmap_problem*, const Geometry&, const RegSpec&, const T*, T*, hipStream_t);
 INSTANTIATE(float)
 INSTANTIATE(double)

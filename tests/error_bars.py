@@ -33,6 +33,17 @@ U = {F64: 2.0 ** -53, F32: 2.0 ** -24}
 #   cost      f64: worst measured 12.97 (sub-pixel S = 4, B = 3, TV);          f32: 0.020 (fp64 cost reductions)
 C_BAR = {F64: 16.0, F32: 10.0}
 C_COST = {F64: 64.0, F32: 1.0}
+# The direct regulariser kernels (tests/test_gpu_reg_kernels.py over tests/reg_matrix.py), measured the same way:
+#   values    M = value_magnitude.  f64 and f32: worst measured 0 -- with dyadic inputs every term and every partial sum
+#             is exact; the constant 1 is a floor, like the f32 cost's above.
+#   gradient  M = reg_magnitude.  f64: worst measured 0 (every product and sum exact, also with the f64 weights the
+#             GPU wrote); f32: 1.29 (IMPL_AUTO, BTV 3 in the tile kernel + 3-D TV in the march), 0.73 over the direct
+#             matrix, 3.38 with GPU-written IRLS weights (BTV 4, decay 1), whose bar adds weights_rel(kind, R).
+#   cost      M_f = reg_magnitude's cost.  f64: worst measured 5.15 (GPU-written weights, BTV 3, decay 1, 41 x 260: the
+#             fp64 reduction of non-dyadic terms), 0 otherwise; f32: 0.060 (GPU-written weights, BTV 4).
+C_REG_VAL = {F64: 1.0, F32: 1.0}
+C_REG_GRAD = {F64: 1.0, F32: 6.0}
+C_REG_COST = {F64: 24.0, F32: 1.0}
 
 LAMBDA = 2.0 ** -6
 DECAYS = (0.5, 0.625)
@@ -49,50 +60,79 @@ def dyadic_weights(rng, C, H, W):
     return rng.integers(1, 33, size=(C, H, W)) / 16.0
 
 
-def _shifted(a, i, j):
-    """b[p] = a[p + (i, j)] where p + (i, j) lies in the image, else 0 (i, j >= 0)."""
+def _shifted(a, i, j, dc=0):
+    """b[p] = a[p + (dc, i, j)] where p + (dc, i, j) lies in the image, else 0 (dc, i, j >= 0)."""
     C, H, W = a.shape
     b = np.zeros_like(a)
-    if i < H and j < W:
-        b[:, :H - i, :W - j] = a[:, i:, j:]
+    if dc < C and i < H and j < W:
+        b[:C - dc, :H - i, :W - j] = a[dc:, i:, j:]
     return b
 
 
-def _inside(shape, i, j):
+def _inside(shape, i, j, dc=0):
     C, H, W = shape
     m = np.zeros(shape)
-    if i < H and j < W:
-        m[:, :H - i, :W - j] = 1.0
+    if dc < C and i < H and j < W:
+        m[:C - dc, :H - i, :W - j] = 1.0
     return m
 
 
-def _add_back(dst, src, i, j):
-    """dst[p + (i, j)] += src[p] for p + (i, j) in the image."""
+def _add_back(dst, src, i, j, dc=0):
+    """dst[p + (dc, i, j)] += src[p] for p + (dc, i, j) in the image."""
     C, H, W = dst.shape
-    if i < H and j < W:
-        dst[:, i:, j:] += src[:, :H - i, :W - j]
+    if dc < C and i < H and j < W:
+        dst[dc:, i:, j:] += src[:C - dc, :H - i, :W - j]
+
+
+def reg_taps(kind, R=0, decay=0.0):
+    """(value taps, own gradient taps, neighbour gradient taps) of one regulariser, each [(dc, i, j, weight)].
+
+    A value r_p sums weight * |x_p - x_(p + tap)| over its value taps inside the image.  The gradient at p has its own
+    terms 2 c_p r_p * weight * sgn over the own taps, and 2 c_q r_q * weight * sgn of every q = p - tap over the
+    neighbour taps.  TV3D has a value tap to the next channel but no own z term (tv_regularizer.cpp:154-170, the
+    reference's quirk that k_reg_gradient_direct documents); its previous channel does contribute.  BTV's gradient
+    window excludes the row and column R (btv_regularizer.cpp:105-166)."""
+    if kind == orc.REG_TV:
+        v = [(0, 0, 1, 1.0), (0, 1, 0, 1.0)]
+        return v, v, v
+    if kind == orc.REG_TV3D:
+        v = [(0, 0, 1, 1.0), (0, 1, 0, 1.0)]
+        return v + [(1, 0, 0, 1.0)], v, v + [(1, 0, 0, 1.0)]
+    if kind == orc.REG_BTV:
+        v = [(0, i, j, decay ** (i + j)) for i in range(R + 1) for j in range(R + 1) if (i, j) != (0, 0)]
+        g = [(0, i, j, decay ** (i + j)) for i in range(R) for j in range(R) if (i, j) != (0, 0)]
+        return v, g, g
+    raise ValueError("unknown regulariser kind %r" % kind)
+
+
+def value_magnitude(kind, x, R=0, decay=0.0):
+    """M of every regulariser value: r~_p, the sum of weight * (|x_p| + |x_q|) over the taps inside the image."""
+    ax = np.abs(np.asarray(x, dtype=np.float64))
+    rt = np.zeros_like(ax)
+    for dc, i, j, a in reg_taps(kind, R, decay)[0]:
+        rt += a * (ax + _shifted(ax, i, j, dc)) * _inside(ax.shape, i, j, dc)
+    return rt
+
+
+def weights_rel(kind, R=0):
+    """Relative error bound of an IRLS weight 1 / max(1e-5, r), in units of u: every value term is non-negative, so the
+    sum of `taps` rounded terms is within taps * u of r (the differences of the dyadic inputs are exact), and the
+    division adds one more."""
+    return len(reg_taps(kind, R, 0.5)[0]) + 1
 
 
 def reg_magnitude(kind, x, w, lam, R=0, decay=0.0):
-    """(M_cost, M_grad) of one IRLS regulariser term (kind 0 = TV, 2 = BTV) at x with weights w."""
+    """(M_cost, M_grad) of one IRLS regulariser term (kind 0 TV, 1 TV3D, 2 BTV) at x with weights w."""
     ax = np.abs(np.asarray(x, dtype=np.float64))
     w = np.asarray(w, dtype=np.float64)
     g = np.zeros_like(ax)
-    if kind == orc.REG_TV:
-        taps = [(0, 1, 1.0), (1, 0, 1.0)]
-        gtaps = taps
-    elif kind == orc.REG_BTV:
-        taps = [(i, j, decay ** (i + j)) for i in range(R + 1) for j in range(R + 1) if (i, j) != (0, 0)]
-        gtaps = [(i, j, decay ** (i + j)) for i in range(R) for j in range(R) if (i, j) != (0, 0)]
-    else:
-        raise ValueError("only TV and BTV are fused into the tile kernel")
-    rt = np.zeros_like(ax)
-    for i, j, a in taps:
-        rt += a * (ax + _shifted(ax, i, j)) * _inside(ax.shape, i, j)
+    _, own, back = reg_taps(kind, R, decay)
+    rt = value_magnitude(kind, ax, R, decay)
     cr = 2.0 * lam * w * rt
-    for i, j, a in gtaps:
-        g += cr * a * _inside(ax.shape, i, j)      # the element's own differences
-        _add_back(g, cr * a, i, j)                 # its neighbours' differences that contain it
+    for dc, i, j, a in own:
+        g += cr * a * _inside(ax.shape, i, j, dc)   # the element's own differences
+    for dc, i, j, a in back:
+        _add_back(g, cr * a, i, j, dc)               # its neighbours' differences that contain it
     return float(lam * np.sum(w * rt * rt)), g
 
 
