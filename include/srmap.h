@@ -138,6 +138,19 @@ int srmap_problem_set_impl(srmap_problem* p, int impl /* srmap_impl */);
  * rounding tie, whose per-row table only the direct kernels read). */
 int srmap_problem_active_impl(const srmap_problem* p, int* impl);
 
+/* Inner minimiser of srmap_solve: MapSolverOptions::least_squares_solver and num_lbfgs_hessian_corrections
+ * (enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER }, map_solver.h:20-51; the choice irls_map_solver.cpp:97-113;
+ * the CLI's --solver=cg|lbfgs, super_resolution.cpp:98-99, 134-141).  SRMAP_SOLVER_CG (mincg, alglib_objective.cpp:47-75)
+ * is the default of every problem.  SRMAP_SOLVER_LBFGS runs ALGLIB's minlbfgs with m = num_lbfgs_hessian_corrections
+ * history pairs and mincg's stopping conditions (alglib_objective.cpp:111-140), default preconditioner.  The history is
+ * kept on the device (2 m vectors of the problem's size).  An unknown solver or m < 1 (ALGLIB asserts m >= 1):
+ * SRMAP_EINVAL; m > 8: SRMAP_EUNSUPPORTED (ALGLIB recommends 3 <= m <= 7, map_solver.h:47-50).  For CG, m is checked
+ * the same way and kept for a later switch to L-BFGS.  L-BFGS solves sharded over a communicator of more than one rank
+ * answer SRMAP_EUNSUPPORTED; unsharded and split_channels solves are supported. */
+typedef enum { SRMAP_SOLVER_CG = 0, SRMAP_SOLVER_LBFGS = 1 } srmap_solver;
+int srmap_problem_set_solver(srmap_problem* p, int least_squares_solver /* srmap_solver */,
+                             int num_lbfgs_hessian_corrections);
+
 /* Row-band sharding (no reference counterpart: the reference is single-process).
  * A rank that owns HR rows [r0, r1) of a larger image creates its problem on the
  * band extended by halo rows and restricts the COST to the rows it owns:
@@ -275,9 +288,9 @@ int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, int width, i
 /* ------------------------------------------------------------- solver */
 /* IRLSMapSolverOptions (irls_map_solver.h:14-36) + MapSolverOptions
  * (map_solver.h:28-79); srmap_irls_options_default() fills the reference
- * defaults.  Only CG with analytic differentiation is provided
- * (alglib_objective.cpp:47-75); L-BFGS / numeric differentiation are test-only
- * alternatives in the reference and are out of scope. */
+ * defaults.  Analytic differentiation only: numeric differentiation is a
+ * test-only alternative in the reference and is out of scope.  The inner
+ * minimiser (CG or L-BFGS) is chosen on the problem: srmap_problem_set_solver. */
 typedef struct {
   int struct_size;                       /* sizeof(srmap_irls_options) of the header the caller was built with: filled by
                                             srmap_irls_options_default(); srmap_solve answers SRMAP_EINVAL when it is
@@ -301,9 +314,9 @@ void srmap_irls_options_default(srmap_irls_options* o);
 
 typedef struct {
   int irls_rounds;
-  int cg_iterations;
+  int cg_iterations;      /* inner iterations of whichever minimiser ran (CG or L-BFGS, srmap_problem_set_solver) */
   int evaluations;       /* cost+gradient evaluations ("MAP gradient iterations") */
-  int last_termination;  /* ALGLIB-style code of the last CG run */
+  int last_termination;  /* ALGLIB-style code of the last inner run (mincg / minlbfgs termination type) */
   double final_cost;
   double loop_seconds;   /* wall time of the IRLS / CG loop itself (device-resident part: no allocation,
                             no upload / download of x) */
@@ -430,6 +443,13 @@ int srmap_solve_sharded(srmap_problem* p, srmap_comm* comm, const srmap_shard_de
 int srmap_cg_trace(srmap_problem* p, double epsg, double epsf, double epsx, int maxits,
                    const double* x0, double* x_out, int* iterations, int* nfev,
                    int* termination, double* f_trace, int trace_cap, int* trace_len);
+
+/* srmap_cg_trace's twin for L-BFGS: one minlbfgs run (optimization.cpp:21640 ff.; driven as
+ * alglib_objective.cpp:111-140 drives it, m = num_lbfgs_hessian_corrections, map_solver.h:51) on the problem's current
+ * objective, with the cost of every evaluation recorded in order.  m outside 1..8 as srmap_problem_set_solver. */
+int srmap_lbfgs_trace(srmap_problem* p, int m, double epsg, double epsf, double epsx, int maxits,
+                      const double* x0, double* x_out, int* iterations, int* nfev,
+                      int* termination, double* f_trace, int trace_cap, int* trace_len);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 // solver.hip -- IRLSMapSolver::Solve on the GPU (irls_map_solver.cpp:45-157,
-// 192-265) with the nonlinear CG the reference obtains from ALGLIB 3.10.0
+// 192-265) with either inner minimiser of the reference: L-BFGS (run_lbfgs, minlbfgs; its passes are in
+// kernels_lbfgs.hip) or the nonlinear CG the reference obtains from ALGLIB 3.10.0
 // (mincg, default settings: DY/HS hybrid beta, More'-Thuente line search,
 // libs/alglib/src/optimization.cpp:17137-17880, alglibinternal.cpp:12313-12632),
 // single-GPU or sharded over one rank per GPU.
@@ -612,6 +613,14 @@ struct DeviceCG {
   int evaluations = 0;
   double wait_seconds = 0;  // host time spent in wait_tag
   int waits = 0;
+  // L-BFGS (run_lbfgs, kernels_lbfgs.hip): ring of lb_m pairs S[j] = s_j, Y[j] = y_j ([lb_m][n] each), the passes'
+  // workgroup partials and ticket, and the update pass's sums (host-mapped: they are not ctx->h_scal's 16 slots)
+  int lb_m = 0;
+  T *S = nullptr, *Y = nullptr;
+  double* lb_part = nullptr;
+  unsigned* lb_ticket = nullptr;
+  double* lb_host = nullptr;
+  static constexpr int kLbRows = 2 + 5 * kLbfgsMaxM;
 
   // Wait until the kernel that was given tag `want` (default: the last one handed out) has published its results (see
   // k_finish): poll the host-mapped word, fall back to a stream synchronisation after ~2 s (also surfaces asynchronous
@@ -662,9 +671,26 @@ struct DeviceCG {
     tag = hs[15];  // tags keep increasing across solves of one context: a stale word can never match
     return SRMAP_OK;
   }
+  int alloc_lbfgs(int m) {
+    lb_m = m;
+    SRMAP_HIP(p->ctx, hipMalloc((void**)&S, (size_t)m * n * sizeof(T)));
+    SRMAP_HIP(p->ctx, hipMalloc((void**)&Y, (size_t)m * n * sizeof(T)));
+    SRMAP_HIP(p->ctx, hipMemsetAsync(S, 0, (size_t)m * n * sizeof(T), st));
+    SRMAP_HIP(p->ctx, hipMemsetAsync(Y, 0, (size_t)m * n * sizeof(T), st));
+    SRMAP_HIP(p->ctx, hipMalloc((void**)&lb_part, sizeof(double) * kLbRows * kRedBlocks));
+    SRMAP_HIP(p->ctx, hipMalloc((void**)&lb_ticket, sizeof(unsigned)));
+    SRMAP_HIP(p->ctx, hipMemsetAsync(lb_ticket, 0, sizeof(unsigned), st));
+    SRMAP_HIP(p->ctx, hipHostMalloc((void**)&lb_host, sizeof(double) * kLbRows, hipHostMallocMapped | hipHostMallocCoherent));
+    for (int i = 0; i < kLbRows; ++i) lb_host[i] = 0.0;
+    SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+    return SRMAP_OK;
+  }
   void release() {
-    T* v[] = {x, g, xk, dk, dn, d, gp};
+    T* v[] = {x, g, xk, dk, dn, d, gp, S, Y};
     for (T* q : v) if (q) (void)hipFree(q);
+    if (lb_part) (void)hipFree(lb_part);
+    if (lb_ticket) (void)hipFree(lb_ticket);
+    if (lb_host) (void)hipHostFree(lb_host);
     if (part) (void)hipFree(part);
     if (gran) (void)hipFree(gran);
     if (dscal) (void)hipFree(dscal);
@@ -820,6 +846,26 @@ struct DeviceCG {
         hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs + 8, (const double*)(dscal + 4), 3, hs + 15, tag);
       }
     }
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return SRMAP_OK;
+  }
+  // L-BFGS: ring slot p <- (x - xk, g - gk) and the Gram rows of the new pair (launch_lbfgs_update) -> lb_host, one wait
+  int lbfgs_update(const T* gk, int p_slot, int live) {
+    tag += 1.0;
+    const LbfgsRed red{lb_part, lb_ticket, nullptr, lb_host, hs + 15, tag};
+    int rc = launch_lbfgs_update<T>(x, xk, g, gk, S, Y, p_slot, live, n, nb(), red, st);
+    if (rc) return set_error(p->ctx, rc, "lbfgs: bad history length");
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return wait_tag();
+  }
+  // L-BFGS: dn from the coefficients over {g, S[0..live), Y[0..live)}; its sums where `direction` leaves them
+  // (dscal[4..6], hs[8..10] under dir_tag)
+  int lbfgs_direction(const LbfgsCoef& c, int live) {
+    tag += 1.0;
+    dir_tag = tag;
+    const LbfgsRed red{lb_part, lb_ticket, dscal + 4, hs + 8, hs + 15, tag};
+    int rc = launch_lbfgs_direction<T>(dn, g, S, Y, live, c, n, nb(), foldable ? 1 : 0, red, st);
+    if (rc) return set_error(p->ctx, rc, "lbfgs: bad history length");
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
@@ -1203,6 +1249,141 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
   return SRMAP_OK;
 }
 
+// minlbfgsiteration (optimization.cpp:21640 ff.), default configuration: no preconditioner (prectype 0), unit scales,
+// no stpmax, analytic gradient.  Same device vectors and line search as run_cg; the history lives in the ring
+// cg.S / cg.Y.  ALGLIB's two-loop recursion runs on the host on the coefficients of the direction over
+// {g, s_j, y_j}, each dot product taken from the Gram rows the update pass reduced (kernels_lbfgs.hip): per iteration
+// one update pass, one direction pass, and a wait for each.  On return cg.x holds the accepted point.  trace
+// (optional): f of every evaluation, in order.
+template <typename T>
+static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int maxits, CgResult* out,
+                     std::vector<double>* trace) {
+  const double gtol = 0.4;  // minlbfgs_gtol, optimization.cpp:8941
+  const int m = cg.lb_m;
+  if (epsg == 0 && epsf == 0 && epsx == 0 && maxits == 0) epsx = 1.0E-6;  // minlbfgssetcond
+  CgResult res;
+  double f = 0, gg = 0;
+  std::swap(cg.xk, cg.x);  // the start point is the line search's base point; x is trial scratch (see run_cg)
+  {
+    const int mode = (cg.comm && cg.shard && comm_world(cg.comm) > 1) ? cg.shard->mode : SRMAP_SHARD_NONE;
+    cg.foldable = mode == SRMAP_SHARD_NONE && cg.fold_enabled && ztile_can_fold(cg.p, cg.view.C > 0 ? cg.view.C : cg.p->geo.C);
+  }
+  int rc = cg.evaluate(nullptr, cg.xk);
+  if (rc) return rc;
+  // d = -g and its sums; g.g = d.d
+  rc = cg.direction(nullptr, 0.0, true);
+  if (rc) return rc;
+  if (cg.fused()) {
+    rc = cg.wait_tag();
+    if (rc) return rc;
+    f = cg.hs[0];
+  } else {
+    double h[1];
+    rc = cg.finish(0, false, true, h, 3);
+    if (rc) return rc;
+    cg.dir_tag = cg.tag;
+    f = h[0];
+  }
+  gg = cg.hs[9];
+  if (trace) trace->push_back(f);
+  std::swap(cg.dk, cg.dn);
+  const double trim = 10 * (std::fabs(f) + 1);  // trimprepare
+  if (std::sqrt(gg) <= epsg) { res.type = 4; res.f = f; *out = res; return cg.copy(cg.x, cg.xk); }
+  res.nfev = 1;
+  double fold = f;
+  double stp = dmin(1.0 / std::sqrt(gg), 1.0);  // prectype 0, stpmax 0
+  // Gram tables over the ring slots: SY[a * m + b] = s_a.y_b, YY[a * m + b] = y_a.y_b, gs[j] = g.s_j, gy[j] = g.y_j (g
+  // the current gradient).  The update pass recomputes every entry of the slot it writes.
+  std::vector<double> SY((size_t)m * m, 0.0), YY((size_t)m * m, 0.0), gs(m, 0.0), gy(m, 0.0), rho(m, 0.0), theta(m, 0.0);
+  std::vector<double> cs(m), cy(m);
+  int k = 0, nfev_state = 0;  // ALGLIB's state->nfev: a line search that returns before its first trial leaves it as it was
+  for (;;) {
+    const int p = k % m, q = k < m - 1 ? k : m - 1, live = q + 1;
+    if (k != 0) stp = 1.0;
+    // linminnormalized from the direction's sums (cg_norm.hpp); the paths whose evaluations read d from memory store it
+    if (!cg.foldable) {
+      rc = cg.normalize(0.0);
+      if (rc) return rc;
+    }
+    double mx = 0, ss = 0, gdn = 0;
+    rc = cg.wait_dir(&mx, &ss, &gdn);
+    if (rc) return rc;
+    double s1, s2;
+    norm_factors(mx, ss, s1, s2);
+    const double dginit = (gdn * s1) * s2;
+    if (mx != 0) { stp = stp / s1; stp = stp / s2; }
+    int mcinfo = 0, nfev = 0;
+    std::swap(cg.g, cg.gp);  // gp = gradient at xk; the trial evaluations write g
+    rc = line_search(cg, &f, dginit, &stp, gtol, &mcinfo, &nfev, trim, trace);
+    if (rc) return rc;
+    if (nfev == 0) std::swap(cg.g, cg.gp);  // nothing evaluated: x = xk, g the gradient there (s = y = 0)
+    if (nfev != 0) nfev_state = nfev;
+    res.nfev += nfev_state;
+    res.its += 1;
+    // sk = x - xk, yk = g - g_k into slot p (ALGLIB writes them whatever mcinfo is) and the Gram rows of the new pair
+    rc = cg.lbfgs_update(nfev == 0 ? (const T*)cg.g : (const T*)cg.gp, p, live);
+    if (rc) return rc;
+    const double* r = cg.lb_host;
+    gg = r[0];
+    const double sks = r[1];
+    for (int j = 0; j < live; ++j) {
+      SY[(size_t)p * m + j] = r[2 + 5 * j];
+      SY[(size_t)j * m + p] = r[3 + 5 * j];
+      YY[(size_t)p * m + j] = r[4 + 5 * j];
+      YY[(size_t)j * m + p] = r[4 + 5 * j];
+      gs[j] = r[5 + 5 * j];
+      gy[j] = r[6 + 5 * j];
+    }
+    if (!std::isfinite(gg) || !std::isfinite(f)) { res.type = -8; break; }
+    if (res.its >= maxits && maxits > 0) { res.type = 5; break; }
+    if (std::sqrt(gg) <= epsg) { res.type = 4; break; }
+    if (fold - f <= epsf * dmax(std::fabs(fold), dmax(std::fabs(f), 1.0))) { res.type = 1; break; }
+    if (std::sqrt(sks) <= epsx) { res.type = 2; break; }
+    if (mcinfo != 1) {
+      // restart from the steepest descent; k is not advanced (slot p is written again), and while k == 0 the next
+      // line search starts from the step this one ended on
+      fold = f;
+      rc = cg.direction(nullptr, 0.0);
+      if (rc) return rc;
+    } else {
+      const double v = SY[(size_t)p * m + p], vv = YY[(size_t)p * m + p];
+      if (v == 0 || vv == 0) { res.type = -2; break; }
+      rho[p] = 1 / v;
+      const double gammak = v / vv;
+      // ALGLIB's two loops on work = cgc g + sum_j (cs_j s_j + cy_j y_j), starting from work = g
+      double cgc = 1.0;
+      for (int j = 0; j < m; ++j) { cs[j] = 0.0; cy[j] = 0.0; }
+      for (int i = k; i >= k - q; --i) {
+        const int ic = i % m;
+        double t = cgc * gs[ic];  // s_ic.work (the s coefficients are still 0)
+        for (int j = 0; j < live; ++j) t += cy[j] * SY[(size_t)ic * m + j];
+        theta[ic] = t;
+        cy[ic] -= t * rho[ic];
+      }
+      cgc *= gammak;
+      for (int j = 0; j < live; ++j) cy[j] *= gammak;
+      for (int i = k - q; i <= k; ++i) {
+        const int ic = i % m;
+        double t = cgc * gy[ic];  // y_ic.work
+        for (int j = 0; j < live; ++j) t += cs[j] * SY[(size_t)j * m + ic] + cy[j] * YY[(size_t)ic * m + j];
+        cs[ic] += rho[ic] * (-t + theta[ic]);
+      }
+      LbfgsCoef c{};
+      c.c[0] = cgc;
+      for (int j = 0; j < live; ++j) { c.c[1 + 2 * j] = cs[j]; c.c[2 + 2 * j] = cy[j]; }
+      rc = cg.lbfgs_direction(c, live);  // d = -work
+      if (rc) return rc;
+      fold = f;
+      k += 1;
+    }
+    std::swap(cg.xk, cg.x);   // xk <- accepted point; the old xk becomes trial scratch
+    std::swap(cg.dk, cg.dn);  // dk <- new direction
+  }
+  res.f = f;
+  *out = res;
+  return SRMAP_OK;
+}
+
 template <typename T>
 static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, const srmap_irls_options* opt,
                        const double* x0, double* x_out, srmap_solve_report* report) {
@@ -1211,6 +1392,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   const size_t N = (size_t)geo.W * geo.H;
   const int C = geo.C;
   const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;
+  const bool lbfgs = p->solver == SRMAP_SOLVER_LBFGS;
+  if (lbfgs && mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
   if (mode != SRMAP_SHARD_NONE && opt->split_channels)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
   if (mode == SRMAP_SHARD_ROWS &&
@@ -1270,6 +1454,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     cg.reduce_scalars = true;
   }
   int rc = cg.alloc();
+  if (rc == SRMAP_OK && lbfgs) rc = cg.alloc_lbfgs(p->lbfgs_m);
   // IRLS weights live in the problem's RegSpec (full [C][H][W]); make sure they exist.
   for (int r = 0; r < p->nreg && rc == SRMAP_OK; ++r) {
     if (!p->reg[r].weights) {
@@ -1294,8 +1479,10 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     const auto t_loop0 = std::chrono::steady_clock::now();
     while (std::fabs(cost_difference) >= o.irls_cost_difference_threshold) {
       CgResult cr;
-      rc = run_cg(cg, o.gradient_norm_threshold, o.cost_decrease_threshold, o.parameter_variation_threshold,
-                  o.max_num_solver_iterations, &cr, nullptr);
+      rc = lbfgs ? run_lbfgs(cg, o.gradient_norm_threshold, o.cost_decrease_threshold, o.parameter_variation_threshold,
+                             o.max_num_solver_iterations, &cr, nullptr)
+                 : run_cg(cg, o.gradient_norm_threshold, o.cost_decrease_threshold, o.parameter_variation_threshold,
+                          o.max_num_solver_iterations, &cr, nullptr);
       if (rc) break;
       rep.cg_iterations += cr.its;
       rep.last_termination = cr.type;
@@ -1339,9 +1526,10 @@ int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard
 }
 
 // One nonlinear-CG run (no IRLS re-weighting) with the f of every evaluation recorded: the trajectory the tests
-// compare with ALGLIB's mincg on the same objective (tests/test_gpu_parity.py).
+// compare with ALGLIB's mincg on the same objective (tests/test_gpu_parity.py).  lbfgs_m > 0: one L-BFGS run with that
+// history instead (minlbfgs; tests/test_gpu_lbfgs.py).
 template <typename T>
-static int cg_trace_typed(srmap_problem* p, double epsg, double epsf, double epsx, int maxits, const double* x0,
+static int cg_trace_typed(srmap_problem* p, int lbfgs_m, double epsg, double epsf, double epsx, int maxits, const double* x0,
                           double* x_out, int* iterations, int* nfev, int* termination, double* f_trace, int trace_cap,
                           int* trace_len) {
   const size_t npts = p->hr_count();
@@ -1349,10 +1537,11 @@ static int cg_trace_typed(srmap_problem* p, double epsg, double epsf, double eps
   cg.p = p; cg.st = p->ctx->stream; cg.n = npts;
   cg.ow.on = 0; cg.ow.e0 = 0; cg.ow.e1 = npts; cg.ow.W = p->geo.W; cg.ow.H = p->geo.H; cg.ow.r0 = 0; cg.ow.r1 = p->geo.H;
   int rc = cg.alloc();
+  if (rc == SRMAP_OK && lbfgs_m > 0) rc = cg.alloc_lbfgs(lbfgs_m);
   if (rc == SRMAP_OK) rc = convert_upload(p, x0, cg.x, npts, cg.st);
   CgResult cr;
   std::vector<double> tr;
-  if (rc == SRMAP_OK) rc = run_cg(cg, epsg, epsf, epsx, maxits, &cr, &tr);
+  if (rc == SRMAP_OK) rc = lbfgs_m > 0 ? run_lbfgs(cg, epsg, epsf, epsx, maxits, &cr, &tr) : run_cg(cg, epsg, epsf, epsx, maxits, &cr, &tr);
   if (rc == SRMAP_OK) rc = convert_download(p, cg.x, x_out, npts, cg.st);
   rc = cg.recover_timeout(rc);
   cg.release();
@@ -1398,8 +1587,21 @@ int srmap_cg_trace(srmap_problem* p, double epsg, double epsf, double epsx, int 
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
   if (p->dtype == SRMAP_F32)
-    return cg_trace_typed<float>(p, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
-  return cg_trace_typed<double>(p, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+    return cg_trace_typed<float>(p, 0, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  return cg_trace_typed<double>(p, 0, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+}
+
+int srmap_lbfgs_trace(srmap_problem* p, int m, double epsg, double epsf, double epsx, int maxits, const double* x0,
+                      double* x_out, int* iterations, int* nfev, int* termination, double* f_trace, int trace_cap,
+                      int* trace_len) {
+  if (!p || !x0 || !x_out || (trace_cap > 0 && !f_trace)) return SRMAP_EINVAL;
+  if (m < 1) return set_error(p->ctx, SRMAP_EINVAL, "num_lbfgs_hessian_corrections must be >= 1 (got %d)", m);
+  if (m > kLbfgsMaxM) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "num_lbfgs_hessian_corrections %d: at most %d are supported", m, kLbfgsMaxM);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  if (p->dtype == SRMAP_F32)
+    return cg_trace_typed<float>(p, m, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  return cg_trace_typed<double>(p, m, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
 }
 
 }  // extern "C"

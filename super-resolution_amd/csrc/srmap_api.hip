@@ -542,6 +542,20 @@ int srmap_problem_set_impl(srmap_problem* p, int impl) {
   return SRMAP_OK;
 }
 
+int srmap_problem_set_solver(srmap_problem* p, int least_squares_solver, int num_lbfgs_hessian_corrections) {
+  if (!p) return SRMAP_EINVAL;
+  if (least_squares_solver != SRMAP_SOLVER_CG && least_squares_solver != SRMAP_SOLVER_LBFGS)
+    return set_error(p->ctx, SRMAP_EINVAL, "unknown least-squares solver %d", least_squares_solver);
+  if (num_lbfgs_hessian_corrections < 1)
+    return set_error(p->ctx, SRMAP_EINVAL, "num_lbfgs_hessian_corrections must be >= 1 (got %d)", num_lbfgs_hessian_corrections);
+  if (num_lbfgs_hessian_corrections > kLbfgsMaxM)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "num_lbfgs_hessian_corrections %d: at most %d are supported",
+                     num_lbfgs_hessian_corrections, kLbfgsMaxM);
+  p->solver = least_squares_solver;
+  p->lbfgs_m = num_lbfgs_hessian_corrections;
+  return SRMAP_OK;
+}
+
 int srmap_problem_active_impl(const srmap_problem* p, int* impl) {
   if (!p || !impl) return SRMAP_EINVAL;
   const bool ztile = p->impl != SRMAP_IMPL_DIRECT && p->zplan != nullptr;

@@ -131,6 +131,8 @@ struct srmap_problem {
   double* d_partials = nullptr;   // per-block cost partials
   size_t partials_cap = 0;
   double* d_cost = nullptr;       // [8] reduced scalars: [0] cost, [1] g.d (EvalOut::gd_valid), [6] time-out word
+  int solver = SRMAP_SOLVER_CG;     // srmap_problem_set_solver: the inner minimiser of srmap_solve
+  int lbfgs_m = 5;                  // L-BFGS history length (num_lbfgs_hessian_corrections)
   double selfcheck_beta_den = 0.0;   // largest relative deviation of the derived beta denominator from the directly summed one
   // stream ordering of the device STATE an evaluation reads (observations, IRLS weights): state_ev is recorded on the
   // stream that last wrote it asynchronously (state_stream); an evaluation on another stream waits for it once
@@ -241,6 +243,32 @@ int recover_reduction_timeout(srmap_problem* p, double* host_word);
 int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
                const srmap_irls_options* o, const double* x0, double* x_out,
                srmap_solve_report* rep);
+
+// ---- L-BFGS passes (kernels_lbfgs.hip) ----
+constexpr int kLbfgsMaxM = 8;  // history cap of srmap_problem_set_solver (bounds the update pass's accumulators)
+// Where a pass leaves its sums: workgroup partials part[rows][gridDim.x], ticket (0 between passes), the reduced sums in
+// out_dev (device, may be null) and out_host (host-mapped), then `tag` at tag_slot behind a system-scope fence.
+struct LbfgsRed {
+  double* part;
+  unsigned* ticket;
+  double* out_dev;
+  double* out_host;
+  double* tag_slot;
+  double tag;
+};
+// coefficients of the direction over the basis: c[0] for g, c[1 + 2j] for s_j, c[2 + 2j] for y_j
+struct LbfgsCoef {
+  double c[1 + 2 * kLbfgsMaxM];
+};
+// ring slot p <- (s, y) = (x - xk, g - gk); sums [0] g.g, [1] s.s, then per slot j < live: s.y_j, y.s_j, y.y_j, g.s_j,
+// g.y_j (2 + 5 live rows)
+template <typename T>
+int launch_lbfgs_update(const T* x, const T* xk, const T* g, const T* gk, T* S, T* Y, int p, int live, size_t n, int nb,
+                        const LbfgsRed& red, hipStream_t st);
+// dn = -(c_g g + sum_{j < live} c_sj s_j + c_yj y_j); sums {max|dn|, dn.dn, g.dn}
+template <typename T>
+int launch_lbfgs_direction(T* dn, const T* g, const T* S, const T* Y, int live, const LbfgsCoef& c, size_t n, int nb,
+                           int keep_dn, const LbfgsRed& red, hipStream_t st);
 
 // conversions / staging
 int ensure_staging(srmap_ctx* ctx);

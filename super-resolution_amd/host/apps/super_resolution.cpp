@@ -2,9 +2,10 @@
 // src/super_resolution.cpp:38-115 flags, :126-199 SetupAndRunSolver, :269-453
 // main), on the drop-in classes: load or generate the LR frames, bilinear
 // initial estimate, IRLS-MAP solve on the GPU, optional PSNR against the ground
-// truth, save.  Same flag names and defaults.  Not carried over (out of scope,
-// DESIGN.md section 7): wavelet-domain solve, L-BFGS / numerical differentiation,
-// SSIM, display.
+// truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
+// least-squares solver as the reference does (super_resolution.cpp:134-141; any
+// other value warns and runs CG).  Not carried over (out of scope, DESIGN.md
+// section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
 #include <cstdio>
 #include <iostream>
@@ -67,7 +68,12 @@ int main(int argc, char** argv) {
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
-  if (solver_name != "cg") std::fprintf(stderr, "WARNING: only the conjugate gradient solver is available; using cg.\n");
+  // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
+  if (solver_name == "lbfgs") {
+    solver_options.least_squares_solver = LBFGS_SOLVER;
+  } else if (solver_name != "cg") {
+    std::fprintf(stderr, "WARNING: Invalid solver flag. Using conjugate gradient solver.\n");
+  }
 
   const ImageModel image_model = ImageModel::CreateImageModel(model_parameters);
 

@@ -3,9 +3,10 @@
 // evaluated on the GPU through the C ABI; the term-by-term classes
 // (ObjectiveFunction / ObjectiveTerm / ObjectiveDataTerm /
 // ObjectiveIRLSRegularizationTerm) live in optimization/objective_function.h.
-// Only the CG solver with analytic
-// differentiation exists (the reference's L-BFGS / numeric-difference variants
-// are alternatives outside the path; the enum is kept for source parity).
+// Both least-squares solvers of the reference run on the GPU: CG (mincg) and
+// L-BFGS (minlbfgs, num_lbfgs_hessian_corrections pairs), chosen as in
+// irls_map_solver.cpp:97-113.  Analytical differentiation only: the reference's
+// numeric-difference variant is a test-only alternative outside the path.
 #pragma once
 #include <cmath>
 #include <iostream>
@@ -35,7 +36,8 @@ struct MapSolverOptions {
     parameter_variation_threshold *= threshold_scale;
   }
   virtual void PrintSolverOptions() const {
-    std::cout << "  Least squares solver:                conjugate gradient (analytical differentiation)\n"
+    std::cout << "  Least squares solver:                "
+              << (least_squares_solver == LBFGS_SOLVER ? "L-BFGS" : "conjugate gradient") << " (analytical differentiation)\n"
               << "  Threshold 1 (gradient norm):         " << gradient_norm_threshold << "\n"
               << "  Threshold 2 (cost decrease):         " << cost_decrease_threshold << "\n"
               << "  Threshold 3 (parameter variation):   " << parameter_variation_threshold << std::endl;
@@ -169,14 +171,21 @@ class IRLSMapSolver : public MapSolver {
     o.split_channels = solver_options_.split_channels ? 1 : 0;
     o.max_num_irls_iterations = solver_options_.max_num_irls_iterations;
     o.irls_cost_difference_threshold = solver_options_.irls_cost_difference_threshold;
-    if (solver_options_.least_squares_solver != CG_SOLVER || solver_options_.use_numerical_differentiation)
-      srmap_host::Fail("only CG with analytical differentiation is provided");
+    if (solver_options_.use_numerical_differentiation)
+      srmap_host::Fail("only analytical differentiation is provided");
+    // LeastSquaresSolver -> srmap_solver (irls_map_solver.cpp:97-113); an out-of-range value is refused by the library
+    srmap_host::Check(srmap_problem_set_solver(problem_.get(),
+                                               solver_options_.least_squares_solver == LBFGS_SOLVER ? SRMAP_SOLVER_LBFGS
+                                               : solver_options_.least_squares_solver == CG_SOLVER  ? SRMAP_SOLVER_CG
+                                                                                                     : -1,
+                                               solver_options_.num_lbfgs_hessian_corrections),
+                      "srmap_problem_set_solver");
     const std::vector<double> x0 = initial_estimate.ToPlanar();
     std::vector<double> x(x0.size());
     srmap_host::Check(srmap_solve(problem_.get(), &o, x0.data(), x.data(), &report_), "srmap_solve");
     if (IsVerbose())
       std::cout << "IRLSMapSolver: " << report_.irls_rounds << " IRLS rounds, " << report_.cg_iterations
-                << " CG iterations, " << report_.evaluations << " cost+gradient evaluations, final cost "
+                << (solver_options_.least_squares_solver == LBFGS_SOLVER ? " L-BFGS" : " CG") << " iterations, " << report_.evaluations << " cost+gradient evaluations, final cost "
                 << report_.final_cost << std::endl;
     ImageData result;
     result.FromPlanar(x, GetImageSize(), GetNumChannels());

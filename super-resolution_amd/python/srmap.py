@@ -17,6 +17,7 @@ F64, F32 = 0, 1
 REG_TV, REG_TV3D, REG_BTV = 0, 1, 2
 TERM_DATA, TERM_REG, TERM_ALL = 1, 2, 3
 IMPL_AUTO, IMPL_DIRECT, IMPL_TILED = 0, 1, 2
+SOLVER_CG, SOLVER_LBFGS = 0, 1  # srmap_solver (MapSolverOptions::least_squares_solver)
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -72,6 +73,7 @@ _SIGNATURES = [
     ("srmap_problem_set_cost_rows", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("srmap_problem_destroy", None, [C.c_void_p]),
     ("srmap_problem_set_impl", C.c_int, [C.c_void_p, C.c_int]),
+    ("srmap_problem_set_solver", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("srmap_problem_lr_size", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("srmap_set_observations", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_active_impl", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
@@ -114,6 +116,8 @@ _SIGNATURES = [
     ("srmap_solve_sharded", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ShardDesc), C.POINTER(IrlsOptions), c_double_p, c_double_p, C.POINTER(SolveReport)]),
     ("srmap_cg_trace", C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_double_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, C.c_int, C.POINTER(C.c_int)]),
+    ("srmap_lbfgs_trace", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, c_double_p, c_double_p,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, C.c_int, C.POINTER(C.c_int)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -252,6 +256,10 @@ class Problem:
     def set_impl(self, impl):
         self.ctx.check(load().srmap_problem_set_impl(self._h, impl))
 
+    def set_solver(self, solver, m=5):
+        """Inner minimiser of solve(): SOLVER_CG (default) or SOLVER_LBFGS with m history pairs (1 <= m <= 8)."""
+        self.ctx.check(load().srmap_problem_set_solver(self._h, solver, m))
+
     def set_cost_rows(self, hr_row0, hr_row1):
         """Row-band sharding: count only the cost terms of HR rows [hr_row0, hr_row1)."""
         self.ctx.check(load().srmap_problem_set_cost_rows(self._h, hr_row0, hr_row1))
@@ -379,6 +387,17 @@ class Problem:
         self.ctx.check(load().srmap_cg_trace(self._h, epsg, epsf, epsx, maxits, pa, out.ctypes.data_as(c_double_p),
                                              C.byref(its), C.byref(nfev), C.byref(term),
                                              tr.ctypes.data_as(c_double_p), cap, C.byref(tl)))
+        return out, its.value, nfev.value, term.value, tr[:min(cap, tl.value)].copy()
+
+    def lbfgs_trace(self, x0, m=5, epsg=0.0, epsf=0.0, epsx=0.0, maxits=0, cap=4096):
+        """One L-BFGS run with m history pairs; returns (x, iterations, nfev, termination, [f of every evaluation])."""
+        a, pa = _d(x0)
+        out = np.empty((self.C, self.H, self.W))
+        its, nfev, term, tl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        tr = np.zeros(cap)
+        self.ctx.check(load().srmap_lbfgs_trace(self._h, m, epsg, epsf, epsx, maxits, pa, out.ctypes.data_as(c_double_p),
+                                                C.byref(its), C.byref(nfev), C.byref(term),
+                                                tr.ctypes.data_as(c_double_p), cap, C.byref(tl)))
         return out, its.value, nfev.value, term.value, tr[:min(cap, tl.value)].copy()
 
 
