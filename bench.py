@@ -26,9 +26,16 @@ own barriers and host scalars travel over a gloo group):
     of all frames meets);
   * --shard channels: N independent channels (the reference's split_channels
     semantics), no collective -- an explicit option only, weak scaling.
-A cfg2 run also carries a "cfg3" block: rows strong scaling of configs[2] (16-frame RGB,
-4096x4096) with its N = 1 time measured in the same run (by rank 0 alone when N > 1), so
+With --full a cfg2 run also carries a "cfg3" block: rows strong scaling of configs[2] (16-frame
+RGB, 4096x4096) with its N = 1 time measured in the same run (by rank 0 alone when N > 1), so
 that the N = 1 / 2 / 4 / 8 curve contains a configuration large enough to scale.
+
+Plain run vs --full: a plain run sets up, warms up, times the K steps, writes --dump-outputs
+and prints the line -- nothing else.  --full (off by default) adds, AFTER the timed steps
+(which it leaves untouched), every measurement that takes runs of its own: the frames variant
+(N > 1, rows), the HBM-fed leg of the roofline and the other arithmetic type (N = 1), the
+cfg3 block and the CPU baseline; --no-cpu-baseline / --no-hbm-fed / --no-other-precision /
+--no-cfg3 drop single ones of them.
 
 Timing: W untimed warm-up steps, then exactly K timed steps between barriers, max
 over ranks.  --min-timed-ms T (opt-in, default off) extends a timed region shorter
@@ -38,10 +45,11 @@ clocks only after ~50 ms of load).
 
 Prints ONE JSON line on rank 0 (see the task contract), including
   "roofline":     algorithmic bytes of one step / mean device time per step vs 8 TB/s
-                  (+ "hbm_fed": the same with three problems in rotation, i.e. inputs from HBM)
-  "cpu_baseline": the CPU oracle (a port of the reference, oracle/) timed on this
-                  host on a bounded sample of the same workload: 1 core (the
-                  reference is single-threaded) and all cores.
+                  (+ with --full "hbm_fed": the same with three problems in rotation, i.e.
+                  inputs from HBM)
+  "cpu_baseline": with --full, the CPU oracle (a port of the reference, oracle/) timed on
+                  this host on a bounded sample of the same workload: 1 core (the
+                  reference is single-threaded) and all cores; null otherwise.
 
 --dump-outputs DIR: after the timed steps, the HR gradient the timed path returned in
 its last step is written as DIR/grad.npy (the evaluation's dtype; a fixed, seeded
@@ -258,11 +266,15 @@ def main():
     ap.add_argument("--hr", type=int, default=0, help="override the HR size of the configuration (testing)")
     ap.add_argument("--terms", choices=["all", "data", "reg"], default="all",
                     help="ablation only: evaluate a subset of the objective terms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-precision", action="store_true", help="skip the labelled block of the other arithmetic type (profiling runs)")
-    ap.add_argument("--no-hbm-fed", action="store_true", help="skip the HBM-fed leg of the roofline (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the frames variant (N > 1, "
+                         "rows), the HBM-fed leg of the roofline and the other arithmetic type (N = 1), the configs[2] "
+                         "block and the CPU baseline (default: the headline run alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-precision", action="store_true", help="--full: skip the labelled block of the other arithmetic type (profiling runs)")
+    ap.add_argument("--no-hbm-fed", action="store_true", help="--full: skip the HBM-fed leg of the roofline (N = 1)")
     ap.add_argument("--no-cfg3", action="store_true",
-                    help="skip the configs[2] block (rows strong scaling of the 16-frame RGB 4096x4096 problem) that a "
+                    help="--full: skip the configs[2] block (rows strong scaling of the 16-frame RGB 4096x4096 problem) that a "
                          "cfg2 run carries so that the N = 1 / 2 / 4 / 8 curve contains a configuration large enough to scale")
     ap.add_argument("--overlap", action="store_true",
                     help="rows, RCCL: post the halo exchange under the interior tile rows (srmap_comm_set_overlap; default: "
@@ -527,7 +539,7 @@ def main():
         main_shard, res, second = "frames", run(cfg, "frames", args.steps, args.warmup), None
     else:
         main_shard, res = "rows", run(cfg, "rows", args.steps, args.warmup)
-        second = run(cfg, "frames", args.steps, args.warmup)
+        second = run(cfg, "frames", args.steps, args.warmup) if args.full else None
 
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, res, main_shard, dist, rank)
@@ -535,7 +547,7 @@ def main():
 
     # ---- HBM-fed leg (N = 1): the same evaluation over three independent problems in rotation ----
     hbm_fed = None
-    if world == 1 and not args.no_hbm_fed:
+    if args.full and world == 1 and not args.no_hbm_fed:
         fed = run(cfg, "none", max(200, args.steps // 4), min(args.warmup, 60), n_problems=3)
         fed_bytes = b_alg_of(cfg, cfg["C"])
         hbm_fed = {"problems_in_rotation": 3, "working_set_bytes": 3 * fed_bytes,
@@ -548,7 +560,7 @@ def main():
 
     # ---- the other precision on the same clock (N = 1): a labelled extra block, never `value` ----
     other_prec = None
-    if world == 1 and args.terms == "all" and not args.no_other_precision:
+    if args.full and world == 1 and args.terms == "all" and not args.no_other_precision:
         o_name = "f32" if args.dtype == "f64" else "f64"
         o_dt = (srmap.F32, torch.float32) if o_name == "f32" else (srmap.F64, torch.float64)
         o_E = 4 if o_name == "f32" else 8
@@ -563,7 +575,7 @@ def main():
 
     # ---- configs[2] block: the configuration of the curve that is large enough to scale (rows, strong scaling) ----
     cfg3_block = None
-    if args.config == "cfg2" and not args.no_cfg3 and args.shard != "channels" and args.terms == "all":
+    if args.full and args.config == "cfg2" and not args.no_cfg3 and args.shard != "channels" and args.terms == "all":
         c3 = make_cfg("cfg3")
         st3, wu3 = max(20, args.steps // 10), max(5, args.warmup // 10)
         ref3 = run(c3, "none", st3, wu3, only_rank0=(world > 1))       # the N = 1 time, measured in this very run
@@ -597,7 +609,7 @@ def main():
             "metric": "MAP gradient iterations/sec at fixed HR size",
             "value": units / res["wall_per_step"],
             "unit": "MAP gradient iterations/s" if main_shard != "channels" else "channel-iterations/s (one %d-frame %dx%d channel per GPU)" % (K, W, H),
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": res["wall_per_step"] * 1e3, "higher_is_better": True,
             # ONE label for the whole N = 1 / 2 / 4 / 8 curve: the workload is the same at every N (only --shard channels
             # gives every GPU its own channel)
@@ -622,7 +634,7 @@ def main():
                          "limited_by": "latency/occupancy (not bandwidth)",
                          "limiter_evidence": limiter_evidence(args.dtype, res["dev_ms_per_step"]),
                          "residency": "one problem re-evaluated every step: its %.0f MB working set stays in the 256 MiB Infinity "
-                                      "Cache between steps (the contract's step); `hbm_fed` is the same step with the inputs "
+                                      "Cache between steps (the contract's step); `hbm_fed` (--full) is the same step with the inputs "
                                       "coming from HBM" % (b_alg * share / 1e6),
                          "hbm_fed": hbm_fed,
                          "traffic_source": (traffic_src + ": rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of this "
@@ -641,7 +653,7 @@ def main():
             out[other_prec["dtype"]] = other_prec
         if cfg3_block is not None:
             out["cfg3"] = cfg3_block
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, res["lr"], res["x0"], res["wts"])
         else:
             out["cpu_baseline"] = None

@@ -74,12 +74,14 @@ def test_two_ranks_on_one_gpu(tmp_path, mode, backend):
 def test_bench_spawns_its_ranks(shard, how):
     """`python bench.py --gpus 2` as a bare subprocess (no launcher, no WORLD_SIZE): the bench re-executes itself under
     torch.distributed.run, one rank per process; here both ranks share GPU 0 over the host-callback communicator, or over
-    RCCL itself on loopback sockets (the path the driver's N > 1 run takes, minus xGMI)."""
+    RCCL itself on loopback sockets (the path the driver's N > 1 run takes, minus xGMI).  --full: the frames variant and
+    the configs[2] block are part of the line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     rccl = how == "--test-rccl-loopback"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", how, "--watchdog-s", "240", "--steps", "5",
-                        "--warmup", "2", "--clock-ramp-ms", "0", "--min-timed-ms", "0", "--hr", "512", "--shard", shard],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", how, "--full", "--watchdog-s", "240",
+                        "--steps", "5", "--warmup", "2", "--clock-ramp-ms", "0", "--min-timed-ms", "0", "--hr", "512",
+                        "--shard", shard],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     if rccl and r.returncode != 0 and r.stderr.count("RCCL communicator up") < 2:
         pytest.skip("RCCL could not create a 2-rank communicator over loopback here:\n" + r.stderr[-1500:])

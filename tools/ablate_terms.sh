@@ -1,8 +1,8 @@
 root=$(pwd); out=$root/gpurun_out/r02_abl; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for t in data reg all; do
-  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$t -o kt -- python $root/bench.py --steps 100 --warmup 10 --no-cpu-baseline --terms $t > /dev/null 2>&1
-  timeout 150 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $out/sqa_$t -o pmc -- python $root/bench.py --steps 10 --warmup 3 --no-cpu-baseline --terms $t > /dev/null 2>&1
+  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$t -o kt -- python $root/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --terms $t > /dev/null 2>&1
+  timeout 150 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $out/sqa_$t -o pmc -- python $root/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --terms $t > /dev/null 2>&1
   echo "== $t"; python - <<PY
 import csv,glob
 for f in glob.glob('$out/kt_$t/**/*kernel_stats.csv',recursive=True):

@@ -6,9 +6,9 @@ dts=${@:-f64}
 root=$(pwd); out=$root/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for d in $dts; do
-  B="python $root/bench.py --steps 20 --warmup 3 --no-cpu-baseline --dtype $d"
-  (cd $root && timeout 200 python bench.py --steps 200 --warmup 20 --dtype $d --no-cpu-baseline > $out/bench_$d.json 2> $out/bench_$d.err)
-  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$d -o kt -- python $root/bench.py --steps 200 --warmup 20 --no-cpu-baseline --dtype $d > $out/kt_$d.log 2>&1
+  B="python $root/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --dtype $d"
+  (cd $root && timeout 200 python bench.py --full --steps 200 --warmup 20 --dtype $d --no-cpu-baseline > $out/bench_$d.json 2> $out/bench_$d.err)
+  timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_$d -o kt -- python $root/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --dtype $d > $out/kt_$d.log 2>&1
   timeout 150 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $out/sqa_$d -o pmc -- $B > /dev/null 2>&1
   timeout 150 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $out/sqb_$d -o pmc -- $B > /dev/null 2>&1
   cat $out/bench_$d.json

@@ -24,9 +24,9 @@ PY
 }
 for rep in 1 2; do
   for n in 2 4 8; do
-    run "rows n$n #$rep" --gpus $n
-    run "rows+overlap n$n #$rep" --gpus $n --overlap
-    run "frames n$n #$rep" --gpus $n --shard frames
+    run "rows n$n #$rep" --full --gpus $n
+    run "rows+overlap n$n #$rep" --full --gpus $n --overlap
+    run "frames n$n #$rep" --full --gpus $n --shard frames
   done
 done
 run "channels n4" --gpus 4 --shard channels

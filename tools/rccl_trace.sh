@@ -7,7 +7,7 @@ rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for shard in rows frames; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$shard -o kt -- \
-    python $root/bench.py --gpus 2 --test-rccl-loopback --watchdog-s 120 --shard $shard --steps 200 --warmup 20 --clock-ramp-ms 0 \
+    python $root/bench.py --full --gpus 2 --test-rccl-loopback --watchdog-s 120 --shard $shard --steps 200 --warmup 20 --clock-ramp-ms 0 \
       --min-timed-ms 0 --no-cfg3 --no-cpu-baseline > $out/$shard.json 2> $out/$shard.err
   echo "rc $? ($shard)"
 done
