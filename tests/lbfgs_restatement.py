@@ -10,6 +10,16 @@ trajectory bit for bit (tests/test_lbfgs_cpu.py checks it against tests/golden/l
   - mcsrch / mcstep (alglibinternal.cpp:12313-12632, 12972-13232), linminnormalized (:12165-12196) and trimfunction
     are restated below.
 
+Two opt-in hooks, both off by default (the restatement is then ALGLIB bit for bit), serve the solver matrix
+(tests/solver_matrix.py): ``store=np.float32`` rounds x, g, s, y and d where the device solver stores T (run_lbfgs,
+kernels_lbfgs.hip), and ``plant=(kind, arg)`` plants one plausible pass bug (tests/test_solver_matrix_cpu.py shows that the
+matrix's bars catch it):
+  ("lose", keep)      the elements from index keep on are left out of s, y and every sum the L-BFGS passes reduce (a
+                      ragged tail on the vector path: keep = n - n % V; a skipped grid-stride round: keep = nb 256 V)
+  ("swap", None)      the direction formed from the Gram table as run_lbfgs does, with s_p.y_j and y_p.s_j swapped
+  ("drop_oldest", None)  once the ring has wrapped, the oldest live pair is left out of the two loops
+  ("maxsum", None)    max|d| of linminnormalized reduced as a sum
+
 ``irls_adapter(m)`` wraps it in the oracle's sro_cg_fn signature (oracle/srmap_oracle.h), so the oracle's own IRLS loop
 (``sro_irls_solve``) runs with L-BFGS as its inner solver.  Test infrastructure only."""
 import ctypes as C
@@ -131,7 +141,7 @@ def mcstep(b, stp, fp, dp, brackt, stmin, stmax):
     return stp, brackt, info
 
 
-def mcsrch(fun, x, f, g, d, stp, gtol, trim, trace, nfev=0):
+def mcsrch(fun, x, f, g, d, stp, gtol, trim, trace, nfev=0, store=None, dginit_dot=dot):
     """mcsrch with the evaluation inlined and trimfunction after each evaluation.  x, g are updated in place; returns
     (f, stp, info, nfev).  nfev is reset only once the search starts: the early returns (stp <= 0, not a descent
     direction) hand back the caller's previous count, as ALGLIB's state->nfev."""
@@ -142,7 +152,7 @@ def mcsrch(fun, x, f, g, d, stp, gtol, trim, trace, nfev=0):
         stp = STPMAX
     if stp <= 0:
         return f, stp, info, nfev
-    dginit = dot(g, d)
+    dginit = dginit_dot(g, d)
     if dginit >= 0:
         return f, stp, info, nfev
     nfev = 0
@@ -167,10 +177,13 @@ def mcsrch(fun, x, f, g, d, stp, gtol, trim, trace, nfev=0):
         if (brackt and (stp <= stmin or stp >= stmax)) or nfev >= MAXFEV - 1 or infoc == 0 or \
                 (brackt and stmax - stmin <= XTOL * stmax):
             stp = b[0]
-        x[:] = wa + stp * d
+        if store is None:
+            x[:] = wa + stp * d
+        else:  # the device's trial point: xk + (T)stp * d in T (one rounding: the FMA of k_axpy_out / the fold)
+            x[:] = (wa + float(store(stp)) * d).astype(store)
         f, gn = fun(x.copy())
         f = float(f)
-        g[:] = gn
+        g[:] = gn if store is None else np.asarray(gn).astype(store)
         if trace is not None:
             trace.append(f)
         if f >= trim:  # trimfunction
@@ -214,16 +227,19 @@ def mcsrch(fun, x, f, g, d, stp, gtol, trim, trace, nfev=0):
             width = abs(b[3] - b[0])
 
 
-def linminnormalized(d, stp):
-    mx = float(np.max(np.abs(d))) if d.size else 0.0
+def linminnormalized(d, stp, store=None, maxsum=False, dot_=dot, keep=None):
+    a = np.abs(d[:keep])
+    mx = (float(np.sum(a)) if maxsum else float(np.max(a))) if a.size else 0.0
     if mx == 0:
         return stp
     s = 1 / mx
     d *= s
     stp = stp / s
-    s = dot(d, d)
+    s = dot_(d, d)
     s = 1 / math.sqrt(s)
     d *= s
+    if store is not None:  # the normalised direction as the device forms it: (T)((dn s1) s2)
+        d[:] = d.astype(store)
     return stp / s
 
 
@@ -233,20 +249,72 @@ class Report:
         self.iterations = 0
         self.nfev = 0
         self.f = 0.0
+        self.updates = 0  # successful iterations (k): history pairs the direction was formed from, counting overwritten ones
 
 
-def minlbfgs(fun, x0, m, epsg, epsf, epsx, maxits, trace=None, xrep=None):
+def _gram_direction(g, sk, yk, rho, k, q, m, swap):
+    """-work by run_lbfgs's host loops (ALGLIB's two loops on the coefficients over {g, s_j, y_j}, each dot product from
+    the Gram table), the table's s_a.y_b entries transposed when swap."""
+    SY = np.array([[dot(sk[a], yk[b]) for b in range(m)] for a in range(m)])
+    YY = np.array([[dot(yk[a], yk[b]) for b in range(m)] for a in range(m)])
+    if swap:
+        SY = SY.T.copy()
+    gs = [dot(g, sk[j]) for j in range(m)]
+    gy = [dot(g, yk[j]) for j in range(m)]
+    live = q + 1
+    p = k % m
+    gammak = SY[p, p] / YY[p, p]
+    cgc, cs, cy, theta = 1.0, np.zeros(m), np.zeros(m), np.zeros(m)
+    for i in range(k, k - q - 1, -1):
+        ic = i % m
+        t = cgc * gs[ic]
+        for j in range(live):
+            t += cy[j] * SY[ic, j]
+        theta[ic] = t
+        cy[ic] -= t * rho[ic]
+    cgc *= gammak
+    cy[:live] *= gammak
+    for i in range(k - q, k + 1):
+        ic = i % m
+        t = cgc * gy[ic]
+        for j in range(live):
+            t += cs[j] * SY[j, ic] + cy[j] * YY[ic, j]
+        cs[ic] += rho[ic] * (-t + theta[ic])
+    w = cgc * g
+    for j in range(live):
+        w = w + cs[j] * sk[j] + cy[j] * yk[j]
+    return -w
+
+
+def minlbfgs(fun, x0, m, epsg, epsf, epsx, maxits, trace=None, xrep=None, store=None, plant=None):
     """Minimise fun(x) -> (f, g).  trace: f of every evaluation, in order; xrep: (x, f) of every point ALGLIB reports
-    (the start point, then the accepted point of every iteration).  Returns (x, Report)."""
+    (the start point, then the accepted point of every iteration).  store, plant: the hooks of the module docstring
+    (default off).  Returns (x, Report)."""
     assert m >= 1
     if epsg == 0 and epsf == 0 and epsx == 0 and maxits == 0:
         epsx = 1.0e-6
+    kind, arg = plant if plant is not None else (None, None)
     x = np.array(x0, dtype=np.float64).ravel().copy()
     n = x.size
+    if kind == "lose":
+        def pdot(a, b):
+            return dot(a[:arg], b[:arg])
+
+        def psq(v):
+            return seqsum(v[:arg] * v[:arg])
+    else:
+        pdot = dot
+
+        def psq(v):
+            return seqsum(v * v)
+    if store is not None:
+        x = x.astype(store).astype(np.float64)
     rep = Report()
     f, g = fun(x.copy())
     f = float(f)
     g = np.array(g, dtype=np.float64).ravel().copy()
+    if store is not None:
+        g = g.astype(store).astype(np.float64)
     if trace is not None:
         trace.append(f)
     trim = 10 * (abs(f) + 1)  # trimprepare
@@ -259,7 +327,7 @@ def minlbfgs(fun, x0, m, epsg, epsf, epsx, maxits, trace=None, xrep=None):
         rep.f = f
         return x, rep
     d = -g
-    stp = min(1.0 / math.sqrt(dot(g, g)), 1.0)
+    stp = min(1.0 / math.sqrt(pdot(g, g)), 1.0)
     sk = np.zeros((m, n))
     yk = np.zeros((m, n))
     rho = np.zeros(m)
@@ -273,15 +341,21 @@ def minlbfgs(fun, x0, m, epsg, epsf, epsx, maxits, trace=None, xrep=None):
         yk[p] = -g
         if k != 0:
             stp = 1.0
-        stp = linminnormalized(d, stp)
-        f, stp, mcinfo, nfev = mcsrch(fun, x, f, g, d, stp, GTOL, trim, trace, nfev)
+        stp = linminnormalized(d, stp, store, kind == "maxsum", pdot, arg if kind == "lose" else None)
+        f, stp, mcinfo, nfev = mcsrch(fun, x, f, g, d, stp, GTOL, trim, trace, nfev, store, pdot)
         if xrep is not None:
             xrep.append((x.copy(), f))
         rep.nfev += nfev
         rep.iterations += 1
         sk[p] += x
         yk[p] += g
-        v = seqsum(g * g)
+        if store is not None:  # s = -x_k + x, y = -g_k + g in T
+            sk[p] = sk[p].astype(store)
+            yk[p] = yk[p].astype(store)
+        if kind == "lose":
+            sk[p][arg:] = 0.0
+            yk[p][arg:] = 0.0
+        v = psq(g)
         if not math.isfinite(v) or not math.isfinite(f):
             rep.termination_type = -8
             break
@@ -294,36 +368,43 @@ def minlbfgs(fun, x0, m, epsg, epsf, epsx, maxits, trace=None, xrep=None):
         if fold - f <= epsf * max(abs(fold), max(abs(f), 1.0)):
             rep.termination_type = 1
             break
-        if math.sqrt(seqsum(sk[p] * sk[p])) <= epsx:
+        if math.sqrt(psq(sk[p])) <= epsx:
             rep.termination_type = 2
             break
         if mcinfo != 1:
             fold = f
             d = -g
         else:
-            v = dot(yk[p], sk[p])
-            vv = dot(yk[p], yk[p])
+            v = pdot(yk[p], sk[p])
+            vv = pdot(yk[p], yk[p])
             if v == 0 or vv == 0:
                 rep.termination_type = -2
                 break
             rho[p] = 1 / v
             gammak = v / vv
-            work = g.copy()
-            for i in range(k, k - q - 1, -1):
-                ic = i % m
-                v = dot(sk[ic], work)
-                theta[ic] = v
-                vv = v * rho[ic]
-                work += (-vv) * yk[ic]   # ae_v_subd = ae_v_addd with -alpha
-            work *= gammak
-            for i in range(k - q, k + 1):
-                ic = i % m
-                v = dot(yk[ic], work)
-                vv = rho[ic] * (-v + theta[ic])
-                work += vv * sk[ic]
-            d = -work
+            if kind == "swap":
+                d = _gram_direction(g, sk, yk, rho, k, q, m, True)
+            else:
+                qq = q - 1 if (kind == "drop_oldest" and k >= m and m >= 2) else q
+                work = g.copy()
+                for i in range(k, k - qq - 1, -1):
+                    ic = i % m
+                    v = pdot(sk[ic], work)
+                    theta[ic] = v
+                    vv = v * rho[ic]
+                    work += (-vv) * yk[ic]   # ae_v_subd = ae_v_addd with -alpha
+                work *= gammak
+                for i in range(k - qq, k + 1):
+                    ic = i % m
+                    v = pdot(yk[ic], work)
+                    vv = rho[ic] * (-v + theta[ic])
+                    work += vv * sk[ic]
+                d = -work
+            if store is not None:  # dn in T
+                d = d.astype(store).astype(np.float64)
             fold = f
             k += 1
+            rep.updates = k
     rep.f = f
     return x, rep
 
