@@ -32,11 +32,11 @@
  *     library enqueues runs on the legacy stream.
  *   - entry points that take HOST pointers (srmap_eval, srmap_solve*,
  *     srmap_cg_trace, srmap_apply*, srmap_reg_values*, srmap_set_observations,
- *     srmap_set_irls_weights, srmap_channel_map, srmap_channel_pca,
+ *     srmap_set_irls_weights, srmap_set_data_weights, srmap_get_data_weights, srmap_channel_map, srmap_channel_pca,
  *     srmap_register_translational, srmap_upload / srmap_download) run on the
  *     context's stream and are complete when they return.
- *   - the problem's device state (observations, IRLS weights) is ordered by the
- *     library itself: a write through srmap_update_irls_weights_device on one
+ *   - the problem's device state (observations, IRLS weights, data weights) is ordered by the
+ *     library itself: a write through srmap_update_irls_weights_device / srmap_update_data_weights_device on one
  *     stream is waited for (an event) by evaluations on another, and a writer
  *     first drains the stream of the LAST evaluation when it is a different one.
  *     Only that one: a problem may have evaluations in flight on ONE stream at a
@@ -187,6 +187,41 @@ int srmap_set_irls_weights(srmap_problem* p, int reg, const double* w_host);
  * Enqueued on hip_stream (NULL = the context's stream) and NOT waited for:
  * later evaluations on any stream are ordered after it by the library. */
 int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_dev, void* hip_stream);
+
+/* ------------------------------------------- robust data term (weights, Huber) */
+/* Per-observation weights of the data term (no reference counterpart: the reference's data term is plain least
+ * squares, objective_data_term.cpp:29-50).  With weights w, shaped and indexed exactly like the observations
+ * ([K][C][h][w]; the channel views of split_channels and the rows of srmap_problem_set_cost_rows apply to them as to
+ * the observations), the data cost is s^2 sum_k sum_i w[k][i] r[k][i]^2 and its gradient 2 s^2 sum_k A_k^T (w[k] .* r[k]),
+ * r[k] = A_k x - y_k.  A weight of 0 removes a pixel ("ignore these pixels": dead pixels, a frame that failed to
+ * register).  NULL = all ones: the unweighted kernels, today's behaviour.  Weights must be finite and >= 0
+ * (SRMAP_EINVAL otherwise; the device form trusts the caller).  They persist across srmap_set_observations.
+ * A problem with weights (or a Huber loss) evaluates through weighted instances of the forward kernels; the tile
+ * family then takes its forward-residual plan for integer shifts too (forward kernel, ring pass, tile gather: DESIGN.md
+ * section 3.5), and a problem without a MotionModule (shifts_xy == NULL) runs the direct family.  Solves and evaluations
+ * sharded over a communicator of more than one rank answer SRMAP_EUNSUPPORTED for such a problem. */
+int srmap_set_data_weights(srmap_problem* p, const double* w_host);
+/* The same from a device buffer holding the problem dtype, copied on hip_stream (NULL = the context's stream);
+ * complete on return.  No reference counterpart. */
+int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip_stream);
+/* The current weights ([K][C][h][w] host doubles; ones if none are set): after a Huber solve, the outlier map -- the
+ * pixels the solve down-weighted.  No reference counterpart. */
+int srmap_get_data_weights(srmap_problem* p, double* w_host);
+/* Loss of the data term (no reference counterpart).  SRMAP_DATA_LOSS_L2: the quadratic above with the caller's
+ * weights, which a solve leaves untouched.  SRMAP_DATA_LOSS_HUBER: srmap_solve minimises
+ * s^2 sum rho(r), rho(r) = r^2 for |r| <= huber_delta and huber_delta (2 |r| - huber_delta) beyond, by IRLS: the data
+ * weights are reset to 1 where the regulariser's are, and re-derived from the iterate after every inner run
+ * (srmap_update_data_weights_device) together with the regulariser's; the loop runs its rounds even without a
+ * regulariser; the reported cost is the weighted quadratic cost of the last inner run.  Huber OWNS the weight buffer:
+ * weights the caller set are overwritten by the solve (a mask combined with Huber is not supported), and
+ * srmap_get_data_weights afterwards returns the final Huber weights.  huber_delta is in the units of the observations;
+ * it must be finite and > 0 for HUBER (ignored for L2).  An unknown loss or a bad delta: SRMAP_EINVAL. */
+typedef enum { SRMAP_DATA_LOSS_L2 = 0, SRMAP_DATA_LOSS_HUBER = 1 } srmap_data_loss;
+int srmap_problem_set_data_loss(srmap_problem* p, int loss /* srmap_data_loss */, double huber_delta);
+/* One Huber re-weighting step (no reference counterpart): w = 1 where |r| <= huber_delta, huber_delta / |r| elsewhere,
+ * r = A x - y at x_dev (UNWEIGHTED residuals: one forward pass plus one elementwise pass over [K][C][h][w]).  Needs a
+ * HUBER loss.  Enqueued on hip_stream and not waited for, ordered like srmap_update_irls_weights_device. */
+int srmap_update_data_weights_device(srmap_problem* p, const void* x_dev, void* hip_stream);
 
 /* ------------------------------------------------------- operators (host) */
 /* ImageModel::ApplyToImage(ImageData*, index) image_model.cpp:86-91:

@@ -8,6 +8,7 @@
 //       (kernels_tiled.hip) do not cover the geometry, and their cross-check.
 //
 // Math: SURVEY.md section 8(a'); reference lines are cited per kernel.
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 
@@ -71,13 +72,14 @@ __device__ __forceinline__ T warp_sample(const T* __restrict__ plane, int W, int
 // Forward model A_k = D B M_k (image_model.cpp:86-91) at every LR pixel of
 // frames [k0, k0+gridDim.z), optionally minus the observation, optionally with
 // the data-term cost partial s^2 * sum(res^2) (objective_data_term.cpp:29-50).
-template <typename T>
+// WEIGHTED (compile time; needs y): per-observation weights dw indexed like y -- out = w * res, partial s^2 * sum(w res^2).
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_forward_direct(
     const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out,
     double* __restrict__ partials, Geometry g,
     const WarpTaps<T>* __restrict__ warps, const T* __restrict__ blur,
     const int* __restrict__ col_map, const int* __restrict__ row_map, int k0,
-    double cost_scale, int obs_C, int obs_c0) {
+    double cost_scale, int obs_C, int obs_c0, const T* __restrict__ dw) {
   __shared__ double red[4];
   __shared__ T comb[36];  // blur (x) bilinear taps of this block's frame, (b+1) x (b+1), b <= 5
   const int lp = blockIdx.x * 256 + threadIdx.x;
@@ -123,10 +125,19 @@ __global__ __launch_bounds__(256) void k_forward_direct(
       }
     }
     T res = acc;
-    if (y) res -= y[((size_t)k * obs_C + c + obs_c0) * n + lp];
-    out[((size_t)kk * g.C + c) * n + lp] = res;
-    // cost rows (row-band sharding): LR row i counts when its first HR row is in [cr0, cr1)
-    sq = (i * g.s >= g.cr0 && i * g.s < g.cr1) ? (double)res * (double)res : 0.0;
+    if (WEIGHTED) {
+      const size_t oi = ((size_t)k * obs_C + c + obs_c0) * n + lp;
+      const T yv = y[oi], wv = dw[oi];  // requested together
+      res -= yv;
+      const T wr = wv * res;
+      out[((size_t)kk * g.C + c) * n + lp] = wr;
+      sq = (i * g.s >= g.cr0 && i * g.s < g.cr1) ? (double)wr * (double)res : 0.0;
+    } else {
+      if (y) res -= y[((size_t)k * obs_C + c + obs_c0) * n + lp];
+      out[((size_t)kk * g.C + c) * n + lp] = res;
+      // cost rows (row-band sharding): LR row i counts when its first HR row is in [cr0, cr1)
+      sq = (i * g.s >= g.cr0 && i * g.s < g.cr1) ? (double)res * (double)res : 0.0;
+    }
   }
   if (partials) {
     const double s = block_sum_256(sq, red);
@@ -139,14 +150,71 @@ __global__ __launch_bounds__(256) void k_forward_direct(
 template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
-                          double* partials, int* nblocks, hipStream_t st) {
+                          double* partials, int* nblocks, hipStream_t st, const T* dw) {
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
-  hipLaunchKernelGGL(k_forward_direct<T>, grid, dim3(256), 0, st, x, y, out, partials, g,
-                     p->has_motion ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr,
-                     (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C,
-                     obs_c0);
+  if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
+  const WarpTaps<T>* warps = p->has_motion ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr;
+  if (dw != nullptr)
+    hipLaunchKernelGGL((k_forward_direct<T, true>), grid, dim3(256), 0, st, x, y, out, partials, g, warps,
+                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
+  else
+    hipLaunchKernelGGL((k_forward_direct<T, false>), grid, dim3(256), 0, st, x, y, out, partials, g, warps,
+                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C,
+                       obs_c0, dw);
   if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  return SRMAP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Huber IRLS weights of the data term from the UNWEIGHTED residuals: w = 1 where |r| <= delta, delta / |r| elsewhere
+// (continuous at |r| = delta), arithmetic in T.  Elementwise and HBM-bound: one read and one write stream.  `rows` runs of
+// `rowlen` elements (blockIdx.y = run; a channel view of [K][C][h][w] is K runs, the whole stack one).  VEC: every run
+// starts on a 16-byte boundary in both buffers -- 16-byte accesses in a grid-stride loop, the run's last elements one by one.
+template <typename T>
+__device__ __forceinline__ T huber_weight(T r, T delta) {
+  const T a = r < T(0) ? -r : r;
+  return a <= delta ? T(1) : delta / a;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, T* __restrict__ w, size_t rowlen,
+                                                      size_t r_stride, size_t w_stride, T delta) {
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
+  const T* rr = r + (size_t)blockIdx.y * r_stride;
+  T* ww = w + (size_t)blockIdx.y * w_stride;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nv = rowlen / V;
+    for (size_t i = tid; i < nv; i += nth) {
+      const VT v = reinterpret_cast<const VT*>(rr)[i];
+      VT o;
+#pragma unroll
+      for (int q = 0; q < V; ++q) o[q] = huber_weight<T>(v[q], delta);
+      reinterpret_cast<VT*>(ww)[i] = o;
+    }
+    done = nv * V;
+  }
+  for (size_t i = done + tid; i < rowlen; i += nth) ww[i] = huber_weight<T>(rr[i], delta);
+}
+
+template <typename T>
+int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
+                         double delta, hipStream_t st) {
+  constexpr size_t V = 16 / sizeof(T);
+  if (rows == 0 || rowlen == 0) return SRMAP_OK;
+  if (rows > 1 && r_stride == rowlen && w_stride == rowlen) { rowlen *= rows; rows = 1; }  // one contiguous run
+  const bool vec = (reinterpret_cast<uintptr_t>(r) % 16 == 0) && (reinterpret_cast<uintptr_t>(w) % 16 == 0) &&
+                   (rows == 1 || (r_stride % V == 0 && w_stride % V == 0));
+  // grid-stride: enough workgroups to fill the device several times over, no more than the run has 16-byte groups
+  const size_t groups = (rowlen + V * 256 - 1) / (V * 256);
+  const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
+  dim3 grid((unsigned)std::max<size_t>(1, std::min(groups, (cap + rows - 1) / rows)), (unsigned)rows);
+  if (vec) hipLaunchKernelGGL((k_huber_weights<T, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta);
+  else hipLaunchKernelGGL((k_huber_weights<T, false>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
@@ -1043,7 +1111,9 @@ int launch_reduce_partials(srmap_problem* p, const double* partials, int n, doub
 #define INSTANTIATE(T)                                                                      \
   template int launch_forward_direct<T>(srmap_problem*, const Geometry&, const T*,         \
                                         const T*, int, int, T*, int, int, double*, int*,   \
-                                        hipStream_t);                                       \
+                                        hipStream_t, const T*);                             \
+  template int launch_huber_weights<T>(srmap_problem*, const T*, T*, size_t, size_t, size_t, size_t, double,  \
+                                       hipStream_t);                                        \
   template int launch_gather_direct<T>(srmap_problem*, const Geometry&, const T*, T*, int, \
                                        int, double, bool, hipStream_t, int, T*);            \
   template int launch_reg_values<T>(srmap_problem*, const Geometry&, const RegSpec&,       \

@@ -66,6 +66,7 @@ struct SpfArgs {
   T* xout;
   T fold_stp;
   const double* fold_norms;
+  const T* dw;  // WEIGHTED instances: the data weights, indexed like y
 };
 
 __device__ __forceinline__ int fdiv_rt(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
@@ -76,7 +77,10 @@ __device__ __forceinline__ double wave_sum64(double v) {
   return v;
 }
 
-template <typename T, int S, int B, bool FOLD>
+// WEIGHTED (per-observation weights of the data term, srmap_set_data_weights / the Huber loss): the weight is requested
+// with the observation, the residual buffer receives w * r (what every gather downstream multiplies A^T onto) and the
+// cost partial w * r^2.  A compile-time leg: the unweighted instances carry no trace of it.
+template <typename T, int S, int B, bool FOLD, bool WEIGHTED>
 __global__ __launch_bounds__(64 * kNW) void k_forward_sp(SpfArgs<T> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* xs = reinterpret_cast<T*>(smem_raw);
@@ -183,11 +187,12 @@ __global__ __launch_bounds__(64 * kNW) void k_forward_sp(SpfArgs<T> A) {
   const size_t lp = (size_t)i * A.wl + j;
   constexpr int U = 4;  // frames per round: their observations are requested together
   for (int kb = par; kb < A.K; kb += kNFG * U) {
-    T yv[U];
+    T yv[U], wv[WEIGHTED ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = kb + kNFG * u;
       yv[u] = (valid && k < A.K) ? A.y[((size_t)k * A.obs_C + ch + A.obs_c0) * nl + lp] : T(0);
+      if (WEIGHTED) wv[u] = (valid && k < A.K) ? A.dw[((size_t)k * A.obs_C + ch + A.obs_c0) * nl + lp] : T(0);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -218,8 +223,14 @@ __global__ __launch_bounds__(64 * kNW) void k_forward_sp(SpfArgs<T> A) {
       }
       const T res = acc - yv[u];
       if (valid) {
-        A.out[((size_t)k * A.C + ch) * nl + lp] = res;
-        if (cost_row) sq += (double)res * (double)res;
+        if (WEIGHTED) {
+          const T wr = wv[u] * res;
+          A.out[((size_t)k * A.C + ch) * nl + lp] = wr;
+          if (cost_row) sq += (double)wr * (double)res;
+        } else {
+          A.out[((size_t)k * A.C + ch) * nl + lp] = res;
+          if (cost_row) sq += (double)res * (double)res;
+        }
       }
     }
   }
@@ -271,8 +282,9 @@ bool upload_frames(const srmap_problem* p, SpForwardPlan* sp) {
 
 template <typename T, int S, int B>
 int launch_typed(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y, int obs_C,
-                 int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st, const SpFold& fold) {
+                 int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st, const SpFold& fold, const T* dw) {
   SpfArgs<T> A;
+  A.dw = dw;
   A.fold_xk = (const T*)fold.xk; A.dvec = (const T*)fold.dvec; A.xout = const_cast<T*>(x); A.fold_stp = (T)fold.stp;
   A.fold_norms = fold.norms;
   if (fold.xk != nullptr && !sp.can_fold)
@@ -286,18 +298,27 @@ int launch_typed(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp,
   A.cost_scale = (double)geo.s * (double)geo.s;
   dim3 grid((unsigned)((geo.w + kCW - 1) / kCW), (unsigned)((geo.h + kLRH - 1) / kLRH), (unsigned)geo.C);
   const size_t lds = (size_t)sp.XR * S * sp.XC * sizeof(T);
-  if (fold.xk != nullptr) hipLaunchKernelGGL((k_forward_sp<T, S, B, true>), grid, dim3(64 * kNW), lds, st, A);
-  else hipLaunchKernelGGL((k_forward_sp<T, S, B, false>), grid, dim3(64 * kNW), lds, st, A);
+  if (dw != nullptr) {
+    if (fold.xk != nullptr) hipLaunchKernelGGL((k_forward_sp<T, S, B, true, true>), grid, dim3(64 * kNW), lds, st, A);
+    else hipLaunchKernelGGL((k_forward_sp<T, S, B, false, true>), grid, dim3(64 * kNW), lds, st, A);
+  } else {
+    if (fold.xk != nullptr) hipLaunchKernelGGL((k_forward_sp<T, S, B, true, false>), grid, dim3(64 * kNW), lds, st, A);
+    else hipLaunchKernelGGL((k_forward_sp<T, S, B, false, false>), grid, dim3(64 * kNW), lds, st, A);
+  }
   SRMAP_HIP(p->ctx, hipGetLastError());
   *nblocks = (int)(grid.x * grid.y * grid.z);
   return SRMAP_OK;
 }
 
 template <typename T, int S, int B>
-void preload_typed() {
+void preload_typed(bool weighted) {
   hipFuncAttributes attr;
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, false>));
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, true>));
+  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, false, false>));
+  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, true, false>));
+  if (weighted) {
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, false, true>));
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, true, true>));
+  }
 }
 
 }  // namespace
@@ -330,14 +351,15 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   sp->RF0 = std::min(sp->RLO, 0); sp->NRF = std::max(sp->RLO + sp->XR, S * kLRH) - sp->RF0;
   sp->CF0 = std::min(sp->CLO, 0); sp->NCF = std::max(sp->CLO + sp->XC, kCW) - sp->CF0;
   sp->can_fold = sp->NRF <= kMaxRowsPerWave * kNW && sp->NCF <= 2 * kCW;
+  const bool wt = p->robust();
   if (p->dtype == SRMAP_F32) {
-    if (S == 2 && B == 1) preload_typed<float, 2, 1>(); else if (S == 2) preload_typed<float, 2, 3>();
-    else if (S == 3 && B == 1) preload_typed<float, 3, 1>(); else if (S == 3) preload_typed<float, 3, 3>();
-    else if (B == 1) preload_typed<float, 4, 1>(); else preload_typed<float, 4, 3>();
+    if (S == 2 && B == 1) preload_typed<float, 2, 1>(wt); else if (S == 2) preload_typed<float, 2, 3>(wt);
+    else if (S == 3 && B == 1) preload_typed<float, 3, 1>(wt); else if (S == 3) preload_typed<float, 3, 3>(wt);
+    else if (B == 1) preload_typed<float, 4, 1>(wt); else preload_typed<float, 4, 3>(wt);
   } else {
-    if (S == 2 && B == 1) preload_typed<double, 2, 1>(); else if (S == 2) preload_typed<double, 2, 3>();
-    else if (S == 3 && B == 1) preload_typed<double, 3, 1>(); else if (S == 3) preload_typed<double, 3, 3>();
-    else if (B == 1) preload_typed<double, 4, 1>(); else preload_typed<double, 4, 3>();
+    if (S == 2 && B == 1) preload_typed<double, 2, 1>(wt); else if (S == 2) preload_typed<double, 2, 3>(wt);
+    else if (S == 3 && B == 1) preload_typed<double, 3, 1>(wt); else if (S == 3) preload_typed<double, 3, 3>(wt);
+    else if (B == 1) preload_typed<double, 4, 1>(wt); else preload_typed<double, 4, 3>(wt);
   }
   return true;
 }
@@ -350,18 +372,19 @@ void spfwd_release(SpForwardPlan* sp) {
 
 template <typename T>
 int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y,
-                      int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st, const SpFold& fold) {
+                      int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st, const SpFold& fold,
+                      const T* dw) {
   const int S = geo.s, B = geo.b;
 #define SPF(SS, BB) \
-  if (S == SS && B == BB) return launch_typed<T, SS, BB>(p, geo, sp, x, y, obs_C, obs_c0, out, partials, nblocks, st, fold)
+  if (S == SS && B == BB) return launch_typed<T, SS, BB>(p, geo, sp, x, y, obs_C, obs_c0, out, partials, nblocks, st, fold, dw)
   SPF(2, 1); SPF(2, 3); SPF(3, 1); SPF(3, 3); SPF(4, 1); SPF(4, 3);
 #undef SPF
   return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no forward tile kernel for scale %d blur %d", S, B);
 }
 
 template int launch_forward_sp<float>(srmap_problem*, const Geometry&, const SpForwardPlan&, const float*,
-                                      const float*, int, int, float*, double*, int*, hipStream_t, const SpFold&);
+                                      const float*, int, int, float*, double*, int*, hipStream_t, const SpFold&, const float*);
 template int launch_forward_sp<double>(srmap_problem*, const Geometry&, const SpForwardPlan&, const double*,
-                                       const double*, int, int, double*, double*, int*, hipStream_t, const SpFold&);
+                                       const double*, int, int, double*, double*, int*, hipStream_t, const SpFold&, const double*);
 
 }  // namespace srmap

@@ -564,7 +564,14 @@ bool ztile_plan(srmap_problem* p) {
   }
   std::vector<int> ox(K, 0), oy(K, 0);
   int amax = 0;
-  bool subpix = false;
+  // Data weights / a Huber loss: the plan takes the forward-residual form below whatever the shifts are.  The integer-shift
+  // tiles recompute residuals inside the tile (z_row / border_residual, ztile_dev.hpp) and carry no weighted leg; the
+  // forward-residual form gathers a residual BUFFER, which the weighted forward kernel fills with w .* r.  An integer
+  // shift is its one-tap case: the source table and the forward kernel's stencils walk ntaps taps.  Without a
+  // MotionModule there are no warp records for that form (ring kernel, forward tile kernel): the direct family runs.
+  const bool robust = p->robust();
+  if (robust && !p->has_motion) return false;
+  bool subpix = robust;
   if (p->has_motion) {
     for (int k = 0; k < K; ++k) {
       const WarpTaps<double>& f = p->fwd_warps[k];
@@ -988,10 +995,11 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
     if (!p->d_resid) SRMAP_HIP(p->ctx, hipMalloc(&p->d_resid, p->lr_count() * sizeof(T)));
     if (req.fold.xk != nullptr && !(with_d && z.spf.ok && z.spf.can_fold))
       return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
+    const T* dw = (const T*)p->d_dw;  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
     if (z.spf.ok)
-      rc = launch_forward_sp<T>(p, geo, z.spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st, req.fold);
+      rc = launch_forward_sp<T>(p, geo, z.spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st, req.fold, dw);
     else
-      rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st);
+      rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st, dw);
     if (rc) return rc;
     partials += nfwd;
     if (ring_ahead) {
@@ -1078,6 +1086,18 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
   *nblocks = total;
   return SRMAP_OK;
 }
+
+template <typename T>
+int launch_forward_residual(srmap_problem* p, const Geometry& geo, int obs_c0, const T* x, double* partials, hipStream_t st) {
+  const ZPlan* z = p->impl != SRMAP_IMPL_DIRECT ? static_cast<const ZPlan*>(p->zplan) : nullptr;
+  if (!p->d_resid) SRMAP_HIP(p->ctx, hipMalloc(&p->d_resid, p->lr_count() * sizeof(T)));
+  int nfwd = 0;
+  if (z != nullptr && z->subpix && z->spf.ok)
+    return launch_forward_sp<T>(p, geo, z->spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st);
+  return launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st);
+}
+template int launch_forward_residual<float>(srmap_problem*, const Geometry&, int, const float*, double*, hipStream_t);
+template int launch_forward_residual<double>(srmap_problem*, const Geometry&, int, const double*, double*, hipStream_t);
 
 template int launch_eval_ztile<float>(srmap_problem*, const EvalReq&, EvalOut*, const Geometry&, int, unsigned,
                                       const float*, float*, double*, int*, hipStream_t);

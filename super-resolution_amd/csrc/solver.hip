@@ -1395,6 +1395,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   const bool lbfgs = p->solver == SRMAP_SOLVER_LBFGS;
   if (lbfgs && mode != SRMAP_SHARD_NONE)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
+  const bool huber = p->data_loss == SRMAP_DATA_LOSS_HUBER;
+  if (p->robust() && mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator (the weights are not split with the frames or rows): run the solve unsharded");
   if (mode != SRMAP_SHARD_NONE && opt->split_channels)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
   if (mode == SRMAP_SHARD_ROWS &&
@@ -1455,6 +1458,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   }
   int rc = cg.alloc();
   if (rc == SRMAP_OK && lbfgs) rc = cg.alloc_lbfgs(p->lbfgs_m);
+  if (rc == SRMAP_OK && huber && !p->d_dw) rc = set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
   // IRLS weights live in the problem's RegSpec (full [C][H][W]); make sure they exist.
   for (int r = 0; r < p->nreg && rc == SRMAP_OK; ++r) {
     if (!p->reg[r].weights) {
@@ -1472,6 +1476,12 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     // w <- 1  (irls_map_solver.cpp:66-74)
     for (int r = 0; r < p->nreg; ++r)
       hipLaunchKernelGGL(k_fill<T>, dim3(cg.blocks()), dim3(256), 0, st, (T*)p->reg[r].weights + (size_t)c0 * N, T(1), npts);
+    if (huber) {  // the data weights of this round's channels likewise ([K][C][h][w]: one run per frame)
+      const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
+      for (int k = 0; k < geo.K; ++k)
+        hipLaunchKernelGGL(k_fill<T>, dim3((unsigned)((run + 255) / 256)), dim3(256), 0, st,
+                           (T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run);
+    }
     double previous_cost = INFINITY;
     double cost_difference = o.irls_cost_difference_threshold + 1.0;
     int ran = 0;
@@ -1487,7 +1497,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       rep.cg_iterations += cr.its;
       rep.last_termination = cr.type;
       rep.final_cost = cr.f;
-      if (p->nreg == 0) { ran++; break; }
+      if (p->nreg == 0 && !huber) { ran++; break; }
       // w = 1/max(1e-5, reg(x)), :128-143 -- on fresh halos (the weights of a halo plane / halo rows feed the
       // owned gradient through the neighbour terms)
       rc = shard_exchange_x(p, comm, mode == SRMAP_SHARD_NONE ? nullptr : shard, cg.x, st);
@@ -1496,6 +1506,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
         rc = launch_reg_weights<T>(p, vg, p->reg[r], (const T*)cg.x, (T*)p->reg[r].weights + (size_t)c0 * N, st);
         if (rc) break;
       }
+      if (rc) break;
+      // Huber: the data weights from the residuals at the same iterate
+      if (huber) rc = update_data_weights(p, c0, per_split, cg.x, st);
       if (rc) break;
       cost_difference = previous_cost - cr.f;
       previous_cost = cr.f;
@@ -1566,6 +1579,8 @@ int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_sh
   if (!p || !x_dev) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  if (p->robust() && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator: evaluate unsharded");
   EvalOut out;
   int rc = shard_eval(p, comm, shard, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;

@@ -269,7 +269,7 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
       if (rc) return rc;
       int nb = 0;
       rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, c0,
-                                    (T*)p->d_resid, 0, geo.K, p->d_partials + nparts, &nb, st);
+                                    (T*)p->d_resid, 0, geo.K, p->d_partials + nparts, &nb, st, (const T*)p->d_dw);
       if (rc) return rc;
       nparts += nb;
       if (g) {
@@ -338,6 +338,58 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
   if (int rc = state_read(p, st)) return rc;
   if (p->dtype == SRMAP_F32) return eval_typed<float>(p, req, out, terms, (const float*)x, (float*)g, st);
   return eval_typed<double>(p, req, out, terms, (const double*)x, (double*)g, st);
+}
+
+template <typename T>
+__global__ void k_fill_value(T* __restrict__ d, T v, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) d[i] = v;
+}
+
+// Weights or the loss changed whether the problem is robust(): the tile plan has another form then (ztile_plan)
+static void replan_if(srmap_problem* p, bool was_robust) {
+  if (p->robust() == was_robust) return;
+  p->plan_gen++;
+  if (ztile_plan(p)) ztile_preload(p);
+}
+
+// allocate the data weights (all ones) if there are none
+static int ensure_data_weights(srmap_problem* p, hipStream_t st) {
+  if (p->d_dw) return SRMAP_OK;
+  const size_t n = p->lr_count();
+  SRMAP_HIP(p->ctx, hipMalloc(&p->d_dw, n * p->elem()));
+  if (p->dtype == SRMAP_F32) hipLaunchKernelGGL(k_fill_value<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float*)p->d_dw, 1.f, n);
+  else hipLaunchKernelGGL(k_fill_value<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (double*)p->d_dw, 1.0, n);
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  return SRMAP_OK;
+}
+
+template <typename T>
+static int update_data_weights_typed(srmap_problem* p, int c0, int C, const T* x, hipStream_t st) {
+  Geometry geo = p->geo;
+  if (C > 0) geo.C = C; else c0 = 0;
+  int rc = ensure_partials(p, partials_needed(p));
+  if (rc) return rc;
+  rc = launch_forward_residual<T>(p, geo, c0, x, p->d_partials, st);  // d_resid: [K][geo.C][h][w], unweighted
+  if (rc) return rc;
+  const size_t nl = (size_t)geo.w * geo.h;
+  return launch_huber_weights<T>(p, (const T*)p->d_resid, (T*)p->d_dw + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
+                                 (size_t)geo.C * nl, (size_t)p->geo.C * nl, p->huber_delta, st);
+}
+
+int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st) {
+  if (p->data_loss != SRMAP_DATA_LOSS_HUBER)
+    return set_error(p->ctx, SRMAP_EINVAL, "the data weights are re-derived for a Huber loss only (srmap_problem_set_data_loss)");
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  rc = ensure_data_weights(p, st);
+  if (rc) return rc;
+  rc = p->dtype == SRMAP_F32 ? update_data_weights_typed<float>(p, c0, C, (const float*)x, st)
+                             : update_data_weights_typed<double>(p, c0, C, (const double*)x, st);
+  if (rc) return rc;
+  return state_end_write(p, st);  // asynchronous: evaluations on other streams wait for this event
 }
 
 int recover_reduction_timeout(srmap_problem* p, double* host_word) {
@@ -526,7 +578,7 @@ void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
   void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_obs, p->d_resid, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
+                  p->d_obs, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
   for (int* t : p->d_ytabs) (void)hipFree(t);
@@ -683,6 +735,85 @@ int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_de
   else rc = launch_reg_weights<double>(p, p->geo, rs, (const double*)x_dev, (double*)rs.weights, st);
   if (rc) return rc;
   return state_end_write(p, st);  // asynchronous: evaluations on other streams wait for this event
+}
+
+// ---- robust data term: per-observation weights, Huber loss (no reference counterpart) ----
+int srmap_set_data_weights(srmap_problem* p, const double* w_host) {
+  if (!p) return SRMAP_EINVAL;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const size_t n = p->lr_count();
+  if (w_host)
+    for (size_t i = 0; i < n; ++i)
+      if (!(w_host[i] >= 0.0) || !std::isfinite(w_host[i]))
+        return set_error(p->ctx, SRMAP_EINVAL, "data weight %zu is %g: weights must be finite and >= 0", i, w_host[i]);
+  hipStream_t st = p->ctx->stream;
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  const bool was = p->robust();
+  if (!w_host) {
+    // all ones: the unweighted kernels again -- except under a Huber loss, which keeps (and owns) the buffer
+    if (p->d_dw) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); (void)hipFree(p->d_dw); p->d_dw = nullptr; }
+    if (p->data_loss == SRMAP_DATA_LOSS_HUBER) rc = ensure_data_weights(p, st);
+  } else {
+    rc = ensure(p, &p->d_dw, n * p->elem());
+    if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw, n, st);
+  }
+  replan_if(p, was);
+  return rc;
+}
+
+int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip_stream) {
+  if (!p) return SRMAP_EINVAL;
+  if (!w_dev) return srmap_set_data_weights(p, nullptr);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  const bool was = p->robust();
+  rc = ensure(p, &p->d_dw, p->lr_count() * p->elem());
+  if (rc) return rc;
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_dw, w_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));  // complete on return, as srmap_set_observations_device
+  replan_if(p, was);
+  return SRMAP_OK;
+}
+
+int srmap_get_data_weights(srmap_problem* p, double* w_host) {
+  if (!p || !w_host) return SRMAP_EINVAL;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const size_t n = p->lr_count();
+  if (!p->d_dw) {
+    for (size_t i = 0; i < n; ++i) w_host[i] = 1.0;
+    return SRMAP_OK;
+  }
+  // the weights may have been written asynchronously on another stream (srmap_update_data_weights_device)
+  if (p->state_stream && p->state_stream != p->ctx->stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->state_stream));
+  return convert_download(p, p->d_dw, w_host, n, p->ctx->stream);
+}
+
+int srmap_problem_set_data_loss(srmap_problem* p, int loss, double huber_delta) {
+  if (!p) return SRMAP_EINVAL;
+  if (loss != SRMAP_DATA_LOSS_L2 && loss != SRMAP_DATA_LOSS_HUBER)
+    return set_error(p->ctx, SRMAP_EINVAL, "unknown data loss %d", loss);
+  if (loss == SRMAP_DATA_LOSS_HUBER && !(huber_delta > 0.0 && std::isfinite(huber_delta)))
+    return set_error(p->ctx, SRMAP_EINVAL, "huber_delta must be finite and > 0 (got %g)", huber_delta);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const bool was = p->robust();
+  p->data_loss = loss;
+  p->huber_delta = loss == SRMAP_DATA_LOSS_HUBER ? huber_delta : 0.0;
+  int rc = SRMAP_OK;
+  if (loss == SRMAP_DATA_LOSS_HUBER) {
+    rc = state_begin_write(p, p->ctx->stream);
+    if (rc == SRMAP_OK) rc = ensure_data_weights(p, p->ctx->stream);
+  }
+  replan_if(p, was);
+  return rc;
+}
+
+int srmap_update_data_weights_device(srmap_problem* p, const void* x_dev, void* hip_stream) {
+  if (!p || !x_dev) return SRMAP_EINVAL;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  return update_data_weights(p, 0, 0, x_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
 }
 
 // ---- operators on host buffers ----

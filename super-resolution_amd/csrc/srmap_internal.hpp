@@ -124,6 +124,12 @@ struct srmap_problem {
   void* d_obs = nullptr;          // [K][C][h][w] dtype
   bool have_obs = false;
   void* d_resid = nullptr;        // [K][C][h][w] dtype scratch
+  void* d_dw = nullptr;           // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
+  int data_loss = SRMAP_DATA_LOSS_L2;  // srmap_problem_set_data_loss; HUBER keeps d_dw allocated (it owns the buffer)
+  double huber_delta = 0.0;
+  // weights or a Huber loss: every evaluation runs a WEIGHTED forward kernel, and the tile plan takes the forward-residual
+  // form for integer shifts too (kernels_ztile.hip ztile_plan)
+  bool robust() const { return d_dw != nullptr || data_loss == SRMAP_DATA_LOSS_HUBER; }
   void* d_regvals = nullptr;      // [C][H][W] dtype scratch
   void* d_x = nullptr;            // [C][H][W] staging for host-buffer entry points
   void* d_g = nullptr;
@@ -173,10 +179,16 @@ void blas_release(srmap_ctx* ctx);
 // cost partials (s^2 * sum of squares, double) appended at partials[0..nblocks).
 // `g` is the geometry of this evaluation (g.C may be a channel sub-range of the
 // problem: y is indexed with the problem's channel count obs_C and offset obs_c0).
+// dw != nullptr (needs y; indexed like y): the WEIGHTED instance -- out = w .* r, partials s^2 * sum(w r^2).
 template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
-                          double* partials, int* nblocks, hipStream_t st);
+                          double* partials, int* nblocks, hipStream_t st, const T* dw = nullptr);
+// w = 1 where |r| <= delta, delta / |r| elsewhere (the Huber loss as an IRLS weight), arithmetic in T.  r: `rows` runs of
+// `rowlen` elements, r_stride apart; w likewise, w_stride apart, starting at w (a channel view of [K][C][h][w]).
+template <typename T>
+int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
+                         double delta, hipStream_t st);
 // g = (accumulate ? g : 0) + 2 s^2 sum_k A_k^T r_k   (r: [K][C][h][w])
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
@@ -214,6 +226,10 @@ size_t ztile_partials_needed(const srmap_problem* p);
 template <typename T>
 int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const Geometry& geo, int obs_c0,
                       unsigned terms, const T* x, T* g, double* partials, int* nblocks, hipStream_t st);
+// d_resid <- A_k x - y_k (UNWEIGHTED) of the channel view geo / obs_c0, by the forward kernel the problem's evaluations use
+// (the forward tile kernel where the plan has one, else the direct kernel); the cost partials it leaves are scratch
+template <typename T>
+int launch_forward_residual(srmap_problem* p, const Geometry& geo, int obs_c0, const T* x, double* partials, hipStream_t st);
 
 // ---- forward tile kernel for sub-pixel shifts (kernels_spfwd.hip) ----
 struct SpForwardPlan {
@@ -225,11 +241,12 @@ struct SpForwardPlan {
 };
 bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp);
 void spfwd_release(SpForwardPlan* sp);
-// out[k][c][h][w] = A_k x - y_k for all frames + cost partials (one per workgroup)
+// out[k][c][h][w] = A_k x - y_k for all frames + cost partials (one per workgroup); dw != nullptr (indexed like y): the
+// WEIGHTED instances, out = w .* r and partials of w r^2
 template <typename T>
 int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y,
                       int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st,
-                      const SpFold& fold = SpFold());
+                      const SpFold& fold = SpFold(), const T* dw = nullptr);
 
 // ---- evaluation (srmap_api.hip) ----
 // One ObjectiveFunction::ComputeAllTerms on device buffers, on the stream st (srmap_eval_device with a request).
@@ -238,6 +255,9 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
 // After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[6]; the host-mapped word
 // host_word when given): re-initialise the granules behind everything in flight and clear both words.
 int recover_reduction_timeout(srmap_problem* p, double* host_word);
+// Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): data weights <- huber(A x - y), enqueued on st
+// (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
+int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
 
 // ---- vector kernels for the solver (solver.hip) ----
 int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,

@@ -4,7 +4,8 @@
 // initial estimate, IRLS-MAP solve on the GPU, optional PSNR against the ground
 // truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
 // least-squares solver as the reference does (super_resolution.cpp:134-141; any
-// other value warns and runs CG).  Not carried over (out of scope, DESIGN.md
+// other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
+// reference flags: the robust data term of include/srmap.h.  Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
 #include <cstdio>
@@ -34,7 +35,9 @@ int main(int argc, char** argv) {
       "  [--regularizer=tv|3dtv|btv] [--btv_scale_range=3] [--btv_spatial_decay=0.5]\n"
       "  [--regularization_parameter=0.01] [--solver=cg] [--solver_iterations=50]\n"
       "  [--interpolate_color] [--solve_in_pca_space] [--num_pca_components=0] [--pca_retained_variance=0]\n"
-      "  [--evaluators=psnr,ssim] [--result_path=<path>] [--verbose]");
+      "  [--evaluators=psnr,ssim] [--result_path=<path>] [--verbose]\n"
+      "  not reference flags: [--data_loss=l2|huber] [--huber_delta=0.02] (robust data term, pixel units 0..1)\n"
+      "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
   const double noise_sigma = flags.Double("noise_sigma", 0.0);
@@ -56,6 +59,10 @@ int main(int argc, char** argv) {
   const double btv_spatial_decay = flags.Double("btv_spatial_decay", 0.5);
   const double regularization_parameter = flags.Double("regularization_parameter", 0.01);
   const std::string solver_name = flags.Str("solver", "cg");
+  // not reference flags: the loss of the data term (the reference's is plain least squares) and the Huber threshold in the
+  // solver's pixel units (ImageData scales 8-bit input to 0..1)
+  const std::string data_loss_name = flags.Str("data_loss", "l2");
+  const double huber_delta = flags.Double("huber_delta", 0.02);
   const bool interpolate_color = flags.Bool("interpolate_color", false);
   const bool solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
   const int num_pca_components = flags.Int("num_pca_components", 0);
@@ -73,6 +80,14 @@ int main(int argc, char** argv) {
     solver_options.least_squares_solver = LBFGS_SOLVER;
   } else if (solver_name != "cg") {
     std::fprintf(stderr, "WARNING: Invalid solver flag. Using conjugate gradient solver.\n");
+  }
+
+  // as --solver: "huber" selects the Huber loss, anything but "l2" warns and runs least squares
+  if (data_loss_name == "huber") {
+    solver_options.data_loss = HUBER_DATA_LOSS;
+    solver_options.huber_delta = huber_delta;
+  } else if (data_loss_name != "l2") {
+    std::fprintf(stderr, "WARNING: Invalid data_loss flag. Using the least-squares (l2) data term.\n");
   }
 
   const ImageModel image_model = ImageModel::CreateImageModel(model_parameters);

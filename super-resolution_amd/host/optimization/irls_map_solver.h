@@ -24,6 +24,9 @@
 namespace super_resolution {
 
 enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER };
+// Loss of the data term.  Not in the reference (its data term is plain least squares): HUBER_DATA_LOSS re-weights the
+// observations between the inner solves as the regulariser is re-weighted (srmap_problem_set_data_loss, include/srmap.h).
+enum DataLoss { L2_DATA_LOSS, HUBER_DATA_LOSS };
 
 struct MapSolverOptions {
   MapSolverOptions() {}
@@ -63,6 +66,9 @@ struct IRLSMapSolverOptions : public MapSolverOptions {
   }
   int max_num_irls_iterations = 20;
   double irls_cost_difference_threshold = 1.0e-5;
+  // not in the reference: robust data term (default: the reference's least squares)
+  DataLoss data_loss = L2_DATA_LOSS;
+  double huber_delta = 0.02;  // in the units of the observations; read for HUBER_DATA_LOSS only
 };
 
 class Solver {
@@ -180,6 +186,12 @@ class IRLSMapSolver : public MapSolver {
                                                                                                      : -1,
                                                solver_options_.num_lbfgs_hessian_corrections),
                       "srmap_problem_set_solver");
+    srmap_host::Check(srmap_problem_set_data_loss(problem_.get(),
+                                                  solver_options_.data_loss == HUBER_DATA_LOSS ? SRMAP_DATA_LOSS_HUBER
+                                                  : solver_options_.data_loss == L2_DATA_LOSS  ? SRMAP_DATA_LOSS_L2
+                                                                                               : -1,
+                                                  solver_options_.huber_delta),
+                      "srmap_problem_set_data_loss");
     const std::vector<double> x0 = initial_estimate.ToPlanar();
     std::vector<double> x(x0.size());
     srmap_host::Check(srmap_solve(problem_.get(), &o, x0.data(), x.data(), &report_), "srmap_solve");
@@ -192,6 +204,15 @@ class IRLSMapSolver : public MapSolver {
     return result;
   }
   const srmap_solve_report& GetReport() const { return report_; }
+  // The data weights, one planar [C][h][w] block per observation ([K][C][h][w]): after a Huber solve the outlier map (the
+  // pixels the solve down-weighted); all ones for a least-squares solve.  Not in the reference.
+  std::vector<double> GetDataWeights() const {
+    int lw = 0, lh = 0;
+    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
+    std::vector<double> w(static_cast<size_t>(GetNumImages()) * GetNumChannels() * lw * lh);
+    srmap_host::Check(srmap_get_data_weights(problem_.get(), w.data()), "srmap_get_data_weights");
+    return w;
+  }
 
  private:
   const IRLSMapSolverOptions solver_options_;

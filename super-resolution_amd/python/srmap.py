@@ -18,6 +18,7 @@ REG_TV, REG_TV3D, REG_BTV = 0, 1, 2
 TERM_DATA, TERM_REG, TERM_ALL = 1, 2, 3
 IMPL_AUTO, IMPL_DIRECT, IMPL_TILED = 0, 1, 2
 SOLVER_CG, SOLVER_LBFGS = 0, 1  # srmap_solver (MapSolverOptions::least_squares_solver)
+DATA_LOSS_L2, DATA_LOSS_HUBER = 0, 1  # srmap_data_loss
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -82,6 +83,11 @@ _SIGNATURES = [
     ("srmap_clear_regularizers", C.c_int, [C.c_void_p]),
     ("srmap_set_irls_weights", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     ("srmap_update_irls_weights_device", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ("srmap_set_data_weights", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_set_data_weights_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("srmap_get_data_weights", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_problem_set_data_loss", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    ("srmap_update_data_weights_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("srmap_apply", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_apply_transpose", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_reg_values", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
@@ -297,6 +303,32 @@ class Problem:
 
     def update_irls_weights_device(self, reg, x_ptr, stream=None):
         self.ctx.check(load().srmap_update_irls_weights_device(self._h, reg, C.c_void_p(x_ptr), C.c_void_p(stream or 0)))
+
+    def set_data_weights(self, w):
+        """Per-observation weights of the data term, [K][C][h][w] like the observations; None = all ones."""
+        if w is None:
+            self.ctx.check(load().srmap_set_data_weights(self._h, None))
+        else:
+            a, pa = _d(w)
+            assert a.size == self.K * self.C * self.h * self.w, (a.shape, self.K, self.C, self.h, self.w)
+            self.ctx.check(load().srmap_set_data_weights(self._h, pa))
+
+    def set_data_weights_device(self, ptr, stream=None):
+        self.ctx.check(load().srmap_set_data_weights_device(self._h, C.c_void_p(ptr), C.c_void_p(stream or 0)))
+
+    def data_weights(self):
+        """The current data weights [K][C][h][w] (ones if none are set); after a Huber solve, the outlier map."""
+        out = np.empty((self.K, self.C, self.h, self.w))
+        self.ctx.check(load().srmap_get_data_weights(self._h, out.ctypes.data_as(c_double_p)))
+        return out
+
+    def set_data_loss(self, loss, huber_delta=0.0):
+        """DATA_LOSS_L2 (default) or DATA_LOSS_HUBER with its delta (> 0, in the observations' units)."""
+        self.ctx.check(load().srmap_problem_set_data_loss(self._h, loss, huber_delta))
+
+    def update_data_weights_device(self, x_ptr, stream=None):
+        """One Huber re-weighting step from the residuals at the device image x_ptr."""
+        self.ctx.check(load().srmap_update_data_weights_device(self._h, C.c_void_p(x_ptr), C.c_void_p(stream or 0)))
 
     def apply(self, hr, k):
         a, pa = _d(hr)
