@@ -138,6 +138,31 @@ int srmap_problem_set_impl(srmap_problem* p, int impl /* srmap_impl */);
  * rounding tie, whose per-row table only the direct kernels read). */
 int srmap_problem_active_impl(const srmap_problem* p, int* impl);
 
+/* Affine per-frame motion model (no reference counterpart: MotionModule warps by a translation only,
+ * motion_module.cpp:18-51, and registration.cpp keeps nothing but the translation of what it fits).
+ * affine_2x3: K x 6 doubles, row-major [a b tx; c d ty] per frame, in HR pixel coordinates, (x, y) order.  With
+ * F_k(p) = L_k p + t_k, content at p in the HR image sits at F_k(p) in frame k's HR-grid image (MotionShift's
+ * convention: L = I, t = (dx, dy) is the shift (dx, dy)).
+ *   forward   (M_k x)(q) = four-tap bilinear sample of x at s = F_k^-1(q); a tap outside the image contributes 0.  Then
+ *             the blur and the decimation of the translational model apply unchanged: A_k = D B M_k.
+ *   coords    s is computed in double for both dtypes and is exact (no 1/32-px quantisation: a set of pure translations
+ *             is a DIFFERENT definition from shifts_xy unless the shifts are multiples of 1/32 px off the rounding ties,
+ *             where the two agree).  F_k^-1 is formed once on the host in double.  The weights are rounded to the dtype.
+ *   adjoint   M_k^T is the exact transpose of that matrix (not a warp by the inverse map), so the gradient
+ *             2 s^2 sum_k M_k^T B^T D^T (w_k .* r_k) is the true gradient of the cost; it is gathered without atomics:
+ *             two evaluations of one input give bit-identical gradients.
+ *   domain    all numbers finite, else SRMAP_EINVAL; max(|a-1|+|b|, |c|+|d-1|) <= 0.25 (about +-7 degrees of rotation
+ *             with a few percent of scale or shear), else SRMAP_EUNSUPPORTED; on an error the problem keeps its motion.
+ * NULL restores the motion the problem was created with (shifts_xy or none).  The call works on problems created with or
+ * without shifts_xy and persists across srmap_set_observations and the data-weight calls.  While an affine motion is
+ * set, the direct kernel family runs (srmap_problem_active_impl answers SRMAP_IMPL_DIRECT; SRMAP_IMPL_TILED answers
+ * SRMAP_EUNSUPPORTED at evaluation) -- also when every L_k is exactly I.  srmap_eval*, srmap_apply, srmap_apply_transpose
+ * (the exact adjoint), srmap_solve (CG, L-BFGS, split_channels), the traces, srmap_problem_set_cost_rows and the robust
+ * data term honour it.  Evaluations and solves sharded over a communicator of more than one rank answer
+ * SRMAP_EUNSUPPORTED.  Not thread-safe against evaluations of the same problem; evaluations already enqueued are waited
+ * for.  Estimating the matrices is the caller's job (srmap_register_translational finds translations only). */
+int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3);
+
 /* Inner minimiser of srmap_solve: MapSolverOptions::least_squares_solver and num_lbfgs_hessian_corrections
  * (enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER }, map_solver.h:20-51; the choice irls_map_solver.cpp:97-113;
  * the CLI's --solver=cg|lbfgs, super_resolution.cpp:98-99, 134-141).  SRMAP_SOLVER_CG (mincg, alglib_objective.cpp:47-75)

@@ -151,6 +151,7 @@ template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
                           double* partials, int* nblocks, hipStream_t st, const T* dw) {
+  if (p->affine) return launch_forward_affine<T>(p, g, x, y, obs_C, obs_c0, out, k0, nk, partials, nblocks, st, dw);
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
   if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
@@ -407,6 +408,10 @@ template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring, T* ringbuf) {
+  if (p->affine) {
+    if (ring > 0 || ringbuf != nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which an affine motion has none of");
+    return launch_gather_affine<T>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
+  }
   // ring > 0: only the pixels within `ring` of the image edge (the exact border of the sub-pixel tile path)
   size_t npix = (size_t)geo.W * geo.H;
   if (ring > 0) {

@@ -578,7 +578,7 @@ void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
   void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_obs, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
+                  p->d_affine, p->d_obs, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
   for (int* t : p->d_ytabs) (void)hipFree(t);
@@ -591,6 +591,32 @@ int srmap_problem_set_impl(srmap_problem* p, int impl) {
   if (impl < SRMAP_IMPL_AUTO || impl > SRMAP_IMPL_TILED) return set_error(p->ctx, SRMAP_EINVAL, "bad impl");
   p->impl = impl;
   p->plan_gen++;
+  return SRMAP_OK;
+}
+
+// ---- affine per-frame motion model (no reference counterpart; generalises motion_module.cpp:18-51) ----
+int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) {
+  if (!p) return SRMAP_EINVAL;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  std::vector<double> recs;
+  if (affine_2x3) {
+    int rc = affine_records(p->ctx, p->geo.K, affine_2x3, &recs);
+    if (rc) return rc;  // the problem keeps the motion it had
+  }
+  // evaluations in flight read the records: drain them before the buffer changes
+  if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  if (affine_2x3) {
+    if (!p->d_affine) SRMAP_HIP(p->ctx, hipMalloc((void**)&p->d_affine, recs.size() * sizeof(double)));
+    SRMAP_HIP(p->ctx, hipMemcpy(p->d_affine, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+    p->affine_recs.swap(recs);
+    p->affine = true;
+  } else {
+    p->affine = false;
+    p->affine_recs.clear();
+  }
+  p->plan_gen++;
+  if (ztile_plan(p)) ztile_preload(p);  // "not covered" while an affine motion is set
   return SRMAP_OK;
 }
 

@@ -15,6 +15,10 @@ namespace srmap {
 constexpr int kMaxRegularizers = 4;
 constexpr int kMaxBtvRange = 8;        // alpha^(i+j) table holds 2*range+1 entries
 constexpr int kMaxBlurTaps = 15 * 15;  // b*b taps kept in kernel-argument space
+// Affine motion (srmap_problem_set_affine_motion, kernels_affine.hip): doubles per frame record -- [0..5] the inverse map
+// [ia ib itx; ic id ity], [6..11] the forward map [a b tx; c d ty], [12..13] the candidate radii of the transpose gather
+constexpr int kAffineRec = 16;
+constexpr double kAffineMaxDeviation = 0.25;  // max(|a-1|+|b|, |c|+|d-1|): bounds the gather at 3 x 3 candidates
 
 // One MotionModule warp (forward or transpose) of one frame, as cv::warpAffine
 // evaluates it (motion_module.cpp:18-51): source pixel = destination + (ox, oy)
@@ -107,6 +111,11 @@ struct srmap_problem {
   bool has_motion = false;
   bool maps_regular = true;       // decimation map == s*j on both axes
   std::vector<double> shifts;     // K x 2
+  // affine motion model: when set, the data term of every evaluation and operator runs kernels_affine.hip and the tile
+  // planner answers "not covered"; the translational warps above stay as created (NULL restores them)
+  bool affine = false;
+  std::vector<double> affine_recs;  // K x kAffineRec (host mirror of d_affine)
+  double* d_affine = nullptr;
   std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
   std::vector<double> blur2d_t;
   std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
@@ -194,6 +203,15 @@ template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring = 0, T* ringbuf = nullptr);
+// ---- affine motion (kernels_affine.hip): the two launchers above route here when p->affine ----
+template <typename T>
+int launch_forward_affine(srmap_problem* p, const Geometry& g, const T* x, const T* y, int obs_C, int obs_c0, T* out,
+                          int k0, int nk, double* partials, int* nblocks, hipStream_t st, const T* dw);
+template <typename T>
+int launch_gather_affine(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk, double out_scale,
+                         bool accumulate, hipStream_t st);
+// K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain)
+int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
 // whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
 template <typename T>

@@ -18,13 +18,16 @@ int main(int argc, char** argv) {
       "generate_data --input_image=<ENVI config | .pgm | .ppm> --output_image_dir=<dir>\n"
       "  [--output_image_extension=<pgm|ppm|''(ENVI)>] [--save_as=<path>] [--motion_sequence_path=<file>]\n"
       "  [--blur_radius=0] [--blur_sigma=0] [--noise_sigma=0] [--noise_seed=1]\n"
-      "  [--downsampling_scale=2] [--number_of_frames=4]");
+      "  [--downsampling_scale=2] [--number_of_frames=4]\n"
+      "  not a reference flag: [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
+      "                        an error together with --motion_sequence_path)");
   const std::string input_image = flags.Str("input_image");
   const std::string output_dir = flags.Str("output_image_dir");
   std::string extension = flags.Str("output_image_extension");
   const std::string save_as = flags.Str("save_as");
   ImageModelParameters parameters;
   parameters.motion_sequence_path = flags.Str("motion_sequence_path");
+  parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
   parameters.blur_radius = flags.Int("blur_radius", 0);
   parameters.blur_sigma = flags.Double("blur_sigma", 0.0);
   parameters.noise_sigma = flags.Double("noise_sigma", 0.0);  // 0..255 units (additive_noise_module.cpp:25-26)
@@ -33,6 +36,10 @@ int main(int argc, char** argv) {
   const int number_of_frames = flags.Int("number_of_frames", 4);
   flags.RejectUnknown();
   flags.Require("input_image");
+  if (!parameters.affine_motion_sequence_path.empty() && !parameters.motion_sequence_path.empty()) {
+    std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
+    return 1;
+  }
 
   const ImageData image_data = util::LoadImage(input_image);
   if (!save_as.empty()) {  // copy / convert only (generate_data.cpp:94-98)

@@ -5,7 +5,7 @@
 // truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
 // least-squares solver as the reference does (super_resolution.cpp:134-141; any
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
-// reference flags: the robust data term of include/srmap.h.  Not carried over (out of scope, DESIGN.md
+// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
 #include <cstdio>
@@ -37,6 +37,8 @@ int main(int argc, char** argv) {
       "  [--interpolate_color] [--solve_in_pca_space] [--num_pca_components=0] [--pca_retained_variance=0]\n"
       "  [--evaluators=psnr,ssim] [--result_path=<path>] [--verbose]\n"
       "  not reference flags: [--data_loss=l2|huber] [--huber_delta=0.02] (robust data term, pixel units 0..1)\n"
+      "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
+      "                       an error together with --motion_sequence_path)\n"
       "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
@@ -50,6 +52,8 @@ int main(int argc, char** argv) {
   model_parameters.blur_radius = flags.Int("blur_radius", 3);
   model_parameters.blur_sigma = flags.Double("blur_sigma", 1.0);
   model_parameters.motion_sequence_path = flags.Str("motion_sequence_path");
+  // not a reference flag: the affine motion model of include/srmap.h (srmap_problem_set_affine_motion)
+  model_parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");
   IRLSMapSolverOptions solver_options;
   solver_options.max_num_irls_iterations = flags.Int("optimization_iterations", 20);
   solver_options.max_num_solver_iterations = flags.Int("solver_iterations", 50);
@@ -75,6 +79,10 @@ int main(int argc, char** argv) {
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
+  if (!model_parameters.affine_motion_sequence_path.empty() && !model_parameters.motion_sequence_path.empty()) {
+    std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
+    return 1;
+  }
   // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
   if (solver_name == "lbfgs") {
     solver_options.least_squares_solver = LBFGS_SOLVER;

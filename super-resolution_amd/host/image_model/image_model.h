@@ -1,7 +1,8 @@
 // The reference's forward-model interface for the MAP path, forwarding to the
 // HIP library through the C ABI:
 //   DegradationOperator  src/image_model/degradation_operator.h:17-57
-//   MotionModule         src/image_model/motion_module.{h,cpp}
+//   MotionModule         src/image_model/motion_module.{h,cpp}; also constructible from an AffineMotionSequence
+//                        (motion/affine_motion.h; no reference counterpart)
 //   BlurModule           src/image_model/blur_module.{h,cpp}
 //   DownsamplingModule   src/image_model/downsampling_module.{h,cpp}
 //   ImageModel, ImageModelParameters, CreateImageModel
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "image/image_data.h"
+#include "motion/affine_motion.h"
 #include "motion/motion_shift.h"
 #include "util/srmap_host.h"
 
@@ -61,20 +63,31 @@ class DegradationOperator {
 
 class MotionModule : public DegradationOperator {
  public:
-  explicit MotionModule(const MotionShiftSequence& sequence) : sequence_(sequence) {}
+  explicit MotionModule(const MotionShiftSequence& sequence) : sequence_(sequence), affine_(false) {}
+  // not in the reference: per-frame affine warps (the exact-coordinate bilinear warp and its exact adjoint, include/srmap.h)
+  explicit MotionModule(const AffineMotionSequence& sequence) : affine_sequence_(sequence), affine_(true) {}
   void ApplyToImage(ImageData* image_data, const int index) const override {
-    sequence_.GetMotionShift(index);
+    CheckIndex(index);
     srmap_host::RunChain(Chain(), image_data, index, false);
   }
   void ApplyTransposeToImage(ImageData* image_data, const int index) const override {
-    sequence_.GetMotionShift(index);
+    CheckIndex(index);
     srmap_host::RunChain(Chain(), image_data, index, true);
   }
-  void Describe(srmap_host::ChainParams* c) const override { c->shifts_xy = sequence_.Flat(); }
+  void Describe(srmap_host::ChainParams* c) const override {
+    if (affine_) { c->affine_2x3 = affine_sequence_.Flat(); c->shifts_xy.clear(); }
+    else { c->shifts_xy = sequence_.Flat(); c->affine_2x3.clear(); }
+  }
+  bool IsAffine() const { return affine_; }
 
  private:
+  void CheckIndex(const int index) const {
+    if (affine_) affine_sequence_.GetAffineMotion(index); else sequence_.GetMotionShift(index);
+  }
   srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const MotionShiftSequence sequence_;
+  const AffineMotionSequence affine_sequence_;
+  const bool affine_;
 };
 
 class BlurModule : public DegradationOperator {
@@ -148,6 +161,9 @@ struct ImageModelParameters {
   double blur_sigma = 0.0;
   std::string motion_sequence_path = "";
   MotionShiftSequence motion_sequence;
+  // not in the reference: per-frame affine motion ("a b tx c d ty" per line); excludes motion_sequence(_path)
+  std::string affine_motion_sequence_path = "";
+  AffineMotionSequence affine_motion_sequence;
   double noise_sigma = 0.0;
   uint64_t noise_seed = 0x5eedULL;  // not in the reference (cv::randn draws from OpenCV's global generator)
 };
@@ -160,6 +176,14 @@ class ImageModel {
   // image_model.cpp:17-61
   static ImageModel CreateImageModel(const ImageModelParameters& parameters) {
     ImageModel model(parameters.scale);
+    const bool affine = !parameters.affine_motion_sequence_path.empty() || parameters.affine_motion_sequence.GetNumMotions() > 0;
+    if (affine && (!parameters.motion_sequence_path.empty() || parameters.motion_sequence.GetNumMotionShifts() > 0))
+      srmap_host::Fail("both an affine motion sequence and a motion shift sequence were given: a model has one MotionModule");
+    if (affine) {
+      AffineMotionSequence seq = parameters.affine_motion_sequence;
+      if (seq.GetNumMotions() == 0) seq.LoadSequenceFromFile(parameters.affine_motion_sequence_path);
+      model.AddDegradationOperator(std::make_shared<MotionModule>(seq));
+    }
     if (!parameters.motion_sequence_path.empty() || parameters.motion_sequence.GetNumMotionShifts() > 0) {
       MotionShiftSequence seq = parameters.motion_sequence;
       if (seq.GetNumMotionShifts() == 0) seq.LoadSequenceFromFile(parameters.motion_sequence_path);
@@ -186,7 +210,7 @@ class ImageModel {
     // MotionModule the fused problem has ONE frame, whatever index the caller passes
     const AdditiveNoiseModule* noise = nullptr;
     if (Canonical(&chain, &noise)) {
-      srmap_host::RunChain(chain, image_data, chain.shifts_xy.empty() ? 0 : index, false);
+      srmap_host::RunChain(chain, image_data, chain.HasMotion() ? index : 0, false);
       if (noise) noise->ApplyToImage(image_data, index);
       return;
     }
@@ -195,7 +219,7 @@ class ImageModel {
   // image_model.cpp:93-101: transposes in reverse order.
   void ApplyTransposeToImage(ImageData* image_data, const int index) const {
     srmap_host::ChainParams chain;
-    if (Canonical(&chain)) { srmap_host::RunChain(chain, image_data, chain.shifts_xy.empty() ? 0 : index, true); return; }  // a trailing noise module's transpose is a no-op
+    if (Canonical(&chain)) { srmap_host::RunChain(chain, image_data, chain.HasMotion() ? index : 0, true); return; }  // a trailing noise module's transpose is a no-op
     for (int i = static_cast<int>(operators_.size()) - 1; i >= 0; --i) operators_[i]->ApplyTransposeToImage(image_data, index);
   }
   int GetDownsamplingScale() const { return downsampling_scale_; }

@@ -103,9 +103,9 @@ class MapSolver : public Solver {
     if (!image_model_.Canonical(&chain))
       srmap_host::Fail("MapSolver needs the [Motion][Blur]Downsampling operator chain");
     chain.frames = static_cast<int>(low_res_images.size());
-    if (!chain.shifts_xy.empty() && chain.shifts_xy.size() / 2 < low_res_images.size())
+    if (chain.HasMotion() && static_cast<size_t>(chain.NumMotions()) < low_res_images.size())
       srmap_host::Fail("fewer motion shifts than observations");
-    if (!chain.shifts_xy.empty()) chain.shifts_xy.resize(2 * low_res_images.size());
+    chain.TrimMotions(low_res_images.size());
     problem_ = srmap_host::MakeProblem(chain, image_size_.width, image_size_.height, num_channels_);
     std::vector<double> stack;
     for (const ImageData& im : low_res_images) {

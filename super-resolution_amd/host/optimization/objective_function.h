@@ -63,9 +63,9 @@ class ObjectiveDataTerm : public ObjectiveTerm {
     if (!image_model.Canonical(&chain)) srmap_host::Fail("ObjectiveDataTerm needs the [Motion][Blur]Downsampling operator chain");
     const int s = image_model.GetDownsamplingScale();
     chain.frames = static_cast<int>(observations.size());
-    if (!chain.shifts_xy.empty() && chain.shifts_xy.size() / 2 < observations.size())
+    if (chain.HasMotion() && static_cast<size_t>(chain.NumMotions()) < observations.size())
       srmap_host::Fail("fewer motion shifts than observations");
-    if (!chain.shifts_xy.empty()) chain.shifts_xy.resize(2 * observations.size());
+    chain.TrimMotions(observations.size());
     problem_ = srmap_host::MakeProblem(chain, image_size.width, image_size.height, num_channels_);
     const int lw = image_size.width / s, lh = image_size.height / s;
     std::vector<double> stack;

@@ -48,23 +48,35 @@ using ProblemPtr = std::unique_ptr<srmap_problem, ProblemDeleter>;
 // Parameters of one operator chain  D(scale) . B(ksize, sigma) . M(shifts).
 struct ChainParams {
   int scale = 1;
-  std::vector<double> shifts_xy;  // empty = no MotionModule
+  std::vector<double> shifts_xy;  // empty = no translational MotionModule
+  std::vector<double> affine_2x3;  // K x [a b tx; c d ty]: a MotionModule over an AffineMotionSequence (then shifts_xy is empty)
   int frames = 1;
   int blur_ksize = 0;
   double blur_sigma = 0.0;
+  bool HasMotion() const { return !shifts_xy.empty() || !affine_2x3.empty(); }
+  int NumMotions() const { return static_cast<int>(affine_2x3.empty() ? shifts_xy.size() / 2 : affine_2x3.size() / 6); }
+  // solvers: n observations need at least n motions; the rest is dropped
+  void TrimMotions(size_t n) {
+    if (!shifts_xy.empty()) shifts_xy.resize(2 * n);
+    if (!affine_2x3.empty()) affine_2x3.resize(6 * n);
+  }
 };
 
 inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int channels) {
   srmap_problem_desc d;
   d.hr_width = width; d.hr_height = height; d.channels = channels;
-  d.frames = c.shifts_xy.empty() ? c.frames : static_cast<int>(c.shifts_xy.size() / 2);
+  if (!c.shifts_xy.empty() && !c.affine_2x3.empty()) Fail("a chain has either motion shifts or affine motions, not both");
+  d.frames = c.HasMotion() ? c.NumMotions() : c.frames;
   d.scale = c.scale;
   d.shifts_xy = c.shifts_xy.empty() ? nullptr : c.shifts_xy.data();
   d.blur_ksize = c.blur_ksize; d.blur_sigma = c.blur_sigma;
   d.dtype = SRMAP_F64;  // the reference computes in double
   srmap_problem* p = nullptr;
   Check(srmap_problem_create(Context(), &d, &p), "srmap_problem_create");
-  return ProblemPtr(p);
+  ProblemPtr problem(p);
+  if (!c.affine_2x3.empty())
+    Check(srmap_problem_set_affine_motion(p, c.affine_2x3.data()), "srmap_problem_set_affine_motion");
+  return problem;
 }
 
 }  // namespace srmap_host

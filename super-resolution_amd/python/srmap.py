@@ -75,6 +75,7 @@ _SIGNATURES = [
     ("srmap_problem_destroy", None, [C.c_void_p]),
     ("srmap_problem_set_impl", C.c_int, [C.c_void_p, C.c_int]),
     ("srmap_problem_set_solver", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("srmap_problem_set_affine_motion", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_lr_size", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("srmap_set_observations", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_active_impl", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
@@ -265,6 +266,16 @@ class Problem:
     def set_solver(self, solver, m=5):
         """Inner minimiser of solve(): SOLVER_CG (default) or SOLVER_LBFGS with m history pairs (1 <= m <= 8)."""
         self.ctx.check(load().srmap_problem_set_solver(self._h, solver, m))
+
+    def set_affine_motion(self, matrices):
+        """Per-frame affine motion [K][2][3] = [a b tx; c d ty] in HR pixel coordinates, (x, y) order: content at p sits at
+        L p + t in frame k's HR-grid image.  None restores the motion the problem was created with."""
+        if matrices is None:
+            self.ctx.check(load().srmap_problem_set_affine_motion(self._h, None))
+        else:
+            a, pa = _d(matrices)
+            assert a.size == self.K * 6, (a.shape, self.K)
+            self.ctx.check(load().srmap_problem_set_affine_motion(self._h, pa))
 
     def set_cost_rows(self, hr_row0, hr_row1):
         """Row-band sharding: count only the cost terms of HR rows [hr_row0, hr_row1)."""

@@ -1,0 +1,117 @@
+// affine_motion_test.cpp -- host side of the affine motion model (super-resolution_amd/host/motion/affine_motion.h, the
+// MotionModule constructor over it, ImageModelParameters::affine_motion_sequence_path): file parsing, index errors, the
+// both-sequences error, and ImageModel::Canonical() carrying the matrices to the C ABI's chain.  No GPU needed: nothing
+// here applies an operator.  argv[1] = scratch directory; argv[2] (optional) names ONE case that must abort the process
+// with a "Check failed" message: index | both | short_line | missing_file.
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "image_model/image_model.h"
+#include "motion/affine_motion.h"
+
+using namespace super_resolution;
+
+static int g_fail = 0;
+#define EXPECT(cond)                                                          \
+  do {                                                                        \
+    if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++g_fail; } \
+  } while (0)
+
+static std::string WriteFile(const std::string& dir, const std::string& name, const std::string& text) {
+  const std::string path = dir + "/" + name;
+  std::ofstream out(path);
+  out << text;
+  return path;
+}
+
+static const char* kThreeFrames =
+    "1 0 0 0 1 0\n"
+    "\n"
+    "0.9993908270190958 -0.03489949670250097 1.25   0.03489949670250097 0.9993908270190958 0.75\n"
+    "1.02\t-0.01\t-3.5\t0.015\t0.98\t2e-1\r\n";
+
+static void TestParsing(const std::string& dir) {
+  AffineMotionSequence seq;
+  seq.LoadSequenceFromFile(WriteFile(dir, "affine3.txt", kThreeFrames));
+  EXPECT(seq.GetNumMotions() == 3);
+  EXPECT(seq[0].a == 1.0 && seq[0].b == 0.0 && seq[0].tx == 0.0 && seq[0].c == 0.0 && seq[0].d == 1.0 && seq[0].ty == 0.0);
+  EXPECT(seq[1].a == 0.9993908270190958 && seq[1].b == -0.03489949670250097 && seq[1].tx == 1.25);
+  EXPECT(seq[1].c == 0.03489949670250097 && seq[1].d == 0.9993908270190958 && seq[1].ty == 0.75);
+  EXPECT(seq.GetAffineMotion(2).a == 1.02 && seq[2].b == -0.01 && seq[2].tx == -3.5 && seq[2].c == 0.015 && seq[2].d == 0.98 &&
+         seq[2].ty == 0.2);
+  const std::vector<double> flat = seq.Flat();
+  EXPECT(flat.size() == 18);
+  EXPECT(flat[6] == seq[1].a && flat[7] == seq[1].b && flat[8] == seq[1].tx && flat[9] == seq[1].c && flat[10] == seq[1].d &&
+         flat[11] == seq[1].ty);
+  // loading again replaces the sequence
+  seq.LoadSequenceFromFile(WriteFile(dir, "affine1.txt", "1 0 2 0 1 3\n"));
+  EXPECT(seq.GetNumMotions() == 1 && seq[0].tx == 2.0 && seq[0].ty == 3.0);
+  AffineMotionSequence set;
+  set.SetMotionSequence({AffineMotion(1, 0, 1, 0, 1, 2), AffineMotion(1, 0.1, 0, -0.1, 1, 0)});
+  EXPECT(set.GetNumMotions() == 2 && set[1].b == 0.1 && set[1].c == -0.1);
+}
+
+static void TestCanonicalCarriesTheMatrices(const std::string& dir) {
+  ImageModelParameters params;
+  params.scale = 3;
+  params.blur_radius = 5;
+  params.blur_sigma = 1.5;
+  params.affine_motion_sequence_path = WriteFile(dir, "affine3b.txt", kThreeFrames);
+  const ImageModel model = ImageModel::CreateImageModel(params);
+  srmap_host::ChainParams chain;
+  EXPECT(model.Canonical(&chain));
+  EXPECT(chain.scale == 3 && chain.blur_ksize == 5 && chain.blur_sigma == 1.5);
+  EXPECT(chain.shifts_xy.empty());
+  EXPECT(chain.affine_2x3.size() == 18);
+  EXPECT(chain.HasMotion() && chain.NumMotions() == 3);
+  EXPECT(chain.affine_2x3[8] == 1.25 && chain.affine_2x3[11] == 0.75 && chain.affine_2x3[12] == 1.02);
+  chain.TrimMotions(2);
+  EXPECT(chain.affine_2x3.size() == 12 && chain.NumMotions() == 2);
+  // a sequence given directly wins over nothing and needs no file
+  ImageModelParameters direct;
+  direct.affine_motion_sequence.SetMotionSequence({AffineMotion(1, 0, 0.5, 0, 1, -0.5)});
+  srmap_host::ChainParams c2;
+  EXPECT(ImageModel::CreateImageModel(direct).Canonical(&c2));
+  EXPECT(c2.affine_2x3.size() == 6 && c2.affine_2x3[2] == 0.5 && c2.affine_2x3[5] == -0.5 && c2.shifts_xy.empty());
+  // the translational model is untouched: shifts, no matrices
+  ImageModelParameters shifts;
+  shifts.motion_sequence.SetMotionSequence({MotionShift(0, 0), MotionShift(1.5, -2)});
+  srmap_host::ChainParams c3;
+  EXPECT(ImageModel::CreateImageModel(shifts).Canonical(&c3));
+  EXPECT(c3.affine_2x3.empty() && c3.shifts_xy.size() == 4 && c3.shifts_xy[2] == 1.5 && c3.NumMotions() == 2);
+  // a MotionModule over either sequence says which it is
+  EXPECT(MotionModule(AffineMotionSequence({AffineMotion(1, 0, 0, 0, 1, 0)})).IsAffine());
+  EXPECT(!MotionModule(MotionShiftSequence({MotionShift(0, 0)})).IsAffine());
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) { std::printf("usage: affine_motion_test <scratch dir> [index|both|short_line|missing_file]\n"); return 2; }
+  const std::string dir = argv[1];
+  if (argc > 2) {  // each of these must abort inside the call; reaching the end is the failure
+    const std::string which = argv[2];
+    if (which == "index") {
+      AffineMotionSequence seq({AffineMotion(1, 0, 0, 0, 1, 0)});
+      seq.GetAffineMotion(1);
+    } else if (which == "both") {
+      ImageModelParameters params;
+      params.affine_motion_sequence_path = WriteFile(dir, "affine_both.txt", kThreeFrames);
+      params.motion_sequence_path = WriteFile(dir, "shifts_both.txt", "0 0\n1 1\n0 1\n");
+      ImageModel::CreateImageModel(params);
+    } else if (which == "short_line") {
+      AffineMotionSequence seq;
+      seq.LoadSequenceFromFile(WriteFile(dir, "affine_short.txt", "1 0 0 0 1 0\n1 0 0 0 1\n"));
+    } else if (which == "missing_file") {
+      AffineMotionSequence seq;
+      seq.LoadSequenceFromFile(dir + "/no_such_affine_file.txt");
+    }
+    std::printf("case '%s' did not abort\n", which.c_str());
+    return 0;
+  }
+  TestParsing(dir);
+  TestCanonicalCarriesTheMatrices(dir);
+  if (g_fail) { std::printf("%d FAILURES\n", g_fail); return 1; }
+  std::printf("AFFINE MOTION HOST TESTS PASSED\n");
+  return 0;
+}
