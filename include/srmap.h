@@ -33,7 +33,7 @@
  *   - entry points that take HOST pointers (srmap_eval, srmap_solve*,
  *     srmap_cg_trace, srmap_apply*, srmap_reg_values*, srmap_set_observations,
  *     srmap_set_irls_weights, srmap_set_data_weights, srmap_get_data_weights, srmap_channel_map, srmap_channel_pca,
- *     srmap_register_translational, srmap_upload / srmap_download) run on the
+ *     srmap_register_translational, srmap_register_affine, srmap_upload / srmap_download) run on the
  *     context's stream and are complete when they return.
  *   - the problem's device state (observations, IRLS weights, data weights) is ordered by the
  *     library itself: a write through srmap_update_irls_weights_device / srmap_update_data_weights_device on one
@@ -160,7 +160,8 @@ int srmap_problem_active_impl(const srmap_problem* p, int* impl);
  * (the exact adjoint), srmap_solve (CG, L-BFGS, split_channels), the traces, srmap_problem_set_cost_rows and the robust
  * data term honour it.  Evaluations and solves sharded over a communicator of more than one rank answer
  * SRMAP_EUNSUPPORTED.  Not thread-safe against evaluations of the same problem; evaluations already enqueued are waited
- * for.  Estimating the matrices is the caller's job (srmap_register_translational finds translations only). */
+ * for.  srmap_register_affine estimates the matrices from the frames (srmap_register_translational finds translations
+ * only); its output goes straight into this call. */
 int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3);
 
 /* Inner minimiser of srmap_solve: MapSolverOptions::least_squares_solver and num_lbfgs_hessian_corrections
@@ -344,6 +345,47 @@ int srmap_register_translational(srmap_ctx* ctx, int num_images, int width, int 
  * should check both, or supply shifts from their own registration (MotionShiftSequence accepts any). */
 int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, int width, int height,
                                     const double* images_host, double* shifts_xy_out, double* quality_out);
+
+/* Affine registration (no reference counterpart; csrc/registration_affine.hip): for every image
+ * k >= 1 the 2 x 3 matrix [a b tx; c d ty] of F_k(p) = L_k p + t_k with I_k(F_k(p)) ~= I_0(p) -- content at p of image 0
+ * sits at F_k(p) in image k, the convention of srmap_problem_set_affine_motion and of MotionShift.  Image 0 gets the
+ * identity.  All arithmetic is f64.
+ *   pyramid   2 x 2 box means of every image (an odd last row / column is dropped), halved while min(w, h) >= 64 (the
+ *             coarsest level's shorter side is 32...63), at most 12 levels; max_levels caps the count;
+ *   seed      coarsest level: exhaustive integer search, R = max(4, min(16, min side / 4)), mean squared difference over
+ *             the fixed template window [R, w-R) x [R, h-R), first minimum in row-major order; skipped when
+ *             initial_affine_2x3 is given (the matrices are then taken down the pyramid);
+ *   steps     inverse-compositional Gauss-Newton, coarse to fine, over the template pixels at least 1 px from the border
+ *             whose four bilinear taps in image k are inside it (others are left out, not sampled as zero); a level ends
+ *             when the four image corners move less than step_tolerance (pixels of that level) or after max_iterations.
+ * With hr_scale = s the returned t is s * t and L is unchanged: the matrices of LR frames in the HR pixel units that
+ * srmap_problem_set_affine_motion takes (the decimation samples HR pixel s u for LR pixel u: no offset term).
+ * What this estimator is and is NOT: it is DENSE (every pixel votes, no features); it has NO outlier rejection (moving
+ * objects, occlusions and saturated regions bias it); its domain is the affine model's, max(|a-1|+|b|, |c|+|d-1|)
+ * <= 0.25, and a translation within R pixels of the coarsest level unless initial matrices are given; PERIODIC texture
+ * can alias to a wrong period (the separation below shows it); it registers ONE plane per image.
+ * quality_out (optional, 4 doubles per image): [4i] separation of the coarse minimum as srmap_register_translational_ex
+ * defines it (1 when an initial matrix was given), [4i+1] root mean squared residual I_k(F(p)) - I_0(p) at the result
+ * (full resolution), [4i+2] the fraction n / (w h) of pixels that pass used, [4i+3] Gauss-Newton passes over all levels.
+ * Image 0: (1, 0, 1, 0).
+ * num_images == 0 returns SRMAP_OK and writes nothing.  SRMAP_EINVAL: width or height < 8; a struct_size that is not this
+ * library's; hr_scale < 1, max_iterations < 1, max_levels < 0 or a negative step_tolerance; an initial matrix (rows
+ * 1...num_images-1; row 0 is ignored) that is not finite or outside the domain; and "Could not determine motion between
+ * images." when a pass has fewer than 0.25 w h usable pixels or an iterate leaves the domain.  A level without texture
+ * (the 6 x 6 Cholesky factorisation fails) keeps its matrix and is not an error.  Results are bit-identical run to run and
+ * do not depend on the other images of the stack. */
+typedef struct {
+  int struct_size;                   /* filled by the _default call; a mismatch is SRMAP_EINVAL */
+  int hr_scale;                      /* 1 */
+  int max_iterations;                /* 30, per level */
+  double step_tolerance;             /* 1e-4 px */
+  int max_levels;                    /* 0 = automatic; 1 = full resolution only */
+  const double* initial_affine_2x3;  /* NULL = coarse search; else num_images x 6, input-pixel units */
+} srmap_affine_registration_options;
+void srmap_affine_registration_options_default(srmap_affine_registration_options* options);
+int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, int height, const double* images_host,
+                          const srmap_affine_registration_options* options /* NULL = defaults */,
+                          double* affine_2x3_out /* num_images x 6 */, double* quality_out /* optional, 4 per image */);
 
 /* ------------------------------------------------------------- solver */
 /* IRLSMapSolverOptions (irls_map_solver.h:14-36) + MapSolverOptions

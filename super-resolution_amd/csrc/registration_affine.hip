@@ -1,0 +1,441 @@
+// registration_affine.hip -- affine registration of a frame stack on the GPU (srmap_register_affine).
+//
+// For every frame k >= 1: F_k(p) = L_k p + t_k with I_k(F_k(p)) ~= I_0(p), the convention of the affine motion model
+// (kernels_affine.hip) and of MotionShift.  No reference counterpart (registration.cpp keeps the translation of a
+// feature-based fit); the checker is tests/affine_registration_restatement.py.
+//   1. box pyramid of the whole stack, built once (k_down2_stack), halved while the shorter side is >= 64;
+//   2. seed at the coarsest level: integer search over [-R, R]^2, mean squared difference over the FIXED template window
+//      [R, w-R) x [R, h-R) (k_ssd_window).  The overlap window of the translational search moves with the candidate and
+//      lets the zero wedges of a rotated frame vote for far-away shifts; a fixed window compares every candidate on the
+//      same pixels;
+//   3. inverse-compositional Gauss-Newton, coarse to fine: per pass ONE launch of k_affine_gn_sums for all frames
+//      (26 sums per workgroup, fixed-order reduction), one k_affine_gn_reduce, one 26 x (K-1) double copy and one stream
+//      wait; the 6 x 6 Cholesky solve and the composition F <- F o W^-1 run on the host in double.
+// Sample positions are computed as kernels_affine.hip computes them (affine_coord: every operation rounded on its own).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "srmap_internal.hpp"
+
+namespace srmap {
+
+namespace {
+
+constexpr int kGnSums = 26;       // 18 of H, 6 of g, sum e^2, pixel count
+constexpr int kFrameRec = 8;      // a b tx c d ty active pad
+constexpr int kMaxLevels = 12;
+constexpr int kMaxRowChunks = 128;
+constexpr int kMaxSeedChunks = 8;
+constexpr double kMaxDeviation = 0.25;
+constexpr double kPivotRtol = 1e-12;
+
+__device__ __forceinline__ double wsum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// kernels_affine.hip's affine_coord: m0 x + (m1 y + m2), no contraction
+__device__ __forceinline__ double affine_coord(double m0, double m1, double m2, double x, double y) {
+#pragma clang fp contract(off)
+  const double t = m1 * y + m2;
+  return m0 * x + t;
+}
+
+// dst[k][h2][w2] = mean of the 2 x 2 blocks of src[k][h][w] (w2 = w / 2, h2 = h / 2), blockIdx.y = k
+__global__ __launch_bounds__(256) void k_down2_stack(const double* __restrict__ src, double* __restrict__ dst, int w, int h,
+                                                     int w2, int h2) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= w2 * h2) return;
+  const int r = i / w2, c = i - r * w2;
+  const double* s = src + (size_t)blockIdx.y * w * h + (size_t)(2 * r) * w + 2 * c;
+  dst[(size_t)blockIdx.y * w2 * h2 + i] = 0.25 * ((s[0] + s[1]) + (s[w] + s[w + 1]));
+}
+
+// partial[((f * ncand + cand) * gridDim.y + chunk)] = sum of (I_{f+1}(p + u) - I_0(p))^2 over the rows of this chunk of
+// the window [R, w-R) x [R, h-R), u = (cand % n1 - R, cand / n1 - R), n1 = 2R + 1.  grid = (ncand, chunks, frames - 1).
+__global__ __launch_bounds__(256) void k_ssd_window(const double* __restrict__ stack, int w, int h, int R,
+                                                    int rows_per_chunk, double* __restrict__ partial) {
+  __shared__ double red[4];
+  const int n1 = 2 * R + 1, cand = blockIdx.x, ux = cand % n1 - R, uy = cand / n1 - R;
+  const double* a = stack;
+  const double* b = stack + (size_t)(blockIdx.z + 1) * w * h;
+  const int r0 = R + blockIdx.y * rows_per_chunk, r1 = min(h - R, r0 + rows_per_chunk);
+  double s = 0.0;
+  for (int r = r0; r < r1; ++r) {
+    for (int c = R + (int)threadIdx.x; c < w - R; c += 256) {
+      const double d = b[(size_t)(r + uy) * w + c + ux] - a[(size_t)r * w + c];
+      s += d * d;
+    }
+  }
+  s = wsum(s);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) red[wv] = s;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partial[((size_t)blockIdx.z * gridDim.x + cand) * gridDim.y + blockIdx.y] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Gauss-Newton sums of one inverse-compositional pass for every frame: grid = (row chunks, frames - 1).
+// table[f][kFrameRec]: F of frame f + 1 at this level and its "active" flag.  Over the template pixels p of this chunk's
+// rows (1 px from the border) whose four taps of I_{f+1} at s = F(p) are inside:
+//   e = I(s) - I_0(p), (gx, gy) central differences of I_0, (u, v) = p - centre,
+//   partial[(f * chunks + chunk)][26] = {gx^2, gx gy, gy^2} x {u^2, uv, u, v^2, v, 1} (index 6 a + m),
+//                                       {gx e, gy e} x {u, v, 1} (18 + 3 a + m), e^2 (24), count (25).
+__global__ __launch_bounds__(256) void k_affine_gn_sums(const double* __restrict__ stack, int w, int h, int rows_per_chunk,
+                                                        const double* __restrict__ table, double* __restrict__ partial) {
+  __shared__ double red[kGnSums][4];
+  const int f = blockIdx.y;
+  const double* m = table + (size_t)f * kFrameRec;
+  if (m[6] == 0.0) return;  // converged frame: uniform
+  const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+  const double* a = stack;
+  const double* b = stack + (size_t)(f + 1) * w * h;
+  const double cx = 0.5 * (double)(w - 1), cy = 0.5 * (double)(h - 1);
+  const double xmax = (double)(w - 1), ymax = (double)(h - 1);
+  const int r0 = 1 + blockIdx.x * rows_per_chunk, r1 = min(h - 1, r0 + rows_per_chunk);
+  double acc[kGnSums];
+#pragma unroll
+  for (int q = 0; q < kGnSums; ++q) acc[q] = 0.0;
+  for (int r = r0; r < r1; ++r) {
+    const double v = (double)r - cy;
+    for (int c = 1 + (int)threadIdx.x; c < w - 1; c += 256) {
+      const double sx = affine_coord(m0, m1, m2, (double)c, (double)r);
+      const double sy = affine_coord(m3, m4, m5, (double)c, (double)r);
+      if (!(sx >= 0.0 && sx < xmax && sy >= 0.0 && sy < ymax)) continue;  // a tap outside (NaN included): left out
+      const double x0 = __builtin_floor(sx), y0 = __builtin_floor(sy);
+      const double fx = sx - x0, fy = sy - y0;
+      const double* pb = b + (size_t)(int)y0 * w + (int)x0;  // x0 in [0, w-2], y0 in [0, h-2]
+      const double val = (1.0 - fy) * ((1.0 - fx) * pb[0] + fx * pb[1]) + fy * ((1.0 - fx) * pb[w] + fx * pb[w + 1]);
+      const double* pa = a + (size_t)r * w + c;
+      const double e = val - pa[0];
+      const double gx = 0.5 * (pa[1] - pa[-1]), gy = 0.5 * (pa[w] - pa[-w]);
+      const double u = (double)c - cx;
+      const double gg[3] = {gx * gx, gx * gy, gy * gy};
+      const double mm[5] = {u * u, u * v, u, v * v, v};
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) acc[6 * i + j] += gg[i] * mm[j];
+        acc[6 * i + 5] += gg[i];
+      }
+      const double ge[2] = {gx * e, gy * e};
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        acc[18 + 3 * i] += ge[i] * u;
+        acc[19 + 3 * i] += ge[i] * v;
+        acc[20 + 3 * i] += ge[i];
+      }
+      acc[24] += e * e;
+      acc[25] += 1.0;
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < kGnSums; ++q) {
+    const double s = wsum(acc[q]);
+    if (lane == 0) red[q][wv] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kGnSums) {
+    const int q = threadIdx.x;
+    partial[((size_t)f * gridDim.x + blockIdx.x) * kGnSums + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+  }
+}
+
+// sums[f][26] = the chunk partials of frame f + 1 added in index order.  grid = frames - 1, 64 threads.
+__global__ __launch_bounds__(64) void k_affine_gn_reduce(const double* __restrict__ partial, int chunks,
+                                                         const double* __restrict__ table, double* __restrict__ sums) {
+  const int f = blockIdx.x, q = threadIdx.x;
+  if (table[(size_t)f * kFrameRec + 6] == 0.0 || q >= kGnSums) return;
+  double s = 0.0;
+  for (int k = 0; k < chunks; ++k) s += partial[((size_t)f * chunks + k) * kGnSums + q];
+  sums[(size_t)f * kGnSums + q] = s;
+}
+
+// ---- host side: 2 x 3 maps [a b tx c d ty] ----
+struct Map { double m[6]; };
+
+double deviation(const Map& F) {
+  return std::max(std::fabs(F.m[0] - 1.0) + std::fabs(F.m[1]), std::fabs(F.m[3]) + std::fabs(F.m[4] - 1.0));
+}
+bool all_finite(const Map& F) {
+  for (double v : F.m) if (!std::isfinite(v)) return false;
+  return true;
+}
+// fine p = 2 u + 1/2: L unchanged, t_fine = 2 t + (1/2, 1/2) - L (1/2, 1/2)
+Map to_finer(const Map& F) {
+  Map G = F;
+  G.m[2] = 2.0 * F.m[2] + 0.5 - (F.m[0] * 0.5 + F.m[1] * 0.5);
+  G.m[5] = 2.0 * F.m[5] + 0.5 - (F.m[3] * 0.5 + F.m[4] * 0.5);
+  return G;
+}
+Map to_coarser(const Map& F) {
+  Map G = F;
+  G.m[2] = 0.5 * (F.m[2] - 0.5 + (F.m[0] * 0.5 + F.m[1] * 0.5));
+  G.m[5] = 0.5 * (F.m[5] - 0.5 + (F.m[3] * 0.5 + F.m[4] * 0.5));
+  return G;
+}
+double corner_displacement(const Map& A, const Map& B, int w, int h) {
+  double worst = 0.0;
+  for (int i = 0; i < 4; ++i) {
+    const double x = (i & 1) ? w - 1.0 : 0.0, y = (i & 2) ? h - 1.0 : 0.0;
+    const double dx = (A.m[0] - B.m[0]) * x + (A.m[1] - B.m[1]) * y + (A.m[2] - B.m[2]);
+    const double dy = (A.m[3] - B.m[3]) * x + (A.m[4] - B.m[4]) * y + (A.m[5] - B.m[5]);
+    worst = std::max(worst, std::hypot(dx, dy));
+  }
+  return worst;
+}
+
+// H (6 x 6, from the 18 sums) D = g by Cholesky; false where a pivot is not above kPivotRtol of its diagonal entry
+bool solve_step(const double* S, double* delta) {
+  // J_i = g_{i / 3} * m_{i % 3}, m = (u, v, 1); product index of (m_i, m_j) in {u^2, uv, u, v^2, v, 1}
+  static const int mprod[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+  double H[6][6], Lc[6][6] = {}, g[6], y[6];
+  for (int i = 0; i < 6; ++i) {
+    for (int j = 0; j < 6; ++j) H[i][j] = S[6 * (i / 3 + j / 3) + mprod[i % 3][j % 3]];
+    g[i] = S[18 + i];
+  }
+  for (int j = 0; j < 6; ++j) {
+    double p = H[j][j];
+    for (int k = 0; k < j; ++k) p -= Lc[j][k] * Lc[j][k];
+    if (!(H[j][j] > 0.0 && p > kPivotRtol * H[j][j])) return false;
+    Lc[j][j] = std::sqrt(p);
+    for (int i = j + 1; i < 6; ++i) {
+      double s = H[i][j];
+      for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
+      Lc[i][j] = s / Lc[j][j];
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    double s = g[i];
+    for (int k = 0; k < i; ++k) s -= Lc[i][k] * y[k];
+    y[i] = s / Lc[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+    for (int k = i + 1; k < 6; ++k) s -= Lc[k][i] * delta[k];
+    delta[i] = s / Lc[i][i];
+  }
+  return true;
+}
+
+// F o W^-1, W(p) = p + D (p - c) + d with D = [D0 D1; D3 D4], d = (D2, D5), c = ((w-1)/2, (h-1)/2)
+Map compose_with_inverse(const Map& F, const double* delta, int w, int h) {
+  const double cx = 0.5 * (w - 1), cy = 0.5 * (h - 1);
+  const double A00 = 1.0 + delta[0], A01 = delta[1], A10 = delta[3], A11 = 1.0 + delta[4];
+  const double tx = delta[2] - (delta[0] * cx + delta[1] * cy), ty = delta[5] - (delta[3] * cx + delta[4] * cy);
+  const double det = A00 * A11 - A01 * A10;
+  const double i00 = A11 / det, i01 = -A01 / det, i10 = -A10 / det, i11 = A00 / det;
+  Map G;
+  G.m[0] = F.m[0] * i00 + F.m[1] * i10;
+  G.m[1] = F.m[0] * i01 + F.m[1] * i11;
+  G.m[3] = F.m[3] * i00 + F.m[4] * i10;
+  G.m[4] = F.m[3] * i01 + F.m[4] * i11;
+  G.m[2] = F.m[2] - (G.m[0] * tx + G.m[1] * ty);
+  G.m[5] = F.m[5] - (G.m[3] * tx + G.m[4] * ty);
+  return G;
+}
+
+}  // namespace
+
+}  // namespace srmap
+
+using namespace srmap;
+
+extern "C" void srmap_affine_registration_options_default(srmap_affine_registration_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_affine_registration_options);
+  o->hr_scale = 1;
+  o->max_iterations = 30;
+  o->step_tolerance = 1e-4;
+  o->max_levels = 0;
+  o->initial_affine_2x3 = nullptr;
+}
+
+extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, int height, const double* images_host,
+                                     const srmap_affine_registration_options* options, double* affine_2x3_out,
+                                     double* quality_out) {
+  if (!ctx || !affine_2x3_out || num_images < 0) return SRMAP_EINVAL;
+  srmap_affine_registration_options opt;
+  srmap_affine_registration_options_default(&opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_affine_registration_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_affine_registration_options.struct_size is not this library's");
+    opt = *options;
+  }
+  if (opt.hr_scale < 1 || opt.max_iterations < 1 || opt.max_levels < 0 || !(opt.step_tolerance >= 0.0))
+    return set_error(ctx, SRMAP_EINVAL, "affine registration: bad options");
+  if (num_images == 0) return SRMAP_OK;
+  if (!images_host || width < 8 || height < 8)
+    return set_error(ctx, SRMAP_EINVAL, "registration needs images of at least 8 x 8");
+  const int K = num_images, nf = K - 1;
+  const double ident[6] = {1, 0, 0, 0, 1, 0};
+  std::copy(ident, ident + 6, affine_2x3_out);
+  if (quality_out) { quality_out[0] = 1.0; quality_out[1] = 0.0; quality_out[2] = 1.0; quality_out[3] = 0.0; }
+  if (K == 1) return SRMAP_OK;
+
+  std::vector<Map> F(nf);
+  std::vector<double> sep(nf, 1.0);
+  if (opt.initial_affine_2x3) {
+    for (int f = 0; f < nf; ++f) {
+      std::copy(opt.initial_affine_2x3 + 6 * (f + 1), opt.initial_affine_2x3 + 6 * (f + 2), F[f].m);
+      if (!all_finite(F[f]) || deviation(F[f]) > kMaxDeviation)
+        return set_error(ctx, SRMAP_EINVAL, "affine registration: initial matrix %d is not finite or outside the model's domain", f + 1);
+    }
+  }
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  std::vector<int> lw{width}, lh{height};
+  while (std::min(lw.back(), lh.back()) >= 64 && (int)lw.size() < kMaxLevels &&
+         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
+    lw.push_back(lw.back() / 2);
+    lh.push_back(lh.back() / 2);
+  }
+  const int L = (int)lw.size();
+  std::vector<size_t> off(L + 1, 0);
+  for (int l = 0; l < L; ++l) off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
+  auto chunks_of = [](int h) { return std::min(kMaxRowChunks, std::max(1, (h - 2 + 7) / 8)); };
+  const int cw = lw.back(), ch = lh.back();
+  const int R = std::max(4, std::min(16, std::min(cw, ch) / 4)), n1 = 2 * R + 1, ncand = n1 * n1;
+  const bool seed = !opt.initial_affine_2x3, seed_window = cw - 2 * R > 0 && ch - 2 * R > 0;
+  const int seed_chunks = seed_window ? std::min(kMaxSeedChunks, ch - 2 * R) : 0;
+  const size_t part_elems = std::max((size_t)nf * chunks_of(height) * kGnSums, seed ? (size_t)nf * ncand * seed_chunks : 0);
+
+  double *d_pyr = nullptr, *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr, *h_tab = nullptr, *h_sums = nullptr;
+  int rc = SRMAP_OK;
+  auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "affine registration: %s", what); };
+  if (hipMalloc((void**)&d_pyr, off[L] * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d_part, part_elems * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d_tab, (size_t)nf * kFrameRec * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d_sums, (size_t)nf * kGnSums * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h_tab, (size_t)nf * kFrameRec * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h_sums, (size_t)nf * kGnSums * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    fail(SRMAP_ENOMEM, "allocation failed");
+  }
+
+  // ---- pyramids of the whole stack, once ----
+  if (rc == SRMAP_OK) {
+    if (hipMemcpyAsync(d_pyr, images_host, (size_t)K * width * height * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+      fail(SRMAP_EHIP, "upload failed");
+    for (int l = 1; l < L && rc == SRMAP_OK; ++l) {
+      const int n = lw[l] * lh[l];
+      hipLaunchKernelGGL(k_down2_stack, dim3((n + 255) / 256, K), dim3(256), 0, st, d_pyr + off[l - 1], d_pyr + off[l],
+                         lw[l - 1], lh[l - 1], lw[l], lh[l]);
+    }
+    if (rc == SRMAP_OK && hipGetLastError() != hipSuccess) fail(SRMAP_EHIP, "pyramid failed");
+  }
+
+  // ---- seed: integer translation at the coarsest level, or the caller's matrices taken down the pyramid ----
+  if (rc == SRMAP_OK && !seed) {
+    for (int f = 0; f < nf; ++f)
+      for (int l = 1; l < L; ++l) F[f] = to_coarser(F[f]);
+  } else if (rc == SRMAP_OK) {
+    for (int f = 0; f < nf; ++f) { std::copy(ident, ident + 6, F[f].m); sep[f] = 0.0; }
+    if (seed_window) {
+      const int rows = ch - 2 * R, rpc = (rows + seed_chunks - 1) / seed_chunks;
+      const size_t n = (size_t)nf * ncand * seed_chunks;
+      std::vector<double> h_part(n);
+      hipLaunchKernelGGL(k_ssd_window, dim3(ncand, seed_chunks, nf), dim3(256), 0, st, d_pyr + off[L - 1], cw, ch, R, rpc, d_part);
+      if (hipGetLastError() != hipSuccess ||
+          hipMemcpyAsync(h_part.data(), d_part, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess) {
+        fail(SRMAP_EHIP, "coarse search failed");
+      } else {
+        const double count = (double)rows * (cw - 2 * R);
+        std::vector<double> msd(ncand);
+        for (int f = 0; f < nf; ++f) {
+          int bi = 0;
+          for (int c = 0; c < ncand; ++c) {
+            double s = 0.0;
+            for (int k = 0; k < seed_chunks; ++k) s += h_part[((size_t)f * ncand + c) * seed_chunks + k];
+            msd[c] = s / count;
+            if (msd[c] < msd[bi]) bi = c;  // the first minimum in row-major order wins
+          }
+          double runner = -1.0;
+          for (int c = 0; c < ncand; ++c) {
+            if (std::max(std::abs(c % n1 - bi % n1), std::abs(c / n1 - bi / n1)) < 2) continue;
+            if (runner < 0 || msd[c] < runner) runner = msd[c];
+          }
+          sep[f] = runner > 0 ? 1.0 - msd[bi] / runner : 0.0;
+          F[f].m[2] = bi % n1 - R;
+          F[f].m[5] = bi / n1 - R;
+        }
+      }
+    }
+  }
+
+  // one pass over every frame flagged active: sums land in h_sums
+  std::vector<char> active(nf, 1);
+  auto pass = [&](int l) -> bool {
+    for (int f = 0; f < nf; ++f) {
+      std::copy(F[f].m, F[f].m + 6, h_tab + (size_t)f * kFrameRec);
+      h_tab[(size_t)f * kFrameRec + 6] = active[f] ? 1.0 : 0.0;
+      h_tab[(size_t)f * kFrameRec + 7] = 0.0;
+    }
+    const int chunks = chunks_of(lh[l]), rpc = (lh[l] - 2 + chunks - 1) / chunks;
+    if (hipMemcpyAsync(d_tab, h_tab, (size_t)nf * kFrameRec * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_affine_gn_sums, dim3(chunks, nf), dim3(256), 0, st, d_pyr + off[l], lw[l], lh[l], rpc, d_tab, d_part);
+    hipLaunchKernelGGL(k_affine_gn_reduce, dim3(nf), dim3(64), 0, st, d_part, chunks, d_tab, d_sums);
+    return hipGetLastError() == hipSuccess &&
+           hipMemcpyAsync(h_sums, d_sums, (size_t)nf * kGnSums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+  };
+
+  // ---- Gauss-Newton, coarse to fine ----
+  std::vector<int> iters(nf, 0);
+  for (int l = L - 1; l >= 0 && rc == SRMAP_OK; --l) {
+    std::fill(active.begin(), active.end(), 1);
+    for (int it = 0; it < opt.max_iterations && rc == SRMAP_OK; ++it) {
+      if (std::find(active.begin(), active.end(), 1) == active.end()) break;
+      if (!pass(l)) { fail(SRMAP_EHIP, "Gauss-Newton pass failed"); break; }
+      for (int f = 0; f < nf; ++f) {
+        if (!active[f]) continue;
+        const double* S = h_sums + (size_t)f * kGnSums;
+        ++iters[f];
+        if (S[25] < 0.25 * lw[l] * lh[l]) { fail(SRMAP_EINVAL, "Could not determine motion between images."); break; }
+        double delta[6];
+        if (!solve_step(S, delta)) { active[f] = 0; continue; }  // no texture: this level keeps F
+        const Map Fn = compose_with_inverse(F[f], delta, lw[l], lh[l]);
+        if (!all_finite(Fn) || deviation(Fn) > kMaxDeviation) { fail(SRMAP_EINVAL, "Could not determine motion between images."); break; }
+        const double step = corner_displacement(Fn, F[f], lw[l], lh[l]);
+        F[f] = Fn;
+        if (step < opt.step_tolerance) active[f] = 0;
+      }
+    }
+    if (l > 0)
+      for (int f = 0; f < nf; ++f) F[f] = to_finer(F[f]);
+  }
+
+  // ---- residual at the result (full resolution), output ----
+  if (rc == SRMAP_OK && quality_out) {
+    std::fill(active.begin(), active.end(), 1);
+    if (!pass(0)) fail(SRMAP_EHIP, "residual pass failed");
+  }
+  if (rc == SRMAP_OK) {
+    for (int f = 0; f < nf; ++f) {
+      double* o = affine_2x3_out + 6 * (f + 1);
+      std::copy(F[f].m, F[f].m + 6, o);
+      o[2] *= opt.hr_scale;
+      o[5] *= opt.hr_scale;
+      if (quality_out) {
+        const double* S = h_sums + (size_t)f * kGnSums;
+        double* q = quality_out + 4 * (f + 1);
+        q[0] = sep[f];
+        q[1] = S[25] > 0 ? std::sqrt(S[24] / S[25]) : 0.0;
+        q[2] = S[25] / ((double)width * height);
+        q[3] = iters[f];
+      }
+    }
+  }
+  if (d_pyr) (void)hipFree(d_pyr);
+  if (d_part) (void)hipFree(d_part);
+  if (d_tab) (void)hipFree(d_tab);
+  if (d_sums) (void)hipFree(d_sums);
+  if (h_tab) (void)hipHostFree(h_tab);
+  if (h_sums) (void)hipHostFree(h_sums);
+  return rc;
+}

@@ -5,9 +5,12 @@
 // truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
 // least-squares solver as the reference does (super_resolution.cpp:134-141; any
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
-// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Not carried over (out of scope, DESIGN.md
+// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor are
+// --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
+// --save_motion_path.  Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <iostream>
 #include <memory>
@@ -21,6 +24,7 @@
 #include "hyperspectral/spectral_pca.h"
 #include "image/image_io.h"
 #include "image_model/image_model.h"
+#include "motion/registration.h"
 #include "optimization/irls_map_solver.h"
 #include "optimization/regularizer.h"
 
@@ -39,6 +43,10 @@ int main(int argc, char** argv) {
       "  not reference flags: [--data_loss=l2|huber] [--huber_delta=0.02] (robust data term, pixel units 0..1)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
+      "                       [--registration=translational|affine] (estimate the solver's motion from the LR frames, in HR\n"
+      "                       pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
+      "                       an error together with either motion file)\n"
+      "                       [--save_motion_path=<file>] (the estimate, 'a b tx c d ty' per line; needs --registration)\n"
       "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
@@ -76,11 +84,29 @@ int main(int argc, char** argv) {
   // not a reference flag: the solver's start x0 as raw little-endian float64 [C][H][W], so that a CPU run of the
   // reference algorithm can start from the IDENTICAL estimate (tests/test_gpu_apps.py compares the two results)
   const std::string save_initial_estimate = flags.Str("save_initial_estimate");
+  // not reference flags: estimate the solver's motion from the LR frames (srmap_register_translational /
+  // srmap_register_affine) instead of reading it from a file, and write the estimate out
+  const std::string registration_name = flags.Str("registration");
+  const std::string save_motion_path = flags.Str("save_motion_path");
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
   if (!model_parameters.affine_motion_sequence_path.empty() && !model_parameters.motion_sequence_path.empty()) {
     std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
+    return 1;
+  }
+  if (!registration_name.empty() && registration_name != "translational" && registration_name != "affine") {
+    std::fprintf(stderr, "ERROR: --registration is 'translational' or 'affine'.\n");
+    return 1;
+  }
+  if (!registration_name.empty() && !generate_lr_images &&
+      (!model_parameters.affine_motion_sequence_path.empty() || !model_parameters.motion_sequence_path.empty())) {
+    std::fprintf(stderr, "ERROR: --registration estimates the motion; it excludes --motion_sequence_path and --affine_motion_path "
+                         "(except with --generate_lr_images, where the files generate the frames).\n");
+    return 1;
+  }
+  if (!save_motion_path.empty() && registration_name.empty()) {
+    std::fprintf(stderr, "ERROR: --save_motion_path needs --registration.\n");
     return 1;
   }
   // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
@@ -153,7 +179,45 @@ int main(int argc, char** argv) {
     std::fclose(f);
   }
 
-  IRLSMapSolver solver(solver_options, image_model, low_res_images, verbose);
+  // --registration: the solver's model takes its motion from the frames it is about to solve (channel 0), in HR pixels;
+  // the generating model above keeps the motion files
+  ImageModelParameters solver_parameters = model_parameters;
+  if (!registration_name.empty()) {
+    solver_parameters.motion_sequence_path.clear();
+    solver_parameters.affine_motion_sequence_path.clear();
+    AffineMotionSequence estimate;
+    if (registration_name == "affine") {
+      estimate = registration::AffineRegistration(low_res_images, upsampling_scale);
+      solver_parameters.affine_motion_sequence = estimate;
+    } else {
+      const MotionShiftSequence lr_shifts = registration::TranslationalRegistration(low_res_images);
+      std::vector<MotionShift> shifts;
+      std::vector<AffineMotion> motions;
+      for (int i = 0; i < lr_shifts.GetNumMotionShifts(); ++i) {
+        shifts.push_back(MotionShift(upsampling_scale * lr_shifts[i].dx, upsampling_scale * lr_shifts[i].dy));
+        motions.push_back(AffineMotion(1.0, 0.0, shifts.back().dx, 0.0, 1.0, shifts.back().dy));
+      }
+      solver_parameters.motion_sequence = MotionShiftSequence(shifts);
+      estimate = AffineMotionSequence(motions);
+    }
+    std::printf("Estimated %s motion of %d frames from the low-resolution images.\n", registration_name.c_str(),
+                estimate.GetNumMotions());
+    if (!save_motion_path.empty()) {
+      std::FILE* f = std::fopen(save_motion_path.c_str(), "w");
+      if (!f) {
+        std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_motion_path.c_str());
+        return 1;
+      }
+      for (int i = 0; i < estimate.GetNumMotions(); ++i) {
+        const AffineMotion& m = estimate[i];
+        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", m.a, m.b, m.tx, m.c, m.d, m.ty);
+      }
+      std::fclose(f);
+    }
+  }
+  const ImageModel solver_model = registration_name.empty() ? image_model : ImageModel::CreateImageModel(solver_parameters);
+
+  IRLSMapSolver solver(solver_options, solver_model, low_res_images, verbose);
   if (regularization_parameter > 0.0) {
     std::shared_ptr<Regularizer> regularizer;
     if (regularizer_name == "btv") {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "image/image_data.h"
+#include "motion/affine_motion.h"
 #include "motion/motion_shift.h"
 #include "util/srmap_host.h"
 
@@ -66,6 +67,46 @@ inline MotionShiftSequence TranslationalRegistrationWithQuality(const std::vecto
   std::vector<MotionShift> shifts;
   for (size_t i = 0; i < images.size(); ++i) shifts.push_back(MotionShift(xy[2 * i], xy[2 * i + 1]));
   return MotionShiftSequence(shifts);
+}
+
+// Not in the reference: the affine motion of every image relative to the first one (srmap_register_affine,
+// csrc/registration_affine.hip), as an AffineMotionSequence in units of `scale` input pixels -- register the LR frames
+// with scale = the upsampling scale and the result is what MotionModule(AffineMotionSequence) takes.  Channel 0 is the
+// registration image; an empty list gives an empty sequence; image 0 gets the identity.  Dense, no outlier rejection,
+// one plane: include/srmap.h states the domain.  quality (WithQuality): 4 per image -- separation of the coarse minimum,
+// RMS residual, fraction of pixels used, Gauss-Newton passes.
+inline AffineMotionSequence AffineRegistrationWithQuality(const std::vector<ImageData>& images, const int scale,
+                                                          std::vector<double>* quality) {
+  if (images.empty()) {
+    std::fprintf(stderr, "WARNING: No images given. Returning an empty motion sequence.\n");
+    return AffineMotionSequence();
+  }
+  const cv::Size size = images[0].GetImageSize();
+  const size_t npx = static_cast<size_t>(size.width) * size.height;
+  std::vector<double> stack(npx * images.size());
+  for (size_t i = 0; i < images.size(); ++i) {
+    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
+        images[i].GetImageSize().height != size.height)
+      srmap_host::Fail("registration needs images of one size with at least one channel");
+    const double* ch = images[i].GetChannelData(0);
+    std::copy(ch, ch + npx, stack.begin() + i * npx);
+  }
+  srmap_affine_registration_options options;
+  srmap_affine_registration_options_default(&options);
+  options.hr_scale = scale;
+  std::vector<double> m(6 * images.size());
+  if (quality) quality->assign(4 * images.size(), 0.0);
+  srmap_host::Check(srmap_register_affine(srmap_host::Context(), static_cast<int>(images.size()), size.width, size.height,
+                                          stack.data(), &options, m.data(), quality ? quality->data() : nullptr),
+                    "Could not determine motion between images.");
+  std::vector<AffineMotion> motions;
+  for (size_t i = 0; i < images.size(); ++i)
+    motions.push_back(AffineMotion(m[6 * i], m[6 * i + 1], m[6 * i + 2], m[6 * i + 3], m[6 * i + 4], m[6 * i + 5]));
+  return AffineMotionSequence(motions);
+}
+
+inline AffineMotionSequence AffineRegistration(const std::vector<ImageData>& images, const int scale = 1) {
+  return AffineRegistrationWithQuality(images, scale, nullptr);
 }
 
 }  // namespace registration

@@ -47,6 +47,11 @@ class IrlsOptions(C.Structure):
                 ("host_paced_passes", C.c_int)]
 
 
+class AffineRegistrationOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("hr_scale", C.c_int), ("max_iterations", C.c_int),
+                ("step_tolerance", C.c_double), ("max_levels", C.c_int), ("initial_affine_2x3", c_double_p)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -104,6 +109,8 @@ _SIGNATURES = [
     ("srmap_channel_map_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, c_double_p, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("srmap_register_translational", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p]),
     ("srmap_register_translational_ex", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+    ("srmap_affine_registration_options_default", None, [C.c_void_p]),
+    ("srmap_register_affine", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p]),
     ("srmap_channel_pca", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_channel_pca_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     ("srmap_synchronize", C.c_int, [C.c_void_p]),
@@ -201,6 +208,28 @@ class Context:
         self.check(load().srmap_register_translational_ex(self._h, n, W, H, pa, out.ctypes.data_as(c_double_p),
                                                           q.ctypes.data_as(c_double_p)))
         return out, q
+
+    def register_affine(self, images, hr_scale=1, init=None, max_iterations=30, step_tolerance=1e-4, max_levels=0,
+                        with_quality=False, struct_size=None):
+        """srmap_register_affine: images [n][H][W] -> [n][2][3] = [a b tx; c d ty] of F_k, I_k(F_k(p)) ~= I_0(p), t in
+        units of hr_scale input pixels (ready for Problem.set_affine_motion); init: [n][2][3] starting matrices in input
+        pixels instead of the coarse search (with_quality: also [n][4] = separation, RMS residual, used pixel fraction,
+        Gauss-Newton passes -- srmap.h).  struct_size overrides the options' size field (tests)."""
+        a, pa = _d(images)
+        n, H, W = a.shape
+        o = AffineRegistrationOptions()
+        load().srmap_affine_registration_options_default(C.byref(o))
+        o.hr_scale, o.max_iterations, o.step_tolerance, o.max_levels = hr_scale, max_iterations, step_tolerance, max_levels
+        if struct_size is not None:
+            o.struct_size = struct_size
+        if init is not None:
+            ini, pi = _d(init)
+            assert ini.size == n * 6, (ini.shape, n)
+            o.initial_affine_2x3 = pi
+        out, q = np.zeros((n, 2, 3)), np.zeros((n, 4))
+        self.check(load().srmap_register_affine(self._h, n, W, H, pa, C.byref(o), out.ctypes.data_as(c_double_p),
+                                                q.ctypes.data_as(c_double_p) if with_quality else None))
+        return (out, q) if with_quality else out
 
     def pca(self, samples):
         """PCA of planar samples [rows][count] on the GPU: (mean, eigenvalues descending, basis rows = eigenvectors)."""
