@@ -33,7 +33,7 @@
  *   - entry points that take HOST pointers (srmap_eval, srmap_solve*,
  *     srmap_cg_trace, srmap_apply*, srmap_reg_values*, srmap_set_observations,
  *     srmap_set_irls_weights, srmap_set_data_weights, srmap_get_data_weights, srmap_channel_map, srmap_channel_pca,
- *     srmap_register_translational, srmap_register_affine, srmap_upload / srmap_download) run on the
+ *     srmap_register_translational, srmap_register_affine, srmap_refine_motion, srmap_upload / srmap_download) run on the
  *     context's stream and are complete when they return.
  *   - the problem's device state (observations, IRLS weights, data weights) is ordered by the
  *     library itself: a write through srmap_update_irls_weights_device / srmap_update_data_weights_device on one
@@ -386,6 +386,51 @@ void srmap_affine_registration_options_default(srmap_affine_registration_options
 int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, int height, const double* images_host,
                           const srmap_affine_registration_options* options /* NULL = defaults */,
                           double* affine_2x3_out /* num_images x 6 */, double* quality_out /* optional, 4 per image */);
+
+/* Joint motion refinement (no reference counterpart; csrc/motion_refinement.hip; it closes what DESIGN.md
+ * 3.7 left out: a registration that honours the forward model and the data weights).  With an HR estimate x, every frame
+ * k >= 1 has its matrix re-fitted THROUGH the affine forward model of 3.6 (srmap_problem_set_affine_motion):
+ *   energy    E_k(G) = sum_c sum_u w_k(c,u) r^2, r = (D B M(G) x)(c,u) - y_k(c,u), G = F_k^-1 (formed as
+ *             srmap_problem_set_affine_motion forms it), over EVERY LR pixel of every channel: the rows of
+ *             srmap_problem_set_cost_rows are ignored.  w: the problem's data weights as they stand (the caller's, or the
+ *             last Huber weights -- a refinement after a Huber solve is an outlier-robust registration), 1 when none are set.
+ *             Always the affine model, exact double coordinates, no 1/32-px quantisation, also for a problem created with
+ *             shifts_xy.  All arithmetic after the loads is double in both dtypes.
+ *   start     F_k from initial_affine_2x3; else the problem's affine motion; else [I | shifts_xy[k]]; else the identity.
+ *   step      G <- G + dL (q - c0) + dt, c0 = ((W-1)/2, (H-1)/2), parameters (da, db, dtx, dc, dd, dty); the pass sums
+ *             H = sum w J J^T (21 entries, upper triangle row-major), g = sum w J r (6) and E: 28 numbers per frame, J the
+ *             exact derivative of the model (the derivative of the four-tap sample, from the sample's own four taps).
+ *   LM        per frame, on the host: (H + lambda diag H) d = -g by the 6 x 6 Cholesky of srmap_register_affine (dof = 2:
+ *             the 2 x 2 system of (dtx, dty), L stays bit-identical); E' < E accepts (lambda <- max(lambda / 10, 1e-9)) and
+ *             stops with status 0 when the four HR image corners moved less than step_tolerance; otherwise lambda <- 10
+ *             lambda, status 2 once lambda > 1e6.  A trial outside 3.6's domain or not finite is a rejection that spends no
+ *             pass.  A failed Cholesky (no texture, or a frame whose weights are all 0) keeps the matrix: status 3.  The
+ *             iteration cap: status 1 (also what max_iterations = 0 answers).  No status is an error of the call.
+ * Frame 0 is the gauge: never changed, quality (cost, cost, 0, 0).
+ * affine_2x3_out (optional, K x 6): the matrices F_k.  quality_out (optional, K x 4): E at the start, E at the result, passes
+ * run, status.  normal_equations_out (optional, K x 28): the sums at the returned matrix.  apply = 1 installs the result as
+ * srmap_problem_set_affine_motion(result) would (the problem then evaluates the affine model); apply = 0 leaves the problem
+ * alone.  SRMAP_EINVAL: no observations set; a struct_size that is not this library's; dof not 2 or 6; negative
+ * max_iterations, step_tolerance or initial_damping; a starting matrix that is not finite.  SRMAP_EUNSUPPORTED: a starting
+ * matrix outside the domain.  Every error leaves the problem unchanged.  Results are bit-identical run to run and a frame's
+ * answer does not depend on the other frames.  Sharded problems are out of scope.  Not thread-safe against evaluations of the
+ * same problem, as srmap_problem_set_affine_motion.  The _device form takes x in the problem's dtype and enqueues on
+ * hip_stream (NULL = the context's stream); both forms are complete when they return. */
+typedef struct {
+  int struct_size;          /* filled by the _default call; a mismatch is SRMAP_EINVAL */
+  int dof;                  /* 6 = full 2 x 3 (default); 2 = translation only (tx, ty) */
+  int max_iterations;       /* 30: trial passes per frame after the initial pass; 0 = evaluate only */
+  double step_tolerance;    /* 1e-4 HR px */
+  double initial_damping;   /* 1e-3; >= 0 */
+  int apply;                /* 1 */
+  const double* initial_affine_2x3; /* NULL = the problem's current motion; else K x 6 */
+} srmap_motion_refinement_options;
+void srmap_motion_refinement_options_default(srmap_motion_refinement_options* options);
+int srmap_refine_motion(srmap_problem* p, const double* x_host, const srmap_motion_refinement_options* options /* NULL = defaults */,
+                        double* affine_2x3_out, double* quality_out, double* normal_equations_out);
+int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                               const srmap_motion_refinement_options* options /* NULL = defaults */,
+                               double* affine_2x3_out, double* quality_out, double* normal_equations_out);
 
 /* ------------------------------------------------------------- solver */
 /* IRLSMapSolverOptions (irls_map_solver.h:14-36) + MapSolverOptions

@@ -1,0 +1,424 @@
+// motion_refinement.hip -- joint motion refinement (srmap_refine_motion): re-fit every frame's 2 x 3 matrix
+// to an HR estimate x THROUGH the forward model, minimising E_k(G) = sum_c sum_u w_k(c,u) r^2, r = (D B M(G) x)(c,u) - y_k(c,u),
+// over G = F_k^-1 by Levenberg-Marquardt.  The model holds the aliasing, the blur and the zero border that bias a
+// frame-to-frame registration (registration_affine.hip).  No reference counterpart; the checker is
+// tests/motion_refinement_restatement.py.
+//   pass      ONE launch of k_refine_sums for every still-active frame: per LR pixel and channel the residual r and
+//             J_i = sum over k_forward_affine's blur taps of blur * g * {q_x - c0x, q_y - c0y, 1}, g the exact derivative of
+//             the four-tap sample in s_x (i = 0..2) or s_y (i = 3..5), from the four tap values the sample itself uses;
+//             28 f64 sums per workgroup (21 of H = sum w J J^T, upper triangle row-major; 6 of g = sum w J r; E), folded by a
+//             wave shuffle and LDS in a fixed order, no atomics; k_refine_reduce adds the chunk records in index order;
+//   pacing    per pass one upload of the frame table, one copy of K x 28 doubles, one stream wait (section 3.7's);
+//   LM        on the host in double, per frame, in lockstep: (H + lambda diag H) d = -g by the 6 x 6 Cholesky of
+//             registration_affine.hip (dof = 2: the 2 x 2 sub-system of (tx, ty)), G' = G + dL (q - c0) + dt.
+// Everything after the loads is double in both dtypes.  Sample positions are kernels_affine.hip's (affine_coord).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "srmap_internal.hpp"
+
+namespace srmap {
+
+namespace {
+
+constexpr int kSums = 28;       // 21 of H, 6 of g, E
+constexpr int kTabRec = 8;      // G = [ia ib itx ic id ity], active, pad
+constexpr int kMaxChunks = 256;
+constexpr double kPivotRtol = 1e-12;
+constexpr double kMinDamping = 1e-9, kMaxDamping = 1e6;
+
+__device__ __forceinline__ double wsum_r(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// kernels_affine.hip's affine_coord: m0 x + (m1 y + m2), no contraction
+__device__ __forceinline__ double affine_coord_r(double m0, double m1, double m2, double x, double y) {
+#pragma clang fp contract(off)
+  const double t = m1 * y + m2;
+  return m0 * x + t;
+}
+
+// Sums of one pass for every active frame: grid = (chunks of LR pixels, frames), 256 threads; a workgroup covers the LR
+// pixels [chunk * 256 * ppt, (chunk + 1) * 256 * ppt) of its frame, thread t the pixels t, t + 256, ...
+// table[k][kTabRec] is indexed by the frame alone (scalar loads).  partial[(k * chunks + chunk)][28].
+template <typename T, bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, const T* __restrict__ y,
+                                                     const T* __restrict__ dw, Geometry g, const T* __restrict__ blur,
+                                                     const int* __restrict__ col_map, const int* __restrict__ row_map,
+                                                     const double* __restrict__ table, int ppt,
+                                                     double* __restrict__ partial) {
+  __shared__ double red[kSums][4];
+  const int k = blockIdx.y;
+  const double* __restrict__ m = table + (size_t)k * kTabRec;  // uniform: scalar loads
+  if (m[6] == 0.0) return;                                     // stopped frame: uniform
+  const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
+  const int n = g.w * g.h;
+  const double c0x = 0.5 * (double)(g.W - 1), c0y = 0.5 * (double)(g.H - 1);
+  double acc[kSums];
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) acc[q] = 0.0;
+  const size_t base = (size_t)blockIdx.x * 256 * ppt + threadIdx.x;
+  for (int t = 0; t < ppt; ++t) {
+    const size_t lp = base + (size_t)t * 256;
+    if (lp >= (size_t)n) break;
+    const int i = (int)(lp / g.w), j = (int)(lp - (size_t)i * g.w);
+    const int R0 = row_map[i], C0 = col_map[j];
+    for (int c = 0; c < g.C; ++c) {
+      const T* __restrict__ plane = x + (size_t)c * g.W * g.H;
+      double val = 0.0, J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int a = 0; a < g.b; ++a) {
+        const int rr = R0 + a - g.hb;
+        if (rr < 0 || rr >= g.H) continue;  // k_forward_affine's taps: the blur's zero border
+        for (int e = 0; e < g.b; ++e) {
+          const int cc = C0 + e - g.hb;
+          if (cc < 0 || cc >= g.W) continue;
+          const double sx = affine_coord_r(m0, m1, m2, (double)cc, (double)rr);
+          const double sy = affine_coord_r(m3, m4, m5, (double)cc, (double)rr);
+          if (!(sx > -1.0 && sx < (double)g.W && sy > -1.0 && sy < (double)g.H)) continue;  // no tap inside (NaN included)
+          const double x0d = __builtin_floor(sx), y0d = __builtin_floor(sy);
+          const double fx = sx - x0d, fy = sy - y0d;
+          const int sc = (int)x0d, sr = (int)y0d;  // sr in [-1, H-1], sc in [-1, W-1]
+          const bool r0 = sr >= 0, r1 = sr + 1 < g.H, q0 = sc >= 0, q1 = sc + 1 < g.W;
+          const double v00 = (r0 && q0) ? (double)plane[(size_t)sr * g.W + sc] : 0.0;
+          const double v01 = (r0 && q1) ? (double)plane[(size_t)sr * g.W + sc + 1] : 0.0;
+          const double v10 = (r1 && q0) ? (double)plane[(size_t)(sr + 1) * g.W + sc] : 0.0;
+          const double v11 = (r1 && q1) ? (double)plane[(size_t)(sr + 1) * g.W + sc + 1] : 0.0;
+          const double bw = (double)blur[a * g.b + e];
+          const double s = (1.0 - fy) * ((1.0 - fx) * v00 + fx * v01) + fy * ((1.0 - fx) * v10 + fx * v11);
+          const double gx = bw * ((1.0 - fy) * (v01 - v00) + fy * (v11 - v10));
+          const double gy = bw * ((1.0 - fx) * (v10 - v00) + fx * (v11 - v01));
+          const double u = (double)cc - c0x, v = (double)rr - c0y;
+          val += bw * s;
+          J[0] += gx * u; J[1] += gx * v; J[2] += gx;
+          J[3] += gy * u; J[4] += gy * v; J[5] += gy;
+        }
+      }
+      const size_t oi = ((size_t)k * g.C + c) * n + lp;
+      const double r = val - (double)y[oi];
+      const double wv = WEIGHTED ? (double)dw[oi] : 1.0;
+      int q = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double wj = wv * J[a];
+#pragma unroll
+        for (int e = a; e < 6; ++e) acc[q++] += wj * J[e];
+        acc[21 + a] += wj * r;
+      }
+      acc[27] += (wv * r) * r;
+    }
+  }
+  const int lane = threadIdx.x & 63, wvi = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < kSums; ++q) {
+    const double s = wsum_r(acc[q]);
+    if (lane == 0) red[q][wvi] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    const int q = threadIdx.x;
+    partial[((size_t)k * gridDim.x + blockIdx.x) * kSums + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+  }
+}
+
+// sums[k][28] = the chunk records of frame k added in index order.  grid = frames, 64 threads.
+__global__ __launch_bounds__(64) void k_refine_reduce(const double* __restrict__ partial, int chunks,
+                                                      const double* __restrict__ table, double* __restrict__ sums) {
+  const int k = blockIdx.x, q = threadIdx.x;
+  if (table[(size_t)k * kTabRec + 6] == 0.0 || q >= kSums) return;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += partial[((size_t)k * chunks + c) * kSums + q];
+  sums[(size_t)k * kSums + q] = s;
+}
+
+// ---- host side ----
+struct Map { double m[6]; };
+
+double deviation(const Map& F) {
+  return std::max(std::fabs(F.m[0] - 1.0) + std::fabs(F.m[1]), std::fabs(F.m[3]) + std::fabs(F.m[4] - 1.0));
+}
+bool all_finite(const Map& F) {
+  for (double v : F.m) if (!std::isfinite(v)) return false;
+  return true;
+}
+// the inverse as affine_records forms it
+Map inverse(const Map& F) {
+  const double a = F.m[0], b = F.m[1], tx = F.m[2], c = F.m[3], d = F.m[4], ty = F.m[5];
+  const double det = a * d - b * c;
+  const double ia = d / det, ib = -b / det, ic = -c / det, id = a / det;
+  Map G;
+  G.m[0] = ia; G.m[1] = ib; G.m[2] = -(ia * tx + ib * ty);
+  G.m[3] = ic; G.m[4] = id; G.m[5] = -(ic * tx + id * ty);
+  return G;
+}
+double corner_displacement(const Map& A, const Map& B, int w, int h) {
+  double worst = 0.0;
+  for (int i = 0; i < 4; ++i) {
+    const double x = (i & 1) ? w - 1.0 : 0.0, y = (i & 2) ? h - 1.0 : 0.0;
+    const double dx = (A.m[0] - B.m[0]) * x + (A.m[1] - B.m[1]) * y + (A.m[2] - B.m[2]);
+    const double dy = (A.m[3] - B.m[3]) * x + (A.m[4] - B.m[4]) * y + (A.m[5] - B.m[5]);
+    worst = std::max(worst, std::hypot(dx, dy));
+  }
+  return worst;
+}
+
+// (H + lambda diag H) d = -g over the parameters idx[0..n) by Cholesky (registration_affine.hip's pivot rule); the other
+// entries of d are 0.  S: the 28 sums.  false: no texture
+bool lm_step(const double* S, double lambda, const int* idx, int n, double* d) {
+  double Hf[6][6], A[6][6], Lc[6][6] = {}, rhs[6], y[6], sol[6];
+  for (int i = 0, q = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++q) Hf[i][j] = Hf[j][i] = S[q];
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) A[i][j] = Hf[idx[i]][idx[j]];
+    A[i][i] = A[i][i] + lambda * A[i][i];
+    rhs[i] = -S[21 + idx[i]];
+  }
+  for (int j = 0; j < n; ++j) {
+    double p = A[j][j];
+    for (int k = 0; k < j; ++k) p -= Lc[j][k] * Lc[j][k];
+    if (!(A[j][j] > 0.0 && p > kPivotRtol * A[j][j])) return false;
+    Lc[j][j] = std::sqrt(p);
+    for (int i = j + 1; i < n; ++i) {
+      double s = A[i][j];
+      for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
+      Lc[i][j] = s / Lc[j][j];
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    double s = rhs[i];
+    for (int k = 0; k < i; ++k) s -= Lc[i][k] * y[k];
+    y[i] = s / Lc[i][i];
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    double s = y[i];
+    for (int k = i + 1; k < n; ++k) s -= Lc[k][i] * sol[k];
+    sol[i] = s / Lc[i][i];
+  }
+  for (int i = 0; i < 6; ++i) d[i] = 0.0;
+  for (int i = 0; i < n; ++i) d[idx[i]] = sol[i];
+  return true;
+}
+
+// G + dL (q - c0) + dt as a map of q
+Map increment(const Map& G, const double* d, double c0x, double c0y) {
+  Map N;
+  N.m[0] = G.m[0] + d[0]; N.m[1] = G.m[1] + d[1]; N.m[2] = G.m[2] + (d[2] - (d[0] * c0x + d[1] * c0y));
+  N.m[3] = G.m[3] + d[3]; N.m[4] = G.m[4] + d[4]; N.m[5] = G.m[5] + (d[5] - (d[3] * c0x + d[4] * c0y));
+  return N;
+}
+
+struct FrameState {
+  Map F, G, Gt, Ft;    // current matrix and its inverse; the trial and its inverse
+  double S[kSums];     // sums at G
+  double lambda = 0.0, e0 = 0.0;
+  int passes = 0, status = 1;
+  bool active = false;
+};
+
+template <typename T>
+void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, int ppt, double* d_part, hipStream_t st) {
+  const Geometry& g = p->geo;
+  dim3 grid(chunks, g.K);
+  if (p->d_dw)
+    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)p->d_dw, g,
+                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, d_tab, ppt, d_part);
+  else
+    hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)nullptr, g,
+                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, d_tab, ppt, d_part);
+}
+
+}  // namespace
+
+}  // namespace srmap
+
+using namespace srmap;
+
+extern "C" void srmap_motion_refinement_options_default(srmap_motion_refinement_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_motion_refinement_options);
+  o->dof = 6;
+  o->max_iterations = 30;
+  o->step_tolerance = 1e-4;
+  o->initial_damping = 1e-3;
+  o->apply = 1;
+  o->initial_affine_2x3 = nullptr;
+}
+
+extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                                          const srmap_motion_refinement_options* options, double* affine_2x3_out,
+                                          double* quality_out, double* normal_equations_out) {
+  if (!p || !x_dev) return SRMAP_EINVAL;
+  srmap_ctx* ctx = p->ctx;
+  srmap_motion_refinement_options opt;
+  srmap_motion_refinement_options_default(&opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_motion_refinement_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
+    opt = *options;
+  }
+  if (opt.dof != 2 && opt.dof != 6) return set_error(ctx, SRMAP_EINVAL, "motion refinement: dof must be 2 or 6 (got %d)", opt.dof);
+  if (opt.max_iterations < 0 || !(opt.step_tolerance >= 0.0) || !(opt.initial_damping >= 0.0) ||
+      !std::isfinite(opt.step_tolerance) || !std::isfinite(opt.initial_damping))
+    return set_error(ctx, SRMAP_EINVAL, "motion refinement: bad options");
+  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
+  const Geometry& g = p->geo;
+  const int K = g.K;
+
+  // starting matrices: the caller's, else the problem's affine motion, else its shifts, else the identity
+  std::vector<double> start((size_t)K * 6, 0.0);
+  for (int k = 0; k < K; ++k) {
+    double* s = start.data() + 6 * (size_t)k;
+    if (opt.initial_affine_2x3) std::copy(opt.initial_affine_2x3 + 6 * (size_t)k, opt.initial_affine_2x3 + 6 * (size_t)(k + 1), s);
+    else if (p->affine) std::copy(p->affine_recs.data() + (size_t)k * kAffineRec + 6, p->affine_recs.data() + (size_t)k * kAffineRec + 12, s);
+    else {
+      s[0] = 1.0; s[4] = 1.0;
+      if (p->has_motion) { s[2] = p->shifts[2 * (size_t)k]; s[5] = p->shifts[2 * (size_t)k + 1]; }
+    }
+  }
+  std::vector<double> recs;
+  int rc = affine_records(ctx, K, start.data(), &recs);  // EINVAL: not finite; EUNSUPPORTED: outside the domain
+  if (rc) return rc;
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  rc = problem_state_read(p, st);
+  if (rc) return rc;
+
+  const int n = g.w * g.h;
+  const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
+  const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
+  double *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr, *h_tab = nullptr, *h_sums = nullptr;
+  auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "motion refinement: %s", what); };
+  if (hipMalloc((void**)&d_part, (size_t)K * chunks * kSums * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d_tab, (size_t)K * kTabRec * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d_sums, (size_t)K * kSums * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h_tab, (size_t)K * kTabRec * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h_sums, (size_t)K * kSums * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    fail(SRMAP_ENOMEM, "allocation failed");
+  }
+
+  std::vector<FrameState> fs(K);
+  for (int k = 0; k < K; ++k) {
+    std::copy(start.data() + 6 * (size_t)k, start.data() + 6 * (size_t)(k + 1), fs[k].F.m);
+    std::copy(recs.data() + (size_t)k * kAffineRec, recs.data() + (size_t)k * kAffineRec + 6, fs[k].G.m);
+    fs[k].Gt = fs[k].G;
+    fs[k].Ft = fs[k].F;
+    fs[k].lambda = opt.initial_damping;
+    fs[k].active = true;
+  }
+
+  // one pass over the trial matrices of every active frame: sums land in h_sums
+  auto pass = [&]() -> bool {
+    for (int k = 0; k < K; ++k) {
+      std::copy(fs[k].Gt.m, fs[k].Gt.m + 6, h_tab + (size_t)k * kTabRec);
+      h_tab[(size_t)k * kTabRec + 6] = fs[k].active ? 1.0 : 0.0;
+      h_tab[(size_t)k * kTabRec + 7] = 0.0;
+    }
+    if (hipMemcpyAsync(d_tab, h_tab, (size_t)K * kTabRec * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, d_tab, chunks, ppt, d_part, st);
+    else launch_sums<double>(p, (const double*)x_dev, d_tab, chunks, ppt, d_part, st);
+    hipLaunchKernelGGL(k_refine_reduce, dim3(K), dim3(64), 0, st, d_part, chunks, d_tab, d_sums);
+    return hipGetLastError() == hipSuccess &&
+           hipMemcpyAsync(h_sums, d_sums, (size_t)K * kSums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+  };
+
+  const double c0x = 0.5 * (double)(g.W - 1), c0y = 0.5 * (double)(g.H - 1);
+  static const int idx6[6] = {0, 1, 2, 3, 4, 5}, idx2[2] = {2, 5};
+  const int* idx = opt.dof == 2 ? idx2 : idx6;
+  // the next trial of frame k from its current sums, or its stop; rejections that need no pass are taken here
+  auto propose = [&](FrameState& f) {
+    while (f.active) {
+      if (f.passes - 1 >= opt.max_iterations) { f.status = 1; f.active = false; break; }
+      double d[6];
+      if (!lm_step(f.S, f.lambda, idx, opt.dof, d)) { f.status = 3; f.active = false; break; }
+      f.Gt = increment(f.G, d, c0x, c0y);
+      f.Ft = inverse(f.Gt);
+      if (opt.dof == 2) { f.Ft.m[0] = f.F.m[0]; f.Ft.m[1] = f.F.m[1]; f.Ft.m[3] = f.F.m[3]; f.Ft.m[4] = f.F.m[4]; }
+      if (all_finite(f.Gt) && all_finite(f.Ft) && deviation(f.Ft) <= kAffineMaxDeviation) break;  // a trial for the next pass
+      f.lambda *= 10.0;
+      if (f.lambda > kMaxDamping) { f.status = 2; f.active = false; }
+    }
+  };
+
+  if (rc == SRMAP_OK) {
+    if (!pass()) fail(SRMAP_EHIP, "pass failed");
+  }
+  if (rc == SRMAP_OK) {
+    for (int k = 0; k < K; ++k) {
+      FrameState& f = fs[k];
+      std::copy(h_sums + (size_t)k * kSums, h_sums + (size_t)(k + 1) * kSums, f.S);
+      f.e0 = f.S[27];
+      f.passes = 1;
+      if (k == 0) { f.active = false; f.passes = 0; f.status = 0; continue; }  // the gauge
+      propose(f);
+    }
+  }
+  while (rc == SRMAP_OK) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) any = any || fs[k].active;
+    if (!any) break;
+    if (!pass()) { fail(SRMAP_EHIP, "pass failed"); break; }
+    for (int k = 0; k < K; ++k) {
+      FrameState& f = fs[k];
+      if (!f.active) continue;
+      const double* S = h_sums + (size_t)k * kSums;
+      ++f.passes;
+      if (S[27] < f.S[27]) {  // accepted: the trial's sums become the current ones
+        const double step = corner_displacement(f.F, f.Ft, g.W, g.H);
+        f.G = f.Gt;
+        f.F = f.Ft;
+        std::copy(S, S + kSums, f.S);
+        f.lambda = std::max(f.lambda / 10.0, kMinDamping);
+        if (step < opt.step_tolerance) { f.status = 0; f.active = false; continue; }
+      } else {
+        f.lambda *= 10.0;
+        if (f.lambda > kMaxDamping) { f.status = 2; f.active = false; continue; }
+      }
+      propose(f);
+    }
+  }
+
+  if (d_part) (void)hipFree(d_part);
+  if (d_tab) (void)hipFree(d_tab);
+  if (d_sums) (void)hipFree(d_sums);
+  if (h_tab) (void)hipHostFree(h_tab);
+  if (h_sums) (void)hipHostFree(h_sums);
+  if (rc) return rc;
+
+  std::vector<double> result((size_t)K * 6);
+  for (int k = 0; k < K; ++k) std::copy(fs[k].F.m, fs[k].F.m + 6, result.data() + 6 * (size_t)k);
+  if (opt.apply) {
+    rc = srmap_problem_set_affine_motion(p, result.data());
+    if (rc) return rc;
+  }
+  for (int k = 0; k < K; ++k) {
+    const FrameState& f = fs[k];
+    if (affine_2x3_out) std::copy(f.F.m, f.F.m + 6, affine_2x3_out + 6 * (size_t)k);
+    if (quality_out) {
+      double* q = quality_out + 4 * (size_t)k;
+      q[0] = f.e0; q[1] = f.S[27]; q[2] = f.passes; q[3] = f.status;
+    }
+    if (normal_equations_out) std::copy(f.S, f.S + kSums, normal_equations_out + (size_t)kSums * k);
+  }
+  return SRMAP_OK;
+}
+
+extern "C" int srmap_refine_motion(srmap_problem* p, const double* x_host, const srmap_motion_refinement_options* options,
+                                   double* affine_2x3_out, double* quality_out, double* normal_equations_out) {
+  if (!p || !x_host) return SRMAP_EINVAL;
+  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
+  if (options && options->struct_size != (int)sizeof(srmap_motion_refinement_options))
+    return set_error(p->ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const size_t n = p->hr_count();
+  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
+  int rc = convert_upload(p, x_host, p->d_x, n, st);
+  if (rc) return rc;
+  return srmap_refine_motion_device(p, p->d_x, st, options, affine_2x3_out, quality_out, normal_equations_out);
+}

@@ -332,6 +332,8 @@ static inline int state_read(srmap_problem* p, hipStream_t st) {
   return SRMAP_OK;
 }
 
+int problem_state_read(srmap_problem* p, hipStream_t st) { return state_read(p, st); }
+
 int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned terms, const void* x, void* g,
                   hipStream_t st) {
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));

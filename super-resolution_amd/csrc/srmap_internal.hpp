@@ -273,6 +273,9 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
 // After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[6]; the host-mapped word
 // host_word when given): re-initialise the granules behind everything in flight and clear both words.
 int recover_reduction_timeout(srmap_problem* p, double* host_word);
+// A reader of the problem's device state (observations, weights) on st that is not an evaluation (motion_refinement.hip):
+// ordered after the last asynchronous state write, and recorded as the stream a later writer drains
+int problem_state_read(srmap_problem* p, hipStream_t st);
 // Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): data weights <- huber(A x - y), enqueued on st
 // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
 int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);

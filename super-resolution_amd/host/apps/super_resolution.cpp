@@ -7,7 +7,8 @@
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
 // reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor are
 // --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
-// --save_motion_path.  Not carried over (out of scope, DESIGN.md
+// --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion).
+// Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
 #include <cstdint>
@@ -46,7 +47,11 @@ int main(int argc, char** argv) {
       "                       [--registration=translational|affine] (estimate the solver's motion from the LR frames, in HR\n"
       "                       pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
       "                       an error together with either motion file)\n"
-      "                       [--save_motion_path=<file>] (the estimate, 'a b tx c d ty' per line; needs --registration)\n"
+      "                       [--save_motion_path=<file>] (the estimate, 'a b tx c d ty' per line; needs --registration or\n"
+      "                       --refine_motion_rounds, and holds the final matrices)\n"
+      "                       [--refine_motion_rounds=0] (after the solve, N times: re-fit the frame matrices to the estimate\n"
+      "                       through the forward model, then solve again from it; 0 = off; works with every motion source)\n"
+      "                       [--refine_motion_dof=6] (6: the full matrices; 2: translations only)\n"
       "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
@@ -88,6 +93,9 @@ int main(int argc, char** argv) {
   // srmap_register_affine) instead of reading it from a file, and write the estimate out
   const std::string registration_name = flags.Str("registration");
   const std::string save_motion_path = flags.Str("save_motion_path");
+  // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
+  const int refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
+  const int refine_motion_dof = flags.Int("refine_motion_dof", 6);
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
@@ -105,8 +113,12 @@ int main(int argc, char** argv) {
                          "(except with --generate_lr_images, where the files generate the frames).\n");
     return 1;
   }
-  if (!save_motion_path.empty() && registration_name.empty()) {
-    std::fprintf(stderr, "ERROR: --save_motion_path needs --registration.\n");
+  if (refine_motion_rounds < 0 || (refine_motion_dof != 2 && refine_motion_dof != 6)) {
+    std::fprintf(stderr, "ERROR: --refine_motion_rounds is >= 0 and --refine_motion_dof is 2 or 6.\n");
+    return 1;
+  }
+  if (!save_motion_path.empty() && registration_name.empty() && refine_motion_rounds == 0) {
+    std::fprintf(stderr, "ERROR: --save_motion_path needs --registration or --refine_motion_rounds.\n");
     return 1;
   }
   // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
@@ -181,6 +193,19 @@ int main(int argc, char** argv) {
 
   // --registration: the solver's model takes its motion from the frames it is about to solve (channel 0), in HR pixels;
   // the generating model above keeps the motion files
+  auto save_motion = [&](const AffineMotionSequence& sequence) -> bool {
+    std::FILE* f = std::fopen(save_motion_path.c_str(), "w");
+    if (!f) {
+      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_motion_path.c_str());
+      return false;
+    }
+    for (int i = 0; i < sequence.GetNumMotions(); ++i) {
+      const AffineMotion& m = sequence[i];
+      std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", m.a, m.b, m.tx, m.c, m.d, m.ty);
+    }
+    std::fclose(f);
+    return true;
+  };
   ImageModelParameters solver_parameters = model_parameters;
   if (!registration_name.empty()) {
     solver_parameters.motion_sequence_path.clear();
@@ -202,18 +227,8 @@ int main(int argc, char** argv) {
     }
     std::printf("Estimated %s motion of %d frames from the low-resolution images.\n", registration_name.c_str(),
                 estimate.GetNumMotions());
-    if (!save_motion_path.empty()) {
-      std::FILE* f = std::fopen(save_motion_path.c_str(), "w");
-      if (!f) {
-        std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_motion_path.c_str());
-        return 1;
-      }
-      for (int i = 0; i < estimate.GetNumMotions(); ++i) {
-        const AffineMotion& m = estimate[i];
-        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", m.a, m.b, m.tx, m.c, m.d, m.ty);
-      }
-      std::fclose(f);
-    }
+    // with refinement rounds the file holds the FINAL matrices: written after the solve
+    if (!save_motion_path.empty() && refine_motion_rounds == 0 && !save_motion(estimate)) return 1;
   }
   const ImageModel solver_model = registration_name.empty() ? image_model : ImageModel::CreateImageModel(solver_parameters);
 
@@ -238,7 +253,17 @@ int main(int argc, char** argv) {
 
   std::printf("Super-resolving from %zu images...\n", low_res_images.size());
   const auto start_time = std::chrono::steady_clock::now();
-  ImageData result = solver.Solve(initial_estimate);
+  ImageData result;
+  if (refine_motion_rounds > 0) {
+    MotionRefinementOptions refinement;
+    refinement.dof = refine_motion_dof;
+    AffineMotionSequence refined;
+    result = solver.SolveJoint(initial_estimate, refine_motion_rounds, refinement, &refined);
+    std::printf("Refined the motion of %d frames in %d rounds.\n", refined.GetNumMotions(), refine_motion_rounds);
+    if (!save_motion_path.empty() && !save_motion(refined)) return 1;
+  } else {
+    result = solver.Solve(initial_estimate);
+  }
   const std::chrono::duration<double> elapsed = std::chrono::steady_clock::now() - start_time;
   std::printf("Done! Finished in %g seconds.\n", elapsed.count());
   if (interpolate_color) {

@@ -7,6 +7,7 @@
 // L-BFGS (minlbfgs, num_lbfgs_hessian_corrections pairs), chosen as in
 // irls_map_solver.cpp:97-113.  Analytical differentiation only: the reference's
 // numeric-difference variant is a test-only alternative outside the path.
+// Not in the reference: RefineMotion / SolveJoint, the joint motion refinement of include/srmap.h (srmap_refine_motion).
 #pragma once
 #include <cmath>
 #include <iostream>
@@ -17,6 +18,7 @@
 
 #include "image/image_data.h"
 #include "image_model/image_model.h"
+#include "motion/affine_motion.h"
 #include "optimization/objective_function.h"
 #include "optimization/regularizer.h"
 #include "util/srmap_host.h"
@@ -69,6 +71,14 @@ struct IRLSMapSolverOptions : public MapSolverOptions {
   // not in the reference: robust data term (default: the reference's least squares)
   DataLoss data_loss = L2_DATA_LOSS;
   double huber_delta = 0.02;  // in the units of the observations; read for HUBER_DATA_LOSS only
+};
+
+// Options of IRLSMapSolver::RefineMotion (srmap_motion_refinement_options, include/srmap.h).  Not in the reference.
+struct MotionRefinementOptions {
+  int dof = 6;                    // 6: the full 2 x 3 matrix; 2: the translation only
+  int max_iterations = 30;        // trial passes per frame after the initial pass
+  double step_tolerance = 1.0e-4; // HR px at the image corners
+  double initial_damping = 1.0e-3;
 };
 
 class Solver {
@@ -204,6 +214,49 @@ class IRLSMapSolver : public MapSolver {
     return result;
   }
   const srmap_solve_report& GetReport() const { return report_; }
+  // Joint motion refinement (srmap_refine_motion; not in the reference): the frame matrices re-fitted to `estimate`
+  // through the forward model, starting from the solver's current motion, and INSTALLED as the solver's motion (later
+  // solves and ComputeAllTerms run the affine model with them).  quality (optional): 4 numbers per frame -- cost at the
+  // start, cost at the result, passes, status.
+  AffineMotionSequence RefineMotion(const ImageData& estimate, const MotionRefinementOptions& options = MotionRefinementOptions(),
+                                    std::vector<double>* quality = nullptr) {
+    if (estimate.GetNumChannels() != GetNumChannels() || estimate.GetImageSize() != GetImageSize())
+      srmap_host::Fail("estimate does not match the HR geometry");
+    srmap_motion_refinement_options o;
+    srmap_motion_refinement_options_default(&o);
+    o.dof = options.dof;
+    o.max_iterations = options.max_iterations;
+    o.step_tolerance = options.step_tolerance;
+    o.initial_damping = options.initial_damping;
+    o.apply = 1;
+    const std::vector<double> x = estimate.ToPlanar();
+    std::vector<double> flat(static_cast<size_t>(GetNumImages()) * 6), q(static_cast<size_t>(GetNumImages()) * 4);
+    srmap_host::Check(srmap_refine_motion(problem_.get(), x.data(), &o, flat.data(), q.data(), nullptr), "srmap_refine_motion");
+    std::vector<AffineMotion> motions;
+    for (int i = 0; i < GetNumImages(); ++i) {
+      const double* m = flat.data() + 6 * static_cast<size_t>(i);
+      motions.push_back(AffineMotion(m[0], m[1], m[2], m[3], m[4], m[5]));
+      if (IsVerbose())
+        std::cout << "  frame " << i << ": cost " << q[4 * i] << " -> " << q[4 * i + 1] << ", " << q[4 * i + 2] << " passes, status "
+                  << q[4 * i + 3] << std::endl;
+    }
+    if (quality) *quality = q;
+    return AffineMotionSequence(motions);
+  }
+  // Solve, then `rounds` times (RefineMotion at the current estimate, Solve warm-started from it).  motion (optional)
+  // receives the final matrices (untouched when rounds == 0).  Not in the reference.
+  ImageData SolveJoint(const ImageData& initial_estimate, const int rounds,
+                       const MotionRefinementOptions& options = MotionRefinementOptions(), AffineMotionSequence* motion = nullptr) {
+    if (rounds < 0) srmap_host::Fail("the number of motion refinement rounds must not be negative");
+    ImageData x = Solve(initial_estimate);
+    for (int r = 0; r < rounds; ++r) {
+      if (IsVerbose()) std::cout << "Motion refinement round " << (r + 1) << " of " << rounds << ":" << std::endl;
+      const AffineMotionSequence refined = RefineMotion(x, options);
+      if (motion) *motion = refined;
+      x = Solve(x);
+    }
+    return x;
+  }
   // The data weights, one planar [C][h][w] block per observation ([K][C][h][w]): after a Huber solve the outlier map (the
   // pixels the solve down-weighted); all ones for a least-squares solve.  Not in the reference.
   std::vector<double> GetDataWeights() const {

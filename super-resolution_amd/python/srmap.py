@@ -52,6 +52,11 @@ class AffineRegistrationOptions(C.Structure):
                 ("step_tolerance", C.c_double), ("max_levels", C.c_int), ("initial_affine_2x3", c_double_p)]
 
 
+class MotionRefinementOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("dof", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double),
+                ("initial_damping", C.c_double), ("apply", C.c_int), ("initial_affine_2x3", c_double_p)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -111,6 +116,9 @@ _SIGNATURES = [
     ("srmap_register_translational_ex", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     ("srmap_affine_registration_options_default", None, [C.c_void_p]),
     ("srmap_register_affine", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p]),
+    ("srmap_motion_refinement_options_default", None, [C.c_void_p]),
+    ("srmap_refine_motion", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_refine_motion_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_channel_pca", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_channel_pca_device", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     ("srmap_synchronize", C.c_int, [C.c_void_p]),
@@ -435,6 +443,47 @@ class Problem:
                                             out.ctypes.data_as(c_double_p), C.byref(rep))
         self.ctx.check(st)
         return out, rep
+
+    def refine_motion(self, x, dof=6, max_iterations=30, step_tolerance=1e-4, initial_damping=1e-3, apply=True, initial=None,
+                      stream=None, struct_size=None):
+        """srmap_refine_motion: re-fit the frame matrices to the HR estimate x through the forward model.  x: a host array
+        [C][H][W], or a device tensor of the problem's dtype (anything with data_ptr(); it is read on `stream`, None = the
+        context's stream, so it must be complete there).  initial: [K][2][3] starting matrices instead of the problem's
+        motion.  Returns (matrices [K][2][3], quality [K][4] = cost at the start, cost at the result, passes, status,
+        normal equations [K][28]).  apply installs the result as set_affine_motion would.  struct_size overrides the
+        options' size field (tests)."""
+        o = MotionRefinementOptions()
+        load().srmap_motion_refinement_options_default(C.byref(o))
+        o.dof, o.max_iterations, o.step_tolerance, o.initial_damping = dof, max_iterations, step_tolerance, initial_damping
+        o.apply = 1 if apply else 0
+        if struct_size is not None:
+            o.struct_size = struct_size
+        if initial is not None:
+            ini, pi = _d(initial)
+            assert ini.size == self.K * 6, (ini.shape, self.K)
+            o.initial_affine_2x3 = pi
+        out, q, ne = np.zeros((self.K, 2, 3)), np.zeros((self.K, 4)), np.zeros((self.K, 28))
+        tail = (C.byref(o), out.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
+        if hasattr(x, "data_ptr"):
+            assert x.numel() == self.C * self.H * self.W
+            self.ctx.check(load().srmap_refine_motion_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
+        else:
+            a, pa = _d(x)
+            assert a.size == self.C * self.H * self.W
+            self.ctx.check(load().srmap_refine_motion(self._h, pa, *tail))
+        return out, q, ne
+
+    def solve_joint(self, x0, options=None, rounds=3, **refine):
+        """Joint estimation: a solve from x0, then `rounds` times (refine_motion at the current x, a solve warm-started from
+        it).  Returns (x, [SolveReport per solve], [(matrices, quality) per refinement]); refine: refine_motion's keywords."""
+        x, rep = self.solve(x0, options)
+        reports, refinements = [rep], []
+        for _ in range(rounds):
+            mats, q, _ = self.refine_motion(x, apply=True, **refine)
+            refinements.append((mats, q))
+            x, rep = self.solve(x, options)
+            reports.append(rep)
+        return x, reports, refinements
 
     def selfcheck(self):
         """Largest relative deviation of the solver's derived beta denominator from the directly summed y.dk (host-paced solves)."""

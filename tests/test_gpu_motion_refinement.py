@@ -1,0 +1,351 @@
+"""The joint motion refinement on the GPU (include/srmap.h: srmap_refine_motion; k_refine_sums and k_refine_reduce of
+csrc/motion_refinement.hip) against its numpy restatement (tests/motion_refinement_restatement.py), against an existing
+kernel (the data cost of srmap_eval) and against itself.
+
+Bars.  One pass: each block of the 28 sums (H, g, E) is held to 100 x the restatement's own sensitivity to the ORDER of its
+sums (by rows, by columns, in reverse), floor 1e-13 of the block's largest magnitude -- the arithmetic is double in both
+dtypes, so an f32 problem has the same bar against the restatement given the f32-rounded inputs.  Whole runs: the same
+status, pass count and accept / reject sequence (tests/test_motion_refinement_cpu.py holds every decision of these inputs to
+a relative cost margin of 1e-9), matrices within 1e-3 px at the corners (section 3.7's whole-run bar)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle as orc
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import affine_restatement as ar  # noqa: E402
+import affine_registration_restatement as rg  # noqa: E402
+import motion_refinement_restatement as mr  # noqa: E402
+import robust_restatement as rr  # noqa: E402
+import test_motion_refinement_cpu as cpu  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+LIBDIR = os.path.join(ROOT, "super-resolution_amd", "lib")
+
+
+@pytest.fixture(scope="module")
+def sr():
+    import srmap
+    return srmap
+
+
+@pytest.fixture(scope="module")
+def ctx(sr):
+    return sr.Context(0)
+
+
+def f32r(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+# ------------------------------------------------------------------------------------------- one pass
+SHAPES = [((5, 7), 2, 0), ((9, 13), 3, 3), ((17, 33), 4, 5), ((70, 129), 2, 3)]  # LR shape, scale, blur
+
+
+def one_pass_case(lr_shape, s, blur, C, K, weights):
+    """Random x, y; frame k's matrix by k % 3: random in-domain, at the 0.25 bound, shifted so that about a third of the
+    samples fall outside the image.  weights: None, "random", or "mask" (0 / 1 with frame 1 all zero)."""
+    h, w = lr_shape
+    H, W = h * s, w * s
+    rng = np.random.default_rng(1000 * h + 10 * w + C + K)
+    x, y = rng.random((C, H, W)), rng.random((K, C, h, w))
+    mats = []
+    for k in range(K):
+        if k % 3 == 0:
+            mats.append(ar.random_matrix(rng, 0.2, shift=2.0))
+        elif k % 3 == 1:
+            mats.append(ar.random_matrix(rng, 0.25, shift=2.0, at_bound=True))
+        else:
+            M = ar.random_matrix(rng, 0.1, shift=1.0)
+            M[0, 2] += W / 3.0
+            mats.append(M)
+    wts = None
+    if weights == "random":
+        wts = 0.1 + rng.random(y.shape)
+    elif weights == "mask":
+        wts = (rng.random(y.shape) < 0.7).astype(np.float64)
+        wts[1] = 0.0
+    return x, y, np.stack(mats), wts
+
+
+def block_bars(x, y, wts, mats, taps, s, k):
+    """(reference sums, bar per entry): 100 x the order sensitivity per block, floor 1e-13 of the block's magnitude."""
+    S = {o: mr.refine_sums(x, y[k], None if wts is None else wts[k], ar.inverse_map(mats[k]), taps, s, o) for o in ("rows", "cols", "reversed")}
+    ref, bar = S["rows"], np.zeros(mr.SUMS)
+    for lo, hi in ((0, 21), (21, 27), (27, 28)):
+        sens = max(np.max(np.abs(S[o][lo:hi] - ref[lo:hi])) for o in ("cols", "reversed"))
+        bar[lo:hi] = max(100 * sens, 1e-13 * np.max(np.abs(ref[lo:hi])))
+    return ref, bar
+
+
+@pytest.mark.parametrize("weights", [None, "random", "mask"])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("K", [2, 5])
+@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda v: "%dx%d_s%d_b%d" % (v[0] + v[1:]))
+def test_one_pass_matches_the_restatement(sr, ctx, shape, C, K, dtype, weights):
+    (h, w), s, blur = shape
+    x, y, mats, wts = one_pass_case((h, w), s, blur, C, K, weights)
+    f32 = dtype == "f32"
+    p = sr.Problem(ctx, w * s, h * s, C, K, s, None, blur, 1.0, sr.F32 if f32 else sr.F64)
+    p.set_observations(y)
+    if wts is not None:
+        p.set_data_weights(wts)
+    got, q, ne = p.refine_motion(x, max_iterations=0, apply=False, initial=mats)
+    assert np.array_equal(got, mats)
+    if f32:
+        x, y, wts = f32r(x), f32r(y), (None if wts is None else f32r(wts))
+    taps = mr.blur_taps(blur, 1.0, f32=f32)
+    worst = 0.0
+    for k in range(K):
+        ref, bar = block_bars(x, y, wts, mats, taps, s, k)
+        dev = np.abs(ne[k] - ref)
+        worst = max(worst, np.max(dev / np.where(bar > 0, bar, 1.0)))
+        assert np.all(dev <= bar), (k, np.argmax(dev - bar), dev, bar)
+        assert q[k, 0] == ne[k, 27] and q[k, 1] == ne[k, 27]
+        assert list(q[k, 2:]) == ([0.0, 0.0] if k == 0 else [1.0, 1.0])
+    if weights == "mask":
+        assert not ne[1].any()
+    print("LR %d x %d scale %d blur %d C %d K %d %s %s: largest deviation / bar %.3f" % (h, w, s, blur, C, K, dtype, weights, worst))
+
+
+# ------------------------------------------------------------------------------------------- whole runs
+def _problem(sr, ctx, x, y, wts, s, blur, dtype=None, shifts=None):
+    K, C, h, w = y.shape
+    p = sr.Problem(ctx, w * s, h * s, C, K, s, shifts, blur[0], blur[1], sr.F64 if dtype is None else dtype)
+    p.set_observations(y)
+    if wts is not None:
+        p.set_data_weights(wts)
+    return p
+
+
+@pytest.mark.parametrize("lr_shape,dof", cpu.WHOLE_RUNS)
+def test_whole_run_matches_the_restatement(sr, ctx, lr_shape, dof):
+    x, y, wts, start, truth, s, blur = cpu.whole_run_input(lr_shape, dof)
+    H, W = x.shape[1:]
+    ref, q_ref, S_ref, dec = mr.refine_motion(x, y, wts, start, mr.blur_taps(*blur), s, with_decisions=True, dof=dof, **cpu.WHOLE_RUN_OPTIONS)
+    p = _problem(sr, ctx, x, y, wts, s, blur)
+    got, q, ne = p.refine_motion(x, dof=dof, apply=False, initial=start, **cpu.WHOLE_RUN_OPTIONS)
+    # the accept / reject sequence: the cost after i trial passes falls exactly where pass i was accepted
+    longest = int(np.max(q_ref[:, 2])) - 1
+    costs = [q[:, 0]]
+    for i in range(1, longest + 1):
+        opts = dict(cpu.WHOLE_RUN_OPTIONS, max_iterations=i)
+        costs.append(p.refine_motion(x, dof=dof, apply=False, initial=start, **opts)[1][:, 1])
+    for k in range(1, len(got)):
+        dev = rg.corner_displacement(got[k], ref[k], W, H)
+        seq = [bool(costs[i][k] < costs[i - 1][k]) for i in range(1, int(q[k, 2]))]
+        print("LR %s dof %d frame %d: GPU - restatement %.2e HR px, cost %.6e / %.6e, passes %d / %d, status %d / %d, decisions %s"
+              % (lr_shape, dof, k, dev, q[k, 1], q_ref[k, 1], q[k, 2], q_ref[k, 2], q[k, 3], q_ref[k, 3],
+                 "".join("A" if a else "r" for a in seq)))
+        assert (q[k, 2], q[k, 3]) == (q_ref[k, 2], q_ref[k, 3])
+        assert seq == [a for a, _, _ in dec[k]]
+        assert dev <= 1e-3
+    assert np.array_equal(got[0], start[0]) and list(q[0, 2:]) == [0.0, 0.0]
+
+
+# ------------------------------------------------------------------------------------------- invariants
+@pytest.fixture(scope="module")
+def run24():
+    return cpu.whole_run_input((24, 32), 6)
+
+
+def test_repeats_are_bit_identical_and_frames_are_independent(sr, ctx, run24):
+    x, y, wts, start, _, s, blur = run24
+    p = _problem(sr, ctx, x, y, wts, s, blur)
+    a = p.refine_motion(x, apply=False, initial=start)
+    b = p.refine_motion(x, apply=False, initial=start)
+    assert all(np.array_equal(u, v) for u, v in zip(a, b))
+    assert np.array_equal(a[0][0], start[0])  # frame 0 is untouched
+    perm = [0, 3, 1, 2]
+    pp = _problem(sr, ctx, x, y[perm], wts[perm], s, blur)
+    c = pp.refine_motion(x, apply=False, initial=start[perm])
+    assert all(np.array_equal(u[perm], v) for u, v in zip(a, c))
+    # a device tensor of the problem's dtype is the same call
+    import torch
+    xd = torch.from_numpy(np.ascontiguousarray(x)).to("cuda")
+    torch.cuda.synchronize()
+    d = p.refine_motion(xd, apply=False, initial=start)
+    assert all(np.array_equal(u, v) for u, v in zip(a, d))
+
+
+def test_apply_installs_the_result_and_no_apply_leaves_the_problem_alone(sr, ctx, run24):
+    x, y, wts, start, _, s, blur = run24
+    p = _problem(sr, ctx, x, y, wts, s, blur)
+    p.set_affine_motion(start)
+    before = p.eval(x)
+    got, _, _ = p.refine_motion(x, apply=False)
+    after = p.eval(x)
+    assert before[0] == after[0] and np.array_equal(before[1], after[1])
+    got1, _, _ = p.refine_motion(x, apply=True)
+    assert np.array_equal(got, got1) and not np.array_equal(got[1:], start[1:])
+    other = _problem(sr, ctx, x, y, wts, s, blur)
+    other.set_affine_motion(got)
+    a, b = p.eval(x), other.eval(x)
+    assert a[0] == b[0] and np.array_equal(a[1], b[1])
+    assert a[0] < before[0]
+
+
+@pytest.mark.parametrize("dof", [2, 6])
+def test_a_translational_problem_starts_from_its_shifts(sr, ctx, dof):
+    x, y, wts, start, truth, s, blur = cpu.whole_run_input((24, 32), 2)
+    shifts = start[:, :, 2]
+    p = _problem(sr, ctx, x, y, wts, s, blur, shifts=shifts)
+    q0 = _problem(sr, ctx, x, y, wts, s, blur)
+    got, q, ne = p.refine_motion(x, dof=dof, apply=False)
+    want = q0.refine_motion(x, dof=dof, apply=False, initial=start)
+    assert np.array_equal(got, want[0]) and np.array_equal(q, want[1]) and np.array_equal(ne, want[2])
+    errs = [rg.corner_displacement(got[k], truth[k], x.shape[2], x.shape[1]) for k in range(1, len(got))]
+    print("dof %d from shifts_xy: corner errors %s HR px, passes %s" % (dof, np.round(errs, 4), q[1:, 2]))
+    assert max(errs) <= cpu.NOISE_BAR
+    if dof == 2:
+        assert np.array_equal(got[:, :, :2], start[:, :, :2])
+    # without shifts and without matrices the start is the identity
+    ident = q0.refine_motion(x, max_iterations=0, apply=False)[0]
+    assert np.array_equal(ident, np.stack([ar.translation(0, 0)] * len(got)))
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+def test_costs_add_up_to_the_data_term_of_eval(sr, ctx, run24, weighted):
+    """An existing kernel as the checker: at f64, s^2 sum_k E_k equals srmap_eval's DATA cost at the same x and matrices."""
+    x, y, wts, start, _, s, blur = run24
+    p = _problem(sr, ctx, x, y, wts if weighted else None, s, blur)
+    p.set_affine_motion(start)
+    _, q, _ = p.refine_motion(x, max_iterations=0, apply=False)
+    cost, _ = p.eval(x, terms=sr.TERM_DATA, want_grad=False)
+    mine = s * s * float(np.sum(q[:, 0]))
+    print("weighted %s: s^2 sum E_k %.15e, eval %.15e, relative difference %.2e" % (weighted, mine, cost, abs(mine - cost) / cost))
+    assert abs(mine - cost) <= 1e-12 * cost
+
+
+def test_error_paths_leave_the_problem_unchanged(sr, ctx, run24):
+    x, y, wts, start, _, s, blur = run24
+    K, C, h, w = y.shape
+    empty = sr.Problem(ctx, w * s, h * s, C, K, s, None, blur[0], blur[1], sr.F64)
+    with pytest.raises(sr.SrmapError) as e:
+        empty.refine_motion(x)
+    assert e.value.status == sr.EINVAL and "no observations" in str(e.value)
+    p = _problem(sr, ctx, x, y, wts, s, blur)
+    p.set_affine_motion(start)
+    before = p.eval(x)
+    nan, inf, far = start.copy(), start.copy(), start.copy()
+    nan[2, 0, 1], inf[1, 1, 2] = np.nan, np.inf
+    far[3] = np.array([[1.2, 0.1, 0.0], [0.0, 1.0, 0.0]])
+    cases = [(dict(struct_size=8), sr.EINVAL), (dict(dof=3), sr.EINVAL), (dict(dof=0), sr.EINVAL),
+             (dict(max_iterations=-1), sr.EINVAL), (dict(step_tolerance=-1e-4), sr.EINVAL), (dict(initial_damping=-1.0), sr.EINVAL),
+             (dict(step_tolerance=np.nan), sr.EINVAL), (dict(initial=nan), sr.EINVAL), (dict(initial=inf), sr.EINVAL),
+             (dict(initial=far), sr.EUNSUPPORTED)]
+    for kw, status in cases:
+        with pytest.raises(sr.SrmapError) as e:
+            p.refine_motion(x, **kw)
+        assert e.value.status == status, kw
+        after = p.eval(x)
+        assert before[0] == after[0] and np.array_equal(before[1], after[1]), kw
+    # frame 0's starting matrix is validated like the others (it is returned as it was given)
+    assert np.array_equal(p.refine_motion(x, max_iterations=0, apply=False)[0], start)
+
+
+# ------------------------------------------------------------------------------------------- end to end
+@pytest.fixture(scope="module")
+def table():
+    return ar.table_inputs()
+
+
+@pytest.mark.parametrize("name", ["0.5deg", "2deg"])
+def test_frames_to_matrices_to_joint_solve(sr, ctx, table, name):
+    """register_affine -> solve_joint(rounds = 3): the rounds / iterations / evaluations of every solve as the CPU test pins
+    them; the PSNR after round 3 within max(0.01 dB, 10 x the restatement's own sensitivity) of the pinned figure."""
+    T = table
+    truth, _, y = T["inputs"][name]
+    x0 = rr.bilinear(y[0], T["s"])
+    p = sr.Problem(ctx, T["W"], T["H"], T["C"], T["K"], T["s"], T["shifts"], T["blur"][0], T["blur"][1], sr.F64)
+    p.set_affine_motion(ctx.register_affine(y[:, 0], hr_scale=T["s"]))
+    p.set_observations(y)
+    p.add_regularizer(*T["reg"])
+    x, reports, refinements = p.solve_joint(x0, rounds=3)
+    labels = ("unrefined", "round1", "round2", "round3")
+    counts = [(r.irls_rounds, r.cg_iterations, r.evaluations) for r in reports]
+    ps = orc.psnr(T["gt"], x)
+    for r, (mats, q) in enumerate(refinements):
+        worst = max(rg.corner_displacement(mats[k], truth[k], T["W"], T["H"]) for k in range(1, T["K"]))
+        print("%s round %d: largest corner error %.3f HR px (pinned %.3f), passes %s, status %s, cost before %s after %s"
+              % (name, r + 1, worst, cpu.TABLE[name]["corner"][r], q[1:, 2].astype(int), q[1:, 3].astype(int),
+                 np.round(q[1:, 0], 5), np.round(q[1:, 1], 5)))
+        assert np.all(q[:, 1] <= q[:, 0])
+    print("%s: GPU solves %s, pinned %s; GPU round-3 PSNR %.3f dB, pinned %.3f dB, sensitivity %.4f dB"
+          % (name, counts, [cpu.TABLE[name][l][1] for l in labels], ps, cpu.TABLE[name]["round3"][0], cpu.ROUND_3_SENSITIVITY))
+    assert counts == [cpu.TABLE[name][l][1] for l in labels]
+    assert abs(ps - cpu.TABLE[name]["round3"][0]) <= max(0.01, 10 * cpu.ROUND_3_SENSITIVITY)
+
+
+def test_cli_refinement_flags(table, tmp_path):
+    """super_resolution --generate_lr_images --affine_motion_path=<2 degrees> --registration=affine: with
+    --refine_motion_rounds=3 the run ends above the same run with 0 rounds; --save_motion_path holds the FINAL matrices, which
+    load again as --affine_motion_path; the flags parse with the other motion sources and refuse bad values."""
+    from test_gpu_apps import _write_envi
+    srbin = os.path.join(LIBDIR, "super_resolution")
+    assert os.path.exists(srbin), "build() makes the tools"
+    T = table
+    Cn, H, W, s, K = T["C"], T["H"], T["W"], T["s"], T["K"]
+    mats = T["inputs"]["2deg"][0]
+    gt = T["gt"].astype(np.float32).astype(np.float64)
+    gt_cfg = _write_envi(str(tmp_path / "gt"), gt)
+    affine = tmp_path / "affine.txt"
+    affine.write_text("".join(" ".join(repr(float(v)) for v in m.ravel()) + "\n" for m in mats))
+    shifts = tmp_path / "shifts.txt"
+    shifts.write_text("".join("%r %r\n" % (float(m[0, 2]), float(m[1, 2])) for m in mats))
+    base = [srbin, "--data_path=" + gt_cfg, "--generate_lr_images", "--number_of_frames=%d" % K, "--noise_sigma=2.55",
+            "--upsampling_scale=%d" % s, "--blur_radius=3", "--blur_sigma=1.0", "--regularizer=btv", "--btv_scale_range=2",
+            "--regularization_parameter=0.005"]
+
+    def run(tag, *flags):
+        res = str(tmp_path / ("result_" + tag))
+        o = subprocess.run(base + ["--result_path=" + res] + list(flags), capture_output=True, text=True, timeout=600)
+        print(o.stdout, o.stderr)
+        assert o.returncode == 0
+        return orc.psnr(gt, np.fromfile(res, dtype="<f4").reshape(Cn, H, W).astype(np.float64)), o.stdout
+
+    saved0, saved3 = tmp_path / "rounds0.txt", tmp_path / "rounds3.txt"
+    ps0, _ = run("rounds0", "--affine_motion_path=" + str(affine), "--registration=affine", "--save_motion_path=" + str(saved0))
+    ps3, out3 = run("rounds3", "--affine_motion_path=" + str(affine), "--registration=affine", "--refine_motion_rounds=3",
+                    "--save_motion_path=" + str(saved3), "--verbose")
+    print("CLI --registration=affine: %.3f dB with 0 refinement rounds, %.3f dB with 3" % (ps0, ps3))
+    assert ps3 > ps0
+    assert out3.count("Motion refinement round") == 3 and "passes, status" in out3
+
+    def load(path):
+        return np.array([[float(v) for v in line.split()] for line in path.read_text().splitlines()]).reshape(K, 2, 3)
+
+    est0, est3 = load(saved0), load(saved3)
+    e0 = max(rg.corner_displacement(est0[k], mats[k], W, H) for k in range(1, K))
+    e3 = max(rg.corner_displacement(est3[k], mats[k], W, H) for k in range(1, K))
+    print("saved matrices: largest corner error %.3f HR px registered, %.3f HR px after 3 rounds" % (e0, e3))
+    assert np.array_equal(est3[0], est0[0]) and e3 < e0
+    # the saved file round-trips: it drives a run as --affine_motion_path, there refined once more, translations only
+    again = tmp_path / "again.txt"
+    run("again", "--affine_motion_path=" + str(saved3), "--refine_motion_rounds=1", "--refine_motion_dof=2",
+        "--save_motion_path=" + str(again), "--optimization_iterations=2", "--solver_iterations=5")
+    assert np.array_equal(load(again)[:, :, :2], est3[:, :, :2])
+    # the other motion sources
+    run("shifts", "--motion_sequence_path=" + str(shifts), "--refine_motion_rounds=1", "--optimization_iterations=2", "--solver_iterations=5")
+    run("translational", "--motion_sequence_path=" + str(shifts), "--registration=translational", "--refine_motion_rounds=1",
+        "--optimization_iterations=2", "--solver_iterations=5")
+    for flags, word in ((["--refine_motion_rounds=-1"], "refine_motion_rounds"), (["--refine_motion_dof=3"], "refine_motion_dof"),
+                        (["--save_motion_path=" + str(again)], "needs --registration")):
+        o = subprocess.run([srbin, "--data_path=" + str(tmp_path)] + flags, capture_output=True, text=True, timeout=120)
+        assert o.returncode == 1 and word in o.stderr, (flags, o.stderr)
+
+
+def test_host_facade_returns_what_the_c_call_returns():
+    exe = os.path.join(LIBDIR, "motion_refinement_test")
+    assert os.path.exists(exe), "build() makes the facade test binary"
+    o = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(o.stdout, o.stderr)
+    assert o.returncode == 0 and "MOTION REFINEMENT FACADE TESTS PASSED" in o.stdout
