@@ -17,21 +17,17 @@
 #include <algorithm>
 #include <cmath>
 
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_a(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // Sum over a 256-thread block; result valid in thread 0 (k_forward_direct's order: the partials mean the same).
 __device__ __forceinline__ double block_sum_256_a(double v, double* smem4) {
-  v = wave_sum_a(v);
+  v = wave_sum(v);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) smem4[wid] = v;
   __syncthreads();
@@ -40,16 +36,7 @@ __device__ __forceinline__ double block_sum_256_a(double v, double* smem4) {
   return r;
 }
 
-// m0 * x + (m1 * y + m2) with every operation rounded on its own: no contraction into fused multiply-adds, so that a host
-// restatement in plain double arithmetic (tests/affine_restatement.py) forms bit-identical coordinates and weights --
-// one ulp of a coordinate at 260 px is 6e-14 of a weight, which a gradient element of size 60 shows as 3e-12
-__device__ __forceinline__ double affine_coord(double m0, double m1, double m2, double x, double y) {
-#pragma clang fp contract(off)
-  const double t = m1 * y + m2;
-  return m0 * x + t;
-}
-
-// s = F^-1(q) for the warped-image pixel q = (qx, qy): THE expression of both kernels
+// s = F^-1(q) for the warped-image pixel q = (qx, qy): THE expression of both kernels (affine_coord, motion_fit_dev.hpp)
 __device__ __forceinline__ void affine_source(const double* __restrict__ m, int qx, int qy, double* sx, double* sy) {
   *sx = affine_coord(m[0], m[1], m[2], (double)qx, (double)qy);
   *sy = affine_coord(m[3], m[4], m[5], (double)qx, (double)qy);
@@ -243,21 +230,20 @@ int affine_records(srmap_ctx* ctx, int K, const double* a23, std::vector<double>
       return set_error(ctx, SRMAP_EINVAL, "affine motion: entry %d of frame %d is not finite", i % 6, i / 6);
   recs->assign((size_t)K * kAffineRec, 0.0);
   for (int k = 0; k < K; ++k) {
-    const double a = a23[6 * k], b = a23[6 * k + 1], tx = a23[6 * k + 2];
-    const double c = a23[6 * k + 3], d = a23[6 * k + 4], ty = a23[6 * k + 5];
-    const double dev = std::max(std::fabs(a - 1.0) + std::fabs(b), std::fabs(c) + std::fabs(d - 1.0));
+    AffineMap F;
+    std::copy(a23 + 6 * k, a23 + 6 * (k + 1), F.m);
+    const double a = F.m[0], b = F.m[1], tx = F.m[2], c = F.m[3], d = F.m[4], ty = F.m[5];
+    const double dev = deviation(F);
     if (!(dev <= kAffineMaxDeviation))
       return set_error(ctx, SRMAP_EUNSUPPORTED,
                        "affine motion of frame %d: max(|a-1|+|b|, |c|+|d-1|) = %g exceeds %g (the transpose gathers 3 x 3 candidates)",
                        k, dev, kAffineMaxDeviation);
     if (!(std::fabs(tx) < 1.0e9) || !(std::fabs(ty) < 1.0e9))
       return set_error(ctx, SRMAP_EUNSUPPORTED, "affine motion of frame %d: translation (%g, %g) too large", k, tx, ty);
-    const double det = a * d - b * c;  // >= 0.75^2 - 0.25^2 inside the domain
-    const double ia = d / det, ib = -b / det, ic = -c / det, id = a / det;
     double* m = recs->data() + (size_t)k * kAffineRec;
-    m[0] = ia; m[1] = ib; m[2] = -(ia * tx + ib * ty);
-    m[3] = ic; m[4] = id; m[5] = -(ic * tx + id * ty);
-    m[6] = a; m[7] = b; m[8] = tx; m[9] = c; m[10] = d; m[11] = ty;
+    const AffineMap G = inverse(F);
+    std::copy(G.m, G.m + 6, m);
+    std::copy(F.m, F.m + 6, m + 6);
     // candidate radii, widened so that rounding of F(p) can drop no candidate (2 * (1.25 + 1e-9) < 3: still three integers)
     m[12] = std::fabs(a) + std::fabs(b) + 1.0e-9;
     m[13] = std::fabs(c) + std::fabs(d) + 1.0e-9;

@@ -7,15 +7,20 @@
 //             J_i = sum over k_forward_affine's blur taps of blur * g * {q_x - c0x, q_y - c0y, 1}, g the exact derivative of
 //             the four-tap sample in s_x (i = 0..2) or s_y (i = 3..5), from the four tap values the sample itself uses;
 //             28 f64 sums per workgroup (21 of H = sum w J J^T, upper triangle row-major; 6 of g = sum w J r; E), folded by a
-//             wave shuffle and LDS in a fixed order, no atomics; k_refine_reduce adds the chunk records in index order;
-//   pacing    per pass one upload of the frame table, one copy of K x 28 doubles, one stream wait (section 3.7's);
-//   LM        on the host in double, per frame, in lockstep: (H + lambda diag H) d = -g by the 6 x 6 Cholesky of
-//             registration_affine.hip (dof = 2: the 2 x 2 sub-system of (tx, ty)), G' = G + dL (q - c0) + dt.
-// Everything after the loads is double in both dtypes.  Sample positions are kernels_affine.hip's (affine_coord).
+//             wave shuffle and LDS in a fixed order, no atomics (fold_sums_256); k_fit_reduce adds the chunk records in
+//             index order;
+//   pacing    per pass one upload of the frame table, one copy of K x 28 doubles, one stream wait (section 3.7's; FitPass,
+//             motion_fit.hip);
+//   LM        on the host in double, per frame, in lockstep: (H + lambda diag H) d = -g by the Cholesky of affine_map.hpp
+//             (dof = 2: the 2 x 2 sub-system of (tx, ty)), G' = G + dL (q - c0) + dt.
+// Everything after the loads is double in both dtypes.  Sample positions are kernels_affine.hip's (affine_coord of
+// motion_fit_dev.hpp).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -23,27 +28,13 @@ namespace srmap {
 namespace {
 
 constexpr int kSums = 28;       // 21 of H, 6 of g, E
-constexpr int kTabRec = 8;      // G = [ia ib itx ic id ity], active, pad
 constexpr int kMaxChunks = 256;
-constexpr double kPivotRtol = 1e-12;
 constexpr double kMinDamping = 1e-9, kMaxDamping = 1e6;
-
-__device__ __forceinline__ double wsum_r(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// kernels_affine.hip's affine_coord: m0 x + (m1 y + m2), no contraction
-__device__ __forceinline__ double affine_coord_r(double m0, double m1, double m2, double x, double y) {
-#pragma clang fp contract(off)
-  const double t = m1 * y + m2;
-  return m0 * x + t;
-}
 
 // Sums of one pass for every active frame: grid = (chunks of LR pixels, frames), 256 threads; a workgroup covers the LR
 // pixels [chunk * 256 * ppt, (chunk + 1) * 256 * ppt) of its frame, thread t the pixels t, t + 256, ...
-// table[k][kTabRec] is indexed by the frame alone (scalar loads).  partial[(k * chunks + chunk)][28].
+// table[k][kFitTabRec] (G = [ia ib itx ic id ity], active, pad) is indexed by the frame alone (scalar loads).
+// partial[(k * chunks + chunk)][28].
 template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, const T* __restrict__ y,
                                                      const T* __restrict__ dw, Geometry g, const T* __restrict__ blur,
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
                                                      double* __restrict__ partial) {
   __shared__ double red[kSums][4];
   const int k = blockIdx.y;
-  const double* __restrict__ m = table + (size_t)k * kTabRec;  // uniform: scalar loads
+  const double* __restrict__ m = table + (size_t)k * kFitTabRec;  // uniform: scalar loads
   if (m[6] == 0.0) return;                                     // stopped frame: uniform
   const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
   const int n = g.w * g.h;
@@ -75,8 +66,8 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
         for (int e = 0; e < g.b; ++e) {
           const int cc = C0 + e - g.hb;
           if (cc < 0 || cc >= g.W) continue;
-          const double sx = affine_coord_r(m0, m1, m2, (double)cc, (double)rr);
-          const double sy = affine_coord_r(m3, m4, m5, (double)cc, (double)rr);
+          const double sx = affine_coord(m0, m1, m2, (double)cc, (double)rr);
+          const double sy = affine_coord(m3, m4, m5, (double)cc, (double)rr);
           if (!(sx > -1.0 && sx < (double)g.W && sy > -1.0 && sy < (double)g.H)) continue;  // no tap inside (NaN included)
           const double x0d = __builtin_floor(sx), y0d = __builtin_floor(sy);
           const double fx = sx - x0d, fy = sy - y0d;
@@ -110,64 +101,14 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
       acc[27] += (wv * r) * r;
     }
   }
-  const int lane = threadIdx.x & 63, wvi = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < kSums; ++q) {
-    const double s = wsum_r(acc[q]);
-    if (lane == 0) red[q][wvi] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    const int q = threadIdx.x;
-    partial[((size_t)k * gridDim.x + blockIdx.x) * kSums + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-  }
-}
-
-// sums[k][28] = the chunk records of frame k added in index order.  grid = frames, 64 threads.
-__global__ __launch_bounds__(64) void k_refine_reduce(const double* __restrict__ partial, int chunks,
-                                                      const double* __restrict__ table, double* __restrict__ sums) {
-  const int k = blockIdx.x, q = threadIdx.x;
-  if (table[(size_t)k * kTabRec + 6] == 0.0 || q >= kSums) return;
-  double s = 0.0;
-  for (int c = 0; c < chunks; ++c) s += partial[((size_t)k * chunks + c) * kSums + q];
-  sums[(size_t)k * kSums + q] = s;
+  fold_sums_256(acc, red, partial + ((size_t)k * gridDim.x + blockIdx.x) * kSums);
 }
 
 // ---- host side ----
-struct Map { double m[6]; };
-
-double deviation(const Map& F) {
-  return std::max(std::fabs(F.m[0] - 1.0) + std::fabs(F.m[1]), std::fabs(F.m[3]) + std::fabs(F.m[4] - 1.0));
-}
-bool all_finite(const Map& F) {
-  for (double v : F.m) if (!std::isfinite(v)) return false;
-  return true;
-}
-// the inverse as affine_records forms it
-Map inverse(const Map& F) {
-  const double a = F.m[0], b = F.m[1], tx = F.m[2], c = F.m[3], d = F.m[4], ty = F.m[5];
-  const double det = a * d - b * c;
-  const double ia = d / det, ib = -b / det, ic = -c / det, id = a / det;
-  Map G;
-  G.m[0] = ia; G.m[1] = ib; G.m[2] = -(ia * tx + ib * ty);
-  G.m[3] = ic; G.m[4] = id; G.m[5] = -(ic * tx + id * ty);
-  return G;
-}
-double corner_displacement(const Map& A, const Map& B, int w, int h) {
-  double worst = 0.0;
-  for (int i = 0; i < 4; ++i) {
-    const double x = (i & 1) ? w - 1.0 : 0.0, y = (i & 2) ? h - 1.0 : 0.0;
-    const double dx = (A.m[0] - B.m[0]) * x + (A.m[1] - B.m[1]) * y + (A.m[2] - B.m[2]);
-    const double dy = (A.m[3] - B.m[3]) * x + (A.m[4] - B.m[4]) * y + (A.m[5] - B.m[5]);
-    worst = std::max(worst, std::hypot(dx, dy));
-  }
-  return worst;
-}
-
-// (H + lambda diag H) d = -g over the parameters idx[0..n) by Cholesky (registration_affine.hip's pivot rule); the other
-// entries of d are 0.  S: the 28 sums.  false: no texture
+// (H + lambda diag H) d = -g over the parameters idx[0..n) by Cholesky; the other entries of d are 0.  S: the 28 sums.
+// false: no texture
 bool lm_step(const double* S, double lambda, const int* idx, int n, double* d) {
-  double Hf[6][6], A[6][6], Lc[6][6] = {}, rhs[6], y[6], sol[6];
+  double Hf[6][6], A[6][6], rhs[6], sol[6];
   for (int i = 0, q = 0; i < 6; ++i)
     for (int j = i; j < 6; ++j, ++q) Hf[i][j] = Hf[j][i] = S[q];
   for (int i = 0; i < n; ++i) {
@@ -175,42 +116,14 @@ bool lm_step(const double* S, double lambda, const int* idx, int n, double* d) {
     A[i][i] = A[i][i] + lambda * A[i][i];
     rhs[i] = -S[21 + idx[i]];
   }
-  for (int j = 0; j < n; ++j) {
-    double p = A[j][j];
-    for (int k = 0; k < j; ++k) p -= Lc[j][k] * Lc[j][k];
-    if (!(A[j][j] > 0.0 && p > kPivotRtol * A[j][j])) return false;
-    Lc[j][j] = std::sqrt(p);
-    for (int i = j + 1; i < n; ++i) {
-      double s = A[i][j];
-      for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
-      Lc[i][j] = s / Lc[j][j];
-    }
-  }
-  for (int i = 0; i < n; ++i) {
-    double s = rhs[i];
-    for (int k = 0; k < i; ++k) s -= Lc[i][k] * y[k];
-    y[i] = s / Lc[i][i];
-  }
-  for (int i = n - 1; i >= 0; --i) {
-    double s = y[i];
-    for (int k = i + 1; k < n; ++k) s -= Lc[k][i] * sol[k];
-    sol[i] = s / Lc[i][i];
-  }
+  if (!cholesky_solve(A, rhs, n, sol)) return false;
   for (int i = 0; i < 6; ++i) d[i] = 0.0;
   for (int i = 0; i < n; ++i) d[idx[i]] = sol[i];
   return true;
 }
 
-// G + dL (q - c0) + dt as a map of q
-Map increment(const Map& G, const double* d, double c0x, double c0y) {
-  Map N;
-  N.m[0] = G.m[0] + d[0]; N.m[1] = G.m[1] + d[1]; N.m[2] = G.m[2] + (d[2] - (d[0] * c0x + d[1] * c0y));
-  N.m[3] = G.m[3] + d[3]; N.m[4] = G.m[4] + d[4]; N.m[5] = G.m[5] + (d[5] - (d[3] * c0x + d[4] * c0y));
-  return N;
-}
-
 struct FrameState {
-  Map F, G, Gt, Ft;    // current matrix and its inverse; the trial and its inverse
+  AffineMap F, G, Gt, Ft;  // current matrix and its inverse; the trial and its inverse
   double S[kSums];     // sums at G
   double lambda = 0.0, e0 = 0.0;
   int passes = 0, status = 1;
@@ -289,13 +202,9 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   const int n = g.w * g.h;
   const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
   const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
-  double *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr, *h_tab = nullptr, *h_sums = nullptr;
+  FitPass fit;
   auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "motion refinement: %s", what); };
-  if (hipMalloc((void**)&d_part, (size_t)K * chunks * kSums * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_tab, (size_t)K * kTabRec * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_sums, (size_t)K * kSums * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&h_tab, (size_t)K * kTabRec * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&h_sums, (size_t)K * kSums * sizeof(double)) != hipSuccess) {
+  if (!fit.alloc(K, kSums, (size_t)K * chunks * kSums)) {
     (void)hipGetLastError();
     fail(SRMAP_ENOMEM, "allocation failed");
   }
@@ -310,20 +219,13 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
     fs[k].active = true;
   }
 
-  // one pass over the trial matrices of every active frame: sums land in h_sums
+  // one pass over the trial matrices of every active frame: sums land in fit.sums(k)
   auto pass = [&]() -> bool {
-    for (int k = 0; k < K; ++k) {
-      std::copy(fs[k].Gt.m, fs[k].Gt.m + 6, h_tab + (size_t)k * kTabRec);
-      h_tab[(size_t)k * kTabRec + 6] = fs[k].active ? 1.0 : 0.0;
-      h_tab[(size_t)k * kTabRec + 7] = 0.0;
-    }
-    if (hipMemcpyAsync(d_tab, h_tab, (size_t)K * kTabRec * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
-    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, d_tab, chunks, ppt, d_part, st);
-    else launch_sums<double>(p, (const double*)x_dev, d_tab, chunks, ppt, d_part, st);
-    hipLaunchKernelGGL(k_refine_reduce, dim3(K), dim3(64), 0, st, d_part, chunks, d_tab, d_sums);
-    return hipGetLastError() == hipSuccess &&
-           hipMemcpyAsync(h_sums, d_sums, (size_t)K * kSums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-           hipStreamSynchronize(st) == hipSuccess;
+    for (int k = 0; k < K; ++k) fit.set(k, fs[k].Gt, fs[k].active);
+    if (!fit.upload(st)) return false;
+    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, fit.d_tab, chunks, ppt, fit.d_part, st);
+    else launch_sums<double>(p, (const double*)x_dev, fit.d_tab, chunks, ppt, fit.d_part, st);
+    return fit.reduce_and_fetch(chunks, st);
   };
 
   const double c0x = 0.5 * (double)(g.W - 1), c0y = 0.5 * (double)(g.H - 1);
@@ -350,7 +252,7 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   if (rc == SRMAP_OK) {
     for (int k = 0; k < K; ++k) {
       FrameState& f = fs[k];
-      std::copy(h_sums + (size_t)k * kSums, h_sums + (size_t)(k + 1) * kSums, f.S);
+      std::copy(fit.sums(k), fit.sums(k) + kSums, f.S);
       f.e0 = f.S[27];
       f.passes = 1;
       if (k == 0) { f.active = false; f.passes = 0; f.status = 0; continue; }  // the gauge
@@ -365,7 +267,7 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
     for (int k = 0; k < K; ++k) {
       FrameState& f = fs[k];
       if (!f.active) continue;
-      const double* S = h_sums + (size_t)k * kSums;
+      const double* S = fit.sums(k);
       ++f.passes;
       if (S[27] < f.S[27]) {  // accepted: the trial's sums become the current ones
         const double step = corner_displacement(f.F, f.Ft, g.W, g.H);
@@ -382,11 +284,6 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
     }
   }
 
-  if (d_part) (void)hipFree(d_part);
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_sums) (void)hipFree(d_sums);
-  if (h_tab) (void)hipHostFree(h_tab);
-  if (h_sums) (void)hipHostFree(h_sums);
   if (rc) return rc;
 
   std::vector<double> result((size_t)K * 6);

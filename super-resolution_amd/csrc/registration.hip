@@ -6,7 +6,8 @@
 // estimateRigidTransform, :41-157), none of which is part of this path or available here; its own test
 // (test/test_registration.cpp) fixes the CONTRACT: shifts applied with MotionModule are recovered to 0.01 px.
 // This is a dense, GPU-native estimator for the same contract:
-//   1. box pyramid of every frame (k_down2) down to <= 64 px (shifts up to a quarter of the frame are searched);
+//   1. box pyramid of every frame (k_down2_stack, motion_fit.hip) down to <= 64 px (shifts up to a quarter of the
+//      frame are searched);
 //   2. integer shift, coarse to fine: mean squared difference over the overlap for the (2R+1)^2 candidates around
 //      twice the coarser level's answer (k_ssd_candidates: one workgroup per candidate x row chunk, fixed-order
 //      reduction) -- the zero border warpAffine leaves in a shifted frame is inside the overlap of the TRUE shift
@@ -18,27 +19,13 @@
 #include <cmath>
 #include <vector>
 
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
 
 namespace {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// dst[h2][w2] = mean of the 2 x 2 blocks of src[h][w] (w2 = w / 2, h2 = h / 2)
-__global__ __launch_bounds__(256) void k_down2(const double* __restrict__ src, double* __restrict__ dst, int w, int w2,
-                                               int h2) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= w2 * h2) return;
-  const int r = i / w2, c = i - r * w2;
-  const double* s = src + (size_t)(2 * r) * w + 2 * c;
-  dst[i] = 0.25 * ((s[0] + s[1]) + (s[w] + s[w + 1]));
-}
 
 // partial[(cand * gridDim.y + chunk) * 2 + {0, 1}] = sum of (b(p + u) - a(p))^2 and the pixel count over the rows of
 // this chunk, u = (ux0 + cand % n1, uy0 + cand / n1).
@@ -59,7 +46,7 @@ __global__ __launch_bounds__(256) void k_ssd_candidates(const double* __restrict
       n += 1.0;
     }
   }
-  s = wsum(s); n = wsum(n);
+  s = wave_sum(s); n = wave_sum(n);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) { red[0][wv] = s; red[1][wv] = n; }
   __syncthreads();
@@ -91,17 +78,7 @@ __global__ __launch_bounds__(256) void k_lk_sums(const double* __restrict__ a, c
       acc[0] += gx * gx; acc[1] += gx * gy; acc[2] += gy * gy; acc[3] += gx * e; acc[4] += gy * e; acc[5] += e * e;
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < 6; ++q) {
-    const double s = wsum(acc[q]);
-    if (lane == 0) red[q][wv] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int q = threadIdx.x;
-    partial[(size_t)blockIdx.x * 6 + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-  }
+  fold_sums_256(acc, red, partial + (size_t)blockIdx.x * 6);
 }
 
 }  // namespace
@@ -157,10 +134,7 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
   for (int l = 1; l < L; ++l) off[l] = off[l - 1] + (size_t)lw[l - 1] * lh[l - 1];
   auto build = [&](double* base, const double* host) -> bool {
     if (hipMemcpyAsync(base, host, npx * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
-    for (int l = 1; l < L; ++l) {
-      const int n = lw[l] * lh[l];
-      hipLaunchKernelGGL(k_down2, dim3((n + 255) / 256), dim3(256), 0, st, base + off[l - 1], base + off[l], lw[l - 1], lw[l], lh[l]);
-    }
+    for (int l = 1; l < L; ++l) launch_down2_stack(base + off[l - 1], base + off[l], lw[l - 1], lh[l - 1], 1, st);
     return hipGetLastError() == hipSuccess;
   };
   if (rc == SRMAP_OK && !build(d_a, images_host)) fail(SRMAP_EHIP, "pyramid of the reference frame failed");
@@ -189,14 +163,7 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
         if (bi < 0 || m < best) { best = m; bi = cnd; }
       }
       if (bi < 0) { fail(SRMAP_EINVAL, "Could not determine motion shift between images."); break; }  // registration.cpp:193-194
-      if (l == L - 1 && quality_out) {
-        double runner = -1.0;
-        for (int cnd = 0; cnd < ncand; ++cnd) {
-          if (msd[cnd] < 0 || std::max(std::abs(cnd % n1 - bi % n1), std::abs(cnd / n1 - bi / n1)) < 2) continue;
-          if (runner < 0 || msd[cnd] < runner) runner = msd[cnd];
-        }
-        quality_out[2 * i] = runner > 0 ? 1.0 - best / runner : 0.0;
-      }
+      if (l == L - 1 && quality_out) quality_out[2 * i] = search_separation(msd.data(), n1, bi);
       sx = sx - R + bi % n1;
       sy = sy - R + bi / n1;
     }

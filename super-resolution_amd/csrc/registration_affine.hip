@@ -3,19 +3,22 @@
 // For every frame k >= 1: F_k(p) = L_k p + t_k with I_k(F_k(p)) ~= I_0(p), the convention of the affine motion model
 // (kernels_affine.hip) and of MotionShift.  No reference counterpart (registration.cpp keeps the translation of a
 // feature-based fit); the checker is tests/affine_registration_restatement.py.
-//   1. box pyramid of the whole stack, built once (k_down2_stack), halved while the shorter side is >= 64;
+//   1. box pyramid of the whole stack, built once (k_down2_stack, motion_fit.hip), halved while the shorter side is >= 64;
 //   2. seed at the coarsest level: integer search over [-R, R]^2, mean squared difference over the FIXED template window
 //      [R, w-R) x [R, h-R) (k_ssd_window).  The overlap window of the translational search moves with the candidate and
 //      lets the zero wedges of a rotated frame vote for far-away shifts; a fixed window compares every candidate on the
 //      same pixels;
 //   3. inverse-compositional Gauss-Newton, coarse to fine: per pass ONE launch of k_affine_gn_sums for all frames
-//      (26 sums per workgroup, fixed-order reduction), one k_affine_gn_reduce, one 26 x (K-1) double copy and one stream
-//      wait; the 6 x 6 Cholesky solve and the composition F <- F o W^-1 run on the host in double.
-// Sample positions are computed as kernels_affine.hip computes them (affine_coord: every operation rounded on its own).
+//      (26 sums per workgroup, fixed-order reduction), one k_fit_reduce, one 26 x (K-1) double copy and one stream wait
+//      (FitPass, motion_fit.hip); the 6 x 6 Cholesky solve and the composition F <- F o W^-1 run on the host in double
+//      (affine_map.hpp).
+// Sample positions are kernels_affine.hip's (affine_coord of motion_fit_dev.hpp: every operation rounded on its own).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -23,35 +26,9 @@ namespace srmap {
 namespace {
 
 constexpr int kGnSums = 26;       // 18 of H, 6 of g, sum e^2, pixel count
-constexpr int kFrameRec = 8;      // a b tx c d ty active pad
 constexpr int kMaxLevels = 12;
 constexpr int kMaxRowChunks = 128;
 constexpr int kMaxSeedChunks = 8;
-constexpr double kMaxDeviation = 0.25;
-constexpr double kPivotRtol = 1e-12;
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// kernels_affine.hip's affine_coord: m0 x + (m1 y + m2), no contraction
-__device__ __forceinline__ double affine_coord(double m0, double m1, double m2, double x, double y) {
-#pragma clang fp contract(off)
-  const double t = m1 * y + m2;
-  return m0 * x + t;
-}
-
-// dst[k][h2][w2] = mean of the 2 x 2 blocks of src[k][h][w] (w2 = w / 2, h2 = h / 2), blockIdx.y = k
-__global__ __launch_bounds__(256) void k_down2_stack(const double* __restrict__ src, double* __restrict__ dst, int w, int h,
-                                                     int w2, int h2) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= w2 * h2) return;
-  const int r = i / w2, c = i - r * w2;
-  const double* s = src + (size_t)blockIdx.y * w * h + (size_t)(2 * r) * w + 2 * c;
-  dst[(size_t)blockIdx.y * w2 * h2 + i] = 0.25 * ((s[0] + s[1]) + (s[w] + s[w + 1]));
-}
 
 // partial[((f * ncand + cand) * gridDim.y + chunk)] = sum of (I_{f+1}(p + u) - I_0(p))^2 over the rows of this chunk of
 // the window [R, w-R) x [R, h-R), u = (cand % n1 - R, cand / n1 - R), n1 = 2R + 1.  grid = (ncand, chunks, frames - 1).
@@ -69,7 +46,7 @@ __global__ __launch_bounds__(256) void k_ssd_window(const double* __restrict__ s
       s += d * d;
     }
   }
-  s = wsum(s);
+  s = wave_sum(s);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) red[wv] = s;
   __syncthreads();
@@ -78,7 +55,7 @@ __global__ __launch_bounds__(256) void k_ssd_window(const double* __restrict__ s
 }
 
 // Gauss-Newton sums of one inverse-compositional pass for every frame: grid = (row chunks, frames - 1).
-// table[f][kFrameRec]: F of frame f + 1 at this level and its "active" flag.  Over the template pixels p of this chunk's
+// table[f][kFitTabRec]: F of frame f + 1 at this level and its "active" flag.  Over the template pixels p of this chunk's
 // rows (1 px from the border) whose four taps of I_{f+1} at s = F(p) are inside:
 //   e = I(s) - I_0(p), (gx, gy) central differences of I_0, (u, v) = p - centre,
 //   partial[(f * chunks + chunk)][26] = {gx^2, gx gy, gy^2} x {u^2, uv, u, v^2, v, 1} (index 6 a + m),
@@ -87,7 +64,7 @@ __global__ __launch_bounds__(256) void k_affine_gn_sums(const double* __restrict
                                                         const double* __restrict__ table, double* __restrict__ partial) {
   __shared__ double red[kGnSums][4];
   const int f = blockIdx.y;
-  const double* m = table + (size_t)f * kFrameRec;
+  const double* m = table + (size_t)f * kFitTabRec;
   if (m[6] == 0.0) return;  // converged frame: uniform
   const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
   const double* a = stack;
@@ -131,111 +108,17 @@ __global__ __launch_bounds__(256) void k_affine_gn_sums(const double* __restrict
       acc[25] += 1.0;
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < kGnSums; ++q) {
-    const double s = wsum(acc[q]);
-    if (lane == 0) red[q][wv] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kGnSums) {
-    const int q = threadIdx.x;
-    partial[((size_t)f * gridDim.x + blockIdx.x) * kGnSums + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-  }
+  fold_sums_256(acc, red, partial + ((size_t)f * gridDim.x + blockIdx.x) * kGnSums);
 }
 
-// sums[f][26] = the chunk partials of frame f + 1 added in index order.  grid = frames - 1, 64 threads.
-__global__ __launch_bounds__(64) void k_affine_gn_reduce(const double* __restrict__ partial, int chunks,
-                                                         const double* __restrict__ table, double* __restrict__ sums) {
-  const int f = blockIdx.x, q = threadIdx.x;
-  if (table[(size_t)f * kFrameRec + 6] == 0.0 || q >= kGnSums) return;
-  double s = 0.0;
-  for (int k = 0; k < chunks; ++k) s += partial[((size_t)f * chunks + k) * kGnSums + q];
-  sums[(size_t)f * kGnSums + q] = s;
-}
-
-// ---- host side: 2 x 3 maps [a b tx c d ty] ----
-struct Map { double m[6]; };
-
-double deviation(const Map& F) {
-  return std::max(std::fabs(F.m[0] - 1.0) + std::fabs(F.m[1]), std::fabs(F.m[3]) + std::fabs(F.m[4] - 1.0));
-}
-bool all_finite(const Map& F) {
-  for (double v : F.m) if (!std::isfinite(v)) return false;
-  return true;
-}
-// fine p = 2 u + 1/2: L unchanged, t_fine = 2 t + (1/2, 1/2) - L (1/2, 1/2)
-Map to_finer(const Map& F) {
-  Map G = F;
-  G.m[2] = 2.0 * F.m[2] + 0.5 - (F.m[0] * 0.5 + F.m[1] * 0.5);
-  G.m[5] = 2.0 * F.m[5] + 0.5 - (F.m[3] * 0.5 + F.m[4] * 0.5);
-  return G;
-}
-Map to_coarser(const Map& F) {
-  Map G = F;
-  G.m[2] = 0.5 * (F.m[2] - 0.5 + (F.m[0] * 0.5 + F.m[1] * 0.5));
-  G.m[5] = 0.5 * (F.m[5] - 0.5 + (F.m[3] * 0.5 + F.m[4] * 0.5));
-  return G;
-}
-double corner_displacement(const Map& A, const Map& B, int w, int h) {
-  double worst = 0.0;
-  for (int i = 0; i < 4; ++i) {
-    const double x = (i & 1) ? w - 1.0 : 0.0, y = (i & 2) ? h - 1.0 : 0.0;
-    const double dx = (A.m[0] - B.m[0]) * x + (A.m[1] - B.m[1]) * y + (A.m[2] - B.m[2]);
-    const double dy = (A.m[3] - B.m[3]) * x + (A.m[4] - B.m[4]) * y + (A.m[5] - B.m[5]);
-    worst = std::max(worst, std::hypot(dx, dy));
-  }
-  return worst;
-}
-
-// H (6 x 6, from the 18 sums) D = g by Cholesky; false where a pivot is not above kPivotRtol of its diagonal entry
+// H (6 x 6, from the 18 sums) D = g by Cholesky; false: no texture
 bool solve_step(const double* S, double* delta) {
   // J_i = g_{i / 3} * m_{i % 3}, m = (u, v, 1); product index of (m_i, m_j) in {u^2, uv, u, v^2, v, 1}
   static const int mprod[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-  double H[6][6], Lc[6][6] = {}, g[6], y[6];
-  for (int i = 0; i < 6; ++i) {
+  double H[6][6];
+  for (int i = 0; i < 6; ++i)
     for (int j = 0; j < 6; ++j) H[i][j] = S[6 * (i / 3 + j / 3) + mprod[i % 3][j % 3]];
-    g[i] = S[18 + i];
-  }
-  for (int j = 0; j < 6; ++j) {
-    double p = H[j][j];
-    for (int k = 0; k < j; ++k) p -= Lc[j][k] * Lc[j][k];
-    if (!(H[j][j] > 0.0 && p > kPivotRtol * H[j][j])) return false;
-    Lc[j][j] = std::sqrt(p);
-    for (int i = j + 1; i < 6; ++i) {
-      double s = H[i][j];
-      for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
-      Lc[i][j] = s / Lc[j][j];
-    }
-  }
-  for (int i = 0; i < 6; ++i) {
-    double s = g[i];
-    for (int k = 0; k < i; ++k) s -= Lc[i][k] * y[k];
-    y[i] = s / Lc[i][i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-    for (int k = i + 1; k < 6; ++k) s -= Lc[k][i] * delta[k];
-    delta[i] = s / Lc[i][i];
-  }
-  return true;
-}
-
-// F o W^-1, W(p) = p + D (p - c) + d with D = [D0 D1; D3 D4], d = (D2, D5), c = ((w-1)/2, (h-1)/2)
-Map compose_with_inverse(const Map& F, const double* delta, int w, int h) {
-  const double cx = 0.5 * (w - 1), cy = 0.5 * (h - 1);
-  const double A00 = 1.0 + delta[0], A01 = delta[1], A10 = delta[3], A11 = 1.0 + delta[4];
-  const double tx = delta[2] - (delta[0] * cx + delta[1] * cy), ty = delta[5] - (delta[3] * cx + delta[4] * cy);
-  const double det = A00 * A11 - A01 * A10;
-  const double i00 = A11 / det, i01 = -A01 / det, i10 = -A10 / det, i11 = A00 / det;
-  Map G;
-  G.m[0] = F.m[0] * i00 + F.m[1] * i10;
-  G.m[1] = F.m[0] * i01 + F.m[1] * i11;
-  G.m[3] = F.m[3] * i00 + F.m[4] * i10;
-  G.m[4] = F.m[3] * i01 + F.m[4] * i11;
-  G.m[2] = F.m[2] - (G.m[0] * tx + G.m[1] * ty);
-  G.m[5] = F.m[5] - (G.m[3] * tx + G.m[4] * ty);
-  return G;
+  return cholesky_solve(H, S + 18, 6, delta);
 }
 
 }  // namespace
@@ -276,12 +159,12 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   if (quality_out) { quality_out[0] = 1.0; quality_out[1] = 0.0; quality_out[2] = 1.0; quality_out[3] = 0.0; }
   if (K == 1) return SRMAP_OK;
 
-  std::vector<Map> F(nf);
+  std::vector<AffineMap> F(nf);
   std::vector<double> sep(nf, 1.0);
   if (opt.initial_affine_2x3) {
     for (int f = 0; f < nf; ++f) {
       std::copy(opt.initial_affine_2x3 + 6 * (f + 1), opt.initial_affine_2x3 + 6 * (f + 2), F[f].m);
-      if (!all_finite(F[f]) || deviation(F[f]) > kMaxDeviation)
+      if (!all_finite(F[f]) || deviation(F[f]) > kAffineMaxDeviation)
         return set_error(ctx, SRMAP_EINVAL, "affine registration: initial matrix %d is not finite or outside the model's domain", f + 1);
     }
   }
@@ -304,15 +187,11 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   const int seed_chunks = seed_window ? std::min(kMaxSeedChunks, ch - 2 * R) : 0;
   const size_t part_elems = std::max((size_t)nf * chunks_of(height) * kGnSums, seed ? (size_t)nf * ncand * seed_chunks : 0);
 
-  double *d_pyr = nullptr, *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr, *h_tab = nullptr, *h_sums = nullptr;
+  double* d_pyr = nullptr;
+  FitPass fit;  // its d_part also takes the seed search's partials
   int rc = SRMAP_OK;
   auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "affine registration: %s", what); };
-  if (hipMalloc((void**)&d_pyr, off[L] * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_part, part_elems * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_tab, (size_t)nf * kFrameRec * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_sums, (size_t)nf * kGnSums * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&h_tab, (size_t)nf * kFrameRec * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&h_sums, (size_t)nf * kGnSums * sizeof(double)) != hipSuccess) {
+  if (hipMalloc((void**)&d_pyr, off[L] * sizeof(double)) != hipSuccess || !fit.alloc(nf, kGnSums, part_elems)) {
     (void)hipGetLastError();
     fail(SRMAP_ENOMEM, "allocation failed");
   }
@@ -321,11 +200,8 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   if (rc == SRMAP_OK) {
     if (hipMemcpyAsync(d_pyr, images_host, (size_t)K * width * height * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
       fail(SRMAP_EHIP, "upload failed");
-    for (int l = 1; l < L && rc == SRMAP_OK; ++l) {
-      const int n = lw[l] * lh[l];
-      hipLaunchKernelGGL(k_down2_stack, dim3((n + 255) / 256, K), dim3(256), 0, st, d_pyr + off[l - 1], d_pyr + off[l],
-                         lw[l - 1], lh[l - 1], lw[l], lh[l]);
-    }
+    for (int l = 1; l < L && rc == SRMAP_OK; ++l)
+      launch_down2_stack(d_pyr + off[l - 1], d_pyr + off[l], lw[l - 1], lh[l - 1], K, st);
     if (rc == SRMAP_OK && hipGetLastError() != hipSuccess) fail(SRMAP_EHIP, "pyramid failed");
   }
 
@@ -339,9 +215,9 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
       const int rows = ch - 2 * R, rpc = (rows + seed_chunks - 1) / seed_chunks;
       const size_t n = (size_t)nf * ncand * seed_chunks;
       std::vector<double> h_part(n);
-      hipLaunchKernelGGL(k_ssd_window, dim3(ncand, seed_chunks, nf), dim3(256), 0, st, d_pyr + off[L - 1], cw, ch, R, rpc, d_part);
+      hipLaunchKernelGGL(k_ssd_window, dim3(ncand, seed_chunks, nf), dim3(256), 0, st, d_pyr + off[L - 1], cw, ch, R, rpc, fit.d_part);
       if (hipGetLastError() != hipSuccess ||
-          hipMemcpyAsync(h_part.data(), d_part, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipMemcpyAsync(h_part.data(), fit.d_part, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
           hipStreamSynchronize(st) != hipSuccess) {
         fail(SRMAP_EHIP, "coarse search failed");
       } else {
@@ -355,12 +231,7 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
             msd[c] = s / count;
             if (msd[c] < msd[bi]) bi = c;  // the first minimum in row-major order wins
           }
-          double runner = -1.0;
-          for (int c = 0; c < ncand; ++c) {
-            if (std::max(std::abs(c % n1 - bi % n1), std::abs(c / n1 - bi / n1)) < 2) continue;
-            if (runner < 0 || msd[c] < runner) runner = msd[c];
-          }
-          sep[f] = runner > 0 ? 1.0 - msd[bi] / runner : 0.0;
+          sep[f] = search_separation(msd.data(), n1, bi);
           F[f].m[2] = bi % n1 - R;
           F[f].m[5] = bi / n1 - R;
         }
@@ -368,21 +239,14 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
     }
   }
 
-  // one pass over every frame flagged active: sums land in h_sums
+  // one pass over every frame flagged active: sums land in fit.sums(f)
   std::vector<char> active(nf, 1);
   auto pass = [&](int l) -> bool {
-    for (int f = 0; f < nf; ++f) {
-      std::copy(F[f].m, F[f].m + 6, h_tab + (size_t)f * kFrameRec);
-      h_tab[(size_t)f * kFrameRec + 6] = active[f] ? 1.0 : 0.0;
-      h_tab[(size_t)f * kFrameRec + 7] = 0.0;
-    }
+    for (int f = 0; f < nf; ++f) fit.set(f, F[f], active[f] != 0);
     const int chunks = chunks_of(lh[l]), rpc = (lh[l] - 2 + chunks - 1) / chunks;
-    if (hipMemcpyAsync(d_tab, h_tab, (size_t)nf * kFrameRec * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_affine_gn_sums, dim3(chunks, nf), dim3(256), 0, st, d_pyr + off[l], lw[l], lh[l], rpc, d_tab, d_part);
-    hipLaunchKernelGGL(k_affine_gn_reduce, dim3(nf), dim3(64), 0, st, d_part, chunks, d_tab, d_sums);
-    return hipGetLastError() == hipSuccess &&
-           hipMemcpyAsync(h_sums, d_sums, (size_t)nf * kGnSums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-           hipStreamSynchronize(st) == hipSuccess;
+    if (!fit.upload(st)) return false;
+    hipLaunchKernelGGL(k_affine_gn_sums, dim3(chunks, nf), dim3(256), 0, st, d_pyr + off[l], lw[l], lh[l], rpc, fit.d_tab, fit.d_part);
+    return fit.reduce_and_fetch(chunks, st);
   };
 
   // ---- Gauss-Newton, coarse to fine ----
@@ -394,13 +258,16 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
       if (!pass(l)) { fail(SRMAP_EHIP, "Gauss-Newton pass failed"); break; }
       for (int f = 0; f < nf; ++f) {
         if (!active[f]) continue;
-        const double* S = h_sums + (size_t)f * kGnSums;
+        const double* S = fit.sums(f);
         ++iters[f];
         if (S[25] < 0.25 * lw[l] * lh[l]) { fail(SRMAP_EINVAL, "Could not determine motion between images."); break; }
         double delta[6];
         if (!solve_step(S, delta)) { active[f] = 0; continue; }  // no texture: this level keeps F
-        const Map Fn = compose_with_inverse(F[f], delta, lw[l], lh[l]);
-        if (!all_finite(Fn) || deviation(Fn) > kMaxDeviation) { fail(SRMAP_EINVAL, "Could not determine motion between images."); break; }
+        const AffineMap Fn = compose_with_inverse(F[f], delta, lw[l], lh[l]);
+        if (!all_finite(Fn) || deviation(Fn) > kAffineMaxDeviation) {
+          fail(SRMAP_EINVAL, "Could not determine motion between images.");
+          break;
+        }
         const double step = corner_displacement(Fn, F[f], lw[l], lh[l]);
         F[f] = Fn;
         if (step < opt.step_tolerance) active[f] = 0;
@@ -422,7 +289,7 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
       o[2] *= opt.hr_scale;
       o[5] *= opt.hr_scale;
       if (quality_out) {
-        const double* S = h_sums + (size_t)f * kGnSums;
+        const double* S = fit.sums(f);
         double* q = quality_out + 4 * (f + 1);
         q[0] = sep[f];
         q[1] = S[25] > 0 ? std::sqrt(S[24] / S[25]) : 0.0;
@@ -432,10 +299,5 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
     }
   }
   if (d_pyr) (void)hipFree(d_pyr);
-  if (d_part) (void)hipFree(d_part);
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_sums) (void)hipFree(d_sums);
-  if (h_tab) (void)hipHostFree(h_tab);
-  if (h_sums) (void)hipHostFree(h_sums);
   return rc;
 }

@@ -212,6 +212,32 @@ int launch_gather_affine(srmap_problem* p, const Geometry& geo, const T* resid, 
                          bool accumulate, hipStream_t st);
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
+// ---- the motion fits' shared kernels and per-pass buffers (motion_fit.hip) ----
+struct AffineMap;  // affine_map.hpp
+// dst[k][h/2][w/2] = mean of the 2 x 2 blocks of src[k][h][w], k < frames: one level of a box pyramid
+void launch_down2_stack(const double* src, double* dst, int w, int h, int frames, hipStream_t st);
+// One pass of a fit over every frame (registration_affine.hip, motion_refinement.hip): the caller's sums kernel reads the
+// frame table d_tab[frame][kFitTabRec] = {six matrix entries, active flag, pad}, returns at once for a frame whose flag is
+// 0 and writes one record of nsums doubles per workgroup to d_part[(frame * chunks + chunk)][nsums].  Per pass: set()
+// every frame, upload(), the sums kernel, reduce_and_fetch() -- one table upload, one copy of frames x nsums doubles and
+// one stream wait; then sums(frame) holds the chunk records added in index order (unchanged for an inactive frame).
+constexpr int kFitTabRec = 8;
+struct FitPass {
+  int frames = 0, nsums = 0;
+  double *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr;  // device
+  double *h_tab = nullptr, *h_sums = nullptr;                     // pinned host
+  FitPass() = default;
+  FitPass(const FitPass&) = delete;
+  FitPass& operator=(const FitPass&) = delete;
+  ~FitPass();
+  // part_elems: doubles of d_part (>= frames * chunks * nsums; a caller may ask for more and share it).  false: an
+  // allocation failed (the caller clears the sticky error)
+  bool alloc(int frames_, int nsums_, size_t part_elems);
+  void set(int frame, const AffineMap& M, bool active);
+  bool upload(hipStream_t st);
+  bool reduce_and_fetch(int chunks, hipStream_t st);  // also reports a failed launch of the caller's sums kernel
+  const double* sums(int frame) const { return h_sums + (size_t)frame * nsums; }
+};
 // whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
 template <typename T>

@@ -1,5 +1,5 @@
-"""The affine registration on the GPU (include/srmap.h: srmap_register_affine; k_affine_gn_sums, k_affine_gn_reduce and
-k_ssd_window of csrc/registration_affine.hip) against its numpy restatement (tests/affine_registration_restatement.py),
+"""The affine registration on the GPU (include/srmap.h: srmap_register_affine; k_affine_gn_sums and k_ssd_window of
+csrc/registration_affine.hip, k_fit_reduce of csrc/motion_fit.hip) against its numpy restatement (tests/affine_registration_restatement.py),
 against the matrices that made the frames, and against itself.
 
 Bars.  One Gauss-Newton step: the corner displacement between the GPU's and the restatement's matrix is at most 100 x the

@@ -1,5 +1,5 @@
-"""The joint motion refinement on the GPU (include/srmap.h: srmap_refine_motion; k_refine_sums and k_refine_reduce of
-csrc/motion_refinement.hip) against its numpy restatement (tests/motion_refinement_restatement.py), against an existing
+"""The joint motion refinement on the GPU (include/srmap.h: srmap_refine_motion; k_refine_sums of
+csrc/motion_refinement.hip and k_fit_reduce of csrc/motion_fit.hip) against its numpy restatement (tests/motion_refinement_restatement.py), against an existing
 kernel (the data cost of srmap_eval) and against itself.
 
 Bars.  One pass: each block of the 28 sums (H, g, E) is held to 100 x the restatement's own sensitivity to the ORDER of its
