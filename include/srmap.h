@@ -33,7 +33,7 @@
  *   - entry points that take HOST pointers (srmap_eval, srmap_solve*,
  *     srmap_cg_trace, srmap_apply*, srmap_reg_values*, srmap_set_observations,
  *     srmap_set_irls_weights, srmap_set_data_weights, srmap_get_data_weights, srmap_channel_map, srmap_channel_pca,
- *     srmap_register_translational, srmap_register_affine, srmap_refine_motion, srmap_upload / srmap_download) run on the
+ *     srmap_register_translational, srmap_register_affine, srmap_refine_motion, srmap_fit_blur, srmap_upload / srmap_download) run on the
  *     context's stream and are complete when they return.
  *   - the problem's device state (observations, IRLS weights, data weights) is ordered by the
  *     library itself: a write through srmap_update_irls_weights_device / srmap_update_data_weights_device on one
@@ -163,6 +163,31 @@ int srmap_problem_active_impl(const srmap_problem* p, int* impl);
  * for.  srmap_register_affine estimates the matrices from the frames (srmap_register_translational finds translations
  * only); its output goes straight into this call. */
 int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3);
+
+/* Free-form blur kernel (no reference counterpart: BlurModule builds an isotropic Gaussian from (blur_radius, sigma) only,
+ * blur_module.cpp:13-22).  taps: ksize x ksize doubles, row-major, the layout of the Gaussian the problem
+ * builds itself.  The forward model CORRELATES with them, as filter2D does (blur_module.cpp:24-28):
+ *   (B z)(R, C) = sum_{a,e} taps[a][e] z(R + a - hb, C + e - hb),  hb = (ksize - 1) / 2,  z = 0 outside the image.
+ *   domain    ksize odd, 1 ... 7; it may differ from the blur_ksize the problem was created with.  Taps finite; no sign and
+ *             no sum is imposed and the call does not normalise.  A tap that is not finite, an even ksize or ksize < 1:
+ *             SRMAP_EINVAL; ksize > 7: SRMAP_EUNSUPPORTED; on an error the problem keeps its blur.
+ *   adjoint   B^T is the exact transpose: the correlation with the kernel FLIPPED IN BOTH AXES, taps[ksize-1-a][ksize-1-e]
+ *             (the reference correlates with kernel.t(), blur_module.cpp:30-36, which is the same thing only for a kernel
+ *             that is symmetric under both flips, as its Gaussian is).  The gradient is the true gradient of the cost.
+ *   NULL      restores the blur the problem was created with (the Gaussian, or none) and its size, bit for bit: evaluations
+ *             before and after a set / restore pair are bit-identical.
+ * While a free-form kernel is set the direct kernel family runs (srmap_problem_active_impl answers SRMAP_IMPL_DIRECT;
+ * SRMAP_IMPL_TILED answers SRMAP_EUNSUPPORTED at evaluation) -- also when the taps equal the Gaussian's; evaluations and
+ * solves sharded over a communicator of more than one rank answer SRMAP_EUNSUPPORTED.  It works with no motion, shifts_xy
+ * and an affine motion, with data weights and the Huber loss; srmap_eval*, srmap_apply, srmap_apply_transpose, srmap_solve
+ * (CG, L-BFGS, split_channels), the traces, srmap_problem_set_cost_rows and srmap_refine_motion honour it.  It persists
+ * across srmap_set_observations, the data-weight calls and srmap_problem_set_affine_motion.  Not thread-safe against
+ * evaluations of the same problem; evaluations already enqueued are waited for.  srmap_fit_blur estimates the taps from a
+ * known HR image. */
+int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* taps);
+/* The blur in force (no reference counterpart; blur_module.cpp keeps its kernel private): *ksize (1 = no blur) and, when
+ * taps_out is not NULL, its ksize x ksize taps (at most 15 x 15 doubles for a created Gaussian, 7 x 7 for a free-form one). */
+int srmap_problem_get_blur_kernel(const srmap_problem* p, int* ksize, double* taps_out);
 
 /* Inner minimiser of srmap_solve: MapSolverOptions::least_squares_solver and num_lbfgs_hessian_corrections
  * (enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER }, map_solver.h:20-51; the choice irls_map_solver.cpp:97-113;
@@ -431,6 +456,42 @@ int srmap_refine_motion(srmap_problem* p, const double* x_host, const srmap_moti
 int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, void* hip_stream,
                                const srmap_motion_refinement_options* options /* NULL = defaults */,
                                double* affine_2x3_out, double* quality_out, double* normal_equations_out);
+
+/* Calibration fit of the blur kernel (no reference counterpart: blur_module.cpp takes (radius, sigma) and nothing is
+ * estimated; csrc/blur_fit.hip).  With a KNOWN HR image x (a chart, a calibration pair) the ksize x ksize taps
+ * h of B are the minimiser of the quadratic
+ *   energy    E(h) = sum_k sum_c sum_u w (sum_t h_t s_t - y)^2, s_t = (M_k x)(R0 + a - hb, C0 + e - hb) the warped image at
+ *             tap t = (a, e) of LR pixel u (0 outside the image), (R0, C0) the decimation source of u, M_k sampled exactly as
+ *             the forward kernel of the problem's motion samples it (the 1/32-px table of shifts_xy, double coordinates for
+ *             an affine motion, the identity without motion), over EVERY LR pixel of every channel and frame: the rows of
+ *             srmap_problem_set_cost_rows are ignored.  w: the problem's data weights as they stand, 1 when none are set.
+ *             The sums are double in both dtypes.
+ *   solve     one pass, one solve: (G + mu I) h = b + mu h_current by Cholesky on the host, G = sum w s s^T, b = sum w s y,
+ *             mu = ridge trace(G) / ksize^2, h_current the kernel in force zero-padded or centre-cropped to ksize;
+ *             sum_to_one adds the constraint sum h = 1 (its KKT system).  A failed factorisation (no texture, every
+ *             weight 0) keeps the kernel: status 3, not an error of the call.
+ * taps_out (optional, ksize^2): the fitted taps (the kernel in force, padded / cropped, for status 3).  quality_out
+ * (optional, 5): E at the kernel in force, E at the fit, smallest and largest pivot of the factorisation, status (0 or 3).
+ * normal_equations_out (optional, (n + 1)(n + 2) / 2 with n = ksize^2): the upper triangle, row-major, of the Gram of
+ * [s_0 ... s_{n-1}, y] under w.  apply = 1 installs the fit as srmap_problem_set_blur_kernel(p, ksize, taps) would.
+ * SRMAP_EINVAL: no observations set; a struct_size that is not this library's; an even ksize or ksize < 0; a negative or
+ * non-finite ridge.  SRMAP_EUNSUPPORTED: ksize > 7.  Every error leaves the problem unchanged.  Results are bit-identical
+ * run to run.  Sharded problems are out of scope.  Blind estimation (x unknown) is NOT offered: alternating a solve and this
+ * fit drifts.  The _device form takes x in the problem's dtype and enqueues on hip_stream (NULL = the
+ * context's stream); both forms are complete when they return. */
+typedef struct {
+  int struct_size;  /* filled by the _default call; a mismatch is SRMAP_EINVAL */
+  int ksize;        /* 0 = the size of the kernel in force (default) */
+  int sum_to_one;   /* 1 */
+  double ridge;     /* 0 */
+  int apply;        /* 1 */
+} srmap_blur_fit_options;
+void srmap_blur_fit_options_default(srmap_blur_fit_options* options);
+int srmap_fit_blur(srmap_problem* p, const double* x_host, const srmap_blur_fit_options* options /* NULL = defaults */,
+                   double* taps_out, double* quality_out, double* normal_equations_out);
+int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                          const srmap_blur_fit_options* options /* NULL = defaults */, double* taps_out, double* quality_out,
+                          double* normal_equations_out);
 
 /* ------------------------------------------------------------- solver */
 /* IRLSMapSolverOptions (irls_map_solver.h:14-36) + MapSolverOptions

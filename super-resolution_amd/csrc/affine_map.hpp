@@ -107,6 +107,42 @@ inline bool cholesky_solve(const double A[6][6], const double* rhs, int n, doubl
   return true;
 }
 
+// The sized copy of the factorisation above for the blur fit (blur_fit.hip: n = ksize^2 <= 49): A = L L^T over the n x n
+// row-major matrix A, the same pivot test.  L replaces nothing: it goes to Lc (n x n, lower triangle).  pivot_min /
+// pivot_max receive the smallest / largest pivot (the squares of L's diagonal).  false: no texture.
+inline bool cholesky_factor_n(const double* A, int n, double* Lc, double* pivot_min, double* pivot_max) {
+  double lo = 0.0, hi = 0.0;
+  for (int j = 0; j < n; ++j) {
+    double p = A[j * n + j];
+    for (int k = 0; k < j; ++k) p -= Lc[j * n + k] * Lc[j * n + k];
+    if (!(A[j * n + j] > 0.0 && p > kCholeskyPivotRtol * A[j * n + j])) return false;
+    lo = j == 0 ? p : std::min(lo, p);
+    hi = j == 0 ? p : std::max(hi, p);
+    Lc[j * n + j] = std::sqrt(p);
+    for (int i = j + 1; i < n; ++i) {
+      double s = A[i * n + j];
+      for (int k = 0; k < j; ++k) s -= Lc[i * n + k] * Lc[j * n + k];
+      Lc[i * n + j] = s / Lc[j * n + j];
+    }
+  }
+  if (pivot_min) *pivot_min = lo;
+  if (pivot_max) *pivot_max = hi;
+  return true;
+}
+// x = (L L^T)^-1 rhs by the two triangular solves of cholesky_solve
+inline void cholesky_apply_n(const double* Lc, int n, const double* rhs, double* x) {
+  for (int i = 0; i < n; ++i) {
+    double s = rhs[i];
+    for (int k = 0; k < i; ++k) s -= Lc[i * n + k] * x[k];
+    x[i] = s / Lc[i * n + i];
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    double s = x[i];
+    for (int k = i + 1; k < n; ++k) s -= Lc[k * n + i] * x[k];
+    x[i] = s / Lc[i * n + i];
+  }
+}
+
 // Separation of a coarse search's minimum: 1 - msd[best] / runner-up, the runner-up being the smallest entry of the
 // n1 x n1 table (row-major) at least 2 cells away from `best`; entries < 0 (a candidate that was not evaluated) are
 // skipped.  Near 1 = one clear minimum, near 0 = ambiguous; 0 where no runner-up is positive.

@@ -1,0 +1,316 @@
+// blur_fit.hip -- calibration fit of the blur kernel (srmap_fit_blur): with the HR image x KNOWN (a chart, a
+// calibration pair) the ksize x ksize taps h of B in A_k = D B M_k are a linear least-squares problem,
+//   E(h) = sum_k sum_c sum_u w (sum_t h_t s_t - y)^2,  s_t = (M_k x)(R0 + a - hb, C0 + e - hb), t = (a, e), 0 outside the image,
+// (R0, C0) the decimation source of LR pixel u, M_k sampled exactly as the forward kernel of the problem's motion samples it
+// (warp_sample / affine_sample of sample_dev.hpp, affine_coord of motion_fit_dev.hpp; the identity without motion), over
+// every LR pixel of every channel and frame (the cost-row restriction is ignored, as in 3.8).  No reference counterpart
+// (blur_module.cpp:13-22 builds a Gaussian from (radius, sigma)); the checker is tests/blur_kernel_restatement.py.
+//   pass      ONE launch of k_blur_fit_sums: with n = ksize^2 the record is the upper triangle (row-major) of the
+//             (n + 1) x (n + 1) Gram of the columns [s_0 ... s_{n-1}, y] under w: P = (n + 1)(n + 2) / 2 sums (3 / 55 / 351 /
+//             1275).  grid (chunks, frames), 256 threads; the workgroup walks its chunk in tiles of 128 observations
+//             (pixel, channel); phase 1 forms the tile's n + 1 columns once, in double after the loads, in LDS (row stride
+//             129 doubles: odd, so the rows a wave reads in phase 2 spread over the banks and lanes that share a row
+//             broadcast); phase 2 gives every thread its own <= 5 pairs (i <= j) and adds (w u_i) u_j over the tile in
+//             index order in f64 registers.  No cross-thread reduction, no atomics, a fixed order: bit-identical run to run;
+//   reduce    k_blur_fit_reduce adds the (frame, chunk) records in index order;
+//   pacing    one launch, one reduce, one copy of P doubles, one stream wait;
+//   solve     on the host in double: (G + mu I) h = b + mu h_current, mu = ridge trace(G) / n, by Cholesky
+//             (cholesky_factor_n, affine_map.hpp); sum_to_one: the KKT system of the constraint 1^T h = 1 by block
+//             elimination over the same factor, h = u - lambda v, u = A^-1 rhs, v = A^-1 1, lambda = (1^T u - 1) / (1^T v).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
+#include "sample_dev.hpp"
+#include "srmap_internal.hpp"
+
+namespace srmap {
+
+namespace {
+
+constexpr int kTile = 128;       // observations per tile
+constexpr int kStride = 129;     // LDS row stride in doubles (odd)
+constexpr int kMaxChunks = 128;  // chunks per frame at most
+constexpr int kMinTilesPerChunk = 2;
+enum { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2 };
+
+template <typename T, int B, int MOTION, bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, const T* __restrict__ y,
+                                                       const T* __restrict__ dw, Geometry g,
+                                                       const WarpTaps<T>* __restrict__ warps,
+                                                       const double* __restrict__ recs, const int* __restrict__ col_map,
+                                                       const int* __restrict__ row_map, int tiles_per_chunk,
+                                                       double* __restrict__ partial) {
+  constexpr int N = B * B, N1 = N + 1, P = N1 * (N1 + 1) / 2, PP = (P + 255) / 256, HB = (B - 1) / 2;
+  __shared__ double u[N1 * kStride];  // column t of the tile: u[t * kStride + observation]; column N is y
+  __shared__ double wl[kTile];
+  const int k = blockIdx.y;
+  const int n = g.w * g.h;
+  const long long nobs = (long long)n * g.C;
+  // this thread's pairs (i <= j) of the upper triangle, row-major: q = threadIdx.x + 256 m
+  int pi[PP], pj[PP];
+  double acc[PP];
+#pragma unroll
+  for (int m = 0; m < PP; ++m) {
+    const int q = (int)threadIdx.x + 256 * m;
+    int i = 0, rem = q < P ? q : 0;
+    while (rem >= N1 - i) { rem -= N1 - i; ++i; }
+    pi[m] = i * kStride;
+    pj[m] = (i + rem) * kStride;
+    acc[m] = 0.0;
+  }
+  const WarpTaps<T> wt = (MOTION == kMotionTable) ? warps[k] : identity_warp<T>();
+  const double* __restrict__ mk = (MOTION == kMotionAffine) ? recs + (size_t)k * kAffineRec : nullptr;  // uniform
+  const int ob = threadIdx.x & (kTile - 1), half = threadIdx.x >> 7;
+  for (int tile = 0; tile < tiles_per_chunk; ++tile) {
+    const long long o0 = ((long long)blockIdx.x * tiles_per_chunk + tile) * kTile;
+    if (o0 >= nobs && tile > 0) break;  // uniform
+    const long long o = o0 + ob;
+    const bool live = o < nobs;
+    __syncthreads();  // the previous tile's phase 2 has read the columns
+    // ---- phase 1: the tile's columns ----
+    int c = 0, lp = 0, R0 = 0, C0 = 0;
+    if (live) {
+      c = (int)(o / n);
+      lp = (int)(o - (long long)c * n);
+      const int i = lp / g.w, j = lp - i * g.w;
+      R0 = row_map[i];
+      C0 = col_map[j];
+    }
+    const T* __restrict__ plane = x + (size_t)c * g.W * g.H;
+    for (int t = half; t < N; t += 2) {
+      const int a = t / B, e = t - a * B;
+      const int rr = R0 + a - HB, cc = C0 + e - HB;
+      double s = 0.0;
+      if (live && rr >= 0 && rr < g.H && cc >= 0 && cc < g.W) {  // the blur's zero border on the warped image
+        if (MOTION == kMotionAffine) {
+          const double sx = affine_coord(mk[0], mk[1], mk[2], (double)cc, (double)rr);
+          const double sy = affine_coord(mk[3], mk[4], mk[5], (double)cc, (double)rr);
+          s = affine_sample<T, double>(plane, g.W, g.H, sx, sy);
+        } else if (MOTION == kMotionTable) {
+          s = warp_sample<T, double>(plane, g.W, g.H, wt, rr, cc);
+        } else {
+          s = (double)plane[(size_t)rr * g.W + cc];
+        }
+      }
+      u[t * kStride + ob] = s;
+    }
+    {
+      const size_t oi = ((size_t)k * g.C + c) * n + lp;
+      if (half == 0) u[N * kStride + ob] = live ? (double)y[oi] : 0.0;
+      else wl[ob] = live ? (WEIGHTED ? (double)dw[oi] : 1.0) : 0.0;
+    }
+    __syncthreads();
+    // ---- phase 2: this thread's pairs over the tile, in index order ----
+    for (int q = 0; q < kTile; ++q) {
+      const double wv = wl[q];
+#pragma unroll
+      for (int m = 0; m < PP; ++m) acc[m] += (wv * u[pi[m] + q]) * u[pj[m] + q];
+    }
+  }
+  double* __restrict__ rec = partial + ((size_t)k * gridDim.x + blockIdx.x) * P;
+#pragma unroll
+  for (int m = 0; m < PP; ++m) {
+    const int q = (int)threadIdx.x + 256 * m;
+    if (q < P) rec[q] = acc[m];
+  }
+}
+
+// sums[q] = the `records` records partial[r][nsums] added in index order (k_fit_reduce of motion_fit.hip holds at most 64
+// sums per frame and keeps one record per frame; this one adds everything and has no cap)
+__global__ __launch_bounds__(256) void k_blur_fit_reduce(const double* __restrict__ partial, int records, int nsums,
+                                                         double* __restrict__ sums) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nsums) return;
+  double s = 0.0;
+  for (int r = 0; r < records; ++r) s += partial[(size_t)r * nsums + q];
+  sums[q] = s;
+}
+
+template <typename T, int B, int MOTION>
+void launch_sums_w(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
+  const Geometry& g = p->geo;
+  dim3 grid(chunks, g.K);
+  const WarpTaps<T>* warps = MOTION == kMotionTable ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr;
+  const double* recs = MOTION == kMotionAffine ? p->d_affine : nullptr;
+  if (p->d_dw)
+    hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)p->d_dw,
+                       g, warps, recs, p->d_col_map, p->d_row_map, tpc, d_part);
+  else
+    hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
+                       (const T*)nullptr, g, warps, recs, p->d_col_map, p->d_row_map, tpc, d_part);
+}
+
+template <typename T, int B>
+void launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
+  if (p->affine) launch_sums_w<T, B, kMotionAffine>(p, x, chunks, tpc, d_part, st);
+  else if (p->has_motion) launch_sums_w<T, B, kMotionTable>(p, x, chunks, tpc, d_part, st);
+  else launch_sums_w<T, B, kMotionNone>(p, x, chunks, tpc, d_part, st);
+}
+
+template <typename T>
+void launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
+  if (ksize == 1) launch_sums_m<T, 1>(p, x, chunks, tpc, d_part, st);
+  else if (ksize == 3) launch_sums_m<T, 3>(p, x, chunks, tpc, d_part, st);
+  else if (ksize == 5) launch_sums_m<T, 5>(p, x, chunks, tpc, d_part, st);
+  else launch_sums_m<T, 7>(p, x, chunks, tpc, d_part, st);
+}
+
+struct FitBuffers {
+  double *d_part = nullptr, *d_sums = nullptr, *h_sums = nullptr;
+  ~FitBuffers() {
+    if (d_part) (void)hipFree(d_part);
+    if (d_sums) (void)hipFree(d_sums);
+    if (h_sums) (void)hipHostFree(h_sums);
+  }
+};
+
+// E(h) = [h; -1]^T M [h; -1], M the (n + 1) x (n + 1) Gram (full, row-major)
+double energy(const std::vector<double>& M, int n, const double* h) {
+  const int n1 = n + 1;
+  double e = 0.0;
+  for (int i = 0; i < n1; ++i) {
+    const double vi = i < n ? h[i] : -1.0;
+    double row = 0.0;
+    for (int j = 0; j < n1; ++j) row += M[(size_t)i * n1 + j] * (j < n ? h[j] : -1.0);
+    e += vi * row;
+  }
+  return e;
+}
+
+}  // namespace
+
+}  // namespace srmap
+
+using namespace srmap;
+
+extern "C" void srmap_blur_fit_options_default(srmap_blur_fit_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_blur_fit_options);
+  o->ksize = 0;
+  o->sum_to_one = 1;
+  o->ridge = 0.0;
+  o->apply = 1;
+}
+
+extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                                     const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
+                                     double* normal_equations_out) {
+  if (!p || !x_dev) return SRMAP_EINVAL;
+  srmap_ctx* ctx = p->ctx;
+  srmap_blur_fit_options opt;
+  srmap_blur_fit_options_default(&opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_blur_fit_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
+    opt = *options;
+  }
+  const Geometry& g = p->geo;
+  const int ksize = opt.ksize == 0 ? g.b : opt.ksize;
+  if (ksize < 1 || ksize % 2 != 1) return set_error(ctx, SRMAP_EINVAL, "blur fit: ksize must be odd and >= 1 (got %d)", ksize);
+  if (ksize > kMaxCustomBlur)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "blur fit: ksize %d: at most %d x %d taps are fitted", ksize, kMaxCustomBlur, kMaxCustomBlur);
+  if (!(opt.ridge >= 0.0) || !std::isfinite(opt.ridge)) return set_error(ctx, SRMAP_EINVAL, "blur fit: ridge must be finite and >= 0");
+  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  int rc = problem_state_read(p, st);
+  if (rc) return rc;
+
+  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
+  const long long nobs = (long long)g.w * g.h * g.C;
+  const long long tiles = (nobs + kTile - 1) / kTile;
+  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
+  const int chunks = (int)((tiles + tpc - 1) / tpc);
+  const int records = g.K * chunks;
+  FitBuffers buf;
+  if (hipMalloc((void**)&buf.d_part, (size_t)records * P * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&buf.d_sums, (size_t)P * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&buf.h_sums, (size_t)P * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
+  }
+  if (p->dtype == SRMAP_F32) launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, buf.d_part, st);
+  else launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, buf.d_part, st);
+  SRMAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, buf.d_part, records, P, buf.d_sums);
+  SRMAP_HIP(ctx, hipGetLastError());
+  SRMAP_HIP(ctx, hipMemcpyAsync(buf.h_sums, buf.d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipStreamSynchronize(st));
+
+  // ---- the host solve ----
+  std::vector<double> M((size_t)n1 * n1);
+  for (int i = 0, q = 0; i < n1; ++i)
+    for (int j = i; j < n1; ++j, ++q) M[(size_t)i * n1 + j] = M[(size_t)j * n1 + i] = buf.h_sums[q];
+  // the kernel in force, zero-padded or centre-cropped to ksize
+  std::vector<double> hcur((size_t)n, 0.0);
+  const int off = (ksize - g.b) / 2;  // both odd: exact, negative when cropping
+  for (int a = 0; a < ksize; ++a)
+    for (int e = 0; e < ksize; ++e) {
+      const int sa = a - off, se = e - off;
+      if (sa >= 0 && sa < g.b && se >= 0 && se < g.b) hcur[(size_t)a * ksize + e] = p->blur2d[(size_t)sa * g.b + se];
+    }
+  const double e0 = energy(M, n, hcur.data());
+  double trace = 0.0;
+  for (int i = 0; i < n; ++i) trace += M[(size_t)i * n1 + i];
+  const double mu = opt.ridge * trace / n;
+  std::vector<double> A((size_t)n * n), Lc((size_t)n * n, 0.0), rhs((size_t)n), h((size_t)n), ones((size_t)n, 1.0), v((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) A[(size_t)i * n + j] = M[(size_t)i * n1 + j];
+    A[(size_t)i * n + i] += mu;
+    rhs[i] = M[(size_t)i * n1 + n] + mu * hcur[i];
+  }
+  double pmin = 0.0, pmax = 0.0, e1 = e0;
+  int status = 0;
+  if (!cholesky_factor_n(A.data(), n, Lc.data(), &pmin, &pmax)) {
+    status = 3;  // no texture, or every weight 0: the kernel stays
+    h = hcur;
+  } else {
+    cholesky_apply_n(Lc.data(), n, rhs.data(), h.data());
+    if (opt.sum_to_one) {
+      cholesky_apply_n(Lc.data(), n, ones.data(), v.data());
+      double su = 0.0, sv = 0.0;
+      for (int i = 0; i < n; ++i) { su += h[i]; sv += v[i]; }
+      const double lambda = (su - 1.0) / sv;
+      for (int i = 0; i < n; ++i) h[i] -= lambda * v[i];
+      // one more step along v for the rounding the first left in the constraint (|sum h - 1| <= 1e-14 is promised)
+      su = 0.0;
+      for (int i = 0; i < n; ++i) su += h[i];
+      const double rest = (su - 1.0) / sv;
+      for (int i = 0; i < n; ++i) h[i] -= rest * v[i];
+    }
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(h[i])) status = 3;
+    if (status == 3) h = hcur;
+    else e1 = energy(M, n, h.data());
+  }
+  if (status == 0 && opt.apply) {
+    rc = srmap_problem_set_blur_kernel(p, ksize, h.data());
+    if (rc) return rc;
+  }
+  if (taps_out) std::copy(h.begin(), h.end(), taps_out);
+  if (quality_out) {
+    quality_out[0] = e0; quality_out[1] = e1; quality_out[2] = pmin; quality_out[3] = pmax; quality_out[4] = status;
+  }
+  if (normal_equations_out) std::copy(buf.h_sums, buf.h_sums + P, normal_equations_out);
+  return SRMAP_OK;
+}
+
+extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srmap_blur_fit_options* options,
+                              double* taps_out, double* quality_out, double* normal_equations_out) {
+  if (!p || !x_host) return SRMAP_EINVAL;
+  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
+  if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
+    return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const size_t n = p->hr_count();
+  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
+  int rc = convert_upload(p, x_host, p->d_x, n, st);
+  if (rc) return rc;
+  return srmap_fit_blur_device(p, p->d_x, st, options, taps_out, quality_out, normal_equations_out);
+}

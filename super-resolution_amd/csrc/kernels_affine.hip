@@ -19,6 +19,7 @@
 
 #include "affine_map.hpp"
 #include "motion_fit_dev.hpp"
+#include "sample_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -42,22 +43,7 @@ __device__ __forceinline__ void affine_source(const double* __restrict__ m, int 
   *sy = affine_coord(m[3], m[4], m[5], (double)qx, (double)qy);
 }
 
-// (M_k x)(q): four-tap bilinear sample of `plane` at (sx, sy), zero outside the image
-template <typename T>
-__device__ __forceinline__ T affine_sample(const T* __restrict__ plane, int W, int H, double sx, double sy) {
-  if (!(sx > -1.0 && sx < (double)W && sy > -1.0 && sy < (double)H)) return T(0);  // no tap inside (NaN included)
-  const double x0d = __builtin_floor(sx), y0d = __builtin_floor(sy);
-  const double fx = sx - x0d, fy = sy - y0d;
-  const int sc = (int)x0d, sr = (int)y0d;
-  const T w0 = (T)((1.0 - fy) * (1.0 - fx)), w1 = (T)((1.0 - fy) * fx), w2 = (T)(fy * (1.0 - fx)), w3 = (T)(fy * fx);
-  const bool r0 = sr >= 0, r1 = sr + 1 < H;  // sr in [-1, H-1], sc in [-1, W-1]
-  const bool c0 = sc >= 0, c1 = sc + 1 < W;
-  const T v0 = (r0 && c0) ? plane[(size_t)sr * W + sc] : T(0);
-  const T v1 = (r0 && c1) ? plane[(size_t)sr * W + sc + 1] : T(0);
-  const T v2 = (r1 && c0) ? plane[(size_t)(sr + 1) * W + sc] : T(0);
-  const T v3 = (r1 && c1) ? plane[(size_t)(sr + 1) * W + sc + 1] : T(0);
-  return ((v0 * w0 + v1 * w1) + v2 * w2) + v3 * w3;
-}
+// (M_k x)(q), the four-tap sample at (sx, sy): affine_sample of sample_dev.hpp (shared with the blur fit)
 
 // weight of tap `p` along one axis for a sample at coordinate s: the forward kernel's (1 - f) / f, 0 for any other p
 __device__ __forceinline__ double affine_axis_weight(double s, int p) {

@@ -12,6 +12,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "sample_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -33,40 +34,7 @@ __device__ __forceinline__ double block_sum_256(double v, double* smem4) {
   return r;
 }
 
-template <typename T>
-__device__ __forceinline__ WarpTaps<T> identity_warp() {
-  WarpTaps<T> w;
-  w.ox = 0; w.oy = 0; w.ntaps = 1; w.fx = 0; w.ytab = nullptr;
-  w.w[0] = T(1); w.w[1] = T(0); w.w[2] = T(0); w.w[3] = T(0);
-  return w;
-}
-
-// warped_k(rr, cc) for (rr, cc) already known to be inside the image:
-// cv::warpAffine bilinear gather with zero border (motion_module.cpp:18-38).
-template <typename T>
-__device__ __forceinline__ T warp_sample(const T* __restrict__ plane, int W, int H,
-                                         const WarpTaps<T>& wt, int rr, int cc) {
-  int sr = rr + wt.oy;
-  const int sc = cc + wt.ox;
-  T w0 = wt.w[0], w1 = wt.w[1], w2 = wt.w[2], w3 = wt.w[3];
-  if (wt.ytab != nullptr) {
-    // per-row y table (rounding-tie shifts): BilinearTab_f's float32 products for this row's fraction index
-    const int Y = wt.ytab[rr];
-    sr = Y >> 5;
-    const float tx1 = (float)wt.fx * (1.f / 32), tx0 = 1.f - tx1;
-    const float ty1 = (float)(Y & 31) * (1.f / 32), ty0 = 1.f - ty1;
-    w0 = (T)(ty0 * tx0); w1 = (T)(ty0 * tx1); w2 = (T)(ty1 * tx0); w3 = (T)(ty1 * tx1);
-  } else if (wt.ntaps == 1) {
-    return (sr >= 0 && sr < H && sc >= 0 && sc < W) ? plane[(size_t)sr * W + sc] : T(0);
-  }
-  const bool r0 = sr >= 0 && sr < H, r1 = sr + 1 >= 0 && sr + 1 < H;
-  const bool c0 = sc >= 0 && sc < W, c1 = sc + 1 >= 0 && sc + 1 < W;
-  const T v0 = (r0 && c0) ? plane[(size_t)sr * W + sc] : T(0);
-  const T v1 = (r0 && c1) ? plane[(size_t)sr * W + sc + 1] : T(0);
-  const T v2 = (r1 && c0) ? plane[(size_t)(sr + 1) * W + sc] : T(0);
-  const T v3 = (r1 && c1) ? plane[(size_t)(sr + 1) * W + sc + 1] : T(0);
-  return ((v0 * w0 + v1 * w1) + v2 * w2) + v3 * w3;
-}
+// identity_warp / warp_sample: sample_dev.hpp (shared with the blur fit)
 
 // ---------------------------------------------------------------------------
 // Forward model A_k = D B M_k (image_model.cpp:86-91) at every LR pixel of

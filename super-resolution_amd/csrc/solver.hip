@@ -1400,6 +1400,8 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator (the weights are not split with the frames or rows): run the solve unsharded");
   if (p->affine && mode != SRMAP_SHARD_NONE)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "an affine motion model is not sharded over a communicator (only the direct family runs it): run the solve unsharded");
+  if (p->custom_blur && mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a free-form blur kernel is not sharded over a communicator (only the direct family runs it): run the solve unsharded");
   if (mode != SRMAP_SHARD_NONE && opt->split_channels)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
   if (mode == SRMAP_SHARD_ROWS &&
@@ -1585,6 +1587,8 @@ int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_sh
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator: evaluate unsharded");
   if (p->affine && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "an affine motion model is not sharded over a communicator: evaluate unsharded");
+  if (p->custom_blur && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a free-form blur kernel is not sharded over a communicator: evaluate unsharded");
   EvalOut out;
   int rc = shard_eval(p, comm, shard, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;

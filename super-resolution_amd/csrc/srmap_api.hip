@@ -506,6 +506,11 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
   for (int a = 0; a < g.b; ++a)
     for (int e = 0; e < g.b; ++e) p->blur2d_t[(size_t)a * g.b + e] = p->blur2d[(size_t)e * g.b + a];
 
+  p->created_b = g.b;
+  p->created_blur2d = p->blur2d;
+  p->created_blur2d_t = p->blur2d_t;
+  p->created_blur1d = p->blur1d;
+
   int rc = SRMAP_OK;
   p->has_motion = d->shifts_xy != nullptr;
   if (p->has_motion) {
@@ -619,6 +624,64 @@ int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) 
   }
   p->plan_gen++;
   if (ztile_plan(p)) ztile_preload(p);  // "not covered" while an affine motion is set
+  return SRMAP_OK;
+}
+
+// ---- free-form blur kernel (no reference counterpart; BlurModule builds a Gaussian only, blur_module.cpp:13-22) ----
+int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* taps) {
+  if (!p) return SRMAP_EINVAL;
+  if (taps) {
+    if (ksize < 1 || ksize % 2 != 1) return set_error(p->ctx, SRMAP_EINVAL, "blur kernel size must be odd and >= 1 (got %d)", ksize);
+    if (ksize > kMaxCustomBlur)
+      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "blur kernel size %d: a free-form kernel has at most %d x %d taps", ksize, kMaxCustomBlur, kMaxCustomBlur);
+    for (int i = 0; i < ksize * ksize; ++i)
+      if (!std::isfinite(taps[i])) return set_error(p->ctx, SRMAP_EINVAL, "blur kernel: tap %d is not finite", i);
+  }
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const int b = taps ? ksize : p->created_b;
+  std::vector<double> k2, k2t;
+  if (taps) {
+    k2.assign(taps, taps + (size_t)b * b);
+    k2t.resize(k2.size());
+    // the adjoint of a correlation is the correlation with the kernel flipped in BOTH axes (kernel.t(), the reference's
+    // form, is that only for a kernel symmetric under both)
+    for (int a = 0; a < b; ++a)
+      for (int e = 0; e < b; ++e) k2t[(size_t)a * b + e] = k2[(size_t)(b - 1 - a) * b + (b - 1 - e)];
+  } else {
+    k2 = p->created_blur2d;
+    k2t = p->created_blur2d_t;
+  }
+  // the new tables first: a failed allocation leaves the problem as it was
+  void *nb = nullptr, *nbt = nullptr;
+  int rc = p->dtype == SRMAP_F32 ? upload_array<float>(p, k2, &nb) : upload_array<double>(p, k2, &nb);
+  if (rc == SRMAP_OK) rc = p->dtype == SRMAP_F32 ? upload_array<float>(p, k2t, &nbt) : upload_array<double>(p, k2t, &nbt);
+  if (rc) {
+    if (nb) (void)hipFree(nb);
+    if (nbt) (void)hipFree(nbt);
+    return rc;
+  }
+  // evaluations in flight read the old tables: drain them before the buffers change
+  if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  if (p->d_blur) (void)hipFree(p->d_blur);
+  if (p->d_blur_t) (void)hipFree(p->d_blur_t);
+  p->d_blur = nb;
+  p->d_blur_t = nbt;
+  p->blur2d.swap(k2);
+  p->blur2d_t.swap(k2t);
+  p->blur1d = taps ? std::vector<double>((size_t)b, 0.0) : p->created_blur1d;  // a free-form kernel has no separable factor
+  p->geo.b = b;
+  p->geo.hb = (b - 1) / 2;
+  p->custom_blur = taps != nullptr;
+  p->plan_gen++;
+  if (ztile_plan(p)) ztile_preload(p);  // "not covered" while a free-form kernel is set
+  return SRMAP_OK;
+}
+
+int srmap_problem_get_blur_kernel(const srmap_problem* p, int* ksize, double* taps_out) {
+  if (!p) return SRMAP_EINVAL;
+  if (ksize) *ksize = p->geo.b;
+  if (taps_out) std::copy(p->blur2d.begin(), p->blur2d.end(), taps_out);
   return SRMAP_OK;
 }
 

@@ -15,6 +15,7 @@ namespace srmap {
 constexpr int kMaxRegularizers = 4;
 constexpr int kMaxBtvRange = 8;        // alpha^(i+j) table holds 2*range+1 entries
 constexpr int kMaxBlurTaps = 15 * 15;  // b*b taps kept in kernel-argument space
+constexpr int kMaxCustomBlur = 7;      // largest size of a free-form kernel (srmap_problem_set_blur_kernel, srmap_fit_blur)
 // Affine motion (srmap_problem_set_affine_motion, kernels_affine.hip): doubles per frame record -- [0..5] the inverse map
 // [ia ib itx; ic id ity], [6..11] the forward map [a b tx; c d ty], [12..13] the candidate radii of the transpose gather
 constexpr int kAffineRec = 16;
@@ -119,6 +120,12 @@ struct srmap_problem {
   std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
   std::vector<double> blur2d_t;
   std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
+  // free-form blur kernel (srmap_problem_set_blur_kernel): while set, geo.b / geo.hb and blur2d hold the caller's taps,
+  // blur2d_t their FLIP in both axes (the exact transpose of a correlation), the tile planner answers "not covered" and
+  // the direct family runs.  created_*: the blur the problem was created with, which NULL restores bit for bit
+  bool custom_blur = false;
+  int created_b = 1;
+  std::vector<double> created_blur2d, created_blur2d_t, created_blur1d;
   // device constants
   std::vector<int*> d_ytabs;      // per-row y tables of frames whose warpAffine y table is not uniform (owned)
   void* d_fwd_warps = nullptr;    // WarpTaps<T>[K]

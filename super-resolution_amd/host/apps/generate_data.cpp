@@ -20,7 +20,9 @@ int main(int argc, char** argv) {
       "  [--blur_radius=0] [--blur_sigma=0] [--noise_sigma=0] [--noise_seed=1]\n"
       "  [--downsampling_scale=2] [--number_of_frames=4]\n"
       "  not a reference flag: [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
-      "                        an error together with --motion_sequence_path)");
+      "                        an error together with --motion_sequence_path)\n"
+      "                        [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
+      "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)");
   const std::string input_image = flags.Str("input_image");
   const std::string output_dir = flags.Str("output_image_dir");
   std::string extension = flags.Str("output_image_extension");
@@ -28,6 +30,7 @@ int main(int argc, char** argv) {
   ImageModelParameters parameters;
   parameters.motion_sequence_path = flags.Str("motion_sequence_path");
   parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
+  parameters.blur_kernel_path = flags.Str("blur_kernel_path");  // not a reference flag
   parameters.blur_radius = flags.Int("blur_radius", 0);
   parameters.blur_sigma = flags.Double("blur_sigma", 0.0);
   parameters.noise_sigma = flags.Double("noise_sigma", 0.0);  // 0..255 units (additive_noise_module.cpp:25-26)

@@ -7,7 +7,9 @@
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
 // reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor are
 // --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
-// --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion).
+// --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion), nor
+// --blur_kernel_path (a free-form blur kernel, srmap_problem_set_blur_kernel) and --fit_blur_from / --fit_blur_ksize /
+// --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur).
 // Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
@@ -52,6 +54,12 @@ int main(int argc, char** argv) {
       "                       [--refine_motion_rounds=0] (after the solve, N times: re-fit the frame matrices to the estimate\n"
       "                       through the forward model, then solve again from it; 0 = off; works with every motion source)\n"
       "                       [--refine_motion_dof=6] (6: the full matrices; 2: translations only)\n"
+      "                       [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
+      "                       --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)\n"
+      "                       [--fit_blur_from=<HR image>] (before solving, fit the blur kernel to the frames from this KNOWN\n"
+      "                       high-resolution image of the scene -- a calibration pair -- and solve with it)\n"
+      "                       [--fit_blur_ksize=0] (size of the fitted kernel; 0 = the size of the blur in force)\n"
+      "                       [--save_blur_kernel_path=<file>] (the fitted kernel, in --blur_kernel_path's format)\n"
       "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
@@ -96,6 +104,11 @@ int main(int argc, char** argv) {
   // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
   const int refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
   const int refine_motion_dof = flags.Int("refine_motion_dof", 6);
+  // not reference flags: a free-form blur kernel (srmap_problem_set_blur_kernel) and its calibration fit (srmap_fit_blur)
+  model_parameters.blur_kernel_path = flags.Str("blur_kernel_path");
+  const std::string fit_blur_from = flags.Str("fit_blur_from");
+  const int fit_blur_ksize = flags.Int("fit_blur_ksize", 0);
+  const std::string save_blur_kernel_path = flags.Str("save_blur_kernel_path");
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
@@ -119,6 +132,14 @@ int main(int argc, char** argv) {
   }
   if (!save_motion_path.empty() && registration_name.empty() && refine_motion_rounds == 0) {
     std::fprintf(stderr, "ERROR: --save_motion_path needs --registration or --refine_motion_rounds.\n");
+    return 1;
+  }
+  if (fit_blur_ksize < 0 || (fit_blur_ksize != 0 && fit_blur_ksize % 2 != 1) || fit_blur_ksize > 7) {
+    std::fprintf(stderr, "ERROR: --fit_blur_ksize is 0 or an odd size up to 7.\n");
+    return 1;
+  }
+  if (fit_blur_from.empty() && (!save_blur_kernel_path.empty() || fit_blur_ksize != 0)) {
+    std::fprintf(stderr, "ERROR: --save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from.\n");
     return 1;
   }
   // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
@@ -249,6 +270,23 @@ int main(int argc, char** argv) {
       regularizer = tv;
     }
     solver.AddRegularizer(regularizer, regularization_parameter);
+  }
+
+  // --fit_blur_from: the calibration fit, before the solve, from a known HR image of what the frames show
+  if (!fit_blur_from.empty()) {
+    if (interpolate_color || spectral_pca) {
+      std::fprintf(stderr, "ERROR: --fit_blur_from works in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
+      return 1;
+    }
+    BlurFitOptions fit_options;
+    fit_options.ksize = fit_blur_ksize;
+    std::vector<double> quality;
+    const BlurKernel fitted = solver.FitBlur(util::LoadImage(fit_blur_from), fit_options, &quality);
+    std::printf("Fitted a %d x %d blur kernel: cost %g -> %g, status %g.\n", fitted.GetSize(), fitted.GetSize(), quality[0], quality[1], quality[4]);
+    if (!save_blur_kernel_path.empty() && !fitted.SaveToFile(save_blur_kernel_path)) {
+      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_blur_kernel_path.c_str());
+      return 1;
+    }
   }
 
   std::printf("Super-resolving from %zu images...\n", low_res_images.size());

@@ -3,7 +3,8 @@
 //   DegradationOperator  src/image_model/degradation_operator.h:17-57
 //   MotionModule         src/image_model/motion_module.{h,cpp}; also constructible from an AffineMotionSequence
 //                        (motion/affine_motion.h; no reference counterpart)
-//   BlurModule           src/image_model/blur_module.{h,cpp}
+//   BlurModule           src/image_model/blur_module.{h,cpp}; also constructible from a BlurKernel, a free-form PSF
+//                        (image_model/blur_kernel.h; no reference counterpart)
 //   DownsamplingModule   src/image_model/downsampling_module.{h,cpp}
 //   ImageModel, ImageModelParameters, CreateImageModel
 //                        src/image_model/image_model.{h,cpp}
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "image/image_data.h"
+#include "image_model/blur_kernel.h"
 #include "motion/affine_motion.h"
 #include "motion/motion_shift.h"
 #include "util/srmap_host.h"
@@ -97,18 +99,28 @@ class BlurModule : public DegradationOperator {
     if (blur_radius < 1 || !(sigma > 0.0) || blur_radius % 2 != 1)
       srmap_host::Fail("BlurModule: radius must be odd and >= 1, sigma > 0");
   }
+  // not in the reference: a free-form kernel (square, odd; the forward model correlates with it, the transpose with its
+  // flip in both axes -- the exact adjoint; srmap_problem_set_blur_kernel, include/srmap.h)
+  explicit BlurModule(const BlurKernel& kernel) : blur_radius_(kernel.GetSize()), sigma_(0.0), kernel_(kernel) {
+    if (kernel.Empty()) srmap_host::Fail("BlurModule: the blur kernel is empty");
+  }
   void ApplyToImage(ImageData* image_data, const int index) const override {
     srmap_host::RunChain(Chain(), image_data, 0, false);
   }
   void ApplyTransposeToImage(ImageData* image_data, const int index) const override {
     srmap_host::RunChain(Chain(), image_data, 0, true);
   }
-  void Describe(srmap_host::ChainParams* c) const override { c->blur_ksize = blur_radius_; c->blur_sigma = sigma_; }
+  void Describe(srmap_host::ChainParams* c) const override {
+    if (kernel_.Empty()) { c->blur_ksize = blur_radius_; c->blur_sigma = sigma_; c->blur_taps.clear(); c->blur_taps_ksize = 0; }
+    else { c->blur_ksize = 0; c->blur_sigma = 0.0; c->blur_taps = kernel_.GetTaps(); c->blur_taps_ksize = kernel_.GetSize(); }
+  }
+  bool IsFreeForm() const { return !kernel_.Empty(); }
 
  private:
   srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const int blur_radius_;
   const double sigma_;
+  const BlurKernel kernel_;
 };
 
 class DownsamplingModule : public DegradationOperator {
@@ -164,6 +176,10 @@ struct ImageModelParameters {
   // not in the reference: per-frame affine motion ("a b tx c d ty" per line); excludes motion_sequence(_path)
   std::string affine_motion_sequence_path = "";
   AffineMotionSequence affine_motion_sequence;
+  // not in the reference: a free-form blur kernel (text file: ksize, then ksize^2 taps); it replaces the Gaussian of
+  // blur_radius / blur_sigma
+  std::string blur_kernel_path = "";
+  BlurKernel blur_kernel;
   double noise_sigma = 0.0;
   uint64_t noise_seed = 0x5eedULL;  // not in the reference (cv::randn draws from OpenCV's global generator)
 };
@@ -189,7 +205,11 @@ class ImageModel {
       if (seq.GetNumMotionShifts() == 0) seq.LoadSequenceFromFile(parameters.motion_sequence_path);
       model.AddDegradationOperator(std::make_shared<MotionModule>(seq));
     }
-    if (parameters.blur_radius > 0 && parameters.blur_sigma > 0.0)
+    if (!parameters.blur_kernel_path.empty() || !parameters.blur_kernel.Empty()) {
+      BlurKernel kernel = parameters.blur_kernel;
+      if (kernel.Empty()) kernel.LoadFromFile(parameters.blur_kernel_path);
+      model.AddDegradationOperator(std::make_shared<BlurModule>(kernel));
+    } else if (parameters.blur_radius > 0 && parameters.blur_sigma > 0.0)
       model.AddDegradationOperator(std::make_shared<BlurModule>(parameters.blur_radius, parameters.blur_sigma));
     model.AddDegradationOperator(std::make_shared<DownsamplingModule>(parameters.scale));
     if (parameters.noise_sigma > 0.0)  // image_model.cpp:53-58

@@ -7,7 +7,8 @@
 // L-BFGS (minlbfgs, num_lbfgs_hessian_corrections pairs), chosen as in
 // irls_map_solver.cpp:97-113.  Analytical differentiation only: the reference's
 // numeric-difference variant is a test-only alternative outside the path.
-// Not in the reference: RefineMotion / SolveJoint, the joint motion refinement of include/srmap.h (srmap_refine_motion).
+// Not in the reference: RefineMotion / SolveJoint, the joint motion refinement of include/srmap.h (srmap_refine_motion),
+// and FitBlur, the calibration fit of the blur kernel (srmap_fit_blur).
 #pragma once
 #include <cmath>
 #include <iostream>
@@ -79,6 +80,13 @@ struct MotionRefinementOptions {
   int max_iterations = 30;        // trial passes per frame after the initial pass
   double step_tolerance = 1.0e-4; // HR px at the image corners
   double initial_damping = 1.0e-3;
+};
+
+// Options of IRLSMapSolver::FitBlur (srmap_blur_fit_options, include/srmap.h).  Not in the reference.
+struct BlurFitOptions {
+  int ksize = 0;           // 0: the size of the solver's current kernel
+  bool sum_to_one = true;
+  double ridge = 0.0;
 };
 
 class Solver {
@@ -242,6 +250,30 @@ class IRLSMapSolver : public MapSolver {
     }
     if (quality) *quality = q;
     return AffineMotionSequence(motions);
+  }
+  // Calibration fit of the blur kernel (srmap_fit_blur; not in the reference): the taps that best explain the solver's
+  // observations from the KNOWN high-resolution image `hr` under the solver's motion and data weights, INSTALLED as the
+  // solver's blur (later solves and ComputeAllTerms use them).  quality (optional): E at the kernel in force, E at the fit,
+  // smallest / largest pivot, status (3: no texture -- the kernel stays and is returned).
+  BlurKernel FitBlur(const ImageData& hr, const BlurFitOptions& options = BlurFitOptions(), std::vector<double>* quality = nullptr) {
+    if (hr.GetNumChannels() != GetNumChannels() || hr.GetImageSize() != GetImageSize())
+      srmap_host::Fail("the high-resolution image does not match the HR geometry");
+    srmap_blur_fit_options o;
+    srmap_blur_fit_options_default(&o);
+    o.ksize = options.ksize;
+    o.sum_to_one = options.sum_to_one ? 1 : 0;
+    o.ridge = options.ridge;
+    o.apply = 1;
+    int ksize = options.ksize;
+    if (ksize == 0) srmap_host::Check(srmap_problem_get_blur_kernel(problem_.get(), &ksize, nullptr), "srmap_problem_get_blur_kernel");
+    const std::vector<double> x = hr.ToPlanar();
+    std::vector<double> taps(static_cast<size_t>(ksize > 0 ? ksize : 1) * (ksize > 0 ? ksize : 1)), q(5);
+    srmap_host::Check(srmap_fit_blur(problem_.get(), x.data(), &o, taps.data(), q.data(), nullptr), "srmap_fit_blur");
+    if (IsVerbose())
+      std::cout << "Blur fit (" << ksize << " x " << ksize << "): cost " << q[0] << " -> " << q[1] << ", pivots " << q[2] << " ... " << q[3]
+                << ", status " << q[4] << std::endl;
+    if (quality) *quality = q;
+    return BlurKernel(ksize, taps);
   }
   // Solve, then `rounds` times (RefineMotion at the current estimate, Solve warm-started from it).  motion (optional)
   // receives the final matrices (untouched when rounds == 0).  Not in the reference.

@@ -45,7 +45,7 @@ struct ProblemDeleter {
 };
 using ProblemPtr = std::unique_ptr<srmap_problem, ProblemDeleter>;
 
-// Parameters of one operator chain  D(scale) . B(ksize, sigma) . M(shifts).
+// Parameters of one operator chain  D(scale) . B(ksize, sigma | free-form taps) . M(shifts | matrices).
 struct ChainParams {
   int scale = 1;
   std::vector<double> shifts_xy;  // empty = no translational MotionModule
@@ -53,6 +53,8 @@ struct ChainParams {
   int frames = 1;
   int blur_ksize = 0;
   double blur_sigma = 0.0;
+  std::vector<double> blur_taps;  // blur_taps_ksize^2 taps of a free-form kernel (then blur_ksize / blur_sigma are unused); empty = the Gaussian
+  int blur_taps_ksize = 0;
   bool HasMotion() const { return !shifts_xy.empty() || !affine_2x3.empty(); }
   int NumMotions() const { return static_cast<int>(affine_2x3.empty() ? shifts_xy.size() / 2 : affine_2x3.size() / 6); }
   // solvers: n observations need at least n motions; the rest is dropped
@@ -69,13 +71,15 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
   d.frames = c.HasMotion() ? c.NumMotions() : c.frames;
   d.scale = c.scale;
   d.shifts_xy = c.shifts_xy.empty() ? nullptr : c.shifts_xy.data();
-  d.blur_ksize = c.blur_ksize; d.blur_sigma = c.blur_sigma;
+  d.blur_ksize = c.blur_taps.empty() ? c.blur_ksize : 0; d.blur_sigma = c.blur_taps.empty() ? c.blur_sigma : 0.0;
   d.dtype = SRMAP_F64;  // the reference computes in double
   srmap_problem* p = nullptr;
   Check(srmap_problem_create(Context(), &d, &p), "srmap_problem_create");
   ProblemPtr problem(p);
   if (!c.affine_2x3.empty())
     Check(srmap_problem_set_affine_motion(p, c.affine_2x3.data()), "srmap_problem_set_affine_motion");
+  if (!c.blur_taps.empty())
+    Check(srmap_problem_set_blur_kernel(p, c.blur_taps_ksize, c.blur_taps.data()), "srmap_problem_set_blur_kernel");
   return problem;
 }
 

@@ -57,6 +57,10 @@ class MotionRefinementOptions(C.Structure):
                 ("initial_damping", C.c_double), ("apply", C.c_int), ("initial_affine_2x3", c_double_p)]
 
 
+class BlurFitOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("ksize", C.c_int), ("sum_to_one", C.c_int), ("ridge", C.c_double), ("apply", C.c_int)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -86,6 +90,11 @@ _SIGNATURES = [
     ("srmap_problem_set_impl", C.c_int, [C.c_void_p, C.c_int]),
     ("srmap_problem_set_solver", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("srmap_problem_set_affine_motion", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_problem_set_blur_kernel", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    ("srmap_problem_get_blur_kernel", C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_double_p]),
+    ("srmap_blur_fit_options_default", None, [C.c_void_p]),
+    ("srmap_fit_blur", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_fit_blur_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_problem_lr_size", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("srmap_set_observations", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_active_impl", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
@@ -313,6 +322,49 @@ class Problem:
             a, pa = _d(matrices)
             assert a.size == self.K * 6, (a.shape, self.K)
             self.ctx.check(load().srmap_problem_set_affine_motion(self._h, pa))
+
+    def set_blur_kernel(self, taps):
+        """Free-form blur kernel [ksize][ksize] (odd, 1...7; the forward model correlates with it, the adjoint is its flip in
+        both axes).  None restores the blur the problem was created with."""
+        if taps is None:
+            self.ctx.check(load().srmap_problem_set_blur_kernel(self._h, 0, None))
+        else:
+            a, pa = _d(taps)
+            assert a.ndim == 2 and a.shape[0] == a.shape[1], a.shape
+            self.ctx.check(load().srmap_problem_set_blur_kernel(self._h, a.shape[0], pa))
+
+    def blur_kernel(self):
+        """The blur in force, [ksize][ksize] ([[1]] without a blur)."""
+        k = C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_blur_kernel(self._h, C.byref(k), None))
+        out = np.empty((k.value, k.value))
+        self.ctx.check(load().srmap_problem_get_blur_kernel(self._h, C.byref(k), out.ctypes.data_as(c_double_p)))
+        return out
+
+    def fit_blur(self, x, ksize=None, sum_to_one=True, ridge=0.0, apply=True, stream=None, struct_size=None):
+        """srmap_fit_blur: the ksize x ksize taps that best explain the observations from the KNOWN HR image x (a host array
+        [C][H][W], or a device tensor of the problem's dtype, read on `stream`).  ksize None = the size of the kernel in
+        force.  Returns (taps [ksize][ksize], quality [5] = E at the kernel in force, E at the fit, smallest / largest pivot,
+        status, sums = the upper triangle of the Gram of [s_0 ... s_{n-1}, y]).  apply installs the fit as set_blur_kernel
+        would.  struct_size overrides the options' size field (tests)."""
+        o = BlurFitOptions()
+        load().srmap_blur_fit_options_default(C.byref(o))
+        o.ksize, o.sum_to_one, o.ridge, o.apply = (0 if ksize is None else ksize), (1 if sum_to_one else 0), ridge, (1 if apply else 0)
+        if struct_size is not None:
+            o.struct_size = struct_size
+        kk = ksize if ksize else self.blur_kernel().shape[0]
+        n = max(kk, 1) ** 2
+        taps, q, ne = np.zeros(n), np.zeros(5), np.zeros((n + 1) * (n + 2) // 2)
+        tail = (C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
+        if hasattr(x, "data_ptr"):
+            assert x.numel() == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_blur_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
+        else:
+            a, pa = _d(x)
+            assert a.size == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_blur(self._h, pa, *tail))
+        k = int(round(np.sqrt(n)))
+        return taps.reshape(k, k), q, ne
 
     def set_cost_rows(self, hr_row0, hr_row1):
         """Row-band sharding: count only the cost terms of HR rows [hr_row0, hr_row1)."""
