@@ -2,7 +2,7 @@
 //
 // linminnormalized (alglibinternal.cpp:12165-12196) scales the direction by s1 = 1 / max|dn|, then by
 // s2 = 1 / sqrt(sum (dn s1)^2); the sum is taken as (dn.dn) * s1^2 from the pass that produced dn.  Every consumer of the
-// normalised direction -- the pass that stores it (solver.hip k_normalize), the evaluation that forms a trial point from
+// normalised direction -- the pass that stores it (solver_passes.hip k_normalize), the evaluation that forms a trial point from
 // the unnormalised direction directly (kernels_ztile.hip, fold_norms) and the host's step scaling (run_cg) -- derives the
 // two factors from the reduced norms with THESE IEEE operations and applies them with norm_elem: the same bits wherever
 // d_i is formed.

@@ -19,6 +19,7 @@
 
 #include <vector>
 
+#include "reduce_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -36,8 +37,7 @@ __global__ __launch_bounds__(256) void k_row_means(const double* __restrict__ in
   const int r = blockIdx.x;
   double s = 0.0;
   for (size_t j = threadIdx.x; j < count; j += 256) s += in[(size_t)r * n + first + j * stride];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  s = wave_sum(s);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) red[wid] = s;
   __syncthreads();

@@ -96,7 +96,7 @@ struct srmap_comm {
   srmap_host_sendrecv_fn sr = nullptr;
   void* user = nullptr;
   void* h_send = nullptr; void* h_recv = nullptr; size_t h_cap = 0;  // pinned staging (host backend)
-  // row shards: the halo exchange runs on this side stream, under the tiles that read no halo row (solver.hip)
+  // row shards: the halo exchange runs on this side stream, under the tiles that read no halo row (shard_eval.hip)
   hipStream_t side = nullptr;
   hipEvent_t ev_x = nullptr, ev_halo = nullptr;
   int overlap = -1;  // row shards: halo exchange under the interior tile rows; -1 = backend default (srmap_comm_set_overlap)

@@ -1,5 +1,5 @@
-// comm.hpp -- internal interface of the communicator (comm.hip) used by the
-// sharded evaluation and solver.
+// comm.hpp -- internal interface of the communicator (comm.hip) and of the sharded
+// evaluation over it (shard_eval.hip), used by the solver.
 #pragma once
 #include "srmap_internal.hpp"
 
@@ -24,6 +24,12 @@ int comm_exchange2(srmap_comm* c, const void* const* send_a, void* const* recv_a
                    int nseg, int dtype, hipStream_t st);
 // Gradient and cost summed over the ranks of `c` in one RCCL group.
 int comm_allreduce_grad_cost(srmap_comm* c, void* g, size_t count, int dtype, double* cost, hipStream_t st);
+
+// The shard mode in force: the description's, or SRMAP_SHARD_NONE without a communicator of more than one rank.
+int shard_mode(const srmap_comm* c, const srmap_shard_desc* sd);
+// What is not sharded over a communicator -- data weights / a Huber loss, an affine motion model, a free-form blur kernel --
+// refused before any collective; `what` ("solve" or "evaluate") words the advice.  SRMAP_OK when mode is SRMAP_SHARD_NONE.
+int refuse_sharded(srmap_problem* p, int mode, const char* what);
 
 // Halo refresh of x for the shard (rows: boundary rows with the two row neighbours; channels: one plane with each
 // channel neighbour when the problem carries halo planes).  x is this rank's [C][H][W] device buffer.

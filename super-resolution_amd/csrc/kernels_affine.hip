@@ -26,17 +26,6 @@ namespace srmap {
 
 namespace {
 
-// Sum over a 256-thread block; result valid in thread 0 (k_forward_direct's order: the partials mean the same).
-__device__ __forceinline__ double block_sum_256_a(double v, double* smem4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) smem4[wid] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0) r = (smem4[0] + smem4[1]) + (smem4[2] + smem4[3]);
-  return r;
-}
-
 // s = F^-1(q) for the warped-image pixel q = (qx, qy): THE expression of both kernels (affine_coord, motion_fit_dev.hpp)
 __device__ __forceinline__ void affine_source(const double* __restrict__ m, int qx, int qy, double* sx, double* sy) {
   *sx = affine_coord(m[0], m[1], m[2], (double)qx, (double)qy);
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(256) void k_forward_affine(
     }
   }
   if (partials) {
-    const double s = block_sum_256_a(sq, red);
+    const double s = block_sum_256(sq, red);
     if (threadIdx.x == 0)
       partials[(size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = cost_scale * s;
   }

@@ -12,27 +12,11 @@
 #include <climits>
 #include <cstdint>
 
+#include "reduce_dev.hpp"
 #include "sample_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// Sum over a 256-thread block; result valid in thread 0.
-__device__ __forceinline__ double block_sum_256(double v, double* smem4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) smem4[wid] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0) r = (smem4[0] + smem4[1]) + (smem4[2] + smem4[3]);
-  return r;
-}
 
 // identity_warp / warp_sample: sample_dev.hpp (shared with the blur fit)
 

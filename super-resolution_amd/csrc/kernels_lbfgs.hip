@@ -18,52 +18,12 @@
 // workgroup is last.  f32 vectors accumulate in f64.
 #include <hip/hip_runtime.h>
 
+#include "reduce_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
 
 namespace {
-
-__device__ __forceinline__ double lb_wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double lb_wmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-
-// V consecutive elements as one request (V * sizeof(T) = 16 bytes, p aligned to it).  STREAM: non-temporal, for the
-// history and the previous gradient, which only these passes read: the evaluations' working set stays in the cache.
-template <typename T, int V, bool STREAM>
-__device__ __forceinline__ void lb_ld(const T* p, T (&out)[V]) {
-  typedef T __attribute__((ext_vector_type(V))) VT;
-  if constexpr (V == 1) {
-    out[0] = STREAM ? __builtin_nontemporal_load(p) : *p;
-  } else {
-    const VT v = STREAM ? __builtin_nontemporal_load(reinterpret_cast<const VT*>(p)) : *reinterpret_cast<const VT*>(p);
-#pragma unroll
-    for (int q = 0; q < V; ++q) out[q] = v[q];
-  }
-}
-template <typename T, int V, bool STREAM>
-__device__ __forceinline__ void lb_st(T* p, const T (&in)[V]) {
-  typedef T __attribute__((ext_vector_type(V))) VT;
-  if constexpr (V == 1) {
-    if (STREAM) __builtin_nontemporal_store(in[0], p); else *p = in[0];
-  } else {
-    VT v;
-#pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = in[q];
-    if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<VT*>(p)); else *reinterpret_cast<VT*>(p) = v;
-  }
-}
-
-__device__ __forceinline__ double combine4(const double (&r)[4], bool mx) {
-  return mx ? fmax(fmax(r[0], r[1]), fmax(r[2], r[3])) : (r[0] + r[1]) + (r[2] + r[3]);
-}
 
 // R sums (row 0 a max when MAX0) of the whole grid: workgroup partials to red.part[r * gridDim.x + block], then the
 // last workgroup to take a ticket adds them per row in workgroup order (thread i: i, i + 256, ...; then the wave and
@@ -76,7 +36,7 @@ __device__ __forceinline__ void ticket_reduce(double (&acc)[R], const LbfgsRed& 
   const unsigned nb = gridDim.x;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const double v = (MAX0 && r == 0) ? lb_wmax(acc[r]) : lb_wsum(acc[r]);
+    const double v = (MAX0 && r == 0) ? wave_max(acc[r]) : wave_sum(acc[r]);
     if (lane == 0) sm[r][wid] = v;
   }
   __syncthreads();
@@ -105,7 +65,7 @@ __device__ __forceinline__ void ticket_reduce(double (&acc)[R], const LbfgsRed& 
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const double t = (MAX0 && r == 0) ? lb_wmax(v[r]) : lb_wsum(v[r]);
+    const double t = (MAX0 && r == 0) ? wave_max(v[r]) : wave_sum(v[r]);
     if (lane == 0) tot[r][wid] = t;
   }
   __syncthreads();
@@ -133,17 +93,17 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(const T* __restrict__ x, c
   T* yp = Y + (size_t)p * n;
   for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
     T xv[V], xkv[V], gv[V], gkv[V], s[V], y[V];
-    lb_ld<T, V, false>(x + i, xv);
-    lb_ld<T, V, false>(xk + i, xkv);
-    lb_ld<T, V, false>(g + i, gv);
-    lb_ld<T, V, true>(gk + i, gkv);
+    ldv<T, V, false>(x + i, xv);
+    ldv<T, V, false>(xk + i, xkv);
+    ldv<T, V, false>(g + i, gv);
+    ldv<T, V, true>(gk + i, gkv);
 #pragma unroll
     for (int q = 0; q < V; ++q) {
       s[q] = -xkv[q] + xv[q];  // sk = -x_k; sk += x_{k+1}
       y[q] = -gkv[q] + gv[q];  // yk = -g_k; yk += g_{k+1}
     }
-    lb_st<T, V, true>(sp + i, s);
-    lb_st<T, V, true>(yp + i, y);
+    stv<T, V, true>(sp + i, s);
+    stv<T, V, true>(yp + i, y);
 #pragma unroll
     for (int q = 0; q < V; ++q) {
       acc[0] += (double)gv[q] * (double)gv[q];
@@ -156,8 +116,8 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(const T* __restrict__ x, c
 #pragma unroll
         for (int q = 0; q < V; ++q) { sj[q] = s[q]; yj[q] = y[q]; }
       } else {
-        lb_ld<T, V, true>(S + (size_t)j * n + i, sj);
-        lb_ld<T, V, true>(Y + (size_t)j * n + i, yj);
+        ldv<T, V, true>(S + (size_t)j * n + i, sj);
+        ldv<T, V, true>(Y + (size_t)j * n + i, yj);
       }
 #pragma unroll
       for (int q = 0; q < V; ++q) {
@@ -180,14 +140,14 @@ __global__ __launch_bounds__(256) void k_lbfgs_direction(T* __restrict__ dn, con
   for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
     T gv[V], v[V];
     double w[V];
-    lb_ld<T, V, false>(g + i, gv);
+    ldv<T, V, false>(g + i, gv);
 #pragma unroll
     for (int q = 0; q < V; ++q) w[q] = c.c[0] * (double)gv[q];
 #pragma unroll
     for (int j = 0; j < L; ++j) {
       T sj[V], yj[V];
-      lb_ld<T, V, true>(S + (size_t)j * n + i, sj);
-      lb_ld<T, V, true>(Y + (size_t)j * n + i, yj);
+      ldv<T, V, true>(S + (size_t)j * n + i, sj);
+      ldv<T, V, true>(Y + (size_t)j * n + i, yj);
 #pragma unroll
       for (int q = 0; q < V; ++q) {
         w[q] += c.c[1 + 2 * j] * (double)sj[q];
@@ -196,7 +156,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_direction(T* __restrict__ dn, con
     }
 #pragma unroll
     for (int q = 0; q < V; ++q) v[q] = (T)(-w[q]);
-    if (keep_dn) lb_st<T, V, false>(dn + i, v); else lb_st<T, V, true>(dn + i, v);
+    if (keep_dn) stv<T, V, false>(dn + i, v); else stv<T, V, true>(dn + i, v);
 #pragma unroll
     for (int q = 0; q < V; ++q) {
       const double d = (double)v[q];

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "cg_norm.hpp"
+#include "reduce_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -54,7 +55,7 @@ struct SpfArgs {
   int RLO, CLO, XR, XC;  // window: rows S*i0 + RLO .. + XR-1, cells j0 + CLO .. + XC-1
   double cost_scale;
   // FOLD instances (solver line search): the point is fold_xk + fold_stp * d, formed as the window is loaded -- the
-  // expression of solver.hip's k_axpy_out, the same contraction -- and the workgroup's OWN pixels (the S kLRH x S kCW
+  // expression of solver_passes.hip's k_axpy_out, the same contraction -- and the workgroup's OWN pixels (the S kLRH x S kCW
   // block of its LR cells) are written to `xout`: the tile kernel behind this launch, and the solver, find the trial
   // point there.  The window holds what the frames read, which need not include every own pixel (frames that all read
   // up-left of their LR pixel leave the block's last row out): FOLD instances walk the union of window and own block,
@@ -70,12 +71,6 @@ struct SpfArgs {
 };
 
 __device__ __forceinline__ int fdiv_rt(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // WEIGHTED (per-observation weights of the data term, srmap_set_data_weights / the Huber loss): the weight is requested
 // with the observation, the residual buffer receives w * r (what every gather downstream multiplies A^T onto) and the
@@ -234,7 +229,7 @@ __global__ __launch_bounds__(64 * kNW) void k_forward_sp(SpfArgs<T> A) {
       }
     }
   }
-  sq = wave_sum64(sq);
+  sq = wave_sum(sq);
   if (lane == 0) red[wv] = sq;
   __syncthreads();
   if (tid == 0) {

@@ -241,7 +241,7 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 || S 
 
   // WD: how elements of the direction are read (as given, or normalised on the fly from the unnormalised direction)
   const DirScale dsc = dir_scale(WD ? A.fold_norms : nullptr);
-  if (WD && fold) {  // trial point: x = xk + stp * d, element by element the expression of solver.hip's k_axpy_out
+  if (WD && fold) {  // trial point: x = xk + stp * d, element by element the expression of solver_passes.hip's k_axpy_out
     T* xout = A.fold_x + (size_t)ch * N;
 #pragma unroll
     for (int it = 0; it < ARI; ++it) {

@@ -4,14 +4,9 @@
 
 #include <hip/hip_runtime.h>
 
-namespace srmap {
+#include "reduce_dev.hpp"
 
-// sum over the 64 lanes of a wave; valid in lane 0
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
+namespace srmap {
 
 // m0 * x + (m1 * y + m2) with every operation rounded on its own: no contraction into fused multiply-adds, so that a host
 // restatement in plain double arithmetic (tests/affine_restatement.py) forms bit-identical coordinates and weights --

@@ -1,36 +1,19 @@
-// solver.hip -- IRLSMapSolver::Solve on the GPU (irls_map_solver.cpp:45-157,
-// 192-265) with either inner minimiser of the reference: L-BFGS (run_lbfgs, minlbfgs; its passes are in
-// kernels_lbfgs.hip) or the nonlinear CG the reference obtains from ALGLIB 3.10.0
-// (mincg, default settings: DY/HS hybrid beta, More'-Thuente line search,
-// libs/alglib/src/optimization.cpp:17137-17880, alglibinternal.cpp:12313-12632),
-// single-GPU or sharded over one rank per GPU.
+// solver.hip -- IRLSMapSolver::Solve on the GPU (irls_map_solver.cpp:45-157, 192-265): the IRLS outer loop
+// (solve_typed) around either inner minimiser of the reference, paced by the host -- L-BFGS (run_lbfgs, minlbfgs) or
+// the nonlinear CG the reference obtains from ALGLIB 3.10.0 (run_cg; mincg, default settings: DY/HS hybrid beta,
+// More'-Thuente line search, libs/alglib/src/optimization.cpp:17137-17880, alglibinternal.cpp:12313-12632) --
+// single-GPU or sharded over one rank per GPU, and the single-run trace entry points.
 //
-// Every n-vector (iterate, gradient, directions, line-search base point) lives
-// in HBM and is touched only by the kernels below.  The control flow (step
-// selection, stopping rules) runs on the host, in double, in ALGLIB's order of
-// operations, so that the trajectory follows the reference's up to reduction
-// order.  Per CG iteration the host waits for the device 2 + nfev times: once
-// for the direction's sums, once per trial point for (f, g.d), once for the beta
-// dot products; the n-vector work is two fused passes:
-//   k_direction      dn = -g + beta dk, max|dn|, dn.dn and g.dn -- from which the
-//                    host derives linminnormalized's two scale factors, g.d and
-//                    d.d (cg_norm.hpp): the normalised direction d = dn s1 s2 is
-//                    not re-summed, and on the tile path not even stored
-//   k_beta_dots      y = g - g_prev on the fly (the gradient buffers ping-pong,
-//                    mincg's yk vector is never stored), g.g, g.y; their
-//                    denominator y.dk = g.dk - g_prev.dk from sums already known
-// plus the trial points x = xk + stp d: formed by the evaluation itself as it
-// loads its window, from dk and the device-resident norms (tile kernel, un-sharded
-// solves: no n-vector pass per trial point); elsewhere k_normalize stores d (and
-// the first trial point) and k_axpy_out the later ones.  Each pass reduces its sums
-// in the SAME launch: every block publishes its partials as write-through
-// granules, the last block of the grid adds them in index order and hands the
-// results (and the arrival tag) to the host -- no one-block second kernel.
+// This file is the control flow only.  Every n-vector lives in HBM and is touched only by the passes
+// (solver_passes.hip, kernels_lbfgs.hip) and the evaluation (shard_eval.hip); DeviceCG owns the vectors, hands out the
+// arrival tags and queues the passes.  Step selection and the stopping rules run on the host, in double, in ALGLIB's
+// order of operations (solver_host.hpp: the More'-Thuente step, the L-BFGS recursion on coefficients), so that the
+// trajectory follows the reference's up to reduction order.  Per CG iteration the host waits for the device 2 + nfev
+// times: once for the direction's sums, once per trial point for (f, g.d), once for the beta dot products.
 //
-// Sharding.  Reductions run over the elements a rank OWNS (row band or channel
-// block; everything for frame shards) and are all-reduced through the
-// communicator (sum, and max for the max-norm), so every rank takes the same
-// decisions; x halos are refreshed before every evaluation (comm.hpp).
+// Sharding.  The passes reduce over the elements a rank OWNS and DeviceCG all-reduces the sums through the
+// communicator (sum, and max for the max-norm), so every rank takes the same decisions; x halos are refreshed before
+// every evaluation (comm.hpp).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -41,544 +24,10 @@
 
 #include "cg_norm.hpp"
 #include "comm.hpp"
+#include "solver_host.hpp"
+#include "solver_passes.hpp"
 
 namespace srmap {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-
-constexpr int kRedBlocks = 1024;
-
-// Which elements of an n-vector a rank owns: element range [e0, e1) (channel block) and, inside each H x W plane,
-// rows [r0, r1) (row band).  on == 0: everything.
-struct Owned {
-  size_t e0, e1;
-  int W, H, r0, r1;
-  int on;
-  __device__ __forceinline__ bool has(size_t i) const {
-    if (!on) return true;
-    if (i < e0 || i >= e1) return false;
-    const int row = (int)((i / (size_t)W) % (size_t)H);
-    return row >= r0 && row < r1;
-  }
-};
-
-// ---- one-launch reductions -------------------------------------------------------------------------------
-// A granule that has not been published yet holds this NaN pattern (both halves equal: hipMemsetD32 arms it).
-constexpr unsigned kArm32 = 0x7FF9ABCDu;
-constexpr unsigned long long kArm = ((unsigned long long)kArm32 << 32) | kArm32;
-__device__ __forceinline__ unsigned long long ld_dev(const unsigned long long* q) {
-  return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_dev(unsigned long long* q, unsigned long long v) {
-  __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// Where a pass leaves its reduced sums.  gran == nullptr: the two-launch scheme (block partials in `part`, k_finish
-// follows; sharded solves, whose sums go through an all-reduce first).  Otherwise the last block of the grid reduces:
-// out[0 .. rows) (device or host-mapped), the evaluation's cost forwarded from cost_src to out[rows], pub_n further
-// device scalars copied to pub_dst (host-mapped), then the arrival tag behind a system-scope fence.
-struct Fin {
-  unsigned long long* gran;
-  double* out;
-  const double* cost_src;
-  const double* pub_src;
-  double* pub_dst;
-  int pub_n;
-  double* tag_slot;
-  double tag;
-  double* timeout_flag;   // sticky device word: a reduction gave up waiting for a block (srmap_solve reports it)
-  double* timeout_host;   // the same event for the host at once (host-mapped word: wait_tag ends the solve on it)
-};
-
-// Block partials of up to 3 sums (row 0 a max when max0).  Two-launch scheme: part[k * gridDim.x + blockIdx.x].
-// One-launch scheme: granules, and the grid's last block adds all of them -- per thread i = tid, tid + 256, ... in
-// ascending order, then the wave and the four-wave combination of k_finish: the same additions in the same order as
-// the two-launch scheme.  Returns true in the one thread that wrote out[] (it still owes fin_tag()).
-__device__ __forceinline__ bool block_partials3(double s0, double s1, double s2, double* __restrict__ part, bool max0,
-                                                int rows, const Fin& fin, double* tot = nullptr) {
-  __shared__ double red[3][4];
-  s0 = max0 ? wmax(s0) : wsum(s0);
-  s1 = wsum(s1);
-  s2 = wsum(s2);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { red[0][wid] = s0; red[1][wid] = s1; red[2][wid] = s2; }
-  __syncthreads();
-  const int nbk = gridDim.x;
-  if (threadIdx.x < 3) {
-    const double* r = red[threadIdx.x];
-    const double v = (threadIdx.x == 0 && max0) ? fmax(fmax(r[0], r[1]), fmax(r[2], r[3])) : (r[0] + r[1]) + (r[2] + r[3]);
-    if (fin.gran == nullptr) part[(size_t)threadIdx.x * nbk + blockIdx.x] = v;
-    else if ((int)threadIdx.x < rows) st_dev(fin.gran + (size_t)threadIdx.x * nbk + blockIdx.x, (unsigned long long)__double_as_longlong(v));
-  }
-  if (fin.gran == nullptr || (int)blockIdx.x != nbk - 1) return false;
-  __syncthreads();  // red[] is reused below
-  double v0 = 0, v1 = 0, v2 = 0;
-  bool timed_out = false;
-  for (int i = threadIdx.x; i < nbk; i += 256) {
-    unsigned long long a0 = 0, a1 = 0, a2 = 0;  // +0.0 for absent rows
-    // bounded like the tile kernel's finisher (~2 s): a block that never publishes ends the pass with NaN sums (the
-    // host's stopping rules then end the solve) instead of hanging the stream
-    for (unsigned spins = 0;; ++spins) {
-      if (rows > 0) a0 = ld_dev(fin.gran + i);
-      if (rows > 1) a1 = ld_dev(fin.gran + (size_t)nbk + i);
-      if (rows > 2) a2 = ld_dev(fin.gran + (size_t)2 * nbk + i);
-      if (a0 != kArm && a1 != kArm && a2 != kArm) break;
-      if (spins > (1u << 22)) { timed_out = true; break; }
-      if (spins < 64) __builtin_amdgcn_s_sleep(1); else __builtin_amdgcn_s_sleep(16);
-    }
-    if (timed_out) continue;   // NOT re-armed: a block that arrives late must not publish into a fresh slot
-    if (rows > 0) st_dev(fin.gran + i, kArm);  // re-armed for the next pass
-    if (rows > 1) st_dev(fin.gran + (size_t)nbk + i, kArm);
-    if (rows > 2) st_dev(fin.gran + (size_t)2 * nbk + i, kArm);
-    const double d0 = __longlong_as_double((long long)a0), d1 = __longlong_as_double((long long)a1), d2 = __longlong_as_double((long long)a2);
-    v0 = max0 ? fmax(v0, d0) : v0 + d0;
-    v1 += d1;
-    v2 += d2;
-  }
-  v0 = max0 ? wmax(v0) : wsum(v0);
-  v1 = wsum(v1);
-  v2 = wsum(v2);
-  // a time-out anywhere in the block makes EVERY row NaN (fmax would drop a NaN partial of the max row): the host's
-  // stopping rules end the solve, srmap_solve reports SRMAP_EHIP (sticky word fin.timeout_flag) and re-initialises the granules
-  const bool any_to = __syncthreads_or(timed_out ? 1 : 0) != 0;
-  if (lane == 0) { red[0][wid] = v0; red[1][wid] = v1; red[2][wid] = v2; }
-  __syncthreads();
-  if (threadIdx.x != 0) return false;
-  if (any_to) {
-    const double qn = __builtin_nan("");
-    red[0][0] = qn; red[1][0] = qn; red[2][0] = qn;
-    if (fin.timeout_flag != nullptr) fin.timeout_flag[0] = 1.0;
-    if (fin.timeout_host != nullptr) *(volatile double*)fin.timeout_host = 1.0;
-  }
-  const double t0 = max0 ? fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]))
-                         : (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-  const double t1 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  const double t2 = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-  if (rows > 0) fin.out[0] = t0;
-  if (rows > 1) fin.out[1] = t1;
-  if (rows > 2) fin.out[2] = t2;
-  if (tot != nullptr) { tot[0] = t0; tot[1] = t1; tot[2] = t2; }  // the same sums for the finishing thread's own use
-  if (fin.cost_src != nullptr) fin.out[rows] = fin.cost_src[0];
-  for (int i = 0; i < fin.pub_n; ++i) fin.pub_dst[i] = fin.pub_src[i];
-  return true;
-}
-__device__ __forceinline__ void fin_tag(const Fin& fin) {
-  if (fin.tag_slot != nullptr) {
-    __threadfence_system();
-    *(volatile double*)fin.tag_slot = fin.tag;
-  }
-}
-
-// Cache policy of the n-vector passes.  What an EVALUATION touches -- x, the observations, the IRLS weights, the
-// direction d (its g.d), g -- and the line search's base point xk (read for every trial point) should survive in the
-// 256 MiB Infinity Cache from one evaluation to the next: 201 MB at cfg2.  The vectors only the CG update itself
-// streams (dn / dk, the previous gradient gp) are read and written NON-TEMPORAL so that they do not displace that set
-// (profiles/r03_solve_trace.txt: the evaluation ran 51.7 us inside the solve against 39.9 us alone).
-// V consecutive elements as one request (V * sizeof(T) <= 16 bytes, p aligned to it); STREAM = non-temporal
-template <typename T, int V, bool STREAM>
-__device__ __forceinline__ void ldv(const T* __restrict__ p, T (&out)[V]) {
-  typedef T __attribute__((ext_vector_type(V))) VT;
-  if (V == 1) { out[0] = STREAM ? __builtin_nontemporal_load(p) : *p; return; }
-  const VT v = STREAM ? __builtin_nontemporal_load(reinterpret_cast<const VT*>(p)) : *reinterpret_cast<const VT*>(p);
-#pragma unroll
-  for (int q = 0; q < V; ++q) out[q] = v[q];
-}
-template <typename T, int V, bool STREAM>
-__device__ __forceinline__ void stv(T* __restrict__ p, const T (&in)[V]) {
-  typedef T __attribute__((ext_vector_type(V))) VT;
-  if (V == 1) { if (STREAM) __builtin_nontemporal_store(in[0], p); else *p = in[0]; return; }
-  VT v;
-#pragma unroll
-  for (int q = 0; q < V; ++q) v[q] = in[q];
-  if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<VT*>(p)); else *reinterpret_cast<VT*>(p) = v;
-}
-
-// Every pass handles V consecutive elements per thread and step (V * sizeof(T) = 16 bytes per request when n is a
-// multiple of V, else V = 1): the element-wise results are the same bits either way, the dot-product partials are
-// summed in a different order (tests/test_gpu_parity.py: the PSNR bar of the ill-conditioned small cases follows the CPU
-// reference path's own sensitivity to a last-bit perturbation).
-
-// dn = -g + beta * dk ; sums: [0] max |dn| (owned), [1] dn.dn (owned), [2] g.dn (owned).  From these the host (and the
-// kernels that need the normalised direction d = dn s1 s2) derive s1, s2, g.d = (g.dn s1) s2 and d.d = dn.dn s1^2 s2^2:
-// the normalisation pass of rounds 1-4 (k_normalize_dots: five n-vector streams and a reduction per CG iteration, only
-// to re-sum g.d and d.d over the stored d) is gone from every path; where d is needed as a vector a plain scaling pass
-// (k_normalize) stores it.  norms_pub (host-mapped), when given, receives the three sums from the finishing thread
-// ahead of the tag.  keep_dn: dn is read again by the evaluations (trial points formed from dn): stored with the
-// default cache policy instead of non-temporal.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_direction(T* __restrict__ dn, const T* __restrict__ g,
-                                                  const T* __restrict__ dk, T beta, size_t n, Owned ow,
-                                                  double* __restrict__ part, Fin fin, const double* __restrict__ beta_dev,
-                                                  double* norms_pub, int keep_dn) {
-  // beta_dev: the beta the preceding k_beta_dots left on the device (the host queues this pass without waiting for it)
-  if (beta_dev != nullptr) beta = (T)beta_dev[0];
-  double mx = 0, ss = 0, gd = 0;
-  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
-    T gi[V], di[V], v[V];
-    ldv<T, V, false>(g + i, gi);
-    if (dk != nullptr) ldv<T, V, true>(dk + i, di);
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      v[q] = -gi[q];
-      if (dk != nullptr) v[q] += beta * di[q];
-    }
-    if (keep_dn) stv<T, V, false>(dn + i, v); else stv<T, V, true>(dn + i, v);
-#pragma unroll
-    for (int q = 0; q < V; ++q)
-      if (ow.has(i + q)) {
-        mx = fmax(mx, fabs((double)v[q])); ss += (double)v[q] * (double)v[q]; gd += (double)gi[q] * (double)v[q];
-      }
-  }
-  if (block_partials3(mx, ss, gd, part, true, 3, fin)) {
-    if (norms_pub != nullptr) { norms_pub[0] = fin.out[0]; norms_pub[1] = fin.out[1]; norms_pub[2] = fin.out[2]; }
-    fin_tag(fin);
-  }
-}
-
-// Second stage: rows (<= 3) x nb partials -> out[rows] in fixed order; row 0 is a max when max0.  extra_src, when
-// given, is one more device scalar (the cost of the evaluation) forwarded to out[rows].  When `tag_slot` is given
-// (host-mapped memory) the kernel finally stores `tag` there behind a system-scope fence: the host polls that word
-// instead of paying a stream synchronisation (tens of microseconds per wait on this runtime).
-__global__ __launch_bounds__(256) void k_finish(const double* __restrict__ part, int nb, int rows, int max0,
-                                               double* __restrict__ out, const double* __restrict__ extra_src,
-                                               double* tag_slot, double tag) {
-  __shared__ double red[3][4];
-  double v0 = 0, v1 = 0, v2 = 0;
-  // four partials per row and thread requested together (nb <= 1024: one round trip instead of four), added in the
-  // same order as before
-  constexpr int U = 4;
-  for (int base = threadIdx.x; base < nb; base += 256 * U) {
-    double a0[U], a1[U], a2[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = base + u * 256;
-      const bool in = i < nb;
-      a0[u] = (in && rows > 0) ? part[i] : 0.0;
-      a1[u] = (in && rows > 1) ? part[(size_t)nb + i] : 0.0;
-      a2[u] = (in && rows > 2) ? part[(size_t)2 * nb + i] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      v0 = max0 ? fmax(v0, a0[u]) : v0 + a0[u];
-      v1 += a1[u];
-      v2 += a2[u];
-    }
-  }
-  v0 = max0 ? wmax(v0) : wsum(v0);
-  v1 = wsum(v1);
-  v2 = wsum(v2);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { red[0][wid] = v0; red[1][wid] = v1; red[2][wid] = v2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (rows > 0) out[0] = max0 ? fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]))
-                                : (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    if (rows > 1) out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    if (rows > 2) out[2] = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-    if (extra_src != nullptr) out[rows] = extra_src[0];
-    if (tag_slot != nullptr) {
-      __threadfence_system();
-      *(volatile double*)tag_slot = tag;
-    }
-  }
-}
-
-// dst[0..n) = src[0..n) (device scalars -> host-mapped memory), then the tag (see k_finish)
-__global__ void k_publish(double* __restrict__ dst, const double* __restrict__ src, int n, double* tag_slot, double tag) {
-  if (threadIdx.x == 0) {
-    for (int i = 0; i < n; ++i) dst[i] = src[i];
-    __threadfence_system();
-    *(volatile double*)tag_slot = tag;
-  }
-}
-
-// d = (dn * s1) * s2 stored as a vector, for the paths whose evaluations read the normalised direction from memory
-// (sharded solves, the direct kernels, host-paced passes).  norms = device {max|dn|, dn.dn} (already all-reduced); every
-// thread derives the same two factors.  When the first step of the line search is known before this pass (ALGLIB's
-// lastgoodstep), its trial point x1 = xk + stp1 * d is written here as well: one pass over xk / x less per CG iteration
-// than a separate k_axpy_out (same expression, same rounding).
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_normalize(T* __restrict__ d, const T* __restrict__ dn, const double* __restrict__ norms,
-                                                  size_t n, const T* __restrict__ xk, T* __restrict__ x1, T stp1) {
-  const double mx = norms[0], ss = norms[1];
-  double s1, s2;
-  norm_factors(mx, ss, s1, s2);
-  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
-    T dv[V], xv[V], v[V];
-    ldv<T, V, true>(dn + i, dv);
-    if (x1 != nullptr) ldv<T, V, false>(xk + i, xv);
-#pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = norm_elem<T>(dv[q], mx, s1, s2);
-    stv<T, V, false>(d + i, v);
-    if (x1 != nullptr) {  // the line search's first trial point (k_axpy_out's expression)
-      T xn[V];
-#pragma unroll
-      for (int q = 0; q < V; ++q) xn[q] = xv[q] + stp1 * v[q];
-      stv<T, V, false>(x1 + i, xn);
-    }
-  }
-}
-
-// y = g - gp (mincg: yk = -g_k, then yk += g_{k+1}: the same rounding) ; sums: [0] g.g, [1] g.y   (the DY / HS betas,
-// optimization.cpp:17700-17760).  Their denominator vv = y.dk is not summed here: y.dk = g.dk - gp.dk, and both terms are
-// already known -- gp.dk is the g.dn the direction pass reduced, g.dk = (g.d) / (s1 s2) from the accepted trial
-// evaluation's g.d (the line search bounds |g.d| by 0.3 |gp.d|: no cancellation) -- so the pass reads two vectors
-// instead of three (dk is not touched).  vv comes as an argument.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_beta_dots(const T* __restrict__ gp, const T* __restrict__ g,
-                                                  size_t n, Owned ow, double* __restrict__ part, Fin fin,
-                                                  double* __restrict__ beta_dst, int restart, double vv,
-                                                  const T* __restrict__ dk_check) {
-  // dk_check (host-paced passes only): the denominator y.dk summed directly as well, row [2] -- the self-check of the
-  // derived vv (srmap_problem_selfcheck); the betas still use the derived one, so both pacing modes stay bit-equal
-  double b = 0, c = 0, e = 0;
-  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
-    T gv[V], pv[V], kv[V];
-    ldv<T, V, false>(g + i, gv);
-    ldv<T, V, true>(gp + i, pv);
-    if (dk_check != nullptr) ldv<T, V, true>(dk_check + i, kv);
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      if (!ow.has(i + q)) continue;
-      const T y = -pv[q] + gv[q];
-      b += (double)gv[q] * (double)gv[q]; c += (double)gv[q] * (double)y;
-      if (dk_check != nullptr) e += (double)y * (double)kv[q];
-    }
-  }
-  double tot[3];
-  if (block_partials3(b, c, e, part, false, dk_check != nullptr ? 3 : 2, fin, tot)) {
-    if (beta_dst != nullptr) {
-      // betak = max(0, min(betady, betahs)) exactly as run_cg forms it on the host (same IEEE divisions and compares):
-      // the direction pass queued behind this one reads it, the host never has to answer in between
-      const double bdy = tot[0] / vv, bhs = tot[1] / vv;
-      const double bm = bdy < bhs ? bdy : bhs;
-      double bk = 0.0 > bm ? 0.0 : bm;
-      if (restart) bk = 0.0;
-      beta_dst[0] = bk;
-    }
-    fin_tag(fin);
-  }
-}
-
-// partial of a.b over the owned elements: [0]
-template <typename T, int V>
-__global__ __launch_bounds__(256) void k_dot(const T* __restrict__ a, const T* __restrict__ b, size_t n, Owned ow,
-                                            double* __restrict__ part, Fin fin) {
-  double s = 0;
-  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; i < n; i += (size_t)gridDim.x * 256 * V) {
-    T av[V], bv[V];
-    ldv<T, V, false>(a + i, av);
-    ldv<T, V, false>(b + i, bv);
-#pragma unroll
-    for (int q = 0; q < V; ++q)
-      if (ow.has(i + q)) s += (double)av[q] * (double)bv[q];
-  }
-  if (block_partials3(s, 0.0, 0.0, part, false, 1, fin)) fin_tag(fin);
-}
-
-// dst = a + alpha * b
-template <typename T>
-__global__ void k_axpy_out(T* __restrict__ dst, const T* __restrict__ a, const T* __restrict__ b, T alpha, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = a[i] + alpha * b[i];
-}
-// the same, four elements per thread (16 / 32-byte requests; hipMalloc'ed vectors are aligned): element by element the
-// same expression, so the same bits
-template <typename T>
-__global__ __launch_bounds__(256) void k_axpy_out4(T* __restrict__ dst, const T* __restrict__ a, const T* __restrict__ b, T alpha,
-                                                  size_t n4) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  T va[4], vb[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { va[q] = a[4 * i + q]; vb[q] = b[4 * i + q]; }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dst[4 * i + q] = va[q] + alpha * vb[q];
-}
-template <typename T>
-__global__ void k_fill(T* __restrict__ d, T v, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) d[i] = v;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// sharded evaluation (comm.hpp)
-int shard_exchange_x(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, void* x_dev, hipStream_t st) {
-  if (!c || !sd || comm_world(c) <= 1) return SRMAP_OK;
-  const Geometry& g = p->geo;
-  const size_t N = (size_t)g.W * g.H, es = p->elem();
-  const int rank = comm_rank(c), world = comm_world(c);
-  const int up = rank > 0 ? rank - 1 : -1, down = rank + 1 < world ? rank + 1 : -1;
-  char* x = (char*)x_dev;
-  if (sd->mode == SRMAP_SHARD_ROWS) {
-    // a frame whose warpAffine y coordinate sits on a 1/32-px rounding tie carries a per-row table built from the row
-    // index of THIS problem (srmap_api.hip make_warp): a band problem would evaluate the tie at its local rows, not
-    // the joint image's
-    if (!p->d_ytabs.empty())
-      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "row shard: a sub-pixel shift on a 1/32-px rounding tie needs the joint image's row index; shard such problems by frames or channels");
-    const int hu = sd->own_row0, hd = g.H - sd->own_row1;  // my halo rows above / below
-    if ((up >= 0 && hu == 0) || (down >= 0 && hd == 0) || sd->send_down_rows > sd->own_row1 - sd->own_row0 ||
-        sd->send_up_rows > sd->own_row1 - sd->own_row0)
-      return set_error(p->ctx, SRMAP_EINVAL, "row shard: halo description inconsistent");
-    if ((up >= 0 && sd->send_up_rows <= 0) || (down >= 0 && sd->send_down_rows <= 0))
-      return set_error(p->ctx, SRMAP_EINVAL, "row shard: a neighbour exists but no rows are sent to it (it would wait for them)");
-    std::vector<const void*> sa(g.C), sb(g.C);
-    std::vector<void*> ra(g.C), rb(g.C);
-    for (int ch = 0; ch < g.C; ++ch) {
-      // downward traffic: my last owned rows -> lower neighbour's top halo; my top halo <- upper neighbour
-      sa[ch] = x + ((size_t)ch * N + (size_t)(sd->own_row1 - sd->send_down_rows) * g.W) * es;
-      ra[ch] = x + ((size_t)ch * N) * es;
-      // upward traffic: my first owned rows -> upper neighbour's bottom halo; my bottom halo <- lower neighbour
-      sb[ch] = x + ((size_t)ch * N + (size_t)sd->own_row0 * g.W) * es;
-      rb[ch] = x + ((size_t)ch * N + (size_t)sd->own_row1 * g.W) * es;
-    }
-    // both directions in ONE group (one launch on the stream)
-    return comm_exchange2(c, sa.data(), ra.data(), (size_t)sd->send_down_rows * g.W, (size_t)hu * g.W, sb.data(), rb.data(),
-                          (size_t)sd->send_up_rows * g.W, (size_t)hd * g.W, up, down, g.C, p->dtype, st);
-  }
-  if (sd->mode == SRMAP_SHARD_CHANNELS || sd->mode == SRMAP_SHARD_GRID) {
-    const bool lo = sd->own_ch0 > 0, hi = sd->own_ch1 < g.C;  // halo planes present (3-D TV coupling)
-    if (!lo && !hi) return SRMAP_OK;
-    // GRID: the channel neighbours are the ranks of the same frame group in the adjacent channel blocks
-    const int stride = sd->mode == SRMAP_SHARD_GRID ? (sd->frame_groups > 0 ? sd->frame_groups : 1) : 1;
-    const int cup = rank - stride >= 0 ? rank - stride : -1, cdown = rank + stride < world ? rank + stride : -1;
-    // downward: my last owned plane -> lower neighbour's low halo plane; my low halo <- upper neighbour
-    const void* s1 = x + (size_t)(sd->own_ch1 - 1) * N * es;
-    void* r1 = x + (size_t)(sd->own_ch0 - 1) * N * es;
-    // upward: my first owned plane -> upper neighbour's high halo plane; my high halo <- lower neighbour
-    const void* s2 = x + (size_t)sd->own_ch0 * N * es;
-    void* r2 = x + (size_t)sd->own_ch1 * N * es;
-    return comm_exchange2(c, &s1, &r1, hi ? N : 0, lo ? N : 0, &s2, &r2, lo ? N : 0, hi ? N : 0, lo ? cup : -1, hi ? cdown : -1, 1,
-                          p->dtype, st);
-  }
-  return SRMAP_OK;
-}
-
-int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, EvalReq req, EvalOut* out, unsigned terms,
-               void* x_dev, void* g_dev, hipStream_t st) {
-  const int mode = (c && sd && comm_world(c) > 1) ? sd->mode : SRMAP_SHARD_NONE;
-  if (mode == SRMAP_SHARD_NONE) return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);
-  const size_t N = (size_t)p->geo.W * p->geo.H, es = p->elem();
-  if (mode == SRMAP_SHARD_ROWS) {
-    // The halo rows of x travel on the communicator's side stream while the evaluation's stream runs the tile rows
-    // that read none of them; the boundary tile rows wait for the event (kernels_ztile.hip launch_z; paths without
-    // that split exchange first).  x is ready when `st` reaches this point; the next exchange cannot start before
-    // this evaluation (which reads the halos) is behind the next ev_x.
-    // Overlap only where it is both enabled on the communicator and SAFE: the caller's halo must be at least the tile
-    // kernel's reach (x rows 2 above / 3 below a tile row: blur transpose + regulariser window), otherwise an
-    // "interior" tile row would read a row the exchange is still writing.
-    const int hu = sd->own_row0, hd = p->geo.H - sd->own_row1;
-    constexpr int kReach = 4;
-    const bool overlap = comm_overlap(c) && ztile_overlaps_halo(p) && (hu == 0 || hu >= kReach) && (hd == 0 || hd >= kReach);
-    if (!overlap) {
-      int rc = shard_exchange_x(p, c, sd, x_dev, st);
-      if (rc) return rc;
-      return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);
-    }
-    struct Hook { srmap_problem* p; srmap_comm* c; const srmap_shard_desc* sd; void* x; hipStream_t side; hipEvent_t ev; bool called; };
-    hipStream_t side; hipEvent_t ev_x, ev_halo;
-    int rc = comm_side(c, &side, &ev_x, &ev_halo);
-    if (rc) return rc;
-    SRMAP_HIP(p->ctx, hipEventRecord(ev_x, st));
-    SRMAP_HIP(p->ctx, hipStreamWaitEvent(side, ev_x, 0));
-    Hook h{p, c, sd, x_dev, side, ev_halo, false};
-    req.overlap.fn = [](void* a) -> int {
-      Hook* k = static_cast<Hook*>(a);
-      k->called = true;
-      int r = shard_exchange_x(k->p, k->c, k->sd, k->x, k->side);
-      if (r) return r;
-      SRMAP_HIP(k->p->ctx, hipEventRecord(k->ev, k->side));
-      return SRMAP_OK;
-    };
-    req.overlap.arg = &h;
-    req.overlap.event = ev_halo;
-    req.overlap.top = hu;
-    req.overlap.bot = hd;
-    rc = eval_dispatch(p, req, out, terms, x_dev, g_dev, st);  // cost rows were set on the problem
-    // An evaluation that failed before it reached the hook has not posted this rank's half of the exchange: post it
-    // now, so that the neighbours' receives complete and they see an error code instead of a hang.
-    if (!h.called) {
-      const int rx = shard_exchange_x(p, c, sd, x_dev, side);
-      if (rc == SRMAP_OK) rc = rx;
-    }
-    return rc;
-  }
-  int rc = shard_exchange_x(p, c, sd, x_dev, st);
-  if (rc) return rc;
-  if (mode == SRMAP_SHARD_FRAMES) {
-    // Every rank adds its frames' data term.  The regulariser is evaluated once over the ranks: split by row band
-    // (whole tile rows, balanced) when the tile kernel alone produces it -- at cfg2-class mixes it is more than half of
-    // the arithmetic, so leaving it to one rank would make that rank the critical path -- else on reg_rank.
-    const int rank = comm_rank(c), world = comm_world(c);
-    unsigned t = terms;
-    // The split is a COLLECTIVE decision: a rank whose own frame subset has no tile plan (a shift on a 1/32-px rounding
-    // tie, a per-rank SRMAP_IMPL_DIRECT, ...) cannot evaluate a band, and if it went its own way the regulariser would
-    // be counted twice or not at all.  The ranks agree once (minimum of their flags over the communicator; cached on
-    // the problem until its plan generation -- bumped by every re-plan and every srmap_problem_set_impl --, term set or
-    // communicator changes); any rank that cannot band-split sends everybody to reg_rank.  The agreement is itself a
-    // collective: under frame sharding srmap_problem_set_impl and the regulariser calls are COLLECTIVE too (every rank
-    // makes them in the same order between the same evaluations; include/srmap.h), or one rank would enter it alone.
-    const bool mine = ztile_reg_band_ok(p, terms);
-    if (p->band_comm != (const void*)c || p->band_terms != terms || p->band_gen != p->plan_gen) {
-      double flag = mine ? 0.0 : 1.0;  // max over the ranks of "I cannot" == 0  <=>  every rank can
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_cost + 7, &flag, sizeof(double), hipMemcpyHostToDevice, st));
-      rc = comm_allreduce(c, p->d_cost + 7, 1, SRMAP_F64, 1, st);
-      if (rc) return rc;
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(&flag, p->d_cost + 7, sizeof(double), hipMemcpyDeviceToHost, st));
-      SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-      p->band_all = flag == 0.0;
-      p->band_comm = c; p->band_terms = terms; p->band_gen = p->plan_gen;
-    }
-    const bool band = mine && p->band_all;
-    if (band) {
-      const int tiles = (p->geo.H + 7) / 8, per = (tiles + world - 1) / world;
-      req.rr0 = rank * per * 8;
-      req.rr1 = (rank + 1) * per * 8;
-    } else if (rank != sd->reg_rank) {
-      t = terms & SRMAP_TERM_DATA;
-    }
-    if (t == 0) {
-      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
-      if (g_dev) SRMAP_HIP(p->ctx, hipMemsetAsync(g_dev, 0, p->hr_count() * es, st));
-    } else {
-      rc = eval_dispatch(p, req, out, t, x_dev, g_dev, st);
-    }
-    if (rc) return rc;
-    // the north-star's gradient all-reduce, with the cost in the same group (one launch)
-    return comm_allreduce_grad_cost(c, g_dev, g_dev ? p->hr_count() : 0, p->dtype, p->d_cost, st);
-  }
-  if (mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
-    const int fgs = (mode == SRMAP_SHARD_GRID && sd->frame_groups > 1) ? sd->frame_groups : 1;
-    const int fg = comm_rank(c) % fgs;
-    // GRID: the regulariser terms of a channel block are evaluated once, by its frame group 0
-    const unsigned t = (fg == 0) ? terms : (terms & SRMAP_TERM_DATA);
-    req.view.c0 = sd->own_ch0; req.view.C = sd->own_ch1 - sd->own_ch0; req.view.coupled = true;
-    const size_t cnt = (size_t)req.view.C * N;
-    char* gown = g_dev ? (char*)g_dev + (size_t)sd->own_ch0 * N * es : nullptr;
-    if (t == 0) {
-      rc = SRMAP_OK;
-      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
-      if (gown) SRMAP_HIP(p->ctx, hipMemsetAsync(gown, 0, cnt * es, st));
-    } else {
-      rc = eval_dispatch(p, req, out, t, (char*)x_dev + (size_t)sd->own_ch0 * N * es, gown, st);
-    }
-    if (rc) return rc;
-    if (fgs > 1 && gown) {  // sum of the frame groups' data-term gradients of this channel block
-      if (!sd->frame_comm) return set_error(p->ctx, SRMAP_EINVAL, "grid shard: frame_comm missing");
-      rc = comm_allreduce(sd->frame_comm, gown, cnt, p->dtype, 0, st);
-    }
-    return rc;
-  }
-  return eval_dispatch(p, req, out, terms, x_dev, g_dev, st);  // rows: cost rows were set on the problem
-}
 
 // ---------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -646,9 +95,6 @@ struct DeviceCG {
     return SRMAP_OK;
   }
 
-  static constexpr int kVec = 16 / (int)sizeof(T);  // elements per 16-byte request of the n-vector passes
-  bool vec() const { return n % kVec == 0; }           // (the vectors are hipMalloc'ed: aligned)
-  unsigned blocks() const { return (unsigned)((n + 255) / 256); }
   int nb() const { size_t b = (n + 255) / 256; return (int)(b < (size_t)kRedBlocks ? b : kRedBlocks); }
 
   int alloc() {
@@ -720,8 +166,7 @@ struct DeviceCG {
     const int cnt = rows + (with_cost ? 1 : 0);
     if (!fused()) {
       tag += 1.0;
-      hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, part, nb(), rows, max0 ? 1 : 0, dscal,
-                         with_cost ? (const double*)p->d_cost : (const double*)nullptr, (double*)nullptr, 0.0);
+      launch_finish(part, nb(), rows, max0 ? 1 : 0, dscal, with_cost ? (const double*)p->d_cost : nullptr, nullptr, 0.0, st);
       int rc = SRMAP_OK;
       if (max0) {
         rc = comm_allreduce(comm, dscal, 1, SRMAP_F64, 1, st);
@@ -732,8 +177,8 @@ struct DeviceCG {
       }
       if (rc) return rc;
       if (extra_n > 0)
-        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs + 8, (const double*)(dscal + 4), extra_n, (double*)(hs + 14), 0.0);
-      hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs, (const double*)dscal, cnt, hs + 15, tag);
+        launch_publish(hs + 8, dscal + 4, extra_n, hs + 14, 0.0, st);
+      launch_publish(hs, dscal, cnt, hs + 15, tag, st);
     }
     SRMAP_HIP(p->ctx, hipGetLastError());
     int rc = wait_tag();
@@ -750,7 +195,7 @@ struct DeviceCG {
   bool fold_enabled = true;   // srmap_irls_options::host_paced_passes also forms every trial point by its own pass (the A/B of the fold)
   int evaluate(const T* dir = nullptr, T* at = nullptr, const T* fold_xk = nullptr, double fold_stp = 0.0) {  // at: the point (default x)
     evaluations++;
-    const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;
+    const int mode = shard_mode(comm, shard);
     EvalReq req;
     req.view = view;
     req.dvec = (mode == SRMAP_SHARD_FRAMES || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) ? nullptr : dir;
@@ -787,8 +232,7 @@ struct DeviceCG {
   // f and g.d of the evaluation just made, with one wait: out[0] = g.d, out[1] = f
   int fetch_f_gd(double* out) {
     if (!gd_valid) {
-      if (vec()) hipLaunchKernelGGL((k_dot<T, kVec>), dim3(nb()), dim3(256), 0, st, (const T*)g, (const T*)d, n, ow, part, fin_host(true));
-      else hipLaunchKernelGGL((k_dot<T, 1>), dim3(nb()), dim3(256), 0, st, (const T*)g, (const T*)d, n, ow, part, fin_host(true));
+      launch_cg_dot<T>(g, d, n, ow, part, fin_host(true), nb(), st);
       return finish(1, false, true, out);
     }
     if (published) {  // the evaluation's own finish kernel carries the tag
@@ -801,12 +245,12 @@ struct DeviceCG {
     }
     tag += 1.0;
     if (!reduce_scalars) {
-      hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs, (const double*)p->d_cost, 2, hs + 15, tag);
+      launch_publish(hs, p->d_cost, 2, hs + 15, tag, st);
     } else {
       SRMAP_HIP(p->ctx, hipMemcpyAsync(dscal, p->d_cost, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
       int rc = comm_allreduce(comm, dscal, 2, SRMAP_F64, 0, st);
       if (rc) return rc;
-      hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs, (const double*)dscal, 2, hs + 15, tag);
+      launch_publish(hs, dscal, 2, hs + 15, tag, st);
     }
     SRMAP_HIP(p->ctx, hipGetLastError());
     int rc = wait_tag();
@@ -831,11 +275,9 @@ struct DeviceCG {
     }
     double* npub = fused() ? hs + 8 : (double*)nullptr;
     const int keep = foldable ? 1 : 0;
-    if (vec()) hipLaunchKernelGGL((k_direction<T, kVec>), dim3(nb()), dim3(256), 0, st, dn, (const T*)g, dk_or_null, (T)beta, n, ow, part, f, beta_dev, npub, keep);
-    else hipLaunchKernelGGL((k_direction<T, 1>), dim3(nb()), dim3(256), 0, st, dn, (const T*)g, dk_or_null, (T)beta, n, ow, part, f, beta_dev, npub, keep);
+    launch_cg_direction<T>(dn, g, dk_or_null, (T)beta, n, ow, part, f, beta_dev, npub, keep, nb(), st);
     if (!fused()) {
-      hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, part, nb(), 3, 1, dscal + 4, (const double*)nullptr,
-                         (double*)nullptr, 0.0);
+      launch_finish(part, nb(), 3, 1, dscal + 4, nullptr, nullptr, 0.0, st);
       int rc = comm_allreduce(comm, dscal + 4, 1, SRMAP_F64, 1, st);
       if (rc) return rc;
       rc = comm_allreduce(comm, dscal + 5, 2, SRMAP_F64, 0, st);
@@ -843,7 +285,7 @@ struct DeviceCG {
       if (!publish_cost) {
         tag += 1.0;
         dir_tag = tag;
-        hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, hs + 8, (const double*)(dscal + 4), 3, hs + 15, tag);
+        launch_publish(hs + 8, dscal + 4, 3, hs + 15, tag, st);
       }
     }
     SRMAP_HIP(p->ctx, hipGetLastError());
@@ -879,98 +321,41 @@ struct DeviceCG {
   // d = dk s1 s2 stored as a vector (+ the first trial point x = xk + stp1 d when stp1 != 0): the paths whose evaluations
   // read the normalised direction from memory
   int normalize(double stp1) {
-    if (vec())
-      hipLaunchKernelGGL((k_normalize<T, kVec>), dim3(nb()), dim3(256), 0, st, d, (const T*)dk, (const double*)(dscal + 4), n,
-                         (const T*)xk, stp1 != 0.0 ? x : (T*)nullptr, (T)stp1);
-    else
-      hipLaunchKernelGGL((k_normalize<T, 1>), dim3(nb()), dim3(256), 0, st, d, (const T*)dk, (const double*)(dscal + 4), n,
-                         (const T*)xk, stp1 != 0.0 ? x : (T*)nullptr, (T)stp1);
+    launch_cg_normalize<T>(d, dk, dscal + 4, n, xk, stp1 != 0.0 ? x : (T*)nullptr, (T)stp1, nb(), st);
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
-};
-
-static inline double dmax(double a, double b) { return a > b ? a : b; }
-static inline double dmin(double a, double b) { return a < b ? a : b; }
-
-// More'-Thuente safeguarded step (MINPACK-2 dcstep; ALGLIB linmin_mcstep,
-// alglibinternal.cpp:12972-13232).
-struct Bracket { double stx, fx, dx, sty, fy, dy; };
-
-static double cubic_gamma(double theta, double da, double db, bool clamp0) {
-  const double s = dmax(std::fabs(theta), dmax(std::fabs(da), std::fabs(db)));
-  double t = (theta / s) * (theta / s) - da / s * (db / s);
-  if (clamp0) t = dmax(0.0, t);
-  return s * std::sqrt(t);
-}
-
-static void mt_step(Bracket* b, double* stp, double fp, double dp, bool* brackt, double stmin,
-                    double stmax, int* info) {
-  *info = 0;
-  if ((*brackt && (*stp <= dmin(b->stx, b->sty) || *stp >= dmax(b->stx, b->sty))) ||
-      b->dx * (*stp - b->stx) >= 0 || stmax < stmin)
-    return;
-  const double sgnd = dp * (b->dx / std::fabs(b->dx));
-  bool bound;
-  double stpf;
-  if (fp > b->fx) {
-    *info = 1; bound = true;
-    const double theta = 3 * (b->fx - fp) / (*stp - b->stx) + b->dx + dp;
-    double gamma = cubic_gamma(theta, b->dx, dp, false);
-    if (*stp < b->stx) gamma = -gamma;
-    const double pp = gamma - b->dx + theta, q = gamma - b->dx + gamma + dp, r = pp / q;
-    const double stpc = b->stx + r * (*stp - b->stx);
-    const double stpq = b->stx + b->dx / ((b->fx - fp) / (*stp - b->stx) + b->dx) / 2 * (*stp - b->stx);
-    stpf = std::fabs(stpc - b->stx) < std::fabs(stpq - b->stx) ? stpc : stpc + (stpq - stpc) / 2;
-    *brackt = true;
-  } else if (sgnd < 0) {
-    *info = 2; bound = false;
-    const double theta = 3 * (b->fx - fp) / (*stp - b->stx) + b->dx + dp;
-    double gamma = cubic_gamma(theta, b->dx, dp, false);
-    if (*stp > b->stx) gamma = -gamma;
-    const double pp = gamma - dp + theta, q = gamma - dp + gamma + b->dx, r = pp / q;
-    const double stpc = *stp + r * (b->stx - *stp);
-    const double stpq = *stp + dp / (dp - b->dx) * (b->stx - *stp);
-    stpf = std::fabs(stpc - *stp) > std::fabs(stpq - *stp) ? stpc : stpq;
-    *brackt = true;
-  } else if (std::fabs(dp) < std::fabs(b->dx)) {
-    *info = 3; bound = true;
-    const double theta = 3 * (b->fx - fp) / (*stp - b->stx) + b->dx + dp;
-    double gamma = cubic_gamma(theta, b->dx, dp, true);
-    if (*stp > b->stx) gamma = -gamma;
-    const double pp = gamma - dp + theta, q = gamma + (b->dx - dp) + gamma, r = pp / q;
-    double stpc;
-    if (r < 0 && gamma != 0) stpc = *stp + r * (b->stx - *stp);
-    else stpc = *stp > b->stx ? stmax : stmin;
-    const double stpq = *stp + dp / (dp - b->dx) * (b->stx - *stp);
-    if (*brackt) stpf = std::fabs(*stp - stpc) < std::fabs(*stp - stpq) ? stpc : stpq;
-    else stpf = std::fabs(*stp - stpc) > std::fabs(*stp - stpq) ? stpc : stpq;
-  } else {
-    *info = 4; bound = false;
-    if (*brackt) {
-      const double theta = 3 * (fp - b->fy) / (b->sty - *stp) + b->dy + dp;
-      double gamma = cubic_gamma(theta, b->dy, dp, false);
-      if (*stp > b->sty) gamma = -gamma;
-      const double pp = gamma - dp + theta, q = gamma - dp + gamma + b->dy, r = pp / q;
-      stpf = *stp + r * (b->sty - *stp);
+  // The opening of a run (run_cg, run_lbfgs): evaluate at the start point, dk = -g with its sums, and f and g.g = dk.dk
+  // on the host after one wait.  *small_g: the epsg rule already holds (the caller ends the run with x = xk).
+  int begin_run(double epsg, double* f, double* gg, bool* small_g, std::vector<double>* trace) {
+    // the start point becomes the base point xk by exchanging the two buffers (no copy); x is trial scratch from here on:
+    // every path of a run writes it before reading it (the trial points) or copies xk back into it (the early exits)
+    std::swap(xk, x);
+    foldable = shard_mode(comm, shard) == SRMAP_SHARD_NONE && fold_enabled && ztile_can_fold(p, view.C > 0 ? view.C : p->geo.C);
+    int rc = evaluate(nullptr, xk);
+    if (rc) return rc;
+    // dk = -g (written as dn, swapped below), norms of dk
+    rc = direction(nullptr, 0.0, true);
+    if (rc) return rc;
+    if (fused()) {  // the direction pass published {f -> hs[0]; max|dk|, dk.dk, g.dk -> hs[8..10]} itself
+      rc = wait_tag();
+      if (rc) return rc;
+      *f = hs[0];
     } else {
-      stpf = *stp > b->stx ? stmax : stmin;
+      // fetch f and the direction's sums (already reduced on the device) with one wait
+      double h[1];
+      rc = finish(0, false, true, h, 3);
+      if (rc) return rc;
+      dir_tag = tag;
+      *f = h[0];
     }
+    *gg = hs[9];  // g.g = dk.dk
+    if (trace) trace->push_back(*f);
+    std::swap(dk, dn);
+    *small_g = std::sqrt(*gg) <= epsg;
+    return SRMAP_OK;
   }
-  if (fp > b->fx) {
-    b->sty = *stp; b->fy = fp; b->dy = dp;
-  } else {
-    if (sgnd < 0.0) { b->sty = b->stx; b->fy = b->fx; b->dy = b->dx; }
-    b->stx = *stp; b->fx = fp; b->dx = dp;
-  }
-  stpf = dmin(stmax, stpf);
-  stpf = dmax(stmin, stpf);
-  *stp = stpf;
-  if (*brackt && bound) {
-    if (b->sty > b->stx) *stp = dmin(b->stx + 0.66 * (b->sty - b->stx), *stp);
-    else *stp = dmax(b->stx + 0.66 * (b->sty - b->stx), *stp);
-  }
-}
+};
 
 // mcsrch with the device evaluation inlined (constants alglibinternal.cpp:156-160;
 // trimfunction after each evaluation as mincgiteration does, optimization.cpp:17594).
@@ -1014,15 +399,7 @@ static int line_search(DeviceCG<T>& cg, double* f, double dginit, double* stp, d
     // the trial point x = xk + stp * d: formed by the evaluation itself as it loads its window where that is possible
     // (one n-vector pass less per trial point; x holds the point afterwards all the same), else by its own pass
     const bool fold_here = !first_in_x && cg.foldable;
-    if (!first_in_x && !fold_here)
-    {
-      if ((cg.n & 3) == 0)
-        hipLaunchKernelGGL(k_axpy_out4<T>, dim3((unsigned)((cg.n / 4 + 255) / 256)), dim3(256), 0, cg.st, cg.x, (const T*)cg.xk,
-                           (const T*)cg.d, (T)*stp, cg.n / 4);
-      else
-        hipLaunchKernelGGL(k_axpy_out<T>, dim3(cg.blocks()), dim3(256), 0, cg.st, cg.x, (const T*)cg.xk,
-                           (const T*)cg.d, (T)*stp, cg.n);
-    }
+    if (!first_in_x && !fold_here) launch_axpy_out<T>(cg.x, cg.xk, cg.d, (T)*stp, cg.n, cg.st);
     if (!(first_in_x && pre_launched)) {
       rc = fold_here ? cg.evaluate(cg.dk, nullptr, cg.xk, *stp) : cg.evaluate(cg.d);
       if (rc) return rc;
@@ -1035,7 +412,7 @@ static int line_search(DeviceCG<T>& cg, double* f, double dginit, double* stp, d
     if (trace) trace->push_back(*f);
     if (*f >= trim) {  // trimfunction: F = threshold, G = 0
       *f = trim;
-      hipLaunchKernelGGL(k_fill<T>, dim3(cg.blocks()), dim3(256), 0, cg.st, cg.g, T(0), cg.n);
+      launch_fill<T>(cg.g, T(0), cg.n, cg.st);
       dg = 0;
     }
     *info = 0;
@@ -1090,35 +467,11 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
   const size_t n = cg.n;
   CgResult res;
   double f = 0, gg = 0;
-  // the start point becomes the base point xk by exchanging the two buffers (no copy); x is trial scratch from here on:
-  // every path below writes it before reading it (the trial points) or copies xk back into it (the early exits)
-  std::swap(cg.xk, cg.x);
-  {
-    const int mode = (cg.comm && cg.shard && comm_world(cg.comm) > 1) ? cg.shard->mode : SRMAP_SHARD_NONE;
-    cg.foldable = mode == SRMAP_SHARD_NONE && cg.fold_enabled && ztile_can_fold(cg.p, cg.view.C > 0 ? cg.view.C : cg.p->geo.C);
-  }
-  int rc = cg.evaluate(nullptr, cg.xk);
+  bool small_g = false;
+  int rc = cg.begin_run(epsg, &f, &gg, &small_g, trace);
   if (rc) return rc;
-  // dk = -g (written as dn, swapped below), norms of dk; g.g = dk.dk comes with them
-  rc = cg.direction(nullptr, 0.0, true);
-  if (rc) return rc;
-  if (cg.fused()) {  // the direction pass published {f -> hs[0]; max|dk|, dk.dk, g.dk -> hs[8..10]} itself
-    rc = cg.wait_tag();
-    if (rc) return rc;
-    f = cg.hs[0];
-  } else {
-    // fetch f and the direction's sums (already reduced on the device) with one wait
-    double h[1];
-    rc = cg.finish(0, false, true, h, 3);
-    if (rc) return rc;
-    cg.dir_tag = cg.tag;
-    f = h[0];
-  }
-  gg = cg.hs[9];  // g.g = dk.dk
-  if (trace) trace->push_back(f);
-  std::swap(cg.dk, cg.dn);
   const double trim = 10 * (std::fabs(f) + 1);
-  if (std::sqrt(gg) <= epsg) { res.type = 4; res.f = f; *out = res; return cg.copy(cg.x, cg.xk); }
+  if (small_g) { res.type = 4; res.f = f; *out = res; return cg.copy(cg.x, cg.xk); }
   res.nfev = 1;
   double fold = f, lastgoodstep = 1.0;
   int rstimer = rscountdownlen;
@@ -1181,12 +534,7 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
       // host-paced passes: the pass also sums y.dk directly (one more vector read) and the deviation of the derived
       // denominator from it is recorded (srmap_problem_selfcheck; tests/test_gpu_solve_parity.py)
       const T* dk_chk = chain ? (const T*)nullptr : (const T*)cg.dk;
-      if (cg.vec())
-        hipLaunchKernelGGL((k_beta_dots<T, DeviceCG<T>::kVec>), dim3(cg.nb()), dim3(256), 0, cg.st, (const T*)cg.gp, (const T*)cg.g,
-                           n, cg.ow, cg.part, cg.fin_host(false), beta_dst, restart, vv, dk_chk);
-      else
-        hipLaunchKernelGGL((k_beta_dots<T, 1>), dim3(cg.nb()), dim3(256), 0, cg.st, (const T*)cg.gp, (const T*)cg.g,
-                           n, cg.ow, cg.part, cg.fin_host(false), beta_dst, restart, vv, dk_chk);
+      launch_cg_beta_dots<T>(cg.gp, cg.g, n, cg.ow, cg.part, cg.fin_host(false), beta_dst, restart, vv, dk_chk, cg.nb(), cg.st);
       if (chain) {
         const double tag_beta = cg.tag;
         rc = cg.direction(cg.dk, 0.0, false, cg.dscal + 8);  // dn, sums of dn (device)
@@ -1204,12 +552,7 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
           cg.p->selfcheck_beta_den = dmax(cg.p->selfcheck_beta_den, std::fabs(vv - h[2]) / std::fabs(h[2]));
       }
     } else {
-      if (cg.vec())
-        hipLaunchKernelGGL((k_dot<T, DeviceCG<T>::kVec>), dim3(cg.nb()), dim3(256), 0, cg.st, (const T*)cg.g, (const T*)cg.g, n, cg.ow,
-                           cg.part, cg.fin_host(false));
-      else
-        hipLaunchKernelGGL((k_dot<T, 1>), dim3(cg.nb()), dim3(256), 0, cg.st, (const T*)cg.g, (const T*)cg.g, n, cg.ow, cg.part,
-                           cg.fin_host(false));
+      launch_cg_dot<T>(cg.g, cg.g, n, cg.ow, cg.part, cg.fin_host(false), cg.nb(), cg.st);
       if (chain) {
         const double tag_gg = cg.tag;
         rc = cg.direction(cg.dk, 0.0);  // beta = 0
@@ -1263,39 +606,17 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
   if (epsg == 0 && epsf == 0 && epsx == 0 && maxits == 0) epsx = 1.0E-6;  // minlbfgssetcond
   CgResult res;
   double f = 0, gg = 0;
-  std::swap(cg.xk, cg.x);  // the start point is the line search's base point; x is trial scratch (see run_cg)
-  {
-    const int mode = (cg.comm && cg.shard && comm_world(cg.comm) > 1) ? cg.shard->mode : SRMAP_SHARD_NONE;
-    cg.foldable = mode == SRMAP_SHARD_NONE && cg.fold_enabled && ztile_can_fold(cg.p, cg.view.C > 0 ? cg.view.C : cg.p->geo.C);
-  }
-  int rc = cg.evaluate(nullptr, cg.xk);
+  bool small_g = false;
+  int rc = cg.begin_run(epsg, &f, &gg, &small_g, trace);
   if (rc) return rc;
-  // d = -g and its sums; g.g = d.d
-  rc = cg.direction(nullptr, 0.0, true);
-  if (rc) return rc;
-  if (cg.fused()) {
-    rc = cg.wait_tag();
-    if (rc) return rc;
-    f = cg.hs[0];
-  } else {
-    double h[1];
-    rc = cg.finish(0, false, true, h, 3);
-    if (rc) return rc;
-    cg.dir_tag = cg.tag;
-    f = h[0];
-  }
-  gg = cg.hs[9];
-  if (trace) trace->push_back(f);
-  std::swap(cg.dk, cg.dn);
   const double trim = 10 * (std::fabs(f) + 1);  // trimprepare
-  if (std::sqrt(gg) <= epsg) { res.type = 4; res.f = f; *out = res; return cg.copy(cg.x, cg.xk); }
+  if (small_g) { res.type = 4; res.f = f; *out = res; return cg.copy(cg.x, cg.xk); }
   res.nfev = 1;
   double fold = f;
   double stp = dmin(1.0 / std::sqrt(gg), 1.0);  // prectype 0, stpmax 0
   // Gram tables over the ring slots: SY[a * m + b] = s_a.y_b, YY[a * m + b] = y_a.y_b, gs[j] = g.s_j, gy[j] = g.y_j (g
   // the current gradient).  The update pass recomputes every entry of the slot it writes.
-  std::vector<double> SY((size_t)m * m, 0.0), YY((size_t)m * m, 0.0), gs(m, 0.0), gy(m, 0.0), rho(m, 0.0), theta(m, 0.0);
-  std::vector<double> cs(m), cy(m);
+  std::vector<double> SY((size_t)m * m, 0.0), YY((size_t)m * m, 0.0), gs(m, 0.0), gy(m, 0.0), rho(m, 0.0);
   int k = 0, nfev_state = 0;  // ALGLIB's state->nfev: a line search that returns before its first trial leaves it as it was
   for (;;) {
     const int p = k % m, q = k < m - 1 ? k : m - 1, live = q + 1;
@@ -1346,31 +667,8 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
       rc = cg.direction(nullptr, 0.0);
       if (rc) return rc;
     } else {
-      const double v = SY[(size_t)p * m + p], vv = YY[(size_t)p * m + p];
-      if (v == 0 || vv == 0) { res.type = -2; break; }
-      rho[p] = 1 / v;
-      const double gammak = v / vv;
-      // ALGLIB's two loops on work = cgc g + sum_j (cs_j s_j + cy_j y_j), starting from work = g
-      double cgc = 1.0;
-      for (int j = 0; j < m; ++j) { cs[j] = 0.0; cy[j] = 0.0; }
-      for (int i = k; i >= k - q; --i) {
-        const int ic = i % m;
-        double t = cgc * gs[ic];  // s_ic.work (the s coefficients are still 0)
-        for (int j = 0; j < live; ++j) t += cy[j] * SY[(size_t)ic * m + j];
-        theta[ic] = t;
-        cy[ic] -= t * rho[ic];
-      }
-      cgc *= gammak;
-      for (int j = 0; j < live; ++j) cy[j] *= gammak;
-      for (int i = k - q; i <= k; ++i) {
-        const int ic = i % m;
-        double t = cgc * gy[ic];  // y_ic.work
-        for (int j = 0; j < live; ++j) t += cs[j] * SY[(size_t)j * m + ic] + cy[j] * YY[(size_t)ic * m + j];
-        cs[ic] += rho[ic] * (-t + theta[ic]);
-      }
       LbfgsCoef c{};
-      c.c[0] = cgc;
-      for (int j = 0; j < live; ++j) { c.c[1 + 2 * j] = cs[j]; c.c[2 + 2 * j] = cy[j]; }
+      if (!lbfgs_two_loop(SY.data(), YY.data(), gs.data(), gy.data(), rho.data(), k, q, m, c.c)) { res.type = -2; break; }
       rc = cg.lbfgs_direction(c, live);  // d = -work
       if (rc) return rc;
       fold = f;
@@ -1391,17 +689,12 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   const Geometry& geo = p->geo;
   const size_t N = (size_t)geo.W * geo.H;
   const int C = geo.C;
-  const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;
+  const int mode = shard_mode(comm, shard);
   const bool lbfgs = p->solver == SRMAP_SOLVER_LBFGS;
   if (lbfgs && mode != SRMAP_SHARD_NONE)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
   const bool huber = p->data_loss == SRMAP_DATA_LOSS_HUBER;
-  if (p->robust() && mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator (the weights are not split with the frames or rows): run the solve unsharded");
-  if (p->affine && mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "an affine motion model is not sharded over a communicator (only the direct family runs it): run the solve unsharded");
-  if (p->custom_blur && mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a free-form blur kernel is not sharded over a communicator (only the direct family runs it): run the solve unsharded");
+  if (int rc = refuse_sharded(p, mode, "solve")) return rc;
   if (mode != SRMAP_SHARD_NONE && opt->split_channels)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
   if (mode == SRMAP_SHARD_ROWS &&
@@ -1479,12 +772,11 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     if (rc) break;
     // w <- 1  (irls_map_solver.cpp:66-74)
     for (int r = 0; r < p->nreg; ++r)
-      hipLaunchKernelGGL(k_fill<T>, dim3(cg.blocks()), dim3(256), 0, st, (T*)p->reg[r].weights + (size_t)c0 * N, T(1), npts);
+      launch_fill<T>((T*)p->reg[r].weights + (size_t)c0 * N, T(1), npts, st);
     if (huber) {  // the data weights of this round's channels likewise ([K][C][h][w]: one run per frame)
       const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
       for (int k = 0; k < geo.K; ++k)
-        hipLaunchKernelGGL(k_fill<T>, dim3((unsigned)((run + 255) / 256)), dim3(256), 0, st,
-                           (T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run);
+        launch_fill<T>((T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run, st);
     }
     double previous_cost = INFINITY;
     double cost_difference = o.irls_cost_difference_threshold + 1.0;
@@ -1577,32 +869,6 @@ static int cg_trace_typed(srmap_problem* p, int lbfgs_m, double epsg, double eps
 using namespace srmap;
 
 extern "C" {
-
-int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, unsigned terms,
-                              void* x_dev, void* g_dev, double* cost, void* hip_stream) {
-  if (!p || !x_dev) return SRMAP_EINVAL;
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
-  if (p->robust() && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator: evaluate unsharded");
-  if (p->affine && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "an affine motion model is not sharded over a communicator: evaluate unsharded");
-  if (p->custom_blur && comm && shard && comm_world(comm) > 1 && shard->mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a free-form blur kernel is not sharded over a communicator: evaluate unsharded");
-  EvalOut out;
-  int rc = shard_eval(p, comm, shard, EvalReq(), &out, terms, x_dev, g_dev, st);
-  if (rc) return rc;
-  if (cost) {
-    const int mode = (comm && shard && comm_world(comm) > 1) ? shard->mode : SRMAP_SHARD_NONE;
-    if (mode == SRMAP_SHARD_ROWS || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
-      rc = comm_allreduce(comm, p->d_cost, 1, SRMAP_F64, 0, st);
-      if (rc) return rc;
-    }
-    SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost, sizeof(double), hipMemcpyDeviceToHost, st));
-    SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-  }
-  return SRMAP_OK;
-}
 
 int srmap_cg_trace(srmap_problem* p, double epsg, double epsf, double epsx, int maxits, const double* x0, double* x_out,
                    int* iterations, int* nfev, int* termination, double* f_trace, int trace_cap, int* trace_len) {

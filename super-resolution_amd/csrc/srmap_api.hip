@@ -9,6 +9,7 @@
 #include <cstring>
 #include <new>
 
+#include "solver_passes.hpp"
 #include "srmap_internal.hpp"
 
 using namespace srmap;
@@ -342,12 +343,6 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
   return eval_typed<double>(p, req, out, terms, (const double*)x, (double*)g, st);
 }
 
-template <typename T>
-__global__ void k_fill_value(T* __restrict__ d, T v, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) d[i] = v;
-}
-
 // Weights or the loss changed whether the problem is robust(): the tile plan has another form then (ztile_plan)
 static void replan_if(srmap_problem* p, bool was_robust) {
   if (p->robust() == was_robust) return;
@@ -360,8 +355,8 @@ static int ensure_data_weights(srmap_problem* p, hipStream_t st) {
   if (p->d_dw) return SRMAP_OK;
   const size_t n = p->lr_count();
   SRMAP_HIP(p->ctx, hipMalloc(&p->d_dw, n * p->elem()));
-  if (p->dtype == SRMAP_F32) hipLaunchKernelGGL(k_fill_value<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float*)p->d_dw, 1.f, n);
-  else hipLaunchKernelGGL(k_fill_value<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (double*)p->d_dw, 1.0, n);
+  if (p->dtype == SRMAP_F32) launch_fill<float>((float*)p->d_dw, 1.f, n, st);
+  else launch_fill<double>((double*)p->d_dw, 1.0, n, st);
   SRMAP_HIP(p->ctx, hipGetLastError());
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
   return SRMAP_OK;

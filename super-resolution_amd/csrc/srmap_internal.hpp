@@ -162,7 +162,7 @@ struct srmap_problem {
   hipEvent_t state_ev = nullptr;
   hipStream_t state_stream = nullptr, state_seen = nullptr, use_stream = nullptr;
   // frame sharding: whether EVERY rank of the communicator can evaluate the regulariser of a row band (agreed once by an
-  // all-reduce, solver.hip shard_eval); the key it was agreed for
+  // all-reduce, shard_eval.hip); the key it was agreed for
   const void* band_comm = nullptr;
   unsigned long long plan_gen = 1;   // bumped whenever the tile plan or the implementation choice changes (a freed and
                                      // re-allocated plan can come back at the same address: pointer identity is no key)
@@ -313,7 +313,7 @@ int problem_state_read(srmap_problem* p, hipStream_t st);
 // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
 int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
 
-// ---- vector kernels for the solver (solver.hip) ----
+// ---- solver (solver.hip) ----
 int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
                const srmap_irls_options* o, const double* x0, double* x_out,
                srmap_solve_report* rep);

@@ -317,7 +317,7 @@ struct ZArgs {
   const double* xpart;   // plain cost partials of an EARLIER launch on the stream (sub-pixel path: the forward kernel's data
   int n_xpart;           //   cost), complete when this kernel starts: the in-kernel finish adds them, in index order
   // ---- solver line search (WD instances): the trial point x = fold_xk + fold_stp * dvec is formed when the window goes
-  // to LDS (the expression of solver.hip's k_axpy_out, same contraction), its own pixels are written to fold_x ----
+  // to LDS (the expression of solver_passes.hip's k_axpy_out, same contraction), its own pixels are written to fold_x ----
   const T* fold_xk;      // nullptr: x is read as given
   T* fold_x;
   T fold_stp;

@@ -1,5 +1,5 @@
-"""The covering matrix of the solver's n-vector passes (csrc/solver.hip run_cg / run_lbfgs, csrc/kernels_lbfgs.hip): a
-mirror of their dispatch, the geometries and solver settings that reach every cell of it, and the trajectory bars.
+"""The covering matrix of the solver's n-vector passes (csrc/solver.hip run_cg / run_lbfgs; csrc/solver_passes.hip,
+csrc/kernels_lbfgs.hip): a mirror of their dispatch, the geometries and solver settings that reach every cell of it, and the trajectory bars.
 Shared by tests/test_gpu_solver_matrix.py (HIP against ALGLIB's mincg / the minlbfgs restatement) and
 tests/test_solver_matrix_cpu.py (the matrix reaches every cell; planted bugs in the restatement fail the same bars).
 
