@@ -493,6 +493,68 @@ int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
                           const srmap_blur_fit_options* options /* NULL = defaults */, double* taps_out, double* quality_out,
                           double* normal_equations_out);
 
+/* Photometric frame model: per-frame gain and bias (no reference counterpart: image_model.cpp:86-91 gives every frame the
+ * photometry of the HR image; csrc/photometric_fit.hip).  Frame k is modelled as
+ *   y_k = a_k (D B M_k x) + b_k + noise,
+ * and while parameters are set the problem solves against the NORMALISED frames yn_k = (y_k - b_k) / a_k: the data cost is
+ * s^2 sum_k sum w (A_k x - yn_k)^2, today's formula with yn in place of y.
+ *   units     the cost is measured in the normalised units.  It is NOT the maximum-likelihood weighting of the model
+ *             above, which would carry a factor a_k^2 per frame.  huber_delta and the Huber weights therefore act on
+ *             normalised residuals.
+ *   storage   the raw frames are kept; yn lives in a second [K][C][h][w] buffer that exists only while parameters are set.
+ *             Per element, in double on the stored value: the subtraction, then a true division, then one rounding to the
+ *             problem's dtype (no reciprocal, no contraction).  NULL switches back to the raw buffer bit for bit.
+ *   scope     one (gain, bias) pair per frame, shared by all channels; gain_bias is K x 2 = {a_k, b_k}.  Only the
+ *             observation buffer changes, so every path that reads observations honours the parameters: both kernel
+ *             families, the sub-pixel path, an affine motion, a free-form blur, data weights and the Huber loss, CG /
+ *             L-BFGS / split_channels, the traces, cost rows, sharded evaluations and solves (each rank normalises its own
+ *             frames), srmap_refine_motion and srmap_fit_blur (which then see yn).  srmap_problem_active_impl is unchanged.
+ *   persists  across srmap_set_observations* (the new frames are normalised), the data-weight calls,
+ *             srmap_problem_set_affine_motion and srmap_problem_set_blur_kernel.
+ * A number that is not finite, or a gain <= 0: SRMAP_EINVAL, and nothing changes.  Not thread-safe against evaluations of
+ * the same problem; evaluations already enqueued are waited for. */
+int srmap_problem_set_photometric(srmap_problem* p, const double* gain_bias /* K x 2; NULL restores */);
+/* The parameters in force: gain_bias_out (optional, K x 2; {1, 0} per frame when none are set), *is_set (optional). */
+int srmap_problem_get_photometric(const srmap_problem* p, double* gain_bias_out /* K x 2 */, int* is_set);
+
+/* Fit of the photometric parameters to an HR image x (no reference counterpart; csrc/photometric_fit.hip):
+ * per frame the minimiser of
+ *   energy    E_k(a, b) = sum_c sum_u w (a s + b - y_raw)^2, s = (D B M_k x)(c, u), M_k sampled exactly as the forward
+ *             kernel of the problem's motion samples it (the 1/32-px table of shifts_xy, double coordinates for an affine
+ *             motion, the identity without motion), B the blur in force (Gaussian or free-form), over EVERY LR pixel of
+ *             every channel: the rows of srmap_problem_set_cost_rows are ignored.  y_raw: the frames as given, whatever
+ *             parameters are in force -- the result is absolute, not an increment, and fitting twice at the same x gives
+ *             the same answer.  w: the problem's data weights as they stand (1 when none are set), so a fit after a Huber
+ *             solve is outlier-robust.
+ *   sums      one kernel launch over all frames: sum w, sum w s, sum w y, sum w s^2, sum w s y, sum w y^2 per frame, double
+ *             in both dtypes, no atomics; bit-identical run to run, and a frame's sums do not depend on the other frames.
+ *   solve     on the host: model 0 the 2 x 2 system in (a, b); model 1 the gain alone with the bias in force held; model 2
+ *             the bias alone with the gain in force held.
+ *   status    per frame, none of them an error of the call: 0 fitted; 2 the fitted gain is outside [min_gain, max_gain],
+ *             the parameters in force are kept; 3 degenerate -- sum w = 0, or a determinant <= 1e-12 sum w sum w s^2 (a flat
+ *             frame) -- the parameters in force are kept.  The gauge frame keeps its parameters with status 0.
+ * gain_bias_out (optional, K x 2): the result.  quality_out (optional, K x 4): E at the parameters in force, E at the
+ * result (both from the six sums), sum w, status.  sums_out (optional, K x 6): the sums in the order above.  apply = 1
+ * installs the result as srmap_problem_set_photometric would.  SRMAP_EINVAL: no observations set; a struct_size that is not
+ * this library's; a model outside 0..2; a gauge_frame outside -1..K-1; gain bounds that are not finite with
+ * 0 < min_gain <= max_gain.  Every error leaves the problem unchanged.  A problem sharded over more than one rank is out of
+ * scope (a rank would fit its own frames alone).  The _device form takes x in the problem's dtype and enqueues on hip_stream
+ * (NULL = the context's stream); both forms are complete when they return. */
+typedef struct {
+  int struct_size;  /* filled by the _default call; a mismatch is SRMAP_EINVAL */
+  int model;        /* 0 gain and bias (default), 1 gain only, 2 bias only */
+  int gauge_frame;  /* 0 (default): this frame keeps its parameters; -1: none */
+  double min_gain;  /* 0.25 */
+  double max_gain;  /* 4 */
+  int apply;        /* 1 */
+} srmap_photometric_fit_options;
+void srmap_photometric_fit_options_default(srmap_photometric_fit_options* options);
+int srmap_fit_photometric(srmap_problem* p, const double* x_host, const srmap_photometric_fit_options* options /* NULL = defaults */,
+                          double* gain_bias_out, double* quality_out /* K x 4 */, double* sums_out /* K x 6 */);
+int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                                 const srmap_photometric_fit_options* options /* NULL = defaults */, double* gain_bias_out,
+                                 double* quality_out /* K x 4 */, double* sums_out /* K x 6 */);
+
 /* ------------------------------------------------------------- solver */
 /* IRLSMapSolverOptions (irls_map_solver.h:14-36) + MapSolverOptions
  * (map_solver.h:28-79); srmap_irls_options_default() fills the reference

@@ -580,7 +580,7 @@ void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
   void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_affine, p->d_obs, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
+                  p->d_affine, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
   for (int* t : p->d_ytabs) (void)hipFree(t);
@@ -735,10 +735,16 @@ int srmap_set_observations(srmap_problem* p, const double* lr_host) {
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   rc = state_begin_write(p, p->ctx->stream);
   if (rc) return rc;
-  rc = ensure(p, &p->d_obs, p->lr_count() * p->elem());
+  void** raw = p->photometric ? &p->d_obs_raw : &p->d_obs;  // photometric parameters persist: the new frames are normalised
+  rc = ensure(p, raw, p->lr_count() * p->elem());
   if (rc) return rc;
-  rc = convert_upload(p, lr_host, p->d_obs, p->lr_count(), p->ctx->stream);
+  rc = convert_upload(p, lr_host, *raw, p->lr_count(), p->ctx->stream);
   if (rc) return rc;
+  if (p->photometric) {
+    rc = photometric_normalise(p, p->ctx->stream);
+    if (rc) return rc;
+    SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  }
   p->have_obs = true;
   return SRMAP_OK;
 }
@@ -751,9 +757,14 @@ int srmap_set_observations_device(srmap_problem* p, const void* lr_dev, void* hi
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
   rc = state_begin_write(p, st);
   if (rc) return rc;
-  rc = ensure(p, &p->d_obs, p->lr_count() * p->elem());
+  void** raw = p->photometric ? &p->d_obs_raw : &p->d_obs;
+  rc = ensure(p, raw, p->lr_count() * p->elem());
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_obs, lr_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(*raw, lr_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  if (p->photometric) {
+    rc = photometric_normalise(p, st);
+    if (rc) return rc;
+  }
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));  // complete on return: lr_dev may be reused, any stream may evaluate
   p->have_obs = true;
   return SRMAP_OK;

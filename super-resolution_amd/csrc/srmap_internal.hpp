@@ -139,6 +139,13 @@ struct srmap_problem {
   // state
   void* d_obs = nullptr;          // [K][C][h][w] dtype
   bool have_obs = false;
+  // photometric frame model (srmap_problem_set_photometric, photometric_fit.hip): while parameters are set, d_obs_raw holds
+  // the frames as given and d_obs -- what every kernel reads -- their normalised copy (y - bias_k) / gain_k; d_obs_raw is
+  // nullptr otherwise (and until a problem with parameters receives its first frames)
+  bool photometric = false;
+  std::vector<double> photo;      // K x 2 {gain, bias} (host mirror of d_photo)
+  double* d_photo = nullptr;
+  void* d_obs_raw = nullptr;      // [K][C][h][w] dtype
   void* d_resid = nullptr;        // [K][C][h][w] dtype scratch
   void* d_dw = nullptr;           // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
   int data_loss = SRMAP_DATA_LOSS_L2;  // srmap_problem_set_data_loss; HUBER keeps d_dw allocated (it owns the buffer)
@@ -245,6 +252,9 @@ struct FitPass {
   bool reduce_and_fetch(int chunks, hipStream_t st);  // also reports a failed launch of the caller's sums kernel
   const double* sums(int frame) const { return h_sums + (size_t)frame * nsums; }
 };
+// ---- photometric frame model (photometric_fit.hip) ----
+// d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
+int photometric_normalise(srmap_problem* p, hipStream_t st);
 // whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
 template <typename T>

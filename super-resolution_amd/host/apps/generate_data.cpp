@@ -4,12 +4,14 @@
 // drawn on the host with std::normal_distribution (the reference's cv::randn
 // stream cannot be reproduced without OpenCV).
 #include <cstdio>
+#include <memory>
 #include <random>
 #include <string>
 
 #include "apps/app_flags.h"
 #include "image/image_io.h"
 #include "image_model/image_model.h"
+#include "image_model/photometric.h"
 
 using namespace super_resolution;
 
@@ -22,7 +24,9 @@ int main(int argc, char** argv) {
       "  not a reference flag: [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                        an error together with --motion_sequence_path)\n"
       "                        [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
-      "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)");
+      "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)\n"
+      "                        [--photometric_path=<file>] (per-frame exposure, 'gain bias' per line, the bias in pixel units\n"
+      "                        0..1: applied to the noise-free frame, the noise is added after)");
   const std::string input_image = flags.Str("input_image");
   const std::string output_dir = flags.Str("output_image_dir");
   std::string extension = flags.Str("output_image_extension");
@@ -31,6 +35,7 @@ int main(int argc, char** argv) {
   parameters.motion_sequence_path = flags.Str("motion_sequence_path");
   parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
   parameters.blur_kernel_path = flags.Str("blur_kernel_path");  // not a reference flag
+  const std::string photometric_path = flags.Str("photometric_path");  // not a reference flag
   parameters.blur_radius = flags.Int("blur_radius", 0);
   parameters.blur_sigma = flags.Double("blur_sigma", 0.0);
   parameters.noise_sigma = flags.Double("noise_sigma", 0.0);  // 0..255 units (additive_noise_module.cpp:25-26)
@@ -50,10 +55,25 @@ int main(int argc, char** argv) {
     return 0;
   }
   flags.Require("output_image_dir");
+  // --photometric_path: gain and bias act on the noise-free frame, so the model runs without its noise module and the
+  // noise (one module, the same stream of draws) is added last
+  PhotometricSequence photometric;
+  std::unique_ptr<AdditiveNoiseModule> noise_after;
+  if (!photometric_path.empty()) {
+    photometric.LoadSequenceFromFile(photometric_path);
+    if (photometric.GetNumFrames() < number_of_frames) {
+      std::fprintf(stderr, "ERROR: --photometric_path holds %d frames, --number_of_frames asks for %d.\n", photometric.GetNumFrames(), number_of_frames);
+      return 1;
+    }
+    if (parameters.noise_sigma > 0.0) noise_after.reset(new AdditiveNoiseModule(parameters.noise_sigma, parameters.noise_seed));
+    parameters.noise_sigma = 0.0;
+  }
   const ImageModel image_model = ImageModel::CreateImageModel(parameters);
   if (!extension.empty() && extension[0] != '.') extension = "." + extension;
   for (int i = 0; i < number_of_frames; ++i) {
-    const ImageData frame = image_model.ApplyToImage(image_data, i);  // incl. the AdditiveNoiseModule, if any
+    ImageData frame = image_model.ApplyToImage(image_data, i);  // incl. the AdditiveNoiseModule, if any
+    if (!photometric.Empty()) photometric.ApplyToImage(&frame, i);
+    if (noise_after) noise_after->ApplyToImage(&frame, i);
     const std::string path = output_dir + "/low_res_" + std::to_string(i) + extension;
     util::SaveImage(frame, path);
     std::printf("Generated output image %s\n", path.c_str());

@@ -9,7 +9,9 @@
 // --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
 // --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion), nor
 // --blur_kernel_path (a free-form blur kernel, srmap_problem_set_blur_kernel) and --fit_blur_from / --fit_blur_ksize /
-// --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur).
+// --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur), nor --photometric_path /
+// --photometric_rounds / --save_photometric_path (per-frame gain and bias, srmap_problem_set_photometric and
+// srmap_fit_photometric).
 // Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
 #include <chrono>
@@ -60,6 +62,14 @@ int main(int argc, char** argv) {
       "                       high-resolution image of the scene -- a calibration pair -- and solve with it)\n"
       "                       [--fit_blur_ksize=0] (size of the fitted kernel; 0 = the size of the blur in force)\n"
       "                       [--save_blur_kernel_path=<file>] (the fitted kernel, in --blur_kernel_path's format)\n"
+      "                       [--photometric_path=<file>] (known per-frame exposure, 'gain bias' per line, the bias in pixel\n"
+      "                       units 0..1: the solve runs against (frame - bias) / gain)\n"
+      "                       [--photometric_rounds=-1] (N >= 0: fit gain and bias of every frame but the first at the initial\n"
+      "                       estimate, solve, then N times: fit at the estimate, solve again from it; with\n"
+      "                       --refine_motion_rounds each round fits, refines the motion, then solves; -1 = off; an error\n"
+      "                       together with --photometric_path)\n"
+      "                       [--save_photometric_path=<file>] (the parameters in force after the solve, in\n"
+      "                       --photometric_path's format; needs one of the two flags above)\n"
       "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
   const std::string data_path = flags.Str("data_path");
   const bool generate_lr_images = flags.Bool("generate_lr_images", false);
@@ -109,6 +119,10 @@ int main(int argc, char** argv) {
   const std::string fit_blur_from = flags.Str("fit_blur_from");
   const int fit_blur_ksize = flags.Int("fit_blur_ksize", 0);
   const std::string save_blur_kernel_path = flags.Str("save_blur_kernel_path");
+  // not reference flags: the photometric frame model (srmap_problem_set_photometric) and its fit (srmap_fit_photometric)
+  const std::string photometric_path = flags.Str("photometric_path");
+  const int photometric_rounds = flags.Int("photometric_rounds", -1);
+  const std::string save_photometric_path = flags.Str("save_photometric_path");
   const bool verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
@@ -140,6 +154,18 @@ int main(int argc, char** argv) {
   }
   if (fit_blur_from.empty() && (!save_blur_kernel_path.empty() || fit_blur_ksize != 0)) {
     std::fprintf(stderr, "ERROR: --save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from.\n");
+    return 1;
+  }
+  if (photometric_rounds < -1) {
+    std::fprintf(stderr, "ERROR: --photometric_rounds is >= 0 (or -1: off).\n");
+    return 1;
+  }
+  if (!photometric_path.empty() && photometric_rounds >= 0) {
+    std::fprintf(stderr, "ERROR: --photometric_path gives the parameters, --photometric_rounds fits them: they exclude each other.\n");
+    return 1;
+  }
+  if (!save_photometric_path.empty() && photometric_path.empty() && photometric_rounds < 0) {
+    std::fprintf(stderr, "ERROR: --save_photometric_path needs --photometric_path or --photometric_rounds.\n");
     return 1;
   }
   // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
@@ -289,10 +315,36 @@ int main(int argc, char** argv) {
     }
   }
 
+  // --photometric_path: known exposure, in force for every solve below
+  const bool photometric = !photometric_path.empty() || photometric_rounds >= 0;
+  if (photometric && (interpolate_color || spectral_pca)) {
+    std::fprintf(stderr, "ERROR: the photometric flags work in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
+    return 1;
+  }
+  if (!photometric_path.empty()) {
+    PhotometricSequence known;
+    known.LoadSequenceFromFile(photometric_path);
+    solver.SetPhotometric(known);
+  }
+
   std::printf("Super-resolving from %zu images...\n", low_res_images.size());
   const auto start_time = std::chrono::steady_clock::now();
   ImageData result;
-  if (refine_motion_rounds > 0) {
+  if (photometric_rounds >= 0) {
+    MotionRefinementOptions refinement;
+    refinement.dof = refine_motion_dof;
+    AffineMotionSequence refined;
+    PhotometricSequence fitted;
+    // with --refine_motion_rounds every round fits the exposure, refines the motion, then solves; the larger count rules
+    const int rounds = refine_motion_rounds > photometric_rounds ? refine_motion_rounds : photometric_rounds;
+    result = solver.SolvePhotometricJoint(initial_estimate, rounds, refine_motion_rounds > 0, PhotometricFitOptions(), refinement,
+                                          &fitted, &refined);
+    std::printf("Fitted gain and bias of %d frames in %d rounds.\n", fitted.GetNumFrames(), rounds);
+    if (refine_motion_rounds > 0) {
+      std::printf("Refined the motion of %d frames in %d rounds.\n", refined.GetNumMotions(), rounds);
+      if (!save_motion_path.empty() && !save_motion(refined)) return 1;
+    }
+  } else if (refine_motion_rounds > 0) {
     MotionRefinementOptions refinement;
     refinement.dof = refine_motion_dof;
     AffineMotionSequence refined;
@@ -301,6 +353,10 @@ int main(int argc, char** argv) {
     if (!save_motion_path.empty() && !save_motion(refined)) return 1;
   } else {
     result = solver.Solve(initial_estimate);
+  }
+  if (!save_photometric_path.empty() && !solver.GetPhotometric().SaveToFile(save_photometric_path)) {
+    std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_photometric_path.c_str());
+    return 1;
   }
   const std::chrono::duration<double> elapsed = std::chrono::steady_clock::now() - start_time;
   std::printf("Done! Finished in %g seconds.\n", elapsed.count());

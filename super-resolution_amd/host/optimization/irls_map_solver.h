@@ -8,7 +8,8 @@
 // irls_map_solver.cpp:97-113.  Analytical differentiation only: the reference's
 // numeric-difference variant is a test-only alternative outside the path.
 // Not in the reference: RefineMotion / SolveJoint, the joint motion refinement of include/srmap.h (srmap_refine_motion),
-// and FitBlur, the calibration fit of the blur kernel (srmap_fit_blur).
+// FitBlur, the calibration fit of the blur kernel (srmap_fit_blur), and SetPhotometric / FitPhotometric / SolvePhotometric /
+// SolvePhotometricJoint, the photometric frame model (srmap_problem_set_photometric, srmap_fit_photometric).
 #pragma once
 #include <cmath>
 #include <iostream>
@@ -19,6 +20,7 @@
 
 #include "image/image_data.h"
 #include "image_model/image_model.h"
+#include "image_model/photometric.h"
 #include "motion/affine_motion.h"
 #include "optimization/objective_function.h"
 #include "optimization/regularizer.h"
@@ -87,6 +89,14 @@ struct BlurFitOptions {
   int ksize = 0;           // 0: the size of the solver's current kernel
   bool sum_to_one = true;
   double ridge = 0.0;
+};
+
+// Options of IRLSMapSolver::FitPhotometric (srmap_photometric_fit_options, include/srmap.h).  Not in the reference.
+struct PhotometricFitOptions {
+  int model = 0;         // 0: gain and bias; 1: gain only; 2: bias only
+  int gauge_frame = 0;   // this frame keeps its parameters; -1: none
+  double min_gain = 0.25;
+  double max_gain = 4.0;
 };
 
 class Solver {
@@ -287,6 +297,76 @@ class IRLSMapSolver : public MapSolver {
       if (motion) *motion = refined;
       x = Solve(x);
     }
+    return x;
+  }
+  // Photometric frame model (srmap_problem_set_photometric; not in the reference): later solves and ComputeAllTerms run
+  // against the frames normalised by these per-frame (gain, bias) pairs.  An empty sequence restores the raw frames.
+  void SetPhotometric(const PhotometricSequence& photometric) {
+    if (photometric.Empty()) {
+      srmap_host::Check(srmap_problem_set_photometric(problem_.get(), nullptr), "srmap_problem_set_photometric");
+      return;
+    }
+    if (photometric.GetNumFrames() < GetNumImages()) srmap_host::Fail("fewer photometric (gain, bias) pairs than observations");
+    std::vector<double> flat = photometric.Flat();
+    flat.resize(static_cast<size_t>(GetNumImages()) * 2);
+    srmap_host::Check(srmap_problem_set_photometric(problem_.get(), flat.data()), "srmap_problem_set_photometric");
+  }
+  // The parameters in force (ones and zeros when none are set).
+  PhotometricSequence GetPhotometric() const {
+    std::vector<double> flat(static_cast<size_t>(GetNumImages()) * 2);
+    srmap_host::Check(srmap_problem_get_photometric(problem_.get(), flat.data(), nullptr), "srmap_problem_get_photometric");
+    return PhotometricSequence(flat.data(), GetNumImages());
+  }
+  // Fit of the per-frame gain and bias to `estimate` (srmap_fit_photometric; not in the reference), from the RAW frames
+  // under the solver's motion, blur and data weights, INSTALLED as SetPhotometric would.  quality (optional): 4 numbers per
+  // frame -- cost at the parameters in force, cost at the result, sum of the weights, status.
+  PhotometricSequence FitPhotometric(const ImageData& estimate, const PhotometricFitOptions& options = PhotometricFitOptions(),
+                                     std::vector<double>* quality = nullptr) {
+    if (estimate.GetNumChannels() != GetNumChannels() || estimate.GetImageSize() != GetImageSize())
+      srmap_host::Fail("estimate does not match the HR geometry");
+    srmap_photometric_fit_options o;
+    srmap_photometric_fit_options_default(&o);
+    o.model = options.model;
+    o.gauge_frame = options.gauge_frame;
+    o.min_gain = options.min_gain;
+    o.max_gain = options.max_gain;
+    o.apply = 1;
+    const std::vector<double> x = estimate.ToPlanar();
+    std::vector<double> flat(static_cast<size_t>(GetNumImages()) * 2), q(static_cast<size_t>(GetNumImages()) * 4);
+    srmap_host::Check(srmap_fit_photometric(problem_.get(), x.data(), &o, flat.data(), q.data(), nullptr), "srmap_fit_photometric");
+    if (IsVerbose())
+      for (int i = 0; i < GetNumImages(); ++i)
+        std::cout << "  frame " << i << ": gain " << flat[2 * i] << ", bias " << flat[2 * i + 1] << ", cost " << q[4 * i] << " -> "
+                  << q[4 * i + 1] << ", status " << q[4 * i + 3] << std::endl;
+    if (quality) *quality = q;
+    return PhotometricSequence(flat.data(), GetNumImages());
+  }
+  // FitPhotometric at the initial estimate, Solve, then `rounds` times (FitPhotometric at the current estimate, Solve
+  // warm-started from it).  photometric (optional) receives the final parameters.  Not in the reference.
+  ImageData SolvePhotometric(const ImageData& initial_estimate, const int rounds,
+                             const PhotometricFitOptions& options = PhotometricFitOptions(), PhotometricSequence* photometric = nullptr) {
+    return SolvePhotometricJoint(initial_estimate, rounds, false, options, MotionRefinementOptions(), photometric, nullptr);
+  }
+  // The same with the motion refined as well: every round runs FitPhotometric, then (refine_motion) RefineMotion, then the
+  // warm Solve.  SolveJoint above is the motion-only loop.  Not in the reference.
+  ImageData SolvePhotometricJoint(const ImageData& initial_estimate, const int rounds, const bool refine_motion,
+                                  const PhotometricFitOptions& fit_options = PhotometricFitOptions(),
+                                  const MotionRefinementOptions& refinement_options = MotionRefinementOptions(),
+                                  PhotometricSequence* photometric = nullptr, AffineMotionSequence* motion = nullptr) {
+    if (rounds < 0) srmap_host::Fail("the number of photometric rounds must not be negative");
+    if (IsVerbose()) std::cout << "Photometric fit at the initial estimate:" << std::endl;
+    PhotometricSequence fitted = FitPhotometric(initial_estimate, fit_options);
+    ImageData x = Solve(initial_estimate);
+    for (int r = 0; r < rounds; ++r) {
+      if (IsVerbose()) std::cout << "Photometric round " << (r + 1) << " of " << rounds << ":" << std::endl;
+      fitted = FitPhotometric(x, fit_options);
+      if (refine_motion) {
+        const AffineMotionSequence refined = RefineMotion(x, refinement_options);
+        if (motion) *motion = refined;
+      }
+      x = Solve(x);
+    }
+    if (photometric) *photometric = fitted;
     return x;
   }
   // The data weights, one planar [C][h][w] block per observation ([K][C][h][w]): after a Huber solve the outlier map (the

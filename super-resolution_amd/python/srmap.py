@@ -61,6 +61,11 @@ class BlurFitOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("ksize", C.c_int), ("sum_to_one", C.c_int), ("ridge", C.c_double), ("apply", C.c_int)]
 
 
+class PhotometricFitOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("model", C.c_int), ("gauge_frame", C.c_int), ("min_gain", C.c_double),
+                ("max_gain", C.c_double), ("apply", C.c_int)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -95,6 +100,11 @@ _SIGNATURES = [
     ("srmap_blur_fit_options_default", None, [C.c_void_p]),
     ("srmap_fit_blur", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_fit_blur_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_problem_set_photometric", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_problem_get_photometric", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
+    ("srmap_photometric_fit_options_default", None, [C.c_void_p]),
+    ("srmap_fit_photometric", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_fit_photometric_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_problem_lr_size", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("srmap_set_observations", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_active_impl", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
@@ -536,6 +546,59 @@ class Problem:
             x, rep = self.solve(x, options)
             reports.append(rep)
         return x, reports, refinements
+
+    def set_photometric(self, gain_bias):
+        """Per-frame photometric parameters [K][2] = (gain, bias): the problem then solves against (y - bias) / gain.  None
+        restores the raw observations bit for bit."""
+        if gain_bias is None:
+            self.ctx.check(load().srmap_problem_set_photometric(self._h, None))
+        else:
+            a, pa = _d(gain_bias)
+            assert a.size == self.K * 2, (a.shape, self.K)
+            self.ctx.check(load().srmap_problem_set_photometric(self._h, pa))
+
+    def photometric(self):
+        """(parameters in force [K][2], ones and zeros when none are set; whether any are set)."""
+        out, flag = np.empty((self.K, 2)), C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_photometric(self._h, out.ctypes.data_as(c_double_p), C.byref(flag)))
+        return out, bool(flag.value)
+
+    def fit_photometric(self, x, model=0, gauge_frame=0, min_gain=0.25, max_gain=4.0, apply=True, stream=None, struct_size=None):
+        """srmap_fit_photometric: per frame the (gain, bias) that best map the model's prediction from the HR image x (a host
+        array [C][H][W], or a device tensor of the problem's dtype, read on `stream`) onto the RAW observations.  model: 0
+        gain and bias, 1 gain only, 2 bias only; gauge_frame keeps its parameters (-1: none).  Returns (gain_bias [K][2],
+        quality [K][4] = E at the parameters in force, E at the result, sum of the weights, status, sums [K][6]).  apply
+        installs the result as set_photometric would.  struct_size overrides the options' size field (tests)."""
+        o = PhotometricFitOptions()
+        load().srmap_photometric_fit_options_default(C.byref(o))
+        o.model, o.gauge_frame, o.min_gain, o.max_gain, o.apply = model, gauge_frame, min_gain, max_gain, (1 if apply else 0)
+        if struct_size is not None:
+            o.struct_size = struct_size
+        gb, q, sums = np.zeros((self.K, 2)), np.zeros((self.K, 4)), np.zeros((self.K, 6))
+        tail = (C.byref(o), gb.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), sums.ctypes.data_as(c_double_p))
+        if hasattr(x, "data_ptr"):
+            assert x.numel() == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_photometric_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
+        else:
+            a, pa = _d(x)
+            assert a.size == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_photometric(self._h, pa, *tail))
+        return gb, q, sums
+
+    def solve_photometric(self, x0, options=None, rounds=3, **fit):
+        """Exposure-compensated solve: fit_photometric at x0, a solve from x0, then `rounds` times (fit_photometric at the
+        current x, a solve warm-started from it).  Returns (x, [SolveReport per solve], [(gain_bias, quality) per fit]);
+        fit: fit_photometric's keywords."""
+        gb, q, _ = self.fit_photometric(x0, apply=True, **fit)
+        fits = [(gb, q)]
+        x, rep = self.solve(x0, options)
+        reports = [rep]
+        for _ in range(rounds):
+            gb, q, _ = self.fit_photometric(x, apply=True, **fit)
+            fits.append((gb, q))
+            x, rep = self.solve(x, options)
+            reports.append(rep)
+        return x, reports, fits
 
     def selfcheck(self):
         """Largest relative deviation of the solver's derived beta denominator from the directly summed y.dk (host-paced solves)."""
