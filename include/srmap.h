@@ -164,6 +164,45 @@ int srmap_problem_active_impl(const srmap_problem* p, int* impl);
  * only); its output goes straight into this call. */
 int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3);
 
+/* Dense per-frame displacement-field motion model (no reference counterpart; csrc/kernels_flow.hip): the
+ * general motion, of which a translation and an affine map are special cases.
+ * flow: K x 2 x H x W, the (ux, uy) planes of every frame on its HR-grid image, in HR pixels.
+ *   forward   (M_k x)(q) = four-tap bilinear sample of x at s = q + u_k(q), q an integer pixel of frame k's HR-grid image;
+ *             a tap outside the image contributes 0 (the affine model's sample).  The blur in force (Gaussian or
+ *             free-form) and the decimation apply unchanged: A_k = D B M_k.  MotionShift (dx, dy) corresponds to
+ *             u = (-dx, -dy), an affine F_k to u(q) = F_k^-1(q) - q.
+ *   storage   the field is kept in the problem's dtype (host doubles are rounded once; the _device form takes that dtype).
+ *             s = (double)q + (double)u is exact for both dtypes; the weights are the double products rounded to the
+ *             dtype, as in the affine model.  Device memory: K*2*H*W*sizeof(dtype) for the field plus K*H*W*4 bytes of
+ *             gather seeds (and the same again, transiently, while a new field is validated).
+ *   adjoint   M_k^T is the exact transpose of that matrix, gathered per HR pixel without atomics: two evaluations of one
+ *             input give bit-identical gradients.  For an HR pixel p the contributing q (those with q + u(q) strictly
+ *             inside p +- 1 per axis) are looked for in the 5 x 5 window around a seed stored per (k, p) when the field is
+ *             set: the fixed point of q <- round(p - u(clamp(q))) from q = p, at most 16 steps.
+ *   domain    VERIFIED when the field is set, by walking the forward direction: every (q, p) pair the forward kernel
+ *             multiplies must lie inside p's window.  Any violation (a fold, shear beyond the window) answers
+ *             SRMAP_EUNSUPPORTED; an entry that is not finite (in the problem's dtype) SRMAP_EINVAL; |u| > 2^20
+ *             SRMAP_EUNSUPPORTED; on an error the problem keeps the motion it had.  Sufficient for acceptance: with
+ *             dx = max_q |u(q + e_x) - u(q)|_inf and dy likewise along y, dx + dy <= 0.4 (then u is 0.4-Lipschitz in the
+ *             max norm, the seed ends within 1.5 / (1 - 0.4) + 0.4^16 * 2^20 < 3 of every contributing q).
+ *             Every affine map of srmap_problem_set_affine_motion's domain with |t| <= 2^20 is accepted (its field is
+ *             1/3-Lipschitz).
+ * A flow and an affine motion are alternatives: setting one replaces the other, and NULL (to either call) restores the
+ * motion the problem was created with (shifts_xy or none).  The flow persists across srmap_set_observations, the
+ * data-weight calls, srmap_problem_set_blur_kernel and srmap_problem_set_photometric.  While a flow is set the direct
+ * kernel family runs (srmap_problem_active_impl answers SRMAP_IMPL_DIRECT; SRMAP_IMPL_TILED answers SRMAP_EUNSUPPORTED at
+ * evaluation).  srmap_eval*, srmap_apply, srmap_apply_transpose (the exact adjoint), srmap_solve (CG, L-BFGS,
+ * split_channels), the traces, srmap_problem_set_cost_rows, the robust data term, a free-form blur and the photometric
+ * parameters honour it.  srmap_refine_motion (it fits matrices), srmap_fit_blur and srmap_fit_photometric (they have no
+ * sampling leg for a field) answer SRMAP_EUNSUPPORTED while a flow is set, as do evaluations and solves sharded over a
+ * communicator of more than one rank.  Not thread-safe against evaluations of the same problem; evaluations already
+ * enqueued are waited for.  The _device form reads flow_dev on hip_stream (NULL = the context's) and returns when the
+ * field is validated and installed.  srmap_problem_get_flow: *is_set, and the field in force as doubles when flow_out is
+ * not NULL and a flow is set. */
+int srmap_problem_set_flow(srmap_problem* p, const double* flow_host /* K x 2 x H x W doubles; NULL restores */);
+int srmap_problem_set_flow_device(srmap_problem* p, const void* flow_dev /* problem dtype */, void* hip_stream);
+int srmap_problem_get_flow(srmap_problem* p, double* flow_out /* K x 2 x H x W, optional */, int* is_set);
+
 /* Free-form blur kernel (no reference counterpart: BlurModule builds an isotropic Gaussian from (blur_radius, sigma) only,
  * blur_module.cpp:13-22).  taps: ksize x ksize doubles, row-major, the layout of the Gaussian the problem
  * builds itself.  The forward model CORRELATES with them, as filter2D does (blur_module.cpp:24-28):

@@ -200,6 +200,8 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
                                      double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
+  if (p->flow)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
   srmap_blur_fit_options opt;
   srmap_blur_fit_options_default(&opt);
   if (options) {

@@ -34,36 +34,7 @@ __device__ __forceinline__ void affine_source(const double* __restrict__ m, int 
 
 // (M_k x)(q), the four-tap sample at (sx, sy): affine_sample of sample_dev.hpp (shared with the blur fit)
 
-// weight of tap `p` along one axis for a sample at coordinate s: the forward kernel's (1 - f) / f, 0 for any other p
-__device__ __forceinline__ double affine_axis_weight(double s, int p) {
-  const double s0 = __builtin_floor(s), f = s - s0, pd = (double)p;
-  return s0 == pd ? 1.0 - f : (s0 + 1.0 == pd ? f : 0.0);
-}
-
-// (B^T D^T r)(q) at the HR pixel q = (pc, pr) inside the image: k_gather_direct's inner expression (zero-insertion
-// upsample, correlation with kernel.t(), each stage clipped to the domain; only the taps that land on the LR grid)
-template <typename T>
-__device__ __forceinline__ T blur_t_upsampled_at(const T* __restrict__ rk, const T* __restrict__ blur_t, const Geometry& g,
-                                                 int gs, int pr, int pc) {
-  T v = T(0);
-  int a0 = (g.hb - pr) % gs, e0 = (g.hb - pc) % gs;
-  if (a0 < 0) a0 += gs;
-  if (e0 < 0) e0 += gs;
-  for (int a = a0; a < g.b; a += gs) {
-    const int R = pr + a - g.hb;
-    if (R < 0 || R >= g.H) continue;
-    const int li = R / gs;
-    if (li >= g.h) continue;
-    for (int e = e0; e < g.b; e += gs) {
-      const int Cc = pc + e - g.hb;
-      if (Cc < 0 || Cc >= g.W) continue;
-      const int lj = Cc / gs;
-      if (lj >= g.w) continue;
-      v += blur_t[a * g.b + e] * rk[(size_t)li * g.w + lj];
-    }
-  }
-  return v;
-}
+// affine_axis_weight and blur_t_upsampled_at: sample_dev.hpp (shared with kernels_flow.hip)
 
 }  // namespace
 

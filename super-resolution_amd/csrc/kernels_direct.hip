@@ -103,6 +103,7 @@ template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
                           double* partials, int* nblocks, hipStream_t st, const T* dw) {
+  if (p->flow) return launch_forward_flow<T>(p, g, x, y, obs_C, obs_c0, out, k0, nk, partials, nblocks, st, dw);
   if (p->affine) return launch_forward_affine<T>(p, g, x, y, obs_C, obs_c0, out, k0, nk, partials, nblocks, st, dw);
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
@@ -360,6 +361,10 @@ template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring, T* ringbuf) {
+  if (p->flow) {
+    if (ring > 0 || ringbuf != nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which a displacement field has none of");
+    return launch_gather_flow<T>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
+  }
   if (p->affine) {
     if (ring > 0 || ringbuf != nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which an affine motion has none of");
     return launch_gather_affine<T>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);

@@ -164,6 +164,8 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
                                           double* quality_out, double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
+  if (p->flow)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while a displacement field is set (srmap_problem_set_flow)");
   srmap_motion_refinement_options opt;
   srmap_motion_refinement_options_default(&opt);
   if (options) {

@@ -244,6 +244,8 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
                                             double* quality_out, double* sums_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
+  if (p->flow)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
   srmap_photometric_fit_options opt;
   int rc = photometric_fit_options(p, options, &opt);
   if (rc) return rc;

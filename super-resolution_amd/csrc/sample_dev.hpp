@@ -1,7 +1,8 @@
 // sample_dev.hpp -- the sample functions of the forward model's warp M_k, shared by the kernels that evaluate it
-// (k_forward_direct of kernels_direct.hip, k_forward_affine of kernels_affine.hip) and the kernel that fits the blur to it
+// (k_forward_direct of kernels_direct.hip, k_forward_affine of kernels_affine.hip, k_forward_flow of kernels_flow.hip),
+// their transposes in gather form (k_gather_affine, k_gather_flow) and the kernel that fits the blur to it
 // (k_blur_fit_sums of blur_fit.hip): ONE copy of each expression, so that a fit sees exactly the warped image an
-// evaluation blurs.  A is the type the four products are formed and added in: the storage type T in the evaluation
+// evaluation blurs and a transpose recomputes exactly the weights its forward kernel multiplied by.  A is the type the four products are formed and added in: the storage type T in the evaluation
 // kernels, double in the fit (the taps and the weights are the same T values either way).
 #pragma once
 
@@ -62,6 +63,44 @@ __device__ __forceinline__ A affine_sample(const T* __restrict__ plane, int W, i
   const A v2 = (r1 && c0) ? (A)plane[(size_t)(sr + 1) * W + sc] : A(0);
   const A v3 = (r1 && c1) ? (A)plane[(size_t)(sr + 1) * W + sc + 1] : A(0);
   return ((v0 * (A)w0 + v1 * (A)w1) + v2 * (A)w2) + v3 * (A)w3;
+}
+
+// s = q + u(q) along one axis, the sample position of the displacement-field model (kernels_flow.hip): both conversions
+// and the one addition are exact in double for |u| <= 2^20, in both dtypes
+template <typename T>
+__device__ __forceinline__ double flow_source(int q, T u) {
+  return (double)q + (double)u;
+}
+
+// weight of tap `p` along one axis for a sample at coordinate s: the forward kernel's (1 - f) / f, 0 for any other p
+__device__ __forceinline__ double affine_axis_weight(double s, int p) {
+  const double s0 = __builtin_floor(s), f = s - s0, pd = (double)p;
+  return s0 == pd ? 1.0 - f : (s0 + 1.0 == pd ? f : 0.0);
+}
+
+// (B^T D^T r)(q) at the HR pixel q = (pc, pr) inside the image: k_gather_direct's inner expression (zero-insertion
+// upsample, correlation with kernel.t(), each stage clipped to the domain; only the taps that land on the LR grid)
+template <typename T>
+__device__ __forceinline__ T blur_t_upsampled_at(const T* __restrict__ rk, const T* __restrict__ blur_t, const Geometry& g,
+                                                 int gs, int pr, int pc) {
+  T v = T(0);
+  int a0 = (g.hb - pr) % gs, e0 = (g.hb - pc) % gs;
+  if (a0 < 0) a0 += gs;
+  if (e0 < 0) e0 += gs;
+  for (int a = a0; a < g.b; a += gs) {
+    const int R = pr + a - g.hb;
+    if (R < 0 || R >= g.H) continue;
+    const int li = R / gs;
+    if (li >= g.h) continue;
+    for (int e = e0; e < g.b; e += gs) {
+      const int Cc = pc + e - g.hb;
+      if (Cc < 0 || Cc >= g.W) continue;
+      const int lj = Cc / gs;
+      if (lj >= g.w) continue;
+      v += blur_t[a * g.b + e] * rk[(size_t)li * g.w + lj];
+    }
+  }
+  return v;
 }
 
 }  // namespace srmap

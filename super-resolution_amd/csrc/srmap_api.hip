@@ -580,7 +580,7 @@ void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
   void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_affine, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
+                  p->d_affine, p->d_flow, p->d_flow_seed, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
   for (int* t : p->d_ytabs) (void)hipFree(t);
@@ -617,6 +617,12 @@ int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) 
     p->affine = false;
     p->affine_recs.clear();
   }
+  // alternatives: an affine motion replaces a displacement field, and NULL restores the created motion
+  if (p->d_flow) (void)hipFree(p->d_flow);
+  if (p->d_flow_seed) (void)hipFree(p->d_flow_seed);
+  p->d_flow = nullptr;
+  p->d_flow_seed = nullptr;
+  p->flow = false;
   p->plan_gen++;
   if (ztile_plan(p)) ztile_preload(p);  // "not covered" while an affine motion is set
   return SRMAP_OK;

@@ -20,6 +20,9 @@ constexpr int kMaxCustomBlur = 7;      // largest size of a free-form kernel (sr
 // [ia ib itx; ic id ity], [6..11] the forward map [a b tx; c d ty], [12..13] the candidate radii of the transpose gather
 constexpr int kAffineRec = 16;
 constexpr double kAffineMaxDeviation = 0.25;  // max(|a-1|+|b|, |c|+|d-1|): bounds the gather at 3 x 3 candidates
+// Displacement-field motion (srmap_problem_set_flow, kernels_flow.hip): the transpose gathers the (2 r + 1)^2 candidates
+// around a stored seed
+constexpr int kFlowRadius = 2;
 
 // One MotionModule warp (forward or transpose) of one frame, as cv::warpAffine
 // evaluates it (motion_module.cpp:18-51): source pixel = destination + (ox, oy)
@@ -117,6 +120,12 @@ struct srmap_problem {
   bool affine = false;
   std::vector<double> affine_recs;  // K x kAffineRec (host mirror of d_affine)
   double* d_affine = nullptr;
+  // displacement-field motion model (an alternative to the affine one: setting either replaces the other): when set, the
+  // data term runs kernels_flow.hip.  d_flow: [K][2][H][W] dtype, the (ux, uy) planes per frame; d_flow_seed: [K][H][W]
+  // packed seeds of the transpose gather, both validated when they were set
+  bool flow = false;
+  void* d_flow = nullptr;
+  int* d_flow_seed = nullptr;
   std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
   std::vector<double> blur2d_t;
   std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
@@ -226,6 +235,13 @@ int launch_gather_affine(srmap_problem* p, const Geometry& geo, const T* resid, 
                          bool accumulate, hipStream_t st);
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
+// ---- displacement-field motion (kernels_flow.hip): the two launchers above route here when p->flow ----
+template <typename T>
+int launch_forward_flow(srmap_problem* p, const Geometry& g, const T* x, const T* y, int obs_C, int obs_c0, T* out,
+                        int k0, int nk, double* partials, int* nblocks, hipStream_t st, const T* dw);
+template <typename T>
+int launch_gather_flow(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk, double out_scale,
+                       bool accumulate, hipStream_t st);
 // ---- the motion fits' shared kernels and per-pass buffers (motion_fit.hip) ----
 struct AffineMap;  // affine_map.hpp
 // dst[k][h/2][w/2] = mean of the 2 x 2 blocks of src[k][h][w], k < frames: one level of a box pyramid

@@ -23,6 +23,9 @@ int main(int argc, char** argv) {
       "  [--downsampling_scale=2] [--number_of_frames=4]\n"
       "  not a reference flag: [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                        an error together with --motion_sequence_path)\n"
+      "                        [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
+      "                        [frames][2][H][W] = the (ux, uy) planes in HR pixels at the input image's size; an error together\n"
+      "                        with --motion_sequence_path or --affine_motion_path)\n"
       "                        [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
       "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)\n"
       "                        [--photometric_path=<file>] (per-frame exposure, 'gain bias' per line, the bias in pixel units\n"
@@ -34,6 +37,7 @@ int main(int argc, char** argv) {
   ImageModelParameters parameters;
   parameters.motion_sequence_path = flags.Str("motion_sequence_path");
   parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
+  const std::string flow_motion_path = flags.Str("flow_motion_path");  // not a reference flag
   parameters.blur_kernel_path = flags.Str("blur_kernel_path");  // not a reference flag
   const std::string photometric_path = flags.Str("photometric_path");  // not a reference flag
   parameters.blur_radius = flags.Int("blur_radius", 0);
@@ -46,6 +50,10 @@ int main(int argc, char** argv) {
   flags.Require("input_image");
   if (!parameters.affine_motion_sequence_path.empty() && !parameters.motion_sequence_path.empty()) {
     std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
+    return 1;
+  }
+  if (!flow_motion_path.empty() && (!parameters.affine_motion_sequence_path.empty() || !parameters.motion_sequence_path.empty())) {
+    std::fprintf(stderr, "ERROR: --flow_motion_path excludes --motion_sequence_path and --affine_motion_path.\n");
     return 1;
   }
 
@@ -67,6 +75,14 @@ int main(int argc, char** argv) {
     }
     if (parameters.noise_sigma > 0.0) noise_after.reset(new AdditiveNoiseModule(parameters.noise_sigma, parameters.noise_seed));
     parameters.noise_sigma = 0.0;
+  }
+  if (!flow_motion_path.empty()) {
+    parameters.flow_motion_sequence.LoadSequenceFromFile(flow_motion_path, image_data.GetImageSize().width, image_data.GetImageSize().height);
+    if (parameters.flow_motion_sequence.GetNumMotions() < number_of_frames) {
+      std::fprintf(stderr, "ERROR: --flow_motion_path holds %d frames, --number_of_frames asks for %d.\n",
+                   parameters.flow_motion_sequence.GetNumMotions(), number_of_frames);
+      return 1;
+    }
   }
   const ImageModel image_model = ImageModel::CreateImageModel(parameters);
   if (!extension.empty() && extension[0] != '.') extension = "." + extension;

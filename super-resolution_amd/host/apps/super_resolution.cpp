@@ -5,7 +5,8 @@
 // truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
 // least-squares solver as the reference does (super_resolution.cpp:134-141; any
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
-// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor are
+// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor is
+// --flow_motion_path: a dense displacement field per frame (srmap_problem_set_flow).  Nor are
 // --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
 // --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion), nor
 // --blur_kernel_path (a free-form blur kernel, srmap_problem_set_blur_kernel) and --fit_blur_from / --fit_blur_ksize /
@@ -48,6 +49,10 @@ int main(int argc, char** argv) {
       "  not reference flags: [--data_loss=l2|huber] [--huber_delta=0.02] (robust data term, pixel units 0..1)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
+      "                       [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
+      "                       [frames][2][H][W] = the (ux, uy) planes in HR pixels at the high-resolution size; an error\n"
+      "                       together with --motion_sequence_path, --affine_motion_path, --registration,\n"
+      "                       --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
       "                       [--registration=translational|affine] (estimate the solver's motion from the LR frames, in HR\n"
       "                       pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
       "                       an error together with either motion file)\n"
@@ -85,6 +90,8 @@ int main(int argc, char** argv) {
   model_parameters.motion_sequence_path = flags.Str("motion_sequence_path");
   // not a reference flag: the affine motion model of include/srmap.h (srmap_problem_set_affine_motion)
   model_parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");
+  // not a reference flag: the displacement-field motion model of include/srmap.h (srmap_problem_set_flow)
+  const std::string flow_motion_path = flags.Str("flow_motion_path");
   IRLSMapSolverOptions solver_options;
   solver_options.max_num_irls_iterations = flags.Int("optimization_iterations", 20);
   solver_options.max_num_solver_iterations = flags.Int("solver_iterations", 50);
@@ -129,6 +136,19 @@ int main(int argc, char** argv) {
   if (!model_parameters.affine_motion_sequence_path.empty() && !model_parameters.motion_sequence_path.empty()) {
     std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
     return 1;
+  }
+  if (!flow_motion_path.empty()) {
+    // the field IS the motion: nothing else may give or estimate one, and the three fits have no sampling leg for a field
+    const char* other = !model_parameters.motion_sequence_path.empty() ? "--motion_sequence_path"
+                        : !model_parameters.affine_motion_sequence_path.empty() ? "--affine_motion_path"
+                        : !registration_name.empty() ? "--registration"
+                        : refine_motion_rounds != 0 ? "--refine_motion_rounds"
+                        : !fit_blur_from.empty() ? "--fit_blur_from"
+                        : photometric_rounds >= 0 ? "--photometric_rounds" : nullptr;
+    if (other) {
+      std::fprintf(stderr, "ERROR: --flow_motion_path and %s exclude each other.\n", other);
+      return 1;
+    }
   }
   if (!registration_name.empty() && registration_name != "translational" && registration_name != "affine") {
     std::fprintf(stderr, "ERROR: --registration is 'translational' or 'affine'.\n");
@@ -183,12 +203,23 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "WARNING: Invalid data_loss flag. Using the least-squares (l2) data term.\n");
   }
 
-  const ImageModel image_model = ImageModel::CreateImageModel(model_parameters);
-
   ImageData high_res_image;
   std::vector<ImageData> low_res_images;
+  if (generate_lr_images) high_res_image = util::LoadImage(data_path);
+  else low_res_images = util::LoadImages(data_path);
+  if (!flow_motion_path.empty()) {  // the file has no header: its size is checked against the HR geometry
+    if (!generate_lr_images && low_res_images.empty()) {
+      std::fprintf(stderr, "Check failed: At least one low-resolution image is required for super-resolution.\n");
+      return 1;
+    }
+    const cv::Size hr = generate_lr_images ? high_res_image.GetImageSize()
+                                           : cv::Size(low_res_images[0].GetImageSize().width * upsampling_scale,
+                                                      low_res_images[0].GetImageSize().height * upsampling_scale);
+    model_parameters.flow_motion_sequence.LoadSequenceFromFile(flow_motion_path, hr.width, hr.height);
+  }
+  const ImageModel image_model = ImageModel::CreateImageModel(model_parameters);
+
   if (generate_lr_images) {  // data_path is the ground truth (super_resolution.cpp:285-299)
-    high_res_image = util::LoadImage(data_path);
     // the generating model carries the AdditiveNoiseModule (sigma in 0..255 units), the solver's does not
     ImageModelParameters with_noise = model_parameters;
     with_noise.noise_sigma = noise_sigma;
@@ -196,7 +227,6 @@ int main(int argc, char** argv) {
     const ImageModel image_model_with_noise = ImageModel::CreateImageModel(with_noise);
     for (int i = 0; i < number_of_frames; ++i) low_res_images.push_back(image_model_with_noise.ApplyToImage(high_res_image, i));
   } else {
-    low_res_images = util::LoadImages(data_path);
     if (!ground_truth_image.empty()) high_res_image = util::LoadImage(ground_truth_image);
   }
   if (low_res_images.empty()) {

@@ -2,7 +2,7 @@
 // HIP library through the C ABI:
 //   DegradationOperator  src/image_model/degradation_operator.h:17-57
 //   MotionModule         src/image_model/motion_module.{h,cpp}; also constructible from an AffineMotionSequence
-//                        (motion/affine_motion.h; no reference counterpart)
+//                        (motion/affine_motion.h) or a FlowMotionSequence (motion/flow_motion.h); no reference counterpart
 //   BlurModule           src/image_model/blur_module.{h,cpp}; also constructible from a BlurKernel, a free-form PSF
 //                        (image_model/blur_kernel.h; no reference counterpart)
 //   DownsamplingModule   src/image_model/downsampling_module.{h,cpp}
@@ -22,6 +22,7 @@
 #include "image/image_data.h"
 #include "image_model/blur_kernel.h"
 #include "motion/affine_motion.h"
+#include "motion/flow_motion.h"
 #include "motion/motion_shift.h"
 #include "util/srmap_host.h"
 
@@ -65,9 +66,14 @@ class DegradationOperator {
 
 class MotionModule : public DegradationOperator {
  public:
-  explicit MotionModule(const MotionShiftSequence& sequence) : sequence_(sequence), affine_(false) {}
+  explicit MotionModule(const MotionShiftSequence& sequence) : sequence_(sequence), affine_(false), flow_(false) {}
   // not in the reference: per-frame affine warps (the exact-coordinate bilinear warp and its exact adjoint, include/srmap.h)
-  explicit MotionModule(const AffineMotionSequence& sequence) : affine_sequence_(sequence), affine_(true) {}
+  explicit MotionModule(const AffineMotionSequence& sequence) : affine_sequence_(sequence), affine_(true), flow_(false) {}
+  // not in the reference: a dense displacement field per frame (srmap_problem_set_flow, include/srmap.h); the transpose
+  // runs at the field's own size only
+  explicit MotionModule(const FlowMotionSequence& sequence) : flow_sequence_(sequence), affine_(false), flow_(true) {
+    if (sequence.Empty()) srmap_host::Fail("MotionModule: the flow motion sequence is empty");
+  }
   void ApplyToImage(ImageData* image_data, const int index) const override {
     CheckIndex(index);
     srmap_host::RunChain(Chain(), image_data, index, false);
@@ -77,19 +83,27 @@ class MotionModule : public DegradationOperator {
     srmap_host::RunChain(Chain(), image_data, index, true);
   }
   void Describe(srmap_host::ChainParams* c) const override {
-    if (affine_) { c->affine_2x3 = affine_sequence_.Flat(); c->shifts_xy.clear(); }
-    else { c->shifts_xy = sequence_.Flat(); c->affine_2x3.clear(); }
+    c->shifts_xy.clear();
+    c->affine_2x3.clear();
+    c->flow.clear();
+    if (flow_) { c->flow = flow_sequence_.Flat(); c->flow_width = flow_sequence_.GetWidth(); c->flow_height = flow_sequence_.GetHeight(); }
+    else if (affine_) c->affine_2x3 = affine_sequence_.Flat();
+    else c->shifts_xy = sequence_.Flat();
   }
   bool IsAffine() const { return affine_; }
+  bool IsFlow() const { return flow_; }
 
  private:
   void CheckIndex(const int index) const {
-    if (affine_) affine_sequence_.GetAffineMotion(index); else sequence_.GetMotionShift(index);
+    if (flow_) flow_sequence_.CheckIndex(index);
+    else if (affine_) affine_sequence_.GetAffineMotion(index);
+    else sequence_.GetMotionShift(index);
   }
   srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const MotionShiftSequence sequence_;
   const AffineMotionSequence affine_sequence_;
-  const bool affine_;
+  const FlowMotionSequence flow_sequence_;
+  const bool affine_, flow_;
 };
 
 class BlurModule : public DegradationOperator {
@@ -176,6 +190,9 @@ struct ImageModelParameters {
   // not in the reference: per-frame affine motion ("a b tx c d ty" per line); excludes motion_sequence(_path)
   std::string affine_motion_sequence_path = "";
   AffineMotionSequence affine_motion_sequence;
+  // not in the reference: a dense displacement field per frame (motion/flow_motion.h).  The file has no header, so the
+  // caller loads it with the HR geometry (FlowMotionSequence::LoadSequenceFromFile); excludes the two sequences above
+  FlowMotionSequence flow_motion_sequence;
   // not in the reference: a free-form blur kernel (text file: ksize, then ksize^2 taps); it replaces the Gaussian of
   // blur_radius / blur_sigma
   std::string blur_kernel_path = "";
@@ -195,6 +212,11 @@ class ImageModel {
     const bool affine = !parameters.affine_motion_sequence_path.empty() || parameters.affine_motion_sequence.GetNumMotions() > 0;
     if (affine && (!parameters.motion_sequence_path.empty() || parameters.motion_sequence.GetNumMotionShifts() > 0))
       srmap_host::Fail("both an affine motion sequence and a motion shift sequence were given: a model has one MotionModule");
+    if (!parameters.flow_motion_sequence.Empty()) {
+      if (affine || !parameters.motion_sequence_path.empty() || parameters.motion_sequence.GetNumMotionShifts() > 0)
+        srmap_host::Fail("a flow motion sequence and another motion sequence were given: a model has one MotionModule");
+      model.AddDegradationOperator(std::make_shared<MotionModule>(parameters.flow_motion_sequence));
+    }
     if (affine) {
       AffineMotionSequence seq = parameters.affine_motion_sequence;
       if (seq.GetNumMotions() == 0) seq.LoadSequenceFromFile(parameters.affine_motion_sequence_path);

@@ -45,22 +45,31 @@ struct ProblemDeleter {
 };
 using ProblemPtr = std::unique_ptr<srmap_problem, ProblemDeleter>;
 
-// Parameters of one operator chain  D(scale) . B(ksize, sigma | free-form taps) . M(shifts | matrices).
+// Parameters of one operator chain  D(scale) . B(ksize, sigma | free-form taps) . M(shifts | matrices | displacement fields).
 struct ChainParams {
   int scale = 1;
   std::vector<double> shifts_xy;  // empty = no translational MotionModule
   std::vector<double> affine_2x3;  // K x [a b tx; c d ty]: a MotionModule over an AffineMotionSequence (then shifts_xy is empty)
+  // K x 2 x flow_height x flow_width: a MotionModule over a FlowMotionSequence (then shifts_xy and affine_2x3 are empty);
+  // the HR image a chain is applied to must have that size
+  std::vector<double> flow;
+  int flow_width = 0, flow_height = 0;
   int frames = 1;
   int blur_ksize = 0;
   double blur_sigma = 0.0;
   std::vector<double> blur_taps;  // blur_taps_ksize^2 taps of a free-form kernel (then blur_ksize / blur_sigma are unused); empty = the Gaussian
   int blur_taps_ksize = 0;
-  bool HasMotion() const { return !shifts_xy.empty() || !affine_2x3.empty(); }
-  int NumMotions() const { return static_cast<int>(affine_2x3.empty() ? shifts_xy.size() / 2 : affine_2x3.size() / 6); }
+  bool HasMotion() const { return !shifts_xy.empty() || !affine_2x3.empty() || !flow.empty(); }
+  size_t FlowFrame() const { return 2 * static_cast<size_t>(flow_width) * static_cast<size_t>(flow_height); }
+  int NumMotions() const {
+    if (!flow.empty()) return static_cast<int>(flow.size() / FlowFrame());
+    return static_cast<int>(affine_2x3.empty() ? shifts_xy.size() / 2 : affine_2x3.size() / 6);
+  }
   // solvers: n observations need at least n motions; the rest is dropped
   void TrimMotions(size_t n) {
     if (!shifts_xy.empty()) shifts_xy.resize(2 * n);
     if (!affine_2x3.empty()) affine_2x3.resize(6 * n);
+    if (!flow.empty()) flow.resize(FlowFrame() * n);
   }
 };
 
@@ -68,6 +77,11 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
   srmap_problem_desc d;
   d.hr_width = width; d.hr_height = height; d.channels = channels;
   if (!c.shifts_xy.empty() && !c.affine_2x3.empty()) Fail("a chain has either motion shifts or affine motions, not both");
+  if (!c.flow.empty() && (!c.shifts_xy.empty() || !c.affine_2x3.empty()))
+    Fail("a chain has either a flow motion or motion shifts / affine motions, not both");
+  if (!c.flow.empty() && (c.flow_width != width || c.flow_height != height))
+    Fail(("the flow motion is given for a " + std::to_string(c.flow_width) + " x " + std::to_string(c.flow_height) +
+          " high-resolution image, the model is applied at " + std::to_string(width) + " x " + std::to_string(height)).c_str());
   d.frames = c.HasMotion() ? c.NumMotions() : c.frames;
   d.scale = c.scale;
   d.shifts_xy = c.shifts_xy.empty() ? nullptr : c.shifts_xy.data();
@@ -78,6 +92,7 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
   ProblemPtr problem(p);
   if (!c.affine_2x3.empty())
     Check(srmap_problem_set_affine_motion(p, c.affine_2x3.data()), "srmap_problem_set_affine_motion");
+  if (!c.flow.empty()) Check(srmap_problem_set_flow(p, c.flow.data()), "srmap_problem_set_flow");
   if (!c.blur_taps.empty())
     Check(srmap_problem_set_blur_kernel(p, c.blur_taps_ksize, c.blur_taps.data()), "srmap_problem_set_blur_kernel");
   return problem;

@@ -95,6 +95,9 @@ _SIGNATURES = [
     ("srmap_problem_set_impl", C.c_int, [C.c_void_p, C.c_int]),
     ("srmap_problem_set_solver", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("srmap_problem_set_affine_motion", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_problem_set_flow", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_problem_set_flow_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("srmap_problem_get_flow", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
     ("srmap_problem_set_blur_kernel", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     ("srmap_problem_get_blur_kernel", C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_double_p]),
     ("srmap_blur_fit_options_default", None, [C.c_void_p]),
@@ -280,6 +283,30 @@ class Context:
             self._h = None
 
 
+def flow_from_shifts(shifts, H, W):
+    """The displacement field [K][2][H][W] of the translations shifts [K][2] = (dx, dy) in MotionShift's convention:
+    u = (-dx, -dy) everywhere."""
+    s = np.asarray(shifts, dtype=np.float64).reshape(-1, 2)
+    out = np.empty((len(s), 2, H, W))
+    out[:, 0] = -s[:, 0, None, None]
+    out[:, 1] = -s[:, 1, None, None]
+    return out
+
+
+def flow_from_affine(matrices, H, W):
+    """The displacement field [K][2][H][W] of the affine maps matrices [K][2][3] = [a b tx; c d ty] (the convention of
+    Problem.set_affine_motion): u(q) = F^-1(q) - q."""
+    m = np.asarray(matrices, dtype=np.float64).reshape(-1, 2, 3)
+    qy, qx = np.mgrid[0:H, 0:W].astype(np.float64)
+    out = np.empty((len(m), 2, H, W))
+    for k, F in enumerate(m):
+        Li = np.linalg.inv(F[:, :2])
+        ti = -Li @ F[:, 2]
+        out[k, 0] = (Li[0, 0] * qx + (Li[0, 1] * qy + ti[0])) - qx
+        out[k, 1] = (Li[1, 0] * qx + (Li[1, 1] * qy + ti[1])) - qy
+    return out
+
+
 def default_irls_options():
     o = IrlsOptions()
     load().srmap_irls_options_default(C.byref(o))
@@ -332,6 +359,32 @@ class Problem:
             a, pa = _d(matrices)
             assert a.size == self.K * 6, (a.shape, self.K)
             self.ctx.check(load().srmap_problem_set_affine_motion(self._h, pa))
+
+    def set_flow(self, flow, stream=None):
+        """Per-frame displacement field [K][2][H][W], the (ux, uy) planes in HR pixels: frame k's HR-grid image at q is x
+        sampled bilinearly at q + u_k(q).  A host array (rounded once to the problem's dtype) or a device tensor of the
+        problem's dtype (anything with data_ptr(); read on `stream`, None = the context's).  None restores the motion the
+        problem was created with.  A flow and an affine motion are alternatives: setting one replaces the other."""
+        n = self.K * 2 * self.H * self.W
+        if flow is None:
+            self.ctx.check(load().srmap_problem_set_flow(self._h, None))
+        elif hasattr(flow, "data_ptr"):
+            assert flow.numel() == n and flow.is_contiguous() and flow.element_size() == (4 if self.dtype == F32 else 8)
+            self.ctx.check(load().srmap_problem_set_flow_device(self._h, C.c_void_p(flow.data_ptr()), C.c_void_p(stream or 0)))
+        else:
+            a, pa = _d(flow)
+            assert a.size == n, (a.shape, self.K, self.H, self.W)
+            self.ctx.check(load().srmap_problem_set_flow(self._h, pa))
+
+    def flow(self):
+        """The displacement field in force, [K][2][H][W] doubles, or None when no flow is set."""
+        v = C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_flow(self._h, None, C.byref(v)))
+        if not v.value:
+            return None
+        out = np.empty((self.K, 2, self.H, self.W))
+        self.ctx.check(load().srmap_problem_get_flow(self._h, out.ctypes.data_as(c_double_p), C.byref(v)))
+        return out
 
     def set_blur_kernel(self, taps):
         """Free-form blur kernel [ksize][ksize] (odd, 1...7; the forward model correlates with it, the adjoint is its flip in
