@@ -451,6 +451,59 @@ int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, int height,
                           const srmap_affine_registration_options* options /* NULL = defaults */,
                           double* affine_2x3_out /* num_images x 6 */, double* quality_out /* optional, 4 per image */);
 
+/* Dense flow registration (no reference counterpart; csrc/registration_flow.hip; it closes what DESIGN.md
+ * 3.11 left out: the estimate of the fields srmap_problem_set_flow takes).  For every image k >= 1 a displacement field u_k
+ * on image k's grid with I_0(q + u_k(q)) ~= I_k(q) -- the convention of srmap_problem_set_flow, image 0 playing x.  Image 0
+ * gets u = 0.  All arithmetic is f64, every operation rounded on its own (no fused multiply-adds).
+ *   pyramid   2 x 2 box means of every image (an odd last row / column is dropped), halved while min(w, h) >= 32 (the
+ *             coarsest level's shorter side is 16...31: the field needs the coarse levels for its range), at most 12
+ *             levels; max_levels caps the count;
+ *   start     u = 0 at the coarsest level; with initial_affine_2x3 (the matrices of srmap_register_affine, input pixels)
+ *             u(q) = F_k^-1(q) - q of the matrix taken down the pyramid -- rotations and shifts beyond the pyramid's range;
+ *   transfer  u_fine(q) = 2 * bilinear(u_coarse at (q - 1/2) / 2), coordinates clamped to the coarse image;
+ *   pass      `warps` passes per level, a fixed count (no convergence test, nothing returns to the host).  At s = q + u(q):
+ *             Tw and the central-difference gradient planes (Tx, Ty) of I_0 (one-sided at the border), four-tap bilinear
+ *             samples; where a tap is outside I_0, e = Tx = Ty = 0; e = Tw - I_k(q).  Window sums (a, b, c, p, q) of
+ *             (Tx Tx, Tx Ty, Ty Ty, Tx e, Ty e), the window separable and triangular, weight 2 r + 1 - |d| per axis for
+ *             |d| <= 2 r (r = window_radius), along x then along y, d ascending, pixels outside the image contributing 0.
+ *             lambda = damping (a + c) / 2, a' = a + lambda, c' = c + lambda, det = a' c' - b b;
+ *             du = -(c' p - b q, a' q - b p) / det where det > 0, else 0; each component clipped to +-1 px of the level;
+ *             u <- the box mean of u + du over radius smooth_radius, divided by the number of in-image pixels of the box.
+ *   output    flow_out [num_images][2][s h][s w] (x then y component, the K*2*H*W layout of srmap_problem_set_flow) with
+ *             s = hr_scale: U_k(Q) = s * bilinear(u_k at Q / s), clamped -- LR pixel q is HR pixel s q, as in
+ *             srmap_register_affine.
+ * valid_out (optional, [num_images][h][w] doubles, input resolution): 1 where the four taps of I_0 at q + u_k(q) are inside
+ * AND q is at least valid_margin pixels from every edge, else 0; image 0 is all 1.  The field is wrong by pixels in the few
+ * border pixels whose content image 0 does not hold: pass the mask on as data weights (srmap_set_data_weights).
+ * quality_out (optional, 3 doubles per image): [3i] root mean squared residual I_0(q + u) - I_k(q) over the valid pixels,
+ * [3i+1] the valid fraction, [3i+2] the largest horizontal plus the largest vertical neighbour difference of the returned
+ * field (what the sufficient condition of srmap_problem_set_flow reads).  Image 0: (0, 1, 0).
+ * What this estimator is NOT: it is dense, LOCAL and unregularised beyond the window and the box mean, so it cannot resolve
+ * motion finer than the window; it has NO occlusion handling; it registers ONE plane per image; and it is NOT fitted through
+ * the blur and decimation of the forward model -- on aliased LR frames it plateaus near 0.2 HR px.  A flow leg of
+ * srmap_refine_motion is future work.
+ * num_images == 0 returns SRMAP_OK and writes nothing.  SRMAP_EINVAL: width or height < 16; a struct_size that is not this
+ * library's; hr_scale < 1, warps < 1, window_radius outside 1...8, smooth_radius outside 0...8, a negative or non-finite
+ * damping, a negative valid_margin or max_levels; an output grid beyond 2^30 pixels; an image that is not finite; an initial
+ * matrix (rows 1...num_images-1; row 0 is ignored) that is not finite or outside the affine model's domain.  Results are
+ * bit-identical run to run and do not depend on the other images of the stack. */
+typedef struct {
+  int struct_size;                   /* filled by the _default call; a mismatch is SRMAP_EINVAL */
+  int hr_scale;                      /* 1 */
+  int warps;                         /* 8, per level */
+  int window_radius;                 /* 4 (1...8): the triangular window spans 2 r pixels to each side */
+  double damping;                    /* 0.05 */
+  int smooth_radius;                 /* 2 (0...8) */
+  int valid_margin;                  /* 3 px */
+  int max_levels;                    /* 0 = automatic; 1 = full resolution only */
+  const double* initial_affine_2x3;  /* NULL = start from u = 0; else num_images x 6, input-pixel units */
+} srmap_flow_registration_options;
+void srmap_flow_registration_options_default(srmap_flow_registration_options* options);
+int srmap_register_flow(srmap_ctx* ctx, int num_images, int width, int height, const double* images_host,
+                        const srmap_flow_registration_options* options /* NULL = defaults */,
+                        double* flow_out /* num_images x 2 x (s h) x (s w) */, double* valid_out /* optional */,
+                        double* quality_out /* optional, 3 per image */);
+
 /* Joint motion refinement (no reference counterpart; csrc/motion_refinement.hip; it closes what DESIGN.md
  * 3.7 left out: a registration that honours the forward model and the data weights).  With an HR estimate x, every frame
  * k >= 1 has its matrix re-fitted THROUGH the affine forward model of 3.6 (srmap_problem_set_affine_motion):

@@ -1,0 +1,448 @@
+// registration_flow.hip -- dense flow registration of a frame stack on the GPU (srmap_register_flow).
+//
+// For every frame k >= 1 a field u_k on frame k's grid with I_0(q + u_k(q)) ~= I_k(q): the convention of the
+// displacement-field motion model (kernels_flow.hip), frame 0 playing x.  No reference counterpart; the checker is
+// tests/flow_registration_restatement.py.
+//   1. box pyramid of the whole stack, built once (k_down2_stack, motion_fit.hip), halved while the shorter side is >= 32,
+//      and the two gradient planes of frame 0 at every level (k_flow_gradients);
+//   2. start at the coarsest level: u = 0, or u(q) = F^-1(q) - q of the caller's matrices taken down the pyramid;
+//   3. per level a FIXED number of warp passes, each two launches for all frames (k_flow_lk_pass, k_flow_smooth), then
+//      k_flow_resample to the next level;
+//   4. k_flow_resample to the HR grid, k_flow_finish (validity mask, residual sums) and k_flow_maxdiff (the neighbour
+//      differences of the returned field), their per-workgroup records added on the host in index order.
+// Nothing comes back to the host between the upload and the final copies: one stream wait per call.
+// Every kernel here keeps fp contraction OFF: each operation is rounded on its own and the sums run in the order the
+// restatement states, so the result does not depend on the tile decomposition and the restatement forms the same numbers.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "affine_map.hpp"
+#include "motion_fit_dev.hpp"
+#include "srmap_internal.hpp"
+
+namespace srmap {
+
+namespace {
+
+constexpr int kMaxLevels = 12;
+constexpr int kMinSize = 16;
+constexpr int kMaxWindowRadius = 8;
+constexpr int kMaxSmoothRadius = 8;
+constexpr int kMaxRecordBlocks = 1024;
+
+// the four-tap sample at p = &plane[y0][x0] with fractions (fx, fy); x0 <= w - 2, y0 <= h - 2
+__device__ __forceinline__ double bilinear4(const double* __restrict__ p, int w, double fx, double fy) {
+#pragma clang fp contract(off)
+  return (1.0 - fy) * ((1.0 - fx) * p[0] + fx * p[1]) + fy * ((1.0 - fx) * p[w] + fx * p[w + 1]);
+}
+
+// the four taps at (sx, sy) are inside a w x h image (a NaN position is outside)
+__device__ __forceinline__ bool taps_inside(double sx, double sy, int w, int h) {
+  return sx >= 0.0 && sx < (double)(w - 1) && sy >= 0.0 && sy < (double)(h - 1);
+}
+
+// gx, gy [h][w]: central differences of img, one-sided at the border.  w, h >= 2.
+__global__ __launch_bounds__(256) void k_flow_gradients(const double* __restrict__ img, int w, int h, double* __restrict__ gx,
+                                                        double* __restrict__ gy) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= w * h) return;
+  const int y = i / w, x = i - y * w;
+  const double* p = img + i;
+  gx[i] = x == 0 ? p[1] - p[0] : x == w - 1 ? p[0] - p[-1] : 0.5 * (p[1] - p[-1]);
+  gy[i] = y == 0 ? p[w] - p[0] : y == h - 1 ? p[0] - p[-w] : 0.5 * (p[w] - p[-w]);
+}
+
+// u[f][2][h][w] = G_f(q) - q, G_f = table[f][6] (the inverse of frame f + 1's matrix at this level).  grid = (pixels, frames)
+__global__ __launch_bounds__(256) void k_flow_affine_start(const double* __restrict__ table, int w, int h, double* __restrict__ u) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= w * h) return;
+  const int y = i / w, x = i - y * w;
+  const double* m = table + (size_t)blockIdx.y * 6;
+  double* o = u + (size_t)blockIdx.y * 2 * w * h;
+  o[i] = affine_coord(m[0], m[1], m[2], (double)x, (double)y) - (double)x;
+  o[(size_t)w * h + i] = affine_coord(m[3], m[4], m[5], (double)x, (double)y) - (double)y;
+}
+
+// One warp pass for every frame, before the smoothing: v = u + du.  grid = (tiles_x * tiles_y, frames - 1), 256 threads,
+// an output tile of TX x TY pixels, window radius r <= RMAX.
+//   1. the tile with its 2 r halo: Tx, Ty, e at q + u(q) into LDS (0 outside the image or where a tap is outside);
+//   2. per product (Tx Tx, Tx Ty, Ty Ty, Tx e, Ty e): the triangular sums along x of the halo rows into LDS, d ascending,
+//      then along y into a register, d ascending -- every window sum is formed from the same numbers in the same order
+//      whichever tile holds it;
+//   3. the damped 2 x 2 solve, the step clipped to +-1 px.
+template <int TX, int TY, int RMAX>
+__global__ __launch_bounds__(256) void k_flow_lk_pass(const double* __restrict__ i0, const double* __restrict__ gx,
+                                                      const double* __restrict__ gy, const double* __restrict__ frames,
+                                                      const double* __restrict__ u, double* __restrict__ v, int w, int h,
+                                                      int tiles_x, int r, double damping) {
+#pragma clang fp contract(off)
+  constexpr int kNpt = TX * TY / 256;
+  static_assert(TX * TY % 256 == 0, "whole outputs per thread");
+  constexpr int kPlane = (TX + 4 * RMAX) * (TY + 4 * RMAX);
+  __shared__ double s_t[3][kPlane];              // Tx, Ty, e
+  __shared__ double s_h[(TY + 4 * RMAX) * TX];   // the sums along x of one product
+  const int f = blockIdx.y, tid = threadIdx.x;
+  const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+  const int x0 = tile_x * TX, y0 = tile_y * TY, halo = 2 * r;
+  const int pw = TX + 2 * halo, ph = TY + 2 * halo;
+  const size_t n = (size_t)w * h;
+  const double* ik = frames + (size_t)(f + 1) * n;
+  const double* uf = u + (size_t)f * 2 * n;
+  double* vf = v + (size_t)f * 2 * n;
+
+  for (int idx = tid; idx < pw * ph; idx += 256) {
+    const int ly = idx / pw, lx = idx - ly * pw;
+    const int y = y0 - halo + ly, x = x0 - halo + lx;
+    double tx = 0.0, ty = 0.0, e = 0.0;
+    if (x >= 0 && x < w && y >= 0 && y < h) {
+      const size_t q = (size_t)y * w + x;
+      const double sx = (double)x + uf[q], sy = (double)y + uf[n + q];
+      if (taps_inside(sx, sy, w, h)) {
+        const double fx0 = __builtin_floor(sx), fy0 = __builtin_floor(sy);
+        const double fx = sx - fx0, fy = sy - fy0;
+        const size_t o = (size_t)(int)fy0 * w + (int)fx0;  // x in [0, w - 2], y in [0, h - 2]
+        tx = bilinear4(gx + o, w, fx, fy);
+        ty = bilinear4(gy + o, w, fx, fy);
+        e = bilinear4(i0 + o, w, fx, fy) - ik[q];
+      }
+    }
+    s_t[0][idx] = tx;
+    s_t[1][idx] = ty;
+    s_t[2][idx] = e;
+  }
+  __syncthreads();
+
+  double acc[kNpt][5];
+  constexpr int kFirst[5] = {0, 0, 1, 0, 1}, kSecond[5] = {0, 1, 1, 2, 2};
+#pragma unroll
+  for (int p = 0; p < 5; ++p) {
+    const double* a = s_t[kFirst[p]];
+    const double* b = s_t[kSecond[p]];
+    for (int idx = tid; idx < ph * TX; idx += 256) {
+      const int ly = idx / TX, lx = idx - ly * TX;
+      const double* pa = a + ly * pw + lx;  // lx + halo + d, d = -halo ... halo
+      const double* pb = b + ly * pw + lx;
+      double s = 0.0;
+      for (int j = 0; j <= 2 * halo; ++j) {
+        const int d = j - halo;
+        s = s + (double)(halo + 1 - (d < 0 ? -d : d)) * (pa[j] * pb[j]);
+      }
+      s_h[idx] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kNpt; ++i) {
+      const int o = tid + i * 256, oy = o / TX, ox = o - oy * TX;
+      const double* ps = s_h + oy * TX + ox;  // row oy + halo + d
+      double s = 0.0;
+      for (int j = 0; j <= 2 * halo; ++j) {
+        const int d = j - halo;
+        s = s + (double)(halo + 1 - (d < 0 ? -d : d)) * ps[j * TX];
+      }
+      acc[i][p] = s;
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < kNpt; ++i) {
+    const int o = tid + i * 256, oy = o / TX, ox = o - oy * TX;
+    const int x = x0 + ox, y = y0 + oy;
+    if (x >= w || y >= h) continue;
+    const double a = acc[i][0], b = acc[i][1], c = acc[i][2], p = acc[i][3], q = acc[i][4];
+    const double lam = damping * (0.5 * (a + c));
+    const double a1 = a + lam, c1 = c + lam;
+    const double det = a1 * c1 - b * b;
+    double dux = 0.0, duy = 0.0;
+    if (det > 0.0) {
+      dux = -((c1 * p - b * q) / det);
+      duy = -((a1 * q - b * p) / det);
+      dux = fmin(fmax(dux, -1.0), 1.0);
+      duy = fmin(fmax(duy, -1.0), 1.0);
+    }
+    const size_t qi = (size_t)y * w + x;
+    vf[qi] = uf[qi] + dux;
+    vf[n + qi] = uf[n + qi] + duy;
+  }
+}
+
+// u[plane] = the box mean of v[plane] over radius R, rows then columns ascending, divided by the number of in-image pixels.
+// grid = (pixels, 2 * (frames - 1))
+__global__ __launch_bounds__(256) void k_flow_smooth(const double* __restrict__ v, double* __restrict__ u, int w, int h, int R) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= w * h) return;
+  const int y = i / w, x = i - y * w;
+  const double* p = v + (size_t)blockIdx.y * w * h;
+  const int ya = max(0, y - R), yb = min(h - 1, y + R), xa = max(0, x - R), xb = min(w - 1, x + R);
+  double s = 0.0;
+  for (int yy = ya; yy <= yb; ++yy)
+    for (int xx = xa; xx <= xb; ++xx) s = s + p[(size_t)yy * w + xx];
+  u[(size_t)blockIdx.y * w * h + i] = s / (double)((yb - ya + 1) * (xb - xa + 1));
+}
+
+// out[plane][oh][ow] = gain * bilinear(u[plane] at (Q - sub) / div), coordinates clamped to u's w x h image (w, h >= 2).
+// grid = (output pixels, planes)
+__global__ __launch_bounds__(256) void k_flow_resample(const double* __restrict__ u, int w, int h, double* __restrict__ out, int ow,
+                                                       int oh, double sub, double div, double gain) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)ow * oh) return;
+  const int y = (int)(i / ow), x = (int)(i - (size_t)y * ow);
+  const double cx = fmin(fmax(((double)x - sub) / div, 0.0), (double)(w - 1));
+  const double cy = fmin(fmax(((double)y - sub) / div, 0.0), (double)(h - 1));
+  const int xi = min((int)__builtin_floor(cx), w - 2), yi = min((int)__builtin_floor(cy), h - 2);
+  const double* p = u + (size_t)blockIdx.y * w * h + (size_t)yi * w + xi;
+  out[(size_t)blockIdx.y * ow * oh + i] = gain * bilinear4(p, w, cx - (double)xi, cy - (double)yi);
+}
+
+// valid[f][h][w] (1 / 0) at the result and record[(f * blocks + block)][2] = {sum of e^2, count} over the valid pixels this
+// workgroup visits, e = I_0(q + u) - I_{f+1}(q).  grid = (blocks, frames - 1)
+__global__ __launch_bounds__(256) void k_flow_finish(const double* __restrict__ i0, const double* __restrict__ frames,
+                                                     const double* __restrict__ u, int w, int h, int margin,
+                                                     double* __restrict__ valid, double* __restrict__ record) {
+#pragma clang fp contract(off)
+  __shared__ double red[2][4];
+  const int f = blockIdx.y;
+  const size_t n = (size_t)w * h;
+  const double* ik = frames + (size_t)(f + 1) * n;
+  const double* uf = u + (size_t)f * 2 * n;
+  double see = 0.0, cnt = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int y = (int)(i / w), x = (int)(i - (size_t)y * w);
+    const double sx = (double)x + uf[i], sy = (double)y + uf[n + i];
+    const bool ok = taps_inside(sx, sy, w, h) && x >= margin && x <= w - 1 - margin && y >= margin && y <= h - 1 - margin;
+    if (ok) {
+      const double fx0 = __builtin_floor(sx), fy0 = __builtin_floor(sy);
+      const double e = bilinear4(i0 + (size_t)(int)fy0 * w + (int)fx0, w, sx - fx0, sy - fy0) - ik[i];
+      see = see + e * e;
+      cnt = cnt + 1.0;
+    }
+    valid[(size_t)f * n + i] = ok ? 1.0 : 0.0;
+  }
+  const double a = block_sum_256(see, red[0]), b = block_sum_256(cnt, red[1]);
+  if (threadIdx.x == 0) {
+    double* o = record + ((size_t)f * gridDim.x + blockIdx.x) * 2;
+    o[0] = a;
+    o[1] = b;
+  }
+}
+
+// record[(f * blocks + block)][2] = the largest |difference| between horizontal / vertical neighbours over both components
+// of field[f][2][H][W], over the pixels this workgroup visits.  grid = (blocks, frames - 1)
+__global__ __launch_bounds__(256) void k_flow_maxdiff(const double* __restrict__ field, int W, int H, double* __restrict__ record) {
+  __shared__ double red[2][4];
+  const size_t n = (size_t)W * H;
+  const double* uf = field + (size_t)blockIdx.y * 2 * n;
+  double mx = 0.0, my = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+    for (int c = 0; c < 2; ++c) {
+      const double* p = uf + (size_t)c * n + i;
+      if (x + 1 < W) mx = fmax(mx, fabs(p[1] - p[0]));
+      if (y + 1 < H) my = fmax(my, fabs(p[W] - p[0]));
+    }
+  }
+  mx = wave_max(mx);
+  my = wave_max(my);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { red[0][wv] = mx; red[1][wv] = my; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = record + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+    o[0] = combine4(red[0], true);
+    o[1] = combine4(red[1], true);
+  }
+}
+
+void launch_lk_pass(const double* i0, const double* gx, const double* gy, const double* frames, const double* u, double* v, int w,
+                    int h, int nf, int r, double damping, hipStream_t st) {
+  if (r <= 4) {
+    const int tx = (w + 31) / 32, ty = (h + 15) / 16;
+    hipLaunchKernelGGL((k_flow_lk_pass<32, 16, 4>), dim3(tx * ty, nf), dim3(256), 0, st, i0, gx, gy, frames, u, v, w, h, tx, r, damping);
+  } else {
+    const int tx = (w + 15) / 16, ty = (h + 15) / 16;
+    hipLaunchKernelGGL((k_flow_lk_pass<16, 16, kMaxWindowRadius>), dim3(tx * ty, nf), dim3(256), 0, st, i0, gx, gy, frames, u, v, w,
+                       h, tx, r, damping);
+  }
+}
+
+int blocks_of(size_t n) { return (int)((n + 255) / 256); }
+
+// the device buffers of one call
+struct FlowBuffers {
+  double *pyr = nullptr, *grad = nullptr, *u = nullptr, *v = nullptr, *hr = nullptr, *valid = nullptr, *rec = nullptr, *tab = nullptr;
+  ~FlowBuffers() {
+    for (double* p : {pyr, grad, u, v, hr, valid, rec, tab})
+      if (p) (void)hipFree(p);
+  }
+  static bool get(double** p, size_t elems) { return hipMalloc((void**)p, std::max<size_t>(elems, 1) * sizeof(double)) == hipSuccess; }
+};
+
+}  // namespace
+
+}  // namespace srmap
+
+using namespace srmap;
+
+extern "C" void srmap_flow_registration_options_default(srmap_flow_registration_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_flow_registration_options);
+  o->hr_scale = 1;
+  o->warps = 8;
+  o->window_radius = 4;
+  o->damping = 0.05;
+  o->smooth_radius = 2;
+  o->valid_margin = 3;
+  o->max_levels = 0;
+  o->initial_affine_2x3 = nullptr;
+}
+
+extern "C" int srmap_register_flow(srmap_ctx* ctx, int num_images, int width, int height, const double* images_host,
+                                   const srmap_flow_registration_options* options, double* flow_out, double* valid_out,
+                                   double* quality_out) {
+  if (!ctx || !flow_out || num_images < 0) return SRMAP_EINVAL;
+  srmap_flow_registration_options opt;
+  srmap_flow_registration_options_default(&opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_flow_registration_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_flow_registration_options.struct_size is not this library's");
+    opt = *options;
+  }
+  if (opt.hr_scale < 1 || opt.warps < 1 || opt.window_radius < 1 || opt.window_radius > kMaxWindowRadius ||
+      !(opt.damping >= 0.0) || !std::isfinite(opt.damping) || opt.smooth_radius < 0 || opt.smooth_radius > kMaxSmoothRadius ||
+      opt.valid_margin < 0 || opt.max_levels < 0)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: bad options");
+  if (num_images == 0) return SRMAP_OK;
+  if (!images_host || width < kMinSize || height < kMinSize)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration needs images of at least 16 x 16");
+  const int K = num_images, nf = K - 1, s = opt.hr_scale;
+  const size_t n = (size_t)width * height;
+  if ((size_t)s * width > (size_t)1 << 20 || (size_t)s * height > (size_t)1 << 20 || n * s * s > (size_t)1 << 30)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: the output grid is too large");
+  for (size_t i = 0; i < (size_t)K * n; ++i)
+    if (!std::isfinite(images_host[i])) return set_error(ctx, SRMAP_EINVAL, "flow registration: image %d is not finite", (int)(i / n));
+
+  std::vector<int> lw{width}, lh{height};
+  while (std::min(lw.back(), lh.back()) >= 2 * kMinSize && (int)lw.size() < kMaxLevels &&
+         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
+    lw.push_back(lw.back() / 2);
+    lh.push_back(lh.back() / 2);
+  }
+  const int L = (int)lw.size();
+
+  std::vector<double> h_tab;
+  if (opt.initial_affine_2x3 && nf > 0) {
+    h_tab.resize((size_t)nf * 6);
+    for (int f = 0; f < nf; ++f) {
+      AffineMap F;
+      std::copy(opt.initial_affine_2x3 + 6 * (f + 1), opt.initial_affine_2x3 + 6 * (f + 2), F.m);
+      if (!all_finite(F) || deviation(F) > kAffineMaxDeviation)
+        return set_error(ctx, SRMAP_EINVAL, "flow registration: initial matrix %d is not finite or outside the model's domain", f + 1);
+      for (int l = 1; l < L; ++l) F = to_coarser(F);
+      const AffineMap G = inverse(F);
+      std::copy(G.m, G.m + 6, h_tab.begin() + 6 * f);
+    }
+  }
+
+  const size_t N = n * s * s;
+  std::memset(flow_out, 0, 2 * N * sizeof(double));
+  if (valid_out) std::fill(valid_out, valid_out + n, 1.0);
+  if (quality_out) { quality_out[0] = 0.0; quality_out[1] = 1.0; quality_out[2] = 0.0; }
+  if (K == 1) return SRMAP_OK;
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  std::vector<size_t> off(L + 1, 0), goff(L + 1, 0);
+  for (int l = 0; l < L; ++l) {
+    off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
+    goff[l + 1] = goff[l] + (size_t)2 * lw[l] * lh[l];
+  }
+  const int fin_blocks = std::min(kMaxRecordBlocks, blocks_of(n)), max_blocks = std::min(kMaxRecordBlocks, blocks_of(N));
+  const size_t rec_elems = (size_t)nf * 2 * (fin_blocks + max_blocks);
+
+  FlowBuffers b;
+  if (!FlowBuffers::get(&b.pyr, off[L]) || !FlowBuffers::get(&b.grad, goff[L]) || !FlowBuffers::get(&b.u, (size_t)nf * 2 * n) ||
+      !FlowBuffers::get(&b.v, (size_t)nf * 2 * n) || !FlowBuffers::get(&b.hr, (size_t)nf * 2 * N) ||
+      !FlowBuffers::get(&b.valid, (size_t)nf * n) || !FlowBuffers::get(&b.rec, rec_elems) ||
+      !FlowBuffers::get(&b.tab, h_tab.size())) {
+    (void)hipGetLastError();
+    return set_error(ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
+  }
+
+  // ---- pyramids of the whole stack and the gradient planes of frame 0, once ----
+  SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, images_host, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, st));
+  for (int l = 1; l < L; ++l) launch_down2_stack(b.pyr + off[l - 1], b.pyr + off[l], lw[l - 1], lh[l - 1], K, st);
+  for (int l = 0; l < L; ++l) {
+    const size_t nl = (size_t)lw[l] * lh[l];
+    hipLaunchKernelGGL(k_flow_gradients, dim3(blocks_of(nl)), dim3(256), 0, st, b.pyr + off[l], lw[l], lh[l], b.grad + goff[l],
+                       b.grad + goff[l] + nl);
+  }
+
+  // ---- start at the coarsest level ----
+  double *u = b.u, *v = b.v;
+  {
+    const int cw = lw[L - 1], ch = lh[L - 1];
+    if (h_tab.empty()) {
+      SRMAP_HIP(ctx, hipMemsetAsync(u, 0, (size_t)nf * 2 * cw * ch * sizeof(double), st));
+    } else {
+      SRMAP_HIP(ctx, hipMemcpyAsync(b.tab, h_tab.data(), h_tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_flow_affine_start, dim3(blocks_of((size_t)cw * ch), nf), dim3(256), 0, st, b.tab, cw, ch, u);
+    }
+  }
+
+  // ---- the warp passes, coarse to fine ----
+  for (int l = L - 1; l >= 0; --l) {
+    const int w = lw[l], h = lh[l];
+    const size_t nl = (size_t)w * h;
+    for (int it = 0; it < opt.warps; ++it) {
+      launch_lk_pass(b.pyr + off[l], b.grad + goff[l], b.grad + goff[l] + nl, b.pyr + off[l], u, v, w, h, nf, opt.window_radius,
+                     opt.damping, st);
+      hipLaunchKernelGGL(k_flow_smooth, dim3(blocks_of(nl), 2 * nf), dim3(256), 0, st, v, u, w, h, opt.smooth_radius);
+    }
+    if (l > 0) {
+      const int fw = lw[l - 1], fh = lh[l - 1];
+      hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of((size_t)fw * fh), 2 * nf), dim3(256), 0, st, u, w, h, v, fw, fh, 0.5, 2.0, 2.0);
+      std::swap(u, v);
+    }
+  }
+
+  // ---- the HR field, the mask and the quality records; the one wait ----
+  double* rec_fin = b.rec;
+  double* rec_max = b.rec + (size_t)nf * 2 * fin_blocks;
+  hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, b.hr, s * width, s * height, 0.0,
+                     (double)s, (double)s);
+  hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, b.pyr, b.pyr, u, width, height, opt.valid_margin, b.valid,
+                     rec_fin);
+  hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, b.hr, s * width, s * height, rec_max);
+  SRMAP_HIP(ctx, hipGetLastError());
+  std::vector<double> h_rec(rec_elems);
+  SRMAP_HIP(ctx, hipMemcpyAsync(flow_out + 2 * N, b.hr, (size_t)nf * 2 * N * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (valid_out) SRMAP_HIP(ctx, hipMemcpyAsync(valid_out + n, b.valid, (size_t)nf * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipMemcpyAsync(h_rec.data(), b.rec, rec_elems * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipStreamSynchronize(st));
+
+  if (quality_out) {
+    for (int f = 0; f < nf; ++f) {
+      double see = 0.0, cnt = 0.0, mx = 0.0, my = 0.0;
+      for (int k = 0; k < fin_blocks; ++k) {
+        see += h_rec[((size_t)f * fin_blocks + k) * 2];
+        cnt += h_rec[((size_t)f * fin_blocks + k) * 2 + 1];
+      }
+      const double* rm = h_rec.data() + (size_t)nf * 2 * fin_blocks;
+      for (int k = 0; k < max_blocks; ++k) {
+        mx = std::max(mx, rm[((size_t)f * max_blocks + k) * 2]);
+        my = std::max(my, rm[((size_t)f * max_blocks + k) * 2 + 1]);
+      }
+      double* q = quality_out + 3 * (f + 1);
+      q[0] = cnt > 0 ? std::sqrt(see / cnt) : 0.0;
+      q[1] = cnt / (double)n;
+      q[2] = mx + my;
+    }
+  }
+  return SRMAP_OK;
+}

@@ -7,7 +7,8 @@
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
 // reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor is
 // --flow_motion_path: a dense displacement field per frame (srmap_problem_set_flow).  Nor are
-// --registration=translational|affine (the solver's motion estimated from the LR frames on the GPU) and
+// --registration=translational|affine|flow (the solver's motion estimated from the LR frames on the GPU; flow: dense
+// displacement fields and their validity masks as data weights, srmap_register_flow), --save_flow_path and
 // --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion), nor
 // --blur_kernel_path (a free-form blur kernel, srmap_problem_set_blur_kernel) and --fit_blur_from / --fit_blur_ksize /
 // --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur), nor --photometric_path /
@@ -53,9 +54,14 @@ int main(int argc, char** argv) {
       "                       [frames][2][H][W] = the (ux, uy) planes in HR pixels at the high-resolution size; an error\n"
       "                       together with --motion_sequence_path, --affine_motion_path, --registration,\n"
       "                       --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
-      "                       [--registration=translational|affine] (estimate the solver's motion from the LR frames, in HR\n"
-      "                       pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
-      "                       an error together with either motion file)\n"
+      "                       [--registration=translational|affine|flow] (estimate the solver's motion from the LR frames, in\n"
+      "                       HR pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
+      "                       an error together with either motion file.  flow: a dense displacement field per frame, and\n"
+      "                       its validity masks as data weights of a least-squares solve (--data_loss=huber derives its own\n"
+      "                       weights and runs without the masks); an error together with --motion_sequence_path,\n"
+      "                       --affine_motion_path, --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
+      "                       [--save_flow_path=<file>] (the estimated fields, in --flow_motion_path's format; needs\n"
+      "                       --registration=flow)\n"
       "                       [--save_motion_path=<file>] (the estimate, 'a b tx c d ty' per line; needs --registration or\n"
       "                       --refine_motion_rounds, and holds the final matrices)\n"
       "                       [--refine_motion_rounds=0] (after the solve, N times: re-fit the frame matrices to the estimate\n"
@@ -118,6 +124,7 @@ int main(int argc, char** argv) {
   // srmap_register_affine) instead of reading it from a file, and write the estimate out
   const std::string registration_name = flags.Str("registration");
   const std::string save_motion_path = flags.Str("save_motion_path");
+  const std::string save_flow_path = flags.Str("save_flow_path");
   // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
   const int refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
   const int refine_motion_dof = flags.Int("refine_motion_dof", 6);
@@ -150,8 +157,30 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (!registration_name.empty() && registration_name != "translational" && registration_name != "affine") {
-    std::fprintf(stderr, "ERROR: --registration is 'translational' or 'affine'.\n");
+  if (!registration_name.empty() && registration_name != "translational" && registration_name != "affine" &&
+      registration_name != "flow") {
+    std::fprintf(stderr, "ERROR: --registration is 'translational' or 'affine', or 'flow'.\n");
+    return 1;
+  }
+  const bool register_flow = registration_name == "flow";
+  if (register_flow) {
+    // the estimated field IS the motion, as --flow_motion_path's: the same flags are refused (--registration itself aside)
+    const char* other = !model_parameters.motion_sequence_path.empty() ? "--motion_sequence_path"
+                        : !model_parameters.affine_motion_sequence_path.empty() ? "--affine_motion_path"
+                        : refine_motion_rounds != 0 ? "--refine_motion_rounds"
+                        : !fit_blur_from.empty() ? "--fit_blur_from"
+                        : photometric_rounds >= 0 ? "--photometric_rounds" : nullptr;
+    if (other) {
+      std::fprintf(stderr, "ERROR: --registration=flow and %s exclude each other.\n", other);
+      return 1;
+    }
+    if (!save_motion_path.empty()) {
+      std::fprintf(stderr, "ERROR: --save_motion_path holds matrices; the fields of --registration=flow go to --save_flow_path.\n");
+      return 1;
+    }
+  }
+  if (!save_flow_path.empty() && !register_flow) {
+    std::fprintf(stderr, "ERROR: --save_flow_path needs --registration=flow.\n");
     return 1;
   }
   if (!registration_name.empty() && !generate_lr_images &&
@@ -284,7 +313,18 @@ int main(int argc, char** argv) {
     return true;
   };
   ImageModelParameters solver_parameters = model_parameters;
-  if (!registration_name.empty()) {
+  std::vector<double> flow_valid;  // --registration=flow: the validity masks, [frames][h][w] at LR resolution
+  if (register_flow) {
+    solver_parameters.flow_motion_sequence = registration::FlowRegistration(low_res_images, upsampling_scale, &flow_valid);
+    double kept = 0.0;
+    for (const double v : flow_valid) kept += v;
+    std::printf("Estimated flow motion of %d frames from the low-resolution images; %.1f %% of the pixels are valid.\n",
+                solver_parameters.flow_motion_sequence.GetNumMotions(), 100.0 * kept / static_cast<double>(flow_valid.size()));
+    if (!save_flow_path.empty() && !solver_parameters.flow_motion_sequence.SaveToFile(save_flow_path)) {
+      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_flow_path.c_str());
+      return 1;
+    }
+  } else if (!registration_name.empty()) {
     solver_parameters.motion_sequence_path.clear();
     solver_parameters.affine_motion_sequence_path.clear();
     AffineMotionSequence estimate;
@@ -327,6 +367,9 @@ int main(int argc, char** argv) {
     }
     solver.AddRegularizer(regularizer, regularization_parameter);
   }
+  // --registration=flow: the field is wrong where frame 0 does not hold the content; those pixels get weight 0.  A Huber
+  // solve derives its own weights and resets the buffer (include/srmap.h)
+  if (register_flow && solver_options.data_loss == L2_DATA_LOSS) solver.MultiplyDataWeights(flow_valid);
 
   // --fit_blur_from: the calibration fit, before the solve, from a known HR image of what the frames show
   if (!fit_blur_from.empty()) {

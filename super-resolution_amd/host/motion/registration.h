@@ -14,6 +14,7 @@
 
 #include "image/image_data.h"
 #include "motion/affine_motion.h"
+#include "motion/flow_motion.h"
 #include "motion/motion_shift.h"
 #include "util/srmap_host.h"
 
@@ -107,6 +108,75 @@ inline AffineMotionSequence AffineRegistrationWithQuality(const std::vector<Imag
 
 inline AffineMotionSequence AffineRegistration(const std::vector<ImageData>& images, const int scale = 1) {
   return AffineRegistrationWithQuality(images, scale, nullptr);
+}
+
+// Options of FlowRegistration (srmap_flow_registration_options, include/srmap.h).
+struct FlowRegistrationOptions {
+  int warps = 8;
+  int window_radius = 4;
+  double damping = 0.05;
+  int smooth_radius = 2;
+  int valid_margin = 3;
+  int max_levels = 0;
+  AffineMotionSequence initial_motion;  // empty: start from u = 0; else one matrix per image, INPUT-pixel units
+};
+
+// Not in the reference: a dense displacement field for every image relative to the first one (srmap_register_flow,
+// csrc/registration_flow.hip), as a FlowMotionSequence at `scale` times the input size in units of `scale` input pixels --
+// register the LR frames with scale = the upsampling scale and the result is what MotionModule(FlowMotionSequence) takes.
+// Channel 0 is the registration image; an empty list gives an empty sequence; image 0 gets u = 0.  valid (optional):
+// [images][h][w] at INPUT resolution, 1 where the field can be trusted, else 0 -- hand it to
+// IRLSMapSolver::MultiplyDataWeights, the field is wrong at the frame border where image 0 does not hold the content.
+// quality (optional): 3 per image -- RMS residual over the valid pixels, the valid fraction, the largest neighbour
+// difference dx + dy of the field.  Dense, local, no occlusion handling, one plane: include/srmap.h states what it is not.
+inline FlowMotionSequence FlowRegistration(const std::vector<ImageData>& images, const int scale = 1,
+                                           std::vector<double>* valid = nullptr, std::vector<double>* quality = nullptr,
+                                           const FlowRegistrationOptions& registration_options = FlowRegistrationOptions()) {
+  if (images.empty()) {
+    std::fprintf(stderr, "WARNING: No images given. Returning an empty motion sequence.\n");
+    if (valid) valid->clear();
+    if (quality) quality->clear();
+    return FlowMotionSequence();
+  }
+  if (scale < 1) srmap_host::Fail("flow registration: the scale must be at least 1");
+  const cv::Size size = images[0].GetImageSize();
+  const size_t npx = static_cast<size_t>(size.width) * size.height;
+  std::vector<double> stack(npx * images.size());
+  for (size_t i = 0; i < images.size(); ++i) {
+    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
+        images[i].GetImageSize().height != size.height)
+      srmap_host::Fail("registration needs images of one size with at least one channel");
+    const double* ch = images[i].GetChannelData(0);
+    std::copy(ch, ch + npx, stack.begin() + i * npx);
+  }
+  srmap_flow_registration_options options;
+  srmap_flow_registration_options_default(&options);
+  options.hr_scale = scale;
+  options.warps = registration_options.warps;
+  options.window_radius = registration_options.window_radius;
+  options.damping = registration_options.damping;
+  options.smooth_radius = registration_options.smooth_radius;
+  options.valid_margin = registration_options.valid_margin;
+  options.max_levels = registration_options.max_levels;
+  std::vector<double> initial;
+  if (registration_options.initial_motion.GetNumMotions() > 0) {
+    if (static_cast<size_t>(registration_options.initial_motion.GetNumMotions()) < images.size())
+      srmap_host::Fail("flow registration: fewer initial matrices than images");
+    for (size_t i = 0; i < images.size(); ++i) {
+      const AffineMotion& m = registration_options.initial_motion[static_cast<int>(i)];
+      const double row[6] = {m.a, m.b, m.tx, m.c, m.d, m.ty};
+      initial.insert(initial.end(), row, row + 6);
+    }
+    options.initial_affine_2x3 = initial.data();
+  }
+  std::vector<double> flow(2 * npx * scale * scale * images.size());
+  if (valid) valid->assign(npx * images.size(), 0.0);
+  if (quality) quality->assign(3 * images.size(), 0.0);
+  srmap_host::Check(srmap_register_flow(srmap_host::Context(), static_cast<int>(images.size()), size.width, size.height,
+                                        stack.data(), &options, flow.data(), valid ? valid->data() : nullptr,
+                                        quality ? quality->data() : nullptr),
+                    "Could not determine motion between images.");
+  return FlowMotionSequence(flow, size.width * scale, size.height * scale);
 }
 
 }  // namespace registration

@@ -378,6 +378,22 @@ class IRLSMapSolver : public MapSolver {
     srmap_host::Check(srmap_get_data_weights(problem_.get(), w.data()), "srmap_get_data_weights");
     return w;
   }
+  // Multiplies per-observation masks [K][h][w] at LR resolution (registration::FlowRegistration's validity masks) into the
+  // data weights, broadcast over the channels: the weights in force (the caller's, ones if none were set) times the mask.
+  // Not in the reference.  A Huber solve owns the weight buffer and resets it (include/srmap.h): masks act on
+  // least-squares solves only.
+  void MultiplyDataWeights(const std::vector<double>& masks) {
+    int lw = 0, lh = 0;
+    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
+    const size_t plane = static_cast<size_t>(lw) * lh, channels = static_cast<size_t>(GetNumChannels());
+    if (masks.size() != static_cast<size_t>(GetNumImages()) * plane)
+      srmap_host::Fail("data weight masks: one [h][w] plane per observation at the low-resolution size is needed");
+    std::vector<double> w = GetDataWeights();
+    for (size_t k = 0; k < static_cast<size_t>(GetNumImages()); ++k)
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t i = 0; i < plane; ++i) w[(k * channels + c) * plane + i] *= masks[k * plane + i];
+    srmap_host::Check(srmap_set_data_weights(problem_.get(), w.data()), "srmap_set_data_weights");
+  }
 
  private:
   const IRLSMapSolverOptions solver_options_;

@@ -52,6 +52,12 @@ class AffineRegistrationOptions(C.Structure):
                 ("step_tolerance", C.c_double), ("max_levels", C.c_int), ("initial_affine_2x3", c_double_p)]
 
 
+class FlowRegistrationOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("hr_scale", C.c_int), ("warps", C.c_int), ("window_radius", C.c_int),
+                ("damping", C.c_double), ("smooth_radius", C.c_int), ("valid_margin", C.c_int), ("max_levels", C.c_int),
+                ("initial_affine_2x3", c_double_p)]
+
+
 class MotionRefinementOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("dof", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double),
                 ("initial_damping", C.c_double), ("apply", C.c_int), ("initial_affine_2x3", c_double_p)]
@@ -138,6 +144,8 @@ _SIGNATURES = [
     ("srmap_register_translational_ex", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     ("srmap_affine_registration_options_default", None, [C.c_void_p]),
     ("srmap_register_affine", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p]),
+    ("srmap_flow_registration_options_default", None, [C.c_void_p]),
+    ("srmap_register_flow", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_motion_refinement_options_default", None, [C.c_void_p]),
     ("srmap_refine_motion", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_refine_motion_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
@@ -260,6 +268,31 @@ class Context:
         self.check(load().srmap_register_affine(self._h, n, W, H, pa, C.byref(o), out.ctypes.data_as(c_double_p),
                                                 q.ctypes.data_as(c_double_p) if with_quality else None))
         return (out, q) if with_quality else out
+
+    def register_flow(self, images, hr_scale=1, init=None, warps=8, window_radius=4, damping=0.05, smooth_radius=2,
+                      valid_margin=3, max_levels=0, struct_size=None):
+        """srmap_register_flow: images [n][H][W] -> (flow [n][2][s H][s W], valid [n][H][W], quality [n][3]) with
+        s = hr_scale: the fields u_k, I_0(q + u_k(q)) ~= I_k(q), in units of HR pixels (ready for Problem.set_flow), the
+        validity mask at input resolution (ready for Problem.set_data_weights, one plane per channel) and (RMS residual,
+        valid fraction, max dx + dy of the field) per image -- srmap.h.  init: [n][2][3] starting matrices in input pixels
+        (register_affine's) instead of u = 0.  struct_size overrides the options' size field (tests)."""
+        a, pa = _d(images)
+        n, H, W = a.shape
+        o = FlowRegistrationOptions()
+        load().srmap_flow_registration_options_default(C.byref(o))
+        o.hr_scale, o.warps, o.window_radius, o.damping = hr_scale, warps, window_radius, damping
+        o.smooth_radius, o.valid_margin, o.max_levels = smooth_radius, valid_margin, max_levels
+        if struct_size is not None:
+            o.struct_size = struct_size
+        if init is not None:
+            ini, pi = _d(init)
+            assert ini.size == n * 6, (ini.shape, n)
+            o.initial_affine_2x3 = pi
+        s = max(1, int(hr_scale))
+        flow, valid, q = np.zeros((n, 2, s * H, s * W)), np.zeros((n, H, W)), np.zeros((n, 3))
+        self.check(load().srmap_register_flow(self._h, n, W, H, pa, C.byref(o), flow.ctypes.data_as(c_double_p),
+                                              valid.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p)))
+        return flow, valid, q
 
     def pca(self, samples):
         """PCA of planar samples [rows][count] on the GPU: (mean, eigenvalues descending, basis rows = eigenvectors)."""
