@@ -27,6 +27,8 @@ The local evaluator is any callable  local_eval(x, terms) -> (cost, grad)
 working on this rank's shard: srmap.Problem.eval_device on the GPU (the tests plug
 a CPU evaluator over gloo).
 """
+import math
+
 TERM_DATA, TERM_REG, TERM_ALL = 1, 2, 3
 
 
@@ -51,9 +53,11 @@ def grid_coords(world, rank, frame_groups):
 def band_halo(scale, blur_ksize, max_abs_shift, reg_reach):
     """Rows of x beyond a band that the gradient and cost of its owned rows depend on:
     data term 2*|shift| + 2*(blur half width) (HR pixel -> shifted -> LR stencil -> warped x),
-    regulariser `reg_reach` (BTV range R / TV 1), rounded up to a multiple of the scale."""
+    regulariser `reg_reach` (BTV range R / TV 1), rounded up to a multiple of the scale.
+    A fractional shift counts as the next integer away from zero: the bilinear taps of a sub-pixel warp reach
+    ceil(|shift|) rows, forward and transposed.  Integer shifts give what they always gave."""
     hb = (max(blur_ksize, 1) - 1) // 2
-    need = max(2 * int(max_abs_shift) + 2 * hb, int(reg_reach))
+    need = max(2 * int(math.ceil(abs(max_abs_shift))) + 2 * hb, int(reg_reach))
     return ((need + scale - 1) // scale) * scale
 
 
