@@ -2,7 +2,7 @@
 // calibration pair) the ksize x ksize taps h of B in A_k = D B M_k are a linear least-squares problem,
 //   E(h) = sum_k sum_c sum_u w (sum_t h_t s_t - y)^2,  s_t = (M_k x)(R0 + a - hb, C0 + e - hb), t = (a, e), 0 outside the image,
 // (R0, C0) the decimation source of LR pixel u, M_k sampled exactly as the forward kernel of the problem's motion samples it
-// (warp_sample / affine_sample of sample_dev.hpp, affine_coord of motion_fit_dev.hpp; the identity without motion), over
+// (MotionSampler of sample_dev.hpp; the identity without motion), over
 // every LR pixel of every channel and frame (the cost-row restriction is ignored, as in 3.8).  No reference counterpart
 // (blur_module.cpp:13-22 builds a Gaussian from (radius, sigma)); the checker is tests/blur_kernel_restatement.py.
 //   pass      ONE launch of k_blur_fit_sums: with n = ksize^2 the record is the upper triangle (row-major) of the
@@ -34,13 +34,11 @@ constexpr int kTile = 128;       // observations per tile
 constexpr int kStride = 129;     // LDS row stride in doubles (odd)
 constexpr int kMaxChunks = 128;  // chunks per frame at most
 constexpr int kMinTilesPerChunk = 2;
-enum { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2 };
 
 template <typename T, int B, int MOTION, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, const T* __restrict__ y,
                                                        const T* __restrict__ dw, Geometry g,
-                                                       const WarpTaps<T>* __restrict__ warps,
-                                                       const double* __restrict__ recs, const int* __restrict__ col_map,
+                                                       MotionArgs<T> ma, const int* __restrict__ col_map,
                                                        const int* __restrict__ row_map, int tiles_per_chunk,
                                                        double* __restrict__ partial) {
   constexpr int N = B * B, N1 = N + 1, P = N1 * (N1 + 1) / 2, PP = (P + 255) / 256, HB = (B - 1) / 2;
@@ -61,8 +59,7 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
     pj[m] = (i + rem) * kStride;
     acc[m] = 0.0;
   }
-  const WarpTaps<T> wt = (MOTION == kMotionTable) ? warps[k] : identity_warp<T>();
-  const double* __restrict__ mk = (MOTION == kMotionAffine) ? recs + (size_t)k * kAffineRec : nullptr;  // uniform
+  const MotionSampler<T, MOTION> ms(ma, g, k);  // uniform
   const int ob = threadIdx.x & (kTile - 1), half = threadIdx.x >> 7;
   for (int tile = 0; tile < tiles_per_chunk; ++tile) {
     const long long o0 = ((long long)blockIdx.x * tiles_per_chunk + tile) * kTile;
@@ -84,17 +81,8 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
       const int a = t / B, e = t - a * B;
       const int rr = R0 + a - HB, cc = C0 + e - HB;
       double s = 0.0;
-      if (live && rr >= 0 && rr < g.H && cc >= 0 && cc < g.W) {  // the blur's zero border on the warped image
-        if (MOTION == kMotionAffine) {
-          const double sx = affine_coord(mk[0], mk[1], mk[2], (double)cc, (double)rr);
-          const double sy = affine_coord(mk[3], mk[4], mk[5], (double)cc, (double)rr);
-          s = affine_sample<T, double>(plane, g.W, g.H, sx, sy);
-        } else if (MOTION == kMotionTable) {
-          s = warp_sample<T, double>(plane, g.W, g.H, wt, rr, cc);
-        } else {
-          s = (double)plane[(size_t)rr * g.W + cc];
-        }
-      }
+      if (live && rr >= 0 && rr < g.H && cc >= 0 && cc < g.W)  // the blur's zero border on the warped image
+        s = ms.template at<double>(plane, g.W, g.H, rr, cc);
       u[t * kStride + ob] = s;
     }
     {
@@ -129,33 +117,29 @@ __global__ __launch_bounds__(256) void k_blur_fit_reduce(const double* __restric
   sums[q] = s;
 }
 
-template <typename T, int B, int MOTION>
-void launch_sums_w(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
+// the instance of the problem's motion kind; false: the kind has none (a displacement field, which the entry point refuses)
+template <typename T, int B>
+bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
-  const WarpTaps<T>* warps = MOTION == kMotionTable ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr;
-  const double* recs = MOTION == kMotionAffine ? p->d_affine : nullptr;
-  if (p->d_dw)
-    hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)p->d_dw,
-                       g, warps, recs, p->d_col_map, p->d_row_map, tpc, d_part);
-  else
-    hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
-                       (const T*)nullptr, g, warps, recs, p->d_col_map, p->d_row_map, tpc, d_part);
-}
-
-template <typename T, int B>
-void launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
-  if (p->affine) launch_sums_w<T, B, kMotionAffine>(p, x, chunks, tpc, d_part, st);
-  else if (p->has_motion) launch_sums_w<T, B, kMotionTable>(p, x, chunks, tpc, d_part, st);
-  else launch_sums_w<T, B, kMotionNone>(p, x, chunks, tpc, d_part, st);
+  const MotionArgs<T> ma = motion_args<T>(p);
+  return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+    constexpr int MOTION = decltype(motion)::value;
+    if (p->d_dw)
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
+                         (const T*)p->d_dw, g, ma, p->d_col_map, p->d_row_map, tpc, d_part);
+    else
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
+                         (const T*)nullptr, g, ma, p->d_col_map, p->d_row_map, tpc, d_part);
+  });
 }
 
 template <typename T>
-void launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
-  if (ksize == 1) launch_sums_m<T, 1>(p, x, chunks, tpc, d_part, st);
-  else if (ksize == 3) launch_sums_m<T, 3>(p, x, chunks, tpc, d_part, st);
-  else if (ksize == 5) launch_sums_m<T, 5>(p, x, chunks, tpc, d_part, st);
-  else launch_sums_m<T, 7>(p, x, chunks, tpc, d_part, st);
+bool launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
+  if (ksize == 1) return launch_sums_m<T, 1>(p, x, chunks, tpc, d_part, st);
+  if (ksize == 3) return launch_sums_m<T, 3>(p, x, chunks, tpc, d_part, st);
+  if (ksize == 5) return launch_sums_m<T, 5>(p, x, chunks, tpc, d_part, st);
+  return launch_sums_m<T, 7>(p, x, chunks, tpc, d_part, st);
 }
 
 struct FitBuffers {
@@ -235,8 +219,9 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
     (void)hipGetLastError();
     return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
   }
-  if (p->dtype == SRMAP_F32) launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, buf.d_part, st);
-  else launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, buf.d_part, st);
+  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, buf.d_part, st)
+                              : launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, buf.d_part, st)))
+    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
   SRMAP_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, buf.d_part, records, P, buf.d_sums);
   SRMAP_HIP(ctx, hipGetLastError());
@@ -308,11 +293,6 @@ extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srma
   if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
     return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  hipStream_t st = p->ctx->stream;
-  const size_t n = p->hr_count();
-  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
-  int rc = convert_upload(p, x_host, p->d_x, n, st);
-  if (rc) return rc;
-  return srmap_fit_blur_device(p, p->d_x, st, options, taps_out, quality_out, normal_equations_out);
+  if (int rc = stage_host_x(p, x_host)) return rc;
+  return srmap_fit_blur_device(p, p->d_x, p->ctx->stream, options, taps_out, quality_out, normal_equations_out);
 }

@@ -6,6 +6,11 @@
 //       srmap_reg_values, srmap_reg_values_and_gradient), and
 //   (b) the fallback of srmap_eval when the LDS-tiled kernels
 //       (kernels_tiled.hip) do not cover the geometry, and their cross-check.
+// The data-term kernels serve every motion kind (none, translation table, affine matrices, displacement field): the
+// forward kernel is one template over the kind's sampler, the transpose k_gather_direct for a translation and
+// k_gather_sampled for the kinds that warp per pixel (MotionSampler, sample_dev.hpp).  Source coordinates of those are
+// double in both dtypes (an f32 coordinate at 2048 px carries 1e-4 px of error); the weights are the double products
+// rounded to T.
 //
 // Math: SURVEY.md section 8(a'); reference lines are cited per kernel.
 #include <algorithm>
@@ -18,40 +23,48 @@
 
 namespace srmap {
 
-// identity_warp / warp_sample: sample_dev.hpp (shared with the blur fit)
+// identity_warp / warp_sample / MotionSampler: sample_dev.hpp (shared with the fits)
 
 // ---------------------------------------------------------------------------
 // Forward model A_k = D B M_k (image_model.cpp:86-91) at every LR pixel of
 // frames [k0, k0+gridDim.z), optionally minus the observation, optionally with
 // the data-term cost partial s^2 * sum(res^2) (objective_data_term.cpp:29-50).
+// MOTION (compile time): how M_k is sampled (MotionSampler) -- kMotionTable (also a problem without motion: the identity
+// table), kMotionAffine, kMotionFlow.  The per-pixel kinds read their sources through the caches: per LR pixel b^2 x 4 taps
+// of x, and two field values per blur tap for a flow.
 // WEIGHTED (compile time; needs y): per-observation weights dw indexed like y -- out = w * res, partial s^2 * sum(w res^2).
-template <typename T, bool WEIGHTED>
+template <typename T, int MOTION, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_forward_direct(
     const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out,
     double* __restrict__ partials, Geometry g,
-    const WarpTaps<T>* __restrict__ warps, const T* __restrict__ blur,
+    MotionArgs<T> ma, const T* __restrict__ blur,
     const int* __restrict__ col_map, const int* __restrict__ row_map, int k0,
     double cost_scale, int obs_C, int obs_c0, const T* __restrict__ dw) {
   __shared__ double red[4];
-  __shared__ T comb[36];  // blur (x) bilinear taps of this block's frame, (b+1) x (b+1), b <= 5
+  __shared__ T comb[36];  // table kind: blur (x) bilinear taps of this block's frame, (b+1) x (b+1), b <= 5
   const int lp = blockIdx.x * 256 + threadIdx.x;
   const int c = blockIdx.y, kk = blockIdx.z, k = k0 + kk;
   const int n = g.w * g.h;
-  const WarpTaps<T> wt = warps ? warps[k] : identity_warp<T>();
-  // interior fast path for bilinear warps: one (b+1)^2 stencil on x instead of b^2 four-tap samples
-  const bool use_comb = wt.ntaps == 4 && wt.ytab == nullptr && g.b <= 5;
+  const MotionSampler<T, MOTION> ms(ma, g, k);
+  // table kind, interior fast path for bilinear warps: one (b+1)^2 stencil on x instead of b^2 four-tap samples (a
+  // per-pixel kind has no such stencil: its fractions vary from pixel to pixel)
+  bool use_comb = false;
   const int nb1 = g.b + 1;
-  if (use_comb) {
-    if ((int)threadIdx.x < nb1 * nb1) {
-      const int a1 = threadIdx.x / nb1, e1 = threadIdx.x - a1 * nb1;
-      T s = T(0);
-      for (int t = 0; t < 4; ++t) {
-        const int a = a1 - (t >> 1), e = e1 - (t & 1);
-        if (a >= 0 && a < g.b && e >= 0 && e < g.b) s += blur[a * g.b + e] * wt.w[t];
+  if constexpr (MOTION == kMotionTable) {
+    const WarpTaps<T>& wt = ms.wt;
+    use_comb = wt.ntaps == 4 && wt.ytab == nullptr && g.b <= 5;
+    if (use_comb) {
+      if ((int)threadIdx.x < nb1 * nb1) {
+        const int a1 = threadIdx.x / nb1, e1 = threadIdx.x - a1 * nb1;
+        T s = T(0);
+        for (int t = 0; t < 4; ++t) {
+          const int a = a1 - (t >> 1), e = e1 - (t & 1);
+          if (a >= 0 && a < g.b && e >= 0 && e < g.b) s += blur[a * g.b + e] * wt.w[t];
+        }
+        comb[threadIdx.x] = s;
       }
-      comb[threadIdx.x] = s;
+      __syncthreads();
     }
-    __syncthreads();
   }
   double sq = 0.0;
   if (lp < n) {
@@ -59,7 +72,11 @@ __global__ __launch_bounds__(256) void k_forward_direct(
     const int R0 = row_map[i], C0 = col_map[j];
     const T* plane = x + (size_t)c * g.W * g.H;
     T acc = T(0);
-    const int sr0 = R0 - g.hb + wt.oy, sc0 = C0 - g.hb + wt.ox;
+    int sr0 = 0, sc0 = 0;  // the stencil's first source pixel
+    if constexpr (MOTION == kMotionTable) {
+      sr0 = R0 - g.hb + ms.wt.oy;
+      sc0 = C0 - g.hb + ms.wt.ox;
+    }
     if (use_comb && R0 - g.hb >= 0 && R0 + g.hb < g.H && C0 - g.hb >= 0 && C0 + g.hb < g.W && sr0 >= 0 &&
         sr0 + g.b < g.H && sc0 >= 0 && sc0 + g.b < g.W) {
       const T* src = plane + (size_t)sr0 * g.W + sc0;
@@ -72,7 +89,7 @@ __global__ __launch_bounds__(256) void k_forward_direct(
         for (int e = 0; e < g.b; ++e) {
           const int cc = C0 + e - g.hb;
           if (cc < 0 || cc >= g.W) continue;
-          acc += blur[a * g.b + e] * warp_sample(plane, g.W, g.H, wt, rr, cc);
+          acc += blur[a * g.b + e] * ms.template at<T>(plane, g.W, g.H, rr, cc);
         }
       }
     }
@@ -99,23 +116,34 @@ __global__ __launch_bounds__(256) void k_forward_direct(
   }
 }
 
+// the device buffers of the problem's motion kind exist (a launcher's internal-consistency refusal)
+static int motion_buffers_ok(srmap_problem* p, int kind) {
+  if (kind == kMotionAffine && !p->d_affine) return set_error(p->ctx, SRMAP_EINVAL, "internal: no affine motion set");
+  if (kind == kMotionFlow && (!p->d_flow || !p->d_flow_seed)) return set_error(p->ctx, SRMAP_EINVAL, "internal: no displacement field set");
+  return SRMAP_OK;
+}
+
 template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
                           double* partials, int* nblocks, hipStream_t st, const T* dw) {
-  if (p->flow) return launch_forward_flow<T>(p, g, x, y, obs_C, obs_c0, out, k0, nk, partials, nblocks, st, dw);
-  if (p->affine) return launch_forward_affine<T>(p, g, x, y, obs_C, obs_c0, out, k0, nk, partials, nblocks, st, dw);
+  int kind = motion_kind(p);
+  if (int rc = motion_buffers_ok(p, kind)) return rc;
+  if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
+  if (kind == kMotionNone) kind = kMotionTable;  // no table: the sampler takes the identity
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
-  if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
-  const WarpTaps<T>* warps = p->has_motion ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr;
-  if (dw != nullptr)
-    hipLaunchKernelGGL((k_forward_direct<T, true>), grid, dim3(256), 0, st, x, y, out, partials, g, warps,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
-  else
-    hipLaunchKernelGGL((k_forward_direct<T, false>), grid, dim3(256), 0, st, x, y, out, partials, g, warps,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C,
-                       obs_c0, dw);
+  const MotionArgs<T> ma = motion_args<T>(p);
+  const bool launched = dispatch_motion<kMotionTable, kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
+    constexpr int MOTION = decltype(motion)::value;
+    if (dw != nullptr)
+      hipLaunchKernelGGL((k_forward_direct<T, MOTION, true>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
+                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
+    else
+      hipLaunchKernelGGL((k_forward_direct<T, MOTION, false>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
+                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
+  });
+  if (!launched) return set_error(p->ctx, SRMAP_EINVAL, "internal: no forward kernel for motion kind %d", kind);
   if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
@@ -352,6 +380,68 @@ __global__ __launch_bounds__(256) void k_gather_ring(const T* __restrict__ resid
   else gout[o] = gold + out_scale * acc;
 }
 
+// ---------------------------------------------------------------------------
+// The same transpose for a motion kind that warps per pixel (kMotionAffine, kMotionFlow), as the EXACT transpose of the
+// forward kernel's matrix in gather form: g = (accumulate ? g : 0) + out_scale * sum_k M_k^T B^T D^T r_k at every HR pixel,
+// frames in increasing order, per frame the kWindow x kWindow candidates q of the kind in row-major order, each weight
+// recomputed by the forward kernel's expressions (MotionSampler::window / weight) -- the two kernels hold the same matrix
+// bit for bit and no atomics are needed.  Per HR pixel, frame and candidate the taps of B^T D^T that land on the LR grid
+// come through the caches.  SC: the scale at compile time (2, 3, 4; 0 = run time), as k_gather_direct.
+template <typename T, int MOTION, int SC>
+__global__ __launch_bounds__(256) void k_gather_sampled(const T* __restrict__ resid, T* __restrict__ gout, Geometry g,
+                                                       MotionArgs<T> ma, const T* __restrict__ blur_t, int k0, int nk,
+                                                       T out_scale, int accumulate) {
+  constexpr int WIN = MotionSampler<T, MOTION>::kWindow;
+  const int gs = SC ? SC : g.s;
+  const int hp = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  const int N = g.W * g.H, n = g.w * g.h;
+  if (hp >= N) return;
+  const int r = hp / g.W, col = hp - r * g.W;
+  T acc = T(0);
+  for (int kk = 0; kk < nk; ++kk) {
+    const MotionSampler<T, MOTION> ms(ma, g, k0 + kk);  // uniform
+    const T* rk = resid + ((size_t)kk * g.C + c) * n;
+    int qx0, qy0;
+    if (!ms.window(g, hp, r, col, &qx0, &qy0)) continue;
+    T tk = T(0);
+    for (int dy = 0; dy < WIN; ++dy) {
+      const int qy = qy0 + dy;
+      if (qy < 0 || qy >= g.H) continue;
+      for (int dx = 0; dx < WIN; ++dx) {
+        const int qx = qx0 + dx;
+        if (qx < 0 || qx >= g.W) continue;
+        const size_t qi = (size_t)qy * g.W + qx;
+        const double wx = ms.weight_x(qi, qx, qy, col);
+        if (wx == 0.0) continue;  // a flow reads the y component only where the x weight is not zero
+        const double wd = ms.weight_y(qi, qx, qy, r) * wx;
+        if (wd == 0.0) continue;  // p is no tap of q
+        tk += (T)wd * blur_t_upsampled_at(rk, blur_t, g, gs, qy, qx);
+      }
+    }
+    acc += tk;
+  }
+  const size_t o = (size_t)c * N + hp;
+  const T base = accumulate ? gout[o] : T(0);
+  gout[o] = base + out_scale * acc;
+}
+
+template <typename T, int MOTION>
+static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk,
+                                  double out_scale, bool accumulate, hipStream_t st) {
+  dim3 grid((unsigned)(((size_t)geo.W * geo.H + 255) / 256), geo.C);
+  const MotionArgs<T> ma = motion_args<T>(p);
+  const T* bt = (const T*)p->d_blur_t;
+  const int acc1 = accumulate ? 1 : 0;
+#define SRMAP_GATHER_SAMPLED(SS) \
+  hipLaunchKernelGGL((k_gather_sampled<T, MOTION, SS>), grid, dim3(256), 0, st, resid, g, geo, ma, bt, k0, nk, (T)out_scale, acc1)
+  if (geo.s == 2) SRMAP_GATHER_SAMPLED(2);
+  else if (geo.s == 3) SRMAP_GATHER_SAMPLED(3);
+  else if (geo.s == 4) SRMAP_GATHER_SAMPLED(4);
+  else SRMAP_GATHER_SAMPLED(0);
+#undef SRMAP_GATHER_SAMPLED
+}
+
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring) {
   return ring > 0 && 2 * ring < geo.H && 2 * ring < geo.W && p->has_motion && p->d_bwd_warps != nullptr && geo.b <= geo.s &&
          geo.s >= 2 && geo.s <= 4 && nk <= 16 && p->d_ytabs.empty();
@@ -361,13 +451,18 @@ template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring, T* ringbuf) {
-  if (p->flow) {
-    if (ring > 0 || ringbuf != nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which a displacement field has none of");
-    return launch_gather_flow<T>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
-  }
-  if (p->affine) {
-    if (ring > 0 || ringbuf != nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which an affine motion has none of");
-    return launch_gather_affine<T>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
+  const int kind = motion_kind(p);
+  if (kind == kMotionAffine || kind == kMotionFlow) {
+    if (ring > 0 || ringbuf != nullptr)
+      return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which %s has none of",
+                       kind == kMotionFlow ? "a displacement field" : "an affine motion");
+    if (int rc = motion_buffers_ok(p, kind)) return rc;
+    if (!dispatch_motion<kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
+          launch_gather_sampled<T, decltype(motion)::value>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
+        }))
+      return set_error(p->ctx, SRMAP_EINVAL, "internal: no sampled gather for motion kind %d", kind);
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return SRMAP_OK;
   }
   // ring > 0: only the pixels within `ring` of the image edge (the exact border of the sub-pixel tile path)
   size_t npix = (size_t)geo.W * geo.H;

@@ -1,10 +1,12 @@
-// kernels_flow.hip -- the direct family's data-term kernels for a DENSE per-frame displacement field
-// (srmap_problem_set_flow; no reference counterpart: motion_module.cpp:18-51 warps by a translation only).  DESIGN.md 3.11.
+// kernels_flow.hip -- the set-time side of the DENSE per-frame displacement field (srmap_problem_set_flow; no reference
+// counterpart: motion_module.cpp:18-51 warps by a translation only).  DESIGN.md 3.11.
 //
 // Frame k carries a field u_k = (ux, uy) on its HR-grid image, stored in the problem's dtype as [K][2][H][W].  The forward
 // warp samples x bilinearly at s = q + u_k(q) for every pixel q of the warped image (taps outside the image contribute 0:
 // affine_sample); blur and decimation are the translational path's.  s = (double)q + (double)u is exact in double for
-// both dtypes (|u| <= 2^20), and the weights are the double products rounded to T, as in the affine model.
+// both dtypes (|u| <= 2^20), and the weights are the double products rounded to T, as in the affine model.  The kernels
+// that evaluate it are k_forward_direct and k_gather_sampled (kernels_direct.hip) through MotionSampler's flow kind
+// (sample_dev.hpp).
 //
 // The transpose is the EXACT transpose of that matrix in gather form.  For an HR pixel p the contributing q are those with
 // q + u(q) strictly inside p +- 1 per axis.  They are found through a SEED stored per (k, p) when the field is set
@@ -12,11 +14,7 @@
 // and recomputes each candidate's weight from s by the forward kernel's expressions (flow_source, affine_axis_weight), so
 // the two kernels hold the same matrix bit for bit and no atomics are needed.  That every (q, p) pair of the matrix lies
 // inside p's window is VERIFIED when the field is set (k_flow_check walks the forward direction), not assumed: a field
-// that folds or shears beyond the window is refused and never reaches these kernels.
-//
-// Both kernels read their sources through the caches (per LR pixel b^2 x (2 field values + 4 taps of x); per HR pixel and
-// frame one seed and <= 25 candidates' field values, the x component first and the y component only where the x weight is
-// not zero).  The plane bases of the field and of the seeds are formed from wave-uniform values (blockIdx, the frame loop).
+// that folds or shears beyond the window is refused and never reaches those kernels.
 #include <algorithm>
 #include <cmath>
 
@@ -29,153 +27,11 @@ namespace srmap {
 namespace {
 
 constexpr int kFlowSeedSteps = 16;         // fixed-point steps of k_flow_seed (it stops early at a fixed point)
-constexpr int kFlowPad = kFlowRadius;      // seeds are clamped to [-kFlowPad, W - 1 + kFlowPad] per axis before packing
 constexpr double kFlowMaxDisp = 1048576.0; // 2^20
 
-// seed (sx, sy), each clamped to [-kFlowPad, size - 1 + kFlowPad], as one int
-__device__ __forceinline__ int flow_pack_seed(int sx, int sy, int W) { return (sy + kFlowPad) * (W + 2 * kFlowPad) + (sx + kFlowPad); }
-__device__ __forceinline__ void flow_unpack_seed(int v, int W, int* sx, int* sy) {
-  const int SW = W + 2 * kFlowPad;
-  const int y = v / SW;
-  *sy = y - kFlowPad;
-  *sx = v - y * SW - kFlowPad;
-}
+// flow_pack_seed / flow_unpack_seed, kFlowPad: sample_dev.hpp (shared with the gather)
 
 }  // namespace
-
-// ---------------------------------------------------------------------------
-// A_k = D B M_k at every LR pixel of frames [k0, k0 + gridDim.z): k_forward_affine's contract (residual or weighted
-// residual into `out`, cost partial with the cost-row test, one partial per workgroup in the same order).
-template <typename T, bool WEIGHTED>
-__global__ __launch_bounds__(256) void k_forward_flow(
-    const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out, double* __restrict__ partials, Geometry g,
-    const T* __restrict__ flow, const T* __restrict__ blur, const int* __restrict__ col_map,
-    const int* __restrict__ row_map, int k0, double cost_scale, int obs_C, int obs_c0, const T* __restrict__ dw) {
-  __shared__ double red[4];
-  const int lp = blockIdx.x * 256 + threadIdx.x;
-  const int c = blockIdx.y, kk = blockIdx.z, k = k0 + kk;
-  const int n = g.w * g.h;
-  const size_t N = (size_t)g.W * g.H;
-  const T* __restrict__ fux = flow + (size_t)k * 2 * N;  // uniform bases
-  const T* __restrict__ fuy = fux + N;
-  double sq = 0.0;
-  if (lp < n) {
-    const int i = lp / g.w, j = lp - i * g.w;
-    const int R0 = row_map[i], C0 = col_map[j];
-    const T* plane = x + (size_t)c * N;
-    T acc = T(0);
-    for (int a = 0; a < g.b; ++a) {
-      const int rr = R0 + a - g.hb;
-      if (rr < 0 || rr >= g.H) continue;  // filter2D BORDER_CONSTANT on the warped image
-      for (int e = 0; e < g.b; ++e) {
-        const int cc = C0 + e - g.hb;
-        if (cc < 0 || cc >= g.W) continue;
-        const size_t qi = (size_t)rr * g.W + cc;
-        const double sx = flow_source(cc, fux[qi]), sy = flow_source(rr, fuy[qi]);
-        acc += blur[a * g.b + e] * affine_sample(plane, g.W, g.H, sx, sy);
-      }
-    }
-    T res = acc;
-    if (WEIGHTED) {
-      const size_t oi = ((size_t)k * obs_C + c + obs_c0) * n + lp;
-      const T yv = y[oi], wv = dw[oi];
-      res -= yv;
-      const T wr = wv * res;
-      out[((size_t)kk * g.C + c) * n + lp] = wr;
-      sq = (i * g.s >= g.cr0 && i * g.s < g.cr1) ? (double)wr * (double)res : 0.0;
-    } else {
-      if (y) res -= y[((size_t)k * obs_C + c + obs_c0) * n + lp];
-      out[((size_t)kk * g.C + c) * n + lp] = res;
-      sq = (i * g.s >= g.cr0 && i * g.s < g.cr1) ? (double)res * (double)res : 0.0;
-    }
-  }
-  if (partials) {
-    const double s = block_sum_256(sq, red);
-    if (threadIdx.x == 0)
-      partials[(size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = cost_scale * s;
-  }
-}
-
-template <typename T>
-int launch_forward_flow(srmap_problem* p, const Geometry& g, const T* x, const T* y, int obs_C, int obs_c0, T* out,
-                        int k0, int nk, double* partials, int* nblocks, hipStream_t st, const T* dw) {
-  if (!p->flow || !p->d_flow) return set_error(p->ctx, SRMAP_EINVAL, "internal: no displacement field set");
-  if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
-  dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
-  const double cost_scale = (double)g.s * (double)g.s;
-  if (dw != nullptr)
-    hipLaunchKernelGGL((k_forward_flow<T, true>), grid, dim3(256), 0, st, x, y, out, partials, g, (const T*)p->d_flow,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
-  else
-    hipLaunchKernelGGL((k_forward_flow<T, false>), grid, dim3(256), 0, st, x, y, out, partials, g, (const T*)p->d_flow,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
-  if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
-  SRMAP_HIP(p->ctx, hipGetLastError());
-  return SRMAP_OK;
-}
-
-// ---------------------------------------------------------------------------
-// g = (accumulate ? g : 0) + out_scale * sum_k M_k^T B^T D^T r_k at every HR pixel: frames in increasing order, per frame
-// the 5 x 5 candidates q around the seed in row-major order.  SC: the scale at compile time (2, 3, 4; 0 = run time).
-template <typename T, int SC>
-__global__ __launch_bounds__(256) void k_gather_flow(const T* __restrict__ resid, T* __restrict__ gout, Geometry g,
-                                                    const T* __restrict__ flow, const int* __restrict__ seeds,
-                                                    const T* __restrict__ blur_t, int k0, int nk, T out_scale,
-                                                    int accumulate) {
-  const int gs = SC ? SC : g.s;
-  const int hp = blockIdx.x * 256 + threadIdx.x;
-  const int c = blockIdx.y;
-  const int N = g.W * g.H, n = g.w * g.h;
-  if (hp >= N) return;
-  const int r = hp / g.W, col = hp - r * g.W;
-  T acc = T(0);
-  for (int kk = 0; kk < nk; ++kk) {
-    const size_t kb = (size_t)(k0 + kk);  // uniform bases
-    const T* __restrict__ fux = flow + kb * 2 * N;
-    const T* __restrict__ fuy = fux + N;
-    const T* rk = resid + ((size_t)kk * g.C + c) * n;
-    int qxs, qys;
-    flow_unpack_seed(seeds[kb * N + hp], g.W, &qxs, &qys);
-    T tk = T(0);
-    for (int dy = -kFlowRadius; dy <= kFlowRadius; ++dy) {
-      const int qy = qys + dy;
-      if (qy < 0 || qy >= g.H) continue;
-      for (int dx = -kFlowRadius; dx <= kFlowRadius; ++dx) {
-        const int qx = qxs + dx;
-        if (qx < 0 || qx >= g.W) continue;
-        const size_t qi = (size_t)qy * g.W + qx;
-        const double wx = affine_axis_weight(flow_source(qx, fux[qi]), col);
-        if (wx == 0.0) continue;
-        const double wd = affine_axis_weight(flow_source(qy, fuy[qi]), r) * wx;
-        if (wd == 0.0) continue;  // p is no tap of q
-        tk += (T)wd * blur_t_upsampled_at(rk, blur_t, g, gs, qy, qx);
-      }
-    }
-    acc += tk;
-  }
-  const size_t o = (size_t)c * N + hp;
-  const T base = accumulate ? gout[o] : T(0);
-  gout[o] = base + out_scale * acc;
-}
-
-template <typename T>
-int launch_gather_flow(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk, double out_scale,
-                       bool accumulate, hipStream_t st) {
-  if (!p->flow || !p->d_flow || !p->d_flow_seed) return set_error(p->ctx, SRMAP_EINVAL, "internal: no displacement field set");
-  dim3 grid((unsigned)(((size_t)geo.W * geo.H + 255) / 256), geo.C);
-  const T* bt = (const T*)p->d_blur_t;
-  const int acc1 = accumulate ? 1 : 0;
-#define SRMAP_GATHER_FLOW(SS)                                                                                      \
-  hipLaunchKernelGGL((k_gather_flow<T, SS>), grid, dim3(256), 0, st, resid, g, geo, (const T*)p->d_flow, p->d_flow_seed, \
-                     bt, k0, nk, (T)out_scale, acc1)
-  if (geo.s == 2) SRMAP_GATHER_FLOW(2);
-  else if (geo.s == 3) SRMAP_GATHER_FLOW(3);
-  else if (geo.s == 4) SRMAP_GATHER_FLOW(4);
-  else SRMAP_GATHER_FLOW(0);
-#undef SRMAP_GATHER_FLOW
-  SRMAP_HIP(p->ctx, hipGetLastError());
-  return SRMAP_OK;
-}
 
 // ---------------------------------------------------------------------------
 // Set time.  seeds[k][p] = the fixed point (or the kFlowSeedSteps-th iterate) of q <- round(p - u_k(clamp(q))) from q = p,
@@ -340,13 +196,6 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
   if (ztile_plan(p)) ztile_preload(p);  // "not covered" while a flow is set
   return SRMAP_OK;
 }
-
-#define INSTANTIATE_FLOW(T)                                                                                            \
-  template int launch_forward_flow<T>(srmap_problem*, const Geometry&, const T*, const T*, int, int, T*, int, int,    \
-                                      double*, int*, hipStream_t, const T*);                                           \
-  template int launch_gather_flow<T>(srmap_problem*, const Geometry&, const T*, T*, int, int, double, bool, hipStream_t);
-INSTANTIATE_FLOW(float)
-INSTANTIATE_FLOW(double)
 
 }  // namespace srmap
 

@@ -1,4 +1,4 @@
-// motion_fit_dev.hpp -- device inlines shared by kernels_affine.hip, registration.hip, registration_affine.hip and
+// motion_fit_dev.hpp -- device inlines shared by sample_dev.hpp, registration.hip, registration_affine.hip and
 // motion_refinement.hip: the sample-position expression of the affine model and the fixed-order reductions of the fits.
 #pragma once
 

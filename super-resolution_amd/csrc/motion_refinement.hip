@@ -4,7 +4,7 @@
 // frame-to-frame registration (registration_affine.hip).  No reference counterpart; the checker is
 // tests/motion_refinement_restatement.py.
 //   pass      ONE launch of k_refine_sums for every still-active frame: per LR pixel and channel the residual r and
-//             J_i = sum over k_forward_affine's blur taps of blur * g * {q_x - c0x, q_y - c0y, 1}, g the exact derivative of
+//             J_i = sum over k_forward_direct's blur taps of blur * g * {q_x - c0x, q_y - c0y, 1}, g the exact derivative of
 //             the four-tap sample in s_x (i = 0..2) or s_y (i = 3..5), from the four tap values the sample itself uses;
 //             28 f64 sums per workgroup (21 of H = sum w J J^T, upper triangle row-major; 6 of g = sum w J r; E), folded by a
 //             wave shuffle and LDS in a fixed order, no atomics (fold_sums_256); k_fit_reduce adds the chunk records in
@@ -13,7 +13,7 @@
 //             motion_fit.hip);
 //   LM        on the host in double, per frame, in lockstep: (H + lambda diag H) d = -g by the Cholesky of affine_map.hpp
 //             (dof = 2: the 2 x 2 sub-system of (tx, ty)), G' = G + dL (q - c0) + dt.
-// Everything after the loads is double in both dtypes.  Sample positions are kernels_affine.hip's (affine_coord of
+// Everything after the loads is double in both dtypes.  Sample positions are the affine sampler's (sample_dev.hpp; affine_coord of
 // motion_fit_dev.hpp).
 #include <algorithm>
 #include <cmath>
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
       double val = 0.0, J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       for (int a = 0; a < g.b; ++a) {
         const int rr = R0 + a - g.hb;
-        if (rr < 0 || rr >= g.H) continue;  // k_forward_affine's taps: the blur's zero border
+        if (rr < 0 || rr >= g.H) continue;  // k_forward_direct's taps: the blur's zero border
         for (int e = 0; e < g.b; ++e) {
           const int cc = C0 + e - g.hb;
           if (cc < 0 || cc >= g.W) continue;
@@ -313,11 +313,6 @@ extern "C" int srmap_refine_motion(srmap_problem* p, const double* x_host, const
   if (options && options->struct_size != (int)sizeof(srmap_motion_refinement_options))
     return set_error(p->ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  hipStream_t st = p->ctx->stream;
-  const size_t n = p->hr_count();
-  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
-  int rc = convert_upload(p, x_host, p->d_x, n, st);
-  if (rc) return rc;
-  return srmap_refine_motion_device(p, p->d_x, st, options, affine_2x3_out, quality_out, normal_equations_out);
+  if (int rc = stage_host_x(p, x_host)) return rc;
+  return srmap_refine_motion_device(p, p->d_x, p->ctx->stream, options, affine_2x3_out, quality_out, normal_equations_out);
 }

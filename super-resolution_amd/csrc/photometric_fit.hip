@@ -6,8 +6,8 @@
 //   normalise k_photometric_normalise: per element, in double on the stored value, the subtraction, a true division, one
 //             rounding to the problem's dtype (no reciprocal, no contraction: a numpy restatement is bit-identical);
 //   pass      ONE launch of k_photometric_sums over every frame: per LR pixel and channel s = (D B M_k x)(c, u), M_k
-//             sampled as the problem's forward kernel samples it (warp_sample / affine_sample of sample_dev.hpp,
-//             affine_coord of motion_fit_dev.hpp; the identity without motion), the blur in force; six f64 sums per
+//             sampled as the problem's forward kernel samples it (MotionSampler of sample_dev.hpp; the
+//             identity without motion), the blur in force; six f64 sums per
 //             workgroup {w, w s, w y, w s^2, w s y, w y^2} held in registers in both dtypes, folded by a wave shuffle and
 //             LDS in a fixed order, no atomics (fold_sums_256); k_fit_reduce adds the chunk records in index order;
 //   pacing    one launch, one reduce, one copy of K x 6 doubles, one stream wait (FitPass, motion_fit.hip);
@@ -27,7 +27,6 @@ namespace srmap {
 namespace {
 
 constexpr int kMaxChunks = 256;
-enum { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2 };
 
 // out[i] = (raw[i] - bias_k) / gain_k rounded once to T, k the frame of element i; gb[k] = {gain, bias}
 template <typename T>
@@ -48,15 +47,13 @@ __global__ __launch_bounds__(256) void k_photometric_normalise(const T* __restri
 template <typename T, int MOTION, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ x, const T* __restrict__ y,
                                                           const T* __restrict__ dw, Geometry g,
-                                                          const WarpTaps<T>* __restrict__ warps,
-                                                          const double* __restrict__ recs, const T* __restrict__ blur,
+                                                          MotionArgs<T> ma, const T* __restrict__ blur,
                                                           const int* __restrict__ col_map, const int* __restrict__ row_map,
                                                           int ppt, double* __restrict__ partial) {
   __shared__ double red[kPhotoSums][4];
   const int k = blockIdx.y;
   const int n = g.w * g.h;
-  const WarpTaps<T> wt = (MOTION == kMotionTable) ? warps[k] : identity_warp<T>();
-  const double* __restrict__ mk = (MOTION == kMotionAffine) ? recs + (size_t)k * kAffineRec : nullptr;  // uniform
+  const MotionSampler<T, MOTION> ms(ma, g, k);  // uniform
   double acc[kPhotoSums];
 #pragma unroll
   for (int q = 0; q < kPhotoSums; ++q) acc[q] = 0.0;
@@ -78,16 +75,7 @@ __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ 
         for (int e = 0; e < g.b; ++e) {
           const int cc = C0 + e - g.hb;
           if (cc < 0 || cc >= g.W) continue;
-          double v;
-          if (MOTION == kMotionAffine) {
-            const double sx = affine_coord(mk[0], mk[1], mk[2], (double)cc, (double)rr);
-            const double sy = affine_coord(mk[3], mk[4], mk[5], (double)cc, (double)rr);
-            v = affine_sample<T, double>(plane, g.W, g.H, sx, sy);
-          } else if (MOTION == kMotionTable) {
-            v = warp_sample<T, double>(plane, g.W, g.H, wt, rr, cc);
-          } else {
-            v = (double)plane[(size_t)rr * g.W + cc];
-          }
+          const double v = ms.template at<double>(plane, g.W, g.H, rr, cc);
           s += (double)blur[a * g.b + e] * v;
         }
       }
@@ -103,26 +91,22 @@ __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ 
   fold_sums_256(acc, red, partial + ((size_t)k * gridDim.x + blockIdx.x) * kPhotoSums);
 }
 
-template <typename T, int MOTION>
-void launch_sums_w(srmap_problem* p, const T* x, const T* y, int chunks, int ppt, double* d_part, hipStream_t st) {
+// the instance of the problem's motion kind; false: the kind has none (a displacement field, which the entry point refuses)
+template <typename T>
+bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
-  const WarpTaps<T>* warps = MOTION == kMotionTable ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr;
-  const double* recs = MOTION == kMotionAffine ? p->d_affine : nullptr;
-  if (p->d_dw)
-    hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, (const T*)p->d_dw, g, warps, recs,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
-  else
-    hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, warps,
-                       recs, (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
-}
-
-template <typename T>
-void launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_part, hipStream_t st) {
   const T* y = (const T*)(p->d_obs_raw ? p->d_obs_raw : p->d_obs);  // always the RAW frames: the fit is absolute
-  if (p->affine) launch_sums_w<T, kMotionAffine>(p, x, y, chunks, ppt, d_part, st);
-  else if (p->has_motion) launch_sums_w<T, kMotionTable>(p, x, y, chunks, ppt, d_part, st);
-  else launch_sums_w<T, kMotionNone>(p, x, y, chunks, ppt, d_part, st);
+  const MotionArgs<T> ma = motion_args<T>(p);
+  return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+    constexpr int MOTION = decltype(motion)::value;
+    if (p->d_dw)
+      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, (const T*)p->d_dw, g, ma,
+                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
+    else
+      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, ma,
+                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
+  });
 }
 
 }  // namespace
@@ -268,8 +252,9 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
   const AffineMap identity = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};  // the table carries the active flags alone here
   for (int k = 0; k < K; ++k) fit.set(k, identity, true);
   if (!fit.upload(st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: upload failed");
-  if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, chunks, ppt, fit.d_part, st);
-  else launch_sums<double>(p, (const double*)x_dev, chunks, ppt, fit.d_part, st);
+  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, (const float*)x_dev, chunks, ppt, fit.d_part, st)
+                              : launch_sums<double>(p, (const double*)x_dev, chunks, ppt, fit.d_part, st)))
+    return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)motion_kind(p));
   if (!fit.reduce_and_fetch(chunks, st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: pass failed");
 
   // ---- the host solve, frame by frame ----
@@ -304,11 +289,7 @@ extern "C" int srmap_fit_photometric(srmap_problem* p, const double* x_host, con
   srmap_photometric_fit_options opt;
   int rc = photometric_fit_options(p, options, &opt);
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  hipStream_t st = p->ctx->stream;
-  const size_t n = p->hr_count();
-  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
-  rc = convert_upload(p, x_host, p->d_x, n, st);
+  rc = stage_host_x(p, x_host);
   if (rc) return rc;
-  return srmap_fit_photometric_device(p, p->d_x, st, options, gain_bias_out, quality_out, sums_out);
+  return srmap_fit_photometric_device(p, p->d_x, p->ctx->stream, options, gain_bias_out, quality_out, sums_out);
 }

@@ -1,7 +1,7 @@
 // registration_affine.hip -- affine registration of a frame stack on the GPU (srmap_register_affine).
 //
 // For every frame k >= 1: F_k(p) = L_k p + t_k with I_k(F_k(p)) ~= I_0(p), the convention of the affine motion model
-// (kernels_affine.hip) and of MotionShift.  No reference counterpart (registration.cpp keeps the translation of a
+// (srmap_problem_set_affine_motion) and of MotionShift.  No reference counterpart (registration.cpp keeps the translation of a
 // feature-based fit); the checker is tests/affine_registration_restatement.py.
 //   1. box pyramid of the whole stack, built once (k_down2_stack, motion_fit.hip), halved while the shorter side is >= 64;
 //   2. seed at the coarsest level: integer search over [-R, R]^2, mean squared difference over the FIXED template window
@@ -12,7 +12,7 @@
 //      (26 sums per workgroup, fixed-order reduction), one k_fit_reduce, one 26 x (K-1) double copy and one stream wait
 //      (FitPass, motion_fit.hip); the 6 x 6 Cholesky solve and the composition F <- F o W^-1 run on the host in double
 //      (affine_map.hpp).
-// Sample positions are kernels_affine.hip's (affine_coord of motion_fit_dev.hpp: every operation rounded on its own).
+// Sample positions are the affine sampler's (sample_dev.hpp; affine_coord of motion_fit_dev.hpp: every operation rounded on its own).
 #include <algorithm>
 #include <cmath>
 #include <vector>

@@ -1,13 +1,17 @@
-// sample_dev.hpp -- the sample functions of the forward model's warp M_k, shared by the kernels that evaluate it
-// (k_forward_direct of kernels_direct.hip, k_forward_affine of kernels_affine.hip, k_forward_flow of kernels_flow.hip),
-// their transposes in gather form (k_gather_affine, k_gather_flow) and the kernel that fits the blur to it
-// (k_blur_fit_sums of blur_fit.hip): ONE copy of each expression, so that a fit sees exactly the warped image an
-// evaluation blurs and a transpose recomputes exactly the weights its forward kernel multiplied by.  A is the type the four products are formed and added in: the storage type T in the evaluation
-// kernels, double in the fit (the taps and the weights are the same T values either way).
+// sample_dev.hpp -- the forward model's warp M_k on the device, shared by the kernels that evaluate it (k_forward_direct
+// of kernels_direct.hip, every motion kind), the transposes in gather form of the per-pixel kinds (k_gather_sampled) and
+// the kernels that fit to it (k_blur_fit_sums of blur_fit.hip, k_photometric_sums of photometric_fit.hip): ONE copy of
+// each expression AND of the choice between them (MotionSampler), so that a fit sees exactly the warped image an
+// evaluation blurs and a transpose recomputes exactly the weights its forward kernel multiplied by.  A is the type the
+// four products are formed and added in: the storage type T in the evaluation kernels, double in the fits (the taps and
+// the weights are the same T values either way).  MotionKind and the kernel argument block MotionArgs<T> are declared in
+// srmap_internal.hpp, next to the host helpers that name the kind, fill the block and dispatch on it.  The table kind
+// tests its table for null in every kernel (a uniform branch): only the forward kernel is ever given none.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "motion_fit_dev.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -65,7 +69,7 @@ __device__ __forceinline__ A affine_sample(const T* __restrict__ plane, int W, i
   return ((v0 * (A)w0 + v1 * (A)w1) + v2 * (A)w2) + v3 * (A)w3;
 }
 
-// s = q + u(q) along one axis, the sample position of the displacement-field model (kernels_flow.hip): both conversions
+// s = q + u(q) along one axis, the sample position of the displacement-field model: both conversions
 // and the one addition are exact in double for |u| <= 2^20, in both dtypes
 template <typename T>
 __device__ __forceinline__ double flow_source(int q, T u) {
@@ -102,5 +106,116 @@ __device__ __forceinline__ T blur_t_upsampled_at(const T* __restrict__ rk, const
   }
   return v;
 }
+
+// The transpose of the displacement-field model finds its candidates around a seed stored per (frame, HR pixel) when the
+// field is set (kernels_flow.hip): seed (sx, sy), each clamped to [-kFlowPad, size - 1 + kFlowPad], as one int
+constexpr int kFlowPad = kFlowRadius;
+__device__ __forceinline__ int flow_pack_seed(int sx, int sy, int W) { return (sy + kFlowPad) * (W + 2 * kFlowPad) + (sx + kFlowPad); }
+__device__ __forceinline__ void flow_unpack_seed(int v, int W, int* sx, int* sy) {
+  const int SW = W + 2 * kFlowPad;
+  const int y = v / SW;
+  *sy = y - kFlowPad;
+  *sx = v - y * SW - kFlowPad;
+}
+
+// M_k of frame k for one motion kind (MotionKind, srmap_internal.hpp), built from the kernel's argument block, the
+// geometry and the WAVE-UNIFORM frame index alone: the affine record then comes through scalar loads, and the plane bases
+// of the field and of the seeds are uniform.
+//   at<A>(plane, W, H, rr, cc)   (M_k x)(rr, cc) for (rr, cc) inside the W x H image: what every forward and fit kernel
+//                             multiplies a blur tap by.  The size comes by value, as the sample functions take it: read
+//                             through a reference to the geometry inside at(), the table kind's forward instance needed
+//                             three more registers and ran 2 % slower.
+// The per-pixel kinds also describe the exact transpose in gather form (k_gather_sampled): the pixels q whose footprint
+// can contain the HR pixel p = (col, r) are a kWindow x kWindow block,
+//   window(g, hp, r, col, &qx0, &qy0)   its first candidate, or false when p has none;
+//   weight_x(qi, qx, qy, col), weight_y(qi, qx, qy, r)   the two factors of the weight of (q, p), qi = qy * W + qx formed
+//                                       once by the gather, each recomputed from q's sample position along that axis by
+//                                       at()'s expressions (0.0: p is no tap of q); the gather asks for the y factor only
+//                                       where the x factor is not zero.
+template <typename T, int MOTION>
+struct MotionSampler;
+
+template <typename T>
+struct MotionSampler<T, kMotionNone> {
+  __device__ __forceinline__ MotionSampler(const MotionArgs<T>&, const Geometry&, int) {}
+  template <typename A>
+  __device__ __forceinline__ A at(const T* __restrict__ plane, int W, int H, int rr, int cc) const {
+    return (A)plane[(size_t)rr * W + cc];
+  }
+};
+
+// translation: the frame's tap table; a problem without motion has no table (warps == nullptr) and takes the identity
+template <typename T>
+struct MotionSampler<T, kMotionTable> {
+  WarpTaps<T> wt;
+  __device__ __forceinline__ MotionSampler(const MotionArgs<T>& a, const Geometry&, int k)
+      : wt(a.warps ? a.warps[k] : identity_warp<T>()) {}
+  template <typename A>
+  __device__ __forceinline__ A at(const T* __restrict__ plane, int W, int H, int rr, int cc) const {
+    return warp_sample<T, A>(plane, W, H, wt, rr, cc);
+  }
+};
+
+// affine: s = F_k^-1(q) by the frame's record (kAffineRec doubles: inverse map, forward map, candidate radii).  The
+// candidates of p are the integers inside F_k(p) +- (|a|+|b|, |c|+|d|), at most 3 x 3 under the entry point's bound.
+template <typename T>
+struct MotionSampler<T, kMotionAffine> {
+  static constexpr int kWindow = 3;
+  const double* __restrict__ m;
+  __device__ __forceinline__ MotionSampler(const MotionArgs<T>& a, const Geometry&, int k)
+      : m(a.recs + (size_t)k * kAffineRec) {}
+  template <typename A>
+  __device__ __forceinline__ A at(const T* __restrict__ plane, int W, int H, int rr, int cc) const {
+    const double sx = affine_coord(m[0], m[1], m[2], (double)cc, (double)rr);
+    const double sy = affine_coord(m[3], m[4], m[5], (double)cc, (double)rr);
+    return affine_sample<T, A>(plane, W, H, sx, sy);
+  }
+  __device__ __forceinline__ bool window(const Geometry& g, int, int r, int col, int* qx0, int* qy0) const {
+    // F_k(p) and the first candidate of each axis; clamped ahead of the conversion (a far translation: no candidate)
+    const double cx = affine_coord(m[6], m[7], m[8], (double)col, (double)r);
+    const double cy = affine_coord(m[9], m[10], m[11], (double)col, (double)r);
+    const double lx = __builtin_ceil(cx - m[12]), ly = __builtin_ceil(cy - m[13]);
+    if (!(lx > -4.0 && lx < (double)g.W && ly > -4.0 && ly < (double)g.H)) return false;
+    *qx0 = (int)lx;
+    *qy0 = (int)ly;
+    return true;
+  }
+  __device__ __forceinline__ double weight_x(size_t, int qx, int qy, int col) const {
+    return affine_axis_weight(affine_coord(m[0], m[1], m[2], (double)qx, (double)qy), col);
+  }
+  __device__ __forceinline__ double weight_y(size_t, int qx, int qy, int r) const {
+    return affine_axis_weight(affine_coord(m[3], m[4], m[5], (double)qx, (double)qy), r);
+  }
+};
+
+// displacement field: s = q + u_k(q), the (ux, uy) planes of frame k.  The candidates of p are the (2 kFlowRadius + 1)^2
+// pixels around p's seed (verified when the field was set).
+template <typename T>
+struct MotionSampler<T, kMotionFlow> {
+  static constexpr int kWindow = 2 * kFlowRadius + 1;
+  const T* __restrict__ fux;
+  const T* __restrict__ fuy;
+  const int* __restrict__ seeds;
+  __device__ __forceinline__ MotionSampler(const MotionArgs<T>& a, const Geometry& g, int k)
+      : fux(a.flow + (size_t)k * 2 * (g.W * g.H)), fuy(fux + g.W * g.H), seeds(a.seeds + (size_t)k * (g.W * g.H)) {}
+  template <typename A>
+  __device__ __forceinline__ A at(const T* __restrict__ plane, int W, int H, int rr, int cc) const {
+    const size_t qi = (size_t)rr * W + cc;
+    const double sx = flow_source(cc, fux[qi]), sy = flow_source(rr, fuy[qi]);
+    return affine_sample<T, A>(plane, W, H, sx, sy);
+  }
+  __device__ __forceinline__ bool window(const Geometry& g, int hp, int, int, int* qx0, int* qy0) const {
+    flow_unpack_seed(seeds[hp], g.W, qx0, qy0);
+    *qx0 -= kFlowRadius;
+    *qy0 -= kFlowRadius;
+    return true;
+  }
+  __device__ __forceinline__ double weight_x(size_t qi, int qx, int, int col) const {
+    return affine_axis_weight(flow_source(qx, fux[qi]), col);
+  }
+  __device__ __forceinline__ double weight_y(size_t qi, int, int qy, int r) const {
+    return affine_axis_weight(flow_source(qy, fuy[qi]), r);
+  }
+};
 
 }  // namespace srmap

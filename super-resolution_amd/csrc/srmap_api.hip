@@ -9,6 +9,7 @@
 #include <cstring>
 #include <new>
 
+#include "affine_map.hpp"
 #include "solver_passes.hpp"
 #include "srmap_internal.hpp"
 
@@ -396,6 +397,42 @@ int recover_reduction_timeout(srmap_problem* p, double* host_word) {
   if (p->d_cost) SRMAP_HIP(p->ctx, hipMemset(p->d_cost + 6, 0, sizeof(double)));
   if (host_word) *host_word = 0.0;
   return SRMAP_OK;
+}
+
+// srmap_problem_set_affine_motion (below) and the motion refinement: validate K 2x3 matrices and fill the per-frame
+// records (inverse in double, formed once here).
+int affine_records(srmap_ctx* ctx, int K, const double* a23, std::vector<double>* recs) {
+  for (int i = 0; i < 6 * K; ++i)
+    if (!std::isfinite(a23[i]))
+      return set_error(ctx, SRMAP_EINVAL, "affine motion: entry %d of frame %d is not finite", i % 6, i / 6);
+  recs->assign((size_t)K * kAffineRec, 0.0);
+  for (int k = 0; k < K; ++k) {
+    AffineMap F;
+    std::copy(a23 + 6 * k, a23 + 6 * (k + 1), F.m);
+    const double a = F.m[0], b = F.m[1], tx = F.m[2], c = F.m[3], d = F.m[4], ty = F.m[5];
+    const double dev = deviation(F);
+    if (!(dev <= kAffineMaxDeviation))
+      return set_error(ctx, SRMAP_EUNSUPPORTED,
+                       "affine motion of frame %d: max(|a-1|+|b|, |c|+|d-1|) = %g exceeds %g (the transpose gathers 3 x 3 candidates)",
+                       k, dev, kAffineMaxDeviation);
+    if (!(std::fabs(tx) < 1.0e9) || !(std::fabs(ty) < 1.0e9))
+      return set_error(ctx, SRMAP_EUNSUPPORTED, "affine motion of frame %d: translation (%g, %g) too large", k, tx, ty);
+    double* m = recs->data() + (size_t)k * kAffineRec;
+    const AffineMap G = inverse(F);
+    std::copy(G.m, G.m + 6, m);
+    std::copy(F.m, F.m + 6, m + 6);
+    // candidate radii, widened so that rounding of F(p) can drop no candidate (2 * (1.25 + 1e-9) < 3: still three integers)
+    m[12] = std::fabs(a) + std::fabs(b) + 1.0e-9;
+    m[13] = std::fabs(c) + std::fabs(d) + 1.0e-9;
+  }
+  return SRMAP_OK;
+}
+
+int stage_host_x(srmap_problem* p, const double* x_host) {
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const size_t n = p->hr_count();
+  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
+  return convert_upload(p, x_host, p->d_x, n, p->ctx->stream);
 }
 
 }  // namespace srmap

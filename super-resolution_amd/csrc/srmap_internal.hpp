@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "srmap.h"
@@ -16,7 +17,7 @@ constexpr int kMaxRegularizers = 4;
 constexpr int kMaxBtvRange = 8;        // alpha^(i+j) table holds 2*range+1 entries
 constexpr int kMaxBlurTaps = 15 * 15;  // b*b taps kept in kernel-argument space
 constexpr int kMaxCustomBlur = 7;      // largest size of a free-form kernel (srmap_problem_set_blur_kernel, srmap_fit_blur)
-// Affine motion (srmap_problem_set_affine_motion, kernels_affine.hip): doubles per frame record -- [0..5] the inverse map
+// Affine motion (srmap_problem_set_affine_motion): doubles per frame record -- [0..5] the inverse map
 // [ia ib itx; ic id ity], [6..11] the forward map [a b tx; c d ty], [12..13] the candidate radii of the transpose gather
 constexpr int kAffineRec = 16;
 constexpr double kAffineMaxDeviation = 0.25;  // max(|a-1|+|b|, |c|+|d-1|): bounds the gather at 3 x 3 candidates
@@ -37,6 +38,18 @@ struct WarpTaps {
   // within rounding distance of a quantisation tie the fraction index differs from row to row.  Then ytab (device,
   // one int per destination row: source row << 5 | fraction index) replaces oy and the y half of w.
   const int* ytab;
+};
+
+// The forms of M_k in A_k = D B M_k: none (the identity), the translational tap table, an affine matrix per frame, a dense
+// displacement field per frame.  MotionArgs: what the kernels that sample M_k (MotionSampler, sample_dev.hpp) take for
+// it, by value as ONE kernel argument; a kind reads its own members only.
+enum MotionKind { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2, kMotionFlow = 3 };
+template <typename T>
+struct MotionArgs {
+  const WarpTaps<T>* warps;  // [K] forward taps (table); nullptr: the identity
+  const double* recs;        // [K][kAffineRec] (affine)
+  const T* flow;             // [K][2][H][W] (flow)
+  const int* seeds;          // [K][H][W] packed seeds of the transpose gather (flow)
 };
 
 struct Geometry {
@@ -115,13 +128,13 @@ struct srmap_problem {
   bool has_motion = false;
   bool maps_regular = true;       // decimation map == s*j on both axes
   std::vector<double> shifts;     // K x 2
-  // affine motion model: when set, the data term of every evaluation and operator runs kernels_affine.hip and the tile
-  // planner answers "not covered"; the translational warps above stay as created (NULL restores them)
+  // affine motion model: when set, the data term of every evaluation and operator samples the frame's matrix (kMotionAffine)
+  // and the tile planner answers "not covered"; the translational warps above stay as created (NULL restores them)
   bool affine = false;
   std::vector<double> affine_recs;  // K x kAffineRec (host mirror of d_affine)
   double* d_affine = nullptr;
   // displacement-field motion model (an alternative to the affine one: setting either replaces the other): when set, the
-  // data term runs kernels_flow.hip.  d_flow: [K][2][H][W] dtype, the (ux, uy) planes per frame; d_flow_seed: [K][H][W]
+  // data term samples the frame's field (kMotionFlow).  d_flow: [K][2][H][W] dtype, the (ux, uy) planes per frame; d_flow_seed: [K][H][W]
   // packed seeds of the transpose gather, both validated when they were set
   bool flow = false;
   void* d_flow = nullptr;
@@ -226,22 +239,22 @@ template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring = 0, T* ringbuf = nullptr);
-// ---- affine motion (kernels_affine.hip): the two launchers above route here when p->affine ----
+// ---- the problem's motion, for the launchers of the kernels that sample it (the two above, the fits) ----
+inline MotionKind motion_kind(const srmap_problem* p) {
+  return p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;
+}
 template <typename T>
-int launch_forward_affine(srmap_problem* p, const Geometry& g, const T* x, const T* y, int obs_C, int obs_c0, T* out,
-                          int k0, int nk, double* partials, int* nblocks, hipStream_t st, const T* dw);
-template <typename T>
-int launch_gather_affine(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk, double out_scale,
-                         bool accumulate, hipStream_t st);
-// K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain)
+MotionArgs<T> motion_args(const srmap_problem* p) {
+  return {p->has_motion ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr, p->d_affine, (const T*)p->d_flow, p->d_flow_seed};
+}
+// f(std::integral_constant<int, KIND>) for the one of KINDS... that `kind` is -- the kinds the caller has kernel instances
+// of; false (and no call) for any other, which the caller answers as an internal error
+template <int... KINDS, typename F>
+bool dispatch_motion(int kind, F&& f) {
+  return ((kind == KINDS && (f(std::integral_constant<int, KINDS>()), true)) || ...);
+}
+// K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (srmap_api.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
-// ---- displacement-field motion (kernels_flow.hip): the two launchers above route here when p->flow ----
-template <typename T>
-int launch_forward_flow(srmap_problem* p, const Geometry& g, const T* x, const T* y, int obs_C, int obs_c0, T* out,
-                        int k0, int nk, double* partials, int* nblocks, hipStream_t st, const T* dw);
-template <typename T>
-int launch_gather_flow(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk, double out_scale,
-                       bool accumulate, hipStream_t st);
 // ---- the motion fits' shared kernels and per-pass buffers (motion_fit.hip) ----
 struct AffineMap;  // affine_map.hpp
 // dst[k][h/2][w/2] = mean of the 2 x 2 blocks of src[k][h][w], k < frames: one level of a box pyramid
@@ -376,5 +389,8 @@ int convert_upload(srmap_problem* p, const double* host, void* dev, size_t n,
                    hipStream_t st);
 int convert_download(srmap_problem* p, const void* dev, double* host, size_t n,
                      hipStream_t st);
+// The HR image of a host-buffer fit entry point into p->d_x (allocated on first use), enqueued on the context's stream.
+// The caller has made every check that needs no device: an error there leaves the problem, this buffer included, untouched
+int stage_host_x(srmap_problem* p, const double* x_host);
 
 }  // namespace srmap

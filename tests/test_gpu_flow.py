@@ -1,5 +1,5 @@
-"""The displacement-field motion model on the GPU (include/srmap.h: srmap_problem_set_flow; k_forward_flow, k_gather_flow,
-k_flow_seed and k_flow_check of csrc/kernels_flow.hip) against its numpy / scipy.sparse restatement
+"""The displacement-field motion model on the GPU (include/srmap.h: srmap_problem_set_flow; the flow instances of
+k_forward_direct and k_gather_sampled, k_flow_seed and k_flow_check of csrc/kernels_flow.hip) against its numpy / scipy.sparse restatement
 (tests/flow_restatement.py: explicit matrices, the literal transpose), against the translational and the affine direct
 kernels where the definitions coincide, and against itself.
 

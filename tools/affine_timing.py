@@ -1,7 +1,7 @@
 """Affine motion model: data-term evaluation times against the direct translational family, in one process.
    python tools/affine_timing.py [--dtype f32]
 At bench.py's cfg2 geometry (2048 x 2048, 16 frames, scale 4, blur 3) and at the 96 x 128 prototype (6 frames, scale 2):
-the affine problem (k_forward_affine + k_gather_affine; rotations of up to 2 degrees about the centre plus sub-pixel
+the affine problem (the affine instances of k_forward_direct + k_gather_sampled; rotations of up to 2 degrees about the centre plus sub-pixel
 shifts) and the same geometry under SRMAP_IMPL_DIRECT with the sub-pixel shifts alone (k_forward_direct +
 k_gather_direct), alternating, after a warm-up at sustained clocks.  Per problem: the cost-only data evaluation (forward
 kernel + cost reduction), the data evaluation with its gradient (+ gather kernel), their difference (the gather), and the

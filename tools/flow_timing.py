@@ -1,8 +1,8 @@
 """Displacement-field motion model: data-term evaluation times next to the affine kernels, in one process.
    python tools/flow_timing.py            (f64 and f32, both geometries; the figures of profiles/r14_flow.txt)
 At bench.py's cfg2 geometry (2048 x 2048, 16 frames, scale 4, blur 3) and at 1024 x 1024, 8 frames, scale 2: the SAME motion
-(rotations of up to 2 degrees about the centre plus sub-pixel shifts) once as matrices (k_forward_affine + k_gather_affine)
-and once as the field u(q) = F^-1(q) - q (k_forward_flow + k_gather_flow), alternating, after a warm-up at sustained clocks.
+(rotations of up to 2 degrees about the centre plus sub-pixel shifts) once as matrices (the affine instances of k_forward_direct
++ k_gather_sampled) and once as the field u(q) = F^-1(q) - q (their flow instances), alternating, after a warm-up at sustained clocks.
 Per problem: the cost-only data evaluation (forward kernel + cost reduction), the data evaluation with its gradient
 (+ gather kernel), their difference (the gather), and the whole evaluation with the BTV regulariser.  Algorithmic bytes:
 forward = x + observations read, residuals written (+ the field, K * 2 * H * W, for the flow); gather = residuals read,

@@ -1,4 +1,4 @@
-"""Joint motion refinement (srmap_refine_motion): what a pass and a whole call cost, next to k_forward_affine alone.
+"""Joint motion refinement (srmap_refine_motion): what a pass and a whole call cost, next to the affine forward kernel alone.
    python tools/motion_refinement_timing.py
 At bench.py's cfg2 geometry (2048 x 2048, scale 4, blur 3) and at 1024 x 1024 (scale 2, blur 3), 8 frames, f64 and f32, one
 process.  x is a texture, the frames are the library's own affine model of x (rotations of up to 2 degrees about the centre
@@ -7,7 +7,7 @@ tensors (min of 5, after a warm-up at sustained clocks):
   one pass     (call with max_iterations = 20 and step_tolerance = 0 - call with max_iterations = 0) / 20 when every frame
                runs all 20 trial passes; a pass INCLUDES its table upload, its K x 28 double download and the stream wait;
   whole call   default options from the 0.3 px start, and the passes it took;
-  forward      the cost-only data evaluation of the same problem and matrices (k_forward_affine + the cost reduction), by
+  forward      the cost-only data evaluation of the same problem and matrices (k_forward_direct, affine kind, + the cost reduction), by
                device events: about 2 x this is what a pass should cost on paper (the same loads plus y / w, about twice
                the f64 arithmetic);
   bytes        algorithmic bytes of one pass per frame: x once, y (and w when weighted) once; and the rate over all frames;
@@ -100,7 +100,7 @@ for label, W, H, s in (("cfg2 2048 x 2048, scale 4", 2048, 2048, 4), ("1024 x 10
             label, K, dname, 1e3 * t_whole, q[1:, 2].astype(int).tolist(), q[1:, 3].astype(int).tolist(), err))
         print("  one pass %.1f us over %d frames still active at most (trial passes per frame in the 20-pass call: %s); call with the "
               "initial pass only %.2f ms" % (1e6 * per, K - 1, ran.astype(int).tolist(), 1e3 * t0p))
-        print("  algorithmic bytes per frame and pass %.2f MB; all %d frames: %.3f TB/s | forward alone (k_forward_affine + cost "
+        print("  algorithmic bytes per frame and pass %.2f MB; all %d frames: %.3f TB/s | forward alone (k_forward_direct, affine kind, + cost "
               "reduction, %d frames) %.1f us = %.3f TB/s | pass / forward %.2f x | host share at least %.0f %% if the pass kernel "
               "costs 2 x forward" % (nbytes / 1e6, K - 1, (K - 1) * nbytes / per / 1e12, K, 1e6 * t_fwd, K * nbytes / t_fwd / 1e12,
                                      per / t_fwd, 100 * max(0.0, 1 - 2 * t_fwd * (K - 1) / K / per)), flush=True)

@@ -2,14 +2,14 @@
 next to the forward kernel on the same problem.
    python tools/photometric_timing.py
 At bench.py's cfg2 geometry (2048 x 2048, scale 4) and at 1024 x 1024 (scale 2), 8 frames, f64 and f32, with sub-pixel
-shifts (k_forward_direct's motion) and with affine matrices (k_forward_affine's), blur 3 / sigma 1, one process.  Host wall
+shifts (k_forward_direct's table kind) and with affine matrices (its affine kind), blur 3 / sigma 1, one process.  Host wall
 clock around the blocking call on a device tensor (min of 5, after a warm-up at sustained clocks):
   one fit      the whole call with apply = 0: its allocations, the table upload, ONE launch of k_photometric_sums, the
                reduce, the copy of K x 6 doubles, the stream wait and the host solve;
   normalise    the whole srmap_problem_set_photometric call on a problem that already holds parameters: the drain, the
                copy of K x 2 doubles, ONE launch of k_photometric_normalise and the stream wait;
-  forward      the cost-only data evaluation of the same problem through the direct family (k_forward_direct or
-               k_forward_affine + the cost reduction), by device events: the yardstick -- the sums pass issues that kernel's
+  forward      the cost-only data evaluation of the same problem through the direct family (k_forward_direct, table or
+               affine kind, + the cost reduction), by device events: the yardstick -- the sums pass issues that kernel's
                loads plus the y / w stream.  The forward kernels are the parent commit's, instance for instance
                (profiles/r13_photometric_resources.txt);
   bytes        algorithmic bytes: a fit reads x once and y (and w, when weights are set) once per frame; a normalise pass
@@ -96,7 +96,7 @@ for label, W, H, s in (("cfg2 2048 x 2048, scale 4", 2048, 2048, 4), ("1024 x 10
                 print("%s, %d frames, %s, %s, %s: fit %.3f ms whole call (statuses %s, gain / bias error %.1e / %.1e) | algorithmic "
                       "%.1f MB = %.3f TB/s | forward (%s, cost only) %.1f us | fit / forward %.1f x" % (
                           label, K, motion, dname, "weighted" if weighted else "unweighted", 1e3 * t_fit, sorted(set(q[:, 3].astype(int))),
-                          err[0], err[1], nbytes / 1e6, nbytes / t_fit / 1e12, "k_forward_affine" if motion == "affine" else "k_forward_direct",
+                          err[0], err[1], nbytes / 1e6, nbytes / t_fit / 1e12, "k_forward_direct, affine kind" if motion == "affine" else "k_forward_direct",
                           1e6 * (t_fwd_w if weighted else t_fwd), t_fit / (t_fwd_w if weighted else t_fwd)), flush=True)
             p.set_data_weights(None)
             p.set_photometric(truth)
