@@ -294,8 +294,9 @@ int srmap_set_data_weights(srmap_problem* p, const double* w_host);
 /* The same from a device buffer holding the problem dtype, copied on hip_stream (NULL = the context's stream);
  * complete on return.  No reference counterpart. */
 int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip_stream);
-/* The current weights ([K][C][h][w] host doubles; ones if none are set): after a Huber solve, the outlier map -- the
- * pixels the solve down-weighted.  No reference counterpart. */
+/* The current EFFECTIVE weights ([K][C][h][w] host doubles; ones if none are set; with a data prior, srmap_set_data_prior,
+ * the product with it): after a Huber solve, the outlier map -- the pixels the solve down-weighted.
+ * No reference counterpart. */
 int srmap_get_data_weights(srmap_problem* p, double* w_host);
 /* Loss of the data term (no reference counterpart).  SRMAP_DATA_LOSS_L2: the quadratic above with the caller's
  * weights, which a solve leaves untouched.  SRMAP_DATA_LOSS_HUBER: srmap_solve minimises
@@ -303,8 +304,8 @@ int srmap_get_data_weights(srmap_problem* p, double* w_host);
  * weights are reset to 1 where the regulariser's are, and re-derived from the iterate after every inner run
  * (srmap_update_data_weights_device) together with the regulariser's; the loop runs its rounds even without a
  * regulariser; the reported cost is the weighted quadratic cost of the last inner run.  Huber OWNS the weight buffer:
- * weights the caller set are overwritten by the solve (a mask combined with Huber is not supported), and
- * srmap_get_data_weights afterwards returns the final Huber weights.  huber_delta is in the units of the observations;
+ * weights the caller set are overwritten by the solve (a mask that must hold under Huber is a data prior:
+ * srmap_set_data_prior below), and srmap_get_data_weights afterwards returns the final Huber weights.  huber_delta is in the units of the observations;
  * it must be finite and > 0 for HUBER (ignored for L2).  An unknown loss or a bad delta: SRMAP_EINVAL. */
 typedef enum { SRMAP_DATA_LOSS_L2 = 0, SRMAP_DATA_LOSS_HUBER = 1 } srmap_data_loss;
 int srmap_problem_set_data_loss(srmap_problem* p, int loss /* srmap_data_loss */, double huber_delta);
@@ -312,6 +313,21 @@ int srmap_problem_set_data_loss(srmap_problem* p, int loss /* srmap_data_loss */
  * r = A x - y at x_dev (UNWEIGHTED residuals: one forward pass plus one elementwise pass over [K][C][h][w]).  Needs a
  * HUBER loss.  Enqueued on hip_stream and not waited for, ordered like srmap_update_irls_weights_device. */
 int srmap_update_data_weights_device(srmap_problem* p, const void* x_dev, void* hip_stream);
+/* A persistent prior m on the data weights (no reference counterpart): [K][C][h][w] host doubles, finite
+ * and >= 0 (SRMAP_EINVAL otherwise; the device form takes the problem dtype and trusts the caller); NULL removes it and
+ * restores the weights as they would be without it.  While a prior is set the weights every kernel reads are
+ * w_eff = m .* w, the product formed in the problem's dtype with one rounding, w being what the rules above give: under L2
+ * the caller's weights (kept in a second buffer while a prior is set) or ones; under HUBER the Huber weights -- the reset at
+ * the start of a solve gives w_eff = m, every re-weighting (the solver's and srmap_update_data_weights_device) gives
+ * m .* huber(r) of the UNWEIGHTED residual.  A validity mask therefore holds under a Huber loss.  srmap_get_data_weights
+ * returns the EFFECTIVE weights.  The prior persists across srmap_set_observations and the weight, loss, motion, blur and
+ * photometric calls.  A problem with a prior is weighted in every respect stated at srmap_set_data_weights (weighted
+ * forward instances, SRMAP_EUNSUPPORTED for sharded solves and evaluations); srmap_refine_motion, srmap_fit_blur and
+ * srmap_fit_photometric read the effective weights. */
+int srmap_set_data_prior(srmap_problem* p, const double* m_host);
+int srmap_set_data_prior_device(srmap_problem* p, const void* m_dev, void* hip_stream);
+/* is_set: 1 while a prior is set; m_host (optional, [K][C][h][w] doubles) receives it (ones if none is set). */
+int srmap_get_data_prior(srmap_problem* p, double* m_host, int* is_set);
 
 /* ------------------------------------------------------- operators (host) */
 /* ImageModel::ApplyToImage(ImageData*, index) image_model.cpp:86-91:
@@ -481,7 +497,9 @@ int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, int height,
  * What this estimator is NOT: it is dense, LOCAL and unregularised beyond the window and the box mean, so it cannot resolve
  * motion finer than the window; it has NO occlusion handling; it registers ONE plane per image; and it is NOT fitted through
  * the blur and decimation of the forward model -- on aliased LR frames it plateaus near 0.2 HR px.  A flow leg of
- * srmap_refine_motion is future work.
+ * srmap_refine_motion was prototyped (a windowed per-pixel Gauss-Newton through D B, and a bilinear control lattice of
+ * 8...32 px fitted by Levenberg-Marquardt): both lower the data energy and both RAISE the endpoint error (0.210 ->
+ * 0.24...0.50 HR px), because the fit follows the noise of x; neither beats the unrefined masked solve, so none is built.
  * num_images == 0 returns SRMAP_OK and writes nothing.  SRMAP_EINVAL: width or height < 16; a struct_size that is not this
  * library's; hr_scale < 1, warps < 1, window_radius outside 1...8, smooth_radius outside 0...8, a negative or non-finite
  * damping, a negative valid_margin or max_levels; an output grid beyond 2^30 pixels; an image that is not finite; an initial
@@ -503,6 +521,29 @@ int srmap_register_flow(srmap_ctx* ctx, int num_images, int width, int height, c
                         const srmap_flow_registration_options* options /* NULL = defaults */,
                         double* flow_out /* num_images x 2 x (s h) x (s w) */, double* valid_out /* optional */,
                         double* quality_out /* optional, 3 per image */);
+/* The same registration of a stack that is already on the device: images_dev [num_images][h][w] doubles, read on
+ * hip_stream (NULL = the context's stream); flow_dev_out / valid_dev_out (optional) are device buffers of the sizes above.
+ * The same kernels in the same order: flow, valid and quality are bit-identical to srmap_register_flow on the same
+ * doubles.  Nothing is uploaded and no field is copied back; image 0's planes are written on the device; the scan for
+ * non-finite pixels is a device count that returns with the quality records (one stream wait per call; complete on
+ * return).  A non-finite image answers SRMAP_EINVAL naming the first one; the output buffers are then unspecified. */
+int srmap_register_flow_device(srmap_ctx* ctx, int num_images, int width, int height, const double* images_dev,
+                               void* hip_stream, const srmap_flow_registration_options* options /* NULL = defaults */,
+                               double* flow_dev_out, double* valid_dev_out /* optional */,
+                               double* quality_out /* host, optional, 3 per image */);
+/* Registration from the problem's own observations: the plane [K][h][w] is taken in double from the observation buffer the
+ * evaluations read (the photometrically normalised one while parameters are set) -- channel >= 0 that channel, -1 the mean
+ * over the channels (the sum in ascending channel order, one division by C, no fused operation; f32 observations convert
+ * exactly) -- and registered as above at the problem's scale (options->hr_scale must be 1 or that scale).  The double field
+ * is rounded once to the problem's dtype (as srmap_problem_set_flow rounds host doubles) and installed with the checks and
+ * answers of srmap_problem_set_flow_device; quality [3i+2] is that of the double field.  install_prior != 0: the validity
+ * masks, one plane per frame broadcast over the channels, become the data prior (srmap_set_data_prior), replacing any in
+ * force.  When the field is refused (SRMAP_EUNSUPPORTED) the problem keeps the motion and the prior it had, and
+ * quality_out is still written.  SRMAP_EINVAL: no observations; an LR side < 16; a bad channel; an HR size that is not
+ * LR size * scale; the options' errors of srmap_register_flow.  Sharded problems are out of scope. */
+int srmap_problem_register_flow(srmap_problem* p, int channel /* -1 = channel mean */,
+                                const srmap_flow_registration_options* options /* NULL = defaults */, int install_prior,
+                                double* quality_out /* optional, K x 3 */);
 
 /* Joint motion refinement (no reference counterpart; csrc/motion_refinement.hip; it closes what DESIGN.md
  * 3.7 left out: a registration that honours the forward model and the data weights).  With an HR estimate x, every frame

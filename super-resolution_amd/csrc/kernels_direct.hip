@@ -160,13 +160,17 @@ __device__ __forceinline__ T huber_weight(T r, T delta) {
   return a <= delta ? T(1) : delta / a;
 }
 
-template <typename T, bool VEC>
+// PRIOR: a third stream m, indexed like w (the persistent prior of srmap_set_data_prior): w = m .* huber(r), the product
+// rounded once in T.  The instance without it reads nothing of m.
+template <typename T, bool VEC, bool PRIOR = false>
 __global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, T* __restrict__ w, size_t rowlen,
-                                                      size_t r_stride, size_t w_stride, T delta) {
+                                                      size_t r_stride, size_t w_stride, T delta,
+                                                      const T* __restrict__ m = nullptr) {
   constexpr int V = 16 / (int)sizeof(T);
   typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
   const T* rr = r + (size_t)blockIdx.y * r_stride;
   T* ww = w + (size_t)blockIdx.y * w_stride;
+  const T* mm = PRIOR ? m + (size_t)blockIdx.y * w_stride : nullptr;
   const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
   size_t done = 0;
   if (VEC) {
@@ -176,27 +180,59 @@ __global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, 
       VT o;
 #pragma unroll
       for (int q = 0; q < V; ++q) o[q] = huber_weight<T>(v[q], delta);
+      if constexpr (PRIOR) {
+        const VT pv = reinterpret_cast<const VT*>(mm)[i];
+#pragma unroll
+        for (int q = 0; q < V; ++q) o[q] = pv[q] * o[q];
+      }
       reinterpret_cast<VT*>(ww)[i] = o;
     }
     done = nv * V;
   }
-  for (size_t i = done + tid; i < rowlen; i += nth) ww[i] = huber_weight<T>(rr[i], delta);
+  for (size_t i = done + tid; i < rowlen; i += nth) {
+    const T hw = huber_weight<T>(rr[i], delta);
+    if constexpr (PRIOR) ww[i] = mm[i] * hw;
+    else ww[i] = hw;
+  }
 }
 
 template <typename T>
 int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
-                         double delta, hipStream_t st) {
+                         double delta, hipStream_t st, const T* prior) {
   constexpr size_t V = 16 / sizeof(T);
   if (rows == 0 || rowlen == 0) return SRMAP_OK;
   if (rows > 1 && r_stride == rowlen && w_stride == rowlen) { rowlen *= rows; rows = 1; }  // one contiguous run
   const bool vec = (reinterpret_cast<uintptr_t>(r) % 16 == 0) && (reinterpret_cast<uintptr_t>(w) % 16 == 0) &&
-                   (rows == 1 || (r_stride % V == 0 && w_stride % V == 0));
+                   (reinterpret_cast<uintptr_t>(prior) % 16 == 0) && (rows == 1 || (r_stride % V == 0 && w_stride % V == 0));
   // grid-stride: enough workgroups to fill the device several times over, no more than the run has 16-byte groups
   const size_t groups = (rowlen + V * 256 - 1) / (V * 256);
   const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
   dim3 grid((unsigned)std::max<size_t>(1, std::min(groups, (cap + rows - 1) / rows)), (unsigned)rows);
-  if (vec) hipLaunchKernelGGL((k_huber_weights<T, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta);
-  else hipLaunchKernelGGL((k_huber_weights<T, false>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta);
+  if (prior) {
+    if (vec) hipLaunchKernelGGL((k_huber_weights<T, true, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
+    else hipLaunchKernelGGL((k_huber_weights<T, false, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
+  } else if (vec) {
+    hipLaunchKernelGGL((k_huber_weights<T, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, (const T*)nullptr);
+  } else {
+    hipLaunchKernelGGL((k_huber_weights<T, false>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, (const T*)nullptr);
+  }
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  return SRMAP_OK;
+}
+
+// out = a .* b (b == nullptr: out = a), one rounding in T: the effective data weights m .* w of a problem with a prior,
+// rebuilt whenever either factor changes.  Elementwise, grid-stride.
+template <typename T>
+__global__ __launch_bounds__(256) void k_weight_product(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = b ? a[i] * b[i] : a[i];
+}
+
+template <typename T>
+int launch_weight_product(srmap_problem* p, const T* a, const T* b, T* out, size_t n, hipStream_t st) {
+  if (n == 0) return SRMAP_OK;
+  const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
+  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min((n + 255) / 256, cap));
+  hipLaunchKernelGGL(k_weight_product<T>, dim3(blocks), dim3(256), 0, st, a, b, out, n);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
@@ -1170,7 +1206,8 @@ int launch_reduce_partials(srmap_problem* p, const double* partials, int n, doub
                                         const T*, int, int, T*, int, int, double*, int*,   \
                                         hipStream_t, const T*);                             \
   template int launch_huber_weights<T>(srmap_problem*, const T*, T*, size_t, size_t, size_t, size_t, double,  \
-                                       hipStream_t);                                        \
+                                       hipStream_t, const T*);                              \
+  template int launch_weight_product<T>(srmap_problem*, const T*, const T*, T*, size_t, hipStream_t); \
   template int launch_gather_direct<T>(srmap_problem*, const Geometry&, const T*, T*, int, \
                                        int, double, bool, hipStream_t, int, T*);            \
   template int launch_reg_values<T>(srmap_problem*, const Geometry&, const RegSpec&,       \

@@ -11,6 +11,10 @@
 //   4. k_flow_resample to the HR grid, k_flow_finish (validity mask, residual sums) and k_flow_maxdiff (the neighbour
 //      differences of the returned field), their per-workgroup records added on the host in index order.
 // Nothing comes back to the host between the upload and the final copies: one stream wait per call.
+// Three entry points share the one body: srmap_register_flow (host doubles in, host results out), srmap_register_flow_device
+// (device doubles in, device results out, the non-finite scan a device count in the records that come back anyway) and
+// srmap_problem_register_flow (the plane from the problem's observation buffer, the field and the masks installed as the
+// problem's motion and data prior without leaving the device).
 // Every kernel here keeps fp contraction OFF: each operation is rounded on its own and the sums run in the order the
 // restatement states, so the result does not depend on the tile decomposition and the restatement forms the same numbers.
 #include <algorithm>
@@ -20,6 +24,7 @@
 
 #include "affine_map.hpp"
 #include "motion_fit_dev.hpp"
+#include "solver_passes.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -273,15 +278,270 @@ void launch_lk_pass(const double* i0, const double* gx, const double* gy, const 
 
 int blocks_of(size_t n) { return (int)((n + 255) / 256); }
 
+// ---- the device-resident forms (srmap_register_flow_device, srmap_problem_register_flow) ----
+// record[k * blocks + block] = the number of non-finite pixels of images[k][n] this workgroup visits.  grid = (blocks, K)
+__global__ __launch_bounds__(256) void k_flow_count_nonfinite(const double* __restrict__ images, size_t n, double* __restrict__ record) {
+  __shared__ double red[4];
+  const double* p = images + (size_t)blockIdx.y * n;
+  double c = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    if (!(fabs(p[i]) < INFINITY)) c = c + 1.0;
+  const double t = block_sum_256(c, red);
+  if (threadIdx.x == 0) record[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+}
+
+// plane[k][n] (double) of obs[k][C][n]: channel >= 0 that channel; else the mean, the sum in ascending channel order and
+// one division by C.  T -> double is exact.  grid = (pixels, K)
+template <typename T>
+__global__ __launch_bounds__(256) void k_flow_plane(const T* __restrict__ obs, int C, int channel, size_t n, double* __restrict__ plane) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const T* o = obs + (size_t)blockIdx.y * C * n + i;
+  double v;
+  if (channel >= 0) {
+    v = (double)o[(size_t)channel * n];
+  } else {
+    double t = 0.0;
+    for (int c = 0; c < C; ++c) t = t + (double)o[(size_t)c * n];
+    v = t / (double)C;
+  }
+  plane[(size_t)blockIdx.y * n + i] = v;
+}
+
+// out[K][2][N] (T) = the double field hr[K - 1][2][N] of the frames 1..., rounded once; frame 0 is zero
+template <typename T>
+__global__ __launch_bounds__(256) void k_flow_round(const double* __restrict__ hr, size_t frame_elems, size_t total, T* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+    out[i] = i < frame_elems ? T(0) : (T)hr[i - frame_elems];
+}
+
+// prior[K][C][n] (T) = valid[K - 1][n] of the frames 1... broadcast over the channels; frame 0 is one.  grid = (pixels, C, K)
+template <typename T>
+__global__ __launch_bounds__(256) void k_flow_prior(const double* __restrict__ valid, size_t n, T* __restrict__ prior) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int k = blockIdx.z;
+  prior[((size_t)k * gridDim.y + blockIdx.y) * n + i] = k == 0 ? T(1) : (T)valid[(size_t)(k - 1) * n + i];
+}
+
 // the device buffers of one call
 struct FlowBuffers {
   double *pyr = nullptr, *grad = nullptr, *u = nullptr, *v = nullptr, *hr = nullptr, *valid = nullptr, *rec = nullptr, *tab = nullptr;
+  void *field = nullptr, *prior = nullptr;  // srmap_problem_register_flow: the field and the prior in the problem's dtype
   ~FlowBuffers() {
-    for (double* p : {pyr, grad, u, v, hr, valid, rec, tab})
+    for (void* p : {(void*)pyr, (void*)grad, (void*)u, (void*)v, (void*)hr, (void*)valid, (void*)rec, (void*)tab, field, prior})
       if (p) (void)hipFree(p);
   }
   static bool get(double** p, size_t elems) { return hipMalloc((void**)p, std::max<size_t>(elems, 1) * sizeof(double)) == hipSuccess; }
 };
+
+// Where the stack of one call comes from and where its results go.  Exactly one source: images_host (pageable doubles,
+// scanned on the host), images_dev (device doubles) or problem (its observation buffer; k_flow_plane).  Host results
+// (flow_host, valid_host) are copied back; device results are written where they are wanted: flow_dev / valid_dev when
+// given, else the call's own buffers b.hr / b.valid ([frames - 1] planes, image 0 left to the caller).
+struct FlowIo {
+  const double* images_host = nullptr;
+  const double* images_dev = nullptr;
+  srmap_problem* problem = nullptr;
+  int channel = -1;
+  double *flow_host = nullptr, *valid_host = nullptr;
+  double *flow_dev = nullptr, *valid_dev = nullptr;
+  bool on_device() const { return images_host == nullptr; }
+};
+
+int check_options(srmap_ctx* ctx, const srmap_flow_registration_options* options, srmap_flow_registration_options* opt) {
+  srmap_flow_registration_options_default(opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_flow_registration_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_flow_registration_options.struct_size is not this library's");
+    *opt = *options;
+  }
+  if (opt->hr_scale < 1 || opt->warps < 1 || opt->window_radius < 1 || opt->window_radius > kMaxWindowRadius ||
+      !(opt->damping >= 0.0) || !std::isfinite(opt->damping) || opt->smooth_radius < 0 || opt->smooth_radius > kMaxSmoothRadius ||
+      opt->valid_margin < 0 || opt->max_levels < 0)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: bad options");
+  return SRMAP_OK;
+}
+
+// The registration of K >= 1 images of width x height by the checked options `opt`, on st: the one body of the host form
+// and the device forms.  One stream wait; everything is complete on return.
+int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap_flow_registration_options& opt, const FlowIo& io,
+                       FlowBuffers& b, hipStream_t st, double* quality_out) {
+  if (width < kMinSize || height < kMinSize)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration needs images of at least 16 x 16");
+  const int nf = K - 1, s = opt.hr_scale;
+  const size_t n = (size_t)width * height;
+  if ((size_t)s * width > (size_t)1 << 20 || (size_t)s * height > (size_t)1 << 20 || n * s * s > (size_t)1 << 30)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: the output grid is too large");
+  if (io.images_host)
+    for (size_t i = 0; i < (size_t)K * n; ++i)
+      if (!std::isfinite(io.images_host[i]))
+        return set_error(ctx, SRMAP_EINVAL, "flow registration: image %d is not finite", (int)(i / n));
+
+  std::vector<int> lw{width}, lh{height};
+  while (std::min(lw.back(), lh.back()) >= 2 * kMinSize && (int)lw.size() < kMaxLevels &&
+         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
+    lw.push_back(lw.back() / 2);
+    lh.push_back(lh.back() / 2);
+  }
+  const int L = (int)lw.size();
+
+  std::vector<double> h_tab;
+  if (opt.initial_affine_2x3 && nf > 0) {
+    h_tab.resize((size_t)nf * 6);
+    for (int f = 0; f < nf; ++f) {
+      AffineMap F;
+      std::copy(opt.initial_affine_2x3 + 6 * (f + 1), opt.initial_affine_2x3 + 6 * (f + 2), F.m);
+      if (!all_finite(F) || deviation(F) > kAffineMaxDeviation)
+        return set_error(ctx, SRMAP_EINVAL, "flow registration: initial matrix %d is not finite or outside the model's domain", f + 1);
+      for (int l = 1; l < L; ++l) F = to_coarser(F);
+      const AffineMap G = inverse(F);
+      std::copy(G.m, G.m + 6, h_tab.begin() + 6 * f);
+    }
+  }
+
+  const size_t N = n * s * s;
+  if (io.flow_host) std::memset(io.flow_host, 0, 2 * N * sizeof(double));
+  if (io.valid_host) std::fill(io.valid_host, io.valid_host + n, 1.0);
+  if (quality_out) { quality_out[0] = 0.0; quality_out[1] = 1.0; quality_out[2] = 0.0; }
+  if (K == 1 && !io.on_device()) return SRMAP_OK;
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  // image 0's planes of the device results
+  if (io.flow_dev) SRMAP_HIP(ctx, hipMemsetAsync(io.flow_dev, 0, 2 * N * sizeof(double), st));
+  if (io.valid_dev) launch_fill<double>(io.valid_dev, 1.0, n, st);
+
+  std::vector<size_t> off(L + 1, 0), goff(L + 1, 0);
+  for (int l = 0; l < L; ++l) {
+    off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
+    goff[l + 1] = goff[l] + (size_t)2 * lw[l] * lh[l];
+  }
+  const int fin_blocks = std::min(kMaxRecordBlocks, blocks_of(n)), max_blocks = std::min(kMaxRecordBlocks, blocks_of(N));
+  const int cnt_blocks = io.on_device() ? fin_blocks : 0;  // the device count of the non-finite pixels, per image
+  const size_t rec_quality = (size_t)nf * 2 * (fin_blocks + max_blocks), rec_elems = rec_quality + (size_t)K * cnt_blocks;
+  const bool own_hr = !io.flow_dev, own_valid = !io.valid_dev;
+
+  if (!FlowBuffers::get(&b.pyr, off[L]) || !FlowBuffers::get(&b.grad, goff[L]) || !FlowBuffers::get(&b.u, (size_t)nf * 2 * n) ||
+      !FlowBuffers::get(&b.v, (size_t)nf * 2 * n) || (own_hr && !FlowBuffers::get(&b.hr, (size_t)nf * 2 * N)) ||
+      (own_valid && !FlowBuffers::get(&b.valid, (size_t)nf * n)) || !FlowBuffers::get(&b.rec, rec_elems) ||
+      !FlowBuffers::get(&b.tab, h_tab.size())) {
+    (void)hipGetLastError();
+    return set_error(ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
+  }
+  double* hr = own_hr ? b.hr : io.flow_dev + 2 * N;
+  double* valid = own_valid ? b.valid : io.valid_dev + n;
+
+  // ---- pyramids of the whole stack and the gradient planes of frame 0, once ----
+  if (io.images_host) {
+    SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, io.images_host, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, st));
+  } else if (io.images_dev) {
+    SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, io.images_dev, (size_t)K * n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  } else {
+    const srmap_problem* p = io.problem;
+    if (p->dtype == SRMAP_F32)
+      hipLaunchKernelGGL(k_flow_plane<float>, dim3(blocks_of(n), K), dim3(256), 0, st, (const float*)p->d_obs, p->geo.C, io.channel, n, b.pyr);
+    else
+      hipLaunchKernelGGL(k_flow_plane<double>, dim3(blocks_of(n), K), dim3(256), 0, st, (const double*)p->d_obs, p->geo.C, io.channel, n, b.pyr);
+  }
+  if (cnt_blocks > 0)
+    hipLaunchKernelGGL(k_flow_count_nonfinite, dim3(cnt_blocks, K), dim3(256), 0, st, (const double*)b.pyr, n, b.rec + rec_quality);
+  if (nf > 0) {
+    for (int l = 1; l < L; ++l) launch_down2_stack(b.pyr + off[l - 1], b.pyr + off[l], lw[l - 1], lh[l - 1], K, st);
+    for (int l = 0; l < L; ++l) {
+      const size_t nl = (size_t)lw[l] * lh[l];
+      hipLaunchKernelGGL(k_flow_gradients, dim3(blocks_of(nl)), dim3(256), 0, st, b.pyr + off[l], lw[l], lh[l], b.grad + goff[l],
+                         b.grad + goff[l] + nl);
+    }
+
+    // ---- start at the coarsest level ----
+    double *u = b.u, *v = b.v;
+    {
+      const int cw = lw[L - 1], ch = lh[L - 1];
+      if (h_tab.empty()) {
+        SRMAP_HIP(ctx, hipMemsetAsync(u, 0, (size_t)nf * 2 * cw * ch * sizeof(double), st));
+      } else {
+        SRMAP_HIP(ctx, hipMemcpyAsync(b.tab, h_tab.data(), h_tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_flow_affine_start, dim3(blocks_of((size_t)cw * ch), nf), dim3(256), 0, st, b.tab, cw, ch, u);
+      }
+    }
+
+    // ---- the warp passes, coarse to fine ----
+    for (int l = L - 1; l >= 0; --l) {
+      const int w = lw[l], h = lh[l];
+      const size_t nl = (size_t)w * h;
+      for (int it = 0; it < opt.warps; ++it) {
+        launch_lk_pass(b.pyr + off[l], b.grad + goff[l], b.grad + goff[l] + nl, b.pyr + off[l], u, v, w, h, nf, opt.window_radius,
+                       opt.damping, st);
+        hipLaunchKernelGGL(k_flow_smooth, dim3(blocks_of(nl), 2 * nf), dim3(256), 0, st, v, u, w, h, opt.smooth_radius);
+      }
+      if (l > 0) {
+        const int fw = lw[l - 1], fh = lh[l - 1];
+        hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of((size_t)fw * fh), 2 * nf), dim3(256), 0, st, u, w, h, v, fw, fh, 0.5, 2.0, 2.0);
+        std::swap(u, v);
+      }
+    }
+
+    // ---- the HR field, the mask and the quality records ----
+    double* rec_fin = b.rec;
+    double* rec_max = b.rec + (size_t)nf * 2 * fin_blocks;
+    hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, hr, s * width, s * height, 0.0,
+                       (double)s, (double)s);
+    hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, b.pyr, b.pyr, u, width, height, opt.valid_margin, valid,
+                       rec_fin);
+    hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, hr, s * width, s * height, rec_max);
+  }
+  SRMAP_HIP(ctx, hipGetLastError());
+  // ---- the one wait ----
+  std::vector<double> h_rec(rec_elems);
+  if (io.flow_host) SRMAP_HIP(ctx, hipMemcpyAsync(io.flow_host + 2 * N, hr, (size_t)nf * 2 * N * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (io.valid_host) SRMAP_HIP(ctx, hipMemcpyAsync(io.valid_host + n, valid, (size_t)nf * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (rec_elems > 0) SRMAP_HIP(ctx, hipMemcpyAsync(h_rec.data(), b.rec, rec_elems * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipStreamSynchronize(st));
+
+  for (int k = 0; k < K && cnt_blocks > 0; ++k) {
+    double bad = 0.0;
+    for (int j = 0; j < cnt_blocks; ++j) bad += h_rec[rec_quality + (size_t)k * cnt_blocks + j];
+    if (bad != 0.0) return set_error(ctx, SRMAP_EINVAL, "flow registration: image %d is not finite", k);
+  }
+  if (quality_out) {
+    for (int f = 0; f < nf; ++f) {
+      double see = 0.0, cnt = 0.0, mx = 0.0, my = 0.0;
+      for (int k = 0; k < fin_blocks; ++k) {
+        see += h_rec[((size_t)f * fin_blocks + k) * 2];
+        cnt += h_rec[((size_t)f * fin_blocks + k) * 2 + 1];
+      }
+      const double* rm = h_rec.data() + (size_t)nf * 2 * fin_blocks;
+      for (int k = 0; k < max_blocks; ++k) {
+        mx = std::max(mx, rm[((size_t)f * max_blocks + k) * 2]);
+        my = std::max(my, rm[((size_t)f * max_blocks + k) * 2 + 1]);
+      }
+      double* q = quality_out + 3 * (f + 1);
+      q[0] = cnt > 0 ? std::sqrt(see / cnt) : 0.0;
+      q[1] = cnt / (double)n;
+      q[2] = mx + my;
+    }
+  }
+  return SRMAP_OK;
+}
+
+// the field and (want_prior) the prior of a problem in its dtype from the body's buffers, enqueued on st
+template <typename T>
+int problem_stage(srmap_problem* p, FlowBuffers& b, bool want_prior, hipStream_t st) {
+  const Geometry& g = p->geo;
+  const size_t n = (size_t)g.w * g.h, N = (size_t)g.W * g.H, total = (size_t)g.K * 2 * N;
+  if (hipMalloc(&b.field, std::max<size_t>(total, 1) * sizeof(T)) != hipSuccess ||
+      (want_prior && hipMalloc(&b.prior, std::max<size_t>(p->lr_count(), 1) * sizeof(T)) != hipSuccess)) {
+    (void)hipGetLastError();
+    return set_error(p->ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
+  }
+  const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)std::max(1, p->ctx->num_cus) * 16);
+  hipLaunchKernelGGL(k_flow_round<T>, dim3(std::max(1u, blocks)), dim3(256), 0, st, (const double*)b.hr, 2 * N, total, (T*)b.field);
+  if (want_prior)
+    hipLaunchKernelGGL(k_flow_prior<T>, dim3(blocks_of(n), g.C, g.K), dim3(256), 0, st, (const double*)b.valid, n, (T*)b.prior);
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  return SRMAP_OK;
+}
 
 }  // namespace
 
@@ -307,142 +567,58 @@ extern "C" int srmap_register_flow(srmap_ctx* ctx, int num_images, int width, in
                                    double* quality_out) {
   if (!ctx || !flow_out || num_images < 0) return SRMAP_EINVAL;
   srmap_flow_registration_options opt;
-  srmap_flow_registration_options_default(&opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_flow_registration_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_flow_registration_options.struct_size is not this library's");
-    opt = *options;
-  }
-  if (opt.hr_scale < 1 || opt.warps < 1 || opt.window_radius < 1 || opt.window_radius > kMaxWindowRadius ||
-      !(opt.damping >= 0.0) || !std::isfinite(opt.damping) || opt.smooth_radius < 0 || opt.smooth_radius > kMaxSmoothRadius ||
-      opt.valid_margin < 0 || opt.max_levels < 0)
-    return set_error(ctx, SRMAP_EINVAL, "flow registration: bad options");
+  if (int rc = check_options(ctx, options, &opt)) return rc;
   if (num_images == 0) return SRMAP_OK;
-  if (!images_host || width < kMinSize || height < kMinSize)
-    return set_error(ctx, SRMAP_EINVAL, "flow registration needs images of at least 16 x 16");
-  const int K = num_images, nf = K - 1, s = opt.hr_scale;
-  const size_t n = (size_t)width * height;
-  if ((size_t)s * width > (size_t)1 << 20 || (size_t)s * height > (size_t)1 << 20 || n * s * s > (size_t)1 << 30)
-    return set_error(ctx, SRMAP_EINVAL, "flow registration: the output grid is too large");
-  for (size_t i = 0; i < (size_t)K * n; ++i)
-    if (!std::isfinite(images_host[i])) return set_error(ctx, SRMAP_EINVAL, "flow registration: image %d is not finite", (int)(i / n));
+  if (!images_host) return set_error(ctx, SRMAP_EINVAL, "flow registration needs images of at least 16 x 16");
+  FlowIo io;
+  io.images_host = images_host;
+  io.flow_host = flow_out;
+  io.valid_host = valid_out;
+  FlowBuffers b;
+  return register_flow_body(ctx, num_images, width, height, opt, io, b, ctx->stream, quality_out);
+}
 
-  std::vector<int> lw{width}, lh{height};
-  while (std::min(lw.back(), lh.back()) >= 2 * kMinSize && (int)lw.size() < kMaxLevels &&
-         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
-    lw.push_back(lw.back() / 2);
-    lh.push_back(lh.back() / 2);
-  }
-  const int L = (int)lw.size();
+extern "C" int srmap_register_flow_device(srmap_ctx* ctx, int num_images, int width, int height, const double* images_dev,
+                                          void* hip_stream, const srmap_flow_registration_options* options, double* flow_dev_out,
+                                          double* valid_dev_out, double* quality_out) {
+  if (!ctx || !flow_dev_out || num_images < 0) return SRMAP_EINVAL;
+  srmap_flow_registration_options opt;
+  if (int rc = check_options(ctx, options, &opt)) return rc;
+  if (num_images == 0) return SRMAP_OK;
+  if (!images_dev) return set_error(ctx, SRMAP_EINVAL, "flow registration needs images of at least 16 x 16");
+  FlowIo io;
+  io.images_dev = images_dev;
+  io.flow_dev = flow_dev_out;
+  io.valid_dev = valid_dev_out;
+  FlowBuffers b;
+  return register_flow_body(ctx, num_images, width, height, opt, io, b, hip_stream ? (hipStream_t)hip_stream : ctx->stream, quality_out);
+}
 
-  std::vector<double> h_tab;
-  if (opt.initial_affine_2x3 && nf > 0) {
-    h_tab.resize((size_t)nf * 6);
-    for (int f = 0; f < nf; ++f) {
-      AffineMap F;
-      std::copy(opt.initial_affine_2x3 + 6 * (f + 1), opt.initial_affine_2x3 + 6 * (f + 2), F.m);
-      if (!all_finite(F) || deviation(F) > kAffineMaxDeviation)
-        return set_error(ctx, SRMAP_EINVAL, "flow registration: initial matrix %d is not finite or outside the model's domain", f + 1);
-      for (int l = 1; l < L; ++l) F = to_coarser(F);
-      const AffineMap G = inverse(F);
-      std::copy(G.m, G.m + 6, h_tab.begin() + 6 * f);
-    }
-  }
-
-  const size_t N = n * s * s;
-  std::memset(flow_out, 0, 2 * N * sizeof(double));
-  if (valid_out) std::fill(valid_out, valid_out + n, 1.0);
-  if (quality_out) { quality_out[0] = 0.0; quality_out[1] = 1.0; quality_out[2] = 0.0; }
-  if (K == 1) return SRMAP_OK;
-
+extern "C" int srmap_problem_register_flow(srmap_problem* p, int channel, const srmap_flow_registration_options* options,
+                                           int install_prior, double* quality_out) {
+  if (!p) return SRMAP_EINVAL;
+  srmap_ctx* ctx = p->ctx;
+  const Geometry& g = p->geo;
+  srmap_flow_registration_options opt;
+  if (int rc = check_options(ctx, options, &opt)) return rc;
+  if (!p->have_obs || !p->d_obs) return set_error(ctx, SRMAP_EINVAL, "flow registration: no observations set");
+  if (channel < -1 || channel >= g.C) return set_error(ctx, SRMAP_EINVAL, "flow registration: channel %d of %d", channel, g.C);
+  if (g.W != g.w * g.s || g.H != g.h * g.s)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: HR size %dx%d is not LR size * scale (%d)", g.W, g.H, g.s);
+  if (opt.hr_scale != 1 && opt.hr_scale != g.s)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: hr_scale %d is neither 1 nor the problem's scale %d", opt.hr_scale, g.s);
+  opt.hr_scale = g.s;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  std::vector<size_t> off(L + 1, 0), goff(L + 1, 0);
-  for (int l = 0; l < L; ++l) {
-    off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
-    goff[l + 1] = goff[l] + (size_t)2 * lw[l] * lh[l];
-  }
-  const int fin_blocks = std::min(kMaxRecordBlocks, blocks_of(n)), max_blocks = std::min(kMaxRecordBlocks, blocks_of(N));
-  const size_t rec_elems = (size_t)nf * 2 * (fin_blocks + max_blocks);
-
+  if (int rc = problem_state_read(p, st)) return rc;
+  FlowIo io;
+  io.problem = p;
+  io.channel = channel;
   FlowBuffers b;
-  if (!FlowBuffers::get(&b.pyr, off[L]) || !FlowBuffers::get(&b.grad, goff[L]) || !FlowBuffers::get(&b.u, (size_t)nf * 2 * n) ||
-      !FlowBuffers::get(&b.v, (size_t)nf * 2 * n) || !FlowBuffers::get(&b.hr, (size_t)nf * 2 * N) ||
-      !FlowBuffers::get(&b.valid, (size_t)nf * n) || !FlowBuffers::get(&b.rec, rec_elems) ||
-      !FlowBuffers::get(&b.tab, h_tab.size())) {
-    (void)hipGetLastError();
-    return set_error(ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
-  }
-
-  // ---- pyramids of the whole stack and the gradient planes of frame 0, once ----
-  SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, images_host, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, st));
-  for (int l = 1; l < L; ++l) launch_down2_stack(b.pyr + off[l - 1], b.pyr + off[l], lw[l - 1], lh[l - 1], K, st);
-  for (int l = 0; l < L; ++l) {
-    const size_t nl = (size_t)lw[l] * lh[l];
-    hipLaunchKernelGGL(k_flow_gradients, dim3(blocks_of(nl)), dim3(256), 0, st, b.pyr + off[l], lw[l], lh[l], b.grad + goff[l],
-                       b.grad + goff[l] + nl);
-  }
-
-  // ---- start at the coarsest level ----
-  double *u = b.u, *v = b.v;
-  {
-    const int cw = lw[L - 1], ch = lh[L - 1];
-    if (h_tab.empty()) {
-      SRMAP_HIP(ctx, hipMemsetAsync(u, 0, (size_t)nf * 2 * cw * ch * sizeof(double), st));
-    } else {
-      SRMAP_HIP(ctx, hipMemcpyAsync(b.tab, h_tab.data(), h_tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_flow_affine_start, dim3(blocks_of((size_t)cw * ch), nf), dim3(256), 0, st, b.tab, cw, ch, u);
-    }
-  }
-
-  // ---- the warp passes, coarse to fine ----
-  for (int l = L - 1; l >= 0; --l) {
-    const int w = lw[l], h = lh[l];
-    const size_t nl = (size_t)w * h;
-    for (int it = 0; it < opt.warps; ++it) {
-      launch_lk_pass(b.pyr + off[l], b.grad + goff[l], b.grad + goff[l] + nl, b.pyr + off[l], u, v, w, h, nf, opt.window_radius,
-                     opt.damping, st);
-      hipLaunchKernelGGL(k_flow_smooth, dim3(blocks_of(nl), 2 * nf), dim3(256), 0, st, v, u, w, h, opt.smooth_radius);
-    }
-    if (l > 0) {
-      const int fw = lw[l - 1], fh = lh[l - 1];
-      hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of((size_t)fw * fh), 2 * nf), dim3(256), 0, st, u, w, h, v, fw, fh, 0.5, 2.0, 2.0);
-      std::swap(u, v);
-    }
-  }
-
-  // ---- the HR field, the mask and the quality records; the one wait ----
-  double* rec_fin = b.rec;
-  double* rec_max = b.rec + (size_t)nf * 2 * fin_blocks;
-  hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, b.hr, s * width, s * height, 0.0,
-                     (double)s, (double)s);
-  hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, b.pyr, b.pyr, u, width, height, opt.valid_margin, b.valid,
-                     rec_fin);
-  hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, b.hr, s * width, s * height, rec_max);
-  SRMAP_HIP(ctx, hipGetLastError());
-  std::vector<double> h_rec(rec_elems);
-  SRMAP_HIP(ctx, hipMemcpyAsync(flow_out + 2 * N, b.hr, (size_t)nf * 2 * N * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (valid_out) SRMAP_HIP(ctx, hipMemcpyAsync(valid_out + n, b.valid, (size_t)nf * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  SRMAP_HIP(ctx, hipMemcpyAsync(h_rec.data(), b.rec, rec_elems * sizeof(double), hipMemcpyDeviceToHost, st));
-  SRMAP_HIP(ctx, hipStreamSynchronize(st));
-
-  if (quality_out) {
-    for (int f = 0; f < nf; ++f) {
-      double see = 0.0, cnt = 0.0, mx = 0.0, my = 0.0;
-      for (int k = 0; k < fin_blocks; ++k) {
-        see += h_rec[((size_t)f * fin_blocks + k) * 2];
-        cnt += h_rec[((size_t)f * fin_blocks + k) * 2 + 1];
-      }
-      const double* rm = h_rec.data() + (size_t)nf * 2 * fin_blocks;
-      for (int k = 0; k < max_blocks; ++k) {
-        mx = std::max(mx, rm[((size_t)f * max_blocks + k) * 2]);
-        my = std::max(my, rm[((size_t)f * max_blocks + k) * 2 + 1]);
-      }
-      double* q = quality_out + 3 * (f + 1);
-      q[0] = cnt > 0 ? std::sqrt(see / cnt) : 0.0;
-      q[1] = cnt / (double)n;
-      q[2] = mx + my;
-    }
-  }
-  return SRMAP_OK;
+  if (int rc = register_flow_body(ctx, g.K, g.w, g.h, opt, io, b, st, quality_out)) return rc;
+  const bool prior = install_prior != 0;
+  if (int rc = p->dtype == SRMAP_F32 ? problem_stage<float>(p, b, prior, st) : problem_stage<double>(p, b, prior, st)) return rc;
+  // a refused field leaves the motion -- and the prior -- the problem had
+  if (int rc = srmap_problem_set_flow_device(p, b.field, st)) return rc;
+  return prior ? srmap_set_data_prior_device(p, b.prior, st) : SRMAP_OK;
 }

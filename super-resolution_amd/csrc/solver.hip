@@ -774,9 +774,14 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     for (int r = 0; r < p->nreg; ++r)
       launch_fill<T>((T*)p->reg[r].weights + (size_t)c0 * N, T(1), npts, st);
     if (huber) {  // the data weights of this round's channels likewise ([K][C][h][w]: one run per frame)
-      const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
-      for (int k = 0; k < geo.K; ++k)
-        launch_fill<T>((T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run, st);
+      if (p->d_prior) {  // a prior on the weights is what they are reset to
+        rc = reset_data_weights(p, c0, per_split, st);
+        if (rc) break;
+      } else {
+        const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
+        for (int k = 0; k < geo.K; ++k)
+          launch_fill<T>((T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run, st);
+      }
     }
     double previous_cost = INFINITY;
     double cost_difference = o.irls_cost_difference_threshold + 1.0;

@@ -373,7 +373,8 @@ static int update_data_weights_typed(srmap_problem* p, int c0, int C, const T* x
   if (rc) return rc;
   const size_t nl = (size_t)geo.w * geo.h;
   return launch_huber_weights<T>(p, (const T*)p->d_resid, (T*)p->d_dw + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
-                                 (size_t)geo.C * nl, (size_t)p->geo.C * nl, p->huber_delta, st);
+                                 (size_t)geo.C * nl, (size_t)p->geo.C * nl, p->huber_delta, st,
+                                 p->d_prior ? (const T*)p->d_prior + (size_t)c0 * nl : nullptr);
 }
 
 int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st) {
@@ -388,6 +389,21 @@ int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStrea
                              : update_data_weights_typed<double>(p, c0, C, (const double*)x, st);
   if (rc) return rc;
   return state_end_write(p, st);  // asynchronous: evaluations on other streams wait for this event
+}
+
+int reset_data_weights(srmap_problem* p, int c0, int C, hipStream_t st) {
+  const Geometry& g = p->geo;
+  if (C <= 0) { c0 = 0; C = g.C; }
+  if (!p->d_dw) return set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
+  const size_t nl = (size_t)g.w * g.h, run = (size_t)C * nl, e = p->elem();
+  for (int k = 0; k < g.K; ++k) {  // [K][C][h][w]: one run per frame
+    const size_t off = ((size_t)k * g.C + c0) * nl;
+    if (p->d_prior)
+      SRMAP_HIP(p->ctx, hipMemcpyAsync((char*)p->d_dw + off * e, (const char*)p->d_prior + off * e, run * e, hipMemcpyDeviceToDevice, st));
+    else if (p->dtype == SRMAP_F32) launch_fill<float>((float*)p->d_dw + off, 1.f, run, st);
+    else launch_fill<double>((double*)p->d_dw + off, 1.0, run, st);
+  }
+  return SRMAP_OK;
 }
 
 int recover_reduction_timeout(srmap_problem* p, double* host_word) {
@@ -617,7 +633,7 @@ void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
   void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_affine, p->d_flow, p->d_flow_seed, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
+                  p->d_affine, p->d_flow, p->d_flow_seed, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_prior, p->d_dw_user, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
   for (int* t : p->d_ytabs) (void)hipFree(t);
@@ -878,6 +894,17 @@ int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_de
 }
 
 // ---- robust data term: per-observation weights, Huber loss (no reference counterpart) ----
+// d_dw <- d_prior .* d_dw_user (ones where the caller gave none) on st, waited for: a problem with a prior only
+static int rebuild_effective_weights(srmap_problem* p, hipStream_t st) {
+  const size_t n = p->lr_count();
+  int rc = p->dtype == SRMAP_F32
+               ? launch_weight_product<float>(p, (const float*)p->d_prior, (const float*)p->d_dw_user, (float*)p->d_dw, n, st)
+               : launch_weight_product<double>(p, (const double*)p->d_prior, (const double*)p->d_dw_user, (double*)p->d_dw, n, st);
+  if (rc) return rc;
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  return SRMAP_OK;
+}
+
 int srmap_set_data_weights(srmap_problem* p, const double* w_host) {
   if (!p) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
@@ -890,6 +917,15 @@ int srmap_set_data_weights(srmap_problem* p, const double* w_host) {
   int rc = state_begin_write(p, st);
   if (rc) return rc;
   const bool was = p->robust();
+  if (p->d_prior) {  // the caller's weights go to the second buffer; d_dw is the product with the prior
+    if (!w_host) {
+      if (p->d_dw_user) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); (void)hipFree(p->d_dw_user); p->d_dw_user = nullptr; }
+    } else {
+      rc = ensure(p, &p->d_dw_user, n * p->elem());
+      if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw_user, n, st);
+    }
+    return rc ? rc : rebuild_effective_weights(p, st);
+  }
   if (!w_host) {
     // all ones: the unweighted kernels again -- except under a Huber loss, which keeps (and owns) the buffer
     if (p->d_dw) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); (void)hipFree(p->d_dw); p->d_dw = nullptr; }
@@ -910,12 +946,101 @@ int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip
   int rc = state_begin_write(p, st);
   if (rc) return rc;
   const bool was = p->robust();
-  rc = ensure(p, &p->d_dw, p->lr_count() * p->elem());
+  void** dst = p->d_prior ? &p->d_dw_user : &p->d_dw;
+  rc = ensure(p, dst, p->lr_count() * p->elem());
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_dw, w_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(*dst, w_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  if (p->d_prior) return rebuild_effective_weights(p, st);
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));  // complete on return, as srmap_set_observations_device
   replan_if(p, was);
   return SRMAP_OK;
+}
+
+// ---- persistent prior on the data weights (no reference counterpart) ----
+// The first prior of a problem: the weights in force become the caller's factor w (d_dw_user), d_dw the product's buffer.
+static int data_prior_begin(srmap_problem* p, hipStream_t st) {
+  const size_t bytes = p->lr_count() * p->elem();
+  if (p->d_prior) return SRMAP_OK;
+  void *m = nullptr, *eff = nullptr;
+  if (hipMalloc(&m, bytes ? bytes : 8) != hipSuccess || hipMalloc(&eff, bytes ? bytes : 8) != hipSuccess) {
+    if (m) (void)hipFree(m);
+    (void)hipGetLastError();
+    return set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed (data prior: 2 x %zu bytes)", bytes);
+  }
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  p->d_prior = m;
+  p->d_dw_user = p->d_dw;  // nullptr: ones
+  p->d_dw = eff;
+  return SRMAP_OK;
+}
+
+// after d_prior was written on st: the product, the plan of a problem that has become robust(); complete on return
+static int data_prior_end(srmap_problem* p, bool was_robust, hipStream_t st) {
+  int rc = rebuild_effective_weights(p, st);
+  replan_if(p, was_robust);
+  return rc;
+}
+
+static int data_prior_remove(srmap_problem* p, hipStream_t st) {
+  if (!p->d_prior) return SRMAP_OK;
+  const bool was = p->robust();
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  (void)hipFree(p->d_prior);
+  (void)hipFree(p->d_dw);
+  p->d_prior = nullptr;
+  p->d_dw = p->d_dw_user;  // the caller's weights as they were given; nullptr: the unweighted kernels again
+  p->d_dw_user = nullptr;
+  int rc = SRMAP_OK;
+  if (p->data_loss == SRMAP_DATA_LOSS_HUBER) rc = ensure_data_weights(p, st);
+  replan_if(p, was);
+  return rc;
+}
+
+int srmap_set_data_prior(srmap_problem* p, const double* m_host) {
+  if (!p) return SRMAP_EINVAL;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  const size_t n = p->lr_count();
+  if (m_host)
+    for (size_t i = 0; i < n; ++i)
+      if (!(m_host[i] >= 0.0) || !std::isfinite(m_host[i]))
+        return set_error(p->ctx, SRMAP_EINVAL, "data prior %zu is %g: the prior must be finite and >= 0", i, m_host[i]);
+  hipStream_t st = p->ctx->stream;
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  if (!m_host) return data_prior_remove(p, st);
+  const bool was = p->robust();
+  rc = data_prior_begin(p, st);
+  if (rc) return rc;
+  rc = convert_upload(p, m_host, p->d_prior, n, st);
+  if (rc) return rc;
+  return data_prior_end(p, was, st);
+}
+
+int srmap_set_data_prior_device(srmap_problem* p, const void* m_dev, void* hip_stream) {
+  if (!p) return SRMAP_EINVAL;
+  if (!m_dev) return srmap_set_data_prior(p, nullptr);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  const bool was = p->robust();
+  rc = data_prior_begin(p, st);
+  if (rc) return rc;
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_prior, m_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  return data_prior_end(p, was, st);
+}
+
+int srmap_get_data_prior(srmap_problem* p, double* m_host, int* is_set) {
+  if (!p) return SRMAP_EINVAL;
+  if (is_set) *is_set = p->d_prior ? 1 : 0;
+  if (!m_host) return SRMAP_OK;
+  const size_t n = p->lr_count();
+  if (!p->d_prior) {
+    for (size_t i = 0; i < n; ++i) m_host[i] = 1.0;
+    return SRMAP_OK;
+  }
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  return convert_download(p, p->d_prior, m_host, n, p->ctx->stream);
 }
 
 int srmap_get_data_weights(srmap_problem* p, double* w_host) {

@@ -172,6 +172,10 @@ struct srmap_problem {
   void* d_dw = nullptr;           // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
   int data_loss = SRMAP_DATA_LOSS_L2;  // srmap_problem_set_data_loss; HUBER keeps d_dw allocated (it owns the buffer)
   double huber_delta = 0.0;
+  // persistent prior m on the data weights (srmap_set_data_prior): while set, d_dw = m .* w (allocated, so the problem is
+  // robust()) and d_dw_user keeps the caller's weights w (nullptr = ones); both nullptr otherwise
+  void* d_prior = nullptr;        // [K][C][h][w] dtype
+  void* d_dw_user = nullptr;      // [K][C][h][w] dtype
   // weights or a Huber loss: every evaluation runs a WEIGHTED forward kernel, and the tile plan takes the forward-residual
   // form for integer shifts too (kernels_ztile.hip ztile_plan)
   bool robust() const { return d_dw != nullptr || data_loss == SRMAP_DATA_LOSS_HUBER; }
@@ -231,9 +235,13 @@ int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const
                           double* partials, int* nblocks, hipStream_t st, const T* dw = nullptr);
 // w = 1 where |r| <= delta, delta / |r| elsewhere (the Huber loss as an IRLS weight), arithmetic in T.  r: `rows` runs of
 // `rowlen` elements, r_stride apart; w likewise, w_stride apart, starting at w (a channel view of [K][C][h][w]).
+// prior != nullptr (indexed like w): the instance with the prior as a third stream, w = prior .* huber(r)
 template <typename T>
 int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
-                         double delta, hipStream_t st);
+                         double delta, hipStream_t st, const T* prior = nullptr);
+// out = a .* b (b == nullptr: a) over n elements, one rounding: the effective data weights of a problem with a prior
+template <typename T>
+int launch_weight_product(srmap_problem* p, const T* a, const T* b, T* out, size_t n, hipStream_t st);
 // g = (accumulate ? g : 0) + 2 s^2 sum_k A_k^T r_k   (r: [K][C][h][w])
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
@@ -351,6 +359,8 @@ int problem_state_read(srmap_problem* p, hipStream_t st);
 // Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): data weights <- huber(A x - y), enqueued on st
 // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
 int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
+// the start of a Huber solve on the channels [c0, c0 + C): data weights <- 1, or the prior where one is set; enqueued on st
+int reset_data_weights(srmap_problem* p, int c0, int C, hipStream_t st);
 
 // ---- solver (solver.hip) ----
 int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,

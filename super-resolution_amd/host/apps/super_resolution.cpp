@@ -62,6 +62,9 @@ int main(int argc, char** argv) {
       "                       --affine_motion_path, --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
       "                       [--save_flow_path=<file>] (the estimated fields, in --flow_motion_path's format; needs\n"
       "                       --registration=flow)\n"
+      "                       [--flow_valid_prior] (install the validity masks of --registration=flow as a persistent prior\n"
+      "                       on the data weights instead of multiplying them in, so that they hold under --data_loss=huber\n"
+      "                       too; needs --registration=flow)\n"
       "                       [--save_motion_path=<file>] (the estimate, 'a b tx c d ty' per line; needs --registration or\n"
       "                       --refine_motion_rounds, and holds the final matrices)\n"
       "                       [--refine_motion_rounds=0] (after the solve, N times: re-fit the frame matrices to the estimate\n"
@@ -125,6 +128,8 @@ int main(int argc, char** argv) {
   const std::string registration_name = flags.Str("registration");
   const std::string save_motion_path = flags.Str("save_motion_path");
   const std::string save_flow_path = flags.Str("save_flow_path");
+  // not a reference flag: the validity masks as the persistent prior of srmap_set_data_prior (they hold under Huber too)
+  const bool flow_valid_prior = flags.Bool("flow_valid_prior", false);
   // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
   const int refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
   const int refine_motion_dof = flags.Int("refine_motion_dof", 6);
@@ -181,6 +186,10 @@ int main(int argc, char** argv) {
   }
   if (!save_flow_path.empty() && !register_flow) {
     std::fprintf(stderr, "ERROR: --save_flow_path needs --registration=flow.\n");
+    return 1;
+  }
+  if (flow_valid_prior && !register_flow) {
+    std::fprintf(stderr, "ERROR: --flow_valid_prior needs --registration=flow.\n");
     return 1;
   }
   if (!registration_name.empty() && !generate_lr_images &&
@@ -368,8 +377,10 @@ int main(int argc, char** argv) {
     solver.AddRegularizer(regularizer, regularization_parameter);
   }
   // --registration=flow: the field is wrong where frame 0 does not hold the content; those pixels get weight 0.  A Huber
-  // solve derives its own weights and resets the buffer (include/srmap.h)
-  if (register_flow && solver_options.data_loss == L2_DATA_LOSS) solver.MultiplyDataWeights(flow_valid);
+  // solve derives its own weights and resets the buffer (include/srmap.h) -- unless the masks are the persistent prior
+  // (--flow_valid_prior, srmap_set_data_prior), which a Huber solve resets to and multiplies its weights by
+  if (register_flow && flow_valid_prior) solver.SetDataPrior(flow_valid);
+  else if (register_flow && solver_options.data_loss == L2_DATA_LOSS) solver.MultiplyDataWeights(flow_valid);
 
   // --fit_blur_from: the calibration fit, before the solve, from a known HR image of what the frames show
   if (!fit_blur_from.empty()) {

@@ -394,6 +394,47 @@ class IRLSMapSolver : public MapSolver {
         for (size_t i = 0; i < plane; ++i) w[(k * channels + c) * plane + i] *= masks[k * plane + i];
     srmap_host::Check(srmap_set_data_weights(problem_.get(), w.data()), "srmap_set_data_weights");
   }
+  // Installs per-observation masks [K][h][w] at LR resolution, broadcast over the channels as MultiplyDataWeights does, as
+  // the PERSISTENT prior on the data weights (srmap_set_data_prior, include/srmap.h): every kernel reads prior .* weights,
+  // and a Huber solve resets to the prior and re-weights to prior .* huber(r) -- the masks hold under both losses.  An
+  // empty vector removes the prior.  Not in the reference.
+  void SetDataPrior(const std::vector<double>& masks) {
+    if (masks.empty()) {
+      srmap_host::Check(srmap_set_data_prior(problem_.get(), nullptr), "srmap_set_data_prior");
+      return;
+    }
+    int lw = 0, lh = 0;
+    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
+    const size_t plane = static_cast<size_t>(lw) * lh, channels = static_cast<size_t>(GetNumChannels());
+    if (masks.size() != static_cast<size_t>(GetNumImages()) * plane)
+      srmap_host::Fail("data prior masks: one [h][w] plane per observation at the low-resolution size is needed");
+    std::vector<double> m(static_cast<size_t>(GetNumImages()) * channels * plane);
+    for (size_t k = 0; k < static_cast<size_t>(GetNumImages()); ++k)
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t i = 0; i < plane; ++i) m[(k * channels + c) * plane + i] = masks[k * plane + i];
+    srmap_host::Check(srmap_set_data_prior(problem_.get(), m.data()), "srmap_set_data_prior");
+  }
+  // The prior in force, [K][C][h][w]; empty when none is set.  Not in the reference.
+  std::vector<double> GetDataPrior() const {
+    int set = 0, lw = 0, lh = 0;
+    srmap_host::Check(srmap_get_data_prior(problem_.get(), nullptr, &set), "srmap_get_data_prior");
+    if (!set) return std::vector<double>();
+    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
+    std::vector<double> m(static_cast<size_t>(GetNumImages()) * GetNumChannels() * lw * lh);
+    srmap_host::Check(srmap_get_data_prior(problem_.get(), m.data(), &set), "srmap_get_data_prior");
+    return m;
+  }
+  // Registers the solver's own observations on the device (srmap_problem_register_flow): the plane of `channel` (-1: the
+  // channel mean), the field installed as the problem's motion and -- with `prior` -- the validity masks as the data
+  // prior.  options (optional): a filled srmap_flow_registration_options.  Returns the quality, 3 per image.  Not in the
+  // reference.
+  std::vector<double> RegisterFlow(const int channel = -1, const srmap_flow_registration_options* options = nullptr,
+                                   const bool prior = true) {
+    std::vector<double> quality(3 * static_cast<size_t>(GetNumImages()), 0.0);
+    srmap_host::Check(srmap_problem_register_flow(problem_.get(), channel, options, prior ? 1 : 0, quality.data()),
+                      "srmap_problem_register_flow");
+    return quality;
+  }
 
  private:
   const IRLSMapSolverOptions solver_options_;

@@ -127,6 +127,9 @@ _SIGNATURES = [
     ("srmap_get_data_weights", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_set_data_loss", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     ("srmap_update_data_weights_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("srmap_set_data_prior", C.c_int, [C.c_void_p, c_double_p]),
+    ("srmap_set_data_prior_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("srmap_get_data_prior", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
     ("srmap_apply", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_apply_transpose", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_reg_values", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
@@ -146,6 +149,8 @@ _SIGNATURES = [
     ("srmap_register_affine", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p]),
     ("srmap_flow_registration_options_default", None, [C.c_void_p]),
     ("srmap_register_flow", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_register_flow_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p]),
+    ("srmap_problem_register_flow", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_double_p]),
     ("srmap_motion_refinement_options_default", None, [C.c_void_p]),
     ("srmap_refine_motion", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_refine_motion_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
@@ -195,6 +200,22 @@ def load():
 def _d(a):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a, a.ctypes.data_as(c_double_p)
+
+
+def _flow_options(n, hr_scale, init, warps, window_radius, damping, smooth_radius, valid_margin, max_levels, struct_size):
+    """srmap_flow_registration_options from keyword values; the second result keeps the matrices alive."""
+    o = FlowRegistrationOptions()
+    load().srmap_flow_registration_options_default(C.byref(o))
+    o.hr_scale, o.warps, o.window_radius, o.damping = hr_scale, warps, window_radius, damping
+    o.smooth_radius, o.valid_margin, o.max_levels = smooth_radius, valid_margin, max_levels
+    if struct_size is not None:
+        o.struct_size = struct_size
+    ini = None
+    if init is not None:
+        ini, pi = _d(init)
+        assert ini.size == n * 6, (ini.shape, n)
+        o.initial_affine_2x3 = pi
+    return o, ini
 
 
 class Context:
@@ -270,26 +291,35 @@ class Context:
         return (out, q) if with_quality else out
 
     def register_flow(self, images, hr_scale=1, init=None, warps=8, window_radius=4, damping=0.05, smooth_radius=2,
-                      valid_margin=3, max_levels=0, struct_size=None):
+                      valid_margin=3, max_levels=0, struct_size=None, flow_out=None, valid_out=None, stream=None):
         """srmap_register_flow: images [n][H][W] -> (flow [n][2][s H][s W], valid [n][H][W], quality [n][3]) with
         s = hr_scale: the fields u_k, I_0(q + u_k(q)) ~= I_k(q), in units of HR pixels (ready for Problem.set_flow), the
-        validity mask at input resolution (ready for Problem.set_data_weights, one plane per channel) and (RMS residual,
-        valid fraction, max dx + dy of the field) per image -- srmap.h.  init: [n][2][3] starting matrices in input pixels
-        (register_affine's) instead of u = 0.  struct_size overrides the options' size field (tests)."""
-        a, pa = _d(images)
-        n, H, W = a.shape
-        o = FlowRegistrationOptions()
-        load().srmap_flow_registration_options_default(C.byref(o))
-        o.hr_scale, o.warps, o.window_radius, o.damping = hr_scale, warps, window_radius, damping
-        o.smooth_radius, o.valid_margin, o.max_levels = smooth_radius, valid_margin, max_levels
-        if struct_size is not None:
-            o.struct_size = struct_size
-        if init is not None:
-            ini, pi = _d(init)
-            assert ini.size == n * 6, (ini.shape, n)
-            o.initial_affine_2x3 = pi
+        validity mask at input resolution (ready for Problem.set_data_prior / set_data_weights, one plane per channel)
+        and (RMS residual, valid fraction, max dx + dy of the field) per image -- srmap.h.  init: [n][2][3] starting
+        matrices in input pixels (register_affine's) instead of u = 0.  struct_size overrides the options' size field
+        (tests).  A device double tensor for `images` (anything with data_ptr(), read on `stream`) runs
+        srmap_register_flow_device: flow_out (required) and valid_out (optional) are device double buffers of those
+        sizes, and the quality alone is returned."""
+        device = hasattr(images, "data_ptr")
+        if device:
+            assert images.is_contiguous() and images.element_size() == 8 and images.dim() == 3
+            n, H, W = (int(v) for v in images.shape)
+        else:
+            assert flow_out is None and valid_out is None, "flow_out / valid_out go with a device tensor for images"
+            a, pa = _d(images)
+            n, H, W = a.shape
+        o, keep = _flow_options(n, hr_scale, init, warps, window_radius, damping, smooth_radius, valid_margin, max_levels, struct_size)
         s = max(1, int(hr_scale))
-        flow, valid, q = np.zeros((n, 2, s * H, s * W)), np.zeros((n, H, W)), np.zeros((n, 3))
+        q = np.zeros((n, 3))
+        if device:
+            assert flow_out is not None and flow_out.is_contiguous() and flow_out.element_size() == 8 and flow_out.numel() == n * 2 * s * s * H * W
+            assert valid_out is None or (valid_out.is_contiguous() and valid_out.element_size() == 8 and valid_out.numel() == n * H * W)
+            self.check(load().srmap_register_flow_device(self._h, n, W, H, C.c_void_p(images.data_ptr()), C.c_void_p(stream or 0),
+                                                         C.byref(o), C.c_void_p(flow_out.data_ptr()),
+                                                         C.c_void_p(valid_out.data_ptr()) if valid_out is not None else None,
+                                                         q.ctypes.data_as(c_double_p)))
+            return q
+        flow, valid = np.zeros((n, 2, s * H, s * W)), np.zeros((n, H, W))
         self.check(load().srmap_register_flow(self._h, n, W, H, pa, C.byref(o), flow.ctypes.data_as(c_double_p),
                                               valid.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p)))
         return flow, valid, q
@@ -517,6 +547,45 @@ class Problem:
         out = np.empty((self.K, self.C, self.h, self.w))
         self.ctx.check(load().srmap_get_data_weights(self._h, out.ctypes.data_as(c_double_p)))
         return out
+
+    def set_data_prior(self, m, stream=None):
+        """Persistent prior on the data weights, [K][C][h][w]: every kernel reads m .* w, also under a Huber loss (whose
+        re-weighting gives m .* huber(r)).  A host array, or a device tensor of the problem's dtype (anything with
+        data_ptr(), read on `stream`); None removes it."""
+        n = self.K * self.C * self.h * self.w
+        if m is None:
+            self.ctx.check(load().srmap_set_data_prior(self._h, None))
+        elif hasattr(m, "data_ptr"):
+            assert m.numel() == n and m.is_contiguous() and m.element_size() == (4 if self.dtype == F32 else 8)
+            self.ctx.check(load().srmap_set_data_prior_device(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(stream or 0)))
+        else:
+            a, pa = _d(m)
+            assert a.size == n, (a.shape, self.K, self.C, self.h, self.w)
+            self.ctx.check(load().srmap_set_data_prior(self._h, pa))
+
+    def data_prior(self):
+        """The prior in force, [K][C][h][w] doubles, or None when none is set."""
+        v = C.c_int(0)
+        self.ctx.check(load().srmap_get_data_prior(self._h, None, C.byref(v)))
+        if not v.value:
+            return None
+        out = np.empty((self.K, self.C, self.h, self.w))
+        self.ctx.check(load().srmap_get_data_prior(self._h, out.ctypes.data_as(c_double_p), C.byref(v)))
+        return out
+
+    def register_flow(self, channel=-1, init=None, prior=True, hr_scale=1, warps=8, window_radius=4, damping=0.05,
+                      smooth_radius=2, valid_margin=3, max_levels=0, struct_size=None):
+        """srmap_problem_register_flow: register the problem's own observations (channel, or -1 = the channel mean) on
+        the device and install the field as set_flow would; prior: the validity masks become the data prior.  Returns
+        the quality [K][3], also when the field is refused (SrmapError with .quality set)."""
+        o, keep = _flow_options(self.K, hr_scale, init, warps, window_radius, damping, smooth_radius, valid_margin, max_levels, struct_size)
+        q = np.zeros((self.K, 3))
+        try:
+            self.ctx.check(load().srmap_problem_register_flow(self._h, channel, C.byref(o), 1 if prior else 0, q.ctypes.data_as(c_double_p)))
+        except SrmapError as e:
+            e.quality = q
+            raise
+        return q
 
     def set_data_loss(self, loss, huber_delta=0.0):
         """DATA_LOSS_L2 (default) or DATA_LOSS_HUBER with its delta (> 0, in the observations' units)."""
