@@ -109,6 +109,10 @@ void srmap_ctx_destroy(srmap_ctx* ctx);
 const char* srmap_last_error(const srmap_ctx* ctx);
 /* Library/version string, e.g. "srmap 0.1 (gfx950)". */
 const char* srmap_version(void);
+/* Diagnostic: the device and pinned-host blocks the library holds in this process (memory handed out by
+ * srmap_device_alloc is the caller's and not counted).  0 once every problem, context and communicator is destroyed;
+ * unchanged by any call that keeps no new state -- a leak test that free-memory queries on a shared GPU cannot give. */
+long long srmap_live_allocations(void);
 
 /* ---------------------------------------------------------------- problem */
 /* ImageModelParameters + MapSolver geometry: image_model.h:26-44,

@@ -126,11 +126,11 @@ bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_
   return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->d_dw)
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
-                         (const T*)p->d_dw, g, ma, p->d_col_map, p->d_row_map, tpc, d_part);
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
+                         p->d_dw.as<const T>(), g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
     else
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs,
-                         (const T*)nullptr, g, ma, p->d_col_map, p->d_row_map, tpc, d_part);
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
+                         (const T*)nullptr, g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
   });
 }
 
@@ -141,15 +141,6 @@ bool launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, d
   if (ksize == 5) return launch_sums_m<T, 5>(p, x, chunks, tpc, d_part, st);
   return launch_sums_m<T, 7>(p, x, chunks, tpc, d_part, st);
 }
-
-struct FitBuffers {
-  double *d_part = nullptr, *d_sums = nullptr, *h_sums = nullptr;
-  ~FitBuffers() {
-    if (d_part) (void)hipFree(d_part);
-    if (d_sums) (void)hipFree(d_sums);
-    if (h_sums) (void)hipHostFree(h_sums);
-  }
-};
 
 // E(h) = [h; -1]^T M [h; -1], M the (n + 1) x (n + 1) Gram (full, row-major)
 double energy(const std::vector<double>& M, int n, const double* h) {
@@ -212,26 +203,25 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
   const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
   const int chunks = (int)((tiles + tpc - 1) / tpc);
   const int records = g.K * chunks;
-  FitBuffers buf;
-  if (hipMalloc((void**)&buf.d_part, (size_t)records * P * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&buf.d_sums, (size_t)P * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&buf.h_sums, (size_t)P * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
+  DevBuf part, sums;
+  PinnedBuf sums_host;
+  if (part.alloc((size_t)records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)P * sizeof(double)) != hipSuccess ||
+      sums_host.alloc((size_t)P * sizeof(double)) != hipSuccess)
     return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
-  }
-  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, buf.d_part, st)
-                              : launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, buf.d_part, st)))
+  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
+  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, d_part, st)
+                              : launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, d_part, st)))
     return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
   SRMAP_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, buf.d_part, records, P, buf.d_sums);
+  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, d_part, records, P, d_sums);
   SRMAP_HIP(ctx, hipGetLastError());
-  SRMAP_HIP(ctx, hipMemcpyAsync(buf.h_sums, buf.d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
   SRMAP_HIP(ctx, hipStreamSynchronize(st));
 
   // ---- the host solve ----
   std::vector<double> M((size_t)n1 * n1);
   for (int i = 0, q = 0; i < n1; ++i)
-    for (int j = i; j < n1; ++j, ++q) M[(size_t)i * n1 + j] = M[(size_t)j * n1 + i] = buf.h_sums[q];
+    for (int j = i; j < n1; ++j, ++q) M[(size_t)i * n1 + j] = M[(size_t)j * n1 + i] = h_sums[q];
   // the kernel in force, zero-padded or centre-cropped to ksize
   std::vector<double> hcur((size_t)n, 0.0);
   const int off = (ksize - g.b) / 2;  // both odd: exact, negative when cropping
@@ -282,7 +272,7 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
   if (quality_out) {
     quality_out[0] = e0; quality_out[1] = e1; quality_out[2] = pmin; quality_out[3] = pmax; quality_out[4] = status;
   }
-  if (normal_equations_out) std::copy(buf.h_sums, buf.h_sums + P, normal_equations_out);
+  if (normal_equations_out) std::copy(h_sums, h_sums + P, normal_equations_out);
   return SRMAP_OK;
 }
 
@@ -294,5 +284,5 @@ extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srma
     return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
   if (int rc = stage_host_x(p, x_host)) return rc;
-  return srmap_fit_blur_device(p, p->d_x, p->ctx->stream, options, taps_out, quality_out, normal_equations_out);
+  return srmap_fit_blur_device(p, p->d_x.as(), p->ctx->stream, options, taps_out, quality_out, normal_equations_out);
 }

@@ -101,17 +101,16 @@ extern "C" int srmap_channel_map_device(srmap_ctx* ctx, int rows_out, int rows_i
       for (int c = 0; c < rows_in; ++c) b -= M[(size_t)r * rows_in + c] * offset_in[c];
     bias[r] = b;
   }
-  double *d_M = nullptr, *d_bias = nullptr;
-  SRMAP_HIP(ctx, hipMalloc((void**)&d_M, (size_t)rows_out * rows_in * sizeof(double)));
-  if (hipMalloc((void**)&d_bias, (size_t)rows_out * sizeof(double)) != hipSuccess) { (void)hipFree(d_M); return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed"); }
+  DevBuf map, bias_dev;
+  SRMAP_HIP(ctx, map.alloc((size_t)rows_out * rows_in * sizeof(double)));
+  if (bias_dev.alloc((size_t)rows_out * sizeof(double)) != hipSuccess) return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed");
+  double *const d_M = map.as<double>(), *const d_bias = bias_dev.as<double>();
   int rc = SRMAP_OK;
   if (hipMemcpyAsync(d_M, M, (size_t)rows_out * rows_in * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(d_bias, bias.data(), (size_t)rows_out * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
     rc = set_error(ctx, SRMAP_EHIP, "upload of the map failed");
   if (rc == SRMAP_OK) rc = channel_map_core(ctx, rows_out, rows_in, n, d_M, d_bias, in_dev, out_dev, st);
-  (void)hipStreamSynchronize(st);  // the map / bias buffers and the host bias vector are released below
-  (void)hipFree(d_M);
-  (void)hipFree(d_bias);
+  (void)hipStreamSynchronize(st);  // the map / bias buffers and the host bias vector go out of scope here
   return rc;
 }
 
@@ -130,21 +129,14 @@ extern "C" int srmap_channel_pca_device(srmap_ctx* ctx, int rows, size_t n, cons
   rocblas_handle handle;
   int rc = blas_handle(ctx, st, &handle);
   if (rc) return rc;
-  double *d_mean = nullptr, *d_t = nullptr, *d_cov = nullptr, *d_w = nullptr, *d_e = nullptr;
-  rocblas_int* d_info = nullptr;
-  auto cleanup = [&]() {
-    void* b[] = {d_mean, d_t, d_cov, d_w, d_e, d_info};
-    for (void* q : b) if (q) (void)hipFree(q);
-  };
-  if (hipMalloc((void**)&d_mean, rows * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_t, (size_t)rows * count * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_cov, (size_t)rows * rows * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_w, rows * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_e, rows * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_info, sizeof(rocblas_int)) != hipSuccess) {
-    cleanup();
+  DevBuf mean, centred, cov, evals, work, info_dev;
+  if (mean.alloc(rows * sizeof(double)) != hipSuccess || centred.alloc((size_t)rows * count * sizeof(double)) != hipSuccess ||
+      cov.alloc((size_t)rows * rows * sizeof(double)) != hipSuccess || evals.alloc(rows * sizeof(double)) != hipSuccess ||
+      work.alloc(rows * sizeof(double)) != hipSuccess || info_dev.alloc(sizeof(rocblas_int)) != hipSuccess)
     return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed");
-  }
+  double *const d_mean = mean.as<double>(), *const d_t = centred.as<double>(), *const d_cov = cov.as<double>();
+  double *const d_w = evals.as<double>(), *const d_e = work.as<double>();
+  rocblas_int* const d_info = info_dev.as<rocblas_int>();
   hipLaunchKernelGGL(k_row_means, dim3(rows), dim3(256), 0, st, in_dev, n, first, stride, count, d_mean);
   hipLaunchKernelGGL(k_center_samples, dim3((unsigned)((count + 255) / 256), rows), dim3(256), 0, st, in_dev, n, first, stride,
                      count, (const double*)d_mean, d_t);
@@ -154,7 +146,7 @@ extern "C" int srmap_channel_pca_device(srmap_ctx* ctx, int rows, size_t n, cons
                                     &alpha, d_t, (rocblas_int)count, d_t, (rocblas_int)count, &beta, d_cov, rows);
   if (bs == rocblas_status_success)
     bs = rocsolver_dsyevd(handle, rocblas_evect_original, rocblas_fill_lower, rows, d_cov, rows, d_w, d_e, d_info);
-  if (bs != rocblas_status_success) { cleanup(); return set_error(ctx, SRMAP_EHIP, "covariance / eigen-decomposition failed"); }
+  if (bs != rocblas_status_success) return set_error(ctx, SRMAP_EHIP, "covariance / eigen-decomposition failed");
   std::vector<double> w(rows), V((size_t)rows * rows);
   rocblas_int info = 0;
   hipError_t e = hipMemcpyAsync(w.data(), d_w, rows * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -162,7 +154,6 @@ extern "C" int srmap_channel_pca_device(srmap_ctx* ctx, int rows, size_t n, cons
   if (e == hipSuccess) e = hipMemcpyAsync(mean_out, d_mean, rows * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   SRMAP_HIP(ctx, e);
   if (info != 0) return set_error(ctx, SRMAP_EHIP, "dsyevd did not converge (info %d)", (int)info);
   // dsyevd: ascending eigenvalues, eigenvector k = column k (column-major).  cv::PCA: descending, rows.
@@ -184,14 +175,11 @@ extern "C" int srmap_channel_pca(srmap_ctx* ctx, int rows, size_t count, const d
                                  double* eigenvalues_out, double* basis_out) {
   if (!ctx || !samples_host || rows <= 0 || count == 0) return SRMAP_EINVAL;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  double* d = nullptr;
-  SRMAP_HIP(ctx, hipMalloc((void**)&d, (size_t)rows * count * sizeof(double)));
-  hipError_t e = hipMemcpy(d, samples_host, (size_t)rows * count * sizeof(double), hipMemcpyHostToDevice);
-  int rc = SRMAP_OK;
-  if (e != hipSuccess) rc = set_error(ctx, SRMAP_EHIP, "upload of the PCA samples failed");
-  if (rc == SRMAP_OK) rc = srmap_channel_pca_device(ctx, rows, count, d, 0, 1, count, mean_out, eigenvalues_out, basis_out, nullptr);
-  (void)hipFree(d);
-  return rc;
+  DevBuf d;
+  SRMAP_HIP(ctx, d.alloc((size_t)rows * count * sizeof(double)));
+  if (hipMemcpy(d.as(), samples_host, (size_t)rows * count * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+    return set_error(ctx, SRMAP_EHIP, "upload of the PCA samples failed");
+  return srmap_channel_pca_device(ctx, rows, count, d.as<const double>(), 0, 1, count, mean_out, eigenvalues_out, basis_out, nullptr);
 }
 
 extern "C" int srmap_channel_map(srmap_ctx* ctx, int rows_out, int rows_in, size_t n, const double* M,
@@ -218,40 +206,31 @@ extern "C" int srmap_channel_map(srmap_ctx* ctx, int rows_out, int rows_in, size
   size_t chunk = ((size_t)2 << 30) / per_pixel;
   if (chunk > n) chunk = n;
   if (chunk == 0) chunk = 1;
-  double *d_in = nullptr, *d_out = nullptr, *d_M = nullptr, *d_bias = nullptr;
-  int rc = SRMAP_OK;
-  auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "%s", what); };
-  if (hipMalloc((void**)&d_in, chunk * rows_in * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_out, chunk * rows_out * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_M, (size_t)rows_out * rows_in * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_bias, (size_t)rows_out * sizeof(double)) != hipSuccess)
-    fail(SRMAP_ENOMEM, "hipMalloc failed");
-  if (rc == SRMAP_OK &&
-      (hipMemcpyAsync(d_M, M, (size_t)rows_out * rows_in * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-       hipMemcpyAsync(d_bias, bias.data(), (size_t)rows_out * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-       hipStreamSynchronize(st) != hipSuccess))
-    fail(SRMAP_EHIP, "upload of the map failed");
+  DevBuf in, out, map, bias_dev;
+  if (in.alloc(chunk * rows_in * sizeof(double)) != hipSuccess || out.alloc(chunk * rows_out * sizeof(double)) != hipSuccess ||
+      map.alloc((size_t)rows_out * rows_in * sizeof(double)) != hipSuccess || bias_dev.alloc((size_t)rows_out * sizeof(double)) != hipSuccess)
+    return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed");
+  double *const d_in = in.as<double>(), *const d_out = out.as<double>(), *const d_M = map.as<double>(), *const d_bias = bias_dev.as<double>();
+  if (hipMemcpyAsync(d_M, M, (size_t)rows_out * rows_in * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d_bias, bias.data(), (size_t)rows_out * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return set_error(ctx, SRMAP_EHIP, "upload of the map failed");
   srmap_problem tmp;  // staging helpers take a problem for its context / dtype
   tmp.ctx = ctx;
   tmp.dtype = SRMAP_F64;
-  for (size_t p0 = 0; p0 < n && rc == SRMAP_OK; p0 += chunk) {
+  for (size_t p0 = 0; p0 < n; p0 += chunk) {
     const size_t m = n - p0 < chunk ? n - p0 : chunk;
-    for (int c = 0; c < rows_in && rc == SRMAP_OK; ++c)  // planar rows of this chunk
-      rc = convert_upload(&tmp, in_host + (size_t)c * n + p0, d_in + (size_t)c * m, m, st);
-    if (rc) break;
+    for (int c = 0; c < rows_in; ++c)  // planar rows of this chunk
+      if (int rc = convert_upload(&tmp, in_host + (size_t)c * n + p0, d_in + (size_t)c * m, m, st)) return rc;
     hipLaunchKernelGGL(k_fill_rows, dim3((unsigned)((m + 255) / 256), rows_out), dim3(256), 0, st, d_out, d_bias, m, rows_out);
     // row-major planar [rows][m] == column-major (m x rows), ld = m:  OUT(m x ro) = IN(m x ri) * M^T(ri x ro) + OUT
     const double one = 1.0;
     const rocblas_status bs = rocblas_dgemm(handle, rocblas_operation_none, rocblas_operation_none, (rocblas_int)m,
                                             rows_out, rows_in, &one, d_in, (rocblas_int)m, d_M, rows_in, &one, d_out,
                                             (rocblas_int)m);
-    if (bs != rocblas_status_success) { fail(SRMAP_EHIP, "rocblas_dgemm failed"); break; }
-    for (int r = 0; r < rows_out && rc == SRMAP_OK; ++r)
-      rc = convert_download(&tmp, d_out + (size_t)r * m, out_host + (size_t)r * n + p0, m, st);
+    if (bs != rocblas_status_success) return set_error(ctx, SRMAP_EHIP, "rocblas_dgemm failed");
+    for (int r = 0; r < rows_out; ++r)
+      if (int rc = convert_download(&tmp, d_out + (size_t)r * m, out_host + (size_t)r * n + p0, m, st)) return rc;
   }
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (d_M) (void)hipFree(d_M);
-  if (d_bias) (void)hipFree(d_bias);
-  return rc;
+  return SRMAP_OK;
 }

@@ -95,7 +95,7 @@ struct srmap_comm {
   srmap_host_allreduce_fn ar = nullptr;
   srmap_host_sendrecv_fn sr = nullptr;
   void* user = nullptr;
-  void* h_send = nullptr; void* h_recv = nullptr; size_t h_cap = 0;  // pinned staging (host backend)
+  PinnedBuf h_send, h_recv; size_t h_cap = 0;  // pinned staging (host backend)
   // row shards: the halo exchange runs on this side stream, under the tiles that read no halo row (shard_eval.hip)
   hipStream_t side = nullptr;
   hipEvent_t ev_x = nullptr, ev_halo = nullptr;
@@ -123,12 +123,11 @@ int comm_world(const srmap_comm* c) { return c ? c->world : 1; }
 
 static int ensure_host(srmap_comm* c, size_t bytes) {
   if (c->h_cap >= bytes) return SRMAP_OK;
-  if (c->h_send) (void)hipHostFree(c->h_send);
-  if (c->h_recv) (void)hipHostFree(c->h_recv);
-  c->h_send = c->h_recv = nullptr; c->h_cap = 0;
+  c->h_recv.reset();
+  c->h_cap = 0;
   const size_t cap = bytes + (bytes >> 2) + 4096;
-  SRMAP_HIP(c->ctx, hipHostMalloc(&c->h_send, cap, hipHostMallocDefault));
-  SRMAP_HIP(c->ctx, hipHostMalloc(&c->h_recv, cap, hipHostMallocDefault));
+  SRMAP_HIP(c->ctx, c->h_send.alloc(cap, hipHostMallocDefault));
+  SRMAP_HIP(c->ctx, c->h_recv.alloc(cap, hipHostMallocDefault));
   c->h_cap = cap;
   return SRMAP_OK;
 }
@@ -144,11 +143,11 @@ int comm_allreduce(srmap_comm* c, void* dev, size_t count, int dtype, int op, hi
   }
   int rc = ensure_host(c, count * esz);
   if (rc) return rc;
-  SRMAP_HIP(c->ctx, hipMemcpyAsync(c->h_send, dev, count * esz, hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(c->ctx, hipMemcpyAsync(c->h_send.as(), dev, count * esz, hipMemcpyDeviceToHost, st));
   SRMAP_HIP(c->ctx, hipStreamSynchronize(st));
-  if (c->ar(c->h_send, count, dtype, op, c->user) != 0)
+  if (c->ar(c->h_send.as(), count, dtype, op, c->user) != 0)
     return set_error(c->ctx, SRMAP_EHIP, "host all-reduce callback failed");
-  SRMAP_HIP(c->ctx, hipMemcpyAsync(dev, c->h_send, count * esz, hipMemcpyHostToDevice, st));
+  SRMAP_HIP(c->ctx, hipMemcpyAsync(dev, c->h_send.as(), count * esz, hipMemcpyHostToDevice, st));
   SRMAP_HIP(c->ctx, hipStreamSynchronize(st));  // the pinned buffer is reused by the next call
   return SRMAP_OK;
 }
@@ -181,13 +180,13 @@ int comm_exchange(srmap_comm* c, const void* const* send, int dst, void* const* 
   if (rc) return rc;
   if (dst >= 0)
     for (int i = 0; i < nseg; ++i)
-      SRMAP_HIP(c->ctx, hipMemcpyAsync((char*)c->h_send + (size_t)i * send_seg * esz, send[i], send_seg * esz, hipMemcpyDeviceToHost, st));
+      SRMAP_HIP(c->ctx, hipMemcpyAsync(c->h_send.as<char>() + (size_t)i * send_seg * esz, send[i], send_seg * esz, hipMemcpyDeviceToHost, st));
   SRMAP_HIP(c->ctx, hipStreamSynchronize(st));
-  if (c->sr(c->h_send, dst >= 0 ? sbytes : 0, dst, c->h_recv, src >= 0 ? rbytes : 0, src, c->user) != 0)
+  if (c->sr(c->h_send.as(), dst >= 0 ? sbytes : 0, dst, c->h_recv.as(), src >= 0 ? rbytes : 0, src, c->user) != 0)
     return set_error(c->ctx, SRMAP_EHIP, "host send/receive callback failed");
   if (src >= 0) {
     for (int i = 0; i < nseg; ++i)
-      SRMAP_HIP(c->ctx, hipMemcpyAsync(recv[i], (char*)c->h_recv + (size_t)i * recv_seg * esz, recv_seg * esz, hipMemcpyHostToDevice, st));
+      SRMAP_HIP(c->ctx, hipMemcpyAsync(recv[i], c->h_recv.as<char>() + (size_t)i * recv_seg * esz, recv_seg * esz, hipMemcpyHostToDevice, st));
     SRMAP_HIP(c->ctx, hipStreamSynchronize(st));
   }
   return SRMAP_OK;
@@ -359,8 +358,6 @@ int srmap_comm_split(srmap_comm* c, int color, int key, int new_rank, int new_wo
 void srmap_comm_destroy(srmap_comm* c) {
   if (!c) return;
   if (c->kind == 1 && c->nccl && c->api) (void)c->api->CommDestroy(c->nccl);
-  if (c->h_send) (void)hipHostFree(c->h_send);
-  if (c->h_recv) (void)hipHostFree(c->h_recv);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->ev_x) (void)hipEventDestroy(c->ev_x);
   if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);

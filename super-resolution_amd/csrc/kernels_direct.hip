@@ -138,10 +138,10 @@ int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const
     constexpr int MOTION = decltype(motion)::value;
     if (dw != nullptr)
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, true>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw);
     else
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, false>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, k0, cost_scale, obs_C, obs_c0, dw);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw);
   });
   if (!launched) return set_error(p->ctx, SRMAP_EINVAL, "internal: no forward kernel for motion kind %d", kind);
   if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
@@ -467,7 +467,7 @@ static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T
                                   double out_scale, bool accumulate, hipStream_t st) {
   dim3 grid((unsigned)(((size_t)geo.W * geo.H + 255) / 256), geo.C);
   const MotionArgs<T> ma = motion_args<T>(p);
-  const T* bt = (const T*)p->d_blur_t;
+  const T* bt = p->d_blur_t.as<const T>();
   const int acc1 = accumulate ? 1 : 0;
 #define SRMAP_GATHER_SAMPLED(SS) \
   hipLaunchKernelGGL((k_gather_sampled<T, MOTION, SS>), grid, dim3(256), 0, st, resid, g, geo, ma, bt, k0, nk, (T)out_scale, acc1)
@@ -479,7 +479,7 @@ static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T
 }
 
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring) {
-  return ring > 0 && 2 * ring < geo.H && 2 * ring < geo.W && p->has_motion && p->d_bwd_warps != nullptr && geo.b <= geo.s &&
+  return ring > 0 && 2 * ring < geo.H && 2 * ring < geo.W && p->has_motion && p->d_bwd_warps && geo.b <= geo.s &&
          geo.s >= 2 && geo.s <= 4 && nk <= 16 && p->d_ytabs.empty();
 }
 
@@ -506,12 +506,12 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
     if (2 * ring >= geo.H || 2 * ring >= geo.W) ring = 0;
     else npix = 2 * (size_t)ring * geo.W + 2 * (size_t)ring * (geo.H - 2 * ring);
   }
-  const WarpTaps<T>* wp0 = p->has_motion ? (const WarpTaps<T>*)p->d_bwd_warps : nullptr;
+  const WarpTaps<T>* wp0 = p->has_motion ? p->d_bwd_warps.as<const WarpTaps<T>>() : nullptr;
   if (ringbuf != nullptr && !(accumulate && k0 == 0 && gather_ring_kernel_ok(p, geo, nk, ring)))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring buffer needs the ring kernel");
   if (ring > 0 && accumulate && k0 == 0 && gather_ring_kernel_ok(p, geo, nk, ring)) {
     dim3 grid((unsigned)((npix + 63) / 64), geo.C);
-    const T* bt0 = (const T*)p->d_blur_t;
+    const T* bt0 = p->d_blur_t.as<const T>();
 #define SRMAP_RING(SS, FF) hipLaunchKernelGGL((k_gather_ring<T, SS, FF>), grid, dim3(256), 0, st, resid, g, geo, wp0, bt0, nk, (T)out_scale, ring, ringbuf)
 #define SRMAP_RING_S(SS) do { if (nk <= 4) SRMAP_RING(SS, 1); else if (nk <= 8) SRMAP_RING(SS, 2); else SRMAP_RING(SS, 4); } while (0)
     if (geo.s == 2) SRMAP_RING_S(2); else if (geo.s == 3) SRMAP_RING_S(3); else SRMAP_RING_S(4);
@@ -524,8 +524,8 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
   while (groups < 16 && groups < nk) groups *= 2;  // thread groups of the ring mode: a power of two, at most 16
   const unsigned ppb = 256u / (unsigned)groups;
   dim3 grid((unsigned)(ring > 0 ? (npix + ppb - 1) / ppb : (npix + 255) / 256), geo.C);
-  const WarpTaps<T>* wp = p->has_motion ? (const WarpTaps<T>*)p->d_bwd_warps : nullptr;
-  const T* bt = (const T*)p->d_blur_t;
+  const WarpTaps<T>* wp = p->has_motion ? p->d_bwd_warps.as<const WarpTaps<T>>() : nullptr;
+  const T* bt = p->d_blur_t.as<const T>();
   const int acc1 = accumulate ? 1 : 0;
   if (geo.s == 2) hipLaunchKernelGGL((k_gather_direct<T, 2>), grid, dim3(256), 0, st, resid, g, geo, wp, bt, k0, nk, (T)out_scale, acc1, ring, groups);
   else if (geo.s == 3) hipLaunchKernelGGL((k_gather_direct<T, 3>), grid, dim3(256), 0, st, resid, g, geo, wp, bt, k0, nk, (T)out_scale, acc1, ring, groups);
@@ -543,6 +543,7 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
 struct PowTable {
   double v[2 * kMaxBtvRange + 1];
 };
+static_assert(std::is_trivially_copyable_v<PowTable>, "a kernel argument: no owner inside");
 
 template <typename T>
 __device__ __forceinline__ T absval(T v) { return v < T(0) ? -v : v; }

@@ -122,8 +122,9 @@ static int flow_seed_and_check(srmap_problem* p, const T* flow, int* seeds, doub
   dim3 grid((unsigned)((N + 255) / 256), g.K);
   const int nblk = (int)(grid.x * grid.y);
   const int stride = nblk + reduce_scratch_slots((size_t)nblk) + 8;  // partials + launch_reduce_partials' second stage
-  double* d_part = nullptr;
-  SRMAP_HIP(p->ctx, hipMalloc((void**)&d_part, ((size_t)3 * stride + 3) * sizeof(double)));
+  DevBuf part;  // the kernels below write it: the stream is waited for on every path before it goes out of scope
+  SRMAP_HIP(p->ctx, part.alloc(((size_t)3 * stride + 3) * sizeof(double)));
+  double* d_part = part.as<double>();
   double* d_counts = d_part + (size_t)3 * stride;
   hipLaunchKernelGGL(k_flow_seed<T>, grid, dim3(256), 0, st, flow, seeds, g.W, g.H);
   hipLaunchKernelGGL(k_flow_check<T>, grid, dim3(256), 0, st, flow, (const int*)seeds, g.W, g.H, d_part, stride);
@@ -133,7 +134,6 @@ static int flow_seed_and_check(srmap_problem* p, const T* flow, int* seeds, doub
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(counts_host, d_counts, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
   const hipError_t e2 = hipStreamSynchronize(st);
-  (void)hipFree(d_part);
   if (rc) return rc;
   SRMAP_HIP(p->ctx, e);
   SRMAP_HIP(p->ctx, e2);
@@ -146,54 +146,45 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
   const Geometry& g = p->geo;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = (size_t)g.W * g.H, n = (size_t)g.K * 2 * N;
-  void* nf = nullptr;
-  int* ns = nullptr;
+  DevBuf nf, ns;  // the new field and its seeds: built here, moved into the problem once they are valid
   const bool set = flow_host != nullptr || flow_dev != nullptr;
   if (set) {
     if (((size_t)g.W + 2 * kFlowPad) * ((size_t)g.H + 2 * kFlowPad) >= ((size_t)1 << 31))
       return set_error(ctx, SRMAP_EUNSUPPORTED, "displacement field: an image of %d x %d is beyond the packed seed's range", g.W, g.H);
-    if (hipMalloc(&nf, n * p->elem()) != hipSuccess || hipMalloc((void**)&ns, (size_t)g.K * N * sizeof(int)) != hipSuccess) {
-      if (nf) (void)hipFree(nf);
-      (void)hipGetLastError();
+    if (nf.alloc(n * p->elem()) != hipSuccess || ns.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
       return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed (displacement field: %zu bytes, seeds: %zu bytes)", n * p->elem(),
                        (size_t)g.K * N * sizeof(int));
-    }
-    auto fail = [&](int code) { (void)hipFree(nf); (void)hipFree(ns); return code; };
     int rc = SRMAP_OK;
     if (flow_dev) {
-      if (hipMemcpyAsync(nf, flow_dev, n * p->elem(), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(set_error(ctx, SRMAP_EHIP, "copying the displacement field failed"));
+      if (hipMemcpyAsync(nf.as(), flow_dev, n * p->elem(), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return set_error(ctx, SRMAP_EHIP, "copying the displacement field failed");
     } else {
-      rc = convert_upload(p, flow_host, nf, n, st);
-      if (rc) return fail(rc);
+      rc = convert_upload(p, flow_host, nf.as(), n, st);
+      if (rc) return rc;
     }
     double counts[3] = {0.0, 0.0, 0.0};
-    rc = p->dtype == SRMAP_F32 ? flow_seed_and_check<float>(p, (const float*)nf, ns, counts, st)
-                               : flow_seed_and_check<double>(p, (const double*)nf, ns, counts, st);
-    if (rc) return fail(rc);
+    rc = p->dtype == SRMAP_F32 ? flow_seed_and_check<float>(p, nf.as<const float>(), ns.as<int>(), counts, st)
+                               : flow_seed_and_check<double>(p, nf.as<const double>(), ns.as<int>(), counts, st);
+    if (rc) return rc;
     // the problem keeps the motion it had
     if (counts[0] != 0.0)
-      return fail(set_error(ctx, SRMAP_EINVAL, "displacement field: %.0f entries are not finite in the problem's dtype", counts[0]));
+      return set_error(ctx, SRMAP_EINVAL, "displacement field: %.0f entries are not finite in the problem's dtype", counts[0]);
     if (counts[1] != 0.0)
-      return fail(set_error(ctx, SRMAP_EUNSUPPORTED, "displacement field: %.0f entries exceed 2^20 pixels", counts[1]));
+      return set_error(ctx, SRMAP_EUNSUPPORTED, "displacement field: %.0f entries exceed 2^20 pixels", counts[1]);
     if (counts[2] != 0.0)
-      return fail(set_error(ctx, SRMAP_EUNSUPPORTED,
-                            "displacement field: %.0f (pixel, tap) pairs lie outside the transpose's %d x %d gather window (the field "
-                            "folds, or its neighbour differences exceed the documented bound)",
-                            counts[2], 2 * kFlowRadius + 1, 2 * kFlowRadius + 1));
+      return set_error(ctx, SRMAP_EUNSUPPORTED,
+                       "displacement field: %.0f (pixel, tap) pairs lie outside the transpose's %d x %d gather window (the field "
+                       "folds, or its neighbour differences exceed the documented bound)",
+                       counts[2], 2 * kFlowRadius + 1, 2 * kFlowRadius + 1);
   }
   // evaluations in flight read the field: drain them before the buffers change
-  if (p->use_stream) SRMAP_HIP(ctx, hipStreamSynchronize(p->use_stream));
-  SRMAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (p->d_flow) (void)hipFree(p->d_flow);
-  if (p->d_flow_seed) (void)hipFree(p->d_flow_seed);
-  p->d_flow = nf;
-  p->d_flow_seed = ns;
+  if (int rc = model_drain(p)) return rc;
+  p->d_flow = std::move(nf);  // empty when the call clears the flow; the old field and seeds are freed
+  p->d_flow_seed = std::move(ns);
   p->flow = set;
   p->affine = false;  // alternatives: a flow replaces an affine motion, and NULL restores the created motion
   p->affine_recs.clear();
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);  // "not covered" while a flow is set
+  model_replan(p);  // "not covered" while a flow is set
   return SRMAP_OK;
 }
 
@@ -216,5 +207,5 @@ extern "C" int srmap_problem_get_flow(srmap_problem* p, double* flow_out, int* i
   if (is_set) *is_set = p->flow ? 1 : 0;
   if (!flow_out || !p->flow) return SRMAP_OK;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return convert_download(p, p->d_flow, flow_out, (size_t)p->geo.K * 2 * p->geo.W * p->geo.H, p->ctx->stream);
+  return convert_download(p, p->d_flow.as(), flow_out, (size_t)p->geo.K * 2 * p->geo.W * p->geo.H, p->ctx->stream);
 }

@@ -43,6 +43,8 @@ struct SpFrame {  // one frame's forward warp folded with the blur
   T comb[4][16];  // (b+1) x (b+1) stencils, row major with stride b+1: [0] interior, [1] without blur column 0
                   // (LR column 0), [2] without blur row 0 (LR row 0), [3] without both
 };
+static_assert(std::is_trivially_copyable_v<SpFrame<float>> && std::is_trivially_copyable_v<SpFrame<double>>,
+              "a kernel argument: no owner inside");
 
 template <typename T>
 struct SpfArgs {
@@ -69,6 +71,8 @@ struct SpfArgs {
   const double* fold_norms;
   const T* dw;  // WEIGHTED instances: the data weights, indexed like y
 };
+static_assert(std::is_trivially_copyable_v<SpfArgs<float>> && std::is_trivially_copyable_v<SpfArgs<double>>,
+              "a kernel argument: no owner inside");
 
 __device__ __forceinline__ int fdiv_rt(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
@@ -271,8 +275,8 @@ bool upload_frames(const srmap_problem* p, SpForwardPlan* sp) {
         }
     }
   }
-  if (hipMalloc(&sp->d_frames, sizeof(SpFrame<T>) * fr.size()) != hipSuccess) return false;
-  return hipMemcpy(sp->d_frames, fr.data(), sizeof(SpFrame<T>) * fr.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (sp->d_frames.alloc(sizeof(SpFrame<T>) * fr.size()) != hipSuccess) return false;
+  return hipMemcpy(sp->d_frames.as(), fr.data(), sizeof(SpFrame<T>) * fr.size(), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 template <typename T, int S, int B>
@@ -286,7 +290,7 @@ int launch_typed(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp,
     return set_error(p->ctx, SRMAP_EINVAL, "internal: the forward tile kernel cannot form the trial point for this geometry (no fold)");
   A.RF0 = sp.RF0; A.NRF = sp.NRF; A.CF0 = sp.CF0; A.NCF = sp.NCF;
   A.x = x; A.y = y; A.out = out; A.partials = partials;
-  A.frames = (const SpFrame<T>*)sp.d_frames;
+  A.frames = sp.d_frames.as<const SpFrame<T>>();
   A.K = geo.K; A.W = geo.W; A.H = geo.H; A.wl = geo.w; A.hl = geo.h; A.C = geo.C;
   A.obs_C = obs_C; A.obs_c0 = obs_c0; A.cr0 = geo.cr0; A.cr1 = geo.cr1;
   A.RLO = sp.RLO; A.CLO = sp.CLO; A.XR = sp.XR; A.XC = sp.XC;
@@ -319,7 +323,7 @@ void preload_typed(bool weighted) {
 }  // namespace
 
 bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
-  spfwd_release(sp);
+  *sp = SpForwardPlan();
   const Geometry& g = p->geo;
   const int S = g.s, B = g.b;
   if (p->affine || p->flow || !p->has_motion || !p->maps_regular || S < 2 || S > 4 || (B != 1 && B != 3)) return false;
@@ -340,7 +344,7 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   const size_t lds = (size_t)sp->XR * S * sp->XC * (p->dtype == SRMAP_F32 ? 4 : 8);
   if (sp->XR > kMaxRowsPerWave * kNW || sp->XC > 2 * kCW || sp->XC < kCW || lds > 64 * 1024) return false;
   const bool ok = p->dtype == SRMAP_F32 ? upload_frames<float>(p, sp) : upload_frames<double>(p, sp);
-  if (!ok) { spfwd_release(sp); return false; }
+  if (!ok) { *sp = SpForwardPlan(); return false; }
   sp->ok = true;
   // fold (solver line search): a workgroup walks the union of its window and its own S kLRH x S kCW pixels
   sp->RF0 = std::min(sp->RLO, 0); sp->NRF = std::max(sp->RLO + sp->XR, S * kLRH) - sp->RF0;
@@ -357,12 +361,6 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
     else if (B == 1) preload_typed<double, 4, 1>(wt); else preload_typed<double, 4, 3>(wt);
   }
   return true;
-}
-
-void spfwd_release(SpForwardPlan* sp) {
-  if (sp->d_frames) (void)hipFree(sp->d_frames);
-  sp->d_frames = nullptr;
-  sp->ok = false;
 }
 
 template <typename T>

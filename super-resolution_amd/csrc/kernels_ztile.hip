@@ -526,26 +526,13 @@ __global__ __launch_bounds__(256) void k_finish_eval(T* __restrict__ g, const T*
 constexpr size_t kMaxFusedPartials = 65536;
 
 void ztile_release(srmap_problem* p) {
-  ZPlan* z = static_cast<ZPlan*>(p->zplan);
-  if (!z) return;
-  if (z->d_hdr) (void)hipFree(z->d_hdr);
-  if (z->d_ent) (void)hipFree(z->d_ent);
-  if (z->d_cnt) (void)hipFree(z->d_cnt);
-  if (z->d_off) (void)hipFree(z->d_off);
-  if (z->d_aux) (void)hipFree(z->d_aux);
-  if (z->d_spsrc) (void)hipFree(z->d_spsrc);
-  if (z->d_ringbuf) (void)hipFree(z->d_ringbuf);
-  spfwd_release(&z->spf);
-  if (z->d_corr) (void)hipFree(z->d_corr);
-  if (z->d_bd) (void)hipFree(z->d_bd);
-  if (z->d_mpart) (void)hipFree(z->d_mpart);
-  delete z;
+  delete static_cast<ZPlan*>(p->zplan);  // and every table it owns
   p->zplan = nullptr;
 }
 
 void ztile_rearm(srmap_problem* p) {
   ZPlan* z = static_cast<ZPlan*>(p->zplan);
-  if (z && z->d_mpart) (void)hipMemsetD32((hipDeviceptr_t)z->d_mpart, (int)kSentinel32, 4 * z->mpart_cap);
+  if (z && z->d_mpart) (void)hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * z->mpart_cap);
 }
 
 // Decide whether k_eval_z covers the problem; build the frame table.
@@ -636,18 +623,18 @@ bool ztile_plan(srmap_problem* p) {
     }
     // the only table an SP instance reads (z_row_sp2: spsrc, spn, spmax); the integer-shift frame table (cnt, off, aux) and
     // the border blocks' tables stay unset -- no border blocks with E = 0
-    bool ok = hipMalloc((void**)&z->d_spsrc, sizeof(ZSrc) * srctab.size()) == hipSuccess &&
-              hipMemcpy(z->d_spsrc, srctab.data(), sizeof(ZSrc) * srctab.size(), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = z->d_spsrc.alloc(sizeof(ZSrc) * srctab.size()) == hipSuccess &&
+              hipMemcpy(z->d_spsrc.as<ZSrc>(), srctab.data(), sizeof(ZSrc) * srctab.size(), hipMemcpyHostToDevice) == hipSuccess;
     p->zplan = z;
     if (ok && gather_ring_kernel_ok(p, g, K, z->Dr)) {
       // the ring pass runs ahead of the tile kernel into this buffer (g.d and the cost then finish inside the tile launch)
       const size_t nring = 2 * (size_t)z->Dr * g.W + 2 * (size_t)z->Dr * (g.H - 2 * z->Dr);
-      ok = hipMalloc(&z->d_ringbuf, nring * g.C * p->elem()) == hipSuccess;
+      ok = z->d_ringbuf.alloc(nring * g.C * p->elem()) == hipSuccess;
     }
     if (ok) {  // granules of the in-kernel cost reduction (as below)
       const size_t cap = std::min<size_t>(ztile_partials_needed(p), kMaxFusedPartials);
-      ok = hipMalloc((void**)&z->d_mpart, 2 * cap * sizeof(double)) == hipSuccess &&
-           hipMemsetD32((hipDeviceptr_t)z->d_mpart, (int)kSentinel32, 4 * cap) == hipSuccess;
+      ok = z->d_mpart.alloc(2 * cap * sizeof(double)) == hipSuccess &&
+           hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * cap) == hipSuccess;
       z->mpart_cap = cap;
     }
     if (!ok) { ztile_release(p); return false; }
@@ -714,16 +701,16 @@ bool ztile_plan(srmap_problem* p) {
     }
   }
   for (size_t i = 0; i < cnt.size(); ++i) z->h_cnt[i] = cnt[i];
-  bool ok = hipMalloc((void**)&z->d_hdr, sizeof(int2) * hdr.size()) == hipSuccess &&
-            hipMemcpy(z->d_hdr, hdr.data(), sizeof(int2) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMalloc((void**)&z->d_ent, sizeof(ZEntry) * ent.size()) == hipSuccess &&
-            hipMemcpy(z->d_ent, ent.data(), sizeof(ZEntry) * ent.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMalloc((void**)&z->d_cnt, sizeof(int) * cnt.size()) == hipSuccess &&
-            hipMemcpy(z->d_cnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMalloc((void**)&z->d_off, sizeof(long long) * off.size()) == hipSuccess &&
-            hipMemcpy(z->d_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMalloc((void**)&z->d_aux, sizeof(ZEntry) * aux.size()) == hipSuccess &&
-            hipMemcpy(z->d_aux, aux.data(), sizeof(ZEntry) * aux.size(), hipMemcpyHostToDevice) == hipSuccess;
+  bool ok = z->d_hdr.alloc(sizeof(int2) * hdr.size()) == hipSuccess &&
+            hipMemcpy(z->d_hdr.as<int2>(), hdr.data(), sizeof(int2) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            z->d_ent.alloc(sizeof(ZEntry) * ent.size()) == hipSuccess &&
+            hipMemcpy(z->d_ent.as<ZEntry>(), ent.data(), sizeof(ZEntry) * ent.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            z->d_cnt.alloc(sizeof(int) * cnt.size()) == hipSuccess &&
+            hipMemcpy(z->d_cnt.as<int>(), cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            z->d_off.alloc(sizeof(long long) * off.size()) == hipSuccess &&
+            hipMemcpy(z->d_off.as<long long>(), off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            z->d_aux.alloc(sizeof(ZEntry) * aux.size()) == hipSuccess &&
+            hipMemcpy(z->d_aux.as<ZEntry>(), aux.data(), sizeof(ZEntry) * aux.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && z->E > 0) {
     // the rectangles of the border frame that can carry work (ztile_dev.hpp RingRects)
     int mnx = 0, mxx = 0, mny = 0, mxy = 0;
@@ -740,14 +727,14 @@ bool ztile_plan(srmap_problem* p) {
     rr.rg[5] = std::max(0, mxx - S + 1);
     z->ring = rr;
     z->n_ring = (int)ring_count(rr, g.W, g.H);
-    if (z->n_ring > 0) ok = hipMalloc(&z->d_corr, (size_t)g.C * z->n_ring * p->elem()) == hipSuccess;
+    if (z->n_ring > 0) ok = z->d_corr.alloc((size_t)g.C * z->n_ring * p->elem()) == hipSuccess;
   }
   if (ok) {
     auto put = [&](auto bd) {
-      bd.hdr = z->d_hdr; bd.ent = z->d_ent; bd.blur_d = (decltype(bd.blur_d))p->d_blur; bd.corr = (decltype(bd.corr))z->d_corr;
+      bd.hdr = z->d_hdr.as<int2>(); bd.ent = z->d_ent.as<ZEntry>(); bd.blur_d = (decltype(bd.blur_d))p->d_blur.as(); bd.corr = (decltype(bd.corr))z->d_corr.as();
       bd.S = S; bd.b = B; bd.hb = g.hb; bd.n_ring = z->n_ring; bd.n_ent = z->n_ent; bd.obs_C = g.C;
-      return hipMalloc(&z->d_bd, sizeof(bd)) == hipSuccess &&
-             hipMemcpy(z->d_bd, &bd, sizeof(bd), hipMemcpyHostToDevice) == hipSuccess;
+      return z->d_bd.alloc(sizeof(bd)) == hipSuccess &&
+             hipMemcpy(z->d_bd.as(), &bd, sizeof(bd), hipMemcpyHostToDevice) == hipSuccess;
     };
     ok = p->dtype == SRMAP_F32 ? put(BorderArgs<float>()) : put(BorderArgs<double>());
   }
@@ -756,8 +743,8 @@ bool ztile_plan(srmap_problem* p) {
     // granules of the in-kernel cost reduction (one per tile + one per border block), up to a cap beyond which the
     // caller's two-stage reduction is used anyway
     const size_t cap = std::min<size_t>(ztile_partials_needed(p), kMaxFusedPartials);
-    ok = hipMalloc((void**)&z->d_mpart, 2 * cap * sizeof(double)) == hipSuccess &&
-         hipMemsetD32((hipDeviceptr_t)z->d_mpart, (int)kSentinel32, 4 * cap) == hipSuccess;
+    ok = z->d_mpart.alloc(2 * cap * sizeof(double)) == hipSuccess &&
+         hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * cap) == hipSuccess;
     z->mpart_cap = cap;
   }
   if (!ok) { ztile_release(p); return false; }
@@ -796,7 +783,7 @@ static size_t ztile_est_partials(const ZPlan* z, int w, int H, int C) {
 static bool ztile_gd_instance_ok(const srmap_problem* p, const ZPlan& z, int w, int H, int C, unsigned terms) {
   // sub-pixel plans: the ring pass must be able to run AHEAD of the tile launch (into z.d_ringbuf) -- a pass that adds to g
   // behind it would leave the launch's g.d without the ring's share
-  if (z.subpix && z.d_ringbuf == nullptr) return false;
+  if (z.subpix && !z.d_ringbuf) return false;
   if (terms & SRMAP_TERM_REG)
     for (int r = 0; r < p->nreg; ++r)
       if (!(z.regk != 0 && r == z.reg_index) && p->reg[r].lambda > 0.0) return false;
@@ -834,7 +821,7 @@ static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, i
   { const unsigned t = grid.x; grid.x = grid.y; grid.y = t; }
   const int n_tile_partials = (int)(grid.x * grid.y * grid.z);
   // border blocks: whole rows of the grid in front of the tiles
-  A.bd = (const BorderArgs<T>*)z.d_bd;
+  A.bd = z.d_bd.as<const BorderArgs<T>>();
   A.nby = 0; A.n_tile_partials = n_tile_partials;
   int nbb = 0;
   if ((terms & SRMAP_TERM_DATA) && z.n_ring > 0) {
@@ -847,9 +834,9 @@ static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, i
 
   A.mfinish = mfin.on ? 1 : 0;
   A.n_partials = n_tile_partials + nbb * (int)grid.z;
-  A.mpart = z.d_mpart;
-  A.mpart_gd = z.d_mpart ? z.d_mpart + z.mpart_cap : nullptr;
-  A.cost_out = p->d_cost;
+  A.mpart = z.d_mpart.as<double>();
+  A.mpart_gd = z.d_mpart ? z.d_mpart.as<double>() + z.mpart_cap : nullptr;
+  A.cost_out = p->d_cost.as<double>();
   A.pub = mfin.publish ? req.pub.out : nullptr;
   A.tag_slot = req.pub.tag_slot;
   A.tag = req.pub.tag;
@@ -858,9 +845,9 @@ static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, i
   if (mfin.on && (size_t)A.n_partials > z.mpart_cap) return set_error(p->ctx, SRMAP_EHIP, "granule capacity");
   A.sel_mode = 0; A.sel0 = 0; A.sel1 = 0;
   if (z.subpix && (terms & SRMAP_TERM_DATA)) {
-    A.rbuf = (const T*)p->d_resid;
+    A.rbuf = p->d_resid.as<const T>();
     A.obs_C = geo.C;  // layout of the residual buffer written by launch_forward_direct for this evaluation
-    A.ringbuf = ring_ahead ? (const T*)z.d_ringbuf : nullptr;
+    A.ringbuf = ring_ahead ? z.d_ringbuf.as<const T>() : nullptr;
     if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, true>), grid, dim3(C::NT), 0, st, A);
     else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, true>), grid, dim3(C::NT), 0, st, A);
   } else {
@@ -970,7 +957,7 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
   if (want_reg && z.regk != 0) {
     regk = z.regk; regr = z.regr;
     const RegSpec& rs = p->reg[z.reg_index];
-    wts = rs.weights ? (const T*)rs.weights + (size_t)obs_c0 * N : nullptr;
+    wts = rs.weights ? rs.weights.as<const T>() + (size_t)obs_c0 * N : nullptr;
   }
   unsigned zterms = terms & SRMAP_TERM_DATA;
   if (regk) zterms |= SRMAP_TERM_REG;
@@ -991,35 +978,35 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
   // adding to g (then no g.d from the launch: ztile_gd_instance_ok).  Ring blocks at the front of the tile launch's own
   // grid (one launch less) were built and measured: every ring workgroup holds a tile slot (73 KB of LDS) for its 6 - 9 us of
   // latency, 450 of the 512 slots of the first generation -- 82.9 us against 82.5 us, and slower inside a solve.
-  const bool ring_ahead = sp_data && g != nullptr && z.d_ringbuf != nullptr;
+  const bool ring_ahead = sp_data && g != nullptr && z.d_ringbuf;
   if (sp_data) {
     // sub-pixel shifts: exact residuals (and the data cost) from the direct forward kernel, then the tile kernel
     // gathers them with the 4-tap tables; the pixels within Dr of the edge are evaluated exactly by the ring pass
-    if (!p->d_resid) SRMAP_HIP(p->ctx, hipMalloc(&p->d_resid, p->lr_count() * sizeof(T)));
+    if (!p->d_resid) SRMAP_HIP(p->ctx, p->d_resid.alloc(p->lr_count() * sizeof(T)));
     if (req.fold.xk != nullptr && !(with_d && z.spf.ok && z.spf.can_fold))
       return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
-    const T* dw = (const T*)p->d_dw;  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
+    const T* dw = p->d_dw.as<const T>();  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
     if (z.spf.ok)
-      rc = launch_forward_sp<T>(p, geo, z.spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st, req.fold, dw);
+      rc = launch_forward_sp<T>(p, geo, z.spf, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), partials, &nfwd, st, req.fold, dw);
     else
-      rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st, dw);
+      rc = launch_forward_direct<T>(p, geo, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), 0, geo.K, partials, &nfwd, st, dw);
     if (rc) return rc;
     partials += nfwd;
     if (ring_ahead) {
-      rc = launch_gather_direct<T>(p, geo, (const T*)p->d_resid, g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr, (T*)z.d_ringbuf);
+      rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr, z.d_ringbuf.as<T>());
       if (rc) return rc;
     }
   }
   if (req.fold.xk != nullptr && !(with_d && req.overlap.fn == nullptr))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the tile kernel's g.d instance (ztile_can_fold)");
   const T* dv = with_d ? (const T*)req.dvec : nullptr;
-  double* pgd = with_d ? p->d_partials + p->partials_cap / 2 : nullptr;
+  double* pgd = with_d ? p->d_partials.as<double>() + p->partials_cap / 2 : nullptr;
   // tiles: the cost reduction inside the kernel (no finish launch) when no in-image pixel of the border frame needs a
   // correction, no further regulariser kernel follows and the granules suffice
   // Sub-pixel plan: the forward kernel's data-cost partials (plain doubles, complete before the tile kernel starts) are
   // added by the same in-kernel finish; the ring pass touches g only.
   MFin mfin;
-  mfin.on = !more_regs && req.overlap.fn == nullptr && z.d_mpart != nullptr && est_parts <= z.mpart_cap &&
+  mfin.on = !more_regs && req.overlap.fn == nullptr && z.d_mpart && est_parts <= z.mpart_cap &&
             (z.n_ring == 0 || (z.ring.rg[0] == 0 && z.ring.rg[1] == 0)) && (size_t)nfwd <= kMaxFusedPartials;
   mfin.publish = mfin.on && with_d && req.pub.out != nullptr;
   mfin.xpart = (mfin.on && sp_data) ? partials - nfwd : nullptr;
@@ -1034,7 +1021,7 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
     partials -= nfwd;
     nb += nfwd;
     if (g != nullptr && !ring_ahead) {
-      rc = launch_gather_direct<T>(p, geo, (const T*)p->d_resid, g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr);
+      rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr);
       if (rc) return rc;
     }
   }
@@ -1047,13 +1034,13 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
       if (rs.lambda <= 0.0) continue;
       const bool onfly = rs.kind != SRMAP_REG_BTV;
       if (!onfly) {
-        if (!p->d_regvals) SRMAP_HIP(p->ctx, hipMalloc(&p->d_regvals, p->hr_count() * sizeof(T)));
-        rc = launch_reg_values<T>(p, geo, rs, x, (T*)p->d_regvals, st);
+        if (!p->d_regvals) SRMAP_HIP(p->ctx, p->d_regvals.alloc(p->hr_count() * sizeof(T)));
+        rc = launch_reg_values<T>(p, geo, rs, x, p->d_regvals.as<T>(), st);
         if (rc) return rc;
       }
-      const T* w2 = rs.weights ? (const T*)rs.weights + (size_t)obs_c0 * N : nullptr;
+      const T* w2 = rs.weights ? rs.weights.as<const T>() + (size_t)obs_c0 * N : nullptr;
       int nb2 = 0;
-      rc = launch_reg_gradient_direct<T>(p, geo, rs, x, w2, rs.lambda, onfly ? nullptr : (const T*)p->d_regvals, g, true,
+      rc = launch_reg_gradient_direct<T>(p, geo, rs, x, w2, rs.lambda, onfly ? nullptr : p->d_regvals.as<const T>(), g, true,
                                          partials + total, &nb2, st);
       if (rc) return rc;
       total += nb2;
@@ -1070,8 +1057,8 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
   if ((size_t)total <= kMaxFusedPartials) {
     const int nring = corr_on ? z.n_ring : 0;
     const unsigned nb_f = 1u + (unsigned)((nring + 255) / 256);
-    hipLaunchKernelGGL(k_finish_eval<T>, dim3(nb_f), dim3(256), 0, st, corr_on ? g : (T*)nullptr, (const T*)z.d_corr,
-                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, total, p->d_cost, (const double*)pgd,
+    hipLaunchKernelGGL(k_finish_eval<T>, dim3(nb_f), dim3(256), 0, st, corr_on ? g : (T*)nullptr, z.d_corr.as<const T>(),
+                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, total, p->d_cost.as<double>(), (const double*)pgd,
                        with_d ? req.pub.out : (double*)nullptr, req.pub.tag_slot, req.pub.tag);
     SRMAP_HIP(p->ctx, hipGetLastError());
     out->gd_valid = with_d;  // d_cost[1] = g.d
@@ -1081,8 +1068,8 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
   }
   // many partials (multi-channel problems): corrections here, two-stage reduction by the caller
   if (corr_on) {
-    hipLaunchKernelGGL(k_finish_eval<T>, dim3(1u + (unsigned)((z.n_ring + 255) / 256)), dim3(256), 0, st, g, (const T*)z.d_corr,
-                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, 0, p->d_cost + 1, (const double*)nullptr,
+    hipLaunchKernelGGL(k_finish_eval<T>, dim3(1u + (unsigned)((z.n_ring + 255) / 256)), dim3(256), 0, st, g, z.d_corr.as<const T>(),
+                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, 0, p->d_cost.as<double>() + 1, (const double*)nullptr,
                        (double*)nullptr, (double*)nullptr, 0.0);
     SRMAP_HIP(p->ctx, hipGetLastError());
   }
@@ -1093,11 +1080,11 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
 template <typename T>
 int launch_forward_residual(srmap_problem* p, const Geometry& geo, int obs_c0, const T* x, double* partials, hipStream_t st) {
   const ZPlan* z = p->impl != SRMAP_IMPL_DIRECT ? static_cast<const ZPlan*>(p->zplan) : nullptr;
-  if (!p->d_resid) SRMAP_HIP(p->ctx, hipMalloc(&p->d_resid, p->lr_count() * sizeof(T)));
+  if (!p->d_resid) SRMAP_HIP(p->ctx, p->d_resid.alloc(p->lr_count() * sizeof(T)));
   int nfwd = 0;
   if (z != nullptr && z->subpix && z->spf.ok)
-    return launch_forward_sp<T>(p, geo, z->spf, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, partials, &nfwd, st);
-  return launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, obs_c0, (T*)p->d_resid, 0, geo.K, partials, &nfwd, st);
+    return launch_forward_sp<T>(p, geo, z->spf, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), partials, &nfwd, st);
+  return launch_forward_direct<T>(p, geo, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), 0, geo.K, partials, &nfwd, st);
 }
 template int launch_forward_residual<float>(srmap_problem*, const Geometry&, int, const float*, double*, hipStream_t);
 template int launch_forward_residual<double>(srmap_problem*, const Geometry&, int, const double*, double*, hipStream_t);

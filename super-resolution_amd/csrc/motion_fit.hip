@@ -42,36 +42,28 @@ bool FitPass::alloc(int frames_, int nsums_, size_t part_elems) {
   frames = frames_;
   nsums = nsums_;
   return nsums <= 64 &&
-         hipMalloc((void**)&d_part, part_elems * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&d_tab, (size_t)frames * kFitTabRec * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&d_sums, (size_t)frames * nsums * sizeof(double)) == hipSuccess &&
-         hipHostMalloc((void**)&h_tab, (size_t)frames * kFitTabRec * sizeof(double)) == hipSuccess &&
-         hipHostMalloc((void**)&h_sums, (size_t)frames * nsums * sizeof(double)) == hipSuccess;
-}
-
-FitPass::~FitPass() {
-  if (d_part) (void)hipFree(d_part);
-  if (d_tab) (void)hipFree(d_tab);
-  if (d_sums) (void)hipFree(d_sums);
-  if (h_tab) (void)hipHostFree(h_tab);
-  if (h_sums) (void)hipHostFree(h_sums);
+         d_part.alloc(part_elems * sizeof(double)) == hipSuccess &&
+         d_tab.alloc((size_t)frames * kFitTabRec * sizeof(double)) == hipSuccess &&
+         d_sums.alloc((size_t)frames * nsums * sizeof(double)) == hipSuccess &&
+         h_tab.alloc((size_t)frames * kFitTabRec * sizeof(double)) == hipSuccess &&
+         h_sums.alloc((size_t)frames * nsums * sizeof(double)) == hipSuccess;
 }
 
 void FitPass::set(int frame, const AffineMap& M, bool active) {
-  double* rec = h_tab + (size_t)frame * kFitTabRec;
+  double* rec = h_tab.as<double>() + (size_t)frame * kFitTabRec;
   std::copy(M.m, M.m + 6, rec);
   rec[6] = active ? 1.0 : 0.0;
   rec[7] = 0.0;
 }
 
 bool FitPass::upload(hipStream_t st) {
-  return hipMemcpyAsync(d_tab, h_tab, (size_t)frames * kFitTabRec * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+  return hipMemcpyAsync(d_tab.as(), h_tab.as(), (size_t)frames * kFitTabRec * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
 }
 
 bool FitPass::reduce_and_fetch(int chunks, hipStream_t st) {
-  hipLaunchKernelGGL(k_fit_reduce, dim3(frames), dim3(64), 0, st, d_part, chunks, nsums, d_tab, d_sums);
+  hipLaunchKernelGGL(k_fit_reduce, dim3(frames), dim3(64), 0, st, d_part.as<double>(), chunks, nsums, d_tab.as<double>(), d_sums.as<double>());
   return hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(h_sums, d_sums, (size_t)frames * nsums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(h_sums.as(), d_sums.as(), (size_t)frames * nsums * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
          hipStreamSynchronize(st) == hipSuccess;
 }
 

@@ -135,11 +135,11 @@ void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, 
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
   if (p->d_dw)
-    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)p->d_dw, g,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, d_tab, ppt, d_part);
+    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), p->d_dw.as<const T>(), g,
+                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part);
   else
-    hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, (const T*)p->d_obs, (const T*)nullptr, g,
-                       (const T*)p->d_blur, p->d_col_map, p->d_row_map, d_tab, ppt, d_part);
+    hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), (const T*)nullptr, g,
+                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part);
 }
 
 }  // namespace
@@ -205,11 +205,8 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
   const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
   FitPass fit;
-  auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "motion refinement: %s", what); };
-  if (!fit.alloc(K, kSums, (size_t)K * chunks * kSums)) {
-    (void)hipGetLastError();
-    fail(SRMAP_ENOMEM, "allocation failed");
-  }
+  auto fail = [&](int code, const char* what) { return set_error(ctx, code, "motion refinement: %s", what); };
+  if (!fit.alloc(K, kSums, (size_t)K * chunks * kSums)) return fail(SRMAP_ENOMEM, "allocation failed");
 
   std::vector<FrameState> fs(K);
   for (int k = 0; k < K; ++k) {
@@ -225,8 +222,8 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   auto pass = [&]() -> bool {
     for (int k = 0; k < K; ++k) fit.set(k, fs[k].Gt, fs[k].active);
     if (!fit.upload(st)) return false;
-    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, fit.d_tab, chunks, ppt, fit.d_part, st);
-    else launch_sums<double>(p, (const double*)x_dev, fit.d_tab, chunks, ppt, fit.d_part, st);
+    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, fit.d_tab.as<double>(), chunks, ppt, fit.d_part.as<double>(), st);
+    else launch_sums<double>(p, (const double*)x_dev, fit.d_tab.as<double>(), chunks, ppt, fit.d_part.as<double>(), st);
     return fit.reduce_and_fetch(chunks, st);
   };
 
@@ -248,24 +245,20 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
     }
   };
 
-  if (rc == SRMAP_OK) {
-    if (!pass()) fail(SRMAP_EHIP, "pass failed");
+  if (!pass()) return fail(SRMAP_EHIP, "pass failed");
+  for (int k = 0; k < K; ++k) {
+    FrameState& f = fs[k];
+    std::copy(fit.sums(k), fit.sums(k) + kSums, f.S);
+    f.e0 = f.S[27];
+    f.passes = 1;
+    if (k == 0) { f.active = false; f.passes = 0; f.status = 0; continue; }  // the gauge
+    propose(f);
   }
-  if (rc == SRMAP_OK) {
-    for (int k = 0; k < K; ++k) {
-      FrameState& f = fs[k];
-      std::copy(fit.sums(k), fit.sums(k) + kSums, f.S);
-      f.e0 = f.S[27];
-      f.passes = 1;
-      if (k == 0) { f.active = false; f.passes = 0; f.status = 0; continue; }  // the gauge
-      propose(f);
-    }
-  }
-  while (rc == SRMAP_OK) {
+  for (;;) {
     bool any = false;
     for (int k = 0; k < K; ++k) any = any || fs[k].active;
     if (!any) break;
-    if (!pass()) { fail(SRMAP_EHIP, "pass failed"); break; }
+    if (!pass()) return fail(SRMAP_EHIP, "pass failed");
     for (int k = 0; k < K; ++k) {
       FrameState& f = fs[k];
       if (!f.active) continue;
@@ -285,8 +278,6 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
       propose(f);
     }
   }
-
-  if (rc) return rc;
 
   std::vector<double> result((size_t)K * 6);
   for (int k = 0; k < K; ++k) std::copy(fs[k].F.m, fs[k].F.m + 6, result.data() + 6 * (size_t)k);
@@ -314,5 +305,5 @@ extern "C" int srmap_refine_motion(srmap_problem* p, const double* x_host, const
     return set_error(p->ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
   if (int rc = stage_host_x(p, x_host)) return rc;
-  return srmap_refine_motion_device(p, p->d_x, p->ctx->stream, options, affine_2x3_out, quality_out, normal_equations_out);
+  return srmap_refine_motion_device(p, p->d_x.as(), p->ctx->stream, options, affine_2x3_out, quality_out, normal_equations_out);
 }

@@ -96,16 +96,16 @@ template <typename T>
 bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
-  const T* y = (const T*)(p->d_obs_raw ? p->d_obs_raw : p->d_obs);  // always the RAW frames: the fit is absolute
+  const T* y = (p->d_obs_raw ? p->d_obs_raw : p->d_obs).as<const T>();  // always the RAW frames: the fit is absolute
   const MotionArgs<T> ma = motion_args<T>(p);
   return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->d_dw)
-      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, (const T*)p->d_dw, g, ma,
-                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
+      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->d_dw.as<const T>(), g, ma,
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part);
     else
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, ma,
-                         (const T*)p->d_blur, p->d_col_map, p->d_row_map, ppt, d_part);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part);
   });
 }
 
@@ -114,14 +114,14 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
 // p->d_obs <- the raw frames (p->d_obs_raw) normalised by the parameters in force (p->d_photo), enqueued on st
 int photometric_normalise(srmap_problem* p, hipStream_t st) {
   const size_t total = p->lr_count(), per_frame = total / p->geo.K;
-  if (!p->d_obs) SRMAP_HIP(p->ctx, hipMalloc(&p->d_obs, std::max<size_t>(total * p->elem(), 8)));
+  if (!p->d_obs) SRMAP_HIP(p->ctx, p->d_obs.alloc(total * p->elem()));
   const dim3 grid((unsigned)((total + 255) / 256));
   if (p->dtype == SRMAP_F32)
-    hipLaunchKernelGGL(k_photometric_normalise<float>, grid, dim3(256), 0, st, (const float*)p->d_obs_raw, (float*)p->d_obs,
-                       p->d_photo, per_frame, total);
+    hipLaunchKernelGGL(k_photometric_normalise<float>, grid, dim3(256), 0, st, p->d_obs_raw.as<const float>(), p->d_obs.as<float>(),
+                       p->d_photo.as<double>(), per_frame, total);
   else
-    hipLaunchKernelGGL(k_photometric_normalise<double>, grid, dim3(256), 0, st, (const double*)p->d_obs_raw,
-                       (double*)p->d_obs, p->d_photo, per_frame, total);
+    hipLaunchKernelGGL(k_photometric_normalise<double>, grid, dim3(256), 0, st, p->d_obs_raw.as<const double>(),
+                       p->d_obs.as<double>(), p->d_photo.as<double>(), per_frame, total);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
@@ -142,37 +142,28 @@ extern "C" int srmap_problem_set_photometric(srmap_problem* p, const double* gai
     }
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   // what the call needs first: a failed allocation leaves the problem as it was
-  double* d_photo = p->d_photo;
-  void* d_norm = nullptr;
+  DevBuf photo, norm;
   const bool move_raw = gain_bias && !p->d_obs_raw && p->d_obs;  // the first parameters of a problem that holds frames
-  if (gain_bias) {
-    if ((!d_photo && hipMalloc((void**)&d_photo, (size_t)K * 2 * sizeof(double)) != hipSuccess) ||
-        (move_raw && hipMalloc(&d_norm, std::max<size_t>(p->lr_count() * p->elem(), 8)) != hipSuccess)) {
-      (void)hipGetLastError();
-      if (d_photo && d_photo != p->d_photo) (void)hipFree(d_photo);
-      return set_error(ctx, SRMAP_ENOMEM, "photometric: allocation failed");
-    }
-  }
+  if (gain_bias && ((!p->d_photo && photo.alloc((size_t)K * 2 * sizeof(double)) != hipSuccess) ||
+                    (move_raw && norm.alloc(p->lr_count() * p->elem()) != hipSuccess)))
+    return set_error(ctx, SRMAP_ENOMEM, "photometric: allocation failed");
   // evaluations in flight read the observations: drain them before the buffer changes
-  if (p->use_stream) SRMAP_HIP(ctx, hipStreamSynchronize(p->use_stream));
-  SRMAP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (int rc = model_drain(p)) return rc;
   if (!gain_bias) {
-    if (p->d_obs_raw) {  // the raw buffer again, bit for bit
-      if (p->d_obs) (void)hipFree(p->d_obs);
-      p->d_obs = p->d_obs_raw;
-      p->d_obs_raw = nullptr;
-    }
+    // d_obs_raw -> d_obs: the raw buffer again, bit for bit (the normalised copy is freed); setting parameters moves it back
+    if (p->d_obs_raw) p->d_obs = std::move(p->d_obs_raw);
+    p->d_photo.reset();
     p->photometric = false;
     p->photo.clear();
     return SRMAP_OK;
   }
-  p->d_photo = d_photo;
-  SRMAP_HIP(ctx, hipMemcpy(p->d_photo, gain_bias, (size_t)K * 2 * sizeof(double), hipMemcpyHostToDevice));
+  if (photo) p->d_photo = std::move(photo);
+  SRMAP_HIP(ctx, hipMemcpy(p->d_photo.as<double>(), gain_bias, (size_t)K * 2 * sizeof(double), hipMemcpyHostToDevice));
   p->photo.assign(gain_bias, gain_bias + (size_t)K * 2);
   p->photometric = true;
   if (move_raw) {
-    p->d_obs_raw = p->d_obs;
-    p->d_obs = d_norm;
+    p->d_obs_raw = std::move(p->d_obs);
+    p->d_obs = std::move(norm);
   }
   if (p->d_obs_raw && p->have_obs) {
     int rc = photometric_normalise(p, ctx->stream);
@@ -245,15 +236,12 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
   const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
   const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
   FitPass fit;
-  if (!fit.alloc(K, kPhotoSums, (size_t)K * chunks * kPhotoSums)) {
-    (void)hipGetLastError();
-    return set_error(ctx, SRMAP_ENOMEM, "photometric fit: allocation failed");
-  }
+  if (!fit.alloc(K, kPhotoSums, (size_t)K * chunks * kPhotoSums)) return set_error(ctx, SRMAP_ENOMEM, "photometric fit: allocation failed");
   const AffineMap identity = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};  // the table carries the active flags alone here
   for (int k = 0; k < K; ++k) fit.set(k, identity, true);
   if (!fit.upload(st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: upload failed");
-  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, (const float*)x_dev, chunks, ppt, fit.d_part, st)
-                              : launch_sums<double>(p, (const double*)x_dev, chunks, ppt, fit.d_part, st)))
+  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, (const float*)x_dev, chunks, ppt, fit.d_part.as<double>(), st)
+                              : launch_sums<double>(p, (const double*)x_dev, chunks, ppt, fit.d_part.as<double>(), st)))
     return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)motion_kind(p));
   if (!fit.reduce_and_fetch(chunks, st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: pass failed");
 
@@ -291,5 +279,5 @@ extern "C" int srmap_fit_photometric(srmap_problem* p, const double* x_host, con
   if (rc) return rc;
   rc = stage_host_x(p, x_host);
   if (rc) return rc;
-  return srmap_fit_photometric_device(p, p->d_x, p->ctx->stream, options, gain_bias_out, quality_out, sums_out);
+  return srmap_fit_photometric_device(p, p->d_x.as(), p->ctx->stream, options, gain_bias_out, quality_out, sums_out);
 }

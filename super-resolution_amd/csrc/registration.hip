@@ -115,21 +115,17 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
   const int L = (int)lw.size();
   size_t pyr_elems = 0;
   for (int l = 0; l < L; ++l) pyr_elems += (size_t)lw[l] * lh[l];
-  double *d_a = nullptr, *d_b = nullptr, *d_part = nullptr;
   // coarsest level: shifts up to a quarter of the frame (16 coarse pixels at most); finer levels: +-1
   const int R0 = std::max(4, std::min(16, std::min(lw.back(), lh.back()) / 4)), n1c = 2 * R0 + 1;
   const int max_chunks = 64;
   const size_t part_elems = std::max((size_t)n1c * n1c * max_chunks * 2, (size_t)height * 6);
   std::vector<double> h_part(part_elems);
-  int rc = SRMAP_OK;
-  auto fail = [&](int code, const char* what) {
-    rc = set_error(ctx, code, "registration: %s", what);
-  };
-  if (hipMalloc((void**)&d_a, pyr_elems * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_b, pyr_elems * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d_part, part_elems * sizeof(double)) != hipSuccess) {
-    fail(SRMAP_ENOMEM, "device allocation failed");
-  }
+  auto fail = [&](int code, const char* what) { return set_error(ctx, code, "registration: %s", what); };
+  DevBuf pyr_a, pyr_b, part;  // every pass below ends in a stream wait before its sums are read
+  if (pyr_a.alloc(pyr_elems * sizeof(double)) != hipSuccess || pyr_b.alloc(pyr_elems * sizeof(double)) != hipSuccess ||
+      part.alloc(part_elems * sizeof(double)) != hipSuccess)
+    return fail(SRMAP_ENOMEM, "device allocation failed");
+  double *const d_a = pyr_a.as<double>(), *const d_b = pyr_b.as<double>(), *const d_part = part.as<double>();
   std::vector<size_t> off(L, 0);
   for (int l = 1; l < L; ++l) off[l] = off[l - 1] + (size_t)lw[l - 1] * lh[l - 1];
   auto build = [&](double* base, const double* host) -> bool {
@@ -137,13 +133,13 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
     for (int l = 1; l < L; ++l) launch_down2_stack(base + off[l - 1], base + off[l], lw[l - 1], lh[l - 1], 1, st);
     return hipGetLastError() == hipSuccess;
   };
-  if (rc == SRMAP_OK && !build(d_a, images_host)) fail(SRMAP_EHIP, "pyramid of the reference frame failed");
+  if (!build(d_a, images_host)) return fail(SRMAP_EHIP, "pyramid of the reference frame failed");
 
-  for (int i = 1; i < num_images && rc == SRMAP_OK; ++i) {
-    if (!build(d_b, images_host + (size_t)i * npx)) { fail(SRMAP_EHIP, "pyramid failed"); break; }
+  for (int i = 1; i < num_images; ++i) {
+    if (!build(d_b, images_host + (size_t)i * npx)) return fail(SRMAP_EHIP, "pyramid failed");
     // ---- integer shift, coarse to fine ----
     int sx = 0, sy = 0;
-    for (int l = L - 1; l >= 0 && rc == SRMAP_OK; --l) {
+    for (int l = L - 1; l >= 0; --l) {
       const int R = (l == L - 1) ? R0 : 1, n1 = 2 * R + 1, ncand = n1 * n1;
       if (l != L - 1) { sx *= 2; sy *= 2; }
       const int chunks = std::min(max_chunks, std::max(1, lh[l] / 16));
@@ -151,7 +147,7 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
       hipLaunchKernelGGL(k_ssd_candidates, dim3(ncand, chunks), dim3(256), 0, st, d_a + off[l], d_b + off[l], lw[l], lh[l],
                          sx - R, sy - R, n1, rpc, d_part);
       if (hipMemcpyAsync(h_part.data(), d_part, (size_t)ncand * chunks * 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) { fail(SRMAP_EHIP, "candidate search failed"); break; }
+          hipStreamSynchronize(st) != hipSuccess) return fail(SRMAP_EHIP, "candidate search failed");
       double best = 0.0; int bi = -1;
       std::vector<double> msd(ncand, -1.0);
       for (int cnd = 0; cnd < ncand; ++cnd) {
@@ -162,12 +158,11 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
         msd[cnd] = m;
         if (bi < 0 || m < best) { best = m; bi = cnd; }
       }
-      if (bi < 0) { fail(SRMAP_EINVAL, "Could not determine motion shift between images."); break; }  // registration.cpp:193-194
+      if (bi < 0) return fail(SRMAP_EINVAL, "Could not determine motion shift between images.");  // registration.cpp:193-194
       if (l == L - 1 && quality_out) quality_out[2 * i] = search_separation(msd.data(), n1, bi);
       sx = sx - R + bi % n1;
       sy = sy - R + bi / n1;
     }
-    if (rc != SRMAP_OK) break;
     // ---- sub-pixel refinement at full resolution ----
     double dx = sx, dy = sy, rms = -1.0;
     for (int it = 0; it < 20; ++it) {
@@ -176,7 +171,7 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
       if (rows < 4 || width - 2 * margin < 4) break;  // keep the integer estimate
       hipLaunchKernelGGL(k_lk_sums, dim3(rows), dim3(256), 0, st, d_a, d_b, width, height, dx, dy, margin, d_part);
       if (hipMemcpyAsync(h_part.data(), d_part, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) { fail(SRMAP_EHIP, "refinement failed"); break; }
+          hipStreamSynchronize(st) != hipSuccess) return fail(SRMAP_EHIP, "refinement failed");
       double S[6] = {0, 0, 0, 0, 0, 0};
       for (int r = 0; r < rows; ++r)
         for (int q = 0; q < 6; ++q) S[q] += h_part[(size_t)r * 6 + q];
@@ -193,8 +188,5 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
     shifts_xy_out[2 * i + 1] = dy;
     if (quality_out) quality_out[2 * i + 1] = rms;
   }
-  if (d_a) (void)hipFree(d_a);
-  if (d_b) (void)hipFree(d_b);
-  if (d_part) (void)hipFree(d_part);
-  return rc;
+  return SRMAP_OK;
 }

@@ -187,54 +187,46 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   const int seed_chunks = seed_window ? std::min(kMaxSeedChunks, ch - 2 * R) : 0;
   const size_t part_elems = std::max((size_t)nf * chunks_of(height) * kGnSums, seed ? (size_t)nf * ncand * seed_chunks : 0);
 
-  double* d_pyr = nullptr;
+  DevBuf pyr;
   FitPass fit;  // its d_part also takes the seed search's partials
-  int rc = SRMAP_OK;
-  auto fail = [&](int code, const char* what) { rc = set_error(ctx, code, "affine registration: %s", what); };
-  if (hipMalloc((void**)&d_pyr, off[L] * sizeof(double)) != hipSuccess || !fit.alloc(nf, kGnSums, part_elems)) {
-    (void)hipGetLastError();
-    fail(SRMAP_ENOMEM, "allocation failed");
-  }
+  auto fail = [&](int code, const char* what) { return set_error(ctx, code, "affine registration: %s", what); };
+  if (pyr.alloc(off[L] * sizeof(double)) != hipSuccess || !fit.alloc(nf, kGnSums, part_elems)) return fail(SRMAP_ENOMEM, "allocation failed");
+  double* const d_pyr = pyr.as<double>();
 
   // ---- pyramids of the whole stack, once ----
-  if (rc == SRMAP_OK) {
-    if (hipMemcpyAsync(d_pyr, images_host, (size_t)K * width * height * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
-      fail(SRMAP_EHIP, "upload failed");
-    for (int l = 1; l < L && rc == SRMAP_OK; ++l)
-      launch_down2_stack(d_pyr + off[l - 1], d_pyr + off[l], lw[l - 1], lh[l - 1], K, st);
-    if (rc == SRMAP_OK && hipGetLastError() != hipSuccess) fail(SRMAP_EHIP, "pyramid failed");
-  }
+  if (hipMemcpyAsync(d_pyr, images_host, (size_t)K * width * height * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+    return fail(SRMAP_EHIP, "upload failed");
+  for (int l = 1; l < L; ++l) launch_down2_stack(d_pyr + off[l - 1], d_pyr + off[l], lw[l - 1], lh[l - 1], K, st);
+  if (hipGetLastError() != hipSuccess) return fail(SRMAP_EHIP, "pyramid failed");
 
   // ---- seed: integer translation at the coarsest level, or the caller's matrices taken down the pyramid ----
-  if (rc == SRMAP_OK && !seed) {
+  if (!seed) {
     for (int f = 0; f < nf; ++f)
       for (int l = 1; l < L; ++l) F[f] = to_coarser(F[f]);
-  } else if (rc == SRMAP_OK) {
+  } else {
     for (int f = 0; f < nf; ++f) { std::copy(ident, ident + 6, F[f].m); sep[f] = 0.0; }
     if (seed_window) {
       const int rows = ch - 2 * R, rpc = (rows + seed_chunks - 1) / seed_chunks;
       const size_t n = (size_t)nf * ncand * seed_chunks;
       std::vector<double> h_part(n);
-      hipLaunchKernelGGL(k_ssd_window, dim3(ncand, seed_chunks, nf), dim3(256), 0, st, d_pyr + off[L - 1], cw, ch, R, rpc, fit.d_part);
+      hipLaunchKernelGGL(k_ssd_window, dim3(ncand, seed_chunks, nf), dim3(256), 0, st, d_pyr + off[L - 1], cw, ch, R, rpc, fit.d_part.as<double>());
       if (hipGetLastError() != hipSuccess ||
-          hipMemcpyAsync(h_part.data(), fit.d_part, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        fail(SRMAP_EHIP, "coarse search failed");
-      } else {
-        const double count = (double)rows * (cw - 2 * R);
-        std::vector<double> msd(ncand);
-        for (int f = 0; f < nf; ++f) {
-          int bi = 0;
-          for (int c = 0; c < ncand; ++c) {
-            double s = 0.0;
-            for (int k = 0; k < seed_chunks; ++k) s += h_part[((size_t)f * ncand + c) * seed_chunks + k];
-            msd[c] = s / count;
-            if (msd[c] < msd[bi]) bi = c;  // the first minimum in row-major order wins
-          }
-          sep[f] = search_separation(msd.data(), n1, bi);
-          F[f].m[2] = bi % n1 - R;
-          F[f].m[5] = bi / n1 - R;
+          hipMemcpyAsync(h_part.data(), fit.d_part.as<double>(), n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return fail(SRMAP_EHIP, "coarse search failed");
+      const double count = (double)rows * (cw - 2 * R);
+      std::vector<double> msd(ncand);
+      for (int f = 0; f < nf; ++f) {
+        int bi = 0;
+        for (int c = 0; c < ncand; ++c) {
+          double s = 0.0;
+          for (int k = 0; k < seed_chunks; ++k) s += h_part[((size_t)f * ncand + c) * seed_chunks + k];
+          msd[c] = s / count;
+          if (msd[c] < msd[bi]) bi = c;  // the first minimum in row-major order wins
         }
+        sep[f] = search_separation(msd.data(), n1, bi);
+        F[f].m[2] = bi % n1 - R;
+        F[f].m[5] = bi / n1 - R;
       }
     }
   }
@@ -245,29 +237,26 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
     for (int f = 0; f < nf; ++f) fit.set(f, F[f], active[f] != 0);
     const int chunks = chunks_of(lh[l]), rpc = (lh[l] - 2 + chunks - 1) / chunks;
     if (!fit.upload(st)) return false;
-    hipLaunchKernelGGL(k_affine_gn_sums, dim3(chunks, nf), dim3(256), 0, st, d_pyr + off[l], lw[l], lh[l], rpc, fit.d_tab, fit.d_part);
+    hipLaunchKernelGGL(k_affine_gn_sums, dim3(chunks, nf), dim3(256), 0, st, d_pyr + off[l], lw[l], lh[l], rpc, fit.d_tab.as<double>(), fit.d_part.as<double>());
     return fit.reduce_and_fetch(chunks, st);
   };
 
   // ---- Gauss-Newton, coarse to fine ----
   std::vector<int> iters(nf, 0);
-  for (int l = L - 1; l >= 0 && rc == SRMAP_OK; --l) {
+  for (int l = L - 1; l >= 0; --l) {
     std::fill(active.begin(), active.end(), 1);
-    for (int it = 0; it < opt.max_iterations && rc == SRMAP_OK; ++it) {
+    for (int it = 0; it < opt.max_iterations; ++it) {
       if (std::find(active.begin(), active.end(), 1) == active.end()) break;
-      if (!pass(l)) { fail(SRMAP_EHIP, "Gauss-Newton pass failed"); break; }
+      if (!pass(l)) return fail(SRMAP_EHIP, "Gauss-Newton pass failed");
       for (int f = 0; f < nf; ++f) {
         if (!active[f]) continue;
         const double* S = fit.sums(f);
         ++iters[f];
-        if (S[25] < 0.25 * lw[l] * lh[l]) { fail(SRMAP_EINVAL, "Could not determine motion between images."); break; }
+        if (S[25] < 0.25 * lw[l] * lh[l]) return fail(SRMAP_EINVAL, "Could not determine motion between images.");
         double delta[6];
         if (!solve_step(S, delta)) { active[f] = 0; continue; }  // no texture: this level keeps F
         const AffineMap Fn = compose_with_inverse(F[f], delta, lw[l], lh[l]);
-        if (!all_finite(Fn) || deviation(Fn) > kAffineMaxDeviation) {
-          fail(SRMAP_EINVAL, "Could not determine motion between images.");
-          break;
-        }
+        if (!all_finite(Fn) || deviation(Fn) > kAffineMaxDeviation) return fail(SRMAP_EINVAL, "Could not determine motion between images.");
         const double step = corner_displacement(Fn, F[f], lw[l], lh[l]);
         F[f] = Fn;
         if (step < opt.step_tolerance) active[f] = 0;
@@ -278,26 +267,23 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   }
 
   // ---- residual at the result (full resolution), output ----
-  if (rc == SRMAP_OK && quality_out) {
+  if (quality_out) {
     std::fill(active.begin(), active.end(), 1);
-    if (!pass(0)) fail(SRMAP_EHIP, "residual pass failed");
+    if (!pass(0)) return fail(SRMAP_EHIP, "residual pass failed");
   }
-  if (rc == SRMAP_OK) {
-    for (int f = 0; f < nf; ++f) {
-      double* o = affine_2x3_out + 6 * (f + 1);
-      std::copy(F[f].m, F[f].m + 6, o);
-      o[2] *= opt.hr_scale;
-      o[5] *= opt.hr_scale;
-      if (quality_out) {
-        const double* S = fit.sums(f);
-        double* q = quality_out + 4 * (f + 1);
-        q[0] = sep[f];
-        q[1] = S[25] > 0 ? std::sqrt(S[24] / S[25]) : 0.0;
-        q[2] = S[25] / ((double)width * height);
-        q[3] = iters[f];
-      }
+  for (int f = 0; f < nf; ++f) {
+    double* o = affine_2x3_out + 6 * (f + 1);
+    std::copy(F[f].m, F[f].m + 6, o);
+    o[2] *= opt.hr_scale;
+    o[5] *= opt.hr_scale;
+    if (quality_out) {
+      const double* S = fit.sums(f);
+      double* q = quality_out + 4 * (f + 1);
+      q[0] = sep[f];
+      q[1] = S[25] > 0 ? std::sqrt(S[24] / S[25]) : 0.0;
+      q[2] = S[25] / ((double)width * height);
+      q[3] = iters[f];
     }
   }
-  if (d_pyr) (void)hipFree(d_pyr);
-  return rc;
+  return SRMAP_OK;
 }

@@ -327,13 +327,9 @@ __global__ __launch_bounds__(256) void k_flow_prior(const double* __restrict__ v
 
 // the device buffers of one call
 struct FlowBuffers {
-  double *pyr = nullptr, *grad = nullptr, *u = nullptr, *v = nullptr, *hr = nullptr, *valid = nullptr, *rec = nullptr, *tab = nullptr;
-  void *field = nullptr, *prior = nullptr;  // srmap_problem_register_flow: the field and the prior in the problem's dtype
-  ~FlowBuffers() {
-    for (void* p : {(void*)pyr, (void*)grad, (void*)u, (void*)v, (void*)hr, (void*)valid, (void*)rec, (void*)tab, field, prior})
-      if (p) (void)hipFree(p);
-  }
-  static bool get(double** p, size_t elems) { return hipMalloc((void**)p, std::max<size_t>(elems, 1) * sizeof(double)) == hipSuccess; }
+  DevBuf pyr, grad, u, v, hr, valid, rec, tab;  // doubles
+  DevBuf field, prior;  // srmap_problem_register_flow: the field and the prior in the problem's dtype
+  static bool get(DevBuf* b, size_t elems) { return b->alloc(elems * sizeof(double)) == hipSuccess; }
 };
 
 // Where the stack of one call comes from and where its results go.  Exactly one source: images_host (pageable doubles,
@@ -425,44 +421,43 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
   if (!FlowBuffers::get(&b.pyr, off[L]) || !FlowBuffers::get(&b.grad, goff[L]) || !FlowBuffers::get(&b.u, (size_t)nf * 2 * n) ||
       !FlowBuffers::get(&b.v, (size_t)nf * 2 * n) || (own_hr && !FlowBuffers::get(&b.hr, (size_t)nf * 2 * N)) ||
       (own_valid && !FlowBuffers::get(&b.valid, (size_t)nf * n)) || !FlowBuffers::get(&b.rec, rec_elems) ||
-      !FlowBuffers::get(&b.tab, h_tab.size())) {
-    (void)hipGetLastError();
+      !FlowBuffers::get(&b.tab, h_tab.size()))
     return set_error(ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
-  }
-  double* hr = own_hr ? b.hr : io.flow_dev + 2 * N;
-  double* valid = own_valid ? b.valid : io.valid_dev + n;
+  double *const pyr = b.pyr.as<double>(), *const grad = b.grad.as<double>(), *const rec = b.rec.as<double>(), *const tab = b.tab.as<double>();
+  double* hr = own_hr ? b.hr.as<double>() : io.flow_dev + 2 * N;
+  double* valid = own_valid ? b.valid.as<double>() : io.valid_dev + n;
 
   // ---- pyramids of the whole stack and the gradient planes of frame 0, once ----
   if (io.images_host) {
-    SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, io.images_host, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, st));
+    SRMAP_HIP(ctx, hipMemcpyAsync(pyr, io.images_host, (size_t)K * n * sizeof(double), hipMemcpyHostToDevice, st));
   } else if (io.images_dev) {
-    SRMAP_HIP(ctx, hipMemcpyAsync(b.pyr, io.images_dev, (size_t)K * n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SRMAP_HIP(ctx, hipMemcpyAsync(pyr, io.images_dev, (size_t)K * n * sizeof(double), hipMemcpyDeviceToDevice, st));
   } else {
     const srmap_problem* p = io.problem;
     if (p->dtype == SRMAP_F32)
-      hipLaunchKernelGGL(k_flow_plane<float>, dim3(blocks_of(n), K), dim3(256), 0, st, (const float*)p->d_obs, p->geo.C, io.channel, n, b.pyr);
+      hipLaunchKernelGGL(k_flow_plane<float>, dim3(blocks_of(n), K), dim3(256), 0, st, p->d_obs.as<const float>(), p->geo.C, io.channel, n, pyr);
     else
-      hipLaunchKernelGGL(k_flow_plane<double>, dim3(blocks_of(n), K), dim3(256), 0, st, (const double*)p->d_obs, p->geo.C, io.channel, n, b.pyr);
+      hipLaunchKernelGGL(k_flow_plane<double>, dim3(blocks_of(n), K), dim3(256), 0, st, p->d_obs.as<const double>(), p->geo.C, io.channel, n, pyr);
   }
   if (cnt_blocks > 0)
-    hipLaunchKernelGGL(k_flow_count_nonfinite, dim3(cnt_blocks, K), dim3(256), 0, st, (const double*)b.pyr, n, b.rec + rec_quality);
+    hipLaunchKernelGGL(k_flow_count_nonfinite, dim3(cnt_blocks, K), dim3(256), 0, st, (const double*)pyr, n, rec + rec_quality);
   if (nf > 0) {
-    for (int l = 1; l < L; ++l) launch_down2_stack(b.pyr + off[l - 1], b.pyr + off[l], lw[l - 1], lh[l - 1], K, st);
+    for (int l = 1; l < L; ++l) launch_down2_stack(pyr + off[l - 1], pyr + off[l], lw[l - 1], lh[l - 1], K, st);
     for (int l = 0; l < L; ++l) {
       const size_t nl = (size_t)lw[l] * lh[l];
-      hipLaunchKernelGGL(k_flow_gradients, dim3(blocks_of(nl)), dim3(256), 0, st, b.pyr + off[l], lw[l], lh[l], b.grad + goff[l],
-                         b.grad + goff[l] + nl);
+      hipLaunchKernelGGL(k_flow_gradients, dim3(blocks_of(nl)), dim3(256), 0, st, pyr + off[l], lw[l], lh[l], grad + goff[l],
+                         grad + goff[l] + nl);
     }
 
     // ---- start at the coarsest level ----
-    double *u = b.u, *v = b.v;
+    double *u = b.u.as<double>(), *v = b.v.as<double>();
     {
       const int cw = lw[L - 1], ch = lh[L - 1];
       if (h_tab.empty()) {
         SRMAP_HIP(ctx, hipMemsetAsync(u, 0, (size_t)nf * 2 * cw * ch * sizeof(double), st));
       } else {
-        SRMAP_HIP(ctx, hipMemcpyAsync(b.tab, h_tab.data(), h_tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_flow_affine_start, dim3(blocks_of((size_t)cw * ch), nf), dim3(256), 0, st, b.tab, cw, ch, u);
+        SRMAP_HIP(ctx, hipMemcpyAsync(tab, h_tab.data(), h_tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_flow_affine_start, dim3(blocks_of((size_t)cw * ch), nf), dim3(256), 0, st, tab, cw, ch, u);
       }
     }
 
@@ -471,7 +466,7 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
       const int w = lw[l], h = lh[l];
       const size_t nl = (size_t)w * h;
       for (int it = 0; it < opt.warps; ++it) {
-        launch_lk_pass(b.pyr + off[l], b.grad + goff[l], b.grad + goff[l] + nl, b.pyr + off[l], u, v, w, h, nf, opt.window_radius,
+        launch_lk_pass(pyr + off[l], grad + goff[l], grad + goff[l] + nl, pyr + off[l], u, v, w, h, nf, opt.window_radius,
                        opt.damping, st);
         hipLaunchKernelGGL(k_flow_smooth, dim3(blocks_of(nl), 2 * nf), dim3(256), 0, st, v, u, w, h, opt.smooth_radius);
       }
@@ -483,11 +478,11 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
     }
 
     // ---- the HR field, the mask and the quality records ----
-    double* rec_fin = b.rec;
-    double* rec_max = b.rec + (size_t)nf * 2 * fin_blocks;
+    double* rec_fin = rec;
+    double* rec_max = rec + (size_t)nf * 2 * fin_blocks;
     hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, hr, s * width, s * height, 0.0,
                        (double)s, (double)s);
-    hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, b.pyr, b.pyr, u, width, height, opt.valid_margin, valid,
+    hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, pyr, pyr, u, width, height, opt.valid_margin, valid,
                        rec_fin);
     hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, hr, s * width, s * height, rec_max);
   }
@@ -496,7 +491,7 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
   std::vector<double> h_rec(rec_elems);
   if (io.flow_host) SRMAP_HIP(ctx, hipMemcpyAsync(io.flow_host + 2 * N, hr, (size_t)nf * 2 * N * sizeof(double), hipMemcpyDeviceToHost, st));
   if (io.valid_host) SRMAP_HIP(ctx, hipMemcpyAsync(io.valid_host + n, valid, (size_t)nf * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (rec_elems > 0) SRMAP_HIP(ctx, hipMemcpyAsync(h_rec.data(), b.rec, rec_elems * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (rec_elems > 0) SRMAP_HIP(ctx, hipMemcpyAsync(h_rec.data(), rec, rec_elems * sizeof(double), hipMemcpyDeviceToHost, st));
   SRMAP_HIP(ctx, hipStreamSynchronize(st));
 
   for (int k = 0; k < K && cnt_blocks > 0; ++k) {
@@ -530,15 +525,12 @@ template <typename T>
 int problem_stage(srmap_problem* p, FlowBuffers& b, bool want_prior, hipStream_t st) {
   const Geometry& g = p->geo;
   const size_t n = (size_t)g.w * g.h, N = (size_t)g.W * g.H, total = (size_t)g.K * 2 * N;
-  if (hipMalloc(&b.field, std::max<size_t>(total, 1) * sizeof(T)) != hipSuccess ||
-      (want_prior && hipMalloc(&b.prior, std::max<size_t>(p->lr_count(), 1) * sizeof(T)) != hipSuccess)) {
-    (void)hipGetLastError();
+  if (b.field.alloc(total * sizeof(T)) != hipSuccess || (want_prior && b.prior.alloc(p->lr_count() * sizeof(T)) != hipSuccess))
     return set_error(p->ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
-  }
   const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)std::max(1, p->ctx->num_cus) * 16);
-  hipLaunchKernelGGL(k_flow_round<T>, dim3(std::max(1u, blocks)), dim3(256), 0, st, (const double*)b.hr, 2 * N, total, (T*)b.field);
+  hipLaunchKernelGGL(k_flow_round<T>, dim3(std::max(1u, blocks)), dim3(256), 0, st, b.hr.as<const double>(), 2 * N, total, b.field.as<T>());
   if (want_prior)
-    hipLaunchKernelGGL(k_flow_prior<T>, dim3(blocks_of(n), g.C, g.K), dim3(256), 0, st, (const double*)b.valid, n, (T*)b.prior);
+    hipLaunchKernelGGL(k_flow_prior<T>, dim3(blocks_of(n), g.C, g.K), dim3(256), 0, st, b.valid.as<const double>(), n, b.prior.as<T>());
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
@@ -619,6 +611,6 @@ extern "C" int srmap_problem_register_flow(srmap_problem* p, int channel, const 
   const bool prior = install_prior != 0;
   if (int rc = p->dtype == SRMAP_F32 ? problem_stage<float>(p, b, prior, st) : problem_stage<double>(p, b, prior, st)) return rc;
   // a refused field leaves the motion -- and the prior -- the problem had
-  if (int rc = srmap_problem_set_flow_device(p, b.field, st)) return rc;
-  return prior ? srmap_set_data_prior_device(p, b.prior, st) : SRMAP_OK;
+  if (int rc = srmap_problem_set_flow_device(p, b.field.as(), st)) return rc;
+  return prior ? srmap_set_data_prior_device(p, b.prior.as(), st) : SRMAP_OK;
 }

@@ -149,10 +149,10 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, Eval
     const bool mine = ztile_reg_band_ok(p, terms);
     if (p->band_comm != (const void*)c || p->band_terms != terms || p->band_gen != p->plan_gen) {
       double flag = mine ? 0.0 : 1.0;  // max over the ranks of "I cannot" == 0  <=>  every rank can
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_cost + 7, &flag, sizeof(double), hipMemcpyHostToDevice, st));
-      rc = comm_allreduce(c, p->d_cost + 7, 1, SRMAP_F64, 1, st);
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_cost.as<double>() + 7, &flag, sizeof(double), hipMemcpyHostToDevice, st));
+      rc = comm_allreduce(c, p->d_cost.as<double>() + 7, 1, SRMAP_F64, 1, st);
       if (rc) return rc;
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(&flag, p->d_cost + 7, sizeof(double), hipMemcpyDeviceToHost, st));
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(&flag, p->d_cost.as<double>() + 7, sizeof(double), hipMemcpyDeviceToHost, st));
       SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
       p->band_all = flag == 0.0;
       p->band_comm = c; p->band_terms = terms; p->band_gen = p->plan_gen;
@@ -166,14 +166,14 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, Eval
       t = terms & SRMAP_TERM_DATA;
     }
     if (t == 0) {
-      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
+      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost.as<double>(), 0, sizeof(double), st));
       if (g_dev) SRMAP_HIP(p->ctx, hipMemsetAsync(g_dev, 0, p->hr_count() * es, st));
     } else {
       rc = eval_dispatch(p, req, out, t, x_dev, g_dev, st);
     }
     if (rc) return rc;
     // the north-star's gradient all-reduce, with the cost in the same group (one launch)
-    return comm_allreduce_grad_cost(c, g_dev, g_dev ? p->hr_count() : 0, p->dtype, p->d_cost, st);
+    return comm_allreduce_grad_cost(c, g_dev, g_dev ? p->hr_count() : 0, p->dtype, p->d_cost.as<double>(), st);
   }
   if (mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
     const int fgs = (mode == SRMAP_SHARD_GRID && sd->frame_groups > 1) ? sd->frame_groups : 1;
@@ -185,7 +185,7 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, Eval
     char* gown = g_dev ? (char*)g_dev + (size_t)sd->own_ch0 * N * es : nullptr;
     if (t == 0) {
       rc = SRMAP_OK;
-      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost, 0, sizeof(double), st));
+      SRMAP_HIP(p->ctx, hipMemsetAsync(p->d_cost.as<double>(), 0, sizeof(double), st));
       if (gown) SRMAP_HIP(p->ctx, hipMemsetAsync(gown, 0, cnt * es, st));
     } else {
       rc = eval_dispatch(p, req, out, t, (char*)x_dev + (size_t)sd->own_ch0 * N * es, gown, st);
@@ -218,10 +218,10 @@ int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_sh
   if (rc) return rc;
   if (cost) {
     if (mode == SRMAP_SHARD_ROWS || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
-      rc = comm_allreduce(comm, p->d_cost, 1, SRMAP_F64, 0, st);
+      rc = comm_allreduce(comm, p->d_cost.as<double>(), 1, SRMAP_F64, 0, st);
       if (rc) return rc;
     }
-    SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost, sizeof(double), hipMemcpyDeviceToHost, st));
+    SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost.as<double>(), sizeof(double), hipMemcpyDeviceToHost, st));
     SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
   }
   return SRMAP_OK;

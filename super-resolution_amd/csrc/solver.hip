@@ -70,6 +70,16 @@ struct DeviceCG {
   unsigned* lb_ticket = nullptr;
   double* lb_host = nullptr;
   static constexpr int kLbRows = 2 + 5 * kLbfgsMaxM;
+  // the owners of every device buffer above (the typed members are views: the passes swap them); freed with the solver
+  std::vector<DevBuf> mem;
+  PinnedBuf lb_host_mem;
+  template <typename U>
+  int dev_alloc(U** view, size_t bytes) {
+    mem.emplace_back();
+    SRMAP_HIP(p->ctx, mem.back().alloc(bytes));
+    *view = mem.back().template as<U>();
+    return SRMAP_OK;
+  }
 
   // Wait until the kernel that was given tag `want` (default: the last one handed out) has published its results (see
   // k_finish): poll the host-mapped word, fall back to a stream synchronisation after ~2 s (also surfaces asynchronous
@@ -99,11 +109,12 @@ struct DeviceCG {
 
   int alloc() {
     T** v[] = {&x, &g, &xk, &dk, &dn, &d, &gp};
-    for (T** q : v) SRMAP_HIP(p->ctx, hipMalloc((void**)q, n * sizeof(T)));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&part, sizeof(double) * 3 * kRedBlocks));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&dscal, sizeof(double) * 16));
+    for (T** q : v)
+      if (int rc = dev_alloc(q, n * sizeof(T))) return rc;
+    if (int rc = dev_alloc(&part, sizeof(double) * 3 * kRedBlocks)) return rc;
+    if (int rc = dev_alloc(&dscal, sizeof(double) * 16)) return rc;
     SRMAP_HIP(p->ctx, hipMemsetAsync(dscal, 0, sizeof(double) * 16, st));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&gran, sizeof(double) * 3 * kRedBlocks));
+    if (int rc = dev_alloc(&gran, sizeof(double) * 3 * kRedBlocks)) return rc;
     SRMAP_HIP(p->ctx, hipMemsetD32Async((hipDeviceptr_t)gran, (int)kArm32, 2 * 3 * kRedBlocks, st));
     // sharded evaluations write only the owned part of g: the vector kernels run over all n elements, so everything
     // they combine starts defined (the halo values never enter a reduction, and x halos are re-exchanged)
@@ -111,7 +122,7 @@ struct DeviceCG {
     for (T* q : z) SRMAP_HIP(p->ctx, hipMemsetAsync(q, 0, n * sizeof(T), st));
     int rc = ensure_staging(p->ctx);
     if (rc) return rc;
-    hs = p->ctx->h_scal;
+    hs = p->ctx->h_scal.as<double>();
     SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
     hs[13] = 0.0;  // time-out word of this solve (Fin::timeout_host, ZArgs::to_host)
     tag = hs[15];  // tags keep increasing across solves of one context: a stale word can never match
@@ -119,27 +130,18 @@ struct DeviceCG {
   }
   int alloc_lbfgs(int m) {
     lb_m = m;
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&S, (size_t)m * n * sizeof(T)));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&Y, (size_t)m * n * sizeof(T)));
+    if (int rc = dev_alloc(&S, (size_t)m * n * sizeof(T))) return rc;
+    if (int rc = dev_alloc(&Y, (size_t)m * n * sizeof(T))) return rc;
     SRMAP_HIP(p->ctx, hipMemsetAsync(S, 0, (size_t)m * n * sizeof(T), st));
     SRMAP_HIP(p->ctx, hipMemsetAsync(Y, 0, (size_t)m * n * sizeof(T), st));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&lb_part, sizeof(double) * kLbRows * kRedBlocks));
-    SRMAP_HIP(p->ctx, hipMalloc((void**)&lb_ticket, sizeof(unsigned)));
+    if (int rc = dev_alloc(&lb_part, sizeof(double) * kLbRows * kRedBlocks)) return rc;
+    if (int rc = dev_alloc(&lb_ticket, sizeof(unsigned))) return rc;
     SRMAP_HIP(p->ctx, hipMemsetAsync(lb_ticket, 0, sizeof(unsigned), st));
-    SRMAP_HIP(p->ctx, hipHostMalloc((void**)&lb_host, sizeof(double) * kLbRows, hipHostMallocMapped | hipHostMallocCoherent));
+    SRMAP_HIP(p->ctx, lb_host_mem.alloc(sizeof(double) * kLbRows, hipHostMallocMapped | hipHostMallocCoherent));
+    lb_host = lb_host_mem.as<double>();
     for (int i = 0; i < kLbRows; ++i) lb_host[i] = 0.0;
     SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
     return SRMAP_OK;
-  }
-  void release() {
-    T* v[] = {x, g, xk, dk, dn, d, gp, S, Y};
-    for (T* q : v) if (q) (void)hipFree(q);
-    if (lb_part) (void)hipFree(lb_part);
-    if (lb_ticket) (void)hipFree(lb_ticket);
-    if (lb_host) (void)hipHostFree(lb_host);
-    if (part) (void)hipFree(part);
-    if (gran) (void)hipFree(gran);
-    if (dscal) (void)hipFree(dscal);
   }
   int copy(T* dst, const T* src) {
     SRMAP_HIP(p->ctx, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
@@ -153,7 +155,7 @@ struct DeviceCG {
     Fin f{};
     if (fused()) {
       tag += 1.0;
-      f.gran = gran; f.out = out ? out : hs; f.cost_src = with_cost ? (const double*)p->d_cost : nullptr;
+      f.gran = gran; f.out = out ? out : hs; f.cost_src = with_cost ? (const double*)p->d_cost.as<double>() : nullptr;
       f.timeout_flag = dscal + 15; f.timeout_host = hs + 13;
       f.pub_src = pub_src; f.pub_dst = pub_dst; f.pub_n = pub_n;
       f.tag_slot = hs + 15; f.tag = tag;
@@ -166,7 +168,7 @@ struct DeviceCG {
     const int cnt = rows + (with_cost ? 1 : 0);
     if (!fused()) {
       tag += 1.0;
-      launch_finish(part, nb(), rows, max0 ? 1 : 0, dscal, with_cost ? (const double*)p->d_cost : nullptr, nullptr, 0.0, st);
+      launch_finish(part, nb(), rows, max0 ? 1 : 0, dscal, with_cost ? (const double*)p->d_cost.as<double>() : nullptr, nullptr, 0.0, st);
       int rc = SRMAP_OK;
       if (max0) {
         rc = comm_allreduce(comm, dscal, 1, SRMAP_F64, 1, st);
@@ -245,9 +247,9 @@ struct DeviceCG {
     }
     tag += 1.0;
     if (!reduce_scalars) {
-      launch_publish(hs, p->d_cost, 2, hs + 15, tag, st);
+      launch_publish(hs, p->d_cost.as<double>(), 2, hs + 15, tag, st);
     } else {
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(dscal, p->d_cost, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(dscal, p->d_cost.as<double>(), 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
       int rc = comm_allreduce(comm, dscal, 2, SRMAP_F64, 0, st);
       if (rc) return rc;
       launch_publish(hs, dscal, 2, hs + 15, tag, st);
@@ -270,7 +272,7 @@ struct DeviceCG {
       tag += 1.0;
       dir_tag = tag;
       f.gran = gran; f.out = dscal + 4; f.timeout_flag = dscal + 15; f.timeout_host = hs + 13;
-      if (publish_cost) { f.pub_src = (const double*)p->d_cost; f.pub_dst = hs; f.pub_n = 1; }  // hs[0] = f
+      if (publish_cost) { f.pub_src = (const double*)p->d_cost.as<double>(); f.pub_dst = hs; f.pub_n = 1; }  // hs[0] = f
       f.tag_slot = hs + 15; f.tag = tag;
     }
     double* npub = fused() ? hs + 8 : (double*)nullptr;
@@ -721,16 +723,12 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       double own = mode == SRMAP_SHARD_ROWS ? (double)C * geo.W * (shard->own_row1 - shard->own_row0)
                                             : (grid_replica ? 0.0 : (double)(shard->own_ch1 - shard->own_ch0) * N);
       // every rank must derive the same thresholds: total parameter count = sum of the owned counts
-      double* tmp = nullptr;
-      SRMAP_HIP(p->ctx, hipMalloc((void**)&tmp, sizeof(double)));
-      SRMAP_HIP(p->ctx, hipMemcpy(tmp, &own, sizeof(double), hipMemcpyHostToDevice));
-      int rc0 = comm_allreduce(comm, tmp, 1, SRMAP_F64, 0, p->ctx->stream);
-      if (rc0 == SRMAP_OK) {
-        SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
-        SRMAP_HIP(p->ctx, hipMemcpy(&own, tmp, sizeof(double), hipMemcpyDeviceToHost));
-      }
-      (void)hipFree(tmp);
-      if (rc0) return rc0;
+      DevBuf tmp;
+      SRMAP_HIP(p->ctx, tmp.alloc(sizeof(double)));
+      SRMAP_HIP(p->ctx, hipMemcpy(tmp.as(), &own, sizeof(double), hipMemcpyHostToDevice));
+      if (int rc0 = comm_allreduce(comm, tmp.as(), 1, SRMAP_F64, 0, p->ctx->stream)) return rc0;
+      SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+      SRMAP_HIP(p->ctx, hipMemcpy(&own, tmp.as(), sizeof(double), hipMemcpyDeviceToHost));
       params = (double)(int)own;
     }
     const double scale = params * lambda_sum;
@@ -758,10 +756,8 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   if (rc == SRMAP_OK && huber && !p->d_dw) rc = set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
   // IRLS weights live in the problem's RegSpec (full [C][H][W]); make sure they exist.
   for (int r = 0; r < p->nreg && rc == SRMAP_OK; ++r) {
-    if (!p->reg[r].weights) {
-      hipError_t e = hipMalloc(&p->reg[r].weights, p->hr_count() * sizeof(T));
-      if (e != hipSuccess) rc = set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed");
-    }
+    if (!p->reg[r].weights && p->reg[r].weights.alloc(p->hr_count() * sizeof(T)) != hipSuccess)
+      rc = set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed");
   }
   for (int round = 0; round < rounds && rc == SRMAP_OK; ++round) {
     const int c0 = round * per_split;
@@ -772,7 +768,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     if (rc) break;
     // w <- 1  (irls_map_solver.cpp:66-74)
     for (int r = 0; r < p->nreg; ++r)
-      launch_fill<T>((T*)p->reg[r].weights + (size_t)c0 * N, T(1), npts, st);
+      launch_fill<T>(p->reg[r].weights.as<T>() + (size_t)c0 * N, T(1), npts, st);
     if (huber) {  // the data weights of this round's channels likewise ([K][C][h][w]: one run per frame)
       if (p->d_prior) {  // a prior on the weights is what they are reset to
         rc = reset_data_weights(p, c0, per_split, st);
@@ -780,7 +776,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       } else {
         const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
         for (int k = 0; k < geo.K; ++k)
-          launch_fill<T>((T*)p->d_dw + ((size_t)k * C + c0) * nl, T(1), run, st);
+          launch_fill<T>(p->d_dw.as<T>() + ((size_t)k * C + c0) * nl, T(1), run, st);
       }
     }
     double previous_cost = INFINITY;
@@ -804,7 +800,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       rc = shard_exchange_x(p, comm, mode == SRMAP_SHARD_NONE ? nullptr : shard, cg.x, st);
       if (rc) break;
       for (int r = 0; r < p->nreg; ++r) {
-        rc = launch_reg_weights<T>(p, vg, p->reg[r], (const T*)cg.x, (T*)p->reg[r].weights + (size_t)c0 * N, st);
+        rc = launch_reg_weights<T>(p, vg, p->reg[r], (const T*)cg.x, p->reg[r].weights.as<T>() + (size_t)c0 * N, st);
         if (rc) break;
       }
       if (rc) break;
@@ -828,7 +824,6 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   rep.wait_seconds = cg.wait_seconds;
   rep.waits = cg.waits;
   rc = cg.recover_timeout(rc);
-  cg.release();
   if (report) *report = rep;
   return rc;
 }
@@ -858,7 +853,6 @@ static int cg_trace_typed(srmap_problem* p, int lbfgs_m, double epsg, double eps
   if (rc == SRMAP_OK) rc = lbfgs_m > 0 ? run_lbfgs(cg, epsg, epsf, epsx, maxits, &cr, &tr) : run_cg(cg, epsg, epsf, epsx, maxits, &cr, &tr);
   if (rc == SRMAP_OK) rc = convert_download(p, cg.x, x_out, npts, cg.st);
   rc = cg.recover_timeout(rc);
-  cg.release();
   if (rc) return rc;
   if (iterations) *iterations = cr.its;
   if (nfev) *nfev = cr.nfev;

@@ -298,7 +298,7 @@ __global__ void k_axpy_out(T* __restrict__ dst, const T* __restrict__ a, const T
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dst[i] = a[i] + alpha * b[i];
 }
-// the same, four elements per thread (16 / 32-byte requests; hipMalloc'ed vectors are aligned): element by element the
+// the same, four elements per thread (16 / 32-byte requests; device allocations are aligned): element by element the
 // same expression, so the same bits
 template <typename T>
 __global__ __launch_bounds__(256) void k_axpy_out4(T* __restrict__ dst, const T* __restrict__ a, const T* __restrict__ b, T alpha,

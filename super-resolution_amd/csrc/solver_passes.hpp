@@ -2,7 +2,7 @@
 // where it leaves its sums (Fin), and one host launcher per pass.
 //
 // Every launcher picks the kernel instance itself: V = 16 / sizeof(T) consecutive elements per thread and step when n is
-// a multiple of V (one 16-byte request; the vectors are hipMalloc'ed: aligned), else V = 1.  The element-wise results are
+// a multiple of V (one 16-byte request; the vectors are device allocations: aligned), else V = 1.  The element-wise results are
 // the same bits either way, the dot-product partials are summed in a different order (tests/test_gpu_parity.py: the PSNR
 // bar of the ill-conditioned small cases follows the CPU reference path's own sensitivity to a last-bit perturbation,
 // DESIGN.md section 4).  The reducing passes take their grid (nb <= kRedBlocks workgroups of 256) from the caller: it
@@ -32,6 +32,7 @@ struct Owned {
     return row >= r0 && row < r1;
   }
 };
+static_assert(std::is_trivially_copyable_v<Owned>, "a kernel argument: no owner inside");
 
 // Where a pass leaves its reduced sums.  gran == nullptr: the two-launch scheme (block partials in `part`, k_finish
 // follows; sharded solves, whose sums go through an all-reduce first).  Otherwise the last block of the grid reduces:
@@ -49,6 +50,7 @@ struct Fin {
   double* timeout_flag;   // sticky device word: a reduction gave up waiting for a block (srmap_solve reports it)
   double* timeout_host;   // the same event for the host at once (host-mapped word: wait_tag ends the solve on it)
 };
+static_assert(std::is_trivially_copyable_v<Fin>, "a kernel argument: no owner inside");
 
 // dn = -g + beta dk (dk may be null; beta_dev, when given, overrides beta); sums {max|dn|, dn.dn, g.dn}
 template <typename T>

@@ -99,23 +99,23 @@ static void nearest_map(int src_len, int dst_len, std::vector<int>* map) {
 }
 
 template <typename T>
-static int upload_warps(srmap_problem* p, const std::vector<WarpTaps<double>>& src, void** dst) {
+static int upload_warps(srmap_problem* p, const std::vector<WarpTaps<double>>& src, DevBuf* dst) {
   std::vector<WarpTaps<T>> tmp(src.size());
   for (size_t i = 0; i < src.size(); ++i) {
     tmp[i].ox = src[i].ox; tmp[i].oy = src[i].oy; tmp[i].ntaps = src[i].ntaps; tmp[i].fx = src[i].fx;
     tmp[i].ytab = src[i].ytab;
     for (int t = 0; t < 4; ++t) tmp[i].w[t] = (T)src[i].w[t];
   }
-  SRMAP_HIP(p->ctx, hipMalloc(dst, sizeof(WarpTaps<T>) * tmp.size()));
-  SRMAP_HIP(p->ctx, hipMemcpy(*dst, tmp.data(), sizeof(WarpTaps<T>) * tmp.size(), hipMemcpyHostToDevice));
+  SRMAP_HIP(p->ctx, dst->alloc(sizeof(WarpTaps<T>) * tmp.size()));
+  SRMAP_HIP(p->ctx, hipMemcpy(dst->as(), tmp.data(), sizeof(WarpTaps<T>) * tmp.size(), hipMemcpyHostToDevice));
   return SRMAP_OK;
 }
 
 template <typename T>
-static int upload_array(srmap_problem* p, const std::vector<double>& src, void** dst) {
+static int upload_array(srmap_problem* p, const std::vector<double>& src, DevBuf* dst) {
   std::vector<T> tmp(src.begin(), src.end());
-  SRMAP_HIP(p->ctx, hipMalloc(dst, sizeof(T) * tmp.size()));
-  SRMAP_HIP(p->ctx, hipMemcpy(*dst, tmp.data(), sizeof(T) * tmp.size(), hipMemcpyHostToDevice));
+  SRMAP_HIP(p->ctx, dst->alloc(sizeof(T) * tmp.size()));
+  SRMAP_HIP(p->ctx, hipMemcpy(dst->as(), tmp.data(), sizeof(T) * tmp.size(), hipMemcpyHostToDevice));
   return SRMAP_OK;
 }
 
@@ -136,12 +136,12 @@ constexpr size_t kStageBytes = 4u << 20;
 
 int ensure_staging(srmap_ctx* ctx) {
   for (int i = 0; i < 2; ++i) {
-    if (!ctx->h_stage[i]) SRMAP_HIP(ctx, hipHostMalloc(&ctx->h_stage[i], kStageBytes, hipHostMallocDefault));
+    if (!ctx->h_stage[i]) SRMAP_HIP(ctx, ctx->h_stage[i].alloc(kStageBytes, hipHostMallocDefault));
     if (!ctx->h_event[i]) SRMAP_HIP(ctx, hipEventCreateWithFlags(&ctx->h_event[i], hipEventDisableTiming));
   }
   if (!ctx->h_scal) {
-    SRMAP_HIP(ctx, hipHostMalloc((void**)&ctx->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    for (int i = 0; i < 16; ++i) ctx->h_scal[i] = 0.0;
+    SRMAP_HIP(ctx, ctx->h_scal.alloc(16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    for (int i = 0; i < 16; ++i) ctx->h_scal.as<double>()[i] = 0.0;
   }
   return SRMAP_OK;
 }
@@ -154,8 +154,8 @@ static int staged_h2d(srmap_ctx* ctx, void* dev, const void* host, size_t bytes,
     const size_t nb = bytes - off < kStageBytes ? bytes - off : kStageBytes;
     const int b = i & 1;
     if (i >= 2) SRMAP_HIP(ctx, hipEventSynchronize(ctx->h_event[b]));  // chunk i-2 has left the buffer
-    std::memcpy(ctx->h_stage[b], (const char*)host + off, nb);
-    SRMAP_HIP(ctx, hipMemcpyAsync((char*)dev + off, ctx->h_stage[b], nb, hipMemcpyHostToDevice, st));
+    std::memcpy(ctx->h_stage[b].as(), (const char*)host + off, nb);
+    SRMAP_HIP(ctx, hipMemcpyAsync((char*)dev + off, ctx->h_stage[b].as(), nb, hipMemcpyHostToDevice, st));
     SRMAP_HIP(ctx, hipEventRecord(ctx->h_event[b], st));
   }
   SRMAP_HIP(ctx, hipStreamSynchronize(st));
@@ -169,13 +169,13 @@ static int staged_d2h(srmap_ctx* ctx, void* host, const void* dev, size_t bytes,
   for (size_t i = 0; i <= nchunks; ++i) {
     if (i < nchunks) {  // chunk i -> pinned buffer (its previous content, chunk i-2, was copied out below)
       const size_t off = i * kStageBytes, nb = bytes - off < kStageBytes ? bytes - off : kStageBytes;
-      SRMAP_HIP(ctx, hipMemcpyAsync(ctx->h_stage[i & 1], (const char*)dev + off, nb, hipMemcpyDeviceToHost, st));
+      SRMAP_HIP(ctx, hipMemcpyAsync(ctx->h_stage[i & 1].as(), (const char*)dev + off, nb, hipMemcpyDeviceToHost, st));
       SRMAP_HIP(ctx, hipEventRecord(ctx->h_event[i & 1], st));
     }
     if (i >= 1) {  // chunk i-1 -> caller, while chunk i is on the wire
       const size_t off = (i - 1) * kStageBytes, nb = bytes - off < kStageBytes ? bytes - off : kStageBytes;
       SRMAP_HIP(ctx, hipEventSynchronize(ctx->h_event[(i - 1) & 1]));
-      std::memcpy((char*)host + off, ctx->h_stage[(i - 1) & 1], nb);
+      std::memcpy((char*)host + off, ctx->h_stage[(i - 1) & 1].as(), nb);
     }
   }
   return SRMAP_OK;
@@ -183,45 +183,34 @@ static int staged_d2h(srmap_ctx* ctx, void* host, const void* dev, size_t bytes,
 
 int convert_upload(srmap_problem* p, const double* host, void* dev, size_t n, hipStream_t st) {
   if (p->dtype == SRMAP_F64) return staged_h2d(p->ctx, dev, host, n * 8, st);
-  double* tmp = nullptr;
-  SRMAP_HIP(p->ctx, hipMalloc((void**)&tmp, n * 8));
-  int rc = staged_h2d(p->ctx, tmp, host, n * 8, st);
-  hipError_t e = hipSuccess;
-  if (rc == SRMAP_OK) {
-    hipLaunchKernelGGL(k_from_double<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       tmp, (float*)dev, n);
-    e = hipStreamSynchronize(st);
-  }
-  (void)hipFree(tmp);
-  if (rc) return rc;
-  SRMAP_HIP(p->ctx, e);
+  DevBuf tmp;  // read by the conversion kernel: the stream is waited for before it goes
+  SRMAP_HIP(p->ctx, tmp.alloc(n * 8));
+  if (int rc = staged_h2d(p->ctx, tmp.as(), host, n * 8, st)) return rc;
+  hipLaunchKernelGGL(k_from_double<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     tmp.as<const double>(), (float*)dev, n);
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
   return SRMAP_OK;
 }
 
 int convert_download(srmap_problem* p, const void* dev, double* host, size_t n, hipStream_t st) {
   if (p->dtype == SRMAP_F64) return staged_d2h(p->ctx, host, dev, n * 8, st);
-  double* tmp = nullptr;
-  SRMAP_HIP(p->ctx, hipMalloc((void**)&tmp, n * 8));
+  DevBuf tmp;
+  SRMAP_HIP(p->ctx, tmp.alloc(n * 8));
   hipLaunchKernelGGL(k_to_double<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     (const float*)dev, tmp, n);
-  int rc = staged_d2h(p->ctx, host, tmp, n * 8, st);
-  (void)hipFree(tmp);
-  return rc;
+                     (const float*)dev, tmp.as<double>(), n);
+  return staged_d2h(p->ctx, host, tmp.as(), n * 8, st);
 }
 
-static int ensure(srmap_problem* p, void** buf, size_t bytes) {
-  if (*buf) return SRMAP_OK;
-  SRMAP_HIP(p->ctx, hipMalloc(buf, bytes ? bytes : 8));
+static int ensure(srmap_problem* p, DevBuf* buf, size_t bytes) {
+  if (!*buf) SRMAP_HIP(p->ctx, buf->alloc(bytes));
   return SRMAP_OK;
 }
 
 static int ensure_partials(srmap_problem* p, size_t n) {
   n *= 2;  // second half: partials of g.d (EvalReq::dvec)
   if (p->partials_cap >= n) return SRMAP_OK;
-  if (p->d_partials) (void)hipFree(p->d_partials);
-  p->d_partials = nullptr;
   p->partials_cap = 0;
-  SRMAP_HIP(p->ctx, hipMalloc((void**)&p->d_partials, n * sizeof(double)));
+  SRMAP_HIP(p->ctx, p->d_partials.alloc(n * sizeof(double)));
   p->partials_cap = n;
   return SRMAP_OK;
 }
@@ -262,7 +251,7 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover this geometry");
   int nparts = 0;
   if (ztile) {
-    rc = launch_eval_ztile<T>(p, req, out, geo, c0, terms, x, g, p->d_partials, &nparts, st);
+    rc = launch_eval_ztile<T>(p, req, out, geo, c0, terms, x, g, p->d_partials.as<double>(), &nparts, st);
     if (rc) return rc;
   } else {
     bool g_written = false;
@@ -270,12 +259,12 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
       rc = ensure(p, &p->d_resid, p->lr_count() * sizeof(T));
       if (rc) return rc;
       int nb = 0;
-      rc = launch_forward_direct<T>(p, geo, x, (const T*)p->d_obs, p->geo.C, c0,
-                                    (T*)p->d_resid, 0, geo.K, p->d_partials + nparts, &nb, st, (const T*)p->d_dw);
+      rc = launch_forward_direct<T>(p, geo, x, p->d_obs.as<const T>(), p->geo.C, c0,
+                                    p->d_resid.as<T>(), 0, geo.K, p->d_partials.as<double>() + nparts, &nb, st, p->d_dw.as<const T>());
       if (rc) return rc;
       nparts += nb;
       if (g) {
-        rc = launch_gather_direct<T>(p, geo, (const T*)p->d_resid, g, 0, geo.K,
+        rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K,
                                      2.0 * geo.s * geo.s, false, st);
         if (rc) return rc;
         g_written = true;
@@ -293,21 +282,21 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
         if (!onfly) {
           rc = ensure(p, &p->d_regvals, p->hr_count() * sizeof(T));
           if (rc) return rc;
-          rc = launch_reg_values<T>(p, geo, rs, x, (T*)p->d_regvals, st);
+          rc = launch_reg_values<T>(p, geo, rs, x, p->d_regvals.as<T>(), st);
           if (rc) return rc;
         }
         int nb = 0;
-        const T* wts = rs.weights ? (const T*)rs.weights + (size_t)c0 * N : nullptr;
+        const T* wts = rs.weights ? rs.weights.as<const T>() + (size_t)c0 * N : nullptr;
         rc = launch_reg_gradient_direct<T>(p, geo, rs, x, wts, rs.lambda,
-                                           onfly ? nullptr : (const T*)p->d_regvals, g, true,
-                                           p->d_partials + nparts, &nb, st);
+                                           onfly ? nullptr : p->d_regvals.as<const T>(), g, true,
+                                           p->d_partials.as<double>() + nparts, &nb, st);
         if (rc) return rc;
         nparts += nb;
       }
     }
   }
   if (ztile && nparts == 0) return SRMAP_OK;  // reduced inside the last kernel of the evaluation
-  return launch_reduce_partials(p, p->d_partials, nparts, p->d_cost, st);
+  return launch_reduce_partials(p, p->d_partials.as<double>(), nparts, p->d_cost.as<double>(), st);
 }
 
 // ---- stream ordering of the problem's device state (include/srmap.h, "Streams") ----
@@ -344,20 +333,29 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
   return eval_typed<double>(p, req, out, terms, (const double*)x, (double*)g, st);
 }
 
-// Weights or the loss changed whether the problem is robust(): the tile plan has another form then (ztile_plan)
-static void replan_if(srmap_problem* p, bool was_robust) {
-  if (p->robust() == was_robust) return;
+int model_drain(srmap_problem* p) {
+  if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  return SRMAP_OK;
+}
+
+void model_replan(srmap_problem* p) {
   p->plan_gen++;
   if (ztile_plan(p)) ztile_preload(p);
+}
+
+// Weights or the loss changed whether the problem is robust(): the tile plan has another form then (ztile_plan)
+static void replan_if(srmap_problem* p, bool was_robust) {
+  if (p->robust() != was_robust) model_replan(p);
 }
 
 // allocate the data weights (all ones) if there are none
 static int ensure_data_weights(srmap_problem* p, hipStream_t st) {
   if (p->d_dw) return SRMAP_OK;
   const size_t n = p->lr_count();
-  SRMAP_HIP(p->ctx, hipMalloc(&p->d_dw, n * p->elem()));
-  if (p->dtype == SRMAP_F32) launch_fill<float>((float*)p->d_dw, 1.f, n, st);
-  else launch_fill<double>((double*)p->d_dw, 1.0, n, st);
+  SRMAP_HIP(p->ctx, p->d_dw.alloc(n * p->elem()));
+  if (p->dtype == SRMAP_F32) launch_fill<float>(p->d_dw.as<float>(), 1.f, n, st);
+  else launch_fill<double>(p->d_dw.as<double>(), 1.0, n, st);
   SRMAP_HIP(p->ctx, hipGetLastError());
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
   return SRMAP_OK;
@@ -369,12 +367,12 @@ static int update_data_weights_typed(srmap_problem* p, int c0, int C, const T* x
   if (C > 0) geo.C = C; else c0 = 0;
   int rc = ensure_partials(p, partials_needed(p));
   if (rc) return rc;
-  rc = launch_forward_residual<T>(p, geo, c0, x, p->d_partials, st);  // d_resid: [K][geo.C][h][w], unweighted
+  rc = launch_forward_residual<T>(p, geo, c0, x, p->d_partials.as<double>(), st);  // d_resid: [K][geo.C][h][w], unweighted
   if (rc) return rc;
   const size_t nl = (size_t)geo.w * geo.h;
-  return launch_huber_weights<T>(p, (const T*)p->d_resid, (T*)p->d_dw + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
+  return launch_huber_weights<T>(p, p->d_resid.as<const T>(), p->d_dw.as<T>() + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
                                  (size_t)geo.C * nl, (size_t)p->geo.C * nl, p->huber_delta, st,
-                                 p->d_prior ? (const T*)p->d_prior + (size_t)c0 * nl : nullptr);
+                                 p->d_prior ? p->d_prior.as<const T>() + (size_t)c0 * nl : nullptr);
 }
 
 int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st) {
@@ -399,9 +397,9 @@ int reset_data_weights(srmap_problem* p, int c0, int C, hipStream_t st) {
   for (int k = 0; k < g.K; ++k) {  // [K][C][h][w]: one run per frame
     const size_t off = ((size_t)k * g.C + c0) * nl;
     if (p->d_prior)
-      SRMAP_HIP(p->ctx, hipMemcpyAsync((char*)p->d_dw + off * e, (const char*)p->d_prior + off * e, run * e, hipMemcpyDeviceToDevice, st));
-    else if (p->dtype == SRMAP_F32) launch_fill<float>((float*)p->d_dw + off, 1.f, run, st);
-    else launch_fill<double>((double*)p->d_dw + off, 1.0, run, st);
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_dw.as<char>() + off * e, p->d_prior.as<const char>() + off * e, run * e, hipMemcpyDeviceToDevice, st));
+    else if (p->dtype == SRMAP_F32) launch_fill<float>(p->d_dw.as<float>() + off, 1.f, run, st);
+    else launch_fill<double>(p->d_dw.as<double>() + off, 1.0, run, st);
   }
   return SRMAP_OK;
 }
@@ -410,7 +408,7 @@ int recover_reduction_timeout(srmap_problem* p, double* host_word) {
   // a late workgroup may still publish into the granules: re-initialise them only behind everything in flight
   SRMAP_HIP(p->ctx, hipDeviceSynchronize());
   ztile_rearm(p);
-  if (p->d_cost) SRMAP_HIP(p->ctx, hipMemset(p->d_cost + 6, 0, sizeof(double)));
+  if (p->d_cost.as<double>()) SRMAP_HIP(p->ctx, hipMemset(p->d_cost.as<double>() + 6, 0, sizeof(double)));
   if (host_word) *host_word = 0.0;
   return SRMAP_OK;
 }
@@ -447,8 +445,8 @@ int affine_records(srmap_ctx* ctx, int K, const double* a23, std::vector<double>
 int stage_host_x(srmap_problem* p, const double* x_host) {
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   const size_t n = p->hr_count();
-  if (!p->d_x) SRMAP_HIP(p->ctx, hipMalloc(&p->d_x, n * p->elem()));
-  return convert_upload(p, x_host, p->d_x, n, p->ctx->stream);
+  if (int rc = ensure(p, &p->d_x, n * p->elem())) return rc;
+  return convert_upload(p, x_host, p->d_x.as(), n, p->ctx->stream);
 }
 
 }  // namespace srmap
@@ -459,6 +457,8 @@ int stage_host_x(srmap_problem* p, const double* x_host) {
 extern "C" {
 
 const char* srmap_version(void) { return "srmap 0.1 (HIP, gfx950)"; }
+
+long long srmap_live_allocations(void) { return g_live_allocations.load(); }
 
 int srmap_ctx_create(int device_id, srmap_ctx** out) {
   if (!out) return SRMAP_EINVAL;
@@ -487,13 +487,10 @@ int srmap_ctx_create(int device_id, srmap_ctx** out) {
 void srmap_ctx_destroy(srmap_ctx* ctx) {
   if (!ctx) return;
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  for (int i = 0; i < 2; ++i) {
-    if (ctx->h_stage[i]) (void)hipHostFree(ctx->h_stage[i]);
+  for (int i = 0; i < 2; ++i)
     if (ctx->h_event[i]) (void)hipEventDestroy(ctx->h_event[i]);
-  }
-  if (ctx->h_scal) (void)hipHostFree(ctx->h_scal);
   blas_release(ctx);
-  delete ctx;
+  delete ctx;  // and its pinned staging
 }
 
 const char* srmap_last_error(const srmap_ctx* ctx) { return ctx ? ctx->error.c_str() : "null context"; }
@@ -567,12 +564,12 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
     p->bwd_warps.resize(g.K);
     auto upload_ytab = [&](const std::vector<int>& t, WarpTaps<double>* wt) -> int {
       if (t.empty()) return SRMAP_OK;
-      int* d = nullptr;
-      if (hipMalloc((void**)&d, sizeof(int) * t.size()) != hipSuccess ||
-          hipMemcpy(d, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
+      DevBuf d;
+      if (d.alloc(sizeof(int) * t.size()) != hipSuccess ||
+          hipMemcpy(d.as(), t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
         return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed");
-      p->d_ytabs.push_back(d);
-      wt->ytab = d;
+      wt->ytab = d.as<const int>();
+      p->d_ytabs.push_back(std::move(d));
       return SRMAP_OK;
     };
     std::vector<int> ytab;
@@ -613,18 +610,16 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
     rc = upload_array<double>(p, p->blur2d, &p->d_blur); if (rc) return fail(rc);
     rc = upload_array<double>(p, p->blur2d_t, &p->d_blur_t); if (rc) return fail(rc);
   }
-  if (hipMalloc((void**)&p->d_col_map, sizeof(int) * g.w) != hipSuccess ||
-      hipMalloc((void**)&p->d_row_map, sizeof(int) * g.h) != hipSuccess ||
-      hipMalloc((void**)&p->d_cost, sizeof(double) * 8) != hipSuccess)
+  if (p->d_col_map.alloc(sizeof(int) * g.w) != hipSuccess || p->d_row_map.alloc(sizeof(int) * g.h) != hipSuccess ||
+      p->d_cost.alloc(sizeof(double) * 8) != hipSuccess)
     return fail(set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed"));
-  (void)hipMemcpy(p->d_col_map, cmap.data(), sizeof(int) * g.w, hipMemcpyHostToDevice);
-  (void)hipMemcpy(p->d_row_map, rmap.data(), sizeof(int) * g.h, hipMemcpyHostToDevice);
+  (void)hipMemcpy(p->d_col_map.as<int>(), cmap.data(), sizeof(int) * g.w, hipMemcpyHostToDevice);
+  (void)hipMemcpy(p->d_row_map.as<int>(), rmap.data(), sizeof(int) * g.h, hipMemcpyHostToDevice);
   // everything above used blocking copies; d_cost is first touched by kernels on caller streams: clear it on the
   // context's (non-blocking) stream and wait, so no legacy-stream work is left behind the creation
-  if (hipMemsetAsync(p->d_cost, 0, sizeof(double) * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+  if (hipMemsetAsync(p->d_cost.as<double>(), 0, sizeof(double) * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
     return fail(set_error(ctx, SRMAP_EHIP, "clearing the cost scalars failed"));
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);
+  model_replan(p);
   *out = p;
   return SRMAP_OK;
 }
@@ -632,13 +627,8 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
 void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
-  void* bufs[] = {p->d_fwd_warps, p->d_bwd_warps, p->d_blur, p->d_blur_t, p->d_col_map, p->d_row_map,
-                  p->d_affine, p->d_flow, p->d_flow_seed, p->d_obs, p->d_obs_raw, p->d_photo, p->d_resid, p->d_dw, p->d_prior, p->d_dw_user, p->d_regvals, p->d_x, p->d_g, p->d_tmp, p->d_partials, p->d_cost};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) (void)hipFree(p->reg[r].weights);
-  for (int* t : p->d_ytabs) (void)hipFree(t);
   if (p->state_ev) (void)hipEventDestroy(p->state_ev);
-  delete p;
+  delete p;  // and every device buffer it owns
 }
 
 int srmap_problem_set_impl(srmap_problem* p, int impl) {
@@ -659,25 +649,22 @@ int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) 
     if (rc) return rc;  // the problem keeps the motion it had
   }
   // evaluations in flight read the records: drain them before the buffer changes
-  if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
-  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  if (int rc = model_drain(p)) return rc;
   if (affine_2x3) {
-    if (!p->d_affine) SRMAP_HIP(p->ctx, hipMalloc((void**)&p->d_affine, recs.size() * sizeof(double)));
-    SRMAP_HIP(p->ctx, hipMemcpy(p->d_affine, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = ensure(p, &p->d_affine, recs.size() * sizeof(double))) return rc;
+    SRMAP_HIP(p->ctx, hipMemcpy(p->d_affine.as<double>(), recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
     p->affine_recs.swap(recs);
     p->affine = true;
   } else {
     p->affine = false;
     p->affine_recs.clear();
+    p->d_affine.reset();
   }
   // alternatives: an affine motion replaces a displacement field, and NULL restores the created motion
-  if (p->d_flow) (void)hipFree(p->d_flow);
-  if (p->d_flow_seed) (void)hipFree(p->d_flow_seed);
-  p->d_flow = nullptr;
-  p->d_flow_seed = nullptr;
+  p->d_flow.reset();
+  p->d_flow_seed.reset();
   p->flow = false;
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);  // "not covered" while an affine motion is set
+  model_replan(p);  // "not covered" while an affine motion is set
   return SRMAP_OK;
 }
 
@@ -706,29 +693,22 @@ int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* tap
     k2t = p->created_blur2d_t;
   }
   // the new tables first: a failed allocation leaves the problem as it was
-  void *nb = nullptr, *nbt = nullptr;
+  DevBuf nb, nbt;
   int rc = p->dtype == SRMAP_F32 ? upload_array<float>(p, k2, &nb) : upload_array<double>(p, k2, &nb);
   if (rc == SRMAP_OK) rc = p->dtype == SRMAP_F32 ? upload_array<float>(p, k2t, &nbt) : upload_array<double>(p, k2t, &nbt);
-  if (rc) {
-    if (nb) (void)hipFree(nb);
-    if (nbt) (void)hipFree(nbt);
-    return rc;
-  }
+  if (rc) return rc;
   // evaluations in flight read the old tables: drain them before the buffers change
-  if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
-  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
-  if (p->d_blur) (void)hipFree(p->d_blur);
-  if (p->d_blur_t) (void)hipFree(p->d_blur_t);
-  p->d_blur = nb;
-  p->d_blur_t = nbt;
+  rc = model_drain(p);
+  if (rc) return rc;
+  p->d_blur = std::move(nb);  // the new tables move in; the old ones are freed
+  p->d_blur_t = std::move(nbt);
   p->blur2d.swap(k2);
   p->blur2d_t.swap(k2t);
   p->blur1d = taps ? std::vector<double>((size_t)b, 0.0) : p->created_blur1d;  // a free-form kernel has no separable factor
   p->geo.b = b;
   p->geo.hb = (b - 1) / 2;
   p->custom_blur = taps != nullptr;
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);  // "not covered" while a free-form kernel is set
+  model_replan(p);  // "not covered" while a free-form kernel is set
   return SRMAP_OK;
 }
 
@@ -794,10 +774,10 @@ int srmap_set_observations(srmap_problem* p, const double* lr_host) {
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   rc = state_begin_write(p, p->ctx->stream);
   if (rc) return rc;
-  void** raw = p->photometric ? &p->d_obs_raw : &p->d_obs;  // photometric parameters persist: the new frames are normalised
+  DevBuf* raw = p->photometric ? &p->d_obs_raw : &p->d_obs;  // photometric parameters persist: the new frames are normalised
   rc = ensure(p, raw, p->lr_count() * p->elem());
   if (rc) return rc;
-  rc = convert_upload(p, lr_host, *raw, p->lr_count(), p->ctx->stream);
+  rc = convert_upload(p, lr_host, raw->as(), p->lr_count(), p->ctx->stream);
   if (rc) return rc;
   if (p->photometric) {
     rc = photometric_normalise(p, p->ctx->stream);
@@ -816,10 +796,10 @@ int srmap_set_observations_device(srmap_problem* p, const void* lr_dev, void* hi
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
   rc = state_begin_write(p, st);
   if (rc) return rc;
-  void** raw = p->photometric ? &p->d_obs_raw : &p->d_obs;
+  DevBuf* raw = p->photometric ? &p->d_obs_raw : &p->d_obs;
   rc = ensure(p, raw, p->lr_count() * p->elem());
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(*raw, lr_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(raw->as(), lr_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
   if (p->photometric) {
     rc = photometric_normalise(p, st);
     if (rc) return rc;
@@ -849,17 +829,15 @@ int srmap_add_regularizer(srmap_problem* p, int kind, double lambda, int btv_ran
   }
   if (reg_index) *reg_index = p->nreg;
   p->nreg++;
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);
+  model_replan(p);
   return SRMAP_OK;
 }
 
 int srmap_clear_regularizers(srmap_problem* p) {
   if (!p) return SRMAP_EINVAL;
-  for (int r = 0; r < p->nreg; ++r) if (p->reg[r].weights) { (void)hipFree(p->reg[r].weights); p->reg[r].weights = nullptr; }
+  for (int r = 0; r < p->nreg; ++r) p->reg[r].weights.reset();
   p->nreg = 0;
-  p->plan_gen++;
-  if (ztile_plan(p)) ztile_preload(p);
+  model_replan(p);
   return SRMAP_OK;
 }
 
@@ -870,12 +848,12 @@ int srmap_set_irls_weights(srmap_problem* p, int reg, const double* w_host) {
   int rc = state_begin_write(p, p->ctx->stream);
   if (rc) return rc;
   if (!w_host) {
-    if (rs.weights) { (void)hipFree(rs.weights); rs.weights = nullptr; }
+    rs.weights.reset();
     return SRMAP_OK;
   }
   rc = ensure(p, &rs.weights, p->hr_count() * p->elem());
   if (rc) return rc;
-  return convert_upload(p, w_host, rs.weights, p->hr_count(), p->ctx->stream);
+  return convert_upload(p, w_host, rs.weights.as(), p->hr_count(), p->ctx->stream);
 }
 
 int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_dev, void* hip_stream) {
@@ -887,8 +865,8 @@ int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_de
   if (rc) return rc;
   rc = ensure(p, &rs.weights, p->hr_count() * p->elem());
   if (rc) return rc;
-  if (p->dtype == SRMAP_F32) rc = launch_reg_weights<float>(p, p->geo, rs, (const float*)x_dev, (float*)rs.weights, st);
-  else rc = launch_reg_weights<double>(p, p->geo, rs, (const double*)x_dev, (double*)rs.weights, st);
+  if (p->dtype == SRMAP_F32) rc = launch_reg_weights<float>(p, p->geo, rs, (const float*)x_dev, rs.weights.as<float>(), st);
+  else rc = launch_reg_weights<double>(p, p->geo, rs, (const double*)x_dev, rs.weights.as<double>(), st);
   if (rc) return rc;
   return state_end_write(p, st);  // asynchronous: evaluations on other streams wait for this event
 }
@@ -898,8 +876,8 @@ int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_de
 static int rebuild_effective_weights(srmap_problem* p, hipStream_t st) {
   const size_t n = p->lr_count();
   int rc = p->dtype == SRMAP_F32
-               ? launch_weight_product<float>(p, (const float*)p->d_prior, (const float*)p->d_dw_user, (float*)p->d_dw, n, st)
-               : launch_weight_product<double>(p, (const double*)p->d_prior, (const double*)p->d_dw_user, (double*)p->d_dw, n, st);
+               ? launch_weight_product<float>(p, p->d_prior.as<const float>(), p->d_dw_user.as<const float>(), p->d_dw.as<float>(), n, st)
+               : launch_weight_product<double>(p, p->d_prior.as<const double>(), p->d_dw_user.as<const double>(), p->d_dw.as<double>(), n, st);
   if (rc) return rc;
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
   return SRMAP_OK;
@@ -919,20 +897,20 @@ int srmap_set_data_weights(srmap_problem* p, const double* w_host) {
   const bool was = p->robust();
   if (p->d_prior) {  // the caller's weights go to the second buffer; d_dw is the product with the prior
     if (!w_host) {
-      if (p->d_dw_user) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); (void)hipFree(p->d_dw_user); p->d_dw_user = nullptr; }
+      if (p->d_dw_user) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); p->d_dw_user.reset(); }
     } else {
       rc = ensure(p, &p->d_dw_user, n * p->elem());
-      if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw_user, n, st);
+      if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw_user.as(), n, st);
     }
     return rc ? rc : rebuild_effective_weights(p, st);
   }
   if (!w_host) {
     // all ones: the unweighted kernels again -- except under a Huber loss, which keeps (and owns) the buffer
-    if (p->d_dw) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); (void)hipFree(p->d_dw); p->d_dw = nullptr; }
+    if (p->d_dw) { SRMAP_HIP(p->ctx, hipStreamSynchronize(st)); p->d_dw.reset(); }
     if (p->data_loss == SRMAP_DATA_LOSS_HUBER) rc = ensure_data_weights(p, st);
   } else {
     rc = ensure(p, &p->d_dw, n * p->elem());
-    if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw, n, st);
+    if (rc == SRMAP_OK) rc = convert_upload(p, w_host, p->d_dw.as(), n, st);
   }
   replan_if(p, was);
   return rc;
@@ -946,10 +924,10 @@ int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip
   int rc = state_begin_write(p, st);
   if (rc) return rc;
   const bool was = p->robust();
-  void** dst = p->d_prior ? &p->d_dw_user : &p->d_dw;
+  DevBuf* dst = p->d_prior ? &p->d_dw_user : &p->d_dw;
   rc = ensure(p, dst, p->lr_count() * p->elem());
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(*dst, w_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(dst->as(), w_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
   if (p->d_prior) return rebuild_effective_weights(p, st);
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));  // complete on return, as srmap_set_observations_device
   replan_if(p, was);
@@ -961,16 +939,13 @@ int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip
 static int data_prior_begin(srmap_problem* p, hipStream_t st) {
   const size_t bytes = p->lr_count() * p->elem();
   if (p->d_prior) return SRMAP_OK;
-  void *m = nullptr, *eff = nullptr;
-  if (hipMalloc(&m, bytes ? bytes : 8) != hipSuccess || hipMalloc(&eff, bytes ? bytes : 8) != hipSuccess) {
-    if (m) (void)hipFree(m);
-    (void)hipGetLastError();
+  DevBuf m, eff;
+  if (m.alloc(bytes) != hipSuccess || eff.alloc(bytes) != hipSuccess)
     return set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed (data prior: 2 x %zu bytes)", bytes);
-  }
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-  p->d_prior = m;
-  p->d_dw_user = p->d_dw;  // nullptr: ones
-  p->d_dw = eff;
+  p->d_prior = std::move(m);
+  p->d_dw_user = std::move(p->d_dw);  // d_dw -> d_dw_user (empty: ones); data_prior_remove moves it back
+  p->d_dw = std::move(eff);
   return SRMAP_OK;
 }
 
@@ -985,11 +960,8 @@ static int data_prior_remove(srmap_problem* p, hipStream_t st) {
   if (!p->d_prior) return SRMAP_OK;
   const bool was = p->robust();
   SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-  (void)hipFree(p->d_prior);
-  (void)hipFree(p->d_dw);
-  p->d_prior = nullptr;
-  p->d_dw = p->d_dw_user;  // the caller's weights as they were given; nullptr: the unweighted kernels again
-  p->d_dw_user = nullptr;
+  p->d_prior.reset();
+  p->d_dw = std::move(p->d_dw_user);  // the product is freed; the caller's weights as given, or empty: the unweighted kernels again
   int rc = SRMAP_OK;
   if (p->data_loss == SRMAP_DATA_LOSS_HUBER) rc = ensure_data_weights(p, st);
   replan_if(p, was);
@@ -1011,7 +983,7 @@ int srmap_set_data_prior(srmap_problem* p, const double* m_host) {
   const bool was = p->robust();
   rc = data_prior_begin(p, st);
   if (rc) return rc;
-  rc = convert_upload(p, m_host, p->d_prior, n, st);
+  rc = convert_upload(p, m_host, p->d_prior.as(), n, st);
   if (rc) return rc;
   return data_prior_end(p, was, st);
 }
@@ -1026,7 +998,7 @@ int srmap_set_data_prior_device(srmap_problem* p, const void* m_dev, void* hip_s
   const bool was = p->robust();
   rc = data_prior_begin(p, st);
   if (rc) return rc;
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_prior, m_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_prior.as(), m_dev, p->lr_count() * p->elem(), hipMemcpyDeviceToDevice, st));
   return data_prior_end(p, was, st);
 }
 
@@ -1040,7 +1012,7 @@ int srmap_get_data_prior(srmap_problem* p, double* m_host, int* is_set) {
     return SRMAP_OK;
   }
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return convert_download(p, p->d_prior, m_host, n, p->ctx->stream);
+  return convert_download(p, p->d_prior.as(), m_host, n, p->ctx->stream);
 }
 
 int srmap_get_data_weights(srmap_problem* p, double* w_host) {
@@ -1053,7 +1025,7 @@ int srmap_get_data_weights(srmap_problem* p, double* w_host) {
   }
   // the weights may have been written asynchronously on another stream (srmap_update_data_weights_device)
   if (p->state_stream && p->state_stream != p->ctx->stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->state_stream));
-  return convert_download(p, p->d_dw, w_host, n, p->ctx->stream);
+  return convert_download(p, p->d_dw.as(), w_host, n, p->ctx->stream);
 }
 
 int srmap_problem_set_data_loss(srmap_problem* p, int loss, double huber_delta) {
@@ -1093,14 +1065,14 @@ int srmap_apply(srmap_problem* p, int frame, const double* hr, double* lr) {
   if (rc) return rc;
   rc = ensure(p, &p->d_tmp, p->hr_count() * p->elem());
   if (rc) return rc;
-  rc = convert_upload(p, hr, p->d_x, p->hr_count(), st);
+  rc = convert_upload(p, hr, p->d_x.as(), p->hr_count(), st);
   if (rc) return rc;
   if (p->dtype == SRMAP_F32)
-    rc = launch_forward_direct<float>(p, p->geo, (const float*)p->d_x, nullptr, p->geo.C, 0, (float*)p->d_tmp, frame, 1, nullptr, nullptr, st);
+    rc = launch_forward_direct<float>(p, p->geo, p->d_x.as<const float>(), nullptr, p->geo.C, 0, p->d_tmp.as<float>(), frame, 1, nullptr, nullptr, st);
   else
-    rc = launch_forward_direct<double>(p, p->geo, (const double*)p->d_x, nullptr, p->geo.C, 0, (double*)p->d_tmp, frame, 1, nullptr, nullptr, st);
+    rc = launch_forward_direct<double>(p, p->geo, p->d_x.as<const double>(), nullptr, p->geo.C, 0, p->d_tmp.as<double>(), frame, 1, nullptr, nullptr, st);
   if (rc) return rc;
-  return convert_download(p, p->d_tmp, lr, nlr, st);
+  return convert_download(p, p->d_tmp.as(), lr, nlr, st);
 }
 
 int srmap_apply_transpose(srmap_problem* p, int frame, const double* lr, double* hr) {
@@ -1116,14 +1088,14 @@ int srmap_apply_transpose(srmap_problem* p, int frame, const double* lr, double*
   if (rc) return rc;
   rc = ensure(p, &p->d_tmp, p->hr_count() * p->elem());
   if (rc) return rc;
-  rc = convert_upload(p, lr, p->d_tmp, nlr, st);
+  rc = convert_upload(p, lr, p->d_tmp.as(), nlr, st);
   if (rc) return rc;
   if (p->dtype == SRMAP_F32)
-    rc = launch_gather_direct<float>(p, p->geo, (const float*)p->d_tmp, (float*)p->d_g, frame, 1, 1.0, false, st);
+    rc = launch_gather_direct<float>(p, p->geo, p->d_tmp.as<const float>(), p->d_g.as<float>(), frame, 1, 1.0, false, st);
   else
-    rc = launch_gather_direct<double>(p, p->geo, (const double*)p->d_tmp, (double*)p->d_g, frame, 1, 1.0, false, st);
+    rc = launch_gather_direct<double>(p, p->geo, p->d_tmp.as<const double>(), p->d_g.as<double>(), frame, 1, 1.0, false, st);
   if (rc) return rc;
-  return convert_download(p, p->d_g, hr, p->hr_count(), st);
+  return convert_download(p, p->d_g.as(), hr, p->hr_count(), st);
 }
 
 int srmap_reg_values(srmap_problem* p, int reg, const double* x, double* values) {
@@ -1134,14 +1106,14 @@ int srmap_reg_values(srmap_problem* p, int reg, const double* x, double* values)
   if (rc) return rc;
   rc = ensure(p, &p->d_regvals, p->hr_count() * p->elem());
   if (rc) return rc;
-  rc = convert_upload(p, x, p->d_x, p->hr_count(), st);
+  rc = convert_upload(p, x, p->d_x.as(), p->hr_count(), st);
   if (rc) return rc;
   if (p->dtype == SRMAP_F32)
-    rc = launch_reg_values<float>(p, p->geo, p->reg[reg], (const float*)p->d_x, (float*)p->d_regvals, st);
+    rc = launch_reg_values<float>(p, p->geo, p->reg[reg], p->d_x.as<const float>(), p->d_regvals.as<float>(), st);
   else
-    rc = launch_reg_values<double>(p, p->geo, p->reg[reg], (const double*)p->d_x, (double*)p->d_regvals, st);
+    rc = launch_reg_values<double>(p, p->geo, p->reg[reg], p->d_x.as<const double>(), p->d_regvals.as<double>(), st);
   if (rc) return rc;
-  return convert_download(p, p->d_regvals, values, p->hr_count(), st);
+  return convert_download(p, p->d_regvals.as(), values, p->hr_count(), st);
 }
 
 int srmap_reg_values_and_gradient(srmap_problem* p, int reg, const double* x, const double* gc,
@@ -1154,21 +1126,21 @@ int srmap_reg_values_and_gradient(srmap_problem* p, int reg, const double* x, co
   rc = ensure(p, &p->d_g, n * p->elem()); if (rc) return rc;
   rc = ensure(p, &p->d_tmp, n * p->elem()); if (rc) return rc;
   rc = ensure(p, &p->d_regvals, n * p->elem()); if (rc) return rc;
-  rc = convert_upload(p, x, p->d_x, n, st); if (rc) return rc;
-  rc = convert_upload(p, gc, p->d_tmp, n, st); if (rc) return rc;
+  rc = convert_upload(p, x, p->d_x.as(), n, st); if (rc) return rc;
+  rc = convert_upload(p, gc, p->d_tmp.as(), n, st); if (rc) return rc;
   const RegSpec& rs = p->reg[reg];
   if (p->dtype == SRMAP_F32) {
-    rc = launch_reg_values<float>(p, p->geo, rs, (const float*)p->d_x, (float*)p->d_regvals, st); if (rc) return rc;
-    rc = launch_reg_gradient_direct<float>(p, p->geo, rs, (const float*)p->d_x, (const float*)p->d_tmp, 1.0,
-                                           (const float*)p->d_regvals, (float*)p->d_g, false, nullptr, nullptr, st);
+    rc = launch_reg_values<float>(p, p->geo, rs, p->d_x.as<const float>(), p->d_regvals.as<float>(), st); if (rc) return rc;
+    rc = launch_reg_gradient_direct<float>(p, p->geo, rs, p->d_x.as<const float>(), p->d_tmp.as<const float>(), 1.0,
+                                           p->d_regvals.as<const float>(), p->d_g.as<float>(), false, nullptr, nullptr, st);
   } else {
-    rc = launch_reg_values<double>(p, p->geo, rs, (const double*)p->d_x, (double*)p->d_regvals, st); if (rc) return rc;
-    rc = launch_reg_gradient_direct<double>(p, p->geo, rs, (const double*)p->d_x, (const double*)p->d_tmp, 1.0,
-                                            (const double*)p->d_regvals, (double*)p->d_g, false, nullptr, nullptr, st);
+    rc = launch_reg_values<double>(p, p->geo, rs, p->d_x.as<const double>(), p->d_regvals.as<double>(), st); if (rc) return rc;
+    rc = launch_reg_gradient_direct<double>(p, p->geo, rs, p->d_x.as<const double>(), p->d_tmp.as<const double>(), 1.0,
+                                            p->d_regvals.as<const double>(), p->d_g.as<double>(), false, nullptr, nullptr, st);
   }
   if (rc) return rc;
-  rc = convert_download(p, p->d_regvals, values, n, st); if (rc) return rc;
-  return convert_download(p, p->d_g, gradient, n, st);
+  rc = convert_download(p, p->d_regvals.as(), values, n, st); if (rc) return rc;
+  return convert_download(p, p->d_g.as(), gradient, n, st);
 }
 
 // ---- objective ----
@@ -1180,11 +1152,11 @@ int srmap_eval_device(srmap_problem* p, unsigned terms, const void* x_dev, void*
   int rc = eval_dispatch(p, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;
   if (cost) {
-    SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost, sizeof(double), hipMemcpyDeviceToHost, st));
+    SRMAP_HIP(p->ctx, hipMemcpyAsync(cost, p->d_cost.as<double>(), sizeof(double), hipMemcpyDeviceToHost, st));
     SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
     if (*cost != *cost) {  // NaN: the input's, or the in-kernel reduction gave up waiting for a workgroup (sticky word)
       double flag = 0.0;
-      SRMAP_HIP(p->ctx, hipMemcpy(&flag, p->d_cost + 6, sizeof(double), hipMemcpyDeviceToHost));
+      SRMAP_HIP(p->ctx, hipMemcpy(&flag, p->d_cost.as<double>() + 6, sizeof(double), hipMemcpyDeviceToHost));
       if (flag != 0.0) {  // re-arm and report: the evaluation's gradient is not trustworthy
         rc = recover_reduction_timeout(p, nullptr);
         if (rc) return rc;
@@ -1199,7 +1171,7 @@ int srmap_last_cost(srmap_problem* p, double* cost) {
   if (!p || !cost) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   SRMAP_HIP(p->ctx, hipDeviceSynchronize());
-  SRMAP_HIP(p->ctx, hipMemcpy(cost, p->d_cost, sizeof(double), hipMemcpyDeviceToHost));
+  SRMAP_HIP(p->ctx, hipMemcpy(cost, p->d_cost.as<double>(), sizeof(double), hipMemcpyDeviceToHost));
   return SRMAP_OK;
 }
 
@@ -1210,18 +1182,20 @@ int srmap_eval(srmap_problem* p, unsigned terms, const double* x, double* cost, 
   const size_t n = p->hr_count();
   int rc = ensure(p, &p->d_x, n * p->elem()); if (rc) return rc;
   if (grad) { rc = ensure(p, &p->d_g, n * p->elem()); if (rc) return rc; }
-  rc = convert_upload(p, x, p->d_x, n, st); if (rc) return rc;
+  rc = convert_upload(p, x, p->d_x.as(), n, st); if (rc) return rc;
   double c = 0;
-  rc = srmap_eval_device(p, terms, p->d_x, grad ? p->d_g : nullptr, &c, st); if (rc) return rc;
+  rc = srmap_eval_device(p, terms, p->d_x.as(), grad ? p->d_g.as() : nullptr, &c, st); if (rc) return rc;
   if (cost) *cost = c;
-  if (grad) return convert_download(p, p->d_g, grad, n, st);
+  if (grad) return convert_download(p, p->d_g.as(), grad, n, st);
   return SRMAP_OK;
 }
 
 int srmap_device_alloc(srmap_ctx* ctx, size_t bytes, void** dev) {
   if (!ctx || !dev) return SRMAP_EINVAL;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  SRMAP_HIP(ctx, hipMalloc(dev, bytes ? bytes : 8));
+  DevBuf b;  // handed to the caller, who returns it through srmap_device_free
+  SRMAP_HIP(ctx, b.alloc(bytes));
+  *dev = b.release();
   return SRMAP_OK;
 }
 int srmap_device_free(srmap_ctx* ctx, void* dev) {

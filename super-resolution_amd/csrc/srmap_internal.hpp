@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "srmap.h"
 
 namespace srmap {
@@ -39,6 +40,8 @@ struct WarpTaps {
   // one int per destination row: source row << 5 | fraction index) replaces oy and the y half of w.
   const int* ytab;
 };
+static_assert(std::is_trivially_copyable_v<WarpTaps<float>> && std::is_trivially_copyable_v<WarpTaps<double>>,
+              "a kernel argument: no owner inside");
 
 // The forms of M_k in A_k = D B M_k: none (the identity), the translational tap table, an affine matrix per frame, a dense
 // displacement field per frame.  MotionArgs: what the kernels that sample M_k (MotionSampler, sample_dev.hpp) take for
@@ -51,6 +54,8 @@ struct MotionArgs {
   const T* flow;             // [K][2][H][W] (flow)
   const int* seeds;          // [K][H][W] packed seeds of the transpose gather (flow)
 };
+static_assert(std::is_trivially_copyable_v<MotionArgs<float>> && std::is_trivially_copyable_v<MotionArgs<double>>,
+              "a kernel argument: no owner inside");
 
 struct Geometry {
   int W, H, C, K;  // HR size, channels, frames
@@ -64,13 +69,14 @@ struct Geometry {
   int zlo, zhi;    // channel sharding: a halo plane exists before channel 0 / after channel C-1 of this view
                    // (3-D TV couples across it, tv_regularizer.cpp:205-222); 0 otherwise
 };
+static_assert(std::is_trivially_copyable_v<Geometry>, "a kernel argument: no owner inside");
 
 struct RegSpec {
   int kind;
   int range;
   double decay;
   double lambda;
-  void* weights;  // device [C][H][W] dtype; nullptr = all ones
+  DevBuf weights;  // device [C][H][W] dtype; empty = all ones
   double pow_table[2 * kMaxBtvRange + 1];  // std::pow(decay, k), host libm
 };
 
@@ -114,9 +120,9 @@ struct srmap_ctx {
   int num_cus = 0;
   // pinned host staging: two chunks for pipelined host<->device copies of caller (pageable) buffers,
   // and a small scalar block the reduction kernels write directly (no copy kernels, one sync)
-  void* h_stage[2] = {nullptr, nullptr};
+  srmap::PinnedBuf h_stage[2];
   hipEvent_t h_event[2] = {nullptr, nullptr};
-  double* h_scal = nullptr;  // [16], host-mapped
+  srmap::PinnedBuf h_scal;   // double[16], host-mapped
   void* blas = nullptr;      // rocblas_handle of this context (channel_map.hip), created on first use
 };
 
@@ -132,13 +138,12 @@ struct srmap_problem {
   // and the tile planner answers "not covered"; the translational warps above stay as created (NULL restores them)
   bool affine = false;
   std::vector<double> affine_recs;  // K x kAffineRec (host mirror of d_affine)
-  double* d_affine = nullptr;
+  srmap::DevBuf d_affine;         // double[K][kAffineRec]
   // displacement-field motion model (an alternative to the affine one: setting either replaces the other): when set, the
   // data term samples the frame's field (kMotionFlow).  d_flow: [K][2][H][W] dtype, the (ux, uy) planes per frame; d_flow_seed: [K][H][W]
   // packed seeds of the transpose gather, both validated when they were set
   bool flow = false;
-  void* d_flow = nullptr;
-  int* d_flow_seed = nullptr;
+  srmap::DevBuf d_flow, d_flow_seed;
   std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
   std::vector<double> blur2d_t;
   std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
@@ -149,43 +154,43 @@ struct srmap_problem {
   int created_b = 1;
   std::vector<double> created_blur2d, created_blur2d_t, created_blur1d;
   // device constants
-  std::vector<int*> d_ytabs;      // per-row y tables of frames whose warpAffine y table is not uniform (owned)
-  void* d_fwd_warps = nullptr;    // WarpTaps<T>[K]
-  void* d_bwd_warps = nullptr;    // WarpTaps<T>[K]
-  void* d_blur = nullptr;         // T[b*b]
-  void* d_blur_t = nullptr;       // T[b*b]
-  int* d_col_map = nullptr;       // int[w]  decimation source column
-  int* d_row_map = nullptr;       // int[h]
+  std::vector<srmap::DevBuf> d_ytabs;     // per-row y tables of frames whose warpAffine y table is not uniform (owned)
+  srmap::DevBuf d_fwd_warps;      // WarpTaps<T>[K]
+  srmap::DevBuf d_bwd_warps;      // WarpTaps<T>[K]
+  srmap::DevBuf d_blur;           // T[b*b]
+  srmap::DevBuf d_blur_t;         // T[b*b]
+  srmap::DevBuf d_col_map;        // int[w]  decimation source column
+  srmap::DevBuf d_row_map;        // int[h]
   // host mirrors of the warp taps (double) for tile planning
   std::vector<srmap::WarpTaps<double>> fwd_warps, bwd_warps;
   // state
-  void* d_obs = nullptr;          // [K][C][h][w] dtype
+  srmap::DevBuf d_obs;            // [K][C][h][w] dtype
   bool have_obs = false;
   // photometric frame model (srmap_problem_set_photometric, photometric_fit.hip): while parameters are set, d_obs_raw holds
   // the frames as given and d_obs -- what every kernel reads -- their normalised copy (y - bias_k) / gain_k; d_obs_raw is
   // nullptr otherwise (and until a problem with parameters receives its first frames)
   bool photometric = false;
   std::vector<double> photo;      // K x 2 {gain, bias} (host mirror of d_photo)
-  double* d_photo = nullptr;
-  void* d_obs_raw = nullptr;      // [K][C][h][w] dtype
-  void* d_resid = nullptr;        // [K][C][h][w] dtype scratch
-  void* d_dw = nullptr;           // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
+  srmap::DevBuf d_photo;          // double[K][2]
+  srmap::DevBuf d_obs_raw;        // [K][C][h][w] dtype
+  srmap::DevBuf d_resid;          // [K][C][h][w] dtype scratch
+  srmap::DevBuf d_dw;             // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
   int data_loss = SRMAP_DATA_LOSS_L2;  // srmap_problem_set_data_loss; HUBER keeps d_dw allocated (it owns the buffer)
   double huber_delta = 0.0;
   // persistent prior m on the data weights (srmap_set_data_prior): while set, d_dw = m .* w (allocated, so the problem is
   // robust()) and d_dw_user keeps the caller's weights w (nullptr = ones); both nullptr otherwise
-  void* d_prior = nullptr;        // [K][C][h][w] dtype
-  void* d_dw_user = nullptr;      // [K][C][h][w] dtype
+  srmap::DevBuf d_prior;          // [K][C][h][w] dtype
+  srmap::DevBuf d_dw_user;        // [K][C][h][w] dtype
   // weights or a Huber loss: every evaluation runs a WEIGHTED forward kernel, and the tile plan takes the forward-residual
   // form for integer shifts too (kernels_ztile.hip ztile_plan)
-  bool robust() const { return d_dw != nullptr || data_loss == SRMAP_DATA_LOSS_HUBER; }
-  void* d_regvals = nullptr;      // [C][H][W] dtype scratch
-  void* d_x = nullptr;            // [C][H][W] staging for host-buffer entry points
-  void* d_g = nullptr;
-  void* d_tmp = nullptr;          // [C][H][W] staging (gradient constants, values)
-  double* d_partials = nullptr;   // per-block cost partials
+  bool robust() const { return d_dw || data_loss == SRMAP_DATA_LOSS_HUBER; }
+  srmap::DevBuf d_regvals;        // [C][H][W] dtype scratch
+  srmap::DevBuf d_x;              // [C][H][W] staging for host-buffer entry points
+  srmap::DevBuf d_g;
+  srmap::DevBuf d_tmp;            // [C][H][W] staging (gradient constants, values)
+  srmap::DevBuf d_partials;       // per-block cost partials
   size_t partials_cap = 0;
-  double* d_cost = nullptr;       // [8] reduced scalars: [0] cost, [1] g.d (EvalOut::gd_valid), [6] time-out word
+  srmap::DevBuf d_cost;           // [8] reduced scalars: [0] cost, [1] g.d (EvalOut::gd_valid), [6] time-out word
   int solver = SRMAP_SOLVER_CG;     // srmap_problem_set_solver: the inner minimiser of srmap_solve
   int lbfgs_m = 5;                  // L-BFGS history length (num_lbfgs_hessian_corrections)
   double selfcheck_beta_den = 0.0;   // largest relative deviation of the derived beta denominator from the directly summed one
@@ -253,7 +258,7 @@ inline MotionKind motion_kind(const srmap_problem* p) {
 }
 template <typename T>
 MotionArgs<T> motion_args(const srmap_problem* p) {
-  return {p->has_motion ? (const WarpTaps<T>*)p->d_fwd_warps : nullptr, p->d_affine, (const T*)p->d_flow, p->d_flow_seed};
+  return {p->has_motion ? p->d_fwd_warps.as<const WarpTaps<T>>() : nullptr, p->d_affine.as<double>(), p->d_flow.as<const T>(), p->d_flow_seed.as<int>()};
 }
 // f(std::integral_constant<int, KIND>) for the one of KINDS... that `kind` is -- the kinds the caller has kernel instances
 // of; false (and no call) for any other, which the caller answers as an internal error
@@ -275,19 +280,15 @@ void launch_down2_stack(const double* src, double* dst, int w, int h, int frames
 constexpr int kFitTabRec = 8;
 struct FitPass {
   int frames = 0, nsums = 0;
-  double *d_part = nullptr, *d_tab = nullptr, *d_sums = nullptr;  // device
-  double *h_tab = nullptr, *h_sums = nullptr;                     // pinned host
-  FitPass() = default;
-  FitPass(const FitPass&) = delete;
-  FitPass& operator=(const FitPass&) = delete;
-  ~FitPass();
+  DevBuf d_part, d_tab, d_sums;  // doubles
+  PinnedBuf h_tab, h_sums;       // doubles
   // part_elems: doubles of d_part (>= frames * chunks * nsums; a caller may ask for more and share it).  false: an
-  // allocation failed (the caller clears the sticky error)
+  // allocation failed
   bool alloc(int frames_, int nsums_, size_t part_elems);
   void set(int frame, const AffineMap& M, bool active);
   bool upload(hipStream_t st);
   bool reduce_and_fetch(int chunks, hipStream_t st);  // also reports a failed launch of the caller's sums kernel
-  const double* sums(int frame) const { return h_sums + (size_t)frame * nsums; }
+  const double* sums(int frame) const { return h_sums.as<const double>() + (size_t)frame * nsums; }
 };
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
@@ -331,20 +332,24 @@ int launch_forward_residual(srmap_problem* p, const Geometry& geo, int obs_c0, c
 
 // ---- forward tile kernel for sub-pixel shifts (kernels_spfwd.hip) ----
 struct SpForwardPlan {
-  void* d_frames = nullptr;  // per frame: integer offsets + blur (x) bilinear stencil
+  DevBuf d_frames;  // per frame: integer offsets + blur (x) bilinear stencil
   int RLO = 0, CLO = 0, XR = 0, XC = 0;  // LDS window of a workgroup relative to its first LR row / cell
   bool ok = false;
   int RF0 = 0, NRF = 0, CF0 = 0, NCF = 0;  // union of the window and the workgroup's own HR block (rows / cells FOLD instances walk)
   bool can_fold = false;     // that union fits the kernel's load loop: the trial point can be formed (folded) here
 };
 bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp);
-void spfwd_release(SpForwardPlan* sp);
 // out[k][c][h][w] = A_k x - y_k for all frames + cost partials (one per workgroup); dw != nullptr (indexed like y): the
 // WEIGHTED instances, out = w .* r and partials of w r^2
 template <typename T>
 int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y,
                       int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st,
                       const SpFold& fold = SpFold(), const T* dw = nullptr);
+
+// ---- a change of the model (srmap_api.hip): every setter checks its arguments, builds the new buffers in locals (a
+// failure leaves the problem as it was), then model_drain, swap, model_replan ----
+int model_drain(srmap_problem* p);    // wait for the evaluations in flight: they read the buffers about to change
+void model_replan(srmap_problem* p);  // a new plan generation, the tile plan for the model now in force and its preload
 
 // ---- evaluation (srmap_api.hip) ----
 // One ObjectiveFunction::ComputeAllTerms on device buffers, on the stream st (srmap_eval_device with a request).
@@ -379,10 +384,12 @@ struct LbfgsRed {
   double* tag_slot;
   double tag;
 };
+static_assert(std::is_trivially_copyable_v<LbfgsRed>, "a kernel argument: no owner inside");
 // coefficients of the direction over the basis: c[0] for g, c[1 + 2j] for s_j, c[2 + 2j] for y_j
 struct LbfgsCoef {
   double c[1 + 2 * kLbfgsMaxM];
 };
+static_assert(std::is_trivially_copyable_v<LbfgsCoef>, "a kernel argument: no owner inside");
 // ring slot p <- (s, y) = (x - xk, g - gk); sums [0] g.g, [1] s.s, then per slot j < live: s.y_j, y.s_j, y.y_j, g.s_j,
 // g.y_j (2 + 5 live rows)
 template <typename T>

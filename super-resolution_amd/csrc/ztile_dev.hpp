@@ -124,6 +124,7 @@ struct ZEntry { int k, io, jo, oyx; };  // frame, LR row / column offset of the 
 //   rg[4] = lo: LEFT-OUTSIDE   columns [-lo, 0)   x rows [0, H)
 //   rg[5] = ro: RIGHT-OUTSIDE  columns [W, W+ro)  x rows [0, H)
 struct RingRects { int rg[6]; };
+static_assert(std::is_trivially_copyable_v<RingRects>, "a kernel argument: no owner inside");
 
 __host__ __device__ __forceinline__ long long ring_count(const RingRects& r, int W, int H) {
   const long long ti = r.rg[0], li = r.rg[1], to = r.rg[2], bo = r.rg[3], lo = r.rg[4], ro = r.rg[5];
@@ -324,6 +325,8 @@ struct ZArgs {
   const double* fold_norms;  // device {max|dk|, dk.dk}: dvec is the UNNORMALISED direction, every element read from it is
                              // scaled to the normalised one (cg_norm.hpp) -- the solver stores no normalised vector
 };
+static_assert(std::is_trivially_copyable_v<ZArgs<float, 1, 1>> && std::is_trivially_copyable_v<ZArgs<double, 3, 1>>,
+              "a kernel argument: no owner inside");
 
 // The x tile is staged PRE-SCALED by 2^Q (exact: a power of two).  Every difference of two staged values is the
 // true difference times 2^Q, large enough that sgn(d) * pw is just a clamp to [-pw, pw] (no ldexp per tap), and
@@ -885,6 +888,8 @@ struct BorderArgs {      // device-resident (one per problem): only the border b
   int n_ent;             // entries of the frame table
   int obs_C;             // channels of the observation stack
 };
+static_assert(std::is_trivially_copyable_v<BorderArgs<float>> && std::is_trivially_copyable_v<BorderArgs<double>>,
+              "a kernel argument: no owner inside");
 
 __device__ __forceinline__ int dfdiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
@@ -1041,27 +1046,27 @@ struct ZPlan {
   int regk = 0, regr = 0, reg_index = -1;
   bool subpix = false;  // sub-pixel shifts: residuals from k_forward_direct, z by 4-tap tables, exact ring by k_gather_direct
   int Dr = 0;           //   ring width
-  void* d_ringbuf = nullptr;   //   [C][ring pixels] data gradient of the ring pixels (the ring pass ahead of the tile kernel)
-  ZSrc* d_spsrc = nullptr;     //   source-major tap table [S][spmax] (z_row_sp2)
+  DevBuf d_ringbuf;            //   [C][ring pixels] data gradient of the ring pixels (the ring pass ahead of the tile kernel)
+  DevBuf d_spsrc;              //   ZSrc:   source-major tap table [S][spmax] (z_row_sp2)
   int spn[4] = {0, 0, 0, 0};
   int spmax = 0;
   SpForwardPlan spf;    //   forward tile kernel (kernels_spfwd.hip); the direct forward kernel when it does not apply
   int E = 0;   // max |shift|
   int MS = 1;  // table slots per (row phase, column phase)
   int n_ent = 0;
-  int2* d_hdr = nullptr;       // flat table of k_border: (count, first entry) per phase
-  ZEntry* d_ent = nullptr;
+  DevBuf d_hdr;                // int2: flat table of k_border: (count, first entry) per phase
+  DevBuf d_ent;                // ZEntry
   int h_cnt[32] = {0};         // host copies handed to the kernel by value: [4][8] counts (+ max, min over the column phases)
   long long h_off0[16] = {0};  //   [4][4] round-0 offsets
   ZEntry h_aux0[16] = {};      //   [4][4] round-0 (frame, LR row / column offset) entries
-  int* d_cnt = nullptr;        // tile kernel: [S][8]
-  long long* d_off = nullptr;  //              [MS][S][S]
-  ZEntry* d_aux = nullptr;     //              [MS][S][S]
+  DevBuf d_cnt;                // tile kernel: int [S][8]
+  DevBuf d_off;                //              long long [MS][S][S]
+  DevBuf d_aux;                //              ZEntry [MS][S][S]
   int n_ring = 0;              // pixels of the border frame (0 when no shift produces border work)
   RingRects ring = {{0, 0, 0, 0, 0, 0}};
-  void* d_corr = nullptr;      // [C][n_ring] border corrections of the gradient
-  void* d_bd = nullptr;        // BorderArgs<T> (device)
-  double* d_mpart = nullptr;   // write-through partial granules of the in-kernel cost reduction, [2][mpart_cap] (cost, g.d); sentinel = unpublished
+  DevBuf d_corr;               // [C][n_ring] border corrections of the gradient
+  DevBuf d_bd;                 // BorderArgs<T> (device)
+  DevBuf d_mpart;              // double: write-through partial granules of the in-kernel cost reduction, [2][mpart_cap] (cost, g.d); sentinel = unpublished
   size_t mpart_cap = 0;
 };
 
@@ -1075,10 +1080,10 @@ static void fill_zargs(ZArgs<T, B, ZCfg<T, S, B, REGK, R>::NP>& A, srmap_problem
                        unsigned terms, const T* x, T* g, const T* wts, const ZPlan& z, double* partials, const T* dvec,
                        double* partials_gd) {
   using C = ZCfg<T, S, B, REGK, R>;
-  A.x = x; A.y = (const T*)p->d_obs + (size_t)obs_c0 * geo.w * geo.h; A.w = wts; A.g = g; A.partials = partials;
+  A.x = x; A.y = p->d_obs.as<const T>() + (size_t)obs_c0 * geo.w * geo.h; A.w = wts; A.g = g; A.partials = partials;
   A.dvec = dvec; A.partials_gd = partials_gd;
-  A.cnt = z.d_cnt; A.off = z.d_off; A.aux = z.d_aux; A.MS = z.MS;
-  A.spsrc = z.d_spsrc; A.spmax = z.spmax;
+  A.cnt = z.d_cnt.as<int>(); A.off = z.d_off.as<long long>(); A.aux = z.d_aux.as<ZEntry>(); A.MS = z.MS;
+  A.spsrc = z.d_spsrc.as<ZSrc>(); A.spmax = z.spmax;
   for (int pr = 0; pr < 4; ++pr) A.spn[pr] = z.spn[pr];
   for (int pr = 0; pr < 4; ++pr) {
     for (int i = 0; i < 8; ++i) A.cntk[pr][i] = z.h_cnt[pr * 8 + i];

@@ -95,6 +95,7 @@ _SIGNATURES = [
     ("srmap_ctx_destroy", None, [C.c_void_p]),
     ("srmap_last_error", C.c_char_p, [C.c_void_p]),
     ("srmap_version", C.c_char_p, []),
+    ("srmap_live_allocations", C.c_longlong, []),
     ("srmap_problem_create", C.c_int, [C.c_void_p, C.POINTER(ProblemDesc), C.POINTER(C.c_void_p)]),
     ("srmap_problem_set_cost_rows", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("srmap_problem_destroy", None, [C.c_void_p]),
