@@ -1,4 +1,4 @@
-// affine_map.hpp -- host algebra of the 2 x 3 frame maps [a b tx; c d ty] that srmap_api.hip (affine_records), registration.hip,
+// affine_map.hpp -- host algebra of the 2 x 3 frame maps [a b tx; c d ty] that problem.hip (affine_records), registration.hip,
 // registration_affine.hip and motion_refinement.hip share: ONE copy of each expression, so that the records, the
 // registration and the refinement cannot drift apart.  Plain C++17, no HIP header (tests/cpp/affine_map_test.cpp compiles
 // it alone); the checkers are tests/affine_registration_restatement.py and tests/motion_refinement_restatement.py.

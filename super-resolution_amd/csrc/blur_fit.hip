@@ -125,9 +125,9 @@ bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_
   const MotionArgs<T> ma = motion_args<T>(p);
   return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
-    if (p->d_dw)
+    if (p->dw.effective<T>())
       hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
-                         p->d_dw.as<const T>(), g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
+                         p->dw.effective<T>(), g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
     else
       hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
                          (const T*)nullptr, g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
@@ -209,8 +209,7 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
       sums_host.alloc((size_t)P * sizeof(double)) != hipSuccess)
     return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
   double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
-  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, ksize, (const float*)x_dev, chunks, tpc, d_part, st)
-                              : launch_sums<double>(p, ksize, (const double*)x_dev, chunks, tpc, d_part, st)))
+  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
     return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
   SRMAP_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, d_part, records, P, d_sums);

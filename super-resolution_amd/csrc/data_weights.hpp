@@ -1,0 +1,76 @@
+// data_weights.hpp -- the per-observation weights of the data term ([K][C][h][w], problem dtype): the caller's weights
+// w (srmap_set_data_weights*), the persistent prior m (srmap_set_data_prior*) and the loss (srmap_problem_set_data_loss).
+// One type owns the three buffers; the moves between them happen in data_weights.hip and nowhere else.
+//
+// Buffers.  eff: what every kernel reads (effective<T>(); none = all ones, the unweighted kernels).  user: the caller's
+// factor while a prior is set (none = ones).  prior: m.
+//
+//   prior  user's w  loss   | eff holds                    user holds   robust()
+//   -      -         L2     | nothing                      nothing      no      (*)
+//   -      w         L2     | w                            nothing      yes
+//   -      -         Huber  | ones, then huber(r)          nothing      yes
+//   -      w         Huber  | w, then huber(r)             nothing      yes
+//   m      - / w     L2     | m .* w (one rounding)        w / nothing  yes
+//   m      - / w     Huber  | m .* w, then m .* huber(r)   w / nothing  yes
+//
+// Without a prior eff IS the caller's buffer, and a Huber loss owns it as well: huber_step() overwrites the caller's
+// weights, and setting "no weights" under Huber gives a buffer of ones instead of none.  (*) Going from Huber back to L2
+// keeps eff and its contents (the last outlier map): the first row is reached again by setting "no weights".
+// The first prior of a problem moves eff -- whatever it holds -- to user and makes eff the product's buffer; removing the
+// prior moves user back (ones under Huber if it was empty).  A Huber step leaves user alone: the next set_user or
+// set_prior forms m .* w from it again.
+//
+// robust() == (eff is allocated || Huber): every evaluation then runs a WEIGHTED forward kernel, and the tile plan takes
+// its forward-residual form for integer shifts too (kernels_ztile.hip ztile_plan).  A transition re-plans
+// (model_replan) exactly when it changes robust(): into or out of the first row.
+//
+// Writes are ordered as include/srmap.h "Streams" says: a setter drains the last evaluation's stream before it writes
+// and is complete on return; huber_step() and reset() are enqueued.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "dev_mem.hpp"
+#include "srmap.h"
+
+struct srmap_problem;
+
+namespace srmap {
+
+// Where a factor comes from: host doubles (converted to the dtype), a device array of the dtype (copied on st), or
+// nothing (the factor is removed).  st: the stream the write is enqueued on and waited for
+struct WeightSource {
+  const double* host = nullptr;
+  const void* dev = nullptr;
+  hipStream_t st = nullptr;
+  bool none() const { return !host && !dev; }
+};
+
+class DataWeights {
+ public:
+  template <typename T>
+  const T* effective() const { return eff_.as<const T>(); }  // nullptr: all ones
+  template <typename T>
+  const T* prior() const { return prior_.as<const T>(); }  // nullptr: none
+  bool robust() const { return eff_ || loss_ == SRMAP_DATA_LOSS_HUBER; }
+  int loss() const { return loss_; }
+  double delta() const { return delta_; }
+
+  int set_user(srmap_problem* p, const WeightSource& src);
+  int set_prior(srmap_problem* p, const WeightSource& src);
+  int set_loss(srmap_problem* p, int loss, double huber_delta);
+  // the start of a Huber solve on the channels [c0, c0 + C) (C = 0: all): eff <- the prior, or 1 without one; enqueued on st
+  int reset(srmap_problem* p, int c0, int C, hipStream_t st);
+  // Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): eff <- prior .* huber(A x - y), enqueued on st
+  // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
+  int huber_step(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
+
+ private:
+  int ensure_ones(srmap_problem* p, hipStream_t st);
+  int rebuild(srmap_problem* p, hipStream_t st);
+  DevBuf eff_, user_, prior_;
+  int loss_ = SRMAP_DATA_LOSS_L2;
+  double delta_ = 0.0;
+};
+
+}  // namespace srmap

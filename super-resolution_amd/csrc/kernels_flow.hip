@@ -163,8 +163,7 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
       if (rc) return rc;
     }
     double counts[3] = {0.0, 0.0, 0.0};
-    rc = p->dtype == SRMAP_F32 ? flow_seed_and_check<float>(p, nf.as<const float>(), ns.as<int>(), counts, st)
-                               : flow_seed_and_check<double>(p, nf.as<const double>(), ns.as<int>(), counts, st);
+    rc = dispatch_dtype(p->dtype, [&](auto t) { return flow_seed_and_check<decltype(t)>(p, nf.as<const decltype(t)>(), ns.as<int>(), counts, st); });
     if (rc) return rc;
     // the problem keeps the motion it had
     if (counts[0] != 0.0)

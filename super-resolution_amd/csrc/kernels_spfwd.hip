@@ -341,25 +341,22 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   const int chi = omax - hb + B;  // rightmost column offset of the last cell's stencil
   const int cq = chi >= 0 ? chi / S : -((-chi + S - 1) / S);
   sp->XC = kCW + cq - sp->CLO;
-  const size_t lds = (size_t)sp->XR * S * sp->XC * (p->dtype == SRMAP_F32 ? 4 : 8);
+  const size_t lds = (size_t)sp->XR * S * sp->XC * p->elem();
   if (sp->XR > kMaxRowsPerWave * kNW || sp->XC > 2 * kCW || sp->XC < kCW || lds > 64 * 1024) return false;
-  const bool ok = p->dtype == SRMAP_F32 ? upload_frames<float>(p, sp) : upload_frames<double>(p, sp);
+  const bool ok = dispatch_dtype(p->dtype, [&](auto t) { return upload_frames<decltype(t)>(p, sp); });
   if (!ok) { *sp = SpForwardPlan(); return false; }
   sp->ok = true;
   // fold (solver line search): a workgroup walks the union of its window and its own S kLRH x S kCW pixels
   sp->RF0 = std::min(sp->RLO, 0); sp->NRF = std::max(sp->RLO + sp->XR, S * kLRH) - sp->RF0;
   sp->CF0 = std::min(sp->CLO, 0); sp->NCF = std::max(sp->CLO + sp->XC, kCW) - sp->CF0;
   sp->can_fold = sp->NRF <= kMaxRowsPerWave * kNW && sp->NCF <= 2 * kCW;
-  const bool wt = p->robust();
-  if (p->dtype == SRMAP_F32) {
-    if (S == 2 && B == 1) preload_typed<float, 2, 1>(wt); else if (S == 2) preload_typed<float, 2, 3>(wt);
-    else if (S == 3 && B == 1) preload_typed<float, 3, 1>(wt); else if (S == 3) preload_typed<float, 3, 3>(wt);
-    else if (B == 1) preload_typed<float, 4, 1>(wt); else preload_typed<float, 4, 3>(wt);
-  } else {
-    if (S == 2 && B == 1) preload_typed<double, 2, 1>(wt); else if (S == 2) preload_typed<double, 2, 3>(wt);
-    else if (S == 3 && B == 1) preload_typed<double, 3, 1>(wt); else if (S == 3) preload_typed<double, 3, 3>(wt);
-    else if (B == 1) preload_typed<double, 4, 1>(wt); else preload_typed<double, 4, 3>(wt);
-  }
+  const bool wt = p->dw.robust();
+  dispatch_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    if (S == 2 && B == 1) preload_typed<T, 2, 1>(wt); else if (S == 2) preload_typed<T, 2, 3>(wt);
+    else if (S == 3 && B == 1) preload_typed<T, 3, 1>(wt); else if (S == 3) preload_typed<T, 3, 3>(wt);
+    else if (B == 1) preload_typed<T, 4, 1>(wt); else preload_typed<T, 4, 3>(wt);
+  });
   return true;
 }
 

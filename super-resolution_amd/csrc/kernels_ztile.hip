@@ -559,7 +559,7 @@ bool ztile_plan(srmap_problem* p) {
   // forward-residual form gathers a residual BUFFER, which the weighted forward kernel fills with w .* r.  An integer
   // shift is its one-tap case: the source table and the forward kernel's stencils walk ntaps taps.  Without a
   // MotionModule there are no warp records for that form (ring kernel, forward tile kernel): the direct family runs.
-  const bool robust = p->robust();
+  const bool robust = p->dw.robust();
   if (robust && !p->has_motion) return false;
   bool subpix = robust;
   if (p->has_motion) {
@@ -736,7 +736,7 @@ bool ztile_plan(srmap_problem* p) {
       return z->d_bd.alloc(sizeof(bd)) == hipSuccess &&
              hipMemcpy(z->d_bd.as(), &bd, sizeof(bd), hipMemcpyHostToDevice) == hipSuccess;
     };
-    ok = p->dtype == SRMAP_F32 ? put(BorderArgs<float>()) : put(BorderArgs<double>());
+    ok = dispatch_dtype(p->dtype, [&](auto t) { return put(BorderArgs<decltype(t)>()); });
   }
   p->zplan = z;
   if (ok) {
@@ -940,8 +940,7 @@ static void preload_instances(int S, int B, int regk, int regr) {
 void ztile_preload(const srmap_problem* p) {
   const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
   if (!z) return;
-  if (p->dtype == SRMAP_F32) preload_instances<float>(z->S, z->B, z->regk, z->regr);
-  else preload_instances<double>(z->S, z->B, z->regk, z->regr);
+  dispatch_dtype(p->dtype, [&](auto t) { preload_instances<decltype(t)>(z->S, z->B, z->regk, z->regr); });
 }
 
 template <typename T>
@@ -985,7 +984,7 @@ int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const 
     if (!p->d_resid) SRMAP_HIP(p->ctx, p->d_resid.alloc(p->lr_count() * sizeof(T)));
     if (req.fold.xk != nullptr && !(with_d && z.spf.ok && z.spf.can_fold))
       return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
-    const T* dw = p->d_dw.as<const T>();  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
+    const T* dw = p->dw.effective<T>();  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
     if (z.spf.ok)
       rc = launch_forward_sp<T>(p, geo, z.spf, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), partials, &nfwd, st, req.fold, dw);
     else

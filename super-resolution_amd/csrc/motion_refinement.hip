@@ -134,8 +134,8 @@ template <typename T>
 void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, int ppt, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
-  if (p->d_dw)
-    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), p->d_dw.as<const T>(), g,
+  if (p->dw.effective<T>())
+    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), p->dw.effective<T>(), g,
                        p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part);
   else
     hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), (const T*)nullptr, g,
@@ -222,8 +222,7 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   auto pass = [&]() -> bool {
     for (int k = 0; k < K; ++k) fit.set(k, fs[k].Gt, fs[k].active);
     if (!fit.upload(st)) return false;
-    if (p->dtype == SRMAP_F32) launch_sums<float>(p, (const float*)x_dev, fit.d_tab.as<double>(), chunks, ppt, fit.d_part.as<double>(), st);
-    else launch_sums<double>(p, (const double*)x_dev, fit.d_tab.as<double>(), chunks, ppt, fit.d_part.as<double>(), st);
+    dispatch_dtype(p->dtype, [&](auto t) { launch_sums<decltype(t)>(p, (const decltype(t)*)x_dev, fit.d_tab.as<double>(), chunks, ppt, fit.d_part.as<double>(), st); });
     return fit.reduce_and_fetch(chunks, st);
   };
 

@@ -100,8 +100,8 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
   const MotionArgs<T> ma = motion_args<T>(p);
   return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
-    if (p->d_dw)
-      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->d_dw.as<const T>(), g, ma,
+    if (p->dw.effective<T>())
+      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->dw.effective<T>(), g, ma,
                          p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part);
     else
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, ma,
@@ -116,12 +116,11 @@ int photometric_normalise(srmap_problem* p, hipStream_t st) {
   const size_t total = p->lr_count(), per_frame = total / p->geo.K;
   if (!p->d_obs) SRMAP_HIP(p->ctx, p->d_obs.alloc(total * p->elem()));
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (p->dtype == SRMAP_F32)
-    hipLaunchKernelGGL(k_photometric_normalise<float>, grid, dim3(256), 0, st, p->d_obs_raw.as<const float>(), p->d_obs.as<float>(),
+  dispatch_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_photometric_normalise<T>, grid, dim3(256), 0, st, p->d_obs_raw.as<const T>(), p->d_obs.as<T>(),
                        p->d_photo.as<double>(), per_frame, total);
-  else
-    hipLaunchKernelGGL(k_photometric_normalise<double>, grid, dim3(256), 0, st, p->d_obs_raw.as<const double>(),
-                       p->d_obs.as<double>(), p->d_photo.as<double>(), per_frame, total);
+  });
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
@@ -240,8 +239,7 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
   const AffineMap identity = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};  // the table carries the active flags alone here
   for (int k = 0; k < K; ++k) fit.set(k, identity, true);
   if (!fit.upload(st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: upload failed");
-  if (!(p->dtype == SRMAP_F32 ? launch_sums<float>(p, (const float*)x_dev, chunks, ppt, fit.d_part.as<double>(), st)
-                              : launch_sums<double>(p, (const double*)x_dev, chunks, ppt, fit.d_part.as<double>(), st)))
+  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, (const decltype(t)*)x_dev, chunks, ppt, fit.d_part.as<double>(), st); }))
     return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)motion_kind(p));
   if (!fit.reduce_and_fetch(chunks, st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: pass failed");
 

@@ -434,10 +434,9 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
     SRMAP_HIP(ctx, hipMemcpyAsync(pyr, io.images_dev, (size_t)K * n * sizeof(double), hipMemcpyDeviceToDevice, st));
   } else {
     const srmap_problem* p = io.problem;
-    if (p->dtype == SRMAP_F32)
-      hipLaunchKernelGGL(k_flow_plane<float>, dim3(blocks_of(n), K), dim3(256), 0, st, p->d_obs.as<const float>(), p->geo.C, io.channel, n, pyr);
-    else
-      hipLaunchKernelGGL(k_flow_plane<double>, dim3(blocks_of(n), K), dim3(256), 0, st, p->d_obs.as<const double>(), p->geo.C, io.channel, n, pyr);
+    dispatch_dtype(p->dtype, [&](auto t) {
+      hipLaunchKernelGGL(k_flow_plane<decltype(t)>, dim3(blocks_of(n), K), dim3(256), 0, st, p->d_obs.as<const decltype(t)>(), p->geo.C, io.channel, n, pyr);
+    });
   }
   if (cnt_blocks > 0)
     hipLaunchKernelGGL(k_flow_count_nonfinite, dim3(cnt_blocks, K), dim3(256), 0, st, (const double*)pyr, n, rec + rec_quality);
@@ -609,7 +608,7 @@ extern "C" int srmap_problem_register_flow(srmap_problem* p, int channel, const 
   FlowBuffers b;
   if (int rc = register_flow_body(ctx, g.K, g.w, g.h, opt, io, b, st, quality_out)) return rc;
   const bool prior = install_prior != 0;
-  if (int rc = p->dtype == SRMAP_F32 ? problem_stage<float>(p, b, prior, st) : problem_stage<double>(p, b, prior, st)) return rc;
+  if (int rc = dispatch_dtype(p->dtype, [&](auto t) { return problem_stage<decltype(t)>(p, b, prior, st); })) return rc;
   // a refused field leaves the motion -- and the prior -- the problem had
   if (int rc = srmap_problem_set_flow_device(p, b.field.as(), st)) return rc;
   return prior ? srmap_set_data_prior_device(p, b.prior.as(), st) : SRMAP_OK;

@@ -16,7 +16,7 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what) {
   if (mode == SRMAP_SHARD_NONE) return SRMAP_OK;
   const bool solve = std::strcmp(what, "solve") == 0;
   const char* tail = solve ? "run the solve unsharded" : "evaluate unsharded";
-  if (p->robust())
+  if (p->dw.robust())
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator%s: %s",
                      solve ? " (the weights are not split with the frames or rows)" : "", tail);
   if (p->affine)
@@ -40,7 +40,7 @@ int shard_exchange_x(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd
   char* x = (char*)x_dev;
   if (sd->mode == SRMAP_SHARD_ROWS) {
     // a frame whose warpAffine y coordinate sits on a 1/32-px rounding tie carries a per-row table built from the row
-    // index of THIS problem (srmap_api.hip make_warp): a band problem would evaluate the tie at its local rows, not
+    // index of THIS problem (model_tables.hpp make_warp): a band problem would evaluate the tie at its local rows, not
     // the joint image's
     if (!p->d_ytabs.empty())
       return set_error(p->ctx, SRMAP_EUNSUPPORTED, "row shard: a sub-pixel shift on a 1/32-px rounding tie needs the joint image's row index; shard such problems by frames or channels");

@@ -695,7 +695,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   const bool lbfgs = p->solver == SRMAP_SOLVER_LBFGS;
   if (lbfgs && mode != SRMAP_SHARD_NONE)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
-  const bool huber = p->data_loss == SRMAP_DATA_LOSS_HUBER;
+  const bool huber = p->dw.loss() == SRMAP_DATA_LOSS_HUBER;
   if (int rc = refuse_sharded(p, mode, "solve")) return rc;
   if (mode != SRMAP_SHARD_NONE && opt->split_channels)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
@@ -753,7 +753,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   }
   int rc = cg.alloc();
   if (rc == SRMAP_OK && lbfgs) rc = cg.alloc_lbfgs(p->lbfgs_m);
-  if (rc == SRMAP_OK && huber && !p->d_dw) rc = set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
+  if (rc == SRMAP_OK && huber && !p->dw.effective<T>()) rc = set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
   // IRLS weights live in the problem's RegSpec (full [C][H][W]); make sure they exist.
   for (int r = 0; r < p->nreg && rc == SRMAP_OK; ++r) {
     if (!p->reg[r].weights && p->reg[r].weights.alloc(p->hr_count() * sizeof(T)) != hipSuccess)
@@ -769,15 +769,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     // w <- 1  (irls_map_solver.cpp:66-74)
     for (int r = 0; r < p->nreg; ++r)
       launch_fill<T>(p->reg[r].weights.as<T>() + (size_t)c0 * N, T(1), npts, st);
-    if (huber) {  // the data weights of this round's channels likewise ([K][C][h][w]: one run per frame)
-      if (p->d_prior) {  // a prior on the weights is what they are reset to
-        rc = reset_data_weights(p, c0, per_split, st);
-        if (rc) break;
-      } else {
-        const size_t nl = (size_t)geo.w * geo.h, run = (size_t)per_split * nl;
-        for (int k = 0; k < geo.K; ++k)
-          launch_fill<T>(p->d_dw.as<T>() + ((size_t)k * C + c0) * nl, T(1), run, st);
-      }
+    if (huber) {  // the data weights of this round's channels likewise, or to their prior
+      rc = p->dw.reset(p, c0, per_split, st);
+      if (rc) break;
     }
     double previous_cost = INFINITY;
     double cost_difference = o.irls_cost_difference_threshold + 1.0;
@@ -805,7 +799,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
       }
       if (rc) break;
       // Huber: the data weights from the residuals at the same iterate
-      if (huber) rc = update_data_weights(p, c0, per_split, cg.x, st);
+      if (huber) rc = p->dw.huber_step(p, c0, per_split, cg.x, st);
       if (rc) break;
       cost_difference = previous_cost - cr.f;
       previous_cost = cr.f;
@@ -826,12 +820,6 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   rc = cg.recover_timeout(rc);
   if (report) *report = rep;
   return rc;
-}
-
-int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, const srmap_irls_options* o,
-               const double* x0, double* x_out, srmap_solve_report* rep) {
-  if (p->dtype == SRMAP_F32) return solve_typed<float>(p, comm, shard, o, x0, x_out, rep);
-  return solve_typed<double>(p, comm, shard, o, x0, x_out, rep);
 }
 
 // One nonlinear-CG run (no IRLS re-weighting) with the f of every evaluation recorded: the trajectory the tests
@@ -874,9 +862,9 @@ int srmap_cg_trace(srmap_problem* p, double epsg, double epsf, double epsx, int 
   if (!p || !x0 || !x_out || (trace_cap > 0 && !f_trace)) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  if (p->dtype == SRMAP_F32)
-    return cg_trace_typed<float>(p, 0, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
-  return cg_trace_typed<double>(p, 0, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  return dispatch_dtype(p->dtype, [&](auto t) {
+    return cg_trace_typed<decltype(t)>(p, 0, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  });
 }
 
 int srmap_lbfgs_trace(srmap_problem* p, int m, double epsg, double epsf, double epsx, int maxits, const double* x0,
@@ -887,9 +875,51 @@ int srmap_lbfgs_trace(srmap_problem* p, int m, double epsg, double epsf, double 
   if (m > kLbfgsMaxM) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "num_lbfgs_hessian_corrections %d: at most %d are supported", m, kLbfgsMaxM);
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  if (p->dtype == SRMAP_F32)
-    return cg_trace_typed<float>(p, m, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
-  return cg_trace_typed<double>(p, m, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  return dispatch_dtype(p->dtype, [&](auto t) {
+    return cg_trace_typed<decltype(t)>(p, m, epsg, epsf, epsx, maxits, x0, x_out, iterations, nfev, termination, f_trace, trace_cap, trace_len);
+  });
+}
+
+void srmap_irls_options_default(srmap_irls_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_irls_options);
+  o->max_num_solver_iterations = 50;
+  o->gradient_norm_threshold = 1.0e-6;
+  o->cost_decrease_threshold = 1.0e-6;
+  o->parameter_variation_threshold = 1.0e-6;
+  o->split_channels = 0;
+  o->max_num_irls_iterations = 20;
+  o->irls_cost_difference_threshold = 1.0e-5;
+  o->host_paced_passes = 0;
+}
+
+int srmap_solve_sharded(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
+                        const srmap_irls_options* options, const double* x0, double* x_out,
+                        srmap_solve_report* report) {
+  if (!p || !x0 || !x_out) return SRMAP_EINVAL;
+  srmap_irls_options o;
+  if (options) {
+    // the first member is the size of the struct the caller was compiled with: another layout is refused, not guessed at
+    if (options->struct_size != (int)sizeof(srmap_irls_options))
+      return set_error(p->ctx, SRMAP_EINVAL, "srmap_irls_options: struct_size %d, this library expects %d (fill the struct with "
+                       "srmap_irls_options_default() of the matching include/srmap.h)", options->struct_size, (int)sizeof(srmap_irls_options));
+    o = *options;
+  } else {
+    srmap_irls_options_default(&o);
+  }
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  return dispatch_dtype(p->dtype, [&](auto t) { return solve_typed<decltype(t)>(p, comm, shard, &o, x0, x_out, report); });
+}
+
+int srmap_problem_selfcheck(const srmap_problem* p, double* beta_denominator_rel_dev) {
+  if (!p || !beta_denominator_rel_dev) return SRMAP_EINVAL;
+  *beta_denominator_rel_dev = p->selfcheck_beta_den;
+  return SRMAP_OK;
+}
+
+int srmap_solve(srmap_problem* p, const srmap_irls_options* options, const double* x0, double* x_out,
+                srmap_solve_report* report) {
+  return srmap_solve_sharded(p, nullptr, nullptr, options, x0, x_out, report);
 }
 
 }  // extern "C"

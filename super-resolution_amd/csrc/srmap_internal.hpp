@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "data_weights.hpp"
 #include "dev_mem.hpp"
 #include "srmap.h"
 
@@ -174,16 +175,8 @@ struct srmap_problem {
   srmap::DevBuf d_photo;          // double[K][2]
   srmap::DevBuf d_obs_raw;        // [K][C][h][w] dtype
   srmap::DevBuf d_resid;          // [K][C][h][w] dtype scratch
-  srmap::DevBuf d_dw;             // [K][C][h][w] dtype data weights (srmap_set_data_weights*, the Huber loss); nullptr = all ones
-  int data_loss = SRMAP_DATA_LOSS_L2;  // srmap_problem_set_data_loss; HUBER keeps d_dw allocated (it owns the buffer)
-  double huber_delta = 0.0;
-  // persistent prior m on the data weights (srmap_set_data_prior): while set, d_dw = m .* w (allocated, so the problem is
-  // robust()) and d_dw_user keeps the caller's weights w (nullptr = ones); both nullptr otherwise
-  srmap::DevBuf d_prior;          // [K][C][h][w] dtype
-  srmap::DevBuf d_dw_user;        // [K][C][h][w] dtype
-  // weights or a Huber loss: every evaluation runs a WEIGHTED forward kernel, and the tile plan takes the forward-residual
-  // form for integer shifts too (kernels_ztile.hip ztile_plan)
-  bool robust() const { return d_dw || data_loss == SRMAP_DATA_LOSS_HUBER; }
+  // per-observation weights of the data term, their prior and the loss: the states and who re-plans, data_weights.hpp
+  srmap::DataWeights dw;
   srmap::DevBuf d_regvals;        // [C][H][W] dtype scratch
   srmap::DevBuf d_x;              // [C][H][W] staging for host-buffer entry points
   srmap::DevBuf d_g;
@@ -217,6 +210,7 @@ struct srmap_problem {
 
 namespace srmap {
 
+// ---- the error text (srmap_api.hip); the context's rocBLAS handle (channel_map.hip) ----
 int set_error(srmap_ctx* ctx, int status, const char* fmt, ...);
 void blas_release(srmap_ctx* ctx);
 
@@ -227,6 +221,20 @@ void blas_release(srmap_ctx* ctx);
       return ::srmap::set_error((ctx), SRMAP_EHIP, "%s failed: %s (%s:%d)", #call, \
                                 hipGetErrorString(e_), __FILE__, __LINE__);      \
   } while (0)
+
+// f(T()) with T the element type of `dtype`, float or double; what f returns.  The one switch from the run-time dtype to
+// the template instances: f is a generic lambda that names T as decltype of its argument
+template <typename F>
+auto dispatch_dtype(int dtype, F&& f) {
+  if (dtype == SRMAP_F32) return f(float());
+  return f(double());
+}
+
+// allocate a lazily created buffer of the problem if it is not there yet
+inline int ensure(srmap_problem* p, DevBuf* buf, size_t bytes) {
+  if (!*buf) SRMAP_HIP(p->ctx, buf->alloc(bytes));
+  return SRMAP_OK;
+}
 
 // ---- kernel launchers (kernels_direct.hip) ----
 // out = A_k x (y == nullptr) or A_k x - y_k for frames [k0, k0+nk); optional
@@ -266,7 +274,7 @@ template <int... KINDS, typename F>
 bool dispatch_motion(int kind, F&& f) {
   return ((kind == KINDS && (f(std::integral_constant<int, KINDS>()), true)) || ...);
 }
-// K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (srmap_api.hip)
+// K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (problem.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
 // ---- the motion fits' shared kernels and per-pass buffers (motion_fit.hip) ----
 struct AffineMap;  // affine_map.hpp
@@ -346,31 +354,28 @@ int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan
                       int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st,
                       const SpFold& fold = SpFold(), const T* dw = nullptr);
 
-// ---- a change of the model (srmap_api.hip): every setter checks its arguments, builds the new buffers in locals (a
+// ---- a change of the model (problem.hip): every setter checks its arguments, builds the new buffers in locals (a
 // failure leaves the problem as it was), then model_drain, swap, model_replan ----
 int model_drain(srmap_problem* p);    // wait for the evaluations in flight: they read the buffers about to change
 void model_replan(srmap_problem* p);  // a new plan generation, the tile plan for the model now in force and its preload
 
-// ---- evaluation (srmap_api.hip) ----
+// ---- evaluation (eval.hip) ----
 // One ObjectiveFunction::ComputeAllTerms on device buffers, on the stream st (srmap_eval_device with a request).
 int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned terms, const void* x, void* g,
                   hipStream_t st);
+// d_partials sized for any evaluation of the problem (and for the forward residual of a Huber step)
+int ensure_eval_partials(srmap_problem* p);
 // After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[6]; the host-mapped word
 // host_word when given): re-initialise the granules behind everything in flight and clear both words.
 int recover_reduction_timeout(srmap_problem* p, double* host_word);
+// Stream ordering of the problem's device state (include/srmap.h, "Streams").  Before overwriting observations or
+// weights on st: the last evaluation may still be reading them on another stream
+int state_begin_write(srmap_problem* p, hipStream_t st);
+// after an ASYNCHRONOUS write on st: later evaluations on other streams wait for this event
+int state_end_write(srmap_problem* p, hipStream_t st);
 // A reader of the problem's device state (observations, weights) on st that is not an evaluation (motion_refinement.hip):
 // ordered after the last asynchronous state write, and recorded as the stream a later writer drains
 int problem_state_read(srmap_problem* p, hipStream_t st);
-// Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): data weights <- huber(A x - y), enqueued on st
-// (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
-int update_data_weights(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
-// the start of a Huber solve on the channels [c0, c0 + C): data weights <- 1, or the prior where one is set; enqueued on st
-int reset_data_weights(srmap_problem* p, int c0, int C, hipStream_t st);
-
-// ---- solver (solver.hip) ----
-int solve_impl(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
-               const srmap_irls_options* o, const double* x0, double* x_out,
-               srmap_solve_report* rep);
 
 // ---- L-BFGS passes (kernels_lbfgs.hip) ----
 constexpr int kLbfgsMaxM = 8;  // history cap of srmap_problem_set_solver (bounds the update pass's accumulators)
@@ -400,7 +405,7 @@ template <typename T>
 int launch_lbfgs_direction(T* dn, const T* g, const T* S, const T* Y, int live, const LbfgsCoef& c, size_t n, int nb,
                            int keep_dn, const LbfgsRed& red, hipStream_t st);
 
-// conversions / staging
+// ---- conversions / staging (transfer.hip) ----
 int ensure_staging(srmap_ctx* ctx);
 int convert_upload(srmap_problem* p, const double* host, void* dev, size_t n,
                    hipStream_t st);

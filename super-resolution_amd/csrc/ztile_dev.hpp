@@ -233,7 +233,7 @@ __device__ __forceinline__ void finish_block(const ArgsT& A, double* red /* LDS,
   }
   // re-arm: the next evaluation finds every granule unpublished.  NOT after a time-out: a workgroup that arrives late
   // would publish into a re-armed slot and the next evaluation would consume that stale partial; the granules stay as
-  // they are, cost_out[0] is NaN, the sticky word cost_out[6] tells the host to re-initialise them (srmap_api.hip).
+  // they are, cost_out[0] is NaN, the sticky word cost_out[6] tells the host to re-initialise them (eval.hip).
   if (timed_out) {
     if (tid == 0) { A.cost_out[0] = __builtin_nan(""); A.cost_out[6] = 1.0; if (A.to_host != nullptr) *(volatile double*)A.to_host = 1.0; if (WD && A.pub != nullptr) { A.pub[0] = A.cost_out[0]; A.pub[1] = 0.0; __threadfence_system(); *(volatile double*)A.tag_slot = A.tag; } }
     return;

@@ -17,7 +17,7 @@ width is 28, at which no band is planned.
 R5's y shift: a shift of an exact odd multiple of 1/64 px is a quantisation tie that double arithmetic resolves the same
 way in every row, so its warp table is uniform and a row shard evaluates it correctly -- nothing is refused.  The
 refusal belongs to a dy within floating-point rounding of such a tie, (16.5 + 1e-10) / 1024 here, whose rounding
-direction depends on the row index (srmap_api.hip make_warp: the per-row table).  test_shard_matrix_cpu.py asserts with
+direction depends on the row index (model_tables.hpp make_warp: the per-row table).  test_shard_matrix_cpu.py asserts with
 the oracle's warp tables that every band of R5 really has a non-uniform table, forward and transposed.
 """
 import numpy as np

@@ -129,7 +129,7 @@ def test_integer_plan_threshold(sr, ctx, S, axis):
 
 
 def _warp_offsets(d):
-    """cv::warpAffine's integer source offset of a shift d (csrc/srmap_api.hip warp_tables: 1/32-px fixed point)."""
+    """cv::warpAffine's integer source offset of a shift d (csrc/model_tables.hpp warp_tables: 1/32-px fixed point)."""
     x0 = (int(np.rint(-d * 1024)) + 16) >> 5
     return x0 >> 5
 
