@@ -44,6 +44,8 @@
 //            pass 1 (values, self term, 2*lambda*w*r -> LDS); halo rows of zh /
 //            2*lambda*w*r by whole waves (0-1 / 2-3), the left halo columns one per
 //            wave (4 / 5, lanes = rows); their IRLS weights wait in LDS;
+//   barrier  the cost terms are complete: the workgroup's cost partial is published here, at the barrier between the
+//            phases (the g.d partial of the WD instances needs the finished gradient and follows the g store);
 //   phase 2  vertical half of B^T from zh; regulariser pass 2; g store.
 // The frame table's counts and round 0 travel by value in the kernel arguments
 // (scalar loads only); later rounds are read through the constant address space.
@@ -370,7 +372,23 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 || S 
       }
     }
   }
+  // ---------------- cost partial of this workgroup ----------------
+  // The cost terms are complete here (phase 2 adds to the gradient only), so the partial leaves at the barrier the
+  // workgroup holds anyway: behind the g stores it cost a wave sum, a third barrier -- at which the waves that finish
+  // phase 2 early waited for the others -- and the publishing store's round trip at the very end of the workgroup's life.
+  // Same wave sum, same order of the eight additions as before: the cost is unchanged bit for bit.
+  {
+    const double cw = wave_sum_d((double)(S * S) * cost_data + cost_reg);
+    if (lane == 0) red[0][wv] = cw;
+  }
   __syncthreads();
+  const size_t pidx = ((size_t)blockIdx.z * nby_t + by) * gridDim.x + blockIdx.x;  // this workgroup's partial
+  if (!WD && tid == 0) {
+    double c = 0.0;
+#pragma unroll
+    for (int i = 0; i < C::NW; ++i) c += red[0][i];
+    put_partial<false>(A, pidx, c, 0.0);
+  }
 
   // ---------------- phase 2 ----------------
   T dreg[S];  // WD: the search direction at this thread's pixels (g.d is produced with g)
@@ -428,29 +446,25 @@ __global__ __launch_bounds__((ZCfg<T, S, B, REGK, R>::NT), (sizeof(T) == 4 || S 
     for (int pc = 0; pc < S; ++pc) __builtin_nontemporal_store(acc[pc], &dst[pc]);  // written once, not re-read here
   }
 
-  // ---------------- cost partial of this workgroup ----------------
-  {
+  // ---------------- g.d partial (WD instances: needs the finished gradient) ----------------
+  if (WD) {
     double gd = 0.0;
-    if (WD) {
 #pragma unroll
-      for (int pc = 0; pc < S; ++pc) gd += (double)acc[pc] * (double)dreg[pc];
-      gd = wave_sum_d(gd);
-    }
-    const double cw = wave_sum_d((double)(S * S) * cost_data + cost_reg);
-    if (lane == 0) { red[0][wv] = cw; if (WD) red[1][wv] = gd; }
+    for (int pc = 0; pc < S; ++pc) gd += (double)acc[pc] * (double)dreg[pc];
+    gd = wave_sum_d(gd);
+    if (lane == 0) red[1][wv] = gd;
     __syncthreads();
     if (tid == 0) {
       double c = 0.0, d = 0.0;
 #pragma unroll
-      for (int i = 0; i < C::NW; ++i) { c += red[0][i]; if (WD) d += red[1][i]; }
-      const size_t b = ((size_t)blockIdx.z * nby_t + by) * gridDim.x + blockIdx.x;
-      put_partial<WD>(A, b, c, d);
+      for (int i = 0; i < C::NW; ++i) { c += red[0][i]; d += red[1][i]; }
+      put_partial<true>(A, pidx, c, d);
     }
-    // in-kernel finish: the last workgroup of the grid gathers the granules of the evaluation
-    if (A.mfinish && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) {
-      __syncthreads();
-      finish_block<WD, C::NT>(A, &red[0][0]);
-    }
+  }
+  // in-kernel finish: the last workgroup of the grid gathers the granules of the evaluation (after its own g stores)
+  if (A.mfinish && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) {
+    __syncthreads();
+    finish_block<WD, C::NT>(A, &red[0][0]);
   }
 }
 
