@@ -123,7 +123,7 @@ bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
   const MotionArgs<T> ma = motion_args<T>(p);
-  return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->dw.effective<T>())
       hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),

@@ -1,7 +1,9 @@
 // data_weights.hip -- DataWeights (data_weights.hpp: the legal states and what each buffer holds in them) and the C
 // entry points of the robust data term (no reference counterpart).  The only code that moves the
 // data-weight buffers.
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <utility>
 
 #include "solver_passes.hpp"
@@ -10,6 +12,100 @@
 using namespace srmap;
 
 namespace srmap {
+
+namespace {  // the kernels of the data weights: only this file launches them
+
+// ---------------------------------------------------------------------------
+// Huber IRLS weights of the data term from the UNWEIGHTED residuals: w = 1 where |r| <= delta, delta / |r| elsewhere
+// (continuous at |r| = delta), arithmetic in T.  Elementwise and HBM-bound: one read and one write stream.  `rows` runs of
+// `rowlen` elements (blockIdx.y = run; a channel view of [K][C][h][w] is K runs, the whole stack one).  VEC: every run
+// starts on a 16-byte boundary in both buffers -- 16-byte accesses in a grid-stride loop, the run's last elements one by one.
+template <typename T>
+__device__ __forceinline__ T huber_weight(T r, T delta) {
+  const T a = r < T(0) ? -r : r;
+  return a <= delta ? T(1) : delta / a;
+}
+
+// PRIOR: a third stream m, indexed like w (the persistent prior of srmap_set_data_prior): w = m .* huber(r), the product
+// rounded once in T.  The instance without it reads nothing of m.
+template <typename T, bool VEC, bool PRIOR = false>
+__global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, T* __restrict__ w, size_t rowlen,
+                                                      size_t r_stride, size_t w_stride, T delta,
+                                                      const T* __restrict__ m = nullptr) {
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
+  const T* rr = r + (size_t)blockIdx.y * r_stride;
+  T* ww = w + (size_t)blockIdx.y * w_stride;
+  const T* mm = PRIOR ? m + (size_t)blockIdx.y * w_stride : nullptr;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nv = rowlen / V;
+    for (size_t i = tid; i < nv; i += nth) {
+      const VT v = reinterpret_cast<const VT*>(rr)[i];
+      VT o;
+#pragma unroll
+      for (int q = 0; q < V; ++q) o[q] = huber_weight<T>(v[q], delta);
+      if constexpr (PRIOR) {
+        const VT pv = reinterpret_cast<const VT*>(mm)[i];
+#pragma unroll
+        for (int q = 0; q < V; ++q) o[q] = pv[q] * o[q];
+      }
+      reinterpret_cast<VT*>(ww)[i] = o;
+    }
+    done = nv * V;
+  }
+  for (size_t i = done + tid; i < rowlen; i += nth) {
+    const T hw = huber_weight<T>(rr[i], delta);
+    if constexpr (PRIOR) ww[i] = mm[i] * hw;
+    else ww[i] = hw;
+  }
+}
+
+// r: `rows` runs of `rowlen` elements, r_stride apart; w likewise, w_stride apart, starting at w (a channel view of
+// [K][C][h][w]).  prior != nullptr (indexed like w): the instance with the prior as a third stream
+template <typename T>
+int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
+                         double delta, hipStream_t st, const T* prior) {
+  constexpr size_t V = 16 / sizeof(T);
+  if (rows == 0 || rowlen == 0) return SRMAP_OK;
+  if (rows > 1 && r_stride == rowlen && w_stride == rowlen) { rowlen *= rows; rows = 1; }  // one contiguous run
+  const bool vec = (reinterpret_cast<uintptr_t>(r) % 16 == 0) && (reinterpret_cast<uintptr_t>(w) % 16 == 0) &&
+                   (reinterpret_cast<uintptr_t>(prior) % 16 == 0) && (rows == 1 || (r_stride % V == 0 && w_stride % V == 0));
+  // grid-stride: enough workgroups to fill the device several times over, no more than the run has 16-byte groups
+  const size_t groups = (rowlen + V * 256 - 1) / (V * 256);
+  const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
+  dim3 grid((unsigned)std::max<size_t>(1, std::min(groups, (cap + rows - 1) / rows)), (unsigned)rows);
+  if (prior) {
+    if (vec) hipLaunchKernelGGL((k_huber_weights<T, true, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
+    else hipLaunchKernelGGL((k_huber_weights<T, false, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
+  } else if (vec) {
+    hipLaunchKernelGGL((k_huber_weights<T, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, (const T*)nullptr);
+  } else {
+    hipLaunchKernelGGL((k_huber_weights<T, false>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, (const T*)nullptr);
+  }
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  return SRMAP_OK;
+}
+
+// out = a .* b (b == nullptr: out = a), one rounding in T: the effective data weights m .* w of a problem with a prior,
+// rebuilt whenever either factor changes.  Elementwise, grid-stride.
+template <typename T>
+__global__ __launch_bounds__(256) void k_weight_product(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = b ? a[i] * b[i] : a[i];
+}
+
+template <typename T>
+int launch_weight_product(srmap_problem* p, const T* a, const T* b, T* out, size_t n, hipStream_t st) {
+  if (n == 0) return SRMAP_OK;
+  const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
+  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min((n + 255) / 256, cap));
+  hipLaunchKernelGGL(k_weight_product<T>, dim3(blocks), dim3(256), 0, st, a, b, out, n);
+  SRMAP_HIP(p->ctx, hipGetLastError());
+  return SRMAP_OK;
+}
+
+}  // namespace
 
 // Weights or the loss changed whether the problem is robust(): the tile plan has another form then (ztile_plan)
 static void replan_if(srmap_problem* p, bool was_robust) {

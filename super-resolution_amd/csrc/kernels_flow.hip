@@ -5,7 +5,7 @@
 // warp samples x bilinearly at s = q + u_k(q) for every pixel q of the warped image (taps outside the image contribute 0:
 // affine_sample); blur and decimation are the translational path's.  s = (double)q + (double)u is exact in double for
 // both dtypes (|u| <= 2^20), and the weights are the double products rounded to T, as in the affine model.  The kernels
-// that evaluate it are k_forward_direct and k_gather_sampled (kernels_direct.hip) through MotionSampler's flow kind
+// that evaluate it are k_forward_direct and k_gather_sampled (kernels_data_direct.hip) through MotionSampler's flow kind
 // (sample_dev.hpp).
 //
 // The transpose is the EXACT transpose of that matrix in gather form.  For an HR pixel p the contributing q are those with

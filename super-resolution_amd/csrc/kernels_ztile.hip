@@ -5,7 +5,7 @@
 // in-image border corrections have to be subtracted), for the common geometry:
 // integer motion shifts, HR = LR * S, S in {2,3,4}, blur size B in {1,3}, first
 // regulariser 2-D TV or BTV with range <= 3.  Everything else is evaluated by
-// kernels_direct.hip.
+// kernels_data_direct.hip / kernels_reg_direct.hip.
 //
 // Formulation.  With integer shifts the warp M_k and the
 // blur B are shift-invariant, so AWAY FROM THE IMAGE BORDER they commute and the

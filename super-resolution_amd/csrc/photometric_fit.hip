@@ -98,7 +98,7 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
   dim3 grid(chunks, g.K);
   const T* y = (p->d_obs_raw ? p->d_obs_raw : p->d_obs).as<const T>();  // always the RAW frames: the fit is absolute
   const MotionArgs<T> ma = motion_args<T>(p);
-  return dispatch_motion<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->dw.effective<T>())
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->dw.effective<T>(), g, ma,

@@ -1,5 +1,5 @@
 // sample_dev.hpp -- the forward model's warp M_k on the device, shared by the kernels that evaluate it (k_forward_direct
-// of kernels_direct.hip, every motion kind), the transposes in gather form of the per-pixel kinds (k_gather_sampled) and
+// of kernels_data_direct.hip, every motion kind), the transposes in gather form of the per-pixel kinds (k_gather_sampled) and
 // the kernels that fit to it (k_blur_fit_sums of blur_fit.hip, k_photometric_sums of photometric_fit.hip): ONE copy of
 // each expression AND of the choice between them (MotionSampler), so that a fit sees exactly the warped image an
 // evaluation blurs and a transpose recomputes exactly the weights its forward kernel multiplied by.  A is the type the
@@ -82,7 +82,7 @@ __device__ __forceinline__ double affine_axis_weight(double s, int p) {
   return s0 == pd ? 1.0 - f : (s0 + 1.0 == pd ? f : 0.0);
 }
 
-// (B^T D^T r)(q) at the HR pixel q = (pc, pr) inside the image: k_gather_direct's inner expression (zero-insertion
+// (B^T D^T r)(q) at the HR pixel q = (pc, pr) inside the image, the inner expression of k_gather_direct and k_gather_sampled (zero-insertion
 // upsample, correlation with kernel.t(), each stage clipped to the domain; only the taps that land on the LR grid)
 template <typename T>
 __device__ __forceinline__ T blur_t_upsampled_at(const T* __restrict__ rk, const T* __restrict__ blur_t, const Geometry& g,

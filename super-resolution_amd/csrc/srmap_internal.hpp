@@ -236,7 +236,7 @@ inline int ensure(srmap_problem* p, DevBuf* buf, size_t bytes) {
   return SRMAP_OK;
 }
 
-// ---- kernel launchers (kernels_direct.hip) ----
+// ---- the data term's direct kernels (kernels_data_direct.hip) ----
 // out = A_k x (y == nullptr) or A_k x - y_k for frames [k0, k0+nk); optional
 // cost partials (s^2 * sum of squares, double) appended at partials[0..nblocks).
 // `g` is the geometry of this evaluation (g.C may be a channel sub-range of the
@@ -246,21 +246,14 @@ template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
                           double* partials, int* nblocks, hipStream_t st, const T* dw = nullptr);
-// w = 1 where |r| <= delta, delta / |r| elsewhere (the Huber loss as an IRLS weight), arithmetic in T.  r: `rows` runs of
-// `rowlen` elements, r_stride apart; w likewise, w_stride apart, starting at w (a channel view of [K][C][h][w]).
-// prior != nullptr (indexed like w): the instance with the prior as a third stream, w = prior .* huber(r)
-template <typename T>
-int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
-                         double delta, hipStream_t st, const T* prior = nullptr);
-// out = a .* b (b == nullptr: a) over n elements, one rounding: the effective data weights of a problem with a prior
-template <typename T>
-int launch_weight_product(srmap_problem* p, const T* a, const T* b, T* out, size_t n, hipStream_t st);
 // g = (accumulate ? g : 0) + 2 s^2 sum_k A_k^T r_k   (r: [K][C][h][w])
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring = 0, T* ringbuf = nullptr);
-// ---- the problem's motion, for the launchers of the kernels that sample it (the two above, the fits) ----
+// whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
+bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
+// ---- the problem's motion, for the launchers of the kernels that sample it (kernels_data_direct.hip, the fits) ----
 inline MotionKind motion_kind(const srmap_problem* p) {
   return p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;
 }
@@ -268,11 +261,17 @@ template <typename T>
 MotionArgs<T> motion_args(const srmap_problem* p) {
   return {p->has_motion ? p->d_fwd_warps.as<const WarpTaps<T>>() : nullptr, p->d_affine.as<double>(), p->d_flow.as<const T>(), p->d_flow_seed.as<int>()};
 }
-// f(std::integral_constant<int, KIND>) for the one of KINDS... that `kind` is -- the kinds the caller has kernel instances
-// of; false (and no call) for any other, which the caller answers as an internal error
-template <int... KINDS, typename F>
-bool dispatch_motion(int kind, F&& f) {
-  return ((kind == KINDS && (f(std::integral_constant<int, KINDS>()), true)) || ...);
+// The one switch from a run-time int to the template instances: f(std::integral_constant<int, V>) for the one of
+// VALUES... that `v` is -- a motion kind: the kinds the caller has kernel instances of; false (and no call) for any other,
+// which the caller answers as an internal error
+template <int... VALUES, typename F>
+bool dispatch_value(int v, F&& f) {
+  return ((v == VALUES && (f(std::integral_constant<int, VALUES>()), true)) || ...);
+}
+// the scale of the transpose kernels at compile time: f(SC) with SC = 2, 3, 4, and 0 (the kernel reads it at run time) otherwise
+template <typename F>
+void dispatch_scale(int s, F&& f) {
+  if (!dispatch_value<2, 3, 4>(s, f)) f(std::integral_constant<int, 0>());
 }
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (problem.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
@@ -301,11 +300,15 @@ struct FitPass {
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
 int photometric_normalise(srmap_problem* p, hipStream_t st);
-// whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
-bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
+// ---- the regularisers' direct kernels (kernels_reg_direct.hip) ----
+// values[c][H][W] = the regulariser's residual value at every pixel
 template <typename T>
 int launch_reg_values(srmap_problem* p, const Geometry& geo, const RegSpec& rs,
                       const T* x, T* values, hipStream_t st);
+// the IRLS weights 1 / max(1e-5, value) in the same pass
+template <typename T>
+int launch_reg_weights(srmap_problem* p, const Geometry& geo, const RegSpec& rs,
+                       const T* x, T* weights, hipStream_t st);
 // g += d(reg)/dx with constants c = lambda_or_1 * gc[p]; optional cost partials
 // lambda * w * r^2 (only meaningful when gc are the IRLS weights).
 template <typename T>
@@ -313,9 +316,8 @@ int launch_reg_gradient_direct(srmap_problem* p, const Geometry& geo, const RegS
                                const T* x, const T* gc, double gc_scale, const T* values,
                                T* g, bool accumulate, double* partials, int* nblocks,
                                hipStream_t st);
-template <typename T>
-int launch_reg_weights(srmap_problem* p, const Geometry& geo, const RegSpec& rs,
-                       const T* x, T* weights, hipStream_t st);
+// ---- the final reduction of per-block cost partials, fixed order (kernels_reduce.hip) ----
+// `partials` must have room for n + reduce_scratch_slots(n) doubles; out[0] = sum
 int reduce_scratch_slots(size_t n);
 int launch_reduce_partials(srmap_problem* p, const double* partials, int n,
                            double* out, hipStream_t st);

@@ -1,4 +1,4 @@
-"""The covering matrix of the direct regulariser kernels (csrc/kernels_direct.hip): every values, IRLS-weights and
+"""The covering matrix of the direct regulariser kernels (csrc/kernels_reg_direct.hip): every values, IRLS-weights and
 gradient variant at the edges of its dispatch rule.  Shared by tests/test_gpu_reg_kernels.py (HIP against the oracle)
 and tests/test_reg_matrix_cpu.py (the rule mirror reaches every cell; the bars of tests/error_bars.py catch planted bugs).
 
@@ -17,7 +17,7 @@ Kinds follow srmap.h: 0 TV, 1 TV3D, 2 BTV.
 import numpy as np
 
 TV, TV3D, BTV = 0, 1, 2
-STRIP_ROWS = 4  # SRMAP_BTV_STRIP
+STRIP_ROWS = 4  # kBtvStripRows
 
 
 def cdiv(a, b):

@@ -1,5 +1,5 @@
 """The affine per-frame motion model on the GPU (include/srmap.h: srmap_problem_set_affine_motion; the affine
-instances of k_forward_direct and k_gather_sampled, csrc/kernels_direct.hip) against its numpy restatement (tests/affine_restatement.py: explicit triplets,
+instances of k_forward_direct and k_gather_sampled, csrc/kernels_data_direct.hip) against its numpy restatement (tests/affine_restatement.py: explicit triplets,
 the literal transpose), against the translational direct kernels where the two definitions coincide, and against itself.
 
 Bars: cost and every gradient element relative to max(1, |ref|), 1e-12 in f64 and 2e-5 in f32 (the project's bars).  Test

@@ -1,5 +1,5 @@
 """The persistent prior on the data weights on the GPU (include/srmap.h: srmap_set_data_prior*, srmap_get_data_prior;
-k_weight_product and the PRIOR instances of k_huber_weights in csrc/kernels_direct.hip, the reset of csrc/solver.hip)
+k_weight_product and the PRIOR instances of k_huber_weights in csrc/data_weights.hip, the reset of csrc/solver.hip)
 against the library itself -- a problem with prior m and weights w must be, bit for bit, the problem whose weights are the
 product in its dtype -- and against the numpy restatement (tests/data_prior_restatement.py).
 

@@ -225,6 +225,9 @@ SUBPIX_CASES = [
     # table with null records behind the last source
     (96, 72, 1, 4, [[0.25 * k - 0.8, 1.1 - 0.35 * k] for k in range(7)], 3, 1.0),
     (81, 75, 1, 3, [[0.3 * k - 1.9, 0.21 * k - 1.3] for k in range(13)], 0, 0.0),
+    # 17 frames: past the ring kernel's 16, so the ring mode of k_gather_direct runs with its thread groups capped at 16
+    # and one group walks two frames
+    (96, 72, 1, 4, [[0.25 * k - 2.1, 1.9 - 0.23 * k] for k in range(17)], 3, 1.0),
 ]
 
 

@@ -1,4 +1,4 @@
-"""Parity matrix of the direct regulariser kernels (csrc/kernels_direct.hip): every values, IRLS-weights and gradient
+"""Parity matrix of the direct regulariser kernels (csrc/kernels_reg_direct.hip): every values, IRLS-weights and gradient
 variant of tests/reg_matrix.py in both dtypes against the f64 oracle with the term-scaled bars of tests/error_bars.py,
 and the bit identities the kernels' comments claim between the variants.
 
