@@ -232,6 +232,33 @@ int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* tap
  * taps_out is not NULL, its ksize x ksize taps (at most 15 x 15 doubles for a created Gaussian, 7 x 7 for a free-form one). */
 int srmap_problem_get_blur_kernel(const srmap_problem* p, int* ksize, double* taps_out);
 
+/* Blur-kernel bank: a point-spread function per frame, per channel or per (frame, channel) (no reference counterpart;
+ * DESIGN.md 3.14).  The forward model becomes y_k,c = D B_{k,c} M_k x_c: a burst whose frames carry different streaks or
+ * lenses, a cube whose PSF differs from band to band.
+ *   taps      entries x ksize x ksize doubles, each entry row-major; entries = K (PER_FRAME), C (PER_CHANNEL) or K * C
+ *             (PER_FRAME_CHANNEL, stored [k][c]).  The bank has ONE ksize: the caller zero-pads a smaller kernel.
+ *   meaning   every entry means what srmap_problem_set_blur_kernel says of its kernel: the forward model CORRELATES with
+ *             it, taps outside the image contribute 0, nothing is normalised, negative taps are allowed; the adjoint is
+ *             the exact transpose (entry (k, c) flipped in both axes) and the gradient is the cost's gradient.
+ *   domain    the single kernel's: an even ksize, ksize < 1, a tap that is not finite or an unknown mode: SRMAP_EINVAL;
+ *             ksize > 7: SRMAP_EUNSUPPORTED; on an error the problem keeps the blur it had.
+ *   NULL      restores the blur the problem was created with, bit for bit (as srmap_problem_set_blur_kernel(p, 0, NULL)).
+ * A bank and the single free-form kernel are alternatives: setting one replaces the other.  While a bank is set
+ * srmap_problem_get_blur_kernel returns the bank's ksize and, asked for taps, answers SRMAP_EUNSUPPORTED
+ * (srmap_problem_get_blur_bank returns them); srmap_fit_blur answers SRMAP_EUNSUPPORTED (its ridge and its energy at the
+ * kernel in force have no single kernel to refer to: srmap_fit_blur_bank is the call).  The direct kernel family runs
+ * (srmap_problem_active_impl answers SRMAP_IMPL_DIRECT, SRMAP_IMPL_TILED answers SRMAP_EUNSUPPORTED at evaluation) and
+ * calls sharded over more than one rank answer SRMAP_EUNSUPPORTED.  Every motion kind (none, shifts_xy, affine, flow), data
+ * weights, the prior, the Huber loss, the photometric parameters, srmap_eval*, srmap_apply, srmap_apply_transpose,
+ * srmap_solve (CG, L-BFGS, split_channels -- a per-channel entry goes by the problem's channel), the traces,
+ * srmap_problem_set_cost_rows, srmap_refine_motion and srmap_fit_photometric honour the bank; it persists across the
+ * observation, weight, prior, loss, motion, flow and photometric calls.  A bank whose entries are all equal evaluates bit
+ * for bit as srmap_problem_set_blur_kernel with those taps does. */
+typedef enum { SRMAP_BLUR_PER_FRAME = 1, SRMAP_BLUR_PER_CHANNEL = 2, SRMAP_BLUR_PER_FRAME_CHANNEL = 3 } srmap_blur_bank_mode;
+int srmap_problem_set_blur_bank(srmap_problem* p, int mode, int ksize, const double* taps /* entries x ksize x ksize; NULL restores */);
+/* The bank in force: *mode (0 = none set), *ksize and, when taps_out is not NULL and a bank is set, its entries x ksize x ksize taps. */
+int srmap_problem_get_blur_bank(const srmap_problem* p, int* mode /* 0 = none */, int* ksize, double* taps_out /* optional */);
+
 /* Inner minimiser of srmap_solve: MapSolverOptions::least_squares_solver and num_lbfgs_hessian_corrections
  * (enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER }, map_solver.h:20-51; the choice irls_map_solver.cpp:97-113;
  * the CLI's --solver=cg|lbfgs, super_resolution.cpp:98-99, 134-141).  SRMAP_SOLVER_CG (mincg, alglib_objective.cpp:47-75)
@@ -629,6 +656,28 @@ int srmap_fit_blur(srmap_problem* p, const double* x_host, const srmap_blur_fit_
 int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
                           const srmap_blur_fit_options* options /* NULL = defaults */, double* taps_out, double* quality_out,
                           double* normal_equations_out);
+
+/* Calibration fit of a blur-kernel bank (csrc/blur_fit.hip): srmap_fit_blur's quadratic, solved separately
+ * over the observations of each entry of `mode` (srmap_blur_bank_mode) -- frame k's for PER_FRAME, channel c's of every
+ * frame for PER_CHANNEL, those of (k, c) for PER_FRAME_CHANNEL.  One launch forms a Gram record per (frame, channel, chunk),
+ * a reduce kernel adds the records of each entry in index order (frame, channel, chunk); double sums, a fixed order, no
+ * atomics: bit-identical run to run.  The host solves entry by entry with srmap_fit_blur's Cholesky / KKT code.
+ *   ridge     pulls entry e towards the kernel in force for it, zero-padded or centre-cropped to ksize: the bank's entry of
+ *             (k, c) -- with (k, 0), (0, c), (k, c) standing for entry k, c, (k, c) of `mode` -- or the single / created
+ *             kernel when no bank is set.  options->ksize = 0: the size of the blur in force.
+ *   status    per entry: 0 fitted, 3 degenerate (no texture, every weight of the entry 0: a frame masked out).  A
+ *             degenerate entry keeps the kernel in force for it and is not an error of the call.
+ * taps_out (optional, entries x ksize^2), quality_out (optional, entries x 5, srmap_fit_blur's layout per entry),
+ * normal_equations_out (optional, entries x (n + 1)(n + 2) / 2, srmap_fit_blur's layout per entry).  apply = 1 installs the
+ * result as srmap_problem_set_blur_bank(p, mode, ksize, taps_out) would, unless every entry is degenerate.  The errors are
+ * srmap_fit_blur's, and an unknown mode is SRMAP_EINVAL; every error leaves the problem unchanged.  Like srmap_fit_blur
+ * this is a CALIBRATION fit from a known HR image: blind alternation of a solve and this fit is NOT offered (it drifts,
+ * DESIGN.md 3.9).  A displacement field answers SRMAP_EUNSUPPORTED, as for srmap_fit_blur. */
+int srmap_fit_blur_bank(srmap_problem* p, const double* x_host, int mode, const srmap_blur_fit_options* options /* NULL = defaults */,
+                        double* taps_out, double* quality_out, double* normal_equations_out);
+int srmap_fit_blur_bank_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode,
+                               const srmap_blur_fit_options* options /* NULL = defaults */, double* taps_out,
+                               double* quality_out, double* normal_equations_out);
 
 /* Photometric frame model: per-frame gain and bias (no reference counterpart: image_model.cpp:86-91 gives every frame the
  * photometry of the HR image; csrc/photometric_fit.hip).  Frame k is modelled as

@@ -35,7 +35,11 @@ constexpr int kStride = 129;     // LDS row stride in doubles (odd)
 constexpr int kMaxChunks = 128;  // chunks per frame at most
 constexpr int kMinTilesPerChunk = 2;
 
-template <typename T, int B, int MOTION, bool WEIGHTED>
+// PER_CHANNEL (compile time; the bank fit): grid (chunks, frames, channels), the workgroup's observations are the LR pixels
+// of channel blockIdx.z alone, so that a record belongs to one (frame, channel): partial[((k * C + c) * chunks + chunk)][P].
+// Otherwise the grid is (chunks, frames) and the chunk walks (channel, pixel) together: partial[(k * chunks + chunk)][P].
+// (A run-time switch cost the existing instances 20 to 45 VGPRs and with them waves per SIMD: profiles/r17_blur_bank_resources.txt.)
+template <typename T, int B, int MOTION, bool WEIGHTED, bool PER_CHANNEL = false>
 __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, const T* __restrict__ y,
                                                        const T* __restrict__ dw, Geometry g,
                                                        MotionArgs<T> ma, const int* __restrict__ col_map,
@@ -46,7 +50,7 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
   __shared__ double wl[kTile];
   const int k = blockIdx.y;
   const int n = g.w * g.h;
-  const long long nobs = (long long)n * g.C;
+  const long long nobs = PER_CHANNEL ? (long long)n : (long long)n * g.C;
   // this thread's pairs (i <= j) of the upper triangle, row-major: q = threadIdx.x + 256 m
   int pi[PP], pj[PP];
   double acc[PP];
@@ -70,8 +74,13 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
     // ---- phase 1: the tile's columns ----
     int c = 0, lp = 0, R0 = 0, C0 = 0;
     if (live) {
-      c = (int)(o / n);
-      lp = (int)(o - (long long)c * n);
+      if constexpr (PER_CHANNEL) {
+        c = (int)blockIdx.z;
+        lp = (int)o;
+      } else {
+        c = (int)(o / n);
+        lp = (int)(o - (long long)c * n);
+      }
       const int i = lp / g.w, j = lp - i * g.w;
       R0 = row_map[i];
       C0 = col_map[j];
@@ -98,7 +107,8 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
       for (int m = 0; m < PP; ++m) acc[m] += (wv * u[pi[m] + q]) * u[pj[m] + q];
     }
   }
-  double* __restrict__ rec = partial + ((size_t)k * gridDim.x + blockIdx.x) * P;
+  const size_t row = PER_CHANNEL ? (size_t)k * gridDim.z + blockIdx.z : (size_t)k;
+  double* __restrict__ rec = partial + (row * gridDim.x + blockIdx.x) * P;
 #pragma unroll
   for (int m = 0; m < PP; ++m) {
     const int q = (int)threadIdx.x + 256 * m;
@@ -117,29 +127,59 @@ __global__ __launch_bounds__(256) void k_blur_fit_reduce(const double* __restric
   sums[q] = s;
 }
 
-// the instance of the problem's motion kind; false: the kind has none (a displacement field, which the entry point refuses)
-template <typename T, int B>
+// The bank fit's reduce: entry e = blockIdx.y adds its records in index order -- `outer` groups `outer_stride` records
+// apart, `inner` consecutive records each, from record e * entry_stride on.  With the records laid out [frame][channel][chunk]
+// that is frame, channel, chunk order for every mode (srmap_fit_blur_bank_device fills the strides).  sums[e][nsums].
+__global__ __launch_bounds__(256) void k_blur_fit_reduce_bank(const double* __restrict__ partial, int nsums, int entry_stride,
+                                                              int outer, int outer_stride, int inner,
+                                                              double* __restrict__ sums) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nsums) return;
+  const int e = blockIdx.y;
+  double s = 0.0;
+  for (int o = 0; o < outer; ++o) {
+    const double* __restrict__ rec = partial + ((size_t)e * entry_stride + (size_t)o * outer_stride) * nsums + q;
+    for (int r = 0; r < inner; ++r) s += rec[(size_t)r * nsums];
+  }
+  sums[(size_t)e * nsums + q] = s;
+}
+
+// the instance of the problem's motion kind; false: the kind has none (a displacement field, which the entry point refuses).
+// per_channel: the bank fit's grid, a record per (frame, channel, chunk)
+template <typename T, int B, bool PER_CHANNEL>
 bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
-  dim3 grid(chunks, g.K);
+  dim3 grid(chunks, g.K, PER_CHANNEL ? g.C : 1);
   const MotionArgs<T> ma = motion_args<T>(p);
   return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->dw.effective<T>())
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true, PER_CHANNEL>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
                          p->dw.effective<T>(), g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
     else
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false, PER_CHANNEL>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
                          (const T*)nullptr, g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
   });
 }
 
-template <typename T>
+template <typename T, bool PER_CHANNEL = false>
 bool launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
-  if (ksize == 1) return launch_sums_m<T, 1>(p, x, chunks, tpc, d_part, st);
-  if (ksize == 3) return launch_sums_m<T, 3>(p, x, chunks, tpc, d_part, st);
-  if (ksize == 5) return launch_sums_m<T, 5>(p, x, chunks, tpc, d_part, st);
-  return launch_sums_m<T, 7>(p, x, chunks, tpc, d_part, st);
+  if (ksize == 1) return launch_sums_m<T, 1, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
+  if (ksize == 3) return launch_sums_m<T, 3, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
+  if (ksize == 5) return launch_sums_m<T, 5, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
+  return launch_sums_m<T, 7, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
+}
+
+// The kernel `cur` (b x b) zero-padded or centre-cropped to ksize
+std::vector<double> resized_kernel(const double* cur, int b, int ksize) {
+  std::vector<double> hcur((size_t)ksize * ksize, 0.0);
+  const int off = (ksize - b) / 2;  // both odd: exact, negative when cropping
+  for (int a = 0; a < ksize; ++a)
+    for (int e = 0; e < ksize; ++e) {
+      const int sa = a - off, se = e - off;
+      if (sa >= 0 && sa < b && se >= 0 && se < b) hcur[(size_t)a * ksize + e] = cur[(size_t)sa * b + se];
+    }
+  return hcur;
 }
 
 // E(h) = [h; -1]^T M [h; -1], M the (n + 1) x (n + 1) Gram (full, row-major)
@@ -155,80 +195,14 @@ double energy(const std::vector<double>& M, int n, const double* h) {
   return e;
 }
 
-}  // namespace
-
-}  // namespace srmap
-
-using namespace srmap;
-
-extern "C" void srmap_blur_fit_options_default(srmap_blur_fit_options* o) {
-  if (!o) return;
-  o->struct_size = (int)sizeof(srmap_blur_fit_options);
-  o->ksize = 0;
-  o->sum_to_one = 1;
-  o->ridge = 0.0;
-  o->apply = 1;
-}
-
-extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
-                                     const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
-                                     double* normal_equations_out) {
-  if (!p || !x_dev) return SRMAP_EINVAL;
-  srmap_ctx* ctx = p->ctx;
-  if (p->flow)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
-  srmap_blur_fit_options opt;
-  srmap_blur_fit_options_default(&opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_blur_fit_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
-    opt = *options;
-  }
-  const Geometry& g = p->geo;
-  const int ksize = opt.ksize == 0 ? g.b : opt.ksize;
-  if (ksize < 1 || ksize % 2 != 1) return set_error(ctx, SRMAP_EINVAL, "blur fit: ksize must be odd and >= 1 (got %d)", ksize);
-  if (ksize > kMaxCustomBlur)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "blur fit: ksize %d: at most %d x %d taps are fitted", ksize, kMaxCustomBlur, kMaxCustomBlur);
-  if (!(opt.ridge >= 0.0) || !std::isfinite(opt.ridge)) return set_error(ctx, SRMAP_EINVAL, "blur fit: ridge must be finite and >= 0");
-  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
-
-  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-  int rc = problem_state_read(p, st);
-  if (rc) return rc;
-
-  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
-  const long long nobs = (long long)g.w * g.h * g.C;
-  const long long tiles = (nobs + kTile - 1) / kTile;
-  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
-  const int chunks = (int)((tiles + tpc - 1) / tpc);
-  const int records = g.K * chunks;
-  DevBuf part, sums;
-  PinnedBuf sums_host;
-  if (part.alloc((size_t)records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)P * sizeof(double)) != hipSuccess ||
-      sums_host.alloc((size_t)P * sizeof(double)) != hipSuccess)
-    return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
-  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
-  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
-    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
-  SRMAP_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, d_part, records, P, d_sums);
-  SRMAP_HIP(ctx, hipGetLastError());
-  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
-  SRMAP_HIP(ctx, hipStreamSynchronize(st));
-
-  // ---- the host solve ----
+// The host solve of one Gram: sums = the packed upper triangle of the (n + 1) x (n + 1) Gram, hcur the kernel in force at the
+// fit's size.  h (n taps; hcur for status 3) and quality[5] = {E(hcur), E(h), smallest / largest pivot, status}.
+void solve_taps(const double* sums, int n, const std::vector<double>& hcur, const srmap_blur_fit_options& opt,
+                std::vector<double>* h_out, double* quality) {
+  const int n1 = n + 1;
   std::vector<double> M((size_t)n1 * n1);
   for (int i = 0, q = 0; i < n1; ++i)
-    for (int j = i; j < n1; ++j, ++q) M[(size_t)i * n1 + j] = M[(size_t)j * n1 + i] = h_sums[q];
-  // the kernel in force, zero-padded or centre-cropped to ksize
-  std::vector<double> hcur((size_t)n, 0.0);
-  const int off = (ksize - g.b) / 2;  // both odd: exact, negative when cropping
-  for (int a = 0; a < ksize; ++a)
-    for (int e = 0; e < ksize; ++e) {
-      const int sa = a - off, se = e - off;
-      if (sa >= 0 && sa < g.b && se >= 0 && se < g.b) hcur[(size_t)a * ksize + e] = p->blur2d[(size_t)sa * g.b + se];
-    }
+    for (int j = i; j < n1; ++j, ++q) M[(size_t)i * n1 + j] = M[(size_t)j * n1 + i] = sums[q];
   const double e0 = energy(M, n, hcur.data());
   double trace = 0.0;
   for (int i = 0; i < n; ++i) trace += M[(size_t)i * n1 + i];
@@ -263,16 +237,179 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
     if (status == 3) h = hcur;
     else e1 = energy(M, n, h.data());
   }
-  if (status == 0 && opt.apply) {
+  quality[0] = e0; quality[1] = e1; quality[2] = pmin; quality[3] = pmax; quality[4] = status;
+  h_out->swap(h);
+}
+
+// the argument checks the two fits share; *ksize: the fit's size
+int check_fit(srmap_problem* p, const srmap_blur_fit_options* options, srmap_blur_fit_options* opt, int* ksize) {
+  srmap_ctx* ctx = p->ctx;
+  if (p->flow)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
+  srmap_blur_fit_options_default(opt);
+  if (options) {
+    if (options->struct_size != (int)sizeof(srmap_blur_fit_options))
+      return set_error(ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
+    *opt = *options;
+  }
+  *ksize = opt->ksize == 0 ? p->geo.b : opt->ksize;
+  if (*ksize < 1 || *ksize % 2 != 1) return set_error(ctx, SRMAP_EINVAL, "blur fit: ksize must be odd and >= 1 (got %d)", *ksize);
+  if (*ksize > kMaxCustomBlur)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "blur fit: ksize %d: at most %d x %d taps are fitted", *ksize, kMaxCustomBlur, kMaxCustomBlur);
+  if (!(opt->ridge >= 0.0) || !std::isfinite(opt->ridge)) return set_error(ctx, SRMAP_EINVAL, "blur fit: ridge must be finite and >= 0");
+  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
+  return SRMAP_OK;
+}
+
+}  // namespace
+
+}  // namespace srmap
+
+using namespace srmap;
+
+extern "C" void srmap_blur_fit_options_default(srmap_blur_fit_options* o) {
+  if (!o) return;
+  o->struct_size = (int)sizeof(srmap_blur_fit_options);
+  o->ksize = 0;
+  o->sum_to_one = 1;
+  o->ridge = 0.0;
+  o->apply = 1;
+}
+
+extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* hip_stream,
+                                     const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
+                                     double* normal_equations_out) {
+  if (!p || !x_dev) return SRMAP_EINVAL;
+  srmap_ctx* ctx = p->ctx;
+  if (p->blur_bank_mode != 0)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
+  srmap_blur_fit_options opt;
+  int ksize = 0;
+  if (int rc = check_fit(p, options, &opt, &ksize)) return rc;
+  const Geometry& g = p->geo;
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  int rc = problem_state_read(p, st);
+  if (rc) return rc;
+
+  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
+  const long long nobs = (long long)g.w * g.h * g.C;
+  const long long tiles = (nobs + kTile - 1) / kTile;
+  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
+  const int chunks = (int)((tiles + tpc - 1) / tpc);
+  const int records = g.K * chunks;
+  DevBuf part, sums;
+  PinnedBuf sums_host;
+  if (part.alloc((size_t)records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)P * sizeof(double)) != hipSuccess ||
+      sums_host.alloc((size_t)P * sizeof(double)) != hipSuccess)
+    return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
+  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
+  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
+    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
+  SRMAP_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, d_part, records, P, d_sums);
+  SRMAP_HIP(ctx, hipGetLastError());
+  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipStreamSynchronize(st));
+
+  // ---- the host solve ----
+  // the kernel in force, zero-padded or centre-cropped to ksize
+  const std::vector<double> hcur = resized_kernel(p->blur2d.data(), g.b, ksize);
+  std::vector<double> h;
+  double quality[5];
+  solve_taps(h_sums, n, hcur, opt, &h, quality);
+  if (quality[4] == 0.0 && opt.apply) {
     rc = srmap_problem_set_blur_kernel(p, ksize, h.data());
     if (rc) return rc;
   }
   if (taps_out) std::copy(h.begin(), h.end(), taps_out);
-  if (quality_out) {
-    quality_out[0] = e0; quality_out[1] = e1; quality_out[2] = pmin; quality_out[3] = pmax; quality_out[4] = status;
-  }
+  if (quality_out) std::copy(quality, quality + 5, quality_out);
   if (normal_equations_out) std::copy(h_sums, h_sums + P, normal_equations_out);
   return SRMAP_OK;
+}
+
+extern "C" int srmap_fit_blur_bank_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode,
+                                          const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
+                                          double* normal_equations_out) {
+  if (!p || !x_dev) return SRMAP_EINVAL;
+  srmap_ctx* ctx = p->ctx;
+  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
+    return set_error(ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
+  srmap_blur_fit_options opt;
+  int ksize = 0;
+  if (int rc = check_fit(p, options, &opt, &ksize)) return rc;
+  const Geometry& g = p->geo;
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  int rc = problem_state_read(p, st);
+  if (rc) return rc;
+
+  // one record per (frame, channel, chunk): a chunk holds LR pixels of one channel
+  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
+  const long long nobs = (long long)g.w * g.h;
+  const long long tiles = (nobs + kTile - 1) / kTile;
+  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
+  const int chunks = (int)((tiles + tpc - 1) / tpc);
+  const size_t records = (size_t)g.K * g.C * chunks;
+  const int entries = blur_bank_entries(mode, g.K, g.C);
+  DevBuf part, sums;
+  PinnedBuf sums_host;
+  if (part.alloc(records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)entries * P * sizeof(double)) != hipSuccess ||
+      sums_host.alloc((size_t)entries * P * sizeof(double)) != hipSuccess)
+    return set_error(ctx, SRMAP_ENOMEM, "blur bank fit: allocation failed");
+  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
+  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t), true>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
+    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
+  SRMAP_HIP(ctx, hipGetLastError());
+  // the records of an entry, in (frame, channel, chunk) order: a frame's C * chunks, a channel's chunks of every frame, or
+  // the chunks of one (frame, channel)
+  const int entry_stride = mode == SRMAP_BLUR_PER_FRAME ? g.C * chunks : chunks;
+  const int outer = mode == SRMAP_BLUR_PER_CHANNEL ? g.K : 1, outer_stride = g.C * chunks;
+  const int inner = mode == SRMAP_BLUR_PER_FRAME ? g.C * chunks : chunks;
+  hipLaunchKernelGGL(k_blur_fit_reduce_bank, dim3((P + 255) / 256, entries), dim3(256), 0, st, d_part, P, entry_stride, outer,
+                     outer_stride, inner, d_sums);
+  SRMAP_HIP(ctx, hipGetLastError());
+  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)entries * P * sizeof(double), hipMemcpyDeviceToHost, st));
+  SRMAP_HIP(ctx, hipStreamSynchronize(st));
+
+  // ---- the host solve, entry by entry ----
+  std::vector<double> bank((size_t)entries * n), quality((size_t)entries * 5);
+  bool any = false;
+  for (int q = 0; q < entries; ++q) {
+    // the (frame, channel) that stands for entry q, and the kernel in force for it
+    const int k = mode == SRMAP_BLUR_PER_CHANNEL ? 0 : mode == SRMAP_BLUR_PER_FRAME ? q : q / g.C;
+    const int c = mode == SRMAP_BLUR_PER_CHANNEL ? q : mode == SRMAP_BLUR_PER_FRAME ? 0 : q % g.C;
+    const double* cur = p->blur_bank_mode ? p->blur_bank.data() + (size_t)blur_bank_entry(p->blur_bank_mode, g.C, k, c) * g.b * g.b
+                                          : p->blur2d.data();
+    const std::vector<double> hcur = resized_kernel(cur, g.b, ksize);
+    std::vector<double> h;
+    solve_taps(h_sums + (size_t)q * P, n, hcur, opt, &h, quality.data() + (size_t)q * 5);
+    std::copy(h.begin(), h.end(), bank.begin() + (size_t)q * n);
+    any = any || quality[(size_t)q * 5 + 4] == 0.0;
+  }
+  if (any && opt.apply) {
+    rc = srmap_problem_set_blur_bank(p, mode, ksize, bank.data());
+    if (rc) return rc;
+  }
+  if (taps_out) std::copy(bank.begin(), bank.end(), taps_out);
+  if (quality_out) std::copy(quality.begin(), quality.end(), quality_out);
+  if (normal_equations_out) std::copy(h_sums, h_sums + (size_t)entries * P, normal_equations_out);
+  return SRMAP_OK;
+}
+
+extern "C" int srmap_fit_blur_bank(srmap_problem* p, const double* x_host, int mode, const srmap_blur_fit_options* options,
+                                   double* taps_out, double* quality_out, double* normal_equations_out) {
+  if (!p || !x_host) return SRMAP_EINVAL;
+  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
+  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
+    return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
+  if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
+    return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  if (int rc = stage_host_x(p, x_host)) return rc;
+  return srmap_fit_blur_bank_device(p, p->d_x.as(), p->ctx->stream, mode, options, taps_out, quality_out, normal_equations_out);
 }
 
 extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srmap_blur_fit_options* options,
@@ -282,6 +419,8 @@ extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srma
   if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
     return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  if (p->blur_bank_mode != 0)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
   if (int rc = stage_host_x(p, x_host)) return rc;
   return srmap_fit_blur_device(p, p->d_x.as(), p->ctx->stream, options, taps_out, quality_out, normal_equations_out);
 }

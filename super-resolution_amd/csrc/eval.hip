@@ -72,7 +72,7 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
       nparts += nb;
       if (g) {
         rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K,
-                                     2.0 * geo.s * geo.s, false, st);
+                                     2.0 * geo.s * geo.s, false, st, 0, nullptr, c0);
         if (rc) return rc;
         g_written = true;
       }

@@ -27,17 +27,19 @@ namespace srmap {
 // table), kMotionAffine, kMotionFlow.  The per-pixel kinds read their sources through the caches: per LR pixel b^2 x 4 taps
 // of x, and two field values per blur tap for a flow.
 // WEIGHTED (compile time; needs y): per-observation weights dw indexed like y -- out = w * res, partial s^2 * sum(w res^2).
+// blur_bank: the table of the block's (frame, absolute channel) -- block-uniform; the strides are 0 without a bank.
 template <typename T, int MOTION, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_forward_direct(
     const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out,
     double* __restrict__ partials, Geometry g,
-    MotionArgs<T> ma, const T* __restrict__ blur,
+    MotionArgs<T> ma, const T* __restrict__ blur_bank,
     const int* __restrict__ col_map, const int* __restrict__ row_map, int k0,
-    double cost_scale, int obs_C, int obs_c0, const T* __restrict__ dw) {
+    double cost_scale, int obs_C, int obs_c0, const T* __restrict__ dw, BlurStride bs) {
   __shared__ double red[4];
-  __shared__ T comb[36];  // table kind: blur (x) bilinear taps of this block's frame, (b+1) x (b+1), b <= 5
+  __shared__ T comb[36];  // table kind: blur (x) bilinear taps of this block's frame and channel, (b+1) x (b+1), b <= 5
   const int lp = blockIdx.x * 256 + threadIdx.x;
   const int c = blockIdx.y, kk = blockIdx.z, k = k0 + kk;
+  const T* __restrict__ blur = blur_bank + ((size_t)k * bs.frame + (size_t)(c + obs_c0) * bs.channel);
   const int n = g.w * g.h;
   const MotionSampler<T, MOTION> ms(ma, g, k);
   // table kind, interior fast path for bilinear warps: one (b+1)^2 stencil on x instead of b^2 four-tap samples (a
@@ -128,14 +130,15 @@ int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
   const MotionArgs<T> ma = motion_args<T>(p);
+  const BlurStride bs = blur_stride(p);
   const bool launched = dispatch_value<kMotionTable, kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (dw != nullptr)
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, true>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
     else
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, false>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
   });
   if (!launched) return set_error(p->ctx, SRMAP_EINVAL, "internal: no forward kernel for motion kind %d", kind);
   if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
@@ -169,7 +172,9 @@ template <typename T, int SC>
 __global__ __launch_bounds__(256) void k_gather_direct(
     const T* __restrict__ resid, T* __restrict__ gout, Geometry g,
     const WarpTaps<T>* __restrict__ warps, const T* __restrict__ blur_t, int k0,
-    int nk, T out_scale, int accumulate, int ring, int ring_groups) {
+    int nk, T out_scale, int accumulate, int ring, int ring_groups, BlurStride bs, int obs_c0) {
+  // blur_t: the flipped table; with a bank the entry of (frame, absolute channel), which changes inside the frame loop
+  // (both strides are 0 without a bank)
   // ring mode: 256 / nfg pixels per block, the frames split over nfg thread groups (nfg = 16 for 16 frames and more:
   // one or a few frames per thread -- every frame costs two dependent memory round trips, its warp record and its
   // residuals, and with 4 groups a thread walked through 8 of them), combined through LDS in fixed order;
@@ -190,10 +195,12 @@ __global__ __launch_bounds__(256) void k_gather_direct(
     return;
   }
   const int r = hp / g.W, col = hp - r * g.W;
+  const T* __restrict__ blur_c = blur_t + (size_t)(c + obs_c0) * bs.channel;
   T acc = T(0);
   for (int kk = fg; kk < nk && live; kk += nfg) {
     const WarpTaps<T> wt = warps ? warps[k0 + kk] : identity_warp<T>();
     const T* rk = resid + ((size_t)kk * g.C + c) * n;
+    const T* __restrict__ blur_k = blur_c + (size_t)(k0 + kk) * bs.frame;
     T tk = T(0);
     int oy = wt.oy;
     T wloc[4] = {wt.w[0], wt.w[1], wt.w[2], wt.w[3]};
@@ -208,7 +215,7 @@ __global__ __launch_bounds__(256) void k_gather_direct(
       const int pr = r + oy + (t >> 1), pc = col + wt.ox + (t & 1);
       if (pr < 0 || pr >= g.H || pc < 0 || pc >= g.W) continue;
       // only the taps that land on the LR grid (every s-th), visited in the same increasing (a, e) order
-      tk += wloc[t] * blur_t_upsampled_at(rk, blur_t, g, gs, pr, pc);
+      tk += wloc[t] * blur_t_upsampled_at(rk, blur_k, g, gs, pr, pc);
     }
     acc += tk;
   }
@@ -321,7 +328,7 @@ __global__ __launch_bounds__(256) void k_gather_ring(const T* __restrict__ resid
 template <typename T, int MOTION, int SC>
 __global__ __launch_bounds__(256) void k_gather_sampled(const T* __restrict__ resid, T* __restrict__ gout, Geometry g,
                                                        MotionArgs<T> ma, const T* __restrict__ blur_t, int k0, int nk,
-                                                       T out_scale, int accumulate) {
+                                                       T out_scale, int accumulate, BlurStride bs, int obs_c0) {
   constexpr int WIN = MotionSampler<T, MOTION>::kWindow;
   const int gs = SC ? SC : g.s;
   const int hp = blockIdx.x * 256 + threadIdx.x;
@@ -329,10 +336,12 @@ __global__ __launch_bounds__(256) void k_gather_sampled(const T* __restrict__ re
   const int N = g.W * g.H, n = g.w * g.h;
   if (hp >= N) return;
   const int r = hp / g.W, col = hp - r * g.W;
+  const T* __restrict__ blur_c = blur_t + (size_t)(c + obs_c0) * bs.channel;  // a bank's entries: k_gather_direct
   T acc = T(0);
   for (int kk = 0; kk < nk; ++kk) {
     const MotionSampler<T, MOTION> ms(ma, g, k0 + kk);  // uniform
     const T* rk = resid + ((size_t)kk * g.C + c) * n;
+    const T* __restrict__ blur_k = blur_c + (size_t)(k0 + kk) * bs.frame;  // uniform
     int qx0, qy0;
     if (!ms.window(g, hp, r, col, &qx0, &qy0)) continue;
     T tk = T(0);
@@ -347,7 +356,7 @@ __global__ __launch_bounds__(256) void k_gather_sampled(const T* __restrict__ re
         if (wx == 0.0) continue;  // a flow reads the y component only where the x weight is not zero
         const double wd = ms.weight_y(qi, qx, qy, r) * wx;
         if (wd == 0.0) continue;  // p is no tap of q
-        tk += (T)wd * blur_t_upsampled_at(rk, blur_t, g, gs, qy, qx);
+        tk += (T)wd * blur_t_upsampled_at(rk, blur_k, g, gs, qy, qx);
       }
     }
     acc += tk;
@@ -359,14 +368,15 @@ __global__ __launch_bounds__(256) void k_gather_sampled(const T* __restrict__ re
 
 template <typename T, int MOTION>
 static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk,
-                                  double out_scale, bool accumulate, hipStream_t st) {
+                                  double out_scale, bool accumulate, hipStream_t st, int obs_c0) {
   dim3 grid((unsigned)(((size_t)geo.W * geo.H + 255) / 256), geo.C);
   const MotionArgs<T> ma = motion_args<T>(p);
   const T* bt = p->d_blur_t.as<const T>();
   const int acc1 = accumulate ? 1 : 0;
+  const BlurStride bs = blur_stride(p);
   dispatch_scale(geo.s, [&](auto sc) {
     hipLaunchKernelGGL((k_gather_sampled<T, MOTION, decltype(sc)::value>), grid, dim3(256), 0, st, resid, g, geo, ma, bt, k0, nk,
-                       (T)out_scale, acc1);
+                       (T)out_scale, acc1, bs, obs_c0);
   });
 }
 
@@ -378,15 +388,17 @@ bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, 
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
-                         hipStream_t st, int ring, T* ringbuf) {
+                         hipStream_t st, int ring, T* ringbuf, int obs_c0) {
   const int kind = motion_kind(p);
+  if (p->blur_bank_mode != 0 && (ring > 0 || ringbuf != nullptr))
+    return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which a blur bank has none of");
   if (kind == kMotionAffine || kind == kMotionFlow) {
     if (ring > 0 || ringbuf != nullptr)
       return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which %s has none of",
                        kind == kMotionFlow ? "a displacement field" : "an affine motion");
     if (int rc = motion_buffers_ok(p, kind)) return rc;
     if (!dispatch_value<kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
-          launch_gather_sampled<T, decltype(motion)::value>(p, geo, resid, g, k0, nk, out_scale, accumulate, st);
+          launch_gather_sampled<T, decltype(motion)::value>(p, geo, resid, g, k0, nk, out_scale, accumulate, st, obs_c0);
         }))
       return set_error(p->ctx, SRMAP_EINVAL, "internal: no sampled gather for motion kind %d", kind);
     SRMAP_HIP(p->ctx, hipGetLastError());
@@ -420,7 +432,7 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
   dim3 grid((unsigned)(ring > 0 ? (npix + ppb - 1) / ppb : (npix + 255) / 256), geo.C);
   dispatch_scale(geo.s, [&](auto sc) {
     hipLaunchKernelGGL((k_gather_direct<T, decltype(sc)::value>), grid, dim3(256), 0, st, resid, g, geo, wp, bt, k0, nk, (T)out_scale,
-                       accumulate ? 1 : 0, ring, groups);
+                       accumulate ? 1 : 0, ring, groups, blur_stride(p), obs_c0);
   });
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
@@ -431,7 +443,7 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
                                         const T*, int, int, T*, int, int, double*, int*,   \
                                         hipStream_t, const T*);                             \
   template int launch_gather_direct<T>(srmap_problem*, const Geometry&, const T*, T*, int, \
-                                       int, double, bool, hipStream_t, int, T*);
+                                       int, double, bool, hipStream_t, int, T*, int);
 INSTANTIATE(float)
 INSTANTIATE(double)
 

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
                                                      const T* __restrict__ dw, Geometry g, const T* __restrict__ blur,
                                                      const int* __restrict__ col_map, const int* __restrict__ row_map,
                                                      const double* __restrict__ table, int ppt,
-                                                     double* __restrict__ partial) {
+                                                     double* __restrict__ partial, BlurStride bs) {
   __shared__ double red[kSums][4];
   const int k = blockIdx.y;
   const double* __restrict__ m = table + (size_t)k * kFitTabRec;  // uniform: scalar loads
@@ -59,6 +59,7 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
     const int R0 = row_map[i], C0 = col_map[j];
     for (int c = 0; c < g.C; ++c) {
       const T* __restrict__ plane = x + (size_t)c * g.W * g.H;
+      const T* __restrict__ blur_kc = blur + ((size_t)k * bs.frame + (size_t)c * bs.channel);  // a bank's entry; strides 0 without one
       double val = 0.0, J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       for (int a = 0; a < g.b; ++a) {
         const int rr = R0 + a - g.hb;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
           const double v01 = (r0 && q1) ? (double)plane[(size_t)sr * g.W + sc + 1] : 0.0;
           const double v10 = (r1 && q0) ? (double)plane[(size_t)(sr + 1) * g.W + sc] : 0.0;
           const double v11 = (r1 && q1) ? (double)plane[(size_t)(sr + 1) * g.W + sc + 1] : 0.0;
-          const double bw = (double)blur[a * g.b + e];
+          const double bw = (double)blur_kc[a * g.b + e];
           const double s = (1.0 - fy) * ((1.0 - fx) * v00 + fx * v01) + fy * ((1.0 - fx) * v10 + fx * v11);
           const double gx = bw * ((1.0 - fy) * (v01 - v00) + fy * (v11 - v10));
           const double gy = bw * ((1.0 - fx) * (v10 - v00) + fx * (v11 - v01));
@@ -134,12 +135,13 @@ template <typename T>
 void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, int ppt, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
+  const BlurStride bs = blur_stride(p);
   if (p->dw.effective<T>())
     hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), p->dw.effective<T>(), g,
-                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part);
+                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
   else
     hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), (const T*)nullptr, g,
-                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part);
+                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
 }
 
 }  // namespace

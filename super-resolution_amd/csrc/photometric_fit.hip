@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ 
                                                           const T* __restrict__ dw, Geometry g,
                                                           MotionArgs<T> ma, const T* __restrict__ blur,
                                                           const int* __restrict__ col_map, const int* __restrict__ row_map,
-                                                          int ppt, double* __restrict__ partial) {
+                                                          int ppt, double* __restrict__ partial, BlurStride bs) {
   __shared__ double red[kPhotoSums][4];
   const int k = blockIdx.y;
   const int n = g.w * g.h;
@@ -65,6 +65,7 @@ __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ 
     const int R0 = row_map[i], C0 = col_map[j];
     for (int c = 0; c < g.C; ++c) {
       const T* __restrict__ plane = x + (size_t)c * g.W * g.H;
+      const T* __restrict__ blur_kc = blur + ((size_t)k * bs.frame + (size_t)c * bs.channel);  // a bank's entry; strides 0 without one
       const size_t oi = ((size_t)k * g.C + c) * n + lp;
       const double yv = (double)y[oi];
       const double wv = WEIGHTED ? (double)dw[oi] : 1.0;
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(256) void k_photometric_sums(const T* __restrict__ 
           const int cc = C0 + e - g.hb;
           if (cc < 0 || cc >= g.W) continue;
           const double v = ms.template at<double>(plane, g.W, g.H, rr, cc);
-          s += (double)blur[a * g.b + e] * v;
+          s += (double)blur_kc[a * g.b + e] * v;
         }
       }
       const double ws = wv * s, wy = wv * yv;
@@ -98,14 +99,15 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
   dim3 grid(chunks, g.K);
   const T* y = (p->d_obs_raw ? p->d_obs_raw : p->d_obs).as<const T>();  // always the RAW frames: the fit is absolute
   const MotionArgs<T> ma = motion_args<T>(p);
+  const BlurStride bs = blur_stride(p);
   return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (p->dw.effective<T>())
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->dw.effective<T>(), g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
     else
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part);
+                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
   });
 }
 

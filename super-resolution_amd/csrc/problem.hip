@@ -237,25 +237,29 @@ int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) 
 }
 
 // ---- free-form blur kernel (no reference counterpart; BlurModule builds a Gaussian only, blur_module.cpp:13-22) ----
-int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* taps) {
-  if (!p) return SRMAP_EINVAL;
+// The blur of the problem from the caller's taps: `entries` tables of ksize x ksize (bank_mode 0: the one free-form kernel, entries
+// 1), or the created blur for taps == NULL.  The one path of srmap_problem_set_blur_kernel and srmap_problem_set_blur_bank.
+static int install_blur(srmap_problem* p, int bank_mode, int entries, int ksize, const double* taps) {
+  const char* what = bank_mode ? "blur bank" : "blur kernel";
   if (taps) {
-    if (ksize < 1 || ksize % 2 != 1) return set_error(p->ctx, SRMAP_EINVAL, "blur kernel size must be odd and >= 1 (got %d)", ksize);
+    if (ksize < 1 || ksize % 2 != 1) return set_error(p->ctx, SRMAP_EINVAL, "%s size must be odd and >= 1 (got %d)", what, ksize);
     if (ksize > kMaxCustomBlur)
-      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "blur kernel size %d: a free-form kernel has at most %d x %d taps", ksize, kMaxCustomBlur, kMaxCustomBlur);
-    for (int i = 0; i < ksize * ksize; ++i)
-      if (!std::isfinite(taps[i])) return set_error(p->ctx, SRMAP_EINVAL, "blur kernel: tap %d is not finite", i);
+      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "%s size %d: a free-form kernel has at most %d x %d taps", what, ksize, kMaxCustomBlur, kMaxCustomBlur);
+    for (int i = 0; i < entries * ksize * ksize; ++i)
+      if (!std::isfinite(taps[i])) return set_error(p->ctx, SRMAP_EINVAL, "%s: tap %d is not finite", what, i);
   }
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   const int b = taps ? ksize : p->created_b;
+  const size_t bb = (size_t)b * b;
   std::vector<double> k2, k2t;
   if (taps) {
-    k2.assign(taps, taps + (size_t)b * b);
+    k2.assign(taps, taps + (size_t)entries * bb);
     k2t.resize(k2.size());
     // the adjoint of a correlation is the correlation with the kernel flipped in BOTH axes (kernel.t(), the reference's
-    // form, is that only for a kernel symmetric under both)
-    for (int a = 0; a < b; ++a)
-      for (int e = 0; e < b; ++e) k2t[(size_t)a * b + e] = k2[(size_t)(b - 1 - a) * b + (b - 1 - e)];
+    // form, is that only for a kernel symmetric under both); per entry of a bank
+    for (int q = 0; q < entries; ++q)
+      for (int a = 0; a < b; ++a)
+        for (int e = 0; e < b; ++e) k2t[q * bb + (size_t)a * b + e] = k2[q * bb + (size_t)(b - 1 - a) * b + (b - 1 - e)];
   } else {
     k2 = p->created_blur2d;
     k2t = p->created_blur2d_t;
@@ -272,20 +276,51 @@ int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* tap
   if (rc) return rc;
   p->d_blur = std::move(nb);  // the new tables move in; the old ones are freed
   p->d_blur_t = std::move(nbt);
+  const bool bank = taps != nullptr && bank_mode != 0;
+  p->blur_bank_mode = bank ? bank_mode : 0;
+  p->blur_bank = bank ? k2 : std::vector<double>();
+  if (bank) {  // the host mirrors of the single kernel hold entry 0
+    k2.resize(bb);
+    k2t.resize(bb);
+  }
   p->blur2d.swap(k2);
   p->blur2d_t.swap(k2t);
   p->blur1d = taps ? std::vector<double>((size_t)b, 0.0) : p->created_blur1d;  // a free-form kernel has no separable factor
   p->geo.b = b;
   p->geo.hb = (b - 1) / 2;
   p->custom_blur = taps != nullptr;
-  model_replan(p);  // "not covered" while a free-form kernel is set
+  model_replan(p);  // "not covered" while a free-form kernel or a bank is set
   return SRMAP_OK;
+}
+
+int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* taps) {
+  if (!p) return SRMAP_EINVAL;
+  return install_blur(p, 0, 1, ksize, taps);
 }
 
 int srmap_problem_get_blur_kernel(const srmap_problem* p, int* ksize, double* taps_out) {
   if (!p) return SRMAP_EINVAL;
   if (ksize) *ksize = p->geo.b;
+  if (taps_out && p->blur_bank_mode != 0)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: no single kernel is in force (srmap_problem_get_blur_bank returns its entries)");
   if (taps_out) std::copy(p->blur2d.begin(), p->blur2d.end(), taps_out);
+  return SRMAP_OK;
+}
+
+// ---- blur-kernel bank: a kernel per frame, per channel or per (frame, channel) (no reference counterpart) ----
+int srmap_problem_set_blur_bank(srmap_problem* p, int mode, int ksize, const double* taps) {
+  if (!p) return SRMAP_EINVAL;
+  if (!taps) return install_blur(p, 0, 1, 0, nullptr);
+  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
+    return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
+  return install_blur(p, mode, blur_bank_entries(mode, p->geo.K, p->geo.C), ksize, taps);
+}
+
+int srmap_problem_get_blur_bank(const srmap_problem* p, int* mode, int* ksize, double* taps_out) {
+  if (!p) return SRMAP_EINVAL;
+  if (mode) *mode = p->blur_bank_mode;
+  if (ksize) *ksize = p->geo.b;
+  if (taps_out) std::copy(p->blur_bank.begin(), p->blur_bank.end(), taps_out);
   return SRMAP_OK;
 }
 

@@ -58,6 +58,14 @@ struct MotionArgs {
 static_assert(std::is_trivially_copyable_v<MotionArgs<float>> && std::is_trivially_copyable_v<MotionArgs<double>>,
               "a kernel argument: no owner inside");
 
+// Blur-kernel bank (srmap_problem_set_blur_bank): the blur tables hold one b x b entry per frame, per channel or per
+// (frame, channel), stored [k][c]; a kernel reads entry (k, c) at table + k * frame + c * channel (elements; c the
+// ABSOLUTE channel of the problem, k the absolute frame).  {0, 0} without a bank: every (k, c) reads the one kernel.
+struct BlurStride {
+  int frame, channel;
+};
+static_assert(std::is_trivially_copyable_v<BlurStride>, "a kernel argument: no owner inside");
+
 struct Geometry {
   int W, H, C, K;  // HR size, channels, frames
   int w, h;        // LR size
@@ -154,12 +162,17 @@ struct srmap_problem {
   bool custom_blur = false;
   int created_b = 1;
   std::vector<double> created_blur2d, created_blur2d_t, created_blur1d;
+  // blur-kernel bank (srmap_problem_set_blur_bank; an alternative to the free-form kernel: setting either replaces the
+  // other): blur_bank_mode is the srmap_blur_bank_mode (0 = none), blur_bank the caller's taps [entries][b][b]; d_blur holds
+  // them in the dtype and d_blur_t the flip of every entry; custom_blur is true, blur2d / blur2d_t hold entry 0
+  int blur_bank_mode = 0;
+  std::vector<double> blur_bank;
   // device constants
   std::vector<srmap::DevBuf> d_ytabs;     // per-row y tables of frames whose warpAffine y table is not uniform (owned)
   srmap::DevBuf d_fwd_warps;      // WarpTaps<T>[K]
   srmap::DevBuf d_bwd_warps;      // WarpTaps<T>[K]
-  srmap::DevBuf d_blur;           // T[b*b]
-  srmap::DevBuf d_blur_t;         // T[b*b]
+  srmap::DevBuf d_blur;           // T[b*b]; T[entries][b*b] while a bank is set
+  srmap::DevBuf d_blur_t;         // T[b*b]; T[entries][b*b]
   srmap::DevBuf d_col_map;        // int[w]  decimation source column
   srmap::DevBuf d_row_map;        // int[h]
   // host mirrors of the warp taps (double) for tile planning
@@ -250,9 +263,22 @@ int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
-                         hipStream_t st, int ring = 0, T* ringbuf = nullptr);
+                         hipStream_t st, int ring = 0, T* ringbuf = nullptr, int obs_c0 = 0);
+// (obs_c0: the problem's channel of the view's channel 0, which selects the entries of a per-channel blur bank)
 // whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
+// ---- the problem's blur bank, for the launchers of the kernels that read a blur table ----
+inline int blur_bank_entries(int mode, int K, int C) {
+  return mode == SRMAP_BLUR_PER_FRAME ? K : mode == SRMAP_BLUR_PER_CHANNEL ? C : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? K * C : 1;
+}
+// the bank entry of (frame, channel); 0 without a bank
+inline int blur_bank_entry(int mode, int C, int k, int c) {
+  return mode == SRMAP_BLUR_PER_FRAME ? k : mode == SRMAP_BLUR_PER_CHANNEL ? c : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? k * C + c : 0;
+}
+inline BlurStride blur_stride(const srmap_problem* p) {
+  const int bb = p->geo.b * p->geo.b;
+  return {blur_bank_entry(p->blur_bank_mode, p->geo.C, 1, 0) * bb, blur_bank_entry(p->blur_bank_mode, p->geo.C, 0, 1) * bb};
+}
 // ---- the problem's motion, for the launchers of the kernels that sample it (kernels_data_direct.hip, the fits) ----
 inline MotionKind motion_kind(const srmap_problem* p) {
   return p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;

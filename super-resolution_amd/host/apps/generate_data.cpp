@@ -28,6 +28,10 @@ int main(int argc, char** argv) {
       "                        with --motion_sequence_path or --affine_motion_path)\n"
       "                        [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
       "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)\n"
+      "                        [--blur_bank_path=<file>] (a blur kernel per frame, per channel or per both instead of one blur:\n"
+      "                        text, `mode ksize entries` with mode 1 = per frame, 2 = per channel, 3 = per frame and channel\n"
+      "                        ([frame][channel]), then entries * ksize * ksize taps; a per-frame bank holds one entry per\n"
+      "                        motion of the sequence; an error together with --blur_kernel_path)\n"
       "                        [--photometric_path=<file>] (per-frame exposure, 'gain bias' per line, the bias in pixel units\n"
       "                        0..1: applied to the noise-free frame, the noise is added after)");
   const std::string input_image = flags.Str("input_image");
@@ -39,6 +43,7 @@ int main(int argc, char** argv) {
   parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
   const std::string flow_motion_path = flags.Str("flow_motion_path");  // not a reference flag
   parameters.blur_kernel_path = flags.Str("blur_kernel_path");  // not a reference flag
+  parameters.blur_bank_path = flags.Str("blur_bank_path");  // not a reference flag
   const std::string photometric_path = flags.Str("photometric_path");  // not a reference flag
   parameters.blur_radius = flags.Int("blur_radius", 0);
   parameters.blur_sigma = flags.Double("blur_sigma", 0.0);
@@ -48,6 +53,10 @@ int main(int argc, char** argv) {
   const int number_of_frames = flags.Int("number_of_frames", 4);
   flags.RejectUnknown();
   flags.Require("input_image");
+  if (!parameters.blur_bank_path.empty() && !parameters.blur_kernel_path.empty()) {
+    std::fprintf(stderr, "ERROR: --blur_bank_path and --blur_kernel_path exclude each other.\n");
+    return 1;
+  }
   if (!parameters.affine_motion_sequence_path.empty() && !parameters.motion_sequence_path.empty()) {
     std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
     return 1;

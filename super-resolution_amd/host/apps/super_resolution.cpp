@@ -11,7 +11,9 @@
 // displacement fields and their validity masks as data weights, srmap_register_flow), --save_flow_path and
 // --save_motion_path, nor --refine_motion_rounds / --refine_motion_dof (the joint motion refinement, srmap_refine_motion), nor
 // --blur_kernel_path (a free-form blur kernel, srmap_problem_set_blur_kernel) and --fit_blur_from / --fit_blur_ksize /
-// --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur), nor --photometric_path /
+// --save_blur_kernel_path (its calibration fit from a known HR image, srmap_fit_blur), nor --blur_bank_path (a blur kernel
+// per frame and / or channel, srmap_problem_set_blur_bank) and --fit_blur_bank_from / --fit_blur_bank_mode /
+// --save_blur_bank_path (its calibration fit, srmap_fit_blur_bank), nor --photometric_path /
 // --photometric_rounds / --save_photometric_path (per-frame gain and bias, srmap_problem_set_photometric and
 // srmap_fit_photometric).
 // Not carried over (out of scope, DESIGN.md
@@ -76,6 +78,12 @@ int main(int argc, char** argv) {
       "                       high-resolution image of the scene -- a calibration pair -- and solve with it)\n"
       "                       [--fit_blur_ksize=0] (size of the fitted kernel; 0 = the size of the blur in force)\n"
       "                       [--save_blur_kernel_path=<file>] (the fitted kernel, in --blur_kernel_path's format)\n"
+      "                       [--blur_bank_path=<file>] (a blur kernel per frame, per channel or per both: text, `mode ksize\n"
+      "                       entries` with mode 1 = per frame, 2 = per channel, 3 = per frame and channel, then the taps)\n"
+      "                       [--fit_blur_bank_from=<HR image>] --fit_blur_bank_mode=frame|channel|frame_channel (before solving,\n"
+      "                       fit a bank to the frames from this KNOWN high-resolution image, one kernel per entry, of\n"
+      "                       --fit_blur_ksize; solve with it) [--save_blur_bank_path=<file>] (the fitted bank, in\n"
+      "                       --blur_bank_path's format).  The bank flags exclude --blur_kernel_path and --fit_blur_from.\n"
       "                       [--photometric_path=<file>] (known per-frame exposure, 'gain bias' per line, the bias in pixel\n"
       "                       units 0..1: the solve runs against (frame - bias) / gain)\n"
       "                       [--photometric_rounds=-1] (N >= 0: fit gain and bias of every frame but the first at the initial\n"
@@ -138,6 +146,11 @@ int main(int argc, char** argv) {
   const std::string fit_blur_from = flags.Str("fit_blur_from");
   const int fit_blur_ksize = flags.Int("fit_blur_ksize", 0);
   const std::string save_blur_kernel_path = flags.Str("save_blur_kernel_path");
+  // not reference flags: a blur-kernel bank (srmap_problem_set_blur_bank) and its calibration fit (srmap_fit_blur_bank)
+  model_parameters.blur_bank_path = flags.Str("blur_bank_path");
+  const std::string fit_blur_bank_from = flags.Str("fit_blur_bank_from");
+  const std::string fit_blur_bank_mode = flags.Str("fit_blur_bank_mode");
+  const std::string save_blur_bank_path = flags.Str("save_blur_bank_path");
   // not reference flags: the photometric frame model (srmap_problem_set_photometric) and its fit (srmap_fit_photometric)
   const std::string photometric_path = flags.Str("photometric_path");
   const int photometric_rounds = flags.Int("photometric_rounds", -1);
@@ -210,8 +223,30 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ERROR: --fit_blur_ksize is 0 or an odd size up to 7.\n");
     return 1;
   }
-  if (fit_blur_from.empty() && (!save_blur_kernel_path.empty() || fit_blur_ksize != 0)) {
-    std::fprintf(stderr, "ERROR: --save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from.\n");
+  if ((fit_blur_from.empty() && !save_blur_kernel_path.empty()) || (fit_blur_from.empty() && fit_blur_bank_from.empty() && fit_blur_ksize != 0)) {
+    std::fprintf(stderr, "ERROR: --save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from (--fit_blur_ksize also goes with --fit_blur_bank_from).\n");
+    return 1;
+  }
+  {
+    // the bank and the single kernel are alternatives, and so are their fits
+    const bool bank_flag = !model_parameters.blur_bank_path.empty() || !fit_blur_bank_from.empty();
+    const char* other = !model_parameters.blur_kernel_path.empty() ? "--blur_kernel_path" : !fit_blur_from.empty() ? "--fit_blur_from" : nullptr;
+    if (bank_flag && other) {
+      std::fprintf(stderr, "ERROR: %s and %s exclude each other.\n", !model_parameters.blur_bank_path.empty() ? "--blur_bank_path" : "--fit_blur_bank_from", other);
+      return 1;
+    }
+  }
+  if (fit_blur_bank_from.empty() && (!fit_blur_bank_mode.empty() || !save_blur_bank_path.empty())) {
+    std::fprintf(stderr, "ERROR: --fit_blur_bank_mode and --save_blur_bank_path need --fit_blur_bank_from.\n");
+    return 1;
+  }
+  const int fit_bank_mode = fit_blur_bank_mode == "frame" ? 1 : fit_blur_bank_mode == "channel" ? 2 : fit_blur_bank_mode == "frame_channel" ? 3 : 0;
+  if (!fit_blur_bank_from.empty() && fit_bank_mode == 0) {
+    std::fprintf(stderr, "ERROR: --fit_blur_bank_from needs --fit_blur_bank_mode=frame|channel|frame_channel.\n");
+    return 1;
+  }
+  if (!fit_blur_bank_from.empty() && (!flow_motion_path.empty() || registration_name == "flow")) {
+    std::fprintf(stderr, "ERROR: --fit_blur_bank_from has no sampling leg for a displacement field: not with --flow_motion_path or --registration=flow.\n");
     return 1;
   }
   if (photometric_rounds < -1) {
@@ -395,6 +430,26 @@ int main(int argc, char** argv) {
     std::printf("Fitted a %d x %d blur kernel: cost %g -> %g, status %g.\n", fitted.GetSize(), fitted.GetSize(), quality[0], quality[1], quality[4]);
     if (!save_blur_kernel_path.empty() && !fitted.SaveToFile(save_blur_kernel_path)) {
       std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_blur_kernel_path.c_str());
+      return 1;
+    }
+  }
+
+  // --fit_blur_bank_from: the same calibration fit per entry of a bank (a kernel per frame, per channel or per both)
+  if (!fit_blur_bank_from.empty()) {
+    if (interpolate_color || spectral_pca) {
+      std::fprintf(stderr, "ERROR: --fit_blur_bank_from works in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
+      return 1;
+    }
+    BlurFitOptions fit_options;
+    fit_options.ksize = fit_blur_ksize;
+    std::vector<double> quality;
+    const BlurKernelBank fitted = solver.FitBlurBank(util::LoadImage(fit_blur_bank_from), fit_bank_mode, fit_options, &quality);
+    int degenerate = 0;
+    for (int e = 0; e < fitted.GetNumEntries(); ++e) degenerate += quality[5 * e + 4] != 0.0;
+    std::printf("Fitted a bank of %d %d x %d blur kernels (mode %s): %d degenerate.\n", fitted.GetNumEntries(), fitted.GetSize(),
+                fitted.GetSize(), fit_blur_bank_mode.c_str(), degenerate);
+    if (!save_blur_bank_path.empty() && !fitted.SaveToFile(save_blur_bank_path)) {
+      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_blur_bank_path.c_str());
       return 1;
     }
   }

@@ -118,23 +118,34 @@ class BlurModule : public DegradationOperator {
   explicit BlurModule(const BlurKernel& kernel) : blur_radius_(kernel.GetSize()), sigma_(0.0), kernel_(kernel) {
     if (kernel.Empty()) srmap_host::Fail("BlurModule: the blur kernel is empty");
   }
+  // not in the reference: a bank of free-form kernels, one per frame, per channel or per (frame, channel)
+  // (srmap_problem_set_blur_bank, include/srmap.h); a per-frame entry goes by the index the operator is applied with
+  explicit BlurModule(const BlurKernelBank& bank) : blur_radius_(bank.GetSize()), sigma_(0.0), bank_(bank) {
+    if (bank.Empty()) srmap_host::Fail("BlurModule: the blur bank is empty");
+  }
   void ApplyToImage(ImageData* image_data, const int index) const override {
-    srmap_host::RunChain(Chain(), image_data, 0, false);
+    srmap_host::RunChain(Chain(), image_data, Chain().BankPerFrame() ? index : 0, false);
   }
   void ApplyTransposeToImage(ImageData* image_data, const int index) const override {
-    srmap_host::RunChain(Chain(), image_data, 0, true);
+    srmap_host::RunChain(Chain(), image_data, Chain().BankPerFrame() ? index : 0, true);
   }
   void Describe(srmap_host::ChainParams* c) const override {
-    if (kernel_.Empty()) { c->blur_ksize = blur_radius_; c->blur_sigma = sigma_; c->blur_taps.clear(); c->blur_taps_ksize = 0; }
+    c->blur_bank_mode = 0; c->blur_bank_ksize = 0; c->blur_bank.clear();
+    if (!bank_.Empty()) {
+      c->blur_ksize = 0; c->blur_sigma = 0.0; c->blur_taps.clear(); c->blur_taps_ksize = 0;
+      c->blur_bank_mode = bank_.GetMode(); c->blur_bank_ksize = bank_.GetSize(); c->blur_bank = bank_.GetTaps();
+    } else if (kernel_.Empty()) { c->blur_ksize = blur_radius_; c->blur_sigma = sigma_; c->blur_taps.clear(); c->blur_taps_ksize = 0; }
     else { c->blur_ksize = 0; c->blur_sigma = 0.0; c->blur_taps = kernel_.GetTaps(); c->blur_taps_ksize = kernel_.GetSize(); }
   }
-  bool IsFreeForm() const { return !kernel_.Empty(); }
+  bool IsFreeForm() const { return !kernel_.Empty() || !bank_.Empty(); }
+  bool IsBank() const { return !bank_.Empty(); }
 
  private:
   srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const int blur_radius_;
   const double sigma_;
   const BlurKernel kernel_;
+  const BlurKernelBank bank_;
 };
 
 class DownsamplingModule : public DegradationOperator {
@@ -197,6 +208,10 @@ struct ImageModelParameters {
   // blur_radius / blur_sigma
   std::string blur_kernel_path = "";
   BlurKernel blur_kernel;
+  // not in the reference: a blur-kernel bank (text file: `mode ksize entries`, then the taps; image_model/blur_kernel.h); it
+  // replaces the Gaussian and excludes blur_kernel(_path)
+  std::string blur_bank_path = "";
+  BlurKernelBank blur_bank;
   double noise_sigma = 0.0;
   uint64_t noise_seed = 0x5eedULL;  // not in the reference (cv::randn draws from OpenCV's global generator)
 };
@@ -227,7 +242,13 @@ class ImageModel {
       if (seq.GetNumMotionShifts() == 0) seq.LoadSequenceFromFile(parameters.motion_sequence_path);
       model.AddDegradationOperator(std::make_shared<MotionModule>(seq));
     }
-    if (!parameters.blur_kernel_path.empty() || !parameters.blur_kernel.Empty()) {
+    if (!parameters.blur_bank_path.empty() || !parameters.blur_bank.Empty()) {
+      if (!parameters.blur_kernel_path.empty() || !parameters.blur_kernel.Empty())
+        srmap_host::Fail("both a blur bank and a blur kernel were given: a model has one BlurModule");
+      BlurKernelBank bank = parameters.blur_bank;
+      if (bank.Empty()) bank.LoadFromFile(parameters.blur_bank_path);
+      model.AddDegradationOperator(std::make_shared<BlurModule>(bank));
+    } else if (!parameters.blur_kernel_path.empty() || !parameters.blur_kernel.Empty()) {
       BlurKernel kernel = parameters.blur_kernel;
       if (kernel.Empty()) kernel.LoadFromFile(parameters.blur_kernel_path);
       model.AddDegradationOperator(std::make_shared<BlurModule>(kernel));
@@ -252,7 +273,7 @@ class ImageModel {
     // MotionModule the fused problem has ONE frame, whatever index the caller passes
     const AdditiveNoiseModule* noise = nullptr;
     if (Canonical(&chain, &noise)) {
-      srmap_host::RunChain(chain, image_data, chain.HasMotion() ? index : 0, false);
+      srmap_host::RunChain(chain, image_data, (chain.HasMotion() || chain.BankPerFrame()) ? index : 0, false);
       if (noise) noise->ApplyToImage(image_data, index);
       return;
     }
@@ -261,7 +282,7 @@ class ImageModel {
   // image_model.cpp:93-101: transposes in reverse order.
   void ApplyTransposeToImage(ImageData* image_data, const int index) const {
     srmap_host::ChainParams chain;
-    if (Canonical(&chain)) { srmap_host::RunChain(chain, image_data, chain.HasMotion() ? index : 0, true); return; }  // a trailing noise module's transpose is a no-op
+    if (Canonical(&chain)) { srmap_host::RunChain(chain, image_data, (chain.HasMotion() || chain.BankPerFrame()) ? index : 0, true); return; }  // a trailing noise module's transpose is a no-op
     for (int i = static_cast<int>(operators_.size()) - 1; i >= 0; --i) operators_[i]->ApplyTransposeToImage(image_data, index);
   }
   int GetDownsamplingScale() const { return downsampling_scale_; }

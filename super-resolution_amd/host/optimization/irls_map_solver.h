@@ -8,7 +8,8 @@
 // irls_map_solver.cpp:97-113.  Analytical differentiation only: the reference's
 // numeric-difference variant is a test-only alternative outside the path.
 // Not in the reference: RefineMotion / SolveJoint, the joint motion refinement of include/srmap.h (srmap_refine_motion),
-// FitBlur, the calibration fit of the blur kernel (srmap_fit_blur), and SetPhotometric / FitPhotometric / SolvePhotometric /
+// FitBlur, the calibration fit of the blur kernel (srmap_fit_blur), SetBlurBank / FitBlurBank, a blur kernel per frame and /
+// or channel and its fit (srmap_problem_set_blur_bank, srmap_fit_blur_bank), and SetPhotometric / FitPhotometric / SolvePhotometric /
 // SolvePhotometricJoint, the photometric frame model (srmap_problem_set_photometric, srmap_fit_photometric).
 #pragma once
 #include <cmath>
@@ -284,6 +285,42 @@ class IRLSMapSolver : public MapSolver {
                 << ", status " << q[4] << std::endl;
     if (quality) *quality = q;
     return BlurKernel(ksize, taps);
+  }
+  // A blur-kernel bank for the solver (srmap_problem_set_blur_bank; not in the reference): it replaces the model's blur
+  // for later solves, fits and ComputeAllTerms.  The entries must fit the solver's frames and channels.
+  void SetBlurBank(const BlurKernelBank& bank) {
+    if (bank.Empty()) srmap_host::Fail("SetBlurBank: the blur bank is empty");
+    const int want = bank.GetMode() == SRMAP_BLUR_PER_FRAME ? GetNumImages() : bank.GetMode() == SRMAP_BLUR_PER_CHANNEL ? GetNumChannels() : GetNumImages() * GetNumChannels();
+    if (bank.GetNumEntries() != want) srmap_host::Fail("SetBlurBank: the number of entries does not fit the solver's frames and channels");
+    srmap_host::Check(srmap_problem_set_blur_bank(problem_.get(), bank.GetMode(), bank.GetSize(), bank.GetTaps().data()), "srmap_problem_set_blur_bank");
+  }
+  // Calibration fit of a blur-kernel bank (srmap_fit_blur_bank; not in the reference): FitBlur's fit, separately over the
+  // observations of each entry of `mode` (1 per frame, 2 per channel, 3 per frame and channel), from the KNOWN
+  // high-resolution image `hr`, INSTALLED as the solver's blur.  quality (optional): 5 numbers per entry, FitBlur's (status
+  // 3: the entry is degenerate and keeps its kernel).  Like FitBlur a calibration fit: blind alternation is not offered.
+  BlurKernelBank FitBlurBank(const ImageData& hr, const int mode, const BlurFitOptions& options = BlurFitOptions(), std::vector<double>* quality = nullptr) {
+    if (hr.GetNumChannels() != GetNumChannels() || hr.GetImageSize() != GetImageSize())
+      srmap_host::Fail("the high-resolution image does not match the HR geometry");
+    if (mode < SRMAP_BLUR_PER_FRAME || mode > SRMAP_BLUR_PER_FRAME_CHANNEL) srmap_host::Fail("FitBlurBank: the mode is 1, 2 or 3");
+    srmap_blur_fit_options o;
+    srmap_blur_fit_options_default(&o);
+    o.ksize = options.ksize;
+    o.sum_to_one = options.sum_to_one ? 1 : 0;
+    o.ridge = options.ridge;
+    o.apply = 1;
+    int ksize = options.ksize;
+    if (ksize == 0) srmap_host::Check(srmap_problem_get_blur_kernel(problem_.get(), &ksize, nullptr), "srmap_problem_get_blur_kernel");
+    const int entries = mode == SRMAP_BLUR_PER_FRAME ? GetNumImages() : mode == SRMAP_BLUR_PER_CHANNEL ? GetNumChannels() : GetNumImages() * GetNumChannels();
+    const std::vector<double> x = hr.ToPlanar();
+    const size_t bb = static_cast<size_t>(ksize > 0 ? ksize : 1) * (ksize > 0 ? ksize : 1);
+    std::vector<double> taps(bb * entries), q(5 * static_cast<size_t>(entries));
+    srmap_host::Check(srmap_fit_blur_bank(problem_.get(), x.data(), mode, &o, taps.data(), q.data(), nullptr), "srmap_fit_blur_bank");
+    if (IsVerbose())
+      for (int e = 0; e < entries; ++e)
+        std::cout << "Blur bank fit, entry " << e << " (" << ksize << " x " << ksize << "): cost " << q[5 * e] << " -> " << q[5 * e + 1]
+                  << ", status " << q[5 * e + 4] << std::endl;
+    if (quality) *quality = q;
+    return BlurKernelBank(mode, ksize, entries, taps);
   }
   // Solve, then `rounds` times (RefineMotion at the current estimate, Solve warm-started from it).  motion (optional)
   // receives the final matrices (untouched when rounds == 0).  Not in the reference.

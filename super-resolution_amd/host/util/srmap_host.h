@@ -59,6 +59,12 @@ struct ChainParams {
   double blur_sigma = 0.0;
   std::vector<double> blur_taps;  // blur_taps_ksize^2 taps of a free-form kernel (then blur_ksize / blur_sigma are unused); empty = the Gaussian
   int blur_taps_ksize = 0;
+  // a blur-kernel bank (srmap_problem_set_blur_bank; then the three blur members above are unused): the mode (0 = none),
+  // its kernel size and entries x blur_bank_ksize^2 taps
+  int blur_bank_mode = 0, blur_bank_ksize = 0;
+  std::vector<double> blur_bank;
+  bool BankPerFrame() const { return blur_bank_mode == SRMAP_BLUR_PER_FRAME || blur_bank_mode == SRMAP_BLUR_PER_FRAME_CHANNEL; }
+  size_t BankEntries() const { return blur_bank_mode ? blur_bank.size() / (static_cast<size_t>(blur_bank_ksize) * blur_bank_ksize) : 0; }
   bool HasMotion() const { return !shifts_xy.empty() || !affine_2x3.empty() || !flow.empty(); }
   size_t FlowFrame() const { return 2 * static_cast<size_t>(flow_width) * static_cast<size_t>(flow_height); }
   int NumMotions() const {
@@ -70,6 +76,8 @@ struct ChainParams {
     if (!shifts_xy.empty()) shifts_xy.resize(2 * n);
     if (!affine_2x3.empty()) affine_2x3.resize(6 * n);
     if (!flow.empty()) flow.resize(FlowFrame() * n);
+    // a per-frame bank with more entries than observations: the first n (a per-(frame, channel) bank must fit as given)
+    if (blur_bank_mode == SRMAP_BLUR_PER_FRAME && BankEntries() > n) blur_bank.resize(n * static_cast<size_t>(blur_bank_ksize) * blur_bank_ksize);
   }
 };
 
@@ -83,9 +91,20 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
     Fail(("the flow motion is given for a " + std::to_string(c.flow_width) + " x " + std::to_string(c.flow_height) +
           " high-resolution image, the model is applied at " + std::to_string(width) + " x " + std::to_string(height)).c_str());
   d.frames = c.HasMotion() ? c.NumMotions() : c.frames;
+  const bool bank = c.blur_bank_mode != 0;
+  if (bank) {
+    // a chain without motion and without a frame count takes its frames from a per-frame bank
+    const int per_frame = c.blur_bank_mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? channels : 1;
+    if (!c.HasMotion() && c.frames <= 1 && c.BankPerFrame()) d.frames = static_cast<int>(c.BankEntries()) / per_frame;
+    const size_t want = c.blur_bank_mode == SRMAP_BLUR_PER_CHANNEL ? static_cast<size_t>(channels) : static_cast<size_t>(d.frames) * per_frame;
+    if (c.BankEntries() != want)
+      Fail(("the blur bank holds " + std::to_string(c.BankEntries()) + " entries, the model has " + std::to_string(d.frames) + " frames and " +
+            std::to_string(channels) + " channels: its mode " + std::to_string(c.blur_bank_mode) + " needs " + std::to_string(want)).c_str());
+  }
   d.scale = c.scale;
   d.shifts_xy = c.shifts_xy.empty() ? nullptr : c.shifts_xy.data();
-  d.blur_ksize = c.blur_taps.empty() ? c.blur_ksize : 0; d.blur_sigma = c.blur_taps.empty() ? c.blur_sigma : 0.0;
+  const bool gaussian = c.blur_taps.empty() && !bank;
+  d.blur_ksize = gaussian ? c.blur_ksize : 0; d.blur_sigma = gaussian ? c.blur_sigma : 0.0;
   d.dtype = SRMAP_F64;  // the reference computes in double
   srmap_problem* p = nullptr;
   Check(srmap_problem_create(Context(), &d, &p), "srmap_problem_create");
@@ -93,7 +112,9 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
   if (!c.affine_2x3.empty())
     Check(srmap_problem_set_affine_motion(p, c.affine_2x3.data()), "srmap_problem_set_affine_motion");
   if (!c.flow.empty()) Check(srmap_problem_set_flow(p, c.flow.data()), "srmap_problem_set_flow");
-  if (!c.blur_taps.empty())
+  if (bank)
+    Check(srmap_problem_set_blur_bank(p, c.blur_bank_mode, c.blur_bank_ksize, c.blur_bank.data()), "srmap_problem_set_blur_bank");
+  else if (!c.blur_taps.empty())
     Check(srmap_problem_set_blur_kernel(p, c.blur_taps_ksize, c.blur_taps.data()), "srmap_problem_set_blur_kernel");
   return problem;
 }

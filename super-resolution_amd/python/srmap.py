@@ -86,6 +86,7 @@ class ShardDesc(C.Structure):
 
 
 SHARD_NONE, SHARD_FRAMES, SHARD_ROWS, SHARD_CHANNELS, SHARD_GRID = 0, 1, 2, 3, 4
+BLUR_PER_FRAME, BLUR_PER_CHANNEL, BLUR_PER_FRAME_CHANNEL = 1, 2, 3  # srmap_blur_bank_mode
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p)
 HOST_SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
@@ -110,6 +111,10 @@ _SIGNATURES = [
     ("srmap_blur_fit_options_default", None, [C.c_void_p]),
     ("srmap_fit_blur", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_fit_blur_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_problem_set_blur_bank", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
+    ("srmap_problem_get_blur_bank", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p]),
+    ("srmap_fit_blur_bank", C.c_int, [C.c_void_p, c_double_p, C.c_int, C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_fit_blur_bank_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_problem_set_photometric", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_get_photometric", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
     ("srmap_photometric_fit_options_default", None, [C.c_void_p]),
@@ -492,6 +497,71 @@ class Problem:
             self.ctx.check(load().srmap_fit_blur(self._h, pa, *tail))
         k = int(round(np.sqrt(n)))
         return taps.reshape(k, k), q, ne
+
+    def _bank_entries(self, mode):
+        return {BLUR_PER_FRAME: self.K, BLUR_PER_CHANNEL: self.C, BLUR_PER_FRAME_CHANNEL: self.K * self.C}[mode]
+
+    def set_blur_bank(self, taps, mode=None):
+        """Blur-kernel bank: a kernel per frame [K][b][b] (BLUR_PER_FRAME), per channel [C][b][b] (BLUR_PER_CHANNEL) or per
+        (frame, channel) [K][C][b][b] (BLUR_PER_FRAME_CHANNEL); every entry as set_blur_kernel takes its kernel.  The mode is
+        inferred from the array's shape where that is unambiguous and required for a [n][b][b] array when K == C.  None
+        restores the blur the problem was created with."""
+        if taps is None:
+            self.ctx.check(load().srmap_problem_set_blur_bank(self._h, 0, 0, None))
+            return
+        a, pa = _d(taps)
+        if mode is None:
+            if a.ndim == 4:
+                mode = BLUR_PER_FRAME_CHANNEL
+            elif a.ndim == 3 and self.K != self.C and a.shape[0] in (self.K, self.C):
+                mode = BLUR_PER_FRAME if a.shape[0] == self.K else BLUR_PER_CHANNEL
+            else:
+                raise ValueError("set_blur_bank: the mode cannot be inferred from shape %s with K = %d, C = %d" % (a.shape, self.K, self.C))
+        if mode in (BLUR_PER_FRAME, BLUR_PER_CHANNEL, BLUR_PER_FRAME_CHANNEL):
+            lead = (self.K, self.C) if mode == BLUR_PER_FRAME_CHANNEL else (self._bank_entries(mode),)
+            if a.shape[:-2] != lead or a.ndim < 3 or a.shape[-1] != a.shape[-2]:
+                raise ValueError("set_blur_bank: shape %s is not %s + (b, b)" % (a.shape, lead))
+        self.ctx.check(load().srmap_problem_set_blur_bank(self._h, mode, a.shape[-1], pa))
+
+    def blur_bank(self):
+        """(mode, taps) of the bank in force -- taps [K][b][b], [C][b][b] or [K][C][b][b] -- or (0, None) when none is set."""
+        m, k = C.c_int(0), C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_blur_bank(self._h, C.byref(m), C.byref(k), None))
+        if m.value == 0:
+            return 0, None
+        lead = (self.K, self.C) if m.value == BLUR_PER_FRAME_CHANNEL else (self._bank_entries(m.value),)
+        out = np.empty(lead + (k.value, k.value))
+        self.ctx.check(load().srmap_problem_get_blur_bank(self._h, C.byref(m), C.byref(k), out.ctypes.data_as(c_double_p)))
+        return m.value, out
+
+    def fit_blur_bank(self, x, mode, ksize=None, sum_to_one=True, ridge=0.0, apply=True, stream=None, struct_size=None):
+        """srmap_fit_blur_bank: fit_blur's quadratic solved separately over the observations of each entry of `mode`, from
+        the KNOWN HR image x (a host array [C][H][W], or a device tensor of the problem's dtype, read on `stream`).  Returns
+        (taps [entries...][ksize][ksize], quality [entries][5] in fit_blur's layout -- status 0 fitted, 3 degenerate: the
+        entry keeps its kernel --, sums [entries][(n + 1)(n + 2) / 2]).  apply installs the result as set_blur_bank would.
+        A calibration fit: blind alternation with a solve is not offered."""
+        o = BlurFitOptions()
+        load().srmap_blur_fit_options_default(C.byref(o))
+        o.ksize, o.sum_to_one, o.ridge, o.apply = (0 if ksize is None else ksize), (1 if sum_to_one else 0), ridge, (1 if apply else 0)
+        if struct_size is not None:
+            o.struct_size = struct_size
+        kc = C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_blur_kernel(self._h, C.byref(kc), None))
+        kk = ksize if ksize else kc.value
+        n = max(kk, 1) ** 2
+        entries = self._bank_entries(mode) if mode in (BLUR_PER_FRAME, BLUR_PER_CHANNEL, BLUR_PER_FRAME_CHANNEL) else 1
+        taps, q, ne = np.zeros((entries, n)), np.zeros((entries, 5)), np.zeros((entries, (n + 1) * (n + 2) // 2))
+        tail = (mode, C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
+        if hasattr(x, "data_ptr"):
+            assert x.numel() == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_blur_bank_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
+        else:
+            a, pa = _d(x)
+            assert a.size == self.C * self.H * self.W
+            self.ctx.check(load().srmap_fit_blur_bank(self._h, pa, *tail))
+        k = int(round(np.sqrt(n)))
+        lead = (self.K, self.C) if mode == BLUR_PER_FRAME_CHANNEL else (entries,)
+        return taps.reshape(lead + (k, k)), q, ne
 
     def set_cost_rows(self, hr_row0, hr_row1):
         """Row-band sharding: count only the cost terms of HR rows [hr_row0, hr_row1)."""
