@@ -1,4 +1,5 @@
-// blur_fit.hip -- calibration fit of the blur kernel (srmap_fit_blur): with the HR image x KNOWN (a chart, a
+// blur_fit.hip -- calibration fit of the blur kernel, one (srmap_fit_blur) or a bank of them
+// (srmap_fit_blur_bank; one body, fit_device): with the HR image x KNOWN (a chart, a
 // calibration pair) the ksize x ksize taps h of B in A_k = D B M_k are a linear least-squares problem,
 //   E(h) = sum_k sum_c sum_u w (sum_t h_t s_t - y)^2,  s_t = (M_k x)(R0 + a - hb, C0 + e - hb), t = (a, e), 0 outside the image,
 // (R0, C0) the decimation source of LR pixel u, M_k sampled exactly as the forward kernel of the problem's motion samples it
@@ -12,9 +13,11 @@
 //             129 doubles: odd, so the rows a wave reads in phase 2 spread over the banks and lanes that share a row
 //             broadcast); phase 2 gives every thread its own <= 5 pairs (i <= j) and adds (w u_i) u_j over the tile in
 //             index order in f64 registers.  No cross-thread reduction, no atomics, a fixed order: bit-identical run to run;
-//   reduce    k_blur_fit_reduce adds the (frame, chunk) records in index order;
-//   pacing    one launch, one reduce, one copy of P doubles, one stream wait;
-//   solve     on the host in double: (G + mu I) h = b + mu h_current, mu = ridge trace(G) / n, by Cholesky
+//             A bank entry is the same quadratic over the entry's observations alone: the PER_CHANNEL instances keep a
+//             record per (frame, channel, chunk);
+//   reduce    k_fit_reduce (motion_fit.hip) adds the records of every entry in index order -- all of them for the single kernel;
+//   pacing    one launch, one reduce, one copy of entries x P doubles, one stream wait (FitPass, motion_fit.hip);
+//   solve     on the host in double, per entry: (G + mu I) h = b + mu h_current, mu = ridge trace(G) / n, by Cholesky
 //             (cholesky_factor_n, affine_map.hpp); sum_to_one: the KKT system of the constraint 1^T h = 1 by block
 //             elimination over the same factor, h = u - lambda v, u = A^-1 rhs, v = A^-1 1, lambda = (1^T u - 1) / (1^T v).
 #include <algorithm>
@@ -116,34 +119,6 @@ __global__ __launch_bounds__(256) void k_blur_fit_sums(const T* __restrict__ x, 
   }
 }
 
-// sums[q] = the `records` records partial[r][nsums] added in index order (k_fit_reduce of motion_fit.hip holds at most 64
-// sums per frame and keeps one record per frame; this one adds everything and has no cap)
-__global__ __launch_bounds__(256) void k_blur_fit_reduce(const double* __restrict__ partial, int records, int nsums,
-                                                         double* __restrict__ sums) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nsums) return;
-  double s = 0.0;
-  for (int r = 0; r < records; ++r) s += partial[(size_t)r * nsums + q];
-  sums[q] = s;
-}
-
-// The bank fit's reduce: entry e = blockIdx.y adds its records in index order -- `outer` groups `outer_stride` records
-// apart, `inner` consecutive records each, from record e * entry_stride on.  With the records laid out [frame][channel][chunk]
-// that is frame, channel, chunk order for every mode (srmap_fit_blur_bank_device fills the strides).  sums[e][nsums].
-__global__ __launch_bounds__(256) void k_blur_fit_reduce_bank(const double* __restrict__ partial, int nsums, int entry_stride,
-                                                              int outer, int outer_stride, int inner,
-                                                              double* __restrict__ sums) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nsums) return;
-  const int e = blockIdx.y;
-  double s = 0.0;
-  for (int o = 0; o < outer; ++o) {
-    const double* __restrict__ rec = partial + ((size_t)e * entry_stride + (size_t)o * outer_stride) * nsums + q;
-    for (int r = 0; r < inner; ++r) s += rec[(size_t)r * nsums];
-  }
-  sums[(size_t)e * nsums + q] = s;
-}
-
 // the instance of the problem's motion kind; false: the kind has none (a displacement field, which the entry point refuses).
 // per_channel: the bank fit's grid, a record per (frame, channel, chunk)
 template <typename T, int B, bool PER_CHANNEL>
@@ -151,18 +126,17 @@ bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K, PER_CHANNEL ? g.C : 1);
   const MotionArgs<T> ma = motion_args<T>(p);
+  const T* dw = p->dw.effective<T>();
   return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
-    if (p->dw.effective<T>())
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, true, PER_CHANNEL>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
-                         p->dw.effective<T>(), g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
-    else
-      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, false, PER_CHANNEL>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(),
-                         (const T*)nullptr, g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
+    dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
+      hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, decltype(weighted)::value != 0, PER_CHANNEL>), grid, dim3(256), 0, st, x,
+                         p->d_obs.as<const T>(), dw, g, ma, p->d_col_map.as<int>(), p->d_row_map.as<int>(), tpc, d_part);
+    });
   });
 }
 
-template <typename T, bool PER_CHANNEL = false>
+template <typename T, bool PER_CHANNEL>
 bool launch_sums(srmap_problem* p, int ksize, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
   if (ksize == 1) return launch_sums_m<T, 1, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
   if (ksize == 3) return launch_sums_m<T, 3, PER_CHANNEL>(p, x, chunks, tpc, d_part, st);
@@ -241,23 +215,89 @@ void solve_taps(const double* sums, int n, const std::vector<double>& hcur, cons
   h_out->swap(h);
 }
 
-// the argument checks the two fits share; *ksize: the fit's size
-int check_fit(srmap_problem* p, const srmap_blur_fit_options* options, srmap_blur_fit_options* opt, int* ksize) {
+const char kOptionsName[] = "srmap_blur_fit_options";
+
+// srmap_fit_blur refuses while a bank is set (the host form after its other checks, the device form first)
+int refuse_bank(srmap_problem* p) {
+  if (p->blur_bank_mode == 0) return SRMAP_OK;
+  return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
+}
+
+// srmap_fit_blur_bank validates its mode first, in both forms
+int check_mode(srmap_problem* p, int mode) {
+  if (mode == SRMAP_BLUR_PER_FRAME || mode == SRMAP_BLUR_PER_CHANNEL || mode == SRMAP_BLUR_PER_FRAME_CHANNEL) return SRMAP_OK;
+  return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
+}
+
+// The one body of the two fits' device forms: a kernel per entry of `mode`, mode 0 the single kernel -- one entry over every
+// observation, by the instances that walk (channel, pixel) together; a bank mode by the PER_CHANNEL instances.  The outputs
+// hold one entry after the other.
+int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, const srmap_blur_fit_options* options,
+               double* taps_out, double* quality_out, double* normal_equations_out) {
   srmap_ctx* ctx = p->ctx;
+  const Geometry& g = p->geo;
+  const char* const what = mode ? "blur bank fit" : "blur fit";
   if (p->flow)
     return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
-  srmap_blur_fit_options_default(opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_blur_fit_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
-    *opt = *options;
-  }
-  *ksize = opt->ksize == 0 ? p->geo.b : opt->ksize;
-  if (*ksize < 1 || *ksize % 2 != 1) return set_error(ctx, SRMAP_EINVAL, "blur fit: ksize must be odd and >= 1 (got %d)", *ksize);
-  if (*ksize > kMaxCustomBlur)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "blur fit: ksize %d: at most %d x %d taps are fitted", *ksize, kMaxCustomBlur, kMaxCustomBlur);
-  if (!(opt->ridge >= 0.0) || !std::isfinite(opt->ridge)) return set_error(ctx, SRMAP_EINVAL, "blur fit: ridge must be finite and >= 0");
+  srmap_blur_fit_options opt;
+  if (int rc = options_in_force(ctx, options, srmap_blur_fit_options_default, kOptionsName, &opt)) return rc;
+  const int ksize = opt.ksize == 0 ? g.b : opt.ksize;
+  if (ksize < 1 || ksize % 2 != 1) return set_error(ctx, SRMAP_EINVAL, "blur fit: ksize must be odd and >= 1 (got %d)", ksize);
+  if (ksize > kMaxCustomBlur)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "blur fit: ksize %d: at most %d x %d taps are fitted", ksize, kMaxCustomBlur, kMaxCustomBlur);
+  if (!(opt.ridge >= 0.0) || !std::isfinite(opt.ridge)) return set_error(ctx, SRMAP_EINVAL, "blur fit: ridge must be finite and >= 0");
   if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
+
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream_of(ctx, hip_stream);
+  if (int rc = problem_state_read(p, st)) return rc;
+
+  // a chunk holds tpc tiles of the observations of a frame (mode 0) or of one of its channels; the records lie
+  // [frame][chunk] or [frame][channel][chunk]
+  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
+  const long long nobs = (long long)g.w * g.h * (mode ? 1 : g.C);
+  const long long tiles = (nobs + kTile - 1) / kTile;
+  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
+  const int chunks = (int)((tiles + tpc - 1) / tpc);
+  const int per_frame = mode ? g.C * chunks : chunks;
+  const int entries = blur_bank_entries(mode, g.K, g.C);
+  FitPass fit;  // a row per entry, no table
+  if (!fit.alloc(entries, P, (size_t)g.K * per_frame * P, false)) return set_error(ctx, SRMAP_ENOMEM, "%s: allocation failed", what);
+  if (!dispatch_dtype(p->dtype, [&](auto t) {
+        using T = decltype(t);
+        return mode ? launch_sums<T, true>(p, ksize, (const T*)x_dev, chunks, tpc, fit.d_part.as<double>(), st)
+                    : launch_sums<T, false>(p, ksize, (const T*)x_dev, chunks, tpc, fit.d_part.as<double>(), st);
+      }))
+    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
+  SRMAP_HIP(ctx, hipGetLastError());
+  // the records of an entry, in (frame, channel, chunk) order: all of them, a frame's, a channel's chunks of every frame, or
+  // the chunks of one (frame, channel)
+  const int row_stride = mode == SRMAP_BLUR_PER_FRAME ? per_frame : chunks;  // (mode 0 has the one row)
+  const int outer = mode == SRMAP_BLUR_PER_CHANNEL ? g.K : 1;
+  const int inner = mode == 0 ? g.K * per_frame : mode == SRMAP_BLUR_PER_FRAME ? per_frame : chunks;
+  if (!fit.reduce_and_fetch(row_stride, outer, per_frame, inner, st)) return set_error(ctx, SRMAP_EHIP, "%s: pass failed", what);
+
+  // ---- the host solve, entry by entry ----
+  std::vector<double> taps((size_t)entries * n), quality((size_t)entries * 5);
+  bool any = false;
+  for (int q = 0; q < entries; ++q) {
+    // the (frame, channel) that stands for entry q, and the kernel in force for it, zero-padded or centre-cropped to ksize
+    const int k = mode == SRMAP_BLUR_PER_FRAME ? q : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? q / g.C : 0;
+    const int c = mode == SRMAP_BLUR_PER_CHANNEL ? q : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? q % g.C : 0;
+    const double* cur = p->blur_bank_mode ? p->blur_bank.data() + (size_t)blur_bank_entry(p->blur_bank_mode, g.C, k, c) * g.b * g.b
+                                          : p->blur2d.data();
+    std::vector<double> h;
+    solve_taps(fit.sums(q), n, resized_kernel(cur, g.b, ksize), opt, &h, quality.data() + (size_t)q * 5);
+    std::copy(h.begin(), h.end(), taps.begin() + (size_t)q * n);
+    any = any || quality[(size_t)q * 5 + 4] == 0.0;
+  }
+  if (any && opt.apply) {
+    const int rc = mode ? srmap_problem_set_blur_bank(p, mode, ksize, taps.data()) : srmap_problem_set_blur_kernel(p, ksize, taps.data());
+    if (rc) return rc;
+  }
+  if (taps_out) std::copy(taps.begin(), taps.end(), taps_out);
+  if (quality_out) std::copy(quality.begin(), quality.end(), quality_out);
+  if (normal_equations_out) std::copy(fit.sums(0), fit.sums(0) + (size_t)entries * P, normal_equations_out);
   return SRMAP_OK;
 }
 
@@ -280,147 +320,31 @@ extern "C" int srmap_fit_blur_device(srmap_problem* p, const void* x_dev, void* 
                                      const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
                                      double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
-  srmap_ctx* ctx = p->ctx;
-  if (p->blur_bank_mode != 0)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
-  srmap_blur_fit_options opt;
-  int ksize = 0;
-  if (int rc = check_fit(p, options, &opt, &ksize)) return rc;
-  const Geometry& g = p->geo;
-
-  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-  int rc = problem_state_read(p, st);
-  if (rc) return rc;
-
-  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
-  const long long nobs = (long long)g.w * g.h * g.C;
-  const long long tiles = (nobs + kTile - 1) / kTile;
-  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
-  const int chunks = (int)((tiles + tpc - 1) / tpc);
-  const int records = g.K * chunks;
-  DevBuf part, sums;
-  PinnedBuf sums_host;
-  if (part.alloc((size_t)records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)P * sizeof(double)) != hipSuccess ||
-      sums_host.alloc((size_t)P * sizeof(double)) != hipSuccess)
-    return set_error(ctx, SRMAP_ENOMEM, "blur fit: allocation failed");
-  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
-  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
-    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
-  SRMAP_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_blur_fit_reduce, dim3((P + 255) / 256), dim3(256), 0, st, d_part, records, P, d_sums);
-  SRMAP_HIP(ctx, hipGetLastError());
-  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st));
-  SRMAP_HIP(ctx, hipStreamSynchronize(st));
-
-  // ---- the host solve ----
-  // the kernel in force, zero-padded or centre-cropped to ksize
-  const std::vector<double> hcur = resized_kernel(p->blur2d.data(), g.b, ksize);
-  std::vector<double> h;
-  double quality[5];
-  solve_taps(h_sums, n, hcur, opt, &h, quality);
-  if (quality[4] == 0.0 && opt.apply) {
-    rc = srmap_problem_set_blur_kernel(p, ksize, h.data());
-    if (rc) return rc;
-  }
-  if (taps_out) std::copy(h.begin(), h.end(), taps_out);
-  if (quality_out) std::copy(quality, quality + 5, quality_out);
-  if (normal_equations_out) std::copy(h_sums, h_sums + P, normal_equations_out);
-  return SRMAP_OK;
+  if (int rc = refuse_bank(p)) return rc;
+  return fit_device(p, x_dev, hip_stream, 0, options, taps_out, quality_out, normal_equations_out);
 }
 
 extern "C" int srmap_fit_blur_bank_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode,
                                           const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
                                           double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
-  srmap_ctx* ctx = p->ctx;
-  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
-    return set_error(ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
-  srmap_blur_fit_options opt;
-  int ksize = 0;
-  if (int rc = check_fit(p, options, &opt, &ksize)) return rc;
-  const Geometry& g = p->geo;
-
-  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-  int rc = problem_state_read(p, st);
-  if (rc) return rc;
-
-  // one record per (frame, channel, chunk): a chunk holds LR pixels of one channel
-  const int n = ksize * ksize, n1 = n + 1, P = n1 * (n1 + 1) / 2;
-  const long long nobs = (long long)g.w * g.h;
-  const long long tiles = (nobs + kTile - 1) / kTile;
-  const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
-  const int chunks = (int)((tiles + tpc - 1) / tpc);
-  const size_t records = (size_t)g.K * g.C * chunks;
-  const int entries = blur_bank_entries(mode, g.K, g.C);
-  DevBuf part, sums;
-  PinnedBuf sums_host;
-  if (part.alloc(records * P * sizeof(double)) != hipSuccess || sums.alloc((size_t)entries * P * sizeof(double)) != hipSuccess ||
-      sums_host.alloc((size_t)entries * P * sizeof(double)) != hipSuccess)
-    return set_error(ctx, SRMAP_ENOMEM, "blur bank fit: allocation failed");
-  double *const d_part = part.as<double>(), *const d_sums = sums.as<double>(), *const h_sums = sums_host.as<double>();
-  if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t), true>(p, ksize, (const decltype(t)*)x_dev, chunks, tpc, d_part, st); }))
-    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
-  SRMAP_HIP(ctx, hipGetLastError());
-  // the records of an entry, in (frame, channel, chunk) order: a frame's C * chunks, a channel's chunks of every frame, or
-  // the chunks of one (frame, channel)
-  const int entry_stride = mode == SRMAP_BLUR_PER_FRAME ? g.C * chunks : chunks;
-  const int outer = mode == SRMAP_BLUR_PER_CHANNEL ? g.K : 1, outer_stride = g.C * chunks;
-  const int inner = mode == SRMAP_BLUR_PER_FRAME ? g.C * chunks : chunks;
-  hipLaunchKernelGGL(k_blur_fit_reduce_bank, dim3((P + 255) / 256, entries), dim3(256), 0, st, d_part, P, entry_stride, outer,
-                     outer_stride, inner, d_sums);
-  SRMAP_HIP(ctx, hipGetLastError());
-  SRMAP_HIP(ctx, hipMemcpyAsync(h_sums, d_sums, (size_t)entries * P * sizeof(double), hipMemcpyDeviceToHost, st));
-  SRMAP_HIP(ctx, hipStreamSynchronize(st));
-
-  // ---- the host solve, entry by entry ----
-  std::vector<double> bank((size_t)entries * n), quality((size_t)entries * 5);
-  bool any = false;
-  for (int q = 0; q < entries; ++q) {
-    // the (frame, channel) that stands for entry q, and the kernel in force for it
-    const int k = mode == SRMAP_BLUR_PER_CHANNEL ? 0 : mode == SRMAP_BLUR_PER_FRAME ? q : q / g.C;
-    const int c = mode == SRMAP_BLUR_PER_CHANNEL ? q : mode == SRMAP_BLUR_PER_FRAME ? 0 : q % g.C;
-    const double* cur = p->blur_bank_mode ? p->blur_bank.data() + (size_t)blur_bank_entry(p->blur_bank_mode, g.C, k, c) * g.b * g.b
-                                          : p->blur2d.data();
-    const std::vector<double> hcur = resized_kernel(cur, g.b, ksize);
-    std::vector<double> h;
-    solve_taps(h_sums + (size_t)q * P, n, hcur, opt, &h, quality.data() + (size_t)q * 5);
-    std::copy(h.begin(), h.end(), bank.begin() + (size_t)q * n);
-    any = any || quality[(size_t)q * 5 + 4] == 0.0;
-  }
-  if (any && opt.apply) {
-    rc = srmap_problem_set_blur_bank(p, mode, ksize, bank.data());
-    if (rc) return rc;
-  }
-  if (taps_out) std::copy(bank.begin(), bank.end(), taps_out);
-  if (quality_out) std::copy(quality.begin(), quality.end(), quality_out);
-  if (normal_equations_out) std::copy(h_sums, h_sums + (size_t)entries * P, normal_equations_out);
-  return SRMAP_OK;
+  if (int rc = check_mode(p, mode)) return rc;
+  return fit_device(p, x_dev, hip_stream, mode, options, taps_out, quality_out, normal_equations_out);
 }
 
 extern "C" int srmap_fit_blur_bank(srmap_problem* p, const double* x_host, int mode, const srmap_blur_fit_options* options,
                                    double* taps_out, double* quality_out, double* normal_equations_out) {
   if (!p || !x_host) return SRMAP_EINVAL;
-  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
-  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
-    return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
-  if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
-    return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
-  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  if (int rc = stage_host_x(p, x_host)) return rc;
-  return srmap_fit_blur_bank_device(p, p->d_x.as(), p->ctx->stream, mode, options, taps_out, quality_out, normal_equations_out);
+  if (int rc = check_mode(p, mode)) return rc;
+  if (int rc = host_fit_prologue(p, x_host, options, srmap_blur_fit_options_default, kOptionsName)) return rc;
+  return fit_device(p, p->d_x.as(), p->ctx->stream, mode, options, taps_out, quality_out, normal_equations_out);
 }
 
 extern "C" int srmap_fit_blur(srmap_problem* p, const double* x_host, const srmap_blur_fit_options* options,
                               double* taps_out, double* quality_out, double* normal_equations_out) {
   if (!p || !x_host) return SRMAP_EINVAL;
-  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
-  if (options && options->struct_size != (int)sizeof(srmap_blur_fit_options))
-    return set_error(p->ctx, SRMAP_EINVAL, "srmap_blur_fit_options.struct_size is not this library's");
-  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  if (p->blur_bank_mode != 0)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
-  if (int rc = stage_host_x(p, x_host)) return rc;
-  return srmap_fit_blur_device(p, p->d_x.as(), p->ctx->stream, options, taps_out, quality_out, normal_equations_out);
+  if (int rc = host_fit_prologue(p, x_host, options, srmap_blur_fit_options_default, kOptionsName, NoFitCheck(),
+                                 [](srmap_problem* q, const srmap_blur_fit_options&) { return refuse_bank(q); }))
+    return rc;
+  return fit_device(p, p->d_x.as(), p->ctx->stream, 0, options, taps_out, quality_out, normal_equations_out);
 }

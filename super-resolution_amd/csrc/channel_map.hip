@@ -93,7 +93,7 @@ extern "C" int srmap_channel_map_device(srmap_ctx* ctx, int rows_out, int rows_i
   if (!ctx || !M || !in_dev || !out_dev || rows_out <= 0 || rows_in <= 0 || n == 0) return SRMAP_EINVAL;
   if (n > (size_t)0x7fffffff) return set_error(ctx, SRMAP_EUNSUPPORTED, "more than 2^31 pixels per call");
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  hipStream_t st = stream_of(ctx, hip_stream);
   std::vector<double> bias((size_t)rows_out, 0.0);
   for (int r = 0; r < rows_out; ++r) {
     double b = offset_out ? offset_out[r] : 0.0;
@@ -125,7 +125,7 @@ extern "C" int srmap_channel_pca_device(srmap_ctx* ctx, int rows, size_t n, cons
   if (first + (count - 1) * stride >= n) return set_error(ctx, SRMAP_EINVAL, "PCA samples outside the cube");
   if (count > (size_t)0x7fffffff) return set_error(ctx, SRMAP_EUNSUPPORTED, "more than 2^31 samples");
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  hipStream_t st = stream_of(ctx, hip_stream);
   rocblas_handle handle;
   int rc = blas_handle(ctx, st, &handle);
   if (rc) return rc;

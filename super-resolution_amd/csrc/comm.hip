@@ -291,7 +291,7 @@ int srmap_comm_create_host(srmap_ctx* ctx, int rank, int world, srmap_host_allre
 int srmap_comm_allreduce(srmap_comm* c, void* dev_buf, size_t count, int dtype, int op, void* hip_stream) {
   if (!c || !dev_buf) return SRMAP_EINVAL;
   SRMAP_HIP(c->ctx, hipSetDevice(c->ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->ctx->stream;
+  hipStream_t st = stream_of(c->ctx, hip_stream);
   if (c->kind == 1) {
     SRMAP_NCCL(c, c->api->AllReduce(dev_buf, dev_buf, count, dtype == SRMAP_F32 ? ncclFloat32 : ncclFloat64,
                                     op == 1 ? ncclMax : ncclSum, c->nccl, st));

@@ -268,7 +268,7 @@ int srmap_set_data_weights_device(srmap_problem* p, const void* w_dev, void* hip
   if (!p) return SRMAP_EINVAL;
   if (!w_dev) return srmap_set_data_weights(p, nullptr);
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return p->dw.set_user(p, {nullptr, w_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream});
+  return p->dw.set_user(p, {nullptr, w_dev, stream_of(p->ctx, hip_stream)});
 }
 
 int srmap_set_data_prior(srmap_problem* p, const double* m_host) {
@@ -282,7 +282,7 @@ int srmap_set_data_prior_device(srmap_problem* p, const void* m_dev, void* hip_s
   if (!p) return SRMAP_EINVAL;
   if (!m_dev) return srmap_set_data_prior(p, nullptr);
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return p->dw.set_prior(p, {nullptr, m_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream});
+  return p->dw.set_prior(p, {nullptr, m_dev, stream_of(p->ctx, hip_stream)});
 }
 
 // a factor for the caller: ones where there is none
@@ -324,7 +324,7 @@ int srmap_problem_set_data_loss(srmap_problem* p, int loss, double huber_delta) 
 int srmap_update_data_weights_device(srmap_problem* p, const void* x_dev, void* hip_stream) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return p->dw.huber_step(p, 0, 0, x_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+  return p->dw.huber_step(p, 0, 0, x_dev, stream_of(p->ctx, hip_stream));
 }
 
 }  // extern "C"

@@ -203,7 +203,7 @@ int srmap_set_observations(srmap_problem* p, const double* lr_host) {
 
 int srmap_set_observations_device(srmap_problem* p, const void* lr_dev, void* hip_stream) {
   if (!p || !lr_dev) return SRMAP_EINVAL;
-  return set_observations(p, nullptr, lr_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+  return set_observations(p, nullptr, lr_dev, stream_of(p->ctx, hip_stream));
 }
 
 int srmap_set_irls_weights(srmap_problem* p, int reg, const double* w_host) {
@@ -225,7 +225,7 @@ int srmap_update_irls_weights_device(srmap_problem* p, int reg, const void* x_de
   if (!p || reg < 0 || reg >= p->nreg || !x_dev) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   RegSpec& rs = p->reg[reg];
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  hipStream_t st = stream_of(p->ctx, hip_stream);
   int rc = state_begin_write(p, st);
   if (rc) return rc;
   rc = ensure(p, &rs.weights, p->hr_count() * p->elem());
@@ -284,7 +284,7 @@ int srmap_reg_values_and_gradient(srmap_problem* p, int reg, const double* x, co
 int srmap_eval_device(srmap_problem* p, unsigned terms, const void* x_dev, void* g_dev, double* cost,
                       void* hip_stream) {
   if (!p || !x_dev) return SRMAP_EINVAL;
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  hipStream_t st = stream_of(p->ctx, hip_stream);
   EvalOut out;
   int rc = eval_dispatch(p, EvalReq(), &out, terms, x_dev, g_dev, st);
   if (rc) return rc;

@@ -198,7 +198,7 @@ extern "C" int srmap_problem_set_flow(srmap_problem* p, const double* flow_host)
 
 extern "C" int srmap_problem_set_flow_device(srmap_problem* p, const void* flow_dev, void* hip_stream) {
   if (!p) return SRMAP_EINVAL;
-  return flow_set(p, nullptr, flow_dev, hip_stream ? (hipStream_t)hip_stream : p->ctx->stream);
+  return flow_set(p, nullptr, flow_dev, stream_of(p->ctx, hip_stream));
 }
 
 extern "C" int srmap_problem_get_flow(srmap_problem* p, double* flow_out, int* is_set) {

@@ -136,12 +136,11 @@ void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, 
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
   const BlurStride bs = blur_stride(p);
-  if (p->dw.effective<T>())
-    hipLaunchKernelGGL((k_refine_sums<T, true>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), p->dw.effective<T>(), g,
+  const T* dw = p->dw.effective<T>();
+  dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
+    hipLaunchKernelGGL((k_refine_sums<T, decltype(weighted)::value != 0>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), dw, g,
                        p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
-  else
-    hipLaunchKernelGGL((k_refine_sums<T, false>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), (const T*)nullptr, g,
-                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
+  });
 }
 
 }  // namespace
@@ -169,12 +168,7 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   if (p->flow)
     return set_error(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while a displacement field is set (srmap_problem_set_flow)");
   srmap_motion_refinement_options opt;
-  srmap_motion_refinement_options_default(&opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_motion_refinement_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
-    opt = *options;
-  }
+  if (int rc = options_in_force(ctx, options, srmap_motion_refinement_options_default, "srmap_motion_refinement_options", &opt)) return rc;
   if (opt.dof != 2 && opt.dof != 6) return set_error(ctx, SRMAP_EINVAL, "motion refinement: dof must be 2 or 6 (got %d)", opt.dof);
   if (opt.max_iterations < 0 || !(opt.step_tolerance >= 0.0) || !(opt.initial_damping >= 0.0) ||
       !std::isfinite(opt.step_tolerance) || !std::isfinite(opt.initial_damping))
@@ -199,16 +193,15 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
   if (rc) return rc;
 
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  hipStream_t st = stream_of(ctx, hip_stream);
   rc = problem_state_read(p, st);
   if (rc) return rc;
 
-  const int n = g.w * g.h;
-  const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
-  const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
+  const PixelChunks plan = plan_pixel_chunks(g.w * g.h, kMaxChunks);
+  const int ppt = plan.ppt, chunks = plan.chunks;
   FitPass fit;
   auto fail = [&](int code, const char* what) { return set_error(ctx, code, "motion refinement: %s", what); };
-  if (!fit.alloc(K, kSums, (size_t)K * chunks * kSums)) return fail(SRMAP_ENOMEM, "allocation failed");
+  if (!fit.alloc(K, kSums, (size_t)K * chunks * kSums, true)) return fail(SRMAP_ENOMEM, "allocation failed");
 
   std::vector<FrameState> fs(K);
   for (int k = 0; k < K; ++k) {
@@ -301,10 +294,6 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
 extern "C" int srmap_refine_motion(srmap_problem* p, const double* x_host, const srmap_motion_refinement_options* options,
                                    double* affine_2x3_out, double* quality_out, double* normal_equations_out) {
   if (!p || !x_host) return SRMAP_EINVAL;
-  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
-  if (options && options->struct_size != (int)sizeof(srmap_motion_refinement_options))
-    return set_error(p->ctx, SRMAP_EINVAL, "srmap_motion_refinement_options.struct_size is not this library's");
-  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
-  if (int rc = stage_host_x(p, x_host)) return rc;
+  if (int rc = host_fit_prologue(p, x_host, options, srmap_motion_refinement_options_default, "srmap_motion_refinement_options")) return rc;
   return srmap_refine_motion_device(p, p->d_x.as(), p->ctx->stream, options, affine_2x3_out, quality_out, normal_equations_out);
 }

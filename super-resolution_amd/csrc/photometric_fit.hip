@@ -10,13 +10,12 @@
 //             identity without motion), the blur in force; six f64 sums per
 //             workgroup {w, w s, w y, w s^2, w s y, w y^2} held in registers in both dtypes, folded by a wave shuffle and
 //             LDS in a fixed order, no atomics (fold_sums_256); k_fit_reduce adds the chunk records in index order;
-//   pacing    one launch, one reduce, one copy of K x 6 doubles, one stream wait (FitPass, motion_fit.hip);
+//   pacing    one launch, one reduce, one copy of K x 6 doubles, one stream wait (FitPass without a table, motion_fit.hip);
 //   solve     on the host in double, per frame: the 2 x 2 (or 1 x 1) system of photometric_host.hpp.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "affine_map.hpp"
 #include "motion_fit_dev.hpp"
 #include "photometric_host.hpp"
 #include "sample_dev.hpp"
@@ -100,14 +99,13 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
   const T* y = (p->d_obs_raw ? p->d_obs_raw : p->d_obs).as<const T>();  // always the RAW frames: the fit is absolute
   const MotionArgs<T> ma = motion_args<T>(p);
   const BlurStride bs = blur_stride(p);
+  const T* dw = p->dw.effective<T>();
   return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
-    if (p->dw.effective<T>())
-      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, true>), grid, dim3(256), 0, st, x, y, p->dw.effective<T>(), g, ma,
+    dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
+      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, decltype(weighted)::value != 0>), grid, dim3(256), 0, st, x, y, dw, g, ma,
                          p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
-    else
-      hipLaunchKernelGGL((k_photometric_sums<T, MOTION, false>), grid, dim3(256), 0, st, x, y, (const T*)nullptr, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
+    });
   });
 }
 
@@ -195,23 +193,15 @@ extern "C" void srmap_photometric_fit_options_default(srmap_photometric_fit_opti
   o->apply = 1;
 }
 
-// the checks of the options that need no device; opt receives the options in force
-static int photometric_fit_options(srmap_problem* p, const srmap_photometric_fit_options* options,
-                                   srmap_photometric_fit_options* opt) {
+// the checks of the options' values (they need no device)
+static int photometric_option_values(srmap_problem* p, const srmap_photometric_fit_options& opt) {
   srmap_ctx* ctx = p->ctx;
-  srmap_photometric_fit_options_default(opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_photometric_fit_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_photometric_fit_options.struct_size is not this library's");
-    *opt = *options;
-  }
-  if (opt->model < kPhotoGainBias || opt->model > kPhotoBiasOnly)
-    return set_error(ctx, SRMAP_EINVAL, "photometric fit: model must be 0, 1 or 2 (got %d)", opt->model);
-  if (opt->gauge_frame < -1 || opt->gauge_frame >= p->geo.K)
-    return set_error(ctx, SRMAP_EINVAL, "photometric fit: gauge_frame %d is no frame of the problem (and not -1)", opt->gauge_frame);
-  if (!std::isfinite(opt->min_gain) || !std::isfinite(opt->max_gain) || !(opt->min_gain > 0.0) || !(opt->max_gain >= opt->min_gain))
+  if (opt.model < kPhotoGainBias || opt.model > kPhotoBiasOnly)
+    return set_error(ctx, SRMAP_EINVAL, "photometric fit: model must be 0, 1 or 2 (got %d)", opt.model);
+  if (opt.gauge_frame < -1 || opt.gauge_frame >= p->geo.K)
+    return set_error(ctx, SRMAP_EINVAL, "photometric fit: gauge_frame %d is no frame of the problem (and not -1)", opt.gauge_frame);
+  if (!std::isfinite(opt.min_gain) || !std::isfinite(opt.max_gain) || !(opt.min_gain > 0.0) || !(opt.max_gain >= opt.min_gain))
     return set_error(ctx, SRMAP_EINVAL, "photometric fit: the gain bounds must be finite with 0 < min_gain <= max_gain");
-  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
   return SRMAP_OK;
 }
 
@@ -223,24 +213,22 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
   if (p->flow)
     return set_error(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
   srmap_photometric_fit_options opt;
-  int rc = photometric_fit_options(p, options, &opt);
+  int rc = options_in_force(ctx, options, srmap_photometric_fit_options_default, "srmap_photometric_fit_options", &opt);
+  if (!rc) rc = photometric_option_values(p, opt);
   if (rc) return rc;
+  if (!p->have_obs) return set_error(ctx, SRMAP_EINVAL, "no observations set");
   const Geometry& g = p->geo;
   const int K = g.K;
 
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  hipStream_t st = stream_of(ctx, hip_stream);
   rc = problem_state_read(p, st);
   if (rc) return rc;
 
-  const int n = g.w * g.h;
-  const int ppt = std::max(1, (n + 256 * kMaxChunks - 1) / (256 * kMaxChunks));
-  const int chunks = (n + 256 * ppt - 1) / (256 * ppt);
-  FitPass fit;
-  if (!fit.alloc(K, kPhotoSums, (size_t)K * chunks * kPhotoSums)) return set_error(ctx, SRMAP_ENOMEM, "photometric fit: allocation failed");
-  const AffineMap identity = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};  // the table carries the active flags alone here
-  for (int k = 0; k < K; ++k) fit.set(k, identity, true);
-  if (!fit.upload(st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: upload failed");
+  const PixelChunks plan = plan_pixel_chunks(g.w * g.h, kMaxChunks);
+  const int ppt = plan.ppt, chunks = plan.chunks;
+  FitPass fit;  // no table: every frame is fitted in the one pass
+  if (!fit.alloc(K, kPhotoSums, (size_t)K * chunks * kPhotoSums, false)) return set_error(ctx, SRMAP_ENOMEM, "photometric fit: allocation failed");
   if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, (const decltype(t)*)x_dev, chunks, ppt, fit.d_part.as<double>(), st); }))
     return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)motion_kind(p));
   if (!fit.reduce_and_fetch(chunks, st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: pass failed");
@@ -273,11 +261,8 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
 extern "C" int srmap_fit_photometric(srmap_problem* p, const double* x_host, const srmap_photometric_fit_options* options,
                                      double* gain_bias_out, double* quality_out, double* sums_out) {
   if (!p || !x_host) return SRMAP_EINVAL;
-  // the checks that need no device come first: an error leaves the problem (its staging buffer included) untouched
-  srmap_photometric_fit_options opt;
-  int rc = photometric_fit_options(p, options, &opt);
-  if (rc) return rc;
-  rc = stage_host_x(p, x_host);
-  if (rc) return rc;
+  if (int rc = host_fit_prologue(p, x_host, options, srmap_photometric_fit_options_default, "srmap_photometric_fit_options",
+                                 photometric_option_values))
+    return rc;
   return srmap_fit_photometric_device(p, p->d_x.as(), p->ctx->stream, options, gain_bias_out, quality_out, sums_out);
 }

@@ -26,7 +26,6 @@ namespace srmap {
 namespace {
 
 constexpr int kGnSums = 26;       // 18 of H, 6 of g, sum e^2, pixel count
-constexpr int kMaxLevels = 12;
 constexpr int kMaxRowChunks = 128;
 constexpr int kMaxSeedChunks = 8;
 
@@ -142,12 +141,7 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
                                      double* quality_out) {
   if (!ctx || !affine_2x3_out || num_images < 0) return SRMAP_EINVAL;
   srmap_affine_registration_options opt;
-  srmap_affine_registration_options_default(&opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_affine_registration_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_affine_registration_options.struct_size is not this library's");
-    opt = *options;
-  }
+  if (int rc = options_in_force(ctx, options, srmap_affine_registration_options_default, "srmap_affine_registration_options", &opt)) return rc;
   if (opt.hr_scale < 1 || opt.max_iterations < 1 || opt.max_levels < 0 || !(opt.step_tolerance >= 0.0))
     return set_error(ctx, SRMAP_EINVAL, "affine registration: bad options");
   if (num_images == 0) return SRMAP_OK;
@@ -171,12 +165,8 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
 
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  std::vector<int> lw{width}, lh{height};
-  while (std::min(lw.back(), lh.back()) >= 64 && (int)lw.size() < kMaxLevels &&
-         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
-    lw.push_back(lw.back() / 2);
-    lh.push_back(lh.back() / 2);
-  }
+  std::vector<int> lw, lh;
+  pyramid_levels(width, height, 64, opt.max_levels, &lw, &lh);
   const int L = (int)lw.size();
   std::vector<size_t> off(L + 1, 0);
   for (int l = 0; l < L; ++l) off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
@@ -190,7 +180,7 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   DevBuf pyr;
   FitPass fit;  // its d_part also takes the seed search's partials
   auto fail = [&](int code, const char* what) { return set_error(ctx, code, "affine registration: %s", what); };
-  if (pyr.alloc(off[L] * sizeof(double)) != hipSuccess || !fit.alloc(nf, kGnSums, part_elems)) return fail(SRMAP_ENOMEM, "allocation failed");
+  if (pyr.alloc(off[L] * sizeof(double)) != hipSuccess || !fit.alloc(nf, kGnSums, part_elems, true)) return fail(SRMAP_ENOMEM, "allocation failed");
   double* const d_pyr = pyr.as<double>();
 
   // ---- pyramids of the whole stack, once ----

@@ -31,7 +31,6 @@ namespace srmap {
 
 namespace {
 
-constexpr int kMaxLevels = 12;
 constexpr int kMinSize = 16;
 constexpr int kMaxWindowRadius = 8;
 constexpr int kMaxSmoothRadius = 8;
@@ -347,12 +346,7 @@ struct FlowIo {
 };
 
 int check_options(srmap_ctx* ctx, const srmap_flow_registration_options* options, srmap_flow_registration_options* opt) {
-  srmap_flow_registration_options_default(opt);
-  if (options) {
-    if (options->struct_size != (int)sizeof(srmap_flow_registration_options))
-      return set_error(ctx, SRMAP_EINVAL, "srmap_flow_registration_options.struct_size is not this library's");
-    *opt = *options;
-  }
+  if (int rc = options_in_force(ctx, options, srmap_flow_registration_options_default, "srmap_flow_registration_options", opt)) return rc;
   if (opt->hr_scale < 1 || opt->warps < 1 || opt->window_radius < 1 || opt->window_radius > kMaxWindowRadius ||
       !(opt->damping >= 0.0) || !std::isfinite(opt->damping) || opt->smooth_radius < 0 || opt->smooth_radius > kMaxSmoothRadius ||
       opt->valid_margin < 0 || opt->max_levels < 0)
@@ -375,12 +369,8 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
       if (!std::isfinite(io.images_host[i]))
         return set_error(ctx, SRMAP_EINVAL, "flow registration: image %d is not finite", (int)(i / n));
 
-  std::vector<int> lw{width}, lh{height};
-  while (std::min(lw.back(), lh.back()) >= 2 * kMinSize && (int)lw.size() < kMaxLevels &&
-         (opt.max_levels == 0 || (int)lw.size() < opt.max_levels)) {
-    lw.push_back(lw.back() / 2);
-    lh.push_back(lh.back() / 2);
-  }
+  std::vector<int> lw, lh;
+  pyramid_levels(width, height, 2 * kMinSize, opt.max_levels, &lw, &lh);
   const int L = (int)lw.size();
 
   std::vector<double> h_tab;
@@ -582,7 +572,7 @@ extern "C" int srmap_register_flow_device(srmap_ctx* ctx, int num_images, int wi
   io.flow_dev = flow_dev_out;
   io.valid_dev = valid_dev_out;
   FlowBuffers b;
-  return register_flow_body(ctx, num_images, width, height, opt, io, b, hip_stream ? (hipStream_t)hip_stream : ctx->stream, quality_out);
+  return register_flow_body(ctx, num_images, width, height, opt, io, b, stream_of(ctx, hip_stream), quality_out);
 }
 
 extern "C" int srmap_problem_register_flow(srmap_problem* p, int channel, const srmap_flow_registration_options* options,

@@ -213,7 +213,7 @@ int srmap_eval_sharded_device(srmap_problem* p, srmap_comm* comm, const srmap_sh
                               void* x_dev, void* g_dev, double* cost, void* hip_stream) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->ctx->stream;
+  hipStream_t st = stream_of(p->ctx, hip_stream);
   const int mode = shard_mode(comm, shard);
   if (int rc = refuse_sharded(p, mode, "evaluate")) return rc;
   EvalOut out;

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -235,6 +236,23 @@ void blas_release(srmap_ctx* ctx);
                                 hipGetErrorString(e_), __FILE__, __LINE__);      \
   } while (0)
 
+// the stream of an entry point that takes one: the caller's hip_stream, or the context's when that is NULL
+inline hipStream_t stream_of(const srmap_ctx* ctx, void* hip_stream) {
+  return hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+}
+
+// The options in force of an entry point that takes an options struct O (`name`, for the message): the library's defaults
+// (set_default, the struct's srmap_*_options_default), or the caller's when given -- refused when their struct_size is not
+// this library's
+template <typename O>
+int options_in_force(srmap_ctx* ctx, const O* options, void (*set_default)(O*), const char* name, O* opt) {
+  set_default(opt);
+  if (!options) return SRMAP_OK;
+  if (options->struct_size != (int)sizeof(O)) return set_error(ctx, SRMAP_EINVAL, "%s.struct_size is not this library's", name);
+  *opt = *options;
+  return SRMAP_OK;
+}
+
 // f(T()) with T the element type of `dtype`, float or double; what f returns.  The one switch from the run-time dtype to
 // the template instances: f is a generic lambda that names T as decltype of its argument
 template <typename F>
@@ -301,27 +319,43 @@ void dispatch_scale(int s, F&& f) {
 }
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (problem.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
-// ---- the motion fits' shared kernels and per-pass buffers (motion_fit.hip) ----
+// ---- the fits' shared kernels, planning and per-pass buffers (motion_fit.hip) ----
 struct AffineMap;  // affine_map.hpp
 // dst[k][h/2][w/2] = mean of the 2 x 2 blocks of src[k][h][w], k < frames: one level of a box pyramid
 void launch_down2_stack(const double* src, double* dst, int w, int h, int frames, hipStream_t st);
-// One pass of a fit over every frame (registration_affine.hip, motion_refinement.hip): the caller's sums kernel reads the
-// frame table d_tab[frame][kFitTabRec] = {six matrix entries, active flag, pad}, returns at once for a frame whose flag is
-// 0 and writes one record of nsums doubles per workgroup to d_part[(frame * chunks + chunk)][nsums].  Per pass: set()
-// every frame, upload(), the sums kernel, reduce_and_fetch() -- one table upload, one copy of frames x nsums doubles and
-// one stream wait; then sums(frame) holds the chunk records added in index order (unchanged for an inactive frame).
+// the level sizes of that pyramid, finest first: halved while the shorter side is >= min_side, max_levels at most (0: no
+// limit but the pyramid's own)
+void pyramid_levels(int width, int height, int min_side, int max_levels, std::vector<int>* lw, std::vector<int>* lh);
+// A pass with a thread per LR pixel (every channel of it) over the n pixels of a frame: grid (chunks, frames), 256 threads,
+// a workgroup covers 256 * ppt pixels; ppt grows so that max_chunks chunks suffice
+struct PixelChunks { int ppt, chunks; };
+inline PixelChunks plan_pixel_chunks(int n, int max_chunks) {
+  const int ppt = std::max(1, (n + 256 * max_chunks - 1) / (256 * max_chunks));
+  return {ppt, (n + 256 * ppt - 1) / (256 * ppt)};
+}
+// One pass of a fit, and the owner of its buffers.  The fit's sums kernel writes one record of nsums doubles per workgroup
+// to d_part; reduce_and_fetch() adds the records of every ROW -- a frame, an entry of a blur bank, or the one row of a fit
+// over everything -- in index order (k_fit_reduce), copies rows x nsums doubles and waits for the stream once; then
+// sums(row) holds the row's sums.  With a table (the fits of matrices: registration_affine.hip, motion_refinement.hip) the
+// sums kernel also reads d_tab[row][kFitTabRec] = {six matrix entries, active flag, pad} and returns at once for a row
+// whose flag is 0, and such a row keeps the sums of its last active pass; per pass: set() every row, upload(), the sums
+// kernel, reduce_and_fetch().  Without one (photometric_fit.hip, blur_fit.hip) nothing is uploaded and every row counts.
 constexpr int kFitTabRec = 8;
 struct FitPass {
-  int frames = 0, nsums = 0;
-  DevBuf d_part, d_tab, d_sums;  // doubles
+  int rows = 0, nsums = 0;
+  DevBuf d_part, d_tab, d_sums;  // doubles; d_tab empty without a table
   PinnedBuf h_tab, h_sums;       // doubles
-  // part_elems: doubles of d_part (>= frames * chunks * nsums; a caller may ask for more and share it).  false: an
+  // part_elems: doubles of d_part (every record of a pass; a caller may ask for more and share it).  false: an
   // allocation failed
-  bool alloc(int frames_, int nsums_, size_t part_elems);
-  void set(int frame, const AffineMap& M, bool active);
+  bool alloc(int rows_, int nsums_, size_t part_elems, bool table);
+  void set(int row, const AffineMap& M, bool active);
   bool upload(hipStream_t st);
-  bool reduce_and_fetch(int chunks, hipStream_t st);  // also reports a failed launch of the caller's sums kernel
-  const double* sums(int frame) const { return h_sums.as<const double>() + (size_t)frame * nsums; }
+  // Row e adds `outer` groups of `inner` consecutive records, the groups outer_stride records apart, from record
+  // e * row_stride on.  Also reports a failed launch of the caller's sums kernel
+  bool reduce_and_fetch(int row_stride, int outer, int outer_stride, int inner, hipStream_t st);
+  // the records [row][chunk] of a sums kernel with grid (chunks, rows)
+  bool reduce_and_fetch(int chunks, hipStream_t st) { return reduce_and_fetch(chunks, 1, 0, chunks, st); }
+  const double* sums(int row) const { return h_sums.as<const double>() + (size_t)row * nsums; }
 };
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
@@ -442,5 +476,23 @@ int convert_download(srmap_problem* p, const void* dev, double* host, size_t n,
 // The HR image of a host-buffer fit entry point into p->d_x (allocated on first use), enqueued on the context's stream.
 // The caller has made every check that needs no device: an error there leaves the problem, this buffer included, untouched
 int stage_host_x(srmap_problem* p, const double* x_host);
+// The prologue of the host form of a fit that takes the HR image (blur_fit.hip, photometric_fit.hip,
+// motion_refinement.hip).  The checks that need no device come first, so that an error leaves the problem (its staging
+// buffer included) untouched: the options' struct_size, before_obs(p, opt) (opt: the options in force), observations
+// present, after_obs(p, opt); then stage_host_x.  The caller goes on to the device form with p->d_x on the context's stream
+struct NoFitCheck {
+  template <typename O>
+  int operator()(srmap_problem*, const O&) const { return SRMAP_OK; }
+};
+template <typename O, typename BeforeObs = NoFitCheck, typename AfterObs = NoFitCheck>
+int host_fit_prologue(srmap_problem* p, const double* x_host, const O* options, void (*set_default)(O*), const char* name,
+                      BeforeObs before_obs = BeforeObs(), AfterObs after_obs = AfterObs()) {
+  O opt;
+  if (int rc = options_in_force(p->ctx, options, set_default, name, &opt)) return rc;
+  if (int rc = before_obs(p, opt)) return rc;
+  if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "no observations set");
+  if (int rc = after_obs(p, opt)) return rc;
+  return stage_host_x(p, x_host);
+}
 
 }  // namespace srmap

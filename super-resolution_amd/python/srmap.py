@@ -473,28 +473,37 @@ class Problem:
         self.ctx.check(load().srmap_problem_get_blur_kernel(self._h, C.byref(k), out.ctypes.data_as(c_double_p)))
         return out
 
+    def _fit(self, name, x, stream, *tail):
+        """The fit entry point `name` on the HR image x: its host form for a host array [C][H][W], its _device form on `stream`
+        for a device tensor (anything with data_ptr())."""
+        if hasattr(x, "data_ptr"):
+            assert x.numel() == self.C * self.H * self.W
+            self.ctx.check(getattr(load(), name + "_device")(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
+        else:
+            a, pa = _d(x)
+            assert a.size == self.C * self.H * self.W
+            self.ctx.check(getattr(load(), name)(self._h, pa, *tail))
+
+    @staticmethod
+    def _blur_fit_options(ksize, sum_to_one, ridge, apply, struct_size):
+        o = BlurFitOptions()
+        load().srmap_blur_fit_options_default(C.byref(o))
+        o.ksize, o.sum_to_one, o.ridge, o.apply = (0 if ksize is None else ksize), (1 if sum_to_one else 0), ridge, (1 if apply else 0)
+        if struct_size is not None:
+            o.struct_size = struct_size
+        return o
+
     def fit_blur(self, x, ksize=None, sum_to_one=True, ridge=0.0, apply=True, stream=None, struct_size=None):
         """srmap_fit_blur: the ksize x ksize taps that best explain the observations from the KNOWN HR image x (a host array
         [C][H][W], or a device tensor of the problem's dtype, read on `stream`).  ksize None = the size of the kernel in
         force.  Returns (taps [ksize][ksize], quality [5] = E at the kernel in force, E at the fit, smallest / largest pivot,
         status, sums = the upper triangle of the Gram of [s_0 ... s_{n-1}, y]).  apply installs the fit as set_blur_kernel
         would.  struct_size overrides the options' size field (tests)."""
-        o = BlurFitOptions()
-        load().srmap_blur_fit_options_default(C.byref(o))
-        o.ksize, o.sum_to_one, o.ridge, o.apply = (0 if ksize is None else ksize), (1 if sum_to_one else 0), ridge, (1 if apply else 0)
-        if struct_size is not None:
-            o.struct_size = struct_size
+        o = self._blur_fit_options(ksize, sum_to_one, ridge, apply, struct_size)
         kk = ksize if ksize else self.blur_kernel().shape[0]
         n = max(kk, 1) ** 2
         taps, q, ne = np.zeros(n), np.zeros(5), np.zeros((n + 1) * (n + 2) // 2)
-        tail = (C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
-        if hasattr(x, "data_ptr"):
-            assert x.numel() == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_blur_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
-        else:
-            a, pa = _d(x)
-            assert a.size == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_blur(self._h, pa, *tail))
+        self._fit("srmap_fit_blur", x, stream, C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
         k = int(round(np.sqrt(n)))
         return taps.reshape(k, k), q, ne
 
@@ -540,25 +549,14 @@ class Problem:
         (taps [entries...][ksize][ksize], quality [entries][5] in fit_blur's layout -- status 0 fitted, 3 degenerate: the
         entry keeps its kernel --, sums [entries][(n + 1)(n + 2) / 2]).  apply installs the result as set_blur_bank would.
         A calibration fit: blind alternation with a solve is not offered."""
-        o = BlurFitOptions()
-        load().srmap_blur_fit_options_default(C.byref(o))
-        o.ksize, o.sum_to_one, o.ridge, o.apply = (0 if ksize is None else ksize), (1 if sum_to_one else 0), ridge, (1 if apply else 0)
-        if struct_size is not None:
-            o.struct_size = struct_size
+        o = self._blur_fit_options(ksize, sum_to_one, ridge, apply, struct_size)
         kc = C.c_int(0)
         self.ctx.check(load().srmap_problem_get_blur_kernel(self._h, C.byref(kc), None))
         kk = ksize if ksize else kc.value
         n = max(kk, 1) ** 2
         entries = self._bank_entries(mode) if mode in (BLUR_PER_FRAME, BLUR_PER_CHANNEL, BLUR_PER_FRAME_CHANNEL) else 1
         taps, q, ne = np.zeros((entries, n)), np.zeros((entries, 5)), np.zeros((entries, (n + 1) * (n + 2) // 2))
-        tail = (mode, C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
-        if hasattr(x, "data_ptr"):
-            assert x.numel() == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_blur_bank_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
-        else:
-            a, pa = _d(x)
-            assert a.size == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_blur_bank(self._h, pa, *tail))
+        self._fit("srmap_fit_blur_bank", x, stream, mode, C.byref(o), taps.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
         k = int(round(np.sqrt(n)))
         lead = (self.K, self.C) if mode == BLUR_PER_FRAME_CHANNEL else (entries,)
         return taps.reshape(lead + (k, k)), q, ne
@@ -751,14 +749,7 @@ class Problem:
             assert ini.size == self.K * 6, (ini.shape, self.K)
             o.initial_affine_2x3 = pi
         out, q, ne = np.zeros((self.K, 2, 3)), np.zeros((self.K, 4)), np.zeros((self.K, 28))
-        tail = (C.byref(o), out.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
-        if hasattr(x, "data_ptr"):
-            assert x.numel() == self.C * self.H * self.W
-            self.ctx.check(load().srmap_refine_motion_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
-        else:
-            a, pa = _d(x)
-            assert a.size == self.C * self.H * self.W
-            self.ctx.check(load().srmap_refine_motion(self._h, pa, *tail))
+        self._fit("srmap_refine_motion", x, stream, C.byref(o), out.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), ne.ctypes.data_as(c_double_p))
         return out, q, ne
 
     def solve_joint(self, x0, options=None, rounds=3, **refine):
@@ -801,14 +792,7 @@ class Problem:
         if struct_size is not None:
             o.struct_size = struct_size
         gb, q, sums = np.zeros((self.K, 2)), np.zeros((self.K, 4)), np.zeros((self.K, 6))
-        tail = (C.byref(o), gb.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), sums.ctypes.data_as(c_double_p))
-        if hasattr(x, "data_ptr"):
-            assert x.numel() == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_photometric_device(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(stream or 0), *tail))
-        else:
-            a, pa = _d(x)
-            assert a.size == self.C * self.H * self.W
-            self.ctx.check(load().srmap_fit_photometric(self._h, pa, *tail))
+        self._fit("srmap_fit_photometric", x, stream, C.byref(o), gb.ctypes.data_as(c_double_p), q.ctypes.data_as(c_double_p), sums.ctypes.data_as(c_double_p))
         return gb, q, sums
 
     def solve_photometric(self, x0, options=None, rounds=3, **fit):

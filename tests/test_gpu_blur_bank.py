@@ -1,6 +1,6 @@
 """The blur-kernel bank and its per-entry calibration fit on the GPU (include/srmap.h: srmap_problem_set_blur_bank,
 srmap_problem_get_blur_bank, srmap_fit_blur_bank; the bank legs of k_forward_direct, k_gather_direct, k_gather_sampled,
-k_refine_sums, k_photometric_sums and the per-channel grid of k_blur_fit_sums / k_blur_fit_reduce_bank) against the numpy
+k_refine_sums, k_photometric_sums and the per-channel grid of k_blur_fit_sums, k_fit_reduce) against the numpy
 restatement (tests/blur_bank_restatement.py), against the single free-form kernel and against itself.
 
 Bars.  Evaluations: the project's per-element bars, 1e-12 (f64) and 2e-5 (f32), every comparison through parity_log.  Fit
@@ -434,6 +434,7 @@ FIT_CASES = [
     ((17, 23), 2, 5, "shifts", "random", 2, 3),
     ((17, 23), 3, 1, "shifts", None, 5, 1),
     ((37, 29), 2, 3, "affine", "random", 2, 3),  # 9 tiles per channel: five chunks, the last of one tile
+    ((17, 23), 2, 7, "shifts", "random", 2, 3),  # 1275 sums: five blocks of the reduce, each over two chunks per channel
 ]
 
 

@@ -1,5 +1,5 @@
 """The free-form blur kernel and its calibration fit on the GPU (include/srmap.h: srmap_problem_set_blur_kernel,
-srmap_fit_blur; k_blur_fit_sums / k_blur_fit_reduce of csrc/blur_fit.hip) against the numpy restatement
+srmap_fit_blur; k_blur_fit_sums of csrc/blur_fit.hip, k_fit_reduce of csrc/motion_fit.hip) against the numpy restatement
 (tests/blur_kernel_restatement.py), against an existing kernel (the data cost of srmap_eval) and against itself.
 
 Bars.  Evaluations: the project's per-element bars, 1e-12 (f64) and 2e-5 (f32), every comparison through parity_log.  Fit

@@ -4,7 +4,7 @@ next to the forward kernel on the same problem.
 At bench.py's cfg2 geometry (2048 x 2048, scale 4) and at 1024 x 1024 (scale 2), 8 frames, f64 and f32, with sub-pixel
 shifts (k_forward_direct's table kind) and with affine matrices (its affine kind), blur 3 / sigma 1, one process.  Host wall
 clock around the blocking call on a device tensor (min of 5, after a warm-up at sustained clocks):
-  one fit      the whole call with apply = 0: its allocations, the table upload, ONE launch of k_photometric_sums, the
+  one fit      the whole call with apply = 0: its allocations, ONE launch of k_photometric_sums, the
                reduce, the copy of K x 6 doubles, the stream wait and the host solve;
   normalise    the whole srmap_problem_set_photometric call on a problem that already holds parameters: the drain, the
                copy of K x 2 doubles, ONE launch of k_photometric_normalise and the stream wait;
