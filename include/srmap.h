@@ -442,7 +442,17 @@ int srmap_channel_pca_device(srmap_ctx* ctx, int rows, size_t n, const double* i
  * not the reference's OpenCV feature pipeline).  images_host: num_images planes [height][width] (the reference
  * registers on channel 0, registration.cpp:41-46).  shifts_xy_out: 2 * num_images doubles, image 0 -> (0, 0).
  * num_images == 0 returns SRMAP_OK and writes nothing (registration.cpp:165-168).  SRMAP_EINVAL when no shift
- * can be determined (the reference CHECK-fails, registration.cpp:193-194). */
+ * can be determined (the reference CHECK-fails, registration.cpp:193-194): width or height < 8, and a pixel of any
+ * image that is not finite ("registration: image %d is not finite"; nothing is written), and a refinement step that
+ * is not finite (finite pixels whose products overflow; the images before that one are answered).
+ *   pyramid   2 x 2 box means (an odd last row / column is dropped); a level is added while min(w, h) > 64 -- 64 x 64 is
+ *             one level, 65 x 65 is two (the other fits halve while min(w, h) >= 64) --, at most 12 levels;
+ *   search    R0 = max(4, min(16, min side of the coarsest level / 4)) around 0 there, +-1 around twice the coarser answer
+ *             on every finer level; mean squared difference over the overlap; the FIRST minimum in row-major candidate
+ *             order wins, so a textureless pair, where every candidate ties, answers (-R0, -R0) 2^(levels - 1) with
+ *             separation 0 and is not an error;
+ *   refine    at most 20 Gauss-Newton passes over the pixels ceil(max(|dx|, |dy|)) + 2 from every edge, none when fewer than
+ *             4 rows or columns remain (the integer shift stands); clamped to the integer shift +-1. */
 int srmap_register_translational(srmap_ctx* ctx, int num_images, int width, int height,
                                  const double* images_host, double* shifts_xy_out);
 /* What this estimator is NOT: the reference finds features (BRISK), fits a RANSAC homography / rigid transform and
@@ -452,7 +462,8 @@ int srmap_register_translational(srmap_ctx* ctx, int num_images, int width, int 
  * rotation / scale between frames bias the result.  The _ex form reports how trustworthy each shift is --
  * quality_out (optional, 2 doubles per image): [2i] separation = 1 - best / runner-up mean squared difference of
  * the coarsest search (runner-up at least 2 coarse pixels away; near 1 = one clear minimum, near 0 = ambiguous),
- * [2i + 1] the root mean squared residual at the returned shift.  Callers with real (non-synthetic) stacks
+ * [2i + 1] the root mean squared residual at the returned shift (of the last refinement pass evaluated), -1 when the
+ * frame is too small for a refinement pass at the integer shift.  Callers with real (non-synthetic) stacks
  * should check both, or supply shifts from their own registration (MotionShiftSequence accepts any). */
 int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, int width, int height,
                                     const double* images_host, double* shifts_xy_out, double* quality_out);
@@ -479,7 +490,8 @@ int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, int width, i
  * defines it (1 when an initial matrix was given), [4i+1] root mean squared residual I_k(F(p)) - I_0(p) at the result
  * (full resolution), [4i+2] the fraction n / (w h) of pixels that pass used, [4i+3] Gauss-Newton passes over all levels.
  * Image 0: (1, 0, 1, 0).
- * num_images == 0 returns SRMAP_OK and writes nothing.  SRMAP_EINVAL: width or height < 8; a struct_size that is not this
+ * num_images == 0 returns SRMAP_OK and writes nothing.  SRMAP_EINVAL: width or height < 8; a pixel of any image that is not
+ * finite ("affine registration: image %d is not finite"; nothing is written); a struct_size that is not this
  * library's; hr_scale < 1, max_iterations < 1, max_levels < 0 or a negative step_tolerance; an initial matrix (rows
  * 1...num_images-1; row 0 is ignored) that is not finite or outside the domain; and "Could not determine motion between
  * images." when a pass has fewer than 0.25 w h usable pixels or an iterate leaves the domain.  A level without texture

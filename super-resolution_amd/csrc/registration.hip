@@ -102,9 +102,12 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
   if (!ctx || !shifts_xy_out || num_images < 0) return SRMAP_EINVAL;
   if (num_images == 0) return SRMAP_OK;  // registration.cpp:165-168: empty sequence
   if (!images_host || width < 8 || height < 8) return set_error(ctx, SRMAP_EINVAL, "registration needs images of at least 8 x 8");
+  const size_t npx = (size_t)width * height;
+  // a NaN mean squared difference compares false with everything: the search would answer its first candidate at every level
+  for (size_t i = 0; i < (size_t)num_images * npx; ++i)
+    if (!std::isfinite(images_host[i])) return set_error(ctx, SRMAP_EINVAL, "registration: image %d is not finite", (int)(i / npx));
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t npx = (size_t)width * height;
   shifts_xy_out[0] = 0.0; shifts_xy_out[1] = 0.0;  // registration.cpp:170-172
   if (quality_out) { quality_out[0] = 1.0; quality_out[1] = 0.0; }
   if (num_images == 1) return SRMAP_OK;
@@ -158,7 +161,10 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
         msd[cnd] = m;
         if (bi < 0 || m < best) { best = m; bi = cnd; }
       }
-      if (bi < 0) return fail(SRMAP_EINVAL, "Could not determine motion shift between images.");  // registration.cpp:193-194
+      // registration.cpp:193-194.  No input reaches this: the count does not depend on the pixel values, the coarsest level's
+      // centre candidate overlaps fully, and a finer level's centre is at most R0 2^k + 2^k - 1 pixels out on a side of at
+      // least 2^k times the coarsest one (>= 32 there, R0 <= a quarter of it): it keeps (1 - 1/4 - 1/32)^2 > 0.25 of the frame.
+      if (bi < 0) return fail(SRMAP_EINVAL, "Could not determine motion shift between images.");
       if (l == L - 1 && quality_out) quality_out[2 * i] = search_separation(msd.data(), n1, bi);
       sx = sx - R + bi % n1;
       sy = sy - R + bi / n1;
@@ -179,8 +185,11 @@ extern "C" int srmap_register_translational_ex(srmap_ctx* ctx, int num_images, i
       const double det = S[0] * S[2] - S[1] * S[1];
       if (!(det > 1e-12 * (S[0] * S[2] + 1e-300))) break;  // no texture: integer estimate stands
       const double ux = -(S[2] * S[3] - S[1] * S[4]) / det, uy = -(S[0] * S[4] - S[1] * S[3]) / det;
+      // finite pixels whose products overflow: a NaN step passes through min / max into dx, and the next pass would take its
+      // margin and its sample offsets from (int)NaN
+      if (!std::isfinite(ux) || !std::isfinite(uy)) return fail(SRMAP_EINVAL, "Could not determine motion shift between images.");
       // stay within the pixel the search found
-      dx = std::min(std::max(dx + ux, sx - 1.0), sx + 1.0);
+      dx =std::min(std::max(dx + ux, sx - 1.0), sx + 1.0);
       dy = std::min(std::max(dy + uy, sy - 1.0), sy + 1.0);
       if (std::fabs(ux) < 1e-5 && std::fabs(uy) < 1e-5) break;
     }

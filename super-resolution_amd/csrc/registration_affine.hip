@@ -147,6 +147,9 @@ extern "C" int srmap_register_affine(srmap_ctx* ctx, int num_images, int width, 
   if (num_images == 0) return SRMAP_OK;
   if (!images_host || width < 8 || height < 8)
     return set_error(ctx, SRMAP_EINVAL, "registration needs images of at least 8 x 8");
+  // a NaN sum fails every comparison: the seed would keep candidate 0 and the Cholesky refusal would keep the matrix
+  for (size_t i = 0, n = (size_t)width * height; i < (size_t)num_images * n; ++i)
+    if (!std::isfinite(images_host[i])) return set_error(ctx, SRMAP_EINVAL, "affine registration: image %d is not finite", (int)(i / n));
   const int K = num_images, nf = K - 1;
   const double ident[6] = {1, 0, 0, 0, 1, 0};
   std::copy(ident, ident + 6, affine_2x3_out);

@@ -173,6 +173,18 @@ def search_radius(w, h):
     return max(4, min(16, min(w, h) // 4))
 
 
+def search_separation(msd, bi):
+    """1 - best / runner-up of a square candidate table (row-major; a negative entry: not evaluated), the runner-up being
+    the smallest entry at least 2 cells (Chebyshev) from the best one `bi`; 0 without a positive runner-up."""
+    msd = np.asarray(msd, dtype=np.float64)
+    n1 = msd.shape[0]
+    by, bx = divmod(int(bi), n1)
+    yy, xx = np.mgrid[0:n1, 0:n1]
+    far = (np.maximum(np.abs(xx - bx), np.abs(yy - by)) >= 2) & (msd >= 0)
+    runner = np.min(msd[far]) if np.any(far) else -1.0
+    return float(1.0 - msd[by, bx] / runner) if runner > 0 else 0.0
+
+
 def coarse_seed(ref, img):
     """((ux, uy), separation): exhaustive search over the fixed central window.  An empty window answers (0, 0), 0."""
     h, w = ref.shape
@@ -188,11 +200,7 @@ def coarse_seed(ref, img):
             msd[iy, ix] = np.sum(d * d) / t.size
     bi = int(np.argmin(msd))  # first minimum, row-major
     by, bx = divmod(bi, n1)
-    yy, xx = np.mgrid[0:n1, 0:n1]
-    far = np.maximum(np.abs(xx - bx), np.abs(yy - by)) >= 2
-    runner = np.min(msd[far])
-    sep = 1.0 - msd[by, bx] / runner if runner > 0 else 0.0
-    return (bx - R, by - R), float(sep)
+    return (bx - R, by - R), search_separation(msd, bi)
 
 
 def register_pair(ref_img, img, init=None, max_iterations=30, step_tolerance=1e-4, max_levels=0):
@@ -246,6 +254,9 @@ def register_affine(images, hr_scale=1, init=None, max_iterations=30, step_toler
         return (out, q) if with_quality else out
     if images.shape[1] < 8 or images.shape[2] < 8:
         raise RegistrationError("registration needs images of at least 8 x 8")
+    for k in range(n):
+        if not np.all(np.isfinite(images[k])):
+            raise RegistrationError("affine registration: image %d is not finite" % k)
     out[0], q[0] = identity(), [1.0, 0.0, 1.0, 0.0]
     for k in range(1, n):
         F, qk, _ = register_pair(images[0], images[k], None if init is None else np.asarray(init).reshape(n, 2, 3)[k],

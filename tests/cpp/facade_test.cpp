@@ -420,6 +420,55 @@ static void TestRegistration() {
   EXPECT(registration::TranslationalRegistration({}).GetNumMotionShifts() == 0);
 }
 
+// TranslationalRegistrationWithQuality and TranslationalRegistration return what srmap_register_translational_ex returns,
+// bit for bit, at a size and with the shifts of the parity table (tests/registration_restatement.py: 33 x 47, under one
+// wave wide, one level; the integer, the largest and the sub-pixel shifts).
+static void TestRegistrationWithQuality() {
+  const int W = 47, H = 33;
+  std::vector<double> px(static_cast<size_t>(W) * H);
+  std::mt19937_64 rng(33047);
+  std::uniform_real_distribution<double> uni(0.0, 1.0);
+  std::vector<double> coarse(14 * 11);
+  for (auto& v : coarse) v = uni(rng);
+  for (int r = 0; r < H; ++r)
+    for (int c = 0; c < W; ++c) {
+      const double u = c / 4.0, v = r / 4.0;  // bilinear blow-up of a random 14 x 11 grid + two sinusoids
+      const int u0 = (int)u, v0 = (int)v;
+      const double a = u - u0, b = v - v0;
+      const double g = (1 - b) * ((1 - a) * coarse[v0 * 14 + u0] + a * coarse[v0 * 14 + u0 + 1]) +
+                       b * ((1 - a) * coarse[(v0 + 1) * 14 + u0] + a * coarse[(v0 + 1) * 14 + u0 + 1]);
+      px[static_cast<size_t>(r) * W + c] = 0.6 * g + 0.2 + 0.1 * std::sin(0.21 * c) * std::cos(0.17 * r);
+    }
+  const ImageData original(px.data(), cv::Size(W, H));
+  const std::vector<MotionShift> truth{MotionShift(0, 0),      MotionShift(1, 0),       MotionShift(0, -1),         MotionShift(2, -1),
+                                       MotionShift(8, -8),     MotionShift(0.5, -0.25), MotionShift(-1.75, 1.5),    MotionShift(-3.125, 0.875),
+                                       MotionShift(1.25, 0.75)};
+  const MotionShiftSequence truth_seq(truth);
+  const MotionModule motion(truth_seq);
+  std::vector<ImageData> frames;
+  std::vector<double> stack;
+  for (size_t i = 0; i < truth.size(); ++i) {
+    ImageData im = original;
+    motion.ApplyToImage(&im, static_cast<int>(i));
+    frames.push_back(im);
+    stack.insert(stack.end(), im.GetChannelData(0), im.GetChannelData(0) + px.size());
+  }
+  const int n = static_cast<int>(truth.size());
+  std::vector<double> xy(2 * n, 7.0), q(2 * n, 7.0), quality;
+  EXPECT(srmap_register_translational_ex(srmap_host::Context(), n, W, H, stack.data(), xy.data(), q.data()) == SRMAP_OK);
+  const MotionShiftSequence got = registration::TranslationalRegistrationWithQuality(frames, &quality);
+  const MotionShiftSequence plain = registration::TranslationalRegistration(frames);
+  EXPECT(got.GetNumMotionShifts() == n && plain.GetNumMotionShifts() == n);
+  EXPECT(quality == q);
+  for (int i = 0; i < n; ++i) {
+    EXPECT(got[i].dx == xy[2 * i] && got[i].dy == xy[2 * i + 1]);
+    EXPECT(plain[i].dx == xy[2 * i] && plain[i].dy == xy[2 * i + 1]);
+    if (i >= 1 && i <= 4)  // integer shifts: the reference's tolerance
+      EXPECT(std::fabs(xy[2 * i] - truth[i].dx) <= 0.01 && std::fabs(xy[2 * i + 1] - truth[i].dy) <= 0.01);
+  }
+  EXPECT(q[0] == 1.0 && q[1] == 0.0);
+}
+
 // A caller-defined operator, as the reference's own tests define them (test/test_image_model.cpp:31-46 subclass
 // DegradationOperator): it overrides the reference's two members only.  A model that contains it is not a canonical
 // chain, so ImageModel applies its operators one by one, in insertion order / reverse order for the transpose
@@ -471,6 +520,7 @@ int main() {
   TestSsimAndNoise();
   TestSpectralPca();
   TestRegistration();
+  TestRegistrationWithQuality();
   std::printf(g_fail ? "FACADE TESTS FAILED (%d)\n" : "FACADE TESTS PASSED\n", g_fail);
   return g_fail ? 1 : 0;
 }
