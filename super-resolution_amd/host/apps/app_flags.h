@@ -1,6 +1,7 @@
 // Minimal gflags-style command line for the host tools: --name=value, --name value,
 // --flag / --noflag for booleans (the reference uses gflags, src/util/util.cpp InitApp).
 #pragma once
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -38,6 +39,19 @@ class Flags {
   std::map<std::string, std::string> values_;
   std::map<std::string, bool> seen_;
 };
+
+// A refused command line: "ERROR: <message>" on stderr, and the exit code 1 to return --  return Refuse("...", ...);
+inline int Refuse(const char* format, ...) {
+  std::va_list args;
+  va_start(args, format);
+  std::fprintf(stderr, "ERROR: ");
+  std::vfprintf(stderr, format, args);
+  std::fprintf(stderr, "\n");
+  va_end(args);
+  return 1;
+}
+inline int RefuseBoth(const char* flag, const char* other) { return Refuse("%s and %s exclude each other.", flag, other); }
+inline int CannotWrite(const std::string& path) { return Refuse("cannot write '%s'.", path.c_str()); }
 
 }  // namespace app
 }  // namespace super_resolution

@@ -8,7 +8,7 @@
 #include <random>
 #include <string>
 
-#include "apps/app_flags.h"
+#include "apps/model_flags.h"
 #include "image/image_io.h"
 #include "image_model/image_model.h"
 #include "image_model/photometric.h"
@@ -38,33 +38,20 @@ int main(int argc, char** argv) {
   const std::string output_dir = flags.Str("output_image_dir");
   std::string extension = flags.Str("output_image_extension");
   const std::string save_as = flags.Str("save_as");
-  ImageModelParameters parameters;
-  parameters.motion_sequence_path = flags.Str("motion_sequence_path");
-  parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");  // not a reference flag
-  const std::string flow_motion_path = flags.Str("flow_motion_path");  // not a reference flag
-  parameters.blur_kernel_path = flags.Str("blur_kernel_path");  // not a reference flag
-  parameters.blur_bank_path = flags.Str("blur_bank_path");  // not a reference flag
+  const app::ModelFlags model = app::ReadModelFlags(&flags, 0, 0.0);
+  ImageModelParameters parameters = model.parameters;
+  const std::string& flow_motion_path = model.flow_motion_path;
   const std::string photometric_path = flags.Str("photometric_path");  // not a reference flag
-  parameters.blur_radius = flags.Int("blur_radius", 0);
-  parameters.blur_sigma = flags.Double("blur_sigma", 0.0);
   parameters.noise_sigma = flags.Double("noise_sigma", 0.0);  // 0..255 units (additive_noise_module.cpp:25-26)
   parameters.noise_seed = static_cast<uint64_t>(flags.Int("noise_seed", 1));
   parameters.scale = flags.Int("downsampling_scale", 2);
   const int number_of_frames = flags.Int("number_of_frames", 4);
   flags.RejectUnknown();
   flags.Require("input_image");
-  if (!parameters.blur_bank_path.empty() && !parameters.blur_kernel_path.empty()) {
-    std::fprintf(stderr, "ERROR: --blur_bank_path and --blur_kernel_path exclude each other.\n");
-    return 1;
-  }
-  if (!parameters.affine_motion_sequence_path.empty() && !parameters.motion_sequence_path.empty()) {
-    std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
-    return 1;
-  }
-  if (!flow_motion_path.empty() && (!parameters.affine_motion_sequence_path.empty() || !parameters.motion_sequence_path.empty())) {
-    std::fprintf(stderr, "ERROR: --flow_motion_path excludes --motion_sequence_path and --affine_motion_path.\n");
-    return 1;
-  }
+  if (!parameters.blur_bank_path.empty() && !parameters.blur_kernel_path.empty()) return app::RefuseBoth("--blur_bank_path", "--blur_kernel_path");
+  if (app::RefuseBothMotionFiles(model)) return 1;
+  if (!flow_motion_path.empty() && (!parameters.affine_motion_sequence_path.empty() || !parameters.motion_sequence_path.empty()))
+    return app::Refuse("--flow_motion_path excludes --motion_sequence_path and --affine_motion_path.");
 
   const ImageData image_data = util::LoadImage(input_image);
   if (!save_as.empty()) {  // copy / convert only (generate_data.cpp:94-98)
@@ -78,20 +65,16 @@ int main(int argc, char** argv) {
   std::unique_ptr<AdditiveNoiseModule> noise_after;
   if (!photometric_path.empty()) {
     photometric.LoadSequenceFromFile(photometric_path);
-    if (photometric.GetNumFrames() < number_of_frames) {
-      std::fprintf(stderr, "ERROR: --photometric_path holds %d frames, --number_of_frames asks for %d.\n", photometric.GetNumFrames(), number_of_frames);
-      return 1;
-    }
+    if (photometric.GetNumFrames() < number_of_frames)
+      return app::Refuse("--photometric_path holds %d frames, --number_of_frames asks for %d.", photometric.GetNumFrames(), number_of_frames);
     if (parameters.noise_sigma > 0.0) noise_after.reset(new AdditiveNoiseModule(parameters.noise_sigma, parameters.noise_seed));
     parameters.noise_sigma = 0.0;
   }
   if (!flow_motion_path.empty()) {
     parameters.flow_motion_sequence.LoadSequenceFromFile(flow_motion_path, image_data.GetImageSize().width, image_data.GetImageSize().height);
-    if (parameters.flow_motion_sequence.GetNumMotions() < number_of_frames) {
-      std::fprintf(stderr, "ERROR: --flow_motion_path holds %d frames, --number_of_frames asks for %d.\n",
-                   parameters.flow_motion_sequence.GetNumMotions(), number_of_frames);
-      return 1;
-    }
+    if (parameters.flow_motion_sequence.GetNumMotions() < number_of_frames)
+      return app::Refuse("--flow_motion_path holds %d frames, --number_of_frames asks for %d.",
+                         parameters.flow_motion_sequence.GetNumMotions(), number_of_frames);
   }
   const ImageModel image_model = ImageModel::CreateImageModel(parameters);
   if (!extension.empty() && extension[0] != '.') extension = "." + extension;

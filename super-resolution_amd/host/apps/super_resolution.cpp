@@ -18,6 +18,7 @@
 // srmap_fit_photometric).
 // Not carried over (out of scope, DESIGN.md
 // section 7): wavelet-domain solve, numerical differentiation, SSIM, display.
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -27,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "apps/app_flags.h"
+#include "apps/model_flags.h"
 #include "evaluation/peak_signal_to_noise_ratio.h"
 #include "evaluation/structural_similarity.h"
 #include "hyperspectral/spectral_pca.h"
@@ -39,8 +40,9 @@
 
 using namespace super_resolution;
 
-int main(int argc, char** argv) {
-  app::Flags flags(argc, argv,
+namespace {
+
+const char kUsage[] =
       "super_resolution --data_path=<dir of LR frames | HR image with --generate_lr_images>\n"
       "  [--generate_lr_images] [--noise_sigma=0] [--noise_seed=1] [--number_of_frames=4]\n"
       "  [--ground_truth_image=<path>] [--upsampling_scale=2] [--blur_radius=3] [--blur_sigma=1]\n"
@@ -92,439 +94,433 @@ int main(int argc, char** argv) {
       "                       together with --photometric_path)\n"
       "                       [--save_photometric_path=<file>] (the parameters in force after the solve, in\n"
       "                       --photometric_path's format; needs one of the two flags above)\n"
-      "                       [--noise_seed=1] [--save_initial_estimate=<path>]");
-  const std::string data_path = flags.Str("data_path");
-  const bool generate_lr_images = flags.Bool("generate_lr_images", false);
-  const double noise_sigma = flags.Double("noise_sigma", 0.0);
-  const int noise_seed = flags.Int("noise_seed", 1);
-  const int number_of_frames = flags.Int("number_of_frames", 4);
-  const std::string ground_truth_image = flags.Str("ground_truth_image");
-  const int upsampling_scale = flags.Int("upsampling_scale", 2);
-  ImageModelParameters model_parameters;
-  model_parameters.scale = upsampling_scale;
-  model_parameters.blur_radius = flags.Int("blur_radius", 3);
-  model_parameters.blur_sigma = flags.Double("blur_sigma", 1.0);
-  model_parameters.motion_sequence_path = flags.Str("motion_sequence_path");
-  // not a reference flag: the affine motion model of include/srmap.h (srmap_problem_set_affine_motion)
-  model_parameters.affine_motion_sequence_path = flags.Str("affine_motion_path");
-  // not a reference flag: the displacement-field motion model of include/srmap.h (srmap_problem_set_flow)
-  const std::string flow_motion_path = flags.Str("flow_motion_path");
-  IRLSMapSolverOptions solver_options;
-  solver_options.max_num_irls_iterations = flags.Int("optimization_iterations", 20);
-  solver_options.max_num_solver_iterations = flags.Int("solver_iterations", 50);
-  solver_options.split_channels = flags.Bool("split_channels", false);
-  std::string regularizer_name = flags.Str("regularizer", "tv");
-  const int btv_scale_range = flags.Int("btv_scale_range", 3);
-  const double btv_spatial_decay = flags.Double("btv_spatial_decay", 0.5);
-  const double regularization_parameter = flags.Double("regularization_parameter", 0.01);
-  const std::string solver_name = flags.Str("solver", "cg");
+      "                       [--noise_seed=1] [--save_initial_estimate=<path>]";
+
+// The parsed command line; ParseFlags states the defaults.
+struct Options {
+  std::string data_path, ground_truth_image;
+  bool generate_lr_images;
+  double noise_sigma;
+  int noise_seed, number_of_frames, upsampling_scale;
+  // the model flags; --affine_motion_path and --flow_motion_path (srmap_problem_set_affine_motion, srmap_problem_set_flow) and
+  // the free-form blur flags (srmap_problem_set_blur_kernel, srmap_problem_set_blur_bank) are not reference flags
+  app::ModelFlags model;
+  IRLSMapSolverOptions solver;
+  std::string regularizer, solver_name;
+  int btv_scale_range;
+  double btv_spatial_decay, regularization_parameter;
   // not reference flags: the loss of the data term (the reference's is plain least squares) and the Huber threshold in the
   // solver's pixel units (ImageData scales 8-bit input to 0..1)
-  const std::string data_loss_name = flags.Str("data_loss", "l2");
-  const double huber_delta = flags.Double("huber_delta", 0.02);
-  const bool interpolate_color = flags.Bool("interpolate_color", false);
-  const bool solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
-  const int num_pca_components = flags.Int("num_pca_components", 0);
-  const double pca_retained_variance = flags.Double("pca_retained_variance", 0.0);
-  const std::string evaluators = flags.Str("evaluators");
-  const std::string result_path = flags.Str("result_path");
+  std::string data_loss;
+  double huber_delta;
+  bool interpolate_color, solve_in_pca_space;
+  int num_pca_components;
+  double pca_retained_variance;
+  std::string evaluators, result_path;
   // not a reference flag: the solver's start x0 as raw little-endian float64 [C][H][W], so that a CPU run of the
   // reference algorithm can start from the IDENTICAL estimate (tests/test_gpu_apps.py compares the two results)
-  const std::string save_initial_estimate = flags.Str("save_initial_estimate");
+  std::string save_initial_estimate;
   // not reference flags: estimate the solver's motion from the LR frames (srmap_register_translational /
-  // srmap_register_affine) instead of reading it from a file, and write the estimate out
-  const std::string registration_name = flags.Str("registration");
-  const std::string save_motion_path = flags.Str("save_motion_path");
-  const std::string save_flow_path = flags.Str("save_flow_path");
+  // srmap_register_affine / srmap_register_flow) instead of reading it from a file, and write the estimate out
+  std::string registration, save_motion_path, save_flow_path;
   // not a reference flag: the validity masks as the persistent prior of srmap_set_data_prior (they hold under Huber too)
-  const bool flow_valid_prior = flags.Bool("flow_valid_prior", false);
+  bool flow_valid_prior;
   // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
-  const int refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
-  const int refine_motion_dof = flags.Int("refine_motion_dof", 6);
-  // not reference flags: a free-form blur kernel (srmap_problem_set_blur_kernel) and its calibration fit (srmap_fit_blur)
-  model_parameters.blur_kernel_path = flags.Str("blur_kernel_path");
-  const std::string fit_blur_from = flags.Str("fit_blur_from");
-  const int fit_blur_ksize = flags.Int("fit_blur_ksize", 0);
-  const std::string save_blur_kernel_path = flags.Str("save_blur_kernel_path");
-  // not reference flags: a blur-kernel bank (srmap_problem_set_blur_bank) and its calibration fit (srmap_fit_blur_bank)
-  model_parameters.blur_bank_path = flags.Str("blur_bank_path");
-  const std::string fit_blur_bank_from = flags.Str("fit_blur_bank_from");
-  const std::string fit_blur_bank_mode = flags.Str("fit_blur_bank_mode");
-  const std::string save_blur_bank_path = flags.Str("save_blur_bank_path");
+  int refine_motion_rounds, refine_motion_dof;
+  // not reference flags: the calibration fits of the blur kernel (srmap_fit_blur) and of a bank (srmap_fit_blur_bank)
+  std::string fit_blur_from, save_blur_kernel_path, fit_blur_bank_from, fit_blur_bank_mode, save_blur_bank_path;
+  int fit_blur_ksize;
   // not reference flags: the photometric frame model (srmap_problem_set_photometric) and its fit (srmap_fit_photometric)
-  const std::string photometric_path = flags.Str("photometric_path");
-  const int photometric_rounds = flags.Int("photometric_rounds", -1);
-  const std::string save_photometric_path = flags.Str("save_photometric_path");
-  const bool verbose = flags.Bool("verbose", false);
+  std::string photometric_path, save_photometric_path;
+  int photometric_rounds;
+  bool verbose;
+
+  bool RegisterFlow() const { return registration == "flow"; }
+  int FitBankMode() const {
+    return fit_blur_bank_mode == "frame" ? 1 : fit_blur_bank_mode == "channel" ? 2 : fit_blur_bank_mode == "frame_channel" ? 3 : 0;
+  }
+};
+
+// The images of a run, as the steps of main() hand them on.
+struct Frames {
+  ImageData high_res_image;  // the ground truth, if there is one
+  std::vector<ImageData> low_res_images;
+  ImageData upsampled_image;   // bilinear upsampling of frame 0 in the original spectral space: the evaluation baseline
+  ImageData initial_estimate;  // the same in the space the solve runs in
+  std::unique_ptr<SpectralPCA> spectral_pca;
+  std::vector<double> flow_valid;  // --registration=flow: the validity masks, [frames][h][w] at LR resolution
+};
+
+Options ParseFlags(int argc, char** argv) {
+  app::Flags flags(argc, argv, kUsage);
+  Options o{};
+  o.data_path = flags.Str("data_path");
+  o.generate_lr_images = flags.Bool("generate_lr_images", false);
+  o.noise_sigma = flags.Double("noise_sigma", 0.0);
+  o.noise_seed = flags.Int("noise_seed", 1);
+  o.number_of_frames = flags.Int("number_of_frames", 4);
+  o.ground_truth_image = flags.Str("ground_truth_image");
+  o.upsampling_scale = flags.Int("upsampling_scale", 2);
+  o.model = app::ReadModelFlags(&flags, 3, 1.0);
+  o.model.parameters.scale = o.upsampling_scale;
+  o.solver.max_num_irls_iterations = flags.Int("optimization_iterations", 20);
+  o.solver.max_num_solver_iterations = flags.Int("solver_iterations", 50);
+  o.solver.split_channels = flags.Bool("split_channels", false);
+  o.regularizer = flags.Str("regularizer", "tv");
+  o.btv_scale_range = flags.Int("btv_scale_range", 3);
+  o.btv_spatial_decay = flags.Double("btv_spatial_decay", 0.5);
+  o.regularization_parameter = flags.Double("regularization_parameter", 0.01);
+  o.solver_name = flags.Str("solver", "cg");
+  o.data_loss = flags.Str("data_loss", "l2");
+  o.huber_delta = flags.Double("huber_delta", 0.02);
+  o.interpolate_color = flags.Bool("interpolate_color", false);
+  o.solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
+  o.num_pca_components = flags.Int("num_pca_components", 0);
+  o.pca_retained_variance = flags.Double("pca_retained_variance", 0.0);
+  o.evaluators = flags.Str("evaluators");
+  o.result_path = flags.Str("result_path");
+  o.save_initial_estimate = flags.Str("save_initial_estimate");
+  o.registration = flags.Str("registration");
+  o.save_motion_path = flags.Str("save_motion_path");
+  o.save_flow_path = flags.Str("save_flow_path");
+  o.flow_valid_prior = flags.Bool("flow_valid_prior", false);
+  o.refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
+  o.refine_motion_dof = flags.Int("refine_motion_dof", 6);
+  o.fit_blur_from = flags.Str("fit_blur_from");
+  o.fit_blur_ksize = flags.Int("fit_blur_ksize", 0);
+  o.save_blur_kernel_path = flags.Str("save_blur_kernel_path");
+  o.fit_blur_bank_from = flags.Str("fit_blur_bank_from");
+  o.fit_blur_bank_mode = flags.Str("fit_blur_bank_mode");
+  o.save_blur_bank_path = flags.Str("save_blur_bank_path");
+  o.photometric_path = flags.Str("photometric_path");
+  o.photometric_rounds = flags.Int("photometric_rounds", -1);
+  o.save_photometric_path = flags.Str("save_photometric_path");
+  o.verbose = flags.Bool("verbose", false);
   flags.RejectUnknown();
   flags.Require("data_path");
-  if (!model_parameters.affine_motion_sequence_path.empty() && !model_parameters.motion_sequence_path.empty()) {
-    std::fprintf(stderr, "ERROR: --affine_motion_path and --motion_sequence_path exclude each other.\n");
-    return 1;
-  }
-  if (!flow_motion_path.empty()) {
-    // the field IS the motion: nothing else may give or estimate one, and the three fits have no sampling leg for a field
-    const char* other = !model_parameters.motion_sequence_path.empty() ? "--motion_sequence_path"
-                        : !model_parameters.affine_motion_sequence_path.empty() ? "--affine_motion_path"
-                        : !registration_name.empty() ? "--registration"
-                        : refine_motion_rounds != 0 ? "--refine_motion_rounds"
-                        : !fit_blur_from.empty() ? "--fit_blur_from"
-                        : photometric_rounds >= 0 ? "--photometric_rounds" : nullptr;
-    if (other) {
-      std::fprintf(stderr, "ERROR: --flow_motion_path and %s exclude each other.\n", other);
-      return 1;
-    }
-  }
-  if (!registration_name.empty() && registration_name != "translational" && registration_name != "affine" &&
-      registration_name != "flow") {
-    std::fprintf(stderr, "ERROR: --registration is 'translational' or 'affine', or 'flow'.\n");
-    return 1;
-  }
-  const bool register_flow = registration_name == "flow";
-  if (register_flow) {
-    // the estimated field IS the motion, as --flow_motion_path's: the same flags are refused (--registration itself aside)
-    const char* other = !model_parameters.motion_sequence_path.empty() ? "--motion_sequence_path"
-                        : !model_parameters.affine_motion_sequence_path.empty() ? "--affine_motion_path"
-                        : refine_motion_rounds != 0 ? "--refine_motion_rounds"
-                        : !fit_blur_from.empty() ? "--fit_blur_from"
-                        : photometric_rounds >= 0 ? "--photometric_rounds" : nullptr;
-    if (other) {
-      std::fprintf(stderr, "ERROR: --registration=flow and %s exclude each other.\n", other);
-      return 1;
-    }
-    if (!save_motion_path.empty()) {
-      std::fprintf(stderr, "ERROR: --save_motion_path holds matrices; the fields of --registration=flow go to --save_flow_path.\n");
-      return 1;
-    }
-  }
-  if (!save_flow_path.empty() && !register_flow) {
-    std::fprintf(stderr, "ERROR: --save_flow_path needs --registration=flow.\n");
-    return 1;
-  }
-  if (flow_valid_prior && !register_flow) {
-    std::fprintf(stderr, "ERROR: --flow_valid_prior needs --registration=flow.\n");
-    return 1;
-  }
-  if (!registration_name.empty() && !generate_lr_images &&
-      (!model_parameters.affine_motion_sequence_path.empty() || !model_parameters.motion_sequence_path.empty())) {
-    std::fprintf(stderr, "ERROR: --registration estimates the motion; it excludes --motion_sequence_path and --affine_motion_path "
-                         "(except with --generate_lr_images, where the files generate the frames).\n");
-    return 1;
-  }
-  if (refine_motion_rounds < 0 || (refine_motion_dof != 2 && refine_motion_dof != 6)) {
-    std::fprintf(stderr, "ERROR: --refine_motion_rounds is >= 0 and --refine_motion_dof is 2 or 6.\n");
-    return 1;
-  }
-  if (!save_motion_path.empty() && registration_name.empty() && refine_motion_rounds == 0) {
-    std::fprintf(stderr, "ERROR: --save_motion_path needs --registration or --refine_motion_rounds.\n");
-    return 1;
-  }
-  if (fit_blur_ksize < 0 || (fit_blur_ksize != 0 && fit_blur_ksize % 2 != 1) || fit_blur_ksize > 7) {
-    std::fprintf(stderr, "ERROR: --fit_blur_ksize is 0 or an odd size up to 7.\n");
-    return 1;
-  }
-  if ((fit_blur_from.empty() && !save_blur_kernel_path.empty()) || (fit_blur_from.empty() && fit_blur_bank_from.empty() && fit_blur_ksize != 0)) {
-    std::fprintf(stderr, "ERROR: --save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from (--fit_blur_ksize also goes with --fit_blur_bank_from).\n");
-    return 1;
-  }
-  {
-    // the bank and the single kernel are alternatives, and so are their fits
-    const bool bank_flag = !model_parameters.blur_bank_path.empty() || !fit_blur_bank_from.empty();
-    const char* other = !model_parameters.blur_kernel_path.empty() ? "--blur_kernel_path" : !fit_blur_from.empty() ? "--fit_blur_from" : nullptr;
-    if (bank_flag && other) {
-      std::fprintf(stderr, "ERROR: %s and %s exclude each other.\n", !model_parameters.blur_bank_path.empty() ? "--blur_bank_path" : "--fit_blur_bank_from", other);
-      return 1;
-    }
-  }
-  if (fit_blur_bank_from.empty() && (!fit_blur_bank_mode.empty() || !save_blur_bank_path.empty())) {
-    std::fprintf(stderr, "ERROR: --fit_blur_bank_mode and --save_blur_bank_path need --fit_blur_bank_from.\n");
-    return 1;
-  }
-  const int fit_bank_mode = fit_blur_bank_mode == "frame" ? 1 : fit_blur_bank_mode == "channel" ? 2 : fit_blur_bank_mode == "frame_channel" ? 3 : 0;
-  if (!fit_blur_bank_from.empty() && fit_bank_mode == 0) {
-    std::fprintf(stderr, "ERROR: --fit_blur_bank_from needs --fit_blur_bank_mode=frame|channel|frame_channel.\n");
-    return 1;
-  }
-  if (!fit_blur_bank_from.empty() && (!flow_motion_path.empty() || registration_name == "flow")) {
-    std::fprintf(stderr, "ERROR: --fit_blur_bank_from has no sampling leg for a displacement field: not with --flow_motion_path or --registration=flow.\n");
-    return 1;
-  }
-  if (photometric_rounds < -1) {
-    std::fprintf(stderr, "ERROR: --photometric_rounds is >= 0 (or -1: off).\n");
-    return 1;
-  }
-  if (!photometric_path.empty() && photometric_rounds >= 0) {
-    std::fprintf(stderr, "ERROR: --photometric_path gives the parameters, --photometric_rounds fits them: they exclude each other.\n");
-    return 1;
-  }
-  if (!save_photometric_path.empty() && photometric_path.empty() && photometric_rounds < 0) {
-    std::fprintf(stderr, "ERROR: --save_photometric_path needs --photometric_path or --photometric_rounds.\n");
-    return 1;
-  }
-  // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
-  if (solver_name == "lbfgs") {
-    solver_options.least_squares_solver = LBFGS_SOLVER;
-  } else if (solver_name != "cg") {
-    std::fprintf(stderr, "WARNING: Invalid solver flag. Using conjugate gradient solver.\n");
-  }
+  return o;
+}
 
+// A displacement field IS the motion, whether --flow_motion_path reads it or --registration=flow estimates it: nothing else
+// may give or estimate one, and the three fits have no sampling leg for a field.  The first such flag given, or nullptr.
+const char* FlagExcludedByFlow(const Options& o, const bool registration_too) {
+  const struct { const char* name; bool given; } excluded[] = {
+      {"--motion_sequence_path", !o.model.parameters.motion_sequence_path.empty()},
+      {"--affine_motion_path", !o.model.parameters.affine_motion_sequence_path.empty()},
+      {"--registration", registration_too && !o.registration.empty()},
+      {"--refine_motion_rounds", o.refine_motion_rounds != 0},
+      {"--fit_blur_from", !o.fit_blur_from.empty()},
+      {"--photometric_rounds", o.photometric_rounds >= 0}};
+  for (const auto& flag : excluded)
+    if (flag.given) return flag.name;
+  return nullptr;
+}
+
+// The flag combinations that are refused before anything is loaded, in the order in which they win.
+int CheckFlags(const Options& o) {
+  using app::Refuse;
+  const ImageModelParameters& model = o.model.parameters;
+  const bool motion_file = !model.affine_motion_sequence_path.empty() || !model.motion_sequence_path.empty();
+  if (app::RefuseBothMotionFiles(o.model)) return 1;
+  if (!o.model.flow_motion_path.empty())
+    if (const char* other = FlagExcludedByFlow(o, true)) return app::RefuseBoth("--flow_motion_path", other);
+  if (!o.registration.empty() && o.registration != "translational" && o.registration != "affine" && !o.RegisterFlow())
+    return Refuse("--registration is 'translational' or 'affine', or 'flow'.");
+  if (o.RegisterFlow()) {
+    if (const char* other = FlagExcludedByFlow(o, false)) return app::RefuseBoth("--registration=flow", other);
+    if (!o.save_motion_path.empty())
+      return Refuse("--save_motion_path holds matrices; the fields of --registration=flow go to --save_flow_path.");
+  }
+  if (!o.save_flow_path.empty() && !o.RegisterFlow()) return Refuse("--save_flow_path needs --registration=flow.");
+  if (o.flow_valid_prior && !o.RegisterFlow()) return Refuse("--flow_valid_prior needs --registration=flow.");
+  if (!o.registration.empty() && !o.generate_lr_images && motion_file)
+    return Refuse("--registration estimates the motion; it excludes --motion_sequence_path and --affine_motion_path "
+                  "(except with --generate_lr_images, where the files generate the frames).");
+  if (o.refine_motion_rounds < 0 || (o.refine_motion_dof != 2 && o.refine_motion_dof != 6))
+    return Refuse("--refine_motion_rounds is >= 0 and --refine_motion_dof is 2 or 6.");
+  if (!o.save_motion_path.empty() && o.registration.empty() && o.refine_motion_rounds == 0)
+    return Refuse("--save_motion_path needs --registration or --refine_motion_rounds.");
+  if (o.fit_blur_ksize < 0 || (o.fit_blur_ksize != 0 && o.fit_blur_ksize % 2 != 1) || o.fit_blur_ksize > 7)
+    return Refuse("--fit_blur_ksize is 0 or an odd size up to 7.");
+  if ((o.fit_blur_from.empty() && !o.save_blur_kernel_path.empty()) ||
+      (o.fit_blur_from.empty() && o.fit_blur_bank_from.empty() && o.fit_blur_ksize != 0))
+    return Refuse("--save_blur_kernel_path and --fit_blur_ksize need --fit_blur_from (--fit_blur_ksize also goes with --fit_blur_bank_from).");
+  // the bank and the single kernel are alternatives, and so are their fits
+  const char* bank_flag = !model.blur_bank_path.empty() ? "--blur_bank_path" : !o.fit_blur_bank_from.empty() ? "--fit_blur_bank_from" : nullptr;
+  const char* kernel_flag = !model.blur_kernel_path.empty() ? "--blur_kernel_path" : !o.fit_blur_from.empty() ? "--fit_blur_from" : nullptr;
+  if (bank_flag && kernel_flag) return app::RefuseBoth(bank_flag, kernel_flag);
+  if (o.fit_blur_bank_from.empty() && (!o.fit_blur_bank_mode.empty() || !o.save_blur_bank_path.empty()))
+    return Refuse("--fit_blur_bank_mode and --save_blur_bank_path need --fit_blur_bank_from.");
+  if (!o.fit_blur_bank_from.empty() && o.FitBankMode() == 0)
+    return Refuse("--fit_blur_bank_from needs --fit_blur_bank_mode=frame|channel|frame_channel.");
+  if (!o.fit_blur_bank_from.empty() && (!o.model.flow_motion_path.empty() || o.RegisterFlow()))
+    return Refuse("--fit_blur_bank_from has no sampling leg for a displacement field: not with --flow_motion_path or --registration=flow.");
+  if (o.photometric_rounds < -1) return Refuse("--photometric_rounds is >= 0 (or -1: off).");
+  if (!o.photometric_path.empty() && o.photometric_rounds >= 0)
+    return Refuse("--photometric_path gives the parameters, --photometric_rounds fits them: they exclude each other.");
+  if (!o.save_photometric_path.empty() && o.photometric_path.empty() && o.photometric_rounds < 0)
+    return Refuse("--save_photometric_path needs --photometric_path or --photometric_rounds.");
+  return 0;
+}
+
+// --solver and --data_loss: a name that is not known warns and runs the default
+void ChooseSolverAndLoss(Options* o) {
+  // super_resolution.cpp:134-141: "lbfgs" selects L-BFGS, anything but "cg" warns and falls back to CG
+  if (o->solver_name == "lbfgs") o->solver.least_squares_solver = LBFGS_SOLVER;
+  else if (o->solver_name != "cg") std::fprintf(stderr, "WARNING: Invalid solver flag. Using conjugate gradient solver.\n");
   // as --solver: "huber" selects the Huber loss, anything but "l2" warns and runs least squares
-  if (data_loss_name == "huber") {
-    solver_options.data_loss = HUBER_DATA_LOSS;
-    solver_options.huber_delta = huber_delta;
-  } else if (data_loss_name != "l2") {
+  if (o->data_loss == "huber") {
+    o->solver.data_loss = HUBER_DATA_LOSS;
+    o->solver.huber_delta = o->huber_delta;
+  } else if (o->data_loss != "l2") {
     std::fprintf(stderr, "WARNING: Invalid data_loss flag. Using the least-squares (l2) data term.\n");
   }
+}
 
-  ImageData high_res_image;
-  std::vector<ImageData> low_res_images;
-  if (generate_lr_images) high_res_image = util::LoadImage(data_path);
-  else low_res_images = util::LoadImages(data_path);
-  if (!flow_motion_path.empty()) {  // the file has no header: its size is checked against the HR geometry
-    if (!generate_lr_images && low_res_images.empty()) {
-      std::fprintf(stderr, "Check failed: At least one low-resolution image is required for super-resolution.\n");
-      return 1;
-    }
-    const cv::Size hr = generate_lr_images ? high_res_image.GetImageSize()
-                                           : cv::Size(low_res_images[0].GetImageSize().width * upsampling_scale,
-                                                      low_res_images[0].GetImageSize().height * upsampling_scale);
-    model_parameters.flow_motion_sequence.LoadSequenceFromFile(flow_motion_path, hr.width, hr.height);
-  }
-  const ImageModel image_model = ImageModel::CreateImageModel(model_parameters);
+int NoLowResImages() {
+  std::fprintf(stderr, "Check failed: At least one low-resolution image is required for super-resolution.\n");
+  return 1;
+}
 
-  if (generate_lr_images) {  // data_path is the ground truth (super_resolution.cpp:285-299)
+// The HR image or the LR frames of --data_path, and the field of --flow_motion_path into the model parameters.
+int LoadImages(Options* o, Frames* f) {
+  if (o->generate_lr_images) f->high_res_image = util::LoadImage(o->data_path);
+  else f->low_res_images = util::LoadImages(o->data_path);
+  if (o->model.flow_motion_path.empty()) return 0;
+  // the file has no header: its size is checked against the HR geometry
+  if (!o->generate_lr_images && f->low_res_images.empty()) return NoLowResImages();
+  const cv::Size hr = o->generate_lr_images ? f->high_res_image.GetImageSize()
+                                            : cv::Size(f->low_res_images[0].GetImageSize().width * o->upsampling_scale,
+                                                       f->low_res_images[0].GetImageSize().height * o->upsampling_scale);
+  o->model.parameters.flow_motion_sequence.LoadSequenceFromFile(o->model.flow_motion_path, hr.width, hr.height);
+  return 0;
+}
+
+// The frames as the solver takes them: generated if asked for, in the space the solve runs in, with the initial estimate.
+int PrepareFrames(const Options& o, Frames* f) {
+  if (o.generate_lr_images) {  // data_path is the ground truth (super_resolution.cpp:285-299)
     // the generating model carries the AdditiveNoiseModule (sigma in 0..255 units), the solver's does not
-    ImageModelParameters with_noise = model_parameters;
-    with_noise.noise_sigma = noise_sigma;
-    with_noise.noise_seed = static_cast<uint64_t>(noise_seed);
+    ImageModelParameters with_noise = o.model.parameters;
+    with_noise.noise_sigma = o.noise_sigma;
+    with_noise.noise_seed = static_cast<uint64_t>(o.noise_seed);
     const ImageModel image_model_with_noise = ImageModel::CreateImageModel(with_noise);
-    for (int i = 0; i < number_of_frames; ++i) low_res_images.push_back(image_model_with_noise.ApplyToImage(high_res_image, i));
-  } else {
-    if (!ground_truth_image.empty()) high_res_image = util::LoadImage(ground_truth_image);
+    for (int i = 0; i < o.number_of_frames; ++i)
+      f->low_res_images.push_back(image_model_with_noise.ApplyToImage(f->high_res_image, i));
+  } else if (!o.ground_truth_image.empty()) {
+    f->high_res_image = util::LoadImage(o.ground_truth_image);
   }
-  if (low_res_images.empty()) {
-    std::fprintf(stderr, "Check failed: At least one low-resolution image is required for super-resolution.\n");
-    return 1;
-  }
-  const bool has_ground_truth = !ground_truth_image.empty() || generate_lr_images;
-  const bool evaluate_results = has_ground_truth && !evaluators.empty();
+  if (f->low_res_images.empty()) return NoLowResImages();
 
-  // bilinear upsampling of frame 0 in the original spectral space: the evaluation baseline
-  ImageData upsampled_image = low_res_images[0];
-  upsampled_image.ResizeImage(upsampling_scale, INTERPOLATE_LINEAR);
+  f->upsampled_image = f->low_res_images[0];
+  f->upsampled_image.ResizeImage(o.upsampling_scale, INTERPOLATE_LINEAR);
 
   // luminance-only colour path (super_resolution.cpp:330-342, 392-395): solve Y, interpolate Cr / Cb
-  if (interpolate_color) {
+  if (o.interpolate_color) {
     std::printf("Super-resolving only the luminance channel.\n");
-    for (auto& frame : low_res_images) frame.ChangeColorSpace(SPECTRAL_MODE_COLOR_YCRCB, true);
+    for (auto& frame : f->low_res_images) frame.ChangeColorSpace(SPECTRAL_MODE_COLOR_YCRCB, true);
   }
-
   // spectral PCA (super_resolution.cpp:344-366): solve on the leading components, reconstruct afterwards
-  std::unique_ptr<SpectralPCA> spectral_pca;
-  if (solve_in_pca_space && !interpolate_color) {
-    if (pca_retained_variance > 0.0) spectral_pca.reset(new SpectralPCA(low_res_images, pca_retained_variance));
-    else spectral_pca.reset(new SpectralPCA(low_res_images, num_pca_components));
-    for (auto& frame : low_res_images) frame = spectral_pca->GetPCAImage(frame);
-    std::printf("Super-resolving in PCA space with %d PCA components.\n", low_res_images[0].GetNumChannels());
+  if (o.solve_in_pca_space && !o.interpolate_color) {
+    if (o.pca_retained_variance > 0.0) f->spectral_pca.reset(new SpectralPCA(f->low_res_images, o.pca_retained_variance));
+    else f->spectral_pca.reset(new SpectralPCA(f->low_res_images, o.num_pca_components));
+    for (auto& frame : f->low_res_images) frame = f->spectral_pca->GetPCAImage(frame);
+    std::printf("Super-resolving in PCA space with %d PCA components.\n", f->low_res_images[0].GetNumChannels());
   }
 
-  ImageData initial_estimate = low_res_images[0];
-  initial_estimate.ResizeImage(upsampling_scale, INTERPOLATE_LINEAR);
-
-  if (!save_initial_estimate.empty()) {
-    const std::vector<double> planar = initial_estimate.ToPlanar();
-    std::FILE* f = std::fopen(save_initial_estimate.c_str(), "wb");
-    if (!f || std::fwrite(planar.data(), sizeof(double), planar.size(), f) != planar.size()) {
-      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_initial_estimate.c_str());
-      return 1;
-    }
-    std::fclose(f);
+  f->initial_estimate = f->low_res_images[0];
+  f->initial_estimate.ResizeImage(o.upsampling_scale, INTERPOLATE_LINEAR);
+  if (!o.save_initial_estimate.empty()) {
+    const std::vector<double> planar = f->initial_estimate.ToPlanar();
+    std::FILE* file = std::fopen(o.save_initial_estimate.c_str(), "wb");
+    if (!file || std::fwrite(planar.data(), sizeof(double), planar.size(), file) != planar.size())
+      return app::CannotWrite(o.save_initial_estimate);
+    std::fclose(file);
   }
+  return 0;
+}
 
-  // --registration: the solver's model takes its motion from the frames it is about to solve (channel 0), in HR pixels;
-  // the generating model above keeps the motion files
-  auto save_motion = [&](const AffineMotionSequence& sequence) -> bool {
-    std::FILE* f = std::fopen(save_motion_path.c_str(), "w");
-    if (!f) {
-      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_motion_path.c_str());
-      return false;
-    }
-    for (int i = 0; i < sequence.GetNumMotions(); ++i) {
-      const AffineMotion& m = sequence[i];
-      std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", m.a, m.b, m.tx, m.c, m.d, m.ty);
-    }
-    std::fclose(f);
-    return true;
-  };
-  ImageModelParameters solver_parameters = model_parameters;
-  std::vector<double> flow_valid;  // --registration=flow: the validity masks, [frames][h][w] at LR resolution
-  if (register_flow) {
-    solver_parameters.flow_motion_sequence = registration::FlowRegistration(low_res_images, upsampling_scale, &flow_valid);
+int SaveMotion(const Options& o, const AffineMotionSequence& sequence) {
+  return sequence.SaveToFile(o.save_motion_path) ? 0 : app::CannotWrite(o.save_motion_path);
+}
+
+// --registration: the solver's model takes its motion from the frames it is about to solve (channel 0), in HR pixels; the
+// generating model keeps the motion files
+int EstimateMotion(const Options& o, Frames* f, ImageModelParameters* solver_parameters) {
+  if (o.RegisterFlow()) {
+    solver_parameters->flow_motion_sequence = registration::FlowRegistration(f->low_res_images, o.upsampling_scale, &f->flow_valid);
     double kept = 0.0;
-    for (const double v : flow_valid) kept += v;
+    for (const double v : f->flow_valid) kept += v;
     std::printf("Estimated flow motion of %d frames from the low-resolution images; %.1f %% of the pixels are valid.\n",
-                solver_parameters.flow_motion_sequence.GetNumMotions(), 100.0 * kept / static_cast<double>(flow_valid.size()));
-    if (!save_flow_path.empty() && !solver_parameters.flow_motion_sequence.SaveToFile(save_flow_path)) {
-      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_flow_path.c_str());
-      return 1;
-    }
-  } else if (!registration_name.empty()) {
-    solver_parameters.motion_sequence_path.clear();
-    solver_parameters.affine_motion_sequence_path.clear();
+                solver_parameters->flow_motion_sequence.GetNumMotions(), 100.0 * kept / static_cast<double>(f->flow_valid.size()));
+    if (!o.save_flow_path.empty() && !solver_parameters->flow_motion_sequence.SaveToFile(o.save_flow_path))
+      return app::CannotWrite(o.save_flow_path);
+  } else if (!o.registration.empty()) {
+    solver_parameters->motion_sequence_path.clear();
+    solver_parameters->affine_motion_sequence_path.clear();
     AffineMotionSequence estimate;
-    if (registration_name == "affine") {
-      estimate = registration::AffineRegistration(low_res_images, upsampling_scale);
-      solver_parameters.affine_motion_sequence = estimate;
+    if (o.registration == "affine") {
+      estimate = registration::AffineRegistration(f->low_res_images, o.upsampling_scale);
+      solver_parameters->affine_motion_sequence = estimate;
     } else {
-      const MotionShiftSequence lr_shifts = registration::TranslationalRegistration(low_res_images);
+      const MotionShiftSequence lr_shifts = registration::TranslationalRegistration(f->low_res_images);
       std::vector<MotionShift> shifts;
       std::vector<AffineMotion> motions;
       for (int i = 0; i < lr_shifts.GetNumMotionShifts(); ++i) {
-        shifts.push_back(MotionShift(upsampling_scale * lr_shifts[i].dx, upsampling_scale * lr_shifts[i].dy));
+        shifts.push_back(MotionShift(o.upsampling_scale * lr_shifts[i].dx, o.upsampling_scale * lr_shifts[i].dy));
         motions.push_back(AffineMotion(1.0, 0.0, shifts.back().dx, 0.0, 1.0, shifts.back().dy));
       }
-      solver_parameters.motion_sequence = MotionShiftSequence(shifts);
+      solver_parameters->motion_sequence = MotionShiftSequence(shifts);
       estimate = AffineMotionSequence(motions);
     }
-    std::printf("Estimated %s motion of %d frames from the low-resolution images.\n", registration_name.c_str(),
-                estimate.GetNumMotions());
+    std::printf("Estimated %s motion of %d frames from the low-resolution images.\n", o.registration.c_str(), estimate.GetNumMotions());
     // with refinement rounds the file holds the FINAL matrices: written after the solve
-    if (!save_motion_path.empty() && refine_motion_rounds == 0 && !save_motion(estimate)) return 1;
+    if (!o.save_motion_path.empty() && o.refine_motion_rounds == 0) return SaveMotion(o, estimate);
   }
-  const ImageModel solver_model = registration_name.empty() ? image_model : ImageModel::CreateImageModel(solver_parameters);
+  return 0;
+}
 
-  IRLSMapSolver solver(solver_options, solver_model, low_res_images, verbose);
-  if (regularization_parameter > 0.0) {
+// --regularizer, and the validity masks of --registration=flow
+void SetUpSolver(const Options& o, const Frames& f, IRLSMapSolver* solver) {
+  if (o.regularization_parameter > 0.0) {
     std::shared_ptr<Regularizer> regularizer;
-    if (regularizer_name == "btv") {
-      regularizer = std::make_shared<BilateralTotalVariationRegularizer>(initial_estimate.GetImageSize(),
-                                                                         btv_scale_range, btv_spatial_decay);
+    if (o.regularizer == "btv") {
+      regularizer = std::make_shared<BilateralTotalVariationRegularizer>(f.initial_estimate.GetImageSize(), o.btv_scale_range,
+                                                                         o.btv_spatial_decay);
     } else {
-      if (regularizer_name != "tv" && regularizer_name != "3dtv") {
+      if (o.regularizer != "tv" && o.regularizer != "3dtv")
         std::fprintf(stderr, "WARNING: Unknown regularizer option '%s'. Using default Total Variation regularizer.\n",
-                     regularizer_name.c_str());
-        regularizer_name = "tv";
-      }
-      auto tv = std::make_shared<TotalVariationRegularizer>(initial_estimate.GetImageSize());
-      if (regularizer_name == "3dtv") tv->SetUse3dTotalVariation(true);
+                     o.regularizer.c_str());
+      auto tv = std::make_shared<TotalVariationRegularizer>(f.initial_estimate.GetImageSize());
+      if (o.regularizer == "3dtv") tv->SetUse3dTotalVariation(true);
       regularizer = tv;
     }
-    solver.AddRegularizer(regularizer, regularization_parameter);
+    solver->AddRegularizer(regularizer, o.regularization_parameter);
   }
   // --registration=flow: the field is wrong where frame 0 does not hold the content; those pixels get weight 0.  A Huber
   // solve derives its own weights and resets the buffer (include/srmap.h) -- unless the masks are the persistent prior
   // (--flow_valid_prior, srmap_set_data_prior), which a Huber solve resets to and multiplies its weights by
-  if (register_flow && flow_valid_prior) solver.SetDataPrior(flow_valid);
-  else if (register_flow && solver_options.data_loss == L2_DATA_LOSS) solver.MultiplyDataWeights(flow_valid);
+  if (o.RegisterFlow() && o.flow_valid_prior) solver->SetDataPrior(f.flow_valid);
+  else if (o.RegisterFlow() && o.solver.data_loss == L2_DATA_LOSS) solver->MultiplyDataWeights(f.flow_valid);
+}
 
-  // --fit_blur_from: the calibration fit, before the solve, from a known HR image of what the frames show
-  if (!fit_blur_from.empty()) {
-    if (interpolate_color || spectral_pca) {
-      std::fprintf(stderr, "ERROR: --fit_blur_from works in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
-      return 1;
-    }
-    BlurFitOptions fit_options;
-    fit_options.ksize = fit_blur_ksize;
-    std::vector<double> quality;
-    const BlurKernel fitted = solver.FitBlur(util::LoadImage(fit_blur_from), fit_options, &quality);
+// The fits and the photometric model compare the frames with images in the frames' own channels.
+int RefuseTransformedChannels(const Frames& f, const Options& o, const char* subject) {
+  if (!o.interpolate_color && !f.spectral_pca) return 0;
+  return app::Refuse("%s in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.", subject);
+}
+
+// The calibration fits before the solve, from a known HR image of what the frames show, and --photometric_path
+int CalibrateSolver(const Options& o, const Frames& f, IRLSMapSolver* solver) {
+  BlurFitOptions fit_options;
+  fit_options.ksize = o.fit_blur_ksize;
+  std::vector<double> quality;
+  if (!o.fit_blur_from.empty()) {
+    if (RefuseTransformedChannels(f, o, "--fit_blur_from works")) return 1;
+    const BlurKernel fitted = solver->FitBlur(util::LoadImage(o.fit_blur_from), fit_options, &quality);
     std::printf("Fitted a %d x %d blur kernel: cost %g -> %g, status %g.\n", fitted.GetSize(), fitted.GetSize(), quality[0], quality[1], quality[4]);
-    if (!save_blur_kernel_path.empty() && !fitted.SaveToFile(save_blur_kernel_path)) {
-      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_blur_kernel_path.c_str());
-      return 1;
-    }
+    if (!o.save_blur_kernel_path.empty() && !fitted.SaveToFile(o.save_blur_kernel_path)) return app::CannotWrite(o.save_blur_kernel_path);
   }
-
   // --fit_blur_bank_from: the same calibration fit per entry of a bank (a kernel per frame, per channel or per both)
-  if (!fit_blur_bank_from.empty()) {
-    if (interpolate_color || spectral_pca) {
-      std::fprintf(stderr, "ERROR: --fit_blur_bank_from works in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
-      return 1;
-    }
-    BlurFitOptions fit_options;
-    fit_options.ksize = fit_blur_ksize;
-    std::vector<double> quality;
-    const BlurKernelBank fitted = solver.FitBlurBank(util::LoadImage(fit_blur_bank_from), fit_bank_mode, fit_options, &quality);
+  if (!o.fit_blur_bank_from.empty()) {
+    if (RefuseTransformedChannels(f, o, "--fit_blur_bank_from works")) return 1;
+    const BlurKernelBank fitted = solver->FitBlurBank(util::LoadImage(o.fit_blur_bank_from), o.FitBankMode(), fit_options, &quality);
     int degenerate = 0;
     for (int e = 0; e < fitted.GetNumEntries(); ++e) degenerate += quality[5 * e + 4] != 0.0;
     std::printf("Fitted a bank of %d %d x %d blur kernels (mode %s): %d degenerate.\n", fitted.GetNumEntries(), fitted.GetSize(),
-                fitted.GetSize(), fit_blur_bank_mode.c_str(), degenerate);
-    if (!save_blur_bank_path.empty() && !fitted.SaveToFile(save_blur_bank_path)) {
-      std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_blur_bank_path.c_str());
-      return 1;
-    }
+                fitted.GetSize(), o.fit_blur_bank_mode.c_str(), degenerate);
+    if (!o.save_blur_bank_path.empty() && !fitted.SaveToFile(o.save_blur_bank_path)) return app::CannotWrite(o.save_blur_bank_path);
   }
-
-  // --photometric_path: known exposure, in force for every solve below
-  const bool photometric = !photometric_path.empty() || photometric_rounds >= 0;
-  if (photometric && (interpolate_color || spectral_pca)) {
-    std::fprintf(stderr, "ERROR: the photometric flags work in the frames' own channels: not with --interpolate_color or --solve_in_pca_space.\n");
-    return 1;
-  }
-  if (!photometric_path.empty()) {
+  if (!o.photometric_path.empty() || o.photometric_rounds >= 0)
+    if (RefuseTransformedChannels(f, o, "the photometric flags work")) return 1;
+  if (!o.photometric_path.empty()) {  // known exposure, in force for every solve below
     PhotometricSequence known;
-    known.LoadSequenceFromFile(photometric_path);
-    solver.SetPhotometric(known);
+    known.LoadSequenceFromFile(o.photometric_path);
+    solver->SetPhotometric(known);
   }
+  return 0;
+}
 
-  std::printf("Super-resolving from %zu images...\n", low_res_images.size());
+// The solve, with the photometric and motion refinement rounds asked for, back in the frames' original channels.
+int Solve(const Options& o, const Frames& f, IRLSMapSolver* solver, ImageData* result) {
+  std::printf("Super-resolving from %zu images...\n", f.low_res_images.size());
   const auto start_time = std::chrono::steady_clock::now();
-  ImageData result;
-  if (photometric_rounds >= 0) {
-    MotionRefinementOptions refinement;
-    refinement.dof = refine_motion_dof;
-    AffineMotionSequence refined;
+  MotionRefinementOptions refinement;
+  refinement.dof = o.refine_motion_dof;
+  AffineMotionSequence refined;
+  // with --photometric_rounds every round fits the exposure, refines the motion, then solves; the larger count rules
+  const int rounds = std::max(o.refine_motion_rounds, o.photometric_rounds);
+  if (o.photometric_rounds >= 0) {
     PhotometricSequence fitted;
-    // with --refine_motion_rounds every round fits the exposure, refines the motion, then solves; the larger count rules
-    const int rounds = refine_motion_rounds > photometric_rounds ? refine_motion_rounds : photometric_rounds;
-    result = solver.SolvePhotometricJoint(initial_estimate, rounds, refine_motion_rounds > 0, PhotometricFitOptions(), refinement,
-                                          &fitted, &refined);
+    *result = solver->SolvePhotometricJoint(f.initial_estimate, rounds, o.refine_motion_rounds > 0, PhotometricFitOptions(), refinement,
+                                            &fitted, &refined);
     std::printf("Fitted gain and bias of %d frames in %d rounds.\n", fitted.GetNumFrames(), rounds);
-    if (refine_motion_rounds > 0) {
-      std::printf("Refined the motion of %d frames in %d rounds.\n", refined.GetNumMotions(), rounds);
-      if (!save_motion_path.empty() && !save_motion(refined)) return 1;
-    }
-  } else if (refine_motion_rounds > 0) {
-    MotionRefinementOptions refinement;
-    refinement.dof = refine_motion_dof;
-    AffineMotionSequence refined;
-    result = solver.SolveJoint(initial_estimate, refine_motion_rounds, refinement, &refined);
-    std::printf("Refined the motion of %d frames in %d rounds.\n", refined.GetNumMotions(), refine_motion_rounds);
-    if (!save_motion_path.empty() && !save_motion(refined)) return 1;
+  } else if (o.refine_motion_rounds > 0) {
+    *result = solver->SolveJoint(f.initial_estimate, rounds, refinement, &refined);
   } else {
-    result = solver.Solve(initial_estimate);
+    *result = solver->Solve(f.initial_estimate);
   }
-  if (!save_photometric_path.empty() && !solver.GetPhotometric().SaveToFile(save_photometric_path)) {
-    std::fprintf(stderr, "ERROR: cannot write '%s'.\n", save_photometric_path.c_str());
-    return 1;
+  if (o.refine_motion_rounds > 0) {
+    std::printf("Refined the motion of %d frames in %d rounds.\n", refined.GetNumMotions(), rounds);
+    if (!o.save_motion_path.empty() && SaveMotion(o, refined)) return 1;
   }
+  if (!o.save_photometric_path.empty() && !solver->GetPhotometric().SaveToFile(o.save_photometric_path))
+    return app::CannotWrite(o.save_photometric_path);
   const std::chrono::duration<double> elapsed = std::chrono::steady_clock::now() - start_time;
   std::printf("Done! Finished in %g seconds.\n", elapsed.count());
-  if (interpolate_color) {
-    result.InterpolateColorFrom(initial_estimate);
-    result.ChangeColorSpace(SPECTRAL_MODE_COLOR_BGR);
+  if (o.interpolate_color) {
+    result->InterpolateColorFrom(f.initial_estimate);
+    result->ChangeColorSpace(SPECTRAL_MODE_COLOR_BGR);
   }
-  if (spectral_pca) result = spectral_pca->ReconstructImage(result);
+  if (f.spectral_pca) *result = f.spectral_pca->ReconstructImage(*result);
+  return 0;
+}
 
-  if (evaluate_results) {
-    size_t pos = 0;
-    while (pos <= evaluators.size()) {
-      const size_t comma = evaluators.find(',', pos);
-      const std::string evaluator = util::TrimString(evaluators.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
-      if (evaluator == "psnr") {
-        const PeakSignalToNoiseRatioEvaluator psnr_evaluator(high_res_image);
-        std::cout << "PSNR score on upsampled: " << psnr_evaluator.Evaluate(upsampled_image) << std::endl;
-        std::cout << "PSNR score on result:    " << psnr_evaluator.Evaluate(result) << std::endl;
-      } else if (evaluator == "ssim") {
-        const StructuralSimilarityEvaluator ssim_evaluator(high_res_image);
-        std::cout << "SSIM score on upsampled: " << ssim_evaluator.Evaluate(upsampled_image) << std::endl;
-        std::cout << "SSIM score on result:    " << ssim_evaluator.Evaluate(result) << std::endl;
-      } else if (!evaluator.empty()) {
-        std::fprintf(stderr, "ERROR: Unknown/unsupported evaluator '%s'.\n", evaluator.c_str());
-      }
-      if (comma == std::string::npos) break;
-      pos = comma + 1;
+// --evaluators against the ground truth: the bilinear baseline and the result
+void Evaluate(const Options& o, const Frames& f, const ImageData& result) {
+  size_t pos = 0;
+  while (pos <= o.evaluators.size()) {
+    const size_t comma = o.evaluators.find(',', pos);
+    const std::string evaluator = util::TrimString(o.evaluators.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
+    if (evaluator == "psnr") {
+      const PeakSignalToNoiseRatioEvaluator psnr_evaluator(f.high_res_image);
+      std::cout << "PSNR score on upsampled: " << psnr_evaluator.Evaluate(f.upsampled_image) << std::endl;
+      std::cout << "PSNR score on result:    " << psnr_evaluator.Evaluate(result) << std::endl;
+    } else if (evaluator == "ssim") {
+      const StructuralSimilarityEvaluator ssim_evaluator(f.high_res_image);
+      std::cout << "SSIM score on upsampled: " << ssim_evaluator.Evaluate(f.upsampled_image) << std::endl;
+      std::cout << "SSIM score on result:    " << ssim_evaluator.Evaluate(result) << std::endl;
+    } else if (!evaluator.empty()) {
+      std::fprintf(stderr, "ERROR: Unknown/unsupported evaluator '%s'.\n", evaluator.c_str());
     }
+    if (comma == std::string::npos) break;
+    pos = comma + 1;
   }
-  if (!result_path.empty()) util::SaveImage(result, result_path);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  Options options = ParseFlags(argc, argv);
+  if (CheckFlags(options)) return 1;
+  ChooseSolverAndLoss(&options);
+
+  Frames frames;
+  if (LoadImages(&options, &frames)) return 1;
+  const ImageModel image_model = ImageModel::CreateImageModel(options.model.parameters);
+  if (PrepareFrames(options, &frames)) return 1;
+
+  ImageModelParameters solver_parameters = options.model.parameters;
+  if (EstimateMotion(options, &frames, &solver_parameters)) return 1;
+  const ImageModel solver_model = options.registration.empty() ? image_model : ImageModel::CreateImageModel(solver_parameters);
+
+  IRLSMapSolver solver(options.solver, solver_model, frames.low_res_images, options.verbose);
+  SetUpSolver(options, frames, &solver);
+  if (CalibrateSolver(options, frames, &solver)) return 1;
+
+  ImageData result;
+  if (Solve(options, frames, &solver, &result)) return 1;
+  const bool has_ground_truth = !options.ground_truth_image.empty() || options.generate_lr_images;
+  if (has_ground_truth && !options.evaluators.empty()) Evaluate(options, frames, result);
+  if (!options.result_path.empty()) util::SaveImage(result, options.result_path);
   return 0;
 }

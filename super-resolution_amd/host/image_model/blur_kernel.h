@@ -3,7 +3,7 @@
 // transpose uses its flip in both axes (srmap_problem_set_blur_kernel, include/srmap.h, which states the domain).  No
 // reference counterpart: BlurModule there builds a Gaussian from (radius, sigma) only (blur_module.cpp:13-22).  Loadable
 // from a text file: the first number is ksize, then ksize * ksize numbers in row-major order, separated by any white space
-// (a reader of its own, written as AffineMotionSequence's is, motion/affine_motion.h).
+// (the taps reader and row writer it shares with BlurKernelBank are in util/number_file.h).
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "util/number_file.h"
 #include "util/srmap_host.h"
 
 namespace super_resolution {
@@ -29,22 +30,15 @@ class BlurKernel {
     if (!(fin >> size) || size < 1.0 || size != std::floor(size) || static_cast<int>(size) % 2 != 1 || size > 99.0)
       srmap_host::Fail((path + ": expected an odd kernel size first").c_str());
     const int ksize = static_cast<int>(size);
-    std::vector<double> taps(static_cast<size_t>(ksize) * ksize);
-    for (size_t i = 0; i < taps.size(); ++i)
-      if (!(fin >> taps[i]))
-        srmap_host::Fail((path + ": expected " + std::to_string(taps.size()) + " taps after the size, read " + std::to_string(i)).c_str());
-    std::string rest;
-    if (fin >> rest) srmap_host::Fail((path + ": more than " + std::to_string(taps.size()) + " taps after the size").c_str());
+    taps_ = srmap_host::ReadTaps(fin, path, static_cast<size_t>(ksize) * ksize, "the size");
     ksize_ = ksize;
-    taps_.swap(taps);
   }
   // the same format, one kernel row per line, every tap with 17 significant digits (it loads again bit for bit)
   bool SaveToFile(const std::string& path) const {
     std::FILE* f = std::fopen(path.c_str(), "w");
     if (!f) return false;
     std::fprintf(f, "%d\n", ksize_);
-    for (int a = 0; a < ksize_; ++a)
-      for (int e = 0; e < ksize_; ++e) std::fprintf(f, "%.17g%c", taps_[static_cast<size_t>(a) * ksize_ + e], e + 1 < ksize_ ? ' ' : '\n');
+    srmap_host::WriteKernelRows(f, taps_.data(), ksize_);
     return std::fclose(f) == 0;
   }
   bool Empty() const { return taps_.empty(); }
@@ -97,16 +91,10 @@ class BlurKernelBank {
       srmap_host::Fail((path + ": expected an odd kernel size after the mode").c_str());
     if (!(fin >> entries) || entries < 1.0 || entries != std::floor(entries) || entries > 1.0e6)
       srmap_host::Fail((path + ": expected the number of entries after the size").c_str());
-    std::vector<double> taps(static_cast<size_t>(entries) * static_cast<size_t>(size) * static_cast<size_t>(size));
-    for (size_t i = 0; i < taps.size(); ++i)
-      if (!(fin >> taps[i]))
-        srmap_host::Fail((path + ": expected " + std::to_string(taps.size()) + " taps after the header, read " + std::to_string(i)).c_str());
-    std::string rest;
-    if (fin >> rest) srmap_host::Fail((path + ": more than " + std::to_string(taps.size()) + " taps after the header").c_str());
+    taps_ = srmap_host::ReadTaps(fin, path, static_cast<size_t>(entries) * static_cast<size_t>(size) * static_cast<size_t>(size), "the header");
     mode_ = static_cast<int>(mode);
     ksize_ = static_cast<int>(size);
     entries_ = static_cast<int>(entries);
-    taps_.swap(taps);
   }
   // the same format, one kernel row per line, a blank line between entries, 17 significant digits (it loads again bit for bit)
   bool SaveToFile(const std::string& path) const {
@@ -114,9 +102,7 @@ class BlurKernelBank {
     if (!f) return false;
     std::fprintf(f, "%d %d %d\n", mode_, ksize_, entries_);
     for (int q = 0; q < entries_; ++q) {
-      for (int a = 0; a < ksize_; ++a)
-        for (int e = 0; e < ksize_; ++e)
-          std::fprintf(f, "%.17g%c", taps_[(static_cast<size_t>(q) * ksize_ + a) * ksize_ + e], e + 1 < ksize_ ? ' ' : '\n');
+      srmap_host::WriteKernelRows(f, taps_.data() + static_cast<size_t>(q) * ksize_ * ksize_, ksize_);
       if (q + 1 < entries_) std::fprintf(f, "\n");
     }
     return std::fclose(f) == 0;

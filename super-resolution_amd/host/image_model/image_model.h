@@ -62,6 +62,10 @@ class DegradationOperator {
   // default is "nothing" -- ImageModel::Canonical() does not recognise such an operator, so a model that contains one is
   // applied operator by operator on the host side of the ABI, exactly as the reference's loop does.
   virtual void Describe(srmap_host::ChainParams* chain) const { (void)chain; }
+
+ protected:
+  // the chain of this operator alone: what its own ApplyToImage / ApplyTransposeToImage run
+  srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
 };
 
 class MotionModule : public DegradationOperator {
@@ -99,7 +103,6 @@ class MotionModule : public DegradationOperator {
     else if (affine_) affine_sequence_.GetAffineMotion(index);
     else sequence_.GetMotionShift(index);
   }
-  srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const MotionShiftSequence sequence_;
   const AffineMotionSequence affine_sequence_;
   const FlowMotionSequence flow_sequence_;
@@ -141,7 +144,6 @@ class BlurModule : public DegradationOperator {
   bool IsBank() const { return !bank_.Empty(); }
 
  private:
-  srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const int blur_radius_;
   const double sigma_;
   const BlurKernel kernel_;
@@ -162,7 +164,6 @@ class DownsamplingModule : public DegradationOperator {
   void Describe(srmap_host::ChainParams* c) const override { c->scale = scale_; }
 
  private:
-  srmap_host::ChainParams Chain() const { srmap_host::ChainParams c; Describe(&c); return c; }
   const int scale_;
 };
 
@@ -311,5 +312,19 @@ class ImageModel {
   std::vector<std::shared_ptr<DegradationOperator>> operators_;
   const int downsampling_scale_;
 };
+
+namespace srmap_host {
+// The problem of a solver over n observations: the model's canonical chain with n frames and the first n of its motions.
+// `who` names the caller in the refusal of any other operator list.
+inline ProblemPtr MakeSolverProblem(const ImageModel& image_model, const size_t n, const cv::Size& image_size, const int channels,
+                                    const char* who) {
+  ChainParams chain;
+  if (!image_model.Canonical(&chain)) Fail((std::string(who) + " needs the [Motion][Blur]Downsampling operator chain").c_str());
+  chain.frames = static_cast<int>(n);
+  if (chain.HasMotion() && static_cast<size_t>(chain.NumMotions()) < n) Fail("fewer motion shifts than observations");
+  chain.TrimMotions(n);
+  return MakeProblem(chain, image_size.width, image_size.height, channels);
+}
+}  // namespace srmap_host
 
 }  // namespace super_resolution

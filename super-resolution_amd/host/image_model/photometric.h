@@ -2,17 +2,15 @@
 // gain_k * (D B M_k x) + bias_k, one pair per frame shared by all channels, the bias in the solver's pixel units (ImageData
 // scales 8-bit input to 0..1).  No reference counterpart: there every frame has the photometry of the HR image
 // (image_model.cpp:86-91).  The pairs go to srmap_problem_set_photometric (include/srmap.h), which states the domain.
-// Loadable from a text file of "gain bias" lines (a reader of its own, written as AffineMotionSequence's is,
-// motion/affine_motion.h).
+// Loadable from a text file of "gain bias" lines (AffineMotionSequence's line reader, util/number_file.h).
 #pragma once
 #include <cmath>
 #include <cstdio>
-#include <fstream>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "image/image_data.h"
+#include "util/number_file.h"
 #include "util/srmap_host.h"
 
 namespace super_resolution {
@@ -32,23 +30,12 @@ class PhotometricSequence {
   }
   // one frame per line, two numbers; blank lines are skipped, anything else is an error
   void LoadSequenceFromFile(const std::string& path) {
-    std::ifstream fin(path);
-    if (!fin.is_open()) srmap_host::Fail(("Could not open file " + path).c_str());
     frames_.clear();
-    std::string line;
-    int number = 0;
-    while (std::getline(fin, line)) {
-      ++number;
-      if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
-      std::istringstream in(line);
-      double gain = 0.0, bias = 0.0;
-      std::string rest;
-      if (!(in >> gain >> bias) || (in >> rest))
-        srmap_host::Fail((path + " line " + std::to_string(number) + ": expected two numbers 'gain bias'").c_str());
-      if (!std::isfinite(gain) || !std::isfinite(bias) || !(gain > 0.0))
-        srmap_host::Fail((path + " line " + std::to_string(number) + ": the gain must be > 0 and both numbers finite").c_str());
-      frames_.push_back(Photometric(gain, bias));
-    }
+    srmap_host::ReadNumberLines(path, 2, "two numbers 'gain bias'", [this](const double* v, const std::string& where) {
+      if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !(v[0] > 0.0))
+        srmap_host::Fail((where + ": the gain must be > 0 and both numbers finite").c_str());
+      frames_.push_back(Photometric(v[0], v[1]));
+    });
   }
   // the same format, every number with 17 significant digits (it loads again bit for bit)
   bool SaveToFile(const std::string& path) const {

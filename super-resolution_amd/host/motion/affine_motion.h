@@ -2,13 +2,13 @@
 // content at p in the HR image sits at L p + t in the frame's HR-grid image (MotionShift's convention: the shift (dx, dy)
 // is [1 0 dx; 0 1 dy]).  No reference counterpart (its MotionModule warps by a MotionShift only, motion_module.cpp:18-51);
 // the class mirrors MotionShiftSequence (src/motion/motion_shift.h:14-57), loadable from a text file of
-// "a b tx c d ty" lines.  The matrices go to srmap_problem_set_affine_motion (include/srmap.h), which states the domain.
+// "a b tx c d ty" lines and writable as one (SaveToFile).  The matrices go to srmap_problem_set_affine_motion (include/srmap.h), which states the domain.
 #pragma once
-#include <fstream>
-#include <sstream>
+#include <cstdio>
 #include <string>
 #include <vector>
 
+#include "util/number_file.h"
 #include "util/srmap_host.h"
 
 namespace super_resolution {
@@ -26,21 +26,17 @@ class AffineMotionSequence {
   void SetMotionSequence(const std::vector<AffineMotion>& motions) { motions_ = motions; }
   // one frame per line, six numbers; blank lines are skipped, anything else is an error
   void LoadSequenceFromFile(const std::string& path) {
-    std::ifstream fin(path);
-    if (!fin.is_open()) srmap_host::Fail(("Could not open file " + path).c_str());
     motions_.clear();
-    std::string line;
-    int number = 0;
-    while (std::getline(fin, line)) {
-      ++number;
-      if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
-      std::istringstream in(line);
-      double v[6];
-      std::string rest;
-      if (!(in >> v[0] >> v[1] >> v[2] >> v[3] >> v[4] >> v[5]) || (in >> rest))
-        srmap_host::Fail((path + " line " + std::to_string(number) + ": expected six numbers 'a b tx c d ty'").c_str());
+    srmap_host::ReadNumberLines(path, 6, "six numbers 'a b tx c d ty'", [this](const double* v, const std::string&) {
       motions_.push_back(AffineMotion(v[0], v[1], v[2], v[3], v[4], v[5]));
-    }
+    });
+  }
+  // the same format, every number with 17 significant digits (it loads again bit for bit)
+  bool SaveToFile(const std::string& path) const {
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    for (const AffineMotion& m : motions_) std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", m.a, m.b, m.tx, m.c, m.d, m.ty);
+    return std::fclose(f) == 0;
   }
   int GetNumMotions() const { return static_cast<int>(motions_.size()); }
   const AffineMotion& GetAffineMotion(const int index) const {

@@ -21,28 +21,47 @@
 namespace super_resolution {
 namespace registration {
 
+namespace internal {
+// Channel 0 of every image, stacked [images][height][width]: what the C entry points register.  The images are of one
+// size with at least one channel; `images` is not empty.
+inline std::vector<double> ChannelZeroStack(const std::vector<ImageData>& images, cv::Size* size) {
+  *size = images[0].GetImageSize();
+  const size_t npx = static_cast<size_t>(size->width) * size->height;
+  std::vector<double> stack(npx * images.size());
+  for (size_t i = 0; i < images.size(); ++i) {
+    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size->width ||
+        images[i].GetImageSize().height != size->height)
+      srmap_host::Fail("registration needs images of one size with at least one channel");
+    const double* ch = images[i].GetChannelData(0);
+    std::copy(ch, ch + npx, stack.begin() + i * npx);
+  }
+  return stack;
+}
+
+// The body of the two translational functions: quality == nullptr is the reference's call (srmap_register_translational).
+inline MotionShiftSequence Translational(const std::vector<ImageData>& images, std::vector<double>* quality) {
+  cv::Size size;
+  const std::vector<double> stack = ChannelZeroStack(images, &size);
+  const int n = static_cast<int>(images.size());
+  std::vector<double> xy(2 * images.size());
+  if (quality) quality->assign(2 * images.size(), 0.0);
+  srmap_host::Check(quality ? srmap_register_translational_ex(srmap_host::Context(), n, size.width, size.height, stack.data(),
+                                                              xy.data(), quality->data())
+                            : srmap_register_translational(srmap_host::Context(), n, size.width, size.height, stack.data(),
+                                                           xy.data()),
+                    "Could not determine motion shift between images.");
+  std::vector<MotionShift> shifts;
+  for (size_t i = 0; i < images.size(); ++i) shifts.push_back(MotionShift(xy[2 * i], xy[2 * i + 1]));
+  return MotionShiftSequence(shifts);
+}
+}  // namespace internal
+
 inline MotionShiftSequence TranslationalRegistration(const std::vector<ImageData>& images) {
   if (images.empty()) {
     std::fprintf(stderr, "WARNING: No images given. Returning an empty motion sequence.\n");
     return MotionShiftSequence();
   }
-  const cv::Size size = images[0].GetImageSize();
-  const size_t npx = static_cast<size_t>(size.width) * size.height;
-  std::vector<double> stack(npx * images.size());
-  for (size_t i = 0; i < images.size(); ++i) {
-    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
-        images[i].GetImageSize().height != size.height)
-      srmap_host::Fail("registration needs images of one size with at least one channel");
-    const double* ch = images[i].GetChannelData(0);
-    std::copy(ch, ch + npx, stack.begin() + i * npx);
-  }
-  std::vector<double> xy(2 * images.size());
-  srmap_host::Check(srmap_register_translational(srmap_host::Context(), static_cast<int>(images.size()), size.width,
-                                                 size.height, stack.data(), xy.data()),
-                    "Could not determine motion shift between images.");
-  std::vector<MotionShift> shifts;
-  for (size_t i = 0; i < images.size(); ++i) shifts.push_back(MotionShift(xy[2 * i], xy[2 * i + 1]));
-  return MotionShiftSequence(shifts);
+  return internal::Translational(images, nullptr);
 }
 
 // The same with the estimator's per-image quality: quality[2i] = separation of the coarse minimum (near 1 = clear,
@@ -50,24 +69,7 @@ inline MotionShiftSequence TranslationalRegistration(const std::vector<ImageData
 inline MotionShiftSequence TranslationalRegistrationWithQuality(const std::vector<ImageData>& images,
                                                                 std::vector<double>* quality) {
   if (images.empty()) return MotionShiftSequence();
-  const cv::Size size = images[0].GetImageSize();
-  const size_t npx = static_cast<size_t>(size.width) * size.height;
-  std::vector<double> stack(npx * images.size());
-  for (size_t i = 0; i < images.size(); ++i) {
-    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
-        images[i].GetImageSize().height != size.height)
-      srmap_host::Fail("registration needs images of one size with at least one channel");
-    const double* ch = images[i].GetChannelData(0);
-    std::copy(ch, ch + npx, stack.begin() + i * npx);
-  }
-  std::vector<double> xy(2 * images.size());
-  quality->assign(2 * images.size(), 0.0);
-  srmap_host::Check(srmap_register_translational_ex(srmap_host::Context(), static_cast<int>(images.size()), size.width,
-                                                    size.height, stack.data(), xy.data(), quality->data()),
-                    "Could not determine motion shift between images.");
-  std::vector<MotionShift> shifts;
-  for (size_t i = 0; i < images.size(); ++i) shifts.push_back(MotionShift(xy[2 * i], xy[2 * i + 1]));
-  return MotionShiftSequence(shifts);
+  return internal::Translational(images, quality);
 }
 
 // Not in the reference: the affine motion of every image relative to the first one (srmap_register_affine,
@@ -82,16 +84,8 @@ inline AffineMotionSequence AffineRegistrationWithQuality(const std::vector<Imag
     std::fprintf(stderr, "WARNING: No images given. Returning an empty motion sequence.\n");
     return AffineMotionSequence();
   }
-  const cv::Size size = images[0].GetImageSize();
-  const size_t npx = static_cast<size_t>(size.width) * size.height;
-  std::vector<double> stack(npx * images.size());
-  for (size_t i = 0; i < images.size(); ++i) {
-    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
-        images[i].GetImageSize().height != size.height)
-      srmap_host::Fail("registration needs images of one size with at least one channel");
-    const double* ch = images[i].GetChannelData(0);
-    std::copy(ch, ch + npx, stack.begin() + i * npx);
-  }
+  cv::Size size;
+  const std::vector<double> stack = internal::ChannelZeroStack(images, &size);
   srmap_affine_registration_options options;
   srmap_affine_registration_options_default(&options);
   options.hr_scale = scale;
@@ -139,16 +133,9 @@ inline FlowMotionSequence FlowRegistration(const std::vector<ImageData>& images,
     return FlowMotionSequence();
   }
   if (scale < 1) srmap_host::Fail("flow registration: the scale must be at least 1");
-  const cv::Size size = images[0].GetImageSize();
+  cv::Size size;
+  const std::vector<double> stack = internal::ChannelZeroStack(images, &size);
   const size_t npx = static_cast<size_t>(size.width) * size.height;
-  std::vector<double> stack(npx * images.size());
-  for (size_t i = 0; i < images.size(); ++i) {
-    if (images[i].GetNumChannels() < 1 || images[i].GetImageSize().width != size.width ||
-        images[i].GetImageSize().height != size.height)
-      srmap_host::Fail("registration needs images of one size with at least one channel");
-    const double* ch = images[i].GetChannelData(0);
-    std::copy(ch, ch + npx, stack.begin() + i * npx);
-  }
   srmap_flow_registration_options options;
   srmap_flow_registration_options_default(&options);
   options.hr_scale = scale;

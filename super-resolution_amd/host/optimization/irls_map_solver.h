@@ -128,14 +128,7 @@ class MapSolver : public Solver {
     image_size_ = cv::Size(lr.width * s, lr.height * s);
     // The library keeps the observations at LR resolution (the reference stores
     // them NN-upsampled, map_solver.cpp:80-85; algebraically identical).
-    srmap_host::ChainParams chain;
-    if (!image_model_.Canonical(&chain))
-      srmap_host::Fail("MapSolver needs the [Motion][Blur]Downsampling operator chain");
-    chain.frames = static_cast<int>(low_res_images.size());
-    if (chain.HasMotion() && static_cast<size_t>(chain.NumMotions()) < low_res_images.size())
-      srmap_host::Fail("fewer motion shifts than observations");
-    chain.TrimMotions(low_res_images.size());
-    problem_ = srmap_host::MakeProblem(chain, image_size_.width, image_size_.height, num_channels_);
+    problem_ = srmap_host::MakeSolverProblem(image_model_, low_res_images.size(), image_size_, num_channels_, "MapSolver");
     std::vector<double> stack;
     for (const ImageData& im : low_res_images) {
       if (im.GetImageSize() != lr) srmap_host::Fail("observation sizes differ");
@@ -194,9 +187,7 @@ class IRLSMapSolver : public MapSolver {
 
   // irls_map_solver.cpp:192-265
   ImageData Solve(const ImageData& initial_estimate) override {
-    if (initial_estimate.GetNumPixels() != GetNumPixels() || initial_estimate.GetNumChannels() != GetNumChannels() ||
-        initial_estimate.GetImageSize() != GetImageSize())
-      srmap_host::Fail("initial estimate does not match the HR geometry");
+    CheckGeometry(initial_estimate, "initial estimate does not match the HR geometry");
     srmap_irls_options o;
     srmap_irls_options_default(&o);
     o.max_num_solver_iterations = solver_options_.max_num_solver_iterations;
@@ -239,8 +230,7 @@ class IRLSMapSolver : public MapSolver {
   // start, cost at the result, passes, status.
   AffineMotionSequence RefineMotion(const ImageData& estimate, const MotionRefinementOptions& options = MotionRefinementOptions(),
                                     std::vector<double>* quality = nullptr) {
-    if (estimate.GetNumChannels() != GetNumChannels() || estimate.GetImageSize() != GetImageSize())
-      srmap_host::Fail("estimate does not match the HR geometry");
+    CheckGeometry(estimate, "estimate does not match the HR geometry");
     srmap_motion_refinement_options o;
     srmap_motion_refinement_options_default(&o);
     o.dof = options.dof;
@@ -267,18 +257,11 @@ class IRLSMapSolver : public MapSolver {
   // solver's blur (later solves and ComputeAllTerms use them).  quality (optional): E at the kernel in force, E at the fit,
   // smallest / largest pivot, status (3: no texture -- the kernel stays and is returned).
   BlurKernel FitBlur(const ImageData& hr, const BlurFitOptions& options = BlurFitOptions(), std::vector<double>* quality = nullptr) {
-    if (hr.GetNumChannels() != GetNumChannels() || hr.GetImageSize() != GetImageSize())
-      srmap_host::Fail("the high-resolution image does not match the HR geometry");
-    srmap_blur_fit_options o;
-    srmap_blur_fit_options_default(&o);
-    o.ksize = options.ksize;
-    o.sum_to_one = options.sum_to_one ? 1 : 0;
-    o.ridge = options.ridge;
-    o.apply = 1;
-    int ksize = options.ksize;
-    if (ksize == 0) srmap_host::Check(srmap_problem_get_blur_kernel(problem_.get(), &ksize, nullptr), "srmap_problem_get_blur_kernel");
+    CheckGeometry(hr, "the high-resolution image does not match the HR geometry");
+    int ksize = 0;
+    const srmap_blur_fit_options o = BlurFit(options, &ksize);
     const std::vector<double> x = hr.ToPlanar();
-    std::vector<double> taps(static_cast<size_t>(ksize > 0 ? ksize : 1) * (ksize > 0 ? ksize : 1)), q(5);
+    std::vector<double> taps(TapsOf(ksize)), q(5);
     srmap_host::Check(srmap_fit_blur(problem_.get(), x.data(), &o, taps.data(), q.data(), nullptr), "srmap_fit_blur");
     if (IsVerbose())
       std::cout << "Blur fit (" << ksize << " x " << ksize << "): cost " << q[0] << " -> " << q[1] << ", pivots " << q[2] << " ... " << q[3]
@@ -290,8 +273,8 @@ class IRLSMapSolver : public MapSolver {
   // for later solves, fits and ComputeAllTerms.  The entries must fit the solver's frames and channels.
   void SetBlurBank(const BlurKernelBank& bank) {
     if (bank.Empty()) srmap_host::Fail("SetBlurBank: the blur bank is empty");
-    const int want = bank.GetMode() == SRMAP_BLUR_PER_FRAME ? GetNumImages() : bank.GetMode() == SRMAP_BLUR_PER_CHANNEL ? GetNumChannels() : GetNumImages() * GetNumChannels();
-    if (bank.GetNumEntries() != want) srmap_host::Fail("SetBlurBank: the number of entries does not fit the solver's frames and channels");
+    if (static_cast<size_t>(bank.GetNumEntries()) != srmap_host::BankEntryCount(bank.GetMode(), GetNumImages(), GetNumChannels()))
+      srmap_host::Fail("SetBlurBank: the number of entries does not fit the solver's frames and channels");
     srmap_host::Check(srmap_problem_set_blur_bank(problem_.get(), bank.GetMode(), bank.GetSize(), bank.GetTaps().data()), "srmap_problem_set_blur_bank");
   }
   // Calibration fit of a blur-kernel bank (srmap_fit_blur_bank; not in the reference): FitBlur's fit, separately over the
@@ -299,21 +282,13 @@ class IRLSMapSolver : public MapSolver {
   // high-resolution image `hr`, INSTALLED as the solver's blur.  quality (optional): 5 numbers per entry, FitBlur's (status
   // 3: the entry is degenerate and keeps its kernel).  Like FitBlur a calibration fit: blind alternation is not offered.
   BlurKernelBank FitBlurBank(const ImageData& hr, const int mode, const BlurFitOptions& options = BlurFitOptions(), std::vector<double>* quality = nullptr) {
-    if (hr.GetNumChannels() != GetNumChannels() || hr.GetImageSize() != GetImageSize())
-      srmap_host::Fail("the high-resolution image does not match the HR geometry");
+    CheckGeometry(hr, "the high-resolution image does not match the HR geometry");
     if (mode < SRMAP_BLUR_PER_FRAME || mode > SRMAP_BLUR_PER_FRAME_CHANNEL) srmap_host::Fail("FitBlurBank: the mode is 1, 2 or 3");
-    srmap_blur_fit_options o;
-    srmap_blur_fit_options_default(&o);
-    o.ksize = options.ksize;
-    o.sum_to_one = options.sum_to_one ? 1 : 0;
-    o.ridge = options.ridge;
-    o.apply = 1;
-    int ksize = options.ksize;
-    if (ksize == 0) srmap_host::Check(srmap_problem_get_blur_kernel(problem_.get(), &ksize, nullptr), "srmap_problem_get_blur_kernel");
-    const int entries = mode == SRMAP_BLUR_PER_FRAME ? GetNumImages() : mode == SRMAP_BLUR_PER_CHANNEL ? GetNumChannels() : GetNumImages() * GetNumChannels();
+    int ksize = 0;
+    const srmap_blur_fit_options o = BlurFit(options, &ksize);
+    const int entries = static_cast<int>(srmap_host::BankEntryCount(mode, GetNumImages(), GetNumChannels()));
     const std::vector<double> x = hr.ToPlanar();
-    const size_t bb = static_cast<size_t>(ksize > 0 ? ksize : 1) * (ksize > 0 ? ksize : 1);
-    std::vector<double> taps(bb * entries), q(5 * static_cast<size_t>(entries));
+    std::vector<double> taps(TapsOf(ksize) * entries), q(5 * static_cast<size_t>(entries));
     srmap_host::Check(srmap_fit_blur_bank(problem_.get(), x.data(), mode, &o, taps.data(), q.data(), nullptr), "srmap_fit_blur_bank");
     if (IsVerbose())
       for (int e = 0; e < entries; ++e)
@@ -359,8 +334,7 @@ class IRLSMapSolver : public MapSolver {
   // frame -- cost at the parameters in force, cost at the result, sum of the weights, status.
   PhotometricSequence FitPhotometric(const ImageData& estimate, const PhotometricFitOptions& options = PhotometricFitOptions(),
                                      std::vector<double>* quality = nullptr) {
-    if (estimate.GetNumChannels() != GetNumChannels() || estimate.GetImageSize() != GetImageSize())
-      srmap_host::Fail("estimate does not match the HR geometry");
+    CheckGeometry(estimate, "estimate does not match the HR geometry");
     srmap_photometric_fit_options o;
     srmap_photometric_fit_options_default(&o);
     o.model = options.model;
@@ -409,9 +383,7 @@ class IRLSMapSolver : public MapSolver {
   // The data weights, one planar [C][h][w] block per observation ([K][C][h][w]): after a Huber solve the outlier map (the
   // pixels the solve down-weighted); all ones for a least-squares solve.  Not in the reference.
   std::vector<double> GetDataWeights() const {
-    int lw = 0, lh = 0;
-    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
-    std::vector<double> w(static_cast<size_t>(GetNumImages()) * GetNumChannels() * lw * lh);
+    std::vector<double> w(static_cast<size_t>(GetNumImages()) * GetNumChannels() * LrPlane());
     srmap_host::Check(srmap_get_data_weights(problem_.get(), w.data()), "srmap_get_data_weights");
     return w;
   }
@@ -420,15 +392,9 @@ class IRLSMapSolver : public MapSolver {
   // Not in the reference.  A Huber solve owns the weight buffer and resets it (include/srmap.h): masks act on
   // least-squares solves only.
   void MultiplyDataWeights(const std::vector<double>& masks) {
-    int lw = 0, lh = 0;
-    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
-    const size_t plane = static_cast<size_t>(lw) * lh, channels = static_cast<size_t>(GetNumChannels());
-    if (masks.size() != static_cast<size_t>(GetNumImages()) * plane)
-      srmap_host::Fail("data weight masks: one [h][w] plane per observation at the low-resolution size is needed");
+    const std::vector<double> m = BroadcastMasks(masks, "data weight masks: one [h][w] plane per observation at the low-resolution size is needed");
     std::vector<double> w = GetDataWeights();
-    for (size_t k = 0; k < static_cast<size_t>(GetNumImages()); ++k)
-      for (size_t c = 0; c < channels; ++c)
-        for (size_t i = 0; i < plane; ++i) w[(k * channels + c) * plane + i] *= masks[k * plane + i];
+    for (size_t i = 0; i < w.size(); ++i) w[i] *= m[i];
     srmap_host::Check(srmap_set_data_weights(problem_.get(), w.data()), "srmap_set_data_weights");
   }
   // Installs per-observation masks [K][h][w] at LR resolution, broadcast over the channels as MultiplyDataWeights does, as
@@ -440,24 +406,15 @@ class IRLSMapSolver : public MapSolver {
       srmap_host::Check(srmap_set_data_prior(problem_.get(), nullptr), "srmap_set_data_prior");
       return;
     }
-    int lw = 0, lh = 0;
-    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
-    const size_t plane = static_cast<size_t>(lw) * lh, channels = static_cast<size_t>(GetNumChannels());
-    if (masks.size() != static_cast<size_t>(GetNumImages()) * plane)
-      srmap_host::Fail("data prior masks: one [h][w] plane per observation at the low-resolution size is needed");
-    std::vector<double> m(static_cast<size_t>(GetNumImages()) * channels * plane);
-    for (size_t k = 0; k < static_cast<size_t>(GetNumImages()); ++k)
-      for (size_t c = 0; c < channels; ++c)
-        for (size_t i = 0; i < plane; ++i) m[(k * channels + c) * plane + i] = masks[k * plane + i];
+    const std::vector<double> m = BroadcastMasks(masks, "data prior masks: one [h][w] plane per observation at the low-resolution size is needed");
     srmap_host::Check(srmap_set_data_prior(problem_.get(), m.data()), "srmap_set_data_prior");
   }
   // The prior in force, [K][C][h][w]; empty when none is set.  Not in the reference.
   std::vector<double> GetDataPrior() const {
-    int set = 0, lw = 0, lh = 0;
+    int set = 0;
     srmap_host::Check(srmap_get_data_prior(problem_.get(), nullptr, &set), "srmap_get_data_prior");
     if (!set) return std::vector<double>();
-    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
-    std::vector<double> m(static_cast<size_t>(GetNumImages()) * GetNumChannels() * lw * lh);
+    std::vector<double> m(static_cast<size_t>(GetNumImages()) * GetNumChannels() * LrPlane());
     srmap_host::Check(srmap_get_data_prior(problem_.get(), m.data(), &set), "srmap_get_data_prior");
     return m;
   }
@@ -474,6 +431,38 @@ class IRLSMapSolver : public MapSolver {
   }
 
  private:
+  void CheckGeometry(const ImageData& image, const char* message) const {
+    if (image.GetNumChannels() != GetNumChannels() || image.GetImageSize() != GetImageSize()) srmap_host::Fail(message);
+  }
+  // BlurFitOptions as the library takes them, applied; *ksize: the size of the fit (ksize 0: that of the kernel in force)
+  srmap_blur_fit_options BlurFit(const BlurFitOptions& options, int* ksize) const {
+    srmap_blur_fit_options o;
+    srmap_blur_fit_options_default(&o);
+    o.ksize = options.ksize;
+    o.sum_to_one = options.sum_to_one ? 1 : 0;
+    o.ridge = options.ridge;
+    o.apply = 1;
+    *ksize = options.ksize;
+    if (*ksize == 0) srmap_host::Check(srmap_problem_get_blur_kernel(problem_.get(), ksize, nullptr), "srmap_problem_get_blur_kernel");
+    return o;
+  }
+  static size_t TapsOf(const int ksize) { return static_cast<size_t>(ksize > 0 ? ksize : 1) * (ksize > 0 ? ksize : 1); }
+  // pixels of one low-resolution plane
+  size_t LrPlane() const {
+    int lw = 0, lh = 0;
+    srmap_host::Check(srmap_problem_lr_size(problem_.get(), &lw, &lh), "srmap_problem_lr_size");
+    return static_cast<size_t>(lw) * lh;
+  }
+  // [K][h][w] masks at LR resolution as [K][C][h][w]: every channel of an observation gets its mask
+  std::vector<double> BroadcastMasks(const std::vector<double>& masks, const char* message) const {
+    const size_t plane = LrPlane(), channels = static_cast<size_t>(GetNumChannels());
+    if (masks.size() != static_cast<size_t>(GetNumImages()) * plane) srmap_host::Fail(message);
+    std::vector<double> m(static_cast<size_t>(GetNumImages()) * channels * plane);
+    for (size_t k = 0; k < static_cast<size_t>(GetNumImages()); ++k)
+      for (size_t c = 0; c < channels; ++c)
+        for (size_t i = 0; i < plane; ++i) m[(k * channels + c) * plane + i] = masks[k * plane + i];
+    return m;
+  }
   const IRLSMapSolverOptions solver_options_;
   srmap_solve_report report_ = {};
 };

@@ -20,6 +20,18 @@
 
 namespace super_resolution {
 
+namespace srmap_host {
+// One term of `problem` at x: returns its cost and ACCUMULATES its gradient of n numbers into `gradient` (nullptr: cost only).
+inline double EvalTerm(srmap_problem* problem, const unsigned term, const double* x, const size_t n, double* gradient) {
+  double cost = 0;
+  std::vector<double> g(gradient ? n : 0);
+  Check(srmap_eval(problem, term, x, &cost, gradient ? g.data() : nullptr), "srmap_eval");
+  if (gradient)
+    for (size_t i = 0; i < n; ++i) gradient[i] += g[i];
+  return cost;
+}
+}  // namespace srmap_host
+
 class ObjectiveTerm {
  public:
   virtual ~ObjectiveTerm() = default;
@@ -59,14 +71,8 @@ class ObjectiveDataTerm : public ObjectiveTerm {
     if (observations.empty()) srmap_host::Fail("Cannot super-resolve with 0 low-res images.");
     if (channel_start < 0 || channel_end <= channel_start || channel_end > observations[0].GetNumChannels())
       srmap_host::Fail("ObjectiveDataTerm: invalid channel range");
-    srmap_host::ChainParams chain;
-    if (!image_model.Canonical(&chain)) srmap_host::Fail("ObjectiveDataTerm needs the [Motion][Blur]Downsampling operator chain");
+    problem_ = srmap_host::MakeSolverProblem(image_model, observations.size(), image_size, num_channels_, "ObjectiveDataTerm");
     const int s = image_model.GetDownsamplingScale();
-    chain.frames = static_cast<int>(observations.size());
-    if (chain.HasMotion() && static_cast<size_t>(chain.NumMotions()) < observations.size())
-      srmap_host::Fail("fewer motion shifts than observations");
-    chain.TrimMotions(observations.size());
-    problem_ = srmap_host::MakeProblem(chain, image_size.width, image_size.height, num_channels_);
     const int lw = image_size.width / s, lh = image_size.height / s;
     std::vector<double> stack;
     stack.reserve(observations.size() * static_cast<size_t>(num_channels_) * lw * lh);
@@ -86,14 +92,7 @@ class ObjectiveDataTerm : public ObjectiveTerm {
   }
   double Compute(const double* estimated_image_data, double* gradient) const override {
     if (!estimated_image_data) srmap_host::Fail("CHECK_NOTNULL(estimated_image_data)");
-    double cost = 0;
-    const size_t n = static_cast<size_t>(image_size_.area()) * num_channels_;
-    std::vector<double> g(gradient ? n : 0);
-    srmap_host::Check(srmap_eval(problem_.get(), SRMAP_TERM_DATA, estimated_image_data, &cost, gradient ? g.data() : nullptr),
-                      "srmap_eval");
-    if (gradient)
-      for (size_t i = 0; i < n; ++i) gradient[i] += g[i];
-    return cost;
+    return srmap_host::EvalTerm(problem_.get(), SRMAP_TERM_DATA, estimated_image_data, static_cast<size_t>(image_size_.area()) * num_channels_, gradient);
   }
 
  private:
@@ -127,13 +126,7 @@ class ObjectiveIRLSRegularizationTerm : public ObjectiveTerm {
     const size_t n = static_cast<size_t>(image_size_.area()) * num_channels_;
     if (irls_weights_.size() < n) srmap_host::Fail("irls_weights too short");
     srmap_host::Check(srmap_set_irls_weights(problem_.get(), 0, irls_weights_.data()), "srmap_set_irls_weights");
-    double cost = 0;
-    std::vector<double> g(gradient ? n : 0);
-    srmap_host::Check(srmap_eval(problem_.get(), SRMAP_TERM_REG, estimated_image_data, &cost, gradient ? g.data() : nullptr),
-                      "srmap_eval");
-    if (gradient)
-      for (size_t i = 0; i < n; ++i) gradient[i] += g[i];
-    return cost;
+    return srmap_host::EvalTerm(problem_.get(), SRMAP_TERM_REG, estimated_image_data, n, gradient);
   }
 
  private:

@@ -45,6 +45,12 @@ struct ProblemDeleter {
 };
 using ProblemPtr = std::unique_ptr<srmap_problem, ProblemDeleter>;
 
+// Entries of a blur-kernel bank of `mode` (srmap_blur_bank_mode) over the given frames and channels.
+inline size_t BankEntryCount(const int mode, const int frames, const int channels) {
+  return mode == SRMAP_BLUR_PER_FRAME ? static_cast<size_t>(frames)
+         : mode == SRMAP_BLUR_PER_CHANNEL ? static_cast<size_t>(channels) : static_cast<size_t>(frames) * channels;
+}
+
 // Parameters of one operator chain  D(scale) . B(ksize, sigma | free-form taps) . M(shifts | matrices | displacement fields).
 struct ChainParams {
   int scale = 1;
@@ -96,7 +102,7 @@ inline ProblemPtr MakeProblem(const ChainParams& c, int width, int height, int c
     // a chain without motion and without a frame count takes its frames from a per-frame bank
     const int per_frame = c.blur_bank_mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? channels : 1;
     if (!c.HasMotion() && c.frames <= 1 && c.BankPerFrame()) d.frames = static_cast<int>(c.BankEntries()) / per_frame;
-    const size_t want = c.blur_bank_mode == SRMAP_BLUR_PER_CHANNEL ? static_cast<size_t>(channels) : static_cast<size_t>(d.frames) * per_frame;
+    const size_t want = BankEntryCount(c.blur_bank_mode, d.frames, channels);
     if (c.BankEntries() != want)
       Fail(("the blur bank holds " + std::to_string(c.BankEntries()) + " entries, the model has " + std::to_string(d.frames) + " frames and " +
             std::to_string(channels) + " channels: its mode " + std::to_string(c.blur_bank_mode) + " needs " + std::to_string(want)).c_str());
