@@ -359,6 +359,39 @@ int srmap_set_data_prior(srmap_problem* p, const double* m_host);
 int srmap_set_data_prior_device(srmap_problem* p, const void* m_dev, void* hip_stream);
 /* is_set: 1 while a prior is set; m_host (optional, [K][C][h][w] doubles) receives it (ones if none is set). */
 int srmap_get_data_prior(srmap_problem* p, double* m_host, int* is_set);
+/* The residual scale and the automatic Huber delta (no reference counterpart).  The scale of a set of
+ * residuals is 1.4826 * the LOWER MEDIAN of |r|: the order statistic of 0-based rank (n - 1) / 2 among the n counted
+ * observations -- an element of the input, never an average, found by an exact radix select on the device, so it does
+ * not depend on any order of summation or arrival.  An observation counts, under an L2 loss, when its effective weight is
+ * > 0 (all count when no weights are set) and, under a HUBER loss, when its prior is > 0 (all count without a prior: the
+ * Huber weights themselves are never zero).  A selection with n = 0 has scale 0 and count 0.  A NaN residual orders above
+ * +inf by its bits; that is not an error.
+ *
+ * srmap_problem_set_huber_scale: where a Huber step takes its delta from.  SRMAP_HUBER_DELTA_FIXED, the default of every
+ * problem: srmap_problem_set_data_loss's huber_delta, today's behaviour bit for bit.  SRMAP_HUBER_DELTA_MAD: every
+ * re-weighting (the solver's and srmap_update_data_weights_device) uses
+ * delta = max(tuning * 1.4826 * median|r|, min_delta), the median over ALL counted observations of the step's own
+ * unweighted residuals (of the step's channel under split_channels), formed on the device between the residual pass and
+ * the weight pass; srmap_problem_set_data_loss's huber_delta is still checked and is unused.  tuning must be finite and
+ * > 0 (1.345 is the usual value: 95 % efficiency on normal residuals), min_delta finite and > 0: the floor keeps a perfect
+ * fit from producing delta = 0 (1e-4 suits observations in 0...1).  An unknown mode or a bad value: SRMAP_EINVAL (values
+ * are not checked for FIXED).  The mode persists across the loss, weight, prior, motion, blur and photometric calls and
+ * is read under a HUBER loss only.  One scale over all frames drives delta on purpose: a scale per frame would grant a
+ * misregistered frame a large delta of its own (README, "Residual scale"). */
+typedef enum { SRMAP_HUBER_DELTA_FIXED = 0, SRMAP_HUBER_DELTA_MAD = 1 } srmap_huber_delta_mode;
+int srmap_problem_set_huber_scale(srmap_problem* p, int mode /* srmap_huber_delta_mode */, double tuning, double min_delta);
+/* The delta, the scales ([0] over all frames, [1 + k] of frame k) and the counts of the last Huber step in the MAD mode
+ * (zeros before the first); waits for that step through an event recorded behind it, so the step's stream need not
+ * exist any more.  In the FIXED mode: the fixed delta and zeros.  Every output is optional. */
+int srmap_problem_get_huber_delta(srmap_problem* p, int* mode, double* delta, double* scales /* 1 + K, optional */,
+                                  double* counts /* 1 + K, optional */);
+/* The diagnostic on its own, under any loss and any model state: scales[0] = 1.4826 * median|A x - y~| over all counted
+ * observations, scales[1 + k] the same of frame k (a frame that fits worse than the others -- misregistered, wrongly
+ * exposed -- stands out), counts the numbers of counted observations.  y~: what every kernel reads, the normalised frames
+ * under the photometric model.  x_host: [C][H][W] doubles; the device form takes the problem dtype, read on hip_stream
+ * (NULL = the context's).  Complete on return.  Without observations: SRMAP_EINVAL. */
+int srmap_residual_scale(srmap_problem* p, const double* x_host, double* scales /* 1 + K */, double* counts /* 1 + K, optional */);
+int srmap_residual_scale_device(srmap_problem* p, const void* x_dev, void* hip_stream, double* scales, double* counts);
 
 /* ------------------------------------------------------- operators (host) */
 /* ImageModel::ApplyToImage(ImageData*, index) image_model.cpp:86-91:

@@ -28,12 +28,18 @@ __device__ __forceinline__ T huber_weight(T r, T delta) {
 
 // PRIOR: a third stream m, indexed like w (the persistent prior of srmap_set_data_prior): w = m .* huber(r), the product
 // rounded once in T.  The instance without it reads nothing of m.
-template <typename T, bool VEC, bool PRIOR = false>
+// DELTA_DEV: delta_arg is a device double -- the record of the step's residual scale (residual_scale.hip), written earlier
+// on the same stream -- rounded to T as the host's (T)delta is; the instances without it take the value itself.
+template <typename T, bool VEC, bool PRIOR = false, bool DELTA_DEV = false>
 __global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, T* __restrict__ w, size_t rowlen,
-                                                      size_t r_stride, size_t w_stride, T delta,
+                                                      size_t r_stride, size_t w_stride,
+                                                      std::conditional_t<DELTA_DEV, const double*, T> delta_arg,
                                                       const T* __restrict__ m = nullptr) {
   constexpr int V = 16 / (int)sizeof(T);
   typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
+  T delta;
+  if constexpr (DELTA_DEV) delta = (T)*delta_arg;
+  else delta = delta_arg;
   const T* rr = r + (size_t)blockIdx.y * r_stride;
   T* ww = w + (size_t)blockIdx.y * w_stride;
   const T* mm = PRIOR ? m + (size_t)blockIdx.y * w_stride : nullptr;
@@ -63,10 +69,11 @@ __global__ __launch_bounds__(256) void k_huber_weights(const T* __restrict__ r, 
 }
 
 // r: `rows` runs of `rowlen` elements, r_stride apart; w likewise, w_stride apart, starting at w (a channel view of
-// [K][C][h][w]).  prior != nullptr (indexed like w): the instance with the prior as a third stream
+// [K][C][h][w]).  prior != nullptr (indexed like w): the instance with the prior as a third stream.  delta_dev != nullptr:
+// the instances that read delta from there (a device double), `delta` unused
 template <typename T>
 int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t rowlen, size_t r_stride, size_t w_stride,
-                         double delta, hipStream_t st, const T* prior) {
+                         double delta, hipStream_t st, const T* prior, const double* delta_dev = nullptr) {
   constexpr size_t V = 16 / sizeof(T);
   if (rows == 0 || rowlen == 0) return SRMAP_OK;
   if (rows > 1 && r_stride == rowlen && w_stride == rowlen) { rowlen *= rows; rows = 1; }  // one contiguous run
@@ -76,7 +83,16 @@ int launch_huber_weights(srmap_problem* p, const T* r, T* w, size_t rows, size_t
   const size_t groups = (rowlen + V * 256 - 1) / (V * 256);
   const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
   dim3 grid((unsigned)std::max<size_t>(1, std::min(groups, (cap + rows - 1) / rows)), (unsigned)rows);
-  if (prior) {
+  if (delta_dev) {  // the MAD scale mode: delta is on the device
+    if (prior) {
+      if (vec) hipLaunchKernelGGL((k_huber_weights<T, true, true, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, delta_dev, prior);
+      else hipLaunchKernelGGL((k_huber_weights<T, false, true, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, delta_dev, prior);
+    } else if (vec) {
+      hipLaunchKernelGGL((k_huber_weights<T, true, false, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, delta_dev, (const T*)nullptr);
+    } else {
+      hipLaunchKernelGGL((k_huber_weights<T, false, false, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, delta_dev, (const T*)nullptr);
+    }
+  } else if (prior) {
     if (vec) hipLaunchKernelGGL((k_huber_weights<T, true, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
     else hipLaunchKernelGGL((k_huber_weights<T, false, true>), grid, dim3(256), 0, st, r, w, rowlen, r_stride, w_stride, (T)delta, prior);
   } else if (vec) {
@@ -238,9 +254,16 @@ int DataWeights::huber_step(srmap_problem* p, int c0, int C, const void* x, hipS
     // d_resid: [K][geo.C][h][w], unweighted
     if (int r = launch_forward_residual<T>(p, geo, c0, (const T*)x, p->d_partials.as<double>(), st)) return r;
     const size_t nl = (size_t)geo.w * geo.h;
+    const T* prior = prior_ ? prior_.as<const T>() + (size_t)c0 * nl : nullptr;
+    const double* delta_dev = nullptr;
+    if (scale_mode_ == SRMAP_HUBER_DELTA_MAD) {  // delta from the scale of these residuals; what counts is the prior's support
+      if (int r = launch_residual_scale<T>(p, p->d_resid.as<const T>(), prior, (size_t)geo.C * nl, (size_t)p->geo.C * nl, 0, true,
+                                           tuning_, min_delta_, st))
+        return r;
+      delta_dev = residual_scale_record(p, 0);
+    }
     return launch_huber_weights<T>(p, p->d_resid.as<const T>(), eff_.as<T>() + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
-                                   (size_t)geo.C * nl, (size_t)p->geo.C * nl, delta_, st,
-                                   prior_ ? prior_.as<const T>() + (size_t)c0 * nl : nullptr);
+                                   (size_t)geo.C * nl, (size_t)p->geo.C * nl, delta_, st, prior, delta_dev);
   });
   if (rc) return rc;
   return state_end_write(p, st);  // asynchronous: evaluations on other streams wait for this event

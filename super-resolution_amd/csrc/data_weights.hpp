@@ -55,6 +55,11 @@ class DataWeights {
   bool robust() const { return eff_ || loss_ == SRMAP_DATA_LOSS_HUBER; }
   int loss() const { return loss_; }
   double delta() const { return delta_; }
+  // Where a Huber step takes its delta from (srmap_problem_set_huber_scale): SRMAP_HUBER_DELTA_FIXED -- delta() --, or
+  // SRMAP_HUBER_DELTA_MAD: max(tuning * 1.4826 median|r|, min_delta) of the step's own residuals, formed on the device
+  // (residual_scale.hip).  Read under a Huber loss only; no other setter touches it
+  int scale_mode() const { return scale_mode_; }
+  void set_scale(int mode, double tuning, double min_delta) { scale_mode_ = mode; tuning_ = tuning; min_delta_ = min_delta; }
 
   int set_user(srmap_problem* p, const WeightSource& src);
   int set_prior(srmap_problem* p, const WeightSource& src);
@@ -62,7 +67,8 @@ class DataWeights {
   // the start of a Huber solve on the channels [c0, c0 + C) (C = 0: all): eff <- the prior, or 1 without one; enqueued on st
   int reset(srmap_problem* p, int c0, int C, hipStream_t st);
   // Huber IRLS step on the channels [c0, c0 + C) (C = 0: all): eff <- prior .* huber(A x - y), enqueued on st
-  // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time)
+  // (srmap_update_data_weights_device with a view: split_channels solves re-weight one channel at a time).  In the MAD
+  // mode the select runs over the view's residuals between the two kernels and the weights read delta from its record
   int huber_step(srmap_problem* p, int c0, int C, const void* x, hipStream_t st);
 
  private:
@@ -71,6 +77,8 @@ class DataWeights {
   DevBuf eff_, user_, prior_;
   int loss_ = SRMAP_DATA_LOSS_L2;
   double delta_ = 0.0;
+  int scale_mode_ = SRMAP_HUBER_DELTA_FIXED;
+  double tuning_ = 0.0, min_delta_ = 0.0;
 };
 
 }  // namespace srmap

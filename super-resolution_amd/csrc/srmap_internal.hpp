@@ -191,6 +191,9 @@ struct srmap_problem {
   srmap::DevBuf d_resid;          // [K][C][h][w] dtype scratch
   // per-observation weights of the data term, their prior and the loss: the states and who re-plans, data_weights.hpp
   srmap::DataWeights dw;
+  // the residual scale's select (residual_scale.hip), allocated on first use: the workgroups' histogram slabs, the K + 1
+  // selection states, and two records {delta, scales[1 + K], counts[1 + K]} (doubles): the last Huber step's, the diagnostic's
+  srmap::DevBuf d_sel_slabs, d_sel_state, d_sel_rec;
   srmap::DevBuf d_regvals;        // [C][H][W] dtype scratch
   srmap::DevBuf d_x;              // [C][H][W] staging for host-buffer entry points
   srmap::DevBuf d_g;
@@ -357,6 +360,16 @@ struct FitPass {
   bool reduce_and_fetch(int chunks, hipStream_t st) { return reduce_and_fetch(chunks, 1, 0, chunks, st); }
   const double* sums(int row) const { return h_sums.as<const double>() + (size_t)row * nsums; }
 };
+// ---- residual scale (residual_scale.hip) ----
+// The K + 1 lower medians of |r| over r = [K] runs of rowlen residuals (a channel view of d_resid), enqueued on st: an
+// element counts where mask (nullptr: everywhere; indexed like the data weights, frames m_stride apart) is > 0.  Leaves
+// {delta, 1.4826 median over all frames and per frame, the counts} in the problem's record `slot` (0: the Huber step's,
+// 1: the diagnostic's); mad: delta = max(tuning * scales[0], min_delta), else 0.  Nothing returns to the host
+template <typename T>
+int launch_residual_scale(srmap_problem* p, const T* r, const T* mask, size_t rowlen, size_t m_stride, int slot, bool mad,
+                          double tuning, double min_delta, hipStream_t st);
+size_t residual_scale_record_doubles(int K);
+double* residual_scale_record(srmap_problem* p, int slot);  // device; nullptr before the first select
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
 int photometric_normalise(srmap_problem* p, hipStream_t st);

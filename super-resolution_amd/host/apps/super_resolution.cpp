@@ -5,7 +5,8 @@
 // truth, save.  Same flag names and defaults.  --solver=cg|lbfgs selects the
 // least-squares solver as the reference does (super_resolution.cpp:134-141; any
 // other value warns and runs CG).  --data_loss=l2|huber and --huber_delta are NOT
-// reference flags: the robust data term of include/srmap.h.  Nor is --affine_motion_path: per-frame affine motion.  Nor is
+// reference flags: the robust data term of include/srmap.h; nor are --huber_scale=fixed|mad / --huber_tuning /
+// --huber_min_delta (the Huber threshold from the residual scale) and --print_residual_scale.  Nor is --affine_motion_path: per-frame affine motion.  Nor is
 // --flow_motion_path: a dense displacement field per frame (srmap_problem_set_flow).  Nor are
 // --registration=translational|affine|flow (the solver's motion estimated from the LR frames on the GPU; flow: dense
 // displacement fields and their validity masks as data weights, srmap_register_flow), --save_flow_path and
@@ -52,6 +53,11 @@ const char kUsage[] =
       "  [--interpolate_color] [--solve_in_pca_space] [--num_pca_components=0] [--pca_retained_variance=0]\n"
       "  [--evaluators=psnr,ssim] [--result_path=<path>] [--verbose]\n"
       "  not reference flags: [--data_loss=l2|huber] [--huber_delta=0.02] (robust data term, pixel units 0..1)\n"
+      "                       [--huber_scale=fixed|mad] [--huber_tuning=1.345] [--huber_min_delta=1e-4] (mad: the Huber threshold\n"
+      "                       is max(tuning * 1.4826 * median|residual|, min_delta) over all frames, re-estimated at every\n"
+      "                       re-weighting, instead of --huber_delta)\n"
+      "                       [--print_residual_scale] (1.4826 * median|residual| of the result over all frames and per frame:\n"
+      "                       a frame that stands out fits badly)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
       "                       [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
@@ -113,6 +119,10 @@ struct Options {
   // solver's pixel units (ImageData scales 8-bit input to 0..1)
   std::string data_loss;
   double huber_delta;
+  // not reference flags: the Huber threshold estimated from the residuals (srmap_problem_set_huber_scale; tuning and floor go
+  // straight into `solver`), and the per-frame residual scales of the final estimate (srmap_residual_scale)
+  std::string huber_scale;
+  bool print_residual_scale;
   bool interpolate_color, solve_in_pca_space;
   int num_pca_components;
   double pca_retained_variance;
@@ -173,6 +183,10 @@ Options ParseFlags(int argc, char** argv) {
   o.solver_name = flags.Str("solver", "cg");
   o.data_loss = flags.Str("data_loss", "l2");
   o.huber_delta = flags.Double("huber_delta", 0.02);
+  o.huber_scale = flags.Str("huber_scale", "fixed");
+  o.solver.huber_tuning = flags.Double("huber_tuning", 1.345);
+  o.solver.huber_min_delta = flags.Double("huber_min_delta", 1.0e-4);
+  o.print_residual_scale = flags.Bool("print_residual_scale", false);
   o.interpolate_color = flags.Bool("interpolate_color", false);
   o.solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
   o.num_pca_components = flags.Int("num_pca_components", 0);
@@ -275,6 +289,9 @@ void ChooseSolverAndLoss(Options* o) {
   } else if (o->data_loss != "l2") {
     std::fprintf(stderr, "WARNING: Invalid data_loss flag. Using the least-squares (l2) data term.\n");
   }
+  // likewise: "mad" estimates the Huber threshold from the residuals, anything but "fixed" warns and keeps --huber_delta
+  if (o->huber_scale == "mad") o->solver.huber_scale = MAD_HUBER_SCALE;
+  else if (o->huber_scale != "fixed") std::fprintf(stderr, "WARNING: Invalid huber_scale flag. Using the fixed --huber_delta.\n");
 }
 
 int NoLowResImages() {
@@ -467,6 +484,13 @@ int Solve(const Options& o, const Frames& f, IRLSMapSolver* solver, ImageData* r
     return app::CannotWrite(o.save_photometric_path);
   const std::chrono::duration<double> elapsed = std::chrono::steady_clock::now() - start_time;
   std::printf("Done! Finished in %g seconds.\n", elapsed.count());
+  if (o.solver.data_loss == HUBER_DATA_LOSS && o.solver.huber_scale == MAD_HUBER_SCALE)
+    std::printf("Huber delta of the last re-weighting: %.9g\n", solver->HuberDelta());
+  if (o.print_residual_scale) {  // of the final estimate, in the space the solve ran in: a frame that stands out fits badly
+    const std::vector<double> scales = solver->ResidualScale(*result);
+    std::printf("Residual scale (1.4826 median|r|) over all frames: %.9g\n", scales[0]);
+    for (size_t k = 1; k < scales.size(); ++k) std::printf("  frame %zu: %.9g\n", k - 1, scales[k]);
+  }
   if (o.interpolate_color) {
     result->InterpolateColorFrom(f.initial_estimate);
     result->ChangeColorSpace(SPECTRAL_MODE_COLOR_BGR);

@@ -33,6 +33,7 @@ enum LeastSquaresSolver { CG_SOLVER, LBFGS_SOLVER };
 // Loss of the data term.  Not in the reference (its data term is plain least squares): HUBER_DATA_LOSS re-weights the
 // observations between the inner solves as the regulariser is re-weighted (srmap_problem_set_data_loss, include/srmap.h).
 enum DataLoss { L2_DATA_LOSS, HUBER_DATA_LOSS };
+enum HuberScale { FIXED_HUBER_SCALE, MAD_HUBER_SCALE };
 
 struct MapSolverOptions {
   MapSolverOptions() {}
@@ -75,6 +76,11 @@ struct IRLSMapSolverOptions : public MapSolverOptions {
   // not in the reference: robust data term (default: the reference's least squares)
   DataLoss data_loss = L2_DATA_LOSS;
   double huber_delta = 0.02;  // in the units of the observations; read for HUBER_DATA_LOSS only
+  // where a Huber solve takes its delta from (srmap_problem_set_huber_scale): huber_delta above, or -- MAD_HUBER_SCALE --
+  // max(huber_tuning * 1.4826 median|r|, huber_min_delta) of the residuals over all frames, re-estimated at every re-weighting
+  HuberScale huber_scale = FIXED_HUBER_SCALE;
+  double huber_tuning = 1.345;
+  double huber_min_delta = 1.0e-4;
 };
 
 // Options of IRLSMapSolver::RefineMotion (srmap_motion_refinement_options, include/srmap.h).  Not in the reference.
@@ -212,6 +218,12 @@ class IRLSMapSolver : public MapSolver {
                                                                                                : -1,
                                                   solver_options_.huber_delta),
                       "srmap_problem_set_data_loss");
+    srmap_host::Check(srmap_problem_set_huber_scale(problem_.get(),
+                                                    solver_options_.huber_scale == MAD_HUBER_SCALE     ? SRMAP_HUBER_DELTA_MAD
+                                                    : solver_options_.huber_scale == FIXED_HUBER_SCALE ? SRMAP_HUBER_DELTA_FIXED
+                                                                                                       : -1,
+                                                    solver_options_.huber_tuning, solver_options_.huber_min_delta),
+                      "srmap_problem_set_huber_scale");
     const std::vector<double> x0 = initial_estimate.ToPlanar();
     std::vector<double> x(x0.size());
     srmap_host::Check(srmap_solve(problem_.get(), &o, x0.data(), x.data(), &report_), "srmap_solve");
@@ -386,6 +398,27 @@ class IRLSMapSolver : public MapSolver {
     std::vector<double> w(static_cast<size_t>(GetNumImages()) * GetNumChannels() * LrPlane());
     srmap_host::Check(srmap_get_data_weights(problem_.get(), w.data()), "srmap_get_data_weights");
     return w;
+  }
+  // The residual scale of `estimate` (srmap_residual_scale; not in the reference): 1 + K numbers, [0] 1.4826 x the median of
+  // |A x - y| over all counted observations, [1 + k] the same of frame k alone -- a frame that fits worse than the others
+  // stands out.  counts (optional): the 1 + K numbers of counted observations.
+  std::vector<double> ResidualScale(const ImageData& estimate, std::vector<double>* counts = nullptr) {
+    CheckGeometry(estimate, "estimate does not match the HR geometry");
+    const std::vector<double> x = estimate.ToPlanar();
+    std::vector<double> scales(1 + static_cast<size_t>(GetNumImages())), n(scales.size());
+    srmap_host::Check(srmap_residual_scale(problem_.get(), x.data(), scales.data(), n.data()), "srmap_residual_scale");
+    if (counts) *counts = n;
+    return scales;
+  }
+  // The delta of the last Huber re-weighting (srmap_problem_get_huber_delta): the fixed one, or the last estimate of the
+  // MAD_HUBER_SCALE mode; scales / counts (optional): the 1 + K scales and counts it was formed from (zeros in the fixed mode).
+  double HuberDelta(std::vector<double>* scales = nullptr, std::vector<double>* counts = nullptr) const {
+    std::vector<double> s(1 + static_cast<size_t>(GetNumImages())), n(s.size());
+    double delta = 0.0;
+    srmap_host::Check(srmap_problem_get_huber_delta(problem_.get(), nullptr, &delta, s.data(), n.data()), "srmap_problem_get_huber_delta");
+    if (scales) *scales = s;
+    if (counts) *counts = n;
+    return delta;
   }
   // Multiplies per-observation masks [K][h][w] at LR resolution (registration::FlowRegistration's validity masks) into the
   // data weights, broadcast over the channels: the weights in force (the caller's, ones if none were set) times the mask.

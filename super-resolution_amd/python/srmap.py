@@ -19,6 +19,7 @@ TERM_DATA, TERM_REG, TERM_ALL = 1, 2, 3
 IMPL_AUTO, IMPL_DIRECT, IMPL_TILED = 0, 1, 2
 SOLVER_CG, SOLVER_LBFGS = 0, 1  # srmap_solver (MapSolverOptions::least_squares_solver)
 DATA_LOSS_L2, DATA_LOSS_HUBER = 0, 1  # srmap_data_loss
+HUBER_DELTA_FIXED, HUBER_DELTA_MAD = 0, 1  # srmap_huber_delta_mode
 
 c_double_p = C.POINTER(C.c_double)
 
@@ -136,6 +137,10 @@ _SIGNATURES = [
     ("srmap_set_data_prior", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_set_data_prior_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("srmap_get_data_prior", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
+    ("srmap_problem_set_huber_scale", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    ("srmap_problem_get_huber_delta", C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p]),
+    ("srmap_residual_scale", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    ("srmap_residual_scale_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p]),
     ("srmap_apply", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_apply_transpose", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_reg_values", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
@@ -663,6 +668,27 @@ class Problem:
     def update_data_weights_device(self, x_ptr, stream=None):
         """One Huber re-weighting step from the residuals at the device image x_ptr."""
         self.ctx.check(load().srmap_update_data_weights_device(self._h, C.c_void_p(x_ptr), C.c_void_p(stream or 0)))
+
+    def set_huber_scale(self, mode, tuning=1.345, min_delta=1e-4):
+        """HUBER_DELTA_FIXED (default: set_data_loss's delta) or HUBER_DELTA_MAD: every Huber re-weighting uses
+        delta = max(tuning * 1.4826 * median|r|, min_delta) of its own residuals over all frames."""
+        self.ctx.check(load().srmap_problem_set_huber_scale(self._h, mode, tuning, min_delta))
+
+    def huber_delta(self):
+        """(mode, delta, scales [1 + K], counts [1 + K]) of the last Huber step; the fixed delta and zeros in the FIXED mode."""
+        mode, delta = C.c_int(0), C.c_double(0.0)
+        scales, counts = np.zeros(1 + self.K), np.zeros(1 + self.K)
+        self.ctx.check(load().srmap_problem_get_huber_delta(self._h, C.byref(mode), C.byref(delta), scales.ctypes.data_as(c_double_p),
+                                                            counts.ctypes.data_as(c_double_p)))
+        return mode.value, delta.value, scales, counts
+
+    def residual_scale(self, x, stream=None):
+        """srmap_residual_scale: (scales [1 + K], counts [1 + K]) at the HR image x (a host array [C][H][W], or a device
+        tensor of the problem's dtype, read on `stream`): scales[0] = 1.4826 * the lower median of |A x - y| over all
+        counted observations, scales[1 + k] of frame k alone."""
+        scales, counts = np.zeros(1 + self.K), np.zeros(1 + self.K)
+        self._fit("srmap_residual_scale", x, stream, scales.ctypes.data_as(c_double_p), counts.ctypes.data_as(c_double_p))
+        return scales, counts
 
     def apply(self, hr, k):
         a, pa = _d(hr)
