@@ -207,6 +207,35 @@ int srmap_problem_set_flow(srmap_problem* p, const double* flow_host /* K x 2 x 
 int srmap_problem_set_flow_device(srmap_problem* p, const void* flow_dev /* problem dtype */, void* hip_stream);
 int srmap_problem_get_flow(srmap_problem* p, double* flow_out /* K x 2 x H x W, optional */, int* is_set);
 
+/* The displacement-field model with the field kept on a CONTROL LATTICE and interpolated in the kernels (no reference
+ * counterpart; csrc/kernels_flow.hip, csrc/sample_dev.hpp): the compact form of srmap_problem_set_flow,
+ * s^2 to step^2 times smaller, and exactly what srmap_register_flow's input-level estimate is.
+ *   lattice   step >= 1 HR pixels between nodes, lw x lh nodes per component; node (i, j) sits at HR pixel (i step, j step).
+ *             nodes: K x 2 x lh x lw doubles (x then y component), kept on the device as DOUBLES in both dtypes.
+ *   field     for the HR pixel Q = (x, y), in double, in this order, without fused operations:
+ *               cx = min(max((double)x / (double)step, 0), lw - 1);  xi = min(floor(cx), lw - 2);  fx = cx - xi  (cy, yi, fy likewise)
+ *               v  = (1 - fy) ((1 - fx) n[yi][xi] + fx n[yi][xi+1]) + fy ((1 - fx) n[yi+1][xi] + fx n[yi+1][xi+1])
+ *               u(Q) = (dtype) v
+ *             -- srmap_register_flow's output rule with the gain folded into the nodes.  Beyond the last node the field is
+ *             constant.  From u(Q) on everything is srmap_problem_set_flow's: the sample, the weights, the seed rule, the
+ *             5 x 5 window and the verified domain (checked on the interpolated values, with the same codes).  A lattice
+ *             problem evaluates BIT FOR BIT as a dense-flow problem given the expanded nodes, in both dtypes.
+ *   domain    1 <= step <= 1024; lw, lh >= 2; (lw - 1) step < W + step and (lh - 1) step < H + step; else SRMAP_EINVAL.
+ *             The registration's form is lw = w, lh = h, step = scale; the covering form lw = ceil((W - 1) / step) + 1.
+ *   memory    K*2*lw*lh*8 bytes of nodes plus the K*H*W*4 bytes of gather seeds (a dense field: K*2*H*W*sizeof(dtype)).
+ * Lattice, dense flow and affine motion are alternatives: setting one replaces the others, NULL (to any of the calls)
+ * restores the created motion, and on a refused lattice the problem keeps its motion.  While a lattice is set
+ * srmap_problem_get_flow reports is_set = 0.  The lattice persists across the calls a dense flow persists across, every
+ * call that honours a dense flow honours it, and every call that answers SRMAP_EUNSUPPORTED under a dense flow
+ * (SRMAP_IMPL_TILED, sharding over more than one rank, srmap_refine_motion, srmap_fit_blur, srmap_fit_blur_bank,
+ * srmap_fit_photometric) answers it under a lattice.  The _device form reads nodes_dev (doubles) on hip_stream (NULL = the
+ * context's) and returns when the lattice is validated and installed.  srmap_problem_get_flow_lattice: *step (0 = none),
+ * *lw, *lh, and the nodes in force when nodes_out is not NULL and a lattice is set. */
+int srmap_problem_set_flow_lattice(srmap_problem* p, int step, int lw, int lh,
+                                   const double* nodes_host /* K x 2 x lh x lw doubles; NULL restores */);
+int srmap_problem_set_flow_lattice_device(srmap_problem* p, int step, int lw, int lh, const double* nodes_dev, void* hip_stream);
+int srmap_problem_get_flow_lattice(srmap_problem* p, int* step, int* lw, int* lh, double* nodes_out /* optional */);
+
 /* Free-form blur kernel (no reference counterpart: BlurModule builds an isotropic Gaussian from (blur_radius, sigma) only,
  * blur_module.cpp:13-22).  taps: ksize x ksize doubles, row-major, the layout of the Gaussian the problem
  * builds itself.  The forward model CORRELATES with them, as filter2D does (blur_module.cpp:24-28):
@@ -620,6 +649,14 @@ int srmap_register_flow_device(srmap_ctx* ctx, int num_images, int width, int he
 int srmap_problem_register_flow(srmap_problem* p, int channel /* -1 = channel mean */,
                                 const srmap_flow_registration_options* options /* NULL = defaults */, int install_prior,
                                 double* quality_out /* optional, K x 3 */);
+/* The same registration -- plane rule, options, prior and errors -- that stops at the input level: the nodes s u are
+ * installed as a lattice with step = scale, lw = w, lh = h (srmap_problem_set_flow_lattice_device).  No HR resample, no
+ * rounding pass and no HR-sized buffer; quality [3i+2] comes from the nodes, (largest node difference along x + along y) /
+ * step, which equals the expanded field's figure to rounding.  At a scale that is a power of two the installed motion
+ * evaluates bit for bit as srmap_problem_register_flow's. */
+int srmap_problem_register_flow_lattice(srmap_problem* p, int channel /* -1 = channel mean */,
+                                        const srmap_flow_registration_options* options /* NULL = defaults */, int install_prior,
+                                        double* quality_out /* optional, K x 3 */);
 
 /* Joint motion refinement (no reference counterpart; csrc/motion_refinement.hip; it closes what DESIGN.md
  * 3.7 left out: a registration that honours the forward model and the data weights).  With an HR estimate x, every frame

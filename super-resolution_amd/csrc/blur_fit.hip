@@ -237,8 +237,9 @@ int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, 
   srmap_ctx* ctx = p->ctx;
   const Geometry& g = p->geo;
   const char* const what = mode ? "blur bank fit" : "blur fit";
-  if (p->flow)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
+  if (field_motion(p))
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for %s: not available while one is set (%s)",
+                     field_motion_name(p), field_motion_setter(p));
   srmap_blur_fit_options opt;
   if (int rc = options_in_force(ctx, options, srmap_blur_fit_options_default, kOptionsName, &opt)) return rc;
   const int ksize = opt.ksize == 0 ? g.b : opt.ksize;

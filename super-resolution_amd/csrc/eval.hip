@@ -54,8 +54,11 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
     SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, req.overlap.event, 0));
     req.overlap.fn = nullptr;
   }
-  if (p->impl == SRMAP_IMPL_TILED && !ztile)
+  if (p->impl == SRMAP_IMPL_TILED && !ztile) {
+    if (p->lat_step)
+      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover %s (%s)", field_motion_name(p), field_motion_setter(p));
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover this geometry");
+  }
   int nparts = 0;
   if (ztile) {
     rc = launch_eval_ztile<T>(p, req, out, geo, c0, terms, x, g, p->d_partials.as<double>(), &nparts, st);

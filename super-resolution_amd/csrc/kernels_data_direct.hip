@@ -4,7 +4,7 @@
 //   (a) the operator entry points (srmap_apply, srmap_apply_transpose), and
 //   (b) the fallback of srmap_eval when the tile kernels (kernels_ztile.hip) do not cover the geometry, and their
 //       cross-check.
-// They serve every motion kind (none, translation table, affine matrices, displacement field): the
+// They serve every motion kind (none, translation table, affine matrices, displacement field, dense or on a lattice): the
 // forward kernel is one template over the kind's sampler, the transpose k_gather_direct for a translation and
 // k_gather_sampled for the kinds that warp per pixel (MotionSampler, sample_dev.hpp).  Source coordinates of those are
 // double in both dtypes (an f32 coordinate at 2048 px carries 1e-4 px of error); the weights are the double products
@@ -24,8 +24,8 @@ namespace srmap {
 // frames [k0, k0+gridDim.z), optionally minus the observation, optionally with
 // the data-term cost partial s^2 * sum(res^2) (objective_data_term.cpp:29-50).
 // MOTION (compile time): how M_k is sampled (MotionSampler) -- kMotionTable (also a problem without motion: the identity
-// table), kMotionAffine, kMotionFlow.  The per-pixel kinds read their sources through the caches: per LR pixel b^2 x 4 taps
-// of x, and two field values per blur tap for a flow.
+// table), kMotionAffine, kMotionFlow, kMotionLattice.  The per-pixel kinds read their sources through the caches: per LR
+// pixel b^2 x 4 taps of x, and per blur tap two field values for a flow, two times four nodes for a lattice.
 // WEIGHTED (compile time; needs y): per-observation weights dw indexed like y -- out = w * res, partial s^2 * sum(w res^2).
 // blur_bank: the table of the block's (frame, absolute channel) -- block-uniform; the strides are 0 without a bank.
 template <typename T, int MOTION, bool WEIGHTED>
@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256) void k_forward_direct(
 static int motion_buffers_ok(srmap_problem* p, int kind) {
   if (kind == kMotionAffine && !p->d_affine) return set_error(p->ctx, SRMAP_EINVAL, "internal: no affine motion set");
   if (kind == kMotionFlow && (!p->d_flow || !p->d_flow_seed)) return set_error(p->ctx, SRMAP_EINVAL, "internal: no displacement field set");
+  if (kind == kMotionLattice && (!p->d_lattice || !p->d_flow_seed)) return set_error(p->ctx, SRMAP_EINVAL, "internal: no flow lattice set");
   return SRMAP_OK;
 }
 
@@ -131,7 +132,7 @@ int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const
   const double cost_scale = (double)g.s * (double)g.s;
   const MotionArgs<T> ma = motion_args<T>(p);
   const BlurStride bs = blur_stride(p);
-  const bool launched = dispatch_value<kMotionTable, kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
+  const bool launched = dispatch_value<kMotionTable, kMotionAffine, kMotionFlow, kMotionLattice>(kind, [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (dw != nullptr)
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, true>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(256) void k_gather_ring(const T* __restrict__ resid
 }
 
 // ---------------------------------------------------------------------------
-// The same transpose for a motion kind that warps per pixel (kMotionAffine, kMotionFlow), as the EXACT transpose of the
+// The same transpose for a motion kind that warps per pixel (kMotionAffine, kMotionFlow, kMotionLattice), as the EXACT transpose of the
 // forward kernel's matrix in gather form: g = (accumulate ? g : 0) + out_scale * sum_k M_k^T B^T D^T r_k at every HR pixel,
 // frames in increasing order, per frame the kWindow x kWindow candidates q of the kind in row-major order, each weight
 // recomputed by the forward kernel's expressions (MotionSampler::window / weight) -- the two kernels hold the same matrix
@@ -392,12 +393,12 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
   const int kind = motion_kind(p);
   if (p->blur_bank_mode != 0 && (ring > 0 || ringbuf != nullptr))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which a blur bank has none of");
-  if (kind == kMotionAffine || kind == kMotionFlow) {
+  if (kind == kMotionAffine || kind == kMotionFlow || kind == kMotionLattice) {
     if (ring > 0 || ringbuf != nullptr)
       return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which %s has none of",
-                       kind == kMotionFlow ? "a displacement field" : "an affine motion");
+                       kind == kMotionAffine ? "an affine motion" : field_motion_name(p));
     if (int rc = motion_buffers_ok(p, kind)) return rc;
-    if (!dispatch_value<kMotionAffine, kMotionFlow>(kind, [&](auto motion) {
+    if (!dispatch_value<kMotionAffine, kMotionFlow, kMotionLattice>(kind, [&](auto motion) {
           launch_gather_sampled<T, decltype(motion)::value>(p, geo, resid, g, k0, nk, out_scale, accumulate, st, obs_c0);
         }))
       return set_error(p->ctx, SRMAP_EINVAL, "internal: no sampled gather for motion kind %d", kind);

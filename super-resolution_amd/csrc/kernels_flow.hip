@@ -1,5 +1,6 @@
-// kernels_flow.hip -- the set-time side of the DENSE per-frame displacement field (srmap_problem_set_flow; no reference
-// counterpart: motion_module.cpp:18-51 warps by a translation only).  DESIGN.md 3.11.
+// kernels_flow.hip -- the set-time side of the per-frame displacement field, DENSE (srmap_problem_set_flow) or on a
+// CONTROL LATTICE (srmap_problem_set_flow_lattice); no reference counterpart: motion_module.cpp:18-51 warps by a
+// translation only.  DESIGN.md 3.11, 3.16.
 //
 // Frame k carries a field u_k = (ux, uy) on its HR-grid image, stored in the problem's dtype as [K][2][H][W].  The forward
 // warp samples x bilinearly at s = q + u_k(q) for every pixel q of the warped image (taps outside the image contribute 0:
@@ -15,6 +16,11 @@
 // the two kernels hold the same matrix bit for bit and no atomics are needed.  That every (q, p) pair of the matrix lies
 // inside p's window is VERIFIED when the field is set (k_flow_check walks the forward direction), not assumed: a field
 // that folds or shears beyond the window is refused and never reaches those kernels.
+//
+// A lattice keeps lw x lh nodes per component and frame, step HR pixels apart, as doubles in both dtypes; u_k(q) is their
+// bilinear interpolant rounded once to the dtype (LatticeField, sample_dev.hpp).  From u_k(q) on everything above is
+// unchanged: the seed and check kernels below are templates over the READER of u (DenseField / LatticeField), the seeds
+// stay a [K][H][W] table, and a lattice problem evaluates bit for bit as a dense one given the expanded nodes.
 #include <algorithm>
 #include <cmath>
 
@@ -31,26 +37,45 @@ constexpr double kFlowMaxDisp = 1048576.0; // 2^20
 
 // flow_pack_seed / flow_unpack_seed, kFlowPad: sample_dev.hpp (shared with the gather)
 
+// The reader of a dense field: frame k's planes of flow[K][2][H][W]; (flat pixel index, x, y) as LatticeField
+template <typename T>
+struct DenseField {
+  const T* __restrict__ fux;
+  const T* __restrict__ fuy;
+  __device__ __forceinline__ T ux(size_t qi, int, int) const { return fux[qi]; }
+  __device__ __forceinline__ T uy(size_t qi, int, int) const { return fuy[qi]; }
+};
+// reader of frame k (uniform bases) from the kernel argument of its form: the dense field, or the lattice
+template <typename T>
+__device__ __forceinline__ DenseField<T> field_of(const T* __restrict__ flow, int k, int N) {
+  const T* fux = flow + (size_t)k * 2 * N;
+  return {fux, fux + N};
+}
+template <typename T>
+__device__ __forceinline__ LatticeField<T> field_of(const LatticeDesc& lat, int k, int) {
+  return LatticeField<T>(lat, k);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
 // Set time.  seeds[k][p] = the fixed point (or the kFlowSeedSteps-th iterate) of q <- round(p - u_k(clamp(q))) from q = p,
 // clamped to the image widened by kFlowPad and packed.  A value that is not finite or beyond 2^20 ends the iteration (the
 // check kernel reports it; the seed only has to be a valid int).
-template <typename T>
-__global__ __launch_bounds__(256) void k_flow_seed(const T* __restrict__ flow, int* __restrict__ seeds, int W, int H) {
+// FIELD: the kernel argument u is read from -- const T* (dense) or LatticeDesc.
+template <typename T, typename FIELD>
+__global__ __launch_bounds__(256) void k_flow_seed(FIELD flow, int* __restrict__ seeds, int W, int H) {
   const int hp = blockIdx.x * 256 + threadIdx.x;
   const int k = blockIdx.y;
   const int N = W * H;
   if (hp >= N) return;
-  const T* __restrict__ fux = flow + (size_t)k * 2 * N;  // uniform bases
-  const T* __restrict__ fuy = fux + N;
+  const auto f = field_of<T>(flow, k, N);
   const int r = hp / W, col = hp - r * W;
   int qx = col, qy = r;
   for (int it = 0; it < kFlowSeedSteps; ++it) {
     const int cx = min(max(qx, 0), W - 1), cy = min(max(qy, 0), H - 1);
     const size_t qi = (size_t)cy * W + cx;
-    const double ux = (double)fux[qi], uy = (double)fuy[qi];
+    const double ux = (double)f.ux(qi, cx, cy), uy = (double)f.uy(qi, cx, cy);
     if (!(__builtin_fabs(ux) <= kFlowMaxDisp && __builtin_fabs(uy) <= kFlowMaxDisp)) break;
     const int nx = (int)__builtin_rint((double)col - ux), ny = (int)__builtin_rint((double)r - uy);
     if (nx == qx && ny == qy) break;
@@ -65,8 +90,8 @@ __global__ __launch_bounds__(256) void k_flow_seed(const T* __restrict__ flow, i
 // The forward direction, per pixel q of frame k: counts {entries that are not finite, entries beyond 2^20, taps p of q
 // (inside the image, weight not zero: the pairs the forward kernel multiplies) whose gather window does not contain q};
 // one record of three partials per workgroup, part[j * nblk + block].
-template <typename T>
-__global__ __launch_bounds__(256) void k_flow_check(const T* __restrict__ flow, const int* __restrict__ seeds, int W, int H,
+template <typename T, typename FIELD>
+__global__ __launch_bounds__(256) void k_flow_check(FIELD flow, const int* __restrict__ seeds, int W, int H,
                                                    double* __restrict__ part, int part_stride) {
   __shared__ double red[3][4];
   const int hp = blockIdx.x * 256 + threadIdx.x;
@@ -74,11 +99,10 @@ __global__ __launch_bounds__(256) void k_flow_check(const T* __restrict__ flow, 
   const int N = W * H;
   double bad_nan = 0.0, bad_big = 0.0, bad_win = 0.0;
   if (hp < N) {
-    const T* __restrict__ fux = flow + (size_t)k * 2 * N;  // uniform bases
-    const T* __restrict__ fuy = fux + N;
+    const auto f = field_of<T>(flow, k, N);
     const int* __restrict__ sk = seeds + (size_t)k * N;
     const int qy = hp / W, qx = hp - qy * W;
-    const T ux = fux[hp], uy = fuy[hp];
+    const T ux = f.ux((size_t)hp, qx, qy), uy = f.uy((size_t)hp, qx, qy);
     const double ax = __builtin_fabs((double)ux), ay = __builtin_fabs((double)uy);
     if (!(ax < __builtin_inf() && ay < __builtin_inf())) bad_nan = 1.0;
     else if (ax > kFlowMaxDisp || ay > kFlowMaxDisp) bad_big = 1.0;
@@ -113,10 +137,10 @@ __global__ __launch_bounds__(256) void k_flow_check(const T* __restrict__ flow, 
   }
 }
 
-// Seeds for the field `flow` ([K][2][H][W] of T, device) into `seeds`, and the three counts of k_flow_check into
-// counts_host: enqueued on st and waited for.
-template <typename T>
-static int flow_seed_and_check(srmap_problem* p, const T* flow, int* seeds, double counts_host[3], hipStream_t st) {
+// Seeds for the field `flow` ([K][2][H][W] of T on the device, or a lattice's description) into `seeds`, and the three
+// counts of k_flow_check into counts_host: enqueued on st and waited for.
+template <typename T, typename FIELD>
+static int flow_seed_and_check(srmap_problem* p, FIELD flow, int* seeds, double counts_host[3], hipStream_t st) {
   const Geometry& g = p->geo;
   const int N = g.W * g.H;
   dim3 grid((unsigned)((N + 255) / 256), g.K);
@@ -126,8 +150,8 @@ static int flow_seed_and_check(srmap_problem* p, const T* flow, int* seeds, doub
   SRMAP_HIP(p->ctx, part.alloc(((size_t)3 * stride + 3) * sizeof(double)));
   double* d_part = part.as<double>();
   double* d_counts = d_part + (size_t)3 * stride;
-  hipLaunchKernelGGL(k_flow_seed<T>, grid, dim3(256), 0, st, flow, seeds, g.W, g.H);
-  hipLaunchKernelGGL(k_flow_check<T>, grid, dim3(256), 0, st, flow, (const int*)seeds, g.W, g.H, d_part, stride);
+  hipLaunchKernelGGL((k_flow_seed<T, FIELD>), grid, dim3(256), 0, st, flow, seeds, g.W, g.H);
+  hipLaunchKernelGGL((k_flow_check<T, FIELD>), grid, dim3(256), 0, st, flow, (const int*)seeds, g.W, g.H, d_part, stride);
   int rc = SRMAP_OK;
   for (int j = 0; j < 3 && rc == SRMAP_OK; ++j)
     rc = launch_reduce_partials(p, d_part + (size_t)j * stride, nblk, d_counts + j, st);
@@ -140,6 +164,44 @@ static int flow_seed_and_check(srmap_problem* p, const T* flow, int* seeds, doub
   return SRMAP_OK;
 }
 
+// The answer to the three counts of k_flow_check for a field called `what`; the problem keeps the motion it had
+static int flow_counts_answer(srmap_ctx* ctx, const char* what, const double counts[3]) {
+  if (counts[0] != 0.0)
+    return set_error(ctx, SRMAP_EINVAL, "%s: %.0f entries are not finite in the problem's dtype", what, counts[0]);
+  if (counts[1] != 0.0)
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "%s: %.0f entries exceed 2^20 pixels", what, counts[1]);
+  if (counts[2] != 0.0)
+    return set_error(ctx, SRMAP_EUNSUPPORTED,
+                     "%s: %.0f (pixel, tap) pairs lie outside the transpose's %d x %d gather window (the field "
+                     "folds, or its neighbour differences exceed the documented bound)",
+                     what, counts[2], 2 * kFlowRadius + 1, 2 * kFlowRadius + 1);
+  return SRMAP_OK;
+}
+
+// The validated field (dense: `field` in the dtype; step > 0: `field` holds the lattice's nodes) and its seeds become the
+// problem's motion; both empty: the created motion is restored.  The three motions are alternatives
+static int flow_install(srmap_problem* p, DevBuf& field, DevBuf& seeds, int step, int lw, int lh) {
+  // evaluations in flight read the field: drain them before the buffers change
+  if (int rc = model_drain(p)) return rc;
+  const bool set = (bool)field;
+  field_motion_clear(p);  // the old field, lattice and seeds are freed
+  (step > 0 ? p->d_lattice : p->d_flow) = std::move(field);
+  p->d_flow_seed = std::move(seeds);
+  p->flow = set && step == 0;
+  if (set && step > 0) { p->lat_step = step; p->lat_lw = lw; p->lat_lh = lh; }
+  p->affine = false;  // a flow replaces an affine motion, and NULL restores the created motion
+  p->affine_recs.clear();
+  model_replan(p);  // "not covered" while a flow is set
+  return SRMAP_OK;
+}
+
+static int flow_seed_range(srmap_problem* p) {
+  const Geometry& g = p->geo;
+  if (((size_t)g.W + 2 * kFlowPad) * ((size_t)g.H + 2 * kFlowPad) >= ((size_t)1 << 31))
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "displacement field: an image of %d x %d is beyond the packed seed's range", g.W, g.H);
+  return SRMAP_OK;
+}
+
 // flow_dev != nullptr: the field in the problem's dtype on the device (read on st); else flow_host (doubles, rounded once)
 static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_dev, hipStream_t st) {
   srmap_ctx* ctx = p->ctx;
@@ -147,10 +209,8 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = (size_t)g.W * g.H, n = (size_t)g.K * 2 * N;
   DevBuf nf, ns;  // the new field and its seeds: built here, moved into the problem once they are valid
-  const bool set = flow_host != nullptr || flow_dev != nullptr;
-  if (set) {
-    if (((size_t)g.W + 2 * kFlowPad) * ((size_t)g.H + 2 * kFlowPad) >= ((size_t)1 << 31))
-      return set_error(ctx, SRMAP_EUNSUPPORTED, "displacement field: an image of %d x %d is beyond the packed seed's range", g.W, g.H);
+  if (flow_host != nullptr || flow_dev != nullptr) {
+    if (int rc = flow_seed_range(p)) return rc;
     if (nf.alloc(n * p->elem()) != hipSuccess || ns.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
       return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed (displacement field: %zu bytes, seeds: %zu bytes)", n * p->elem(),
                        (size_t)g.K * N * sizeof(int));
@@ -163,28 +223,41 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
       if (rc) return rc;
     }
     double counts[3] = {0.0, 0.0, 0.0};
-    rc = dispatch_dtype(p->dtype, [&](auto t) { return flow_seed_and_check<decltype(t)>(p, nf.as<const decltype(t)>(), ns.as<int>(), counts, st); });
+    rc = dispatch_dtype(p->dtype, [&](auto t) {
+      using T = decltype(t);
+      return flow_seed_and_check<T, const T*>(p, nf.as<const T>(), ns.as<int>(), counts, st);
+    });
     if (rc) return rc;
-    // the problem keeps the motion it had
-    if (counts[0] != 0.0)
-      return set_error(ctx, SRMAP_EINVAL, "displacement field: %.0f entries are not finite in the problem's dtype", counts[0]);
-    if (counts[1] != 0.0)
-      return set_error(ctx, SRMAP_EUNSUPPORTED, "displacement field: %.0f entries exceed 2^20 pixels", counts[1]);
-    if (counts[2] != 0.0)
-      return set_error(ctx, SRMAP_EUNSUPPORTED,
-                       "displacement field: %.0f (pixel, tap) pairs lie outside the transpose's %d x %d gather window (the field "
-                       "folds, or its neighbour differences exceed the documented bound)",
-                       counts[2], 2 * kFlowRadius + 1, 2 * kFlowRadius + 1);
+    if (int rc2 = flow_counts_answer(ctx, "displacement field", counts)) return rc2;
   }
-  // evaluations in flight read the field: drain them before the buffers change
-  if (int rc = model_drain(p)) return rc;
-  p->d_flow = std::move(nf);  // empty when the call clears the flow; the old field and seeds are freed
-  p->d_flow_seed = std::move(ns);
-  p->flow = set;
-  p->affine = false;  // alternatives: a flow replaces an affine motion, and NULL restores the created motion
-  p->affine_recs.clear();
-  model_replan(p);  // "not covered" while a flow is set
-  return SRMAP_OK;
+  return flow_install(p, nf, ns, 0, 0, 0);  // both empty when the call clears the flow
+}
+
+// The lattice form: nodes [K][2][lh][lw] doubles, on the device (read on st) or on the host; both NULL restores the created
+// motion.  The nodes are kept as doubles in both dtypes; u is read through LatticeField by the kernels above
+static int lattice_set(srmap_problem* p, int step, int lw, int lh, const double* nodes_host, const double* nodes_dev, hipStream_t st) {
+  srmap_ctx* ctx = p->ctx;
+  const Geometry& g = p->geo;
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  DevBuf nn, ns;
+  if (nodes_host != nullptr || nodes_dev != nullptr) {
+    if (step < 1 || step > kLatticeMaxStep) return set_error(ctx, SRMAP_EINVAL, "flow lattice: step %d is outside 1 ... %d", step, kLatticeMaxStep);
+    if (lw < 2 || lh < 2) return set_error(ctx, SRMAP_EINVAL, "flow lattice: %d x %d nodes (at least 2 x 2)", lw, lh);
+    if ((long long)(lw - 1) * step >= (long long)g.W + step || (long long)(lh - 1) * step >= (long long)g.H + step)
+      return set_error(ctx, SRMAP_EINVAL, "flow lattice: %d x %d nodes at step %d reach more than a cell beyond the %d x %d image", lw, lh, step, g.W, g.H);
+    if (int rc = flow_seed_range(p)) return rc;
+    const size_t N = (size_t)g.W * g.H, bytes = (size_t)g.K * 2 * lw * lh * sizeof(double);
+    if (nn.alloc(bytes) != hipSuccess || ns.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
+      return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed (flow lattice: %zu bytes, seeds: %zu bytes)", bytes, (size_t)g.K * N * sizeof(int));
+    if (hipMemcpyAsync(nn.as(), nodes_dev ? nodes_dev : nodes_host, bytes, nodes_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st) != hipSuccess)
+      return set_error(ctx, SRMAP_EHIP, "copying the flow lattice failed");
+    const LatticeDesc lat = {nn.as<const double>(), step, lw, lh};
+    double counts[3] = {0.0, 0.0, 0.0};
+    int rc = dispatch_dtype(p->dtype, [&](auto t) { return flow_seed_and_check<decltype(t), LatticeDesc>(p, lat, ns.as<int>(), counts, st); });
+    if (rc) return rc;
+    if (int rc2 = flow_counts_answer(ctx, "flow lattice (the interpolated field)", counts)) return rc2;
+  }
+  return flow_install(p, nn, ns, step, lw, lh);
 }
 
 }  // namespace srmap
@@ -207,4 +280,27 @@ extern "C" int srmap_problem_get_flow(srmap_problem* p, double* flow_out, int* i
   if (!flow_out || !p->flow) return SRMAP_OK;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   return convert_download(p, p->d_flow.as(), flow_out, (size_t)p->geo.K * 2 * p->geo.W * p->geo.H, p->ctx->stream);
+}
+
+extern "C" int srmap_problem_set_flow_lattice(srmap_problem* p, int step, int lw, int lh, const double* nodes_host) {
+  if (!p) return SRMAP_EINVAL;
+  return lattice_set(p, step, lw, lh, nodes_host, nullptr, p->ctx->stream);
+}
+
+extern "C" int srmap_problem_set_flow_lattice_device(srmap_problem* p, int step, int lw, int lh, const double* nodes_dev, void* hip_stream) {
+  if (!p) return SRMAP_EINVAL;
+  return lattice_set(p, step, lw, lh, nullptr, nodes_dev, stream_of(p->ctx, hip_stream));
+}
+
+extern "C" int srmap_problem_get_flow_lattice(srmap_problem* p, int* step, int* lw, int* lh, double* nodes_out) {
+  if (!p) return SRMAP_EINVAL;
+  if (step) *step = p->lat_step;
+  if (lw) *lw = p->lat_lw;
+  if (lh) *lh = p->lat_lh;
+  if (!nodes_out || !p->lat_step) return SRMAP_OK;
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(nodes_out, p->d_lattice.as(), (size_t)p->geo.K * 2 * p->lat_lw * p->lat_lh * sizeof(double),
+                                   hipMemcpyDeviceToHost, p->ctx->stream));
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
+  return SRMAP_OK;
 }

@@ -326,7 +326,7 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   *sp = SpForwardPlan();
   const Geometry& g = p->geo;
   const int S = g.s, B = g.b;
-  if (p->affine || p->flow || !p->has_motion || !p->maps_regular || S < 2 || S > 4 || (B != 1 && B != 3)) return false;
+  if (p->affine || field_motion(p) || !p->has_motion || !p->maps_regular || S < 2 || S > 4 || (B != 1 && B != 3)) return false;
   int omin = INT_MAX, omax = INT_MIN;
   for (int k = 0; k < g.K; ++k) {
     const WarpTaps<double>& f = p->fwd_warps[k];

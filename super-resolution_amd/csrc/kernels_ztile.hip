@@ -555,7 +555,7 @@ bool ztile_plan(srmap_problem* p) {
   const Geometry& g = p->geo;
   const int S = g.s, B = g.b, K = g.K;
   if (p->affine) return false;  // affine motion: the tiles' frame table holds translations only -- not covered
-  if (p->flow) return false;  // displacement field: likewise -- not covered
+  if (field_motion(p)) return false;  // displacement field (dense or on a lattice): likewise -- not covered
   if (p->custom_blur) return false;  // free-form blur kernel: the tiles carry a symmetric 3 x 3 kernel's three values
   if (!p->maps_regular) return false;
   if (S < 2 || S > 4) return false;

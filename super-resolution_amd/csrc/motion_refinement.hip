@@ -165,8 +165,9 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
                                           double* quality_out, double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
-  if (p->flow)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while a displacement field is set (srmap_problem_set_flow)");
+  if (field_motion(p))
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while %s is set (%s)",
+                     field_motion_name(p), field_motion_setter(p));
   srmap_motion_refinement_options opt;
   if (int rc = options_in_force(ctx, options, srmap_motion_refinement_options_default, "srmap_motion_refinement_options", &opt)) return rc;
   if (opt.dof != 2 && opt.dof != 6) return set_error(ctx, SRMAP_EINVAL, "motion refinement: dof must be 2 or 6 (got %d)", opt.dof);

@@ -210,8 +210,9 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
                                             double* quality_out, double* sums_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
-  if (p->flow)
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for a displacement field: not available while one is set (srmap_problem_set_flow)");
+  if (field_motion(p))
+    return set_error(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for %s: not available while one is set (%s)",
+                     field_motion_name(p), field_motion_setter(p));
   srmap_photometric_fit_options opt;
   int rc = options_in_force(ctx, options, srmap_photometric_fit_options_default, "srmap_photometric_fit_options", &opt);
   if (!rc) rc = photometric_option_values(p, opt);

@@ -48,6 +48,14 @@ void model_replan(srmap_problem* p) {
   if (ztile_plan(p)) ztile_preload(p);
 }
 
+void field_motion_clear(srmap_problem* p) {
+  p->flow = false;
+  p->d_flow.reset();
+  p->d_flow_seed.reset();
+  p->lat_step = p->lat_lw = p->lat_lh = 0;
+  p->d_lattice.reset();
+}
+
 // srmap_problem_set_affine_motion (below) and the motion refinement: validate K 2x3 matrices and fill the per-frame
 // records (inverse in double, formed once here).
 int affine_records(srmap_ctx* ctx, int K, const double* a23, std::vector<double>* recs) {
@@ -228,10 +236,8 @@ int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) 
     p->affine_recs.clear();
     p->d_affine.reset();
   }
-  // alternatives: an affine motion replaces a displacement field, and NULL restores the created motion
-  p->d_flow.reset();
-  p->d_flow_seed.reset();
-  p->flow = false;
+  // alternatives: an affine motion replaces a displacement field (dense or on a lattice), and NULL restores the created motion
+  field_motion_clear(p);
   model_replan(p);  // "not covered" while an affine motion is set
   return SRMAP_OK;
 }

@@ -315,6 +315,12 @@ __global__ __launch_bounds__(256) void k_flow_round(const double* __restrict__ h
     out[i] = i < frame_elems ? T(0) : (T)hr[i - frame_elems];
 }
 
+// nodes[frames][2][n] = gain * u[frames][2][n]: the input-level field in HR pixels, the control lattice of step `gain`
+// (srmap_problem_register_flow_lattice; the product commutes with k_flow_resample's rounding for a power of two)
+__global__ __launch_bounds__(256) void k_flow_nodes(const double* __restrict__ u, size_t total, double gain, double* __restrict__ nodes) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) nodes[i] = gain * u[i];
+}
+
 // prior[K][C][n] (T) = valid[K - 1][n] of the frames 1... broadcast over the channels; frame 0 is one.  grid = (pixels, C, K)
 template <typename T>
 __global__ __launch_bounds__(256) void k_flow_prior(const double* __restrict__ valid, size_t n, T* __restrict__ prior) {
@@ -328,18 +334,22 @@ __global__ __launch_bounds__(256) void k_flow_prior(const double* __restrict__ v
 struct FlowBuffers {
   DevBuf pyr, grad, u, v, hr, valid, rec, tab;  // doubles
   DevBuf field, prior;  // srmap_problem_register_flow: the field and the prior in the problem's dtype
+  DevBuf nodes;         // srmap_problem_register_flow_lattice: [K][2][h][w] doubles, s * u of the input level (image 0: zero)
   static bool get(DevBuf* b, size_t elems) { return b->alloc(elems * sizeof(double)) == hipSuccess; }
 };
 
 // Where the stack of one call comes from and where its results go.  Exactly one source: images_host (pageable doubles,
 // scanned on the host), images_dev (device doubles) or problem (its observation buffer; k_flow_plane).  Host results
 // (flow_host, valid_host) are copied back; device results are written where they are wanted: flow_dev / valid_dev when
-// given, else the call's own buffers b.hr / b.valid ([frames - 1] planes, image 0 left to the caller).
+// given, else the call's own buffers b.hr / b.valid ([frames - 1] planes, image 0 left to the caller).  lattice (with
+// problem): the call stops at the input level -- b.nodes instead of b.hr, no output-sized buffer, and quality [3i+2] from
+// the nodes: (largest node difference along x + along y) / step, which the expanded field's equals to rounding.
 struct FlowIo {
   const double* images_host = nullptr;
   const double* images_dev = nullptr;
   srmap_problem* problem = nullptr;
   int channel = -1;
+  bool lattice = false;
   double *flow_host = nullptr, *valid_host = nullptr;
   double *flow_dev = nullptr, *valid_dev = nullptr;
   bool on_device() const { return images_host == nullptr; }
@@ -403,18 +413,20 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
     off[l + 1] = off[l] + (size_t)K * lw[l] * lh[l];
     goff[l + 1] = goff[l] + (size_t)2 * lw[l] * lh[l];
   }
-  const int fin_blocks = std::min(kMaxRecordBlocks, blocks_of(n)), max_blocks = std::min(kMaxRecordBlocks, blocks_of(N));
+  const int fin_blocks = std::min(kMaxRecordBlocks, blocks_of(n)), max_blocks = std::min(kMaxRecordBlocks, blocks_of(io.lattice ? n : N));
   const int cnt_blocks = io.on_device() ? fin_blocks : 0;  // the device count of the non-finite pixels, per image
   const size_t rec_quality = (size_t)nf * 2 * (fin_blocks + max_blocks), rec_elems = rec_quality + (size_t)K * cnt_blocks;
-  const bool own_hr = !io.flow_dev, own_valid = !io.valid_dev;
+  const bool own_hr = !io.flow_dev && !io.lattice, own_valid = !io.valid_dev;
 
   if (!FlowBuffers::get(&b.pyr, off[L]) || !FlowBuffers::get(&b.grad, goff[L]) || !FlowBuffers::get(&b.u, (size_t)nf * 2 * n) ||
       !FlowBuffers::get(&b.v, (size_t)nf * 2 * n) || (own_hr && !FlowBuffers::get(&b.hr, (size_t)nf * 2 * N)) ||
       (own_valid && !FlowBuffers::get(&b.valid, (size_t)nf * n)) || !FlowBuffers::get(&b.rec, rec_elems) ||
+      (io.lattice && !FlowBuffers::get(&b.nodes, (size_t)K * 2 * n)) ||
       !FlowBuffers::get(&b.tab, h_tab.size()))
     return set_error(ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
   double *const pyr = b.pyr.as<double>(), *const grad = b.grad.as<double>(), *const rec = b.rec.as<double>(), *const tab = b.tab.as<double>();
-  double* hr = own_hr ? b.hr.as<double>() : io.flow_dev + 2 * N;
+  double* hr = io.lattice ? nullptr : own_hr ? b.hr.as<double>() : io.flow_dev + 2 * N;
+  if (io.lattice) SRMAP_HIP(ctx, hipMemsetAsync(b.nodes.as(), 0, 2 * n * sizeof(double), st));  // image 0
   double* valid = own_valid ? b.valid.as<double>() : io.valid_dev + n;
 
   // ---- pyramids of the whole stack and the gradient planes of frame 0, once ----
@@ -469,11 +481,20 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
     // ---- the HR field, the mask and the quality records ----
     double* rec_fin = rec;
     double* rec_max = rec + (size_t)nf * 2 * fin_blocks;
-    hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, hr, s * width, s * height, 0.0,
-                       (double)s, (double)s);
+    if (io.lattice) {
+      const size_t total = (size_t)nf * 2 * n;
+      hipLaunchKernelGGL(k_flow_nodes, dim3(std::min(blocks_of(total), 4096)), dim3(256), 0, st, (const double*)u, total, (double)s,
+                         b.nodes.as<double>() + 2 * n);
+    } else {
+      hipLaunchKernelGGL(k_flow_resample, dim3(blocks_of(N), 2 * nf), dim3(256), 0, st, u, width, height, hr, s * width, s * height, 0.0,
+                         (double)s, (double)s);
+    }
     hipLaunchKernelGGL(k_flow_finish, dim3(fin_blocks, nf), dim3(256), 0, st, pyr, pyr, u, width, height, opt.valid_margin, valid,
                        rec_fin);
-    hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, hr, s * width, s * height, rec_max);
+    if (io.lattice)
+      hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, b.nodes.as<const double>() + 2 * n, width, height, rec_max);
+    else
+      hipLaunchKernelGGL(k_flow_maxdiff, dim3(max_blocks, nf), dim3(256), 0, st, hr, s * width, s * height, rec_max);
   }
   SRMAP_HIP(ctx, hipGetLastError());
   // ---- the one wait ----
@@ -503,25 +524,59 @@ int register_flow_body(srmap_ctx* ctx, int K, int width, int height, const srmap
       double* q = quality_out + 3 * (f + 1);
       q[0] = cnt > 0 ? std::sqrt(see / cnt) : 0.0;
       q[1] = cnt / (double)n;
-      q[2] = mx + my;
+      q[2] = io.lattice ? (mx + my) / (double)s : mx + my;
     }
   }
   return SRMAP_OK;
 }
 
-// the field and (want_prior) the prior of a problem in its dtype from the body's buffers, enqueued on st
+// (want_field) the field and (want_prior) the prior of a problem in its dtype from the body's buffers, enqueued on st
 template <typename T>
-int problem_stage(srmap_problem* p, FlowBuffers& b, bool want_prior, hipStream_t st) {
+int problem_stage(srmap_problem* p, FlowBuffers& b, bool want_field, bool want_prior, hipStream_t st) {
   const Geometry& g = p->geo;
   const size_t n = (size_t)g.w * g.h, N = (size_t)g.W * g.H, total = (size_t)g.K * 2 * N;
-  if (b.field.alloc(total * sizeof(T)) != hipSuccess || (want_prior && b.prior.alloc(p->lr_count() * sizeof(T)) != hipSuccess))
+  if ((want_field && b.field.alloc(total * sizeof(T)) != hipSuccess) || (want_prior && b.prior.alloc(p->lr_count() * sizeof(T)) != hipSuccess))
     return set_error(p->ctx, SRMAP_ENOMEM, "flow registration: allocation failed");
   const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)std::max(1, p->ctx->num_cus) * 16);
-  hipLaunchKernelGGL(k_flow_round<T>, dim3(std::max(1u, blocks)), dim3(256), 0, st, b.hr.as<const double>(), 2 * N, total, b.field.as<T>());
+  if (want_field)
+    hipLaunchKernelGGL(k_flow_round<T>, dim3(std::max(1u, blocks)), dim3(256), 0, st, b.hr.as<const double>(), 2 * N, total, b.field.as<T>());
   if (want_prior)
     hipLaunchKernelGGL(k_flow_prior<T>, dim3(blocks_of(n), g.C, g.K), dim3(256), 0, st, b.valid.as<const double>(), n, b.prior.as<T>());
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
+}
+
+// srmap_problem_register_flow (lattice = false) and srmap_problem_register_flow_lattice: the plane rule, the options and
+// the errors are one; the lattice form stops at the input level and installs nodes = s * u with step s on the LR grid
+int problem_register(srmap_problem* p, int channel, const srmap_flow_registration_options* options, int install_prior,
+                     double* quality_out, bool lattice) {
+  srmap_ctx* ctx = p->ctx;
+  const Geometry& g = p->geo;
+  srmap_flow_registration_options opt;
+  if (int rc = check_options(ctx, options, &opt)) return rc;
+  if (!p->have_obs || !p->d_obs) return set_error(ctx, SRMAP_EINVAL, "flow registration: no observations set");
+  if (channel < -1 || channel >= g.C) return set_error(ctx, SRMAP_EINVAL, "flow registration: channel %d of %d", channel, g.C);
+  if (g.W != g.w * g.s || g.H != g.h * g.s)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: HR size %dx%d is not LR size * scale (%d)", g.W, g.H, g.s);
+  if (opt.hr_scale != 1 && opt.hr_scale != g.s)
+    return set_error(ctx, SRMAP_EINVAL, "flow registration: hr_scale %d is neither 1 nor the problem's scale %d", opt.hr_scale, g.s);
+  opt.hr_scale = g.s;
+  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (int rc = problem_state_read(p, st)) return rc;
+  FlowIo io;
+  io.problem = p;
+  io.channel = channel;
+  io.lattice = lattice;
+  FlowBuffers b;
+  if (int rc = register_flow_body(ctx, g.K, g.w, g.h, opt, io, b, st, quality_out)) return rc;
+  const bool prior = install_prior != 0;
+  if (int rc = dispatch_dtype(p->dtype, [&](auto t) { return problem_stage<decltype(t)>(p, b, !lattice, prior, st); })) return rc;
+  // a refused field leaves the motion -- and the prior -- the problem had
+  if (int rc = lattice ? srmap_problem_set_flow_lattice_device(p, g.s, g.w, g.h, b.nodes.as<const double>(), st)
+                       : srmap_problem_set_flow_device(p, b.field.as(), st))
+    return rc;
+  return prior ? srmap_set_data_prior_device(p, b.prior.as(), st) : SRMAP_OK;
 }
 
 }  // namespace
@@ -578,28 +633,11 @@ extern "C" int srmap_register_flow_device(srmap_ctx* ctx, int num_images, int wi
 extern "C" int srmap_problem_register_flow(srmap_problem* p, int channel, const srmap_flow_registration_options* options,
                                            int install_prior, double* quality_out) {
   if (!p) return SRMAP_EINVAL;
-  srmap_ctx* ctx = p->ctx;
-  const Geometry& g = p->geo;
-  srmap_flow_registration_options opt;
-  if (int rc = check_options(ctx, options, &opt)) return rc;
-  if (!p->have_obs || !p->d_obs) return set_error(ctx, SRMAP_EINVAL, "flow registration: no observations set");
-  if (channel < -1 || channel >= g.C) return set_error(ctx, SRMAP_EINVAL, "flow registration: channel %d of %d", channel, g.C);
-  if (g.W != g.w * g.s || g.H != g.h * g.s)
-    return set_error(ctx, SRMAP_EINVAL, "flow registration: HR size %dx%d is not LR size * scale (%d)", g.W, g.H, g.s);
-  if (opt.hr_scale != 1 && opt.hr_scale != g.s)
-    return set_error(ctx, SRMAP_EINVAL, "flow registration: hr_scale %d is neither 1 nor the problem's scale %d", opt.hr_scale, g.s);
-  opt.hr_scale = g.s;
-  SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  if (int rc = problem_state_read(p, st)) return rc;
-  FlowIo io;
-  io.problem = p;
-  io.channel = channel;
-  FlowBuffers b;
-  if (int rc = register_flow_body(ctx, g.K, g.w, g.h, opt, io, b, st, quality_out)) return rc;
-  const bool prior = install_prior != 0;
-  if (int rc = dispatch_dtype(p->dtype, [&](auto t) { return problem_stage<decltype(t)>(p, b, prior, st); })) return rc;
-  // a refused field leaves the motion -- and the prior -- the problem had
-  if (int rc = srmap_problem_set_flow_device(p, b.field.as(), st)) return rc;
-  return prior ? srmap_set_data_prior_device(p, b.prior.as(), st) : SRMAP_OK;
+  return problem_register(p, channel, options, install_prior, quality_out, false);
+}
+
+extern "C" int srmap_problem_register_flow_lattice(srmap_problem* p, int channel, const srmap_flow_registration_options* options,
+                                                   int install_prior, double* quality_out) {
+  if (!p) return SRMAP_EINVAL;
+  return problem_register(p, channel, options, install_prior, quality_out, true);
 }

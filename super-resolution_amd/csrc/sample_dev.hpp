@@ -118,6 +118,33 @@ __device__ __forceinline__ void flow_unpack_seed(int v, int W, int* sx, int* sy)
   *sx = v - y * SW - kFlowPad;
 }
 
+// The displacement field of one frame kept on a control lattice (LatticeDesc, srmap_internal.hpp): u at the HR pixel
+// (x, y) is the bilinear interpolant of the frame's nodes at (x, y) / step, clamped to the lattice (constant beyond the
+// last node), in double, in k_flow_resample's order (registration_flow.hip with sub = 0, div = step, gain = 1) and
+// without contraction, then rounded ONCE to T: the value a dense field holds after srmap_problem_set_flow rounded the
+// same interpolant.  The one copy of that expression: the evaluation kernels (MotionSampler's lattice kind) and the
+// set-time kernels (kernels_flow.hip) read u through it.  The node bases are wave-uniform.
+template <typename T>
+struct LatticeField {
+  const double* __restrict__ nx;
+  const double* __restrict__ ny;
+  int step, lw, lh;
+  __device__ __forceinline__ LatticeField(const LatticeDesc& a, int k)
+      : nx(a.nodes + (size_t)k * 2 * (a.lw * a.lh)), ny(nx + a.lw * a.lh), step(a.step), lw(a.lw), lh(a.lh) {}
+  __device__ __forceinline__ double value(const double* __restrict__ plane, int x, int y) const {
+#pragma clang fp contract(off)
+    const double cx = fmin(fmax((double)x / (double)step, 0.0), (double)(lw - 1));
+    const double cy = fmin(fmax((double)y / (double)step, 0.0), (double)(lh - 1));
+    const int xi = min((int)__builtin_floor(cx), lw - 2), yi = min((int)__builtin_floor(cy), lh - 2);
+    const double fx = cx - (double)xi, fy = cy - (double)yi;
+    const double* __restrict__ p = plane + (size_t)yi * lw + xi;
+    return (1.0 - fy) * ((1.0 - fx) * p[0] + fx * p[1]) + fy * ((1.0 - fx) * p[lw] + fx * p[lw + 1]);
+  }
+  // the reader's form of the set-time kernels: (flat pixel index, x, y)
+  __device__ __forceinline__ T ux(size_t, int x, int y) const { return (T)value(nx, x, y); }
+  __device__ __forceinline__ T uy(size_t, int x, int y) const { return (T)value(ny, x, y); }
+};
+
 // M_k of frame k for one motion kind (MotionKind, srmap_internal.hpp), built from the kernel's argument block, the
 // geometry and the WAVE-UNIFORM frame index alone: the affine record then comes through scalar loads, and the plane bases
 // of the field and of the seeds are uniform.
@@ -215,6 +242,38 @@ struct MotionSampler<T, kMotionFlow> {
   }
   __device__ __forceinline__ double weight_y(size_t qi, int, int qy, int r) const {
     return affine_axis_weight(flow_source(qy, fuy[qi]), r);
+  }
+};
+
+// displacement field on a control lattice: the flow kind with u_k(q) interpolated from the frame's nodes (LatticeField)
+// where that kind loads it; seeds, window and weights are the flow kind's.  The nodes come through the caches per
+// sample: 4 doubles per component, shared by the step x step pixels of a cell.  The gather was also measured with the
+// 3 x 3 ux nodes of a window held in registers (loaded once per frame, picked by selects): 88-92 VGPRs against 52-56 and
+// 1.23 x the time of this form (profiles/r24_flow_lattice.txt), so the per-candidate form stays.  The compiler already
+// forms cy / yi / fy once per window row; one double division per candidate (cx) is left.
+template <typename T>
+struct MotionSampler<T, kMotionLattice> {
+  static constexpr int kWindow = 2 * kFlowRadius + 1;
+  const LatticeField<T> f;
+  const int* __restrict__ seeds;
+  __device__ __forceinline__ MotionSampler(const MotionArgs<T>& a, const Geometry& g, int k)
+      : f(a.lat, k), seeds(a.seeds + (size_t)k * (g.W * g.H)) {}
+  template <typename A>
+  __device__ __forceinline__ A at(const T* __restrict__ plane, int W, int H, int rr, int cc) const {
+    const double sx = flow_source(cc, f.ux(0, cc, rr)), sy = flow_source(rr, f.uy(0, cc, rr));
+    return affine_sample<T, A>(plane, W, H, sx, sy);
+  }
+  __device__ __forceinline__ bool window(const Geometry& g, int hp, int, int, int* qx0, int* qy0) const {
+    flow_unpack_seed(seeds[hp], g.W, qx0, qy0);
+    *qx0 -= kFlowRadius;
+    *qy0 -= kFlowRadius;
+    return true;
+  }
+  __device__ __forceinline__ double weight_x(size_t, int qx, int qy, int col) const {
+    return affine_axis_weight(flow_source(qx, f.ux(0, qx, qy)), col);
+  }
+  __device__ __forceinline__ double weight_y(size_t, int qx, int qy, int r) const {
+    return affine_axis_weight(flow_source(qy, f.uy(0, qx, qy)), r);
   }
 };
 

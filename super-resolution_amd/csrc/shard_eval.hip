@@ -25,6 +25,9 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what) {
   if (p->flow)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a displacement-field motion model is not sharded over a communicator%s: %s",
                      solve ? " (only the direct family runs it)" : "", tail);
+  if (p->lat_step)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a displacement-field motion model on a control lattice is not sharded over a communicator%s: %s",
+                     solve ? " (only the direct family runs it)" : "", tail);
   if (p->blur_bank_mode != 0)
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur-kernel bank is not sharded over a communicator%s: %s",
                      solve ? " (only the direct family runs it)" : "", tail);

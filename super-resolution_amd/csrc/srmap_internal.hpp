@@ -46,15 +46,25 @@ static_assert(std::is_trivially_copyable_v<WarpTaps<float>> && std::is_trivially
               "a kernel argument: no owner inside");
 
 // The forms of M_k in A_k = D B M_k: none (the identity), the translational tap table, an affine matrix per frame, a dense
-// displacement field per frame.  MotionArgs: what the kernels that sample M_k (MotionSampler, sample_dev.hpp) take for
-// it, by value as ONE kernel argument; a kind reads its own members only.
-enum MotionKind { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2, kMotionFlow = 3 };
+// displacement field per frame, a displacement field on a control lattice per frame.  MotionArgs: what the kernels that
+// sample M_k (MotionSampler, sample_dev.hpp) take for it, by value as ONE kernel argument; a kind reads its own members
+// only.
+enum MotionKind { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2, kMotionFlow = 3, kMotionLattice = 4 };
+// The control lattice of a displacement field (srmap_problem_set_flow_lattice, kernels_flow.hip): lw x lh nodes
+// per component, node (i, j) at HR pixel (i * step, j * step); nodes [K][2][lh][lw] doubles in both dtypes
+constexpr int kLatticeMaxStep = 1024;
+struct LatticeDesc {
+  const double* nodes;
+  int step, lw, lh;
+};
+static_assert(std::is_trivially_copyable_v<LatticeDesc>, "a kernel argument: no owner inside");
 template <typename T>
 struct MotionArgs {
   const WarpTaps<T>* warps;  // [K] forward taps (table); nullptr: the identity
   const double* recs;        // [K][kAffineRec] (affine)
   const T* flow;             // [K][2][H][W] (flow)
-  const int* seeds;          // [K][H][W] packed seeds of the transpose gather (flow)
+  const int* seeds;          // [K][H][W] packed seeds of the transpose gather (flow, lattice)
+  LatticeDesc lat;           // (lattice)
 };
 static_assert(std::is_trivially_copyable_v<MotionArgs<float>> && std::is_trivially_copyable_v<MotionArgs<double>>,
               "a kernel argument: no owner inside");
@@ -154,6 +164,10 @@ struct srmap_problem {
   // packed seeds of the transpose gather, both validated when they were set
   bool flow = false;
   srmap::DevBuf d_flow, d_flow_seed;
+  // the same model with the field kept as values on a control lattice and interpolated in the kernels (kMotionLattice; a
+  // third alternative): d_lattice [K][2][lat_lh][lat_lw] doubles in both dtypes, its seeds in d_flow_seed.  lat_step = 0: none
+  int lat_step = 0, lat_lw = 0, lat_lh = 0;
+  srmap::DevBuf d_lattice;
   std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
   std::vector<double> blur2d_t;
   std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
@@ -302,11 +316,17 @@ inline BlurStride blur_stride(const srmap_problem* p) {
 }
 // ---- the problem's motion, for the launchers of the kernels that sample it (kernels_data_direct.hip, the fits) ----
 inline MotionKind motion_kind(const srmap_problem* p) {
-  return p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;
+  return p->lat_step ? kMotionLattice : p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;
 }
+// "a displacement field" / "... on a control lattice" (srmap_problem_set_flow / _lattice): the refusals of what has no leg for
+// either name the one that is set
+inline bool field_motion(const srmap_problem* p) { return p->flow || p->lat_step != 0; }
+inline const char* field_motion_name(const srmap_problem* p) { return p->lat_step ? "a displacement field on a control lattice" : "a displacement field"; }
+inline const char* field_motion_setter(const srmap_problem* p) { return p->lat_step ? "srmap_problem_set_flow_lattice" : "srmap_problem_set_flow"; }
 template <typename T>
 MotionArgs<T> motion_args(const srmap_problem* p) {
-  return {p->has_motion ? p->d_fwd_warps.as<const WarpTaps<T>>() : nullptr, p->d_affine.as<double>(), p->d_flow.as<const T>(), p->d_flow_seed.as<int>()};
+  return {p->has_motion ? p->d_fwd_warps.as<const WarpTaps<T>>() : nullptr, p->d_affine.as<double>(), p->d_flow.as<const T>(), p->d_flow_seed.as<int>(),
+          {p->d_lattice.as<double>(), p->lat_step, p->lat_lw, p->lat_lh}};
 }
 // The one switch from a run-time int to the template instances: f(std::integral_constant<int, V>) for the one of
 // VALUES... that `v` is -- a motion kind: the kinds the caller has kernel instances of; false (and no call) for any other,
@@ -320,6 +340,9 @@ template <typename F>
 void dispatch_scale(int s, F&& f) {
   if (!dispatch_value<2, 3, 4>(s, f)) f(std::integral_constant<int, 0>());
 }
+// Leaves the problem without a displacement field, dense or on a lattice, and without their seeds (problem.hip): what a
+// motion setter does after model_drain, before it installs its own
+void field_motion_clear(srmap_problem* p);
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (problem.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
 // ---- the fits' shared kernels, planning and per-pass buffers (motion_fit.hip) ----

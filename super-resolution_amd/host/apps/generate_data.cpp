@@ -26,6 +26,9 @@ int main(int argc, char** argv) {
       "                        [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
       "                        [frames][2][H][W] = the (ux, uy) planes in HR pixels at the input image's size; an error together\n"
       "                        with --motion_sequence_path or --affine_motion_path)\n"
+      "                        [--flow_lattice_path=<file>] (the same motion on a control lattice: one text line `step lw lh\n"
+      "                        frames`, then the raw little-endian float64 nodes [frames][2][lh][lw], node (i, j) at HR pixel\n"
+      "                        (i step, j step), interpolated bilinearly; an error together with any other motion flag)\n"
       "                        [--blur_kernel_path=<file>] (a free-form blur kernel instead of the Gaussian of --blur_radius /\n"
       "                        --blur_sigma: text, the odd size ksize <= 7, then ksize * ksize taps in row-major order)\n"
       "                        [--blur_bank_path=<file>] (a blur kernel per frame, per channel or per both instead of one blur:\n"
@@ -52,6 +55,9 @@ int main(int argc, char** argv) {
   if (app::RefuseBothMotionFiles(model)) return 1;
   if (!flow_motion_path.empty() && (!parameters.affine_motion_sequence_path.empty() || !parameters.motion_sequence_path.empty()))
     return app::Refuse("--flow_motion_path excludes --motion_sequence_path and --affine_motion_path.");
+  if (app::RefuseBothFlowFiles(model)) return 1;
+  if (!model.flow_lattice_path.empty() && (!parameters.affine_motion_sequence_path.empty() || !parameters.motion_sequence_path.empty()))
+    return app::Refuse("--flow_lattice_path excludes --motion_sequence_path and --affine_motion_path.");
 
   const ImageData image_data = util::LoadImage(input_image);
   if (!save_as.empty()) {  // copy / convert only (generate_data.cpp:94-98)
@@ -75,6 +81,13 @@ int main(int argc, char** argv) {
     if (parameters.flow_motion_sequence.GetNumMotions() < number_of_frames)
       return app::Refuse("--flow_motion_path holds %d frames, --number_of_frames asks for %d.",
                          parameters.flow_motion_sequence.GetNumMotions(), number_of_frames);
+  }
+  if (!model.flow_lattice_path.empty()) {  // the forward model samples the interpolated field: the lattice, expanded
+    FlowLatticeSequence lattice;
+    lattice.LoadSequenceFromFile(model.flow_lattice_path);
+    if (lattice.GetNumMotions() < number_of_frames)
+      return app::Refuse("--flow_lattice_path holds %d frames, --number_of_frames asks for %d.", lattice.GetNumMotions(), number_of_frames);
+    parameters.flow_motion_sequence = lattice.Expand(image_data.GetImageSize().width, image_data.GetImageSize().height);
   }
   const ImageModel image_model = ImageModel::CreateImageModel(parameters);
   if (!extension.empty() && extension[0] != '.') extension = "." + extension;

@@ -64,6 +64,9 @@ const char kUsage[] =
       "                       [frames][2][H][W] = the (ux, uy) planes in HR pixels at the high-resolution size; an error\n"
       "                       together with --motion_sequence_path, --affine_motion_path, --registration,\n"
       "                       --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
+      "                       [--flow_lattice_path=<file>] (the same motion on a control lattice, generate_data's format: the\n"
+      "                       solver keeps the nodes and interpolates them, srmap_problem_set_flow_lattice; an error with what\n"
+      "                       --flow_motion_path is an error with, and with --flow_motion_path)\n"
       "                       [--registration=translational|affine|flow] (estimate the solver's motion from the LR frames, in\n"
       "                       HR pixels; with --generate_lr_images the motion files still generate the frames, without it\n"
       "                       an error together with either motion file.  flow: a dense displacement field per frame, and\n"
@@ -72,6 +75,10 @@ const char kUsage[] =
       "                       --affine_motion_path, --refine_motion_rounds, --fit_blur_from and --photometric_rounds)\n"
       "                       [--save_flow_path=<file>] (the estimated fields, in --flow_motion_path's format; needs\n"
       "                       --registration=flow)\n"
+      "                       [--flow_lattice] (with --registration=flow: the estimate stays at the frames' resolution and is\n"
+      "                       installed as a control lattice, srmap_problem_register_flow_lattice; --save_flow_path then\n"
+      "                       writes the expanded field) [--save_flow_lattice_path=<file>] (the lattice itself, in\n"
+      "                       --flow_lattice_path's format; needs --flow_lattice)\n"
       "                       [--flow_valid_prior] (install the validity masks of --registration=flow as a persistent prior\n"
       "                       on the data weights instead of multiplying them in, so that they hold under --data_loss=huber\n"
       "                       too; needs --registration=flow)\n"
@@ -133,6 +140,9 @@ struct Options {
   // not reference flags: estimate the solver's motion from the LR frames (srmap_register_translational /
   // srmap_register_affine / srmap_register_flow) instead of reading it from a file, and write the estimate out
   std::string registration, save_motion_path, save_flow_path;
+  // not reference flags: --registration=flow kept on a control lattice (srmap_problem_register_flow_lattice), and its file
+  bool flow_lattice;
+  std::string save_flow_lattice_path;
   // not a reference flag: the validity masks as the persistent prior of srmap_set_data_prior (they hold under Huber too)
   bool flow_valid_prior;
   // not reference flags: joint motion refinement (srmap_refine_motion) around the solve
@@ -146,6 +156,7 @@ struct Options {
   bool verbose;
 
   bool RegisterFlow() const { return registration == "flow"; }
+  bool RegisterFlowLattice() const { return RegisterFlow() && flow_lattice; }
   int FitBankMode() const {
     return fit_blur_bank_mode == "frame" ? 1 : fit_blur_bank_mode == "channel" ? 2 : fit_blur_bank_mode == "frame_channel" ? 3 : 0;
   }
@@ -159,6 +170,7 @@ struct Frames {
   ImageData initial_estimate;  // the same in the space the solve runs in
   std::unique_ptr<SpectralPCA> spectral_pca;
   std::vector<double> flow_valid;  // --registration=flow: the validity masks, [frames][h][w] at LR resolution
+  FlowLatticeSequence flow_lattice;  // --flow_lattice_path: the solver's motion, set once the solver exists
 };
 
 Options ParseFlags(int argc, char** argv) {
@@ -198,6 +210,8 @@ Options ParseFlags(int argc, char** argv) {
   o.save_motion_path = flags.Str("save_motion_path");
   o.save_flow_path = flags.Str("save_flow_path");
   o.flow_valid_prior = flags.Bool("flow_valid_prior", false);
+  o.flow_lattice = flags.Bool("flow_lattice", false);
+  o.save_flow_lattice_path = flags.Str("save_flow_lattice_path");
   o.refine_motion_rounds = flags.Int("refine_motion_rounds", 0);
   o.refine_motion_dof = flags.Int("refine_motion_dof", 6);
   o.fit_blur_from = flags.Str("fit_blur_from");
@@ -238,6 +252,9 @@ int CheckFlags(const Options& o) {
   if (app::RefuseBothMotionFiles(o.model)) return 1;
   if (!o.model.flow_motion_path.empty())
     if (const char* other = FlagExcludedByFlow(o, true)) return app::RefuseBoth("--flow_motion_path", other);
+  if (app::RefuseBothFlowFiles(o.model)) return 1;
+  if (!o.model.flow_lattice_path.empty())
+    if (const char* other = FlagExcludedByFlow(o, true)) return app::RefuseBoth("--flow_lattice_path", other);
   if (!o.registration.empty() && o.registration != "translational" && o.registration != "affine" && !o.RegisterFlow())
     return Refuse("--registration is 'translational' or 'affine', or 'flow'.");
   if (o.RegisterFlow()) {
@@ -247,6 +264,8 @@ int CheckFlags(const Options& o) {
   }
   if (!o.save_flow_path.empty() && !o.RegisterFlow()) return Refuse("--save_flow_path needs --registration=flow.");
   if (o.flow_valid_prior && !o.RegisterFlow()) return Refuse("--flow_valid_prior needs --registration=flow.");
+  if (o.flow_lattice && !o.RegisterFlow()) return Refuse("--flow_lattice needs --registration=flow.");
+  if (!o.save_flow_lattice_path.empty() && !o.RegisterFlowLattice()) return Refuse("--save_flow_lattice_path needs --registration=flow --flow_lattice.");
   if (!o.registration.empty() && !o.generate_lr_images && motion_file)
     return Refuse("--registration estimates the motion; it excludes --motion_sequence_path and --affine_motion_path "
                   "(except with --generate_lr_images, where the files generate the frames).");
@@ -267,7 +286,7 @@ int CheckFlags(const Options& o) {
     return Refuse("--fit_blur_bank_mode and --save_blur_bank_path need --fit_blur_bank_from.");
   if (!o.fit_blur_bank_from.empty() && o.FitBankMode() == 0)
     return Refuse("--fit_blur_bank_from needs --fit_blur_bank_mode=frame|channel|frame_channel.");
-  if (!o.fit_blur_bank_from.empty() && (!o.model.flow_motion_path.empty() || o.RegisterFlow()))
+  if (!o.fit_blur_bank_from.empty() && (!o.model.flow_motion_path.empty() || !o.model.flow_lattice_path.empty() || o.RegisterFlow()))
     return Refuse("--fit_blur_bank_from has no sampling leg for a displacement field: not with --flow_motion_path or --registration=flow.");
   if (o.photometric_rounds < -1) return Refuse("--photometric_rounds is >= 0 (or -1: off).");
   if (!o.photometric_path.empty() && o.photometric_rounds >= 0)
@@ -303,12 +322,19 @@ int NoLowResImages() {
 int LoadImages(Options* o, Frames* f) {
   if (o->generate_lr_images) f->high_res_image = util::LoadImage(o->data_path);
   else f->low_res_images = util::LoadImages(o->data_path);
-  if (o->model.flow_motion_path.empty()) return 0;
-  // the file has no header: its size is checked against the HR geometry
+  if (o->model.flow_motion_path.empty() && o->model.flow_lattice_path.empty()) return 0;
+  // the field's file has no header: its size is checked against the HR geometry; the lattice is expanded at it
   if (!o->generate_lr_images && f->low_res_images.empty()) return NoLowResImages();
   const cv::Size hr = o->generate_lr_images ? f->high_res_image.GetImageSize()
                                             : cv::Size(f->low_res_images[0].GetImageSize().width * o->upsampling_scale,
                                                        f->low_res_images[0].GetImageSize().height * o->upsampling_scale);
+  if (!o->model.flow_lattice_path.empty()) {
+    // the solver is given the lattice itself (InstallLattice) and its model no motion; only a model that generates the
+    // frames carries the expanded field
+    f->flow_lattice.LoadSequenceFromFile(o->model.flow_lattice_path);
+    if (o->generate_lr_images) o->model.parameters.flow_motion_sequence = f->flow_lattice.Expand(hr.width, hr.height);
+    return 0;
+  }
   o->model.parameters.flow_motion_sequence.LoadSequenceFromFile(o->model.flow_motion_path, hr.width, hr.height);
   return 0;
 }
@@ -363,7 +389,9 @@ int SaveMotion(const Options& o, const AffineMotionSequence& sequence) {
 // --registration: the solver's model takes its motion from the frames it is about to solve (channel 0), in HR pixels; the
 // generating model keeps the motion files
 int EstimateMotion(const Options& o, Frames* f, ImageModelParameters* solver_parameters) {
-  if (o.RegisterFlow()) {
+  if (o.RegisterFlowLattice()) {
+    // the solver registers its own observations once it exists (InstallLattice); its model starts without a motion
+  } else if (o.RegisterFlow()) {
     solver_parameters->flow_motion_sequence = registration::FlowRegistration(f->low_res_images, o.upsampling_scale, &f->flow_valid);
     double kept = 0.0;
     for (const double v : f->flow_valid) kept += v;
@@ -392,6 +420,34 @@ int EstimateMotion(const Options& o, Frames* f, ImageModelParameters* solver_par
     std::printf("Estimated %s motion of %d frames from the low-resolution images.\n", o.registration.c_str(), estimate.GetNumMotions());
     // with refinement rounds the file holds the FINAL matrices: written after the solve
     if (!o.save_motion_path.empty() && o.refine_motion_rounds == 0) return SaveMotion(o, estimate);
+  }
+  return 0;
+}
+
+// --registration=flow --flow_lattice: channel 0 of the solver's own observations is registered on the device and the
+// estimate installed as a control lattice, the validity masks as the data prior; the masks come back as f->flow_valid for
+// SetUpSolver, which places them as the dense route does.  --flow_lattice_path: the lattice replaces the expanded field.
+int InstallLattice(const Options& o, Frames* f, IRLSMapSolver* solver) {
+  if (!f->flow_lattice.Empty()) {
+    f->flow_lattice.Trim(solver->GetNumImages());
+    solver->SetFlowLattice(f->flow_lattice);
+  }
+  if (!o.RegisterFlowLattice()) return 0;
+  solver->RegisterFlowLattice(0, nullptr, true);
+  const std::vector<double> prior = solver->GetDataPrior();  // [K][C][h][w], every channel the frame's mask
+  solver->SetDataPrior(std::vector<double>());
+  const size_t frames = static_cast<size_t>(solver->GetNumImages()), plane = prior.size() / (frames * solver->GetNumChannels());
+  f->flow_valid.resize(frames * plane);
+  double kept = 0.0;
+  for (size_t k = 0; k < frames; ++k)
+    for (size_t i = 0; i < plane; ++i) kept += f->flow_valid[k * plane + i] = prior[k * solver->GetNumChannels() * plane + i];
+  const FlowLatticeSequence lattice = solver->GetFlowLattice();
+  std::printf("Estimated flow motion of %d frames from the low-resolution images; %.1f %% of the pixels are valid.\n",
+              lattice.GetNumMotions(), 100.0 * kept / static_cast<double>(f->flow_valid.size()));
+  if (!o.save_flow_lattice_path.empty() && !lattice.SaveToFile(o.save_flow_lattice_path)) return app::CannotWrite(o.save_flow_lattice_path);
+  if (!o.save_flow_path.empty()) {
+    const cv::Size hr = f->initial_estimate.GetImageSize();
+    if (!lattice.Expand(hr.width, hr.height).SaveToFile(o.save_flow_path)) return app::CannotWrite(o.save_flow_path);
   }
   return 0;
 }
@@ -535,9 +591,13 @@ int main(int argc, char** argv) {
 
   ImageModelParameters solver_parameters = options.model.parameters;
   if (EstimateMotion(options, &frames, &solver_parameters)) return 1;
-  const ImageModel solver_model = options.registration.empty() ? image_model : ImageModel::CreateImageModel(solver_parameters);
+  // --flow_lattice_path: the solver never holds the expanded field, on the host or on the device
+  if (!frames.flow_lattice.Empty()) solver_parameters.flow_motion_sequence = FlowMotionSequence();
+  const bool own_model = !options.registration.empty() || !frames.flow_lattice.Empty();
+  const ImageModel solver_model = own_model ? ImageModel::CreateImageModel(solver_parameters) : image_model;
 
   IRLSMapSolver solver(options.solver, solver_model, frames.low_res_images, options.verbose);
+  if (InstallLattice(options, &frames, &solver)) return 1;
   SetUpSolver(options, frames, &solver);
   if (CalibrateSolver(options, frames, &solver)) return 1;
 

@@ -23,6 +23,7 @@
 #include "image_model/image_model.h"
 #include "image_model/photometric.h"
 #include "motion/affine_motion.h"
+#include "motion/flow_lattice.h"
 #include "optimization/objective_function.h"
 #include "optimization/regularizer.h"
 #include "util/srmap_host.h"
@@ -460,6 +461,38 @@ class IRLSMapSolver : public MapSolver {
     std::vector<double> quality(3 * static_cast<size_t>(GetNumImages()), 0.0);
     srmap_host::Check(srmap_problem_register_flow(problem_.get(), channel, options, prior ? 1 : 0, quality.data()),
                       "srmap_problem_register_flow");
+    return quality;
+  }
+  // Installs a displacement field on a control lattice as the solver's motion (srmap_problem_set_flow_lattice): it replaces
+  // whatever motion the model gave, and evaluates bit for bit as the model over lattice.Expand(HR size) does.  An empty
+  // sequence restores the model's motion.  The lattice holds at least one frame per observation; the rest is dropped.  Not
+  // in the reference.
+  void SetFlowLattice(const FlowLatticeSequence& lattice) {
+    if (lattice.Empty()) {
+      srmap_host::Check(srmap_problem_set_flow_lattice(problem_.get(), 0, 0, 0, nullptr), "srmap_problem_set_flow_lattice");
+      return;
+    }
+    if (lattice.GetNumMotions() < GetNumImages()) srmap_host::Fail("flow lattice: fewer frames than observations");
+    srmap_host::Check(srmap_problem_set_flow_lattice(problem_.get(), lattice.GetStep(), lattice.GetLatticeWidth(), lattice.GetLatticeHeight(),
+                                                     lattice.Flat().data()),
+                      "srmap_problem_set_flow_lattice");
+  }
+  // The lattice in force; empty when none is set.  Not in the reference.
+  FlowLatticeSequence GetFlowLattice() const {
+    int step = 0, lw = 0, lh = 0;
+    srmap_host::Check(srmap_problem_get_flow_lattice(problem_.get(), &step, &lw, &lh, nullptr), "srmap_problem_get_flow_lattice");
+    if (step == 0) return FlowLatticeSequence();
+    std::vector<double> nodes(static_cast<size_t>(GetNumImages()) * 2 * lw * lh);
+    srmap_host::Check(srmap_problem_get_flow_lattice(problem_.get(), &step, &lw, &lh, nodes.data()), "srmap_problem_get_flow_lattice");
+    return FlowLatticeSequence(nodes, step, lw, lh);
+  }
+  // RegisterFlow that stops at the input level (srmap_problem_register_flow_lattice): the estimate is installed as a
+  // lattice with step = the scale on the LR grid, without forming the HR field.  Not in the reference.
+  std::vector<double> RegisterFlowLattice(const int channel = -1, const srmap_flow_registration_options* options = nullptr,
+                                          const bool prior = true) {
+    std::vector<double> quality(3 * static_cast<size_t>(GetNumImages()), 0.0);
+    srmap_host::Check(srmap_problem_register_flow_lattice(problem_.get(), channel, options, prior ? 1 : 0, quality.data()),
+                      "srmap_problem_register_flow_lattice");
     return quality;
   }
 

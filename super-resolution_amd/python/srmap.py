@@ -107,6 +107,9 @@ _SIGNATURES = [
     ("srmap_problem_set_flow", C.c_int, [C.c_void_p, c_double_p]),
     ("srmap_problem_set_flow_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("srmap_problem_get_flow", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_int)]),
+    ("srmap_problem_set_flow_lattice", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p]),
+    ("srmap_problem_set_flow_lattice_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("srmap_problem_get_flow_lattice", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p]),
     ("srmap_problem_set_blur_kernel", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     ("srmap_problem_get_blur_kernel", C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_double_p]),
     ("srmap_blur_fit_options_default", None, [C.c_void_p]),
@@ -162,6 +165,7 @@ _SIGNATURES = [
     ("srmap_register_flow", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_register_flow_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p]),
     ("srmap_problem_register_flow", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_double_p]),
+    ("srmap_problem_register_flow_lattice", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_double_p]),
     ("srmap_motion_refinement_options_default", None, [C.c_void_p]),
     ("srmap_refine_motion", C.c_int, [C.c_void_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_refine_motion_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p, c_double_p]),
@@ -381,6 +385,24 @@ def flow_from_affine(matrices, H, W):
     return out
 
 
+def flow_lattice_expand(nodes, step, H, W, dtype=F64):
+    """The dense field [K][2][H][W] of the lattice nodes [K][2][lh][lw] at `step` HR pixels between nodes, as the kernels
+    interpolate it (srmap_problem_set_flow_lattice): bilinear at (x, y) / step clamped to the lattice, in double, rounded
+    once to `dtype` (F32 or F64) and returned as doubles -- what Problem.set_flow then stores unchanged."""
+    n = np.asarray(nodes, dtype=np.float64)
+    lh, lw = n.shape[-2:]
+    assert step >= 1 and lw >= 2 and lh >= 2
+    cx = np.clip(np.arange(W, dtype=np.float64) / float(step), 0.0, lw - 1.0)
+    cy = np.clip(np.arange(H, dtype=np.float64) / float(step), 0.0, lh - 1.0)
+    xi = np.minimum(np.floor(cx).astype(np.int64), lw - 2)
+    yi = np.minimum(np.floor(cy).astype(np.int64), lh - 2)
+    fx, fy = (cx - xi)[None, :], (cy - yi)[:, None]
+    Y, X = yi[:, None], xi[None, :]
+    v = ((1 - fy) * ((1 - fx) * n[..., Y, X] + fx * n[..., Y, X + 1]) +
+         fy * ((1 - fx) * n[..., Y + 1, X] + fx * n[..., Y + 1, X + 1]))
+    return v.astype(np.float32).astype(np.float64) if dtype == F32 else v
+
+
 def default_irls_options():
     o = IrlsOptions()
     load().srmap_irls_options_default(C.byref(o))
@@ -459,6 +481,38 @@ class Problem:
         out = np.empty((self.K, 2, self.H, self.W))
         self.ctx.check(load().srmap_problem_get_flow(self._h, out.ctypes.data_as(c_double_p), C.byref(v)))
         return out
+
+    def set_flow_lattice(self, nodes, step, stream=None):
+        """The displacement field on a control lattice: nodes [K][2][lh][lw] doubles, node (i, j) at HR pixel
+        (i step, j step); the kernels interpolate u (flow_lattice_expand).  A host array or a device tensor of doubles
+        (anything with data_ptr(); read on `stream`, None = the context's).  None restores the motion the problem was
+        created with.  Lattice, dense flow and affine motion are alternatives: setting one replaces the others."""
+        if nodes is None:
+            self.ctx.check(load().srmap_problem_set_flow_lattice(self._h, 0, 0, 0, None))
+            return
+        on_device = hasattr(nodes, "data_ptr")
+        if not on_device:
+            nodes = np.asarray(nodes, dtype=np.float64)
+        shape = tuple(nodes.shape)
+        assert len(shape) == 4 and shape[0] == self.K and shape[1] == 2, shape
+        lh, lw = shape[2], shape[3]
+        if on_device:
+            assert nodes.is_contiguous() and str(nodes.dtype).endswith("float64"), "a device lattice is float64"
+            self.ctx.check(load().srmap_problem_set_flow_lattice_device(self._h, step, lw, lh, C.c_void_p(nodes.data_ptr()),
+                                                                        C.c_void_p(stream or 0)))
+        else:
+            a, pa = _d(nodes)
+            self.ctx.check(load().srmap_problem_set_flow_lattice(self._h, step, lw, lh, pa))
+
+    def flow_lattice(self):
+        """(nodes [K][2][lh][lw] doubles, step) of the lattice in force, or None when none is set."""
+        st, lw, lh = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_flow_lattice(self._h, C.byref(st), C.byref(lw), C.byref(lh), None))
+        if not st.value:
+            return None
+        out = np.empty((self.K, 2, lh.value, lw.value))
+        self.ctx.check(load().srmap_problem_get_flow_lattice(self._h, C.byref(st), C.byref(lw), C.byref(lh), out.ctypes.data_as(c_double_p)))
+        return out, st.value
 
     def set_blur_kernel(self, taps):
         """Free-form blur kernel [ksize][ksize] (odd, 1...7; the forward model correlates with it, the adjoint is its flip in
@@ -656,6 +710,20 @@ class Problem:
         q = np.zeros((self.K, 3))
         try:
             self.ctx.check(load().srmap_problem_register_flow(self._h, channel, C.byref(o), 1 if prior else 0, q.ctypes.data_as(c_double_p)))
+        except SrmapError as e:
+            e.quality = q
+            raise
+        return q
+
+    def register_flow_lattice(self, channel=-1, init=None, prior=True, hr_scale=1, warps=8, window_radius=4, damping=0.05,
+                              smooth_radius=2, valid_margin=3, max_levels=0, struct_size=None):
+        """srmap_problem_register_flow_lattice: register_flow that stops at the input level and installs the estimate as
+        a lattice (step = scale on the LR grid), without forming the HR field.  Returns the quality [K][3], also when the
+        lattice is refused (SrmapError with .quality set)."""
+        o, keep = _flow_options(self.K, hr_scale, init, warps, window_radius, damping, smooth_radius, valid_margin, max_levels, struct_size)
+        q = np.zeros((self.K, 3))
+        try:
+            self.ctx.check(load().srmap_problem_register_flow_lattice(self._h, channel, C.byref(o), 1 if prior else 0, q.ctypes.data_as(c_double_p)))
         except SrmapError as e:
             e.quality = q
             raise
