@@ -330,6 +330,12 @@ int srmap_set_observations_device(srmap_problem* p, const void* lr_dev, void* hi
 int srmap_add_regularizer(srmap_problem* p, int kind, double lambda,
                           int btv_range, double btv_decay, int* reg_index);
 int srmap_clear_regularizers(srmap_problem* p);
+/* The regularization_parameter of regulariser `reg` (the handle srmap_add_regularizer gave), changed in place: the kind,
+ * the BTV constants and the IRLS weights stay as they are.  No reference counterpart (the reference fixes it at
+ * AddRegularizer).  lambda must be finite and >= 0, the handle must exist: SRMAP_EINVAL otherwise.  Waits for the
+ * evaluations in flight and re-plans as srmap_add_regularizer does. */
+int srmap_problem_set_regularizer_lambda(srmap_problem* p, int reg, double lambda);
+int srmap_problem_get_regularizer_lambda(const srmap_problem* p, int reg, double* lambda);
 /* The irls_weights_ vector an ObjectiveIRLSRegularizationTerm holds
  * (objective_irls_regularization_term.h:40); NULL = all ones. */
 int srmap_set_irls_weights(srmap_problem* p, int reg, const double* w_host);
@@ -421,6 +427,49 @@ int srmap_problem_get_huber_delta(srmap_problem* p, int* mode, double* delta, do
  * (NULL = the context's).  Complete on return.  Without observations: SRMAP_EINVAL. */
 int srmap_residual_scale(srmap_problem* p, const double* x_host, double* scales /* 1 + K */, double* counts /* 1 + K, optional */);
 int srmap_residual_scale_device(srmap_problem* p, const void* x_dev, void* hip_stream, double* scales, double* counts);
+
+/* ------------------------------------------- hold-out validation (mask, score) */
+/* A hold-out keeps a pseudo-random share of the observations out of the data term, so that how well A x predicts them
+ * measures a solve without the ground truth (no reference counterpart).  Observation i -- the flat index
+ * into the whole problem's [K][C][h][w], as a 64-bit unsigned integer, the same under a split_channels view -- is held out
+ * iff (z >> 40) < T, T = floor(fraction * 2^24) formed in double, and (mod 2^64)
+ *     z = i + seed * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *     z ^= z >> 31.
+ * fraction must be in (0, 0.5] with T >= 1; 0 lifts the hold-out; anything else: SRMAP_EINVAL.  The hold-out is a factor
+ * of the data prior: while it is set, everything that reads the prior -- the evaluation kernels through the effective
+ * weights, a Huber step, the count rule of the residual scale, the fits -- sees m .* (1 - h) (m = ones without a prior),
+ * formed once by an elementwise kernel; srmap_get_data_prior still returns the caller's m, srmap_get_data_weights the
+ * effective weights (0 where held out).  A problem with a hold-out evaluates and solves bit for bit as one whose caller set
+ * the prior m .* (1 - h) itself, and is weighted in every respect stated at srmap_set_data_weights.  It persists across
+ * srmap_set_observations and the weight, prior, loss, motion, blur and photometric calls; lifting it restores the weights
+ * as they would be without it and frees what it allocated.  Solves and evaluations sharded over a communicator of more
+ * than one rank answer SRMAP_EUNSUPPORTED.  As under a prior, the caller's weights are kept in a second buffer while a hold-out
+ * is set; a HUBER loss owns the weight buffer (srmap_problem_set_data_loss), so when a hold-out is set under HUBER, or the
+ * loss returns from HUBER to L2, that buffer holds the last Huber weights: set the weights again (NULL for none) after
+ * leaving HUBER -- the effective weights and the L2 base weight of srmap_holdout_score are formed from it. */
+int srmap_problem_set_holdout(srmap_problem* p, double fraction, unsigned long long seed);
+/* The hold-out in force: *fraction (0: none) and *seed; mask_out ([K][C][h][w] doubles, 1 = held out) as the device
+ * computes it; counts[0] the held-out observations, counts[1 + k] those of frame k.  Every output is optional. */
+int srmap_problem_get_holdout(srmap_problem* p, double* fraction, unsigned long long* seed, double* mask_out /* optional */,
+                              double* counts /* 1 + K, optional */);
+/* The score of the held-out observations at x: one forward-residual pass (as srmap_residual_scale's: every model state)
+ * and ONE streaming launch that recomputes h from the index and accumulates, per frame and in a fixed order without
+ * atomics (bit-identical from run to run), over the held-out observations
+ *     S1 = sum u rho(r),  S2 = sum u rho(r)^2,  S0 = sum u,  n = #{u > 0},        r = A x - y~
+ * (y~ as at srmap_residual_scale).  u is the BASE weight: what the observation would weigh were it not held out, before
+ * any Huber factor -- under L2 the caller's prior times the caller's weights (each 1 when absent, the product rounded once
+ * in the problem's dtype), under HUBER the caller's prior.  rho: delta == 0: r^2;  delta > 0: the Huber function, r^2 for
+ * |r| <= delta and 2 delta |r| - delta^2 beyond (under outliers the mean squared residual is dominated by the corrupted
+ * held-out pixels and says nothing);  delta < 0: "the problem's" -- 0 under L2, the fixed delta under HUBER / FIXED, the
+ * last Huber step's delta under MAD, read on the device from that step's record (SRMAP_EINVAL if no step has run since the
+ * loss and the scale rule in force were set).
+ * score[0] = sum_k S1_k / sum_k S0_k with the frames added in index order, score[1 + k] = S1_k / S0_k (0 where S0_k = 0);
+ * sums (optional): (1 + K) x 4 doubles {S1, S2, S0, n}, row 0 the totals -- S2 and n let a caller form a standard error.
+ * The rows of srmap_problem_set_cost_rows do not apply: the score covers the whole frames.  Without observations, without
+ * a hold-out, or when no held-out observation has a base weight above 0: SRMAP_EINVAL.  x_host: [C][H][W] doubles; the
+ * device form takes the problem dtype, read on hip_stream (NULL = the context's).  Complete on return. */
+int srmap_holdout_score(srmap_problem* p, const double* x_host, double delta, double* score /* 1 + K */, double* sums /* (1 + K) x 4, optional */);
+int srmap_holdout_score_device(srmap_problem* p, const void* x_dev, void* hip_stream, double delta, double* score, double* sums);
 
 /* ------------------------------------------------------- operators (host) */
 /* ImageModel::ApplyToImage(ImageData*, index) image_model.cpp:86-91:
@@ -870,6 +919,37 @@ typedef struct {
  * environment variable. */
 int srmap_solve(srmap_problem* p, const srmap_irls_options* options,
                 const double* x0, double* x_out, srmap_solve_report* report);
+
+/* The regularisation weight by hold-out validation (no reference counterpart): one solve per multiplier
+ * of the problem's lambdas, each scored on the held-out observations, and the best kept.  Needs a hold-out
+ * (srmap_problem_set_holdout), at least one regulariser with lambda > 0 and observations: SRMAP_EINVAL otherwise, the
+ * message naming the missing call.  scales[0 .. num_scales): finite, > 0, strictly decreasing multipliers applied to the
+ * lambda of EVERY regulariser as it stands at the call.  Row j: the lambdas are set (srmap_problem_set_regularizer_lambda),
+ * srmap_solve's loop runs from x0 -- always from x0: warm starts cost more evaluations than they save --, and the
+ * solution is scored (srmap_holdout_score) with the path's delta: 0 under L2; the problem's under HUBER / FIXED; under
+ * HUBER / MAD the delta of the last Huber step of row 0, held for every row so that the rows are comparable.  Row j is bit
+ * for bit what the caller gets from those three calls.  patience: 0 runs every row; n > 0 stops after the score rose n
+ * rows in a row.  *chosen: the FIRST minimum of the score, so a tie goes to the larger lambda.  final_solve != 0: the
+ * hold-out is lifted, the chosen lambdas are set and one more solve from x0 on ALL observations gives x_out (bit for bit
+ * srmap_problem_set_holdout(0), srmap_solve), then the hold-out is set again; final_solve == 0: x_out is the chosen row's
+ * solution.  On return the chosen lambdas stay set and the hold-out is as it was; on an error the lambdas of the call's
+ * start are restored.  x0 is staged once; the iterates and the best solution so far stay on the device.
+ * table: num_scales rows of SRMAP_LAMBDA_PATH_ROW doubles, *rows_run of them written:
+ *   {scale, score, S1, S2, S0, n, IRLS rounds, inner iterations, evaluations, final cost, delta used}.
+ * final_report (optional): the final solve's report, or the chosen row's without one. */
+#define SRMAP_LAMBDA_PATH_MAX_SCALES 32
+#define SRMAP_LAMBDA_PATH_ROW 11
+typedef struct {
+  int struct_size;   /* filled by srmap_lambda_path_options_default(); another size is refused */
+  int num_scales;    /* 8 */
+  double scales[SRMAP_LAMBDA_PATH_MAX_SCALES]; /* 1, 1/2, ..., 1/128 */
+  int patience;      /* 0 */
+  int final_solve;   /* 1 */
+} srmap_lambda_path_options;
+void srmap_lambda_path_options_default(srmap_lambda_path_options* options);
+int srmap_solve_lambda_path(srmap_problem* p, const srmap_irls_options* irls_options /* NULL = defaults */,
+                            const srmap_lambda_path_options* path_options /* NULL = defaults */, const double* x0, double* x_out,
+                            double* table, int* rows_run, int* chosen, srmap_solve_report* final_report);
 
 /* Self-check of the solver's derived sums (no reference counterpart).  mincg forms the DY / HS betas with the
  * denominator y.dk summed over the vectors (optimization.cpp:17700-17760); this solver derives it from sums it already

@@ -159,6 +159,83 @@ int DataWeights::rebuild(srmap_problem* p, hipStream_t st) {
   return SRMAP_OK;
 }
 
+// The first prior of a problem: the weights in force become the caller's factor, eff the product's buffer.  Allocates
+// prior_ (contents for the caller to write) and the product; a failure leaves the problem as it was
+int DataWeights::enter_prior(srmap_problem* p, hipStream_t st) {
+  const size_t bytes = p->lr_count() * p->elem();
+  DevBuf m, product;
+  if (m.alloc(bytes) != hipSuccess || product.alloc(bytes) != hipSuccess)
+    return set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed (data prior: 2 x %zu bytes)", bytes);
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  prior_ = std::move(m);
+  user_ = std::move(eff_);  // possibly none (ones)
+  eff_ = std::move(product);
+  return SRMAP_OK;
+}
+
+// Removing the prior: the product is freed; the caller's weights as given, or none: the unweighted kernels again
+int DataWeights::leave_prior(srmap_problem* p, hipStream_t st) {
+  SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+  prior_.reset();
+  eff_ = std::move(user_);
+  return loss_ == SRMAP_DATA_LOSS_HUBER ? ensure_ones(p, st) : SRMAP_OK;
+}
+
+// prior <- caller's m (ones without one) .* (1 - h) on st: a problem with a hold-out only
+int DataWeights::form_held_prior(srmap_problem* p, hipStream_t st) {
+  return dispatch_dtype(p->dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_holdout_prior<T>(p, caller_.as<const T>(), prior_.as<T>(), p->lr_count(), hold_.seed, hold_.threshold, st);
+  });
+}
+
+int DataWeights::set_holdout(srmap_problem* p, const Holdout& h) {
+  const hipStream_t st = p->ctx->stream;
+  int rc = state_begin_write(p, st);
+  if (rc) return rc;
+  const bool was = robust();
+  if (h.threshold == 0) {  // lift it
+    if (!hold_.threshold) return SRMAP_OK;
+    holdout_pass_release(p);  // a score is complete on return: nothing of it is in flight
+    p->holdout_counts.clear();
+    if (caller_) {  // the caller's prior again, as it was given
+      SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+      prior_ = std::move(caller_);
+      hold_ = Holdout();
+      rc = rebuild(p, st);
+    } else {
+      hold_ = Holdout();
+      rc = leave_prior(p, st);
+    }
+    replan_if(p, was);
+    return rc;
+  }
+  if (!hold_.threshold) {
+    if (prior_) {  // the caller's prior moves aside, the product takes its place
+      DevBuf product;
+      if (product.alloc(p->lr_count() * p->elem()) != hipSuccess)
+        return set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed (hold-out: %zu bytes)", p->lr_count() * p->elem());
+      SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+      caller_ = std::move(prior_);
+      prior_ = std::move(product);
+    } else {
+      rc = enter_prior(p, st);
+      if (rc) return rc;
+    }
+  }
+  const Holdout before = hold_;
+  hold_ = h;
+  p->holdout_counts.clear();
+  rc = form_held_prior(p, st);
+  if (rc == SRMAP_OK) rc = rebuild(p, st);  // complete on return
+  if (rc != SRMAP_OK && before.threshold) {  // the factor in force again (a failed launch: best effort, the first error stands)
+    hold_ = before;
+    if (form_held_prior(p, st) == SRMAP_OK) (void)rebuild(p, st);
+  }
+  replan_if(p, was);
+  return rc;
+}
+
 int DataWeights::set_user(srmap_problem* p, const WeightSource& src) {
   const hipStream_t st = src.st;
   int rc = state_begin_write(p, st);
@@ -183,24 +260,27 @@ int DataWeights::set_prior(srmap_problem* p, const WeightSource& src) {
   int rc = state_begin_write(p, st);
   if (rc) return rc;
   const bool was = robust();
+  if (hold_.threshold) {  // beside a hold-out the caller's m is kept apart; what the kernels read is its product with 1 - h
+    if (src.none()) {
+      if (!caller_) return SRMAP_OK;
+      SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+      caller_.reset();
+    } else {
+      rc = write_factor(p, &caller_, src);
+      if (rc) return rc;
+    }
+    rc = form_held_prior(p, st);
+    return rc ? rc : rebuild(p, st);
+  }
   if (src.none()) {
     if (!prior_) return SRMAP_OK;
-    SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-    prior_.reset();
-    eff_ = std::move(user_);  // the product is freed; the caller's weights as given, or none: the unweighted kernels again
-    if (loss_ == SRMAP_DATA_LOSS_HUBER) rc = ensure_ones(p, st);
+    rc = leave_prior(p, st);
     replan_if(p, was);
     return rc;
   }
-  if (!prior_) {  // the first prior: the weights in force become the caller's factor, eff the product's buffer
-    const size_t bytes = p->lr_count() * p->elem();
-    DevBuf m, product;
-    if (m.alloc(bytes) != hipSuccess || product.alloc(bytes) != hipSuccess)
-      return set_error(p->ctx, SRMAP_ENOMEM, "hipMalloc failed (data prior: 2 x %zu bytes)", bytes);
-    SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-    prior_ = std::move(m);
-    user_ = std::move(eff_);  // possibly none (ones)
-    eff_ = std::move(product);
+  if (!prior_) {
+    rc = enter_prior(p, st);
+    if (rc) return rc;
   }
   rc = write_factor(p, &prior_, src);
   if (rc) return rc;
@@ -211,6 +291,7 @@ int DataWeights::set_prior(srmap_problem* p, const WeightSource& src) {
 
 int DataWeights::set_loss(srmap_problem* p, int loss, double huber_delta) {
   const bool was = robust();
+  if (loss != loss_) mad_recorded_ = false;  // the record of a step belongs to the loss it ran under
   loss_ = loss;
   delta_ = loss == SRMAP_DATA_LOSS_HUBER ? huber_delta : 0.0;
   int rc = SRMAP_OK;
@@ -261,6 +342,7 @@ int DataWeights::huber_step(srmap_problem* p, int c0, int C, const void* x, hipS
                                            tuning_, min_delta_, st))
         return r;
       delta_dev = residual_scale_record(p, 0);
+      mad_recorded_ = true;
     }
     return launch_huber_weights<T>(p, p->d_resid.as<const T>(), eff_.as<T>() + (size_t)c0 * nl, (size_t)geo.K, (size_t)geo.C * nl,
                                    (size_t)geo.C * nl, (size_t)p->geo.C * nl, delta_, st, prior, delta_dev);
@@ -318,7 +400,7 @@ static int download_or_ones(srmap_problem* p, const void* dev, double* host) {
 
 int srmap_get_data_prior(srmap_problem* p, double* m_host, int* is_set) {
   if (!p) return SRMAP_EINVAL;
-  const void* m = p->dw.prior<void>();
+  const void* m = p->dw.caller_prior<void>();  // under a hold-out still what the caller set
   if (is_set) *is_set = m ? 1 : 0;
   if (!m_host) return SRMAP_OK;
   if (m) SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));

@@ -203,6 +203,7 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
 void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
   ztile_release(p);
+  holdout_pass_release(p);
   if (p->state_ev) (void)hipEventDestroy(p->state_ev);
   delete p;  // and every device buffer it owns
 }
@@ -391,6 +392,25 @@ int srmap_add_regularizer(srmap_problem* p, int kind, double lambda, int btv_ran
   if (reg_index) *reg_index = p->nreg;
   p->nreg++;
   model_replan(p);
+  return SRMAP_OK;
+}
+
+int srmap_problem_set_regularizer_lambda(srmap_problem* p, int reg, double lambda) {
+  if (!p) return SRMAP_EINVAL;
+  if (reg < 0 || reg >= p->nreg) return set_error(p->ctx, SRMAP_EINVAL, "no regularizer %d (the problem has %d)", reg, p->nreg);
+  if (!(lambda >= 0.0 && std::isfinite(lambda)))
+    return set_error(p->ctx, SRMAP_EINVAL, "the regularization parameter must be finite and >= 0 (got %g)", lambda);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  if (int rc = model_drain(p)) return rc;
+  p->reg[reg].lambda = lambda;  // the IRLS weights stay as they are
+  model_replan(p);
+  return SRMAP_OK;
+}
+
+int srmap_problem_get_regularizer_lambda(const srmap_problem* p, int reg, double* lambda) {
+  if (!p || !lambda) return SRMAP_EINVAL;
+  if (reg < 0 || reg >= p->nreg) return set_error(p->ctx, SRMAP_EINVAL, "no regularizer %d (the problem has %d)", reg, p->nreg);
+  *lambda = p->reg[reg].lambda;
   return SRMAP_OK;
 }
 

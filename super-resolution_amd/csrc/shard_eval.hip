@@ -16,6 +16,9 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what) {
   if (mode == SRMAP_SHARD_NONE) return SRMAP_OK;
   const bool solve = std::strcmp(what, "solve") == 0;
   const char* tail = solve ? "run the solve unsharded" : "evaluate unsharded";
+  if (p->dw.holdout().threshold)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a hold-out is not sharded over a communicator%s: %s",
+                     solve ? " (the held-out observations are a function of the whole problem's index)" : "", tail);
   if (p->dw.robust())
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator%s: %s",
                      solve ? " (the weights are not split with the frames or rows)" : "", tail);

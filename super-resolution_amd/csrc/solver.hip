@@ -686,7 +686,8 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
 
 template <typename T>
 static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, const srmap_irls_options* opt,
-                       const double* x0, double* x_out, srmap_solve_report* report) {
+                       const double* x0, double* x_out, srmap_solve_report* report, const void* x0_dev = nullptr,
+                       void* x_out_dev = nullptr) {
   if (!p->have_obs) return set_error(p->ctx, SRMAP_EINVAL, "cannot super-resolve with 0 low-res images");
   const Geometry& geo = p->geo;
   const size_t N = (size_t)geo.W * geo.H;
@@ -764,7 +765,10 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     if (opt->split_channels) { cg.view.c0 = c0; cg.view.C = per_split; }
     Geometry vg = geo;
     vg.C = per_split;
-    rc = convert_upload(p, x0 + (size_t)c0 * N, cg.x, npts, st);
+    // the start: the caller's host doubles rounded to the dtype, or (solve_device) an image that already holds them so
+    if (!x0_dev) rc = convert_upload(p, x0 + (size_t)c0 * N, cg.x, npts, st);
+    else if (hipMemcpyAsync(cg.x, (const T*)x0_dev + (size_t)c0 * N, npts * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      rc = set_error(p->ctx, SRMAP_EHIP, "solve: the copy of the start failed: %s", hipGetErrorString(hipGetLastError()));
     if (rc) break;
     // w <- 1  (irls_map_solver.cpp:66-74)
     for (int r = 0; r < p->nreg; ++r)
@@ -812,7 +816,13 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     rep.irls_rounds += ran;
     rc = shard_exchange_x(p, comm, mode == SRMAP_SHARD_NONE ? nullptr : shard, cg.x, st);  // x_out carries valid halos
     if (rc) break;
-    rc = convert_download(p, cg.x, x_out + (size_t)c0 * N, npts, st);
+    if (x_out_dev) {
+      if (hipMemcpyAsync((T*)x_out_dev + (size_t)c0 * N, cg.x, npts * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        rc = set_error(p->ctx, SRMAP_EHIP, "solve: the copy of the result failed: %s", hipGetErrorString(hipGetLastError()));
+    } else {
+      rc = convert_download(p, cg.x, x_out + (size_t)c0 * N, npts, st);
+    }
   }
   rep.evaluations = cg.evaluations;
   rep.wait_seconds = cg.wait_seconds;
@@ -893,11 +903,12 @@ void srmap_irls_options_default(srmap_irls_options* o) {
   o->host_paced_passes = 0;
 }
 
-int srmap_solve_sharded(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
-                        const srmap_irls_options* options, const double* x0, double* x_out,
-                        srmap_solve_report* report) {
-  if (!p || !x0 || !x_out) return SRMAP_EINVAL;
-  srmap_irls_options o;
+}  // extern "C"
+
+namespace srmap {
+
+int irls_options_in_force(srmap_problem* p, const srmap_irls_options* options, srmap_irls_options* out) {
+  srmap_irls_options& o = *out;
   if (options) {
     // the first member is the size of the struct the caller was compiled with: another layout is refused, not guessed at
     if (options->struct_size != (int)sizeof(srmap_irls_options))
@@ -907,6 +918,25 @@ int srmap_solve_sharded(srmap_problem* p, srmap_comm* comm, const srmap_shard_de
   } else {
     srmap_irls_options_default(&o);
   }
+  return SRMAP_OK;
+}
+
+int solve_device(srmap_problem* p, const srmap_irls_options* opt, const void* x0_dev, void* x_out_dev, srmap_solve_report* report) {
+  return dispatch_dtype(p->dtype, [&](auto t) {
+    return solve_typed<decltype(t)>(p, nullptr, nullptr, opt, nullptr, nullptr, report, x0_dev, x_out_dev);
+  });
+}
+
+}  // namespace srmap
+
+extern "C" {
+
+int srmap_solve_sharded(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard,
+                        const srmap_irls_options* options, const double* x0, double* x_out,
+                        srmap_solve_report* report) {
+  if (!p || !x0 || !x_out) return SRMAP_EINVAL;
+  srmap_irls_options o;
+  if (int rc = irls_options_in_force(p, options, &o)) return rc;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
   return dispatch_dtype(p->dtype, [&](auto t) { return solve_typed<decltype(t)>(p, comm, shard, &o, x0, x_out, report); });
 }

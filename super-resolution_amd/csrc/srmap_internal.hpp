@@ -131,6 +131,8 @@ struct EvalOut {
   bool published = false;  // its finish kernel published {cost, g.d} and the tag (EvalReq::pub)
 };
 
+struct FitPass;  // below
+
 }  // namespace srmap
 
 struct srmap_ctx {
@@ -208,6 +210,12 @@ struct srmap_problem {
   // the residual scale's select (residual_scale.hip), allocated on first use: the workgroups' histogram slabs, the K + 1
   // selection states, and two records {delta, scales[1 + K], counts[1 + K]} (doubles): the last Huber step's, the diagnostic's
   srmap::DevBuf d_sel_slabs, d_sel_state, d_sel_rec;
+  // the hold-out score's pass (holdout.hip), allocated by the first score and freed when the hold-out is lifted: the
+  // records of its workgroups and the K rows of four sums
+  srmap::FitPass* holdout_pass = nullptr;
+  // the 1 + K counts of held-out observations, formed by the first srmap_problem_get_holdout that asks for them and kept
+  // until the hold-out changes (empty: not formed)
+  std::vector<double> holdout_counts;
   srmap::DevBuf d_regvals;        // [C][H][W] dtype scratch
   srmap::DevBuf d_x;              // [C][H][W] staging for host-buffer entry points
   srmap::DevBuf d_g;
@@ -393,6 +401,12 @@ int launch_residual_scale(srmap_problem* p, const T* r, const T* mask, size_t ro
                           double tuning, double min_delta, hipStream_t st);
 size_t residual_scale_record_doubles(int K);
 double* residual_scale_record(srmap_problem* p, int slot);  // device; nullptr before the first select
+// ---- hold-out validation (holdout.hip) ----
+// out[i] = (m ? m[i] : 1) where observation i is kept, 0 where it is held out (holdout_dev.hpp), i < n the flat index into
+// [K][C][h][w]; enqueued on st
+template <typename T>
+int launch_holdout_prior(srmap_problem* p, const T* m, T* out, size_t n, unsigned long long seed, unsigned threshold, hipStream_t st);
+void holdout_pass_release(srmap_problem* p);  // frees the score's pass; the stream that ran it has been waited for
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)
 int photometric_normalise(srmap_problem* p, hipStream_t st);
@@ -474,6 +488,13 @@ int state_end_write(srmap_problem* p, hipStream_t st);
 // A reader of the problem's device state (observations, weights) on st that is not an evaluation (motion_refinement.hip):
 // ordered after the last asynchronous state write, and recorded as the stream a later writer drains
 int problem_state_read(srmap_problem* p, hipStream_t st);
+
+// ---- the solve on device images (solver.hip; lambda_path.hip runs its rows through it) ----
+// the options srmap_solve would run with: the caller's, their struct_size checked, or the defaults
+int irls_options_in_force(srmap_problem* p, const srmap_irls_options* options, srmap_irls_options* out);
+// srmap_solve's loop, unsharded, from x0_dev to x_out_dev ([C][H][W] of the problem dtype; distinct from each other) on
+// the context's stream, complete on return.  A start that holds the caller's doubles rounded to the dtype gives srmap_solve's bits
+int solve_device(srmap_problem* p, const srmap_irls_options* opt, const void* x0_dev, void* x_out_dev, srmap_solve_report* report);
 
 // ---- L-BFGS passes (kernels_lbfgs.hip) ----
 constexpr int kLbfgsMaxM = 8;  // history cap of srmap_problem_set_solver (bounds the update pass's accumulators)

@@ -39,6 +39,11 @@
 #include "optimization/irls_map_solver.h"
 #include "optimization/regularizer.h"
 
+#include <cmath>
+#include <cstdlib>
+
+#include "holdout_host.hpp"  // csrc/: the rules of hold-out validation, plain C++
+
 using namespace super_resolution;
 
 namespace {
@@ -58,6 +63,11 @@ const char kUsage[] =
       "                       re-weighting, instead of --huber_delta)\n"
       "                       [--print_residual_scale] (1.4826 * median|residual| of the result over all frames and per frame:\n"
       "                       a frame that stands out fits badly)\n"
+      "                       [--holdout_fraction=0.1] [--holdout_seed=1] --lambda_path=<largest>:<ratio>:<count>\n"
+      "                       [--lambda_patience=0] [--print_lambda_path] (the regularization parameter by hold-out validation:\n"
+      "                       <count> solves at lambda = <largest> * <ratio>^j with that share of the pixels held out, each\n"
+      "                       scored on the held-out pixels; the result is the solve on all pixels at the best lambda;\n"
+      "                       --regularization_parameter is then unused; --lambda_path needs --holdout_fraction)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
       "                       [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
@@ -130,6 +140,15 @@ struct Options {
   // straight into `solver`), and the per-frame residual scales of the final estimate (srmap_residual_scale)
   std::string huber_scale;
   bool print_residual_scale;
+  // not reference flags: the regularization parameter by hold-out validation (srmap_problem_set_holdout,
+  // srmap_solve_lambda_path); lambda_path is the raw "<largest>:<ratio>:<count>"
+  double holdout_fraction;
+  unsigned long long holdout_seed;
+  std::string holdout_seed_text;
+  std::string lambda_path;
+  int lambda_patience;
+  bool print_lambda_path;
+  bool LambdaPath() const { return !lambda_path.empty(); }
   bool interpolate_color, solve_in_pca_space;
   int num_pca_components;
   double pca_retained_variance;
@@ -199,6 +218,12 @@ Options ParseFlags(int argc, char** argv) {
   o.solver.huber_tuning = flags.Double("huber_tuning", 1.345);
   o.solver.huber_min_delta = flags.Double("huber_min_delta", 1.0e-4);
   o.print_residual_scale = flags.Bool("print_residual_scale", false);
+  o.holdout_fraction = flags.Double("holdout_fraction", 0.0);
+  o.holdout_seed_text = flags.Str("holdout_seed", "1");
+  o.holdout_seed = std::strtoull(o.holdout_seed_text.c_str(), nullptr, 10);
+  o.lambda_path = flags.Str("lambda_path", "");
+  o.lambda_patience = flags.Int("lambda_patience", 0);
+  o.print_lambda_path = flags.Bool("print_lambda_path", false);
   o.interpolate_color = flags.Bool("interpolate_color", false);
   o.solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
   o.num_pca_components = flags.Int("num_pca_components", 0);
@@ -293,6 +318,25 @@ int CheckFlags(const Options& o) {
     return Refuse("--photometric_path gives the parameters, --photometric_rounds fits them: they exclude each other.");
   if (!o.save_photometric_path.empty() && o.photometric_path.empty() && o.photometric_rounds < 0)
     return Refuse("--save_photometric_path needs --photometric_path or --photometric_rounds.");
+  // hold-out validation: refused here, before any GPU work
+  if (o.holdout_fraction != 0.0 && srmap::holdout_threshold(o.holdout_fraction) == 0)
+    return Refuse("--holdout_fraction is in (0, 0.5].");
+  if (o.holdout_seed_text.empty() || o.holdout_seed_text.size() > 19 ||
+      o.holdout_seed_text.find_first_not_of("0123456789") != std::string::npos)
+    return Refuse("--holdout_seed is a non-negative integer of at most 19 digits.");
+  if (o.holdout_seed_text != "1" && o.holdout_fraction == 0.0) return Refuse("--holdout_seed needs --holdout_fraction.");
+  if (o.LambdaPath()) {
+    double largest = 0.0, ratio = 0.0;
+    int count = 0;
+    if (!srmap::holdout_parse_lambda_path(o.lambda_path.c_str(), &largest, &ratio, &count))
+      return Refuse("--lambda_path is <largest>:<ratio>:<count> with largest > 0, 0 < ratio < 1 and 1 <= count <= 32.");
+    if (o.holdout_fraction == 0.0) return Refuse("--lambda_path needs --holdout_fraction.");
+    if (o.lambda_patience < 0) return Refuse("--lambda_patience is >= 0.");
+    if (o.refine_motion_rounds > 0 || o.photometric_rounds >= 0)
+      return Refuse("--lambda_path runs plain solves: not with --refine_motion_rounds or --photometric_rounds.");
+  } else if (o.lambda_patience != 0 || o.print_lambda_path) {
+    return Refuse("--lambda_patience and --print_lambda_path need --lambda_path.");
+  }
   return 0;
 }
 
@@ -454,7 +498,10 @@ int InstallLattice(const Options& o, Frames* f, IRLSMapSolver* solver) {
 
 // --regularizer, and the validity masks of --registration=flow
 void SetUpSolver(const Options& o, const Frames& f, IRLSMapSolver* solver) {
-  if (o.regularization_parameter > 0.0) {
+  double lambda = o.regularization_parameter, ratio = 0.0;
+  int count = 0;
+  if (o.LambdaPath()) srmap::holdout_parse_lambda_path(o.lambda_path.c_str(), &lambda, &ratio, &count);  // the largest: the path scales it
+  if (lambda > 0.0) {
     std::shared_ptr<Regularizer> regularizer;
     if (o.regularizer == "btv") {
       regularizer = std::make_shared<BilateralTotalVariationRegularizer>(f.initial_estimate.GetImageSize(), o.btv_scale_range,
@@ -467,13 +514,15 @@ void SetUpSolver(const Options& o, const Frames& f, IRLSMapSolver* solver) {
       if (o.regularizer == "3dtv") tv->SetUse3dTotalVariation(true);
       regularizer = tv;
     }
-    solver->AddRegularizer(regularizer, o.regularization_parameter);
+    solver->AddRegularizer(regularizer, lambda);
   }
   // --registration=flow: the field is wrong where frame 0 does not hold the content; those pixels get weight 0.  A Huber
   // solve derives its own weights and resets the buffer (include/srmap.h) -- unless the masks are the persistent prior
   // (--flow_valid_prior, srmap_set_data_prior), which a Huber solve resets to and multiplies its weights by
   if (o.RegisterFlow() && o.flow_valid_prior) solver->SetDataPrior(f.flow_valid);
   else if (o.RegisterFlow() && o.solver.data_loss == L2_DATA_LOSS) solver->MultiplyDataWeights(f.flow_valid);
+  // --holdout_fraction: that share of the pixels stays out of the data term (a factor of the prior, whatever the above set)
+  if (o.holdout_fraction != 0.0) solver->SetHoldout(o.holdout_fraction, o.holdout_seed);
 }
 
 // The fits and the photometric model compare the frames with images in the frames' own channels.
@@ -529,6 +578,22 @@ int Solve(const Options& o, const Frames& f, IRLSMapSolver* solver, ImageData* r
     std::printf("Fitted gain and bias of %d frames in %d rounds.\n", fitted.GetNumFrames(), rounds);
   } else if (o.refine_motion_rounds > 0) {
     *result = solver->SolveJoint(f.initial_estimate, rounds, refinement, &refined);
+  } else if (o.LambdaPath()) {
+    double largest = 0.0, ratio = 0.0;
+    int count = 0, chosen = -1;
+    srmap::holdout_parse_lambda_path(o.lambda_path.c_str(), &largest, &ratio, &count);
+    std::vector<double> scales(count), table;
+    for (int j = 0; j < count; ++j) scales[j] = std::pow(ratio, j);
+    *result = solver->SolveLambdaPath(f.initial_estimate, scales, o.lambda_patience, true, &table, &chosen);
+    const size_t rows = table.size() / SRMAP_LAMBDA_PATH_ROW;
+    std::printf("Lambda path: %zu of %d rows, chosen lambda %.9g (row %d, hold-out score %.9g).\n", rows, count,
+                largest * scales[chosen], chosen, table[chosen * SRMAP_LAMBDA_PATH_ROW + 1]);
+    if (o.print_lambda_path)
+      for (size_t j = 0; j < rows; ++j) {
+        const double* r = table.data() + j * SRMAP_LAMBDA_PATH_ROW;
+        std::printf("  lambda %.9g: score %.9g over %.0f held-out pixels, %.0f IRLS rounds, %.0f iterations, %.0f evaluations, "
+                    "final cost %.9g, delta %.9g\n", largest * r[0], r[1], r[5], r[6], r[7], r[8], r[9], r[10]);
+      }
   } else {
     *result = solver->Solve(f.initial_estimate);
   }
@@ -542,6 +607,8 @@ int Solve(const Options& o, const Frames& f, IRLSMapSolver* solver, ImageData* r
   std::printf("Done! Finished in %g seconds.\n", elapsed.count());
   if (o.solver.data_loss == HUBER_DATA_LOSS && o.solver.huber_scale == MAD_HUBER_SCALE)
     std::printf("Huber delta of the last re-weighting: %.9g\n", solver->HuberDelta());
+  if (o.holdout_fraction != 0.0)  // of the final estimate, with the loss the solve ran with
+    std::printf("Hold-out score of the result: %.9g\n", solver->HoldoutScore(*result)[0]);
   if (o.print_residual_scale) {  // of the final estimate, in the space the solve ran in: a frame that stands out fits badly
     const std::vector<double> scales = solver->ResidualScale(*result);
     std::printf("Residual scale (1.4826 median|r|) over all frames: %.9g\n", scales[0]);

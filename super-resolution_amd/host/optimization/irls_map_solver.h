@@ -195,6 +195,79 @@ class IRLSMapSolver : public MapSolver {
   // irls_map_solver.cpp:192-265
   ImageData Solve(const ImageData& initial_estimate) override {
     CheckGeometry(initial_estimate, "initial estimate does not match the HR geometry");
+    const srmap_irls_options o = PrepareSolve();
+    const std::vector<double> x0 = initial_estimate.ToPlanar();
+    std::vector<double> x(x0.size());
+    srmap_host::Check(srmap_solve(problem_.get(), &o, x0.data(), x.data(), &report_), "srmap_solve");
+    ReportSolve();
+    ImageData result;
+    result.FromPlanar(x, GetImageSize(), GetNumChannels());
+    return result;
+  }
+  const srmap_solve_report& GetReport() const { return report_; }
+  // Hold-out validation (srmap_problem_set_holdout; not in the reference): the share `fraction` (0 < fraction <= 0.5) of the
+  // observations, chosen by a hash of (index, seed), is kept out of the data term of every later solve and evaluation;
+  // 0 lifts the hold-out.
+  void SetHoldout(const double fraction, const unsigned long long seed = 1) {
+    srmap_host::Check(srmap_problem_set_holdout(problem_.get(), fraction, seed), "srmap_problem_set_holdout");
+  }
+  // The score of the held-out observations at `estimate` (srmap_holdout_score): 1 + K numbers, [0] over all frames, [1 + k]
+  // of frame k.  delta 0: the mean squared residual; > 0: the mean Huber function; < 0: the loss the solver would solve
+  // with (solver_options: 0 under L2, huber_delta under a fixed Huber scale, the last Huber step's delta under MAD).
+  // sums (optional): (1 + K) x 4 = S1, S2, S0, n.
+  std::vector<double> HoldoutScore(const ImageData& estimate, const double delta = -1.0, std::vector<double>* sums = nullptr) {
+    CheckGeometry(estimate, "estimate does not match the HR geometry");
+    if (delta < 0.0) PrepareSolve();  // "the problem's" loss is the options'
+    const std::vector<double> x = estimate.ToPlanar();
+    std::vector<double> score(1 + static_cast<size_t>(GetNumImages())), s(4 * score.size());
+    srmap_host::Check(srmap_holdout_score(problem_.get(), x.data(), delta, score.data(), s.data()), "srmap_holdout_score");
+    if (sums) *sums = s;
+    return score;
+  }
+  // The regularization parameter of regulariser `index` (the order of AddRegularizer), changed in place
+  // (srmap_problem_set_regularizer_lambda; the reference fixes it at AddRegularizer).
+  void SetRegularizationParameter(const int index, const double regularization_parameter) {
+    srmap_host::Check(srmap_problem_set_regularizer_lambda(problem_.get(), index, regularization_parameter),
+                      "srmap_problem_set_regularizer_lambda");
+  }
+  double GetRegularizationParameter(const int index) const {
+    double lambda = 0.0;
+    srmap_host::Check(srmap_problem_get_regularizer_lambda(problem_.get(), index, &lambda), "srmap_problem_get_regularizer_lambda");
+    return lambda;
+  }
+  // The regularization parameters by hold-out validation (srmap_solve_lambda_path): one solve from initial_estimate per
+  // multiplier in `scales` (strictly decreasing) of every regulariser's parameter, scored on the held-out observations;
+  // the result is the solve on all observations at the chosen parameters (final_solve) or the chosen row's solution.  The
+  // chosen parameters stay set.  table (optional): rows of SRMAP_LAMBDA_PATH_ROW doubles; chosen (optional): the row.
+  ImageData SolveLambdaPath(const ImageData& initial_estimate, const std::vector<double>& scales, const int patience = 0,
+                            const bool final_solve = true, std::vector<double>* table = nullptr, int* chosen = nullptr) {
+    CheckGeometry(initial_estimate, "initial estimate does not match the HR geometry");
+    const srmap_irls_options o = PrepareSolve();
+    srmap_lambda_path_options po;
+    srmap_lambda_path_options_default(&po);
+    if (scales.empty() || scales.size() > SRMAP_LAMBDA_PATH_MAX_SCALES) srmap_host::Fail("SolveLambdaPath: between 1 and 32 scales");
+    po.num_scales = static_cast<int>(scales.size());
+    for (int j = 0; j < SRMAP_LAMBDA_PATH_MAX_SCALES; ++j) po.scales[j] = j < po.num_scales ? scales[j] : 0.0;
+    po.patience = patience;
+    po.final_solve = final_solve ? 1 : 0;
+    const std::vector<double> x0 = initial_estimate.ToPlanar();
+    std::vector<double> x(x0.size()), rows(scales.size() * SRMAP_LAMBDA_PATH_ROW);
+    int rows_run = 0, row = -1;
+    srmap_host::Check(srmap_solve_lambda_path(problem_.get(), &o, &po, x0.data(), x.data(), rows.data(), &rows_run, &row, &report_),
+                      "srmap_solve_lambda_path");
+    rows.resize(static_cast<size_t>(rows_run) * SRMAP_LAMBDA_PATH_ROW);
+    if (table) *table = rows;
+    if (chosen) *chosen = row;
+    if (IsVerbose()) std::cout << "IRLSMapSolver: lambda path, " << rows_run << " rows, chosen scale " << scales[row] << std::endl;
+    ReportSolve();
+    ImageData result;
+    result.FromPlanar(x, GetImageSize(), GetNumChannels());
+    return result;
+  }
+
+ private:
+  // solver_options as srmap_irls_options, and the solver, loss and Huber scale they name set on the problem
+  srmap_irls_options PrepareSolve() {
     srmap_irls_options o;
     srmap_irls_options_default(&o);
     o.max_num_solver_iterations = solver_options_.max_num_solver_iterations;
@@ -225,18 +298,16 @@ class IRLSMapSolver : public MapSolver {
                                                                                                        : -1,
                                                     solver_options_.huber_tuning, solver_options_.huber_min_delta),
                       "srmap_problem_set_huber_scale");
-    const std::vector<double> x0 = initial_estimate.ToPlanar();
-    std::vector<double> x(x0.size());
-    srmap_host::Check(srmap_solve(problem_.get(), &o, x0.data(), x.data(), &report_), "srmap_solve");
+    return o;
+  }
+  void ReportSolve() const {
     if (IsVerbose())
       std::cout << "IRLSMapSolver: " << report_.irls_rounds << " IRLS rounds, " << report_.cg_iterations
                 << (solver_options_.least_squares_solver == LBFGS_SOLVER ? " L-BFGS" : " CG") << " iterations, " << report_.evaluations << " cost+gradient evaluations, final cost "
                 << report_.final_cost << std::endl;
-    ImageData result;
-    result.FromPlanar(x, GetImageSize(), GetNumChannels());
-    return result;
   }
-  const srmap_solve_report& GetReport() const { return report_; }
+
+ public:
   // Joint motion refinement (srmap_refine_motion; not in the reference): the frame matrices re-fitted to `estimate`
   // through the forward model, starting from the solver's current motion, and INSTALLED as the solver's motion (later
   // solves and ComputeAllTerms run the affine model with them).  quality (optional): 4 numbers per frame -- cost at the

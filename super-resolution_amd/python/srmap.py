@@ -73,6 +73,14 @@ class PhotometricFitOptions(C.Structure):
                 ("max_gain", C.c_double), ("apply", C.c_int)]
 
 
+LAMBDA_PATH_MAX_SCALES, LAMBDA_PATH_ROW = 32, 11  # SRMAP_LAMBDA_PATH_MAX_SCALES, SRMAP_LAMBDA_PATH_ROW
+
+
+class LambdaPathOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("num_scales", C.c_int), ("scales", C.c_double * LAMBDA_PATH_MAX_SCALES),
+                ("patience", C.c_int), ("final_solve", C.c_int)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -144,6 +152,15 @@ _SIGNATURES = [
     ("srmap_problem_get_huber_delta", C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p]),
     ("srmap_residual_scale", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     ("srmap_residual_scale_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p]),
+    ("srmap_problem_set_holdout", C.c_int, [C.c_void_p, C.c_double, C.c_ulonglong]),
+    ("srmap_problem_get_holdout", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_ulonglong), c_double_p, c_double_p]),
+    ("srmap_holdout_score", C.c_int, [C.c_void_p, c_double_p, C.c_double, c_double_p, c_double_p]),
+    ("srmap_holdout_score_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    ("srmap_problem_set_regularizer_lambda", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    ("srmap_problem_get_regularizer_lambda", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    ("srmap_lambda_path_options_default", None, [C.c_void_p]),
+    ("srmap_solve_lambda_path", C.c_int, [C.c_void_p, C.POINTER(IrlsOptions), C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(SolveReport)]),
     ("srmap_apply", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_apply_transpose", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_reg_values", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
@@ -757,6 +774,64 @@ class Problem:
         scales, counts = np.zeros(1 + self.K), np.zeros(1 + self.K)
         self._fit("srmap_residual_scale", x, stream, scales.ctypes.data_as(c_double_p), counts.ctypes.data_as(c_double_p))
         return scales, counts
+
+    def set_holdout(self, fraction, seed=1):
+        """srmap_problem_set_holdout: keep the share `fraction` (0 < fraction <= 0.5) of the observations, chosen by a hash
+        of (index, seed), out of the data term; 0 lifts the hold-out."""
+        self.ctx.check(load().srmap_problem_set_holdout(self._h, fraction, seed))
+
+    def holdout(self, want_mask=True):
+        """(fraction, seed, mask [K][C][h][w] of 0 / 1 or None, counts [1 + K]) of the hold-out in force; fraction 0: none."""
+        fr, seed = C.c_double(0.0), C.c_ulonglong(0)
+        mask = np.zeros((self.K, self.C, self.h, self.w)) if want_mask else None
+        counts = np.zeros(1 + self.K)
+        self.ctx.check(load().srmap_problem_get_holdout(self._h, C.byref(fr), C.byref(seed),
+                                                        mask.ctypes.data_as(c_double_p) if want_mask else None,
+                                                        counts.ctypes.data_as(c_double_p)))
+        return fr.value, seed.value, mask, counts
+
+    def holdout_score(self, x, delta=None, stream=None):
+        """srmap_holdout_score at the HR image x (a host array [C][H][W], or a device tensor of the problem's dtype, read on
+        `stream`): (score [1 + K], sums [1 + K][4] = S1, S2, S0, n) over the held-out observations.  delta: 0 = squared
+        residuals, > 0 = the Huber function, None = the problem's."""
+        score, sums = np.zeros(1 + self.K), np.zeros((1 + self.K, 4))
+        self._fit("srmap_holdout_score", x, stream, -1.0 if delta is None else float(delta), score.ctypes.data_as(c_double_p),
+                  sums.ctypes.data_as(c_double_p))
+        return score, sums
+
+    def set_regularizer_lambda(self, reg, lam):
+        """The regularization parameter of regulariser `reg`, changed in place (its IRLS weights stay)."""
+        self.ctx.check(load().srmap_problem_set_regularizer_lambda(self._h, reg, lam))
+
+    def regularizer_lambda(self, reg):
+        v = C.c_double(0.0)
+        self.ctx.check(load().srmap_problem_get_regularizer_lambda(self._h, reg, C.byref(v)))
+        return v.value
+
+    def solve_lambda_path(self, x0, scales, options=None, patience=0, final_solve=True, struct_size=None):
+        """srmap_solve_lambda_path: one solve from x0 per multiplier in `scales` (strictly decreasing) of the problem's
+        lambdas, each scored on the held-out observations.  Returns (x, table [rows_run][11] = scale, score, S1, S2, S0, n,
+        IRLS rounds, iterations, evaluations, final cost, delta used; chosen; report): x is the solve on all observations
+        at the chosen lambdas (final_solve) or the chosen row's solution.  struct_size overrides the options' size field
+        (tests)."""
+        a, pa = _d(x0)
+        assert a.size == self.C * self.H * self.W
+        po = LambdaPathOptions()
+        load().srmap_lambda_path_options_default(C.byref(po))
+        sc = [float(v) for v in scales]
+        po.num_scales = len(sc)
+        for j in range(LAMBDA_PATH_MAX_SCALES):
+            po.scales[j] = sc[j] if j < len(sc) else 0.0
+        po.patience, po.final_solve = patience, 1 if final_solve else 0
+        if struct_size is not None:
+            po.struct_size = struct_size
+        out = np.empty((self.C, self.H, self.W))
+        table = np.zeros((max(1, min(len(sc), LAMBDA_PATH_MAX_SCALES)), LAMBDA_PATH_ROW))
+        rows, chosen, rep = C.c_int(0), C.c_int(-1), SolveReport()
+        o = options if options is not None else default_irls_options()
+        self.ctx.check(load().srmap_solve_lambda_path(self._h, C.byref(o), C.byref(po), pa, out.ctypes.data_as(c_double_p),
+                                                      table.ctypes.data_as(c_double_p), C.byref(rows), C.byref(chosen), C.byref(rep)))
+        return out, table[:rows.value].copy(), chosen.value, rep
 
     def apply(self, hr, k):
         a, pa = _d(hr)
