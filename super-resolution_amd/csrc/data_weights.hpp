@@ -36,7 +36,7 @@
 // hold-out therefore evaluates bit for bit as one whose caller set the prior m .* (1 - h) itself.
 //
 // robust() == (eff is allocated || Huber): every evaluation then runs a WEIGHTED forward kernel, and the tile plan takes
-// its forward-residual form for integer shifts too (kernels_ztile.hip ztile_plan).  A transition re-plans
+// its forward-residual form for integer shifts too (ztile_plan.hip).  A transition re-plans
 // (model_replan) exactly when it changes robust(): into or out of the first row.
 //
 // Writes are ordered as include/srmap.h "Streams" says: a setter drains the last evaluation's stream before it writes

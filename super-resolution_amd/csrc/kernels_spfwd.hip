@@ -245,7 +245,7 @@ __global__ __launch_bounds__(64 * kNW) void k_forward_sp(SpfArgs<T> A) {
 }
 
 template <typename T>
-bool upload_frames(const srmap_problem* p, SpForwardPlan* sp) {
+bool upload_frames(srmap_problem* p, SpForwardPlan* sp) {
   const Geometry& g = p->geo;
   const int B = g.b, NB1 = B + 1;
   std::vector<SpFrame<T>> fr((size_t)g.K);
@@ -275,8 +275,17 @@ bool upload_frames(const srmap_problem* p, SpForwardPlan* sp) {
         }
     }
   }
-  if (sp->d_frames.alloc(sizeof(SpFrame<T>) * fr.size()) != hipSuccess) return false;
-  return hipMemcpy(sp->d_frames.as(), fr.data(), sizeof(SpFrame<T>) * fr.size(), hipMemcpyHostToDevice) == hipSuccess;
+  return upload_vector(p, fr, &sp->d_frames) == SRMAP_OK;
+}
+
+// The (FOLD, WEIGHTED) legs of an instance: f(kernel) for the leg (fold, weighted), or for every leg (the weighted ones only
+// with `weighted`).  Preloading and launching both go through here.
+template <typename T, int S, int B, class F>
+void with_legs(bool every, bool fold, bool weighted, F&& f) {
+  if (every || (!fold && !weighted)) f(&k_forward_sp<T, S, B, false, false>);
+  if (every || (fold && !weighted)) f(&k_forward_sp<T, S, B, true, false>);
+  if (weighted && (every || !fold)) f(&k_forward_sp<T, S, B, false, true>);
+  if (weighted && (every || fold)) f(&k_forward_sp<T, S, B, true, true>);
 }
 
 template <typename T, int S, int B>
@@ -297,13 +306,8 @@ int launch_typed(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp,
   A.cost_scale = (double)geo.s * (double)geo.s;
   dim3 grid((unsigned)((geo.w + kCW - 1) / kCW), (unsigned)((geo.h + kLRH - 1) / kLRH), (unsigned)geo.C);
   const size_t lds = (size_t)sp.XR * S * sp.XC * sizeof(T);
-  if (dw != nullptr) {
-    if (fold.xk != nullptr) hipLaunchKernelGGL((k_forward_sp<T, S, B, true, true>), grid, dim3(64 * kNW), lds, st, A);
-    else hipLaunchKernelGGL((k_forward_sp<T, S, B, false, true>), grid, dim3(64 * kNW), lds, st, A);
-  } else {
-    if (fold.xk != nullptr) hipLaunchKernelGGL((k_forward_sp<T, S, B, true, false>), grid, dim3(64 * kNW), lds, st, A);
-    else hipLaunchKernelGGL((k_forward_sp<T, S, B, false, false>), grid, dim3(64 * kNW), lds, st, A);
-  }
+  with_legs<T, S, B>(false, fold.xk != nullptr, dw != nullptr,
+                     [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(64 * kNW), lds, st, A); });
   SRMAP_HIP(p->ctx, hipGetLastError());
   *nblocks = (int)(grid.x * grid.y * grid.z);
   return SRMAP_OK;
@@ -312,12 +316,8 @@ int launch_typed(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp,
 template <typename T, int S, int B>
 void preload_typed(bool weighted) {
   hipFuncAttributes attr;
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, false, false>));
-  (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, true, false>));
-  if (weighted) {
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, false, true>));
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_forward_sp<T, S, B, true, true>));
-  }
+  with_legs<T, S, B>(true, false, weighted,
+                     [&](auto* kernel) { (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)); });
 }
 
 }  // namespace
@@ -352,10 +352,7 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   sp->can_fold = sp->NRF <= kMaxRowsPerWave * kNW && sp->NCF <= 2 * kCW;
   const bool wt = p->dw.robust();
   dispatch_dtype(p->dtype, [&](auto t) {
-    using T = decltype(t);
-    if (S == 2 && B == 1) preload_typed<T, 2, 1>(wt); else if (S == 2) preload_typed<T, 2, 3>(wt);
-    else if (S == 3 && B == 1) preload_typed<T, 3, 1>(wt); else if (S == 3) preload_typed<T, 3, 3>(wt);
-    else if (B == 1) preload_typed<T, 4, 1>(wt); else preload_typed<T, 4, 3>(wt);
+    dispatch_scale_blur(S, B, [&](auto s, auto b) { preload_typed<decltype(t), decltype(s)::value, decltype(b)::value>(wt); });
   });
   return true;
 }
@@ -364,12 +361,12 @@ template <typename T>
 int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan& sp, const T* x, const T* y,
                       int obs_C, int obs_c0, T* out, double* partials, int* nblocks, hipStream_t st, const SpFold& fold,
                       const T* dw) {
-  const int S = geo.s, B = geo.b;
-#define SPF(SS, BB) \
-  if (S == SS && B == BB) return launch_typed<T, SS, BB>(p, geo, sp, x, y, obs_C, obs_c0, out, partials, nblocks, st, fold, dw)
-  SPF(2, 1); SPF(2, 3); SPF(3, 1); SPF(3, 3); SPF(4, 1); SPF(4, 3);
-#undef SPF
-  return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no forward tile kernel for scale %d blur %d", S, B);
+  int rc = SRMAP_OK;
+  const bool have = dispatch_scale_blur(geo.s, geo.b, [&](auto s, auto b) {
+    rc = launch_typed<T, decltype(s)::value, decltype(b)::value>(p, geo, sp, x, y, obs_C, obs_c0, out, partials, nblocks, st, fold, dw);
+  });
+  if (!have) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no forward tile kernel for scale %d blur %d", geo.s, geo.b);
+  return rc;
 }
 
 template int launch_forward_sp<float>(srmap_problem*, const Geometry&, const SpForwardPlan&, const float*,

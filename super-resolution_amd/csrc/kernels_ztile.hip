@@ -56,6 +56,7 @@
 #include <type_traits>
 
 #include "ztile_dev.hpp"
+#include "ztile_plan.hpp"
 
 namespace srmap {
 
@@ -512,13 +513,13 @@ __global__ __launch_bounds__(256) void k_finish_eval(T* __restrict__ g, const T*
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) { red[wid] = v; red2[wid] = v2; }
     __syncthreads();
-    if (threadIdx.x == 0) cost_out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) cost_out[kCostValue] = (red[0] + red[1]) + (red[2] + red[3]);
     if (partials_gd != nullptr) {  // g.d of the same evaluation (solver line search)
       if (threadIdx.x == 0) {
         const double gd = (red2[0] + red2[1]) + (red2[2] + red2[3]);
-        cost_out[1] = gd;
+        cost_out[kCostGd] = gd;
         if (pub != nullptr) {  // solver line search: {cost, g.d} straight to the host-mapped words, then the arrival tag
-          pub[0] = cost_out[0];
+          pub[0] = cost_out[kCostValue];
           pub[1] = gd;
           __threadfence_system();
           *(volatile double*)tag_slot = tag;
@@ -531,296 +532,67 @@ __global__ __launch_bounds__(256) void k_finish_eval(T* __restrict__ g, const T*
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
-// host side: plan (per problem, owned by the problem) and launch
+// host side: launch -- only what has to name a kernel instance (the plan: ztile_plan.hip; the sequence of a tile
+// evaluation: eval.hip)
 
-// Up to this many cost partials (tiles + border blocks of all channels) one workgroup reduces them -- the tile kernel's
-// last one, or k_finish_eval's block 0 -- and the solver gets g.d out of the same launch; beyond it the caller reduces in
-// two stages.  64 K covers configs[2] (RGB 4096^2: 24 576 tiles), which at 16 K paid two more launches per evaluation and
-// a separate 400 MB dot-product pass per trial point of a solve.
-constexpr size_t kMaxFusedPartials = 65536;
-
-void ztile_release(srmap_problem* p) {
-  delete static_cast<ZPlan*>(p->zplan);  // and every table it owns
-  p->zplan = nullptr;
-}
-
-void ztile_rearm(srmap_problem* p) {
-  ZPlan* z = static_cast<ZPlan*>(p->zplan);
-  if (z && z->d_mpart) (void)hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * z->mpart_cap);
-}
-
-// Decide whether k_eval_z covers the problem; build the frame table.
-bool ztile_plan(srmap_problem* p) {
-  ztile_release(p);
-  const Geometry& g = p->geo;
-  const int S = g.s, B = g.b, K = g.K;
-  if (p->affine) return false;  // affine motion: the tiles' frame table holds translations only -- not covered
-  if (field_motion(p)) return false;  // displacement field (dense or on a lattice): likewise -- not covered
-  if (p->custom_blur) return false;  // free-form blur kernel: the tiles carry a symmetric 3 x 3 kernel's three values
-  if (!p->maps_regular) return false;
-  if (S < 2 || S > 4) return false;
-  if (B != 1 && B != 3) return false;
-  if (B == 3) {  // the tile kernel carries the three distinct values of the symmetric Gaussian kernel
-    const std::vector<double>& k2 = p->blur2d;
-    if (!(k2[0] == k2[2] && k2[0] == k2[6] && k2[0] == k2[8] && k2[1] == k2[3] && k2[1] == k2[5] && k2[1] == k2[7] &&
-          p->blur1d[0] == p->blur1d[2]))
-      return false;
-  }
-  std::vector<int> ox(K, 0), oy(K, 0);
-  int amax = 0;
-  // Data weights / a Huber loss: the plan takes the forward-residual form below whatever the shifts are.  The integer-shift
-  // tiles recompute residuals inside the tile (z_row / border_residual, ztile_dev.hpp) and carry no weighted leg; the
-  // forward-residual form gathers a residual BUFFER, which the weighted forward kernel fills with w .* r.  An integer
-  // shift is its one-tap case: the source table and the forward kernel's stencils walk ntaps taps.  Without a
-  // MotionModule there are no warp records for that form (ring kernel, forward tile kernel): the direct family runs.
-  const bool robust = p->dw.robust();
-  if (robust && !p->has_motion) return false;
-  bool subpix = robust;
-  if (p->has_motion) {
-    for (int k = 0; k < K; ++k) {
-      const WarpTaps<double>& f = p->fwd_warps[k];
-      const WarpTaps<double>& b = p->bwd_warps[k];
-      if (f.ytab != nullptr || b.ytab != nullptr) return false;  // rounding-tie shifts: per-row tables, direct kernels
-      if (f.ntaps != 1 || b.ntaps != 1) subpix = true;
-      else if (b.ox != -f.ox || b.oy != -f.oy) return false;
-      ox[k] = f.ox; oy[k] = f.oy;
-      amax = std::max(amax, std::max(std::abs(f.ox), std::abs(f.oy)));
-      amax = std::max(amax, std::max(std::abs(b.ox), std::abs(b.oy)));
-    }
-  }
-  if (amax > 4096) return false;
-  if ((long long)g.W * g.H >= (long long)INT_MAX) return false;  // the border blocks index a plane with 32 bits
-  ZPlan* z = new ZPlan();
-  z->S = S; z->B = B;
-  z->E = amax;
-  if (subpix) {
-    // ---- sub-pixel plan: z(p) = sum over (frame, bilinear tap of the TRANSPOSE warp) pairs that land on the LR grid ----
-    z->subpix = true;
-    z->E = 0;  // no border blocks: the forward kernel counts the cost, the ring pass evaluates the border exactly
-    z->Dr = amax + 2 + g.hb;
-    if (g.W <= 4 * z->Dr + 2 * S || g.H <= 4 * z->Dr + 2 * S) { delete z; return false; }
-    for (int r = 0; r < p->nreg && z->regk == 0; ++r) {
-      const RegSpec& rs = p->reg[r];
-      if (rs.lambda <= 0) continue;
-      if (rs.kind == SRMAP_REG_TV) { z->regk = 1; z->reg_index = r; }
-      else if (rs.kind == SRMAP_REG_BTV && rs.range >= 1 && rs.range <= 3) { z->regk = 2; z->regr = rs.range; z->reg_index = r; }
-      break;
-    }
-    // the taps source-major (z_row_sp2): per row phase one record per (frame, vertical tap) on the LR grid
-    std::vector<std::vector<ZSrc>> srcs((size_t)S);
-    for (int pr = 0; pr < S; ++pr)
-      for (int k = 0; k < K; ++k) {
-        const WarpTaps<double>& b = p->bwd_warps[k];
-        for (int dy = 0; dy < 2; ++dy) {
-          double w0 = 0.0, w1 = 0.0;
-          for (int t = 0; t < b.ntaps; ++t)
-            if ((t >> 1) == dy) { if (t & 1) w1 = b.w[t]; else w0 = b.w[t]; }
-          if (w0 == 0.0 && w1 == 0.0) continue;
-          const int rr = pr + b.oy + dy;
-          if (pmod(rr, S) != 0) continue;
-          ZSrc q; q.k = k; q.io = fdiv(rr, S); q.w0 = w0; q.w1 = w1;
-          const int a = pmod(-b.ox, S);
-          q.q = (b.ox + a) / S;  // exact
-          // the first residual column e in {-1, 0, 1} that a cell's S + 2 HB pixels use (sp_apply derives the same from a)
-          const bool lo = (a - S >= -g.hb) || (a - 1 - S >= -g.hb);
-          q.am = a | ((lo ? 0 : 1) << 8);  // (e_lo + 1) << 8
-          srcs[(size_t)pr].push_back(q);
-        }
-      }
-    int spmax = kSpChunk;
-    for (const auto& l : srcs) spmax = std::max(spmax, (int)((l.size() + kSpChunk - 1) / kSpChunk) * kSpChunk);
-    z->spmax = spmax;
-    std::vector<ZSrc> srctab((size_t)S * spmax, ZSrc{0, 0, 0, kSpNull, 0.0, 0.0});   // null records behind the sources
-    for (int pr = 0; pr < S; ++pr) {
-      z->spn[pr] = (int)((srcs[(size_t)pr].size() + kSpChunk - 1) / kSpChunk) * kSpChunk;
-      for (size_t n = 0; n < srcs[(size_t)pr].size(); ++n) srctab[(size_t)pr * spmax + n] = srcs[(size_t)pr][n];
-    }
-    // the only table an SP instance reads (z_row_sp2: spsrc, spn, spmax); the integer-shift frame table (cnt, off, aux) and
-    // the border blocks' tables stay unset -- no border blocks with E = 0
-    bool ok = z->d_spsrc.alloc(sizeof(ZSrc) * srctab.size()) == hipSuccess &&
-              hipMemcpy(z->d_spsrc.as<ZSrc>(), srctab.data(), sizeof(ZSrc) * srctab.size(), hipMemcpyHostToDevice) == hipSuccess;
-    p->zplan = z;
-    if (ok && gather_ring_kernel_ok(p, g, K, z->Dr)) {
-      // the ring pass runs ahead of the tile kernel into this buffer (g.d and the cost then finish inside the tile launch)
-      const size_t nring = 2 * (size_t)z->Dr * g.W + 2 * (size_t)z->Dr * (g.H - 2 * z->Dr);
-      ok = z->d_ringbuf.alloc(nring * g.C * p->elem()) == hipSuccess;
-    }
-    if (ok) {  // granules of the in-kernel cost reduction (as below)
-      const size_t cap = std::min<size_t>(ztile_partials_needed(p), kMaxFusedPartials);
-      ok = z->d_mpart.alloc(2 * cap * sizeof(double)) == hipSuccess &&
-           hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * cap) == hipSuccess;
-      z->mpart_cap = cap;
-    }
-    if (!ok) { ztile_release(p); return false; }
-    (void)spfwd_plan(p, &z->spf);
-    return true;
-  }
-  // the border frame (k_border, width 2E) must stay a small part of the image
-  if (g.W <= 4 * z->E + 2 * S || g.H <= 4 * z->E + 2 * S) { delete z; return false; }
-  // the one regulariser handled in-kernel (first TV / BTV with lambda > 0)
-  for (int r = 0; r < p->nreg && z->regk == 0; ++r) {
-    const RegSpec& rs = p->reg[r];
-    if (rs.lambda <= 0) continue;
-    if (rs.kind == SRMAP_REG_TV) { z->regk = 1; z->reg_index = r; }
-    else if (rs.kind == SRMAP_REG_BTV && rs.range >= 1 && rs.range <= 3) { z->regk = 2; z->regr = rs.range; z->reg_index = r; }
-    break;  // only the first active regulariser may be fused (order of accumulation)
-  }
-  // frame table: pixel (row phase pr, column phase pc) owns the residual of frame k iff (pr - oy) and (pc - ox)
-  // are multiples of S; the LR pixel is (rc + io, cell + jo)
-  std::vector<int2> hdr((size_t)S * S);
-  std::vector<ZEntry> ent;
-  for (int pr = 0; pr < S; ++pr)
-    for (int pc = 0; pc < S; ++pc) {
-      int2 h; h.x = 0; h.y = (int)ent.size();
-      for (int k = 0; k < K; ++k) {
-        if (pmod(pr - oy[k], S) != 0 || pmod(pc - ox[k], S) != 0) continue;
-        ZEntry e; e.k = k; e.io = fdiv(pr - oy[k], S); e.jo = fdiv(pc - ox[k], S);
-        e.oyx = (int)(((unsigned)oy[k] << 16) | ((unsigned)ox[k] & 0xffffu));
-        ent.push_back(e);
-        h.x++;
-      }
-      hdr[(size_t)pr * S + pc] = h;
-    }
-  if (ent.empty()) { ZEntry e = {0, 0, 0, 0}; ent.push_back(e); }
-  if ((int)ent.size() > kBorderTabEntries) { delete z; return false; }  // k_border stages the table in LDS
-  z->n_ent = (int)ent.size();
-  // the tile kernel's layout of the same table: [pr][t][pc], with the observation's element offset precomputed
-  int MS = 1;
-  for (const int2& h : hdr) MS = std::max(MS, h.x);
-  z->MS = MS;
-  std::vector<int> cnt((size_t)S * 8, 0);
-  std::vector<long long> off((size_t)S * MS * S, 0);
-  std::vector<ZEntry> aux((size_t)S * MS * S, ZEntry{0, 0, 0, 0});
-  const long long nl = (long long)g.w * g.h;
-  for (int pr = 0; pr < S; ++pr) {
-    int mx = 0;
-    for (int pc = 0; pc < S; ++pc) {
-      const int2 h = hdr[(size_t)pr * S + pc];
-      cnt[(size_t)pr * 8 + pc] = h.x;
-      mx = std::max(mx, h.x);
-      for (int t = 0; t < h.x; ++t) {
-        const ZEntry& e = ent[(size_t)h.y + t];
-        const size_t slot = ((size_t)t * S + pr) * S + pc;
-        aux[slot] = e;
-        off[slot] = (long long)e.k * g.C * nl + (long long)e.io * g.w + e.jo;
-      }
-    }
-    cnt[(size_t)pr * 8 + S] = mx;
-    int mn = INT_MAX;
-    for (int pc = 0; pc < S; ++pc) mn = std::min(mn, cnt[(size_t)pr * 8 + pc]);
-    cnt[(size_t)pr * 8 + S + 1] = mn;
-    for (int pc = 0; pc < S; ++pc) {
-      z->h_off0[pr * 4 + pc] = off[((size_t)0 * S + pr) * S + pc];
-      z->h_aux0[pr * 4 + pc] = aux[((size_t)0 * S + pr) * S + pc];
-    }
-  }
-  for (size_t i = 0; i < cnt.size(); ++i) z->h_cnt[i] = cnt[i];
-  bool ok = z->d_hdr.alloc(sizeof(int2) * hdr.size()) == hipSuccess &&
-            hipMemcpy(z->d_hdr.as<int2>(), hdr.data(), sizeof(int2) * hdr.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            z->d_ent.alloc(sizeof(ZEntry) * ent.size()) == hipSuccess &&
-            hipMemcpy(z->d_ent.as<ZEntry>(), ent.data(), sizeof(ZEntry) * ent.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            z->d_cnt.alloc(sizeof(int) * cnt.size()) == hipSuccess &&
-            hipMemcpy(z->d_cnt.as<int>(), cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            z->d_off.alloc(sizeof(long long) * off.size()) == hipSuccess &&
-            hipMemcpy(z->d_off.as<long long>(), off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            z->d_aux.alloc(sizeof(ZEntry) * aux.size()) == hipSuccess &&
-            hipMemcpy(z->d_aux.as<ZEntry>(), aux.data(), sizeof(ZEntry) * aux.size(), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && z->E > 0) {
-    // the rectangles of the border frame that can carry work (ztile_dev.hpp RingRects)
-    int mnx = 0, mxx = 0, mny = 0, mxy = 0;
-    for (int k = 0; k < K; ++k) {
-      mnx = std::min(mnx, ox[k]); mxx = std::max(mxx, ox[k]);
-      mny = std::min(mny, oy[k]); mxy = std::max(mxy, oy[k]);
-    }
-    RingRects rr;
-    rr.rg[0] = (B > 1) ? std::max(0, mxy) : 0;   // corrections need a blur tap between the pixel and the residual
-    rr.rg[1] = (B > 1) ? std::max(0, mxx) : 0;
-    rr.rg[2] = std::max(0, -mny);
-    rr.rg[3] = std::max(0, mxy - S + 1);
-    rr.rg[4] = std::max(0, -mnx);
-    rr.rg[5] = std::max(0, mxx - S + 1);
-    z->ring = rr;
-    z->n_ring = (int)ring_count(rr, g.W, g.H);
-    if (z->n_ring > 0) ok = z->d_corr.alloc((size_t)g.C * z->n_ring * p->elem()) == hipSuccess;
-  }
-  if (ok) {
-    auto put = [&](auto bd) {
-      bd.hdr = z->d_hdr.as<int2>(); bd.ent = z->d_ent.as<ZEntry>(); bd.blur_d = (decltype(bd.blur_d))p->d_blur.as(); bd.corr = (decltype(bd.corr))z->d_corr.as();
-      bd.S = S; bd.b = B; bd.hb = g.hb; bd.n_ring = z->n_ring; bd.n_ent = z->n_ent; bd.obs_C = g.C;
-      return z->d_bd.alloc(sizeof(bd)) == hipSuccess &&
-             hipMemcpy(z->d_bd.as(), &bd, sizeof(bd), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    ok = dispatch_dtype(p->dtype, [&](auto t) { return put(BorderArgs<decltype(t)>()); });
-  }
-  p->zplan = z;
-  if (ok) {
-    // granules of the in-kernel cost reduction (one per tile + one per border block), up to a cap beyond which the
-    // caller's two-stage reduction is used anyway
-    const size_t cap = std::min<size_t>(ztile_partials_needed(p), kMaxFusedPartials);
-    ok = z->d_mpart.alloc(2 * cap * sizeof(double)) == hipSuccess &&
-         hipMemsetD32((hipDeviceptr_t)z->d_mpart.as<double>(), (int)kSentinel32, 4 * cap) == hipSuccess;
-    z->mpart_cap = cap;
-  }
-  if (!ok) { ztile_release(p); return false; }
-  return true;  // the caller preloads the kernel instance (ztile_preload)
-}
-
-// Frame sharding may split the regulariser by row band when the tile kernel alone produces it: one active
-// regulariser, the one fused into the plan (no 3-D TV / second regulariser / wide BTV pass of the direct kernels).
-bool ztile_overlaps_halo(const srmap_problem* p) {
-  const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
-  return z != nullptr && p->impl != SRMAP_IMPL_DIRECT && !z->subpix;
-}
-
-bool ztile_reg_band_ok(const srmap_problem* p, unsigned terms) {
-  const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
-  if (!z || p->impl == SRMAP_IMPL_DIRECT) return false;
-  if (!(terms & SRMAP_TERM_REG)) return false;
-  int active = 0;
-  for (int r = 0; r < p->nreg; ++r)
-    if (p->reg[r].lambda > 0.0) { if (!(z->regk != 0 && r == z->reg_index)) return false; active++; }
-  return active == 1;
-}
-
-// Upper bound of the cost partials one tile launch over C channels produces (tiles + border blocks, which fill whole
-// grid rows) -- ONE definition for the granule allocation, the launch and the solver's decisions.
-static size_t ztile_est_partials(const ZPlan* z, int w, int H, int C) {
-  const size_t tiles = (size_t)((w + 63) / 64) * ((H + 7) / 8) * C;
-  const size_t ring = (z && z->n_ring > 0) ? (size_t)((z->n_ring + 511) / 512 + (H + 7) / 8) * C : (size_t)0;
-  return tiles + ring;
-}
-
-// Whether the tile launch of an evaluation with `terms` over C channels is the g.d instance (k_eval_z<..., WD>): it must
-// produce the WHOLE gradient (no further regulariser kernel behind it) and few enough partials for its in-kernel
-// reduction.  launch_eval_ztile asks it for the launch, ztile_can_fold for the solver (a folded trial point exists only
-// inside that instance): the two cannot drift apart.
-static bool ztile_gd_instance_ok(const srmap_problem* p, const ZPlan& z, int w, int H, int C, unsigned terms) {
-  // sub-pixel plans: the ring pass must be able to run AHEAD of the tile launch (into z.d_ringbuf) -- a pass that adds to g
-  // behind it would leave the launch's g.d without the ring's share
-  if (z.subpix && !z.d_ringbuf) return false;
-  if (terms & SRMAP_TERM_REG)
-    for (int r = 0; r < p->nreg; ++r)
-      if (!(z.regk != 0 && r == z.reg_index) && p->reg[r].lambda > 0.0) return false;
-  return ztile_est_partials(&z, w, H, C) <= kMaxFusedPartials;
-}
-
-bool ztile_can_fold(const srmap_problem* p, int C) {
-  const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
-  if (!z || p->impl == SRMAP_IMPL_DIRECT) return false;
-  // sub-pixel plans: the trial point is formed by the forward tile kernel, whose window has to hold a workgroup's own pixels
-  if (z->subpix && !(z->spf.ok && z->spf.can_fold)) return false;
-  return ztile_gd_instance_ok(p, *z, p->geo.w, p->geo.H, C, SRMAP_TERM_ALL);
-}
-
-size_t ztile_partials_needed(const srmap_problem* p) {
-  const Geometry& g = p->geo;
-  return ztile_est_partials(static_cast<const ZPlan*>(p->zplan), g.w, g.H, g.C);
-}
-
+// Kernel arguments of the tile kernel (everything but the grid-dependent fields).
 template <typename T, int S, int B, int REGK, int R>
+static void fill_zargs(ZArgs<T, B, ZCfg<T, S, B, REGK, R>::NP>& A, srmap_problem* p, const Geometry& geo, int obs_c0,
+                       unsigned terms, const T* x, T* g, const T* wts, const ZPlan& z, double* partials, const T* dvec,
+                       double* partials_gd) {
+  using C = ZCfg<T, S, B, REGK, R>;
+  A.x = x; A.y = p->d_obs.as<const T>() + (size_t)obs_c0 * geo.w * geo.h; A.w = wts; A.g = g; A.partials = partials;
+  A.dvec = dvec; A.partials_gd = partials_gd;
+  A.cnt = z.d_cnt.as<int>(); A.off = z.d_off.as<long long>(); A.aux = z.d_aux.as<ZEntry>(); A.MS = z.ft.MS;
+  A.spsrc = z.d_spsrc.as<ZSrc>(); A.spmax = z.st.spmax;
+  for (int pr = 0; pr < 4; ++pr) A.spn[pr] = z.st.spn[pr];
+  for (int pr = 0; pr < 4; ++pr) {
+    for (int i = 0; i < 8; ++i) A.cntk[pr][i] = z.ft.cnt0[pr * 8 + i];
+    for (int pc = 0; pc < 4; ++pc) { A.off0[pr][pc] = z.ft.off0[pr * 4 + pc]; A.aux0[pr][pc] = z.ft.aux0[pr * 4 + pc]; }
+  }
+  A.W = geo.W; A.H = geo.H; A.wl = geo.w; A.hl = geo.h;
+  A.obs_C = p->geo.C;
+  A.E = z.E;
+  A.ring = z.ring;
+  A.cr0 = geo.cr0; A.cr1 = geo.cr1;
+  A.rr0 = geo.rr0; A.rr1 = geo.rr1;
+  A.terms = (int)terms;
+  if (B == 1) { A.blur3[0] = A.blur3[1] = A.blur3[2] = T(1); A.k1s[0] = A.k1s[1] = T(1); }
+  else {
+    const int hb = (B - 1) / 2;
+    A.blur3[0] = (T)p->blur2d[0]; A.blur3[1] = (T)p->blur2d[hb]; A.blur3[2] = (T)p->blur2d[hb * B + hb];
+    A.k1s[0] = (T)p->blur1d[0]; A.k1s[1] = (T)p->blur1d[hb];
+  }
+  A.lambda = T(0);
+  for (int i = 0; i < C::NP; ++i) A.powtab[i] = T(1);
+  if (REGK != 0) {
+    const RegSpec& rs = p->reg[z.reg_index];
+    A.lambda = (T)rs.lambda;
+    if (REGK == 2) for (int i = 0; i < C::NP; ++i) A.powtab[i] = (T)rs.pow_table[i];
+  }
+  A.pwsum = T(0);
+  if (REGK == 2)
+    for (int i = 0; i < R; ++i)
+      for (int j = 0; j < R; ++j)
+        if (i + j > 0) A.pwsum += A.powtab[i + j];
+  A.fold_xk = nullptr; A.fold_x = nullptr; A.fold_stp = T(0); A.fold_norms = nullptr;
+}
+
+// The four (WD, SP) legs of a tile kernel instance I: f(kernel) for the leg (wd, sp), or for every leg.  Preloading and
+// launching both go through here.
+template <typename T, class I, class F>
+static void with_legs(bool every, bool wd, bool sp, F&& f) {
+  if (every || (!wd && !sp)) f(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, false>);
+  if (every || (wd && !sp)) f(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, false>);
+  if (every || (!wd && sp)) f(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, true>);
+  if (every || (wd && sp)) f(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, true>);
+}
+
+template <typename T, class I>
 static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, int obs_c0, unsigned terms, const T* x, T* g,
                     const T* wts, const ZPlan& z, double* partials, int* nblocks, hipStream_t st, const T* dvec,
                     double* partials_gd, MFin mfin, bool ring_ahead) {
+  constexpr int S = I::S, B = I::B, REGK = I::REGK, R = I::R;
   using C = ZCfg<T, S, B, REGK, R>;
   ZArgs<T, B, C::NP> A;
   fill_zargs<T, S, B, REGK, R>(A, p, geo, obs_c0, terms, x, g, wts, z, partials, dvec, partials_gd);
@@ -828,8 +600,8 @@ static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, i
     A.fold_norms = req.fold.norms;
     if (!(z.subpix && (terms & SRMAP_TERM_DATA))) {
       A.fold_xk = (const T*)req.fold.xk; A.fold_x = const_cast<T*>(x); A.fold_stp = (T)req.fold.stp;
-    }  // sub-pixel plans: the forward kernel ahead of this launch formed the point and wrote x (launch_eval_ztile); dvec is
-       // still the unnormalised direction here (fold_norms)
+    }  // sub-pixel plans: the forward kernel ahead of this launch formed the point and wrote x (the tile evaluation,
+       // eval.hip); dvec is still the unnormalised direction here (fold_norms)
   }
   dim3 grid((geo.w + C::CW - 1) / C::CW, (geo.H + C::TH - 1) / C::TH, geo.C);
   { const unsigned t = grid.x; grid.x = grid.y; grid.y = t; }
@@ -858,32 +630,30 @@ static int launch_z(srmap_problem* p, const EvalReq& req, const Geometry& geo, i
   A.xpart = mfin.xpart; A.n_xpart = mfin.n_xpart;
   if (mfin.on && (size_t)A.n_partials > z.mpart_cap) return set_error(p->ctx, SRMAP_EHIP, "granule capacity");
   A.sel_mode = 0; A.sel0 = 0; A.sel1 = 0;
-  if (z.subpix && (terms & SRMAP_TERM_DATA)) {
+  const bool sp = z.subpix && (terms & SRMAP_TERM_DATA);
+  auto launch = [&]() {
+    with_legs<T, I>(false, dvec != nullptr, sp,
+                    [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(C::NT), 0, st, A); });
+  };
+  if (sp) {
     A.rbuf = p->d_resid.as<const T>();
-    A.obs_C = geo.C;  // layout of the residual buffer written by launch_forward_direct for this evaluation
+    A.obs_C = geo.C;  // layout of the residual buffer written by the forward kernel for this evaluation
     A.ringbuf = ring_ahead ? z.d_ringbuf.as<const T>() : nullptr;
-    if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, true>), grid, dim3(C::NT), 0, st, A);
-    else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, true>), grid, dim3(C::NT), 0, st, A);
+    launch();
+  } else if (req.overlap.fn != nullptr) {
+    // Row shard: a tile row [8 t, 8 t + 8) reads x rows within the halo width of itself, so the tile rows t with
+    // 8 t >= 2 * top and 8 t + 8 <= H - 2 * bot touch no halo row.  They run first, the halo exchange is
+    // posted on its own stream under them, and the boundary tile rows (and the border blocks) follow the event.
+    const int th = C::TH;
+    A.sel0 = (2 * req.overlap.top + th - 1) / th;
+    A.sel1 = (geo.H - 2 * req.overlap.bot) / th;
+    if (A.sel1 > A.sel0) { A.sel_mode = 1; launch(); }
+    const int rch = req.overlap.fn(req.overlap.arg);
+    if (rch) return rch;
+    SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, req.overlap.event, 0));
+    if (A.sel1 > A.sel0) { A.sel_mode = 2; launch(); } else { A.sel_mode = 0; launch(); }
   } else {
-    auto launch = [&]() {
-      if (dvec != nullptr) hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, true, false>), grid, dim3(C::NT), 0, st, A);
-      else hipLaunchKernelGGL((k_eval_z<T, S, B, REGK, R, false, false>), grid, dim3(C::NT), 0, st, A);
-    };
-    if (req.overlap.fn != nullptr) {
-      // Row shard: a tile row [8 t, 8 t + 8) reads x rows within the halo width of itself, so the tile rows t with
-      // 8 t >= 2 * top and 8 t + 8 <= H - 2 * bot touch no halo row.  They run first, the halo exchange is
-      // posted on its own stream under them, and the boundary tile rows (and the border blocks) follow the event.
-      const int th = C::TH;
-      A.sel0 = (2 * req.overlap.top + th - 1) / th;
-      A.sel1 = (geo.H - 2 * req.overlap.bot) / th;
-      if (A.sel1 > A.sel0) { A.sel_mode = 1; launch(); }
-      const int rch = req.overlap.fn(req.overlap.arg);
-      if (rch) return rch;
-      SRMAP_HIP(p->ctx, hipStreamWaitEvent(st, req.overlap.event, 0));
-      if (A.sel1 > A.sel0) { A.sel_mode = 2; launch(); } else { A.sel_mode = 0; launch(); }
-    } else {
-      launch();
-    }
+    launch();
   }
   *nblocks = n_tile_partials + nbb * (int)grid.z;
   SRMAP_HIP(p->ctx, hipGetLastError());
@@ -923,13 +693,9 @@ static bool with_instance(int S, int B, int regk, int regr, F&& f) {
   }
   return false;
 #else
-  if (S == 2 && B == 1) return with_reg_instance<2, 1>(regk, regr, f);
-  if (S == 2 && B == 3) return with_reg_instance<2, 3>(regk, regr, f);
-  if (S == 3 && B == 1) return with_reg_instance<3, 1>(regk, regr, f);
-  if (S == 3 && B == 3) return with_reg_instance<3, 3>(regk, regr, f);
-  if (S == 4 && B == 1) return with_reg_instance<4, 1>(regk, regr, f);
-  if (S == 4 && B == 3) return with_reg_instance<4, 3>(regk, regr, f);
-  return false;
+  bool hit = false;
+  auto regs = [&](auto s, auto b) { hit = with_reg_instance<decltype(s)::value, decltype(b)::value>(regk, regr, f); };
+  return dispatch_scale_blur(S, B, regs) && hit;
 #endif
 }
 
@@ -938,173 +704,48 @@ static bool with_instance(int S, int B, int regk, int regr, F&& f) {
 // that leave the regulariser out).
 template <typename T>
 static void preload_instances(int S, int B, int regk, int regr) {
-  auto touch = [](auto inst) {
-    using I = decltype(inst);
-    hipFuncAttributes attr;
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, false>));
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, false>));
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, false, true>));
-    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_eval_z<T, I::S, I::B, I::REGK, I::R, true, true>));
-  };
+  hipFuncAttributes attr;
+  auto get = [&](auto* kernel) { (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)); };
+  auto touch = [&](auto inst) { with_legs<T, decltype(inst)>(true, false, false, get); };
   (void)with_instance<T>(S, B, 0, 0, touch);
   (void)with_instance<T>(S, B, regk, regr, touch);
-  hipFuncAttributes attr;
   (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_finish_eval<T>));
 }
 void ztile_preload(const srmap_problem* p) {
-  const ZPlan* z = static_cast<const ZPlan*>(p->zplan);
+  const ZPlan* z = p->zplan.get();
   if (!z) return;
-  dispatch_dtype(p->dtype, [&](auto t) { preload_instances<decltype(t)>(z->S, z->B, z->regk, z->regr); });
+  dispatch_dtype(p->dtype, [&](auto t) { preload_instances<decltype(t)>(p->geo.s, p->geo.b, z->regk, z->regr); });
 }
 
 template <typename T>
-int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const Geometry& geo, int obs_c0,
-                      unsigned terms, const T* x, T* g, double* partials, int* nblocks, hipStream_t st) {
-  const ZPlan* zp = static_cast<const ZPlan*>(p->zplan);
-  if (!zp) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile plan");
-  const ZPlan& z = *zp;
-  const size_t N = (size_t)geo.W * geo.H;
-  const bool want_reg = (terms & SRMAP_TERM_REG) != 0;
-  int regk = 0, regr = 0;
-  const T* wts = nullptr;
-  if (want_reg && z.regk != 0) {
-    regk = z.regk; regr = z.regr;
-    const RegSpec& rs = p->reg[z.reg_index];
-    wts = rs.weights ? rs.weights.as<const T>() + (size_t)obs_c0 * N : nullptr;
-  }
-  unsigned zterms = terms & SRMAP_TERM_DATA;
-  if (regk) zterms |= SRMAP_TERM_REG;
-  int rc = SRMAP_OK, nb = 0;
-  const int S = geo.s, B = geo.b;
-  // g.d with the gradient (solver line search): only when this launch produces the WHOLE gradient and the single
-  // finish launch reduces it -- no further regulariser kernels, few enough partials
-  bool more_regs = false;
-  if (want_reg)
-    for (int r = 0; r < p->nreg; ++r)
-      if (!(regk && r == z.reg_index) && p->reg[r].lambda > 0.0) more_regs = true;
-  const size_t est_parts = ztile_est_partials(&z, geo.w, geo.H, geo.C);
-  const bool sp_data = z.subpix && (terms & SRMAP_TERM_DATA);
-  const bool with_d = req.dvec != nullptr && g != nullptr && ztile_gd_instance_ok(p, z, geo.w, geo.H, geo.C, terms);
-  int nfwd = 0;
-  // the exact ring pass AHEAD of the tile kernel (k_gather_ring into the plan's buffer; the edge tiles add the values as
-  // they store g, so g.d and the cost finish inside the tile launch) wherever the ring kernel applies; else behind it,
-  // adding to g (then no g.d from the launch: ztile_gd_instance_ok).  Ring blocks at the front of the tile launch's own
-  // grid (one launch less) were built and measured: every ring workgroup holds a tile slot (73 KB of LDS) for its 6 - 9 us of
-  // latency, 450 of the 512 slots of the first generation -- 82.9 us against 82.5 us, and slower inside a solve.
-  const bool ring_ahead = sp_data && g != nullptr && z.d_ringbuf;
-  if (sp_data) {
-    // sub-pixel shifts: exact residuals (and the data cost) from the direct forward kernel, then the tile kernel
-    // gathers them with the 4-tap tables; the pixels within Dr of the edge are evaluated exactly by the ring pass
-    if (!p->d_resid) SRMAP_HIP(p->ctx, p->d_resid.alloc(p->lr_count() * sizeof(T)));
-    if (req.fold.xk != nullptr && !(with_d && z.spf.ok && z.spf.can_fold))
-      return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the forward tile kernel and the g.d instance (ztile_can_fold)");
-    const T* dw = p->dw.effective<T>();  // data weights: the WEIGHTED forward instances leave w .* r for the gathers
-    if (z.spf.ok)
-      rc = launch_forward_sp<T>(p, geo, z.spf, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), partials, &nfwd, st, req.fold, dw);
-    else
-      rc = launch_forward_direct<T>(p, geo, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), 0, geo.K, partials, &nfwd, st, dw);
-    if (rc) return rc;
-    partials += nfwd;
-    if (ring_ahead) {
-      rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr, z.d_ringbuf.as<T>());
-      if (rc) return rc;
-    }
-  }
-  if (req.fold.xk != nullptr && !(with_d && req.overlap.fn == nullptr))
-    return set_error(p->ctx, SRMAP_EINVAL, "internal: a folded trial point needs the tile kernel's g.d instance (ztile_can_fold)");
-  const T* dv = with_d ? (const T*)req.dvec : nullptr;
-  double* pgd = with_d ? p->d_partials.as<double>() + p->partials_cap / 2 : nullptr;
-  // tiles: the cost reduction inside the kernel (no finish launch) when no in-image pixel of the border frame needs a
-  // correction, no further regulariser kernel follows and the granules suffice
-  // Sub-pixel plan: the forward kernel's data-cost partials (plain doubles, complete before the tile kernel starts) are
-  // added by the same in-kernel finish; the ring pass touches g only.
-  MFin mfin;
-  mfin.on = !more_regs && req.overlap.fn == nullptr && z.d_mpart && est_parts <= z.mpart_cap &&
-            (z.n_ring == 0 || (z.ring.rg[0] == 0 && z.ring.rg[1] == 0)) && (size_t)nfwd <= kMaxFusedPartials;
-  mfin.publish = mfin.on && with_d && req.pub.out != nullptr;
-  mfin.xpart = (mfin.on && sp_data) ? partials - nfwd : nullptr;
-  mfin.n_xpart = (mfin.on && sp_data) ? nfwd : 0;
-  const bool have = with_instance<T>(S, B, regk, regr, [&](auto inst) {
-    using I = decltype(inst);
-    rc = launch_z<T, I::S, I::B, I::REGK, I::R>(p, req, geo, obs_c0, zterms, x, g, wts, z, partials, &nb, st, dv, pgd, mfin, ring_ahead);
+int launch_ztiles(srmap_problem* p, const EvalReq& req, const Geometry& geo, int obs_c0, unsigned zterms, int regk, int regr,
+                  const T* x, T* g, const T* wts, const ZPlan& z, double* partials, int* nblocks, hipStream_t st,
+                  const T* dvec, double* partials_gd, MFin mfin, bool ring_ahead) {
+  int rc = SRMAP_OK;
+  const bool have = with_instance<T>(geo.s, geo.b, regk, regr, [&](auto inst) {
+    rc = launch_z<T, decltype(inst)>(p, req, geo, obs_c0, zterms, x, g, wts, z, partials, nblocks, st, dvec, partials_gd, mfin, ring_ahead);
   });
-  if (!have) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile kernel for scale %d blur %d regulariser %d/%d", S, B, regk, regr);
-  if (rc) return rc;
-  if (sp_data) {
-    partials -= nfwd;
-    nb += nfwd;
-    if (g != nullptr && !ring_ahead) {
-      rc = launch_gather_direct<T>(p, geo, p->d_resid.as<const T>(), g, 0, geo.K, 2.0 * geo.s * geo.s, true, st, z.Dr);
-      if (rc) return rc;
-    }
-  }
-  int total = nb;
-  // remaining regularisers (3-D TV, a second regulariser, BTV range > 3): direct kernels, accumulating into g
-  if (want_reg) {
-    for (int r = 0; r < p->nreg; ++r) {
-      if (regk && r == z.reg_index) continue;
-      const RegSpec& rs = p->reg[r];
-      if (rs.lambda <= 0.0) continue;
-      const bool onfly = rs.kind != SRMAP_REG_BTV;
-      if (!onfly) {
-        if (!p->d_regvals) SRMAP_HIP(p->ctx, p->d_regvals.alloc(p->hr_count() * sizeof(T)));
-        rc = launch_reg_values<T>(p, geo, rs, x, p->d_regvals.as<T>(), st);
-        if (rc) return rc;
-      }
-      const T* w2 = rs.weights ? rs.weights.as<const T>() + (size_t)obs_c0 * N : nullptr;
-      int nb2 = 0;
-      rc = launch_reg_gradient_direct<T>(p, geo, rs, x, w2, rs.lambda, onfly ? nullptr : p->d_regvals.as<const T>(), g, true,
-                                         partials + total, &nb2, st);
-      if (rc) return rc;
-      total += nb2;
-    }
-  }
-  if (mfin.on) {  // reduced by the last workgroup of the tile kernel
-    out->gd_valid = with_d;  // d_cost[1] = g.d
-    out->published = mfin.publish;
-    *nblocks = 0;
-    return SRMAP_OK;
-  }
-  // finish: border corrections of g + the fixed-order cost reduction, one launch
-  const bool corr_on = (terms & SRMAP_TERM_DATA) && z.n_ring > 0 && g != nullptr;
-  if ((size_t)total <= kMaxFusedPartials) {
-    const int nring = corr_on ? z.n_ring : 0;
-    const unsigned nb_f = 1u + (unsigned)((nring + 255) / 256);
-    hipLaunchKernelGGL(k_finish_eval<T>, dim3(nb_f), dim3(256), 0, st, corr_on ? g : (T*)nullptr, z.d_corr.as<const T>(),
-                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, total, p->d_cost.as<double>(), (const double*)pgd,
-                       with_d ? req.pub.out : (double*)nullptr, req.pub.tag_slot, req.pub.tag);
-    SRMAP_HIP(p->ctx, hipGetLastError());
-    out->gd_valid = with_d;  // d_cost[1] = g.d
-    out->published = with_d && req.pub.out != nullptr;
-    *nblocks = 0;  // total already in d_cost[0]
-    return SRMAP_OK;
-  }
-  // many partials (multi-channel problems): corrections here, two-stage reduction by the caller
-  if (corr_on) {
-    hipLaunchKernelGGL(k_finish_eval<T>, dim3(1u + (unsigned)((z.n_ring + 255) / 256)), dim3(256), 0, st, g, z.d_corr.as<const T>(),
-                       z.n_ring, geo.W, geo.H, z.ring, geo.C, (const double*)partials, 0, p->d_cost.as<double>() + 1, (const double*)nullptr,
-                       (double*)nullptr, (double*)nullptr, 0.0);
-    SRMAP_HIP(p->ctx, hipGetLastError());
-  }
-  *nblocks = total;
+  if (!have) return set_error(p->ctx, SRMAP_EUNSUPPORTED, "no tile kernel for scale %d blur %d regulariser %d/%d", geo.s, geo.b, regk, regr);
+  return rc;
+}
+
+template <typename T>
+int launch_zfinish(srmap_problem* p, const ZPlan& z, const Geometry& geo, T* corr_g, const double* partials, int n,
+                   double* cost_out, const double* partials_gd, double* pub_out, double* tag_slot, double tag, hipStream_t st) {
+  const unsigned blocks = 1u + (unsigned)(((corr_g != nullptr ? z.n_ring : 0) + 255) / 256);
+  hipLaunchKernelGGL(k_finish_eval<T>, dim3(blocks), dim3(256), 0, st, corr_g, z.d_corr.as<const T>(), z.n_ring, geo.W, geo.H,
+                     z.ring, geo.C, partials, n, cost_out, partials_gd, pub_out, tag_slot, tag);
+  SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
 
-template <typename T>
-int launch_forward_residual(srmap_problem* p, const Geometry& geo, int obs_c0, const T* x, double* partials, hipStream_t st) {
-  const ZPlan* z = p->impl != SRMAP_IMPL_DIRECT ? static_cast<const ZPlan*>(p->zplan) : nullptr;
-  if (!p->d_resid) SRMAP_HIP(p->ctx, p->d_resid.alloc(p->lr_count() * sizeof(T)));
-  int nfwd = 0;
-  if (z != nullptr && z->subpix && z->spf.ok)
-    return launch_forward_sp<T>(p, geo, z->spf, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), partials, &nfwd, st);
-  return launch_forward_direct<T>(p, geo, x, p->d_obs.as<const T>(), p->geo.C, obs_c0, p->d_resid.as<T>(), 0, geo.K, partials, &nfwd, st);
-}
-template int launch_forward_residual<float>(srmap_problem*, const Geometry&, int, const float*, double*, hipStream_t);
-template int launch_forward_residual<double>(srmap_problem*, const Geometry&, int, const double*, double*, hipStream_t);
-
-template int launch_eval_ztile<float>(srmap_problem*, const EvalReq&, EvalOut*, const Geometry&, int, unsigned,
-                                      const float*, float*, double*, int*, hipStream_t);
-template int launch_eval_ztile<double>(srmap_problem*, const EvalReq&, EvalOut*, const Geometry&, int, unsigned,
-                                       const double*, double*, double*, int*, hipStream_t);
+#define SRMAP_ZTILE_ENTRY_POINTS(T)                                                                                          \
+  template int launch_ztiles<T>(srmap_problem*, const EvalReq&, const Geometry&, int, unsigned, int, int, const T*, T*,      \
+                                const T*, const ZPlan&, double*, int*, hipStream_t, const T*, double*, MFin, bool);          \
+  template int launch_zfinish<T>(srmap_problem*, const ZPlan&, const Geometry&, T*, const double*, int, double*,             \
+                                 const double*, double*, double*, double, hipStream_t);
+SRMAP_ZTILE_ENTRY_POINTS(float)
+SRMAP_ZTILE_ENTRY_POINTS(double)
+#undef SRMAP_ZTILE_ENTRY_POINTS
 
 }  // namespace srmap

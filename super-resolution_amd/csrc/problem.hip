@@ -13,14 +13,6 @@ using namespace srmap;
 
 namespace srmap {
 
-// *dst <- a new block holding v (blocking copy)
-template <typename E>
-static int upload_vector(srmap_problem* p, const std::vector<E>& v, DevBuf* dst) {
-  SRMAP_HIP(p->ctx, dst->alloc(sizeof(E) * v.size()));
-  SRMAP_HIP(p->ctx, hipMemcpy(dst->as(), v.data(), sizeof(E) * v.size(), hipMemcpyHostToDevice));
-  return SRMAP_OK;
-}
-
 template <typename T>
 static int upload_warps(srmap_problem* p, const std::vector<WarpTaps<double>>& src, DevBuf* dst) {
   std::vector<WarpTaps<T>> tmp(src.size());
@@ -187,13 +179,13 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
   });
   if (rc) return fail(rc);
   if (p->d_col_map.alloc(sizeof(int) * g.w) != hipSuccess || p->d_row_map.alloc(sizeof(int) * g.h) != hipSuccess ||
-      p->d_cost.alloc(sizeof(double) * 8) != hipSuccess)
+      p->d_cost.alloc(sizeof(double) * kCostSlots) != hipSuccess)
     return fail(set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed"));
   (void)hipMemcpy(p->d_col_map.as<int>(), cmap.data(), sizeof(int) * g.w, hipMemcpyHostToDevice);
   (void)hipMemcpy(p->d_row_map.as<int>(), rmap.data(), sizeof(int) * g.h, hipMemcpyHostToDevice);
   // everything above used blocking copies; d_cost is first touched by kernels on caller streams: clear it on the
   // context's (non-blocking) stream and wait, so no legacy-stream work is left behind the creation
-  if (hipMemsetAsync(p->d_cost.as<double>(), 0, sizeof(double) * 8, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+  if (hipMemsetAsync(p->d_cost.as<double>(), 0, sizeof(double) * kCostSlots, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
     return fail(set_error(ctx, SRMAP_EHIP, "clearing the cost scalars failed"));
   model_replan(p);
   *out = p;
@@ -202,7 +194,6 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
 
 void srmap_problem_destroy(srmap_problem* p) {
   if (!p) return;
-  ztile_release(p);
   holdout_pass_release(p);
   if (p->state_ev) (void)hipEventDestroy(p->state_ev);
   delete p;  // and every device buffer it owns
@@ -347,8 +338,7 @@ int srmap_problem_set_solver(srmap_problem* p, int least_squares_solver, int num
 
 int srmap_problem_active_impl(const srmap_problem* p, int* impl) {
   if (!p || !impl) return SRMAP_EINVAL;
-  const bool ztile = p->impl != SRMAP_IMPL_DIRECT && p->zplan != nullptr;
-  *impl = ztile ? SRMAP_IMPL_TILED : SRMAP_IMPL_DIRECT;
+  *impl = ztile_active(p) ? SRMAP_IMPL_TILED : SRMAP_IMPL_DIRECT;
   return SRMAP_OK;
 }
 

@@ -158,10 +158,10 @@ int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, Eval
     const bool mine = ztile_reg_band_ok(p, terms);
     if (p->band_comm != (const void*)c || p->band_terms != terms || p->band_gen != p->plan_gen) {
       double flag = mine ? 0.0 : 1.0;  // max over the ranks of "I cannot" == 0  <=>  every rank can
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_cost.as<double>() + 7, &flag, sizeof(double), hipMemcpyHostToDevice, st));
-      rc = comm_allreduce(c, p->d_cost.as<double>() + 7, 1, SRMAP_F64, 1, st);
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(p->d_cost.as<double>() + kCostBand, &flag, sizeof(double), hipMemcpyHostToDevice, st));
+      rc = comm_allreduce(c, p->d_cost.as<double>() + kCostBand, 1, SRMAP_F64, 1, st);
       if (rc) return rc;
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(&flag, p->d_cost.as<double>() + 7, sizeof(double), hipMemcpyDeviceToHost, st));
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(&flag, p->d_cost.as<double>() + kCostBand, sizeof(double), hipMemcpyDeviceToHost, st));
       SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
       p->band_all = flag == 0.0;
       p->band_comm = c; p->band_terms = terms; p->band_gen = p->plan_gen;

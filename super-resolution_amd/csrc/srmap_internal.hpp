@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -105,7 +106,7 @@ struct RegSpec {
 struct SpFold { const void* xk = nullptr; const void* dvec = nullptr; double stp = 0.0; const double* norms = nullptr; };
 
 // What one evaluation is asked for beyond (terms, x, g), set by its caller for that call alone.  A default request
-// evaluates the whole problem and returns nothing but the cost in d_cost[0] (srmap_eval_device).
+// evaluates the whole problem and returns nothing but the cost in d_cost[kCostValue] (srmap_eval_device).
 struct EvalReq {
   // channels [c0, c0 + C) (split_channels solves one channel at a time, irls_map_solver.cpp:200-262; C = 0: all);
   // coupled: the view's neighbour planes are halo channels of a channel shard (3-D TV reads them)
@@ -127,11 +128,26 @@ struct EvalReq {
   struct Publish { double* out = nullptr; double* tag_slot = nullptr; double tag = 0.0; double* timeout_host = nullptr; } pub;
 };
 struct EvalOut {
-  bool gd_valid = false;   // the evaluation left g.d in d_cost[1]
+  bool gd_valid = false;   // the evaluation left g.d in d_cost[kCostGd]
   bool published = false;  // its finish kernel published {cost, g.d} and the tag (EvalReq::pub)
 };
 
 struct FitPass;  // below
+
+// the plan of the tile kernels (ztile_plan.hpp), owned by its problem
+struct ZPlan;
+struct ZPlanDelete { void operator()(ZPlan* z) const; };  // ztile_plan.hip
+
+// The scalars of srmap_problem::d_cost, host and device code alike
+constexpr int kCostValue = 0;    // the cost of the last evaluation
+constexpr int kCostGd = 1;       // its g.d (EvalOut::gd_valid)
+constexpr int kCostTimeout = 6;  // sticky: an in-kernel cost reduction gave up waiting for a workgroup (recover_reduction_timeout)
+constexpr int kCostBand = 7;     // scratch of the frame shards' row-band agreement (shard_eval.hip)
+constexpr int kCostSlots = 8;
+// A granule of the in-kernel cost reduction that has not been published yet holds this NaN pattern (both 32-bit halves
+// equal: hipMemsetD32 writes it).
+constexpr unsigned kSentinel32 = 0x7FF9ABCDu;
+constexpr unsigned long long kSentinel = ((unsigned long long)kSentinel32 << 32) | kSentinel32;
 
 }  // namespace srmap
 
@@ -220,9 +236,9 @@ struct srmap_problem {
   srmap::DevBuf d_x;              // [C][H][W] staging for host-buffer entry points
   srmap::DevBuf d_g;
   srmap::DevBuf d_tmp;            // [C][H][W] staging (gradient constants, values)
-  srmap::DevBuf d_partials;       // per-block cost partials
+  srmap::DevBuf d_partials;       // per-block cost partials; the second half: those of g.d (gd_partials)
   size_t partials_cap = 0;
-  srmap::DevBuf d_cost;           // [8] reduced scalars: [0] cost, [1] g.d (EvalOut::gd_valid), [6] time-out word
+  srmap::DevBuf d_cost;           // [kCostSlots] reduced scalars: kCostValue, kCostGd, kCostTimeout, kCostBand
   int solver = SRMAP_SOLVER_CG;     // srmap_problem_set_solver: the inner minimiser of srmap_solve
   int lbfgs_m = 5;                  // L-BFGS history length (num_lbfgs_hessian_corrections)
   double selfcheck_beta_den = 0.0;   // largest relative deviation of the derived beta denominator from the directly summed one
@@ -241,7 +257,7 @@ struct srmap_problem {
   bool band_all = false;
   int nreg = 0;
   srmap::RegSpec reg[srmap::kMaxRegularizers];
-  void* zplan = nullptr;          // srmap::ZPlan of the z-tile kernels (kernels_ztile.hip), owned; nullptr = not covered
+  std::unique_ptr<srmap::ZPlan, srmap::ZPlanDelete> zplan;  // plan of the tile kernels (ztile_plan.hip); empty = not covered
   size_t elem() const { return dtype == SRMAP_F32 ? 4 : 8; }
   size_t hr_count() const { return (size_t)geo.C * geo.H * geo.W; }
   size_t lr_count() const { return (size_t)geo.K * geo.C * geo.h * geo.w; }
@@ -291,6 +307,15 @@ inline int ensure(srmap_problem* p, DevBuf* buf, size_t bytes) {
   if (!*buf) SRMAP_HIP(p->ctx, buf->alloc(bytes));
   return SRMAP_OK;
 }
+// *dst <- a new block holding v (blocking copy)
+template <typename E>
+int upload_vector(srmap_problem* p, const std::vector<E>& v, DevBuf* dst) {
+  SRMAP_HIP(p->ctx, dst->alloc(sizeof(E) * v.size()));
+  SRMAP_HIP(p->ctx, hipMemcpy(dst->as(), v.data(), sizeof(E) * v.size(), hipMemcpyHostToDevice));
+  return SRMAP_OK;
+}
+// where an evaluation's partials of g.d go: the second half of d_partials (ensure_eval_partials sizes both halves)
+inline double* gd_partials(const srmap_problem* p) { return p->d_partials.as<double>() + p->partials_cap / 2; }
 
 // ---- the data term's direct kernels (kernels_data_direct.hip) ----
 // out = A_k x (y == nullptr) or A_k x - y_k for frames [k0, k0+nk); optional
@@ -347,6 +372,14 @@ bool dispatch_value(int v, F&& f) {
 template <typename F>
 void dispatch_scale(int s, F&& f) {
   if (!dispatch_value<2, 3, 4>(s, f)) f(std::integral_constant<int, 0>());
+}
+// the (scale, blur size) pairs the tile kernels (kernels_ztile.hip, kernels_spfwd.hip) are instantiated for: f(S, B) as
+// integral constants; false (and no call) for any other pair
+template <typename F>
+bool dispatch_scale_blur(int s, int b, F&& f) {
+  bool hit = false;
+  dispatch_value<2, 3, 4>(s, [&](auto S) { hit = dispatch_value<1, 3>(b, [&](auto B) { f(S, B); }); });
+  return hit;
 }
 // Leaves the problem without a displacement field, dense or on a lattice, and without their seeds (problem.hip): what a
 // motion setter does after model_drain, before it installs its own
@@ -432,19 +465,17 @@ int reduce_scratch_slots(size_t n);
 int launch_reduce_partials(srmap_problem* p, const double* partials, int n,
                            double* out, hipStream_t st);
 
-// ---- z-tile kernels (kernels_ztile.hip): the hot path ----
+// ---- the tile path: its plan and what reads it (ztile_plan.hip; ztile_plan.hpp for the plan itself), the kernels and
+// their launch (kernels_ztile.hip), the sequence of a tile evaluation (eval.hip) ----
 bool ztile_plan(srmap_problem* p);
-void ztile_release(srmap_problem* p);
 void ztile_preload(const srmap_problem* p);
 void ztile_rearm(srmap_problem* p);  // re-initialise the granules of the in-kernel cost reduction (after its time-out)
+// the plan when the tile path is in force for the problem's evaluations, else nullptr
+inline const ZPlan* ztile_active(const srmap_problem* p) { return p->impl != SRMAP_IMPL_DIRECT ? p->zplan.get() : nullptr; }
 bool ztile_overlaps_halo(const srmap_problem* p);  // the next tile evaluation can run interior tiles under the halo exchange
 bool ztile_reg_band_ok(const srmap_problem* p, unsigned terms);  // the tile kernel alone produces the regulariser part
 // a TERM_ALL evaluation over C channels with a direction can form its point from xk + stp * d itself (EvalReq::fold)
 bool ztile_can_fold(const srmap_problem* p, int C);
-size_t ztile_partials_needed(const srmap_problem* p);
-template <typename T>
-int launch_eval_ztile(srmap_problem* p, const EvalReq& req, EvalOut* out, const Geometry& geo, int obs_c0,
-                      unsigned terms, const T* x, T* g, double* partials, int* nblocks, hipStream_t st);
 // d_resid <- A_k x - y_k (UNWEIGHTED) of the channel view geo / obs_c0, by the forward kernel the problem's evaluations use
 // (the forward tile kernel where the plan has one, else the direct kernel); the cost partials it leaves are scratch
 template <typename T>
@@ -477,7 +508,7 @@ int eval_dispatch(srmap_problem* p, const EvalReq& req, EvalOut* out, unsigned t
                   hipStream_t st);
 // d_partials sized for any evaluation of the problem (and for the forward residual of a Huber step)
 int ensure_eval_partials(srmap_problem* p);
-// After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[6]; the host-mapped word
+// After a device-side reduction gave up waiting for a workgroup (sticky word d_cost[kCostTimeout]; the host-mapped word
 // host_word when given): re-initialise the granules behind everything in flight and clear both words.
 int recover_reduction_timeout(srmap_problem* p, double* host_word);
 // Stream ordering of the problem's device state (include/srmap.h, "Streams").  Before overwriting observations or

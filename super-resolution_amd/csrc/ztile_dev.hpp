@@ -1,20 +1,14 @@
-// ztile_dev.hpp -- device helpers, kernel-argument block and the host-side plan of the hot-path kernel
-// (kernels_ztile.hip: workgroup tiles).  Formulation: DESIGN.md section 3.1.
+// ztile_dev.hpp -- device helpers and the kernel-argument blocks of the hot-path kernel (kernels_ztile.hip: workgroup
+// tiles).  Device code only: the table records shared with the host arithmetic are ztile_tables.hpp's, the plan is
+// ztile_plan.hpp's.  Formulation: DESIGN.md section 3.1.
 #pragma once
-#include <algorithm>
-#include <climits>
 #include <cmath>
-#include <cstdlib>
-#include <vector>
 
 #include "cg_norm.hpp"
 #include "srmap_internal.hpp"
+#include "ztile_tables.hpp"
 
 namespace srmap {
-
-// integer floor division / modulo on the host
-static inline int fdiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-static inline int pmod(int a, int b) { return a - fdiv(a, b) * b; }
 
 namespace {
 
@@ -38,9 +32,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   v += dpp_perm_d<0x140>(v);  // row_mirror: every lane holds the sum of its row of 16
   return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
 }
-
-constexpr int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-constexpr int posmod(int a, int b) { return a - floordiv(a, b) * b; }
 
 template <typename T>
 __device__ __forceinline__ T absv(T d) { return d < T(0) ? -d : d; }
@@ -95,41 +86,8 @@ struct ZCfg {
   static constexpr int NP = REGK == 2 ? 2 * R + 1 : 1;
 };
 
-// Sub-pixel instances, source-major table: one record per (frame, vertical tap of the transpose warp) that lands on a
-// row phase -- LR row offset io, the two horizontal tap weights (already multiplied by the vertical one) and what follows
-// from the frame's integer column offset ox alone, worked out on the host (the scalar unit of a CU is shared by its
-// sixteen waves: per-source divisions and range tests there were a fifth of the kernel): a = (-ox) mod S, the residual
-// column offset q = (ox + a) / S of e = 0, and the first of the residual columns e in {-1, 0, 1} a cell's S + 2 HB pixels
-// use (am = a | (e_lo + 1) << 8; the kSpSlots(S, HB) columns from e_lo on are requested unconditionally -- no per-column
-// test on the scalar unit).  Rows of the table are padded to a multiple of kSpChunk with null records (am = kSpNull,
-// weights 0): a chunk's records are loaded back to back without control flow in between (z_row_sp2).
-struct ZSrc { int k, io, q, am; double w0, w1; };
-constexpr int kSpNull = 0xff;
+// residual columns a sub-pixel source requests per cell (ZSrc, ztile_tables.hpp)
 __host__ __device__ constexpr int kSpSlots(int S, int HB) { return (S == 2 && HB == 1) ? 3 : 2; }
-struct ZEntry { int k, io, jo, oyx; };  // frame, LR row / column offset of the residual a pixel of this phase owns,
-                                         // forward offset packed (oy << 16) | (ox & 0xffff)
-
-// The pixels of the border frame that can carry work, as six rectangles in HR coordinates (host: ring_rects()).
-// With blur reach (B - 1) / 2 <= 1 < S a frame k with forward offset o_k = (ox, oy) has
-//   * a residual whose z position S (i, j) + o_k lies OUTSIDE the image only in the rows [min oy, 0) / [H, H + max oy - S]
-//     and the columns [min ox, 0) / [W, W + max ox - S]                                (cost of ownerless residuals),
-//   * a contribution to an in-image pixel q that the clipped transpose warp excludes (q - o_k outside, while a residual
-//     sits within blur reach of q) only for q - o_k = -1 in a row or column, i.e. rows [0, max oy) and columns [0, max ox)
-//     (gradient corrections).
-// Everything else of the 2E-wide frame around the image edge evaluates to zero and is not enumerated.
-//   rg[0] = ti: TOP-INSIDE     rows [0, ti)       x columns [0, W)
-//   rg[1] = li: LEFT-INSIDE    columns [0, li)    x rows [ti, H)
-//   rg[2] = to: TOP-OUTSIDE    rows [-to, 0)      x columns [-lo, W + ro)
-//   rg[3] = bo: BOTTOM-OUTSIDE rows [H, H + bo)   x columns [-lo, W + ro)
-//   rg[4] = lo: LEFT-OUTSIDE   columns [-lo, 0)   x rows [0, H)
-//   rg[5] = ro: RIGHT-OUTSIDE  columns [W, W+ro)  x rows [0, H)
-struct RingRects { int rg[6]; };
-static_assert(std::is_trivially_copyable_v<RingRects>, "a kernel argument: no owner inside");
-
-__host__ __device__ __forceinline__ long long ring_count(const RingRects& r, int W, int H) {
-  const long long ti = r.rg[0], li = r.rg[1], to = r.rg[2], bo = r.rg[3], lo = r.rg[4], ro = r.rg[5];
-  return ti * W + li * (H - ti) + (to + bo) * (W + lo + ro) + (lo + ro) * H;
-}
 
 // pixel of the frame for thread index t
 __device__ __forceinline__ void ring_pixel(int t, int W, int H, const RingRects& r, int& qr, int& qc) {
@@ -159,10 +117,6 @@ __device__ __forceinline__ int ring_index(int qr, int qc, int W, int H, const Ri
   if (qc < li) return ti * W + (qr - ti) * li + qc;
   return -1;
 }
-
-// A granule that has not been published yet holds this NaN pattern (both 32-bit halves equal: hipMemsetD32 writes it).
-constexpr unsigned kSentinel32 = 0x7FF9ABCDu;
-constexpr unsigned long long kSentinel = ((unsigned long long)kSentinel32 << 32) | kSentinel32;
 
 // device-scope relaxed accesses: write-through stores / L1-bypassing loads (MI355X_MICROARCH.md, inter-workgroup visibility)
 template <typename U>
@@ -233,9 +187,9 @@ __device__ __forceinline__ void finish_block(const ArgsT& A, double* red /* LDS,
   }
   // re-arm: the next evaluation finds every granule unpublished.  NOT after a time-out: a workgroup that arrives late
   // would publish into a re-armed slot and the next evaluation would consume that stale partial; the granules stay as
-  // they are, cost_out[0] is NaN, the sticky word cost_out[6] tells the host to re-initialise them (eval.hip).
+  // they are, cost_out[kCostValue] is NaN, the sticky word cost_out[kCostTimeout] tells the host to re-initialise them (eval.hip).
   if (timed_out) {
-    if (tid == 0) { A.cost_out[0] = __builtin_nan(""); A.cost_out[6] = 1.0; if (A.to_host != nullptr) *(volatile double*)A.to_host = 1.0; if (WD && A.pub != nullptr) { A.pub[0] = A.cost_out[0]; A.pub[1] = 0.0; __threadfence_system(); *(volatile double*)A.tag_slot = A.tag; } }
+    if (tid == 0) { A.cost_out[kCostValue] = __builtin_nan(""); A.cost_out[kCostTimeout] = 1.0; if (A.to_host != nullptr) *(volatile double*)A.to_host = 1.0; if (WD && A.pub != nullptr) { A.pub[0] = A.cost_out[kCostValue]; A.pub[1] = 0.0; __threadfence_system(); *(volatile double*)A.tag_slot = A.tag; } }
     return;
   }
   for (int i = tid; i < A.n_partials; i += NT) {
@@ -244,9 +198,9 @@ __device__ __forceinline__ void finish_block(const ArgsT& A, double* red /* LDS,
   }
   if (tid == 0) {
     const double v = tot[0];
-    A.cost_out[0] = v;
+    A.cost_out[kCostValue] = v;
     if (WD) {
-      A.cost_out[1] = tot[1];
+      A.cost_out[kCostGd] = tot[1];
       if (A.pub != nullptr) {  // solver line search: {cost, g.d} straight to the host-mapped words, then the arrival tag
         A.pub[0] = v;
         A.pub[1] = tot[1];
@@ -310,7 +264,7 @@ struct ZArgs {
   int n_partials;        // granules of the evaluation
   double* mpart;         // cost granules [n_partials]; the sentinel pattern = not yet published
   double* mpart_gd;      // g.d granules [n_partials] (WD)
-  double* cost_out;      // [0] cost, [1] g.d
+  double* cost_out;      // the problem's d_cost: [kCostValue], [kCostGd], [kCostTimeout]
   double* pub;           // solver line search: host-mapped {cost, g.d}, then the arrival tag
   double* tag_slot;
   double tag;
@@ -359,11 +313,11 @@ __device__ __forceinline__ T step_pre(T dq) { return __builtin_fmin(__builtin_fm
 // ---- index helpers: `col` is a pixel column relative to the first pixel of the thread's cell ----
 template <typename C>
 __device__ __forceinline__ constexpr int xi(int row, int col) {
-  return row * C::XROW + posmod(col, C::TW / C::CW) * C::XC + C::XCL + floordiv(col, C::TW / C::CW);
+  return row * C::XROW + pmod(col, C::TW / C::CW) * C::XC + C::XCL + fdiv(col, C::TW / C::CW);
 }
 template <typename C>
 __device__ __forceinline__ constexpr int ci(int row, int col) {
-  return row * C::CROW + posmod(col, C::TW / C::CW) * C::CC + C::CCL + floordiv(col, C::TW / C::CW);
+  return row * C::CROW + pmod(col, C::TW / C::CW) * C::CC + C::CCL + fdiv(col, C::TW / C::CW);
 }
 
 // Read-only tables (frame table rounds > 0, edge-tile entries) are read through the CONSTANT
@@ -434,7 +388,7 @@ __device__ __forceinline__ void load_obs_row(const ArgsT& A, int pr, int rc, int
     for (int pc = 0; pc < S; ++pc) offs[pc] = (t == 0) ? A.off0[pr][pc] : ctab(A.off, slot + pc);  // t: uniform
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const int pcv = v - HB, pc = posmod(pcv, S), dc = floordiv(pcv, S);
+      const int pcv = v - HB, pc = pmod(pcv, S), dc = fdiv(pcv, S);
       const T* yp = yrow + (offs[pc] + dc);  // uniform pointer; the lane adds its (non-negative) cell index
       yv[v] = yp[(unsigned)lane];
     }
@@ -447,7 +401,7 @@ __device__ __forceinline__ void load_obs_row(const ArgsT& A, int pr, int rc, int
   for (int pc = 0; pc < S; ++pc) ent[pc] = (t == 0) ? aux0_at(A, pr, pc) : ctab(A.aux, slot + pc);  // t: uniform
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    const int pcv = v - HB, pc = posmod(pcv, S), dc = floordiv(pcv, S);
+    const int pcv = v - HB, pc = pmod(pcv, S), dc = fdiv(pcv, S);
     const ZEntry e = ent[pc];
     yv[v] = obs_at<T>(ybase + (size_t)e.k * A.obs_C * ((size_t)A.wl * A.hl), rc + e.io, cell0 + lane + dc + e.jo, A.hl, A.wl);
   }
@@ -520,7 +474,7 @@ __device__ __forceinline__ void z_row(const ArgsT& A, const T* __restrict__ xs, 
     const size_t slot = (size_t)(t * S + pr) * S;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const int pcv = v - HB, pc = posmod(pcv, S), dc = floordiv(pcv, S);
+      const int pcv = v - HB, pc = pmod(pcv, S), dc = fdiv(pcv, S);
       const bool own = pcv >= 0 && pcv < S;
       if (t < cn[pc]) {  // uniform
         T rr;
@@ -585,7 +539,6 @@ __device__ __forceinline__ void z_row(const ArgsT& A, const T* __restrict__ xs, 
 // is clamped and the WEIGHT masked per lane (nothing is done to the loaded value before the multiply-add, so a chunk's
 // loads stay in flight together); false: tile columns whose table columns all stay inside the LR image -- the address is
 // a uniform base + the lane, the weight a scalar operand of the multiply-add.
-constexpr int kSpChunk = 4;
 template <typename T, int S, typename C, int A, bool COLCLAMP, typename ArgsT>
 __device__ __forceinline__ void sp_apply(const ArgsT& A_, const T (&rv)[kSpSlots(S, C::HB)], int elo, int jbase, int lane,
                                          T w0, T w1, T (&z)[C::NV]) {
@@ -875,8 +828,6 @@ __device__ __forceinline__ void reg_pass2z(T (&acc)[S], const T* __restrict__ xs
 //       q only if q - o_k is inside the image.  The tiles add every frame; the excluded ones are collected here,
 //       corr[q] = 2 S^2 sum_tap B^T[tap] sum_{k in L(q + tap), q - o_k outside} r_k, and subtracted from g by
 //       k_finish_eval after the tile kernel.
-constexpr int kBorderTabEntries = 256;  // frame-table entries staged in LDS by the border blocks
-
 template <typename T>
 struct BorderArgs {      // device-resident (one per problem): only the border blocks read it
   const int2* hdr;       // flat frame table: (count, first entry) per (row phase, column phase)
@@ -890,8 +841,6 @@ struct BorderArgs {      // device-resident (one per problem): only the border b
 };
 static_assert(std::is_trivially_copyable_v<BorderArgs<float>> && std::is_trivially_copyable_v<BorderArgs<double>>,
               "a kernel argument: no owner inside");
-
-__device__ __forceinline__ int dfdiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
 // r_k(i, j) = (D B M_k x)(i, j) - y_k(i, j) with both clips (warped image, blur zero padding)
 // S, B at compile time and the taps from the kernel arguments: the B * B loads of a residual are requested together
@@ -966,7 +915,7 @@ __device__ __forceinline__ void border_block(const ArgsT& A, const BorderArgs<T>
     T corr = T(0);
     if (!inside) {
       if (A.terms & SRMAP_TERM_DATA) {
-        const int rc = dfdiv(qr, S), cc = dfdiv(qc, S);
+        const int rc = fdiv(qr, S), cc = fdiv(qc, S);
         const int2 h = s_hdr[(qr - rc * S) * S + (qc - cc * S)];
         for (int n = 0; n < h.x; ++n) {
           const ZEntry e = s_ent[h.y + n];
@@ -986,7 +935,7 @@ __device__ __forceinline__ void border_block(const ArgsT& A, const BorderArgs<T>
 #pragma unroll
         for (int b2 = 0; b2 < B; ++b2) {
           const int pr = qr + a - hb, pc = qc + b2 - hb;
-          const int rc = dfdiv(pr, S), cc = dfdiv(pc, S);
+          const int rc = fdiv(pr, S), cc = fdiv(pc, S);
           const int2 h = s_hdr[(pr - rc * S) * S + (pc - cc * S)];
           for (int n = 0; n < h.x; ++n) {
             const ZEntry e = s_ent[h.y + n];
@@ -1039,82 +988,5 @@ __device__ __forceinline__ void border_block(const ArgsT& A, const BorderArgs<T>
 
 
 }  // namespace
-
-// host side: plan (per problem, owned by the problem)
-struct ZPlan {
-  int S = 0, B = 1;
-  int regk = 0, regr = 0, reg_index = -1;
-  bool subpix = false;  // sub-pixel shifts: residuals from k_forward_direct, z by 4-tap tables, exact ring by k_gather_direct
-  int Dr = 0;           //   ring width
-  DevBuf d_ringbuf;            //   [C][ring pixels] data gradient of the ring pixels (the ring pass ahead of the tile kernel)
-  DevBuf d_spsrc;              //   ZSrc:   source-major tap table [S][spmax] (z_row_sp2)
-  int spn[4] = {0, 0, 0, 0};
-  int spmax = 0;
-  SpForwardPlan spf;    //   forward tile kernel (kernels_spfwd.hip); the direct forward kernel when it does not apply
-  int E = 0;   // max |shift|
-  int MS = 1;  // table slots per (row phase, column phase)
-  int n_ent = 0;
-  DevBuf d_hdr;                // int2: flat table of k_border: (count, first entry) per phase
-  DevBuf d_ent;                // ZEntry
-  int h_cnt[32] = {0};         // host copies handed to the kernel by value: [4][8] counts (+ max, min over the column phases)
-  long long h_off0[16] = {0};  //   [4][4] round-0 offsets
-  ZEntry h_aux0[16] = {};      //   [4][4] round-0 (frame, LR row / column offset) entries
-  DevBuf d_cnt;                // tile kernel: int [S][8]
-  DevBuf d_off;                //              long long [MS][S][S]
-  DevBuf d_aux;                //              ZEntry [MS][S][S]
-  int n_ring = 0;              // pixels of the border frame (0 when no shift produces border work)
-  RingRects ring = {{0, 0, 0, 0, 0, 0}};
-  DevBuf d_corr;               // [C][n_ring] border corrections of the gradient
-  DevBuf d_bd;                 // BorderArgs<T> (device)
-  DevBuf d_mpart;              // double: write-through partial granules of the in-kernel cost reduction, [2][mpart_cap] (cost, g.d); sentinel = unpublished
-  size_t mpart_cap = 0;
-};
-
-
-// in-kernel finish of this launch; publish {cost, g.d} to the solver's host words; plain partials of an earlier launch to add
-struct MFin { bool on, publish; const double* xpart; int n_xpart; };
-
-// Kernel arguments of the tile kernel (everything but the grid-dependent fields).
-template <typename T, int S, int B, int REGK, int R>
-static void fill_zargs(ZArgs<T, B, ZCfg<T, S, B, REGK, R>::NP>& A, srmap_problem* p, const Geometry& geo, int obs_c0,
-                       unsigned terms, const T* x, T* g, const T* wts, const ZPlan& z, double* partials, const T* dvec,
-                       double* partials_gd) {
-  using C = ZCfg<T, S, B, REGK, R>;
-  A.x = x; A.y = p->d_obs.as<const T>() + (size_t)obs_c0 * geo.w * geo.h; A.w = wts; A.g = g; A.partials = partials;
-  A.dvec = dvec; A.partials_gd = partials_gd;
-  A.cnt = z.d_cnt.as<int>(); A.off = z.d_off.as<long long>(); A.aux = z.d_aux.as<ZEntry>(); A.MS = z.MS;
-  A.spsrc = z.d_spsrc.as<ZSrc>(); A.spmax = z.spmax;
-  for (int pr = 0; pr < 4; ++pr) A.spn[pr] = z.spn[pr];
-  for (int pr = 0; pr < 4; ++pr) {
-    for (int i = 0; i < 8; ++i) A.cntk[pr][i] = z.h_cnt[pr * 8 + i];
-    for (int pc = 0; pc < 4; ++pc) { A.off0[pr][pc] = z.h_off0[pr * 4 + pc]; A.aux0[pr][pc] = z.h_aux0[pr * 4 + pc]; }
-  }
-  A.W = geo.W; A.H = geo.H; A.wl = geo.w; A.hl = geo.h;
-  A.obs_C = p->geo.C;
-  A.E = z.E;
-  A.ring = z.ring;
-  A.cr0 = geo.cr0; A.cr1 = geo.cr1;
-  A.rr0 = geo.rr0; A.rr1 = geo.rr1;
-  A.terms = (int)terms;
-  if (B == 1) { A.blur3[0] = A.blur3[1] = A.blur3[2] = T(1); A.k1s[0] = A.k1s[1] = T(1); }
-  else {
-    const int hb = (B - 1) / 2;
-    A.blur3[0] = (T)p->blur2d[0]; A.blur3[1] = (T)p->blur2d[hb]; A.blur3[2] = (T)p->blur2d[hb * B + hb];
-    A.k1s[0] = (T)p->blur1d[0]; A.k1s[1] = (T)p->blur1d[hb];
-  }
-  A.lambda = T(0);
-  for (int i = 0; i < C::NP; ++i) A.powtab[i] = T(1);
-  if (REGK != 0) {
-    const RegSpec& rs = p->reg[z.reg_index];
-    A.lambda = (T)rs.lambda;
-    if (REGK == 2) for (int i = 0; i < C::NP; ++i) A.powtab[i] = (T)rs.pow_table[i];
-  }
-  A.pwsum = T(0);
-  if (REGK == 2)
-    for (int i = 0; i < R; ++i)
-      for (int j = 0; j < R; ++j)
-        if (i + j > 0) A.pwsum += A.powtab[i + j];
-  A.fold_xk = nullptr; A.fold_x = nullptr; A.fold_stp = T(0); A.fold_norms = nullptr;
-}
 
 }  // namespace srmap

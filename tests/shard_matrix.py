@@ -9,7 +9,7 @@ its srmap_shard_desc and the part of the gradient it owns.  A RUN is a case with
 srmap_eval_sharded_device / srmap_solve_sharded call.
 
 The shapes are the smallest at which the named edge exists.  None had to be moved for the tile planner
-(kernels_ztile.hip plans a band when W, H > 4 E + 2 S, E the largest shift): the smallest band here is R3's last one,
+(ztile_plan.hip plans a band when W, H > 4 E + 2 S, E the largest shift): the smallest band here is R3's last one,
 12 + 3 rows against 4 * 1 + 2 * 3 = 10.  R4 is the other way round: it is there for the direct kernels, and at
 BAND_CASES[4]'s width of 32 the sub-pixel plan (W, H > 4 Dr + 2 S = 28, Dr = 2 + 2 + 1) takes the taller bands, so its
 width is 28, at which no band is planned.

@@ -86,7 +86,7 @@ class Geo:
         return int(math.ceil(max(max(abs(a), abs(b)) for a, b in self.shifts())))
 
     def tiles(self):
-        """Whether ztile_plan accepts the geometry (kernels_ztile.hip): 2 <= s <= 4, blur 1 / 3, a border frame that
+        """Whether ztile_plan accepts the geometry (ztile_plan.hip): 2 <= s <= 4, blur 1 / 3, a border frame that
         fits -- then IMPL_AUTO evaluates on the tile kernel, whose g.d instance forms the trial points (the fold)."""
         if not (2 <= self.s <= 4 and self.blur in (1, 3)):
             return False

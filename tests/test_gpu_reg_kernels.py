@@ -226,7 +226,7 @@ def test_with_data_term_accumulates(sr, ctx, kind, R, C, H, W, dtype):
 @pytest.mark.parametrize("first", [(0, 0), (2, 3)], ids=["tv", "btv3"])
 def test_auto_tile_with_march_second_regulariser(sr, ctx, first, dtype):
     """IMPL_AUTO at a tile-eligible size: the tile kernel fuses the first regulariser, the march adds 3-D TV onto its
-    gradient ("remaining regularisers" of launch_eval_ztile)."""
+    gradient ("remaining regularisers" of the tile evaluation, eval.hip launch_regs_direct)."""
     S, W, H, C = 2, 128, 24, 3
     shifts = [[0, 0], [0, 0]]
     rng = np.random.default_rng(5 + first[0])

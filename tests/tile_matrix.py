@@ -1,4 +1,4 @@
-"""The covering matrix of the tile path (csrc/kernels_ztile.hip launch_eval_ztile): every instance of k_eval_z at the
+"""The covering matrix of the tile path (csrc/kernels_ztile.hip, the sequence eval_ztile of csrc/eval.hip): every instance of k_eval_z at the
 ragged right / bottom edges it has to handle.  Shared by tests/test_gpu_tile_edges.py (HIP against the oracle) and
 tests/test_error_bars_cpu.py (the bars of tests/error_bars.py catch plausible kernel bugs on the same geometries).
 

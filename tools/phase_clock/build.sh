@@ -6,7 +6,7 @@
 set -e
 root=$(cd "$(dirname "$0")/../.." && pwd)
 mkdir -p /tmp/spx
-# SRMAP_TIME_SRC: another kernels_ztile.hip (the parent commit's, its ztile_dev.hpp beside it); SRMAP_TIME_OUT: the library's name
+# SRMAP_TIME_SRC: another kernels_ztile.hip (the parent commit's, its headers beside it); SRMAP_TIME_OUT: the library's name
 src=${SRMAP_TIME_SRC:-$root/super-resolution_amd/csrc/kernels_ztile.hip}
 out=${SRMAP_TIME_OUT:-$root/tools/phase_clock/libsrmap_time.so}
 python "$root/tools/phase_clock/patch_kernel.py" "$root" "$src" /tmp/spx/kz_time.hip

@@ -2,7 +2,7 @@
 phase boundaries of k_eval_z and a setter srmap_dbg_set_timing(buffer).  Timing-only: see build.sh / run.py."""
 import sys
 root = sys.argv[1] if len(sys.argv) > 1 else "/root/repo"
-# optional 2nd argument: another kernels_ztile.hip to instrument (e.g. the parent commit's, with its ztile_dev.hpp beside
+# optional 2nd argument: another kernels_ztile.hip to instrument (e.g. the parent commit's, with its headers beside
 # it); optional 3rd: where the instrumented copy goes
 srcfile = sys.argv[2] if len(sys.argv) > 2 else root + '/super-resolution_amd/csrc/kernels_ztile.hip'
 outfile = sys.argv[3] if len(sys.argv) > 3 else '/tmp/spx/kz_time.hip'
@@ -65,5 +65,5 @@ rep('''    else if (threadIdx.x == 0) {
       const int nbb = A.nby * gridDim.x;''','''    if (g_ztdbg && threadIdx.x == 0) { unsigned long long* d = g_ztdbg + ((size_t)(2048 + bidx) * 8) * 16; d[10] = brt0; d[11] = wall_clock64(); d[12] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492); d[13] = (bidx * C::NT < Bd.n_ring); }
     if (!(bidx * C::NT < Bd.n_ring) && threadIdx.x == 0) {
       const int nbb = A.nby * gridDim.x;''')
-rep('// ---------------------------------------------------------------------------------------------------------\n// host side: plan','extern "C" int srmap_dbg_set_timing(unsigned long long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_ztdbg), &buf, sizeof(buf)); }\n// ---------------------------------------------------------------------------------------------------------\n// host side: plan')
+rep('// ---------------------------------------------------------------------------------------------------------\n// host side: ','extern "C" int srmap_dbg_set_timing(unsigned long long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_ztdbg), &buf, sizeof(buf)); }\n// ---------------------------------------------------------------------------------------------------------\n// host side: ')
 open(outfile,'w').write(s)
