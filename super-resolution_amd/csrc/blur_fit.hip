@@ -125,9 +125,9 @@ template <typename T, int B, bool PER_CHANNEL>
 bool launch_sums_m(srmap_problem* p, const T* x, int chunks, int tpc, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K, PER_CHANNEL ? g.C : 1);
-  const MotionArgs<T> ma = motion_args<T>(p);
+  const MotionArgs<T> ma = p->motion.args<T>();
   const T* dw = p->dw.effective<T>();
-  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(p->motion.kind(), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
       hipLaunchKernelGGL((k_blur_fit_sums<T, B, MOTION, decltype(weighted)::value != 0, PER_CHANNEL>), grid, dim3(256), 0, st, x,
@@ -219,14 +219,8 @@ const char kOptionsName[] = "srmap_blur_fit_options";
 
 // srmap_fit_blur refuses while a bank is set (the host form after its other checks, the device form first)
 int refuse_bank(srmap_problem* p) {
-  if (p->blur_bank_mode == 0) return SRMAP_OK;
+  if (!p->blur.is_bank()) return SRMAP_OK;
   return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: the ridge and the energy at the kernel in force have no single kernel to refer to (srmap_fit_blur_bank fits a bank)");
-}
-
-// srmap_fit_blur_bank validates its mode first, in both forms
-int check_mode(srmap_problem* p, int mode) {
-  if (mode == SRMAP_BLUR_PER_FRAME || mode == SRMAP_BLUR_PER_CHANNEL || mode == SRMAP_BLUR_PER_FRAME_CHANNEL) return SRMAP_OK;
-  return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
 }
 
 // The one body of the two fits' device forms: a kernel per entry of `mode`, mode 0 the single kernel -- one entry over every
@@ -237,9 +231,8 @@ int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, 
   srmap_ctx* ctx = p->ctx;
   const Geometry& g = p->geo;
   const char* const what = mode ? "blur bank fit" : "blur fit";
-  if (field_motion(p))
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for %s: not available while one is set (%s)",
-                     field_motion_name(p), field_motion_setter(p));
+  if (p->motion.is_field())
+    return p->motion.refuse(ctx, SRMAP_EUNSUPPORTED, "the blur fit has no sampling leg for %s: not available while one is set (%s)");
   srmap_blur_fit_options opt;
   if (int rc = options_in_force(ctx, options, srmap_blur_fit_options_default, kOptionsName, &opt)) return rc;
   const int ksize = opt.ksize == 0 ? g.b : opt.ksize;
@@ -261,7 +254,7 @@ int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, 
   const int tpc = (int)std::max<long long>(kMinTilesPerChunk, (tiles + kMaxChunks - 1) / kMaxChunks);
   const int chunks = (int)((tiles + tpc - 1) / tpc);
   const int per_frame = mode ? g.C * chunks : chunks;
-  const int entries = blur_bank_entries(mode, g.K, g.C);
+  const int entries = BlurModel::entries(mode, g.K, g.C);
   FitPass fit;  // a row per entry, no table
   if (!fit.alloc(entries, P, (size_t)g.K * per_frame * P, false)) return set_error(ctx, SRMAP_ENOMEM, "%s: allocation failed", what);
   if (!dispatch_dtype(p->dtype, [&](auto t) {
@@ -269,7 +262,7 @@ int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, 
         return mode ? launch_sums<T, true>(p, ksize, (const T*)x_dev, chunks, tpc, fit.d_part.as<double>(), st)
                     : launch_sums<T, false>(p, ksize, (const T*)x_dev, chunks, tpc, fit.d_part.as<double>(), st);
       }))
-    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)motion_kind(p));
+    return set_error(ctx, SRMAP_EINVAL, "internal: the blur fit has no kernel for motion kind %d", (int)p->motion.kind());
   SRMAP_HIP(ctx, hipGetLastError());
   // the records of an entry, in (frame, channel, chunk) order: all of them, a frame's, a channel's chunks of every frame, or
   // the chunks of one (frame, channel)
@@ -285,10 +278,8 @@ int fit_device(srmap_problem* p, const void* x_dev, void* hip_stream, int mode, 
     // the (frame, channel) that stands for entry q, and the kernel in force for it, zero-padded or centre-cropped to ksize
     const int k = mode == SRMAP_BLUR_PER_FRAME ? q : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? q / g.C : 0;
     const int c = mode == SRMAP_BLUR_PER_CHANNEL ? q : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? q % g.C : 0;
-    const double* cur = p->blur_bank_mode ? p->blur_bank.data() + (size_t)blur_bank_entry(p->blur_bank_mode, g.C, k, c) * g.b * g.b
-                                          : p->blur2d.data();
     std::vector<double> h;
-    solve_taps(fit.sums(q), n, resized_kernel(cur, g.b, ksize), opt, &h, quality.data() + (size_t)q * 5);
+    solve_taps(fit.sums(q), n, resized_kernel(p->blur.entry_taps(k, c), g.b, ksize), opt, &h, quality.data() + (size_t)q * 5);
     std::copy(h.begin(), h.end(), taps.begin() + (size_t)q * n);
     any = any || quality[(size_t)q * 5 + 4] == 0.0;
   }
@@ -329,14 +320,14 @@ extern "C" int srmap_fit_blur_bank_device(srmap_problem* p, const void* x_dev, v
                                           const srmap_blur_fit_options* options, double* taps_out, double* quality_out,
                                           double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
-  if (int rc = check_mode(p, mode)) return rc;
+  if (int rc = BlurModel::check_bank_mode(p->ctx, mode)) return rc;
   return fit_device(p, x_dev, hip_stream, mode, options, taps_out, quality_out, normal_equations_out);
 }
 
 extern "C" int srmap_fit_blur_bank(srmap_problem* p, const double* x_host, int mode, const srmap_blur_fit_options* options,
                                    double* taps_out, double* quality_out, double* normal_equations_out) {
   if (!p || !x_host) return SRMAP_EINVAL;
-  if (int rc = check_mode(p, mode)) return rc;
+  if (int rc = BlurModel::check_bank_mode(p->ctx, mode)) return rc;
   if (int rc = host_fit_prologue(p, x_host, options, srmap_blur_fit_options_default, kOptionsName)) return rc;
   return fit_device(p, p->d_x.as(), p->ctx->stream, mode, options, taps_out, quality_out, normal_equations_out);
 }

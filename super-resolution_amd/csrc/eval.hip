@@ -186,8 +186,7 @@ static int eval_typed(srmap_problem* p, EvalReq req, EvalOut* out, unsigned term
     req.overlap.fn = nullptr;
   }
   if (p->impl == SRMAP_IMPL_TILED && !ztile) {
-    if (p->lat_step)
-      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover %s (%s)", field_motion_name(p), field_motion_setter(p));
+    if (p->motion.kind() == kMotionLattice) return p->motion.refuse(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover %s (%s)");
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "tiled kernels do not cover this geometry");
   }
   int nparts = 0;

@@ -112,34 +112,24 @@ __global__ __launch_bounds__(256) void k_forward_direct(
   }
 }
 
-// the device buffers of the problem's motion kind exist (a launcher's internal-consistency refusal)
-static int motion_buffers_ok(srmap_problem* p, int kind) {
-  if (kind == kMotionAffine && !p->d_affine) return set_error(p->ctx, SRMAP_EINVAL, "internal: no affine motion set");
-  if (kind == kMotionFlow && (!p->d_flow || !p->d_flow_seed)) return set_error(p->ctx, SRMAP_EINVAL, "internal: no displacement field set");
-  if (kind == kMotionLattice && (!p->d_lattice || !p->d_flow_seed)) return set_error(p->ctx, SRMAP_EINVAL, "internal: no flow lattice set");
-  return SRMAP_OK;
-}
-
 template <typename T>
 int launch_forward_direct(srmap_problem* p, const Geometry& g, const T* x, const T* y,
                           int obs_C, int obs_c0, T* out, int k0, int nk,
                           double* partials, int* nblocks, hipStream_t st, const T* dw) {
-  int kind = motion_kind(p);
-  if (int rc = motion_buffers_ok(p, kind)) return rc;
+  const int kind = p->motion.kind() == kMotionNone ? kMotionTable : p->motion.kind();  // no table: the sampler takes the identity
   if (dw != nullptr && y == nullptr) return set_error(p->ctx, SRMAP_EINVAL, "internal: data weights without observations");
-  if (kind == kMotionNone) kind = kMotionTable;  // no table: the sampler takes the identity
   dim3 grid((g.w * g.h + 255) / 256, g.C, nk);
   const double cost_scale = (double)g.s * (double)g.s;
-  const MotionArgs<T> ma = motion_args<T>(p);
-  const BlurStride bs = blur_stride(p);
+  const MotionArgs<T> ma = p->motion.args<T>();
+  const BlurStride bs = p->blur.stride();
   const bool launched = dispatch_value<kMotionTable, kMotionAffine, kMotionFlow, kMotionLattice>(kind, [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     if (dw != nullptr)
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, true>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
+                         p->blur.table<T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
     else
       hipLaunchKernelGGL((k_forward_direct<T, MOTION, false>), grid, dim3(256), 0, st, x, y, out, partials, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
+                         p->blur.table<T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), k0, cost_scale, obs_C, obs_c0, dw, bs);
   });
   if (!launched) return set_error(p->ctx, SRMAP_EINVAL, "internal: no forward kernel for motion kind %d", kind);
   if (nblocks) *nblocks = (int)(grid.x * grid.y * grid.z);
@@ -371,10 +361,10 @@ template <typename T, int MOTION>
 static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T* resid, T* g, int k0, int nk,
                                   double out_scale, bool accumulate, hipStream_t st, int obs_c0) {
   dim3 grid((unsigned)(((size_t)geo.W * geo.H + 255) / 256), geo.C);
-  const MotionArgs<T> ma = motion_args<T>(p);
-  const T* bt = p->d_blur_t.as<const T>();
+  const MotionArgs<T> ma = p->motion.args<T>();
+  const T* bt = p->blur.table_t<T>();
   const int acc1 = accumulate ? 1 : 0;
-  const BlurStride bs = blur_stride(p);
+  const BlurStride bs = p->blur.stride();
   dispatch_scale(geo.s, [&](auto sc) {
     hipLaunchKernelGGL((k_gather_sampled<T, MOTION, decltype(sc)::value>), grid, dim3(256), 0, st, resid, g, geo, ma, bt, k0, nk,
                        (T)out_scale, acc1, bs, obs_c0);
@@ -382,22 +372,20 @@ static void launch_gather_sampled(srmap_problem* p, const Geometry& geo, const T
 }
 
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring) {
-  return ring > 0 && 2 * ring < geo.H && 2 * ring < geo.W && p->has_motion && p->d_bwd_warps && geo.b <= geo.s &&
-         geo.s >= 2 && geo.s <= 4 && nk <= 16 && p->d_ytabs.empty();
+  return ring > 0 && 2 * ring < geo.H && 2 * ring < geo.W && p->motion.has_table() && geo.b <= geo.s && geo.s >= 2 &&
+         geo.s <= 4 && nk <= 16 && !p->motion.has_ytabs();
 }
 
 template <typename T>
 int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, T* g,
                          int k0, int nk, double out_scale, bool accumulate,
                          hipStream_t st, int ring, T* ringbuf, int obs_c0) {
-  const int kind = motion_kind(p);
-  if (p->blur_bank_mode != 0 && (ring > 0 || ringbuf != nullptr))
+  const int kind = p->motion.kind();
+  if (p->blur.is_bank() && (ring > 0 || ringbuf != nullptr))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which a blur bank has none of");
-  if (kind == kMotionAffine || kind == kMotionFlow || kind == kMotionLattice) {
+  if (!p->motion.is_created()) {
     if (ring > 0 || ringbuf != nullptr)
-      return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which %s has none of",
-                       kind == kMotionAffine ? "an affine motion" : field_motion_name(p));
-    if (int rc = motion_buffers_ok(p, kind)) return rc;
+      return p->motion.refuse(p->ctx, SRMAP_EINVAL, "internal: the ring pass belongs to the tile plan, which %s has none of");
     if (!dispatch_value<kMotionAffine, kMotionFlow, kMotionLattice>(kind, [&](auto motion) {
           launch_gather_sampled<T, decltype(motion)::value>(p, geo, resid, g, k0, nk, out_scale, accumulate, st, obs_c0);
         }))
@@ -411,8 +399,8 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
     if (2 * ring >= geo.H || 2 * ring >= geo.W) ring = 0;
     else npix = 2 * (size_t)ring * geo.W + 2 * (size_t)ring * (geo.H - 2 * ring);
   }
-  const WarpTaps<T>* wp = p->has_motion ? p->d_bwd_warps.as<const WarpTaps<T>>() : nullptr;
-  const T* bt = p->d_blur_t.as<const T>();
+  const WarpTaps<T>* wp = p->motion.bwd_dev<T>();
+  const T* bt = p->blur.table_t<T>();
   if (ringbuf != nullptr && !(accumulate && k0 == 0 && gather_ring_kernel_ok(p, geo, nk, ring)))
     return set_error(p->ctx, SRMAP_EINVAL, "internal: the ring buffer needs the ring kernel");
   if (ring > 0 && accumulate && k0 == 0 && gather_ring_kernel_ok(p, geo, nk, ring)) {
@@ -433,7 +421,7 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
   dim3 grid((unsigned)(ring > 0 ? (npix + ppb - 1) / ppb : (npix + 255) / 256), geo.C);
   dispatch_scale(geo.s, [&](auto sc) {
     hipLaunchKernelGGL((k_gather_direct<T, decltype(sc)::value>), grid, dim3(256), 0, st, resid, g, geo, wp, bt, k0, nk, (T)out_scale,
-                       accumulate ? 1 : 0, ring, groups, blur_stride(p), obs_c0);
+                       accumulate ? 1 : 0, ring, groups, p->blur.stride(), obs_c0);
   });
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;

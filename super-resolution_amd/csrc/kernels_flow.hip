@@ -178,23 +178,6 @@ static int flow_counts_answer(srmap_ctx* ctx, const char* what, const double cou
   return SRMAP_OK;
 }
 
-// The validated field (dense: `field` in the dtype; step > 0: `field` holds the lattice's nodes) and its seeds become the
-// problem's motion; both empty: the created motion is restored.  The three motions are alternatives
-static int flow_install(srmap_problem* p, DevBuf& field, DevBuf& seeds, int step, int lw, int lh) {
-  // evaluations in flight read the field: drain them before the buffers change
-  if (int rc = model_drain(p)) return rc;
-  const bool set = (bool)field;
-  field_motion_clear(p);  // the old field, lattice and seeds are freed
-  (step > 0 ? p->d_lattice : p->d_flow) = std::move(field);
-  p->d_flow_seed = std::move(seeds);
-  p->flow = set && step == 0;
-  if (set && step > 0) { p->lat_step = step; p->lat_lw = lw; p->lat_lh = lh; }
-  p->affine = false;  // a flow replaces an affine motion, and NULL restores the created motion
-  p->affine_recs.clear();
-  model_replan(p);  // "not covered" while a flow is set
-  return SRMAP_OK;
-}
-
 static int flow_seed_range(srmap_problem* p) {
   const Geometry& g = p->geo;
   if (((size_t)g.W + 2 * kFlowPad) * ((size_t)g.H + 2 * kFlowPad) >= ((size_t)1 << 31))
@@ -208,29 +191,30 @@ static int flow_set(srmap_problem* p, const double* flow_host, const void* flow_
   const Geometry& g = p->geo;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = (size_t)g.W * g.H, n = (size_t)g.K * 2 * N;
-  DevBuf nf, ns;  // the new field and its seeds: built here, moved into the problem once they are valid
+  MotionModel::Replacement r;  // the new field and its seeds: built here, installed once they are valid
   if (flow_host != nullptr || flow_dev != nullptr) {
     if (int rc = flow_seed_range(p)) return rc;
-    if (nf.alloc(n * p->elem()) != hipSuccess || ns.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
+    if (r.d_flow.alloc(n * p->elem()) != hipSuccess || r.d_seeds.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
       return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed (displacement field: %zu bytes, seeds: %zu bytes)", n * p->elem(),
                        (size_t)g.K * N * sizeof(int));
     int rc = SRMAP_OK;
     if (flow_dev) {
-      if (hipMemcpyAsync(nf.as(), flow_dev, n * p->elem(), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      if (hipMemcpyAsync(r.d_flow.as(), flow_dev, n * p->elem(), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return set_error(ctx, SRMAP_EHIP, "copying the displacement field failed");
     } else {
-      rc = convert_upload(p, flow_host, nf.as(), n, st);
+      rc = convert_upload(p, flow_host, r.d_flow.as(), n, st);
       if (rc) return rc;
     }
     double counts[3] = {0.0, 0.0, 0.0};
     rc = dispatch_dtype(p->dtype, [&](auto t) {
       using T = decltype(t);
-      return flow_seed_and_check<T, const T*>(p, nf.as<const T>(), ns.as<int>(), counts, st);
+      return flow_seed_and_check<T, const T*>(p, r.d_flow.as<const T>(), r.d_seeds.as<int>(), counts, st);
     });
     if (rc) return rc;
     if (int rc2 = flow_counts_answer(ctx, "displacement field", counts)) return rc2;
+    r.kind = kMotionFlow;
   }
-  return flow_install(p, nf, ns, 0, 0, 0);  // both empty when the call clears the flow
+  return p->motion.install(p, std::move(r));  // empty when the call clears the flow
 }
 
 // The lattice form: nodes [K][2][lh][lw] doubles, on the device (read on st) or on the host; both NULL restores the created
@@ -239,7 +223,7 @@ static int lattice_set(srmap_problem* p, int step, int lw, int lh, const double*
   srmap_ctx* ctx = p->ctx;
   const Geometry& g = p->geo;
   SRMAP_HIP(ctx, hipSetDevice(ctx->device));
-  DevBuf nn, ns;
+  MotionModel::Replacement r;
   if (nodes_host != nullptr || nodes_dev != nullptr) {
     if (step < 1 || step > kLatticeMaxStep) return set_error(ctx, SRMAP_EINVAL, "flow lattice: step %d is outside 1 ... %d", step, kLatticeMaxStep);
     if (lw < 2 || lh < 2) return set_error(ctx, SRMAP_EINVAL, "flow lattice: %d x %d nodes (at least 2 x 2)", lw, lh);
@@ -247,17 +231,18 @@ static int lattice_set(srmap_problem* p, int step, int lw, int lh, const double*
       return set_error(ctx, SRMAP_EINVAL, "flow lattice: %d x %d nodes at step %d reach more than a cell beyond the %d x %d image", lw, lh, step, g.W, g.H);
     if (int rc = flow_seed_range(p)) return rc;
     const size_t N = (size_t)g.W * g.H, bytes = (size_t)g.K * 2 * lw * lh * sizeof(double);
-    if (nn.alloc(bytes) != hipSuccess || ns.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
+    if (r.d_lattice.alloc(bytes) != hipSuccess || r.d_seeds.alloc((size_t)g.K * N * sizeof(int)) != hipSuccess)
       return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed (flow lattice: %zu bytes, seeds: %zu bytes)", bytes, (size_t)g.K * N * sizeof(int));
-    if (hipMemcpyAsync(nn.as(), nodes_dev ? nodes_dev : nodes_host, bytes, nodes_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(r.d_lattice.as(), nodes_dev ? nodes_dev : nodes_host, bytes, nodes_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st) != hipSuccess)
       return set_error(ctx, SRMAP_EHIP, "copying the flow lattice failed");
-    const LatticeDesc lat = {nn.as<const double>(), step, lw, lh};
+    const LatticeDesc lat = {r.d_lattice.as<const double>(), step, lw, lh};
     double counts[3] = {0.0, 0.0, 0.0};
-    int rc = dispatch_dtype(p->dtype, [&](auto t) { return flow_seed_and_check<decltype(t), LatticeDesc>(p, lat, ns.as<int>(), counts, st); });
+    int rc = dispatch_dtype(p->dtype, [&](auto t) { return flow_seed_and_check<decltype(t), LatticeDesc>(p, lat, r.d_seeds.as<int>(), counts, st); });
     if (rc) return rc;
     if (int rc2 = flow_counts_answer(ctx, "flow lattice (the interpolated field)", counts)) return rc2;
+    r.kind = kMotionLattice; r.step = step; r.lw = lw; r.lh = lh;
   }
-  return flow_install(p, nn, ns, step, lw, lh);
+  return p->motion.install(p, std::move(r));
 }
 
 }  // namespace srmap
@@ -276,10 +261,10 @@ extern "C" int srmap_problem_set_flow_device(srmap_problem* p, const void* flow_
 
 extern "C" int srmap_problem_get_flow(srmap_problem* p, double* flow_out, int* is_set) {
   if (!p) return SRMAP_EINVAL;
-  if (is_set) *is_set = p->flow ? 1 : 0;
-  if (!flow_out || !p->flow) return SRMAP_OK;
+  if (is_set) *is_set = p->motion.kind() == kMotionFlow ? 1 : 0;
+  if (!flow_out || p->motion.kind() != kMotionFlow) return SRMAP_OK;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  return convert_download(p, p->d_flow.as(), flow_out, (size_t)p->geo.K * 2 * p->geo.W * p->geo.H, p->ctx->stream);
+  return convert_download(p, p->motion.replacement().d_flow.as(), flow_out, (size_t)p->geo.K * 2 * p->geo.W * p->geo.H, p->ctx->stream);
 }
 
 extern "C" int srmap_problem_set_flow_lattice(srmap_problem* p, int step, int lw, int lh, const double* nodes_host) {
@@ -294,12 +279,13 @@ extern "C" int srmap_problem_set_flow_lattice_device(srmap_problem* p, int step,
 
 extern "C" int srmap_problem_get_flow_lattice(srmap_problem* p, int* step, int* lw, int* lh, double* nodes_out) {
   if (!p) return SRMAP_EINVAL;
-  if (step) *step = p->lat_step;
-  if (lw) *lw = p->lat_lw;
-  if (lh) *lh = p->lat_lh;
-  if (!nodes_out || !p->lat_step) return SRMAP_OK;
+  const MotionModel::Replacement& r = p->motion.replacement();
+  if (step) *step = r.step;
+  if (lw) *lw = r.lw;
+  if (lh) *lh = r.lh;
+  if (!nodes_out || !r.step) return SRMAP_OK;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  SRMAP_HIP(p->ctx, hipMemcpyAsync(nodes_out, p->d_lattice.as(), (size_t)p->geo.K * 2 * p->lat_lw * p->lat_lh * sizeof(double),
+  SRMAP_HIP(p->ctx, hipMemcpyAsync(nodes_out, r.d_lattice.as(), (size_t)p->geo.K * 2 * r.lw * r.lh * sizeof(double),
                                    hipMemcpyDeviceToHost, p->ctx->stream));
   SRMAP_HIP(p->ctx, hipStreamSynchronize(p->ctx->stream));
   return SRMAP_OK;

@@ -250,7 +250,7 @@ bool upload_frames(srmap_problem* p, SpForwardPlan* sp) {
   const int B = g.b, NB1 = B + 1;
   std::vector<SpFrame<T>> fr((size_t)g.K);
   for (int k = 0; k < g.K; ++k) {
-    const WarpTaps<double>& f = p->fwd_warps[k];
+    const WarpTaps<double>& f = p->motion.fwd()[k];
     SpFrame<T>& o = fr[k];
     o.oy = f.oy; o.ox = f.ox; o.pad0 = 0;
     o.rowb = -g.hb + f.oy - sp->RLO;
@@ -269,7 +269,7 @@ bool upload_frames(srmap_problem* p, SpForwardPlan* sp) {
           T s = T(0);
           for (int t = 0; t < 4; ++t) {
             const int a = a1 - (t >> 1), e = e1 - (t & 1);
-            if (a >= a_lo && a < B && e >= e_lo && e < B) s += (T)p->blur2d[(size_t)a * B + e] * w[t];
+            if (a >= a_lo && a < B && e >= e_lo && e < B) s += (T)p->blur.taps()[(size_t)a * B + e] * w[t];
           }
           o.comb[v][a1 * NB1 + e1] = s;
         }
@@ -326,10 +326,10 @@ bool spfwd_plan(srmap_problem* p, SpForwardPlan* sp) {
   *sp = SpForwardPlan();
   const Geometry& g = p->geo;
   const int S = g.s, B = g.b;
-  if (p->affine || field_motion(p) || !p->has_motion || !p->maps_regular || S < 2 || S > 4 || (B != 1 && B != 3)) return false;
+  if (p->motion.kind() != kMotionTable || !p->maps_regular || S < 2 || S > 4 || (B != 1 && B != 3)) return false;
   int omin = INT_MAX, omax = INT_MIN;
   for (int k = 0; k < g.K; ++k) {
-    const WarpTaps<double>& f = p->fwd_warps[k];
+    const WarpTaps<double>& f = p->motion.fwd()[k];
     if (f.ytab != nullptr || (f.ntaps != 1 && f.ntaps != 4)) return false;
     omin = std::min(omin, std::min(f.ox, f.oy));
     omax = std::max(omax, std::max(f.ox, f.oy));

@@ -560,8 +560,8 @@ static void fill_zargs(ZArgs<T, B, ZCfg<T, S, B, REGK, R>::NP>& A, srmap_problem
   if (B == 1) { A.blur3[0] = A.blur3[1] = A.blur3[2] = T(1); A.k1s[0] = A.k1s[1] = T(1); }
   else {
     const int hb = (B - 1) / 2;
-    A.blur3[0] = (T)p->blur2d[0]; A.blur3[1] = (T)p->blur2d[hb]; A.blur3[2] = (T)p->blur2d[hb * B + hb];
-    A.k1s[0] = (T)p->blur1d[0]; A.k1s[1] = (T)p->blur1d[hb];
+    A.blur3[0] = (T)p->blur.taps()[0]; A.blur3[1] = (T)p->blur.taps()[hb]; A.blur3[2] = (T)p->blur.taps()[hb * B + hb];
+    A.k1s[0] = (T)p->blur.factor()[0]; A.k1s[1] = (T)p->blur.factor()[hb];
   }
   A.lambda = T(0);
   for (int i = 0; i < C::NP; ++i) A.powtab[i] = T(1);

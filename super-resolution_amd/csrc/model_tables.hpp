@@ -30,7 +30,7 @@ inline void warp_tables(int W, int H, double dx, double dy, std::vector<int>* X,
     (*Y)[y] = (cv_round((M[4] * y + M[5]) * 1024) + 16 + cv_round(M[3] * 0 * 1024)) >> 5;
 }
 
-// One warp of one frame as the kernels take it (WarpTaps, srmap_internal.hpp): the integer offset, the x fraction index
+// One warp of one frame as the kernels take it (WarpTaps, motion_model.hpp): the integer offset, the x fraction index
 // and the four bilinear weights; ytab is empty unless the y table is not uniform.
 struct WarpTable {
   int ox = 0, oy = 0, ntaps = 1, fx = 0;

@@ -135,11 +135,11 @@ template <typename T>
 void launch_sums(srmap_problem* p, const T* x, const double* d_tab, int chunks, int ppt, double* d_part, hipStream_t st) {
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
-  const BlurStride bs = blur_stride(p);
+  const BlurStride bs = p->blur.stride();
   const T* dw = p->dw.effective<T>();
   dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
     hipLaunchKernelGGL((k_refine_sums<T, decltype(weighted)::value != 0>), grid, dim3(256), 0, st, x, p->d_obs.as<const T>(), dw, g,
-                       p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
+                       p->blur.table<T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), d_tab, ppt, d_part, bs);
   });
 }
 
@@ -165,9 +165,8 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
                                           double* quality_out, double* normal_equations_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
-  if (field_motion(p))
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while %s is set (%s)",
-                     field_motion_name(p), field_motion_setter(p));
+  if (p->motion.is_field())
+    return p->motion.refuse(ctx, SRMAP_EUNSUPPORTED, "motion refinement fits affine matrices: not available while %s is set (%s)");
   srmap_motion_refinement_options opt;
   if (int rc = options_in_force(ctx, options, srmap_motion_refinement_options_default, "srmap_motion_refinement_options", &opt)) return rc;
   if (opt.dof != 2 && opt.dof != 6) return set_error(ctx, SRMAP_EINVAL, "motion refinement: dof must be 2 or 6 (got %d)", opt.dof);
@@ -180,13 +179,14 @@ extern "C" int srmap_refine_motion_device(srmap_problem* p, const void* x_dev, v
 
   // starting matrices: the caller's, else the problem's affine motion, else its shifts, else the identity
   std::vector<double> start((size_t)K * 6, 0.0);
+  const std::vector<double>& set = p->motion.replacement().recs;  // the records of an affine motion in force
   for (int k = 0; k < K; ++k) {
     double* s = start.data() + 6 * (size_t)k;
     if (opt.initial_affine_2x3) std::copy(opt.initial_affine_2x3 + 6 * (size_t)k, opt.initial_affine_2x3 + 6 * (size_t)(k + 1), s);
-    else if (p->affine) std::copy(p->affine_recs.data() + (size_t)k * kAffineRec + 6, p->affine_recs.data() + (size_t)k * kAffineRec + 12, s);
+    else if (p->motion.kind() == kMotionAffine) std::copy(&set[(size_t)k * kAffineRec + 6], &set[(size_t)k * kAffineRec + 12], s);
     else {
       s[0] = 1.0; s[4] = 1.0;
-      if (p->has_motion) { s[2] = p->shifts[2 * (size_t)k]; s[5] = p->shifts[2 * (size_t)k + 1]; }
+      if (p->motion.has_table()) { s[2] = p->motion.shifts()[2 * (size_t)k]; s[5] = p->motion.shifts()[2 * (size_t)k + 1]; }
     }
   }
   std::vector<double> recs;

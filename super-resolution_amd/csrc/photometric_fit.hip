@@ -97,14 +97,14 @@ bool launch_sums(srmap_problem* p, const T* x, int chunks, int ppt, double* d_pa
   const Geometry& g = p->geo;
   dim3 grid(chunks, g.K);
   const T* y = (p->d_obs_raw ? p->d_obs_raw : p->d_obs).as<const T>();  // always the RAW frames: the fit is absolute
-  const MotionArgs<T> ma = motion_args<T>(p);
-  const BlurStride bs = blur_stride(p);
+  const MotionArgs<T> ma = p->motion.args<T>();
+  const BlurStride bs = p->blur.stride();
   const T* dw = p->dw.effective<T>();
-  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(motion_kind(p), [&](auto motion) {
+  return dispatch_value<kMotionNone, kMotionTable, kMotionAffine>(p->motion.kind(), [&](auto motion) {
     constexpr int MOTION = decltype(motion)::value;
     dispatch_value<0, 1>(dw != nullptr, [&](auto weighted) {
       hipLaunchKernelGGL((k_photometric_sums<T, MOTION, decltype(weighted)::value != 0>), grid, dim3(256), 0, st, x, y, dw, g, ma,
-                         p->d_blur.as<const T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
+                         p->blur.table<T>(), p->d_col_map.as<int>(), p->d_row_map.as<int>(), ppt, d_part, bs);
     });
   });
 }
@@ -210,9 +210,8 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
                                             double* quality_out, double* sums_out) {
   if (!p || !x_dev) return SRMAP_EINVAL;
   srmap_ctx* ctx = p->ctx;
-  if (field_motion(p))
-    return set_error(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for %s: not available while one is set (%s)",
-                     field_motion_name(p), field_motion_setter(p));
+  if (p->motion.is_field())
+    return p->motion.refuse(ctx, SRMAP_EUNSUPPORTED, "the photometric fit has no sampling leg for %s: not available while one is set (%s)");
   srmap_photometric_fit_options opt;
   int rc = options_in_force(ctx, options, srmap_photometric_fit_options_default, "srmap_photometric_fit_options", &opt);
   if (!rc) rc = photometric_option_values(p, opt);
@@ -231,7 +230,7 @@ extern "C" int srmap_fit_photometric_device(srmap_problem* p, const void* x_dev,
   FitPass fit;  // no table: every frame is fitted in the one pass
   if (!fit.alloc(K, kPhotoSums, (size_t)K * chunks * kPhotoSums, false)) return set_error(ctx, SRMAP_ENOMEM, "photometric fit: allocation failed");
   if (!dispatch_dtype(p->dtype, [&](auto t) { return launch_sums<decltype(t)>(p, (const decltype(t)*)x_dev, chunks, ppt, fit.d_part.as<double>(), st); }))
-    return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)motion_kind(p));
+    return set_error(ctx, SRMAP_EINVAL, "internal: the photometric fit has no kernel for motion kind %d", (int)p->motion.kind());
   if (!fit.reduce_and_fetch(chunks, st)) return set_error(ctx, SRMAP_EHIP, "photometric fit: pass failed");
 
   // ---- the host solve, frame by frame ----

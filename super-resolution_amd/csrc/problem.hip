@@ -6,28 +6,11 @@
 
 #include "affine_map.hpp"
 #include "model_tables.hpp"
-#include "solver_passes.hpp"
 #include "srmap_internal.hpp"
 
 using namespace srmap;
 
 namespace srmap {
-
-template <typename T>
-static int upload_warps(srmap_problem* p, const std::vector<WarpTaps<double>>& src, DevBuf* dst) {
-  std::vector<WarpTaps<T>> tmp(src.size());
-  for (size_t i = 0; i < src.size(); ++i) {
-    tmp[i].ox = src[i].ox; tmp[i].oy = src[i].oy; tmp[i].ntaps = src[i].ntaps; tmp[i].fx = src[i].fx;
-    tmp[i].ytab = src[i].ytab;
-    for (int t = 0; t < 4; ++t) tmp[i].w[t] = (T)src[i].w[t];
-  }
-  return upload_vector(p, tmp, dst);
-}
-
-template <typename T>
-static int upload_array(srmap_problem* p, const std::vector<double>& src, DevBuf* dst) {
-  return upload_vector(p, std::vector<T>(src.begin(), src.end()), dst);
-}
 
 int model_drain(srmap_problem* p) {
   if (p->use_stream) SRMAP_HIP(p->ctx, hipStreamSynchronize(p->use_stream));
@@ -38,14 +21,6 @@ int model_drain(srmap_problem* p) {
 void model_replan(srmap_problem* p) {
   p->plan_gen++;
   if (ztile_plan(p)) ztile_preload(p);
-}
-
-void field_motion_clear(srmap_problem* p) {
-  p->flow = false;
-  p->d_flow.reset();
-  p->d_flow_seed.reset();
-  p->lat_step = p->lat_lw = p->lat_lh = 0;
-  p->d_lattice.reset();
 }
 
 // srmap_problem_set_affine_motion (below) and the motion refinement: validate K 2x3 matrices and fill the per-frame
@@ -110,74 +85,16 @@ int srmap_problem_create(srmap_ctx* ctx, const srmap_problem_desc* d, srmap_prob
   g.w = (int)(g.W * scale_factor);
   g.h = (int)(g.H * scale_factor);
   if (g.w <= 0 || g.h <= 0) { delete p; return set_error(ctx, SRMAP_EINVAL, "image smaller than the scale"); }
-  g.b = blur ? d->blur_ksize : 1;
-  g.hb = (g.b - 1) / 2;
   g.cr0 = 0; g.cr1 = g.H;
   g.rr0 = 0; g.rr1 = g.H;
   g.zlo = 0; g.zhi = 0;
-  p->blur2d.assign((size_t)g.b * g.b, 1.0);
-  p->blur1d.assign((size_t)g.b, 1.0);
-  if (blur) gaussian_kernel(g.b, d->blur_sigma, &p->blur1d, &p->blur2d);
-  p->blur2d_t.resize(p->blur2d.size());
-  for (int a = 0; a < g.b; ++a)
-    for (int e = 0; e < g.b; ++e) p->blur2d_t[(size_t)a * g.b + e] = p->blur2d[(size_t)e * g.b + a];
-
-  p->created_b = g.b;
-  p->created_blur2d = p->blur2d;
-  p->created_blur2d_t = p->blur2d_t;
-  p->created_blur1d = p->blur1d;
-
-  int rc = SRMAP_OK;
-  p->has_motion = d->shifts_xy != nullptr;
-  if (p->has_motion) {
-    p->shifts.assign(d->shifts_xy, d->shifts_xy + 2 * (size_t)g.K);
-    p->fwd_warps.resize(g.K);
-    p->bwd_warps.resize(g.K);
-    auto upload_ytab = [&](const std::vector<int>& t, WarpTaps<double>* wt) -> int {
-      if (t.empty()) return SRMAP_OK;
-      DevBuf d;
-      if (d.alloc(sizeof(int) * t.size()) != hipSuccess ||
-          hipMemcpy(d.as(), t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed");
-      wt->ytab = d.as<const int>();
-      p->d_ytabs.push_back(std::move(d));
-      return SRMAP_OK;
-    };
-    // one warp of one frame: the tables of model_tables.hpp into the problem's tap record, the y table onto the device
-    auto warp = [&](int W, int H, double dx, double dy, WarpTaps<double>* wt) -> int {
-      WarpTable t;
-      switch (make_warp(W, H, dx, dy, &t)) {
-        case kWarpShiftTooLarge: return set_error(ctx, SRMAP_EUNSUPPORTED, "motion shift (%g, %g) too large", dx, dy);
-        case kWarpNonUniformX: return set_error(ctx, SRMAP_EUNSUPPORTED, "non-uniform warpAffine x table");
-        case kWarpOk: break;
-      }
-      wt->ox = t.ox; wt->oy = t.oy; wt->ntaps = t.ntaps; wt->fx = t.fx;
-      std::copy(t.w, t.w + 4, wt->w);
-      wt->ytab = nullptr;
-      return upload_ytab(t.ytab, wt);
-    };
-    for (int k = 0; k < g.K && rc == SRMAP_OK; ++k) {
-      rc = warp(g.W, g.H, p->shifts[2 * k], p->shifts[2 * k + 1], &p->fwd_warps[k]);
-      // the transpose warps an image of size (w*s, h*s)
-      if (rc == SRMAP_OK) rc = warp(g.w * g.s, g.h * g.s, -p->shifts[2 * k], -p->shifts[2 * k + 1], &p->bwd_warps[k]);
-    }
-  }
   std::vector<int> cmap, rmap;
   nearest_map(g.W, g.w, &cmap);
   nearest_map(g.H, g.h, &rmap);
   p->maps_regular = maps_regular(g.W, g.H, g.w, g.h, g.s, cmap, rmap);
   auto fail = [&](int code) { srmap_problem_destroy(p); return code; };
-  if (rc) return fail(rc);
-  rc = dispatch_dtype(p->dtype, [&](auto t) {
-    using T = decltype(t);
-    if (p->has_motion) {
-      if (int r = upload_warps<T>(p, p->fwd_warps, &p->d_fwd_warps)) return r;
-      if (int r = upload_warps<T>(p, p->bwd_warps, &p->d_bwd_warps)) return r;
-    }
-    if (int r = upload_array<T>(p, p->blur2d, &p->d_blur)) return r;
-    return upload_array<T>(p, p->blur2d_t, &p->d_blur_t);
-  });
-  if (rc) return fail(rc);
+  if (int rc = p->motion.create(p, d->shifts_xy)) return fail(rc);
+  if (int rc = p->blur.create(p, blur ? d->blur_ksize : 0, d->blur_sigma)) return fail(rc);
   if (p->d_col_map.alloc(sizeof(int) * g.w) != hipSuccess || p->d_row_map.alloc(sizeof(int) * g.h) != hipSuccess ||
       p->d_cost.alloc(sizeof(double) * kCostSlots) != hipSuccess)
     return fail(set_error(ctx, SRMAP_ENOMEM, "hipMalloc failed"));
@@ -211,114 +128,43 @@ int srmap_problem_set_impl(srmap_problem* p, int impl) {
 int srmap_problem_set_affine_motion(srmap_problem* p, const double* affine_2x3) {
   if (!p) return SRMAP_EINVAL;
   SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  std::vector<double> recs;
+  MotionModel::Replacement r;  // stays empty for NULL: the created motion is restored
   if (affine_2x3) {
-    int rc = affine_records(p->ctx, p->geo.K, affine_2x3, &recs);
-    if (rc) return rc;  // the problem keeps the motion it had
+    if (int rc = affine_records(p->ctx, p->geo.K, affine_2x3, &r.recs)) return rc;  // the problem keeps the motion it had
+    if (int rc = upload_vector(p, r.recs, &r.d_recs)) return rc;
+    r.kind = kMotionAffine;
   }
-  // evaluations in flight read the records: drain them before the buffer changes
-  if (int rc = model_drain(p)) return rc;
-  if (affine_2x3) {
-    if (int rc = ensure(p, &p->d_affine, recs.size() * sizeof(double))) return rc;
-    SRMAP_HIP(p->ctx, hipMemcpy(p->d_affine.as<double>(), recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
-    p->affine_recs.swap(recs);
-    p->affine = true;
-  } else {
-    p->affine = false;
-    p->affine_recs.clear();
-    p->d_affine.reset();
-  }
-  // alternatives: an affine motion replaces a displacement field (dense or on a lattice), and NULL restores the created motion
-  field_motion_clear(p);
-  model_replan(p);  // "not covered" while an affine motion is set
-  return SRMAP_OK;
+  return p->motion.install(p, std::move(r));
 }
 
 // ---- free-form blur kernel (no reference counterpart; BlurModule builds a Gaussian only, blur_module.cpp:13-22) ----
-// The blur of the problem from the caller's taps: `entries` tables of ksize x ksize (bank_mode 0: the one free-form kernel, entries
-// 1), or the created blur for taps == NULL.  The one path of srmap_problem_set_blur_kernel and srmap_problem_set_blur_bank.
-static int install_blur(srmap_problem* p, int bank_mode, int entries, int ksize, const double* taps) {
-  const char* what = bank_mode ? "blur bank" : "blur kernel";
-  if (taps) {
-    if (ksize < 1 || ksize % 2 != 1) return set_error(p->ctx, SRMAP_EINVAL, "%s size must be odd and >= 1 (got %d)", what, ksize);
-    if (ksize > kMaxCustomBlur)
-      return set_error(p->ctx, SRMAP_EUNSUPPORTED, "%s size %d: a free-form kernel has at most %d x %d taps", what, ksize, kMaxCustomBlur, kMaxCustomBlur);
-    for (int i = 0; i < entries * ksize * ksize; ++i)
-      if (!std::isfinite(taps[i])) return set_error(p->ctx, SRMAP_EINVAL, "%s: tap %d is not finite", what, i);
-  }
-  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
-  const int b = taps ? ksize : p->created_b;
-  const size_t bb = (size_t)b * b;
-  std::vector<double> k2, k2t;
-  if (taps) {
-    k2.assign(taps, taps + (size_t)entries * bb);
-    k2t.resize(k2.size());
-    // the adjoint of a correlation is the correlation with the kernel flipped in BOTH axes (kernel.t(), the reference's
-    // form, is that only for a kernel symmetric under both); per entry of a bank
-    for (int q = 0; q < entries; ++q)
-      for (int a = 0; a < b; ++a)
-        for (int e = 0; e < b; ++e) k2t[q * bb + (size_t)a * b + e] = k2[q * bb + (size_t)(b - 1 - a) * b + (b - 1 - e)];
-  } else {
-    k2 = p->created_blur2d;
-    k2t = p->created_blur2d_t;
-  }
-  // the new tables first: a failed allocation leaves the problem as it was
-  DevBuf nb, nbt;
-  int rc = dispatch_dtype(p->dtype, [&](auto t) {
-    if (int r = upload_array<decltype(t)>(p, k2, &nb)) return r;
-    return upload_array<decltype(t)>(p, k2t, &nbt);
-  });
-  if (rc) return rc;
-  // evaluations in flight read the old tables: drain them before the buffers change
-  rc = model_drain(p);
-  if (rc) return rc;
-  p->d_blur = std::move(nb);  // the new tables move in; the old ones are freed
-  p->d_blur_t = std::move(nbt);
-  const bool bank = taps != nullptr && bank_mode != 0;
-  p->blur_bank_mode = bank ? bank_mode : 0;
-  p->blur_bank = bank ? k2 : std::vector<double>();
-  if (bank) {  // the host mirrors of the single kernel hold entry 0
-    k2.resize(bb);
-    k2t.resize(bb);
-  }
-  p->blur2d.swap(k2);
-  p->blur2d_t.swap(k2t);
-  p->blur1d = taps ? std::vector<double>((size_t)b, 0.0) : p->created_blur1d;  // a free-form kernel has no separable factor
-  p->geo.b = b;
-  p->geo.hb = (b - 1) / 2;
-  p->custom_blur = taps != nullptr;
-  model_replan(p);  // "not covered" while a free-form kernel or a bank is set
-  return SRMAP_OK;
-}
-
 int srmap_problem_set_blur_kernel(srmap_problem* p, int ksize, const double* taps) {
   if (!p) return SRMAP_EINVAL;
-  return install_blur(p, 0, 1, ksize, taps);
+  return p->blur.install(p, 0, ksize, taps);
 }
 
 int srmap_problem_get_blur_kernel(const srmap_problem* p, int* ksize, double* taps_out) {
   if (!p) return SRMAP_EINVAL;
   if (ksize) *ksize = p->geo.b;
-  if (taps_out && p->blur_bank_mode != 0)
+  if (taps_out && p->blur.is_bank())
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur bank is set: no single kernel is in force (srmap_problem_get_blur_bank returns its entries)");
-  if (taps_out) std::copy(p->blur2d.begin(), p->blur2d.end(), taps_out);
+  if (taps_out) std::copy(p->blur.taps().begin(), p->blur.taps().end(), taps_out);
   return SRMAP_OK;
 }
 
 // ---- blur-kernel bank: a kernel per frame, per channel or per (frame, channel) (no reference counterpart) ----
 int srmap_problem_set_blur_bank(srmap_problem* p, int mode, int ksize, const double* taps) {
   if (!p) return SRMAP_EINVAL;
-  if (!taps) return install_blur(p, 0, 1, 0, nullptr);
-  if (mode != SRMAP_BLUR_PER_FRAME && mode != SRMAP_BLUR_PER_CHANNEL && mode != SRMAP_BLUR_PER_FRAME_CHANNEL)
-    return set_error(p->ctx, SRMAP_EINVAL, "unknown blur bank mode %d", mode);
-  return install_blur(p, mode, blur_bank_entries(mode, p->geo.K, p->geo.C), ksize, taps);
+  if (!taps) return p->blur.install(p, 0, 0, nullptr);
+  if (int rc = BlurModel::check_bank_mode(p->ctx, mode)) return rc;
+  return p->blur.install(p, mode, ksize, taps);
 }
 
 int srmap_problem_get_blur_bank(const srmap_problem* p, int* mode, int* ksize, double* taps_out) {
   if (!p) return SRMAP_EINVAL;
-  if (mode) *mode = p->blur_bank_mode;
+  if (mode) *mode = p->blur.bank_mode();
   if (ksize) *ksize = p->geo.b;
-  if (taps_out) std::copy(p->blur_bank.begin(), p->blur_bank.end(), taps_out);
+  if (taps_out && p->blur.is_bank()) std::copy(p->blur.taps().begin(), p->blur.taps().end(), taps_out);
   return SRMAP_OK;
 }
 

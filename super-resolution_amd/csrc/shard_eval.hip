@@ -22,20 +22,9 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what) {
   if (p->dw.robust())
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "data weights / a Huber loss are not sharded over a communicator%s: %s",
                      solve ? " (the weights are not split with the frames or rows)" : "", tail);
-  if (p->affine)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "an affine motion model is not sharded over a communicator%s: %s",
-                     solve ? " (only the direct family runs it)" : "", tail);
-  if (p->flow)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a displacement-field motion model is not sharded over a communicator%s: %s",
-                     solve ? " (only the direct family runs it)" : "", tail);
-  if (p->lat_step)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a displacement-field motion model on a control lattice is not sharded over a communicator%s: %s",
-                     solve ? " (only the direct family runs it)" : "", tail);
-  if (p->blur_bank_mode != 0)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a blur-kernel bank is not sharded over a communicator%s: %s",
-                     solve ? " (only the direct family runs it)" : "", tail);
-  if (p->custom_blur)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "a free-form blur kernel is not sharded over a communicator%s: %s",
+  // a replaced motion, then a replaced blur, in the owners' words
+  if (const char* model = p->motion.sharded_name() ? p->motion.sharded_name() : p->blur.sharded_name())
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "%s is not sharded over a communicator%s: %s", model,
                      solve ? " (only the direct family runs it)" : "", tail);
   return SRMAP_OK;
 }
@@ -51,7 +40,7 @@ int shard_exchange_x(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd
     // a frame whose warpAffine y coordinate sits on a 1/32-px rounding tie carries a per-row table built from the row
     // index of THIS problem (model_tables.hpp make_warp): a band problem would evaluate the tie at its local rows, not
     // the joint image's
-    if (!p->d_ytabs.empty())
+    if (p->motion.has_ytabs())
       return set_error(p->ctx, SRMAP_EUNSUPPORTED, "row shard: a sub-pixel shift on a 1/32-px rounding tie needs the joint image's row index; shard such problems by frames or channels");
     const int hu = sd->own_row0, hd = g.H - sd->own_row1;  // my halo rows above / below
     if ((up >= 0 && hu == 0) || (down >= 0 && hd == 0) || sd->send_down_rows > sd->own_row1 - sd->own_row0 ||

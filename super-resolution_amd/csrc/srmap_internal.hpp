@@ -11,78 +11,22 @@
 #include <type_traits>
 #include <vector>
 
+#include "blur_model.hpp"
 #include "data_weights.hpp"
 #include "dev_mem.hpp"
+#include "motion_model.hpp"
 #include "srmap.h"
 
 namespace srmap {
 
 constexpr int kMaxRegularizers = 4;
 constexpr int kMaxBtvRange = 8;        // alpha^(i+j) table holds 2*range+1 entries
-constexpr int kMaxBlurTaps = 15 * 15;  // b*b taps kept in kernel-argument space
-constexpr int kMaxCustomBlur = 7;      // largest size of a free-form kernel (srmap_problem_set_blur_kernel, srmap_fit_blur)
-// Affine motion (srmap_problem_set_affine_motion): doubles per frame record -- [0..5] the inverse map
-// [ia ib itx; ic id ity], [6..11] the forward map [a b tx; c d ty], [12..13] the candidate radii of the transpose gather
-constexpr int kAffineRec = 16;
-constexpr double kAffineMaxDeviation = 0.25;  // max(|a-1|+|b|, |c|+|d-1|): bounds the gather at 3 x 3 candidates
-// Displacement-field motion (srmap_problem_set_flow, kernels_flow.hip): the transpose gathers the (2 r + 1)^2 candidates
-// around a stored seed
-constexpr int kFlowRadius = 2;
-
-// One MotionModule warp (forward or transpose) of one frame, as cv::warpAffine
-// evaluates it (motion_module.cpp:18-51): source pixel = destination + (ox, oy)
-// plus up to four bilinear taps with 1/32-pixel quantised weights.
-template <typename T>
-struct WarpTaps {
-  int ox, oy;
-  int ntaps;  // 1 = integer shift (weights 1,0,0,0), 4 = bilinear
-  int fx;     // x fraction index 0..31 (1/32 px) -- used with ytab
-  T w[4];     // (0,0) (1,0) (0,1) (1,1) as (dx,dy) tap offsets
-  // warpAffine evaluates the y coordinate of every row in floating point before quantising it to 1/32 px; for a dy
-  // within rounding distance of a quantisation tie the fraction index differs from row to row.  Then ytab (device,
-  // one int per destination row: source row << 5 | fraction index) replaces oy and the y half of w.
-  const int* ytab;
-};
-static_assert(std::is_trivially_copyable_v<WarpTaps<float>> && std::is_trivially_copyable_v<WarpTaps<double>>,
-              "a kernel argument: no owner inside");
-
-// The forms of M_k in A_k = D B M_k: none (the identity), the translational tap table, an affine matrix per frame, a dense
-// displacement field per frame, a displacement field on a control lattice per frame.  MotionArgs: what the kernels that
-// sample M_k (MotionSampler, sample_dev.hpp) take for it, by value as ONE kernel argument; a kind reads its own members
-// only.
-enum MotionKind { kMotionNone = 0, kMotionTable = 1, kMotionAffine = 2, kMotionFlow = 3, kMotionLattice = 4 };
-// The control lattice of a displacement field (srmap_problem_set_flow_lattice, kernels_flow.hip): lw x lh nodes
-// per component, node (i, j) at HR pixel (i * step, j * step); nodes [K][2][lh][lw] doubles in both dtypes
-constexpr int kLatticeMaxStep = 1024;
-struct LatticeDesc {
-  const double* nodes;
-  int step, lw, lh;
-};
-static_assert(std::is_trivially_copyable_v<LatticeDesc>, "a kernel argument: no owner inside");
-template <typename T>
-struct MotionArgs {
-  const WarpTaps<T>* warps;  // [K] forward taps (table); nullptr: the identity
-  const double* recs;        // [K][kAffineRec] (affine)
-  const T* flow;             // [K][2][H][W] (flow)
-  const int* seeds;          // [K][H][W] packed seeds of the transpose gather (flow, lattice)
-  LatticeDesc lat;           // (lattice)
-};
-static_assert(std::is_trivially_copyable_v<MotionArgs<float>> && std::is_trivially_copyable_v<MotionArgs<double>>,
-              "a kernel argument: no owner inside");
-
-// Blur-kernel bank (srmap_problem_set_blur_bank): the blur tables hold one b x b entry per frame, per channel or per
-// (frame, channel), stored [k][c]; a kernel reads entry (k, c) at table + k * frame + c * channel (elements; c the
-// ABSOLUTE channel of the problem, k the absolute frame).  {0, 0} without a bank: every (k, c) reads the one kernel.
-struct BlurStride {
-  int frame, channel;
-};
-static_assert(std::is_trivially_copyable_v<BlurStride>, "a kernel argument: no owner inside");
 
 struct Geometry {
   int W, H, C, K;  // HR size, channels, frames
   int w, h;        // LR size
   int s;           // scale
-  int b, hb;       // blur kernel size (1 = none) and (b-1)/2
+  int b, hb;       // blur kernel size (1 = none) and (b-1)/2; written by BlurModel alone (blur_model.hpp)
   int rr0, rr1;    // HR rows [rr0, rr1) whose regulariser terms (gradient AND cost) this evaluation produces
                    // (EvalReq::rr0/rr1, multiples of 8, the tile height; default 0, H)
   int cr0, cr1;    // HR rows [cr0, cr1) whose cost terms are counted (row-band sharding; default 0, H):
@@ -169,47 +113,13 @@ struct srmap_problem {
   srmap::Geometry geo{};
   int dtype = SRMAP_F64;
   int impl = SRMAP_IMPL_AUTO;
-  bool has_motion = false;
   bool maps_regular = true;       // decimation map == s*j on both axes
-  std::vector<double> shifts;     // K x 2
-  // affine motion model: when set, the data term of every evaluation and operator samples the frame's matrix (kMotionAffine)
-  // and the tile planner answers "not covered"; the translational warps above stay as created (NULL restores them)
-  bool affine = false;
-  std::vector<double> affine_recs;  // K x kAffineRec (host mirror of d_affine)
-  srmap::DevBuf d_affine;         // double[K][kAffineRec]
-  // displacement-field motion model (an alternative to the affine one: setting either replaces the other): when set, the
-  // data term samples the frame's field (kMotionFlow).  d_flow: [K][2][H][W] dtype, the (ux, uy) planes per frame; d_flow_seed: [K][H][W]
-  // packed seeds of the transpose gather, both validated when they were set
-  bool flow = false;
-  srmap::DevBuf d_flow, d_flow_seed;
-  // the same model with the field kept as values on a control lattice and interpolated in the kernels (kMotionLattice; a
-  // third alternative): d_lattice [K][2][lat_lh][lat_lw] doubles in both dtypes, its seeds in d_flow_seed.  lat_step = 0: none
-  int lat_step = 0, lat_lw = 0, lat_lh = 0;
-  srmap::DevBuf d_lattice;
-  std::vector<double> blur2d;     // b*b (double); transposed copy in blur2d_t
-  std::vector<double> blur2d_t;
-  std::vector<double> blur1d;     // b (the separable factor: blur2d = blur1d * blur1d^T)
-  // free-form blur kernel (srmap_problem_set_blur_kernel): while set, geo.b / geo.hb and blur2d hold the caller's taps,
-  // blur2d_t their FLIP in both axes (the exact transpose of a correlation), the tile planner answers "not covered" and
-  // the direct family runs.  created_*: the blur the problem was created with, which NULL restores bit for bit
-  bool custom_blur = false;
-  int created_b = 1;
-  std::vector<double> created_blur2d, created_blur2d_t, created_blur1d;
-  // blur-kernel bank (srmap_problem_set_blur_bank; an alternative to the free-form kernel: setting either replaces the
-  // other): blur_bank_mode is the srmap_blur_bank_mode (0 = none), blur_bank the caller's taps [entries][b][b]; d_blur holds
-  // them in the dtype and d_blur_t the flip of every entry; custom_blur is true, blur2d / blur2d_t hold entry 0
-  int blur_bank_mode = 0;
-  std::vector<double> blur_bank;
-  // device constants
-  std::vector<srmap::DevBuf> d_ytabs;     // per-row y tables of frames whose warpAffine y table is not uniform (owned)
-  srmap::DevBuf d_fwd_warps;      // WarpTaps<T>[K]
-  srmap::DevBuf d_bwd_warps;      // WarpTaps<T>[K]
-  srmap::DevBuf d_blur;           // T[b*b]; T[entries][b*b] while a bank is set
-  srmap::DevBuf d_blur_t;         // T[b*b]; T[entries][b*b]
+  // the forward model A_k = D B M_k: the motion and the blur in force, each with one owner -- the states, what NULL
+  // restores and who re-plans: motion_model.hpp, blur_model.hpp
+  srmap::MotionModel motion;
+  srmap::BlurModel blur;
   srmap::DevBuf d_col_map;        // int[w]  decimation source column
   srmap::DevBuf d_row_map;        // int[h]
-  // host mirrors of the warp taps (double) for tile planning
-  std::vector<srmap::WarpTaps<double>> fwd_warps, bwd_warps;
   // state
   srmap::DevBuf d_obs;            // [K][C][h][w] dtype
   bool have_obs = false;
@@ -335,32 +245,6 @@ int launch_gather_direct(srmap_problem* p, const Geometry& geo, const T* resid, 
 // (obs_c0: the problem's channel of the view's channel 0, which selects the entries of a per-channel blur bank)
 // whether the ring mode (ring > 0) runs as k_gather_ring (which can also write the ring's values to a side buffer)
 bool gather_ring_kernel_ok(const srmap_problem* p, const Geometry& geo, int nk, int ring);
-// ---- the problem's blur bank, for the launchers of the kernels that read a blur table ----
-inline int blur_bank_entries(int mode, int K, int C) {
-  return mode == SRMAP_BLUR_PER_FRAME ? K : mode == SRMAP_BLUR_PER_CHANNEL ? C : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? K * C : 1;
-}
-// the bank entry of (frame, channel); 0 without a bank
-inline int blur_bank_entry(int mode, int C, int k, int c) {
-  return mode == SRMAP_BLUR_PER_FRAME ? k : mode == SRMAP_BLUR_PER_CHANNEL ? c : mode == SRMAP_BLUR_PER_FRAME_CHANNEL ? k * C + c : 0;
-}
-inline BlurStride blur_stride(const srmap_problem* p) {
-  const int bb = p->geo.b * p->geo.b;
-  return {blur_bank_entry(p->blur_bank_mode, p->geo.C, 1, 0) * bb, blur_bank_entry(p->blur_bank_mode, p->geo.C, 0, 1) * bb};
-}
-// ---- the problem's motion, for the launchers of the kernels that sample it (kernels_data_direct.hip, the fits) ----
-inline MotionKind motion_kind(const srmap_problem* p) {
-  return p->lat_step ? kMotionLattice : p->flow ? kMotionFlow : p->affine ? kMotionAffine : p->has_motion ? kMotionTable : kMotionNone;
-}
-// "a displacement field" / "... on a control lattice" (srmap_problem_set_flow / _lattice): the refusals of what has no leg for
-// either name the one that is set
-inline bool field_motion(const srmap_problem* p) { return p->flow || p->lat_step != 0; }
-inline const char* field_motion_name(const srmap_problem* p) { return p->lat_step ? "a displacement field on a control lattice" : "a displacement field"; }
-inline const char* field_motion_setter(const srmap_problem* p) { return p->lat_step ? "srmap_problem_set_flow_lattice" : "srmap_problem_set_flow"; }
-template <typename T>
-MotionArgs<T> motion_args(const srmap_problem* p) {
-  return {p->has_motion ? p->d_fwd_warps.as<const WarpTaps<T>>() : nullptr, p->d_affine.as<double>(), p->d_flow.as<const T>(), p->d_flow_seed.as<int>(),
-          {p->d_lattice.as<double>(), p->lat_step, p->lat_lw, p->lat_lh}};
-}
 // The one switch from a run-time int to the template instances: f(std::integral_constant<int, V>) for the one of
 // VALUES... that `v` is -- a motion kind: the kinds the caller has kernel instances of; false (and no call) for any other,
 // which the caller answers as an internal error
@@ -381,9 +265,6 @@ bool dispatch_scale_blur(int s, int b, F&& f) {
   dispatch_value<2, 3, 4>(s, [&](auto S) { hit = dispatch_value<1, 3>(b, [&](auto B) { f(S, B); }); });
   return hit;
 }
-// Leaves the problem without a displacement field, dense or on a lattice, and without their seeds (problem.hip): what a
-// motion setter does after model_drain, before it installs its own
-void field_motion_clear(srmap_problem* p);
 // K matrices [a b tx; c d ty] -> records; SRMAP_EINVAL (not finite) / SRMAP_EUNSUPPORTED (outside the domain) (problem.hip)
 int affine_records(srmap_ctx* ctx, int K, const double* affine_2x3, std::vector<double>* recs);
 // ---- the fits' shared kernels, planning and per-pass buffers (motion_fit.hip) ----
@@ -498,7 +379,8 @@ int launch_forward_sp(srmap_problem* p, const Geometry& geo, const SpForwardPlan
                       const SpFold& fold = SpFold(), const T* dw = nullptr);
 
 // ---- a change of the model (problem.hip): every setter checks its arguments, builds the new buffers in locals (a
-// failure leaves the problem as it was), then model_drain, swap, model_replan ----
+// failure leaves the problem as it was), then model_drain, swap, model_replan -- for the motion and the blur inside their
+// owners' install (motion_model.hip, blur_model.hip) ----
 int model_drain(srmap_problem* p);    // wait for the evaluations in flight: they read the buffers about to change
 void model_replan(srmap_problem* p);  // a new plan generation, the tile plan for the model now in force and its preload
 

@@ -46,13 +46,13 @@ bool ztile_plan(srmap_problem* p) {
   p->zplan.reset();
   const Geometry& g = p->geo;
   const int S = g.s, B = g.b, K = g.K;
-  if (p->affine) return false;  // affine motion: the tiles' frame table holds translations only -- not covered
-  if (field_motion(p)) return false;  // displacement field (dense or on a lattice): likewise -- not covered
-  if (p->custom_blur) return false;  // free-form blur kernel: the tiles carry a symmetric 3 x 3 kernel's three values
+  const MotionModel& m = p->motion;
+  if (!m.is_created()) return false;  // affine motion or a displacement field: the tiles' frame table holds translations only
+  if (!p->blur.is_created()) return false;  // free-form kernel or bank: the tiles carry a symmetric 3 x 3 kernel's three values
   if (!p->maps_regular) return false;
   if (S < 2 || S > 4) return false;
   if (B != 1 && B != 3) return false;
-  if (B == 3 && !ztile_blur3_symmetric(p->blur2d.data(), p->blur1d.data())) return false;
+  if (B == 3 && !ztile_blur3_symmetric(p->blur.taps().data(), p->blur.factor())) return false;
   std::vector<int> ox(K, 0), oy(K, 0);
   int amax = 0;
   // Data weights / a Huber loss: the plan takes the forward-residual form below whatever the shifts are.  The integer-shift
@@ -61,12 +61,12 @@ bool ztile_plan(srmap_problem* p) {
   // shift is its one-tap case: the source table and the forward kernel's stencils walk ntaps taps.  Without a
   // MotionModule there are no warp records for that form (ring kernel, forward tile kernel): the direct family runs.
   const bool robust = p->dw.robust();
-  if (robust && !p->has_motion) return false;
+  if (robust && !m.has_table()) return false;
   bool subpix = robust;
-  if (p->has_motion) {
+  if (m.has_table()) {
     for (int k = 0; k < K; ++k) {
-      const WarpTaps<double>& f = p->fwd_warps[k];
-      const WarpTaps<double>& b = p->bwd_warps[k];
+      const WarpTaps<double>& f = m.fwd()[k];
+      const WarpTaps<double>& b = m.bwd()[k];
       if (f.ytab != nullptr || b.ytab != nullptr) return false;  // rounding-tie shifts: per-row tables, direct kernels
       if (f.ntaps != 1 || b.ntaps != 1) subpix = true;
       else if (b.ox != -f.ox || b.oy != -f.oy) return false;
@@ -87,7 +87,7 @@ bool ztile_plan(srmap_problem* p) {
     z->E = 0;  // no border blocks: the forward kernel counts the cost, the ring pass evaluates the border exactly
     z->Dr = amax + 2 + g.hb;
     if (!ztile_frame_fits(g.W, g.H, z->Dr, S)) return false;
-    z->st = ztile_source_table(S, K, p->bwd_warps.data(), g.hb);
+    z->st = ztile_source_table(S, K, m.bwd().data(), g.hb);
     // the only table an SP instance reads (z_row_sp2: spsrc, spn, spmax); the integer-shift frame table (cnt, off, aux) and
     // the border blocks' tables stay unset -- no border blocks with E = 0
     bool ok = upload_vector(p, z->st.srctab, &z->d_spsrc) == SRMAP_OK;
@@ -117,7 +117,7 @@ bool ztile_plan(srmap_problem* p) {
   if (ok) {
     ok = dispatch_dtype(p->dtype, [&](auto dt) {
       BorderArgs<decltype(dt)> bd{};
-      bd.hdr = z->d_hdr.as<int2>(); bd.ent = z->d_ent.as<ZEntry>(); bd.blur_d = (decltype(bd.blur_d))p->d_blur.as(); bd.corr = (decltype(bd.corr))z->d_corr.as();
+      bd.hdr = z->d_hdr.as<int2>(); bd.ent = z->d_ent.as<ZEntry>(); bd.blur_d = (decltype(bd.blur_d))p->blur.table(); bd.corr = (decltype(bd.corr))z->d_corr.as();
       bd.S = S; bd.b = B; bd.hb = g.hb; bd.n_ring = z->n_ring; bd.n_ent = (int)t.ent.size(); bd.obs_C = g.C;
       return upload_vector(p, std::vector<BorderArgs<decltype(dt)>>(1, bd), &z->d_bd) == SRMAP_OK;
     });

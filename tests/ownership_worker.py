@@ -176,6 +176,48 @@ class Run:
                                  ("weights removed", lambda: p.set_data_weights(None), 0, None)])
         self.destroy(p)
 
+    def replacement(self, tag, dtype):
+        """The motions are alternatives, and so are the blurs: a problem taken from one to another holds exactly the
+        blocks of a fresh problem given only the second (the first one's are all freed), and NULL to any setter of the
+        family gives the count before the first setter.  (No step here keeps a tile plan but the last: neither a replaced
+        motion nor a replaced blur has one.)"""
+        def held(steps):
+            """A fresh problem: the change of the count after each of `steps`, from the count before the first."""
+            p = self.problem(dtype)
+            p.eval(self.x0)
+            c0, out = self.live(), []
+            for step in steps:
+                step(p)
+                out.append(self.live() - c0)
+            self.destroy(p)
+            return out
+
+        def family(name, setters, sequences):
+            """sequences: (first, second, the setter that takes the closing NULL)."""
+            fresh = {k: held([call])[0] for k, call in setters.items()}
+            checks = []
+            for a, b, closing in sequences:
+                _, after_b, after_null = held([setters[a], setters[b], null[closing]])
+                checks.append(["%s -> %s: as a fresh problem with the second alone" % (a, b), after_b, fresh[b]])
+                checks.append(["%s -> %s -> %s(None)" % (a, b, closing), after_null, 0])
+            self.record("replacement[%s,%s]" % (name, tag), checks, fresh=fresh)
+
+        null = {"set_affine_motion": lambda p: p.set_affine_motion(None), "set_flow": lambda p: p.set_flow(None),
+                "set_flow_lattice": lambda p: p.set_flow_lattice(None, 0), "set_blur_kernel": lambda p: p.set_blur_kernel(None),
+                "set_blur_bank": lambda p: p.set_blur_bank(None)}
+        affine = np.tile(np.array([[1.0, 0, 0], [0, 1.0, 0]]), (K, 1, 1))
+        affine[1] = [[1.01, 0.02, 0.5], [-0.02, 0.99, -0.25]]
+        field = self.sr.flow_from_shifts(INT_SHIFTS, H, W)
+        nodes = np.full((K, 2, 5, 5), 0.25)  # step 16: the last node one cell beyond the 64 x 64 image
+        family("motion", {"affine": lambda p: p.set_affine_motion(affine), "flow": lambda p: p.set_flow(field),
+                          "lattice": lambda p: p.set_flow_lattice(nodes, 16)},
+               [("affine", "flow", "set_affine_motion"), ("affine", "lattice", "set_flow"), ("flow", "affine", "set_flow_lattice"),
+                ("lattice", "flow", "set_affine_motion"), ("flow", "lattice", "set_flow")])
+        taps = np.outer([0.2, 0.6, 0.2], [0.25, 0.5, 0.25])
+        bank = np.stack([taps, taps.T, taps[::-1].copy()])  # a kernel per frame
+        family("blur", {"free-form": lambda p: p.set_blur_kernel(taps), "bank": lambda p: p.set_blur_bank(bank, self.sr.BLUR_PER_FRAME)},
+               [("free-form", "bank", "set_blur_kernel"), ("bank", "free-form", "set_blur_bank")])
+
     def churn(self, tag, dtype):
         sr = self.sr
         p = self.problem(dtype)
@@ -266,6 +308,7 @@ class Run:
         for tag, dtype in DTYPES:
             self.create_eval_destroy(tag, dtype)
             self.setters(tag, dtype)
+            self.replacement(tag, dtype)
             self.churn(tag, dtype)
             self.scratch(tag, dtype)
         self.registrations()

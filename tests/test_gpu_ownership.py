@@ -1,5 +1,6 @@
 """Device-memory ownership (csrc/dev_mem.hpp): srmap_live_allocations() around create / evaluate / destroy, every model
-setter as set -> refused -> cleared, re-plan churn, and every call with scratch of its own.
+setter as set -> refused -> cleared, every motion and blur replaced by another and then cleared, re-plan churn, and
+every call with scratch of its own.
 
 The counts are read in ONE fresh child process (tests/ownership_worker.py, which lists the scenarios): in the pytest
 process they depend on when Python collects the problems of other tests.  Every test here reads the record of its
@@ -25,6 +26,7 @@ SCENARIOS = (
     ["create_eval_destroy[%s,%s]" % (k, t) for t in DT for k in ("integer", "subpixel", "rounding_tie", "direct")]
     + ["setter[%s,%s]" % (k, t) for t in DT
        for k in ("affine", "flow", "blur", "photometric", "prior_then_weights", "huber_then_prior")]
+    + ["replacement[%s,%s]" % (k, t) for t in DT for k in ("motion", "blur")]
     + ["churn[%s,%s]" % (k, t) for t in DT for k in ("regularizers", "data_loss")]
     + ["scratch[%s,%s]" % (k, t) for t in DT
        for k in ("solve_cg", "solve_lbfgs", "solve_split_channels", "cg_trace", "lbfgs_trace", "fit_blur", "fit_photometric",
