@@ -35,7 +35,7 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what);
 // channel neighbour when the problem carries halo planes).  x is this rank's [C][H][W] device buffer.
 int shard_exchange_x(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, void* x_dev, hipStream_t st);
 // The sharded evaluation without the final cost read-back: exchange, local evaluation, gradient / cost all-reduce
-// for frame shards.  The (local, or for frame shards global) cost is left in p->d_cost[0].  The local evaluation gets
+// for frame shards.  The (local, or for frame shards global) cost is left in p->d_cost[kCostValue].  The local evaluation gets
 // the caller's request plus the channel view, regulariser band or halo overlap of the shard mode.
 int shard_eval(srmap_problem* p, srmap_comm* c, const srmap_shard_desc* sd, EvalReq req, EvalOut* out, unsigned terms,
                void* x_dev, void* g_dev, hipStream_t st);

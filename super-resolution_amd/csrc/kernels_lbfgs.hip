@@ -8,7 +8,8 @@
 // from a Gram table, and the device does two streaming passes per iteration:
 //   k_lbfgs_update     s_p = x - x_k and y_p = g - g_k into ring slot p (by subtraction, as ALGLIB forms sk / yk),
 //                      and every dot product the next direction needs that involves a new vector:
-//                      [0] g.g (epsg)  [1] s_p.s_p (epsx)  then per live slot j: s_p.y_j, y_p.s_j, y_p.y_j, g.s_j, g.y_j
+//                      g.g (epsg), s_p.s_p (epsx), then per live slot j: s_p.y_j, y_p.s_j, y_p.y_j, g.s_j, g.y_j -- the rows
+//                      kLbGg, kLbSs, lb_row(j, .) of solver_mailbox.hpp
 //                      (the older pairs' entries do not change: the host keeps them)
 //   k_lbfgs_direction  dn = -(c_g g + sum_j (c_sj s_j + c_yj y_j)) and {max|dn|, dn.dn, g.dn}: the sums k_direction
 //                      leaves, in the same device and host-mapped slots, so the normalisation factors, the fold of the
@@ -85,7 +86,7 @@ template <typename T, int V, int L>
 __global__ __launch_bounds__(256) void k_lbfgs_update(const T* __restrict__ x, const T* __restrict__ xk,
                                                      const T* __restrict__ g, const T* __restrict__ gk, T* S, T* Y,
                                                      int p, size_t n, LbfgsRed red) {
-  constexpr int R = 2 + 5 * L;
+  constexpr int R = lb_rows(L);
   double acc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) acc[r] = 0.0;
@@ -106,8 +107,8 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(const T* __restrict__ x, c
     stv<T, V, true>(yp + i, y);
 #pragma unroll
     for (int q = 0; q < V; ++q) {
-      acc[0] += (double)gv[q] * (double)gv[q];
-      acc[1] += (double)s[q] * (double)s[q];
+      acc[kLbGg] += (double)gv[q] * (double)gv[q];
+      acc[kLbSs] += (double)s[q] * (double)s[q];
     }
 #pragma unroll
     for (int j = 0; j < L; ++j) {
@@ -121,11 +122,11 @@ __global__ __launch_bounds__(256) void k_lbfgs_update(const T* __restrict__ x, c
       }
 #pragma unroll
       for (int q = 0; q < V; ++q) {
-        acc[2 + 5 * j + 0] += (double)s[q] * (double)yj[q];
-        acc[2 + 5 * j + 1] += (double)y[q] * (double)sj[q];
-        acc[2 + 5 * j + 2] += (double)y[q] * (double)yj[q];
-        acc[2 + 5 * j + 3] += (double)gv[q] * (double)sj[q];
-        acc[2 + 5 * j + 4] += (double)gv[q] * (double)yj[q];
+        acc[lb_row(j, kLbSyj)] += (double)s[q] * (double)yj[q];
+        acc[lb_row(j, kLbYsj)] += (double)y[q] * (double)sj[q];
+        acc[lb_row(j, kLbYyj)] += (double)y[q] * (double)yj[q];
+        acc[lb_row(j, kLbGsj)] += (double)gv[q] * (double)sj[q];
+        acc[lb_row(j, kLbGyj)] += (double)gv[q] * (double)yj[q];
       }
     }
   }

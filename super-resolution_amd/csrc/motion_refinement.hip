@@ -109,15 +109,15 @@ __global__ __launch_bounds__(256) void k_refine_sums(const T* __restrict__ x, co
 // (H + lambda diag H) d = -g over the parameters idx[0..n) by Cholesky; the other entries of d are 0.  S: the 28 sums.
 // false: no texture
 bool lm_step(const double* S, double lambda, const int* idx, int n, double* d) {
-  double Hf[6][6], A[6][6], rhs[6], sol[6];
+  double Hf[6][6], A[6][6], ng[6], sol[6];
   for (int i = 0, q = 0; i < 6; ++i)
     for (int j = i; j < 6; ++j, ++q) Hf[i][j] = Hf[j][i] = S[q];
   for (int i = 0; i < n; ++i) {
     for (int j = 0; j < n; ++j) A[i][j] = Hf[idx[i]][idx[j]];
     A[i][i] = A[i][i] + lambda * A[i][i];
-    rhs[i] = -S[21 + idx[i]];
+    ng[i] = -S[21 + idx[i]];
   }
-  if (!cholesky_solve(A, rhs, n, sol)) return false;
+  if (!cholesky_solve(A, ng, n, sol)) return false;
   for (int i = 0; i < 6; ++i) d[i] = 0.0;
   for (int i = 0; i < n; ++i) d[idx[i]] = sol[i];
   return true;

@@ -5,20 +5,18 @@
 // single-GPU or sharded over one rank per GPU, and the single-run trace entry points.
 //
 // This file is the control flow only.  Every n-vector lives in HBM and is touched only by the passes
-// (solver_passes.hip, kernels_lbfgs.hip) and the evaluation (shard_eval.hip); DeviceCG owns the vectors, hands out the
-// arrival tags and queues the passes.  Step selection and the stopping rules run on the host, in double, in ALGLIB's
+// (solver_passes.hip, kernels_lbfgs.hip) and the evaluation (shard_eval.hip); DeviceCG owns the vectors and queues the
+// passes, its Mailbox owns the scalars the device and the host exchange (the slot map: solver_mailbox.hpp), hands out the
+// arrival tags and waits on them.  Step selection and the stopping rules run on the host, in double, in ALGLIB's
 // order of operations (solver_host.hpp: the More'-Thuente step, the L-BFGS recursion on coefficients), so that the
 // trajectory follows the reference's up to reduction order.  Per CG iteration the host waits for the device 2 + nfev
 // times: once for the direction's sums, once per trial point for (f, g.d), once for the beta dot products.
 //
-// Sharding.  The passes reduce over the elements a rank OWNS and DeviceCG all-reduces the sums through the
+// Sharding.  The passes reduce over the elements a rank OWNS and the Mailbox all-reduces the sums through the
 // communicator (sum, and max for the max-norm), so every rank takes the same decisions; x halos are refreshed before
 // every evaluation (comm.hpp).
-#include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -29,18 +27,174 @@
 
 namespace srmap {
 
+static_assert(kHsPubF - kHsPass == kCostValue && kHsPubGd - kHsPass == kCostGd, "a published {f, g.d} pair is d_cost's head");
+
+// GRID: the unknowns of a channel block are replicated over its frame groups; group 0 counts them in the reductions
+static bool grid_replica(const srmap_comm* comm, const srmap_shard_desc* shard) {
+  return shard_mode(comm, shard) == SRMAP_SHARD_GRID && shard->frame_groups > 1 && (comm_rank(comm) % shard->frame_groups) != 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------
+// The host's one owner of the scalar protocol of solver_mailbox.hpp (the table there: who writes which word under which
+// tag).  One-launch scheme (fused(): the sums need no all-reduce): a pass's last workgroup publishes (struct Fin).
+// Two-launch scheme: finish / finish_dir reduce the block partials, all-reduce and publish.
+struct Mailbox {
+  srmap_problem* p = nullptr;
+  hipStream_t st = nullptr;
+  srmap_comm* comm = nullptr;          // the scalar all-reduces of the two-launch scheme
+  bool reduce_scalars = false;         // row / channel shards: the owned-element sums are all-reduced
+  double* hs = nullptr;                // ctx->h_scal, host-mapped [kHsSlots]
+  double* dscal = nullptr;             // device scalars [kDsSlots]
+  double* part = nullptr;              // [3][kRedBlocks] block partials (two-launch scheme)
+  unsigned long long* gran = nullptr;  // [3][kRedBlocks] granules of the one-launch reductions (armed)
+  DevBuf dscal_mem, part_mem, gran_mem;
+  double tag = 0, dir_tag = 0;         // the last tag handed to a publishing kernel; the last direction pass's
+  double wait_seconds = 0;             // host time spent in wait_tag
+  int waits = 0;
+
+  bool fused() const { return !reduce_scalars; }
+  double next_tag() { return tag += 1.0; }
+  const double* cost() const { return p->d_cost.as<double>(); }
+
+  int alloc() {
+    constexpr size_t kGranules = 3 * (size_t)kRedBlocks, kArmWords = sizeof(*gran) / sizeof(kArm32);
+    SRMAP_HIP(p->ctx, part_mem.alloc(sizeof(*part) * 3 * kRedBlocks));
+    SRMAP_HIP(p->ctx, dscal_mem.alloc(sizeof(*dscal) * kDsSlots));
+    SRMAP_HIP(p->ctx, gran_mem.alloc(sizeof(*gran) * kGranules));
+    part = part_mem.as<double>(); dscal = dscal_mem.as<double>(); gran = gran_mem.as<unsigned long long>();
+    SRMAP_HIP(p->ctx, hipMemsetAsync(dscal, 0, sizeof(*dscal) * kDsSlots, st));
+    SRMAP_HIP(p->ctx, hipMemsetD32Async((hipDeviceptr_t)gran, (int)kArm32, kGranules * kArmWords, st));
+    if (int rc = ensure_staging(p->ctx)) return rc;
+    hs = p->ctx->h_scal.as<double>();
+    return SRMAP_OK;
+  }
+  // behind alloc and a stream synchronisation: this solve's time-out word (Fin::timeout_host, ZArgs::to_host) starts clear,
+  // its tags go on from the context's last -- they keep increasing across solves, so a stale word can never match
+  void open() { hs[kHsTimeout] = 0.0; tag = hs[kHsTag]; }
+
+  // Wait until the kernel that was given tag `want` (default: the last one handed out) has published its results:
+  // poll_tag on the host-mapped words, and after ~2 s a stream synchronisation (also surfaces asynchronous errors).
+  int wait_tag(double want = -1.0) {
+    if (want < 0) want = tag;
+    const volatile double* slot = hs + kHsTag;
+    using Clock = std::chrono::steady_clock;
+    struct Acc { Mailbox* c; Clock::time_point t; ~Acc() {
+      c->wait_seconds += std::chrono::duration<double>(Clock::now() - t).count(); c->waits++; } } acc{this, Clock::now()};
+    switch (poll_tag(slot, hs + kHsTimeout, want, 2.0)) {
+      case Arrival::kArrived: break;
+      case Arrival::kDeviceTimeout:  // its sums are NaN, its granules not re-armed
+        return set_error(p->ctx, SRMAP_EHIP, "solver: a device-side reduction timed out waiting for a workgroup");
+      case Arrival::kExpired:
+        SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
+        if (!tag_arrived(slot, want)) return set_error(p->ctx, SRMAP_EHIP, "solver: device results did not arrive");
+    }
+    return SRMAP_OK;
+  }
+  // the sums of the last direction pass on the host: {max|dn|, dn.dn, g.dn}
+  int wait_dir(double* mx, double* ss, double* gdn) {
+    const int rc = wait_tag(dir_tag);
+    if (rc) return rc;
+    *mx = hs[kHsDir + kDirMax]; *ss = hs[kHsDir + kDirSs]; *gdn = hs[kHsDir + kDirGdn];
+    return SRMAP_OK;
+  }
+
+  // Where the pass about to be launched leaves its sums.  One-launch scheme: under the next tag, in h_scal's pass words
+  // (+ the cost behind them) or, a direction pass (dir), in dscal's direction words under dir_tag, f published beside them
+  // (publish_f).  Two-launch scheme: empty -- block partials; finish / finish_dir follows.
+  Fin fin(bool with_cost, bool dir = false, bool publish_f = false) {
+    Fin f{};
+    if (!fused()) return f;
+    f.gran = gran; f.out = dir ? dscal + kDsDir : hs + kHsPass; f.cost_src = with_cost ? cost() : nullptr;
+    if (publish_f) { f.pub_src = cost() + kCostValue; f.pub_dst = hs + kHsPubF; f.pub_n = 1; }
+    f.timeout_flag = dscal + kDsTimeout; f.timeout_host = hs + kHsTimeout;
+    f.tag_slot = hs + kHsTag; f.tag = next_tag();
+    if (dir) dir_tag = tag;
+    return f;
+  }
+  // What an evaluation's finish kernel may publish itself: {f, g.d} (with_gd, and no scalar all-reduce) and the next
+  // tag.  The tag is taken (next_tag) only when the evaluation reports that it published.
+  EvalReq::Publish offer(bool with_gd) const {
+    return {(fused() && with_gd) ? hs + kHsPubF : nullptr, hs + kHsTag, tag + 1.0, hs + kHsTimeout};
+  }
+  // Behind a reducing pass of nb workgroups, what brings its `rows` sums (+ the cost behind them) to h_scal's pass words.
+  // One-launch scheme: nothing, the pass does.  Two-launch scheme: k_finish over the partial rows, the all-reduce, the
+  // publish under the next tag; with_dir: the direction's sums (already reduced in dscal) ride along under that tag.
+  int queue_finish(int nb, int rows, bool with_cost, bool with_dir = false) {
+    const int cnt = rows + (with_cost ? 1 : 0);
+    if (!fused()) {
+      next_tag();
+      launch_finish(part, nb, rows, 0, dscal + kDsPass, with_cost ? cost() : nullptr, nullptr, 0.0, st);
+      if (int rc = comm_allreduce(comm, dscal + kDsPass, (size_t)cnt, SRMAP_F64, 0, st)) return rc;
+      if (with_dir) launch_publish(hs + kHsDir, dscal + kDsDir, kDirWords, hs + kHsSideTag, 0.0, st);
+      launch_publish(hs + kHsPass, dscal + kDsPass, cnt, hs + kHsTag, tag, st);
+      if (with_dir) dir_tag = tag;
+    }
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return SRMAP_OK;
+  }
+  // queue_finish, one wait, and the sums on the host: out[0..rows) (+ out[rows] = cost)
+  int finish(int nb, int rows, bool with_cost, double* out, bool with_dir = false) {
+    int rc = queue_finish(nb, rows, with_cost, with_dir);
+    if (rc == SRMAP_OK) rc = wait_tag();
+    if (rc) return rc;
+    for (int i = 0; i < rows + (with_cost ? 1 : 0); ++i) out[i] = hs[kHsPass + i];
+    return SRMAP_OK;
+  }
+  // Two-launch scheme, behind a direction pass: its three partial rows -> dscal's direction words, all-reduced;
+  // publish: to the host under a tag of their own (else the caller's finish(with_dir) carries them)
+  int finish_dir(int nb, bool publish) {
+    double* d = dscal + kDsDir;
+    launch_finish(part, nb, kDirWords, 1, d, nullptr, nullptr, 0.0, st);
+    int rc = comm_allreduce(comm, d + kDirMax, 1, SRMAP_F64, 1, st);
+    if (rc) return rc;
+    rc = comm_allreduce(comm, d + kDirSs, 2, SRMAP_F64, 0, st);
+    if (rc) return rc;
+    if (publish) {
+      dir_tag = next_tag();
+      launch_publish(hs + kHsDir, d, kDirWords, hs + kHsTag, tag, st);
+    }
+    return SRMAP_OK;
+  }
+  // The {f, g.d} an evaluation left in d_cost, to the host under the next tag (all-reduced first where sums are)
+  int publish_f_gd() {
+    next_tag();
+    const double* src = cost();
+    if (reduce_scalars) {
+      SRMAP_HIP(p->ctx, hipMemcpyAsync(dscal + kDsPass, src, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+      int rc = comm_allreduce(comm, dscal + kDsPass, 2, SRMAP_F64, 0, st);
+      if (rc) return rc;
+      src = dscal + kDsPass;
+    }
+    launch_publish(hs + kHsPubF, src, 2, hs + kHsTag, tag, st);
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return SRMAP_OK;
+  }
+  // End of a solve or trace: a reduction that gave up waiting for a workgroup (the tile kernel's in-kernel finish:
+  // sticky word d_cost[kCostTimeout]; a CG pass: dscal[kDsTimeout]) left NaN sums behind -- the stopping rules ended the
+  // run -- and its granules un-re-armed.  wait_tag ends the run on hs[kHsTimeout], which both kinds of finisher raise:
+  // look now, re-initialise, report.  No device copy on success.
+  int recover_timeout(int rc) {
+    (void)hipStreamSynchronize(st);
+    if (hs == nullptr || hs[kHsTimeout] == 0.0) return rc;
+    const int rr = recover_reduction_timeout(p, hs + kHsTimeout);
+    if (rc != SRMAP_OK) return rc;
+    return rr ? rr : set_error(p->ctx, SRMAP_EHIP, "a device-side reduction timed out waiting for a workgroup during the solve (device fault or a wedged queue)");
+  }
+};
+
+// What both runs need of the direction's sums at the opening of an iteration (DeviceCG::begin_step)
+struct StepNorms { double dginit, dd, gdn, s1, s2; };
+
 template <typename T>
 struct DeviceCG {
-  srmap_problem* p;
-  hipStream_t st;
-  size_t n;
-  srmap_comm* comm = nullptr;
+  srmap_problem* p = nullptr;
+  hipStream_t st = nullptr;
+  size_t n = 0;
   const srmap_shard_desc* shard = nullptr;
+  Mailbox mb;
   Owned ow{};
-  bool reduce_scalars = false;  // row / channel shards: the owned-element sums are all-reduced
   EvalReq::View view;           // channel view of every evaluation (split_channels)
-  bool gd_valid = false;        // the last evaluation left g.d in d_cost[1]
+  bool gd_valid = false;        // the last evaluation left g.d in d_cost[kCostGd]
   bool published = false;       // the last evaluation's finish kernel published {f, g.d} + tag (fetch_f_gd just waits)
   // chained passes (run_cg): launches whose inputs are already on the device are queued without waiting for the host.
   // srmap_irls_options::host_paced_passes turns this off (every pass then waits for the host's answer, as up to
@@ -48,28 +202,23 @@ struct DeviceCG {
   // applies to un-sharded solves only: under frame sharding a speculative first-trial evaluation would queue a
   // gradient + cost all-reduce that every rank has to match before the host has decided to keep it.
   bool chain_enabled = true;
-  bool chained() const { return fused() && chain_enabled && (shard == nullptr || comm == nullptr); }
-  // x, g: current point and gradient; xk/dk: accepted point and direction; dn: next direction;
-  // d: normalised direction (stored only where evaluations read it from memory: !foldable); gp: the gradient at xk
-  // while the line search writes its trial gradients to g (the two
-  // buffers swap; mincg's yk = g_{k+1} - g_k is formed on the fly).  The line-search base is xk itself.
+  bool chained() const { return mb.fused() && chain_enabled && (shard == nullptr || mb.comm == nullptr); }
+  // the line search may hand its trial point to the evaluation as (xk, stp): un-sharded solves on the tile kernel's
+  // g.d instance (ztile_can_fold); decided once per run (begin_run).  fold_enabled: srmap_irls_options::host_paced_passes
+  // also forms every trial point by its own pass (the A/B of the fold)
+  bool foldable = false, fold_enabled = true;
+  // x, g: current point and gradient; xk/dk: accepted point and direction; dn: next direction; d: normalised direction
+  // (stored only where evaluations read it from memory: !foldable); gp: the gradient at xk while the line search writes its
+  // trial gradients to g (the two buffers swap; mincg's yk = g_{k+1} - g_k is formed on the fly).  The line-search base is xk.
   T *x = nullptr, *g = nullptr, *xk = nullptr, *dk = nullptr, *dn = nullptr, *d = nullptr, *gp = nullptr;
-  double* part = nullptr;   // [3][kRedBlocks] block partials (two-launch reductions: sharded solves)
-  unsigned long long* gran = nullptr;  // [3][kRedBlocks] granules of the one-launch reductions (armed)
-  double* dscal = nullptr;  // device scalars: [0..3] reduction results, [4..6] the direction's sums {max|dn|, dn.dn, g.dn}, [8] beta, [15] time-out flag
-  double* hs = nullptr;     // host-mapped pinned scalars (ctx->h_scal): pass results [0..3], the direction's sums [8..10], arrival tag [15]
-  double tag = 0;           // last tag handed to a publishing kernel
   int evaluations = 0;
-  double wait_seconds = 0;  // host time spent in wait_tag
-  int waits = 0;
   // L-BFGS (run_lbfgs, kernels_lbfgs.hip): ring of lb_m pairs S[j] = s_j, Y[j] = y_j ([lb_m][n] each), the passes'
-  // workgroup partials and ticket, and the update pass's sums (host-mapped: they are not ctx->h_scal's 16 slots)
+  // workgroup partials and ticket, and the update pass's kLbRows sums (host-mapped, a buffer of their own)
   int lb_m = 0;
   T *S = nullptr, *Y = nullptr;
   double* lb_part = nullptr;
   unsigned* lb_ticket = nullptr;
   double* lb_host = nullptr;
-  static constexpr int kLbRows = 2 + 5 * kLbfgsMaxM;
   // the owners of every device buffer above (the typed members are views: the passes swap them); freed with the solver
   std::vector<DevBuf> mem;
   PinnedBuf lb_host_mem;
@@ -81,52 +230,35 @@ struct DeviceCG {
     return SRMAP_OK;
   }
 
-  // Wait until the kernel that was given tag `want` (default: the last one handed out) has published its results (see
-  // k_finish): poll the host-mapped word, fall back to a stream synchronisation after ~2 s (also surfaces asynchronous
-  // errors).  Tags only grow and the publishing kernels of one stream finish in order, so "arrived" is slot >= want:
-  // a later kernel queued behind the awaited one (chained passes, run_cg) may already have stored its own tag.
-  int wait_tag(double want = -1.0) {
-    if (want < 0) want = tag;
-    volatile double* slot = hs + 15;
-    const auto t0 = std::chrono::steady_clock::now();
-    struct Acc { DeviceCG* c; std::chrono::steady_clock::time_point t; ~Acc() {
-      c->wait_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); c->waits++; } } acc{this, t0};
-    unsigned spins = 0;
-    volatile double* to = hs + 13;   // a device-side reduction of this solve timed out: its sums are NaN, its granules not re-armed
-    while (!(*slot >= want)) {
-      if (*to != 0.0) return set_error(p->ctx, SRMAP_EHIP, "solver: a device-side reduction timed out waiting for a workgroup");
-      if ((++spins & 0x3ff) == 0 &&
-          std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
-        SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-        if (!(*slot >= want)) return set_error(p->ctx, SRMAP_EHIP, "solver: device results did not arrive");
-        break;
-      }
-    }
-    return SRMAP_OK;
-  }
-
   int nb() const { size_t b = (n + 255) / 256; return (int)(b < (size_t)kRedBlocks ? b : kRedBlocks); }
 
-  int alloc() {
+  // The solver of problem p_ over n_ unknowns, this rank's shard of them: the owned elements, the reduction scheme, every
+  // buffer (lbfgs_m > 0: the ring too).  opt == nullptr (the traces): chained and folded.
+  int init(srmap_problem* p_, srmap_comm* comm, const srmap_shard_desc* shard_, size_t n_, const srmap_irls_options* opt,
+           int lbfgs_m) {
+    p = p_; st = p->ctx->stream; n = n_; shard = shard_;
+    mb.p = p; mb.st = st; mb.comm = comm;
+    if (opt) chain_enabled = fold_enabled = opt->host_paced_passes == 0;
+    const Geometry& geo = p->geo;
+    const size_t N = (size_t)geo.W * geo.H;
+    const int mode = shard_mode(comm, shard);
+    ow.on = 0; ow.e0 = 0; ow.e1 = n; ow.W = geo.W; ow.H = geo.H; ow.r0 = 0; ow.r1 = geo.H;
+    if (mode == SRMAP_SHARD_ROWS) { ow.on = 1; ow.r0 = shard->own_row0; ow.r1 = shard->own_row1; }
+    if (mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
+      ow.on = 1; ow.e0 = (size_t)shard->own_ch0 * N; ow.e1 = grid_replica(comm, shard) ? ow.e0 : (size_t)shard->own_ch1 * N;
+    }
+    mb.reduce_scalars = ow.on != 0;
     T** v[] = {&x, &g, &xk, &dk, &dn, &d, &gp};
     for (T** q : v)
       if (int rc = dev_alloc(q, n * sizeof(T))) return rc;
-    if (int rc = dev_alloc(&part, sizeof(double) * 3 * kRedBlocks)) return rc;
-    if (int rc = dev_alloc(&dscal, sizeof(double) * 16)) return rc;
-    SRMAP_HIP(p->ctx, hipMemsetAsync(dscal, 0, sizeof(double) * 16, st));
-    if (int rc = dev_alloc(&gran, sizeof(double) * 3 * kRedBlocks)) return rc;
-    SRMAP_HIP(p->ctx, hipMemsetD32Async((hipDeviceptr_t)gran, (int)kArm32, 2 * 3 * kRedBlocks, st));
+    if (int rc = mb.alloc()) return rc;
     // sharded evaluations write only the owned part of g: the vector kernels run over all n elements, so everything
     // they combine starts defined (the halo values never enter a reduction, and x halos are re-exchanged)
     T* z[] = {g, dn, d, dk, gp};
     for (T* q : z) SRMAP_HIP(p->ctx, hipMemsetAsync(q, 0, n * sizeof(T), st));
-    int rc = ensure_staging(p->ctx);
-    if (rc) return rc;
-    hs = p->ctx->h_scal.as<double>();
     SRMAP_HIP(p->ctx, hipStreamSynchronize(st));
-    hs[13] = 0.0;  // time-out word of this solve (Fin::timeout_host, ZArgs::to_host)
-    tag = hs[15];  // tags keep increasing across solves of one context: a stale word can never match
-    return SRMAP_OK;
+    mb.open();
+    return lbfgs_m > 0 ? alloc_lbfgs(lbfgs_m) : SRMAP_OK;
   }
   int alloc_lbfgs(int m) {
     lb_m = m;
@@ -147,70 +279,24 @@ struct DeviceCG {
     SRMAP_HIP(p->ctx, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
     return SRMAP_OK;
   }
-  // One-launch reductions (struct Fin) whenever the sums need no all-reduce.
-  bool fused() const { return !reduce_scalars; }
-  // the pass about to be launched reduces to the host: out = hs[0 .. rows) (+ the cost at hs[rows]), then the tag
-  Fin fin_host(bool with_cost, const double* pub_src = nullptr, double* pub_dst = nullptr, int pub_n = 0,
-               double* out = nullptr) {
-    Fin f{};
-    if (fused()) {
-      tag += 1.0;
-      f.gran = gran; f.out = out ? out : hs; f.cost_src = with_cost ? (const double*)p->d_cost.as<double>() : nullptr;
-      f.timeout_flag = dscal + 15; f.timeout_host = hs + 13;
-      f.pub_src = pub_src; f.pub_dst = pub_dst; f.pub_n = pub_n;
-      f.tag_slot = hs + 15; f.tag = tag;
-    }
-    return f;
-  }
-  // Bring the sums of the pass just launched to the host: out[0..rows) (+ out[rows] = cost).  One wait.  Two-launch
-  // scheme: reduces the `rows` partial rows here (k_finish), all-reduces them, publishes.
-  int finish(int rows, bool max0, bool with_cost, double* out, int extra_n = 0) {
-    const int cnt = rows + (with_cost ? 1 : 0);
-    if (!fused()) {
-      tag += 1.0;
-      launch_finish(part, nb(), rows, max0 ? 1 : 0, dscal, with_cost ? (const double*)p->d_cost.as<double>() : nullptr, nullptr, 0.0, st);
-      int rc = SRMAP_OK;
-      if (max0) {
-        rc = comm_allreduce(comm, dscal, 1, SRMAP_F64, 1, st);
-        if (rc) return rc;
-        if (cnt > 1) rc = comm_allreduce(comm, dscal + 1, (size_t)cnt - 1, SRMAP_F64, 0, st);
-      } else {
-        rc = comm_allreduce(comm, dscal, (size_t)cnt, SRMAP_F64, 0, st);
-      }
-      if (rc) return rc;
-      if (extra_n > 0)
-        launch_publish(hs + 8, dscal + 4, extra_n, hs + 14, 0.0, st);
-      launch_publish(hs, dscal, cnt, hs + 15, tag, st);
-    }
-    SRMAP_HIP(p->ctx, hipGetLastError());
-    int rc = wait_tag();
-    if (rc) return rc;
-    for (int i = 0; i < cnt; ++i) out[i] = hs[i];
-    return SRMAP_OK;
-  }
-  // objective at x: g <- gradient; the cost stays on the device (finish(with_cost) fetches it).  With a direction
-  // the tile kernel may produce g.d in the same pass (gd_valid; not under frame sharding, where the local
-  // gradient is only a partial sum).
-  // the line search may hand its trial point to the evaluation as (xk, stp): un-sharded solves on the tile kernel's
-  // g.d instance (ztile_can_fold); decided once per CG run
-  bool foldable = false;
-  bool fold_enabled = true;   // srmap_irls_options::host_paced_passes also forms every trial point by its own pass (the A/B of the fold)
+  // objective at x: g <- gradient; the cost stays on the device (Mailbox::finish(with_cost) fetches it).  With a direction
+  // the tile kernel may produce g.d in the same pass (gd_valid; not under frame sharding: the local gradient is a partial sum).
   int evaluate(const T* dir = nullptr, T* at = nullptr, const T* fold_xk = nullptr, double fold_stp = 0.0) {  // at: the point (default x)
     evaluations++;
-    const int mode = shard_mode(comm, shard);
+    const int mode = shard_mode(mb.comm, shard);
     EvalReq req;
     req.view = view;
     req.dvec = (mode == SRMAP_SHARD_FRAMES || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) ? nullptr : dir;
     // without a scalar all-reduce the evaluation's finish kernel can publish {f, g.d} and the arrival tag itself
-    req.pub = {(!reduce_scalars && req.dvec != nullptr) ? hs : nullptr, hs + 15, tag + 1.0, hs + 13};
+    req.pub = mb.offer(req.dvec != nullptr);
     // fold: `dir` is the UNNORMALISED direction dk; the kernel scales it by the factors it derives from the norms the
-    // direction pass left at dscal[4..5] (norm_factors / norm_elem: the bits of the stored d)
-    if (fold_xk != nullptr && req.dvec != nullptr) req.fold = {fold_xk, req.dvec, fold_stp, (const double*)(dscal + 4)};
+    // direction pass left in dscal's direction words (norm_factors / norm_elem: the bits of the stored d)
+    if (fold_xk != nullptr && req.dvec != nullptr) req.fold = {fold_xk, req.dvec, fold_stp, (const double*)(mb.dscal + kDsDir)};
     EvalOut out;
-    const int rc = shard_eval(p, comm, shard, req, &out, SRMAP_TERM_ALL, at ? at : x, g, st);
+    const int rc = shard_eval(p, mb.comm, shard, req, &out, SRMAP_TERM_ALL, at ? at : x, g, st);
     gd_valid = out.gd_valid;
     published = out.published;
-    if (published) tag += 1.0;
+    if (published) mb.next_tag();
     return rc;
   }
   // The evaluation queued ahead of the host's decision (run_cg: the first trial point behind the normalisation pass)
@@ -220,110 +306,58 @@ struct DeviceCG {
     evaluations--;
     published = false;
   }
-  // End of a solve or trace: a reduction that gave up waiting for a workgroup (the tile kernel's in-kernel finish:
-  // sticky word d_cost[6]; a CG pass: dscal[15]) left NaN sums behind -- the stopping rules ended the run -- and its
-  // granules un-re-armed.  The evaluations of a run never look at the word (wait_tag ends the run on the host-mapped
-  // word hs[13], which both kinds of finisher raise): look now, re-initialise, report.  No device copy on success.
-  int recover_timeout(int rc) {
-    (void)hipStreamSynchronize(st);
-    if (hs == nullptr || hs[13] == 0.0) return rc;
-    const int rr = recover_reduction_timeout(p, hs + 13);
-    if (rc != SRMAP_OK) return rc;
-    return rr ? rr : set_error(p->ctx, SRMAP_EHIP, "a device-side reduction timed out waiting for a workgroup during the solve (device fault or a wedged queue)");
-  }
   // f and g.d of the evaluation just made, with one wait: out[0] = g.d, out[1] = f
   int fetch_f_gd(double* out) {
-    if (!gd_valid) {
-      launch_cg_dot<T>(g, d, n, ow, part, fin_host(true), nb(), st);
-      return finish(1, false, true, out);
-    }
-    if (published) {  // the evaluation's own finish kernel carries the tag
-      published = false;
-      const int rcw = wait_tag();
-      if (rcw) return rcw;
-      out[0] = hs[1];
-      out[1] = hs[0];
-      return SRMAP_OK;
-    }
-    tag += 1.0;
-    if (!reduce_scalars) {
-      launch_publish(hs, p->d_cost.as<double>(), 2, hs + 15, tag, st);
+    int i_gd = kHsPubGd, i_f = kHsPubF, rc = SRMAP_OK;
+    if (!gd_valid) {  // g.d by a pass of its own: its one row, the cost forwarded behind it
+      launch_cg_dot<T>(g, d, n, ow, mb.part, mb.fin(true), nb(), st);
+      rc = mb.queue_finish(nb(), 1, true);
+      i_gd = kHsPass; i_f = kHsPass + 1;
+    } else if (published) {
+      published = false;  // the evaluation's own finish kernel carries the tag
     } else {
-      SRMAP_HIP(p->ctx, hipMemcpyAsync(dscal, p->d_cost.as<double>(), 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-      int rc = comm_allreduce(comm, dscal, 2, SRMAP_F64, 0, st);
-      if (rc) return rc;
-      launch_publish(hs, dscal, 2, hs + 15, tag, st);
+      rc = mb.publish_f_gd();
     }
-    SRMAP_HIP(p->ctx, hipGetLastError());
-    int rc = wait_tag();
+    if (rc == SRMAP_OK) rc = mb.wait_tag();
     if (rc) return rc;
-    out[0] = hs[1];
-    out[1] = hs[0];
+    out[0] = mb.hs[i_gd];
+    out[1] = mb.hs[i_f];
     return SRMAP_OK;
   }
-  // dn = -g + beta dk (dk may be null); {max|dn|, dn.dn, g.dn} -> dscal[4..6] (device, all-reduced) and, under a tag of
-  // the pass's own (dir_tag: wait_dir), hs[8..10].  publish_cost: the first pass of a CG run also hands f to the host
-  // (one-launch scheme: hs[0] with the same tag; two-launch scheme: the caller's finish(0, ..., 3) publishes all four).
+  // dn = -g + beta dk (dk may be null); {max|dn|, dn.dn, g.dn} -> dscal's direction words (device, all-reduced) and, under
+  // dir_tag (Mailbox::wait_dir), h_scal's.  publish_cost: the first pass of a run also hands f to the host (one-launch
+  // scheme: with the same tag; two-launch scheme: the caller's finish(with_dir) publishes all four).
   // beta_dev: beta comes from the device scalar the k_beta_dots queued just before left there (one-launch scheme only)
-  double dir_tag = 0;
   int direction(const T* dk_or_null, double beta, bool publish_cost = false, const double* beta_dev = nullptr) {
-    Fin f{};
-    if (fused()) {
-      tag += 1.0;
-      dir_tag = tag;
-      f.gran = gran; f.out = dscal + 4; f.timeout_flag = dscal + 15; f.timeout_host = hs + 13;
-      if (publish_cost) { f.pub_src = (const double*)p->d_cost.as<double>(); f.pub_dst = hs; f.pub_n = 1; }  // hs[0] = f
-      f.tag_slot = hs + 15; f.tag = tag;
-    }
-    double* npub = fused() ? hs + 8 : (double*)nullptr;
-    const int keep = foldable ? 1 : 0;
-    launch_cg_direction<T>(dn, g, dk_or_null, (T)beta, n, ow, part, f, beta_dev, npub, keep, nb(), st);
-    if (!fused()) {
-      launch_finish(part, nb(), 3, 1, dscal + 4, nullptr, nullptr, 0.0, st);
-      int rc = comm_allreduce(comm, dscal + 4, 1, SRMAP_F64, 1, st);
-      if (rc) return rc;
-      rc = comm_allreduce(comm, dscal + 5, 2, SRMAP_F64, 0, st);
-      if (rc) return rc;
-      if (!publish_cost) {
-        tag += 1.0;
-        dir_tag = tag;
-        launch_publish(hs + 8, dscal + 4, 3, hs + 15, tag, st);
-      }
-    }
+    const Fin f = mb.fin(false, true, publish_cost);
+    double* npub = mb.fused() ? mb.hs + kHsDir : (double*)nullptr;
+    launch_cg_direction<T>(dn, g, dk_or_null, (T)beta, n, ow, mb.part, f, beta_dev, npub, foldable ? 1 : 0, nb(), st);
+    if (!mb.fused())
+      if (int rc = mb.finish_dir(nb(), !publish_cost)) return rc;
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
   // L-BFGS: ring slot p <- (x - xk, g - gk) and the Gram rows of the new pair (launch_lbfgs_update) -> lb_host, one wait
   int lbfgs_update(const T* gk, int p_slot, int live) {
-    tag += 1.0;
-    const LbfgsRed red{lb_part, lb_ticket, nullptr, lb_host, hs + 15, tag};
+    const LbfgsRed red{lb_part, lb_ticket, nullptr, lb_host, mb.hs + kHsTag, mb.next_tag()};
     int rc = launch_lbfgs_update<T>(x, xk, g, gk, S, Y, p_slot, live, n, nb(), red, st);
     if (rc) return set_error(p->ctx, rc, "lbfgs: bad history length");
     SRMAP_HIP(p->ctx, hipGetLastError());
-    return wait_tag();
+    return mb.wait_tag();
   }
-  // L-BFGS: dn from the coefficients over {g, S[0..live), Y[0..live)}; its sums where `direction` leaves them
-  // (dscal[4..6], hs[8..10] under dir_tag)
+  // L-BFGS: dn from the coefficients over {g, S[0..live), Y[0..live)}; its sums where `direction` leaves them, under dir_tag
   int lbfgs_direction(const LbfgsCoef& c, int live) {
-    tag += 1.0;
-    dir_tag = tag;
-    const LbfgsRed red{lb_part, lb_ticket, dscal + 4, hs + 8, hs + 15, tag};
+    mb.dir_tag = mb.next_tag();
+    const LbfgsRed red{lb_part, lb_ticket, mb.dscal + kDsDir, mb.hs + kHsDir, mb.hs + kHsTag, mb.tag};
     int rc = launch_lbfgs_direction<T>(dn, g, S, Y, live, c, n, nb(), foldable ? 1 : 0, red, st);
     if (rc) return set_error(p->ctx, rc, "lbfgs: bad history length");
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
-  // the sums of the last direction pass on the host: {max|dn|, dn.dn, g.dn}
-  int wait_dir(double* mx, double* ss, double* gdn) {
-    const int rc = wait_tag(dir_tag);
-    if (rc) return rc;
-    *mx = hs[8]; *ss = hs[9]; *gdn = hs[10];
-    return SRMAP_OK;
-  }
   // d = dk s1 s2 stored as a vector (+ the first trial point x = xk + stp1 d when stp1 != 0): the paths whose evaluations
   // read the normalised direction from memory
   int normalize(double stp1) {
-    launch_cg_normalize<T>(d, dk, dscal + 4, n, xk, stp1 != 0.0 ? x : (T*)nullptr, (T)stp1, nb(), st);
+    launch_cg_normalize<T>(d, dk, mb.dscal + kDsDir, n, xk, stp1 != 0.0 ? x : (T*)nullptr, (T)stp1, nb(), st);
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
@@ -333,28 +367,37 @@ struct DeviceCG {
     // the start point becomes the base point xk by exchanging the two buffers (no copy); x is trial scratch from here on:
     // every path of a run writes it before reading it (the trial points) or copies xk back into it (the early exits)
     std::swap(xk, x);
-    foldable = shard_mode(comm, shard) == SRMAP_SHARD_NONE && fold_enabled && ztile_can_fold(p, view.C > 0 ? view.C : p->geo.C);
+    foldable = shard_mode(mb.comm, shard) == SRMAP_SHARD_NONE && fold_enabled && ztile_can_fold(p, view.C > 0 ? view.C : p->geo.C);
     int rc = evaluate(nullptr, xk);
     if (rc) return rc;
     // dk = -g (written as dn, swapped below), norms of dk
     rc = direction(nullptr, 0.0, true);
     if (rc) return rc;
-    if (fused()) {  // the direction pass published {f -> hs[0]; max|dk|, dk.dk, g.dk -> hs[8..10]} itself
-      rc = wait_tag();
+    if (mb.fused()) {  // the direction pass published f and {max|dk|, dk.dk, g.dk} itself
+      rc = mb.wait_tag();
       if (rc) return rc;
-      *f = hs[0];
-    } else {
-      // fetch f and the direction's sums (already reduced on the device) with one wait
-      double h[1];
-      rc = finish(0, false, true, h, 3);
+      *f = mb.hs[kHsPubF];
+    } else {  // fetch f and the direction's sums (already reduced on the device) with one wait
+      rc = mb.finish(nb(), 0, true, f, true);
       if (rc) return rc;
-      dir_tag = tag;
-      *f = h[0];
     }
-    *gg = hs[9];  // g.g = dk.dk
+    *gg = mb.hs[kHsDir + kDirSs];  // g.g = dk.dk
     if (trace) trace->push_back(*f);
     std::swap(dk, dn);
     *small_g = std::sqrt(*gg) <= epsg;
+    return SRMAP_OK;
+  }
+  // The opening of an iteration, behind the pass that stores d where one is needed (normalize): wait for the direction's
+  // sums; linminnormalized's factors (cg_norm.hpp), g.d and d.d of the normalised direction; *stp rescaled as mincg /
+  // minlbfgs rescale it.
+  int begin_step(double* stp, StepNorms* o) {
+    double mx = 0, ss = 0;
+    const int rc = mb.wait_dir(&mx, &ss, &o->gdn);
+    if (rc) return rc;
+    norm_factors(mx, ss, o->s1, o->s2);
+    o->dginit = (o->gdn * o->s1) * o->s2;
+    o->dd = ((ss * o->s1) * o->s1) * (o->s2 * o->s2);
+    if (mx != 0) { *stp = *stp / o->s1; *stp = *stp / o->s2; }
     return SRMAP_OK;
   }
 };
@@ -467,6 +510,7 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
   const int rscountdownlen = 10;
   if (epsg == 0 && epsf == 0 && epsx == 0 && maxits == 0) epsx = 1.0E-6;
   const size_t n = cg.n;
+  Mailbox& mb = cg.mb;
   CgResult res;
   double f = 0, gg = 0;
   bool small_g = false;
@@ -481,44 +525,35 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
     // d = dk s1 s2 (linminnormalized); g.d and d.d follow from the sums of the pass that produced dk.  x = xk is not
     // materialised: every trial point x = xk + stp * d is written by the line search -- by the evaluation itself, from dk
     // and the norms on the device, where the tile kernel can (foldable), else from the d a scaling pass stores.
-    double stp = 1.0, dginit = 0, dd = 0;
-    double gdk = 0, ns1 = 1, ns2 = 1;  // g.dk at xk and the two scale factors, for the beta denominator below
+    double stp = 1.0;
     bool pre_launched = false, g_swapped = false;
     // the first step is lastgoodstep unless that is 0 (then it comes from the direction's norms)
     const double stp_pre = (lastgoodstep != 0 && lastgoodstep >= 1.0e-50 && lastgoodstep <= 1.0e+50) ? lastgoodstep : 0.0;
     double stp_ready = 0.0;  // the step whose trial point is already in cg.x and / or whose evaluation is already queued
-    {
-      if (!cg.foldable) {
-        rc = cg.normalize(stp_pre);
-        if (rc) return rc;
-        stp_ready = stp_pre;
-      }
-      // The line search's first trial evaluation is queued NOW, behind the passes above, and runs while the host waits
-      // for the direction's sums and decides (mcsrch tries stp first whenever g.d < 0; otherwise line_search discards the
-      // evaluation): no host round trip in front of it.
-      if (stp_pre != 0.0 && cg.chained()) {
-        std::swap(cg.g, cg.gp);  // gp = gradient at xk
-        g_swapped = true;
-        rc = cg.foldable ? cg.evaluate(cg.dk, nullptr, cg.xk, stp_pre) : cg.evaluate(cg.d);
-        if (rc) return rc;
-        pre_launched = true;
-        stp_ready = stp_pre;
-      }
-      double mx = 0, ss = 0, gdn = 0;
-      rc = cg.wait_dir(&mx, &ss, &gdn);
+    if (!cg.foldable) {
+      rc = cg.normalize(stp_pre);
       if (rc) return rc;
-      double s1, s2;
-      norm_factors(mx, ss, s1, s2);
-      dginit = (gdn * s1) * s2;
-      dd = ((ss * s1) * s1) * (s2 * s2);
-      gdk = gdn; ns1 = s1; ns2 = s2;
-      if (mx != 0) { stp = stp / s1; stp = stp / s2; }
+      stp_ready = stp_pre;
     }
+    // The line search's first trial evaluation is queued NOW, behind the passes above, and runs while the host waits
+    // for the direction's sums and decides (mcsrch tries stp first whenever g.d < 0; otherwise line_search discards the
+    // evaluation): no host round trip in front of it.
+    if (stp_pre != 0.0 && cg.chained()) {
+      std::swap(cg.g, cg.gp);  // gp = gradient at xk
+      g_swapped = true;
+      rc = cg.foldable ? cg.evaluate(cg.dk, nullptr, cg.xk, stp_pre) : cg.evaluate(cg.d);
+      if (rc) return rc;
+      pre_launched = true;
+      stp_ready = stp_pre;
+    }
+    StepNorms sn;  // g.dk at xk (sn.gdn) and the two scale factors also serve the beta denominator below
+    rc = cg.begin_step(&stp, &sn);
+    if (rc) return rc;
     if (lastgoodstep != 0) stp = lastgoodstep;
     int mcinfo = 0, nfev = 0;
     if (!g_swapped) std::swap(cg.g, cg.gp);  // gp = gradient at xk; the trial evaluations write g
     double dg_acc = 0;  // g.d at the last trial point
-    rc = line_search(cg, &f, dginit, &stp, gtol, &mcinfo, &nfev, trim, trace, stp_ready, pre_launched, &dg_acc);
+    rc = line_search(cg, &f, sn.dginit, &stp, gtol, &mcinfo, &nfev, trim, trace, stp_ready, pre_launched, &dg_acc);
     if (rc) return rc;
     if (nfev == 0) std::swap(cg.g, cg.gp);  // nothing was evaluated: g stays the gradient at xk, as in mcsrch
     double betak = 0;
@@ -528,55 +563,44 @@ static int run_cg(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int ma
     // rules are looked at.)
     const bool chain = cg.chained();
     const int restart = (res.its > 0 && res.its % (3 + (long long)n) == 0) ? 1 : 0;
+    // yk = g - gp ; vv = yk.dk ; betady = g.g/vv ; betahs = g.yk/vv.  vv = g.dk - gp.dk from sums already on the
+    // host: gp.dk is the direction pass's g.dn, g.dk = (g.d) / (s2 s1) with the accepted evaluation's g.d (k_beta_dots)
+    const double vv = (dg_acc / sn.s2) / sn.s1 - sn.gdn;
+    double* beta_dev = (chain && mcinfo == 1) ? mb.dscal + kDsBeta : (double*)nullptr;
     if (mcinfo == 1) {
-      // yk = g - gp ; vv = yk.dk ; betady = g.g/vv ; betahs = g.yk/vv.  vv = g.dk - gp.dk from sums already on the
-      // host: gp.dk is the direction pass's g.dn, g.dk = (g.d) / (s2 s1) with the accepted evaluation's g.d (k_beta_dots)
-      const double vv = (dg_acc / ns2) / ns1 - gdk;
-      double* beta_dst = chain ? cg.dscal + 8 : (double*)nullptr;
       // host-paced passes: the pass also sums y.dk directly (one more vector read) and the deviation of the derived
       // denominator from it is recorded (srmap_problem_selfcheck; tests/test_gpu_solve_parity.py)
       const T* dk_chk = chain ? (const T*)nullptr : (const T*)cg.dk;
-      launch_cg_beta_dots<T>(cg.gp, cg.g, n, cg.ow, cg.part, cg.fin_host(false), beta_dst, restart, vv, dk_chk, cg.nb(), cg.st);
-      if (chain) {
-        const double tag_beta = cg.tag;
-        rc = cg.direction(cg.dk, 0.0, false, cg.dscal + 8);  // dn, sums of dn (device)
-        if (rc) return rc;
-        rc = cg.wait_tag(tag_beta);
-        if (rc) return rc;
-        gg = cg.hs[0];
-      } else {
-        double h[3];
-        rc = cg.finish(3, false, false, h);
-        if (rc) return rc;
+      launch_cg_beta_dots<T>(cg.gp, cg.g, n, cg.ow, mb.part, mb.fin(false), beta_dev, restart, vv, dk_chk, cg.nb(), cg.st);
+    } else {
+      launch_cg_dot<T>(cg.g, cg.g, n, cg.ow, mb.part, mb.fin(false), cg.nb(), cg.st);
+    }
+    double h[3] = {0, 0, 0};  // g.g [, g.y, y.dk summed directly]
+    if (chain) {
+      const double tag_sums = mb.tag;
+      rc = cg.direction(cg.dk, 0.0, false, beta_dev);  // dn (beta from the device, or 0), sums of dn (device)
+      if (rc) return rc;
+      rc = mb.wait_tag(tag_sums);
+      if (rc) return rc;
+      h[0] = mb.hs[kHsPass];
+    } else {
+      rc = mb.finish(cg.nb(), mcinfo == 1 ? 3 : 1, false, h);
+      if (rc) return rc;
+      if (mcinfo == 1) {
         betak = dmax(0.0, dmin(h[0] / vv, h[1] / vv));
-        gg = h[0];
         if (h[2] != 0.0 && std::isfinite(h[2]) && std::isfinite(vv))
           cg.p->selfcheck_beta_den = dmax(cg.p->selfcheck_beta_den, std::fabs(vv - h[2]) / std::fabs(h[2]));
       }
-    } else {
-      launch_cg_dot<T>(cg.g, cg.g, n, cg.ow, cg.part, cg.fin_host(false), cg.nb(), cg.st);
-      if (chain) {
-        const double tag_gg = cg.tag;
-        rc = cg.direction(cg.dk, 0.0);  // beta = 0
-        if (rc) return rc;
-        rc = cg.wait_tag(tag_gg);
-        if (rc) return rc;
-        gg = cg.hs[0];
-      } else {
-        double h[1];
-        rc = cg.finish(1, false, false, h);
-        if (rc) return rc;
-        gg = h[0];
-      }
     }
+    gg = h[0];
     if (restart) betak = 0;
     if (mcinfo == 1 || mcinfo == 5) rstimer = rscountdownlen; else rstimer -= 1;
     if (!chain) {
       rc = cg.direction(cg.dk, betak);  // dn, norms of dn (device)
       if (rc) return rc;
     }
-    const double lastscaledstep = stp * std::sqrt(dd);
-    if (mcinfo == 1) lastgoodstep = stp * std::sqrt(dd);
+    const double lastscaledstep = stp * std::sqrt(sn.dd);
+    if (mcinfo == 1) lastgoodstep = stp * std::sqrt(sn.dd);
     if (!std::isfinite(gg) || !std::isfinite(f)) { res.type = -8; break; }
     res.nfev += nfev;
     res.its += 1;
@@ -628,16 +652,12 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
       rc = cg.normalize(0.0);
       if (rc) return rc;
     }
-    double mx = 0, ss = 0, gdn = 0;
-    rc = cg.wait_dir(&mx, &ss, &gdn);
+    StepNorms sn;
+    rc = cg.begin_step(&stp, &sn);
     if (rc) return rc;
-    double s1, s2;
-    norm_factors(mx, ss, s1, s2);
-    const double dginit = (gdn * s1) * s2;
-    if (mx != 0) { stp = stp / s1; stp = stp / s2; }
     int mcinfo = 0, nfev = 0;
     std::swap(cg.g, cg.gp);  // gp = gradient at xk; the trial evaluations write g
-    rc = line_search(cg, &f, dginit, &stp, gtol, &mcinfo, &nfev, trim, trace);
+    rc = line_search(cg, &f, sn.dginit, &stp, gtol, &mcinfo, &nfev, trim, trace);
     if (rc) return rc;
     if (nfev == 0) std::swap(cg.g, cg.gp);  // nothing evaluated: x = xk, g the gradient there (s = y = 0)
     if (nfev != 0) nfev_state = nfev;
@@ -646,17 +666,9 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
     // sk = x - xk, yk = g - g_k into slot p (ALGLIB writes them whatever mcinfo is) and the Gram rows of the new pair
     rc = cg.lbfgs_update(nfev == 0 ? (const T*)cg.g : (const T*)cg.gp, p, live);
     if (rc) return rc;
-    const double* r = cg.lb_host;
-    gg = r[0];
-    const double sks = r[1];
-    for (int j = 0; j < live; ++j) {
-      SY[(size_t)p * m + j] = r[2 + 5 * j];
-      SY[(size_t)j * m + p] = r[3 + 5 * j];
-      YY[(size_t)p * m + j] = r[4 + 5 * j];
-      YY[(size_t)j * m + p] = r[4 + 5 * j];
-      gs[j] = r[5 + 5 * j];
-      gy[j] = r[6 + 5 * j];
-    }
+    gg = cg.lb_host[kLbGg];
+    const double sks = cg.lb_host[kLbSs];
+    lbfgs_unpack_rows(cg.lb_host, p, live, m, SY.data(), YY.data(), gs.data(), gy.data());
     if (!std::isfinite(gg) || !std::isfinite(f)) { res.type = -8; break; }
     if (res.its >= maxits && maxits > 0) { res.type = 5; break; }
     if (std::sqrt(gg) <= epsg) { res.type = 4; break; }
@@ -684,6 +696,28 @@ static int run_lbfgs(DeviceCG<T>& cg, double epsg, double epsf, double epsx, int
   return SRMAP_OK;
 }
 
+// What a solve over `mode` shards refuses, before any collective
+static int check_solve_shard(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, const srmap_irls_options* opt,
+                             int mode) {
+  const Geometry& geo = p->geo;
+  if (p->solver == SRMAP_SOLVER_LBFGS && mode != SRMAP_SHARD_NONE)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
+  if (int rc = refuse_sharded(p, mode, "solve")) return rc;
+  if (mode != SRMAP_SHARD_NONE && opt->split_channels)
+    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
+  if (mode == SRMAP_SHARD_ROWS &&
+      (shard->own_row0 < 0 || shard->own_row1 > geo.H || shard->own_row0 >= shard->own_row1 ||
+       shard->own_row0 != geo.cr0 || shard->own_row1 != geo.cr1))
+    return set_error(p->ctx, SRMAP_EINVAL, "row shard: owned rows must equal the problem's cost rows");
+  if ((mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) &&
+      (shard->own_ch0 < 0 || shard->own_ch1 > geo.C || shard->own_ch0 >= shard->own_ch1))
+    return set_error(p->ctx, SRMAP_EINVAL, "channel shard: bad owned channel range");
+  if (mode == SRMAP_SHARD_GRID && (shard->frame_groups < 1 || comm_world(comm) % shard->frame_groups != 0 ||
+                                   (shard->frame_groups > 1 && !shard->frame_comm)))
+    return set_error(p->ctx, SRMAP_EINVAL, "grid shard: frame_groups must divide the world size and frame_comm must be given");
+  return SRMAP_OK;
+}
+
 template <typename T>
 static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_desc* shard, const srmap_irls_options* opt,
                        const double* x0, double* x_out, srmap_solve_report* report, const void* x0_dev = nullptr,
@@ -694,24 +728,8 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
   const int C = geo.C;
   const int mode = shard_mode(comm, shard);
   const bool lbfgs = p->solver == SRMAP_SOLVER_LBFGS;
-  if (lbfgs && mode != SRMAP_SHARD_NONE)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "L-BFGS solves are not sharded over a communicator (its Gram rows would need an all-reduce): run them unsharded, or per channel with split_channels");
   const bool huber = p->dw.loss() == SRMAP_DATA_LOSS_HUBER;
-  if (int rc = refuse_sharded(p, mode, "solve")) return rc;
-  if (mode != SRMAP_SHARD_NONE && opt->split_channels)
-    return set_error(p->ctx, SRMAP_EUNSUPPORTED, "split_channels solves are independent per channel: run them unsharded");
-  if (mode == SRMAP_SHARD_ROWS &&
-      (shard->own_row0 < 0 || shard->own_row1 > geo.H || shard->own_row0 >= shard->own_row1 ||
-       shard->own_row0 != geo.cr0 || shard->own_row1 != geo.cr1))
-    return set_error(p->ctx, SRMAP_EINVAL, "row shard: owned rows must equal the problem's cost rows");
-  if ((mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) &&
-      (shard->own_ch0 < 0 || shard->own_ch1 > C || shard->own_ch0 >= shard->own_ch1))
-    return set_error(p->ctx, SRMAP_EINVAL, "channel shard: bad owned channel range");
-  if (mode == SRMAP_SHARD_GRID && (shard->frame_groups < 1 || comm_world(comm) % shard->frame_groups != 0 ||
-                                   (shard->frame_groups > 1 && !shard->frame_comm)))
-    return set_error(p->ctx, SRMAP_EINVAL, "grid shard: frame_groups must divide the world size and frame_comm must be given");
-  // GRID: the unknowns of a channel block are replicated over its frame groups; group 0 counts them in the reductions
-  const bool grid_replica = mode == SRMAP_SHARD_GRID && shard->frame_groups > 1 && (comm_rank(comm) % shard->frame_groups) != 0;
+  if (int rc = check_solve_shard(p, comm, shard, opt, mode)) return rc;
   const int per_split = opt->split_channels ? 1 : C;
   const int rounds = C / per_split;
   const size_t npts = (size_t)per_split * N;
@@ -722,7 +740,7 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     double params = (double)(int)npts;
     if (mode == SRMAP_SHARD_ROWS || mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
       double own = mode == SRMAP_SHARD_ROWS ? (double)C * geo.W * (shard->own_row1 - shard->own_row0)
-                                            : (grid_replica ? 0.0 : (double)(shard->own_ch1 - shard->own_ch0) * N);
+                                            : (grid_replica(comm, shard) ? 0.0 : (double)(shard->own_ch1 - shard->own_ch0) * N);
       // every rank must derive the same thresholds: total parameter count = sum of the owned counts
       DevBuf tmp;
       SRMAP_HIP(p->ctx, tmp.alloc(sizeof(double)));
@@ -741,19 +759,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     }
   }
   srmap_solve_report rep = {0, 0, 0, 0, 0.0, 0.0, 0.0, 0};
-  hipStream_t st = p->ctx->stream;
   DeviceCG<T> cg;
-  cg.p = p; cg.st = st; cg.n = npts; cg.comm = comm; cg.shard = shard;
-  cg.chain_enabled = o.host_paced_passes == 0;
-  cg.fold_enabled = o.host_paced_passes == 0;
-  cg.ow.on = 0; cg.ow.e0 = 0; cg.ow.e1 = npts; cg.ow.W = geo.W; cg.ow.H = geo.H; cg.ow.r0 = 0; cg.ow.r1 = geo.H;
-  if (mode == SRMAP_SHARD_ROWS) { cg.ow.on = 1; cg.ow.r0 = shard->own_row0; cg.ow.r1 = shard->own_row1; cg.reduce_scalars = true; }
-  if (mode == SRMAP_SHARD_CHANNELS || mode == SRMAP_SHARD_GRID) {
-    cg.ow.on = 1; cg.ow.e0 = (size_t)shard->own_ch0 * N; cg.ow.e1 = grid_replica ? cg.ow.e0 : (size_t)shard->own_ch1 * N;
-    cg.reduce_scalars = true;
-  }
-  int rc = cg.alloc();
-  if (rc == SRMAP_OK && lbfgs) rc = cg.alloc_lbfgs(p->lbfgs_m);
+  int rc = cg.init(p, comm, shard, npts, &o, lbfgs ? p->lbfgs_m : 0);
+  hipStream_t st = cg.st;
   if (rc == SRMAP_OK && huber && !p->dw.effective<T>()) rc = set_error(p->ctx, SRMAP_EINVAL, "internal: a Huber loss without its weight buffer");
   // IRLS weights live in the problem's RegSpec (full [C][H][W]); make sure they exist.
   for (int r = 0; r < p->nreg && rc == SRMAP_OK; ++r) {
@@ -825,9 +833,9 @@ static int solve_typed(srmap_problem* p, srmap_comm* comm, const srmap_shard_des
     }
   }
   rep.evaluations = cg.evaluations;
-  rep.wait_seconds = cg.wait_seconds;
-  rep.waits = cg.waits;
-  rc = cg.recover_timeout(rc);
+  rep.wait_seconds = cg.mb.wait_seconds;
+  rep.waits = cg.mb.waits;
+  rc = cg.mb.recover_timeout(rc);
   if (report) *report = rep;
   return rc;
 }
@@ -841,16 +849,13 @@ static int cg_trace_typed(srmap_problem* p, int lbfgs_m, double epsg, double eps
                           int* trace_len) {
   const size_t npts = p->hr_count();
   DeviceCG<T> cg;
-  cg.p = p; cg.st = p->ctx->stream; cg.n = npts;
-  cg.ow.on = 0; cg.ow.e0 = 0; cg.ow.e1 = npts; cg.ow.W = p->geo.W; cg.ow.H = p->geo.H; cg.ow.r0 = 0; cg.ow.r1 = p->geo.H;
-  int rc = cg.alloc();
-  if (rc == SRMAP_OK && lbfgs_m > 0) rc = cg.alloc_lbfgs(lbfgs_m);
+  int rc = cg.init(p, nullptr, nullptr, npts, nullptr, lbfgs_m);
   if (rc == SRMAP_OK) rc = convert_upload(p, x0, cg.x, npts, cg.st);
   CgResult cr;
   std::vector<double> tr;
   if (rc == SRMAP_OK) rc = lbfgs_m > 0 ? run_lbfgs(cg, epsg, epsf, epsx, maxits, &cr, &tr) : run_cg(cg, epsg, epsf, epsx, maxits, &cr, &tr);
   if (rc == SRMAP_OK) rc = convert_download(p, cg.x, x_out, npts, cg.st);
-  rc = cg.recover_timeout(rc);
+  rc = cg.mb.recover_timeout(rc);
   if (rc) return rc;
   if (iterations) *iterations = cr.its;
   if (nfev) *nfev = cr.nfev;

@@ -1,5 +1,5 @@
 // solver_host.hpp -- the host arithmetic of the inner solvers (solver.hip) that touches no device: the More'-Thuente
-// safeguarded step of the line search and the L-BFGS two-loop recursion on coefficients.  Plain C++ in double, in
+// safeguarded step of the line search, the L-BFGS two-loop recursion on coefficients and its Gram tables.  Plain C++ in double, in
 // ALGLIB's order of operations; tests/cpp/solver_host_test.cpp runs it without a GPU against the numpy restatement
 // (tests/lbfgs_restatement.py), bit for bit.
 #pragma once
@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstddef>
 #include <vector>
+
+#include "solver_mailbox.hpp"
 
 namespace srmap {
 
@@ -126,6 +128,18 @@ inline bool lbfgs_two_loop(const double* SY, const double* YY, const double* gs,
   coef[0] = cgc;
   for (int j = 0; j < live; ++j) { coef[1 + 2 * j] = cs[j]; coef[2 + 2 * j] = cy[j]; }
   return true;
+}
+
+// The rows r of the update pass that wrote the new pair to ring slot p (solver_mailbox.hpp: lb_row) into the tables above,
+// `live` slots holding pairs.  The pass recomputes every entry that involves slot p; the older pairs' entries stay.
+inline void lbfgs_unpack_rows(const double* r, int p, int live, int m, double* SY, double* YY, double* gs, double* gy) {
+  for (int j = 0; j < live; ++j) {
+    SY[(size_t)p * m + j] = r[lb_row(j, kLbSyj)];
+    SY[(size_t)j * m + p] = r[lb_row(j, kLbYsj)];
+    YY[(size_t)p * m + j] = YY[(size_t)j * m + p] = r[lb_row(j, kLbYyj)];
+    gs[j] = r[lb_row(j, kLbGsj)];
+    gy[j] = r[lb_row(j, kLbGyj)];
+  }
 }
 
 }  // namespace srmap

@@ -15,6 +15,7 @@
 #include "data_weights.hpp"
 #include "dev_mem.hpp"
 #include "motion_model.hpp"
+#include "solver_mailbox.hpp"
 #include "srmap.h"
 
 namespace srmap {
@@ -104,7 +105,7 @@ struct srmap_ctx {
   // and a small scalar block the reduction kernels write directly (no copy kernels, one sync)
   srmap::PinnedBuf h_stage[2];
   hipEvent_t h_event[2] = {nullptr, nullptr};
-  srmap::PinnedBuf h_scal;   // double[16], host-mapped
+  srmap::PinnedBuf h_scal;   // double[kHsSlots], host-mapped: the solver's mailbox (solver_mailbox.hpp)
   void* blas = nullptr;      // rocblas_handle of this context (channel_map.hip), created on first use
 };
 
@@ -409,8 +410,7 @@ int irls_options_in_force(srmap_problem* p, const srmap_irls_options* options, s
 // the context's stream, complete on return.  A start that holds the caller's doubles rounded to the dtype gives srmap_solve's bits
 int solve_device(srmap_problem* p, const srmap_irls_options* opt, const void* x0_dev, void* x_out_dev, srmap_solve_report* report);
 
-// ---- L-BFGS passes (kernels_lbfgs.hip) ----
-constexpr int kLbfgsMaxM = 8;  // history cap of srmap_problem_set_solver (bounds the update pass's accumulators)
+// ---- L-BFGS passes (kernels_lbfgs.hip; kLbfgsMaxM and the update pass's rows: solver_mailbox.hpp) ----
 // Where a pass leaves its sums: workgroup partials part[rows][gridDim.x], ticket (0 between passes), the reduced sums in
 // out_dev (device, may be null) and out_host (host-mapped), then `tag` at tag_slot behind a system-scope fence.
 struct LbfgsRed {
@@ -427,8 +427,8 @@ struct LbfgsCoef {
   double c[1 + 2 * kLbfgsMaxM];
 };
 static_assert(std::is_trivially_copyable_v<LbfgsCoef>, "a kernel argument: no owner inside");
-// ring slot p <- (s, y) = (x - xk, g - gk); sums [0] g.g, [1] s.s, then per slot j < live: s.y_j, y.s_j, y.y_j, g.s_j,
-// g.y_j (2 + 5 live rows)
+// ring slot p <- (s, y) = (x - xk, g - gk); sums [kLbGg] g.g, [kLbSs] s.s, then per slot j < live [lb_row(j, .)]: s.y_j,
+// y.s_j, y.y_j, g.s_j, g.y_j (lb_rows(live) rows)
 template <typename T>
 int launch_lbfgs_update(const T* x, const T* xk, const T* g, const T* gk, T* S, T* Y, int p, int live, size_t n, int nb,
                         const LbfgsRed& red, hipStream_t st);

@@ -29,8 +29,8 @@ int ensure_staging(srmap_ctx* ctx) {
     if (!ctx->h_event[i]) SRMAP_HIP(ctx, hipEventCreateWithFlags(&ctx->h_event[i], hipEventDisableTiming));
   }
   if (!ctx->h_scal) {
-    SRMAP_HIP(ctx, ctx->h_scal.alloc(16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    for (int i = 0; i < 16; ++i) ctx->h_scal.as<double>()[i] = 0.0;
+    SRMAP_HIP(ctx, ctx->h_scal.alloc(kHsSlots * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    for (int i = 0; i < kHsSlots; ++i) ctx->h_scal.as<double>()[i] = 0.0;
   }
   return SRMAP_OK;
 }

@@ -1,7 +1,9 @@
 """csrc/solver_host.hpp, the solvers' host arithmetic (tests/cpp/solver_host_test.cpp), CPU only, against
 tests/lbfgs_restatement.py (bit-exact against ALGLIB, tests/test_lbfgs_cpu.py): the More'-Thuente step mt_step against
 mcstep, the L-BFGS recursion on coefficients lbfgs_two_loop against _gram_direction.  Both sides are the same IEEE
-double operations in the same order and neither build contracts a * b + c, so every comparison is equality of bits."""
+double operations in the same order and neither build contracts a * b + c, so every comparison is equality of bits.
+Further the unpacking of the update pass's rows into the Gram tables (lbfgs_unpack_rows) against numpy, and the polling
+decision of csrc/solver_mailbox.hpp (poll_tag) on plain host memory."""
 import os
 import subprocess
 import sys
@@ -181,3 +183,44 @@ def test_two_loop_reports_a_zero_curvature_pair():
         lines.append(_line(m, k, q, (t, YY, gs, gy) if table is SY else (SY, t, gs, gy), np.ones(m)))
     rows = _run(lines)
     assert rows[0] != "none" and rows[1:] == ["none", "none"]
+
+
+# ---- lbfgs_unpack_rows --------------------------------------------------------------------------------------------
+def test_unpack_rows_equals_numpy():
+    """The rows [g.g, s.s, then per slot j: s.y_j, y.s_j, y.y_j, g.s_j, g.y_j] into row / column p of the tables; every
+    other entry keeps its bits.  p at both ends of the ring, every live count."""
+    rng = np.random.default_rng(29)
+    cases, lines = [], []
+    for m in (1, 3, 8):
+        for live in range(1, m + 1):
+            for p in sorted({0, m - 1}):
+                SY, YY = rng.standard_normal((m, m)), rng.standard_normal((m, m))
+                gs, gy = rng.standard_normal(m), rng.standard_normal(m)
+                rows = rng.standard_normal(2 + 5 * live)
+                lines.append("up %d %d %d " % (m, p, live) + " ".join(_hex(t.ravel()) for t in (SY, YY, gs, gy, rows)))
+                per = rows[2:].reshape(live, 5)
+                SY[p, :live] = per[:, 0]
+                SY[:live, p] = per[:, 1]   # j == p: s_p.y_p is summed twice, the second sum stays
+                YY[p, :live] = per[:, 2]
+                YY[:live, p] = per[:, 2]
+                gs[:live] = per[:, 3]
+                gy[:live] = per[:, 4]
+                cases.append((m, p, live, np.concatenate([SY.ravel(), YY.ravel(), gs, gy])))
+    assert len(cases) == len(lines) == 1 + 2 * 3 + 2 * 8
+    for (m, p, live, want), row in zip(cases, _run(lines)):
+        got = [float.fromhex(v) for v in row.split()]
+        assert np.array_equal(_bits(got), _bits(want)), (m, p, live)
+
+
+# ---- poll_tag -----------------------------------------------------------------------------------------------------
+def test_poll_tag_decisions():
+    """Single-threaded on plain host memory: nothing changes the words while the call polls them."""
+    rows = _run([
+        "pt 7 0 7 0.003",    # the wanted tag is there
+        "pt 9 0 7 0.003",    # a later kernel's tag: arrived all the same (tags only grow)
+        "pt 7 1 7 0.003",    # arrived wins over a raised time-out word
+        "pt 6 1 7 0.003",    # not there and the device gave up
+        "pt 6 0 7 0.003",    # neither: the budget runs out
+        "pt nan 0 7 0.003",  # a word that compares false is not an arrival
+    ])
+    assert rows == ["arrived", "arrived", "arrived", "timeout", "expired", "expired"]
