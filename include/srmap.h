@@ -448,6 +448,18 @@ int srmap_residual_scale_device(srmap_problem* p, const void* x_dev, void* hip_s
  * loss returns from HUBER to L2, that buffer holds the last Huber weights: set the weights again (NULL for none) after
  * leaving HUBER -- the effective weights and the L2 base weight of srmap_holdout_score are formed from it. */
 int srmap_problem_set_holdout(srmap_problem* p, double fraction, unsigned long long seed);
+/* A hold-out given as a FOLD of a partition.  Both forms are one band test on v = z >> 40, the top 24 bits of the mix:
+ * observation i is held out iff lo <= v < hi.  srmap_problem_set_holdout is the band [0, T); fold `fold` of `folds` is
+ *     lo = floor(fold * 2^24 / folds),  hi = floor((fold + 1) * 2^24 / folds)       (integer arithmetic)
+ * so the bands of folds 0 ... folds - 1 meet end to start, the first begins at 0 and the last ends at exactly 2^24: every
+ * observation is in exactly one fold.  folds must be in 2...32 and 0 <= fold < folds; folds == 0 lifts the hold-out;
+ * anything else: SRMAP_EINVAL, the message naming this call.  In every other respect it IS the hold-out above -- a factor
+ * of the prior, persistent across the setters, refused when sharded --; a fold and a fraction replace each other, and 0 in
+ * either call lifts whichever is set.  srmap_problem_get_holdout then reports fraction = (hi - lo) / 2^24, and the mask
+ * and the counts of the band. */
+int srmap_problem_set_holdout_fold(srmap_problem* p, int folds, int fold, unsigned long long seed);
+/* The fold in force: *folds (0: none, or a fraction is set), *fold, *seed.  Every output is optional. */
+int srmap_problem_get_holdout_fold(srmap_problem* p, int* folds, int* fold, unsigned long long* seed);
 /* The hold-out in force: *fraction (0: none) and *seed; mask_out ([K][C][h][w] doubles, 1 = held out) as the device
  * computes it; counts[0] the held-out observations, counts[1 + k] those of frame k.  Every output is optional. */
 int srmap_problem_get_holdout(srmap_problem* p, double* fraction, unsigned long long* seed, double* mask_out /* optional */,
@@ -950,6 +962,53 @@ void srmap_lambda_path_options_default(srmap_lambda_path_options* options);
 int srmap_solve_lambda_path(srmap_problem* p, const srmap_irls_options* irls_options /* NULL = defaults */,
                             const srmap_lambda_path_options* path_options /* NULL = defaults */, const double* x0, double* x_out,
                             double* table, int* rows_run, int* chosen, srmap_solve_report* final_report);
+
+/* The cross-validated path: srmap_solve_lambda_path over the `folds` folds of a partition of the
+ * observations, and the one-standard-error rule.  Needs at least one regulariser with lambda > 0 and observations, and NO
+ * hold-out beforehand: whatever hold-out is set at the call -- none, a fraction or a fold -- is in force again on return,
+ * on success and on an error.  scales: as above.  Rows are the outer loop, folds the inner one; row j, fold f is bit for bit
+ *     srmap_problem_set_regularizer_lambda for every regulariser,  srmap_problem_set_holdout_fold(folds, f, seed),
+ *     srmap_solve from x0,  srmap_holdout_score
+ * with the path's delta as above (under HUBER / MAD the delta of row 0, fold 0, held for every row and fold).  A fold whose
+ * score call fails -- no held-out observation with a base weight above 0, say -- fails the path.  With s[j][f] that
+ * fold's score[0] (its S1 / S0 over all frames):
+ *     mean[j] = (sum_f s[j][f]) / folds                                   (added in fold order)
+ *     se[j]   = sqrt(sum_f (s[j][f] - mean[j])^2 / (folds - 1) / folds)   (the standard error of that mean)
+ *     j*      = the FIRST minimum of mean, so a tie goes to the larger lambda
+ * SRMAP_LAMBDA_RULE_MIN chooses j*.  SRMAP_LAMBDA_RULE_ONE_SE chooses the smallest j -- the largest lambda among the rows
+ * run -- with mean[j] <= mean[j*] + se_factor * se[j*] (se_factor finite, >= 0; 0 is MIN but for exact ties): the score
+ * under-counts the high-frequency error of too little regularisation because A blurs, so among rows the folds cannot tell
+ * apart the larger lambda is the better one.  A row with a fold score that is not a number is neither j* nor eligible.
+ * patience reads mean.  The standard error is the spread OVER THE FOLDS, not the per-pixel one that S2 and n give: under
+ * outliers the per-pixel error is dominated by the corrupted held-out pixels (several times the fold error) and a rule
+ * built on it picks the largest lambda of any grid.  That is why srmap_solve_lambda_path, which has one split, has no
+ * one-standard-error rule.
+ * final_solve != 0: the hold-out is lifted and one solve from x0 at the chosen lambdas on ALL observations gives x_out and
+ * *final_report; final_solve == 0: neither is written (a row has one solution per fold, none of them the row's), and x_out
+ * may be NULL.  The chosen lambdas stay set; on an error the lambdas of the call's start are restored.  x0 is staged once;
+ * the iterates stay on the device.
+ * table: num_scales rows of SRMAP_LAMBDA_PATH_ROW doubles, *rows_run of them written:
+ *   {scale, mean, se, pooled S1, S2, S0, n (each added in fold order), sum of IRLS rounds, of inner iterations, of
+ *    evaluations over the folds, delta used}.
+ * fold_table (optional): num_scales x folds rows, [scale][fold], each in srmap_solve_lambda_path's layout. */
+#define SRMAP_LAMBDA_RULE_MIN 0
+#define SRMAP_LAMBDA_RULE_ONE_SE 1
+typedef struct {
+  int struct_size;   /* filled by srmap_lambda_cv_options_default(); another size is refused */
+  int num_scales;    /* 8 */
+  double scales[SRMAP_LAMBDA_PATH_MAX_SCALES]; /* 1, 1/2, ..., 1/128 */
+  int folds;         /* 5; 2...32 */
+  int rule;          /* SRMAP_LAMBDA_RULE_ONE_SE */
+  unsigned long long seed; /* 1 */
+  double se_factor;  /* 1.0 */
+  int patience;      /* 0 */
+  int final_solve;   /* 1 */
+} srmap_lambda_cv_options;
+void srmap_lambda_cv_options_default(srmap_lambda_cv_options* options);
+int srmap_solve_lambda_path_folds(srmap_problem* p, const srmap_irls_options* irls_options /* NULL = defaults */,
+                                  const srmap_lambda_cv_options* cv_options /* NULL = defaults */, const double* x0,
+                                  double* x_out, double* table, double* fold_table /* optional */, int* rows_run, int* chosen,
+                                  srmap_solve_report* final_report /* optional */);
 
 /* Self-check of the solver's derived sums (no reference counterpart).  mincg forms the DY / HS betas with the
  * denominator y.dk summed over the vectors (optimization.cpp:17700-17760); this solver derives it from sums it already

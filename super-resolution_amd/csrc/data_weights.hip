@@ -185,7 +185,7 @@ int DataWeights::leave_prior(srmap_problem* p, hipStream_t st) {
 int DataWeights::form_held_prior(srmap_problem* p, hipStream_t st) {
   return dispatch_dtype(p->dtype, [&](auto t) {
     using T = decltype(t);
-    return launch_holdout_prior<T>(p, caller_.as<const T>(), prior_.as<T>(), p->lr_count(), hold_.seed, hold_.threshold, st);
+    return launch_holdout_prior<T>(p, caller_.as<const T>(), prior_.as<T>(), p->lr_count(), hold_.seed, hold_.lo, hold_.threshold, st);
   });
 }
 

@@ -73,8 +73,10 @@ class DataWeights {
   // the caller's weights while a prior or a hold-out keeps them in the second buffer; nullptr: none, or not kept apart
   template <typename T>
   const T* user() const { return user_.as<const T>(); }
-  // the hold-out in force: threshold 0 = none (holdout_host.hpp)
-  struct Holdout { unsigned threshold = 0; unsigned long long seed = 0; double fraction = 0.0; };
+  // the hold-out in force: observation i is held out iff lo <= hash24(i, seed) < threshold (holdout_host.hpp); threshold
+  // 0 = none.  A fraction is the band [0, T), folds = 0; fold `fold` of `folds` (srmap_problem_set_holdout_fold) is its
+  // band of the partition, fraction = (threshold - lo) / 2^24
+  struct Holdout { unsigned threshold = 0; unsigned long long seed = 0; double fraction = 0.0; unsigned lo = 0; int folds = 0, fold = 0; };
   const Holdout& holdout() const { return hold_; }
   // whether a Huber step in the MAD mode has left its delta in the problem's record (residual_scale.hip) since the loss
   // and the scale rule in force were set

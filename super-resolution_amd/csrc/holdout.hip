@@ -23,7 +23,7 @@ namespace {
 // whole allocations), the last elements one by one.  The instance without m reads nothing.
 template <typename T, bool HAS_M>
 __global__ __launch_bounds__(256) void k_holdout_prior(const T* __restrict__ m, T* __restrict__ out, size_t n,
-                                                      unsigned long long seed, unsigned threshold) {
+                                                      unsigned long long seed, unsigned lo, unsigned hi) {
   constexpr int V = 16 / (int)sizeof(T);
   typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
   const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, nth = (size_t)gridDim.x * 256;
@@ -34,13 +34,13 @@ __global__ __launch_bounds__(256) void k_holdout_prior(const T* __restrict__ m, 
 #pragma unroll
     for (int q = 0; q < V; ++q) {
       const T keep = HAS_M ? o[q] : T(1);
-      o[q] = holdout_held_dev((uint64_t)(g * V + q), seed, threshold) ? T(0) : keep;
+      o[q] = holdout_held_dev((uint64_t)(g * V + q), seed, lo, hi) ? T(0) : keep;
     }
     reinterpret_cast<VT*>(out)[g] = o;
   }
   for (size_t i = nv * V + tid; i < n; i += nth) {
     const T keep = HAS_M ? m[i] : T(1);
-    out[i] = holdout_held_dev((uint64_t)i, seed, threshold) ? T(0) : keep;
+    out[i] = holdout_held_dev((uint64_t)i, seed, lo, hi) ? T(0) : keep;
   }
 }
 
@@ -57,7 +57,7 @@ constexpr int kHoldSums = 4;  // S1 = sum u rho, S2 = sum u rho^2, S0 = sum u, n
 // that is 16-byte aligned in every stream, as k_select_hist does.
 template <typename T, int BASE>
 __global__ __launch_bounds__(256) void k_holdout_sums(const T* __restrict__ r, const T* __restrict__ a, const T* __restrict__ b,
-                                                     size_t rowlen, unsigned long long seed, unsigned threshold, double delta,
+                                                     size_t rowlen, unsigned long long seed, unsigned lo, unsigned hi, double delta,
                                                      const double* __restrict__ delta_dev, double* __restrict__ part) {
   constexpr int V = 16 / (int)sizeof(T);
   typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_holdout_sums(const T* __restrict__ r, c
   double acc[kHoldSums] = {0.0, 0.0, 0.0, 0.0};
   auto take = [&](size_t j, T rv, T uv) {
 #pragma clang fp contract(off)
-    if (!holdout_held_dev(i0 + j, seed, threshold)) return;
+    if (!holdout_held_dev(i0 + j, seed, lo, hi)) return;
     const double u = (double)uv, rd = (double)rv, ar = fabs(rd);
     double rho = rd * rd;
     if (dl > 0.0 && ar > dl) {
@@ -115,18 +115,18 @@ int holdout_sums_groups(const srmap_problem* p, size_t rowlen) {
 }  // namespace
 
 template <typename T>
-int launch_holdout_prior(srmap_problem* p, const T* m, T* out, size_t n, unsigned long long seed, unsigned threshold, hipStream_t st) {
+int launch_holdout_prior(srmap_problem* p, const T* m, T* out, size_t n, unsigned long long seed, unsigned lo, unsigned hi, hipStream_t st) {
   constexpr size_t V = 16 / sizeof(T);
   if (n == 0) return SRMAP_OK;
   const size_t cap = (size_t)std::max(1, p->ctx->num_cus) * 8;
   const unsigned blocks = (unsigned)std::max<size_t>(1, std::min((n + V * 256 - 1) / (V * 256), cap));
-  if (m) hipLaunchKernelGGL((k_holdout_prior<T, true>), dim3(blocks), dim3(256), 0, st, m, out, n, seed, threshold);
-  else hipLaunchKernelGGL((k_holdout_prior<T, false>), dim3(blocks), dim3(256), 0, st, m, out, n, seed, threshold);
+  if (m) hipLaunchKernelGGL((k_holdout_prior<T, true>), dim3(blocks), dim3(256), 0, st, m, out, n, seed, lo, hi);
+  else hipLaunchKernelGGL((k_holdout_prior<T, false>), dim3(blocks), dim3(256), 0, st, m, out, n, seed, lo, hi);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;
 }
-template int launch_holdout_prior<float>(srmap_problem*, const float*, float*, size_t, unsigned long long, unsigned, hipStream_t);
-template int launch_holdout_prior<double>(srmap_problem*, const double*, double*, size_t, unsigned long long, unsigned, hipStream_t);
+template int launch_holdout_prior<float>(srmap_problem*, const float*, float*, size_t, unsigned long long, unsigned, unsigned, hipStream_t);
+template int launch_holdout_prior<double>(srmap_problem*, const double*, double*, size_t, unsigned long long, unsigned, unsigned, hipStream_t);
 
 void holdout_pass_release(srmap_problem* p) {
   delete p->holdout_pass;
@@ -157,9 +157,9 @@ static int holdout_sums(srmap_problem* p, const T* x, double delta, const double
   const DataWeights::Holdout& h = p->dw.holdout();
   double* part = p->holdout_pass->d_part.as<double>();
   const dim3 grid(G, g.K);
-  if (a && b) hipLaunchKernelGGL((k_holdout_sums<T, 2>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.threshold, delta, delta_dev, part);
-  else if (a) hipLaunchKernelGGL((k_holdout_sums<T, 1>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.threshold, delta, delta_dev, part);
-  else hipLaunchKernelGGL((k_holdout_sums<T, 0>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.threshold, delta, delta_dev, part);
+  if (a && b) hipLaunchKernelGGL((k_holdout_sums<T, 2>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.lo, h.threshold, delta, delta_dev, part);
+  else if (a) hipLaunchKernelGGL((k_holdout_sums<T, 1>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.lo, h.threshold, delta, delta_dev, part);
+  else hipLaunchKernelGGL((k_holdout_sums<T, 0>), grid, dim3(256), 0, st, r, a, b, run, h.seed, h.lo, h.threshold, delta, delta_dev, part);
   SRMAP_HIP(p->ctx, hipGetLastError());
   if (!p->holdout_pass->reduce_and_fetch(G, st))
     return set_error(p->ctx, SRMAP_EHIP, "hold-out score: the reduction of the sums failed: %s", hipGetErrorString(hipGetLastError()));
@@ -185,6 +185,31 @@ int srmap_problem_set_holdout(srmap_problem* p, double fraction, unsigned long l
   return p->dw.set_holdout(p, h);
 }
 
+int srmap_problem_set_holdout_fold(srmap_problem* p, int folds, int fold, unsigned long long seed) {
+  if (!p) return SRMAP_EINVAL;
+  DataWeights::Holdout h;
+  if (folds != 0) {
+    if (!holdout_fold_band(folds, fold, &h.lo, &h.threshold))
+      return set_error(p->ctx, SRMAP_EINVAL, "srmap_problem_set_holdout_fold: folds must be in %d...%d and 0 <= fold < folds, or folds 0 to lift the hold-out (got folds %d, fold %d)",
+                       kHoldoutMinFolds, kHoldoutMaxFolds, folds, fold);
+    h.seed = seed;
+    h.fraction = std::ldexp((double)(h.threshold - h.lo), -kHoldoutBits);
+    h.folds = folds;
+    h.fold = fold;
+  }
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  return p->dw.set_holdout(p, h);
+}
+
+int srmap_problem_get_holdout_fold(srmap_problem* p, int* folds, int* fold, unsigned long long* seed) {
+  if (!p) return SRMAP_EINVAL;
+  const DataWeights::Holdout& h = p->dw.holdout();
+  if (folds) *folds = h.folds;
+  if (fold) *fold = h.fold;
+  if (seed) *seed = h.seed;
+  return SRMAP_OK;
+}
+
 int srmap_problem_get_holdout(srmap_problem* p, double* fraction, unsigned long long* seed, double* mask_out, double* counts) {
   if (!p) return SRMAP_EINVAL;
   const DataWeights::Holdout& h = p->dw.holdout();
@@ -198,7 +223,7 @@ int srmap_problem_get_holdout(srmap_problem* p, double* fraction, unsigned long 
       p->holdout_counts.assign(1 + (size_t)g.K, 0.0);
       for (int k = 0; k < g.K && h.threshold; ++k) {
         double c = 0.0;
-        for (size_t j = 0; j < run; ++j) c += holdout_held((uint64_t)k * run + j, h.seed, h.threshold) ? 1.0 : 0.0;
+        for (size_t j = 0; j < run; ++j) c += holdout_held_band((uint64_t)k * run + j, h.seed, h.lo, h.threshold) ? 1.0 : 0.0;
         p->holdout_counts[1 + k] = c;
         p->holdout_counts[0] += c;
       }
@@ -216,7 +241,7 @@ int srmap_problem_get_holdout(srmap_problem* p, double* fraction, unsigned long 
     const hipStream_t st = p->ctx->stream;
     int rc = dispatch_dtype(p->dtype, [&](auto t) {
       using T = decltype(t);
-      return launch_holdout_prior<T>(p, (const T*)nullptr, keep.as<T>(), n, h.seed, h.threshold, st);
+      return launch_holdout_prior<T>(p, (const T*)nullptr, keep.as<T>(), n, h.seed, h.lo, h.threshold, st);
     });
     if (rc == SRMAP_OK) rc = convert_download(p, keep.as(), mask, n, st);
     if (rc) return rc;

@@ -320,7 +320,7 @@ double* residual_scale_record(srmap_problem* p, int slot);  // device; nullptr b
 // out[i] = (m ? m[i] : 1) where observation i is kept, 0 where it is held out (holdout_dev.hpp), i < n the flat index into
 // [K][C][h][w]; enqueued on st
 template <typename T>
-int launch_holdout_prior(srmap_problem* p, const T* m, T* out, size_t n, unsigned long long seed, unsigned threshold, hipStream_t st);
+int launch_holdout_prior(srmap_problem* p, const T* m, T* out, size_t n, unsigned long long seed, unsigned lo, unsigned hi, hipStream_t st);
 void holdout_pass_release(srmap_problem* p);  // frees the score's pass; the stream that ran it has been waited for
 // ---- photometric frame model (photometric_fit.hip) ----
 // d_obs <- (d_obs_raw - bias_k) / gain_k by the parameters in force, enqueued on st (allocates d_obs when it is missing)

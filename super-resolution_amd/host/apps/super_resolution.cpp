@@ -68,6 +68,10 @@ const char kUsage[] =
       "                       <count> solves at lambda = <largest> * <ratio>^j with that share of the pixels held out, each\n"
       "                       scored on the held-out pixels; the result is the solve on all pixels at the best lambda;\n"
       "                       --regularization_parameter is then unused; --lambda_path needs --holdout_fraction)\n"
+      "                       [--holdout_folds=5] [--lambda_rule=min|one_se] [--lambda_se_factor=1] (instead of\n"
+      "                       --holdout_fraction: k-fold cross-validation, every lambda solved and scored once per fold of a\n"
+      "                       partition of the pixels into 2...32 folds; one_se, the default, takes the largest lambda whose\n"
+      "                       mean score is within <factor> standard errors over the folds of the least, min the least)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
       "                       [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
@@ -146,6 +150,9 @@ struct Options {
   unsigned long long holdout_seed;
   std::string holdout_seed_text;
   std::string lambda_path;
+  // not reference flags: the same by k-fold cross-validation (srmap_solve_lambda_path_folds); an empty text: not given
+  int holdout_folds;
+  std::string lambda_rule, lambda_se_factor_text;
   int lambda_patience;
   bool print_lambda_path;
   bool LambdaPath() const { return !lambda_path.empty(); }
@@ -222,6 +229,9 @@ Options ParseFlags(int argc, char** argv) {
   o.holdout_seed_text = flags.Str("holdout_seed", "1");
   o.holdout_seed = std::strtoull(o.holdout_seed_text.c_str(), nullptr, 10);
   o.lambda_path = flags.Str("lambda_path", "");
+  o.holdout_folds = flags.Int("holdout_folds", 0);
+  o.lambda_rule = flags.Str("lambda_rule", "");
+  o.lambda_se_factor_text = flags.Str("lambda_se_factor", "");
   o.lambda_patience = flags.Int("lambda_patience", 0);
   o.print_lambda_path = flags.Bool("print_lambda_path", false);
   o.interpolate_color = flags.Bool("interpolate_color", false);
@@ -324,13 +334,26 @@ int CheckFlags(const Options& o) {
   if (o.holdout_seed_text.empty() || o.holdout_seed_text.size() > 19 ||
       o.holdout_seed_text.find_first_not_of("0123456789") != std::string::npos)
     return Refuse("--holdout_seed is a non-negative integer of at most 19 digits.");
-  if (o.holdout_seed_text != "1" && o.holdout_fraction == 0.0) return Refuse("--holdout_seed needs --holdout_fraction.");
+  if (o.holdout_folds != 0 && o.holdout_fraction != 0.0)
+    return Refuse("--holdout_folds and --holdout_fraction exclude each other: folds partition the pixels, a fraction is one split.");
+  if (o.holdout_folds != 0 && (o.holdout_folds < srmap::kHoldoutMinFolds || o.holdout_folds > srmap::kHoldoutMaxFolds))
+    return Refuse("--holdout_folds is in 2...32.");
+  if (o.holdout_folds == 0 && (!o.lambda_rule.empty() || !o.lambda_se_factor_text.empty()))
+    return Refuse("--lambda_rule and --lambda_se_factor need --holdout_folds: one split gives no standard error over folds.");
+  if (o.holdout_folds != 0) {
+    int rule = 0;
+    if (!o.lambda_rule.empty() && !srmap::holdout_parse_rule(o.lambda_rule.c_str(), &rule)) return Refuse("--lambda_rule is min or one_se.");
+    if (!o.lambda_se_factor_text.empty() && !srmap::holdout_parse_se_factor(o.lambda_se_factor_text.c_str(), nullptr))
+      return Refuse("--lambda_se_factor is a finite number >= 0.");
+    if (!o.LambdaPath()) return Refuse("--holdout_folds needs --lambda_path.");
+  }
+  if (o.holdout_seed_text != "1" && o.holdout_fraction == 0.0 && o.holdout_folds == 0) return Refuse("--holdout_seed needs --holdout_fraction.");
   if (o.LambdaPath()) {
     double largest = 0.0, ratio = 0.0;
     int count = 0;
     if (!srmap::holdout_parse_lambda_path(o.lambda_path.c_str(), &largest, &ratio, &count))
       return Refuse("--lambda_path is <largest>:<ratio>:<count> with largest > 0, 0 < ratio < 1 and 1 <= count <= 32.");
-    if (o.holdout_fraction == 0.0) return Refuse("--lambda_path needs --holdout_fraction.");
+    if (o.holdout_fraction == 0.0 && o.holdout_folds == 0) return Refuse("--lambda_path needs --holdout_fraction.");
     if (o.lambda_patience < 0) return Refuse("--lambda_patience is >= 0.");
     if (o.refine_motion_rounds > 0 || o.photometric_rounds >= 0)
       return Refuse("--lambda_path runs plain solves: not with --refine_motion_rounds or --photometric_rounds.");
@@ -578,6 +601,33 @@ int Solve(const Options& o, const Frames& f, IRLSMapSolver* solver, ImageData* r
     std::printf("Fitted gain and bias of %d frames in %d rounds.\n", fitted.GetNumFrames(), rounds);
   } else if (o.refine_motion_rounds > 0) {
     *result = solver->SolveJoint(f.initial_estimate, rounds, refinement, &refined);
+  } else if (o.LambdaPath() && o.holdout_folds != 0) {
+    double largest = 0.0, ratio = 0.0, se_factor = 1.0;
+    int count = 0, chosen = -1, rule = SRMAP_LAMBDA_RULE_ONE_SE;
+    srmap::holdout_parse_lambda_path(o.lambda_path.c_str(), &largest, &ratio, &count);
+    if (!o.lambda_rule.empty()) srmap::holdout_parse_rule(o.lambda_rule.c_str(), &rule);
+    if (!o.lambda_se_factor_text.empty()) srmap::holdout_parse_se_factor(o.lambda_se_factor_text.c_str(), &se_factor);
+    std::vector<double> scales(count), table;
+    for (int j = 0; j < count; ++j) scales[j] = std::pow(ratio, j);
+    *result = solver->SolveLambdaPathFolds(f.initial_estimate, scales, o.holdout_folds, o.holdout_seed, rule, se_factor, o.lambda_patience,
+                                           &table, nullptr, &chosen);
+    const size_t rows = table.size() / SRMAP_LAMBDA_PATH_ROW;
+    std::vector<double> mean(rows), se(rows);
+    for (size_t j = 0; j < rows; ++j) {
+      mean[j] = table[j * SRMAP_LAMBDA_PATH_ROW + 1];
+      se[j] = table[j * SRMAP_LAMBDA_PATH_ROW + 2];
+    }
+    const int least = srmap::holdout_choose(mean.data(), static_cast<int>(rows));
+    std::printf("Lambda path, %d folds, rule %s: %zu of %d rows, chosen lambda %.9g (row %d, mean score %.9g +- %.9g; least mean at row %d).\n",
+                o.holdout_folds, rule == SRMAP_LAMBDA_RULE_ONE_SE ? "one_se" : "min", rows, count, largest * scales[chosen], chosen,
+                mean[chosen], se[chosen], least);
+    if (o.print_lambda_path)
+      for (size_t j = 0; j < rows; ++j) {
+        const double* r = table.data() + j * SRMAP_LAMBDA_PATH_ROW;
+        std::printf("  lambda %.9g: mean score %.9g +- %.9g over %.0f held-out pixels, %.0f IRLS rounds, %.0f iterations, %.0f evaluations, "
+                    "delta %.9g%s%s\n", largest * r[0], r[1], r[2], r[6], r[7], r[8], r[9], r[10],
+                    static_cast<int>(j) == least ? "  <- least mean" : "", static_cast<int>(j) == chosen ? "  <- chosen" : "");
+      }
   } else if (o.LambdaPath()) {
     double largest = 0.0, ratio = 0.0;
     int count = 0, chosen = -1;

@@ -264,6 +264,52 @@ class IRLSMapSolver : public MapSolver {
     result.FromPlanar(x, GetImageSize(), GetNumChannels());
     return result;
   }
+  // A hold-out given as fold `fold` of the partition of the observations into `folds` (2...32) folds
+  // (srmap_problem_set_holdout_fold); folds 0 lifts the hold-out.  A fold and a fraction replace each other.
+  void SetHoldoutFold(const int folds, const int fold, const unsigned long long seed = 1) {
+    srmap_host::Check(srmap_problem_set_holdout_fold(problem_.get(), folds, fold, seed), "srmap_problem_set_holdout_fold");
+  }
+  // The regularization parameters by k-fold cross-validation (srmap_solve_lambda_path_folds): per multiplier in `scales`
+  // one solve from initial_estimate and one score for every fold; rule SRMAP_LAMBDA_RULE_MIN chooses the least mean score,
+  // SRMAP_LAMBDA_RULE_ONE_SE the largest parameter whose mean is within se_factor standard errors over the folds of it.
+  // The result is the solve on all observations at the chosen parameters, which stay set; the hold-out is as it was.
+  // table (optional): rows {scale, mean, se, pooled S1, S2, S0, n, rounds, iterations, evaluations, delta}; fold_table
+  // (optional): [scale][fold] rows in SolveLambdaPath's layout; chosen (optional): the row.
+  ImageData SolveLambdaPathFolds(const ImageData& initial_estimate, const std::vector<double>& scales, const int folds = 5,
+                                 const unsigned long long seed = 1, const int rule = SRMAP_LAMBDA_RULE_ONE_SE,
+                                 const double se_factor = 1.0, const int patience = 0, std::vector<double>* table = nullptr,
+                                 std::vector<double>* fold_table = nullptr, int* chosen = nullptr) {
+    CheckGeometry(initial_estimate, "initial estimate does not match the HR geometry");
+    const srmap_irls_options o = PrepareSolve();
+    srmap_lambda_cv_options po;
+    srmap_lambda_cv_options_default(&po);
+    if (scales.empty() || scales.size() > SRMAP_LAMBDA_PATH_MAX_SCALES) srmap_host::Fail("SolveLambdaPathFolds: between 1 and 32 scales");
+    if (folds < 2 || folds > 32) srmap_host::Fail("SolveLambdaPathFolds: between 2 and 32 folds");
+    po.num_scales = static_cast<int>(scales.size());
+    for (int j = 0; j < SRMAP_LAMBDA_PATH_MAX_SCALES; ++j) po.scales[j] = j < po.num_scales ? scales[j] : 0.0;
+    po.folds = folds;
+    po.seed = seed;
+    po.rule = rule;
+    po.se_factor = se_factor;
+    po.patience = patience;
+    const std::vector<double> x0 = initial_estimate.ToPlanar();
+    std::vector<double> x(x0.size()), rows(scales.size() * SRMAP_LAMBDA_PATH_ROW), fold_rows(rows.size() * static_cast<size_t>(folds));
+    int rows_run = 0, row = -1;
+    srmap_host::Check(srmap_solve_lambda_path_folds(problem_.get(), &o, &po, x0.data(), x.data(), rows.data(), fold_rows.data(),
+                                                    &rows_run, &row, &report_),
+                      "srmap_solve_lambda_path_folds");
+    rows.resize(static_cast<size_t>(rows_run) * SRMAP_LAMBDA_PATH_ROW);
+    fold_rows.resize(rows.size() * static_cast<size_t>(folds));
+    if (table) *table = rows;
+    if (fold_table) *fold_table = fold_rows;
+    if (chosen) *chosen = row;
+    if (IsVerbose())
+      std::cout << "IRLSMapSolver: lambda path, " << folds << " folds, " << rows_run << " rows, chosen scale " << scales[row] << std::endl;
+    ReportSolve();
+    ImageData result;
+    result.FromPlanar(x, GetImageSize(), GetNumChannels());
+    return result;
+  }
 
  private:
   // solver_options as srmap_irls_options, and the solver, loss and Huber scale they name set on the problem

@@ -81,6 +81,16 @@ class LambdaPathOptions(C.Structure):
                 ("patience", C.c_int), ("final_solve", C.c_int)]
 
 
+LAMBDA_RULE_MIN, LAMBDA_RULE_ONE_SE = 0, 1  # SRMAP_LAMBDA_RULE_*
+LAMBDA_RULES = {"min": LAMBDA_RULE_MIN, "one_se": LAMBDA_RULE_ONE_SE}
+
+
+class LambdaCvOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("num_scales", C.c_int), ("scales", C.c_double * LAMBDA_PATH_MAX_SCALES),
+                ("folds", C.c_int), ("rule", C.c_int), ("seed", C.c_ulonglong), ("se_factor", C.c_double),
+                ("patience", C.c_int), ("final_solve", C.c_int)]
+
+
 class SolveReport(C.Structure):
     _fields_ = [("irls_rounds", C.c_int), ("cg_iterations", C.c_int), ("evaluations", C.c_int),
                 ("last_termination", C.c_int), ("final_cost", C.c_double), ("loop_seconds", C.c_double),
@@ -154,6 +164,8 @@ _SIGNATURES = [
     ("srmap_residual_scale_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, c_double_p]),
     ("srmap_problem_set_holdout", C.c_int, [C.c_void_p, C.c_double, C.c_ulonglong]),
     ("srmap_problem_get_holdout", C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_ulonglong), c_double_p, c_double_p]),
+    ("srmap_problem_set_holdout_fold", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_ulonglong]),
+    ("srmap_problem_get_holdout_fold", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
     ("srmap_holdout_score", C.c_int, [C.c_void_p, c_double_p, C.c_double, c_double_p, c_double_p]),
     ("srmap_holdout_score_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, c_double_p, c_double_p]),
     ("srmap_problem_set_regularizer_lambda", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
@@ -161,6 +173,9 @@ _SIGNATURES = [
     ("srmap_lambda_path_options_default", None, [C.c_void_p]),
     ("srmap_solve_lambda_path", C.c_int, [C.c_void_p, C.POINTER(IrlsOptions), C.c_void_p, c_double_p, c_double_p, c_double_p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(SolveReport)]),
+    ("srmap_lambda_cv_options_default", None, [C.c_void_p]),
+    ("srmap_solve_lambda_path_folds", C.c_int, [C.c_void_p, C.POINTER(IrlsOptions), C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(SolveReport)]),
     ("srmap_apply", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_apply_transpose", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     ("srmap_reg_values", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
@@ -780,6 +795,17 @@ class Problem:
         of (index, seed), out of the data term; 0 lifts the hold-out."""
         self.ctx.check(load().srmap_problem_set_holdout(self._h, fraction, seed))
 
+    def set_holdout_fold(self, folds, fold, seed=1):
+        """srmap_problem_set_holdout_fold: hold out fold `fold` of the partition of the observations into `folds` (2...32)
+        folds by the hash of (index, seed); folds 0 lifts the hold-out.  Replaces a fraction, and is replaced by one."""
+        self.ctx.check(load().srmap_problem_set_holdout_fold(self._h, folds, fold, seed))
+
+    def holdout_fold(self):
+        """(folds, fold, seed) of the fold in force; folds 0: none, or a fraction is set."""
+        folds, fold, seed = C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+        self.ctx.check(load().srmap_problem_get_holdout_fold(self._h, C.byref(folds), C.byref(fold), C.byref(seed)))
+        return folds.value, fold.value, seed.value
+
     def holdout(self, want_mask=True):
         """(fraction, seed, mask [K][C][h][w] of 0 / 1 or None, counts [1 + K]) of the hold-out in force; fraction 0: none."""
         fr, seed = C.c_double(0.0), C.c_ulonglong(0)
@@ -832,6 +858,39 @@ class Problem:
         self.ctx.check(load().srmap_solve_lambda_path(self._h, C.byref(o), C.byref(po), pa, out.ctypes.data_as(c_double_p),
                                                       table.ctypes.data_as(c_double_p), C.byref(rows), C.byref(chosen), C.byref(rep)))
         return out, table[:rows.value].copy(), chosen.value, rep
+
+    def solve_lambda_path_folds(self, x0, scales, folds=5, seed=1, rule="one_se", se_factor=1.0, options=None, patience=0,
+                                final_solve=True, struct_size=None):
+        """srmap_solve_lambda_path_folds: per multiplier in `scales` one solve from x0 and one score for every fold of the
+        partition into `folds`; rule "min" chooses the least mean score, "one_se" the largest lambda whose mean is within
+        se_factor standard errors (over the folds) of it.  Returns (x, table [rows_run][11] = scale, mean, se, pooled S1, S2,
+        S0, n, summed IRLS rounds, iterations, evaluations, delta used; fold_table [rows_run][folds][11] in
+        solve_lambda_path's layout; chosen; report): x and report are the solve on all observations at the chosen lambdas,
+        None without final_solve.  The hold-out in force at the call is in force on return.  struct_size overrides the
+        options' size field (tests)."""
+        a, pa = _d(x0)
+        assert a.size == self.C * self.H * self.W
+        po = LambdaCvOptions()
+        load().srmap_lambda_cv_options_default(C.byref(po))
+        sc = [float(v) for v in scales]
+        po.num_scales = len(sc)
+        for j in range(LAMBDA_PATH_MAX_SCALES):
+            po.scales[j] = sc[j] if j < len(sc) else 0.0
+        po.folds, po.seed, po.se_factor = folds, seed, se_factor
+        po.rule = LAMBDA_RULES[rule] if isinstance(rule, str) else rule
+        po.patience, po.final_solve = patience, 1 if final_solve else 0
+        if struct_size is not None:
+            po.struct_size = struct_size
+        out = np.empty((self.C, self.H, self.W)) if final_solve else None
+        nrows, nf = max(1, min(len(sc), LAMBDA_PATH_MAX_SCALES)), max(1, min(int(folds), 32))
+        table, fold_table = np.zeros((nrows, LAMBDA_PATH_ROW)), np.zeros((nrows, nf, LAMBDA_PATH_ROW))
+        rows, chosen, rep = C.c_int(0), C.c_int(-1), SolveReport()
+        o = options if options is not None else default_irls_options()
+        self.ctx.check(load().srmap_solve_lambda_path_folds(self._h, C.byref(o), C.byref(po), pa,
+                                                            out.ctypes.data_as(c_double_p) if final_solve else None,
+                                                            table.ctypes.data_as(c_double_p), fold_table.ctypes.data_as(c_double_p),
+                                                            C.byref(rows), C.byref(chosen), C.byref(rep)))
+        return out, table[:rows.value].copy(), fold_table[:rows.value].copy(), chosen.value, rep if final_solve else None
 
     def apply(self, hr, k):
         a, pa = _d(hr)
