@@ -326,10 +326,32 @@ int srmap_set_observations_device(srmap_problem* p, const void* lr_dev, void* hi
 /* MapSolver::AddRegularizer(regularizer, regularization_parameter)
  * map_solver.cpp:88-94; constructors tv_regularizer.h / btv_regularizer.cpp
  * :50-65 (range >= 1, 0 < decay <= 1).  Gradients are bug-compatible with the
- * reference.  *reg_index receives the handle. */
+ * reference.  In that reference mode the gradient of BTV with btv_range = 1 is identically
+ * zero (the differentiated window [0, R-1] holds the pixel itself only): such a regulariser adds to the cost and leaves
+ * the minimiser alone; srmap_problem_set_regularizer_gradient(.., SRMAP_REG_GRADIENT_EXACT) gives it its true gradient.
+ * *reg_index receives the handle. */
 int srmap_add_regularizer(srmap_problem* p, int kind, double lambda,
                           int btv_range, double btv_decay, int* reg_index);
 int srmap_clear_regularizers(srmap_problem* p);
+/* The gradient regulariser `reg` contributes (no reference counterpart).  The cost lambda sum w r^2, the
+ * values r and the IRLS weights 1 / max(1e-5, r) are the same in both modes; with c[q] = lambda w[q] held fixed:
+ *   REFERENCE (default)  the reference's gradients, bug for bug: BTV differentiates the window i, j in [0, R-1] although
+ *             r sums [0, R] and never takes the absolute pixel (0, 0) as a source; 3-D TV has no -sgn dz in the self term.
+ *   EXACT     the gradient of the cost.  BTV:
+ *               g[p] += 2 c[p] r[p] sum_{i,j in [0,R], p+(i,j) inside} a^(i+j) sgn(x[p] - x[p+(i,j)])
+ *                     - sum_{i,j in [0,R], (i,j) != (0,0), q = p-(i,j) inside} 2 c[q] r[q] a^(i+j) sgn(x[q] - x[p])
+ *             with sgn(0) = 0.  3-D TV: the self term is -sgn dx - sgn dy - sgn dz, the last where the next channel
+ *             exists.  2-D TV: the reference's gradient is the true one; EXACT runs the same kernels, bit for bit.
+ * srmap_eval*, srmap_reg_values_and_gradient, srmap_solve (CG, L-BFGS, split_channels), the traces, the lambda paths and
+ * srmap_problem_set_cost_rows honour the mode.  A BTV regulariser in EXACT mode is not fused into the tile kernels: the
+ * tiles keep the data term and the direct kernels add the regulariser.  While a BTV or 3-D TV regulariser is EXACT,
+ * evaluations and solves sharded over a communicator of more than one rank answer SRMAP_EUNSUPPORTED (the exact BTV
+ * gradient reaches one halo row further than the shard description promises).  An unknown mode or handle:
+ * SRMAP_EINVAL.  Waits for the evaluations in flight and re-plans as srmap_problem_set_regularizer_lambda does; the mode
+ * persists across every other setter. */
+typedef enum { SRMAP_REG_GRADIENT_REFERENCE = 0, SRMAP_REG_GRADIENT_EXACT = 1 } srmap_reg_gradient;
+int srmap_problem_set_regularizer_gradient(srmap_problem* p, int reg, int mode);
+int srmap_problem_get_regularizer_gradient(const srmap_problem* p, int reg, int* mode);
 /* The regularization_parameter of regulariser `reg` (the handle srmap_add_regularizer gave), changed in place: the kind,
  * the BTV constants and the IRLS weights stay as they are.  No reference counterpart (the reference fixes it at
  * AddRegularizer).  lambda must be finite and >= 0, the handle must exist: SRMAP_EINVAL otherwise.  Waits for the

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "reduce_dev.hpp"
+#include "reg_gradient_host.hpp"
 #include "srmap_internal.hpp"
 
 namespace srmap {
@@ -245,10 +246,13 @@ int launch_reg_weights(srmap_problem* p, const Geometry& g, const RegSpec& rs, c
 // btv_regularizer.cpp:105-166), bug-compatible: 3-D TV has no z self term; BTV
 // uses the exclusive window and skips the absolute pixel (0,0) as a source.
 // Constants c[q] = gc_scale * gc[q] (gc == nullptr means 1).
+// Exact (srmap_problem_set_regularizer_gradient): the gradient of the cost with c held fixed instead -- BTV over the
+// inclusive window with every pixel a source, 3-D TV with its -sgn dz self term.  A compile-time leg: the reference
+// instances are the code they were (profiles/r31_reg_exact_resources.txt).
 template <typename T>
 __device__ __forceinline__ T sgn(T d) { return d > T(0) ? T(1) : (d < T(0) ? T(-1) : T(0)); }
 
-template <typename T>
+template <typename T, bool Exact = false>
 __global__ __launch_bounds__(256) void k_reg_gradient_direct(
     const T* __restrict__ x, const T* __restrict__ gc, T gc_scale,
     const T* __restrict__ values, T* __restrict__ gout, int accumulate,
@@ -274,23 +278,24 @@ __global__ __launch_bounds__(256) void k_reg_gradient_direct(
     const T r0 = onfly ? reg_value_at(x, W, H, C, c, r, col, kind, range, pw) : vals[idx];
     T grad = T(0);
     if (kind == SRMAP_REG_BTV) {
+      const int wend = Exact ? range + 1 : range;  // the window differentiated: [0, R] or the reference's [0, R - 1]
       T didi = T(0);
-      for (int i = 0; i < range; ++i) {
+      for (int i = 0; i < wend; ++i) {
         const int rr = r + i;
         if (rr >= H) continue;
-        for (int j = 0; j < range; ++j) {
+        for (int j = 0; j < wend; ++j) {
           const int cc = col + j;
           if (cc >= W) continue;
           didi += (T)pw.v[i + j] * sgn(x0 - plane[(size_t)rr * W + cc]);
         }
       }
       grad += T(2) * c0 * r0 * didi;
-      for (int i = 0; i < range; ++i) {
+      for (int i = 0; i < wend; ++i) {
         const int rr = r - i;
         if (rr < 0) continue;
-        for (int j = 0; j < range; ++j) {
+        for (int j = 0; j < wend; ++j) {
           const int cc = col - j;
-          if (cc < 0 || (rr == 0 && cc == 0)) continue;
+          if (cc < 0 || (Exact ? (i == 0 && j == 0) : (rr == 0 && cc == 0))) continue;
           const size_t q = (size_t)rr * W + cc;
           const T cq = gc_scale * (gcp ? gcp[q] : T(1));
           const T didj = -sgn(plane[q] - x0) * (T)pw.v[i + j];
@@ -301,6 +306,7 @@ __global__ __launch_bounds__(256) void k_reg_gradient_direct(
       T didi = T(0);
       if (col + 1 < W) didi -= sgn(plane[idx + 1] - x0);
       if (r + 1 < H) didi -= sgn(plane[idx + W] - x0);
+      if (Exact && kind == SRMAP_REG_TV3D && c + 1 < C) didi -= sgn(plane[idx + N] - x0);
       grad += T(2) * c0 * r0 * didi;
       if (col - 1 >= 0) {
         const size_t q = idx - 1;
@@ -344,8 +350,9 @@ __device__ __forceinline__ T tv_value(const T& v, const T& d, const T& r, const 
 // tv_pixel: the gradient at the pixel x0 (returned) and its value (*r0).  x0 comes with its right, down and next-channel
 // neighbours and its constant c0 = gc_scale * weight; the left (l), upper (u) and previous-channel (p) neighbours each with
 // the down / right / next-channel neighbours of THEIR value that are not x0 itself, and their weight; then which of the six
-// neighbours exist.  What does not exist is not read (the arguments are references).
-template <typename T>
+// neighbours exist.  What does not exist is not read (the arguments are references).  ExactZ: the self term has its
+// -sgn dz (the exact 3-D TV gradient); without it the reference's.
+template <typename T, bool ExactZ = false>
 __device__ __forceinline__ T tv_pixel(const T& x0, const T& xr, const T& xd, const T& xn, T c0, T gc_scale,
                                       const T& l, const T& ld, const T& ln, const T& wl,
                                       const T& u, const T& ur, const T& un, const T& wu,
@@ -357,7 +364,8 @@ __device__ __forceinline__ T tv_pixel(const T& x0, const T& xr, const T& xd, con
   T didi = T(0);
   if (right) didi -= sgn(xr - x0);
   if (down) didi -= sgn(xd - x0);
-  grad += T(2) * c0 * val * didi;  // 3-D TV has no z self term (tv_regularizer.cpp:154-170)
+  if (ExactZ && has_next) didi -= sgn(xn - x0);
+  grad += T(2) * c0 * val * didi;  // reference: 3-D TV has no z self term (tv_regularizer.cpp:154-170)
   // the neighbour's own value has x0 as its right / down / next-channel neighbour, which always exists
   if (left) grad += T(2) * (gc_scale * wl) * tv_value(l, ld, x0, ln, down, true, has_next) * sgn(x0 - l);
   if (up) grad += T(2) * (gc_scale * wu) * tv_value(u, x0, ur, un, true, right, has_next) * sgn(x0 - u);
@@ -370,7 +378,7 @@ __device__ __forceinline__ T tv_pixel(const T& x0, const T& xr, const T& xd, con
 // array, no integer division.  A thread owns 4 consecutive pixels of a row (block = 256 columns x 4 rows) and
 // loads the row segments it needs once: rows r-1, r, r+1 of its plane, and for 3-D TV rows of the next and the
 // previous channel; the arithmetic is tv_pixel.
-template <typename T, bool D3>
+template <typename T, bool D3, bool ExactZ = false>
 __global__ __launch_bounds__(256) void k_tv_onepass(const T* __restrict__ x, const T* __restrict__ gc, T gc_scale,
                                                     T* __restrict__ gout, int accumulate,
                                                     double* __restrict__ partials, int W, int H, int C, int cr0,
@@ -443,7 +451,7 @@ __global__ __launch_bounds__(256) void k_tv_onepass(const T* __restrict__ x, con
       if (col < W) {
         const T cc0 = gc_scale * (gcp ? wc[i + 1] : one);
         T r0;
-        const T grad = tv_pixel<T>(xc[i + 1], xc[i + 2], xd[i + 1], xn[i + 1], cc0, gc_scale,
+        const T grad = tv_pixel<T, ExactZ>(xc[i + 1], xc[i + 2], xd[i + 1], xn[i + 1], cc0, gc_scale,
                                    xc[i], xd[i], xn[i], gcp ? wc[i] : one,
                                    xu[i], xu[i + 1], xnu[i], gcp ? wu[i] : one,
                                    xp[i], xpd[i], xp[i + 1], gcp ? wp[i] : one,
@@ -488,7 +496,7 @@ __device__ __forceinline__ void tv_load_plane(const T* __restrict__ pl, size_t o
   tv_load4(pl + ou + c0, R.u); R.u[4] = pl[ou + cr];
 }
 
-template <typename T>
+template <typename T, bool ExactZ = false>
 __global__ __launch_bounds__(256) void k_tv3d_march(const T* __restrict__ x, const T* __restrict__ gc, T gc_scale,
                                                     T* __restrict__ gout, int accumulate,
                                                     double* __restrict__ partials, int W, int H, int C, int cr0,
@@ -539,7 +547,7 @@ __global__ __launch_bounds__(256) void k_tv3d_march(const T* __restrict__ x, con
             const int col = c0 + i;
             const T cc0 = gc_scale * wc[i + 1];
             T r0;
-            const T grad = tv_pixel<T>(Rc.m[i + 1], Rc.m[i + 2], Rc.d[i + 1], Rn.m[i + 1], cc0, gc_scale,
+            const T grad = tv_pixel<T, ExactZ>(Rc.m[i + 1], Rc.m[i + 2], Rc.d[i + 1], Rn.m[i + 1], cc0, gc_scale,
                                        Rc.m[i], Rc.d[i], Rn.m[i], wc[i],
                                        Rc.u[i], Rc.u[i + 1], Rn.u[i], wu[i],
                                        Rp.m[i + 1], Rp.d[i + 1], Rp.m[i + 2], wprev[i],
@@ -567,11 +575,165 @@ __global__ __launch_bounds__(256) void k_tv3d_march(const T* __restrict__ x, con
   }
 }
 
+// The EXACT BTV gradient given the values, FOUR consecutive pixels per thread in gather form (the Exact leg of
+// k_reg_gradient_direct asks for 2 (R + 1)^2 scalar x loads, (R + 1)^2 value and weight loads and an integer division per
+// pixel).  A pixel p gathers
+//   its own term      2 c[p] r[p] sum_{i,j in [0,R]} a^(i+j) sgn(x[p] - x[p + (i,j)])          rows r .. r + R, this cell and the next
+//   its sources' terms  - sum_{(i,j) != (0,0)} 2 c[q] r[q] a^(i+j) sgn(x[q] - x[p]), q = p - (i,j)   rows r - R .. r, the previous cell and this
+// so a thread requests every row of its window as two 4-element vectors (row r: three) of x, and for the source rows two
+// each of the values and the weights, and forms m[q] = 2 c[q] r[q] once per element loaded -- the values come from the
+// evaluation's values pass, never recomputed: a pixel has (R + 1)^2 - 1 sources of (R + 1)^2 taps each.  Per pixel the
+// same terms in the same (i outer, j inner) order as the generic leg, masked taps as exact zeros.  No atomics, no LDS but
+// the cost reduction's four words: results are bit-identical run to run.  Requires W % 4 == 0, R <= 3 and arrays aligned
+// to four elements.  BORDER = false: the whole window lies inside the image and both neighbour cells exist (no masks, no
+// clamped addresses).
+template <typename T, int R, bool BORDER>
+__device__ __forceinline__ double btv_exact_cell(const T* __restrict__ plane, const T* __restrict__ vals,
+                                                 const T* __restrict__ gcp, T gc_scale, int W, int H, int r, int c0,
+                                                 const PowTable& pw, T (&grad)[4]) {
+  const bool pin = !BORDER || c0 >= 4, nin = !BORDER || c0 + 4 < W;  // the previous / next cell of the row exists
+  const size_t o0 = (size_t)r * W + c0;
+  const int dp = pin ? 4 : 0, dn = nin ? 4 : 0;  // a missing cell: a valid address, never used unmasked
+  T pwt[2 * R + 1];
+#pragma unroll
+  for (int k = 0; k <= 2 * R; ++k) pwt[k] = (T)pw.v[k];
+  T xr[12];  // row r: the previous cell, this one, the next
+  tv_load4(plane + o0 - dp, xr);
+  tv_load4(plane + o0, xr + 4);
+  tv_load4(plane + o0 + dn, xr + 8);
+  T didi[4] = {T(0), T(0), T(0), T(0)};
+#pragma unroll
+  for (int i = 0; i <= R; ++i) {  // the own term: rows r .. r + R
+    const bool rin = !BORDER || r + i < H;
+    T a[8];
+    if (i == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = xr[4 + e];
+    } else {
+      const T* row = plane + o0 + (rin ? (size_t)i * W : (size_t)0);
+      tv_load4(row, a);
+      tv_load4(row + dn, a + 4);
+    }
+#pragma unroll
+    for (int pc = 0; pc < 4; ++pc) {
+#pragma unroll
+      for (int j = 0; j <= R; ++j) {
+        T s = sgn(xr[4 + pc] - a[pc + j]);
+        if (BORDER) s = (rin && (pc + j < 4 || nin)) ? s : T(0);
+        didi[pc] += pwt[i + j] * s;
+      }
+    }
+  }
+  double cost = 0.0;
+#pragma unroll
+  for (int i = 0; i <= R; ++i) {  // the sources' terms: rows r .. r - R
+    const bool rin = !BORDER || r - i >= 0;
+    const size_t o = o0 - (rin ? (size_t)i * W : (size_t)0);
+    T b[8], v[8], w[8];
+    if (i == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) b[e] = xr[e];
+    } else {
+      tv_load4(plane + o - dp, b);
+      tv_load4(plane + o, b + 4);
+    }
+    tv_load4(vals + o - dp, v);
+    tv_load4(vals + o, v + 4);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = T(1);
+    if (gcp) {
+      tv_load4(gcp + o - dp, w);
+      tv_load4(gcp + o, w + 4);
+    }
+    T m[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m[e] = T(2) * (gc_scale * w[e]) * v[e];
+    if (i == 0) {
+#pragma unroll
+      for (int pc = 0; pc < 4; ++pc) {
+        grad[pc] = m[4 + pc] * didi[pc];
+        // lambda * w * r^2  (objective_irls_regularization_term.cpp:45-50)
+        cost += (double)(gc_scale * w[4 + pc]) * (double)v[4 + pc] * (double)v[4 + pc];
+      }
+    }
+#pragma unroll
+    for (int pc = 0; pc < 4; ++pc) {
+#pragma unroll
+      for (int j = 0; j <= R; ++j) {
+        if (i == 0 && j == 0) continue;
+        const int e = 4 + pc - j;
+        T t = -sgn(b[e] - xr[4 + pc]) * pwt[i + j];
+        if (BORDER) t = (rin && (e >= 4 || pin)) ? t : T(0);
+        grad[pc] += m[e] * t;
+      }
+    }
+  }
+  return cost;
+}
+
+template <typename T, int R>
+__global__ __launch_bounds__(256) void k_btv_gradient_exact4(const T* __restrict__ x, const T* __restrict__ gc, T gc_scale,
+                                                            const T* __restrict__ values, T* __restrict__ gout,
+                                                            int accumulate, double* __restrict__ partials, int W, int H,
+                                                            PowTable pw, int cr0, int cr1) {
+  __shared__ double red[4];
+  const int W4 = W >> 2;
+  const int cell = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  const size_t N = (size_t)W * H;
+  double cost = 0.0;
+  if (cell < W4 * H) {
+    const int r = cell / W4, c0 = (cell - r * W4) * 4;
+    const T* plane = x + (size_t)c * N;
+    const T* vals = values + (size_t)c * N;
+    const T* gcp = gc ? gc + (size_t)c * N : nullptr;
+    T grad[4];
+    double cst;
+    // one path per wave: only the waves that hold a row's first or last cell or one of the image's first / last R rows
+    // take the masked one
+    if (__all(c0 >= 4 && c0 + 4 < W && r >= R && r + R < H)) cst = btv_exact_cell<T, R, false>(plane, vals, gcp, gc_scale, W, H, r, c0, pw, grad);
+    else cst = btv_exact_cell<T, R, true>(plane, vals, gcp, gc_scale, W, H, r, c0, pw, grad);
+    if (gout) {
+      T* gdst = gout + (size_t)c * N + (size_t)r * W + c0;
+      T gold[4] = {T(0), T(0), T(0), T(0)};
+      if (accumulate) tv_load4(gdst, gold);
+      typedef T V4 __attribute__((ext_vector_type(4)));
+      V4 o; o.x = gold[0] + grad[0]; o.y = gold[1] + grad[1]; o.z = gold[2] + grad[2]; o.w = gold[3] + grad[3];
+      *reinterpret_cast<V4*>(gdst) = o;
+    }
+    cost = (r >= cr0 && r < cr1) ? cst : 0.0;
+  }
+  if (partials) {
+    const double s = block_sum_256(cost, red);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// the launch where k_btv_gradient_exact4 serves the call (the rule: reg_gradient_host.hpp)
+template <typename T>
+static bool launch_btv_gradient_exact4(const Geometry& geo, const RegSpec& rs, const T* x, const T* gc, T gc_scale,
+                                       const T* values, T* g, int accumulate, double* partials, int* nblocks,
+                                       hipStream_t st) {
+  if (!btv_exact4_serves(rs.range, geo.W, geo.H, sizeof(T), (uintptr_t)x, (uintptr_t)values, (uintptr_t)gc, (uintptr_t)g)) return false;
+  dim3 grid((unsigned)(((long long)(geo.W >> 2) * geo.H + 255) / 256), geo.C);
+  const PowTable pw = make_pow(rs);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, x, gc, gc_scale, values, g, accumulate, partials, geo.W, geo.H, pw,
+                       geo.cr0, geo.cr1);
+  };
+  if (rs.range == 1) go(k_btv_gradient_exact4<T, 1>);
+  else if (rs.range == 2) go(k_btv_gradient_exact4<T, 2>);
+  else go(k_btv_gradient_exact4<T, 3>);
+  if (nblocks) *nblocks = (int)(grid.x * grid.y);
+  return true;
+}
+
 template <typename T>
 int launch_reg_gradient_direct(srmap_problem* p, const Geometry& geo, const RegSpec& rs,
                                const T* x, const T* gc, double gc_scale, const T* values,
                                T* g, bool accumulate, double* partials, int* nblocks,
                                hipStream_t st) {
+  const bool exact = rs.exact();
   if (values == nullptr && rs.kind != SRMAP_REG_BTV) {  // TV kinds, one pass
     dim3 grid2((geo.W + 255) / 256, (geo.H + 3) / 4, geo.C);
     const size_t valign = 4 * sizeof(T);
@@ -582,13 +744,20 @@ int launch_reg_gradient_direct(srmap_problem* p, const Geometry& geo, const RegS
       int chunk = geo.C;
       while (chunk > 16 && per_plane * ((geo.C + chunk - 1) / chunk) < 4096) chunk = (chunk + 1) / 2;
       dim3 grid3(grid2.x, grid2.y, (geo.C + chunk - 1) / chunk);
-      hipLaunchKernelGGL(k_tv3d_march<T>, grid3, dim3(64, 4), 0, st, x, gc, (T)gc_scale, g, accumulate ? 1 : 0, partials,
-                         geo.W, geo.H, geo.C, geo.cr0, geo.cr1, geo.zlo, geo.zhi, chunk);
+      if (exact)
+        hipLaunchKernelGGL((k_tv3d_march<T, true>), grid3, dim3(64, 4), 0, st, x, gc, (T)gc_scale, g, accumulate ? 1 : 0, partials,
+                           geo.W, geo.H, geo.C, geo.cr0, geo.cr1, geo.zlo, geo.zhi, chunk);
+      else
+        hipLaunchKernelGGL(k_tv3d_march<T>, grid3, dim3(64, 4), 0, st, x, gc, (T)gc_scale, g, accumulate ? 1 : 0, partials,
+                           geo.W, geo.H, geo.C, geo.cr0, geo.cr1, geo.zlo, geo.zhi, chunk);
       if (nblocks) *nblocks = (int)(grid3.x * grid3.y * grid3.z);
       SRMAP_HIP(p->ctx, hipGetLastError());
       return SRMAP_OK;
     }
-    if (rs.kind == SRMAP_REG_TV3D)
+    if (rs.kind == SRMAP_REG_TV3D && exact)
+      hipLaunchKernelGGL((k_tv_onepass<T, true, true>), grid2, dim3(64, 4), 0, st, x, gc, (T)gc_scale, g, accumulate ? 1 : 0,
+                         partials, geo.W, geo.H, geo.C, geo.cr0, geo.cr1, geo.zlo, geo.zhi);
+    else if (rs.kind == SRMAP_REG_TV3D)
       hipLaunchKernelGGL((k_tv_onepass<T, true>), grid2, dim3(64, 4), 0, st, x, gc, (T)gc_scale, g, accumulate ? 1 : 0,
                          partials, geo.W, geo.H, geo.C, geo.cr0, geo.cr1, geo.zlo, geo.zhi);
     else
@@ -598,10 +767,22 @@ int launch_reg_gradient_direct(srmap_problem* p, const Geometry& geo, const RegS
     SRMAP_HIP(p->ctx, hipGetLastError());
     return SRMAP_OK;
   }
+  // given the values (every BTV call; the TV kinds from srmap_reg_values_and_gradient, whose view has no halo channel:
+  // the Exact leg's dz self term asks c + 1 < C)
+  if (exact && rs.kind == SRMAP_REG_BTV &&
+      launch_btv_gradient_exact4<T>(geo, rs, x, gc, (T)gc_scale, values, g, accumulate ? 1 : 0, partials, nblocks, st)) {
+    SRMAP_HIP(p->ctx, hipGetLastError());
+    return SRMAP_OK;
+  }
   dim3 grid((geo.W * geo.H + 255) / 256, geo.C);
-  hipLaunchKernelGGL(k_reg_gradient_direct<T>, grid, dim3(256), 0, st, x, gc, (T)gc_scale,
-                     values, g, accumulate ? 1 : 0, partials, geo.W, geo.H, geo.C, rs.kind,
-                     rs.range, make_pow(rs), geo.cr0, geo.cr1);
+  if (exact)
+    hipLaunchKernelGGL((k_reg_gradient_direct<T, true>), grid, dim3(256), 0, st, x, gc, (T)gc_scale,
+                       values, g, accumulate ? 1 : 0, partials, geo.W, geo.H, geo.C, rs.kind,
+                       rs.range, make_pow(rs), geo.cr0, geo.cr1);
+  else
+    hipLaunchKernelGGL(k_reg_gradient_direct<T>, grid, dim3(256), 0, st, x, gc, (T)gc_scale,
+                       values, g, accumulate ? 1 : 0, partials, geo.W, geo.H, geo.C, rs.kind,
+                       rs.range, make_pow(rs), geo.cr0, geo.cr1);
   if (nblocks) *nblocks = (int)(grid.x * grid.y);
   SRMAP_HIP(p->ctx, hipGetLastError());
   return SRMAP_OK;

@@ -250,6 +250,25 @@ int srmap_problem_get_regularizer_lambda(const srmap_problem* p, int reg, double
   return SRMAP_OK;
 }
 
+int srmap_problem_set_regularizer_gradient(srmap_problem* p, int reg, int mode) {
+  if (!p) return SRMAP_EINVAL;
+  if (reg < 0 || reg >= p->nreg) return set_error(p->ctx, SRMAP_EINVAL, "no regularizer %d (the problem has %d)", reg, p->nreg);
+  if (mode != SRMAP_REG_GRADIENT_REFERENCE && mode != SRMAP_REG_GRADIENT_EXACT)
+    return set_error(p->ctx, SRMAP_EINVAL, "unknown regularizer gradient mode %d", mode);
+  SRMAP_HIP(p->ctx, hipSetDevice(p->ctx->device));
+  if (int rc = model_drain(p)) return rc;
+  p->reg[reg].gradient = mode;  // the cost, the values and the IRLS weights stay as they are
+  model_replan(p);              // an exact BTV regulariser is not fused into the tiles (pick_fused_reg)
+  return SRMAP_OK;
+}
+
+int srmap_problem_get_regularizer_gradient(const srmap_problem* p, int reg, int* mode) {
+  if (!p || !mode) return SRMAP_EINVAL;
+  if (reg < 0 || reg >= p->nreg) return set_error(p->ctx, SRMAP_EINVAL, "no regularizer %d (the problem has %d)", reg, p->nreg);
+  *mode = p->reg[reg].gradient;
+  return SRMAP_OK;
+}
+
 int srmap_clear_regularizers(srmap_problem* p) {
   if (!p) return SRMAP_EINVAL;
   for (int r = 0; r < p->nreg; ++r) p->reg[r].weights.reset();

@@ -26,6 +26,12 @@ int refuse_sharded(srmap_problem* p, int mode, const char* what) {
   if (const char* model = p->motion.sharded_name() ? p->motion.sharded_name() : p->blur.sharded_name())
     return set_error(p->ctx, SRMAP_EUNSUPPORTED, "%s is not sharded over a communicator%s: %s", model,
                      solve ? " (only the direct family runs it)" : "", tail);
+  // an exact BTV gradient reaches R halo rows where the shard description promises R - 1; exact 3-D TV goes with it
+  for (int r = 0; r < p->nreg; ++r)
+    if (p->reg[r].exact())
+      return set_error(p->ctx, SRMAP_EUNSUPPORTED,
+                       "an exact regulariser gradient (srmap_problem_set_regularizer_gradient, regulariser %d) is not sharded over a communicator: %s",
+                       r, tail);
   return SRMAP_OK;
 }
 

@@ -44,6 +44,9 @@ struct RegSpec {
   double lambda;
   DevBuf weights;  // device [C][H][W] dtype; empty = all ones
   double pow_table[2 * kMaxBtvRange + 1];  // std::pow(decay, k), host libm
+  int gradient = SRMAP_REG_GRADIENT_REFERENCE;  // srmap_problem_set_regularizer_gradient
+  // EXACT changes what the kernels compute: BTV and 3-D TV (the reference's TV gradient is the true one already)
+  bool exact() const { return gradient == SRMAP_REG_GRADIENT_EXACT && kind != SRMAP_REG_TV; }
 };
 
 // solver line search: the evaluation's point is xk + stp * d (d = dvec, scaled by the factors of `norms` when given:

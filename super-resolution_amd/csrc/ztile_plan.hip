@@ -28,12 +28,13 @@ static bool alloc_granules(const srmap_problem* p, ZPlan* z) {
 }
 
 // the one regulariser handled in-kernel: the first active one (order of accumulation), when it is TV or BTV of range <= 3
+// in the reference's gradient mode (the tiles carry no exact BTV leg: such a regulariser goes through launch_regs_direct)
 static void pick_fused_reg(const srmap_problem* p, ZPlan* z) {
   for (int r = 0; r < p->nreg && z->regk == 0; ++r) {
     const RegSpec& rs = p->reg[r];
     if (rs.lambda <= 0) continue;
     if (rs.kind == SRMAP_REG_TV) { z->regk = 1; z->reg_index = r; }
-    else if (rs.kind == SRMAP_REG_BTV && rs.range >= 1 && rs.range <= 3) { z->regk = 2; z->regr = rs.range; z->reg_index = r; }
+    else if (rs.kind == SRMAP_REG_BTV && rs.range >= 1 && rs.range <= 3 && !rs.exact()) { z->regk = 2; z->regr = rs.range; z->reg_index = r; }
     break;
   }
 }

@@ -43,6 +43,7 @@
 #include <cstdlib>
 
 #include "holdout_host.hpp"  // csrc/: the rules of hold-out validation, plain C++
+#include "reg_gradient_host.hpp"  // csrc/: the words of --regularizer_gradient, plain C++
 
 using namespace super_resolution;
 
@@ -72,6 +73,9 @@ const char kUsage[] =
       "                       --holdout_fraction: k-fold cross-validation, every lambda solved and scored once per fold of a\n"
       "                       partition of the pixels into 2...32 folds; one_se, the default, takes the largest lambda whose\n"
       "                       mean score is within <factor> standard errors over the folds of the least, min the least)\n"
+      "                       [--regularizer_gradient=reference|exact] (reference, the default: the reference's regulariser\n"
+      "                       gradients, bug for bug -- BTV of --btv_scale_range=1 then has none at all; exact: the gradient\n"
+      "                       of the cost, srmap_problem_set_regularizer_gradient)\n"
       "                       [--affine_motion_path=<file>] (per-frame affine motion, 'a b tx c d ty' per line, HR pixels;\n"
       "                       an error together with --motion_sequence_path)\n"
       "                       [--flow_motion_path=<file>] (a dense displacement field per frame: raw little-endian float64,\n"
@@ -155,6 +159,8 @@ struct Options {
   std::string lambda_rule, lambda_se_factor_text;
   int lambda_patience;
   bool print_lambda_path;
+  // not a reference flag: the regulariser's gradient mode (srmap_problem_set_regularizer_gradient); empty: not given
+  std::string regularizer_gradient;
   bool LambdaPath() const { return !lambda_path.empty(); }
   bool interpolate_color, solve_in_pca_space;
   int num_pca_components;
@@ -234,6 +240,7 @@ Options ParseFlags(int argc, char** argv) {
   o.lambda_se_factor_text = flags.Str("lambda_se_factor", "");
   o.lambda_patience = flags.Int("lambda_patience", 0);
   o.print_lambda_path = flags.Bool("print_lambda_path", false);
+  o.regularizer_gradient = flags.Str("regularizer_gradient", "");
   o.interpolate_color = flags.Bool("interpolate_color", false);
   o.solve_in_pca_space = flags.Bool("solve_in_pca_space", false);
   o.num_pca_components = flags.Int("num_pca_components", 0);
@@ -328,6 +335,8 @@ int CheckFlags(const Options& o) {
     return Refuse("--photometric_path gives the parameters, --photometric_rounds fits them: they exclude each other.");
   if (!o.save_photometric_path.empty() && o.photometric_path.empty() && o.photometric_rounds < 0)
     return Refuse("--save_photometric_path needs --photometric_path or --photometric_rounds.");
+  if (!o.regularizer_gradient.empty() && !srmap::reg_gradient_parse(o.regularizer_gradient.c_str(), nullptr))
+    return Refuse("--regularizer_gradient is reference or exact.");
   // hold-out validation: refused here, before any GPU work
   if (o.holdout_fraction != 0.0 && srmap::holdout_threshold(o.holdout_fraction) == 0)
     return Refuse("--holdout_fraction is in (0, 0.5].");
@@ -538,6 +547,8 @@ void SetUpSolver(const Options& o, const Frames& f, IRLSMapSolver* solver) {
       regularizer = tv;
     }
     solver->AddRegularizer(regularizer, lambda);
+    int gradient_mode = 0;
+    if (srmap::reg_gradient_parse(o.regularizer_gradient.c_str(), &gradient_mode)) solver->SetRegularizerGradient(0, gradient_mode);
   }
   // --registration=flow: the field is wrong where frame 0 does not hold the content; those pixels get weight 0.  A Huber
   // solve derives its own weights and resets the buffer (include/srmap.h) -- unless the masks are the persistent prior

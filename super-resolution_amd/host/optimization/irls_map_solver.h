@@ -235,6 +235,17 @@ class IRLSMapSolver : public MapSolver {
     srmap_host::Check(srmap_problem_get_regularizer_lambda(problem_.get(), index, &lambda), "srmap_problem_get_regularizer_lambda");
     return lambda;
   }
+  // The gradient regulariser `index` contributes (srmap_problem_set_regularizer_gradient; no reference counterpart):
+  // SRMAP_REG_GRADIENT_REFERENCE, the reference's bug for bug (the default), or SRMAP_REG_GRADIENT_EXACT, the gradient of
+  // the cost.  The cost, the values and the IRLS weights are the same in both.
+  void SetRegularizerGradient(const int index, const int mode) {
+    srmap_host::Check(srmap_problem_set_regularizer_gradient(problem_.get(), index, mode), "srmap_problem_set_regularizer_gradient");
+  }
+  int GetRegularizerGradient(const int index) const {
+    int mode = 0;
+    srmap_host::Check(srmap_problem_get_regularizer_gradient(problem_.get(), index, &mode), "srmap_problem_get_regularizer_gradient");
+    return mode;
+  }
   // The regularization parameters by hold-out validation (srmap_solve_lambda_path): one solve from initial_estimate per
   // multiplier in `scales` (strictly decreasing) of every regulariser's parameter, scored on the held-out observations;
   // the result is the solve on all observations at the chosen parameters (final_solve) or the chosen row's solution.  The

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SRMAP_LIB") or os.path.join(os.path.dirname(_HERE), "
 OK, EINVAL, ENOMEM, EHIP, EUNSUPPORTED = 0, 1, 2, 3, 4
 F64, F32 = 0, 1
 REG_TV, REG_TV3D, REG_BTV = 0, 1, 2
+REG_GRADIENT_REFERENCE, REG_GRADIENT_EXACT = 0, 1  # srmap_reg_gradient
 TERM_DATA, TERM_REG, TERM_ALL = 1, 2, 3
 IMPL_AUTO, IMPL_DIRECT, IMPL_TILED = 0, 1, 2
 SOLVER_CG, SOLVER_LBFGS = 0, 1  # srmap_solver (MapSolverOptions::least_squares_solver)
@@ -170,6 +171,8 @@ _SIGNATURES = [
     ("srmap_holdout_score_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, c_double_p, c_double_p]),
     ("srmap_problem_set_regularizer_lambda", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     ("srmap_problem_get_regularizer_lambda", C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    ("srmap_problem_set_regularizer_gradient", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("srmap_problem_get_regularizer_gradient", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("srmap_lambda_path_options_default", None, [C.c_void_p]),
     ("srmap_solve_lambda_path", C.c_int, [C.c_void_p, C.POINTER(IrlsOptions), C.c_void_p, c_double_p, c_double_p, c_double_p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(SolveReport)]),
@@ -832,6 +835,16 @@ class Problem:
     def regularizer_lambda(self, reg):
         v = C.c_double(0.0)
         self.ctx.check(load().srmap_problem_get_regularizer_lambda(self._h, reg, C.byref(v)))
+        return v.value
+
+    def set_regularizer_gradient(self, reg, mode):
+        """The gradient regulariser `reg` contributes: REG_GRADIENT_REFERENCE (the reference's, bug for bug; the default) or
+        REG_GRADIENT_EXACT (the gradient of the cost).  The cost, the values and the IRLS weights are the same in both."""
+        self.ctx.check(load().srmap_problem_set_regularizer_gradient(self._h, reg, mode))
+
+    def regularizer_gradient(self, reg):
+        v = C.c_int(0)
+        self.ctx.check(load().srmap_problem_get_regularizer_gradient(self._h, reg, C.byref(v)))
         return v.value
 
     def solve_lambda_path(self, x0, scales, options=None, patience=0, final_solve=True, struct_size=None):
